@@ -91,7 +91,37 @@ def parse_args():
                          "driver's mode: that is one process per GPU under torch.distributed.run)")
     ap.add_argument("--devices", default="", help="--in-process: comma-separated device list (a device may repeat: "
                                                   "logical shards); default 0..gpus-1")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (labels, distances, counts) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write ``arrays`` (per-query results: first axis = query) as ``out_dir/<name>.npy`` in float64, or float32 when that
+    is their type already; labels and counts are integers far below 2**53, so float64 holds them exactly.  Over
+    DUMP_LIMIT_BYTES, a fixed seeded sample of the queries is written, and its row numbers as ``query_rows.npy``.
+    Returns {name: shape} of what was written."""
+    arrays = {name: np.asarray(a, dtype=np.float32 if np.asarray(a).dtype == np.float32 else np.float64)
+              for name, a in arrays.items()}
+    nq = min(a.shape[0] for a in arrays.values())
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096  # (the .npy headers: 128 B per file)
+    if total > budget:
+        keep = max(1, int(nq * budget // (total + 8 * nq)))
+        rows = np.sort(np.random.default_rng(0).choice(nq, keep, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["query_rows"] = rows.astype(np.float64)
+    path = Path(out_dir)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(path / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def in_process_main(args, json_fd) -> None:
@@ -142,9 +172,14 @@ def in_process_main(args, json_fd) -> None:
     unpipelined = time.perf_counter() - t_start
     # throughput mode: Index.search_stream -- the shard scans of wave i+1 are queued before wave i is merged (round 3)
     t_start = time.perf_counter()
-    n_waves = sum(1 for _ in index.search_stream((q_host for _ in range(args.steps)), k, "bench", args.space))
+    n_waves, last = 0, None
+    for last in index.search_stream((q_host for _ in range(args.steps)), k, "bench", args.space):
+        n_waves += 1
     elapsed = time.perf_counter() - t_start
     assert n_waves == args.steps
+    if args.dump_outputs:
+        out["outputs_dumped"] = dump_outputs(args.dump_outputs, {"labels": last.labels, "scores": last.scores,
+                                                                 "counts": last.counts})
     out.update({"value": round(g * batch * args.steps / elapsed, 1), "ms_per_step": round(elapsed / args.steps * 1e3, 3),
                 "ms_per_step_unpipelined_search_many": round(unpipelined / args.steps * 1e3, 3),
                 "whole_corpus_qps": round(batch * args.steps / elapsed, 1),
@@ -544,6 +579,13 @@ def main() -> None:
     barrier()
     elapsed = time.perf_counter() - t_start
     st = eng.last_stats()  # accumulated over the K steps (HIP events of every scan launch)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before the sustained loops below overwrite the result buffers)
+        if world == 1:
+            dumped = dump_outputs(args.dump_outputs, {"labels": lab.cpu().numpy(), "distances": dst.cpu().numpy(),
+                                                      "distances_f64": d64.cpu().numpy(), "counts": cnt.cpu().numpy()})
+        else:
+            dumped = dump_outputs(args.dump_outputs, dict(zip(("labels", "distances", "counts"), last)))
     scan_ms, scan_launches, rows_scanned = st["scan_ms"], st["scan_launches"], st["rows_scanned"]
     rescored, fallbacks = st["candidates_rescored"], st["fallback_queries"]
     # ---- sustained rate (N = 1): the K timed steps above are a 40 ms burst on a power-limited kernel; a server gets the
@@ -692,6 +734,8 @@ def main() -> None:
         "parity_gate": verify,
         "load_s": round(load_s, 1),
     }
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
 
     # ---- CPU exact-scan baseline (rank 0, N=1): this repo's NumPy/OpenBLAS scan on a bounded sample
     if world == 1 and not args.no_cpu_baseline:

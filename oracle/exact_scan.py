@@ -73,7 +73,25 @@ def exact_distances(queries, rows, space: str) -> np.ndarray:
                 out[:, s:s + xc.shape[0]] = 1.0 - dots * qinv[:, None] * xinv[None, :]
             else:
                 out[:, s:s + xc.shape[0]] = 1.0 - dots
+    # Identical rows share the distance of their first occurrence.  A BLAS product's last bit depends on where a row sits
+    # (kernel, tile and thread split vary with the CPU, the thread count and the chunk's shape), and exact duplicates must
+    # tie exactly so that the label alone orders them.
+    dup, first = _repeated_rows(x)
+    if dup.size:
+        out[:, dup] = out[:, first]
     return out
+
+
+def _repeated_rows(x: np.ndarray):
+    """(indices of the rows that repeat an earlier row, index of that earlier row's first occurrence)."""
+    n = x.shape[0]
+    if n < 2 or x.shape[1] == 0:  # (zero-width rows: every distance is the same already)
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    v = x.view(np.dtype((np.void, x.dtype.itemsize * x.shape[1])))[:, 0]
+    _, first, inv = np.unique(v, return_index=True, return_inverse=True)
+    rep = first[inv.reshape(-1)]
+    dup = np.nonzero(rep != np.arange(n))[0]
+    return dup, rep[dup]
 
 
 def _rank(dist_row: np.ndarray, labels: np.ndarray) -> np.ndarray:

@@ -57,6 +57,36 @@ def test_pmc_traffic_file_matches_the_kernel_sources_in_the_tree():
     assert pmc["traffic_bytes_per_launch_avg"] > 0
 
 
+def test_dump_outputs_writes_float_arrays_exactly_and_samples_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+
+    rng = np.random.default_rng(3)
+    arrays = {"labels": rng.integers(-1, 80_000_000, (300, 10)), "distances": rng.random((300, 10), dtype=np.float32),
+              "distances_f64": rng.random((300, 10)), "counts": np.full(300, 10, np.int32)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert shapes == {name: list(a.shape) for name, a in arrays.items()}
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == (np.float32 if a.dtype == np.float32 else np.float64) and np.array_equal(got, a)
+    # over the size limit: the same seeded sample of queries in every file, its row numbers beside them
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10_000)
+    for out in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / out), arrays)
+    rows = np.load(tmp_path / "b" / "query_rows.npy").astype(np.int64)
+    assert 0 < rows.size < 300 and np.array_equal(rows, np.load(tmp_path / "c" / "query_rows.npy"))
+    assert sum((tmp_path / "b" / f"{name}.npy").stat().st_size for name in list(arrays) + ["query_rows"]) <= 10_000
+    for name, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f"{name}.npy"), a[rows])
+
+
+def test_steps_below_one_are_refused():
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, timeout=120)
+    assert r.returncode == 2 and b"--steps" in r.stderr and r.stdout.strip() == b""
+
+
 # ---- `python bench.py --gpus N` must run N ranks or fail: the launch decision, without a GPU
 class _Args:
     def __init__(self, gpus, in_process=False):

@@ -33,6 +33,23 @@ def test_bare_gpus_2_starts_two_ranks_and_passes_the_sharded_gate():
     assert d["value"] > 0 and abs(d["value"] - 2 * 1024 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01
 
 
+def test_dump_outputs_of_two_identical_runs_are_identical(tmp_path):
+    """--dump-outputs writes the last timed wave's results; the same arguments give the same inputs, hence the same arrays."""
+    import numpy as np
+
+    args = ["--rows-per-gpu", "300000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
+            "--sustained-seconds", "0"]
+    lines = [_run(args + ["--dump-outputs", str(tmp_path / run)]) for run in ("a", "b")]
+    names = {"labels": [256, 10], "distances": [256, 10], "distances_f64": [256, 10], "counts": [256]}
+    for d in lines:
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["outputs_dumped"] == names
+    for name in names:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == (np.float32 if name == "distances" else np.float64) and np.array_equal(a, b), name
+    labels, counts = np.load(tmp_path / "a" / "labels.npy"), np.load(tmp_path / "a" / "counts.npy")
+    assert (counts == 10).all() and (labels >= 0).all() and (labels < 300000).all()
+
+
 def test_one_gpu_line_has_the_contract_keys_on_a_small_shard():
     d = _run(["--rows-per-gpu", "400000", "--steps", "3", "--warmup", "1", "--no-extras", "--cpu-sample-rows", "100000"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",

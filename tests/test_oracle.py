@@ -40,6 +40,22 @@ def test_ties_break_by_ascending_label_and_tombstones_are_skipped():
     assert np.isinf(dist[0, 2:]).all()
 
 
+@pytest.mark.parametrize("space", exact_scan.SPACES)
+def test_identical_rows_tie_wherever_they_sit(space):
+    # one row repeated in a full chunk and in a 3-row last chunk: BLAS computes those positions with different kernels
+    n, d = exact_scan._CHUNK_ROWS + 3, 128
+    rng = np.random.default_rng(5)
+    rows = rng.standard_normal((n, d), dtype=np.float32)
+    twins = [1, n // 2, n - 1]
+    rows[twins] = rows[1]
+    qs = rng.standard_normal((64, d), dtype=np.float32)
+    qs[0] = rows[1]
+    dist = exact_scan.exact_distances(qs, rows, space)
+    assert all(np.array_equal(dist[:, 1], dist[:, t]) for t in twins)
+    labels, _, _ = exact_scan.knn(qs[:1], rows, 3, space)
+    assert labels.tolist() == [twins]
+
+
 def test_zero_vector_follows_hnswlib_normalisation():
     # x / (|x| + 1e-30): a zero row normalises to zero, similarity 0, distance 1
     rows = np.array([[0, 0], [1, 0], [-1, 0]], np.float32)
