@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MLVDB_ABI_VERSION 6
+#define MLVDB_ABI_VERSION 7
 
 /* status codes */
 #define MLVDB_OK 0

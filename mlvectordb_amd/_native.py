@@ -18,7 +18,7 @@ SPACE_CODES = {"l2": 0, "cosine": 1, "ip": 2}
 STRATEGY_CODES = {"auto": 0, "exact": 1, "filter": 2}
 MAX_TOPK = 64
 MAX_TOPK_PAGED = 16384
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class Stats(C.Structure):
@@ -68,6 +68,27 @@ SIGNATURES = {
     "mlvdb_layout_ld": (C.c_int32, [C.c_int32]),
 }
 
+# include/mlvdb_where.h: metadata filters on the device (bound in their own table: SIGNATURES mirrors mlvdb_hip.h alone)
+ATTR_INT64 = 1
+ATTR_FLOAT64 = 2
+ATTR_CODES = {"int64": ATTR_INT64, "float64": ATTR_FLOAT64}
+
+
+class Where(C.Structure):
+    _fields_ = [("ops", C.c_void_p), ("n_ops", C.c_int32), ("set", C.c_void_p), ("n_set", C.c_int64)]
+
+
+WHERE_SIGNATURES = {
+    "mlvdb_attr_define": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "mlvdb_attr_set": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P]),
+    "mlvdb_attr_get": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P]),
+    "mlvdb_where_count": (C.c_int, [_P, C.POINTER(Where), C.POINTER(C.c_int64)]),
+    "mlvdb_where_labels": (C.c_int, [_P, C.POINTER(Where), _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "mlvdb_search_batch_where": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(Where), _P, _P, _P, _P]),
+    "mlvdb_range_batch_packed_where": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int64, C.c_int64, C.POINTER(Where),
+                                                 _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -96,7 +117,7 @@ def load() -> C.CDLL:
             f"`python -c 'import __graft_entry__ as g; g.build()'` or `make -C mlvectordb_amd/csrc`. "
             f"There is no CPU fallback for the search path.")
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -105,6 +105,12 @@ struct mlvdb_index {
     bool mask_active = false;  // h->rn is a masked copy (mlvdb_search_batch_filtered)
     bool mask_pairs_ready = false;  // ... and rp8_masked holds the masked copy of the int8 shadow's row pairs
     DevBuf rp8_masked;
+    // metadata filters (mlvdb_where.h): typed attribute columns of `capacity` values each (absent-filled beyond the rows), and
+    // the validated program of the current call (host copy kept until the call's stream has consumed it) + its match counter
+    int32_t attr_type[MLVDB_MAX_ATTRS] = {};  // MLVDB_ATTR_*, 0 = not defined
+    int64_t* attr_col[MLVDB_MAX_ATTRS] = {};  // nullptr while capacity == 0
+    std::vector<WhereOp> where_ops;
+    DevBuf where_prog, where_cnt;
     // fp16 row-major shadow for the mid bounds (kernels_refine.hip): built lazily by the first range query / top_k > 64 search
     DevBuf x16, s16, rowerr16, picks, npicks;
     int64_t l2_rows = 0;      // rows [0, l2_rows) of the fp16 shadow are current (0 after compact / reset / regrowth)
@@ -188,6 +194,46 @@ const TuningField* find_tuning_field(const char* key, size_t len) {
     return nullptr;
 }
 
+// ---- attribute columns (mlvdb_where.h): the absent sentinel of a column type, and new column buffers for a capacity change
+int64_t attr_absent(int32_t type) { return type == MLVDB_ATTR_INT64 ? INT64_MIN : (int64_t)0x7ff8000000000000ll; }
+
+void attr_release(int64_t* (&cols)[MLVDB_MAX_ATTRS]) {
+    for (int64_t*& c : cols) {
+        if (c) (void)hipFree(c);
+        c = nullptr;
+    }
+}
+
+// ncol[a] = a fresh column of `cap` values for every defined attribute: rows [0, keep) copied from the current column
+// (old_of_new == nullptr: regrowth) or gathered through old_of_new (compaction), the rest absent.  Enqueued on h->stream;
+// the caller swaps them in (attr_commit) after the stream has drained, and releases them if anything else fails first.
+int attr_alloc(mlvdb_index* h, int64_t cap, int64_t keep, const int32_t* old_of_new, int64_t* (&ncol)[MLVDB_MAX_ATTRS]) {
+    for (int64_t*& c : ncol) c = nullptr;
+    for (int a = 0; a < MLVDB_MAX_ATTRS; ++a) {
+        if (!h->attr_type[a] || cap == 0) continue;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ncol[a]), (size_t)cap * sizeof(int64_t));
+        const bool copy = keep > 0 && h->attr_col[a];
+        if (e == hipSuccess) e = launch_attr_fill(ncol[a], attr_absent(h->attr_type[a]), copy ? keep : 0, cap - (copy ? keep : 0), h->stream);
+        if (e == hipSuccess && copy)
+            e = old_of_new ? launch_attr_gather(h->attr_col[a], ncol[a], old_of_new, keep, h->stream)
+                           : hipMemcpyAsync(ncol[a], h->attr_col[a], (size_t)keep * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream);
+        if (e != hipSuccess) {
+            attr_release(ncol);
+            return fail(h, e == hipErrorOutOfMemory ? MLVDB_ERR_OUT_OF_MEMORY : MLVDB_ERR_HIP, "attribute columns", e);
+        }
+    }
+    return MLVDB_OK;
+}
+
+void attr_commit(mlvdb_index* h, int64_t* (&ncol)[MLVDB_MAX_ATTRS]) {
+    for (int a = 0; a < MLVDB_MAX_ATTRS; ++a) {
+        if (!h->attr_type[a]) continue;
+        if (h->attr_col[a]) (void)hipFree(h->attr_col[a]);
+        h->attr_col[a] = ncol[a];
+        ncol[a] = nullptr;
+    }
+}
+
 int reserve_rows(mlvdb_index* h, int64_t rows) {
     if (!h->rowerr.p) {  // largest relative bf16 rounding error of any row appended so far (0 = no rows)
         HIP_TRY(h, h->rowerr.ensure(sizeof(unsigned int)));
@@ -208,6 +254,13 @@ int reserve_rows(mlvdb_index* h, int64_t rows) {
         if (nrn) (void)hipFree(nrn);
         return fail(h, MLVDB_ERR_OUT_OF_MEMORY, "hipMalloc(row norms / bf16 shadow)", e);
     }
+    int64_t* ncol[MLVDB_MAX_ATTRS];
+    if (int rc = attr_alloc(h, cap, h->total, nullptr, ncol)) {  // the attribute columns grow with the rows
+        (void)hipFree(nX);
+        (void)hipFree(nrn);
+        if (nXb) (void)hipFree(nXb);
+        return rc;
+    }
     const size_t used_floats = (size_t)((h->total + 15) / 16) * 16 * h->ld;
     HIP_TRY(h, hipMemsetAsync(nX + used_floats, 0, ((size_t)cap * h->ld - used_floats) * sizeof(float), h->stream));
     HIP_TRY(h, hipMemsetAsync(nrn, 0xFF, (size_t)cap * sizeof(float), h->stream));  // 0xFFFFFFFF = NaN
@@ -222,6 +275,7 @@ int reserve_rows(mlvdb_index* h, int64_t rows) {
         HIP_TRY(h, hipMemcpyAsync(nrn, h->rn, (size_t)h->total * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    attr_commit(h, ncol);
     if (h->X) (void)hipFree(h->X);
     if (h->rn) (void)hipFree(h->rn);
     if (h->Xb) (void)hipFree(h->Xb);
@@ -1221,6 +1275,9 @@ int mlvdb_index_destroy(mlvdb_index* h) {
                       &h->counters, &h->labels_in, &h->page_lab, &h->page_dist, &h->page_cnt, &h->page_d64, &h->cur_d,
                       &h->cur_l})
         b->release();
+    attr_release(h->attr_col);
+    h->where_prog.release();
+    h->where_cnt.release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
     h->pin_out.release();
@@ -1350,10 +1407,19 @@ int mlvdb_index_compact(mlvdb_index* h, int64_t* old_labels, int64_t capacity, i
     HIP_TRY(h, hipMemsetAsync(nrn, 0xFF, (size_t)cap * sizeof(float), s));  // NaN = not a row
     if (nXb) HIP_TRY(h, hipMemsetAsync(nXb, 0, (size_t)cap * h->ld * 2, s));
     HIP_TRY(h, launch_compact_rows(h->X, nX, h->Xb, nXb, h->rn, nrn, old_of_new, want, h->ld, s));
+    int64_t* ncol[MLVDB_MAX_ATTRS];
+    if (int rc2 = attr_alloc(h, cap, want, old_of_new, ncol)) {  // the attribute columns move with their rows
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(nX);
+        (void)hipFree(nrn);
+        if (nXb) (void)hipFree(nXb);
+        return rc2;
+    }
     std::vector<int32_t> host_map((size_t)want);
     if (want > 0)
         HIP_TRY(h, hipMemcpyAsync(host_map.data(), old_of_new, (size_t)want * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
+    attr_commit(h, ncol);
     for (int64_t i = 0; i < want; ++i) old_labels[i] = host_map[(size_t)i];
     (void)hipFree(h->X);
     (void)hipFree(h->rn);
@@ -1388,6 +1454,8 @@ int mlvdb_index_reset(mlvdb_index* h, int32_t space) {
         HIP_TRY(h, hipMemsetAsync(h->X, 0, (size_t)h->capacity * h->ld * sizeof(float), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->rn, 0xFF, (size_t)h->capacity * sizeof(float), h->stream));
         if (h->Xb) HIP_TRY(h, hipMemsetAsync(h->Xb, 0, (size_t)h->capacity * h->ld * 2, h->stream));
+        for (int a = 0; a < MLVDB_MAX_ATTRS; ++a)  // attribute values go, their definitions stay
+            if (h->attr_col[a]) HIP_TRY(h, launch_attr_fill(h->attr_col[a], attr_absent(h->attr_type[a]), 0, h->capacity, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     if (h->rowerr.p) HIP_TRY(h, hipMemsetAsync(h->rowerr.p, 0, sizeof(unsigned int), h->stream));
@@ -1623,21 +1691,20 @@ int search_host(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int
 }
 }  // namespace
 
-int mlvdb_search_batch_ex(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const uint8_t* row_mask,
-                          int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if (!row_mask || h->total == 0) return search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64);
-    HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
+extern "C++" {
+namespace {
+// A filtered call: h->row_mask holds its row mask (h->total bytes, on the device).  For the duration of `call` the index's
+// norms -- and, when the int8 shadow serves the call, its row pairs -- are swapped for masked copies, so a masked-out row
+// looks tombstoned to every kernel the call reaches (seeding, bounds, mid prune, rescoring, exact and paged fallbacks).
+template <class F>
+int with_row_mask(mlvdb_index* h, int64_t nq, F&& call) {
     HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
-    HIP_TRY(h, hipMemcpyAsync(h->row_mask.p, row_mask, (size_t)h->total, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, h->stream));
     // the int8 shadow serves masked searches too: bring it up to date with the index's own norms, then mask a copy of its
     // row pairs (8 bytes per row) exactly like the norms
     h->mask_pairs_ready = false;
     if (i8_eligible(h) && h->strategy != MLVDB_STRATEGY_EXACT && use_filter(h, nq, true)) {  // (not for a call the exact scan takes)
-        rc = update_i8_shadow(h, h->stream);
+        int rc = update_i8_shadow(h, h->stream);
         if (rc) return rc;
         HIP_TRY(h, h->rp8_masked.ensure((size_t)h->capacity * (h->space == kSpaceL2 ? 3 : 2) * sizeof(float)));
         HIP_TRY(h, launch_mask_pairs(h->rp8.as<float>(), h->row_mask.as<uint8_t>(), h->rp8_masked.as<float>(), h->total,
@@ -1649,11 +1716,24 @@ int mlvdb_search_batch_ex(mlvdb_index* h, const float* queries, int64_t nq, int3
     float* const all_rows = h->rn;  // every kernel of the call reads the masked norms instead
     h->rn = h->rn_masked.as<float>();
     h->mask_active = true;
-    rc = search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64);
+    const int rc = call();
     h->rn = all_rows;
     h->mask_active = false;
     h->mask_pairs_ready = false;
     return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_ex(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const uint8_t* row_mask,
+                          int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!row_mask || h->total == 0) return search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64);
+    HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
+    HIP_TRY(h, hipMemcpyAsync(h->row_mask.p, row_mask, (size_t)h->total, hipMemcpyHostToDevice, h->stream));
+    return with_row_mask(h, nq, [&]() { return search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64); });
     });
 }
 
@@ -2048,6 +2128,204 @@ int mlvdb_index_last_stats(mlvdb_index* h, mlvdb_stats* out) {
     h->stats.strategy_used = strategy;
     h->scan_events_used = 0;
     return MLVDB_OK;
+    });
+}
+
+namespace {
+// ---- metadata filters (mlvdb_where.h)
+int attr_check(mlvdb_index* h, int32_t attr) {
+    if (attr < 0 || attr >= MLVDB_MAX_ATTRS) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute index out of range");
+    if (!h->attr_type[attr]) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute not defined");
+    return MLVDB_OK;
+}
+
+// Host validation of a program (stack depth >= 1 throughout and exactly 1 at the end, defined attributes, ops valid for their
+// column's type, set ranges inside the table and sorted) -> h->where_ops, the form the kernel reads.  Nothing is launched for a
+// program refused here.
+int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
+    if (!w) return fail(h, MLVDB_ERR_INVALID_ARG, "where is null");
+    if (w->n_ops < 1 || w->n_ops > MLVDB_WHERE_MAX_OPS || !w->ops)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a program holds 1..MLVDB_WHERE_MAX_OPS ops");
+    if (w->n_set < 0 || (w->n_set > 0 && !w->set)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad set table");
+    h->where_ops.resize((size_t)w->n_ops);
+    int depth = 0;
+    for (int32_t i = 0; i < w->n_ops; ++i) {
+        const mlvdb_where_op& o = w->ops[i];
+        WhereOp& d = h->where_ops[(size_t)i];
+        d = WhereOp{o.op, 0, o.a, o.b, nullptr};
+        switch (o.op) {
+            case MLVDB_WHERE_AND:
+            case MLVDB_WHERE_OR:
+                if (depth < 2) return fail(h, MLVDB_ERR_INVALID_ARG, "AND / OR needs two operands on the stack");
+                --depth;
+                continue;
+            case MLVDB_WHERE_NOT:
+                if (depth < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "NOT needs an operand on the stack");
+                continue;
+            case MLVDB_WHERE_TRUE:
+                break;
+            case MLVDB_WHERE_EQ: case MLVDB_WHERE_NE: case MLVDB_WHERE_LT: case MLVDB_WHERE_LE:
+            case MLVDB_WHERE_GT: case MLVDB_WHERE_GE: case MLVDB_WHERE_IN: case MLVDB_WHERE_EXISTS:
+                if (int rc = attr_check(h, o.attr)) return rc;
+                d.type = h->attr_type[o.attr];
+                d.col = h->attr_col[o.attr];
+                if (o.op == MLVDB_WHERE_IN) {
+                    if (d.type != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "IN needs an int64 column");
+                    if (o.a < 0 || o.b < 0 || o.a > w->n_set || o.b > w->n_set - o.a)
+                        return fail(h, MLVDB_ERR_INVALID_ARG, "IN: set range outside the set table");
+                    for (int64_t j = o.a + 1; j < o.a + o.b; ++j)
+                        if (w->set[j - 1] > w->set[j]) return fail(h, MLVDB_ERR_INVALID_ARG, "IN: set range not sorted ascending");
+                }
+                break;
+            default:
+                return fail(h, MLVDB_ERR_INVALID_ARG, "unknown where op");
+        }
+        if (++depth > MLVDB_WHERE_MAX_DEPTH) return fail(h, MLVDB_ERR_INVALID_ARG, "program deeper than MLVDB_WHERE_MAX_DEPTH");
+    }
+    if (depth != 1) return fail(h, MLVDB_ERR_INVALID_ARG, "a program must leave exactly one value on the stack");
+    return MLVDB_OK;
+}
+
+// Validate, upload and evaluate a program into h->row_mask (live matching rows); matches != nullptr: also wait for their count.
+int where_run(mlvdb_index* h, const mlvdb_where* w, int64_t* matches) {
+    if (int rc = where_prepare(h, w)) return rc;
+    if (matches) *matches = 0;
+    if (h->total == 0) return MLVDB_OK;
+    hipStream_t s = h->stream;
+    const size_t pbytes = h->where_ops.size() * sizeof(WhereOp), sbytes = (size_t)w->n_set * sizeof(int64_t);
+    HIP_TRY(h, h->where_prog.ensure(pbytes + sbytes + sizeof(int64_t)));
+    HIP_TRY(h, h->where_cnt.ensure(sizeof(unsigned long long)));
+    HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
+    HIP_TRY(h, hipMemcpyAsync(h->where_prog.p, h->where_ops.data(), pbytes, hipMemcpyHostToDevice, s));
+    const int64_t* set_d = reinterpret_cast<const int64_t*>(h->where_prog.as<char>() + pbytes);
+    if (sbytes) HIP_TRY(h, hipMemcpyAsync(h->where_prog.as<char>() + pbytes, w->set, sbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(h->where_cnt.p, 0, sizeof(unsigned long long), s));
+    HIP_TRY(h, launch_where_eval(h->where_prog.as<WhereOp>(), w->n_ops, set_d, h->rn, h->total, h->row_mask.as<uint8_t>(),
+                                 h->where_cnt.as<unsigned long long>(), s));
+    if (matches) {
+        unsigned long long n = 0;
+        HIP_TRY(h, hipMemcpyAsync(&n, h->where_cnt.p, sizeof n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        *matches = (int64_t)n;
+    }
+    return MLVDB_OK;
+}
+}  // namespace
+
+int mlvdb_attr_define(mlvdb_index* h, int32_t attr, int32_t type) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (attr < 0 || attr >= MLVDB_MAX_ATTRS) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute index out of range");
+    if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown attribute type");
+    if (h->attr_type[attr]) {
+        if (h->attr_type[attr] != type) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute already defined with another type");
+        return MLVDB_OK;
+    }
+    if (h->capacity > 0) {
+        int64_t* col = nullptr;
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&col), (size_t)h->capacity * sizeof(int64_t)));
+        hipError_t e = launch_attr_fill(col, attr_absent(type), 0, h->capacity, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(col);
+            return fail(h, MLVDB_ERR_HIP, "attribute column fill", e);
+        }
+        h->attr_col[attr] = col;
+    }
+    h->attr_type[attr] = type;
+    return MLVDB_OK;
+    });
+}
+
+int mlvdb_attr_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const void* values) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((rc = attr_check(h, attr))) return rc;
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first || (n > 0 && !values))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (n == 0) return MLVDB_OK;
+    // (the sentinels are values like any other here: INT64_MIN / NaN written to a row make it absent)
+    HIP_TRY(h, hipMemcpyAsync(h->attr_col[attr] + first, values, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MLVDB_OK;
+    });
+}
+
+int mlvdb_attr_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, void* out_values) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((rc = attr_check(h, attr))) return rc;
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first || (n > 0 && !out_values))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (n == 0) return MLVDB_OK;
+    HIP_TRY(h, hipMemcpyAsync(out_values, h->attr_col[attr] + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MLVDB_OK;
+    });
+}
+
+int mlvdb_where_count(mlvdb_index* h, const mlvdb_where* where, int64_t* matches) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!matches) return fail(h, MLVDB_ERR_INVALID_ARG, "matches is null");
+    return where_run(h, where, matches);
+    });
+}
+
+int mlvdb_where_labels(mlvdb_index* h, const mlvdb_where* where, int64_t* out_labels, int64_t capacity, int64_t* matches) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!matches || capacity < 0 || (capacity > 0 && !out_labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
+    rc = where_run(h, where, matches);
+    if (rc || *matches == 0 || capacity == 0) return rc;
+    // the matching rows' labels in ascending order: the compaction map of the masked norms (NaN = tombstoned or no match)
+    hipStream_t s = h->stream;
+    const int64_t nblocks = (h->total + 1023) / 1024;
+    HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
+    HIP_TRY(h, h->partial.ensure((size_t)nblocks * sizeof(uint32_t) + 64));
+    HIP_TRY(h, h->labels_in.ensure((size_t)*matches * sizeof(int32_t)));
+    HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, s));
+    HIP_TRY(h, launch_compact_map(h->rn_masked.as<float>(), h->total, h->partial.as<uint32_t>(),
+                                  h->where_cnt.as<unsigned long long>(), h->labels_in.as<int32_t>(), s));
+    const int64_t n = std::min(capacity, *matches);
+    std::vector<int32_t> host((size_t)n);
+    HIP_TRY(h, hipMemcpyAsync(host.data(), h->labels_in.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (int64_t i = 0; i < n; ++i) out_labels[i] = host[(size_t)i];
+    return MLVDB_OK;
+    });
+}
+
+int mlvdb_search_batch_where(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const mlvdb_where* where,
+                             int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy
+    if (rc) return rc;
+    if (h->total == 0) return search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64);
+    return with_row_mask(h, nq, [&]() { return search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64); });
+    });
+}
+
+int mlvdb_range_batch_packed_where(mlvdb_index* h, const float* queries, int64_t nq, float radius, int64_t capacity,
+                                   int64_t total_capacity, const mlvdb_where* where, int64_t* out_labels, float* out_dist,
+                                   int64_t* out_offsets, int64_t* out_counts) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    rc = where_run(h, where, nullptr);
+    if (rc) return rc;
+    auto call = [&]() {
+        return range_batch_impl(h, queries, nq, radius, capacity, out_labels, out_dist, out_counts, out_offsets, total_capacity, true);
+    };
+    if (h->total == 0) return call();
+    return with_row_mask(h, nq, call);
     });
 }
 

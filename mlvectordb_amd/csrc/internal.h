@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/mlvdb_hip.h"
+#include "../../include/mlvdb_where.h"
 #include "layout.h"
 #include "wave_topk.h"
 
@@ -327,5 +328,21 @@ hipError_t launch_bigk_select(const FilterArgs& a, int32_t want, int32_t forced_
                               int32_t picks_cap, hipStream_t s);
 // k > 0: threshold from the k-th largest mid lower bound, then prune; k == 0: prune only (range passes)
 hipError_t launch_bigk_thr_prune(const FilterArgs& a, const MidArgs& m, int32_t k, int32_t forced_cnt, hipStream_t s);
+
+// ---------------------------------------------------------------- metadata filters (kernels_where.hip)
+constexpr int kWhereMaxOps = MLVDB_WHERE_MAX_OPS;
+// One op of a validated program as the device reads it: the column resolved to its pointer and type on the host
+// (no per-row lookup of the attribute table, no dynamic indexing of kernel arguments)
+struct WhereOp {
+    int32_t op;
+    int32_t type;      // MLVDB_ATTR_* of the column (0 for TRUE / AND / OR / NOT)
+    int64_t a, b;
+    const void* col;   // the column's capacity values (int64 or float64 bits)
+};
+// mask[i] = row i is live and matches, for i < total; *matches += their count
+hipError_t launch_where_eval(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, int64_t total,
+                             uint8_t* mask, unsigned long long* matches, hipStream_t s);
+hipError_t launch_attr_fill(int64_t* col, int64_t value, int64_t first, int64_t n, hipStream_t s);
+hipError_t launch_attr_gather(const int64_t* col, int64_t* ncol, const int32_t* old_of_new, int64_t live, hipStream_t s);
 
 }  // namespace mlvdb

@@ -195,17 +195,59 @@ class HipScanEngine:
                                                    labels.shape[1], d64.ctypes.data, d32.ctypes.data), "pair_distances")
         return d64, d32
 
-    def search64(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None):
-        """kNN; ``mask`` (optional, one byte per row, non-zero = allowed) restricts the search to those rows.
+    # -- metadata filters (include/mlvdb_where.h) ------------------------------------
+    def define_attr(self, attr: int, kind: str) -> None:
+        """Column ``attr`` (0..15) of type "int64" (absent = INT64_MIN) or "float64" (absent = NaN), every row absent."""
+        self._check(self._lib.mlvdb_attr_define(self._h, int(attr), _native.ATTR_CODES[kind]), "attr_define")
+
+    def set_attr(self, attr: int, first: int, values: np.ndarray) -> None:
+        """Values of rows first..first+len(values)-1 (int64 or float64 by the column's type)."""
+        values = np.ascontiguousarray(values)
+        if values.dtype not in (np.int64, np.float64):
+            raise RuntimeError(f"attribute values must be int64 or float64, got {values.dtype}")
+        self._check(self._lib.mlvdb_attr_set(self._h, int(attr), int(first), values.size, values.ctypes.data), "attr_set")
+
+    def get_attr(self, attr: int, first: int, n: int, dtype=np.int64) -> np.ndarray:
+        out = np.empty(int(n), dtype=dtype)
+        self._check(self._lib.mlvdb_attr_get(self._h, int(attr), int(first), int(n), out.ctypes.data), "attr_get")
+        return out
+
+    @staticmethod
+    def _where(program):
+        """(mlvdb_where, the arrays it points into: kept alive by the caller for the call)."""
+        ops = np.ascontiguousarray(program.ops)
+        table = np.ascontiguousarray(program.set, dtype=np.int64)
+        w = _native.Where(ops.ctypes.data, int(ops.size), table.ctypes.data if table.size else None, int(table.size))
+        return w, (ops, table)
+
+    def where_count(self, program) -> int:
+        """Live rows the compiled filter (``where.Program``) matches, counted on the device."""
+        w, keep = self._where(program)
+        n = C.c_int64(0)
+        self._check(self._lib.mlvdb_where_count(self._h, C.byref(w), C.byref(n)), "where_count")
+        return int(n.value)
+
+    def where_labels(self, program) -> np.ndarray:
+        """Ascending labels of the live rows the compiled filter matches."""
+        w, keep = self._where(program)
+        total, deleted = self.counts()
+        out = np.empty(max(total - deleted, 1), dtype=np.int64)
+        n = C.c_int64(0)
+        self._check(self._lib.mlvdb_where_labels(self._h, C.byref(w), out.ctypes.data, out.size, C.byref(n)), "where_labels")
+        return out[: n.value]
+
+    def search64(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None, where=None):
+        """kNN; ``mask`` (optional, one byte per row, non-zero = allowed) restricts the search to those rows, ``where``
+        (optional, a compiled ``where.Program``) to the rows it matches, evaluated on the device.
         Returns (labels int64, dist float32, counts int32, dist64 float64): the last is what a merge over several
         engines (row shards) has to rank on."""
-        return self._search(queries, k, mask, True)
+        return self._search(queries, k, mask, True, where)
 
-    def search(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None):
-        """kNN -> (labels int64 [nq, k], dist float32 [nq, k], counts int32 [nq]); ``mask`` as in ``search64``."""
-        return self._search(queries, k, mask, False)
+    def search(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None, where=None):
+        """kNN -> (labels int64 [nq, k], dist float32 [nq, k], counts int32 [nq]); ``mask`` / ``where`` as in ``search64``."""
+        return self._search(queries, k, mask, False, where)
 
-    def _search(self, queries: np.ndarray, k: int, mask, want64: bool):
+    def _search(self, queries: np.ndarray, k: int, mask, want64: bool, where=None):
         queries = np.ascontiguousarray(queries, dtype=np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.dim:
             raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
@@ -214,6 +256,14 @@ class HipScanEngine:
         dist = np.empty((nq, k), dtype=np.float32)
         counts = np.empty(nq, dtype=np.int32)
         d64 = np.empty((nq, k), dtype=np.float64) if want64 else None
+        if where is not None:
+            if mask is not None:
+                raise RuntimeError("search: give a row mask or a where program, not both")
+            w, keep = self._where(where)
+            self._check(self._lib.mlvdb_search_batch_where(self._h, queries.ctypes.data, nq, int(k), C.byref(w),
+                                                           labels.ctypes.data, dist.ctypes.data, counts.ctypes.data,
+                                                           None if d64 is None else d64.ctypes.data), "search_batch_where")
+            return (labels, dist, counts, d64) if want64 else (labels, dist, counts)
         if mask is not None:
             mask = np.ascontiguousarray(mask, dtype=np.uint8)
             if mask.shape != (self.counts()[0],):
@@ -235,7 +285,7 @@ class HipScanEngine:
             self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(labels_ptr), C.c_void_p(dist_ptr),
             C.c_void_p(counts_ptr), C.c_void_p(dist64_ptr or None), C.c_void_p(stream or None)), "search_batch_device")
 
-    def range(self, queries: np.ndarray, radius: float, capacity: int, truncate: bool = False):
+    def range(self, queries: np.ndarray, radius: float, capacity: int, truncate: bool = False, where=None):
         """Per query (labels, fp32 distances) of the live rows within ``radius``, nearest first: a ``RangeHits`` sequence
         (``hits[i]`` -> the two arrays of query i, views of the call's packed outputs).
 
@@ -244,22 +294,29 @@ class HipScanEngine:
         that the nearest 16384 are returned).  ``truncate=True``: at most ``capacity`` hits per query, the nearest.
         Through ``mlvdb_range_batch_packed``: hit counts differ by orders of magnitude between queries, the packed arrays
         hold the hits and nothing else (a first call with room for 256 hits per query on average; when the hits need
-        more, the call is repeated with the size the first one reported)."""
+        more, the call is repeated with the size the first one reported).  ``where`` (optional, a compiled ``where.Program``)
+        restricts the hits to the rows it matches (``mlvdb_range_batch_packed_where``)."""
         queries = np.ascontiguousarray(queries, dtype=np.float32)
         if queries.ndim != 2 or queries.shape[1] != self.dim:
             raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
         nq = queries.shape[0]
         capacity = max(1, min(int(capacity), _native.MAX_TOPK_PAGED))
         total = min(nq * capacity, max(65_536, 256 * nq))
+        w, keep = self._where(where) if where is not None else (None, None)
         while True:
             labels = np.empty(total, dtype=np.int64)
             dist = np.empty(total, dtype=np.float32)
             offsets = np.zeros(nq + 1, dtype=np.int64)
             counts = np.zeros(nq, dtype=np.int64)
-            rc = self._check(self._lib.mlvdb_range_batch_packed(self._h, queries.ctypes.data, nq, float(radius), capacity, total,
-                                                                labels.ctypes.data, dist.ctypes.data, offsets.ctypes.data,
-                                                                counts.ctypes.data),
-                             "range_batch_packed", allow=(_native.ERR_OVERFLOW,))
+            if w is None:
+                rc = self._lib.mlvdb_range_batch_packed(self._h, queries.ctypes.data, nq, float(radius), capacity, total,
+                                                        labels.ctypes.data, dist.ctypes.data, offsets.ctypes.data,
+                                                        counts.ctypes.data)
+            else:
+                rc = self._lib.mlvdb_range_batch_packed_where(self._h, queries.ctypes.data, nq, float(radius), capacity, total,
+                                                              C.byref(w), labels.ctypes.data, dist.ctypes.data,
+                                                              offsets.ctypes.data, counts.ctypes.data)
+            rc = self._check(rc, "range_batch_packed", allow=(_native.ERR_OVERFLOW,))
             if rc == _native.OK:
                 break
             need_cap = capacity if truncate else min(max(int(counts.max(initial=0)), capacity), _native.MAX_TOPK_PAGED)

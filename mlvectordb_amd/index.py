@@ -18,7 +18,8 @@ swallowed by index.py:110-119); rows of the wrong dimensionality raise ``Runtime
 
 Additive (no reference counterpart): ``search_many`` (one scan for a whole query batch),
 ``range_search`` / ``range_search_many``, ``metric="euclidean"`` as sqrt(l2), ``compact`` and
-``save_index`` / ``load_index`` (named in the reference's README.md:240-241 only).
+``save_index`` / ``load_index`` (named in the reference's README.md:240-241 only); metadata filters evaluated on the device
+(``attributes=`` / ``where=`` / ``count`` / ``query_by_metadata``: README.md:121,130,252,274 intent, no reference code).
 """
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ from uuid import UUID
 
 import numpy as np
 
+from . import where as _where
 from .engine import HipScanEngine, ScanEngine
 from .idtable import IdTable, mint_uuid4_bytes
 from .interfaces import VectorDTO, VectorProtocol
@@ -47,7 +49,7 @@ class SearchResult:
 class _Namespace:
     """Host-side bookkeeping for one namespace (reference index.py:19-29, per key)."""
 
-    __slots__ = ("engine", "dim", "ids", "total", "deleted", "rebuild_required")
+    __slots__ = ("engine", "dim", "ids", "total", "deleted", "rebuild_required", "strings")
 
     def __init__(self, engine: ScanEngine, dim: int) -> None:
         self.engine = engine
@@ -56,6 +58,7 @@ class _Namespace:
         self.total = 0
         self.deleted = 0
         self.rebuild_required = False
+        self.strings: Dict[str, Dict[str, int]] = {}  # str attribute -> {value: dictionary code} (codes in order of first use)
 
 
 class BatchHits(SequenceABC):
@@ -140,7 +143,7 @@ class Index:
     def __init__(self, space: str = "l2", ef_construction: int = 200, M: int = 16,
                  rebuild_threshold: float = 0.2, *, device: int = 0, devices: Optional[Sequence[int]] = None,
                  strategy: str = "auto", capacity_hint: int = 0,
-                 engine_factory: Optional[EngineFactory] = None) -> None:
+                 engine_factory: Optional[EngineFactory] = None, attributes: Optional[Mapping[str, str]] = None) -> None:
         # ef_construction / M are HNSW build knobs (index.py:18,37); an exhaustive scan has none.
         self._space = space
         self._ef_construction = ef_construction
@@ -154,6 +157,27 @@ class Index:
         self._capacity_hint = int(capacity_hint)  # rows to reserve per namespace (and shard) up front: no regrowth copies
         self._engine_factory = engine_factory
         self._ns: Dict[str, _Namespace] = {}
+        # attributes={"genre": "str", "year": "int", ...}: per-row metadata columns in HBM, filtered on the device (where.py);
+        # attribute i (declaration order) is the engine's column i
+        self._attributes: Dict[str, str] = self._check_schema(attributes or {})
+        if self._attributes and self._devices is not None and len(self._devices) > 1:
+            raise ValueError("attributes= is not supported on a row-sharded index (devices=[...] with more than one entry)")
+
+    @staticmethod
+    def _check_schema(attributes: Mapping[str, str]) -> Dict[str, str]:
+        attributes = dict(attributes)
+        if len(attributes) > _where.MAX_ATTRS:
+            raise ValueError(f"at most {_where.MAX_ATTRS} attributes per index (got {len(attributes)})")
+        for name, kind in attributes.items():
+            if not isinstance(name, str) or name.startswith("$"):
+                raise ValueError(f"attribute name {name!r}: a string not starting with '$'")
+            if kind not in _where.ATTR_TYPES:
+                raise ValueError(f"attribute {name!r}: type {kind!r} is not one of {_where.ATTR_TYPES}")
+        return attributes
+
+    @property
+    def attributes(self) -> Dict[str, str]:
+        return dict(self._attributes)
 
     # ------------------------------------------------------------------ internals
     def _new_engine(self, dim: int, space: str) -> ScanEngine:
@@ -177,8 +201,58 @@ class Index:
         ns = self._ns.get(namespace)
         if ns is None:
             ns = _Namespace(self._new_engine(dim, space), dim)
+            for i, kind in enumerate(self._attributes.values()):
+                ns.engine.define_attr(i, _where.column_kind(kind))
             self._ns[namespace] = ns
         return ns
+
+    # ------------------------------------------------------------------ attributes
+    def _stage_attrs(self, namespace: str, columns: Mapping[str, Sequence], n: int):
+        """Encode a batch's attribute values (``columns``: name -> n values, ``None`` = absent) -> (column index -> array,
+        the namespace's string dictionaries with the batch's new strings).  Raises ``ValueError`` before anything is mutated."""
+        if not self._attributes:
+            if columns:
+                raise ValueError(f"this index declares no attributes (got {sorted(columns)})")
+            return {}, None
+        for name in columns:
+            if name not in self._attributes:
+                raise ValueError(f"{name!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        ns = self._ns.get(namespace)
+        strings = {name: dict(codes) for name, codes in (ns.strings if ns is not None else {}).items()}
+        out = {}
+        for i, (name, kind) in enumerate(self._attributes.items()):
+            values = columns.get(name)
+            if values is None:
+                continue
+            if len(values) != n:
+                raise ValueError(f"attribute {name!r}: {len(values)} values for {n} rows")
+            col = _where.encode_column(name, kind, values, strings.setdefault(name, {}) if kind == "str" else {})
+            present = ~np.isnan(col) if col.dtype == np.float64 else col != _where.INT64_ABSENT
+            if present.any():
+                out[i] = col
+        return out, strings
+
+    def _metadata_columns(self, metadata: Sequence[Optional[Mapping]]) -> Dict[str, list]:
+        """The declared attributes' values out of per-row metadata dicts (missing key / no metadata = absent)."""
+        return {name: [None if m is None else m.get(name) for m in metadata] for name in self._attributes}
+
+    def extract_attributes(self, metadata: Sequence[Optional[Mapping]]) -> Dict[str, list]:
+        """Columnar ``attributes=`` for ``add_arrays`` out of per-row metadata dicts (``QueryProcessor.upsert_arrays``)."""
+        return self._metadata_columns(metadata)
+
+    @staticmethod
+    def _commit_attrs(ns: _Namespace, first: int, staged) -> None:
+        cols, strings = staged
+        for i, col in cols.items():
+            ns.engine.set_attr(i, first, col)
+        if strings is not None:
+            ns.strings = strings
+
+    def _compile(self, namespace: str, where) -> "_where.Program":
+        if not isinstance(where, Mapping):
+            raise ValueError(f"where must be a dict filter (where.py), got {type(where).__name__}")
+        ns = self._ns.get(namespace)
+        return _where.compile_where(where, self._attributes, ns.strings if ns is not None else {})
 
     @staticmethod
     def _stack_rows(vectors: Sequence[VectorProtocol], dim: int) -> np.ndarray:
@@ -238,10 +312,16 @@ class Index:
         known = self._ns.get(namespace)
         dim = known.dim if known is not None else int(np.asarray(vectors[0].values).shape[0])
         staged = self._stage(vectors, dim)  # a refused batch creates no namespace and appends nothing
+        attrs = self._stage_attrs(namespace, self._metadata_columns([getattr(v, "metadata", None) for v in vectors]),
+                                  len(vectors)) if self._attributes else None
         ns = self._get_or_create(namespace, dim, self._space)
+        first = ns.total
         self._append(ns, vectors, staged)
+        if attrs is not None:
+            self._commit_attrs(ns, first, attrs)
 
-    def validate_arrays(self, rows: np.ndarray, namespace: str, handles: Optional[np.ndarray] = None) -> None:
+    def validate_arrays(self, rows: np.ndarray, namespace: str, handles: Optional[np.ndarray] = None,
+                        attributes: Optional[Mapping[str, Sequence]] = None) -> None:
         """Raises what ``add_arrays`` would raise for this batch, without touching the index: a caller that writes to a
         second store first (``QueryProcessor.upsert_arrays``) checks here before it writes anything."""
         if rows.ndim != 2:
@@ -252,13 +332,16 @@ class Index:
         if handles is not None and np.asarray(handles).shape != (rows.shape[0],):
             raise RuntimeError(f"{rows.shape[0]} rows but handles of shape {np.asarray(handles).shape}")
         self._check_finite(rows)
+        if attributes is not None:
+            self._stage_attrs(namespace, attributes, rows.shape[0])
 
     def add_arrays(self, rows: np.ndarray, namespace: str, ids: Optional[np.ndarray] = None,
-                   handles: Optional[np.ndarray] = None) -> np.ndarray:
+                   handles: Optional[np.ndarray] = None, attributes: Optional[Mapping[str, Sequence]] = None) -> np.ndarray:
         """Additive bulk form of ``add``: ``rows`` is a float ``[n, dim]`` matrix, ``ids`` an optional ``[n, 16] uint8``
         table of UUID bytes (minted as uuid4 when omitted), ``handles`` an optional int64 payload per row that comes
-        back with every hit (``BatchHits.handles``: a storage row number).  No Python object per row is created;
-        returns the id table.  Same label rule as ``add`` (index.py:56-63)."""
+        back with every hit (``BatchHits.handles``: a storage row number), ``attributes`` optional columnar values of the
+        declared attributes (name -> n values: an array, or a list with ``None`` for absent).  No Python object per row
+        is created; returns the id table.  Same label rule as ``add`` (index.py:56-63)."""
         rows = np.ascontiguousarray(rows, dtype=np.float32)
         if rows.ndim != 2:
             raise RuntimeError(f"Wrong dimensionality of the vectors: expected a matrix, got shape {rows.shape}")
@@ -269,11 +352,14 @@ class Index:
         if n == 0:
             return ids
         self.validate_arrays(rows, namespace, handles)  # every refusal happens before the engine is touched
+        attrs = self._stage_attrs(namespace, attributes or {}, n) if (attributes or self._attributes) else None
         ns = self._get_or_create(namespace, rows.shape[1], self._space)
         first = ns.engine.append(rows)
         if first != ns.total or ns.ids.append_raw(ids, handles) != first:
             raise RuntimeError(f"engine label base {first} != host row count {ns.total}")
         ns.total += n
+        if attrs is not None:
+            self._commit_attrs(ns, first, attrs)
         return ids
 
     def remove(self, ids: Sequence[UUID], namespace: str) -> None:
@@ -313,13 +399,23 @@ class Index:
             if getattr(vectors[0], "values", None) is None:
                 raise RuntimeError(f"namespace {namespace!r}: the source rows carry no values")
             dim = int(np.asarray(vectors[0].values).shape[0])
-            staged.append((namespace, dim, vectors, self._stage(vectors, dim)))
+            attrs = None
+            if self._attributes:  # (dictionaries start afresh: the namespace is rebuilt from nothing)
+                cols = self._metadata_columns([getattr(v, "metadata", None) for v in vectors])
+                saved, self._ns = self._ns, {}
+                try:
+                    attrs = self._stage_attrs(namespace, cols, len(vectors))
+                finally:
+                    self._ns = saved
+            staged.append((namespace, dim, vectors, self._stage(vectors, dim), attrs))
         for ns in self._ns.values():
             ns.engine.close()
         self._ns.clear()
-        for namespace, dim, vectors, st in staged:
+        for namespace, dim, vectors, st, attrs in staged:
             ns = self._get_or_create(namespace, dim, metric)
             self._append(ns, vectors, st)
+            if attrs is not None:
+                self._commit_attrs(ns, 0, attrs)
 
     def is_rebuild_required(self, namespace: str) -> bool:
         ns = self._ns.get(namespace)
@@ -353,14 +449,18 @@ class Index:
         return score
 
     def search_many(self, queries, top_k: int, namespace: str, metric: str,
-                    allowed_ids: Optional[Iterable[UUID]] = None) -> BatchHits:
+                    allowed_ids: Optional[Iterable[UUID]] = None, where: Optional[Mapping] = None) -> BatchHits:
         """kNN for a batch of queries in one corpus scan.
 
         ``queries`` is an ``[nq, dim]`` array or a sequence of ``VectorDTO``.  Each entry of
         the result is what ``search`` would return for that query (``BatchHits``: a lazy sequence over the result
         arrays).  ``allowed_ids`` (additive: the row mask of a metadata-filtered search, README.md:121,130 intent)
-        restricts the search to those vectors; the answer is the exact top-k among them.
+        restricts the search to those vectors; the answer is the exact top-k among them.  ``where`` (additive: a dict
+        filter over the declared attributes, where.py) does the same with the row mask evaluated on the device.
         """
+        if where is not None and allowed_ids is not None:
+            raise ValueError("search_many: give allowed_ids or where, not both")
+        program = None if where is None else self._compile(namespace, where)
         q = self._coerce_queries(queries)
         nq = q.shape[0]
         ns = self._ns.get(namespace)
@@ -381,7 +481,10 @@ class Index:
             mask[picked] = 1
             active = int(mask.sum())
         k = min(int(top_k), active, self._MAX_TOP_K)  # the reference clamps to the live count (index.py:107)
-        labels, dist, counts = self._search_engine(ns, q, k, mask)
+        if program is not None:  # (counts = min(k, matching rows): the padding says how many matched)
+            labels, dist, counts = ns.engine.search(q, k, where=program)
+        else:
+            labels, dist, counts = self._search_engine(ns, q, k, mask)
         return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
 
     _MAX_TOP_K = 16384  # MLVDB_MAX_TOPK_PAGED: the most neighbours one call returns per query
@@ -438,21 +541,39 @@ class Index:
                 yield pending.result()
 
     def range_search(self, query: VectorDTO, radius: float, namespace: str, metric: str,
-                     max_results: int = 1024) -> List[SearchResult]:
+                     max_results: int = 1024, where: Optional[Mapping] = None) -> List[SearchResult]:
         values = np.asarray(query.values, dtype=np.float32)
         if values.ndim != 1:
             return []
-        return self.range_search_many(values[None, :], radius, namespace, metric, max_results)[0]
+        return self.range_search_many(values[None, :], radius, namespace, metric, max_results, where=where)[0]
+
+    # ------------------------------------------------------------------ additive: metadata queries on the device
+    def count(self, namespace: str, where: Mapping) -> int:
+        """Live rows of ``namespace`` whose attributes satisfy the dict filter ``where`` (where.py); 0 for an unknown
+        namespace."""
+        program = self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        return 0 if ns is None or ns.total == 0 else ns.engine.where_count(program)
+
+    def query_by_metadata(self, namespace: str, where: Mapping) -> List[UUID]:
+        """UUIDs of the live rows satisfying ``where``, in insertion order (README.md:252,274: ``query_by_metadata``)."""
+        program = self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total == 0:
+            return []
+        return ns.ids.uuids_at(ns.engine.where_labels(program)).tolist()
 
     def range_search_many(self, queries, radius: float, namespace: str, metric: str,
-                          max_results: int = 1024) -> List[List[SearchResult]]:
+                          max_results: int = 1024, where: Optional[Mapping] = None) -> List[List[SearchResult]]:
         """The live rows within ``radius`` of each query, nearest first (ties by insertion order), at most
         ``max_results`` per query (the nearest ones; ``None`` = all, up to the engine's 16384 per query).
 
         ``radius`` is a distance in the namespace's space (squared for l2; plain for
         ``metric="euclidean"``); scores are post-processed exactly like ``search``.
-        No reference implementation exists for range queries (README prose only).
+        No reference implementation exists for range queries (README prose only).  ``where``: a dict filter over the
+        declared attributes (where.py), evaluated on the device.
         """
+        program = None if where is None else self._compile(namespace, where)
         q = self._coerce_queries(queries)
         nq = q.shape[0]
         ns = self._ns.get(namespace)
@@ -460,7 +581,8 @@ class Index:
             return [[] for _ in range(nq)]
         native_radius = float(radius) ** 2 if metric == "euclidean" else float(radius)
         cap = self._MAX_TOP_K if max_results is None else max(1, int(max_results))
-        per_query = ns.engine.range(q, native_radius, cap, truncate=True)
+        per_query = (ns.engine.range(q, native_radius, cap, truncate=True) if program is None
+                     else ns.engine.range(q, native_radius, cap, truncate=True, where=program))
         out: List[List[SearchResult]] = []
         for labels, dist in per_query:
             uids = ns.ids.uuids_at(labels).tolist()
@@ -537,14 +659,22 @@ class Index:
     #   ns<i>.ids.u8       [total, 16] UUID bytes, all-zero for tombstoned labels
     # The fp32 rows are the ones the device holds (bit-exact round trip); norms, bf16 shadow and panel layout are
     # rebuilt by the ingest kernels at load.  No reference behaviour (README.md:240-241 names the two methods only).
+    # An index with attributes writes "mlvdb-index-v2": v1 + per namespace i and attribute j
+    #   ns<i>.attr<j>.i64 / .f64   the raw device column [total] (int64, INT64_MIN = absent / float64, NaN = absent)
+    # and in index.json "attributes" (name -> type, in column order) and per namespace "strings" (str attribute -> its
+    # dictionary, code order).  An index without attributes writes exactly v1.
     _FORMAT = "mlvdb-index-v1"
+    _FORMAT_V2 = "mlvdb-index-v2"
     _CHUNK_BYTES = 256 << 20
 
     def save_index(self, path: str) -> bool:
         """Write every namespace to directory ``path`` (created if missing); streams the rows off the device in
         chunks, so host memory stays bounded."""
         os.makedirs(path, exist_ok=True)
-        meta = {"format": self._FORMAT, "space": self._space, "rebuild_threshold": self._rebuild_threshold, "namespaces": []}
+        meta = {"format": self._FORMAT_V2 if self._attributes else self._FORMAT, "space": self._space,
+                "rebuild_threshold": self._rebuild_threshold, "namespaces": []}
+        if self._attributes:
+            meta["attributes"] = dict(self._attributes)
         for i, (name, ns) in enumerate(self._ns.items()):
             chunk = max(1, self._CHUNK_BYTES // (4 * ns.dim))
             with open(os.path.join(path, f"ns{i}.rows.f32"), "wb") as f:
@@ -555,13 +685,24 @@ class Index:
             ids[dead] = 0
             ids.tofile(os.path.join(path, f"ns{i}.ids.u8"))
             dead.tofile(os.path.join(path, f"ns{i}.deleted.i64"))
-            meta["namespaces"].append({"name": name, "dim": ns.dim, "space": ns.engine.space, "total": ns.total,
-                                       "deleted": ns.deleted, "rebuild_required": ns.rebuild_required})
+            entry = {"name": name, "dim": ns.dim, "space": ns.engine.space, "total": ns.total,
+                     "deleted": ns.deleted, "rebuild_required": ns.rebuild_required}
+            if self._attributes:
+                for j, kind in enumerate(self._attributes.values()):
+                    col = self._attr_file(path, i, j, kind)
+                    dtype = np.float64 if kind == "float" else np.int64
+                    (ns.engine.get_attr(j, 0, ns.total, dtype) if ns.total else np.zeros(0, dtype)).tofile(col)
+                entry["strings"] = {a: sorted(codes, key=codes.get) for a, codes in ns.strings.items()}
+            meta["namespaces"].append(entry)
         tmp = os.path.join(path, "index.json.tmp")
         with open(tmp, "w") as f:
             json.dump(meta, f, indent=1)
         os.replace(tmp, os.path.join(path, "index.json"))  # the manifest appears last and atomically
         return True
+
+    @staticmethod
+    def _attr_file(path: str, i: int, j: int, kind: str) -> str:
+        return os.path.join(path, f"ns{i}.attr{j}.{'f64' if kind == 'float' else 'i64'}")
 
     def load_index(self, path: str) -> bool:
         """Replace the contents of this index by the directory written by ``save_index``.  Returns False (index
@@ -571,14 +712,23 @@ class Index:
             return False
         with open(manifest) as f:
             meta = json.load(f)
-        if meta.get("format") != self._FORMAT:
+        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2):
             raise RuntimeError(f"unknown index format {meta.get('format')!r}")
+        v2 = meta["format"] == self._FORMAT_V2
+        # v2: the snapshot's attributes replace the declared ones; v1: the declared ones stay, every value absent
+        attributes = self._check_schema(meta.get("attributes", {})) if v2 else self._attributes
+        if v2 and attributes and self._devices is not None and len(self._devices) > 1:
+            raise ValueError("attributes= is not supported on a row-sharded index (devices=[...] with more than one entry)")
         for i, m in enumerate(meta["namespaces"]):  # validate sizes before touching anything
             total, dim = int(m["total"]), int(m["dim"])
             if os.path.getsize(os.path.join(path, f"ns{i}.rows.f32")) != total * dim * 4 or \
                     os.path.getsize(os.path.join(path, f"ns{i}.ids.u8")) != total * 16:
                 raise RuntimeError(f"namespace {m['name']!r}: file sizes do not match the manifest")
+            if v2 and any(os.path.getsize(self._attr_file(path, i, j, kind)) != total * 8
+                          for j, kind in enumerate(attributes.values())):
+                raise RuntimeError(f"namespace {m['name']!r}: attribute file sizes do not match the manifest")
         self.close()
+        self._attributes = attributes
         self._space = meta["space"]
         self._rebuild_threshold = float(meta["rebuild_threshold"])
         for i, m in enumerate(meta["namespaces"]):
@@ -596,6 +746,12 @@ class Index:
                 ns.engine.tombstone(deleted)
             ns.ids.append_raw(np.fromfile(os.path.join(path, f"ns{i}.ids.u8"), dtype=np.uint8).reshape(total, 16))
             ns.ids.kill(deleted)
+            if v2:
+                for j, kind in enumerate(attributes.values()):
+                    col = np.fromfile(self._attr_file(path, i, j, kind), dtype=np.float64 if kind == "float" else np.int64)
+                    if col.size:
+                        ns.engine.set_attr(j, 0, col)
+                ns.strings = {a: {s: c for c, s in enumerate(values)} for a, values in m.get("strings", {}).items()}
             ns.total = total
             ns.deleted = int(m["deleted"])
             ns.rebuild_required = bool(m["rebuild_required"])

@@ -16,6 +16,7 @@ to reproduce the reference byte for byte.
 from __future__ import annotations
 
 import numpy as np
+from collections.abc import Mapping
 from typing import Any, Dict, Iterable, List, Sequence
 from uuid import UUID
 
@@ -68,15 +69,19 @@ class QueryProcessor:
                           metric: str = "cosine", where=None) -> List[List[dict]]:
         """Batched ``find_similar``: ``queries`` is an [nq, dim] array or a sequence of VectorDTO.
 
-        ``where`` (additive; README.md:121,130,252,274 intent, no reference code): a predicate over a stored
-        vector's metadata dict.  It is evaluated once over the namespace's stored vectors and handed to the
-        index as a row mask, so the answer is the exact top-k among the matching vectors (not a post-filter of
-        an unrestricted top-k)."""
+        ``where`` (additive; README.md:121,130,252,274 intent, no reference code) restricts the search to the matching
+        vectors -- the exact top-k among them, not a post-filter of an unrestricted top-k:
+          - a dict filter over the index's declared attributes (``Index(attributes=...)``, where.py): compiled once and
+            evaluated on the device into the row mask; nothing per row happens on the host;
+          - a predicate over a stored vector's metadata dict: evaluated once over the namespace's stored vectors and
+            handed to the index as a row mask."""
         return self._enrich_many(self._search_many(queries, top_k, namespace, metric, where), namespace)
 
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
         if where is None:
             return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric)
+        if isinstance(where, Mapping):
+            return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric, where=where)
         allowed = [v.id for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
         return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric, allowed_ids=allowed)
 
@@ -146,16 +151,37 @@ class QueryProcessor:
         return self.find_similar_many(values[None, :], top_k, namespace, metric, where=where)[0]
 
     def find_in_radius(self, query: VectorDTO, radius: float, namespace: str = "default",
-                       metric: str = "cosine", max_results: int = 1024) -> List[dict]:
-        """Range query (no reference counterpart; README.md:30-41 intent only)."""
-        hits = self._index.range_search(query, radius, namespace=namespace, metric=metric, max_results=max_results)
-        out = self._enrich(hits, namespace)
+                       metric: str = "cosine", max_results: int = 1024, where=None) -> List[dict]:
+        """Range query (no reference counterpart; README.md:30-41 intent only).  ``where`` as in ``find_similar_many``: a
+        dict filter is evaluated on the device; a predicate filters the hits (all of them, up to the index's 16384 per
+        query) by their stored metadata before ``max_results`` applies."""
+        if where is None or isinstance(where, Mapping):
+            kw = {} if where is None else {"where": where}
+            hits = self._index.range_search(query, radius, namespace=namespace, metric=metric, max_results=max_results, **kw)
+            out = self._enrich(hits, namespace)
+        else:
+            hits = self._index.range_search(query, radius, namespace=namespace, metric=metric, max_results=None)
+            out = [h for h in self._enrich(hits, namespace) if where(h["metadata"])]
+            out = out if max_results is None else out[:max(1, int(max_results))]
         missing = [i for i, h in enumerate(out) if h["values"] is None]  # array storage that keeps the rows in HBM only
         if missing and hasattr(self._index, "fetch_values_by_id"):
             rows = self._index.fetch_values_by_id(namespace, [out[i]["id"] for i in missing])
             for i, r in zip(missing, rows):
                 out[i]["values"] = r
         return out
+
+    # ---- additive: metadata queries (README.md:252,274: StorageEngine.query_by_metadata; no reference code)
+    def count_where(self, where, namespace: str = "default") -> int:
+        """Live vectors of ``namespace`` matching ``where`` (dict filter: counted on the device; predicate: over storage)."""
+        if isinstance(where, Mapping):
+            return self._index.count(namespace, where)
+        return sum(1 for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata))
+
+    def query_by_metadata(self, where, namespace: str = "default") -> List[UUID]:
+        """Ids of the vectors of ``namespace`` matching ``where``, in insertion order."""
+        if isinstance(where, Mapping):
+            return self._index.query_by_metadata(namespace, where)
+        return [v.id for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
 
     # ---- delete -> lazy rebuild (query_processor.py:51-62)
     def delete(self, ids: Sequence[UUID], namespace: str = "default") -> Sequence[UUID]:
@@ -226,10 +252,20 @@ class QueryProcessor:
             raise ValueError('keep_host_copy=False needs rebuild_scope="all": a namespace-scoped rebuild closes the other '
                              "namespaces' engines, which would hold the only copy of their rows")
         # the index's refusals (dimension, non-finite rows) come before the storage is written: no ghost rows
+        # declared attributes (Index(attributes=...)) come out of the metadata and are refused here too when mistyped
+        attrs = None
+        if metadata is not None and getattr(self._index, "attributes", None):
+            if len(metadata) != values.shape[0]:
+                raise ValueError(f"{len(metadata)} metadata entries for {values.shape[0]} rows")
+            attrs = self._index.extract_attributes(metadata)
         if hasattr(self._index, "validate_arrays"):
-            self._index.validate_arrays(values, namespace)
+            if attrs is None:
+                self._index.validate_arrays(values, namespace)
+            else:
+                self._index.validate_arrays(values, namespace, attributes=attrs)
         ids = mint_uuid4_bytes(values.shape[0])
         first = self._storage.write_arrays(ids, namespace, values if keep_host_copy else None, metadata)
+        kw = {} if attrs is None else {"attributes": attrs}
         self._index.add_arrays(values, namespace, ids=ids,
-                               handles=np.arange(first, first + values.shape[0], dtype=np.int64))
+                               handles=np.arange(first, first + values.shape[0], dtype=np.int64), **kw)
         return ids

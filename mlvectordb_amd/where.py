@@ -1,0 +1,264 @@
+"""Dict metadata filters -> the postfix predicate program the device evaluates (include/mlvdb_where.h).
+
+A filter is a dict over a namespace's declared attributes (``Index(attributes={"genre": "str", "year": "int", ...})``):
+
+    {"genre": "jazz"}                              equality
+    {"year": {"$gte": 2000, "$lt": 2010}}          several operators on one key: AND
+    {"$or": [{"genre": "jazz"}, {"year": {"$lt": 1960}}]}
+    {"genre": {"$in": ["jazz", "blues"]}, "in_stock": True}   several keys: AND;  {} matches every row
+
+Operators ``$eq $ne $lt $lte $gt $gte $in $nin $exists``; combinators ``$and $or $not``.  Semantics on a row without a value
+(key missing, ``None``, NaN for a float attribute): every comparison, ``$eq`` and ``$in`` is false; ``$ne`` / ``$nin`` are
+their negations, so such a row matches them; ``$exists: False`` matches it.
+
+Type rules: ``int`` / ``bool`` attributes take int and bool literals only (a float literal is refused), ``float`` attributes
+take int and float literals, ``str`` attributes take strings and only ``$eq $ne $in $nin $exists`` (matched through the
+namespace's dictionary codes: a string never ingested matches nothing).  A key that is not a declared attribute, or a
+program longer than 64 ops or deeper than 32, is a ``ValueError``: there is no slow host path to fall back to.
+"""
+from __future__ import annotations
+
+import math
+import struct
+from dataclasses import dataclass
+from typing import Any, Dict, List, Mapping, Tuple
+
+import numpy as np
+
+ATTR_TYPES = ("int", "float", "str", "bool")
+MAX_ATTRS = 16
+MAX_OPS = 64
+MAX_DEPTH = 32
+
+# op codes (MLVDB_WHERE_*)
+TRUE, EQ, NE, LT, LE, GT, GE, IN, EXISTS, AND, OR, NOT = range(12)
+OP_DTYPE = np.dtype([("op", "<i4"), ("attr", "<i4"), ("a", "<i8"), ("b", "<i8")])  # mlvdb_where_op
+
+_ORDERED = {"$lt": LT, "$lte": LE, "$gt": GT, "$gte": GE}
+_FIELD_OPS = ("$eq", "$ne", "$lt", "$lte", "$gt", "$gte", "$in", "$nin", "$exists")
+
+
+@dataclass
+class Program:
+    """A compiled filter: ``ops`` (structured array in the layout of ``mlvdb_where_op``) and the int64 ``set`` table the IN
+    ops index into (each op's range sorted ascending)."""
+
+    ops: np.ndarray
+    set: np.ndarray
+
+
+def float_bits(x: float) -> int:
+    """The int64 carrying a double's bit pattern (the ``a`` of an op on a float64 column)."""
+    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
+
+
+def column_kind(attr_type: str) -> str:
+    """The device column type of an attribute type: float -> float64, everything else -> int64."""
+    return "float64" if attr_type == "float" else "int64"
+
+
+class _Builder:
+    def __init__(self, schema: Mapping[str, str], strings: Mapping[str, Mapping[str, int]]) -> None:
+        self.schema = schema
+        self.index = {name: i for i, name in enumerate(schema)}
+        self.strings = strings
+        self.ops: List[Tuple[int, int, int, int]] = []
+        self.sets: List[np.ndarray] = []
+        self.n_set = 0
+
+    # -- emission
+    def emit(self, op: int, attr: int = 0, a: int = 0, b: int = 0) -> None:
+        self.ops.append((op, attr, a, b))
+
+    def false(self) -> None:
+        self.emit(TRUE)
+        self.emit(NOT)
+
+    def fold(self, parts: List[Any], combine: int, empty_true: bool, fn) -> None:
+        if not parts:
+            self.emit(TRUE) if empty_true else self.false()
+            return
+        for i, part in enumerate(parts):
+            fn(part)
+            if i:
+                self.emit(combine)
+
+    # -- filters
+    def node(self, where: Any) -> None:
+        if not isinstance(where, Mapping):
+            raise ValueError(f"a filter is a dict, got {type(where).__name__}")
+        self.fold(list(where.items()), AND, True, lambda kv: self.clause(*kv))
+
+    def clause(self, key: Any, value: Any) -> None:
+        if key in ("$and", "$or"):
+            if not isinstance(value, (list, tuple)):
+                raise ValueError(f"{key} takes a list of filters")
+            self.fold(list(value), AND if key == "$and" else OR, key == "$and", self.node)
+        elif key == "$not":
+            self.node(value)
+            self.emit(NOT)
+        elif isinstance(key, str) and key.startswith("$"):
+            raise ValueError(f"unknown combinator {key!r}")
+        else:
+            if key not in self.schema:
+                raise ValueError(f"{key!r} is not a declared attribute of this index (declared: {sorted(self.schema)})")
+            if isinstance(value, Mapping):
+                if not value:
+                    raise ValueError(f"{key!r}: an empty operator dict")
+                for op in value:
+                    if op not in _FIELD_OPS:
+                        raise ValueError(f"{key!r}: unknown operator {op!r}")
+                self.fold(list(value.items()), AND, True, lambda kv: self.field(key, *kv))
+            else:
+                self.field(key, "$eq", value)
+
+    def literal(self, key: str, value: Any) -> int:
+        """A scalar literal as the int64 the column holds (int / bool / str code; float bits), or None: matches no row."""
+        kind = self.schema[key]
+        if kind in ("int", "bool"):
+            if isinstance(value, (bool, np.bool_)) or (isinstance(value, (int, np.integer))):
+                v = int(value)
+                if not -(2 ** 63) < v < 2 ** 63:
+                    return None  # no stored value can equal it (INT64_MIN is the absent marker)
+                return v
+            raise ValueError(f"{key!r} is an {kind} attribute: literal {value!r} is not an int or bool")
+        if kind == "float":
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{key!r} is a float attribute: literal {value!r} is not an int or float")
+            return float_bits(float(value))
+        if not isinstance(value, str):
+            raise ValueError(f"{key!r} is a str attribute: literal {value!r} is not a string")
+        return self.strings.get(key, {}).get(value)
+
+    def field(self, key: str, op: str, value: Any) -> None:
+        attr, kind = self.index[key], self.schema[key]
+        if op == "$exists":
+            if not isinstance(value, (bool, np.bool_)):
+                raise ValueError(f"{key!r}: $exists takes True or False")
+            self.emit(EXISTS, attr)
+            if not value:
+                self.emit(NOT)
+            return
+        if op in ("$in", "$nin"):
+            if not isinstance(value, (list, tuple, set, frozenset)):
+                raise ValueError(f"{key!r}: {op} takes a list")
+            self.member(key, attr, kind, list(value))
+            if op == "$nin":
+                self.emit(NOT)
+            return
+        if op in _ORDERED and kind == "str":
+            raise ValueError(f"{key!r} is a str attribute: only $eq, $ne, $in, $nin and $exists apply")
+        v = self.literal(key, value)
+        if kind == "float" and math.isnan(float(value)) and op != "$ne":
+            self.false()  # NaN equals / orders against nothing (the ops would say so too; no column read needed)
+            return
+        if v is None and op in _ORDERED:  # an int literal outside int64: every present value lies on one side of it
+            below = (int(value) > 0) == (op in ("$lt", "$lte"))
+            self.emit(EXISTS, attr) if below else self.false()
+            return
+        if v is None:  # a string never ingested, an int outside int64: no row holds it
+            self.false() if op != "$ne" else self.emit(TRUE)
+            return
+        self.emit({"$eq": EQ, "$ne": NE}.get(op) or _ORDERED[op], attr, v)
+
+    def member(self, key: str, attr: int, kind: str, values: List[Any]) -> None:
+        lits = [self.literal(key, x) for x in values]
+        if kind == "float":  # IN reads int64 columns: a float membership is an OR of equalities
+            lits = [v for v, x in zip(lits, values) if not math.isnan(float(x))]
+            self.fold(sorted(set(lits)), OR, False, lambda v: self.emit(EQ, attr, v))
+            return
+        vals = np.unique(np.array([v for v in lits if v is not None], dtype=np.int64))
+        if vals.size == 0:
+            self.false()
+            return
+        self.emit(IN, attr, self.n_set, int(vals.size))
+        self.sets.append(vals)
+        self.n_set += int(vals.size)
+
+    def program(self) -> Program:
+        if len(self.ops) > MAX_OPS:
+            raise ValueError(f"the filter compiles to {len(self.ops)} ops; the device evaluates at most {MAX_OPS}")
+        depth = deepest = 0
+        for op, _, _, _ in self.ops:
+            depth += 1 if op <= EXISTS else (-1 if op in (AND, OR) else 0)
+            deepest = max(deepest, depth)
+        if deepest > MAX_DEPTH:
+            raise ValueError(f"the filter needs a stack {deepest} deep; the device evaluates at most {MAX_DEPTH}")
+        table = np.concatenate(self.sets) if self.sets else np.zeros(0, dtype=np.int64)  # each IN range sorted by itself
+        return Program(np.array(self.ops, dtype=OP_DTYPE), np.ascontiguousarray(table, dtype=np.int64))
+
+
+def compile_where(where: Mapping[str, Any], schema: Mapping[str, str],
+                  strings: Mapping[str, Mapping[str, int]] | None = None) -> Program:
+    """Compile ``where`` against ``schema`` (attribute name -> "int" / "float" / "str" / "bool", in declaration order:
+    attribute i is column i) and the namespace's string dictionaries (attribute -> {string: code})."""
+    b = _Builder(schema, strings or {})
+    b.node(where)
+    return b.program()
+
+
+# ---------------------------------------------------------------- ingest: metadata values -> column values
+INT64_ABSENT = np.iinfo(np.int64).min
+
+
+def encode_column(name: str, kind: str, values, codes: Dict[str, int]) -> np.ndarray:
+    """One attribute's values of a batch (``None`` = absent) as the device column (int64 with INT64_MIN absent, float64
+    with NaN absent).  New strings get codes in ``codes`` (the caller passes a copy and keeps it only if the whole batch
+    is accepted).  A value of the wrong type raises ``ValueError`` naming the attribute."""
+    if isinstance(values, np.ndarray) and values.dtype != object:
+        return _encode_array(name, kind, values, codes)
+    n = len(values)
+    if kind == "float":
+        out = np.full(n, np.nan)
+        for i, v in enumerate(values):
+            if v is None:
+                continue
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"attribute {name!r} (float): row {i} holds {v!r}")
+            out[i] = float(v)
+        return out
+    out = np.full(n, INT64_ABSENT, dtype=np.int64)
+    for i, v in enumerate(values):
+        if v is None:
+            continue
+        if kind == "str":
+            if not isinstance(v, str):
+                raise ValueError(f"attribute {name!r} (str): row {i} holds {v!r}")
+            code = codes.get(v)
+            if code is None:
+                code = codes[v] = len(codes)
+            out[i] = code
+        elif kind == "bool":
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"attribute {name!r} (bool): row {i} holds {v!r}")
+            out[i] = int(v)
+        else:
+            if not isinstance(v, (int, np.integer)):  # (bool is an int)
+                raise ValueError(f"attribute {name!r} (int): row {i} holds {v!r}")
+            if not -(2 ** 63) < int(v) < 2 ** 63:
+                raise ValueError(f"attribute {name!r} (int): row {i} holds {v!r}, outside int64 (INT64_MIN marks absent)")
+            out[i] = int(v)
+    return out
+
+
+def _encode_array(name: str, kind: str, values: np.ndarray, codes: Dict[str, int]) -> np.ndarray:
+    values = values.ravel()
+    ch = values.dtype.kind
+    if kind == "float":
+        if ch not in "iuf":
+            raise ValueError(f"attribute {name!r} (float): array of dtype {values.dtype}")
+        return values.astype(np.float64)
+    if kind == "str":
+        if ch not in "US":
+            raise ValueError(f"attribute {name!r} (str): array of dtype {values.dtype}")
+        return encode_column(name, kind, values.astype(str).tolist(), codes)
+    if kind == "bool" and ch != "b":
+        raise ValueError(f"attribute {name!r} (bool): array of dtype {values.dtype}")
+    if kind == "int" and ch not in "iub":
+        raise ValueError(f"attribute {name!r} (int): array of dtype {values.dtype}")
+    if ch == "u" and values.size and values.max() > np.iinfo(np.int64).max:
+        raise ValueError(f"attribute {name!r} (int): values outside int64")
+    out = values.astype(np.int64)
+    if (out == INT64_ABSENT).any():
+        raise ValueError(f"attribute {name!r} (int): INT64_MIN is the absent marker, not a value")
+    return out
