@@ -14,6 +14,11 @@ A step = one query wave through the hot path with queries and corpus resident in
 query prep -> int8- (cosine) or bf16-MFMA filter scan of the shard -> threshold updates -> exact fp64 rescoring
 (-> gather + host merge when N>1).  Prints ONE JSON line (rank 0).  roofline.achieved: algorithmic
 bytes of the scan launches / their HIP-event durations (events around filter_scan_asm_kernel only).
+
+A plain run does what the headline needs: load the shard, warm up, time the K steps (at N=1 once per wave mode), write
+--dump-outputs, print the line.  `--full` adds everything else, untimed for the headline: the fatal parity gate (exact fp64
+scans + NumPy oracle, before the warm-up), the sustained rate, single-wave latencies, the CPU baseline and the side configs
+(configs[0], [1], [3], top_k = 100, the Protocol-level path).
 """
 from __future__ import annotations
 
@@ -72,18 +77,20 @@ def parse_args():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--space", default="cosine")
     ap.add_argument("--strategy", default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity gate, the sustained rate, the latencies, the CPU baseline and the side configs")
     ap.add_argument("--cpu-sample-rows", type=int, default=1_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the config-2 (1M x 768, batch 1) side measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and the side configs in it)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the side configs")
     ap.add_argument("--tombstones", type=float, default=0.0,
                     help="secondary run (SURVEY 8d): tombstone this fraction of every shard's rows, default_rng(99), before searching")
     ap.add_argument("--gen-threads", type=int, default=0)
     ap.add_argument("--wave-mode", choices=["synchronised", "back_to_back"], default="synchronised",
                     help="N=1: what the timed K steps do between waves (both are measured; this one is `ms_per_step` / `value`)")
     ap.add_argument("--query-batches", type=int, default=8,
-                    help="distinct seeded query batches the timed loops rotate through (each gated once, untimed)")
+                    help="distinct seeded query batches the timed loops rotate through (with --full each is gated once, untimed)")
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
-                    help="N=1: also time >= this many seconds (and >= 1000 waves) in both wave modes (0 = skip)")
+                    help="N=1, --full: also time >= this many seconds (and >= 1000 waves) in both wave modes (0 = skip)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (gloo for single-device rehearsals)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--in-process", action="store_true",
@@ -144,26 +151,29 @@ def in_process_main(args, json_fd) -> None:
     shards = getattr(eng, "shards", [eng])
     log(f"{g} shards on devices {devices}: {[s.counts()[0] for s in shards]} rows after {load_s:.1f} s")
     q_host = synth.queries(batch, d)
-    hits = index.search_many(q_host, k, "bench", args.space)
-    for s in shards:
-        s.set_strategy("exact")
-    exact = index.search_many(q_host, k, "bench", args.space)
-    for s in shards:
-        s.set_strategy(args.strategy)
-    verify = {"queries_compared": int(batch), "merged_ids_equal_merged_exact_scans": bool(np.array_equal(hits.labels, exact.labels)),
-              "max_abs_score_err": float(np.abs(hits.scores - exact.scores).max())}
     out = {"metric": "queries/sec, exact cosine kNN k=10 over a row-sharded Nx768 fp32 corpus (10M rows per GPU)",
            "unit": "queries/s (each query scanned against one shard; whole-corpus QPS = value / n_gpus)",
            "n_gpus": g, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "data": "synthetic", "mode": "in-process: Index(devices=...) behind the Protocol surface",
            "config": {"workload": f"{g * n_local} x {d} fp32 N(0,1) rows ({n_local}/shard), {args.space} kNN k={k}, batch={batch}",
                       "devices": devices, "rows_per_gpu": n_local, "dim": d, "k": k, "batch": batch},
-           "parity_gate": verify, "load_s": round(load_s, 1)}
-    if not verify["merged_ids_equal_merged_exact_scans"] or verify["max_abs_score_err"] > 1e-5:
-        log(f"PARITY GATE FAILED: {verify}")
-        out.update({"value": None, "error": "parity gate failed"})
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-        sys.exit(1)
+           "parity_gate": None, "load_s": round(load_s, 1)}
+    if args.full:
+        hits = index.search_many(q_host, k, "bench", args.space)
+        for s in shards:
+            s.set_strategy("exact")
+        exact = index.search_many(q_host, k, "bench", args.space)
+        for s in shards:
+            s.set_strategy(args.strategy)
+        verify = {"queries_compared": int(batch),
+                  "merged_ids_equal_merged_exact_scans": bool(np.array_equal(hits.labels, exact.labels)),
+                  "max_abs_score_err": float(np.abs(hits.scores - exact.scores).max())}
+        out["parity_gate"] = verify
+        if not verify["merged_ids_equal_merged_exact_scans"] or verify["max_abs_score_err"] > 1e-5:
+            log(f"PARITY GATE FAILED: {verify}")
+            out.update({"value": None, "error": "parity gate failed"})
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+            sys.exit(1)
     for _ in range(args.warmup):
         index.search_many(q_host, k, "bench", args.space)
     t_start = time.perf_counter()
@@ -367,16 +377,16 @@ def main() -> None:
 
     index = Index(space=args.space, device=local_rank, strategy=args.strategy, capacity_hint=n_local)
     qp = QueryProcessor(ArrayStorage(), index)
-    # BASELINE configs[3] (squared-l2 kNN + range query on the same rows) is measured beside the headline at N=1:
+    # BASELINE configs[3] (squared-l2 kNN + range query on the same rows) is measured beside the headline at N=1 (--full):
     # its index is filled from the same generated pieces (one more upload per piece, no second generation)
-    want_cfg4 = world == 1 and not args.no_extras and args.space == "cosine" and args.tombstones == 0.0
+    want_cfg4 = world == 1 and args.full and not args.no_extras and args.space == "cosine" and args.tombstones == 0.0
     eng_l2 = HipScanEngine(d, "l2", device=local_rank, capacity_hint=n_local) if want_cfg4 else None
     sample_rows = None
     for off, rows in synth.iter_corpus(row0, n_local, d, threads=threads):
         qp.upsert_arrays(rows, "bench", keep_host_copy=False)
         if eng_l2 is not None:
             eng_l2.append(rows)
-        if rank == 0 and off == 0:
+        if rank == 0 and off == 0 and args.full:
             sample_rows = rows.copy()  # first 250k rows, reused for the parity gate
     eng = index._ns["bench"].engine
     if args.tombstones > 0.0:
@@ -390,7 +400,7 @@ def main() -> None:
     log(f"shard rows [{row0}, {row0 + n_local}) resident after {load_s:.1f} s ({threads} generator threads)")
 
     # Query batches: batch 0 is SURVEY 8d's default_rng(4321); every timed loop rotates through all of them, so thresholds,
-    # candidate counts and branch behaviour are not those of one draw.  Each batch passes the parity gate once, untimed.
+    # candidate counts and branch behaviour are not those of one draw.  --full: each batch passes the parity gate once, untimed.
     nqb = max(1, args.query_batches)
     q_hosts = [synth.queries(batch, d, i) for i in range(nqb)]
     q_devs = [torch.from_numpy(q).to(dev) for q in q_hosts]
@@ -463,62 +473,63 @@ def main() -> None:
                 return merge_topk([t.numpy() for t in gl], [t.numpy() for t in gd], k)
             return None
 
-    # ---- parity gate (untimed): ids must equal the exact fp64 GPU scan, and the oracle on a sample
-    verify = {"query_batches": nqb, "filter_equals_exact_scan_ids": True, "filter_equals_exact_scan_max_abs_err": 0.0}
-    for qi in range(nqb - 1, -1, -1):  # (batch 0 last: its answer stays in fast_ids for the protocol-level check below)
-        local_wave(qi)
-        torch.cuda.synchronize()
-        stats0 = eng.last_stats()
-        fast_ids = lab.cpu().numpy().copy()
-        fast_dist = dst.cpu().numpy().copy()
-        eng.set_strategy("exact")
-        ex_l, ex_d, _ = eng.search(q_hosts[qi], k)  # every query of the wave against the exact fp64 scan of the whole shard
-        eng.set_strategy(args.strategy)
-        verify["filter_equals_exact_scan_ids"] &= bool(np.array_equal(fast_ids, ex_l))
-        verify["filter_equals_exact_scan_max_abs_err"] = max(verify["filter_equals_exact_scan_max_abs_err"],
-                                                             float(np.abs(fast_dist - ex_d).max()))
-    verify["queries_compared"] = int(batch) * nqb
-    if rank == 0 and sample_rows is not None:
-        from oracle import exact_scan
+    # ---- parity gate (--full, untimed): ids must equal the exact fp64 GPU scan, and the oracle on a sample
+    verify = None
+    if args.full:
+        verify = {"query_batches": nqb, "filter_equals_exact_scan_ids": True, "filter_equals_exact_scan_max_abs_err": 0.0}
+        for qi in range(nqb - 1, -1, -1):  # (batch 0 last: its answer stays in fast_ids for the protocol-level check below)
+            local_wave(qi)
+            torch.cuda.synchronize()
+            fast_ids = lab.cpu().numpy().copy()
+            fast_dist = dst.cpu().numpy().copy()
+            eng.set_strategy("exact")
+            ex_l, ex_d, _ = eng.search(q_hosts[qi], k)  # every query of the wave against the exact fp64 scan of the whole shard
+            eng.set_strategy(args.strategy)
+            verify["filter_equals_exact_scan_ids"] &= bool(np.array_equal(fast_ids, ex_l))
+            verify["filter_equals_exact_scan_max_abs_err"] = max(verify["filter_equals_exact_scan_max_abs_err"],
+                                                                 float(np.abs(fast_dist - ex_d).max()))
+        verify["queries_compared"] = int(batch) * nqb
+        if rank == 0 and sample_rows is not None:
+            from oracle import exact_scan
 
-        small = HipScanEngine(d, args.space, device=local_rank, strategy="filter" if d % 64 == 0 else "exact")
-        small.append(sample_rows)
-        if args.tombstones > 0.0:
-            small.tombstone(np.nonzero(sample_dead)[0].astype(np.int64))
-        sl, sd, _ = small.search(q_host[:64], k)
-        small.close()
-        ol, od, _ = exact_scan.knn(q_host[:64], sample_rows, k, args.space,
-                                   deleted=sample_dead if args.tombstones > 0.0 else None)
-        verify["oracle_sample"] = f"{sample_rows.shape[0]} rows x 64 queries"
-        verify["oracle_ids_equal"] = bool(np.array_equal(sl, ol))
-        verify["oracle_max_abs_err"] = float(np.abs(sd - od).max())
-    if world > 1:
-        # sharded path: the host-merged answer of the filter strategy must equal the merged exact scans
-        merged_fast = step(0)
-        eng.set_strategy("exact")
-        merged_exact = step(0)
-        eng.set_strategy(args.strategy)
-        if rank == 0:
-            verify["sharded_merge_equals_exact_ids"] = bool(np.array_equal(merged_fast[0], merged_exact[0]))
-            verify["sharded_merge_max_abs_err"] = float(np.abs(merged_fast[1] - merged_exact[1]).max())
-    gate_red = (not verify["filter_equals_exact_scan_ids"] or verify["filter_equals_exact_scan_max_abs_err"] > 1e-5
-                or verify.get("oracle_ids_equal") is False or verify.get("oracle_max_abs_err", 0.0) > 1e-5
-                or verify.get("sharded_merge_equals_exact_ids") is False)
-    if world > 1:  # one red rank fails the whole job: every rank learns it and exits non-zero after this exchange
-        flag = torch.tensor([1.0 if gate_red else 0.0], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
-        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-        gate_red = bool(flag.item() > 0)
-    if gate_red:
-        log(f"PARITY GATE FAILED: {verify}")
-        if rank == 0:
-            sys.stdout.flush()
-            os.write(json_fd, (json.dumps({"metric": "queries/sec, exact cosine kNN k=10 over a row-sharded Nx768 fp32 corpus (10M rows per GPU)",
-                                           "value": None, "unit": "queries/s", "n_gpus": world, "steps": args.steps,
-                                           "warmup": args.warmup, "error": "parity gate failed: results differ from the exact scan / oracle",
-                                           "parity_gate": verify}) + "\n").encode())
+            small = HipScanEngine(d, args.space, device=local_rank, strategy="filter" if d % 64 == 0 else "exact")
+            small.append(sample_rows)
+            if args.tombstones > 0.0:
+                small.tombstone(np.nonzero(sample_dead)[0].astype(np.int64))
+            sl, sd, _ = small.search(q_host[:64], k)
+            small.close()
+            ol, od, _ = exact_scan.knn(q_host[:64], sample_rows, k, args.space,
+                                       deleted=sample_dead if args.tombstones > 0.0 else None)
+            verify["oracle_sample"] = f"{sample_rows.shape[0]} rows x 64 queries"
+            verify["oracle_ids_equal"] = bool(np.array_equal(sl, ol))
+            verify["oracle_max_abs_err"] = float(np.abs(sd - od).max())
         if world > 1:
-            dist.destroy_process_group()
-        sys.exit(1)
+            # sharded path: the host-merged answer of the filter strategy must equal the merged exact scans
+            merged_fast = step(0)
+            eng.set_strategy("exact")
+            merged_exact = step(0)
+            eng.set_strategy(args.strategy)
+            if rank == 0:
+                verify["sharded_merge_equals_exact_ids"] = bool(np.array_equal(merged_fast[0], merged_exact[0]))
+                verify["sharded_merge_max_abs_err"] = float(np.abs(merged_fast[1] - merged_exact[1]).max())
+        gate_red = (not verify["filter_equals_exact_scan_ids"] or verify["filter_equals_exact_scan_max_abs_err"] > 1e-5
+                    or verify.get("oracle_ids_equal") is False or verify.get("oracle_max_abs_err", 0.0) > 1e-5
+                    or verify.get("sharded_merge_equals_exact_ids") is False)
+        if world > 1:  # one red rank fails the whole job: every rank learns it and exits non-zero after this exchange
+            flag = torch.tensor([1.0 if gate_red else 0.0], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+            gate_red = bool(flag.item() > 0)
+        if gate_red:
+            log(f"PARITY GATE FAILED: {verify}")
+            if rank == 0:
+                sys.stdout.flush()
+                os.write(json_fd, (json.dumps({"metric": "queries/sec, exact cosine kNN k=10 over a row-sharded Nx768 fp32 corpus (10M rows per GPU)",
+                                               "value": None, "unit": "queries/s", "n_gpus": world, "steps": args.steps,
+                                               "warmup": args.warmup, "error": "parity gate failed: results differ from the exact scan / oracle",
+                                               "parity_gate": verify}) + "\n").encode())
+            if world > 1:
+                dist.destroy_process_group()
+            sys.exit(1)
 
     # ---- timed region
     def barrier():
@@ -588,11 +599,11 @@ def main() -> None:
             dumped = dump_outputs(args.dump_outputs, dict(zip(("labels", "distances", "counts"), last)))
     scan_ms, scan_launches, rows_scanned = st["scan_ms"], st["scan_launches"], st["rows_scanned"]
     rescored, fallbacks = st["candidates_rescored"], st["fallback_queries"]
-    # ---- sustained rate (N = 1): the K timed steps above are a 40 ms burst on a power-limited kernel; a server gets the
+    # ---- sustained rate (N = 1, --full): the K timed steps above are a 40 ms burst on a power-limited kernel; a server gets the
     # rate the chip holds for seconds.  Both wave modes again, >= --sustained-seconds and >= 1000 waves each, same rotation of
     # query batches, scan-kernel events on (what the first seconds of load cost in clock shows in scan_avg_launch_ms).
     sustained = None
-    if world == 1 and args.sustained_seconds > 0:
+    if world == 1 and args.full and args.sustained_seconds > 0:
         n_sus = max(1000, int(args.sustained_seconds * 1.1 / max(elapsed / args.steps, 1e-4)) + 1)
         sustained = {"waves_per_mode": n_sus, "query_batches": nqb,
                      "effective_clock_ghz": None,
@@ -617,22 +628,23 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # latency of a single wave (host-synchronised), measured outside the throughput region.  Device-resident: queries
-    # and outputs already in HBM.  host_io (SURVEY 8d's latency definition): the host-pointer entry, i.e. H2D of the
-    # queries and D2H of labels / distances / counts included.
+    # latency of a single wave (--full; host-synchronised), measured outside the throughput region.  Device-resident:
+    # queries and outputs already in HBM.  host_io (SURVEY 8d's latency definition): the host-pointer entry, i.e. H2D of
+    # the queries and D2H of labels / distances / counts included.
     per_step, per_step_io = [], []
-    for _ in range(10):
-        torch.cuda.synchronize()
-        ts = time.perf_counter()
-        step()
-        torch.cuda.current_stream().synchronize()
-        per_step.append(time.perf_counter() - ts)
-    if world == 1:
-        for _ in range(35):
+    if args.full:
+        for _ in range(10):
+            torch.cuda.synchronize()
             ts = time.perf_counter()
-            eng.search(q_host, k)
-            per_step_io.append(time.perf_counter() - ts)
-        per_step_io = per_step_io[5:]
+            step()
+            torch.cuda.current_stream().synchronize()
+            per_step.append(time.perf_counter() - ts)
+        if world == 1:
+            for _ in range(35):
+                ts = time.perf_counter()
+                eng.search(q_host, k)
+                per_step_io.append(time.perf_counter() - ts)
+            per_step_io = per_step_io[5:]
 
     ms_per_step = elapsed / args.steps * 1e3
     shard_queries_per_s = world * batch * args.steps / elapsed  # one unit = one query against one 10M-row shard
@@ -643,8 +655,8 @@ def main() -> None:
     roofline = None
     if scan_ms > 0:
         scan_s = scan_ms * 1e-3
-        filt = stats0["strategy_used"] == 2
-        i8 = filt and stats0.get("bound_dtype") == 2  # the int8 shadow computed the bounds (dim % 256 == 0)
+        filt = st["strategy_used"] == 2
+        i8 = filt and st.get("bound_dtype") == 2  # the int8 shadow computed the bounds (dim % 256 == 0)
         # Two physical floors of the scan kernel as built: the matrix-core time of 2*rows*d*256 multiply-adds
         # at the dense peak of the operand type, and the HBM time of the bytes the kernel has to move -- the shadow it
         # streams (1 B / 2 B per element) + 8 B / 4 B of row constants per row + the query image.  The roof that binds
@@ -707,15 +719,15 @@ def main() -> None:
         "n_gpus": ranks_ran, "rccl_ranks": rccl_ranks, "rank_devices": rank_devices,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": (("i8" if stats0.get("bound_dtype") == 2 else "bf16") + " (MFMA bounds) + f64 (exact rescoring of the f32 rows)")
-                 if stats0["strategy_used"] == 2 else "f64 (exact scan of the f32 rows)",
+        "dtype": (("i8" if st.get("bound_dtype") == 2 else "bf16") + " (MFMA bounds) + f64 (exact rescoring of the f32 rows)")
+                 if st["strategy_used"] == 2 else "f64 (exact scan of the f32 rows)",
         "data": "synthetic",
         "config": {"workload": f"BASELINE configs[{2 if world == 1 else 4}]: {world * n_local} x {d} fp32 N(0,1) "
                                f"rows ({n_local}/GPU), {args.space} kNN k={k}, batch={batch}, exact ids "
-                               f"({'int8' if stats0.get('bound_dtype') == 2 else 'bf16'}-MFMA bound filter + fp64 rescoring)",
+                               f"({'int8' if st.get('bound_dtype') == 2 else 'bf16'}-MFMA bound filter + fp64 rescoring)",
                    "rows_per_gpu": n_local, "dim": d, "k": k, "batch": batch, "space": args.space,
                    "tombstoned_fraction": args.tombstones,
-                   "strategy": {1: "exact", 2: "filter"}.get(stats0["strategy_used"], "?"),
+                   "strategy": {1: "exact", 2: "filter"}.get(st["strategy_used"], "?"),
                    "sharding": f"row-wise over {world} ranks, host merge of per-shard top-k"},
         "whole_corpus_qps": round(batch * args.steps / elapsed, 1),
         "host_enqueue_ms_per_wave": round(host_enqueue_s / args.steps * 1e3, 3) if host_enqueue_s is not None else None,
@@ -726,19 +738,19 @@ def main() -> None:
         "value_back_to_back": (round(shard_queries_per_s, 1) if args.wave_mode == "back_to_back" else other["value"]) if world == 1 else None,
         "value_synchronised": (round(shard_queries_per_s, 1) if args.wave_mode == "synchronised" else other["value"]) if world == 1 else None,
         "sustained": sustained,
-        "p50_ms_per_wave": round(float(np.median(per_step)) * 1e3, 3),
+        "p50_ms_per_wave": round(float(np.median(per_step)) * 1e3, 3) if per_step else None,
         "p50_ms_per_wave_host_io": round(float(np.median(per_step_io)) * 1e3, 3) if per_step_io else None,
         "roofline": roofline,
         "candidates_rescored_per_query": round(rescored / max(1, args.steps * batch), 1),
         "fallback_queries": int(fallbacks),
-        "parity_gate": verify,
+        "parity_gate": verify,  # (null, like sustained and the latencies, unless --full)
         "load_s": round(load_s, 1),
     }
     if dumped is not None:
         out["outputs_dumped"] = dumped
 
-    # ---- CPU exact-scan baseline (rank 0, N=1): this repo's NumPy/OpenBLAS scan on a bounded sample
-    if world == 1 and not args.no_cpu_baseline:
+    # ---- CPU exact-scan baseline (rank 0, N=1, --full): this repo's NumPy/OpenBLAS scan on a bounded sample
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle.blas_scan import BlasScanEngine
 
         # the CPU scan is timed THROUGH the same surface as the GPU path -- QueryProcessor.find_similar_many ->
@@ -825,9 +837,9 @@ def main() -> None:
             out["config2_1Mx768_batch1"] = side
         if not args.no_extras:
             out["config1_10kx128_find_similar"] = config1_side(local_rank)
-    # ---- top_k = 100 (top_k 65..1024 stays on the filter path): one wave of the same batch, gated against
+    # ---- top_k = 100 (--full; VERDICT r3 item 1: top_k 65..1024 stays on the filter path): one wave of the same batch, gated against
     # the exact scan for every query, timed device-resident like p50_ms_per_wave
-    if world == 1 and not args.no_extras and args.tombstones == 0.0:
+    if world == 1 and args.full and not args.no_extras and args.tombstones == 0.0:
         k2 = 100
         lab2 = torch.empty((batch, k2), dtype=torch.int64, device=dev)
         dst2 = torch.empty((batch, k2), dtype=torch.float32, device=dev)
@@ -860,11 +872,11 @@ def main() -> None:
             out["error"] = "top_k = 100 results differ from the exact scan"
             os.write(json_fd, (json.dumps(out) + "\n").encode())
             sys.exit(1)
-    # ---- the same workload through the Protocol surface: QueryProcessor.find_similar_many over Index.search_many
+    # ---- (--full) the same workload through the Protocol surface: QueryProcessor.find_similar_many over Index.search_many
     # (reference query_processor.py:26-49 batched).  Every hit comes back as {"id": UUID, "values": float32[d],
     # "metadata", "score"}; values are gathered from the index's rows in HBM.  "stream" = find_similar_stream: the scan
     # of wave i+1 overlaps the enrichment of wave i (one worker thread inside the GIL-free ctypes call).
-    if world == 1 and args.tombstones == 0.0 and not args.no_extras:
+    if world == 1 and args.full and args.tombstones == 0.0 and not args.no_extras:
         # A serving process with a 10M-row heap freezes what it has loaded (gc.freeze: the objects alive now are never walked
         # again by the cyclic collector); without it a full collection that lands inside the 20-wave stream below costs
         # tens of milliseconds and the figure measures the collector's phase, not the path (seen: 2.2 vs 8 ms per wave)

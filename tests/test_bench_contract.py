@@ -135,3 +135,10 @@ def test_a_contradicting_world_size_exits_non_zero_before_any_gpu_work():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "8"], env=env, capture_output=True, timeout=120)
     assert r.returncode == 2 and b"WORLD_SIZE=1" in r.stderr and r.stdout.strip() == b""
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "3", "--full"])
+    assert bench.parse_args().full is True

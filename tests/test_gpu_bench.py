@@ -25,7 +25,7 @@ def test_bare_gpus_2_starts_two_ranks_and_passes_the_sharded_gate():
     box's one GPU: --single-device, gloo), every rank scans its own 300k-row shard for the 1024-query wave (four passes), rank 0
     merges on the host; the merged ids must equal the merged exact scans."""
     d = _run(["--gpus", "2", "--single-device", "--backend", "gloo", "--rows-per-gpu", "300000", "--steps", "3", "--warmup", "1",
-              "--no-cpu-baseline", "--no-extras"])
+              "--full", "--no-cpu-baseline", "--no-extras"])
     assert d["n_gpus"] == 2 and d["rank_devices"] == [0, 0] and d["scaling"] == "weak"
     gate = d["parity_gate"]
     assert gate["sharded_merge_equals_exact_ids"] is True and gate["filter_equals_exact_scan_ids"] is True
@@ -51,7 +51,7 @@ def test_dump_outputs_of_two_identical_runs_are_identical(tmp_path):
 
 
 def test_one_gpu_line_has_the_contract_keys_on_a_small_shard():
-    d = _run(["--rows-per-gpu", "400000", "--steps", "3", "--warmup", "1", "--no-extras", "--cpu-sample-rows", "100000"])
+    d = _run(["--rows-per-gpu", "400000", "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--cpu-sample-rows", "100000"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -73,3 +73,20 @@ def test_one_gpu_line_has_the_contract_keys_on_a_small_shard():
     assert r["frac_basis"].endswith("shadow bytes") and r["alg_frac"] == r["alg_hbm_frac"] and r["alg_frac"] > r["frac"]
     # (--wave-mode back_to_back swaps which region is `value`: the same code path with the flag inverted; both regions ran here)
     assert d["host_enqueue_ms_per_wave"] > 0
+
+
+def test_a_plain_run_times_the_steps_and_leaves_the_rest_to_full():
+    """Without --full the line carries the headline keys and the figures of the timed steps themselves (both wave modes,
+    roofline from their scan events); the parity gate, the sustained rate, the latencies, the CPU baseline and the side
+    configs are not run."""
+    d = _run(["--rows-per-gpu", "400000", "--steps", "3", "--warmup", "1"])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config",
+                "roofline"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and "MFMA bounds" in d["dtype"]
+    assert abs(d["value"] - 256 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01
+    assert d["other_wave_mode"]["wave_mode"] == "back_to_back" and d["value_synchronised"] == d["value"]
+    assert d["parity_gate"] is None and d["sustained"] is None and d["p50_ms_per_wave"] is None
+    for key in ("cpu_baseline", "config1_10kx128_find_similar", "config2_1Mx768_batch1", "config4_10Mx768_l2_range", "topk100",
+                "protocol_qps"):
+        assert key not in d, key

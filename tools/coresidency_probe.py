@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Does a second resident 10M x 768 index slow the first one's waves?  (bench.py keeps the cosine and the l2 engine resident
+"""Does a second resident 10M x 768 index slow the first one's waves?  (bench.py --full keeps the cosine and the l2 engine resident
 together; tools/wave_profile.py measures one engine alone.)  Host-pointer kNN waves, p50 of 30, in this order: l2 alone; l2 with
 a cosine engine resident beside it; l2 again after the cosine engine was closed."""
 import sys

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The measurements a round commits under profiles/rNN/, in ONE gpurun call (from the repository root):
 #   tools/measure_round.sh <tag> [bench|stats|pmc|sq ...]      default: bench stats pmc
-#   bench  python bench.py (the driver's command)                        -> gpurun_out/<tag>/bench_n1.json
+#   bench  python bench.py --full (the headline and everything beside it) -> $out/bench_n1.json
 #   stats  rocprofv3 --kernel-trace --stats of the same command          -> gpurun_out/<tag>/kstats/run_results.db
 #          (ROCm 7.2 writes a rocpd database: tools/rocpd_stats.py turns it into the per-kernel CSV that is committed)
 #   pmc    rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, --kernel-trace only (gpurun refuses other trace domains with
@@ -19,9 +19,9 @@ short="--steps 4 --warmup 1 --no-cpu-baseline --no-extras --sustained-seconds 0"
 for w in $what; do
   case $w in
     bench)
-      timeout -k 10 600 python3 $R/bench.py > $out/bench_n1.json 2> $out/bench_n1.err; echo "bench rc=$?" | tee -a $out/log.txt ;;
+      timeout -k 10 600 python3 $R/bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err; echo "bench rc=$?" | tee -a $out/log.txt ;;
     stats)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $out/kstats -o run -- python3 $R/bench.py > $out/bench_n1_under_rocprof.json 2> $out/kstats.err
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $out/kstats -o run -- python3 $R/bench.py --full > $out/bench_n1_under_rocprof.json 2> $out/kstats.err
       echo "stats rc=$?" | tee -a $out/log.txt ;;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do
