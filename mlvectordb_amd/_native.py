@@ -89,6 +89,20 @@ WHERE_SIGNATURES = {
                                                  _P, _P, _P, _P]),
 }
 
+# include/mlvdb_where_each.h: per-query filters in one batched kNN call (their own table, like WHERE_SIGNATURES)
+WHERE_EACH_MAX_PROGRAMS = 64
+WHERE_EACH_MAX_OPS = 1024
+ROUTE_NONE = 0
+ROUTE_SCAN = 1
+ROUTE_GATHER = 2
+ROUTE_NAMES = {ROUTE_NONE: "none", ROUTE_SCAN: "scan", ROUTE_GATHER: "gather"}
+
+WHERE_EACH_SIGNATURES = {
+    "mlvdb_search_batch_where_each": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(Where), C.c_int32, _P,
+                                                _P, _P, _P, _P, _P]),
+    "mlvdb_where_count_each": (C.c_int, [_P, C.POINTER(Where), C.c_int32, _P]),
+}
+
 _lib = None
 
 
@@ -117,7 +131,7 @@ def load() -> C.CDLL:
             f"`python -c 'import __graft_entry__ as g; g.build()'` or `make -C mlvectordb_amd/csrc`. "
             f"There is no CPU fallback for the search path.")
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -111,6 +111,9 @@ struct mlvdb_index {
     int64_t* attr_col[MLVDB_MAX_ATTRS] = {};  // nullptr while capacity == 0
     std::vector<WhereOp> where_ops;
     DevBuf where_prog, where_cnt;
+    // per-query filters (mlvdb_where_each.h): the call's programs, one 64-bit word per row, per-segment counts / offsets,
+    // match totals, the gathered route's label lists, tiles, queries and outputs
+    DevBuf each_prog, each_bits, each_seg, each_tot, each_lab, each_tiles, each_q, each_qpad, each_qaux, each_out;
     // fp16 row-major shadow for the mid bounds (kernels_refine.hip): built lazily by the first range query / top_k > 64 search
     DevBuf x16, s16, rowerr16, picks, npicks;
     int64_t l2_rows = 0;      // rows [0, l2_rows) of the fp16 shadow are current (0 after compact / reset / regrowth)
@@ -1278,6 +1281,9 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     attr_release(h->attr_col);
     h->where_prog.release();
     h->where_cnt.release();
+    for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
+                      &h->each_qpad, &h->each_qaux, &h->each_out})
+        b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
     h->pin_out.release();
@@ -2326,6 +2332,294 @@ int mlvdb_range_batch_packed_where(mlvdb_index* h, const float* queries, int64_t
     };
     if (h->total == 0) return call();
     return with_row_mask(h, nq, call);
+    });
+}
+
+extern "C++" {
+namespace {
+// ---- per-query filters (mlvdb_where_each.h)
+constexpr int32_t kGatherQT = 4;  // queries per tile of the gathered kernel (fewer only when the tile would not fit in LDS)
+
+// The programs of a call validated (where_prepare, each against its own set table) and packed for the device: ops
+// concatenated (off[p] .. off[p + 1]), the IN ranges rebased onto one concatenated set table.
+// Every column op also carries its column's slot in `cols` (the referenced columns, each read once per row by the
+// evaluation) in the high bits of its type.
+struct EachPrograms {
+    std::vector<WhereOp> ops;
+    std::vector<int32_t> off;
+    std::vector<int64_t> set;
+    std::vector<const int64_t*> cols;
+};
+
+int where_each_pack(mlvdb_index* h, const mlvdb_where* programs, int32_t n, EachPrograms& out) {
+    if (n < 0 || n > MLVDB_WHERE_EACH_MAX_PROGRAMS)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "n_programs outside 0..MLVDB_WHERE_EACH_MAX_PROGRAMS");
+    if (n > 0 && !programs) return fail(h, MLVDB_ERR_INVALID_ARG, "programs is null");
+    int64_t n_ops = 0;
+    for (int32_t p = 0; p < n; ++p) n_ops += programs[p].n_ops > 0 ? programs[p].n_ops : 0;
+    if (n_ops > MLVDB_WHERE_EACH_MAX_OPS) return fail(h, MLVDB_ERR_INVALID_ARG, "more than MLVDB_WHERE_EACH_MAX_OPS ops over all programs");
+    out.ops.clear();
+    out.set.clear();
+    out.cols.clear();
+    out.off.assign(1, 0);
+    for (int32_t p = 0; p < n; ++p) {
+        if (int rc = where_prepare(h, &programs[p])) return rc;
+        const int64_t rebase = (int64_t)out.set.size();
+        for (WhereOp o : h->where_ops) {
+            if (o.op == MLVDB_WHERE_IN) o.a += rebase;
+            if (o.col) {
+                const auto* col = static_cast<const int64_t*>(o.col);
+                auto it = std::find(out.cols.begin(), out.cols.end(), col);
+                if (it == out.cols.end()) it = out.cols.insert(out.cols.end(), col);
+                o.type |= (int32_t)(it - out.cols.begin()) << 8;
+            }
+            out.ops.push_back(o);
+        }
+        out.set.insert(out.set.end(), programs[p].set, programs[p].set + programs[p].n_set);
+        out.off.push_back((int32_t)out.ops.size());
+    }
+    return MLVDB_OK;
+}
+
+// Segments of the evaluation / scatter (kernels_where_each.hip): one wave per run of seg_rows rows.
+struct EachSegs {
+    int64_t seg_rows = 64;
+    int32_t nseg = 0;
+};
+
+EachSegs each_segments(int64_t total) {
+    EachSegs sg;
+    if (total <= 0) return sg;
+    const int64_t want = std::min<int64_t>(4096, (total + 63) / 64);
+    sg.seg_rows = ((total + want - 1) / want + 63) / 64 * 64;
+    sg.nseg = (int32_t)((total + sg.seg_rows - 1) / sg.seg_rows);
+    return sg;
+}
+
+// Every program on every row in one pass: h->each_bits, the per-segment counts (exclusive offsets afterwards) and
+// matches[p] on the host (the call's one synchronisation).  Requires h->total > 0 and at least one program.
+int where_each_eval(mlvdb_index* h, const EachPrograms& pk, const EachSegs& sg, int64_t* matches) {
+    hipStream_t s = h->stream;
+    const int32_t n = (int32_t)pk.off.size() - 1;
+    const size_t obytes = pk.ops.size() * sizeof(WhereOp), fbytes = pk.off.size() * sizeof(int32_t);
+    const size_t sbytes = pk.set.size() * sizeof(int64_t), cbytes = pk.cols.size() * sizeof(void*);
+    const size_t foff = obytes, soff = (foff + fbytes + 15) / 16 * 16, coff = soff + sbytes;
+    HIP_TRY(h, h->each_prog.ensure(coff + cbytes + 16));
+    HIP_TRY(h, h->each_bits.ensure((size_t)h->total * sizeof(unsigned long long)));
+    HIP_TRY(h, h->each_seg.ensure((size_t)n * sg.nseg * sizeof(uint32_t)));
+    HIP_TRY(h, h->each_tot.ensure((size_t)(2 * kWhereEachMaxPrograms) * sizeof(int64_t)));  // [totals | label bases]
+    char* dp = h->each_prog.as<char>();
+    HIP_TRY(h, hipMemcpyAsync(dp, pk.ops.data(), obytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(dp + foff, pk.off.data(), fbytes, hipMemcpyHostToDevice, s));
+    if (sbytes) HIP_TRY(h, hipMemcpyAsync(dp + soff, pk.set.data(), sbytes, hipMemcpyHostToDevice, s));
+    if (cbytes) HIP_TRY(h, hipMemcpyAsync(dp + coff, pk.cols.data(), cbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_where_each_eval(reinterpret_cast<const WhereOp*>(dp), reinterpret_cast<const int32_t*>(dp + foff), n,
+                                      (int32_t)pk.ops.size(), reinterpret_cast<const int64_t*>(dp + soff),
+                                      reinterpret_cast<const int64_t* const*>(dp + coff), (int32_t)pk.cols.size(), h->rn, h->total,
+                                      sg.seg_rows, sg.nseg, h->each_bits.as<unsigned long long>(), h->each_seg.as<uint32_t>(), s));
+    HIP_TRY(h, launch_where_each_scan(h->each_seg.as<uint32_t>(), n, sg.nseg, h->each_tot.as<int64_t>(), s));
+    HIP_TRY(h, hipMemcpyAsync(matches, h->each_tot.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
+    return MLVDB_OK;
+}
+
+// The queries `sel` of a host batch as one contiguous host batch.
+std::vector<float> pick_queries(const float* queries, int32_t dim, const std::vector<int32_t>& sel) {
+    std::vector<float> out(sel.size() * (size_t)dim);
+    for (size_t i = 0; i < sel.size(); ++i)
+        std::memcpy(out.data() + i * dim, queries + (size_t)sel[i] * dim, (size_t)dim * sizeof(float));
+    return out;
+}
+
+// Outputs of a sub-batch (rows 0..sel.size()-1 of lab / dist / cnt / d64) into the caller's rows sel[i].
+void put_rows(const std::vector<int32_t>& sel, int32_t k, const int64_t* lab, const float* dist, const int32_t* cnt,
+              const double* d64, int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
+    for (size_t i = 0; i < sel.size(); ++i) {
+        const size_t q = (size_t)sel[i];
+        std::memcpy(out_labels + q * k, lab + i * k, (size_t)k * sizeof(int64_t));
+        std::memcpy(out_dist + q * k, dist + i * k, (size_t)k * sizeof(float));
+        if (out_dist64) std::memcpy(out_dist64 + q * k, d64 + i * k, (size_t)k * sizeof(double));
+        out_counts[q] = cnt[i];
+    }
+}
+
+// search_host of the sub-batch `sel` (masked by h->row_mask when `masked`), scattered into the caller's rows.
+int search_rows(mlvdb_index* h, const float* queries, const std::vector<int32_t>& sel, int32_t k, bool masked,
+                int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
+    const int64_t m = (int64_t)sel.size();
+    const std::vector<float> q = pick_queries(queries, h->dim, sel);
+    std::vector<int64_t> lab((size_t)m * k);
+    std::vector<float> dist((size_t)m * k);
+    std::vector<int32_t> cnt((size_t)m);
+    std::vector<double> d64(out_dist64 ? (size_t)m * k : 0);
+    double* p64 = out_dist64 ? d64.data() : nullptr;
+    auto call = [&]() { return search_host(h, q.data(), m, k, lab.data(), dist.data(), cnt.data(), p64); };
+    const int rc = masked ? with_row_mask(h, m, call) : call();
+    if (rc) return rc;
+    put_rows(sel, k, lab.data(), dist.data(), cnt.data(), p64, out_labels, out_dist, out_counts, out_dist64);
+    return MLVDB_OK;
+}
+
+// The GATHER route for the programs `gp` (their queries in qof[p], matches[p] rows each): label lists, tiles, the gathered
+// kernel, exact_merge_kernel, outputs into the caller's rows.
+int gather_programs(mlvdb_index* h, const float* queries, int32_t k, int32_t qt, const EachSegs& sg, int32_t n_programs,
+                    const std::vector<int32_t>& gp, const std::vector<std::vector<int32_t>>& qof, const int64_t* matches,
+                    int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
+    hipStream_t s = h->stream;
+    std::vector<int64_t> base(kWhereEachMaxPrograms, 0);
+    std::vector<int32_t> sel;  // the gathered queries, sorted by program (positions of the prepared batch)
+    std::vector<GatherTile> tiles;
+    unsigned long long gmask = 0;
+    int64_t nlab = 0, max_m = 0;
+    for (int32_t p : gp) {
+        gmask |= 1ull << p;
+        base[p] = nlab;
+        const std::vector<int32_t>& qs = qof[p];
+        for (size_t t0 = 0; t0 < qs.size(); t0 += qt) {
+            GatherTile t;
+            t.lab_begin = (int32_t)nlab;
+            t.lab_count = (int32_t)matches[p];
+            t.sel0 = (int32_t)sel.size() + (int32_t)t0;
+            t.nsel = (int32_t)std::min<size_t>(qt, qs.size() - t0);
+            tiles.push_back(t);
+        }
+        sel.insert(sel.end(), qs.begin(), qs.end());
+        nlab += matches[p];
+        max_m = std::max(max_m, matches[p]);
+    }
+    const int32_t ng = (int32_t)sel.size(), ntiles = (int32_t)tiles.size();
+    // chunks per tile: enough blocks to fill the chip (~2048), none shorter than 64 rows, at most 64 partial lists per query
+    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>({64, (2048 + ntiles - 1) / ntiles, (max_m + 63) / 64}));
+    // label lists: one scatter pass over the bit words
+    HIP_TRY(h, h->each_lab.ensure((size_t)nlab * sizeof(int32_t)));
+    HIP_TRY(h, hipMemcpyAsync(h->each_tot.as<int64_t>() + kWhereEachMaxPrograms, base.data(), base.size() * sizeof(int64_t),
+                              hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_where_each_scatter(h->each_bits.as<unsigned long long>(), h->total, sg.seg_rows, sg.nseg, n_programs,
+                                         h->each_seg.as<uint32_t>(), gmask, h->each_tot.as<int64_t>() + kWhereEachMaxPrograms,
+                                         h->each_lab.as<int32_t>(), s));
+    // the gathered queries, prepared as every exact path prepares them
+    const std::vector<float> q = pick_queries(queries, h->dim, sel);
+    HIP_TRY(h, h->each_q.ensure(q.size() * sizeof(float)));
+    HIP_TRY(h, h->each_qpad.ensure((size_t)ng * h->ld * sizeof(float)));
+    HIP_TRY(h, h->each_qaux.ensure((size_t)ng * sizeof(double)));
+    HIP_TRY(h, h->each_tiles.ensure(tiles.size() * sizeof(GatherTile)));
+    HIP_TRY(h, hipMemcpyAsync(h->each_q.p, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->each_tiles.p, tiles.data(), tiles.size() * sizeof(GatherTile), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_query_prep(h->each_q.as<float>(), ng, h->dim, h->ld, h->space, h->each_qpad.as<float>(),
+                                 h->each_qaux.as<double>(), nullptr, s));
+    HIP_TRY(h, h->partial.ensure((size_t)ng * nchunk * k * sizeof(TopEntry)));
+    HIP_TRY(h, launch_where_gather(h->X, h->each_qpad.as<float>(), h->each_qaux.as<double>(), h->each_lab.as<int32_t>(),
+                                   h->each_tiles.as<GatherTile>(), ntiles, h->ld, h->space, qt, k, (int32_t)nchunk,
+                                   h->partial.as<TopEntry>(), s));
+    // outputs [d64 | labels | dist | counts] in the sorted order, one copy back
+    const size_t b64 = (size_t)ng * k * sizeof(double), blab = (size_t)ng * k * sizeof(int64_t);
+    const size_t bdist = (size_t)ng * k * sizeof(float), bcnt = (size_t)ng * sizeof(int32_t);
+    HIP_TRY(h, h->each_out.ensure(b64 + blab + bdist + bcnt));
+    char* dout = h->each_out.as<char>();
+    HIP_TRY(h, launch_exact_merge(h->partial.as<TopEntry>(), ng, nullptr, nullptr, (int32_t)nchunk, k,
+                                  reinterpret_cast<int64_t*>(dout + b64), reinterpret_cast<float*>(dout + b64 + blab),
+                                  reinterpret_cast<int32_t*>(dout + b64 + blab + bdist), reinterpret_cast<double*>(dout), s));
+    std::vector<char> host(b64 + blab + bdist + bcnt);
+    HIP_TRY(h, hipMemcpyAsync(host.data(), dout, host.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    const char* ho = host.data();
+    put_rows(sel, k, reinterpret_cast<const int64_t*>(ho + b64), reinterpret_cast<const float*>(ho + b64 + blab),
+             reinterpret_cast<const int32_t*>(ho + b64 + blab + bdist), reinterpret_cast<const double*>(ho), out_labels,
+             out_dist, out_counts, out_dist64);
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_where_count_each(mlvdb_index* h, const mlvdb_where* programs, int32_t n_programs, int64_t* out_matches) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    EachPrograms pk;
+    if ((rc = where_each_pack(h, programs, n_programs, pk))) return rc;
+    if (n_programs > 0 && !out_matches) return fail(h, MLVDB_ERR_INVALID_ARG, "out_matches is null");
+    for (int32_t p = 0; p < n_programs; ++p) out_matches[p] = 0;
+    if (n_programs == 0 || h->total == 0) return MLVDB_OK;
+    return where_each_eval(h, pk, each_segments(h->total), out_matches);
+    });
+}
+
+int mlvdb_search_batch_where_each(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const mlvdb_where* programs,
+                                  int32_t n_programs, const int32_t* program_of_query, int64_t* out_labels, float* out_dist,
+                                  int32_t* out_counts, double* out_dist64, int32_t* out_routes) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (k > MLVDB_MAX_TOPK_PAGED) return fail(h, MLVDB_ERR_UNSUPPORTED, "k above MLVDB_MAX_TOPK_PAGED");
+    EachPrograms pk;
+    if ((rc = where_each_pack(h, programs, n_programs, pk))) return rc;
+    if (nq > 0 && (!queries || !program_of_query || !out_labels || !out_dist || !out_counts))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    std::vector<std::vector<int32_t>> qof((size_t)n_programs);  // each program's queries, ascending
+    std::vector<int32_t> plain;                                  // the unfiltered ones
+    for (int64_t i = 0; i < nq; ++i) {
+        const int32_t p = program_of_query[i];
+        if (p < -1 || p >= n_programs) return fail(h, MLVDB_ERR_INVALID_ARG, "program_of_query entry outside [-1, n_programs)");
+        (p < 0 ? plain : qof[(size_t)p]).push_back((int32_t)i);
+    }
+    std::vector<int32_t> routes((size_t)n_programs, MLVDB_WHERE_ROUTE_NONE);
+    std::vector<int64_t> matches((size_t)n_programs, 0);
+    const EachSegs sg = each_segments(h->total);
+    bool any = false;
+    for (const auto& qs : qof) any = any || !qs.empty();
+    if (any && h->total > 0) {
+        rc = where_each_eval(h, pk, sg, matches.data());
+        if (rc) return rc;
+    }
+    // routes: GATHER while the gathered rows stay a small share of what the masked scan would read
+    int32_t qt = kGatherQT;
+    while (qt > 1 && where_gather_lds(qt, h->ld) > 64 * 1024) qt >>= 1;
+    const bool gather_fits = k <= MLVDB_MAX_TOPK && where_gather_lds(qt, h->ld) <= 64 * 1024;
+    const __int128 live = h->total - h->deleted;
+    std::vector<int32_t> gp, sp;
+    int64_t nlab = 0;
+    for (int32_t p = 0; p < n_programs; ++p) {
+        const size_t nqp = qof[(size_t)p].size();
+        if (nqp == 0 || matches[(size_t)p] == 0) continue;
+        const __int128 tiles = (__int128)((nqp + qt - 1) / qt);
+        const bool gather = gather_fits && (__int128)matches[(size_t)p] * tiles * 1000 <= live * h->tn.where_gather &&
+                            nlab + matches[(size_t)p] <= INT32_MAX;
+        if (gather) nlab += matches[(size_t)p];
+        routes[(size_t)p] = gather ? MLVDB_WHERE_ROUTE_GATHER : MLVDB_WHERE_ROUTE_SCAN;
+        (gather ? gp : sp).push_back(p);
+    }
+    if (out_routes)
+        for (int32_t p = 0; p < n_programs; ++p) out_routes[p] = routes[(size_t)p];
+    // NONE: padding, as a call whose program matches nothing returns it
+    for (int32_t p = 0; p < n_programs; ++p) {
+        if (routes[(size_t)p] != MLVDB_WHERE_ROUTE_NONE) continue;
+        for (int32_t q : qof[(size_t)p]) {
+            for (int32_t j = 0; j < k; ++j) {
+                out_labels[(size_t)q * k + j] = -1;
+                out_dist[(size_t)q * k + j] = __builtin_inff();
+                if (out_dist64) out_dist64[(size_t)q * k + j] = __builtin_inf();
+            }
+            out_counts[q] = 0;
+        }
+    }
+    if (!gp.empty()) {
+        rc = gather_programs(h, queries, k, qt, sg, n_programs, gp, qof, matches.data(), out_labels, out_dist, out_counts,
+                             out_dist64);
+        if (rc) return rc;
+    }
+    // SCAN: the program's row mask out of its bit, then exactly the masked call of mlvdb_search_batch_where
+    for (int32_t p : sp) {
+        HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
+        HIP_TRY(h, launch_where_each_expand(h->each_bits.as<unsigned long long>(), p, h->total, h->row_mask.as<uint8_t>(),
+                                            h->stream));
+        rc = search_rows(h, queries, qof[(size_t)p], k, true, out_labels, out_dist, out_counts, out_dist64);
+        if (rc) return rc;
+    }
+    if (!plain.empty()) return search_rows(h, queries, plain, k, false, out_labels, out_dist, out_counts, out_dist64);
+    return MLVDB_OK;
     });
 }
 

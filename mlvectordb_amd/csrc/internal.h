@@ -9,6 +9,7 @@
 
 #include "../../include/mlvdb_hip.h"
 #include "../../include/mlvdb_where.h"
+#include "../../include/mlvdb_where_each.h"
 #include "layout.h"
 #include "wave_topk.h"
 
@@ -84,7 +85,8 @@ inline hipError_t ensure_dynamic_lds(std::atomic<uint64_t>& done, const void* ke
     X(exact_nt, "EXACT_NT", 1)                                                                                          \
     X(exact_nblk, "EXACT_NBLK", 0)                                                                                      \
     X(prefix_pf, "PREFIX_PF", 24)                                                                                       \
-    X(prefix_waves, "PREFIX_WAVES", 4)
+    X(prefix_waves, "PREFIX_WAVES", 4)                                                                                  \
+    X(where_gather, "WHERE_GATHER", 150) /* per-query filters: gather a program's rows when matches x query tiles x 1000 <= live x this (0: never; tools/where_each_ab.py) */
 
 struct Tuning {
 #define X(field, name, dflt) int field = dflt;
@@ -344,5 +346,35 @@ hipError_t launch_where_eval(const WhereOp* prog, int32_t n_ops, const int64_t* 
                              uint8_t* mask, unsigned long long* matches, hipStream_t s);
 hipError_t launch_attr_fill(int64_t* col, int64_t value, int64_t first, int64_t n, hipStream_t s);
 hipError_t launch_attr_gather(const int64_t* col, int64_t* ncol, const int32_t* old_of_new, int64_t live, hipStream_t s);
+
+// ---------------------------------------------------------------- per-query filters (kernels_where_each.hip)
+constexpr int kWhereEachMaxPrograms = MLVDB_WHERE_EACH_MAX_PROGRAMS;
+constexpr int kWhereEachMaxOps = MLVDB_WHERE_EACH_MAX_OPS;
+static_assert(sizeof(WhereOp) == 32, "the programs of a call are staged in 32 KiB of LDS");
+// one block row of the gathered kernel: <= QT queries of one program (positions sel0.. of the call's sorted query list)
+// and that program's label list labels[lab_begin, lab_begin + lab_count)
+struct GatherTile {
+    int32_t lab_begin, lab_count, sel0, nsel;
+};
+// bits[i]: bit p = row i is live and matches program p; seg_cnt[p][seg] = program p's matches in segment seg
+// (segment = rows [seg * seg_rows, (seg + 1) * seg_rows), seg_rows a multiple of 64)
+// (ops reach it with their column's slot in cols[] in the high bits of op.type: where_each_pack)
+hipError_t launch_where_each_eval(const WhereOp* prog, const int32_t* prog_off, int32_t n_progs, int32_t n_ops,
+                                  const int64_t* set, const int64_t* const* cols, int32_t ncols, const float* rn, int64_t total,
+                                  int64_t seg_rows, int32_t nseg, unsigned long long* bits, uint32_t* seg_cnt, hipStream_t s);
+// seg_cnt[p][*] -> exclusive prefix sums in place; totals[p] = program p's matches
+hipError_t launch_where_each_scan(uint32_t* seg_cnt, int32_t n_progs, int32_t nseg, int64_t* totals, hipStream_t s);
+// ascending label lists of the programs in gmask at labels + base[p]
+hipError_t launch_where_each_scatter(const unsigned long long* bits, int64_t total, int64_t seg_rows, int32_t nseg,
+                                     int32_t n_progs, const uint32_t* seg_off, unsigned long long gmask, const int64_t* base,
+                                     int32_t* labels, hipStream_t s);
+// mask[i] = bit p of bits[i]
+hipError_t launch_where_each_expand(const unsigned long long* bits, int32_t p, int64_t total, uint8_t* mask, hipStream_t s);
+// LDS of the gathered kernel for qt queries per tile (it must stay <= 64 KiB)
+size_t where_gather_lds(int32_t qt, int32_t ld);
+// partial[(sel * nchunk + chunk) * k + j] for every query of every tile (qt in 1, 2, 4; k <= 64)
+hipError_t launch_where_gather(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
+                               const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t space, int32_t qt, int32_t k,
+                               int32_t nchunk, TopEntry* partial, hipStream_t s);
 
 }  // namespace mlvdb

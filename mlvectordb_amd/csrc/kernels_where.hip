@@ -4,12 +4,12 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "where_common.h"
 
 namespace mlvdb {
 
-// One thread per row, grid-stride.  The program (<= 64 ops, 2 KiB) is staged in LDS; the boolean stack is one 32-bit
-// register (bit 0 = top).  Every op of the program is uniform over the wave, so the branches below never diverge; what
-// differs per lane is only the value each column op loads (8 coalesced bytes per row and referenced op).
+// One thread per row, grid-stride.  The program (<= 64 ops, 2 KiB) is staged in LDS and evaluated by where_eval_row
+// (where_common.h).
 __global__ __launch_bounds__(256) void where_eval_kernel(const WhereOp* __restrict__ prog, int32_t n_ops,
                                                          const int64_t* __restrict__ set, const float* __restrict__ rn,
                                                          int64_t total, uint8_t* __restrict__ mask,
@@ -26,56 +26,8 @@ __global__ __launch_bounds__(256) void where_eval_kernel(const WhereOp* __restri
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < total; i0 += stride) {
         const int64_t i = i0 + threadIdx.x;
         const bool in = i < total;
-        uint32_t st = 0;
-        for (int p = 0; p < n_ops; ++p) {
-            const WhereOp o = sp[p];
-            if (o.op == MLVDB_WHERE_AND || o.op == MLVDB_WHERE_OR) {
-                const uint32_t x = st & 1u, y = (st >> 1) & 1u;
-                st = ((st >> 2) << 1) | (o.op == MLVDB_WHERE_AND ? (x & y) : (x | y));
-                continue;
-            }
-            if (o.op == MLVDB_WHERE_NOT) {
-                st ^= 1u;
-                continue;
-            }
-            bool bit = true;  // MLVDB_WHERE_TRUE
-            if (o.op != MLVDB_WHERE_TRUE) {
-                const int64_t raw = in ? static_cast<const int64_t*>(o.col)[i] : INT64_MIN;
-                if (o.type == MLVDB_ATTR_INT64) {
-                    const bool have = raw != INT64_MIN;
-                    switch (o.op) {
-                        case MLVDB_WHERE_EQ: bit = have && raw == o.a; break;
-                        case MLVDB_WHERE_NE: bit = !(have && raw == o.a); break;
-                        case MLVDB_WHERE_LT: bit = have && raw < o.a; break;
-                        case MLVDB_WHERE_LE: bit = have && raw <= o.a; break;
-                        case MLVDB_WHERE_GT: bit = have && raw > o.a; break;
-                        case MLVDB_WHERE_GE: bit = have && raw >= o.a; break;
-                        case MLVDB_WHERE_EXISTS: bit = have; break;
-                        default: {  // MLVDB_WHERE_IN: binary search of set[a, a + b), sorted ascending
-                            int64_t lo = o.a, hi = o.a + o.b;
-                            while (lo < hi) {
-                                const int64_t mid = lo + ((hi - lo) >> 1);
-                                if (set[mid] < raw) lo = mid + 1; else hi = mid;
-                            }
-                            bit = have && lo < o.a + o.b && set[lo] == raw;
-                        }
-                    }
-                } else {  // float64: absent = NaN, so every ordered comparison of an absent value is false by itself
-                    const double v = __longlong_as_double(raw), a = __longlong_as_double(o.a);
-                    switch (o.op) {
-                        case MLVDB_WHERE_EQ: bit = v == a; break;
-                        case MLVDB_WHERE_NE: bit = !(v == a); break;
-                        case MLVDB_WHERE_LT: bit = v < a; break;
-                        case MLVDB_WHERE_LE: bit = v <= a; break;
-                        case MLVDB_WHERE_GT: bit = v > a; break;
-                        case MLVDB_WHERE_GE: bit = v >= a; break;
-                        default: bit = v == v;  // MLVDB_WHERE_EXISTS
-                    }
-                }
-            }
-            st = (st << 1) | (bit ? 1u : 0u);
-        }
-        const bool hit = in && (st & 1u) && rn[i] == rn[i];  // tombstoned rows (NaN norm) never match
+        const bool match = where_eval_row(sp, n_ops, set, i, in);
+        const bool hit = in && match && rn[i] == rn[i];  // tombstoned rows (NaN norm) never match
         if (in) mask[i] = hit ? 1 : 0;
         const unsigned long long b = __ballot(hit);
         if (lane == 0) wave_hits += __popcll(b);

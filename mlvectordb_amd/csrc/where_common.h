@@ -1,0 +1,77 @@
+// The predicate program of a metadata filter evaluated on one row (include/mlvdb_where.h): shared by the single-program
+// kernel (kernels_where.hip) and the multi-program one of per-query filters (kernels_where_each.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "internal.h"
+
+namespace mlvdb {
+
+// `prog` (validated on the host, usually staged in LDS) on one row; the boolean stack is one 32-bit register (bit 0 = top).
+// Every op is uniform over the wave, so the branches never diverge; what differs per lane is only the value `load(op)`
+// returns for the op's column (INT64_MIN / NaN bits when the row has none).  The column type is the low byte of op.type.
+template <class Load>
+__device__ __forceinline__ bool where_eval_with(const WhereOp* prog, int32_t n_ops, const int64_t* __restrict__ set,
+                                                Load&& load) {
+    uint32_t st = 0;
+    for (int p = 0; p < n_ops; ++p) {
+        const WhereOp o = prog[p];
+        if (o.op == MLVDB_WHERE_AND || o.op == MLVDB_WHERE_OR) {
+            const uint32_t x = st & 1u, y = (st >> 1) & 1u;
+            st = ((st >> 2) << 1) | (o.op == MLVDB_WHERE_AND ? (x & y) : (x | y));
+            continue;
+        }
+        if (o.op == MLVDB_WHERE_NOT) {
+            st ^= 1u;
+            continue;
+        }
+        bool bit = true;  // MLVDB_WHERE_TRUE
+        if (o.op != MLVDB_WHERE_TRUE) {
+            const int64_t raw = load(o);
+            if ((o.type & 0xff) == MLVDB_ATTR_INT64) {
+                const bool have = raw != INT64_MIN;
+                switch (o.op) {
+                    case MLVDB_WHERE_EQ: bit = have && raw == o.a; break;
+                    case MLVDB_WHERE_NE: bit = !(have && raw == o.a); break;
+                    case MLVDB_WHERE_LT: bit = have && raw < o.a; break;
+                    case MLVDB_WHERE_LE: bit = have && raw <= o.a; break;
+                    case MLVDB_WHERE_GT: bit = have && raw > o.a; break;
+                    case MLVDB_WHERE_GE: bit = have && raw >= o.a; break;
+                    case MLVDB_WHERE_EXISTS: bit = have; break;
+                    default: {  // MLVDB_WHERE_IN: binary search of set[a, a + b), sorted ascending
+                        int64_t lo = o.a, hi = o.a + o.b;
+                        while (lo < hi) {
+                            const int64_t mid = lo + ((hi - lo) >> 1);
+                            if (set[mid] < raw) lo = mid + 1; else hi = mid;
+                        }
+                        bit = have && lo < o.a + o.b && set[lo] == raw;
+                    }
+                }
+            } else {  // float64: absent = NaN, so every ordered comparison of an absent value is false by itself
+                const double v = __longlong_as_double(raw), a = __longlong_as_double(o.a);
+                switch (o.op) {
+                    case MLVDB_WHERE_EQ: bit = v == a; break;
+                    case MLVDB_WHERE_NE: bit = !(v == a); break;
+                    case MLVDB_WHERE_LT: bit = v < a; break;
+                    case MLVDB_WHERE_LE: bit = v <= a; break;
+                    case MLVDB_WHERE_GT: bit = v > a; break;
+                    case MLVDB_WHERE_GE: bit = v >= a; break;
+                    default: bit = v == v;  // MLVDB_WHERE_EXISTS
+                }
+            }
+        }
+        st = (st << 1) | (bit ? 1u : 0u);
+    }
+    return st & 1u;
+}
+
+// ... on row i of the ops' own columns (8 coalesced bytes per row and referenced op).  in == false: the row does not exist
+// (nothing is loaded).
+__device__ __forceinline__ bool where_eval_row(const WhereOp* prog, int32_t n_ops, const int64_t* __restrict__ set,
+                                               int64_t i, bool in) {
+    return where_eval_with(prog, n_ops, set,
+                           [&](const WhereOp& o) { return in ? static_cast<const int64_t*>(o.col)[i] : INT64_MIN; });
+}
+
+}  // namespace mlvdb

@@ -236,6 +236,73 @@ class HipScanEngine:
         self._check(self._lib.mlvdb_where_labels(self._h, C.byref(w), out.ctypes.data, out.size, C.byref(n)), "where_labels")
         return out[: n.value]
 
+    # -- per-query filters (include/mlvdb_where_each.h) -------------------------------
+    @staticmethod
+    def _where_array(programs):
+        """(mlvdb_where[len(programs)], the arrays they point into: kept alive by the caller for the call)."""
+        arr = (_native.Where * max(len(programs), 1))()
+        keep = []
+        for j, prog in enumerate(programs):
+            w, k = HipScanEngine._where(prog)
+            arr[j] = w
+            keep.append(k)
+        return arr, keep
+
+    def count_each(self, programs) -> np.ndarray:
+        """Live rows each compiled filter of ``programs`` matches (int64 array), all counted in one pass per native call."""
+        from .where import chunk_programs
+
+        out = np.zeros(len(programs), dtype=np.int64)
+        start = 0
+        for _, chunk, _ in chunk_programs(list(programs), np.zeros(0, np.int32)):
+            arr, keep = self._where_array(chunk)
+            part = np.zeros(max(len(chunk), 1), dtype=np.int64)
+            self._check(self._lib.mlvdb_where_count_each(self._h, arr, len(chunk), part.ctypes.data), "where_count_each")
+            out[start:start + len(chunk)] = part[:len(chunk)]
+            start += len(chunk)
+        return out
+
+    def search_each(self, queries: np.ndarray, k: int, programs, program_of_query, want64: bool = False,
+                    return_routes: bool = False):
+        """kNN with a filter per query: query i searches the rows ``programs[program_of_query[i]]`` matches (-1: all
+        rows).  Returns what ``search`` (``want64=False``) or ``search64`` returns, each query's row bit-identical to a call
+        for it alone; ``return_routes=True`` appends an int32 array with each program's route (``_native.ROUTE_*``).
+        One native call per chunk of at most 64 programs / 1024 ops (``where.chunk_programs``)."""
+        from .where import chunk_programs
+
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        of = np.ascontiguousarray(program_of_query, dtype=np.int32)
+        nq = queries.shape[0]
+        if of.shape != (nq,):
+            raise RuntimeError(f"program_of_query: {of.shape}, expected ({nq},)")
+        labels = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.int32)
+        d64 = np.empty((nq, k), dtype=np.float64) if want64 else None
+        routes = np.zeros(len(programs), dtype=np.int32)
+        start = 0
+        for idx, chunk, local in chunk_programs(list(programs), of):
+            n = idx.size
+            q = np.ascontiguousarray(queries[idx])
+            lab = np.empty((n, k), dtype=np.int64)
+            dst = np.empty((n, k), dtype=np.float32)
+            cnt = np.empty(n, dtype=np.int32)
+            l64 = np.empty((n, k), dtype=np.float64) if want64 else None
+            rts = np.zeros(max(len(chunk), 1), dtype=np.int32)
+            arr, keep = self._where_array(chunk)
+            self._check(self._lib.mlvdb_search_batch_where_each(
+                self._h, q.ctypes.data, n, int(k), arr, len(chunk), local.ctypes.data, lab.ctypes.data, dst.ctypes.data,
+                cnt.ctypes.data, None if l64 is None else l64.ctypes.data, rts.ctypes.data), "search_batch_where_each")
+            labels[idx], dist[idx], counts[idx] = lab, dst, cnt
+            if want64:
+                d64[idx] = l64
+            routes[start:start + len(chunk)] = rts[:len(chunk)]
+            start += len(chunk)
+        out = (labels, dist, counts, d64) if want64 else (labels, dist, counts)
+        return out + (routes,) if return_routes else out
+
     def search64(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None, where=None):
         """kNN; ``mask`` (optional, one byte per row, non-zero = allowed) restricts the search to those rows, ``where``
         (optional, a compiled ``where.Program``) to the rows it matches, evaluated on the device.

@@ -27,7 +27,7 @@ import json
 import os
 from dataclasses import dataclass
 from collections.abc import Sequence as SequenceABC
-from typing import Callable, Dict, Iterable, List, Mapping, Optional, Sequence
+from typing import Callable, Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 from uuid import UUID
 
 import numpy as np
@@ -456,10 +456,14 @@ class Index:
         the result is what ``search`` would return for that query (``BatchHits``: a lazy sequence over the result
         arrays).  ``allowed_ids`` (additive: the row mask of a metadata-filtered search, README.md:121,130 intent)
         restricts the search to those vectors; the answer is the exact top-k among them.  ``where`` (additive: a dict
-        filter over the declared attributes, where.py) does the same with the row mask evaluated on the device.
+        filter over the declared attributes, where.py) does the same with the row mask evaluated on the device; a list or
+        tuple of ``nq`` entries, each a dict filter or ``None`` (unfiltered), gives every query its own filter (one batched
+        call, include/mlvdb_where_each.h): each query's answer is what a single-dict call for it alone returns.
         """
         if where is not None and allowed_ids is not None:
             raise ValueError("search_many: give allowed_ids or where, not both")
+        if isinstance(where, (list, tuple)):
+            return self._search_many_each(queries, top_k, namespace, metric, where)
         program = None if where is None else self._compile(namespace, where)
         q = self._coerce_queries(queries)
         nq = q.shape[0]
@@ -488,6 +492,38 @@ class Index:
         return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
 
     _MAX_TOP_K = 16384  # MLVDB_MAX_TOPK_PAGED: the most neighbours one call returns per query
+
+    def _compile_each(self, namespace: str, wheres) -> Tuple[list, np.ndarray]:
+        for w in wheres:
+            if w is not None and not isinstance(w, Mapping):
+                raise ValueError(f"per-query where entries must be dict filters or None (where.py), got {type(w).__name__}")
+        ns = self._ns.get(namespace)
+        return _where.compile_each(list(wheres), self._attributes, ns.strings if ns is not None else {})
+
+    def _search_many_each(self, queries, top_k: int, namespace: str, metric: str, wheres) -> BatchHits:
+        """``search_many`` with ``where`` = one dict filter (or ``None``) per query."""
+        q = self._coerce_queries(queries)
+        nq = q.shape[0]
+        if len(wheres) != nq:
+            raise ValueError(f"search_many: {len(wheres)} per-query filters for {nq} queries")
+        programs, of = self._compile_each(namespace, wheres)
+        ns = self._ns.get(namespace)
+        if ns is None:
+            return BatchHits.empty(nq)
+        active = ns.total - ns.deleted
+        if active <= 0 or top_k <= 0 or nq == 0:
+            return BatchHits.empty(nq)
+        if q.shape[1] != ns.dim:
+            return BatchHits.empty(nq)
+        k = min(int(top_k), active, self._MAX_TOP_K)  # as a single-dict call clamps it
+        if not programs:
+            labels, dist, counts = self._search_engine(ns, q, k)
+        else:
+            search_each = getattr(ns.engine, "search_each", None)
+            if search_each is None:
+                raise ValueError("per-query filters need an engine with search_each (a single-device namespace)")
+            labels, dist, counts = search_each(q, k, programs, of)
+        return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
 
     def search_stream(self, batches, top_k: int, namespace: str, metric: str):
         """Additive: ``search_many`` over an iterable of query batches, pipelined -- yields one ``BatchHits`` per batch, in
@@ -554,6 +590,18 @@ class Index:
         program = self._compile(namespace, where)
         ns = self._ns.get(namespace)
         return 0 if ns is None or ns.total == 0 else ns.engine.where_count(program)
+
+    def count_many(self, namespace: str, wheres: Sequence[Mapping]) -> List[int]:
+        """``count`` of each dict filter of ``wheres``, all evaluated in one pass over the columns per native call."""
+        wheres = list(wheres)
+        if any(w is None for w in wheres):
+            raise ValueError("count_many: every entry must be a dict filter")
+        programs, of = self._compile_each(namespace, wheres)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total == 0 or not programs:
+            return [0] * len(wheres)
+        counts = np.asarray(ns.engine.count_each(programs), dtype=np.int64)
+        return [int(counts[j]) for j in of]
 
     def query_by_metadata(self, namespace: str, where: Mapping) -> List[UUID]:
         """UUIDs of the live rows satisfying ``where``, in insertion order (README.md:252,274: ``query_by_metadata``)."""

@@ -74,7 +74,9 @@ class QueryProcessor:
           - a dict filter over the index's declared attributes (``Index(attributes=...)``, where.py): compiled once and
             evaluated on the device into the row mask; nothing per row happens on the host;
           - a predicate over a stored vector's metadata dict: evaluated once over the namespace's stored vectors and
-            handed to the index as a row mask."""
+            handed to the index as a row mask;
+          - a list of ``nq`` entries, each a dict filter or ``None``: every query its own filter, all evaluated on the
+            device in one batched call (``Index.search_many``); a predicate inside the list is a ``ValueError``."""
         return self._enrich_many(self._search_many(queries, top_k, namespace, metric, where), namespace)
 
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
@@ -82,6 +84,10 @@ class QueryProcessor:
             return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric)
         if isinstance(where, Mapping):
             return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric, where=where)
+        if isinstance(where, (list, tuple)):  # one dict filter (or None) per query: all on the device, one batched call
+            if any(w is not None and not isinstance(w, Mapping) for w in where):
+                raise ValueError("per-query where entries must be dict filters or None (per-query predicates have no host path)")
+            return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric, where=list(where))
         allowed = [v.id for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
         return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric, allowed_ids=allowed)
 

@@ -197,6 +197,67 @@ def compile_where(where: Mapping[str, Any], schema: Mapping[str, str],
     return b.program()
 
 
+# ---------------------------------------------------------------- per-query filters (include/mlvdb_where_each.h)
+EACH_MAX_PROGRAMS = 64  # MLVDB_WHERE_EACH_MAX_PROGRAMS: distinct programs per native call
+EACH_MAX_OPS = 1024     # MLVDB_WHERE_EACH_MAX_OPS: ops over all programs of one native call
+
+
+def _program_key(program: Program) -> Tuple[bytes, bytes]:
+    return program.ops.tobytes(), np.ascontiguousarray(program.set, dtype=np.int64).tobytes()
+
+
+def compile_each(wheres, schema: Mapping[str, str],
+                 strings: Mapping[str, Mapping[str, int]] | None = None) -> Tuple[List[Program], np.ndarray]:
+    """Per-query filters: ``wheres[i]`` is a dict filter or ``None`` (unfiltered) -> (the distinct compiled programs,
+    ``program_of_query`` int32 [len(wheres)]: an index into them or -1).  Filters that compile to the same program (same
+    ops and set table) share one entry, so a batch of many queries over few tenants scans the columns for few programs."""
+    programs: List[Program] = []
+    seen: Dict[Tuple[bytes, bytes], int] = {}
+    of = np.full(len(wheres), -1, dtype=np.int32)
+    for i, w in enumerate(wheres):
+        if w is None:
+            continue
+        prog = compile_where(w, schema, strings)
+        key = _program_key(prog)
+        j = seen.get(key)
+        if j is None:
+            j = seen[key] = len(programs)
+            programs.append(prog)
+        of[i] = j
+    return programs, of
+
+
+def chunk_programs(programs: List[Program], program_of_query, max_programs: int = EACH_MAX_PROGRAMS,
+                   max_ops: int = EACH_MAX_OPS) -> List[Tuple[np.ndarray, List[Program], np.ndarray]]:
+    """Split per-query programs into native calls within the per-call limits: a list of (query indices, the call's
+    programs, the call's ``program_of_query`` for those queries).  Programs are taken in order; every call holds at most
+    ``max_programs`` of them and ``max_ops`` ops in all.  The unfiltered queries (-1) ride with the first call (a call of
+    their own when there is no program).  Queries keep their batch order inside each call."""
+    of = np.asarray(program_of_query, dtype=np.int32)
+    groups: List[List[int]] = []
+    ops = 0
+    for j, prog in enumerate(programs):
+        n = int(prog.ops.size)
+        if n > max_ops:
+            raise ValueError(f"a filter compiles to {n} ops; one call evaluates at most {max_ops}")
+        if not groups or len(groups[-1]) >= max_programs or ops + n > max_ops:
+            groups.append([])
+            ops = 0
+        groups[-1].append(j)
+        ops += n
+    if not groups:
+        groups.append([])
+    out = []
+    for c, members in enumerate(groups):
+        local = np.full(len(programs) + 1, -1, dtype=np.int32)  # (slot len(programs): the unfiltered queries' -1)
+        local[members] = np.arange(len(members), dtype=np.int32)
+        take = np.isin(of, members) | ((of < 0) if c == 0 else False)
+        idx = np.flatnonzero(take)
+        sub = of[idx]
+        out.append((idx, [programs[j] for j in members], local[np.where(sub >= 0, sub, len(programs))]))
+    return out
+
+
 # ---------------------------------------------------------------- ingest: metadata values -> column values
 INT64_ABSENT = np.iinfo(np.int64).min
 
