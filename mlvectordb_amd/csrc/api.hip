@@ -709,31 +709,6 @@ int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, flo
             fprintf(stderr, "[mlvdb] scan rows [%lld, %lld): %llu entries appended (%.1f per query), max per wave %llu\n",
                     (long long)b, (long long)e, (unsigned long long)sum, (double)sum / fa.nq, (unsigned long long)mx);
         }
-#ifdef MLVDB_SCAN_DIAGNOSTICS  // make DIAG=1, MLVDB_SCAN_DIAG=234: where a scan launch's time goes (its waves stamp their phases)
-        if (fa.wgbuf && h->tn.scan_diag == 234) {
-            const int nwg = (int)std::min<int64_t>(256, (e - b + 255) / 256);
-            std::vector<unsigned long long> st((size_t)nwg * 8 * 8, 0ull);
-            HIP_TRY(h, hipMemcpyAsync(st.data(), fa.wgbuf + (size_t)256 * kWgCap, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-            unsigned long long t0 = ~0ull, t5 = 0;
-            double ph[3] = {0, 0, 0};
-            const double tiles = (double)((e - b + 255) / 256);
-            int n = 0;
-            for (int w = 0; w < nwg * 8; ++w) {
-                const unsigned long long* p = &st[(size_t)w * 8];
-                if (!p[0] || !p[5]) continue;
-                ++n;
-                t0 = std::min(t0, p[0]);
-                t5 = std::max(t5, p[5]);
-                ph[0] += (double)(p[1] - p[0]) * 0.01;  // C++ preamble
-                ph[1] += (double)(p[4] - p[1]) * 0.01;  // the assembly: prologue + tiles
-                ph[2] += (double)(p[5] - p[4]) * 0.01;  // scatter tail
-            }
-            fprintf(stderr, "[mlvdb] scan rows [%lld, %lld): %d waves, first start -> last end %.1f us; mean per wave: preamble %.1f, "
-                    "assembly %.1f (%.1f tiles per workgroup), tail %.1f us\n", (long long)b, (long long)e, n,
-                    (double)(t5 - t0) * 0.01, ph[0] / n, ph[1] / n, tiles / nwg, ph[2] / n);
-        }
-#endif
         h->stats.scan_launches += 1;
         h->stats.rows_scanned += e - b;
         // int8 bounds are loose: thresholds from exact scores of the k best bounds; the same kernel prunes the lists
@@ -752,23 +727,6 @@ int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, flo
             break;
         }
         if (fa.X8) HIP_TRY(h, launch_filter_refine_thr(fa, k, -1, fuse, s));
-#ifdef MLVDB_SCAN_DIAGNOSTICS  // make DIAG=1: where the refine kernel's time goes (its blocks stamp their phases)
-        if (fa.X8 && fa.wgbuf && h->tn.debug_refine) {
-            std::vector<unsigned long long> st((size_t)fa.nq * 8, 0ull);
-            HIP_TRY(h, hipMemcpyAsync(st.data(), fa.wgbuf, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-            unsigned long long t0 = ~0ull, t5 = 0;
-            double ph[5] = {0, 0, 0, 0, 0};
-            for (int q = 0; q < fa.nq; ++q) {
-                t0 = std::min(t0, st[(size_t)q * 8]);
-                t5 = std::max(t5, st[(size_t)q * 8 + 5]);
-                for (int i = 0; i < 5; ++i) ph[i] += (double)(st[(size_t)q * 8 + i + 1] - st[(size_t)q * 8 + i]) * 0.01 / fa.nq;
-            }
-            fprintf(stderr, "[mlvdb] refine rows [%lld, %lld): first start -> last end %.1f us; mean per block: load+keys %.1f, "
-                    "select+compact %.1f, gather %.1f, rank+thr %.1f, prune %.1f us\n", (long long)b, (long long)e,
-                    (double)(t5 - t0) * 0.01, ph[0], ph[1], ph[2], ph[3], ph[4]);
-        }
-#endif
         if (!fuse) HIP_TRY(h, launch_filter_update(fa, k, s));
     }
     return finish_filter_pass(h, s, fa, q0, nq, k, out_labels, out_dist, out_counts, out_d64, defer_fallback, ranked);
@@ -781,53 +739,12 @@ int finish_filter_pass(mlvdb_index* h, hipStream_t s, FilterArgs& fa, int32_t q0
     int rc = MLVDB_OK;
     // counters: [0] rescored pairs, [1] fallback queries (accumulated over the passes of a call), [2] flag count
     unsigned long long* stats = h->counters.as<unsigned long long>();
-#ifdef MLVDB_SCAN_DIAGNOSTICS
-    if (fa.wgbuf && h->tn.debug_refine) HIP_TRY(h, hipMemsetAsync(fa.wgbuf, 0, (16384 + 1024) * 8, s));
-#endif
     // (its ranking kernel also compacts the overflowed queries for the device-decided fallback below: qsel, nflag)
     HIP_TRY(h, h->qsel.ensure(kFilterQueries * sizeof(int32_t)));
     int32_t* nflag = reinterpret_cast<int32_t*>(stats + 2);
     if (!ranked)
         HIP_TRY(h, launch_filter_rescore(fa, k, q0, out_labels, out_dist, out_counts, out_d64, stats,
                                          defer_fallback ? nullptr : h->qsel.as<int32_t>(), nflag, s));
-#ifdef MLVDB_SCAN_DIAGNOSTICS  // make DIAG=1: where the ranking kernel's time goes (its blocks stamp their phases)
-    if (!ranked && fa.wgbuf && h->tn.debug_refine) {
-        std::vector<unsigned long long> st(16384 + 1024, 0ull);
-        HIP_TRY(h, hipMemcpyAsync(st.data(), fa.wgbuf, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        {
-            unsigned long long t0 = ~0ull, tl = 0;
-            double ph[3] = {0, 0, 0};
-            int nw = 0, idle = 0;
-            for (int w = 0; w < 4096; ++w) {
-                const unsigned long long* p = &st[(size_t)w * 4];
-                if (!p[0]) continue;
-                t0 = std::min(t0, p[0]);
-                if (!p[3]) { ++idle; tl = std::max(tl, p[1]); continue; }
-                tl = std::max(tl, p[3]);
-                ++nw;
-                for (int i = 0; i < 3; ++i) ph[i] += (double)(p[i + 1] - p[i]) * 0.01;
-            }
-            fprintf(stderr, "[mlvdb] rescoring, score kernel: %d waves with rows, %d without; first start -> last end %.1f us; mean per "
-                    "working wave (its last 16-row group): prefix %.1f, query %.1f, gather + score %.1f us\n", nw, idle,
-                    (double)(tl - t0) * 0.01, ph[0] / std::max(nw, 1), ph[1] / std::max(nw, 1), ph[2] / std::max(nw, 1));
-        }
-        unsigned long long r0 = ~0ull, rl = 0, rs1 = 0, rmax = 0;
-        double rp[3] = {0, 0, 0};
-        for (int q = 0; q < fa.nq; ++q) {
-            const unsigned long long* p = &st[16384 + (size_t)q * 4];
-            if (!p[0] || !p[3]) continue;
-            r0 = std::min(r0, p[0]);
-            rl = std::max(rl, p[3]);
-            rs1 = std::max(rs1, p[0]);
-            rmax = std::max(rmax, p[3] - p[0]);
-            for (int i = 0; i < 3; ++i) rp[i] += (double)(p[i + 1] - p[i]) * 0.01 / fa.nq;
-        }
-        fprintf(stderr, "[mlvdb] rescoring, rank kernel: first start -> last end %.1f us (last start %.1f us after the first, longest "
-                "block %.1f); mean per block: load %.1f, rank %.1f, output %.1f us\n",
-                (double)(rl - r0) * 0.01, (double)(rs1 - r0) * 0.01, (double)rmax * 0.01, rp[0], rp[1], rp[2]);
-    }
-#endif
     // overflowed queries (adversarial near-ties) are re-run on the exact scan.  The decision stays on
     // the device: the list is compacted there and the scan's blocks exit at once when it is empty,
     // so the call never waits for the host.

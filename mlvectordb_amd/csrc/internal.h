@@ -34,8 +34,6 @@ inline hipError_t ensure_dynamic_lds(std::atomic<uint64_t>& done, const void* ke
 // MLVDB_* environment variables of that moment (tuning_from_env, api.hip: the library's only getenv loop), and changed
 // afterwards only through mlvdb_index_set_tuning(h, "KEY=VAL") -- nothing on the search path reads the environment, so
 // host threads that serve different handles (MultiDeviceEngine: one per shard) never race a setenv in glibc.
-// Variants marked [AB] exist only in `make AB=1` builds (tools/scan_ab.py, the `ab`-marked tests); the default
-// library ignores them.
 #define MLVDB_TUNING_FIELDS(X)                                                                                          \
     X(i8, "I8", 1)                     /* 0: bf16 bodies on an index that keeps a bf16 shadow */                       \
     X(no_shadow, "NO_SHADOW", 0)       /* creation: no shadow at all (the filter converts fp32 rows in registers) */   \
@@ -62,25 +60,13 @@ inline hipError_t ensure_dynamic_lds(std::atomic<uint64_t>& done, const void* ke
     X(bigk_budget, "BIGK_BUDGET", 400000) /* entries one scan launch of a big-k pass may append (sizes its rounds) */ \
     X(l2_shadow, "L2_SHADOW", 1)       /* fp16 row-major shadow for second-level bounds (built lazily; 0: never) */    \
     X(debug_entries, "DEBUG_ENTRIES", 0)                                                                                \
-    X(debug_refine, "DEBUG_REFINE", 0)                                                                                  \
     X(scan_narrow, "SCAN_NARROW", 1)                                                                                    \
     X(narrow_i8_max, "NARROW_I8_MAX", 0) /* largest batch the int8 NARROW kernel scans (round 4: none -- the 4-tile assembly body is faster at every batch size) */                                                                                \
     X(narrow_wgs, "NARROW_WGS", 0)     /* 0 = as many workgroups per CU as the image leaves LDS for */                  \
     X(narrow_balance, "NARROW_BALANCE", 1)                                                                              \
-    X(scan_xcd, "SCAN_XCD", 0)                                                                                          \
-    X(scan_asm, "SCAN_ASM", 1)                                                                                          \
     X(scan_l2c, "SCAN_L2C", 1)         /* l2: one query quantisation step per pass + one error coefficient: cosine's one-constant test */ \
     X(scan_l2e, "SCAN_L2E", 1)         /* l2: folded admission test with per-row integer offsets (0: serial test, round 3's body) */ \
     X(scan_nqt, "SCAN_NQT", 0)         /* query tiles of the int8 body: 0 = by batch size, else 4 / 8 / 16 */          \
-    X(scan_nw, "SCAN_NW", 8)           /* [AB] */                                                                       \
-    X(scan_mt, "SCAN_MT", 2)           /* [AB] */                                                                       \
-    X(scan_va, "SCAN_VA", 1)           /* [AB] 0: AccVGPR accumulators, serial admission test (round 1) */             \
-    X(scan_var, "SCAN_VAR", 0)         /* 237: round 2's body; the other codes [AB] */                                  \
-    X(scan_prio, "SCAN_PRIO", -1)      /* [AB] -1 = the body's default */                                               \
-    X(scan_nt, "SCAN_NT", 1)           /* [AB] */                                                                       \
-    X(scan_dma, "SCAN_DMA", 1)         /* [AB] */                                                                       \
-    X(scan_stag, "SCAN_STAG", 0)       /* [AB] */                                                                       \
-    X(scan_diag, "SCAN_DIAG", 0)       /* make DIAG=1 builds */                                                         \
     X(l2_offset_cache, "L2_OFFSET_CACHE", 1) /* l2: keep the offsets plane across passes of the same scale (0: recompute per pass) */ \
     X(exact_nt, "EXACT_NT", 1)                                                                                          \
     X(exact_nblk, "EXACT_NBLK", 0)                                                                                      \
@@ -264,7 +250,6 @@ hipError_t launch_filter_seed_thr(const FilterArgs& a, const double* seed_d64, i
 // moves them into the per-query candidate lists (round 1 had a separate scatter launch for that).
 struct ScanInfo {
     int nw = 0;
-    int dbg = 0;
     int i8 = 0;  // int8 scan, entries in units of the query's scale: 1 cosine (u = w sq8 + ke), 2 ip (u = w sq8)
 };
 // int8 shadow: (re)build the panels covering rows [row_begin, row_end) (also rp8 and the index-wide error), the query image of a

@@ -601,24 +601,13 @@ __global__ __launch_bounds__(NW * 64) void filter_scan_narrow_kernel(const Filte
 // ------------------------------------------------------------------ the scan, hand-written for gfx950
 // Same geometry, data flow and bounds as filter_scan_kernel<.., kMT = 2, XB = true> above, but the
 // whole body -- prologue, persistent tile loop, k-loop, admission test, append path -- is the
-// generated assembly of tools/gen_scan_asm.py (scan_asm_<space>_nw<NW>_r<R>.inc; the schedule and
-// the reasons are documented there).  This wrapper only computes addresses.
-// Requires the bf16 shadow.  Tile = NW*32 rows; the 2*ld/64 k-steps of a tile must be a multiple of R.
+// generated assembly of tools/gen_scan_asm.py (scan_asm_*.inc; the schedule and the reasons are
+// documented there).  This wrapper only computes addresses.
+// Requires a shadow: bf16 (I8 false) or int8.  Tile = 8 waves x 32 rows; the k-steps of a tile must be a multiple of R.
 typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
 
 #include "scan_asm_consts.inc"
 static_assert(kAsmWgCap == kWgCap, "tools/gen_scan_asm.py and internal.h disagree");
-
-// The QD template slot doubles as a variant code: 2..8 = B-fragment read-ahead of a bf16 body; 1xx = timing diagnostics of
-// the bf16 body; 208..219 = int8 bodies (208 AccVGPR accumulators; 211 ArchVGPR accumulators, cosine: admission folded into the
-// last k-step; 214 / 215 / 216 tuning variants of 211: ring of 6, read-ahead 8, no wave priorities; 209 / 210 / 212 / 213
-// timing diagnostics).
-constexpr bool scan_code_i8(int qd) { return qd >= 208 && qd <= 249; }
-// 241 / 242 (round 4): the default int8 body computing only the first 8 / 4 query tiles (passes of <= 128 / <= 64 queries)
-constexpr int scan_code_nqt(int qd) { return (qd == 241 || qd == 247 || qd == 244) ? 8 : ((qd == 242 || qd == 248 || qd == 245) ? 4 : 16); }
-// 246 / 247 / 248 (round 4): l2 with the folded admission test, per-row integer offsets through the first k-step's C operand
-constexpr bool scan_code_l2e(int qd) { return qd >= 243 && qd <= 248; }  // 243-245: l2c (+ one query scale, one error coefficient per pass)
-constexpr bool scan_code_l2c(int qd) { return qd >= 243 && qd <= 245; }
 
 // l2c: what the pass's common error coefficient KE = max_q KE_q costs query q, taken back.  The body's bound of row j is
 //   u'_j = (per-query bound with q's own KE_q) + (KE - KE_q) N_j   and   N_j >= Nmin  (the smallest row norm the index ever held),
@@ -632,39 +621,28 @@ __device__ __forceinline__ float l2c_delta(const FilterArgs& a, int q) {
     if (!(d > 0.0) || !(nmin < 3.0e38)) return 0.f;
     return float_below(d);
 }
-constexpr int scan_code_qd(int qd) { return qd == 215 ? 8 : (qd > 8 ? 4 : qd); }
-constexpr bool scan_code_q4(int qd) { return qd == 219 || qd == 229 || qd == 231 || qd == 233; }  // four Q chunk buffers
-constexpr int scan_code_qbufs(int qd) { return scan_code_q4(qd) ? 4 : 2; }
-constexpr int scan_code_stage_cap(int qd, int nw, int mt) {
-    return scan_code_q4(qd) ? kAsmStageCapNw8Q4 : (mt == 4 ? kAsmStageCapNw4Mt4 : (nw == 8 ? kAsmStageCapNw8 : kAsmStageCapNw4));
-}
-
-template <int SPACE, int R, int NW, bool NT, int QD, bool PRIO, int MT, bool DMA, bool STAG>
-__global__ __launch_bounds__(NW * 64, MT == 4 ? 1 : 2) void filter_scan_asm_kernel(const FilterArgs a, const int64_t tile_begin,
-                                                                                  const int64_t tile_end, const int xcd_mode) {
+// The bodies (tools/gen_scan_asm.py, entries): R = the ring's k-steps (4; bf16 also 2, for odd chunk counts); I8 = the int8
+// shadow (k-steps of 64 int8 columns, same bytes per step; l2: the l2c body), else bf16; NQT = the query tiles the body
+// computes (int8: 8 / 4 for passes of <= 128 / <= 64 queries, else 16).
+constexpr int kAsmWaves = 8;      // waves per workgroup, two per SIMD
+constexpr int kAsmQBufs = 2;      // Q chunk buffers in LDS
+constexpr int kAsmQD = 4;         // B fragments read ahead
+template <int SPACE, int R, bool I8, int NQT>
+__global__ __launch_bounds__(kAsmWaves * 64, 2) void filter_scan_asm_kernel(const FilterArgs a, const int64_t tile_begin,
+                                                                           const int64_t tile_end, const int xcd_mode) {
+    constexpr int NW = kAsmWaves, MT = 2;
+    constexpr bool L2C = I8 && SPACE == kSpaceL2;
     constexpr int kThreads = NW * 64;
-    constexpr int kQPer = 1024 / kThreads;  // uint4 of a Q half-chunk moved per thread
-    constexpr int kWaveRows = 16 * MT;  // MT = 2: two waves per SIMD; MT = 4: one, 64 rows each
+    constexpr int kWaveRows = 16 * MT;
     constexpr int kTileRowsV = NW * kWaveRows;
-    constexpr int kQBufs = scan_code_qbufs(QD);
-    constexpr int kStageCap = scan_code_stage_cap(QD, NW, MT);  // entries a wave stages in LDS
-    constexpr bool I8 = scan_code_i8(QD);  // int8 shadow: k-steps of 64 int8 columns, same bytes per step
+    constexpr int kQBufs = kAsmQBufs;
+    constexpr int kStageCap = kAsmStageCap;  // entries a wave stages in LDS
     // LDS: [2][32 KiB] Q chunks at offset 0, thr[256], qscale[256], ke[256], [NW waves] staging {u[], row[], q[]}
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* thr_l = reinterpret_cast<float*>(smem + kQBufs * kChunkVec * sizeof(uint4));
     float* sq_l = thr_l + kFilterQueries;
     float* ke_l = sq_l + kFilterQueries;
     if (threadIdx.x < NW) a.wgcnt[blockIdx.x * NW + threadIdx.x] = 0;  // workgroups without tiles return below
-#ifdef MLVDB_SCAN_DIAGNOSTICS  // make DIAG=1, MLVDB_SCAN_DIAG=234: phase stamps (100 MHz) per wave, in the unused upper half of wgbuf
-    // (the pointer is recomputed at every stamp: kept live across the assembly it costs the SGPRs the statement's "s"
-    // operands need -- they then come out as VGPRs and the assembler refuses them)
-    auto phase = [&]() __attribute__((always_inline)) {
-        return reinterpret_cast<unsigned long long*>(a.wgbuf + (size_t)256 * kWgCap) +
-               ((size_t)blockIdx.x * NW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * 8;
-    };
-    constexpr bool stamping = QD == 234;  // wave-uniform: every lane stores the same word
-    if (stamping) phase()[0] = __builtin_amdgcn_s_memrealtime();
-#endif
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -688,7 +666,7 @@ __global__ __launch_bounds__(NW * 64, MT == 4 ? 1 : 2) void filter_scan_asm_kern
             } else {  // l2: sq' (w + ke' |x|) + p1 >= thr with sq' = 2|q| sq8
                 kev = float_above((double)kev / sq8);
                 sqv = sqv * a.sq8[t];
-                if (scan_code_l2c(QD) && t < a.nq && thr > -1.0e30f && thr < 1.0e30f)
+                if (L2C && t < a.nq && thr > -1.0e30f && thr < 1.0e30f)
                     thr = float_below((double)thr + (double)l2c_delta(a, t));  // (see l2c_delta)
             }
         }
@@ -697,13 +675,13 @@ __global__ __launch_bounds__(NW * 64, MT == 4 ? 1 : 2) void filter_scan_asm_kern
         ke_l[t] = kev;
     }
     const int64_t ntiles_all = tile_end - tile_begin;
-    // Which tiles this workgroup scans: tile0 + i * tstride, i < my_tiles.  Default: the grid walks the range together
-    // (workgroup b takes tiles b, b + grid, ...).  xcd_mode (MLVDB_SCAN_XCD=1, tuning): workgroups b, b + 8, ... share an
-    // XCD under the observed round-robin placement (speed only, never correctness), so each XCD gets one contiguous
-    // eighth of the range and its workgroups walk that eighth together.
+    // Which tiles this workgroup scans: tile0 + i * tstride, i < my_tiles -- the grid walks the range together (workgroup b
+    // takes tiles b, b + grid, ...).  xcd_mode = 1 gave each XCD one contiguous eighth of the range (0.9 % slower,
+    // profiles/r03/scan_ab_qa_eo_xcd_10m.txt); every launch passes 0.  The branch stays because taking it out re-allocates
+    // the body's SGPR operands, i.e. changes the measured instruction stream of every scan kernel.
     int64_t tile0 = tile_begin + blockIdx.x, my_tiles = ntiles_all > blockIdx.x ? (ntiles_all - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
     uint32_t tstride = gridDim.x;
-    if (xcd_mode) {  // (the launcher only sets it for grids that are multiples of 8)
+    if (xcd_mode) {
         const int64_t per = (ntiles_all + 7) / 8, x = blockIdx.x & 7, slot = blockIdx.x >> 3, gs = gridDim.x >> 3;
         const int64_t n_x = per * x < ntiles_all ? (per * (x + 1) <= ntiles_all ? per : ntiles_all - per * x) : 0;
         tile0 = tile_begin + per * x + slot;
@@ -751,19 +729,9 @@ __global__ __launch_bounds__(NW * 64, MT == 4 ? 1 : 2) void filter_scan_asm_kern
     // l2: p1 = k1 |x|^2; int8 cosine: K = 1.016 / min sq8, the factor of the rows' own errors (filter_prep8_fin_kernel)
     const float k1 = I8 && SPACE == kSpaceCosine ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a.ke8[kFilterQueries])))
                                                  : -(1.0f - kSlack);
-    // the later-dispatched half of the workgroup's waves (readfirstlane: an "s" operand must live in an SGPR)
+    // the later-dispatched half of the workgroup's waves: the int8 bodies' wave priorities (readfirstlane: an "s" operand must
+    // live in an SGPR)
     const uint32_t wtype = __builtin_amdgcn_readfirstlane(wave >= NW / 2 ? 1u : 0u);
-    (void)wtype;
-    // stagger (STAG): the later half runs nkc/2 chunk periods behind, its k origin rotated by half a row
-    // (tools/gen_scan_asm.py, generate); needs the R ring steps after the rotated origin inside the panel
-    const uint32_t hc = STAG && nkc % 2 == 0 && nkc >= R ? (uint32_t)nkc / 2 : 0u;
-    const uint32_t xrot = __builtin_amdgcn_readfirstlane(wtype && hc ? (uint32_t)nkc * 1024u : 0u);
-    const uint32_t pbrot = __builtin_amdgcn_readfirstlane(pb + xrot);
-    const uint32_t pb2 = 2 * pb;
-    (void)hc;
-    (void)xrot;
-    (void)pbrot;
-    (void)pb2;
     // this wave's append buffer in global memory: u[cap], row[cap], q[cap]
     constexpr int kCapW = kWgCap / NW;
     const char* wgb = reinterpret_cast<const char*>(a.wgbuf + ((size_t)blockIdx.x * NW + wave) * kCapW);
@@ -776,8 +744,7 @@ __global__ __launch_bounds__(NW * 64, MT == 4 ? 1 : 2) void filter_scan_asm_kern
     const uint32_t lane16 = lane * 16;
     // LDS-DMA staging: which fragment of a Q chunk this wave moves (tools/gen_scan_asm.py, dma_pieces): query tile `wave` (+ 8), both
     // k-step halves -- or, when only 4 query tiles are computed, the single fragment (tile wave & 3, half wave >> 2)
-    constexpr int kNQT = scan_code_nqt(QD);
-    const uint32_t wave_piece = kNQT == 4 ? (uint32_t)(wave & 3) * 2048u + (uint32_t)(wave >> 2) * 1024u : (uint32_t)wave * 2048u;
+    const uint32_t wave_piece = NQT == 4 ? (uint32_t)(wave & 3) * 2048u + (uint32_t)(wave >> 2) * 1024u : (uint32_t)wave * 2048u;
     const uint32_t qvoff = wave_piece + lane16;  // this thread's uint4 of the wave's fragment
     const uint32_t rnvoff = g * (I8 ? 32 : 16);
     const uint32_t thra = (uint32_t)(kQBufs * chunk_bytes) + c16 * 4;
@@ -792,9 +759,9 @@ __global__ __launch_bounds__(NW * 64, MT == 4 ? 1 : 2) void filter_scan_asm_kern
         (uint32_t)(8ull * (uint64_t)a.rp8_cap - 4ull * (uint64_t)(first_tile * kTileRowsV + wave * kWaveRows)));
     (void)eo0;
     // l2c bodies: the pass's common query scale SQ and error coefficient KE (filter_l2_offsets_kernel; SGPR operands)
-    const float sqc = scan_code_l2e(QD) ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a.l2c_out[0]))) : 0.f;
-    const float kec = scan_code_l2e(QD) ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a.l2c_out[1]))) : 0.f;
-    const float krc = scan_code_l2e(QD) ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a.l2c_out[2]))) : 0.f;
+    const float sqc = L2C ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a.l2c_out[0]))) : 0.f;
+    const float kec = L2C ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a.l2c_out[1]))) : 0.f;
+    const float krc = L2C ? __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a.l2c_out[2]))) : 0.f;
     (void)sqc;
     (void)kec;
     (void)krc;
@@ -802,29 +769,16 @@ __global__ __launch_bounds__(NW * 64, MT == 4 ? 1 : 2) void filter_scan_asm_kern
     uint32_t s_eo;
     (void)veo;
     (void)s_eo;
-    u32x4s xring[R * MT], qsa[kQPer], qsb[kQPer], qt[scan_code_qd(QD)];
+    u32x4s xring[R * MT], qt[kAsmQD];
     float vr[4 * MT], vp[4 * MT], vu[4 * MT], vs[4 * MT], vt[16];
     (void)vs;
     (void)vt;
-    uint32_t ve[13], ldr, ldw, s_sldw;
+    uint32_t ve[13], ldr, s_sldw;
     const uint32_t wave2k = __builtin_amdgcn_readfirstlane(wave_piece);  // LDS-DMA staging: this wave's fragment offset inside a Q buffer
-    (void)ldw;
-    (void)s_sldw;
-    (void)wave2k;
-    (void)qsa;
-    (void)qsb;
-    uint32_t s_xso0, s_xso1, s_xso2, s_xso3, s_qcur, s_cnt, s_st0, s_tl, s_trow, s_sn64, s_wcnt, s_sacc0, s_sacc1;
+    uint32_t s_xso0, s_xso1, s_qcur, s_cnt, s_st0, s_tl, s_trow, s_sn64, s_wcnt, s_sacc0, s_sacc1;  // (sacc*: scratch SGPRs)
     (void)vp;
-    (void)s_xso2;
-    (void)s_xso3;
     (void)k1;
-#ifdef MLVDB_SCAN_DIAGNOSTICS
-    if (stamping) phase()[1] = __builtin_amdgcn_s_memrealtime();
-#endif
 #include "scan_asm_dispatch.inc"
-#ifdef MLVDB_SCAN_DIAGNOSTICS
-    if (stamping) phase()[4] = __builtin_amdgcn_s_memrealtime();
-#endif
     // ---- the workgroup's own scatter: append buffers -> per-query candidate lists (what filter_scatter_kernel did in a
     // launch of its own).  Every wave staged its entries {u[], row[], q[]} in its LDS area (the first kStageCap of
     // them; later ones went to its slice of a.wgbuf, same slot numbering, stores drained); s_wcnt = how many it
@@ -880,16 +834,13 @@ __global__ __launch_bounds__(NW * 64, MT == 4 ? 1 : 2) void filter_scan_asm_kern
                     CandEntry e;
                     // int8 scan: the stored value is in units of the query's scale (cosine: w, ip: w + ke' |x|)
                     e.u = kI8Mode == 1 ? __builtin_fmaf(u, a.sq8[q], a.ke8[q]) : (kI8Mode == 2 ? u * a.sq8[q] : u);
-                    if (scan_code_l2c(QD)) e.u = float_above((double)u - (double)l2c_delta(a, (int)q));
+                    if (L2C) e.u = float_above((double)u - (double)l2c_delta(a, (int)q));
                     e.row = row;
                     a.cand[(size_t)q * a.cand_cap + slot] = e;
                 }
             }
         }
     }
-#ifdef MLVDB_SCAN_DIAGNOSTICS
-    if (stamping) phase()[5] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
 // ------------------------------------------------------------------ threshold update + compaction
@@ -1071,13 +1022,6 @@ __global__ __launch_bounds__(kRescoreWaves * 64) void filter_rescore_score_kerne
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nwaves = blockDim.x >> 6;
     double* qs = reinterpret_cast<double*>(smem) + (size_t)wave * ld;  // this wave's copy of its current query
-#ifdef MLVDB_SCAN_DIAGNOSTICS  // make DIAG=1: phase stamps (100 MHz) of every wave, read back by api.hip (MLVDB_DEBUG_REFINE)
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(a.wgbuf) + ((size_t)blockIdx.x * nwaves + wave) * 4;
-#define SCORE_STAMP(i) do { if (lane == 0 && a.wgbuf) stamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define SCORE_STAMP(i) do { } while (0)
-#endif
-    SCORE_STAMP(0);
     if (wave == 0) {  // lane l: queries 4l .. 4l+3; inclusive scan over the lanes (a serial loop over LDS here cost 12 us)
         uint32_t n[4], sum = 0;
 #pragma unroll
@@ -1101,7 +1045,6 @@ __global__ __launch_bounds__(kRescoreWaves * 64) void filter_rescore_score_kerne
     }
     __syncthreads();
     const uint32_t total = pre[kFilterQueries];
-    SCORE_STAMP(1);
     const int g = lane >> 4, r = lane & 15;
     int cur = -1;
     double qinv = 0.0;
@@ -1118,7 +1061,6 @@ __global__ __launch_bounds__(kRescoreWaves * 64) void filter_rescore_score_kerne
             qinv = a.qaux[q];
             cur = q;
         }
-        SCORE_STAMP(2);
         const uint32_t cnt = min(a.cnt[q], (uint32_t)kCandCap);
         const CandEntry* list = a.cand + (int64_t)q * kCandCap;
         RangeHit* rs = a.rs + (int64_t)q * kCandCap;
@@ -1138,9 +1080,7 @@ __global__ __launch_bounds__(kRescoreWaves * 64) void filter_rescore_score_kerne
             hit.pad = 0;
             rs[idx] = hit;
         }
-        SCORE_STAMP(3);
     }
-#undef SCORE_STAMP
 }
 
 // Block 0 also compacts the indices of the overflowed queries (ascending) for the exact fallback that follows when the
@@ -1174,13 +1114,6 @@ __global__ __launch_bounds__(kRankWaves * 64) void filter_rescore_rank_kernel(co
             if (rescored) rescored[1] += (unsigned long long)n;
         }
     }
-#ifdef MLVDB_SCAN_DIAGNOSTICS
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(a.wgbuf) + 16384 + (size_t)blockIdx.x * 4;
-#define RANK_STAMP(i) do { if (threadIdx.x == 0 && a.wgbuf) stamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define RANK_STAMP(i) do { } while (0)
-#endif
-    RANK_STAMP(0);
     if (q >= a.nq || a.overflow[q]) return;
     const uint32_t cnt = min(a.cnt[q], (uint32_t)kCandCap);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1194,7 +1127,6 @@ __global__ __launch_bounds__(kRankWaves * 64) void filter_rescore_rank_kernel(co
             el[i] = h.l;
         }
         __syncthreads();
-        RANK_STAMP(1);
         // an entry's rank = how many entries precede it in (distance, label) order; one entry per wave at a time, 64
         // comparisons per step by ballot, given up as soon as k entries precede it (wave-uniform).  (A thread per entry
         // looping over the whole list took 13.5 us for ~100 entries; 4 waves without the early exit 16 us, and 70 us for
@@ -1220,7 +1152,6 @@ __global__ __launch_bounds__(kRankWaves * 64) void filter_rescore_rank_kernel(co
         }
         if (lane == 0 && mine) atomicAdd(&s_nvalid, mine);
         __syncthreads();
-        RANK_STAMP(2);
         const int n_out = min(s_nvalid, k);
         for (int i = n_out + threadIdx.x; i < k; i += kRankWaves * 64) {
             out_labels[o + i] = -1;
@@ -1231,8 +1162,6 @@ __global__ __launch_bounds__(kRankWaves * 64) void filter_rescore_rank_kernel(co
             out_counts[q0 + q] = n_out;
             if (rescored) atomicAdd(rescored, (unsigned long long)cnt);
         }
-        RANK_STAMP(3);
-#undef RANK_STAMP
         return;
     }
     // long lists (k <= 64 here): per-wave sorted top-k lists, merged by wave 0
@@ -2341,13 +2270,6 @@ __global__ __launch_bounds__(256) void filter_refine_thr_kernel(const FilterArgs
     uint32_t* keys = s_scan + 24;                                                   // [kCandCap]
     CandEntry* stage = reinterpret_cast<CandEntry*>(keys + kCandCap);               // [kCandCap] (fuse only)
     const int q = blockIdx.x;
-#ifdef MLVDB_SCAN_DIAGNOSTICS  // make DIAG=1: phase stamps (100 MHz) of every block, read back by api.hip (MLVDB_DEBUG_REFINE)
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(a.wgbuf) + (size_t)blockIdx.x * 8;
-#define REFINE_STAMP(i) do { if (threadIdx.x == 0 && a.wgbuf) stamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define REFINE_STAMP(i) do { } while (0)
-#endif
-    REFINE_STAMP(0);
     if (FINISH && blockIdx.x == 0 && fo.qsel) {  // block-uniform; 256 threads = kFilterQueries
         uint32_t* s_flagged = s_scan + 18;  // [4] (no static LDS here: the dynamic allocation is sized to the CU's limit)
         const int t = threadIdx.x;
@@ -2418,7 +2340,6 @@ __global__ __launch_bounds__(256) void filter_refine_thr_kernel(const FilterArgs
     kmin = min(min(s_scan[4], s_scan[5]), min(s_scan[6], s_scan[7]));
     kmax = max(max(s_scan[8], s_scan[9]), max(s_scan[10], s_scan[11]));
     if (n_valid < (uint32_t)k) ok = false;  // fewer than k valid entries (block-uniform)
-    REFINE_STAMP(1);
     uint32_t m = 0;  // rows picked
     if (ok) {
         // at least `want` and at most `cap` rows (32 = one gather step): every entry whose key is >= tkey
@@ -2451,7 +2372,6 @@ __global__ __launch_bounds__(256) void filter_refine_thr_kernel(const FilterArgs
     }
     __syncthreads();
     if (ok) m = min(m, 64u);  // (the selection's own count; the gather below never reads past pick[])
-    REFINE_STAMP(2);
     // exact scores of the picked rows: 32 rows per step, lane l8 of a row takes the 16-column groups l8, l8 + 8, ...
     const int rslot = threadIdx.x >> 3, l8 = threadIdx.x & 7;
     const double qinv = a.qaux[q];
@@ -2505,7 +2425,6 @@ __global__ __launch_bounds__(256) void filter_refine_thr_kernel(const FilterArgs
     }
     if (threadIdx.x == 0) *smin = -__builtin_inf();
     __syncthreads();
-    REFINE_STAMP(3);
     if (ok && threadIdx.x < m) {  // the k-th largest of the m exact scores (ranks are a permutation: one thread writes)
         const double si = sc[threadIdx.x];
         uint32_t rank = 0;
@@ -2525,7 +2444,6 @@ __global__ __launch_bounds__(256) void filter_refine_thr_kernel(const FilterArgs
             if (t > thr) thr = t;
         }
     }
-    REFINE_STAMP(4);
     if (!fuse) {
         if (threadIdx.x == 0) a.thr[q] = thr;
         return;
@@ -2563,8 +2481,6 @@ __global__ __launch_bounds__(256) void filter_refine_thr_kernel(const FilterArgs
         a.thr[q] = thr;
         a.cnt[q] = new_cnt;
     }
-    REFINE_STAMP(5);
-#undef REFINE_STAMP
     if (!FINISH) return;
     __syncthreads();  // surv[] complete; stage[] is free from here on
     // ---- exact distances of the survivors: 16 rows per wave and step (filter_rescore_score_kernel's inner step)
@@ -2801,18 +2717,17 @@ static hipError_t launch_scan_narrow(const FilterArgs& a, int64_t row_begin, int
     }
 }
 
-template <int SPACE, int R, int NW, bool NT = false, int QD = 4, bool PRIO = false, int MT = 2, bool DMA = false, bool STAG = false>
+template <int SPACE, int R, bool I8, int NQT = 16>
 static hipError_t launch_scan_asm(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s, ScanInfo* info) {
-    constexpr int tile_rows = NW * 16 * MT;
+    constexpr int NW = kAsmWaves, tile_rows = NW * 32;
     const int64_t tile_begin = row_begin / tile_rows;
     const int64_t tile_end = (row_end + tile_rows - 1) / tile_rows;
     if (tile_end <= tile_begin) return hipSuccess;
-    const size_t lds = scan_code_qbufs(QD) * kChunkVec * sizeof(uint4) + 3 * kFilterQueries * sizeof(float) +
-                       (size_t)NW * 12 * scan_code_stage_cap(QD, NW, MT);
+    const size_t lds = kAsmQBufs * kChunkVec * sizeof(uint4) + 3 * kFilterQueries * sizeof(float) + (size_t)NW * 12 * kAsmStageCap;
     const int64_t ntiles = tile_end - tile_begin;
-    const int max_grid = 256 * ((16 / MT) / NW);  // two waves per SIMD on every CU (<= kScanMaxGrid)  // two waves per SIMD on every CU
+    const int max_grid = 256;  // one 8-wave workgroup per CU: two waves per SIMD (<= kScanMaxGrid)
     const int grid = (int)(ntiles < max_grid ? ntiles : max_grid);
-    auto kern = filter_scan_asm_kernel<SPACE, R, NW, NT, QD, PRIO, MT, DMA, STAG>;
+    auto kern = filter_scan_asm_kernel<SPACE, R, I8, NQT>;
     static std::atomic<uint64_t> configured{0};  // per instantiation
     static std::atomic<int> lds_base_ok{0};      // 0 = not checked yet, 1 = ok, -1 = the kernel has static LDS
     if (lds_base_ok.load(std::memory_order_acquire) == 0) {
@@ -2823,137 +2738,36 @@ static hipError_t launch_scan_asm(const FilterArgs& a, int64_t row_begin, int64_
     if (lds_base_ok.load(std::memory_order_acquire) < 0) return hipErrorInvalidConfiguration;  // dynamic LDS would not start at 0
     if (hipError_t e = ensure_dynamic_lds(configured, reinterpret_cast<const void*>(kern), (int)lds); e != hipSuccess)
         return e;
-    const int xcd_mode = grid % 8 == 0 && ntiles >= grid && a.tn->scan_xcd ? 1 : 0;
-    kern<<<grid, NW * 64, lds, s>>>(a, tile_begin, tile_end, xcd_mode);
+    kern<<<grid, NW * 64, lds, s>>>(a, tile_begin, tile_end, /*xcd_mode=*/0);
     // (the kernel's own tail moves the entries into the candidate lists: there is no scatter launch)
     info->nw = NW;
-    info->dbg = QD == 108 ? 1 : 0;
-    info->i8 = !scan_code_i8(QD) ? 0 : (SPACE == kSpaceCosine ? 1 : (SPACE == kSpaceIp ? 2 : 0));  // how the scatter turns stored values into bounds
+    info->i8 = !I8 ? 0 : (SPACE == kSpaceCosine ? 1 : (SPACE == kSpaceIp ? 2 : 0));  // how the scatter turns stored values into bounds
     return hipGetLastError();
 }
 
-// Picks the scan kernel for a launch.  Default library: the int8 body (ArchVGPR accumulators) wherever the pass has an int8
-// shadow, the bf16 body (8 waves, LDS-DMA staging) for an index that keeps a bf16 shadow, the compiler-scheduled kernel for
-// an index without shadow.  `make AB=1` adds the tuning variants (Tuning::scan_*; tools/scan_ab.py and the `ab`-marked
-// tests); the handle's tuning state picks among them -- nothing here reads the environment.
+// Picks the scan kernel for a launch: the narrow kernel for small batches it takes; the int8 body wherever the pass has an
+// int8 shadow; the bf16 body for an index that keeps a bf16 shadow; the compiler-scheduled kernel for an index without
+// shadow (fp32 rows converted in registers).  The handle's tuning state picks among them -- nothing here reads the
+// environment.
 template <int SPACE>
 static hipError_t launch_scan_space(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s, ScanInfo* info) {
-    const Tuning& tn = *a.tn;
-    const int nkc = a.ld / kFilterChunkK;
     if (filter_narrow_ok(a)) return launch_scan_narrow<SPACE, false>(a, row_begin, row_end, s);  // appends to the lists itself
-    if ((a.Xb || a.X8) && tn.scan_asm) {
-        // hand-written body (tools/gen_scan_asm.py): one 8-wave workgroup per CU (256-row tiles: the query image is staged
-        // once per CU, by LDS-DMA), non-temporal X loads, ring of 4 k-steps -- measured fastest (profiles/r01/scan_ab_*.txt);
-        // a ring of R k-steps needs the tile's k-steps to be a multiple of R
-#ifdef MLVDB_AB
-        if (a.Xb && tn.scan_mt == 4) {  // one wave per SIMD, 64 rows per wave
-            if (nkc % 2 == 0) return launch_scan_asm<SPACE, 4, 4, true, 4, false, 4>(a, row_begin, row_end, s, info);
-            return launch_scan_asm<SPACE, 2, 4, true, 4, false, 4>(a, row_begin, row_end, s, info);
-        }
-#endif
-        if (a.X8 && a.ld8 > 0) {  // int8 shadow (the caller attached it): ld8/128 chunks, an even number
-#ifdef MLVDB_SCAN_DIAGNOSTICS  // make DIAG=1: timing diagnostics of the int8 body (wrong results by design)
-            if constexpr (SPACE == kSpaceCosine) {
-                switch (tn.scan_diag) {
-                    case 209: return launch_scan_asm<SPACE, 4, 8, true, 209, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 210: return launch_scan_asm<SPACE, 4, 8, true, 210, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 212: return launch_scan_asm<SPACE, 4, 8, true, 212, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 213: return launch_scan_asm<SPACE, 4, 8, true, 213, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 234: return launch_scan_asm<SPACE, 4, 8, true, 234, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 223: return launch_scan_asm<SPACE, 4, 8, true, 223, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 224: return launch_scan_asm<SPACE, 4, 8, true, 224, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 225: return launch_scan_asm<SPACE, 4, 8, true, 225, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 226: return launch_scan_asm<SPACE, 4, 8, true, 226, true, 2, true>(a, row_begin, row_end, s, info);
-                    case 227: return launch_scan_asm<SPACE, 4, 8, true, 227, true, 2, true>(a, row_begin, row_end, s, info);
-                    default: break;
-                }
-            }
-#endif
-#ifdef MLVDB_AB
-            if constexpr (SPACE != kSpaceL2) {  // round 1: AccVGPR accumulators, serial admission phase; with / without wave priorities
-                if (!tn.scan_va) {
-                    if (tn.scan_prio != 0) return launch_scan_asm<SPACE, 4, 8, true, 208, true, 2, true>(a, row_begin, row_end, s, info);
-                    return launch_scan_asm<SPACE, 4, 8, true, 208, false, 2, true>(a, row_begin, row_end, s, info);
-                }
-            }
-            if constexpr (SPACE == kSpaceCosine) {  // tuning variants of the folded body
-                const int var = tn.scan_var;
-                if (var == 229 && (a.ld8 / 64) % 6 == 0) return launch_scan_asm<SPACE, 6, 8, true, 229, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 228 && (a.ld8 / 64) % 6 == 0) return launch_scan_asm<SPACE, 6, 8, true, 228, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 214 && (a.ld8 / 64) % 6 == 0) return launch_scan_asm<SPACE, 6, 8, true, 214, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 215) return launch_scan_asm<SPACE, 4, 8, true, 215, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 216) return launch_scan_asm<SPACE, 4, 8, true, 216, false, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 219) return launch_scan_asm<SPACE, 4, 8, true, 219, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 222) return launch_scan_asm<SPACE, 4, 8, true, 222, true, 2, true, true>(a, row_begin, row_end, s, info);
-                if (var == 220) return launch_scan_asm<SPACE, 4, 8, true, 220, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 221) return launch_scan_asm<SPACE, 4, 8, true, 221, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 230) return launch_scan_asm<SPACE, 4, 4, true, 230, false, 4, true>(a, row_begin, row_end, s, info);
-                if (var == 231) return launch_scan_asm<SPACE, 4, 8, true, 231, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 232) return launch_scan_asm<SPACE, 4, 8, true, 232, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 233) return launch_scan_asm<SPACE, 4, 8, true, 233, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 235) return launch_scan_asm<SPACE, 4, 8, true, 235, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 236) return launch_scan_asm<SPACE, 4, 8, true, 236, true, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 217) return launch_scan_asm<SPACE, 4, 4, true, 217, false, 2, true>(a, row_begin, row_end, s, info);
-                if (var == 218) return launch_scan_asm<SPACE, 4, 4, true, 218, true, 2, true>(a, row_begin, row_end, s, info);
-            }
-#endif
-            if constexpr (SPACE == kSpaceCosine) {  // round 2's default body stays in the default library as the A/B reference
-                if (tn.scan_var == 237) return launch_scan_asm<SPACE, 4, 8, true, 237, true, 2, true>(a, row_begin, row_end, s, info);
-            }
-            // passes of <= 64 / <= 128 queries: the same body computing 4 / 8 of the 16 query tiles (round 4; SCAN_NQT=16 pads)
-            const int nqt = tn.scan_nqt > 0 ? tn.scan_nqt : (a.nq <= 64 ? 4 : (a.nq <= 128 ? 8 : 16));
-            if constexpr (SPACE == kSpaceL2) {  // folded admission test with per-row integer offsets (the pass computed them: api.hip prep_pass)
-                // (the only int8 bodies of l2: api.hip attaches the int8 shadow to an l2 pass only with rp8_cap and l2c set)
-                if (nqt <= 4 && a.nq <= 64) return launch_scan_asm<SPACE, 4, 8, true, 245, true, 2, true>(a, row_begin, row_end, s, info);
-                if (nqt <= 8 && a.nq <= 128) return launch_scan_asm<SPACE, 4, 8, true, 244, true, 2, true>(a, row_begin, row_end, s, info);
-                return launch_scan_asm<SPACE, 4, 8, true, 243, true, 2, true>(a, row_begin, row_end, s, info);
-            } else {
-                if (nqt <= 4 && a.nq <= 64) return launch_scan_asm<SPACE, 4, 8, true, 242, true, 2, true>(a, row_begin, row_end, s, info);
-                if (nqt <= 8 && a.nq <= 128) return launch_scan_asm<SPACE, 4, 8, true, 241, true, 2, true>(a, row_begin, row_end, s, info);
-                return launch_scan_asm<SPACE, 4, 8, true, 211, true, 2, true>(a, row_begin, row_end, s, info);
-            }
-        }
-        // everything below streams the bf16 shadow (an int8-only index without usable int8 bounds has none: its
-        // fp32 rows are converted in registers by the compiler-scheduled kernel)
-        if (!a.Xb) return launch_scan_one<SPACE, false>(a, row_begin, row_end, s, info);
-#ifdef MLVDB_AB
-        const int nw = tn.scan_nw;
-        if constexpr (SPACE == kSpaceCosine) {
-            if (nw == 8 && nkc % 2 == 0 && tn.scan_prio == 1)
-                return launch_scan_asm<SPACE, 4, 8, true, 4, true>(a, row_begin, row_end, s, info);
-            if (nkc % 2 == 0 && tn.scan_nt == 0)
-                return nw == 8 ? launch_scan_asm<SPACE, 4, 8, false>(a, row_begin, row_end, s, info)
-                               : launch_scan_asm<SPACE, 4, 4, false>(a, row_begin, row_end, s, info);
-#ifdef MLVDB_SCAN_DIAGNOSTICS  // make DIAG=1: timing diagnostics (tools/scan_ab.py --no-check), wrong results by design
-            switch (nw == 8 && nkc % 2 == 0 ? tn.scan_diag : 0) {
-                case 101: return launch_scan_asm<SPACE, 4, 8, true, 101>(a, row_begin, row_end, s, info);
-                case 102: return launch_scan_asm<SPACE, 4, 8, true, 102>(a, row_begin, row_end, s, info);
-                case 103: return launch_scan_asm<SPACE, 4, 8, true, 103>(a, row_begin, row_end, s, info);
-                case 104: return launch_scan_asm<SPACE, 4, 8, true, 104>(a, row_begin, row_end, s, info);
-                case 107: return launch_scan_asm<SPACE, 4, 8, true, 107>(a, row_begin, row_end, s, info);
-                case 108: return launch_scan_asm<SPACE, 4, 8, true, 108>(a, row_begin, row_end, s, info);
-                case 109: return launch_scan_asm<SPACE, 4, 8, true, 109>(a, row_begin, row_end, s, info);
-                default: break;
-            }
-#endif
-        }
-        if (nw == 8 && nkc % 2 == 0 && tn.scan_dma && tn.scan_stag)  // later half of the waves half a tile behind
-            return launch_scan_asm<SPACE, 4, 8, true, 4, false, 2, true, true>(a, row_begin, row_end, s, info);
-        if (nw == 8 && !tn.scan_dma) {  // query image staged through registers
-            if (nkc % 2 == 0) return launch_scan_asm<SPACE, 4, 8, true>(a, row_begin, row_end, s, info);
-            return launch_scan_asm<SPACE, 2, 8, true>(a, row_begin, row_end, s, info);
-        }
-        if (nw != 8) {  // two 4-wave workgroups per CU
-            if (nkc % 2 == 0) return launch_scan_asm<SPACE, 4, 4, true>(a, row_begin, row_end, s, info);
-            return launch_scan_asm<SPACE, 2, 4, true>(a, row_begin, row_end, s, info);
-        }
-#endif
-        // query image staged by LDS-DMA (+2 % over the register-staged variant)
-        if (nkc % 2 == 0) return launch_scan_asm<SPACE, 4, 8, true, 4, false, 2, true>(a, row_begin, row_end, s, info);
-        return launch_scan_asm<SPACE, 2, 8, true, 4, false, 2, true>(a, row_begin, row_end, s, info);
+    // hand-written bodies (tools/gen_scan_asm.py): one 8-wave workgroup per CU (256-row tiles: the query image is staged
+    // once per CU, by LDS-DMA), non-temporal X loads, ring of 4 k-steps -- measured fastest (profiles/r01/scan_ab_*.txt)
+    if (a.X8 && a.ld8 > 0) {  // int8 shadow (the caller attached it): ld8/128 chunks, an even number
+        // passes of <= 64 / <= 128 queries: the same body computing 4 / 8 of the 16 query tiles (round 4; SCAN_NQT=16 pads).
+        // l2: the folded admission test with per-row integer offsets (the pass computed them: api.hip prep_pass) is the only
+        // int8 body -- api.hip attaches the int8 shadow to an l2 pass only with rp8_cap and l2c set
+        const int nqt = a.tn->scan_nqt > 0 ? a.tn->scan_nqt : (a.nq <= 64 ? 4 : (a.nq <= 128 ? 8 : 16));
+        if (nqt <= 4 && a.nq <= 64) return launch_scan_asm<SPACE, 4, true, 4>(a, row_begin, row_end, s, info);
+        if (nqt <= 8 && a.nq <= 128) return launch_scan_asm<SPACE, 4, true, 8>(a, row_begin, row_end, s, info);
+        return launch_scan_asm<SPACE, 4, true, 16>(a, row_begin, row_end, s, info);
     }
-    // compiler-scheduled kernel: corpora without shadow (fp32 rows converted in registers), and the A/B reference
-    if (a.Xb) return launch_scan_one<SPACE, true>(a, row_begin, row_end, s, info);
+    if (a.Xb) {  // bf16 shadow; a ring of R k-steps needs the tile's k-steps (two per chunk) to be a multiple of R
+        if ((a.ld / kFilterChunkK) % 2 == 0) return launch_scan_asm<SPACE, 4, false>(a, row_begin, row_end, s, info);
+        return launch_scan_asm<SPACE, 2, false>(a, row_begin, row_end, s, info);
+    }
+    // no shadow (or an int8-only index without usable int8 bounds): fp32 rows converted in registers
     return launch_scan_one<SPACE, false>(a, row_begin, row_end, s, info);
 }
 

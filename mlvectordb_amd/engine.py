@@ -108,7 +108,7 @@ class HipScanEngine:
         self._check(self._lib.mlvdb_index_set_strategy(self._h, _native.STRATEGY_CODES[strategy]), "set_strategy")
 
     def set_tuning(self, **knobs: int) -> None:
-        """Tuning state of the handle (``mlvdb_index_set_tuning``): ``set_tuning(SCAN_VAR=237, I8=0)``.  The MLVDB_* environment
+        """Tuning state of the handle (``mlvdb_index_set_tuning``): ``set_tuning(SCAN_NQT=16, I8=0)``.  The MLVDB_* environment
         variables are only read when the handle is created; this is how a live handle is switched (tools/scan_ab.py)."""
         for key, value in knobs.items():
             self._check(self._lib.mlvdb_index_set_tuning(self._h, f"{key}={int(value)}".encode()), f"set_tuning({key})")

@@ -9,13 +9,11 @@ ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "mlvectordb_amd" / "csrc"
 
 
-def test_scan_bodies_are_what_the_generator_emits(tmp_path):
+def test_default_scan_bodies_are_what_the_generator_emits(tmp_path):
     gen = ROOT / "tools" / "gen_scan_asm.py"
-    # --diag: the default library's bodies + the AB variants + the timing diagnostics (make / make AB=1 / make DIAG=1)
-    names = subprocess.run([sys.executable, str(gen), "--list", "--diag"], check=True, capture_output=True, text=True).stdout.split()
-    default = subprocess.run([sys.executable, str(gen), "--list"], check=True, capture_output=True, text=True).stdout.split()
-    assert set(default) < set(names) and len(default) <= 24, "the default library carries only its own bodies"
-    subprocess.run([sys.executable, str(gen), "--outdir", str(tmp_path), "--diag"], check=True, capture_output=True)
+    names = subprocess.run([sys.executable, str(gen), "--list"], check=True, capture_output=True, text=True).stdout.split()
+    assert len(names) <= 24, "the library carries only its own bodies"
+    subprocess.run([sys.executable, str(gen), "--outdir", str(tmp_path)], check=True, capture_output=True)
     assert names and sorted(p.name for p in tmp_path.iterdir()) == sorted(names)
     dispatch = (tmp_path / "scan_asm_dispatch.inc").read_text()
     for name in names:
@@ -25,7 +23,7 @@ def test_scan_bodies_are_what_the_generator_emits(tmp_path):
         if name.startswith("scan_asm_") and name not in ("scan_asm_dispatch.inc", "scan_asm_consts.inc"):
             assert f'#include "{name}"' in dispatch, f"{name} is generated but never dispatched"
             assert fresh.count("asm volatile(") == 1  # one statement: nothing in flight crosses compiler-managed code
-    body = (tmp_path / "scan_asm_cosine_i8.inc").read_text()
+    body = (tmp_path / "scan_asm_cosine_i8_va.inc").read_text()
     assert "v_mfma_i32_16x16x64_i8" in body and "v_mfma_f32_16x16x32_bf16" not in body
 
 
@@ -41,7 +39,7 @@ def test_bench_hash_of_the_default_bodies_needs_no_built_tree():
         assert (CSRC / "scan_asm_cosine_i8_va.inc").read_text() == body
 
 
-def test_query_tile_and_l2_bodies_have_the_structure_they_claim():
+def test_int8_query_tile_and_l2_bodies_have_the_structure_they_claim():
     """Round 4 bodies, by their text: the 4- / 8-tile bodies issue a quarter / half of the 16-tile body's MFMAs (nothing for the
     empty query tiles); the l2 body takes its first k-step's C operand from the offset registers, prefetches them a tile ahead
     through the row pairs' descriptor and keeps its thresholds in registers (one compare per query tile, like cosine's)."""
@@ -52,8 +50,7 @@ def test_query_tile_and_l2_bodies_have_the_structure_they_claim():
     spec.loader.exec_module(gen)
     mf = {}
     for nqt in (16, 8, 4):
-        gen.DBG.clear()
-        body = gen.generate("cosine", 4, 4, 8, True, True, 2, True, False, True, True, eo=True, fs=True, nqt=nqt)
+        body = gen.generate("cosine", 4, i8=True, nqt=nqt)
         mf[nqt] = body.count("v_mfma_i32_16x16x64_i8 v[")
         assert body.count("asm volatile(") == 1 and f".Lhit{nqt - 1}c200" in body and f".Lhit{nqt}c200" not in body
     assert mf[16] == 4 * 128 and mf[8] * 2 == mf[16] and mf[4] * 4 == mf[16]  # 4 copies of the 4-k-step body x 2 * NQT * 2 x 2

@@ -692,15 +692,16 @@ def test_range_capacity_overflow_is_reported_then_resolved():
         eng.close()
 
 
-# one case per live code path of the DEFAULT library (the tuning variants of `make AB=1` are in tests/test_ab_variants.py, marked `ab`)
-SCAN_VARIANTS = [
-    {},                                              # defaults: the int8 body (shadow zero-padded to a multiple of 256 columns); bf16 body for d = 64 / 128
-    {"MLVDB_I8": "0", "MLVDB_SHADOW": "bf16"},       # bf16 body: one 8-wave workgroup per CU, Q by LDS-DMA (rings of 4 and of 2 k-steps)
-    {"MLVDB_SCAN_VAR": "237"},                       # (cosine, int8) round 2's default body: the A/B reference kept in the default library
-    {"MLVDB_SCAN_XCD": "1"},                         # every XCD scans one contiguous eighth of the tile range
-    {"MLVDB_SHADOW": "bf16"},                        # both shadows kept (round 2's default): int8 scans, bf16 seeding / narrow passes off
-    {"MLVDB_SEED_I8": "0"},                          # int8-only index, seeding pass by the compiler kernel on the fp32 rows
-    {"MLVDB_I8_PAD": "0"},                           # round 3: int8 shadow only where dim % 256 == 0
+# one case per live code path of the library
+VARIANT_SHAPES = [("cosine", 128), ("l2", 192), ("ip", 64), ("cosine", 768), ("l2", 1536), ("ip", 768), ("l2", 256)]
+SCAN_VARIANTS = [  # (tuning variables, the shapes the variant runs)
+    ({}, VARIANT_SHAPES),                                    # defaults: the int8 body (shadow zero-padded to a multiple of 256 columns); bf16 body for d = 64 / 128
+    ({"MLVDB_I8": "0", "MLVDB_SHADOW": "bf16"},              # bf16 body: one 8-wave workgroup per CU, Q by LDS-DMA (rings of 4 and of 2 k-steps)
+     [("ip", 64), ("ip", 768)]),
+    ({"MLVDB_SHADOW": "bf16"}, [("ip", 64), ("ip", 768)]),   # both shadows kept (round 2's default): int8 scans, bf16 seeding / narrow passes off
+    ({"MLVDB_SEED_I8": "0"}, [("l2", 192), ("l2", 1536)]),   # int8-only index, seeding pass by the compiler kernel on the fp32 rows
+    ({"MLVDB_I8_PAD": "0"},                                  # round 3: int8 shadow only where dim % 256 == 0
+     [("cosine", 128), ("cosine", 768), ("l2", 256)]),
 ]
 
 NARROW_CASES = [
@@ -763,8 +764,8 @@ def test_wide_rows_through_the_filter_agree_with_oracle(space, d, nq):
     assert_knn_matches(got, oracle_knn(qs, rows, 10, space, deleted), f"wide/{space}/d{d}/nq{nq}")
 
 
-# (the default structure only: each step switched off in turn -- SMALL_SEED=0, SMALL_FINISH=0, SMALL_NQ=0 / 8 -- is in
-# tests/test_ab_variants.py, marked `ab`: alternative paths, not live ones)
+# (the default structure only: each step switched off in turn -- SMALL_SEED=0, SMALL_FINISH=0, SMALL_NQ=0 / 8 -- is
+# test_alternative_small_batch_and_l2_paths_agree_with_oracle below)
 SMALL_KNOBS = [
     {},                                 # 1-2 queries: exact prefix seed + fused last refine / rescoring / ranking; one query on a corpus
                                         # of <= 11.5M / k rows: ONE scan round after an 11,520-row exact prefix (round 4)
@@ -815,11 +816,7 @@ def test_one_query_among_thousands_of_equal_rows(copies, expect_fallback):
     assert np.array_equal(got[0][0], np.sort(where)[:k])
 
 
-VARIANT_SHAPES = [("cosine", 128), ("l2", 192), ("ip", 64), ("cosine", 768), ("l2", 1536), ("ip", 768), ("l2", 256)]
-
-
-@pytest.mark.parametrize("variant,space,d", [(v, sp, d) for i, v in enumerate(SCAN_VARIANTS)
-                                             for j, (sp, d) in enumerate(VARIANT_SHAPES) if i == 0 or (i + j) % 3 == 0],
+@pytest.mark.parametrize("variant,space,d", [(v, sp, d) for v, shapes in SCAN_VARIANTS for sp, d in shapes],
                          ids=lambda v: (",".join(f"{k[6:]}={x}" for k, x in v.items()) or "default") if isinstance(v, dict) else str(v))
 def test_scan_kernel_variants_agree_with_oracle(variant, space, d, monkeypatch):
     """Every generated geometry of the filter scan (the variable is read per launch), on corpora with more
@@ -835,6 +832,43 @@ def test_scan_kernel_variants_agree_with_oracle(variant, space, d, monkeypatch):
     ld8 = 0 if d in (64, 128) or (variant.get("MLVDB_I8_PAD") == "0" and d % 256) else -(-d // 256) * 256
     assert stats["bound_dtype"] == (2 if ld8 and variant.get("MLVDB_I8") != "0" else 1)
     assert_knn_matches(got, oracle_knn(qs, rows, 10, space, deleted), f"variant {variant}/{space}/d{d}")
+
+
+SMALL_KNOBS = [
+    {"MLVDB_SMALL_SEED": "0"},          # dense int8 seeding pass + refine, fused finish
+    {"MLVDB_SMALL_FINISH": "0"},        # prefix seed, the three finishing kernels
+    {"MLVDB_SMALL_NQ": "0"},            # round 2's structure
+    {"MLVDB_SMALL_NQ": "8"},            # both steps for up to 8 queries
+    {"MLVDB_NARROW_I8_MAX": "8"},       # the int8 narrow kernel (round 3's scan for 1-8 queries) instead of the 4-tile assembly body
+    {"MLVDB_SCAN_NQT": "16"},           # every pass padded to 16 query tiles (round 3)
+]
+SMALL_CASES = [
+    ("cosine", 768, 1, 70_003, 10, 0.05), ("cosine", 768, 2, 70_003, 10, 0.05), ("l2", 768, 1, 40_001, 10, 0.3),
+    ("ip", 256, 2, 150_001, 1, 0.0), ("l2", 1536, 1, 33_001, 64, 0.05), ("cosine", 256, 1, 150_001, 33, 0.9),
+    ("ip", 768, 1, 3_000, 10, 0.05), ("l2", 256, 2, 9_000, 64, 0.995), ("cosine", 768, 5, 70_003, 10, 0.05), ("l2", 768, 40, 40_001, 10, 0.05),
+]
+
+
+@pytest.mark.parametrize("knobs", SMALL_KNOBS, ids=lambda v: ",".join(f"{k[6:]}={x}" for k, x in v.items()))
+@pytest.mark.parametrize("space,d,nq,n,k,frac", SMALL_CASES)
+def test_alternative_small_batch_and_l2_paths_agree_with_oracle(space, d, nq, n, k, frac, knobs, monkeypatch):
+    from mlvectordb_amd.engine import HipScanEngine
+
+    for key, val in knobs.items():
+        monkeypatch.setenv(key, val)
+    rows, qs = make_case(900 + d + nq + k, n, d, nq, dup=True)
+    deleted = deleted_mask(13, n, frac)
+    eng = HipScanEngine(d, space, device=0, strategy="filter")
+    try:
+        for part in (rows[: n // 2], rows[n // 2:]):
+            eng.append(part)
+        eng.tombstone(deleted.nonzero()[0])
+        got = eng.search(qs, k)
+        stats = eng.last_stats()
+    finally:
+        eng.close()
+    assert stats["strategy_used"] == 2 and stats["fallback_queries"] == 0 and stats["bound_dtype"] == 2
+    assert_knn_matches(got, oracle_knn(qs, rows, k, space, deleted), f"alt {knobs}/{space}/d{d}/nq{nq}/k{k}")
 
 
 @pytest.mark.parametrize("space,d,strategy", [("cosine", 128, "filter"), ("l2", 20, "exact"), ("ip", 192, "filter")])

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""A/B the filter-scan kernel variants in ONE process on one resident corpus (tuning aid).
+"""A/B the library's tuning knobs in ONE process on one resident corpus (tuning aid).
 
-Variants are compile-time instantiations picked per launch from the handle's tuning state (mlvdb_index_set_tuning: the
-library reads the environment only when a handle is created), given as --envs "A=1,B=2;A=0" with the tuning keys
-(SCAN_VAR, SCAN_NW, I8, ...; an MLVDB_ prefix is accepted).  Most variants exist only in the AB build:
-    make -C mlvectordb_amd/csrc AB=1 && MLVDB_HIP_LIBRARY=mlvectordb_amd/csrc/libmlvdb_hip_ab.so python tools/scan_ab.py ...
-Prints per-variant median wave time and scan-kernel GB/s (HIP events), interleaved over rounds.
+The knobs are picked per launch from the handle's tuning state (mlvdb_index_set_tuning: the library reads the environment
+only when a handle is created), given as --envs "A=1,B=2;A=0" with the tuning keys (SCAN_NQT, I8, ROUND1, ...; an MLVDB_
+prefix is accepted).  A knob that selects another kernel -- a new scan body under trial, say -- is A/B'd the same way.
+Every variant must return the first one's ids.  Prints per-variant median wave time and scan-kernel GB/s (HIP events),
+interleaved over rounds.
 """
 import argparse
 import sys
@@ -24,9 +24,8 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--waves", type=int, default=6)
-    ap.add_argument("--envs", default=";SCAN_VAR=237")
+    ap.add_argument("--envs", default=";SCAN_NQT=16")
     ap.add_argument("--space", default="cosine")
-    ap.add_argument("--no-check", action="store_true", help="timing diagnostics that change the answer")
     args = ap.parse_args()
     import torch
 
@@ -64,7 +63,7 @@ def main():
             ids = lab.cpu().numpy().copy()
             if ref is None:
                 ref = ids
-            assert args.no_check or np.array_equal(ids, ref), f"variant {c} changed the answer"
+            assert np.array_equal(ids, ref), f"variant {c} changed the answer"
     print(f"rows {args.rows} dim {args.dim} batch {args.batch}")
     for c in combos:
         scan = np.median(res[c]["scan"])
