@@ -72,10 +72,13 @@ hipError_t launch_where_each_eval(const WhereOp* prog, const int32_t* prog_off, 
                                   int64_t seg_rows, int32_t nseg, unsigned long long* bits, uint32_t* seg_cnt, hipStream_t s) {
     if (total <= 0 || nseg <= 0) return hipSuccess;
     if (n_ops > kWhereEachMaxOps || n_progs > kWhereEachMaxPrograms || ncols > MLVDB_MAX_ATTRS) return hipErrorInvalidValue;
-    static std::atomic<uint64_t> lds_set{0};
     const size_t lds = each_eval_vals_offset(n_ops) + (size_t)ncols * 256 * sizeof(int64_t);
+    // configured once, for the largest call (kWhereEachMaxOps ops over MLVDB_MAX_ATTRS columns: 65,808 B): the attribute
+    // holds for the rest of the process, so it must cover every size a later call may launch with
+    static std::atomic<uint64_t> lds_set{0};
+    const size_t lds_max = each_eval_vals_offset(kWhereEachMaxOps) + (size_t)MLVDB_MAX_ATTRS * 256 * sizeof(int64_t);
     if (lds > 48 * 1024) {
-        hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(where_each_eval_kernel), (int)lds);
+        hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(where_each_eval_kernel), (int)lds_max);
         if (e != hipSuccess) return e;
     }
     where_each_eval_kernel<<<(unsigned)((nseg + kEachWaves - 1) / kEachWaves), kEachWaves * 64, lds, s>>>(
@@ -258,11 +261,13 @@ template <int SPACE, int QT>
 static hipError_t launch_gather_qt(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
                                    const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t k, int32_t nchunk,
                                    TopEntry* partial, hipStream_t s) {
+    // configured once per instance, for the largest tile any ld may ask for (64 KiB, launch_where_gather's limit): the
+    // attribute holds for the rest of the process, whatever the ld of a later call
     static std::atomic<uint64_t> lds_set{0};
     auto kern = where_gather_kernel<SPACE, QT>;
     const size_t lds = where_gather_lds(QT, ld);
     if (lds > 48 * 1024) {
-        hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(kern), (int)lds);
+        hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(kern), 64 * 1024);
         if (e != hipSuccess) return e;
     }
     kern<<<dim3((unsigned)ntiles, (unsigned)nchunk), 256, lds, s>>>(X, Qpad, qaux, labels, tiles, ld, k, nchunk, partial);

@@ -352,3 +352,70 @@ def test_upsert_arrays_extracts_declared_attributes():
     with pytest.raises(ValueError):
         qp.upsert_arrays(rng.standard_normal((1, 4)), "ns", metadata=[{"year": "1990"}])
     assert qp.count_where({}, "ns") == 3
+
+
+# ---------------------------------------------------------------- the raw-program generator and the NumPy evaluator
+def _scalar_match(program, cols, i):
+    """One row through the program, op by op, with Python ints and floats: the semantics of include/mlvdb_where.h."""
+    stack = []
+    for op, attr, a, b in program.ops.tolist():
+        if op in (W.AND, W.OR):
+            y, x = stack.pop(), stack.pop()
+            stack.append((x and y) if op == W.AND else (x or y))
+        elif op == W.NOT:
+            stack.append(not stack.pop())
+        elif op == W.TRUE:
+            stack.append(True)
+        elif cols[attr].dtype == np.int64:
+            v = int(cols[attr][i])
+            have = v != -(2 ** 63)
+            if op == W.IN:
+                stack.append(have and v in program.set[a:a + b].tolist())
+            elif op == W.EXISTS:
+                stack.append(have)
+            elif op == W.NE:
+                stack.append(not (have and v == a))
+            else:
+                stack.append(have and {W.EQ: v == a, W.LT: v < a, W.LE: v <= a, W.GT: v > a, W.GE: v >= a}[op])
+        else:
+            v = float(cols[attr][i])
+            lit = float(np.array([a], np.int64).view(np.float64)[0])
+            stack.append({W.EQ: v == lit, W.NE: not v == lit, W.LT: v < lit, W.LE: v <= lit, W.GT: v > lit,
+                          W.GE: v >= lit, W.EXISTS: v == v}[op])
+    assert len(stack) == 1
+    return stack[0]
+
+
+def test_raw_programs_are_valid_and_the_numpy_evaluator_matches_a_scalar_one():
+    from tests.where_helpers import eval_program, hostile_columns, program_depth, random_raw_program
+
+    rng = np.random.default_rng(32)
+    kinds = {0: "int64", 3: "float64", 7: "int64", 15: "float64"}
+    n = 300
+    cols = hostile_columns(rng, n, kinds)
+    sizes = set()
+    for j in range(60):
+        size = [1, 2, 17, 63, 64][j % 5]
+        prog = random_raw_program(rng, kinds, size, deep=j % 3 == 0, p_in=0.3)
+        ops = prog.ops
+        # the host validation of api.hip (where_prepare): exactly `size` ops, depth 1..32 throughout and 1 at the end,
+        # IN on int64 columns only, every IN range inside the set table and sorted
+        assert ops.size == size and program_depth(prog) <= W.MAX_DEPTH
+        depth = 0
+        for op, attr, a, b in ops.tolist():
+            depth += 1 if op <= W.EXISTS else (-1 if op in (W.AND, W.OR) else 0)
+            assert depth >= 1
+            if W.EQ <= op <= W.EXISTS:
+                assert attr in kinds
+            if op == W.IN:
+                assert kinds[attr] == "int64" and 0 <= a and 0 <= b and a + b <= prog.set.size
+                r = prog.set[a:a + b]
+                assert np.all(r[:-1] <= r[1:])
+                sizes.add(min(b, 2))
+        assert depth == 1
+        if size == 64 and j % 3 == 0:
+            assert program_depth(prog) == W.MAX_DEPTH
+        got = eval_program(prog, cols, n)
+        want = np.array([_scalar_match(prog, cols, i) for i in range(n)])
+        assert np.array_equal(got, want), j
+    assert sizes == {0, 1, 2}  # empty, single and longer IN ranges all drawn

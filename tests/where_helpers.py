@@ -223,3 +223,101 @@ def random_filter(rng, depth=0):
         return out
     comb = "$and" if r < 0.85 else "$or"
     return {comb: [random_filter(rng, depth + 1) for _ in range(rng.integers(0, 4))]}
+
+
+# ---------------------------------------------------------------- hostile columns and raw programs
+# Value pools for the attribute columns and the literals of raw programs: the sentinels, the extremes of each type, and
+# a few small values repeated often so that EQ / IN / LT / LE land on the values the rows hold.
+INT64_MAX = np.iinfo(np.int64).max
+INT_POOL = np.array([W.INT64_ABSENT, W.INT64_ABSENT + 1, W.INT64_ABSENT + 2, INT64_MAX, INT64_MAX - 1, -1, 0, 1,
+                     2, 3, 7, 2, 3, 7, 2, 3], dtype=np.int64)
+_F_BASE = [0.0, 1.0, -1.0, 1.5, 5e-324, np.finfo(np.float64).max, -np.finfo(np.float64).max]
+with np.errstate(over="ignore"):  # (the neighbour of DBL_MAX above it is inf)
+    FLOAT_POOL = np.array(
+        [np.nan, -np.nan, np.array([0x7FF0000000000001], np.int64).view(np.float64)[0],  # NaNs: quiet, signed, signalling
+         0.0, -0.0, np.inf, -np.inf, 5e-324, -5e-324, np.finfo(np.float64).tiny]
+        + _F_BASE + [np.nextafter(x, np.inf) for x in _F_BASE] + [np.nextafter(x, -np.inf) for x in _F_BASE]
+        + [1.0, 1.5, 1.0, 1.5], dtype=np.float64)
+
+
+def hostile_columns(rng, n, kinds):
+    """{attr: column} with ``kinds[attr]`` in ("int64", "float64"), every value drawn from the pools above (INT64_MIN and
+    NaN are the absent markers)."""
+    return {a: (rng.choice(INT_POOL, n) if kind == "int64" else rng.choice(FLOAT_POOL, n)) for a, kind in kinds.items()}
+
+
+def set_segments(rng):
+    """An int64 table made of sorted ranges -> (table, [(offset, length), ...]): empty ranges, one entry, duplicates
+    and a long run of ~500 entries, at offsets inside the one table."""
+    parts = [np.sort(rng.choice(INT_POOL, 1)),                                      # one entry
+             np.sort(rng.choice(INT_POOL, 6)),                                      # duplicates (a pool of repeats)
+             np.sort(np.concatenate([rng.choice(INT_POOL, 8), rng.integers(-1000, 1000, 492)])),  # ~500 entries
+             np.sort(rng.integers(-50, 50, int(rng.integers(2, 200))))]
+    rng.shuffle(parts)
+    ranges, table, at = [], [], 0
+    for p in parts:
+        ranges.append((at, 0))  # empty, at this offset
+        ranges.append((at, p.size))
+        table.append(p)
+        at += p.size
+    ranges.append((at, 0))  # empty, at the very end of the table
+    return np.concatenate(table).astype(np.int64), ranges
+
+
+def random_raw_program(rng, kinds, n_ops, deep=False, p_in=0.2):
+    """A valid postfix ``W.Program`` of exactly ``n_ops`` ops over the columns ``kinds`` (attr -> kind), built directly
+    (no dict compiler): leaves TRUE / EQ..GE / IN / EXISTS with literals from the value pools, AND / OR / NOT.
+    ``deep``: push until the stack is MAX_DEPTH deep (64 ops reach exactly 32).  Its own set table from ``set_segments``."""
+    table, ranges = set_segments(rng)
+    attrs = list(kinds)
+    int_attrs = [a for a in attrs if kinds[a] == "int64"]
+    ops, depth, peak = [], 0, 0
+    for i in range(n_ops):
+        left = n_ops - i  # ops still to emit, this one included
+        can_push = depth + 1 <= W.MAX_DEPTH and depth <= left - 1
+        can_comb = depth >= 2
+        can_not = depth >= 1 and depth - 1 <= left - 1
+        if deep and can_push and peak < W.MAX_DEPTH:
+            choice = "push"
+        else:
+            opts = [o for o, ok, w in (("push", can_push, 0.5), ("comb", can_comb, 0.35), ("not", can_not, 0.15)) if ok]
+            wts = np.array([{"push": 0.5, "comb": 0.35, "not": 0.15}[o] for o in opts])
+            choice = opts[rng.choice(len(opts), p=wts / wts.sum())]
+        if choice == "comb":
+            ops.append((W.AND if rng.random() < 0.5 else W.OR, 0, 0, 0))
+            depth -= 1
+        elif choice == "not":
+            ops.append((W.NOT, 0, 0, 0))
+        else:
+            ops.append(_random_leaf_op(rng, kinds, attrs, int_attrs, ranges, p_in))
+            depth += 1
+            peak = max(peak, depth)
+    assert depth == 1, (depth, n_ops)
+    return W.Program(np.array(ops, dtype=W.OP_DTYPE), table)
+
+
+def _random_leaf_op(rng, kinds, attrs, int_attrs, ranges, p_in):
+    if int_attrs and rng.random() < p_in:
+        a, b = ranges[rng.integers(len(ranges))]
+        return (W.IN, int(int_attrs[rng.integers(len(int_attrs))]), a, b)
+    r = rng.random()
+    if r < 0.04:
+        return (W.TRUE, 0, 0, 0)
+    attr = int(attrs[rng.integers(len(attrs))])
+    if r < 0.12:
+        return (W.EXISTS, attr, 0, 0)
+    op = (W.EQ, W.NE, W.LT, W.LE, W.GT, W.GE)[rng.integers(6)]
+    if kinds[attr] == "int64":
+        lit = int(rng.choice(INT_POOL))
+    else:
+        lit = int(FLOAT_POOL[rng.integers(FLOAT_POOL.size):][:1].view(np.int64)[0])  # the bits as drawn (NaN payloads)
+    return (op, attr, lit, 0)
+
+
+def program_depth(program: W.Program) -> int:
+    """The deepest stack the program reaches."""
+    d = deepest = 0
+    for op in program.ops["op"].tolist():
+        d += 1 if op <= W.EXISTS else (-1 if op in (W.AND, W.OR) else 0)
+        deepest = max(deepest, d)
+    return deepest
