@@ -295,10 +295,8 @@ int reserve_rows(mlvdb_index* h, int64_t rows) {
 // Timing-only events (profiling): created without the system-scope fence an event record otherwise carries -- the cache
 // write-back / invalidate it costs sits between the kernels of the pass being measured (hip_runtime_api.h,
 // hipEventDisableSystemFence: "events that are only being used to measure timing").  Nothing synchronises-with these events:
-// results are read after a stream synchronisation.  Tuning EVENT_FENCE=1: default events (A/B).
-static hipError_t create_timing_event(hipEvent_t* ev, bool fence) {
-    return fence ? hipEventCreate(ev) : hipEventCreateWithFlags(ev, hipEventDisableSystemFence);
-}
+// results are read after a stream synchronisation.
+static hipError_t create_timing_event(hipEvent_t* ev) { return hipEventCreateWithFlags(ev, hipEventDisableSystemFence); }
 
 int begin_call(mlvdb_index* h, hipStream_t s) {
     if (h->scan_events_used > 8192) {  // nobody is reading them: start over rather than grow forever
@@ -308,7 +306,7 @@ int begin_call(mlvdb_index* h, hipStream_t s) {
     }
     if (h->profiling && !h->stats_pending) {
         for (auto& ev : h->total_events)
-            if (!ev) HIP_TRY(h, create_timing_event(&ev, h->tn.event_fence != 0));
+            if (!ev) HIP_TRY(h, create_timing_event(&ev));
         HIP_TRY(h, hipEventRecord(h->total_events[0], s));
     }
     return MLVDB_OK;
@@ -327,8 +325,8 @@ int scan_event(mlvdb_index* h, hipStream_t s, bool start) {
     if (start) {
         if (h->scan_events_used == h->scan_events.size()) {
             hipEvent_t a = nullptr, b = nullptr;
-            HIP_TRY(h, create_timing_event(&a, h->tn.event_fence != 0));
-            HIP_TRY(h, create_timing_event(&b, h->tn.event_fence != 0));
+            HIP_TRY(h, create_timing_event(&a));
+            HIP_TRY(h, create_timing_event(&b));
             h->scan_events.emplace_back(a, b);
         }
         HIP_TRY(h, hipEventRecord(h->scan_events[h->scan_events_used].first, s));
@@ -336,6 +334,19 @@ int scan_event(mlvdb_index* h, hipStream_t s, bool start) {
         HIP_TRY(h, hipEventRecord(h->scan_events[h->scan_events_used].second, s));
         ++h->scan_events_used;
     }
+    return MLVDB_OK;
+}
+
+// One scan launch of a pass over `rows` rows: timed when profiling, counted in the statistics.
+template <class Launch>
+int scan_step(mlvdb_index* h, hipStream_t s, int64_t rows, Launch&& launch) {
+    int rc = scan_event(h, s, true);
+    if (rc) return rc;
+    HIP_TRY(h, launch());
+    rc = scan_event(h, s, false);
+    if (rc) return rc;
+    h->stats.scan_launches += 1;
+    h->stats.rows_scanned += rows;
     return MLVDB_OK;
 }
 
@@ -347,7 +358,7 @@ int run_exact(mlvdb_index* h, hipStream_t s, const float* Qpad, const double* qa
               const int32_t* nq_sel_dev = nullptr, const double* cursor_d = nullptr,
               const int32_t* cursor_l = nullptr) {
     if (nq_sel <= 0) return MLVDB_OK;
-    ExactPlan plan = plan_exact(row_end - row_begin, h->ld, nq_sel, k, h->tn);
+    ExactPlan plan = plan_exact(row_end - row_begin, h->ld, nq_sel, k);
     if (nq_sel_dev) {
         // device-decided fallback: usually zero or a few queries are selected, so spread each query
         // tile over many blocks; blocks of unselected tiles exit at once
@@ -371,17 +382,11 @@ int run_exact(mlvdb_index* h, hipStream_t s, const float* Qpad, const double* qa
     a.cursor_d = cursor_d;
     a.cursor_l = cursor_l;
     a.partial = h->partial.as<TopEntry>();
-    a.tn = &h->tn;
     if (is_main_scan) {
-        int rc = scan_event(h, s, true);
+        int rc = scan_step(h, s, (row_end - row_begin) * plan.nqtiles, [&] { return launch_exact_scan(a, plan, s); });
         if (rc) return rc;
-    }
-    HIP_TRY(h, launch_exact_scan(a, plan, s));
-    if (is_main_scan) {
-        int rc = scan_event(h, s, false);
-        if (rc) return rc;
-        h->stats.scan_launches += 1;
-        h->stats.rows_scanned += (row_end - row_begin) * plan.nqtiles;
+    } else {
+        HIP_TRY(h, launch_exact_scan(a, plan, s));
     }
     HIP_TRY(h, launch_exact_merge(a.partial, nq_sel, nq_sel_dev, qsel, plan.nblk, k, out_labels, out_dist, out_counts,
                                   out_d64, s));
@@ -400,12 +405,15 @@ __global__ void fill_empty_kernel(int64_t* labels, float* dist, int32_t* counts,
 
 __global__ void copy_words_kernel(const uint32_t* src, uint32_t* dst) { dst[threadIdx.x] = src[threadIdx.x]; }
 
-int setup_filter_ws(mlvdb_index* h, FilterArgs& fa, const float* Qpad, const double* qaux, const float* qerr, int32_t nq) {
+// The workspace of one pass over queries q0 .. q0 + nq of the call (their prepared form lives in h->qpad / qaux / qerr at q0).
+// range_lists: the pass keeps its own, larger candidate lists -- true hits + the band of the bound, per query anything from
+// none to tens of thousands -- and the exact hit arrays of the range kernels (range and big-k passes).
+int setup_filter_ws(mlvdb_index* h, FilterArgs& fa, int32_t q0, int32_t nq, bool range_lists) {
     HIP_TRY(h, h->qimg.ensure(filter_qimg_bytes((h->ld + 63) / 64 * 64)));
     {
         const void* before = h->fmisc.p;
         HIP_TRY(h, h->fmisc.ensure(9 * kFilterQueries * sizeof(uint32_t)));
-        if (h->fmisc.p != before) h->sqmin_fresh = true;  // the two scalars the fused prep's atomics start from: see run_filter_pass
+        if (h->fmisc.p != before) h->sqmin_fresh = true;  // the two scalars the fused prep's atomics start from: see begin_pass
     }
     HIP_TRY(h, h->cand.ensure((size_t)kFilterQueries * kCandCap * sizeof(CandEntry)));
     HIP_TRY(h, h->rescr.ensure((size_t)kFilterQueries * kCandCap * sizeof(RangeHit)));  // exact scores of the rescored candidates
@@ -423,9 +431,9 @@ int setup_filter_ws(mlvdb_index* h, FilterArgs& fa, const float* Qpad, const dou
     fa.ld = h->ld;
     fa.ld8 = h->ld8;
     fa.space = h->space;
-    fa.Qpad = Qpad;
-    fa.qaux = qaux;
-    fa.qerr = qerr;
+    fa.Qpad = h->qpad.as<float>() + (size_t)q0 * h->ld;
+    fa.qaux = h->qaux.as<double>() + q0;
+    fa.qerr = h->qerr.as<float>() + q0;
     fa.row_err = h->rowerr.as<float>();
     fa.nq = nq;
     fa.qimg = h->qimg.p;
@@ -444,6 +452,15 @@ int setup_filter_ws(mlvdb_index* h, FilterArgs& fa, const float* Qpad, const dou
     fa.cand_cap = kCandCap;
     fa.wgbuf = h->wgbuf.as<WgEntry>();
     fa.wgcnt = h->wgcnt.as<uint32_t>();
+    if (range_lists) {
+        HIP_TRY(h, h->cand_range.ensure((size_t)kFilterQueries * kRangeCandCap * sizeof(CandEntry)));
+        HIP_TRY(h, h->rhits.ensure((size_t)kFilterQueries * kCandCap * sizeof(RangeHit)));
+        HIP_TRY(h, h->rhit_cnt.ensure(kFilterQueries * sizeof(uint32_t)));
+        fa.cand = h->cand_range.as<CandEntry>();
+        fa.cand_cap = kRangeCandCap;
+        fa.rhits = h->rhits.as<RangeHit>();
+        fa.rhit_cnt = h->rhit_cnt.as<uint32_t>();
+    }
     return MLVDB_OK;
 }
 
@@ -562,181 +579,36 @@ int attach_i8(mlvdb_index* h, hipStream_t s, FilterArgs& fa) {
     return MLVDB_OK;
 }
 
-// One pass of <= 256 queries through the filter path; outputs at query index q0.. of the batch.
-int finish_filter_pass(mlvdb_index* h, hipStream_t s, FilterArgs& fa, int32_t q0, int32_t nq, int32_t k, int64_t* out_labels,
-                       float* out_dist, int32_t* out_counts, double* out_d64, bool defer_fallback, bool ranked = false);
-
-// Everything a filter pass needs of its queries, in one fused launch (+ the one-block fin for int8 passes of several queries).
-int prep_pass(mlvdb_index* h, hipStream_t s, const FilterArgs& fa, const float* queries_raw, float* Qpad, double* qaux, float* qerr) {
+// The prologue of a filter pass over queries q0 .. q0 + nq of the call: workspace, the int8 shadow when it serves the pass,
+// then everything the pass needs of its queries in one fused launch (+ the one-block fin for int8 passes of several queries).
+// `queries_raw`: the call's queries [.][dim] as the caller gave them (device); their padded copy, norms and image errors go
+// to h->qpad / qaux / qerr at q0.
+int begin_pass(mlvdb_index* h, hipStream_t s, FilterArgs& fa, const float* queries_raw, int32_t q0, int32_t nq, bool range_lists) {
+    int rc = setup_filter_ws(h, fa, q0, nq, range_lists);
+    if (rc) return rc;
+    rc = attach_i8(h, s, fa);
+    if (rc) return rc;
     if (h->sqmin_fresh) {  // what the fused prep's atomicMin / atomicMax start from; afterwards every fin kernel restores it
         HIP_TRY(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(fa.sqmin), 0x7f7f7f7f, 1, s));
         HIP_TRY(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(fa.sqmin + 1), 0, 1, s));
         h->sqmin_fresh = false;
     }
-    HIP_TRY(h, launch_filter_prep_fused(fa, queries_raw, h->dim, Qpad, qaux, qerr, s));
+    HIP_TRY(h, launch_filter_prep_fused(fa, queries_raw + (size_t)q0 * h->dim, h->dim, h->qpad.as<float>() + (size_t)q0 * h->ld,
+                                        h->qaux.as<double>() + q0, h->qerr.as<float>() + q0, s));
     if (fa.X8 && fa.rp8_cap > 0) {
-        // l2: this pass's integer offsets (they depend on its largest query scale and on which rows are live): 29 us for 10M rows.
-        // (Tried: on a side stream beside the seeding pass and the first refine, joined by an event before the first assembly scan
-        // -- no gain, 1.971 vs 1.954 ms per wave in same-process A/Bs: profiles/r04/scan_ab_l2*_10m.txt; it stays in the pass's stream.)
+        // l2: this pass's integer offsets (they depend on its largest query scale and on which rows are live): 29 us for 10M rows
+        // (it stays in the pass's stream: DESIGN "tried and dropped")
         const int64_t rows = std::min<int64_t>(h->capacity, (h->total + kFilterTile - 1) / kFilterTile * kFilterTile);
         HIP_TRY(h, launch_filter_l2_offsets(fa, rows, s));
     }
-    return MLVDB_OK;
-}
-
-// `queries_raw`: the pass's queries [nq][dim] as the caller gave them (device); this pass prepares them itself (padded copy,
-// norms, images: one fused launch) into Qpad / qaux / qerr at q0.
-int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, float* Qpad, double* qaux, int32_t q0, int32_t nq,
-                    int32_t k, int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64,
-                    bool defer_fallback = false) {
-    FilterArgs fa{};
-    int rc = setup_filter_ws(h, fa, Qpad + (size_t)q0 * h->ld, qaux + q0, h->qerr.as<float>() + q0, nq);
-    if (rc) return rc;
-    rc = attach_i8(h, s, fa);
-    if (rc) return rc;
-    rc = prep_pass(h, s, fa, queries_raw + (size_t)q0 * h->dim, Qpad + (size_t)q0 * h->ld, qaux + q0, h->qerr.as<float>() + q0);
-    if (rc) return rc;
     h->stats.bound_dtype = fa.X8 ? 2 : 1;
-    // (Round 3 had tried a single scan round for <= 8 queries behind the generic exact scan of a 12k-row prefix: slower, 0.273 vs
-    // 0.248 ms at batch 1 -- profiles/r03/small_batch_single_round_tried_1m.txt.  Round 4's version for single queries follows.)
-    // ---- one round for single queries on small corpora (round 4; SMALL_BATCH=0: the rounds below): the exact k-th best of an
-    // 11,520-row prefix (prefix_exact_kernel all over the chip + the one-block selection) puts the threshold at quantile
-    // k / 11,520; ONE scan launch over every row then appends ~total (k / 11,520) x band entries per query -- 1M x 768, k = 10:
-    // 870 x band (~4 on N(0,1) rows) of the list's 8,192 -- and the fused finish prunes, rescores and ranks: five launches instead
-    // of seven (no 65k-row first round, no refine after it): 0.197-0.199 vs 0.206-0.212 ms at batch 1
-    // (profiles/r04/small_batch_one_round_vs_rounds_1m.txt).  Taken only while the estimate with band = 6 stays inside the list;
-    // a list that overflows all the same sends its query to the exact scan, as everywhere.
-    {
-        const int small_nq1 = std::max(0, std::min(1, h->tn.small_nq));  // (two queries: 0.214-0.220 vs 0.211-0.219 ms -- no gain)
-        const int64_t m = 3 * kSeedRows;
-        const bool one_round = h->tn.small_batch != 0 && fa.X8 && nq <= small_nq1 && k <= 64 && !h->mask_active &&
-                               filter_refine_can_fuse(fa) && h->tn.small_finish != 0 && h->tn.small_seed != 0 && h->total > 4 * m &&
-                               (double)h->total * k * 6.0 <= 6000.0 * (double)m;
-        if (one_round) {
-            HIP_TRY(h, h->seed_d64.ensure(((size_t)kFilterQueries * 64 + (size_t)8 * kSeedRows) * sizeof(double)));
-            double* d64 = h->seed_d64.as<double>();
-            HIP_TRY(h, launch_prefix_exact(h->X, fa.rn, fa.Qpad, fa.qaux, nq, (int32_t)m, h->ld, h->space, d64, h->tn, s));
-            HIP_TRY(h, launch_filter_prefix_thr(fa, d64, (int32_t)m, k, s));
-            rc = scan_event(h, s, true);
-            if (rc) return rc;
-            ScanInfo info;
-            HIP_TRY(h, launch_filter_scan(fa, 0, h->total, s, &info));
-            rc = scan_event(h, s, false);
-            if (rc) return rc;
-            h->stats.scan_launches += 1;
-            h->stats.rows_scanned += h->total;
-            HIP_TRY(h, h->qsel.ensure(kFilterQueries * sizeof(int32_t)));
-            unsigned long long* stats = h->counters.as<unsigned long long>();
-            HIP_TRY(h, launch_filter_finish_small(fa, k, q0, out_labels, out_dist, out_counts, out_d64, stats,
-                                                  defer_fallback ? nullptr : h->qsel.as<int32_t>(),
-                                                  reinterpret_cast<int32_t*>(stats + 2), s));
-            return finish_filter_pass(h, s, fa, q0, nq, k, out_labels, out_dist, out_counts, out_d64, defer_fallback, true);
-        }
-    }
-    // seed: a dense pass of the filter kernel over the first rows puts every bound into the lists,
-    // the update kernel turns them into thresholds; the remaining rows follow in rounds of growing
-    // size so that thresholds tighten early
-    // rows of the dense seeding pass: a multiple of kFilterTile (the first scan round starts there), at most kSeedRows
-    // (MLVDB_SEED_ROWS, in units of kFilterTile = 768 rows: tuning, read per call)
-    const int64_t seed_rows = std::min<int64_t>(kSeedRows, std::max<int64_t>(1, h->tn.seed_rows) * kFilterTile);
-    const int64_t n_seed = std::min<int64_t>(h->total, seed_rows);
-    int64_t first_row = seed_rows;
-    {
-        // Tried in round 2 (MLVDB_SEED_EXACT=1): thresholds seeded from the EXACT k-th best score among the first
-        // kSeedRows rows (exact fp64 scan of that prefix + merge + one tiny kernel) instead of the dense bf16 pass that
-        // puts all 3840 bounds of every query into the lists + the exact-threshold refine over them; the prefix rows
-        // then belong to the first scan round.  Slower: 2.16 vs 2.04 ms per 256-query wave, 0.303 vs 0.288 ms at batch 1
-        // (3840 x 768 x 256 fp64 multiply-adds are not free); the dense pass stays the default.
-        // (l2 index with a few badly quantising rows: the dense int8 pass would bound every seed row with the index-wide error,
-        // and those inflated bounds then crowd the refines' picks -- the threshold stalls at the seed's quantile)
-        const bool seed_exact = h->tn.seed_exact == 1 || (fa.X8 && h->space == kSpaceL2 && h->i8_err > 0.03f);
-        // Batches of 1-2 queries (round 3): the exact k-th best of the prefix by a kernel made for it (one 16-row group per
-        // wave all over the chip + a one-block selection of the k-th: 8 + 10 us) instead of the dense int8 pass + exact-threshold refine (7 + 15.5 us
-        // of latency chains at batch 1); the prefix rows then belong to the first scan round.  MLVDB_SMALL_SEED=0: the dense pass.
-        // (4-8 queries: no gain from either step; profiles/r03/small_batch_fused_finish_and_prefix_seed_1m.txt)
-        const int small_nq = std::max(0, std::min(8, h->tn.small_nq));
-        if (fa.X8 && nq <= small_nq && k <= 64 && !h->mask_active && !seed_exact && h->tn.small_seed != 0) {
-            HIP_TRY(h, h->seed_d64.ensure(((size_t)kFilterQueries * 64 + (size_t)8 * kSeedRows) * sizeof(double)));
-            double* d64 = h->seed_d64.as<double>();
-            HIP_TRY(h, launch_prefix_exact(h->X, fa.rn, fa.Qpad, fa.qaux, nq, (int32_t)n_seed, h->ld, h->space, d64, h->tn, s));
-            HIP_TRY(h, launch_filter_prefix_thr(fa, d64, (int32_t)n_seed, k, s));
-            first_row = 0;
-        } else if (seed_exact) {
-            HIP_TRY(h, h->seed_lab.ensure((size_t)kFilterQueries * k * sizeof(int64_t)));
-            HIP_TRY(h, h->seed_dist.ensure((size_t)kFilterQueries * k * sizeof(float)));
-            HIP_TRY(h, h->seed_cnt.ensure(kFilterQueries * sizeof(int32_t)));
-            HIP_TRY(h, h->seed_d64.ensure((size_t)kFilterQueries * k * sizeof(double)));
-            rc = run_exact(h, s, fa.Qpad, fa.qaux, nq, nullptr, 0, n_seed, k, h->seed_lab.as<int64_t>(),
-                           h->seed_dist.as<float>(), h->seed_cnt.as<int32_t>(), h->seed_d64.as<double>(), false);
-            if (rc) return rc;
-            HIP_TRY(h, launch_filter_seed_thr(fa, h->seed_d64.as<double>(), k, s));
-            first_row = 0;
-        } else {
-            HIP_TRY(h, launch_filter_seed_scan(fa, n_seed, k, s));  // includes the first threshold update
-        }
-    }
-    // scan rounds: [seed, r1) [r1, r2) [r2, total), each followed by an exact-threshold refine; in units of kFilterTile rows
-    // (MLVDB_ROUND1 / MLVDB_ROUND2: tuning, read per call)
-    // r1 = 85: 3840 + 240 tiles of 256 rows -- one tile for (nearly) every CU costs what 192 tiles did (64: +1.5 % per 10M-row
-    // wave; 170: the same as 85; r2 = 1024 .. 2389: within noise, 4096: +2.5 %; profiles/r02/scan_ab_round_sizes_10m.txt)
-    const int64_t r1 = std::max<int64_t>(6, h->tn.round1), r2 = std::max<int64_t>(r1, h->tn.round2);
-    const int64_t bounds[] = {first_row, (int64_t)kFilterTile * r1, (int64_t)kFilterTile * r2, h->total};
-    // Batches of 1-2 queries: the refine after the LAST round also rescores and ranks (one launch instead of three:
-    // launch_filter_finish_small); MLVDB_SMALL_FINISH=0: the three kernels
-    // (one block per query: at 4-8 queries the rescoring kernel's spread over the whole chip wins again -- 0.261 vs 0.247 ms at 4)
-    const int small_nq = std::max(0, std::min(8, h->tn.small_nq));
-    const bool small_finish = fa.X8 && nq <= small_nq && k <= 64 && filter_refine_can_fuse(fa) && h->tn.small_finish != 0;
-    bool ranked = false;
-    for (int r = 0; r < 3; ++r) {
-        const int64_t b = std::min(bounds[r], h->total), e = std::min(bounds[r + 1], h->total);
-        if (e <= b) continue;
-        rc = scan_event(h, s, true);
-        if (rc) return rc;
-        ScanInfo info;
-        HIP_TRY(h, launch_filter_scan(fa, b, e, s, &info));
-        rc = scan_event(h, s, false);
-        if (rc) return rc;
-        if (h->tn.debug_entries) {  // tuning aid: entries appended by this scan launch (synchronises the stream)
-            std::vector<uint32_t> wc((size_t)kScanMaxGrid * 8, 0u);
-            HIP_TRY(h, hipMemcpyAsync(wc.data(), fa.wgcnt, wc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-            uint64_t sum = 0, mx = 0;
-            const int waves = (int)std::min<int64_t>(256, (e - b + 255) / 256) * 8;  // 8-wave workgroups of 256-row tiles
-            for (int i = 0; i < waves; ++i) {
-                sum += wc[(size_t)i];
-                mx = std::max<uint64_t>(mx, wc[(size_t)i]);
-            }
-            fprintf(stderr, "[mlvdb] scan rows [%lld, %lld): %llu entries appended (%.1f per query), max per wave %llu\n",
-                    (long long)b, (long long)e, (unsigned long long)sum, (double)sum / fa.nq, (unsigned long long)mx);
-        }
-        h->stats.scan_launches += 1;
-        h->stats.rows_scanned += e - b;
-        // int8 bounds are loose: thresholds from exact scores of the k best bounds; the same kernel prunes the lists
-        // (the update kernel's bound-derived threshold could only be lower) unless the query does not fit beside them
-        const bool fuse = fa.X8 && filter_refine_can_fuse(fa);
-        // (Tried in round 3 for batches of <= 8 queries: no refine after the LAST round -- the rescoring takes the unpruned
-        // lists.  Slower: 0.257 vs 0.226 ms at batch 1 on 1M x 768, the ranking kernel pays more for the ~800-entry list
-        // than the refine's launch costs; profiles/r03/small_batch_last_refine_1m.txt.)
-        if (small_finish && e == h->total) {  // the last round of a small batch
-            HIP_TRY(h, h->qsel.ensure(kFilterQueries * sizeof(int32_t)));
-            unsigned long long* stats = h->counters.as<unsigned long long>();
-            HIP_TRY(h, launch_filter_finish_small(fa, k, q0, out_labels, out_dist, out_counts, out_d64, stats,
-                                                  defer_fallback ? nullptr : h->qsel.as<int32_t>(),
-                                                  reinterpret_cast<int32_t*>(stats + 2), s));
-            ranked = true;
-            break;
-        }
-        if (fa.X8) HIP_TRY(h, launch_filter_refine_thr(fa, k, -1, fuse, s));
-        if (!fuse) HIP_TRY(h, launch_filter_update(fa, k, s));
-    }
-    return finish_filter_pass(h, s, fa, q0, nq, k, out_labels, out_dist, out_counts, out_d64, defer_fallback, ranked);
+    return MLVDB_OK;
 }
 
 // The end of a kNN pass: exact fp64 rescoring of the candidate lists (unless the last refine did it: ranked), then the exact
 // fallback for overflowed queries.
 int finish_filter_pass(mlvdb_index* h, hipStream_t s, FilterArgs& fa, int32_t q0, int32_t nq, int32_t k, int64_t* out_labels,
                        float* out_dist, int32_t* out_counts, double* out_d64, bool defer_fallback, bool ranked) {
-    int rc = MLVDB_OK;
     // counters: [0] rescored pairs, [1] fallback queries (accumulated over the passes of a call), [2] flag count
     unsigned long long* stats = h->counters.as<unsigned long long>();
     // (its ranking kernel also compacts the overflowed queries for the device-decided fallback below: qsel, nflag)
@@ -761,11 +633,116 @@ int finish_filter_pass(mlvdb_index* h, hipStream_t s, FilterArgs& fa, int32_t q0
         h->deferred = true;
         return MLVDB_OK;
     }
-    rc = run_exact(h, s, fa.Qpad, fa.qaux, nq, h->qsel.as<int32_t>(), 0, h->total, k, out_labels + (size_t)q0 * k,
-                   out_dist + (size_t)q0 * k, out_counts + q0, out_d64 ? out_d64 + (size_t)q0 * k : nullptr, false,
-                   nflag);
-    if (rc) return rc;
+    return run_exact(h, s, fa.Qpad, fa.qaux, nq, h->qsel.as<int32_t>(), 0, h->total, k, out_labels + (size_t)q0 * k,
+                     out_dist + (size_t)q0 * k, out_counts + q0, out_d64 ? out_d64 + (size_t)q0 * k : nullptr, false, nflag);
+}
+
+// tuning aid (DEBUG_ENTRIES): entries appended by the scan launch over rows [b, e) (synchronises the stream)
+int print_scan_entries(mlvdb_index* h, hipStream_t s, const FilterArgs& fa, int64_t b, int64_t e) {
+    std::vector<uint32_t> wc((size_t)kScanMaxGrid * 8, 0u);
+    HIP_TRY(h, hipMemcpyAsync(wc.data(), fa.wgcnt, wc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    uint64_t sum = 0, mx = 0;
+    const int waves = (int)std::min<int64_t>(256, (e - b + 255) / 256) * 8;  // 8-wave workgroups of 256-row tiles
+    for (int i = 0; i < waves; ++i) {
+        sum += wc[(size_t)i];
+        mx = std::max<uint64_t>(mx, wc[(size_t)i]);
+    }
+    fprintf(stderr, "[mlvdb] scan rows [%lld, %lld): %llu entries appended (%.1f per query), max per wave %llu\n",
+            (long long)b, (long long)e, (unsigned long long)sum, (double)sum / fa.nq, (unsigned long long)mx);
     return MLVDB_OK;
+}
+
+// One pass of <= 256 queries through the filter path; outputs at query index q0.. of the batch.  `queries_raw`: see begin_pass.
+int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, int32_t q0, int32_t nq, int32_t k,
+                    int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64, bool defer_fallback = false) {
+    FilterArgs fa{};
+    int rc = begin_pass(h, s, fa, queries_raw, q0, nq, false);
+    if (rc) return rc;
+    // Small batches (k <= 64, int8 shadow, no row mask), up to SMALL_NQ queries (at most 8; default 2):
+    //  - seed (SMALL_SEED): the exact k-th best of the prefix by a kernel made for it (one 16-row group per wave all over the
+    //    chip + a one-block selection of the k-th: 8 + 10 us) instead of the dense int8 pass + exact-threshold refine (7 + 15.5 us
+    //    of latency chains at batch 1); the prefix rows then belong to the first scan round.
+    //  - finish (SMALL_FINISH): the refine after the LAST round also rescores and ranks (one launch instead of three:
+    //    launch_filter_finish_small).  One block per query: at 4-8 queries the rescoring kernel's spread over the whole chip
+    //    wins again -- 0.261 vs 0.247 ms at 4; neither step gains there (profiles/r03/small_batch_fused_finish_and_prefix_seed_1m.txt).
+    const int small_nq = std::max(0, std::min(8, h->tn.small_nq));
+    const bool small = fa.X8 && nq <= small_nq && k <= 64;
+    const bool small_finish = small && filter_refine_can_fuse(fa) && h->tn.small_finish != 0;
+    // One query on a small corpus (SMALL_BATCH; two queries: 0.214-0.220 vs 0.211-0.219 ms -- no gain) goes ONE round: the exact
+    // k-th best of an 11,520-row prefix puts the threshold at quantile k / 11,520; one scan launch over every row then appends
+    // ~total (k / 11,520) x band entries per query -- 1M x 768, k = 10: 870 x band (~4 on N(0,1) rows) of the list's 8,192 --
+    // and the fused finish prunes, rescores and ranks: five launches instead of seven (no 65k-row first round, no refine
+    // after it): 0.197-0.199 vs 0.206-0.212 ms at batch 1 (profiles/r04/small_batch_one_round_vs_rounds_1m.txt).  Taken only
+    // while the estimate with band = 6 stays inside the list; a list that overflows all the same sends its query to the exact
+    // scan, as everywhere.
+    const int64_t m1 = 3 * kSeedRows;
+    const bool one_round = h->tn.small_batch != 0 && small_finish && nq <= std::min(1, small_nq) && !h->mask_active &&
+                           h->tn.small_seed != 0 && h->total > 4 * m1 && (double)h->total * k * 6.0 <= 6000.0 * (double)m1;
+    // seed: a dense pass of the filter kernel over the first rows puts every bound into the lists,
+    // the update kernel turns them into thresholds; the remaining rows follow in rounds of growing
+    // size so that thresholds tighten early
+    // rows of the dense seeding pass: a multiple of kFilterTile (the first scan round starts there), at most kSeedRows
+    // (MLVDB_SEED_ROWS, in units of kFilterTile = 768 rows: tuning, read per call)
+    const int64_t seed_rows = one_round ? m1 : std::min<int64_t>(kSeedRows, std::max<int64_t>(1, h->tn.seed_rows) * kFilterTile);
+    const int64_t n_seed = std::min<int64_t>(h->total, seed_rows);
+    int64_t first_row = seed_rows;
+    // l2 index with a few badly quantising rows: the dense int8 pass would bound every seed row with the index-wide error,
+    // and those inflated bounds then crowd the refines' picks -- the threshold stalls at the seed's quantile.  Such a pass takes
+    // its thresholds from the EXACT k-th best score among the seed rows (exact fp64 scan of that prefix + merge + one tiny kernel)
+    const bool seed_exact = fa.X8 && h->space == kSpaceL2 && h->i8_err > 0.03f;
+    if (one_round || (small && !h->mask_active && !seed_exact && h->tn.small_seed != 0)) {
+        HIP_TRY(h, h->seed_d64.ensure(((size_t)kFilterQueries * 64 + (size_t)8 * kSeedRows) * sizeof(double)));
+        double* d64 = h->seed_d64.as<double>();
+        HIP_TRY(h, launch_prefix_exact(h->X, fa.rn, fa.Qpad, fa.qaux, nq, (int32_t)n_seed, h->ld, h->space, d64, s));
+        HIP_TRY(h, launch_filter_prefix_thr(fa, d64, (int32_t)n_seed, k, s));
+        first_row = 0;
+    } else if (seed_exact) {
+        HIP_TRY(h, h->seed_lab.ensure((size_t)kFilterQueries * k * sizeof(int64_t)));
+        HIP_TRY(h, h->seed_dist.ensure((size_t)kFilterQueries * k * sizeof(float)));
+        HIP_TRY(h, h->seed_cnt.ensure(kFilterQueries * sizeof(int32_t)));
+        HIP_TRY(h, h->seed_d64.ensure((size_t)kFilterQueries * k * sizeof(double)));
+        rc = run_exact(h, s, fa.Qpad, fa.qaux, nq, nullptr, 0, n_seed, k, h->seed_lab.as<int64_t>(),
+                       h->seed_dist.as<float>(), h->seed_cnt.as<int32_t>(), h->seed_d64.as<double>(), false);
+        if (rc) return rc;
+        HIP_TRY(h, launch_filter_seed_thr(fa, h->seed_d64.as<double>(), k, s));
+        first_row = 0;
+    } else {
+        HIP_TRY(h, launch_filter_seed_scan(fa, n_seed, k, s));  // includes the first threshold update
+    }
+    // scan rounds: [seed, r1) [r1, r2) [r2, total), each followed by an exact-threshold refine; in units of kFilterTile rows
+    // (MLVDB_ROUND1 / MLVDB_ROUND2: tuning, read per call); one_round: [0, total)
+    // r1 = 85: 3840 + 240 tiles of 256 rows -- one tile for (nearly) every CU costs what 192 tiles did (64: +1.5 % per 10M-row
+    // wave; 170: the same as 85; r2 = 1024 .. 2389: within noise, 4096: +2.5 %; profiles/r02/scan_ab_round_sizes_10m.txt)
+    const int64_t r1 = std::max<int64_t>(6, h->tn.round1), r2 = std::max<int64_t>(r1, h->tn.round2);
+    const int64_t bounds[] = {first_row, one_round ? h->total : (int64_t)kFilterTile * r1,
+                              one_round ? h->total : (int64_t)kFilterTile * r2, h->total};
+    bool ranked = false;
+    for (int r = 0; r < 3; ++r) {
+        const int64_t b = std::min(bounds[r], h->total), e = std::min(bounds[r + 1], h->total);
+        if (e <= b) continue;
+        rc = scan_step(h, s, e - b, [&] { return launch_filter_scan(fa, b, e, s); });
+        if (rc) return rc;
+        if (h->tn.debug_entries) {
+            rc = print_scan_entries(h, s, fa, b, e);
+            if (rc) return rc;
+        }
+        if (small_finish && e == h->total) {  // the last round of a small batch
+            HIP_TRY(h, h->qsel.ensure(kFilterQueries * sizeof(int32_t)));
+            unsigned long long* stats = h->counters.as<unsigned long long>();
+            HIP_TRY(h, launch_filter_finish_small(fa, k, q0, out_labels, out_dist, out_counts, out_d64, stats,
+                                                  defer_fallback ? nullptr : h->qsel.as<int32_t>(),
+                                                  reinterpret_cast<int32_t*>(stats + 2), s));
+            ranked = true;
+            break;
+        }
+        // int8 bounds are loose: thresholds from exact scores of the k best bounds; the same kernel prunes the lists
+        // (the update kernel's bound-derived threshold could only be lower) unless the query does not fit beside them
+        const bool fuse = fa.X8 && filter_refine_can_fuse(fa);
+        if (fa.X8) HIP_TRY(h, launch_filter_refine_thr(fa, k, -1, fuse, s));
+        if (!fuse) HIP_TRY(h, launch_filter_update(fa, k, s));
+    }
+    return finish_filter_pass(h, s, fa, q0, nq, k, out_labels, out_dist, out_counts, out_d64, defer_fallback, ranked);
 }
 
 // ---- the fp16 row-major shadow of the mid bounds (kernels_refine.hip): kept current lazily, like the int8 shadow.
@@ -818,30 +795,18 @@ int run_paged_exact(mlvdb_index* h, hipStream_t s, const float* Qpad, const doub
 // each) run over; with n rows seen the k-th best is at quantile k / n, so the next m rows yield ~nq m (k / n) band entries:
 // m = n BUDGET / (nq k).  A query whose list or wave buffer overflows all the same is served by the paged exact scan.
 // *handled = false: the index has no mid shadow (the caller takes the paged exact scan).
-int run_bigk_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, float* Qpad, double* qaux, int32_t q0, int32_t nq,
-                  int32_t k, int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64, bool* handled) {
+int run_bigk_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, int32_t q0, int32_t nq, int32_t k,
+                  int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64, bool* handled) {
     *handled = false;
     MidArgs m{};
     int rc = attach_mid(h, s, &m);
     if (rc) return rc;
     if (!m.X16) return MLVDB_OK;
     FilterArgs fa{};
-    rc = setup_filter_ws(h, fa, Qpad + (size_t)q0 * h->ld, qaux + q0, h->qerr.as<float>() + q0, nq);
+    rc = begin_pass(h, s, fa, queries_raw, q0, nq, true);
     if (rc) return rc;
-    HIP_TRY(h, h->cand_range.ensure((size_t)kFilterQueries * kRangeCandCap * sizeof(CandEntry)));
-    HIP_TRY(h, h->rhits.ensure((size_t)kFilterQueries * kCandCap * sizeof(RangeHit)));
-    HIP_TRY(h, h->rhit_cnt.ensure(kFilterQueries * sizeof(uint32_t)));
     HIP_TRY(h, h->picks.ensure((size_t)kFilterQueries * kPicksCap * sizeof(uint32_t)));
     HIP_TRY(h, h->npicks.ensure(kFilterQueries * sizeof(uint32_t)));
-    fa.cand = h->cand_range.as<CandEntry>();
-    fa.cand_cap = kRangeCandCap;
-    fa.rhits = h->rhits.as<RangeHit>();
-    fa.rhit_cnt = h->rhit_cnt.as<uint32_t>();
-    rc = attach_i8(h, s, fa);
-    if (rc) return rc;
-    rc = prep_pass(h, s, fa, queries_raw + (size_t)q0 * h->dim, Qpad + (size_t)q0 * h->ld, qaux + q0, h->qerr.as<float>() + q0);
-    if (rc) return rc;
-    h->stats.bound_dtype = fa.X8 ? 2 : 1;
     uint32_t* picks = h->picks.as<uint32_t>();
     uint32_t* npicks = h->npicks.as<uint32_t>();
     MidArgs mp = m;  // refine the picks / (m) everything still unrefined
@@ -873,14 +838,8 @@ int run_bigk_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, float
         int64_t e = (int64_t)((double)b * growth) / kFilterTile * kFilterTile;
         if (e <= b) e = b + kFilterTile;
         if (e > h->total || (double)e * 1.25 > (double)h->total) e = h->total;  // (no sliver of a last round)
-        rc = scan_event(h, s, true);
+        rc = scan_step(h, s, e - b, [&] { return launch_filter_scan(fa, b, e, s); });
         if (rc) return rc;
-        ScanInfo info;
-        HIP_TRY(h, launch_filter_scan(fa, b, e, s, &info));
-        rc = scan_event(h, s, false);
-        if (rc) return rc;
-        h->stats.scan_launches += 1;
-        h->stats.rows_scanned += e - b;
         rc = refine(-1);
         if (rc) return rc;
         b = e;
@@ -1007,9 +966,9 @@ __global__ void range_resolve_kernel(uint32_t* overflow, const uint32_t* cnt, co
 }
 
 // (l2: the int8 bodies are the l2c ones -- folded test, per-row integer offsets read through the row pairs' descriptor, which needs
-// pairs + offsets, 12 bytes per row, below 4 GB; SCAN_L2C=0 / SCAN_L2E=0 take l2 off the int8 shadow: bf16 / fp32 / exact paths)
+// pairs + offsets, 12 bytes per row, below 4 GB; SCAN_L2C=0 takes l2 off the int8 shadow: bf16 / fp32 / exact paths)
 bool l2_int8_ok(const mlvdb_index* h) {
-    return h->space != kSpaceL2 || (h->tn.scan_l2e && h->tn.scan_l2c && (uint64_t)h->capacity * 12ull < 0xfff00000ull);
+    return h->space != kSpaceL2 || (h->tn.scan_l2c && (uint64_t)h->capacity * 12ull < 0xfff00000ull);
 }
 // One scale per row (l2 / ip: per group of 8 rows): a row with an outlier component quantises badly.  Cosine bounds carry every
 // row's own error (any index-wide maximum up to 0.5 will do).  ip bounds use the index-wide maximum: beyond 0.03 (typical data:
@@ -1478,46 +1437,48 @@ static int search_device_impl(mlvdb_index* h, const float* queries_device, int64
     bool ready = false;
     rc = filter_ready(h, s, nq, &ready);
     if (rc) return rc;
-    const bool filt = k <= MLVDB_MAX_TOPK && use_filter(h, nq, ready);
-    if (!filt && k <= MLVDB_MAX_TOPK)  // (the filter passes prepare their own queries: one fused launch each)
-        HIP_TRY(h, launch_query_prep(queries_device, (int32_t)nq, h->dim, h->ld, h->space, h->qpad.as<float>(),
-                                     h->qaux.as<double>(), h->qerr.as<float>(), s));
-    bool bigk_done = false;
-    if (k > MLVDB_MAX_TOPK && k <= kBigKMax && h->tn.bigk && use_filter(h, nq, ready) && h->total - h->deleted > (int64_t)k) {
-        // top_k 65..1024 stays on the filter path (round 4): passes of 256 queries with 65,536-slot lists, mid bounds, exact
-        // rescoring of the survivors.  (The first pass tells whether the index has a mid shadow at all.)
+    // the route of the call, decided once: top_k <= 64 on the filter path or the exact scan; above, big-k filter passes
+    // (top_k 65..1024: passes of 256 queries with 65,536-slot lists, mid bounds, exact rescoring of the survivors) or
+    // rank-ordered pages of the exact scan
+    enum { kRouteBigK, kRoutePaged, kRouteFilter, kRouteExact } route;
+    const bool filt = use_filter(h, nq, ready);
+    if (k > MLVDB_MAX_TOPK)
+        route = k <= kBigKMax && h->tn.bigk && filt && h->total - h->deleted > (int64_t)k ? kRouteBigK : kRoutePaged;
+    else
+        route = filt ? kRouteFilter : kRouteExact;
+    if (route == kRouteBigK) {
         h->counters_pending = true;
         for (int64_t q0 = 0; q0 < nq; q0 += kFilterQueries) {
             const int32_t n = (int32_t)std::min<int64_t>(kFilterQueries, nq - q0);
             bool handled = false;
-            rc = run_bigk_pass(h, s, queries_device, h->qpad.as<float>(), h->qaux.as<double>(), (int32_t)q0, n, k, out_labels_device,
-                               out_dist_device, out_counts_device, out_dist64_device, &handled);
+            rc = run_bigk_pass(h, s, queries_device, (int32_t)q0, n, k, out_labels_device, out_dist_device, out_counts_device,
+                               out_dist64_device, &handled);
             if (rc) return rc;
-            if (!handled) break;  // (only ever the first pass)
-            bigk_done = true;
+            // the one decision left to a pass: the first one found no mid shadow (L2_SHADOW=0, or HBM was full when it was
+            // wanted) and did nothing, so the paged exact scan serves the whole call
+            if (!handled) {
+                route = kRoutePaged;
+                break;
+            }
         }
-        if (bigk_done) h->stats.strategy_used = MLVDB_STRATEGY_FILTER;
     }
-    if (bigk_done) {
-    } else if (k > MLVDB_MAX_TOPK) {
+    if (route == kRoutePaged || route == kRouteExact)  // (the filter passes prepare their own queries: one fused launch each)
         HIP_TRY(h, launch_query_prep(queries_device, (int32_t)nq, h->dim, h->ld, h->space, h->qpad.as<float>(),
                                      h->qaux.as<double>(), h->qerr.as<float>(), s));
-        h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+    h->stats.strategy_used = route == kRouteBigK || route == kRouteFilter ? MLVDB_STRATEGY_FILTER : MLVDB_STRATEGY_EXACT;
+    if (route == kRoutePaged) {
         rc = run_paged_exact(h, s, h->qpad.as<float>(), h->qaux.as<double>(), nq, nullptr, (int32_t)nq, k, out_labels_device,
                              out_dist_device, out_counts_device, out_dist64_device);
         if (rc) return rc;
-    } else if (filt) {
-        h->stats.strategy_used = MLVDB_STRATEGY_FILTER;
+    } else if (route == kRouteFilter) {
         h->counters_pending = true;
         for (int64_t q0 = 0; q0 < nq; q0 += kFilterQueries) {
             const int32_t n = (int32_t)std::min<int64_t>(kFilterQueries, nq - q0);
-            rc = run_filter_pass(h, s, queries_device, h->qpad.as<float>(), h->qaux.as<double>(), (int32_t)q0, n, k, out_labels_device,
-                                 out_dist_device, out_counts_device, out_dist64_device,
-                                 defer_fallback && nq <= kFilterQueries);
+            rc = run_filter_pass(h, s, queries_device, (int32_t)q0, n, k, out_labels_device, out_dist_device, out_counts_device,
+                                 out_dist64_device, defer_fallback && nq <= kFilterQueries);
             if (rc) return rc;
         }
-    } else {
-        h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+    } else if (route == kRouteExact) {
         rc = run_exact(h, s, h->qpad.as<float>(), h->qaux.as<double>(), (int32_t)nq, nullptr, 0, h->total, k,
                        out_labels_device, out_dist_device, out_counts_device, out_dist64_device, true);
         if (rc) return rc;
@@ -1542,23 +1503,21 @@ int search_host(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int
     HIP_TRY(h, h->io_q.ensure(qbytes));
     const size_t fbytes = kFilterQueries * sizeof(uint32_t), obytes_all = ((obytes + 15) & ~(size_t)15) + fbytes;
     HIP_TRY(h, h->io_out.ensure(obytes_all));
-    // (Tried in round 3: outputs of small batches written by the kernels straight into host-mapped pinned memory -- no D2H
-    // copy, one host wait instead of two.  No gain: 0.239 vs 0.238 ms at batch 1 on 1M x 768; removed.)
     char* dout = h->io_out.as<char>();
     double* d_d64 = out_dist64 ? reinterpret_cast<double*>(dout) : nullptr;
     int64_t* d_lab = reinterpret_cast<int64_t*>(dout + b64);
     float* d_dist = reinterpret_cast<float*>(dout + b64 + blab);
     int32_t* d_cnt = reinterpret_cast<int32_t*>(dout + b64 + blab + bdist);
-    // MLVDB_PINNED_IO=0: round 2's pageable copies (A/B).  The pinned D2H copy is enqueued only AFTER the kernels have
+    // Pinned staging.  The pinned D2H copy is enqueued only AFTER the kernels have
     // finished (one more host wait, ~10 us): enqueued behind them it parks at the head of the copy engine's queue for the
     // whole scan and every copy of the index's other stream -- the hit-enrichment gather of find_similar_stream -- waits
     // with it; measured on 4M rows: protocol stream 1.92 ms per wave parked vs 1.20 unparked (engine alone 1.07;
     // profiles/r03/protocol_stream_pinned_io_modes_4m.txt).  A blocking event wait instead of hipStreamSynchronize: no change.
     // (pinned staging only while it stays small: a paged search with nq = 1024, k = 16384 would pin ~400 MB per handle -- per
     // shard under MultiDeviceEngine -- for the handle's lifetime, and every growth goes through hipHostFree / hipHostMalloc,
-    // which synchronise the device; above 16 MB the pageable copies of round 2 are used and nothing stays pinned)
+    // which synchronise the device; above 16 MB pageable copies are used and nothing stays pinned)
     constexpr size_t kPinnedMax = (size_t)16 << 20;
-    const bool pinned = h->tn.pinned_io != 0 && qbytes <= kPinnedMax && obytes_all <= kPinnedMax;
+    const bool pinned = qbytes <= kPinnedMax && obytes_all <= kPinnedMax;
     h->flags_in_out = pinned;  // the pass copies its overflow flags device-to-device behind the outputs (no parked D2H either)
     h->flags_out = reinterpret_cast<uint32_t*>(dout + ((obytes + 15) & ~(size_t)15));
     if (pinned) {
@@ -1575,7 +1534,7 @@ int search_host(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int
         if (pinned) {
             HIP_TRY(h, hipStreamSynchronize(h->stream));  // the copy must not park behind the kernels (see above)
             HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, dout, obytes_all, hipMemcpyDeviceToHost, h->stream));
-        } else {  // round 2's form: pageable copies straight into the caller's arrays
+        } else {  // pageable copies straight into the caller's arrays
             if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64, d_d64, b64, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, hipMemcpyAsync(out_labels, d_lab, blab, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, hipMemcpyAsync(out_dist, d_dist, bdist, hipMemcpyDeviceToHost, h->stream));
@@ -1674,6 +1633,38 @@ int mlvdb_search_batch_filtered(mlvdb_index* h, const float* queries, int64_t nq
     });
 }
 
+// The valid prefixes of the dense device results (io_lab / io_dist: cap_eff slots per query) packed at `offsets` into one
+// device buffer [labels | distances] and brought to the host in one DMA through pinned memory; *labels / *dist point at them
+// there.  Pinned staging only while it stays small (search_host): above 16 MB a caller whose own arrays have the packed
+// layout (direct_lab / direct_dist; nullptr: none) gets pageable copies straight into those instead.
+static int pack_range_hits(mlvdb_index* h, hipStream_t s, int64_t nq, int64_t cap_eff, const std::vector<int64_t>& offsets,
+                           int64_t* direct_lab, float* direct_dist, const int64_t** labels, const float** dist) {
+    const size_t plab = (size_t)offsets[(size_t)nq] * sizeof(int64_t), pdst = (size_t)offsets[(size_t)nq] * sizeof(float);
+    HIP_TRY(h, h->labels_in.ensure(((size_t)nq + 1) * sizeof(int64_t)));
+    HIP_TRY(h, h->seed_lab.ensure(plab + pdst));
+    const bool pinned = !direct_lab || plab + pdst <= ((size_t)16 << 20);
+    if (pinned) HIP_TRY(h, h->pin_out.ensure(plab + pdst));
+    int64_t* d_pl = h->seed_lab.as<int64_t>();
+    float* d_pd = reinterpret_cast<float*>(h->seed_lab.as<char>() + plab);
+    std::memcpy(h->pin_in.p, offsets.data(), ((size_t)nq + 1) * sizeof(int64_t));
+    HIP_TRY(h, hipMemcpyAsync(h->labels_in.p, h->pin_in.p, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    range_pack_kernel<<<(unsigned)nq, 256, 0, s>>>(h->io_lab.as<int64_t>(), h->io_dist.as<float>(), h->labels_in.as<int64_t>(),
+                                                   cap_eff, d_pl, d_pd);
+    HIP_TRY(h, hipGetLastError());
+    if (pinned) {
+        HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, d_pl, plab + pdst, hipMemcpyDeviceToHost, s));
+        *labels = static_cast<const int64_t*>(h->pin_out.p);
+        *dist = reinterpret_cast<const float*>(static_cast<const char*>(h->pin_out.p) + plab);
+    } else {
+        HIP_TRY(h, hipMemcpyAsync(direct_lab, d_pl, plab, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(direct_dist, d_pd, pdst, hipMemcpyDeviceToHost, s));
+        *labels = direct_lab;
+        *dist = direct_dist;
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MLVDB_OK;
+}
+
 // Both range entries.  out_offsets == nullptr: the dense form (out_labels / out_dist are [nq, capacity]); otherwise the packed
 // form: the hits of query i are entries out_offsets[i] .. out_offsets[i + 1] of out_labels / out_dist (total_capacity entries).
 static int range_batch_impl(mlvdb_index* h, const float* queries, int64_t nq, float radius, int64_t capacity, int64_t* out_labels,
@@ -1720,46 +1711,24 @@ static int range_batch_impl(mlvdb_index* h, const float* queries, int64_t nq, fl
     h->stats.strategy_used = filt ? MLVDB_STRATEGY_FILTER : MLVDB_STRATEGY_EXACT;
     for (int64_t q0 = 0; q0 < nq; q0 += kFilterQueries) {
         const int32_t n = (int32_t)std::min<int64_t>(kFilterQueries, nq - q0);
+        // int8 bounds wherever the filter serves the pass (half the scan time of the bf16 body): their band admits ~8x more
+        // candidates than there are hits, which the mid bounds and the flat rescoring below absorb
         FilterArgs fa{};
-        rc = setup_filter_ws(h, fa, h->qpad.as<float>() + (size_t)q0 * h->ld, h->qaux.as<double>() + q0,
-                             h->qerr.as<float>() + q0, n);
-        if (rc) return rc;
-        // a range pass keeps its own, larger candidate lists: true hits + the band of the bound, per query anything
-        // from none to tens of thousands
-        HIP_TRY(h, h->cand_range.ensure((size_t)kFilterQueries * kRangeCandCap * sizeof(CandEntry)));
-        HIP_TRY(h, h->rhits.ensure((size_t)kFilterQueries * kCandCap * sizeof(RangeHit)));
-        HIP_TRY(h, h->rhit_cnt.ensure(kFilterQueries * sizeof(uint32_t)));
-        fa.cand = h->cand_range.as<CandEntry>();
-        fa.cand_cap = kRangeCandCap;
-        fa.rhits = h->rhits.as<RangeHit>();
-        fa.rhit_cnt = h->rhit_cnt.as<uint32_t>();
-        // int8 bounds (half the scan time of the bf16 body; MLVDB_RANGE_I8=0 keeps the bf16 one): their band admits
-        // ~8x more candidates than there are hits, which the chunked rescoring below absorbs
-        if (filt && h->tn.range_i8 != 0) {
-            rc = attach_i8(h, s, fa);
-            if (rc) return rc;
-        }
         if (filt) {  // (also clears the candidate counters)
-            rc = prep_pass(h, s, fa, h->io_q.as<float>() + (size_t)q0 * h->dim, h->qpad.as<float>() + (size_t)q0 * h->ld,
-                           h->qaux.as<double>() + q0, h->qerr.as<float>() + q0);
+            rc = begin_pass(h, s, fa, h->io_q.as<float>(), (int32_t)q0, n, true);
             if (rc) return rc;
         } else {
+            rc = setup_filter_ws(h, fa, (int32_t)q0, n, true);
+            if (rc) return rc;
             HIP_TRY(h, launch_filter_prep(fa, s));  // per-query state only (no image: the exact range scan reads Qpad)
+            h->stats.bound_dtype = 0;
         }
-        h->stats.bound_dtype = fa.X8 ? 2 : (filt ? 1 : 0);
-        rc = scan_event(h, s, true);
+        rc = scan_step(h, s, h->total, [&]() -> hipError_t {
+            if (!filt) return launch_exact_range_scan(fa, radius, nullptr, 0, s);
+            const hipError_t e = launch_filter_range_thr(fa, radius, s);
+            return e != hipSuccess ? e : launch_filter_scan(fa, 0, h->total, s);
+        });
         if (rc) return rc;
-        if (filt) {
-            HIP_TRY(h, launch_filter_range_thr(fa, radius, s));
-            ScanInfo info;
-            HIP_TRY(h, launch_filter_scan(fa, 0, h->total, s, &info));
-            } else {
-            HIP_TRY(h, launch_exact_range_scan(fa, radius, nullptr, 0, s));
-        }
-        rc = scan_event(h, s, false);
-        if (rc) return rc;
-        h->stats.scan_launches += 1;
-        h->stats.rows_scanned += h->total;
         int32_t n_flagged = 0;
         rc = collect_overflow(h, s, fa, &n_flagged);
         if (rc) return rc;
@@ -1825,71 +1794,33 @@ static int range_batch_impl(mlvdb_index* h, const float* queries, int64_t nq, fl
     std::vector<int64_t> offsets((size_t)nq + 1, 0);
     for (int64_t i = 0; i < nq; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + std::min<int64_t>(std::max<int64_t>(counts[i], 0), cap_eff);
     const int64_t total_hits = offsets[(size_t)nq];
+    bool over = false, hard = false;
+    for (int64_t i = 0; i < nq; ++i) {
+        out_counts[i] = counts[i];
+        over |= counts[i] > capacity;
+        hard |= counts[i] > cap_eff && capacity > cap_eff;
+    }
+    const size_t plab = (size_t)total_hits * sizeof(int64_t), pdst = (size_t)total_hits * sizeof(float);
+    const int64_t* pl = nullptr;
+    const float* pd = nullptr;
+    bool fits = true;
     if (out_offsets) {
-        // packed form: offsets and counts always; the hits when they fit (one packing kernel, one DMA, two copies out of pinned memory)
+        // packed form: offsets and counts always; the hits when they fit (pageable copies straight into the caller's arrays
+        // when they are too many for the pinned staging)
         std::memcpy(out_offsets, offsets.data(), ((size_t)nq + 1) * sizeof(int64_t));
-        bool hard_p = false;
-        for (int64_t i = 0; i < nq; ++i) {
-            out_counts[i] = counts[i];
-            hard_p |= counts[i] > cap_eff && capacity > cap_eff;
-        }
-        const bool fits = total_hits <= total_capacity;
+        fits = total_hits <= total_capacity;
         if (fits && total_hits > 0) {
-            HIP_TRY(h, h->labels_in.ensure(((size_t)nq + 1) * sizeof(int64_t)));
-            const size_t plab = (size_t)total_hits * sizeof(int64_t), pdst = (size_t)total_hits * sizeof(float);
-            HIP_TRY(h, h->seed_lab.ensure(plab + pdst));
-            const bool pinned = plab + pdst <= ((size_t)16 << 20);  // (pinned staging only while it stays small: search_host)
-            if (pinned) HIP_TRY(h, h->pin_out.ensure(plab + pdst));
-            int64_t* d_pl = h->seed_lab.as<int64_t>();
-            float* d_pd = reinterpret_cast<float*>(h->seed_lab.as<char>() + plab);
-            std::memcpy(h->pin_in.p, offsets.data(), ((size_t)nq + 1) * sizeof(int64_t));
-            HIP_TRY(h, hipMemcpyAsync(h->labels_in.p, h->pin_in.p, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            range_pack_kernel<<<(unsigned)nq, 256, 0, s>>>(h->io_lab.as<int64_t>(), h->io_dist.as<float>(), h->labels_in.as<int64_t>(),
-                                                           cap_eff, d_pl, d_pd);
-            HIP_TRY(h, hipGetLastError());
-            if (pinned) {
-                HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, d_pl, plab + pdst, hipMemcpyDeviceToHost, s));
-                HIP_TRY(h, hipStreamSynchronize(s));
-                std::memcpy(out_labels, h->pin_out.p, plab);
-                std::memcpy(out_dist, static_cast<const char*>(h->pin_out.p) + plab, pdst);
-            } else {
-                HIP_TRY(h, hipMemcpyAsync(out_labels, d_pl, plab, hipMemcpyDeviceToHost, s));
-                HIP_TRY(h, hipMemcpyAsync(out_dist, d_pd, pdst, hipMemcpyDeviceToHost, s));
-                HIP_TRY(h, hipStreamSynchronize(s));
+            rc = pack_range_hits(h, s, nq, cap_eff, offsets, out_labels, out_dist, &pl, &pd);
+            if (rc) return rc;
+            if (pl != out_labels) {
+                std::memcpy(out_labels, pl, plab);
+                std::memcpy(out_dist, pd, pdst);
             }
         }
-        rc = end_call(h, s);
-        if (rc) return rc;
-        if (!fits)
-            return fail(h, MLVDB_ERR_OVERFLOW, "range query: more hits in all than total_capacity; out_counts / out_offsets hold "
-                                               "the exact counts and the layout the hits need, out_labels / out_dist nothing");
-        if (hard_p)
-            return fail(h, MLVDB_ERR_UNSUPPORTED,
-                        "range query: a query has more than MLVDB_MAX_TOPK_PAGED hits; out_counts holds the exact counts, the "
-                        "outputs the nearest MLVDB_MAX_TOPK_PAGED");
-        for (int64_t i = 0; i < nq; ++i)
-            if (counts[i] > capacity)
-                return fail(h, MLVDB_ERR_OVERFLOW, "some query has more hits than `capacity`; out_counts holds the exact counts");
-        return MLVDB_OK;
-    }
-    if (total_hits * 4 < nq * cap_eff) {
+    } else if (total_hits * 4 < nq * cap_eff) {
         if (total_hits > 0) {
-            HIP_TRY(h, h->labels_in.ensure(((size_t)nq + 1) * sizeof(int64_t)));
-            // packed outputs: one device buffer [labels | distances], one DMA into pinned memory
-            const size_t plab = (size_t)total_hits * sizeof(int64_t), pdst = (size_t)total_hits * sizeof(float);
-            HIP_TRY(h, h->seed_lab.ensure(plab + pdst));
-            HIP_TRY(h, h->pin_out.ensure(plab + pdst));
-            int64_t* d_pl = h->seed_lab.as<int64_t>();
-            float* d_pd = reinterpret_cast<float*>(h->seed_lab.as<char>() + plab);
-            std::memcpy(h->pin_in.p, offsets.data(), ((size_t)nq + 1) * sizeof(int64_t));
-            HIP_TRY(h, hipMemcpyAsync(h->labels_in.p, h->pin_in.p, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            range_pack_kernel<<<(unsigned)nq, 256, 0, s>>>(h->io_lab.as<int64_t>(), h->io_dist.as<float>(), h->labels_in.as<int64_t>(),
-                                                           cap_eff, d_pl, d_pd);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, d_pl, plab + pdst, hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-            const int64_t* pl = static_cast<const int64_t*>(h->pin_out.p);
-            const float* pd = reinterpret_cast<const float*>(static_cast<const char*>(h->pin_out.p) + plab);
+            rc = pack_range_hits(h, s, nq, cap_eff, offsets, nullptr, nullptr, &pl, &pd);
+            if (rc) return rc;
             for (int64_t i = 0; i < nq; ++i) {
                 const int64_t n = offsets[(size_t)i + 1] - offsets[(size_t)i];
                 std::memcpy(out_labels + (size_t)i * capacity, pl + offsets[(size_t)i], (size_t)n * sizeof(int64_t));
@@ -1903,14 +1834,11 @@ static int range_batch_impl(mlvdb_index* h, const float* queries, int64_t nq, fl
                                     (size_t)cap_eff * sizeof(float), (size_t)nq, hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
     }
-    bool over = false, hard = false;
-    for (int64_t i = 0; i < nq; ++i) {
-        out_counts[i] = counts[i];
-        over |= counts[i] > capacity;
-        hard |= counts[i] > cap_eff && capacity > cap_eff;
-    }
     rc = end_call(h, s);
     if (rc) return rc;
+    if (!fits)
+        return fail(h, MLVDB_ERR_OVERFLOW, "range query: more hits in all than total_capacity; out_counts / out_offsets hold "
+                                           "the exact counts and the layout the hits need, out_labels / out_dist nothing");
     if (hard)
         return fail(h, MLVDB_ERR_UNSUPPORTED,
                     "range query: a query has more than MLVDB_MAX_TOPK_PAGED hits; out_counts holds the exact counts, the "

@@ -46,32 +46,19 @@ inline hipError_t ensure_dynamic_lds(std::atomic<uint64_t>& done, const void* ke
     X(small_finish, "SMALL_FINISH", 1) /* 1-2 queries: fused last refine + rescoring + ranking */                       \
     X(small_nq, "SMALL_NQ", 2)                                                                                          \
     X(seed_rows, "SEED_ROWS", 5)       /* dense seeding pass, units of 768 rows */                                      \
-    X(seed_exact, "SEED_EXACT", 0)                                                                                      \
     X(seed_i8, "SEED_I8", 1)                                                                                            \
     X(round1, "ROUND1", 85)            /* ends of the first / second scan round, units of 768 rows */                   \
     X(round2, "ROUND2", 2048)                                                                                           \
     X(refine_picks, "REFINE_PICKS", 0) /* 0 = 1.5 k, at least 16 */                                                     \
-    X(pinned_io, "PINNED_IO", 1)                                                                                        \
-    X(event_fence, "EVENT_FENCE", 0)                                                                                    \
-    X(range_i8, "RANGE_I8", 1)                                                                                          \
-    X(range_flat, "RANGE_FLAT", 1)                                                                                      \
     X(range_l2, "RANGE_L2", 1)         /* range passes: fp16 second-level bound before the exact gather */             \
     X(bigk, "BIGK", 1)                 /* top_k in (64, 1024] on the filter path (0: paged exact scan) */              \
     X(bigk_budget, "BIGK_BUDGET", 400000) /* entries one scan launch of a big-k pass may append (sizes its rounds) */ \
     X(l2_shadow, "L2_SHADOW", 1)       /* fp16 row-major shadow for second-level bounds (built lazily; 0: never) */    \
     X(debug_entries, "DEBUG_ENTRIES", 0)                                                                                \
     X(scan_narrow, "SCAN_NARROW", 1)                                                                                    \
-    X(narrow_i8_max, "NARROW_I8_MAX", 0) /* largest batch the int8 NARROW kernel scans (round 4: none -- the 4-tile assembly body is faster at every batch size) */                                                                                \
-    X(narrow_wgs, "NARROW_WGS", 0)     /* 0 = as many workgroups per CU as the image leaves LDS for */                  \
-    X(narrow_balance, "NARROW_BALANCE", 1)                                                                              \
-    X(scan_l2c, "SCAN_L2C", 1)         /* l2: one query quantisation step per pass + one error coefficient: cosine's one-constant test */ \
-    X(scan_l2e, "SCAN_L2E", 1)         /* l2: folded admission test with per-row integer offsets (0: serial test, round 3's body) */ \
+    X(scan_l2c, "SCAN_L2C", 1)         /* l2: the int8 bodies (one query quantisation step per pass, per-row integer offsets: cosine's one-constant test); 0: l2 off the int8 shadow */ \
     X(scan_nqt, "SCAN_NQT", 0)         /* query tiles of the int8 body: 0 = by batch size, else 4 / 8 / 16 */          \
     X(l2_offset_cache, "L2_OFFSET_CACHE", 1) /* l2: keep the offsets plane across passes of the same scale (0: recompute per pass) */ \
-    X(exact_nt, "EXACT_NT", 1)                                                                                          \
-    X(exact_nblk, "EXACT_NBLK", 0)                                                                                      \
-    X(prefix_pf, "PREFIX_PF", 24)                                                                                       \
-    X(prefix_waves, "PREFIX_WAVES", 4)                                                                                  \
     X(where_gather, "WHERE_GATHER", 150) /* per-query filters: gather a program's rows when matches x query tiles x 1000 <= live x this (0: never; tools/where_each_ab.py) */
 
 struct Tuning {
@@ -124,7 +111,7 @@ struct ExactPlan {
     int threads;   // block size
     size_t lds_bytes;
 };
-ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k, const Tuning& tn);
+ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k);
 
 struct ExactArgs {
     const float* X;
@@ -142,7 +129,6 @@ struct ExactArgs {
     const double* cursor_d;   // optional paging cursor per query (nullptr = none):
     const int32_t* cursor_l;  //   only rows strictly after (cursor_d, cursor_l) in rank order are admitted
     TopEntry* partial;        // [nq_sel][nblk][k]
-    const Tuning* tn;         // host only
 };
 hipError_t launch_exact_scan(const ExactArgs& a, const ExactPlan& p, hipStream_t s);
 // merge partial lists -> final outputs at the original query index
@@ -153,7 +139,7 @@ hipError_t launch_exact_merge(const TopEntry* partial, int32_t nq_sel, const int
 
 // exact fp64 distances of rows 0..m-1 to every query (tombstoned rows: +inf): d64 = [nq][m]
 hipError_t launch_prefix_exact(const float* X, const float* rn, const float* Qpad, const double* qaux, int32_t nq, int32_t m,
-                               int32_t ld, int32_t space, double* d64, const Tuning& tn, hipStream_t s);
+                               int32_t ld, int32_t space, double* d64, hipStream_t s);
 // exact fp64 distances of given pairs: out[q][j] = d(query q, row labels[q][j]) (labels on the device, each < total or < 0 = +inf)
 hipError_t launch_pair_distances(const float* X, const float* Qpad, const double* qaux, const int64_t* labels, int32_t nq,
                                  int32_t m, int32_t ld, int32_t space, double* out64, float* out32, hipStream_t s);
@@ -163,8 +149,6 @@ constexpr int kFilterQueries = 256;   // queries per filter pass
 constexpr int kFilterChunkK = 64;     // columns per Q chunk staged in LDS
 constexpr int kCandCap = 8192;        // candidate slots per query (kNN passes; also the most range hits sorted in LDS)
 constexpr int kRangeCandCap = 65536;  // candidate slots per query of a range pass: true hits + the bound's band
-constexpr int kRangeChunk = 256;      // candidates one block of the range rescoring scores (4 gather steps: the gathers are
-                                      // latency-bound, so a long list is spread over many resident blocks rather than looped over)
 constexpr int kFilterTile = 768;      // scan ranges start on multiples of it (common multiple of the kernels' 192/128/256-row tiles)
 constexpr int kScanMaxGrid = 512;     // most workgroups any scan launch uses
 constexpr int kWgCap = 16384;         // append slots per workgroup and launch (assembly scan: split evenly over its waves)
@@ -215,7 +199,7 @@ struct FilterArgs {
     uint32_t* overflow;     // [256] nonzero = list overflowed, query must be re-run exactly
     CandEntry* cand;        // [256][cand_cap]
     int32_t cand_cap;       // kCandCap (kNN passes) or kRangeCandCap (range passes: their own, larger lists)
-    struct RangeHit* rhits; // range passes: [256][kCandCap] exact hits (fp64 distance, row) found by range_score_kernel
+    struct RangeHit* rhits; // range passes: [256][kCandCap] exact hits (fp64 distance, row) found by range_score_flat_kernel
     uint32_t* rhit_cnt;     // [256] exact hit count per query (may exceed kCandCap: the excess is counted, not stored)
     // int8 shadow (cosine, ld % 256 == 0; MLVDB_I8=0 disables): all null / unused otherwise
     const void* X8;         // int8 rows, per-row scale: panels of 16 rows, 64-column groups of 1 KiB (layout_offset_i8)
@@ -246,12 +230,6 @@ hipError_t launch_filter_prep_fused(const FilterArgs& a, const float* queries, i
 // thr[q] from the k-th smallest of d64[q][0..m) (m <= 3 kSeedRows; fewer than k finite values: thr stays as it is)
 hipError_t launch_filter_prefix_thr(const FilterArgs& a, const double* d64, int32_t m, int32_t k, hipStream_t s);
 hipError_t launch_filter_seed_thr(const FilterArgs& a, const double* seed_d64, int32_t k, hipStream_t s);
-// What a scan launch reports back (tuning aids).  The assembly scan stages its hits per wave in LDS and its own tail
-// moves them into the per-query candidate lists (round 1 had a separate scatter launch for that).
-struct ScanInfo {
-    int nw = 0;
-    int i8 = 0;  // int8 scan, entries in units of the query's scale: 1 cosine (u = w sq8 + ke), 2 ip (u = w sq8)
-};
 // int8 shadow: (re)build the panels covering rows [row_begin, row_end) (also rp8 and the index-wide error), the query image of a
 // pass (after launch_filter_prep: overrides ke with the int8 error term), exact thresholds from the k best bounds
 hipError_t launch_shadow8_rows(const float* X, const float* rn, void* X8, float* rp8, float* row_err8, int64_t row_begin,
@@ -261,13 +239,13 @@ hipError_t launch_filter_prep8(const FilterArgs& a, hipStream_t s);
 // score into the scan's accumulators (tools/gen_scan_asm.py, l2e): needs a.rp8_cap > 0
 hipError_t launch_filter_l2_offsets(const FilterArgs& a, int64_t rows, hipStream_t s);
 bool filter_refine_can_fuse(const FilterArgs& a);
-bool filter_narrow_ok(const FilterArgs& a);  // the pass's scans run on the narrow kernel (<= 64 queries, image resident in LDS)
+bool filter_narrow_ok(const FilterArgs& a);  // the pass's scans run on the narrow kernel (bf16 shadow, <= 64 queries, image resident in LDS)
 hipError_t launch_filter_refine_thr(const FilterArgs& a, int32_t k, int32_t forced_cnt, bool fuse, hipStream_t s);
 // batches of <= 8 queries: the last refine + exact rescoring + ranking + output in one launch (needs filter_refine_can_fuse)
 hipError_t launch_filter_finish_small(const FilterArgs& a, int32_t k, int32_t q0, int64_t* out_labels, float* out_dist,
                                       int32_t* out_counts, double* out_d64, unsigned long long* rescored, int32_t* qsel,
                                       int32_t* nflag, hipStream_t s);
-hipError_t launch_filter_scan(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s, ScanInfo* info);
+hipError_t launch_filter_scan(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s);
 // dense seeding pass over rows [0,row_end), row_end <= kSeedRows: all bounds -> candidate lists -> thresholds (update)
 constexpr int kSeedRows = 3840;  // a multiple of every scan tile (128, 192) and <= kCandCap
 hipError_t launch_filter_seed_scan(const FilterArgs& a, int64_t row_end, int32_t k, hipStream_t s);

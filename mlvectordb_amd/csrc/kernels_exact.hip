@@ -14,7 +14,7 @@
 
 namespace mlvdb {
 
-template <int SPACE, int QT, int PW, int NW, bool NT>
+template <int SPACE, int QT, int PW, int NW>
 __global__ __launch_bounds__(NW * 64) void exact_scan_kernel(const ExactArgs a, const int nblk) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(NW * 64) void exact_scan_kernel(const ExactArgs a, 
         }
         double acc[PW][QT];
         double nx[PW];
-        accumulate_rows<SPACE, QT, PW, (QT == 8 ? 4 : 0), NT>(base, qs, ld, g, acc, nx);
+        accumulate_rows<SPACE, QT, PW, (QT == 8 ? 4 : 0), /*NT=*/true>(base, qs, ld, g, acc, nx);  // every row is read once per launch
 #pragma unroll
         for (int p = 0; p < PW; ++p) {
             const int64_t row = panel[p] * kPanelRows + r;
@@ -326,13 +326,13 @@ __global__ __launch_bounds__(256) void prefix_exact_kernel(const float* __restri
 }
 
 hipError_t launch_prefix_exact(const float* X, const float* rn, const float* Qpad, const double* qaux, int32_t nq, int32_t m,
-                               int32_t ld, int32_t space, double* d64, const Tuning& tn, hipStream_t s) {
+                               int32_t ld, int32_t space, double* d64, hipStream_t s) {
     if (nq <= 0 || m <= 0) return hipErrorInvalidValue;
     const size_t lds = (size_t)ld * sizeof(double);
     // a whole 768-column row in flight per lane (24 groups x two banks) when the row is a whole number of such halves:
-    // one round trip per row instead of three (the kernel is one latency chain per wave); MLVDB_PREFIX_PF=8: tuning
-    const bool pf24 = (ld / 16) % 24 == 0 && tn.prefix_pf == 24;
-    const int nw = std::max(1, std::min(4, tn.prefix_waves));  // waves per block, 16 rows each
+    // one round trip per row instead of three (the kernel is one latency chain per wave)
+    const bool pf24 = (ld / 16) % 24 == 0;
+    const int nw = 4;  // waves per block, 16 rows each
     const dim3 grid((unsigned)nq, (unsigned)(((int64_t)m + 16 * nw - 1) / (16 * nw)));
     hipError_t e = hipSuccess;
 #define MLVDB_LAUNCH_PREFIX(SP)                                                                                        \
@@ -373,7 +373,7 @@ hipError_t launch_pair_distances(const float* X, const float* Qpad, const double
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k, const Tuning& tn) {
+ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k) {
     ExactPlan p;
     int qt = nq_sel >= 8 ? 8 : nq_sel >= 4 ? 4 : nq_sel >= 2 ? 2 : 1;
     while (qt > 1 && (size_t)qt * ld * sizeof(double) > 64 * 1024) qt >>= 1;
@@ -385,10 +385,9 @@ ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k, const
     const int64_t npanels = (nrows + 15) / 16;
     const int64_t ntasks = (npanels + pw - 1) / pw;
     int64_t nblk = (ntasks + nw - 1) / nw;
-    // one block per CU is the sweet spot for the streaming scan (tools/exact_ab.py); with several query
+    // one block per CU is the sweet spot for the streaming scan (profiles/r01/exact_ab_nt_1m.txt); with several query
     // tiles the corpus is split over fewer blocks each
     int64_t cap = std::min<int64_t>(256, 1024 / p.nqtiles);
-    if (tn.exact_nblk > 0) cap = tn.exact_nblk;  // tuning experiments only
     if (cap < 8) cap = 8;
     if (nblk > cap) nblk = cap;
     if (nblk < 1) nblk = 1;
@@ -400,9 +399,9 @@ ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k, const
     return p;
 }
 
-template <int SPACE, int QT, int PW, int NW, bool NT = false>
+template <int SPACE, int QT, int PW, int NW>
 static hipError_t launch_one(const ExactArgs& a, const ExactPlan& p, hipStream_t s) {
-    auto kern = exact_scan_kernel<SPACE, QT, PW, NW, NT>;
+    auto kern = exact_scan_kernel<SPACE, QT, PW, NW>;
     if (p.lds_bytes > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
@@ -414,15 +413,11 @@ static hipError_t launch_one(const ExactArgs& a, const ExactPlan& p, hipStream_t
 
 template <int SPACE>
 static hipError_t launch_space(const ExactArgs& a, const ExactPlan& p, hipStream_t s) {
-    // non-temporal corpus loads (every row is read once per launch); MLVDB_EXACT_NT=0 selects plain loads for the
-    // batch-1 shape only (A/B: tools/exact_ab.py)
-    const bool plain = a.tn && a.tn->exact_nt == 0;
-    if (p.qt == 1 && plain) return launch_one<SPACE, 1, 2, 16, false>(a, p, s);
     switch (p.qt) {
-        case 1: return launch_one<SPACE, 1, 2, 16, true>(a, p, s);
-        case 2: return launch_one<SPACE, 2, 2, 16, true>(a, p, s);
-        case 4: return launch_one<SPACE, 4, 4, 8, true>(a, p, s);
-        default: return launch_one<SPACE, 8, 2, 8, true>(a, p, s);
+        case 1: return launch_one<SPACE, 1, 2, 16>(a, p, s);
+        case 2: return launch_one<SPACE, 2, 2, 16>(a, p, s);
+        case 4: return launch_one<SPACE, 4, 4, 8>(a, p, s);
+        default: return launch_one<SPACE, 8, 2, 8>(a, p, s);
     }
 }
 

@@ -1198,69 +1198,16 @@ __global__ __launch_bounds__(kRankWaves * 64) void filter_rescore_rank_kernel(co
 }
 
 // Range variant, two kernels.  A range pass can hold tens of thousands of candidates for one query and a handful for
-// the next (hit counts vary ~1000x with |q| on unnormalised data), so the exact rescoring is spread over
-// (query, chunk of kRangeChunk candidates) blocks instead of one block per query:
-//   range_score_kernel  exact fp64 distance of every candidate of its chunk; the hits (dist <= radius, live) are
-//                       collected in LDS and copied to the query's hit array behind one atomic reservation;
-//   range_rank_kernel   blocks over (query, 256 hits): rank of every hit by (distance, label), written to its place;
-//                       publishes the exact count.  More than kCandCap hits: flagged, served by the paged exact kNN (api.hip).
-template <int SPACE>
-__global__ __launch_bounds__(256) void range_score_kernel(const FilterArgs a, const float radius) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* qs = reinterpret_cast<double*>(smem);                                  // [ld]
-    RangeHit* found = reinterpret_cast<RangeHit*>(qs + a.ld);                      // [kRangeChunk]
-    uint32_t& s_n = *reinterpret_cast<uint32_t*>(found + kRangeChunk);
-    uint32_t& s_base = *(&s_n + 1);
-    const int q = blockIdx.x;
-    if (q >= a.nq || a.overflow[q]) return;
-    const uint32_t cnt = min(a.cnt[q], (uint32_t)a.cand_cap);
-    const uint32_t begin = blockIdx.y * (uint32_t)kRangeChunk;
-    if (begin >= cnt) return;
-    const uint32_t end = min(cnt, begin + (uint32_t)kRangeChunk);
-    const int ld = a.ld;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, r = lane & 15;
-    for (int c = threadIdx.x; c < ld; c += 256) qs[c] = (double)a.Qpad[(int64_t)q * ld + c];
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    const double qinv = a.qaux[q];
-    const double rad = (double)radius;
-    const CandEntry* list = a.cand + (int64_t)q * a.cand_cap;
-    for (uint32_t i0 = begin + wave * 16; i0 < end; i0 += 64) {
-        const uint32_t idx = i0 + r;
-        const bool have = idx < end;
-        const int32_t row = have ? (int32_t)((uint32_t)list[idx].row & ~kRefinedBit) : 0;
-        const float* base[1] = {a.X + (int64_t)(row >> 4) * (kPanelRows * ld) + (row & 15) * 16 + g * 4};
-        double acc[1][1], nx[1];
-        accumulate_rows<SPACE, 1, 1, 8>(base, qs, ld, g, acc, nx);
-        const double dist = finish_distance<SPACE>(acc[0][0], nx[0], qinv);
-        bool hit = have && lane < 16 && dist <= rad;
-        if (hit) {
-            const float nrm = a.rn[row];
-            hit = nrm == nrm;
-        }
-        if (hit) {
-            const uint32_t slot = atomicAdd(&s_n, 1u);
-            found[slot].d = dist;
-            found[slot].l = row;
-        }
-    }
-    __syncthreads();
-    const uint32_t n = s_n;
-    if (n == 0) return;
-    if (threadIdx.x == 0) s_base = atomicAdd(&a.rhit_cnt[q], n);
-    __syncthreads();
-    const uint32_t base = s_base;
-    RangeHit* out = a.rhits + (int64_t)q * kCandCap;
-    for (uint32_t i = threadIdx.x; i < n; i += 256)
-        if (base + i < (uint32_t)kCandCap) out[base + i] = found[i];  // beyond: counted only (the query is paged exactly)
-}
-
-// Round 3: the same work as range_score_kernel, dealt out like the kNN rescoring (filter_rescore_score_kernel): the
-// 16-candidate groups of ALL queries form one flat list, group u goes to wave (u mod waves-of-the-grid), one block per CU --
-// every CU gathers the same number of rows whatever the spread of the list lengths (a query's hit count varies ~1000x with
-// |q|: the (query, chunk) grid launched 65,536 blocks of which ~1,000 had work, 820 us per 256-query wave).  A group's
-// hits (dist <= radius, live) are appended to the query's hit array behind one atomic per group.
+// the next (hit counts vary ~1000x with |q| on unnormalised data):
+//   range_score_flat_kernel  exact fp64 distance of every candidate; the hits (dist <= radius, live) go to the query's
+//                            hit array;
+//   range_rank_kernel        blocks over (query, 32 hits): rank of every hit by (distance, label), written to its place;
+//                            publishes the exact count.  More than kCandCap hits: flagged, served by the paged exact kNN (api.hip).
+// The scoring is dealt out like the kNN rescoring (filter_rescore_score_kernel): the 16-candidate groups of ALL queries
+// form one flat list, group u goes to wave (u mod waves-of-the-grid), one block per CU -- every CU gathers the same number
+// of rows whatever the spread of the list lengths (a grid of (query, 256-candidate chunk) blocks launched 65,536 blocks of
+// which ~1,000 had work, 820 us per 256-query wave).  A group's hits are appended to the query's hit array behind one
+// atomic per group.
 template <int SPACE>
 __global__ __launch_bounds__(kRescoreWaves * 64) void range_score_flat_kernel(const FilterArgs a, const float radius) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2635,8 +2582,7 @@ hipError_t launch_filter_finish_small(const FilterArgs& a, int32_t k, int32_t q0
 }
 
 template <int SPACE, bool XB, bool DENSE = false>
-static hipError_t launch_scan_one(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s,
-                                  ScanInfo* info = nullptr) {
+static hipError_t launch_scan_one(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
     constexpr int NW = 4, MT = 2;
     constexpr int tile_rows = NW * 16 * MT;
     const int64_t tile_begin = row_begin / tile_rows;
@@ -2663,13 +2609,11 @@ static size_t narrow_lds(int32_t ld, int nqt, int nw, bool i8 = false) {
     return (size_t)(ld / (i8 ? 64 : 32)) * nqt * 1024 + 3 * kFilterQueries * sizeof(float) + (size_t)nw * 4 * 2 * 64 * sizeof(float);
 }
 bool filter_narrow_ok(const FilterArgs& a) {
-    if (!(a.Xb || a.X8) || a.nq > kNarrowMaxQueries) return false;  // streams the int8 shadow when the pass has one, else the bf16 one
+    // a pass with an int8 shadow scans on the assembly body generated for 4 query tiles, at any batch size: this kernel streams
+    // the bf16 shadow (its int8 form serves only the dense seeding pass: launch_filter_dense_scan)
+    if (!a.Xb || a.X8 || a.nq > kNarrowMaxQueries) return false;
     if (a.tn->scan_narrow == 0) return false;
-    // int8 shadow: the assembly body generated for 4 query tiles (round 4) streams it at the copy ceiling and stages its hits
-    // per wave; this compiler-scheduled kernel appends them one atomic at a time and is slower at every batch size (10M x 768:
-    // 1.25-1.47 vs 1.20-1.21 ms for 1-8 queries, profiles/r04/small_batch_nqt4_vs_narrow_*.txt).  NARROW_I8_MAX > 0 brings it back (A/B).
-    if (a.X8 && a.nq > a.tn->narrow_i8_max) return false;
-    return narrow_lds(a.X8 ? a.ld8 : a.ld, narrow_nqt(a.nq), 8, a.X8 != nullptr) <= kNarrowLdsMax;
+    return narrow_lds(a.ld, narrow_nqt(a.nq), 8) <= kNarrowLdsMax;
 }
 template <int SPACE, int NQT, bool DENSE, int R, int NW, bool I8 = false>
 static hipError_t launch_scan_narrow_n(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s, int qgroups = 1) {
@@ -2680,11 +2624,10 @@ static hipError_t launch_scan_narrow_n(const FilterArgs& a, int64_t row_begin, i
     const size_t lds = narrow_lds(I8 ? a.ld8 : a.ld, NQT, NW, I8);
     const int64_t ntiles = tile_end - tile_begin;
     const int per_cu = (int)std::min<size_t>(32 / NW, (160 * 1024) / lds);  // workgroups resident per CU
-    const int max_grid = 256 * (a.tn->narrow_wgs > 0 ? a.tn->narrow_wgs : per_cu);
+    const int max_grid = 256 * per_cu;
     // equal tile counts per workgroup: the kernel is a pure stream, a last round with a few busy workgroups is all tail
     const int64_t rounds = (ntiles + max_grid - 1) / max_grid;
-    const int grid = a.tn->narrow_balance ? (int)((ntiles + rounds - 1) / rounds)
-                                                        : (int)(ntiles < max_grid ? ntiles : max_grid);
+    const int grid = (int)((ntiles + rounds - 1) / rounds);
     auto kern = filter_scan_narrow_kernel<SPACE, NQT, DENSE, R, NW, I8>;
     static std::atomic<uint64_t> configured{0};  // per instantiation
     if (hipError_t e = ensure_dynamic_lds(configured, reinterpret_cast<const void*>(kern), (int)kNarrowLdsMax); e != hipSuccess)
@@ -2694,10 +2637,6 @@ static hipError_t launch_scan_narrow_n(const FilterArgs& a, int64_t row_begin, i
 }
 template <int SPACE, int NQT, bool DENSE>
 static hipError_t launch_scan_narrow_q(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
-    if (a.X8) {  // int8 shadow: k-steps of 64 columns; ld % 256 == 0, so their count is a multiple of 4
-        if constexpr (DENSE) return launch_scan_narrow_n<SPACE, NQT, true, 4, 4, true>(a, row_begin, row_end, s);
-        else return launch_scan_narrow_n<SPACE, NQT, false, 4, 8, true>(a, row_begin, row_end, s);
-    }
     const bool r4 = (a.ld / 32) % 4 == 0;
     if constexpr (DENSE) {  // the seeding pass is a few tiles: one geometry
         return r4 ? launch_scan_narrow_n<SPACE, NQT, true, 4, 4>(a, row_begin, row_end, s)
@@ -2718,7 +2657,7 @@ static hipError_t launch_scan_narrow(const FilterArgs& a, int64_t row_begin, int
 }
 
 template <int SPACE, int R, bool I8, int NQT = 16>
-static hipError_t launch_scan_asm(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s, ScanInfo* info) {
+static hipError_t launch_scan_asm(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
     constexpr int NW = kAsmWaves, tile_rows = NW * 32;
     const int64_t tile_begin = row_begin / tile_rows;
     const int64_t tile_end = (row_end + tile_rows - 1) / tile_rows;
@@ -2740,8 +2679,6 @@ static hipError_t launch_scan_asm(const FilterArgs& a, int64_t row_begin, int64_
         return e;
     kern<<<grid, NW * 64, lds, s>>>(a, tile_begin, tile_end, /*xcd_mode=*/0);
     // (the kernel's own tail moves the entries into the candidate lists: there is no scatter launch)
-    info->nw = NW;
-    info->i8 = !I8 ? 0 : (SPACE == kSpaceCosine ? 1 : (SPACE == kSpaceIp ? 2 : 0));  // how the scatter turns stored values into bounds
     return hipGetLastError();
 }
 
@@ -2750,7 +2687,7 @@ static hipError_t launch_scan_asm(const FilterArgs& a, int64_t row_begin, int64_
 // shadow (fp32 rows converted in registers).  The handle's tuning state picks among them -- nothing here reads the
 // environment.
 template <int SPACE>
-static hipError_t launch_scan_space(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s, ScanInfo* info) {
+static hipError_t launch_scan_space(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
     if (filter_narrow_ok(a)) return launch_scan_narrow<SPACE, false>(a, row_begin, row_end, s);  // appends to the lists itself
     // hand-written bodies (tools/gen_scan_asm.py): one 8-wave workgroup per CU (256-row tiles: the query image is staged
     // once per CU, by LDS-DMA), non-temporal X loads, ring of 4 k-steps -- measured fastest (profiles/r01/scan_ab_*.txt)
@@ -2759,16 +2696,16 @@ static hipError_t launch_scan_space(const FilterArgs& a, int64_t row_begin, int6
         // l2: the folded admission test with per-row integer offsets (the pass computed them: api.hip prep_pass) is the only
         // int8 body -- api.hip attaches the int8 shadow to an l2 pass only with rp8_cap and l2c set
         const int nqt = a.tn->scan_nqt > 0 ? a.tn->scan_nqt : (a.nq <= 64 ? 4 : (a.nq <= 128 ? 8 : 16));
-        if (nqt <= 4 && a.nq <= 64) return launch_scan_asm<SPACE, 4, true, 4>(a, row_begin, row_end, s, info);
-        if (nqt <= 8 && a.nq <= 128) return launch_scan_asm<SPACE, 4, true, 8>(a, row_begin, row_end, s, info);
-        return launch_scan_asm<SPACE, 4, true, 16>(a, row_begin, row_end, s, info);
+        if (nqt <= 4 && a.nq <= 64) return launch_scan_asm<SPACE, 4, true, 4>(a, row_begin, row_end, s);
+        if (nqt <= 8 && a.nq <= 128) return launch_scan_asm<SPACE, 4, true, 8>(a, row_begin, row_end, s);
+        return launch_scan_asm<SPACE, 4, true, 16>(a, row_begin, row_end, s);
     }
     if (a.Xb) {  // bf16 shadow; a ring of R k-steps needs the tile's k-steps (two per chunk) to be a multiple of R
-        if ((a.ld / kFilterChunkK) % 2 == 0) return launch_scan_asm<SPACE, 4, false>(a, row_begin, row_end, s, info);
-        return launch_scan_asm<SPACE, 2, false>(a, row_begin, row_end, s, info);
+        if ((a.ld / kFilterChunkK) % 2 == 0) return launch_scan_asm<SPACE, 4, false>(a, row_begin, row_end, s);
+        return launch_scan_asm<SPACE, 2, false>(a, row_begin, row_end, s);
     }
     // no shadow (or an int8-only index without usable int8 bounds): fp32 rows converted in registers
-    return launch_scan_one<SPACE, false>(a, row_begin, row_end, s, info);
+    return launch_scan_one<SPACE, false>(a, row_begin, row_end, s);
 }
 
 // Seeding pass over rows [0, row_end): every bound goes into the candidate lists (slot = row),
@@ -2778,7 +2715,7 @@ static hipError_t launch_update(const FilterArgs& a, int32_t k, int32_t forced_c
 
 hipError_t launch_filter_dense_scan(const FilterArgs& a, int64_t rows, hipStream_t s) {
     const bool xb = a.Xb != nullptr;
-    if (filter_narrow_ok(a)) {  // (round 3: the narrow kernel runs on the int8 shadow for every space)
+    if (filter_narrow_ok(a)) {
         return a.space == kSpaceL2       ? launch_scan_narrow<kSpaceL2, true>(a, 0, rows, s)
                : a.space == kSpaceCosine ? launch_scan_narrow<kSpaceCosine, true>(a, 0, rows, s)
                                          : launch_scan_narrow<kSpaceIp, true>(a, 0, rows, s);
@@ -2823,12 +2760,11 @@ hipError_t launch_filter_seed_scan(const FilterArgs& a, int64_t row_end, int32_t
     return launch_update(a, k, (int32_t)rows, s);  // lists -> thresholds; cnt[q] = survivors
 }
 
-hipError_t launch_filter_scan(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s, ScanInfo* info) {
-    *info = ScanInfo{};
+hipError_t launch_filter_scan(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
     switch (a.space) {
-        case kSpaceL2: return launch_scan_space<kSpaceL2>(a, row_begin, row_end, s, info);
-        case kSpaceCosine: return launch_scan_space<kSpaceCosine>(a, row_begin, row_end, s, info);
-        default: return launch_scan_space<kSpaceIp>(a, row_begin, row_end, s, info);
+        case kSpaceL2: return launch_scan_space<kSpaceL2>(a, row_begin, row_end, s);
+        case kSpaceCosine: return launch_scan_space<kSpaceCosine>(a, row_begin, row_end, s);
+        default: return launch_scan_space<kSpaceIp>(a, row_begin, row_end, s);
     }
 }
 
@@ -2873,72 +2809,37 @@ hipError_t launch_filter_rescore(const FilterArgs& a, int32_t k, int32_t q0, int
     return hipGetLastError();
 }
 
-hipError_t launch_range_rescore(const FilterArgs& a, float radius, int32_t q0, int64_t capacity, int64_t* out_labels,
-                                float* out_dist, int64_t* out_counts, hipStream_t s) {
+// Exact fp64 distance of every list entry -- the hits (dist <= radius, live) go to the query's hit array -- then the ranking
+// kernel: range results (knn.k == 0) or the k nearest.
+static hipError_t launch_score_rank(const FilterArgs& a, float radius, int32_t q0, int64_t capacity, int64_t* out_labels,
+                                    float* out_dist, int64_t* out_counts, const KnnOut& knn, hipStream_t s) {
     const size_t lds_sort = (size_t)kCandCap * (sizeof(double) + sizeof(int32_t));  // the ranking kernel's {d[], l[]} (kCandCap % 64 == 0)
-    hipError_t e = hipMemsetAsync(a.rhit_cnt, 0, kFilterQueries * sizeof(uint32_t), s);
-    if (e != hipSuccess) return e;
-    // MLVDB_RANGE_FLAT=0: round 2's (query, 256-candidate chunk) grid (A/B)
-    const bool flat = a.tn->range_flat != 0;
-    int waves = kRescoreWaves;
-    while (waves > 1 && (size_t)waves * a.ld * sizeof(double) > 144 * 1024) waves >>= 1;
-    const size_t lds_score = flat ? std::max((size_t)waves * a.ld * sizeof(double), (size_t)96 * 1024)
-                                  : (size_t)a.ld * sizeof(double) + (size_t)kRangeChunk * sizeof(RangeHit) + 16;
-    const dim3 grid = flat ? dim3(kRescoreGrid) : dim3((unsigned)a.nq, (unsigned)((a.cand_cap + kRangeChunk - 1) / kRangeChunk));
-    const int threads = flat ? waves * 64 : 256;
-#define MLVDB_LAUNCH_RANGE(SP)                                                                                        \
-    do {                                                                                                              \
-        auto kern = flat ? range_score_flat_kernel<SP> : range_score_kernel<SP>;                                      \
-        if (lds_score > 48 * 1024)                                                                                    \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                    (int)lds_score);                                                                  \
-        if (e == hipSuccess) kern<<<grid, threads, lds_score, s>>>(a, radius);                                        \
-    } while (0)
-    switch (a.space) {
-        case kSpaceL2: MLVDB_LAUNCH_RANGE(kSpaceL2); break;
-        case kSpaceCosine: MLVDB_LAUNCH_RANGE(kSpaceCosine); break;
-        default: MLVDB_LAUNCH_RANGE(kSpaceIp); break;
-    }
-#undef MLVDB_LAUNCH_RANGE
-    if (e != hipSuccess) return e;
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(range_rank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds_sort);
-    if (e != hipSuccess) return e;
-    range_rank_kernel<<<kRankGrid, kRankThreads, lds_sort, s>>>(a, q0, capacity, out_labels, out_dist, out_counts, KnnOut{});
-    return hipGetLastError();
-}
-
-hipError_t launch_knn_rescore_rank(const FilterArgs& a, int32_t k, int32_t q0, int64_t* out_labels, float* out_dist,
-                                   int32_t* out_counts, double* out_d64, unsigned long long* rescored, hipStream_t s) {
-    const size_t lds_sort = (size_t)kCandCap * (sizeof(double) + sizeof(int32_t));
     hipError_t e = hipMemsetAsync(a.rhit_cnt, 0, kFilterQueries * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     int waves = kRescoreWaves;
     while (waves > 1 && (size_t)waves * a.ld * sizeof(double) > 144 * 1024) waves >>= 1;
     const size_t lds_score = std::max((size_t)waves * a.ld * sizeof(double), (size_t)96 * 1024);
-    const float inf = __builtin_inff();  // every live entry is a "hit"
-#define MLVDB_LAUNCH_KNN_SCORE(SP)                                                                                    \
-    do {                                                                                                              \
-        auto kern = range_score_flat_kernel<SP>;                                                                      \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                (int)lds_score);                                                                      \
-        if (e == hipSuccess) kern<<<kRescoreGrid, waves * 64, lds_score, s>>>(a, inf);                                \
-    } while (0)
-    switch (a.space) {
-        case kSpaceL2: MLVDB_LAUNCH_KNN_SCORE(kSpaceL2); break;
-        case kSpaceCosine: MLVDB_LAUNCH_KNN_SCORE(kSpaceCosine); break;
-        default: MLVDB_LAUNCH_KNN_SCORE(kSpaceIp); break;
-    }
-#undef MLVDB_LAUNCH_KNN_SCORE
-    if (e != hipSuccess) return e;
+    auto kern = a.space == kSpaceL2 ? range_score_flat_kernel<kSpaceL2>
+                : a.space == kSpaceCosine ? range_score_flat_kernel<kSpaceCosine> : range_score_flat_kernel<kSpaceIp>;
+    static std::atomic<uint64_t> score_configured[3], rank_configured{0};
+    if ((e = ensure_dynamic_lds(score_configured[a.space], reinterpret_cast<const void*>(kern), 144 * 1024)) != hipSuccess) return e;
+    kern<<<kRescoreGrid, waves * 64, lds_score, s>>>(a, radius);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(range_rank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds_sort);
-    if (e != hipSuccess) return e;
-    range_rank_kernel<<<kRankGrid, kRankThreads, lds_sort, s>>>(a, q0, (int64_t)k, out_labels, out_dist, nullptr,
-                                                                KnnOut{k, out_counts, out_d64, rescored});
+    if ((e = ensure_dynamic_lds(rank_configured, reinterpret_cast<const void*>(range_rank_kernel), (int)lds_sort)) != hipSuccess)
+        return e;
+    range_rank_kernel<<<kRankGrid, kRankThreads, lds_sort, s>>>(a, q0, capacity, out_labels, out_dist, out_counts, knn);
     return hipGetLastError();
+}
+
+hipError_t launch_range_rescore(const FilterArgs& a, float radius, int32_t q0, int64_t capacity, int64_t* out_labels,
+                                float* out_dist, int64_t* out_counts, hipStream_t s) {
+    return launch_score_rank(a, radius, q0, capacity, out_labels, out_dist, out_counts, KnnOut{}, s);
+}
+
+hipError_t launch_knn_rescore_rank(const FilterArgs& a, int32_t k, int32_t q0, int64_t* out_labels, float* out_dist,
+                                   int32_t* out_counts, double* out_d64, unsigned long long* rescored, hipStream_t s) {
+    // an infinite radius: every live entry is a "hit"
+    return launch_score_rank(a, __builtin_inff(), q0, (int64_t)k, out_labels, out_dist, nullptr, KnnOut{k, out_counts, out_d64, rescored}, s);
 }
 
 }  // namespace mlvdb

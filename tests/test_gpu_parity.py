@@ -750,6 +750,30 @@ def test_passes_of_9_to_128_queries_compute_only_their_query_tiles(space, nq):
         eng.close()
 
 
+RETIRED_TUNING_KEYS = ["RANGE_FLAT", "RANGE_I8", "NARROW_I8_MAX", "NARROW_WGS", "NARROW_BALANCE", "EVENT_FENCE", "SEED_EXACT",
+                       "PINNED_IO", "PREFIX_PF", "PREFIX_WAVES", "EXACT_NT", "EXACT_NBLK", "SCAN_L2E"]
+
+
+@pytest.mark.parametrize("key", RETIRED_TUNING_KEYS)
+def test_retired_tuning_keys_are_refused(key, monkeypatch):
+    """DESIGN section 9, retired keys: the A/B switches whose experiments are closed are no tuning keys any more.  Their MLVDB_*
+    variables are ignored when an index is created, mlvdb_index_set_tuning / _get_tuning answer MLVDB_ERR_INVALID_ARG (1), and
+    a surviving key is still taken."""
+    monkeypatch.setenv(f"MLVDB_{key}", "1")
+    eng = HipScanEngine(64, "cosine", device=0)
+    try:
+        assert eng._lib.mlvdb_index_set_tuning(eng.handle, f"{key}=1".encode()) == 1
+        assert eng._lib.mlvdb_index_set_tuning(eng.handle, f"MLVDB_{key}=0".encode()) == 1
+        with pytest.raises(RuntimeError, match=r"failed \(1\): unknown tuning key"):
+            eng.set_tuning(**{key: 0})
+        with pytest.raises(RuntimeError, match=r"failed \(1\): unknown tuning key"):
+            eng.get_tuning(key)
+        eng.set_tuning(SCAN_NQT=16)
+        assert eng.get_tuning("SCAN_NQT") == 16
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("space,d,nq", [("cosine", 4096, 40), ("l2", 2560, 70), ("ip", 8192, 20), ("cosine", 8192, 3),
                                         # 1-2 queries: the prefix seed with a 64 KB query in LDS; the fused finish at and beyond its ld = 2048 limit
                                         ("l2", 8192, 1), ("cosine", 4096, 2), ("ip", 2048, 1), ("cosine", 2304, 2)])
@@ -839,7 +863,6 @@ SMALL_KNOBS = [
     {"MLVDB_SMALL_FINISH": "0"},        # prefix seed, the three finishing kernels
     {"MLVDB_SMALL_NQ": "0"},            # round 2's structure
     {"MLVDB_SMALL_NQ": "8"},            # both steps for up to 8 queries
-    {"MLVDB_NARROW_I8_MAX": "8"},       # the int8 narrow kernel (round 3's scan for 1-8 queries) instead of the 4-tile assembly body
     {"MLVDB_SCAN_NQT": "16"},           # every pass padded to 16 query tiles (round 3)
 ]
 SMALL_CASES = [
