@@ -103,6 +103,13 @@ WHERE_EACH_SIGNATURES = {
     "mlvdb_where_count_each": (C.c_int, [_P, C.POINTER(Where), C.c_int32, _P]),
 }
 
+# include/mlvdb_where_each_range.h: per-query filters in one batched range call
+WHERE_EACH_RANGE_LIST = 8192
+WHERE_EACH_RANGE_SIGNATURES = {
+    "mlvdb_range_batch_packed_where_each": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int64, C.c_int64, C.POINTER(Where),
+                                                      C.c_int32, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -131,7 +138,8 @@ def load() -> C.CDLL:
             f"`python -c 'import __graft_entry__ as g; g.build()'` or `make -C mlvectordb_amd/csrc`. "
             f"There is no CPU fallback for the search path.")
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
+                                      **WHERE_EACH_RANGE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

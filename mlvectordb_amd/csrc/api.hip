@@ -1665,35 +1665,15 @@ static int pack_range_hits(mlvdb_index* h, hipStream_t s, int64_t nq, int64_t ca
     return MLVDB_OK;
 }
 
-// Both range entries.  out_offsets == nullptr: the dense form (out_labels / out_dist are [nq, capacity]); otherwise the packed
-// form: the hits of query i are entries out_offsets[i] .. out_offsets[i + 1] of out_labels / out_dist (total_capacity entries).
-static int range_batch_impl(mlvdb_index* h, const float* queries, int64_t nq, float radius, int64_t capacity, int64_t* out_labels,
-                            float* out_dist, int64_t* out_counts, int64_t* out_offsets, int64_t total_capacity, bool packed) {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if (packed && !out_offsets) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
-    if (out_offsets && total_capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "total_capacity must be >= 0");
-    if (nq == 0) {
-        if (out_offsets) out_offsets[0] = 0;
-        return MLVDB_OK;
-    }
-    if (!queries || !out_counts || ((!out_labels || !out_dist) && (!out_offsets || total_capacity > 0)))
-        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    hipStream_t s = h->stream;
-    rc = begin_call(h, s);
-    if (rc) return rc;
-    if (h->total == 0 || h->total == h->deleted) {
-        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
-        if (out_offsets)
-            for (int64_t i = 0; i <= nq; ++i) out_offsets[i] = 0;
-        return end_call(h, s);
-    }
+// The range passes of a call (between its begin_call and end_call; the index holds live rows, nq >= 1): the ranked hits of
+// query i -- its nearest min(count, cap_eff) -- are left on the device in rows i of h->io_lab / h->io_dist (cap_eff slots each),
+// counts[i] is its exact hit count and offsets ([nq + 1]) the packed layout of the returned hits.
+static int range_ranked(mlvdb_index* h, hipStream_t s, const float* queries, int64_t nq, float radius, int64_t cap_eff,
+                        std::vector<int64_t>& counts, std::vector<int64_t>& offsets) {
+    int rc = MLVDB_OK;
     HIP_TRY(h, h->io_q.ensure((size_t)nq * h->dim * sizeof(float)));
     HIP_TRY(h, h->qpad.ensure((size_t)nq * h->ld * sizeof(float)));
     HIP_TRY(h, h->qaux.ensure((size_t)nq * sizeof(double)));
-    const int64_t cap_eff = std::min<int64_t>(capacity, MLVDB_MAX_TOPK_PAGED);  // most hits returned per query
     HIP_TRY(h, h->io_lab.ensure((size_t)nq * cap_eff * sizeof(int64_t)));
     HIP_TRY(h, h->io_dist.ensure((size_t)nq * cap_eff * sizeof(float)));
     HIP_TRY(h, h->io_cnt.ensure((size_t)nq * sizeof(int64_t)));
@@ -1783,16 +1763,49 @@ static int range_batch_impl(mlvdb_index* h, const float* queries, int64_t nq, fl
             HIP_TRY(h, hipGetLastError());
         }
     }
-    // copy back.  Hit counts vary by orders of magnitude between queries, so the dense [nq, cap_eff] device
-    // arrays are mostly padding: when the hits are a small part of them, pack the rows' valid prefixes on the
-    // device and send only those (25 MB -> 0.4 MB at 256 queries x 8192 slots with 128 hits on average).
+    // the exact counts, and where each query's returned hits go in a packed array
     HIP_TRY(h, h->pin_out.ensure((size_t)nq * sizeof(int64_t)));
     HIP_TRY(h, hipStreamSynchronize(s));
     HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->io_cnt.p, (size_t)nq * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
-    std::vector<int64_t> counts(static_cast<const int64_t*>(h->pin_out.p), static_cast<const int64_t*>(h->pin_out.p) + nq);
-    std::vector<int64_t> offsets((size_t)nq + 1, 0);
+    counts.assign(static_cast<const int64_t*>(h->pin_out.p), static_cast<const int64_t*>(h->pin_out.p) + nq);
+    offsets.assign((size_t)nq + 1, 0);
     for (int64_t i = 0; i < nq; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + std::min<int64_t>(std::max<int64_t>(counts[i], 0), cap_eff);
+    return MLVDB_OK;
+}
+
+// Both range entries.  out_offsets == nullptr: the dense form (out_labels / out_dist are [nq, capacity]); otherwise the packed
+// form: the hits of query i are entries out_offsets[i] .. out_offsets[i + 1] of out_labels / out_dist (total_capacity entries).
+static int range_batch_impl(mlvdb_index* h, const float* queries, int64_t nq, float radius, int64_t capacity, int64_t* out_labels,
+                            float* out_dist, int64_t* out_counts, int64_t* out_offsets, int64_t total_capacity, bool packed) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (packed && !out_offsets) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
+    if (out_offsets && total_capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "total_capacity must be >= 0");
+    if (nq == 0) {
+        if (out_offsets) out_offsets[0] = 0;
+        return MLVDB_OK;
+    }
+    if (!queries || !out_counts || ((!out_labels || !out_dist) && (!out_offsets || total_capacity > 0)))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    hipStream_t s = h->stream;
+    rc = begin_call(h, s);
+    if (rc) return rc;
+    if (h->total == 0 || h->total == h->deleted) {
+        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        if (out_offsets)
+            for (int64_t i = 0; i <= nq; ++i) out_offsets[i] = 0;
+        return end_call(h, s);
+    }
+    const int64_t cap_eff = std::min<int64_t>(capacity, MLVDB_MAX_TOPK_PAGED);  // most hits returned per query
+    std::vector<int64_t> counts, offsets;
+    rc = range_ranked(h, s, queries, nq, radius, cap_eff, counts, offsets);
+    if (rc) return rc;
+    // copy back.  Hit counts vary by orders of magnitude between queries, so the dense [nq, cap_eff] device
+    // arrays are mostly padding: when the hits are a small part of them, pack the rows' valid prefixes on the
+    // device and send only those (25 MB -> 0.4 MB at 256 queries x 8192 slots with 128 hits on average).
     const int64_t total_hits = offsets[(size_t)nq];
     bool over = false, hard = false;
     for (int64_t i = 0; i < nq; ++i) {
@@ -2464,6 +2477,275 @@ int mlvdb_search_batch_where_each(mlvdb_index* h, const float* queries, int64_t 
         if (rc) return rc;
     }
     if (!plain.empty()) return search_rows(h, queries, plain, k, false, out_labels, out_dist, out_counts, out_dist64);
+    return MLVDB_OK;
+    });
+}
+
+extern "C++" {
+namespace {
+// ---- per-query filters in a range call (mlvdb_where_each_range.h)
+static_assert(MLVDB_WHERE_EACH_RANGE_LIST == kCandCap, "the GATHER route lists what the ranking kernel ranks");
+
+// What the sub-batches of a call found, by query of the call: its exact hit count and where its returned hits lie in lab / dist.
+struct RangeParts {
+    std::vector<int64_t> count, begin, len;  // [nq]
+    std::vector<int64_t> lab;
+    std::vector<float> dist;
+};
+
+// A sub-batch's answer (counts / offsets by its own queries 0.., packed hits pl / pd) as the answer of the call's queries sel[i].
+void take_hits(RangeParts& parts, const std::vector<int32_t>& sel, const std::vector<int64_t>& counts,
+               const std::vector<int64_t>& offsets, const int64_t* pl, const float* pd) {
+    const size_t at = parts.lab.size(), n = (size_t)offsets[sel.size()];
+    if (n) {
+        parts.lab.insert(parts.lab.end(), pl, pl + n);
+        parts.dist.insert(parts.dist.end(), pd, pd + n);
+    }
+    for (size_t i = 0; i < sel.size(); ++i) {
+        const size_t q = (size_t)sel[i];
+        parts.count[q] = counts[i];
+        parts.begin[q] = (int64_t)at + offsets[i];
+        parts.len[q] = offsets[i + 1] - offsets[i];
+    }
+}
+
+// The range passes of the sub-batch `sel` (masked by h->row_mask when `masked`): exactly what range_batch_impl runs for a call
+// of those queries, its ranked hits packed on the device and taken into `parts`.
+int range_rows(mlvdb_index* h, const float* queries, const std::vector<int32_t>& sel, float radius, int64_t cap_eff, bool masked,
+               RangeParts& parts) {
+    const int64_t m = (int64_t)sel.size();
+    const std::vector<float> q = pick_queries(queries, h->dim, sel);
+    auto call = [&]() -> int {
+        hipStream_t s = h->stream;
+        int rc = begin_call(h, s);
+        if (rc) return rc;
+        std::vector<int64_t> counts, offsets;
+        rc = range_ranked(h, s, q.data(), m, radius, cap_eff, counts, offsets);
+        if (rc) return rc;
+        const int64_t* pl = nullptr;
+        const float* pd = nullptr;
+        if (offsets[(size_t)m] > 0) {
+            rc = pack_range_hits(h, s, m, cap_eff, offsets, nullptr, nullptr, &pl, &pd);
+            if (rc) return rc;
+        }
+        take_hits(parts, sel, counts, offsets, pl, pd);
+        return end_call(h, s);
+    };
+    return masked ? with_row_mask(h, m, call) : call();
+}
+
+// The GATHER route of a range call for the programs `gp`: label lists, tiles, then per group of 256 gathered queries (the
+// ranking kernel's workspace holds 256 hit lists) the gathered range kernel and range_rank_kernel; one synchronisation reads
+// the exact counts back.  A query with more hits than its list holds (> kCandCap) gets nothing here: it is appended to
+// redo[its program] for the SCAN route.
+int gather_range_programs(mlvdb_index* h, const float* queries, float radius, int64_t cap_eff, int32_t qt, const EachSegs& sg,
+                          int32_t n_programs, const std::vector<int32_t>& gp, const std::vector<std::vector<int32_t>>& qof,
+                          const int64_t* matches, RangeParts& parts, std::vector<std::vector<int32_t>>& redo) {
+    hipStream_t s = h->stream;
+    std::vector<int64_t> base(kWhereEachMaxPrograms, 0);
+    std::vector<int32_t> sel, prog_of_sel;  // the gathered queries, sorted by program (positions of the prepared batch)
+    std::vector<GatherTile> tiles;
+    unsigned long long gmask = 0;
+    int64_t nlab = 0, max_m = 0;
+    for (int32_t p : gp) {
+        gmask |= 1ull << p;
+        base[p] = nlab;
+        const std::vector<int32_t>& qs = qof[p];
+        for (size_t t0 = 0; t0 < qs.size();) {  // (no tile straddles two 256-query groups)
+            const size_t pos = sel.size() + t0;
+            GatherTile t;
+            t.lab_begin = (int32_t)nlab;
+            t.lab_count = (int32_t)matches[p];
+            t.sel0 = (int32_t)pos;
+            t.nsel = (int32_t)std::min<size_t>({(size_t)qt, qs.size() - t0, kFilterQueries - pos % kFilterQueries});
+            tiles.push_back(t);
+            t0 += (size_t)t.nsel;
+        }
+        sel.insert(sel.end(), qs.begin(), qs.end());
+        prog_of_sel.insert(prog_of_sel.end(), qs.size(), p);
+        nlab += matches[p];
+        max_m = std::max(max_m, matches[p]);
+    }
+    const int64_t ng = (int64_t)sel.size();
+    const int64_t per_group = std::min<int64_t>((int64_t)tiles.size(), kFilterQueries);  // (at most: tiles of a full group)
+    // chunks per tile as the gathered kNN cuts them: enough blocks to fill the chip (~2048), none shorter than 64 rows
+    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>({64, (2048 + per_group - 1) / per_group, (max_m + 63) / 64}));
+    HIP_TRY(h, h->each_lab.ensure((size_t)nlab * sizeof(int32_t)));
+    HIP_TRY(h, hipMemcpyAsync(h->each_tot.as<int64_t>() + kWhereEachMaxPrograms, base.data(), base.size() * sizeof(int64_t),
+                              hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_where_each_scatter(h->each_bits.as<unsigned long long>(), h->total, sg.seg_rows, sg.nseg, n_programs,
+                                         h->each_seg.as<uint32_t>(), gmask, h->each_tot.as<int64_t>() + kWhereEachMaxPrograms,
+                                         h->each_lab.as<int32_t>(), s));
+    const std::vector<float> q = pick_queries(queries, h->dim, sel);
+    HIP_TRY(h, h->each_q.ensure(q.size() * sizeof(float)));
+    HIP_TRY(h, h->each_qpad.ensure((size_t)ng * h->ld * sizeof(float)));
+    HIP_TRY(h, h->each_qaux.ensure((size_t)ng * sizeof(double)));
+    HIP_TRY(h, h->each_tiles.ensure(tiles.size() * sizeof(GatherTile)));
+    HIP_TRY(h, hipMemcpyAsync(h->each_q.p, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->each_tiles.p, tiles.data(), tiles.size() * sizeof(GatherTile), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_query_prep(h->each_q.as<float>(), (int32_t)ng, h->dim, h->ld, h->space, h->each_qpad.as<float>(),
+                                 h->each_qaux.as<double>(), nullptr, s));
+    // the ranking kernel's workspace (what setup_filter_ws gives a range pass, without the candidate lists) and outputs
+    {
+        const void* before = h->fmisc.p;
+        HIP_TRY(h, h->fmisc.ensure(9 * kFilterQueries * sizeof(uint32_t)));
+        if (h->fmisc.p != before) h->sqmin_fresh = true;
+    }
+    HIP_TRY(h, h->rhits.ensure((size_t)kFilterQueries * kCandCap * sizeof(RangeHit)));
+    HIP_TRY(h, h->rhit_cnt.ensure(kFilterQueries * sizeof(uint32_t)));
+    HIP_TRY(h, h->io_lab.ensure((size_t)ng * cap_eff * sizeof(int64_t)));
+    HIP_TRY(h, h->io_dist.ensure((size_t)ng * cap_eff * sizeof(float)));
+    HIP_TRY(h, h->io_cnt.ensure((size_t)ng * sizeof(int64_t)));
+    HIP_TRY(h, h->pin_in.ensure(((size_t)ng + 1) * sizeof(int64_t)));  // (pack_range_hits stages the offsets there)
+    HIP_TRY(h, h->pin_out.ensure((size_t)ng * sizeof(int64_t)));
+    FilterArgs fa{};
+    fa.cnt = h->fmisc.as<uint32_t>() + 2 * kFilterQueries;
+    fa.overflow = h->fmisc.as<uint32_t>() + 3 * kFilterQueries;
+    fa.rhits = h->rhits.as<RangeHit>();
+    fa.rhit_cnt = h->rhit_cnt.as<uint32_t>();
+    size_t t_lo = 0;
+    for (int64_t g0 = 0; g0 < ng; g0 += kFilterQueries) {
+        fa.nq = (int32_t)std::min<int64_t>(kFilterQueries, ng - g0);
+        size_t t_hi = t_lo;
+        while (t_hi < tiles.size() && tiles[t_hi].sel0 < g0 + kFilterQueries) ++t_hi;
+        HIP_TRY(h, hipMemsetAsync(fa.rhit_cnt, 0, kFilterQueries * sizeof(uint32_t), s));
+        HIP_TRY(h, hipMemsetAsync(fa.overflow, 0, kFilterQueries * sizeof(uint32_t), s));
+        HIP_TRY(h, launch_where_gather_range(h->X, h->each_qpad.as<float>(), h->each_qaux.as<double>(), h->each_lab.as<int32_t>(),
+                                             h->each_tiles.as<GatherTile>() + t_lo, (int32_t)(t_hi - t_lo), h->ld, h->space, qt,
+                                             (int32_t)nchunk, radius, (int32_t)g0, fa.rhits, fa.rhit_cnt, s));
+        HIP_TRY(h, launch_range_rank(fa, (int32_t)g0, cap_eff, h->io_lab.as<int64_t>(), h->io_dist.as<float>(),
+                                     h->io_cnt.as<int64_t>(), s));
+        t_lo = t_hi;
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, hipMemcpyAsync(h->pin_out.p, h->io_cnt.p, (size_t)ng * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    const std::vector<int64_t> counts(static_cast<const int64_t*>(h->pin_out.p), static_cast<const int64_t*>(h->pin_out.p) + ng);
+    std::vector<int64_t> offsets((size_t)ng + 1, 0);
+    int64_t n_redo = 0;
+    for (int64_t i = 0; i < ng; ++i) {
+        const bool flagged = counts[(size_t)i] > kCandCap;  // (the ranking kernel wrote none of its hits)
+        if (flagged) {
+            redo[(size_t)prog_of_sel[(size_t)i]].push_back(sel[(size_t)i]);
+            ++n_redo;
+        }
+        offsets[(size_t)i + 1] = offsets[(size_t)i] + (flagged ? 0 : std::min<int64_t>(counts[(size_t)i], cap_eff));
+    }
+    h->stats.fallback_queries += n_redo;
+    const int64_t* pl = nullptr;
+    const float* pd = nullptr;
+    if (offsets[(size_t)ng] > 0) {
+        int rc = pack_range_hits(h, s, ng, cap_eff, offsets, nullptr, nullptr, &pl, &pd);
+        if (rc) return rc;
+    }
+    take_hits(parts, sel, counts, offsets, pl, pd);
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_range_batch_packed_where_each(mlvdb_index* h, const float* queries, int64_t nq, float radius, int64_t capacity,
+                                        int64_t total_capacity, const mlvdb_where* programs, int32_t n_programs,
+                                        const int32_t* program_of_query, int64_t* out_labels, float* out_dist,
+                                        int64_t* out_offsets, int64_t* out_counts, int32_t* out_routes) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched: the range arguments as range_batch_impl checks them, the programs
+    // as mlvdb_search_batch_where_each does
+    if (!out_offsets) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
+    if (total_capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "total_capacity must be >= 0");
+    EachPrograms pk;
+    if ((rc = where_each_pack(h, programs, n_programs, pk))) return rc;
+    if (nq > 0 && (!queries || !program_of_query || !out_counts || ((!out_labels || !out_dist) && total_capacity > 0)))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    std::vector<std::vector<int32_t>> qof((size_t)n_programs);  // each program's queries, ascending
+    std::vector<int32_t> plain;                                  // the unfiltered ones
+    for (int64_t i = 0; i < nq; ++i) {
+        const int32_t p = program_of_query[i];
+        if (p < -1 || p >= n_programs) return fail(h, MLVDB_ERR_INVALID_ARG, "program_of_query entry outside [-1, n_programs)");
+        (p < 0 ? plain : qof[(size_t)p]).push_back((int32_t)i);
+    }
+    std::vector<int32_t> routes((size_t)n_programs, MLVDB_WHERE_ROUTE_NONE);
+    RangeParts parts;
+    parts.count.assign((size_t)nq, 0);
+    parts.begin.assign((size_t)nq, 0);
+    parts.len.assign((size_t)nq, 0);
+    const int64_t cap_eff = std::min<int64_t>(capacity, MLVDB_MAX_TOPK_PAGED);  // most hits returned per query
+    if (nq > 0 && h->total > h->deleted) {
+        std::vector<int64_t> matches((size_t)n_programs, 0);
+        const EachSegs sg = each_segments(h->total);
+        bool any = false;
+        for (const auto& qs : qof) any = any || !qs.empty();
+        if (any) {
+            rc = where_each_eval(h, pk, sg, matches.data());
+            if (rc) return rc;
+        }
+        // routes: the rule of mlvdb_search_batch_where_each without its bound on k
+        int32_t qt = kGatherQT;
+        while (qt > 1 && where_gather_lds(qt, h->ld) > 64 * 1024) qt >>= 1;
+        const bool gather_fits = where_gather_lds(qt, h->ld) <= 64 * 1024;
+        const __int128 live = h->total - h->deleted;
+        std::vector<int32_t> gp, sp;
+        int64_t nlab = 0;
+        for (int32_t p = 0; p < n_programs; ++p) {
+            const size_t nqp = qof[(size_t)p].size();
+            if (nqp == 0 || matches[(size_t)p] == 0) continue;
+            const __int128 tiles = (__int128)((nqp + qt - 1) / qt);
+            const bool gather = gather_fits && (__int128)matches[(size_t)p] * tiles * 1000 <= live * h->tn.where_gather &&
+                                nlab + matches[(size_t)p] <= INT32_MAX;
+            if (gather) nlab += matches[(size_t)p];
+            routes[(size_t)p] = gather ? MLVDB_WHERE_ROUTE_GATHER : MLVDB_WHERE_ROUTE_SCAN;
+            (gather ? gp : sp).push_back(p);
+        }
+        // GATHER; the queries whose hits its lists could not hold join the SCAN route of their program
+        std::vector<std::vector<int32_t>> redo((size_t)n_programs);
+        if (!gp.empty()) {
+            rc = gather_range_programs(h, queries, radius, cap_eff, qt, sg, n_programs, gp, qof, matches.data(), parts, redo);
+            if (rc) return rc;
+        }
+        // SCAN: the program's row mask out of its bit, then exactly the masked passes of mlvdb_range_batch_packed_where
+        for (int32_t p = 0; p < n_programs; ++p) {
+            const std::vector<int32_t>& qs = routes[(size_t)p] == MLVDB_WHERE_ROUTE_SCAN ? qof[(size_t)p] : redo[(size_t)p];
+            if (qs.empty()) continue;
+            HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
+            HIP_TRY(h, launch_where_each_expand(h->each_bits.as<unsigned long long>(), p, h->total, h->row_mask.as<uint8_t>(),
+                                                h->stream));
+            rc = range_rows(h, queries, qs, radius, cap_eff, true, parts);
+            if (rc) return rc;
+        }
+        if (!plain.empty()) {
+            rc = range_rows(h, queries, plain, radius, cap_eff, false, parts);
+            if (rc) return rc;
+        }
+    }
+    if (out_routes)
+        for (int32_t p = 0; p < n_programs; ++p) out_routes[p] = routes[(size_t)p];
+    // the packed output, once for the whole call, under the rules of range_batch_impl
+    out_offsets[0] = 0;
+    bool over = false, hard = false;
+    for (int64_t i = 0; i < nq; ++i) {
+        out_offsets[i + 1] = out_offsets[i] + parts.len[(size_t)i];
+        out_counts[i] = parts.count[(size_t)i];
+        over |= parts.count[(size_t)i] > capacity;
+        hard |= parts.count[(size_t)i] > cap_eff && capacity > cap_eff;
+    }
+    if (out_offsets[nq] > total_capacity)
+        return fail(h, MLVDB_ERR_OVERFLOW, "range query: more hits in all than total_capacity; out_counts / out_offsets hold "
+                                           "the exact counts and the layout the hits need, out_labels / out_dist nothing");
+    for (int64_t i = 0; i < nq; ++i) {
+        const size_t n = (size_t)parts.len[(size_t)i];
+        if (n == 0) continue;
+        std::memcpy(out_labels + out_offsets[i], parts.lab.data() + parts.begin[(size_t)i], n * sizeof(int64_t));
+        std::memcpy(out_dist + out_offsets[i], parts.dist.data() + parts.begin[(size_t)i], n * sizeof(float));
+    }
+    if (hard)
+        return fail(h, MLVDB_ERR_UNSUPPORTED,
+                    "range query: a query has more than MLVDB_MAX_TOPK_PAGED hits; out_counts holds the exact counts, the "
+                    "outputs the nearest MLVDB_MAX_TOPK_PAGED");
+    if (over) return fail(h, MLVDB_ERR_OVERFLOW, "some query has more hits than `capacity`; out_counts holds the exact counts");
     return MLVDB_OK;
     });
 }

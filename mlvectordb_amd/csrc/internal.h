@@ -10,6 +10,7 @@
 #include "../../include/mlvdb_hip.h"
 #include "../../include/mlvdb_where.h"
 #include "../../include/mlvdb_where_each.h"
+#include "../../include/mlvdb_where_each_range.h"
 #include "layout.h"
 #include "wave_topk.h"
 
@@ -262,6 +263,10 @@ hipError_t launch_filter_range_thr(const FilterArgs& a, float radius, hipStream_
 hipError_t launch_exact_range_scan(const FilterArgs& a, float radius, const int32_t* qsel, int32_t nsel, hipStream_t s);
 hipError_t launch_range_rescore(const FilterArgs& a, float radius, int32_t q0, int64_t capacity, int64_t* out_labels,
                                 float* out_dist, int64_t* out_counts, hipStream_t s);
+// the ranking alone, over hit arrays another kernel filled (a.rhits / a.rhit_cnt / a.overflow of a.nq <= 256 queries; range
+// mode): ranked hits and exact counts at rows q0.. of the outputs; more than kCandCap hits flag the query (overflow = 2)
+hipError_t launch_range_rank(const FilterArgs& a, int32_t q0, int64_t capacity, int64_t* out_labels, float* out_dist,
+                             int64_t* out_counts, hipStream_t s);
 // The dense pass alone: every (query, row) bound of rows [0, rows) -> slot `row` of the query's list (rows a multiple of 128,
 // <= a.cand_cap).  launch_filter_seed_scan = this + the first refine / update; big-k passes seed up to 65,280 rows with it.
 hipError_t launch_filter_dense_scan(const FilterArgs& a, int64_t rows, hipStream_t s);
@@ -339,5 +344,12 @@ size_t where_gather_lds(int32_t qt, int32_t ld);
 hipError_t launch_where_gather(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
                                const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t space, int32_t qt, int32_t k,
                                int32_t nchunk, TopEntry* partial, hipStream_t s);
+// The gathered range kernel: the tiles' queries (positions q_base .. q_base + 255 of the sorted query list) against their
+// programs' label lists; every hit (fp64 distance <= radius) is counted in rhit_cnt[sel - q_base] (exact, whatever the list
+// holds) and the first kCandCap of a query stored in rhits[(sel - q_base) * kCandCap ..] -- the input of launch_range_rank.
+hipError_t launch_where_gather_range(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
+                                     const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t space, int32_t qt,
+                                     int32_t nchunk, float radius, int32_t q_base, RangeHit* rhits, uint32_t* rhit_cnt,
+                                     hipStream_t s);
 
 }  // namespace mlvdb

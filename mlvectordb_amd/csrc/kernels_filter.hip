@@ -2809,11 +2809,26 @@ hipError_t launch_filter_rescore(const FilterArgs& a, int32_t k, int32_t q0, int
     return hipGetLastError();
 }
 
+// The ranking kernel over the hit arrays as they stand (a.rhits / a.rhit_cnt of the pass's a.nq queries).
+static hipError_t launch_rank(const FilterArgs& a, int32_t q0, int64_t capacity, int64_t* out_labels, float* out_dist,
+                              int64_t* out_counts, const KnnOut& knn, hipStream_t s) {
+    const size_t lds_sort = (size_t)kCandCap * (sizeof(double) + sizeof(int32_t));  // the ranking kernel's {d[], l[]} (kCandCap % 64 == 0)
+    static std::atomic<uint64_t> rank_configured{0};
+    hipError_t e = ensure_dynamic_lds(rank_configured, reinterpret_cast<const void*>(range_rank_kernel), (int)lds_sort);
+    if (e != hipSuccess) return e;
+    range_rank_kernel<<<kRankGrid, kRankThreads, lds_sort, s>>>(a, q0, capacity, out_labels, out_dist, out_counts, knn);
+    return hipGetLastError();
+}
+
+hipError_t launch_range_rank(const FilterArgs& a, int32_t q0, int64_t capacity, int64_t* out_labels, float* out_dist,
+                             int64_t* out_counts, hipStream_t s) {
+    return launch_rank(a, q0, capacity, out_labels, out_dist, out_counts, KnnOut{}, s);
+}
+
 // Exact fp64 distance of every list entry -- the hits (dist <= radius, live) go to the query's hit array -- then the ranking
 // kernel: range results (knn.k == 0) or the k nearest.
 static hipError_t launch_score_rank(const FilterArgs& a, float radius, int32_t q0, int64_t capacity, int64_t* out_labels,
                                     float* out_dist, int64_t* out_counts, const KnnOut& knn, hipStream_t s) {
-    const size_t lds_sort = (size_t)kCandCap * (sizeof(double) + sizeof(int32_t));  // the ranking kernel's {d[], l[]} (kCandCap % 64 == 0)
     hipError_t e = hipMemsetAsync(a.rhit_cnt, 0, kFilterQueries * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     int waves = kRescoreWaves;
@@ -2821,14 +2836,11 @@ static hipError_t launch_score_rank(const FilterArgs& a, float radius, int32_t q
     const size_t lds_score = std::max((size_t)waves * a.ld * sizeof(double), (size_t)96 * 1024);
     auto kern = a.space == kSpaceL2 ? range_score_flat_kernel<kSpaceL2>
                 : a.space == kSpaceCosine ? range_score_flat_kernel<kSpaceCosine> : range_score_flat_kernel<kSpaceIp>;
-    static std::atomic<uint64_t> score_configured[3], rank_configured{0};
+    static std::atomic<uint64_t> score_configured[3];
     if ((e = ensure_dynamic_lds(score_configured[a.space], reinterpret_cast<const void*>(kern), 144 * 1024)) != hipSuccess) return e;
     kern<<<kRescoreGrid, waves * 64, lds_score, s>>>(a, radius);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = ensure_dynamic_lds(rank_configured, reinterpret_cast<const void*>(range_rank_kernel), (int)lds_sort)) != hipSuccess)
-        return e;
-    range_rank_kernel<<<kRankGrid, kRankThreads, lds_sort, s>>>(a, q0, capacity, out_labels, out_dist, out_counts, knn);
-    return hipGetLastError();
+    return launch_rank(a, q0, capacity, out_labels, out_dist, out_counts, knn, s);
 }
 
 hipError_t launch_range_rescore(const FilterArgs& a, float radius, int32_t q0, int64_t capacity, int64_t* out_labels,

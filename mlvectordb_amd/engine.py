@@ -71,6 +71,26 @@ class RangeHits(Sequence):
         return self.labels[a:b], self.dist[a:b]
 
 
+def stitch_range_hits(parts, nq: int) -> RangeHits:
+    """The packed answers of several calls, each over a subset of a batch's queries -- ``parts`` = [(query indices,
+    labels, dist, offsets), ...], every query of the batch in exactly one part -- as one ``RangeHits`` in query order."""
+    if len(parts) == 1 and np.array_equal(parts[0][0], np.arange(nq)):
+        return RangeHits(*parts[0][1:])
+    lens = np.zeros(nq, dtype=np.int64)
+    for idx, _, _, off in parts:
+        lens[idx] = np.diff(off)
+    offsets = np.zeros(nq + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    labels = np.empty(int(offsets[-1]), dtype=np.int64)
+    dist = np.empty(int(offsets[-1]), dtype=np.float32)
+    for idx, lab, dst, off in parts:
+        for j, i in enumerate(idx.tolist()):
+            a, b = int(off[j]), int(off[j + 1])
+            labels[offsets[i]:offsets[i] + b - a] = lab[a:b]
+            dist[offsets[i]:offsets[i] + b - a] = dst[a:b]
+    return RangeHits(labels, dist, offsets)
+
+
 class HipScanEngine:
     """Exhaustive fp32 corpus scan on one MI355X, through the C ABI."""
 
@@ -367,23 +387,32 @@ class HipScanEngine:
         if queries.ndim != 2 or queries.shape[1] != self.dim:
             raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
         nq = queries.shape[0]
+        w, keep = self._where(where) if where is not None else (None, None)
+
+        def call(capacity, total, labels, dist, offsets, counts):
+            if w is None:
+                return self._lib.mlvdb_range_batch_packed(self._h, queries.ctypes.data, nq, float(radius), capacity, total,
+                                                          labels.ctypes.data, dist.ctypes.data, offsets.ctypes.data,
+                                                          counts.ctypes.data)
+            return self._lib.mlvdb_range_batch_packed_where(self._h, queries.ctypes.data, nq, float(radius), capacity, total,
+                                                            C.byref(w), labels.ctypes.data, dist.ctypes.data,
+                                                            offsets.ctypes.data, counts.ctypes.data)
+
+        return RangeHits(*self._range_packed(call, nq, capacity, truncate))
+
+    def _range_packed(self, call, nq: int, capacity: int, truncate: bool):
+        """The protocol of the packed range entries: a first guess of ``total_capacity`` (room for 256 hits per query on
+        average) and one repeat with the sizes the first call reported.  ``call(capacity, total, labels, dist, offsets,
+        counts)`` -> status.  Returns (labels, dist, offsets)."""
         capacity = max(1, min(int(capacity), _native.MAX_TOPK_PAGED))
         total = min(nq * capacity, max(65_536, 256 * nq))
-        w, keep = self._where(where) if where is not None else (None, None)
         while True:
             labels = np.empty(total, dtype=np.int64)
             dist = np.empty(total, dtype=np.float32)
             offsets = np.zeros(nq + 1, dtype=np.int64)
             counts = np.zeros(nq, dtype=np.int64)
-            if w is None:
-                rc = self._lib.mlvdb_range_batch_packed(self._h, queries.ctypes.data, nq, float(radius), capacity, total,
-                                                        labels.ctypes.data, dist.ctypes.data, offsets.ctypes.data,
-                                                        counts.ctypes.data)
-            else:
-                rc = self._lib.mlvdb_range_batch_packed_where(self._h, queries.ctypes.data, nq, float(radius), capacity, total,
-                                                              C.byref(w), labels.ctypes.data, dist.ctypes.data,
-                                                              offsets.ctypes.data, counts.ctypes.data)
-            rc = self._check(rc, "range_batch_packed", allow=(_native.ERR_OVERFLOW,))
+            rc = self._check(call(capacity, total, labels, dist, offsets, counts), "range_batch_packed",
+                             allow=(_native.ERR_OVERFLOW,))
             if rc == _native.OK:
                 break
             need_cap = capacity if truncate else min(max(int(counts.max(initial=0)), capacity), _native.MAX_TOPK_PAGED)
@@ -391,7 +420,43 @@ class HipScanEngine:
             if need_cap == capacity and need_total <= total:
                 break  # per-query truncation was asked for (or the engine's limit reached): the outputs hold the nearest
             capacity, total = need_cap, max(need_total, 1)
-        return RangeHits(labels, dist, offsets)
+        return labels, dist, offsets
+
+    def range_each(self, queries: np.ndarray, radius: float, capacity: int, programs, program_of_query,
+                   truncate: bool = False, return_routes: bool = False):
+        """Range search with a filter per query: query i's hits are the rows ``programs[program_of_query[i]]`` matches (-1:
+        all rows) within ``radius``.  Returns what ``range`` returns (``RangeHits``), each query's hits bit-identical to a
+        ``range(..., where=program)`` call for it alone; ``return_routes=True`` -> (hits, int32 array with each program's
+        route, ``_native.ROUTE_*``).  One native call per chunk of at most 64 programs / 1024 ops
+        (``where.chunk_programs``), each with ``range``'s protocol for ``total_capacity``; the chunks' answers are
+        stitched in query order."""
+        from .where import chunk_programs
+
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        of = np.ascontiguousarray(program_of_query, dtype=np.int32)
+        nq = queries.shape[0]
+        if of.shape != (nq,):
+            raise RuntimeError(f"program_of_query: {of.shape}, expected ({nq},)")
+        routes = np.zeros(len(programs), dtype=np.int32)
+        parts = []
+        start = 0
+        for idx, chunk, local in chunk_programs(list(programs), of):
+            q = np.ascontiguousarray(queries[idx])
+            rts = np.zeros(max(len(chunk), 1), dtype=np.int32)
+            arr, keep = self._where_array(chunk)
+
+            def call(capacity, total, labels, dist, offsets, counts):
+                return self._lib.mlvdb_range_batch_packed_where_each(
+                    self._h, q.ctypes.data, idx.size, float(radius), capacity, total, arr, len(chunk), local.ctypes.data,
+                    labels.ctypes.data, dist.ctypes.data, offsets.ctypes.data, counts.ctypes.data, rts.ctypes.data)
+
+            parts.append((idx,) + self._range_packed(call, idx.size, capacity, truncate))
+            routes[start:start + len(chunk)] = rts[:len(chunk)]
+            start += len(chunk)
+        hits = stitch_range_hits(parts, nq)
+        return (hits, routes) if return_routes else hits
 
     def close(self) -> None:
         if getattr(self, "_h", None):

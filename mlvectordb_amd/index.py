@@ -612,25 +612,40 @@ class Index:
         return ns.ids.uuids_at(ns.engine.where_labels(program)).tolist()
 
     def range_search_many(self, queries, radius: float, namespace: str, metric: str,
-                          max_results: int = 1024, where: Optional[Mapping] = None) -> List[List[SearchResult]]:
+                          max_results: int = 1024, where=None) -> List[List[SearchResult]]:
         """The live rows within ``radius`` of each query, nearest first (ties by insertion order), at most
         ``max_results`` per query (the nearest ones; ``None`` = all, up to the engine's 16384 per query).
 
         ``radius`` is a distance in the namespace's space (squared for l2; plain for
         ``metric="euclidean"``); scores are post-processed exactly like ``search``.
         No reference implementation exists for range queries (README prose only).  ``where``: a dict filter over the
-        declared attributes (where.py), evaluated on the device.
+        declared attributes (where.py), evaluated on the device; a list or tuple of ``nq`` entries, each a dict filter or
+        ``None`` (unfiltered), gives every query its own filter (one batched call, include/mlvdb_where_each_range.h): each
+        query's answer is what a single-dict call for it alone returns.
         """
-        program = None if where is None else self._compile(namespace, where)
+        programs = of = program = None
         q = self._coerce_queries(queries)
         nq = q.shape[0]
+        if isinstance(where, (list, tuple)):
+            if len(where) != nq:
+                raise ValueError(f"range_search_many: {len(where)} per-query filters for {nq} queries")
+            programs, of = self._compile_each(namespace, where)
+        elif where is not None:
+            program = self._compile(namespace, where)
         ns = self._ns.get(namespace)
         if ns is None or ns.total - ns.deleted <= 0 or nq == 0 or q.shape[1] != ns.dim:
             return [[] for _ in range(nq)]
         native_radius = float(radius) ** 2 if metric == "euclidean" else float(radius)
         cap = self._MAX_TOP_K if max_results is None else max(1, int(max_results))
-        per_query = (ns.engine.range(q, native_radius, cap, truncate=True) if program is None
-                     else ns.engine.range(q, native_radius, cap, truncate=True, where=program))
+        if programs:
+            range_each = getattr(ns.engine, "range_each", None)
+            if range_each is None:
+                raise ValueError("per-query filters need an engine with range_each (a single-device namespace)")
+            per_query = range_each(q, native_radius, cap, programs, of, truncate=True)
+        elif program is None:
+            per_query = ns.engine.range(q, native_radius, cap, truncate=True)
+        else:
+            per_query = ns.engine.range(q, native_radius, cap, truncate=True, where=program)
         out: List[List[SearchResult]] = []
         for labels, dist in per_query:
             uids = ns.ids.uuids_at(labels).tolist()

@@ -169,12 +169,37 @@ class QueryProcessor:
             hits = self._index.range_search(query, radius, namespace=namespace, metric=metric, max_results=None)
             out = [h for h in self._enrich(hits, namespace) if where(h["metadata"])]
             out = out if max_results is None else out[:max(1, int(max_results))]
+        return self._fill_values(out, namespace)
+
+    def _fill_values(self, out: List[dict], namespace: str) -> List[dict]:
         missing = [i for i, h in enumerate(out) if h["values"] is None]  # array storage that keeps the rows in HBM only
         if missing and hasattr(self._index, "fetch_values_by_id"):
             rows = self._index.fetch_values_by_id(namespace, [out[i]["id"] for i in missing])
             for i, r in zip(missing, rows):
                 out[i]["values"] = r
         return out
+
+    def find_in_radius_many(self, queries, radius: float, namespace: str = "default", metric: str = "cosine",
+                            max_results: int = 1024, where=None) -> List[List[dict]]:
+        """Batched ``find_in_radius``: ``queries`` is an [nq, dim] array or a sequence of VectorDTO, one ``radius`` for all.
+        ``where`` as in ``find_similar_many``: a dict filter, or a list of ``nq`` entries, each a dict filter or ``None`` --
+        every query its own filter, all evaluated on the device in one batched call (``Index.range_search_many``); a
+        predicate filters every query's hits by their stored metadata, and inside the list it is a ``ValueError``."""
+        if isinstance(where, (list, tuple)):
+            if any(w is not None and not isinstance(w, Mapping) for w in where):
+                raise ValueError("per-query where entries must be dict filters or None (per-query predicates have no host path)")
+            where = list(where)
+        if where is None or isinstance(where, (Mapping, list)):
+            kw = {} if where is None else {"where": where}
+            per_query = self._index.range_search_many(queries, radius, namespace=namespace, metric=metric,
+                                                      max_results=max_results, **kw)
+            out = [self._enrich(hits, namespace) for hits in per_query]
+        else:
+            per_query = self._index.range_search_many(queries, radius, namespace=namespace, metric=metric, max_results=None)
+            out = [[h for h in self._enrich(hits, namespace) if where(h["metadata"])] for hits in per_query]
+            if max_results is not None:
+                out = [hits[:max(1, int(max_results))] for hits in out]
+        return [self._fill_values(hits, namespace) for hits in out]
 
     # ---- additive: metadata queries (README.md:252,274: StorageEngine.query_by_metadata; no reference code)
     def count_where(self, where, namespace: str = "default") -> int:
