@@ -144,9 +144,10 @@ namespace {
 
 int fail(mlvdb_index* h, int code, const char* what, hipError_t e = hipSuccess) {
     char buf[512];
-    if (e != hipSuccess)
+    if (e != hipSuccess) {
         snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    else
+        (void)hipGetLastError();  // reported here: the next launch's hipGetLastError() must not find it again
+    } else
         snprintf(buf, sizeof buf, "%s", what);
     if (h)
         h->err = buf;
@@ -960,9 +961,12 @@ __global__ void range_pack_kernel(const int64_t* lab, const float* dist, const i
 }
 
 __global__ void range_reset_kernel(uint32_t* cnt, const int32_t* qsel) { cnt[qsel[threadIdx.x]] = 0; }
-__global__ void range_resolve_kernel(uint32_t* overflow, const uint32_t* cnt, const int32_t* qsel, uint32_t cap) {
+// (thr: a resolved list holds exact hits with u = 0, so the mid pruning must keep every entry whatever threshold the scan had --
+// an l2 query that filter_l2_offsets_kernel took off the filter carries +inf, which dropped all of its hits)
+__global__ void range_resolve_kernel(uint32_t* overflow, float* thr, const uint32_t* cnt, const int32_t* qsel, uint32_t cap) {
     const int q = qsel[threadIdx.x];
     overflow[q] = cnt[q] > cap ? 1u : 0u;
+    thr[q] = -3.4e38f;
 }
 
 // (l2: the int8 bodies are the l2c ones -- folded test, per-row integer offsets read through the row pairs' descriptor, which needs
@@ -1720,7 +1724,7 @@ static int range_ranked(mlvdb_index* h, hipStream_t s, const float* queries, int
             range_reset_kernel<<<1, n_flagged, 0, s>>>(fa.cnt, qsel);
             HIP_TRY(h, hipGetLastError());
             HIP_TRY(h, launch_exact_range_scan(fa, radius, qsel, n_flagged, s));
-            range_resolve_kernel<<<1, n_flagged, 0, s>>>(fa.overflow, fa.cnt, qsel, (uint32_t)fa.cand_cap);
+            range_resolve_kernel<<<1, n_flagged, 0, s>>>(fa.overflow, fa.thr, fa.cnt, qsel, (uint32_t)fa.cand_cap);
             HIP_TRY(h, hipGetLastError());
         }
         // mid bounds first (round 4): the int8 band admits ~8x the hits; a pass over the candidates' fp16 rows (whole 128-byte

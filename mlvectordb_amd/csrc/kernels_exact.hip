@@ -161,11 +161,12 @@ __global__ __launch_bounds__(256) void exact_merge_kernel(const TopEntry* __rest
 }
 
 // Range-query candidate generator: same scan, but every live row with dist <= radius is
-// appended to its query's candidate list (rescored and sorted by range_rescore_kernel).
-template <int SPACE>
+// appended to its query's candidate list (rescored and sorted by range_rescore_kernel).  QT queries per block, their fp64
+// image [QT][ld] in LDS: launch_exact_range_scan picks 4 / 2 / 1 by the row width.
+template <int SPACE, int QT>
 __global__ __launch_bounds__(512) void exact_range_kernel(const FilterArgs a, const double radius, const int nblk,
                                                           const int32_t* qsel, const int32_t nsel) {
-    constexpr int QT = 4, PW = 2, NW = 8;
+    constexpr int PW = 2, NW = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
     const int lane = threadIdx.x & 63;
@@ -228,17 +229,21 @@ __global__ __launch_bounds__(512) void exact_range_kernel(const FilterArgs a, co
 hipError_t launch_exact_range_scan(const FilterArgs& a, float radius, const int32_t* qsel, int32_t nsel, hipStream_t s) {
     if (!qsel) nsel = a.nq;
     if (nsel <= 0) return hipSuccess;
-    const int nqtiles = (nsel + 3) / 4;
+    // the query tile halves until its fp64 image fits 64 KiB of LDS, as plan_exact's does: 4 queries up to ld = 2048, 2 up to
+    // 4096, 1 beyond (ld <= 8192).  Four queries of an ld > 5120 would ask for more LDS than a CU has (160 KiB).
+    int qt = 4;
+    while (qt > 1 && (size_t)qt * a.ld * sizeof(double) > 64 * 1024) qt >>= 1;
+    const int nqtiles = (nsel + qt - 1) / qt;
     const int64_t ntasks = ((a.total + 15) / 16 + 1) / 2;
     int64_t nblk = (ntasks + 7) / 8;
     const int64_t cap = std::max<int64_t>(8, 1024 / nqtiles);
     if (nblk > cap) nblk = cap;
     if (nblk < 1) nblk = 1;
-    const size_t lds = (size_t)4 * a.ld * sizeof(double);
+    const size_t lds = (size_t)qt * a.ld * sizeof(double);
     hipError_t e = hipSuccess;
 #define MLVDB_LAUNCH_ER(SP)                                                                                      \
     do {                                                                                                         \
-        auto kern = exact_range_kernel<SP>;                                                                      \
+        auto kern = qt == 4 ? exact_range_kernel<SP, 4> : qt == 2 ? exact_range_kernel<SP, 2> : exact_range_kernel<SP, 1>; \
         if (lds > 48 * 1024)                                                                                     \
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                     (int)lds);                                                                   \

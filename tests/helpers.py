@@ -46,5 +46,29 @@ def assert_knn_matches(got, want, tag: str):
     assert err <= SCORE_ATOL, f"{tag}: max |distance error| {err}"
 
 
+def assert_range_matches(got, want, tag: str):
+    """Range hits ``got`` (a ``RangeHits`` or a list of (labels, distances) per query) against the oracle's ``want``: the
+    labels equal query by query, every distance within SCORE_ATOL * max(1, |d|) -- the 1e-5 bar, relative beyond 1 as in
+    tests/test_pairwise.py (fp32 holds 1e-5 absolute only up to ~100)."""
+    assert len(got) == len(want), f"{tag}: {len(got)} queries answered, {len(want)} asked"
+    for i, ((gl, gd), (wl, wd)) in enumerate(zip(got, want)):
+        gl, gd, wl, wd = np.asarray(gl), np.asarray(gd), np.asarray(wl), np.asarray(wd)
+        if not np.array_equal(gl, wl):
+            from tests.conftest import dump_mismatch
+
+            dump_mismatch(tag.replace("/", "_"), query=np.int64(i), got_labels=gl, want_labels=wl, got_dist=gd, want_dist=wd)
+            m = min(gl.size, wl.size)
+            at = int(np.argmax(gl[:m] != wl[:m])) if (gl[:m] != wl[:m]).any() else m
+            raise AssertionError(f"{tag}: query {i}: {gl.size} hits, the oracle has {wl.size}; first difference at rank {at}: "
+                                 f"got {gl[at:at + 4]} (d {gd[at:at + 4]}) want {wl[at:at + 4]} (d {wd[at:at + 4]})")
+        g64, w64 = gd.astype(np.float64), wd.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            err = np.where(g64 == w64, 0.0, np.abs(g64 - w64))  # (equal infinities: no error)
+        bad = ~(err <= SCORE_ATOL * np.maximum(1.0, np.abs(w64)))
+        if bad.any():
+            j = int(np.argmax(bad))
+            raise AssertionError(f"{tag}: query {i}: distance of label {wl[j]} is {gd[j]!r}, the oracle's {wd[j]!r}")
+
+
 def oracle_knn(qs, rows, k, space, deleted=None):
     return exact_scan.knn(qs, rows, k, space, deleted=deleted)
