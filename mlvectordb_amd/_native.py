@@ -110,6 +110,12 @@ WHERE_EACH_RANGE_SIGNATURES = {
                                                       C.c_int32, _P, _P, _P, _P, _P, _P]),
 }
 
+# include/mlvdb_distinct.h: the nearest row of each of the k nearest groups of an int64 attribute column
+DISTINCT_SIGNATURES = {
+    "mlvdb_search_batch_distinct": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(Where),
+                                              _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -139,7 +145,7 @@ def load() -> C.CDLL:
             f"There is no CPU fallback for the search path.")
     lib = C.CDLL(str(path))
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
-                                      **WHERE_EACH_RANGE_SIGNATURES}.items():
+                                      **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -114,6 +114,9 @@ struct mlvdb_index {
     // per-query filters (mlvdb_where_each.h): the call's programs, one 64-bit word per row, per-segment counts / offsets,
     // match totals, the gathered route's label lists, tiles, queries and outputs
     DevBuf each_prog, each_bits, each_seg, each_tot, each_lab, each_tiles, each_q, each_qpad, each_qaux, each_out;
+    // distinct kNN (mlvdb_distinct.h): a chunk's queries, its ranked lists from the plain search, its outputs, and the
+    // flagged queries' list + counter -- all sized by the chunk (<= kDistinctChunk queries), k and L, never by the corpus
+    DevBuf dist_q, dist_list, dist_out, dist_sel;
     // fp16 row-major shadow for the mid bounds (kernels_refine.hip): built lazily by the first range query / top_k > 64 search
     DevBuf x16, s16, rowerr16, picks, npicks;
     int64_t l2_rows = 0;      // rows [0, l2_rows) of the fp16 shadow are current (0 after compact / reset / regrowth)
@@ -1162,7 +1165,7 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     h->where_prog.release();
     h->where_cnt.release();
     for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
-                      &h->each_qpad, &h->each_qaux, &h->each_out})
+                      &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
@@ -2751,6 +2754,130 @@ int mlvdb_range_batch_packed_where_each(mlvdb_index* h, const float* queries, in
                     "outputs the nearest MLVDB_MAX_TOPK_PAGED");
     if (over) return fail(h, MLVDB_ERR_OVERFLOW, "some query has more hits than `capacity`; out_counts holds the exact counts");
     return MLVDB_OK;
+    });
+}
+
+extern "C++" {
+namespace {
+// ---- distinct-by-attribute kNN (mlvdb_distinct.h)
+constexpr int64_t kDistinctChunk = 1024;  // queries per round of list pass + pick + grouped scan (bounds the workspaces)
+
+// The validated call (h->rn is the masked copy when a program restricts the rows).  Per chunk of queries:
+// the plain device search for L neighbours -> the pick (final outputs of the complete queries, the others flagged) -> one
+// synchronisation for the flagged count -> the grouped exact scan + merge of the flagged queries -> outputs to the host.
+int distinct_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t attr, int64_t max_groups,
+                  int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64, int64_t* out_groups) {
+    hipStream_t s = h->stream;
+    const int32_t k_eff = max_groups > 0 ? (int32_t)std::min<int64_t>(k, max_groups) : k;
+    if (h->total == 0 || h->total == h->deleted) {
+        for (int64_t i = 0; i < nq * k; ++i) {
+            out_labels[i] = -1;
+            out_dist[i] = __builtin_inff();
+            if (out_dist64) out_dist64[i] = __builtin_inf();
+            if (out_groups) out_groups[i] = INT64_MIN;
+        }
+        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        return MLVDB_OK;
+    }
+    const int64_t* group = h->attr_col[attr];
+    const int32_t os = h->tn.distinct_oversample;
+    // k <= 64 costs the filter path what k = 64 does, hence the floor; 0: no list pass
+    const int32_t L = os > 0 ? (int32_t)std::min<int64_t>(kDistinctMaxList, std::max<int64_t>(64, (int64_t)os * k)) : 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += kDistinctChunk) {
+        const int32_t n = (int32_t)std::min<int64_t>(kDistinctChunk, nq - q0);
+        const size_t nk = (size_t)n * k;
+        HIP_TRY(h, h->dist_q.ensure((size_t)n * h->dim * sizeof(float)));
+        HIP_TRY(h, h->dist_out.ensure(nk * (2 * sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
+        HIP_TRY(h, h->dist_sel.ensure((size_t)(n + 1) * sizeof(int32_t)));
+        float* dq = h->dist_q.as<float>();
+        double* o_d64 = h->dist_out.as<double>();  // [d64 | groups | labels | dist | counts]
+        int64_t* o_grp = reinterpret_cast<int64_t*>(o_d64 + nk);
+        int64_t* o_lab = o_grp + nk;
+        float* o_dist = reinterpret_cast<float*>(o_lab + nk);
+        int32_t* o_cnt = reinterpret_cast<int32_t*>(o_dist + nk);
+        int32_t* nflag_d = h->dist_sel.as<int32_t>();  // [counter | flagged queries]
+        int32_t* qsel_d = nflag_d + 1;
+        HIP_TRY(h, hipMemcpyAsync(dq, queries + (size_t)q0 * h->dim, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
+        int32_t nsel = n;               // queries of the chunk the grouped scan serves
+        const int32_t* qsel = nullptr;  // ... all of them without a list pass
+        if (L > 0) {
+            const size_t nl = (size_t)n * L;
+            HIP_TRY(h, h->dist_list.ensure(nl * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
+            double* l_d64 = h->dist_list.as<double>();  // [d64 | labels | dist | counts]
+            int64_t* l_lab = reinterpret_cast<int64_t*>(l_d64 + nl);
+            float* l_dist = reinterpret_cast<float*>(l_lab + nl);
+            int32_t* l_cnt = reinterpret_cast<int32_t*>(l_dist + nl);
+            if (int rc = search_device_impl(h, dq, n, L, l_lab, l_dist, l_cnt, l_d64, s, false)) return rc;
+            HIP_TRY(h, hipMemsetAsync(nflag_d, 0, sizeof(int32_t), s));
+            HIP_TRY(h, launch_distinct_pick(l_lab, l_d64, l_cnt, n, L, group, k, k_eff, qsel_d, nflag_d, o_lab, o_dist, o_cnt,
+                                            o_d64, o_grp, s));
+            HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
+            HIP_TRY(h, hipMemcpyAsync(&nsel, nflag_d, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+            qsel = qsel_d;
+            h->host_fallbacks += nsel;
+        }
+        if (nsel > 0) {
+            HIP_TRY(h, h->qpad.ensure((size_t)n * h->ld * sizeof(float)));
+            HIP_TRY(h, h->qaux.ensure((size_t)n * sizeof(double)));
+            HIP_TRY(h, launch_query_prep(dq, n, h->dim, h->ld, h->space, h->qpad.as<float>(), h->qaux.as<double>(), nullptr, s));
+            const ExactPlan plan = plan_distinct(h->total, h->ld, nsel, k);
+            HIP_TRY(h, h->partial.ensure((size_t)nsel * plan.nblk * k * sizeof(DistinctEntry)));
+            DistinctArgs a{};
+            a.X = h->X;
+            a.rn = h->rn;
+            a.group = group;
+            a.total = h->total;
+            a.ld = h->ld;
+            a.space = h->space;
+            a.Qpad = h->qpad.as<float>();
+            a.qaux = h->qaux.as<double>();
+            a.qsel = qsel;
+            a.nq_sel = nsel;
+            a.nq_sel_dev = nullptr;
+            a.k = k;
+            a.partial = h->partial.as<DistinctEntry>();
+            if (int rc = scan_step(h, s, h->total * plan.nqtiles, [&] { return launch_distinct_scan(a, plan, s); })) return rc;
+            HIP_TRY(h, launch_distinct_merge(a.partial, nsel, nullptr, qsel, plan.nblk, k, k_eff, o_lab, o_dist, o_cnt, o_d64,
+                                             o_grp, s));
+            h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+        }
+        const size_t at = (size_t)q0 * k;
+        HIP_TRY(h, hipStreamSynchronize(s));
+        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o_d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_groups) HIP_TRY(h, hipMemcpyAsync(out_groups + at, o_grp, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o_lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_dist + at, o_dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t attr, int64_t max_groups,
+                                const mlvdb_where* where, int64_t* out_labels, float* out_dist, int32_t* out_counts,
+                                double* out_dist64, int64_t* out_groups) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched (the program: where_run validates it before its first launch)
+    if ((rc = attr_check(h, attr))) return rc;
+    if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "distinct needs an int64 column");
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "distinct: k above MLVDB_MAX_TOPK");
+    if (max_groups < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "max_groups < 0");
+    if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    auto call = [&]() {
+        return distinct_impl(h, queries, nq, k, attr, max_groups, out_labels, out_dist, out_counts, out_dist64, out_groups);
+    };
+    if (!where) return nq == 0 ? MLVDB_OK : call();
+    rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy
+    if (rc || nq == 0) return rc;
+    if (h->total == 0) return call();
+    return with_row_mask(h, nq, call);
     });
 }
 

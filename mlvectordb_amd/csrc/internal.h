@@ -11,8 +11,10 @@
 #include "../../include/mlvdb_where.h"
 #include "../../include/mlvdb_where_each.h"
 #include "../../include/mlvdb_where_each_range.h"
+#include "../../include/mlvdb_distinct.h"
 #include "layout.h"
 #include "wave_topk.h"
+#include "wave_topk_distinct.h"
 
 namespace mlvdb {
 
@@ -60,7 +62,8 @@ inline hipError_t ensure_dynamic_lds(std::atomic<uint64_t>& done, const void* ke
     X(scan_l2c, "SCAN_L2C", 1)         /* l2: the int8 bodies (one query quantisation step per pass, per-row integer offsets: cosine's one-constant test); 0: l2 off the int8 shadow */ \
     X(scan_nqt, "SCAN_NQT", 0)         /* query tiles of the int8 body: 0 = by batch size, else 4 / 8 / 16 */          \
     X(l2_offset_cache, "L2_OFFSET_CACHE", 1) /* l2: keep the offsets plane across passes of the same scale (0: recompute per pass) */ \
-    X(where_gather, "WHERE_GATHER", 150) /* per-query filters: gather a program's rows when matches x query tiles x 1000 <= live x this (0: never; tools/where_each_ab.py) */
+    X(where_gather, "WHERE_GATHER", 150) /* per-query filters: gather a program's rows when matches x query tiles x 1000 <= live x this (0: never; tools/where_each_ab.py) */ \
+    X(distinct_oversample, "DISTINCT_OVERSAMPLE", 4) /* distinct kNN: the list pass ranks min(1024, max(64, this x k)) rows per query (0: no list pass, every query takes the grouped exact scan; tools/distinct_ab.py) */
 
 struct Tuning {
 #define X(field, name, dflt) int field = dflt;
@@ -351,5 +354,36 @@ hipError_t launch_where_gather_range(const float* X, const float* Qpad, const do
                                      const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t space, int32_t qt,
                                      int32_t nchunk, float radius, int32_t q_base, RangeHit* rhits, uint32_t* rhit_cnt,
                                      hipStream_t s);
+
+// ---------------------------------------------------------------- distinct-by-attribute kNN (kernels_distinct.hip)
+constexpr int kDistinctMaxList = 1024;  // longest ranked list the pick walks (the list pass's top_k)
+struct DistinctArgs {
+    const float* X;
+    const float* rn;
+    const int64_t* group;  // the int64 attribute column: one group code per row, INT64_MIN = in no group
+    int64_t total;
+    int32_t ld;
+    int32_t space;
+    const float* Qpad;     // [nq][ld]
+    const double* qaux;    // [nq]
+    const int32_t* qsel;   // [nq_sel] query indices to process, or nullptr for 0..nq_sel-1
+    int32_t nq_sel;
+    const int32_t* nq_sel_dev;  // optional: the actual count lives on the device (<= nq_sel); blocks beyond it exit
+    int32_t k;
+    DistinctEntry* partial;  // [nq_sel][nblk][k]
+};
+// One wave per query over its ranked list (lab / d64: [nq][L], cnt[q] valid entries): the first entry of each group until
+// k_eff are kept.  Complete queries (k_eff kept, or fewer than L valid entries) get their final outputs; the others are
+// appended to qsel[*nflag ...] (*nflag zeroed by the caller).
+hipError_t launch_distinct_pick(const int64_t* lab, const double* d64, const int32_t* cnt, int32_t nq, int32_t L,
+                                const int64_t* group, int32_t k, int32_t k_eff, int32_t* qsel, int32_t* nflag,
+                                int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64, int64_t* out_groups,
+                                hipStream_t s);
+ExactPlan plan_distinct(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k);
+hipError_t launch_distinct_scan(const DistinctArgs& a, const ExactPlan& p, hipStream_t s);
+// merge partial lists -> final outputs at the original query index (at most k_eff <= k groups, the rest padded)
+hipError_t launch_distinct_merge(const DistinctEntry* partial, int32_t nq_sel, const int32_t* nq_sel_dev, const int32_t* qsel,
+                                 int32_t nblk, int32_t k, int32_t k_eff, int64_t* out_labels, float* out_dist,
+                                 int32_t* out_counts, double* out_d64, int64_t* out_groups, hipStream_t s);
 
 }  // namespace mlvdb

@@ -323,6 +323,30 @@ class HipScanEngine:
         out = (labels, dist, counts, d64) if want64 else (labels, dist, counts)
         return out + (routes,) if return_routes else out
 
+    # -- distinct-by-attribute kNN (include/mlvdb_distinct.h) ---------------------------
+    def search_distinct(self, queries: np.ndarray, k: int, attr: int, max_groups: int = 0, where=None,
+                        want64: bool = False):
+        """The nearest row of each of the ``k`` nearest groups, a group being one present value of int64 column ``attr``
+        (rows with an absent value are in no group).  ``max_groups``: an upper bound on the number of distinct present
+        values (0 = unknown), which only lets a query stop early; ``where`` (optional, a compiled ``where.Program``)
+        restricts the rows first.  Returns (labels int64 [nq, k], dist float32, counts int32, groups int64 [nq, k]) or,
+        with ``want64``, (labels, dist, counts, dist64, groups); padding is label -1 / +inf / group INT64_MIN."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        nq = queries.shape[0]
+        labels = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.int32)
+        groups = np.empty((nq, k), dtype=np.int64)
+        d64 = np.empty((nq, k), dtype=np.float64) if want64 else None
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_search_batch_distinct(
+            self._h, queries.ctypes.data, nq, int(k), int(attr), int(max_groups), None if w is None else C.byref(w),
+            labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
+            groups.ctypes.data), "search_batch_distinct")
+        return (labels, dist, counts, d64, groups) if want64 else (labels, dist, counts, groups)
+
     def search64(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None, where=None):
         """kNN; ``mask`` (optional, one byte per row, non-zero = allowed) restricts the search to those rows, ``where``
         (optional, a compiled ``where.Program``) to the rows it matches, evaluated on the device.

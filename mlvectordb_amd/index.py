@@ -449,7 +449,8 @@ class Index:
         return score
 
     def search_many(self, queries, top_k: int, namespace: str, metric: str,
-                    allowed_ids: Optional[Iterable[UUID]] = None, where: Optional[Mapping] = None) -> BatchHits:
+                    allowed_ids: Optional[Iterable[UUID]] = None, where: Optional[Mapping] = None,
+                    distinct: Optional[str] = None) -> BatchHits:
         """kNN for a batch of queries in one corpus scan.
 
         ``queries`` is an ``[nq, dim]`` array or a sequence of ``VectorDTO``.  Each entry of
@@ -459,7 +460,12 @@ class Index:
         filter over the declared attributes, where.py) does the same with the row mask evaluated on the device; a list or
         tuple of ``nq`` entries, each a dict filter or ``None`` (unfiltered), gives every query its own filter (one batched
         call, include/mlvdb_where_each.h): each query's answer is what a single-dict call for it alone returns.
+        ``distinct`` (additive: the name of a declared ``int`` / ``str`` / ``bool`` attribute) returns one hit per value of
+        that attribute -- the nearest row of each of the ``top_k`` (<= 64) nearest groups, rows without a value left out
+        (include/mlvdb_distinct.h); an optional single dict ``where`` restricts the rows first.
         """
+        if distinct is not None:
+            return self._search_many_distinct(queries, top_k, namespace, metric, allowed_ids, where, distinct)
         if where is not None and allowed_ids is not None:
             raise ValueError("search_many: give allowed_ids or where, not both")
         if isinstance(where, (list, tuple)):
@@ -492,6 +498,44 @@ class Index:
         return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
 
     _MAX_TOP_K = 16384  # MLVDB_MAX_TOPK_PAGED: the most neighbours one call returns per query
+
+    _MAX_TOP_K_DISTINCT = 64  # MLVDB_MAX_TOPK: one selection list of a wavefront
+
+    def _search_many_distinct(self, queries, top_k: int, namespace: str, metric: str, allowed_ids, where,
+                              distinct: str) -> BatchHits:
+        """``search_many`` with ``distinct=``: every refusal happens before the engine is touched."""
+        if self._devices is not None and len(self._devices) > 1:
+            raise ValueError("distinct= is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        if distinct not in self._attributes:
+            raise ValueError(f"distinct: {distinct!r} is not a declared attribute of this index "
+                             f"(declared: {sorted(self._attributes)})")
+        kind = self._attributes[distinct]
+        if kind == "float":
+            raise ValueError(f"distinct: attribute {distinct!r} is a float column; groups need an int, str or bool attribute")
+        if top_k > self._MAX_TOP_K_DISTINCT:
+            raise ValueError(f"distinct: top_k must be <= {self._MAX_TOP_K_DISTINCT} (got {top_k})")
+        if isinstance(where, (list, tuple)):
+            raise ValueError("distinct: a per-query where list is not supported, give one dict filter")
+        if allowed_ids is not None:
+            raise ValueError("distinct: allowed_ids is not supported, give a dict where filter")
+        program = None if where is None else self._compile(namespace, where)
+        q = self._coerce_queries(queries)
+        nq = q.shape[0]
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
+            return BatchHits.empty(nq)
+        search_distinct = getattr(ns.engine, "search_distinct", None)
+        if search_distinct is None:
+            raise ValueError("distinct= needs an engine with search_distinct (a single-device namespace)")
+        k = min(int(top_k), ns.total - ns.deleted)
+        # what the host knows about the number of groups: the dictionary's size, two booleans, nothing for integers
+        max_groups = len(ns.strings.get(distinct, {})) if kind == "str" else 2 if kind == "bool" else 0
+        if kind == "str" and max_groups == 0:
+            return BatchHits(np.full((nq, k), -1, np.int64), self._scores(np.full((nq, k), np.inf, np.float32), metric),
+                             np.zeros(nq, np.int32), ns.ids)  # no string was ever stored: every row is absent
+        attr = list(self._attributes).index(distinct)
+        labels, dist, counts, _ = search_distinct(q, k, attr, max_groups=max_groups, where=program)
+        return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
 
     def _compile_each(self, namespace: str, wheres) -> Tuple[list, np.ndarray]:
         for w in wheres:

@@ -66,7 +66,7 @@ class QueryProcessor:
         return self._enrich(hits, namespace)
 
     def find_similar_many(self, queries, top_k: int, namespace: str = "default",
-                          metric: str = "cosine", where=None) -> List[List[dict]]:
+                          metric: str = "cosine", where=None, distinct=None) -> List[List[dict]]:
         """Batched ``find_similar``: ``queries`` is an [nq, dim] array or a sequence of VectorDTO.
 
         ``where`` (additive; README.md:121,130,252,274 intent, no reference code) restricts the search to the matching
@@ -76,7 +76,16 @@ class QueryProcessor:
           - a predicate over a stored vector's metadata dict: evaluated once over the namespace's stored vectors and
             handed to the index as a row mask;
           - a list of ``nq`` entries, each a dict filter or ``None``: every query its own filter, all evaluated on the
-            device in one batched call (``Index.search_many``); a predicate inside the list is a ``ValueError``."""
+            device in one batched call (``Index.search_many``); a predicate inside the list is a ``ValueError``.
+        ``distinct`` (additive: a declared ``int`` / ``str`` / ``bool`` attribute of the index) returns one hit per value of
+        that attribute: the nearest vector of each of the ``top_k`` (<= 64) nearest groups (``Index.search_many``).  With
+        it ``where`` is ``None`` or one dict filter."""
+        if distinct is not None:
+            if where is not None and not isinstance(where, Mapping):
+                raise ValueError("distinct: where must be one dict filter (or None)")
+            hits = self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric, where=where,
+                                           distinct=distinct)
+            return self._enrich_many(hits, namespace)
         return self._enrich_many(self._search_many(queries, top_k, namespace, metric, where), namespace)
 
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
