@@ -116,6 +116,16 @@ DISTINCT_SIGNATURES = {
                                               _P, _P, _P, _P, _P]),
 }
 
+# include/mlvdb_facet.h: facet counts and histograms of attribute columns
+FACET_MAX_VALUES = 1 << 20
+FACET_MAX_EDGES = 4096
+FACET_SIGNATURES = {
+    "mlvdb_facet_values": (C.c_int, [_P, C.c_int32, C.POINTER(Where), C.c_int64, _P, _P, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mlvdb_facet_bins": (C.c_int, [_P, C.c_int32, C.POINTER(Where), _P, C.c_int32, _P, C.POINTER(C.c_int64),
+                                   C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -145,7 +155,7 @@ def load() -> C.CDLL:
             f"There is no CPU fallback for the search path.")
     lib = C.CDLL(str(path))
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
-                                      **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES}.items():
+                                      **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **FACET_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -117,6 +117,9 @@ struct mlvdb_index {
     // distinct kNN (mlvdb_distinct.h): a chunk's queries, its ranked lists from the plain search, its outputs, and the
     // flagged queries' list + counter -- all sized by the chunk (<= kDistinctChunk queries), k and L, never by the corpus
     DevBuf dist_q, dist_list, dist_out, dist_sel;
+    // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
+    // bin counts -- never sized by the corpus
+    DevBuf facet_tab, facet_misc;
     // fp16 row-major shadow for the mid bounds (kernels_refine.hip): built lazily by the first range query / top_k > 64 search
     DevBuf x16, s16, rowerr16, picks, npicks;
     int64_t l2_rows = 0;      // rows [0, l2_rows) of the fp16 shadow are current (0 after compact / reset / regrowth)
@@ -1165,7 +1168,8 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     h->where_prog.release();
     h->where_cnt.release();
     for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
-                      &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel})
+                      &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel,
+                      &h->facet_tab, &h->facet_misc})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
@@ -2057,19 +2061,27 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
     return MLVDB_OK;
 }
 
+// The validated program (h->where_ops) and its set table -> h->where_prog on the device, enqueued on h->stream.
+int where_upload(mlvdb_index* h, const mlvdb_where* w, const int64_t** set_d) {
+    hipStream_t s = h->stream;
+    const size_t pbytes = h->where_ops.size() * sizeof(WhereOp), sbytes = (size_t)w->n_set * sizeof(int64_t);
+    HIP_TRY(h, h->where_prog.ensure(pbytes + sbytes + sizeof(int64_t)));
+    HIP_TRY(h, hipMemcpyAsync(h->where_prog.p, h->where_ops.data(), pbytes, hipMemcpyHostToDevice, s));
+    *set_d = reinterpret_cast<const int64_t*>(h->where_prog.as<char>() + pbytes);
+    if (sbytes) HIP_TRY(h, hipMemcpyAsync(h->where_prog.as<char>() + pbytes, w->set, sbytes, hipMemcpyHostToDevice, s));
+    return MLVDB_OK;
+}
+
 // Validate, upload and evaluate a program into h->row_mask (live matching rows); matches != nullptr: also wait for their count.
 int where_run(mlvdb_index* h, const mlvdb_where* w, int64_t* matches) {
     if (int rc = where_prepare(h, w)) return rc;
     if (matches) *matches = 0;
     if (h->total == 0) return MLVDB_OK;
     hipStream_t s = h->stream;
-    const size_t pbytes = h->where_ops.size() * sizeof(WhereOp), sbytes = (size_t)w->n_set * sizeof(int64_t);
-    HIP_TRY(h, h->where_prog.ensure(pbytes + sbytes + sizeof(int64_t)));
+    const int64_t* set_d = nullptr;
+    if (int rc = where_upload(h, w, &set_d)) return rc;
     HIP_TRY(h, h->where_cnt.ensure(sizeof(unsigned long long)));
     HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
-    HIP_TRY(h, hipMemcpyAsync(h->where_prog.p, h->where_ops.data(), pbytes, hipMemcpyHostToDevice, s));
-    const int64_t* set_d = reinterpret_cast<const int64_t*>(h->where_prog.as<char>() + pbytes);
-    if (sbytes) HIP_TRY(h, hipMemcpyAsync(h->where_prog.as<char>() + pbytes, w->set, sbytes, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemsetAsync(h->where_cnt.p, 0, sizeof(unsigned long long), s));
     HIP_TRY(h, launch_where_eval(h->where_prog.as<WhereOp>(), w->n_ops, set_d, h->rn, h->total, h->row_mask.as<uint8_t>(),
                                  h->where_cnt.as<unsigned long long>(), s));
@@ -2878,6 +2890,148 @@ int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq
     if (rc || nq == 0) return rc;
     if (h->total == 0) return call();
     return with_row_mask(h, nq, call);
+    });
+}
+
+// ---- facet counts and histograms (mlvdb_facet.h)
+extern "C++" {
+namespace {
+// The program of a facet call on the device (where == nullptr: no program, n_ops 0); validated by the caller.
+int facet_program(mlvdb_index* h, const mlvdb_where* where, const WhereOp** prog, int32_t* n_ops, const int64_t** set_d) {
+    *prog = nullptr;
+    *n_ops = 0;
+    *set_d = nullptr;
+    if (!where) return MLVDB_OK;
+    if (int rc = where_upload(h, where, set_d)) return rc;
+    *prog = h->where_prog.as<WhereOp>();
+    *n_ops = where->n_ops;
+    return MLVDB_OK;
+}
+
+int facet_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
+                      int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
+    hipStream_t s = h->stream;
+    const WhereOp* prog;
+    int32_t n_ops;
+    const int64_t* set_d;
+    if (int rc = facet_program(h, where, &prog, &n_ops, &set_d)) return rc;
+    uint64_t slots = 64;  // a power of two >= 2 max_values: the table is at most half full when the call succeeds
+    while (slots < 2 * (uint64_t)max_values) slots *= 2;
+    // [keys | counts | packed keys | packed counts]
+    HIP_TRY(h, h->facet_tab.ensure((2 * slots + 2 * (size_t)max_values) * sizeof(int64_t)));
+    HIP_TRY(h, h->facet_misc.ensure(kFacetCounters * sizeof(unsigned long long)));
+    FacetTable t{};
+    t.keys = h->facet_tab.as<unsigned long long>();
+    t.counts = t.keys + slots;
+    t.mask = slots - 1;
+    t.max_values = (unsigned long long)max_values;
+    t.ctr = h->facet_misc.as<unsigned long long>();
+    long long* packed_keys = reinterpret_cast<long long*>(t.counts + slots);
+    unsigned long long* packed_counts = t.counts + slots + max_values;
+    HIP_TRY(h, launch_attr_fill(reinterpret_cast<int64_t*>(t.keys), INT64_MIN, 0, (int64_t)slots, s));
+    HIP_TRY(h, hipMemsetAsync(t.counts, 0, slots * sizeof(unsigned long long), s));
+    HIP_TRY(h, hipMemsetAsync(t.ctr, 0, kFacetCounters * sizeof(unsigned long long), s));
+    HIP_TRY(h, launch_facet_values(prog, n_ops, set_d, h->rn, h->attr_col[attr], h->total, t, s));
+    HIP_TRY(h, launch_facet_collect(t, packed_keys, packed_counts, s));
+    unsigned long long ctr[kFacetCounters] = {};
+    HIP_TRY(h, hipMemcpyAsync(ctr, t.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *matched = (int64_t)ctr[kFacetMatched];
+    *absent = (int64_t)ctr[kFacetAbsent];
+    *n_values = (int64_t)ctr[kFacetDistinct];
+    if (ctr[kFacetOverflow] || ctr[kFacetDistinct] > (unsigned long long)max_values) {
+        *n_values = std::max<int64_t>(*n_values, max_values + 1);
+        return fail(h, MLVDB_ERR_OVERFLOW, "facet: more than max_values distinct values");
+    }
+    const size_t n = (size_t)ctr[kFacetDistinct];
+    if (ctr[kFacetCursor] != ctr[kFacetDistinct]) return fail(h, MLVDB_ERR_INTERNAL, "facet: table and counter disagree");
+    if (n == 0) return MLVDB_OK;
+    std::vector<std::pair<int64_t, int64_t>> pairs(n);
+    std::vector<int64_t> keys(n), counts(n);
+    HIP_TRY(h, hipMemcpyAsync(keys.data(), packed_keys, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(counts.data(), packed_counts, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; ++i) pairs[i] = {keys[i], counts[i]};
+    std::sort(pairs.begin(), pairs.end());  // (the values are distinct: the order is total)
+    for (size_t i = 0; i < n; ++i) {
+        out_values[i] = pairs[i].first;
+        out_counts[i] = pairs[i].second;
+    }
+    return MLVDB_OK;
+}
+
+int facet_bins_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, const void* edges, int32_t n_edges,
+                    int64_t* out_counts, int64_t* matched, int64_t* absent) {
+    hipStream_t s = h->stream;
+    const WhereOp* prog;
+    int32_t n_ops;
+    const int64_t* set_d;
+    if (int rc = facet_program(h, where, &prog, &n_ops, &set_d)) return rc;
+    // [counters | bins | edges]
+    const size_t nbins = (size_t)n_edges + 1;
+    HIP_TRY(h, h->facet_misc.ensure((kFacetCounters + nbins + (size_t)n_edges) * sizeof(int64_t)));
+    unsigned long long* ctr_d = h->facet_misc.as<unsigned long long>();
+    unsigned long long* bins_d = ctr_d + kFacetCounters;
+    int64_t* edges_d = reinterpret_cast<int64_t*>(bins_d + nbins);
+    HIP_TRY(h, hipMemsetAsync(ctr_d, 0, (kFacetCounters + nbins) * sizeof(unsigned long long), s));
+    HIP_TRY(h, hipMemcpyAsync(edges_d, edges, (size_t)n_edges * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_facet_bins(prog, n_ops, set_d, h->rn, h->attr_col[attr], h->attr_type[attr], h->total, edges_d, n_edges,
+                                 bins_d, ctr_d, s));
+    std::vector<int64_t> host(kFacetCounters + nbins);
+    HIP_TRY(h, hipMemcpyAsync(host.data(), ctr_d, host.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *matched = host[kFacetMatched];
+    *absent = host[kFacetAbsent];
+    std::copy(host.begin() + kFacetCounters, host.end(), out_counts);
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_facet_values(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
+                       int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = attr_check(h, attr))) return rc;
+    if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "value facets need an int64 column");
+    if (max_values < 1 || max_values > MLVDB_FACET_MAX_VALUES)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "max_values must be in 1..MLVDB_FACET_MAX_VALUES");
+    if (!out_values || !out_counts || !n_values || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (where && (rc = where_prepare(h, where))) return rc;
+    *n_values = *matched = *absent = 0;
+    if (h->total == 0) return MLVDB_OK;
+    return facet_values_impl(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent);
+    });
+}
+
+int mlvdb_facet_bins(mlvdb_index* h, int32_t attr, const mlvdb_where* where, const void* edges, int32_t n_edges,
+                     int64_t* out_counts, int64_t* matched, int64_t* absent) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = attr_check(h, attr))) return rc;
+    if (n_edges < 1 || n_edges > MLVDB_FACET_MAX_EDGES)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "n_edges must be in 1..MLVDB_FACET_MAX_EDGES");
+    if (!edges || !out_counts || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (h->attr_type[attr] == MLVDB_ATTR_INT64) {
+        const int64_t* e = static_cast<const int64_t*>(edges);
+        if (e[0] == INT64_MIN) return fail(h, MLVDB_ERR_INVALID_ARG, "an int64 edge must not be INT64_MIN (the absent marker)");
+        for (int32_t i = 1; i < n_edges; ++i)
+            if (!(e[i - 1] < e[i])) return fail(h, MLVDB_ERR_INVALID_ARG, "edges must be strictly ascending");
+    } else {
+        const double* e = static_cast<const double*>(edges);
+        if (e[0] != e[0]) return fail(h, MLVDB_ERR_INVALID_ARG, "a float64 edge must not be NaN");
+        for (int32_t i = 1; i < n_edges; ++i)  // (a NaN edge fails the comparison too)
+            if (!(e[i - 1] < e[i])) return fail(h, MLVDB_ERR_INVALID_ARG, "edges must be strictly ascending and not NaN");
+    }
+    if (where && (rc = where_prepare(h, where))) return rc;
+    *matched = *absent = 0;
+    for (int32_t i = 0; i <= n_edges; ++i) out_counts[i] = 0;
+    if (h->total == 0) return MLVDB_OK;
+    return facet_bins_impl(h, attr, where, edges, n_edges, out_counts, matched, absent);
     });
 }
 

@@ -12,6 +12,7 @@
 #include "../../include/mlvdb_where_each.h"
 #include "../../include/mlvdb_where_each_range.h"
 #include "../../include/mlvdb_distinct.h"
+#include "../../include/mlvdb_facet.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -385,5 +386,37 @@ hipError_t launch_distinct_scan(const DistinctArgs& a, const ExactPlan& p, hipSt
 hipError_t launch_distinct_merge(const DistinctEntry* partial, int32_t nq_sel, const int32_t* nq_sel_dev, const int32_t* qsel,
                                  int32_t nblk, int32_t k, int32_t k_eff, int64_t* out_labels, float* out_dist,
                                  int32_t* out_counts, double* out_d64, int64_t* out_groups, hipStream_t s);
+
+// ---------------------------------------------------------------- facet counts and histograms (kernels_facet.hip)
+constexpr int kFacetLdsSlots = 4096;  // per-block table of the value kernel: int64 key + uint32 count = 48 KiB, three blocks per CU
+constexpr int kFacetLdsProbes = 8;    // linear probes in the block table; a key that finds no slot goes to the global table
+constexpr int kFacetPeelRounds = 8;   // wave peel: at most this many leading values get one add for all their lanes
+constexpr int kFacetMaxEdges = MLVDB_FACET_MAX_EDGES;
+// The one hash of both tables (mirrored in tests/facet_helpers.py): slot = facet_hash(v) & (slots - 1)
+__host__ __device__ inline uint64_t facet_hash(int64_t v) {
+    const uint64_t x = (uint64_t)v * 0x9E3779B97F4A7C15ull;
+    return x ^ (x >> 32);
+}
+// words of the counters a facet call zeroes before its launch
+enum { kFacetMatched = 0, kFacetAbsent = 1, kFacetDistinct = 2, kFacetOverflow = 3, kFacetCursor = 4, kFacetCounters = 8 };
+// The global table of one value-facet call: `mask + 1` slots (a power of two >= 2 max_values), keys INT64_MIN = empty
+struct FacetTable {
+    unsigned long long* keys;
+    unsigned long long* counts;
+    uint64_t mask;
+    unsigned long long max_values;
+    unsigned long long* ctr;  // [kFacetCounters]
+};
+// One pass over rn, the program's columns and `col` (int64): every live matching row counted under its value in `t`,
+// ctr[matched / absent / distinct / overflow] updated.  n_ops == 0: no program, every live row matches.
+hipError_t launch_facet_values(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* col,
+                               int64_t total, const FacetTable& t, hipStream_t s);
+// the non-empty slots of `t` packed through ctr[kFacetCursor] into out_keys / out_counts (max_values entries each), in no order
+hipError_t launch_facet_collect(const FacetTable& t, long long* out_keys, unsigned long long* out_counts, hipStream_t s);
+// The same pass into bins[n_edges + 1] (zeroed by the caller): bin = number of edges <= value; `edges` on the device, int64 or
+// the bits of doubles by `type` (MLVDB_ATTR_*)
+hipError_t launch_facet_bins(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* col,
+                             int32_t type, int64_t total, const int64_t* edges, int32_t n_edges, unsigned long long* bins,
+                             unsigned long long* ctr, hipStream_t s);
 
 }  // namespace mlvdb

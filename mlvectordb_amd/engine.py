@@ -91,6 +91,15 @@ def stitch_range_hits(parts, nq: int) -> RangeHits:
     return RangeHits(labels, dist, offsets)
 
 
+class FacetOverflow(RuntimeError):
+    """A value-facet call met more than ``max_values`` distinct values (``MLVDB_ERR_OVERFLOW``).  ``matched`` and ``absent``
+    are still exact; ``n_values`` is some number above ``max_values``."""
+
+    def __init__(self, max_values: int, n_values: int, matched: int, absent: int) -> None:
+        super().__init__(f"facet_values: more than max_values={max_values} distinct values")
+        self.max_values, self.n_values, self.matched, self.absent = max_values, n_values, matched, absent
+
+
 class HipScanEngine:
     """Exhaustive fp32 corpus scan on one MI355X, through the C ABI."""
 
@@ -110,6 +119,7 @@ class HipScanEngine:
             msg = self._lib.mlvdb_last_global_error().decode(errors="replace")
             raise RuntimeError(f"mlvdb_index_create failed ({rc}): {msg}")
         self._h = handle
+        self._attr_kinds = {}  # column -> "int64" / "float64", as defined through this object
         if strategy != "auto":
             self.set_strategy(strategy)
 
@@ -219,6 +229,7 @@ class HipScanEngine:
     def define_attr(self, attr: int, kind: str) -> None:
         """Column ``attr`` (0..15) of type "int64" (absent = INT64_MIN) or "float64" (absent = NaN), every row absent."""
         self._check(self._lib.mlvdb_attr_define(self._h, int(attr), _native.ATTR_CODES[kind]), "attr_define")
+        self._attr_kinds[int(attr)] = kind
 
     def set_attr(self, attr: int, first: int, values: np.ndarray) -> None:
         """Values of rows first..first+len(values)-1 (int64 or float64 by the column's type)."""
@@ -346,6 +357,41 @@ class HipScanEngine:
             labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
             groups.ctypes.data), "search_batch_distinct")
         return (labels, dist, counts, d64, groups) if want64 else (labels, dist, counts, groups)
+
+    # -- facet counts and histograms (include/mlvdb_facet.h) ---------------------------
+    def facet_values(self, attr: int, max_values: int, where=None):
+        """The distinct present values of int64 column ``attr`` among the live rows (those the compiled ``where.Program``
+        matches, when one is given) and how many rows hold each: (values int64 ascending, counts int64, matched, absent)
+        with ``counts.sum() + absent == matched``.  More than ``max_values`` distinct values raise ``FacetOverflow``."""
+        max_values = int(max_values)
+        values = np.empty(max(0, min(max_values, _native.FACET_MAX_VALUES)), dtype=np.int64)
+        counts = np.empty(values.size, dtype=np.int64)
+        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        w, keep = self._where(where) if where is not None else (None, None)
+        rc = self._check(self._lib.mlvdb_facet_values(
+            self._h, int(attr), None if w is None else C.byref(w), max_values, values.ctypes.data, counts.ctypes.data,
+            C.byref(n), C.byref(matched), C.byref(absent)), "facet_values", allow=(_native.ERR_OVERFLOW,))
+        if rc == _native.ERR_OVERFLOW:
+            raise FacetOverflow(max_values, int(n.value), int(matched.value), int(absent.value))
+        return values[: n.value].copy(), counts[: n.value].copy(), int(matched.value), int(absent.value)
+
+    def facet_bins(self, attr: int, edges: np.ndarray, where=None):
+        """Histogram of column ``attr`` over the strictly ascending ``edges`` (an int64 array for an int64 column, float64
+        for a float64 one): (counts int64 [len(edges) + 1], matched, absent), ``counts[i]`` = the live matching rows whose
+        present value has ``i`` edges at or below it (``np.searchsorted(edges, v, side="right")``)."""
+        edges = np.ascontiguousarray(edges)
+        if edges.ndim != 1 or edges.dtype not in (np.int64, np.float64):
+            raise RuntimeError(f"edges must be a 1-d int64 or float64 array, got {edges.dtype} {edges.shape}")
+        kind = self._attr_kinds.get(int(attr))
+        if kind is not None and kind != edges.dtype.name:
+            raise RuntimeError(f"attribute {attr} is an {kind} column, the edges are {edges.dtype.name}")
+        counts = np.zeros(edges.size + 1, dtype=np.int64)
+        matched, absent = C.c_int64(0), C.c_int64(0)
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_facet_bins(
+            self._h, int(attr), None if w is None else C.byref(w), edges.ctypes.data, int(edges.size), counts.ctypes.data,
+            C.byref(matched), C.byref(absent)), "facet_bins")
+        return counts, int(matched.value), int(absent.value)
 
     def search64(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None, where=None):
         """kNN; ``mask`` (optional, one byte per row, non-zero = allowed) restricts the search to those rows, ``where``

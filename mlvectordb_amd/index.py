@@ -19,7 +19,8 @@ swallowed by index.py:110-119); rows of the wrong dimensionality raise ``Runtime
 Additive (no reference counterpart): ``search_many`` (one scan for a whole query batch),
 ``range_search`` / ``range_search_many``, ``metric="euclidean"`` as sqrt(l2), ``compact`` and
 ``save_index`` / ``load_index`` (named in the reference's README.md:240-241 only); metadata filters evaluated on the device
-(``attributes=`` / ``where=`` / ``count`` / ``query_by_metadata``: README.md:121,130,252,274 intent, no reference code).
+(``attributes=`` / ``where=`` / ``count`` / ``query_by_metadata``: README.md:121,130,252,274 intent, no reference code) and
+aggregated there (``facets`` / ``histogram``).
 """
 from __future__ import annotations
 
@@ -33,7 +34,7 @@ from uuid import UUID
 import numpy as np
 
 from . import where as _where
-from .engine import HipScanEngine, ScanEngine
+from .engine import FacetOverflow, HipScanEngine, ScanEngine
 from .idtable import IdTable, mint_uuid4_bytes
 from .interfaces import VectorDTO, VectorProtocol
 
@@ -654,6 +655,122 @@ class Index:
         if ns is None or ns.total == 0:
             return []
         return ns.ids.uuids_at(ns.engine.where_labels(program)).tolist()
+
+    # ------------------------------------------------------------------ additive: facet counts and histograms on the device
+    _MAX_FACET_VALUES = 1 << 20  # MLVDB_FACET_MAX_VALUES
+    _MAX_FACET_EDGES = 4096      # MLVDB_FACET_MAX_EDGES
+
+    def check_facet_args(self, by, order: str = "count", limit: Optional[int] = None, max_values: int = 65536) -> List[str]:
+        """The refusals of ``facets`` that need no namespace -> the attributes to facet (``by`` as a list)."""
+        names = list(by) if isinstance(by, (list, tuple)) else [by]
+        for name in names:
+            if name not in self._attributes:
+                raise ValueError(f"facets: {name!r} is not a declared attribute of this index "
+                                 f"(declared: {sorted(self._attributes)})")
+            if self._attributes[name] == "float":
+                raise ValueError(f"facets: attribute {name!r} is a float column; value facets need an int, str or bool "
+                                 f"attribute (histogram() bins floats)")
+        if order not in ("count", "value"):
+            raise ValueError(f'facets: order must be "count" or "value" (got {order!r})')
+        if limit is not None and (isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1):
+            raise ValueError(f"facets: limit must be None or an int >= 1 (got {limit!r})")
+        if isinstance(max_values, bool) or not isinstance(max_values, (int, np.integer)) or \
+                not 1 <= max_values <= self._MAX_FACET_VALUES:
+            raise ValueError(f"facets: max_values must be in 1..{self._MAX_FACET_VALUES} (got {max_values!r})")
+        return names
+
+    @staticmethod
+    def order_facets(pairs: List[tuple], order: str, limit: Optional[int]) -> List[tuple]:
+        """(decoded value, count) pairs in the order ``facets`` returns them: by count descending with ties by value
+        ascending, or by value ascending; cut to ``limit``."""
+        pairs = sorted(pairs, key=(lambda p: (-p[1], p[0])) if order == "count" else (lambda p: p[0]))
+        return pairs if limit is None else pairs[:int(limit)]
+
+    def facets(self, namespace: str, by, where: Optional[Mapping] = None, *, limit: Optional[int] = None,
+               order: str = "count", max_values: int = 65536):
+        """Group-by counts of a declared ``str`` / ``int`` / ``bool`` attribute over the live rows of ``namespace`` (those the
+        dict filter ``where`` matches, when one is given), aggregated on the device (include/mlvdb_facet.h):
+        ``{"values": [(value, count), ...], "matched": live matching rows, "absent": those of them without a value}``,
+        the values decoded (strings, ``True`` / ``False``).  ``order="count"``: by count descending, ties by value
+        ascending; ``order="value"``: by value ascending; ``limit`` cuts after ordering.  ``max_values`` bounds the distinct
+        values of an ``int`` attribute (more: ``ValueError``); a ``str`` attribute is bounded by its dictionary, a ``bool``
+        by two.  ``by`` as a list of attributes returns a dict keyed by attribute (one device pass each).  An unknown or
+        empty namespace gives no values and zeros."""
+        names = self.check_facet_args(by, order, limit, max_values)
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"facets: where must be one dict filter or None (got {type(where).__name__})")
+        program = None if where is None else self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        out = {}
+        for name in names:
+            if ns is None or ns.total == 0:
+                out[name] = {"values": [], "matched": 0, "absent": 0}
+                continue
+            facet_values = getattr(ns.engine, "facet_values", None)
+            if facet_values is None:
+                raise ValueError("facets needs an engine with facet_values (a single-device namespace)")
+            kind = self._attributes[name]
+            codes = ns.strings.get(name, {})
+            bound = max(1, len(codes)) if kind == "str" else 2 if kind == "bool" else int(max_values)
+            try:
+                values, counts, matched, absent = facet_values(list(self._attributes).index(name), bound, where=program)
+            except FacetOverflow as e:
+                raise ValueError(f"facets: attribute {name!r} holds more than max_values={bound} distinct values among the "
+                                 f"{e.matched} matching rows; raise max_values (at most {self._MAX_FACET_VALUES})") from e
+            values, counts = values.tolist(), counts.tolist()
+            if kind == "str":
+                strings = sorted(codes, key=codes.get)  # code order
+                values = [strings[v] for v in values]
+            elif kind == "bool":
+                values = [bool(v) for v in values]
+            out[name] = {"values": self.order_facets(list(zip(values, counts)), order, limit), "matched": matched,
+                         "absent": absent}
+        return out if isinstance(by, (list, tuple)) else out[names[0]]
+
+    def check_histogram_args(self, by: str, edges) -> np.ndarray:
+        """The refusals of ``histogram`` -> the edges as the column's own type (int64 / float64)."""
+        if not isinstance(by, str) or by not in self._attributes:
+            raise ValueError(f"histogram: {by!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        kind = self._attributes[by]
+        if kind not in ("int", "float"):
+            raise ValueError(f"histogram: attribute {by!r} is a {kind} column; bins need an int or float attribute")
+        edges = edges.tolist() if isinstance(edges, np.ndarray) else list(edges)
+        if not 1 <= len(edges) <= self._MAX_FACET_EDGES:
+            raise ValueError(f"histogram: 1..{self._MAX_FACET_EDGES} edges (got {len(edges)})")
+        for e in edges:  # where.py's literal rules: an int attribute refuses floats, a float one takes ints and floats
+            if kind == "int":
+                if not isinstance(e, (int, np.integer)):  # (bool is an int)
+                    raise ValueError(f"histogram: {by!r} is an int attribute: edge {e!r} is not an int")
+                if not -(2 ** 63) < int(e) < 2 ** 63:
+                    raise ValueError(f"histogram: edge {e!r} is outside int64 (INT64_MIN marks absent)")
+            elif isinstance(e, (bool, np.bool_)) or not isinstance(e, (int, float, np.integer, np.floating)):
+                raise ValueError(f"histogram: {by!r} is a float attribute: edge {e!r} is not an int or float")
+        out = np.array([int(e) for e in edges], dtype=np.int64) if kind == "int" else \
+            np.array([float(e) for e in edges], dtype=np.float64)
+        if kind == "float" and np.isnan(out).any():
+            raise ValueError("histogram: an edge is NaN")
+        if not (out[1:] > out[:-1]).all():
+            raise ValueError("histogram: edges must be strictly ascending (unsorted or duplicate edges)")
+        return out
+
+    def histogram(self, namespace: str, by: str, edges, where: Optional[Mapping] = None):
+        """Bin counts of a declared ``int`` / ``float`` attribute over the live rows of ``namespace`` (those the dict filter
+        ``where`` matches, when one is given), on the device: ``{"counts": int64 array [len(edges) + 1], "matched",
+        "absent"}`` with ``counts[i]`` = rows whose value has ``i`` edges at or below it (``np.searchsorted(edges, v,
+        side="right")``: slot 0 below the first edge, the last slot at or above the last).  ``edges``: 1..4096 strictly
+        ascending literals, ints for an ``int`` attribute, ints or floats (not NaN) for a ``float`` one."""
+        e = self.check_histogram_args(by, edges)
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"histogram: where must be one dict filter or None (got {type(where).__name__})")
+        program = None if where is None else self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total == 0:
+            return {"counts": np.zeros(e.size + 1, dtype=np.int64), "matched": 0, "absent": 0}
+        facet_bins = getattr(ns.engine, "facet_bins", None)
+        if facet_bins is None:
+            raise ValueError("histogram needs an engine with facet_bins (a single-device namespace)")
+        counts, matched, absent = facet_bins(list(self._attributes).index(by), e, where=program)
+        return {"counts": counts, "matched": matched, "absent": absent}
 
     def range_search_many(self, queries, radius: float, namespace: str, metric: str,
                           max_results: int = 1024, where=None) -> List[List[SearchResult]]:

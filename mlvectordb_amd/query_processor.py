@@ -223,6 +223,48 @@ class QueryProcessor:
             return self._index.query_by_metadata(namespace, where)
         return [v.id for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
 
+    # ---- additive: facet counts and histograms (Index.facets / Index.histogram; no reference code)
+    def _host_column(self, by: str, where, namespace: str):
+        """(values of attribute ``by`` of the stored vectors ``where`` accepts -- ``None`` / NaN = absent --, their number)."""
+        kind = self._index.attributes[by]
+        picked = [None if v.metadata is None else v.metadata.get(by)
+                  for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
+        present = [x for x in picked if x is not None and not (kind == "float" and isinstance(x, float) and x != x)]
+        return present, len(picked)
+
+    def facets(self, by, where=None, namespace: str = "default", *, limit=None, order: str = "count",
+               max_values: int = 65536):
+        """``Index.facets`` of ``namespace``: a dict filter (or no filter) is aggregated on the device; a predicate is
+        computed over the storage's metadata on the host, as ``count_where`` does, with the same answer format."""
+        if where is None or isinstance(where, Mapping):
+            return self._index.facets(namespace, by, where, limit=limit, order=order, max_values=max_values)
+        if not callable(where):
+            raise ValueError(f"facets: where must be a dict filter, a predicate or None (got {type(where).__name__})")
+        names = self._index.check_facet_args(by, order, limit, max_values)
+        out = {}
+        for name in names:
+            present, matched = self._host_column(name, where, namespace)
+            counts: Dict[Any, int] = {}
+            for x in present:
+                counts[x] = counts.get(x, 0) + 1
+            if self._index.attributes[name] == "int" and len(counts) > max_values:
+                raise ValueError(f"facets: attribute {name!r} holds more than max_values={max_values} distinct values")
+            out[name] = {"values": self._index.order_facets(list(counts.items()), order, limit), "matched": matched,
+                         "absent": matched - len(present)}
+        return out if isinstance(by, (list, tuple)) else out[names[0]]
+
+    def histogram(self, by: str, edges, where=None, namespace: str = "default"):
+        """``Index.histogram`` of ``namespace``; ``where`` as in ``facets``."""
+        if where is None or isinstance(where, Mapping):
+            return self._index.histogram(namespace, by, edges, where)
+        if not callable(where):
+            raise ValueError(f"histogram: where must be a dict filter, a predicate or None (got {type(where).__name__})")
+        e = self._index.check_histogram_args(by, edges)
+        present, matched = self._host_column(by, where, namespace)
+        bins = np.searchsorted(e, np.asarray(present, dtype=e.dtype), side="right")
+        return {"counts": np.bincount(bins, minlength=e.size + 1).astype(np.int64), "matched": matched,
+                "absent": matched - len(present)}
+
     # ---- delete -> lazy rebuild (query_processor.py:51-62)
     def delete(self, ids: Sequence[UUID], namespace: str = "default") -> Sequence[UUID]:
         removed = [vid for vid in ids if self._storage.delete(vid, namespace)]
