@@ -1,0 +1,47 @@
+"""Seeded call histories on ONE ``HipScanEngine`` handle from creation to close, against the NumPy model of the whole engine
+(tests/history_helpers.py; the coverage the committed seed set reaches is asserted without a GPU in tests/test_history_host.py).
+Every answer is compared at once: labels, counts, groups, facet and bin counts exactly, distances by the suite's bars.  A
+mismatch leaves history_<tag>.json (the ops up to the failing step) in the mismatch directory of tests/conftest.py and the
+arrays beside it, names seed, step and op, and starts nothing more on the device but ``close()``."""
+import pytest
+
+from mlvectordb_amd.engine import HipScanEngine
+from mlvectordb_amd.multi_device import MultiDeviceEngine
+from tests import history_helpers as H
+
+pytestmark = pytest.mark.gpu
+
+
+def _replay(key, make_engine):
+    ops, expected = H.make_history(*key)
+    drawn, redrawn = H.redraw_counts(*key)
+    print(f"history {H.history_tag(*key)}: {redrawn} of {drawn} drawn queries were redrawn")
+    engine = make_engine()
+    try:
+        stats = H.run_history(engine, ops, expected, H.history_tag(*key))
+    finally:
+        engine.close()
+    assert stats["steps"] == len(ops)
+
+
+@pytest.mark.parametrize("key", H.SMALL, ids=lambda key: H.history_tag(*key))
+def test_small_history_equals_the_model_at_every_step(key):
+    """d = 20 / 64 / 128 / 256 / 100: the bf16-shadow widths, the zero-padded int8 shadow and a 256-column row; the corpus stays
+    under ~6,000 rows and ``set_strategy`` switches the routes."""
+    seed, space, d, _ = key
+    _replay(key, lambda: HipScanEngine(d, space, device=0))
+
+
+@pytest.mark.parametrize("key", H.LARGE, ids=lambda key: H.history_tag(*key))
+def test_large_history_crosses_the_threshold_of_auto_both_ways(key):
+    """Appends of 12,000 rows until past 32,768 live rows, so that `auto` itself changes route at nq = 12 and 40; tombstones and a
+    compaction back below the threshold; growth again."""
+    seed, space, d, _ = key
+    _replay(key, lambda: HipScanEngine(d, space, device=0))
+
+
+@pytest.mark.parametrize("key", H.MULTI, ids=lambda key: H.history_tag(*key))
+def test_history_through_three_logical_shards_equals_one_model(key):
+    """``MultiDeviceEngine`` over three ``HipScanEngine`` shards on device 0, the ops of tests/test_host_fuzz.py."""
+    seed, space, d, _ = key
+    _replay(key, lambda: MultiDeviceEngine(d, space, [0, 0, 0]))

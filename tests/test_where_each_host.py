@@ -9,7 +9,7 @@ import pytest
 
 from mlvectordb_amd import Index, InMemoryStorage, QueryProcessor, Vector, VectorDTO, _native
 from mlvectordb_amd import where as W
-from tests.where_helpers import SCHEMA, WhereOracleEngine, py_match, random_filter, random_metadata
+from tests.where_helpers import SCHEMA, EachOracleEngine, py_match, random_filter, random_metadata
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -18,25 +18,6 @@ def each_header_functions():
     text = (ROOT / "include" / "mlvdb_where_each.h").read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(mlvdb_[a-z0-9_]+)\s*\(", text)))
-
-
-class EachOracleEngine(WhereOracleEngine):
-    """``WhereOracleEngine`` + ``search_each`` / ``count_each``: every query searched alone under its own mask."""
-
-    def search_each(self, queries, k, programs, program_of_query, want64=False, return_routes=False):
-        nq = queries.shape[0]
-        labels = np.empty((nq, k), np.int64)
-        dist = np.empty((nq, k), np.float32)
-        counts = np.empty(nq, np.int32)
-        d64 = np.empty((nq, k))
-        for i, p in enumerate(np.asarray(program_of_query).tolist()):
-            where = None if p < 0 else programs[p]
-            labels[i:i + 1], dist[i:i + 1], counts[i:i + 1], d64[i:i + 1] = self.search64(queries[i:i + 1], k, where=where)
-        out = (labels, dist, counts, d64) if want64 else (labels, dist, counts)
-        return out + (np.zeros(len(programs), np.int32),) if return_routes else out
-
-    def count_each(self, programs):
-        return np.array([self.where_count(p) for p in programs], dtype=np.int64)
 
 
 def eidx(space="l2", **kw):

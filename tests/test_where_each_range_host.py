@@ -11,7 +11,7 @@ import pytest
 from mlvectordb_amd import Index, InMemoryStorage, QueryProcessor, Vector, VectorDTO, _native
 from mlvectordb_amd import where as W
 from mlvectordb_amd.engine import HipScanEngine, RangeHits, stitch_range_hits
-from tests.where_helpers import SCHEMA, WhereOracleEngine, py_match, random_filter, random_metadata
+from tests.where_helpers import SCHEMA, EachRangeOracleEngine, py_match, random_filter, random_metadata
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRY = "mlvdb_range_batch_packed_where_each"
@@ -181,19 +181,6 @@ def test_range_each_stitches_chunked_calls_in_query_order():
 
 
 # ---------------------------------------------------------------- Index / QueryProcessor over the oracle engine
-class EachRangeOracleEngine(WhereOracleEngine):
-    """``WhereOracleEngine`` + ``range_each``: every query ranged alone under its own mask; every call is counted."""
-
-    each_calls = 0
-
-    def range_each(self, queries, radius, capacity, programs, program_of_query, truncate=False, return_routes=False):
-        type(self).each_calls += 1
-        out = []
-        for i, p in enumerate(np.asarray(program_of_query).tolist()):
-            out.append(self.range(queries[i:i + 1], radius, capacity, truncate, where=None if p < 0 else programs[p])[0])
-        return (out, np.zeros(len(programs), np.int32)) if return_routes else out
-
-
 def _filled(space="l2", seed=11, n=320, d=8):
     rng = np.random.default_rng(seed)
     index = Index(space=space, engine_factory=EachRangeOracleEngine, attributes=SCHEMA)

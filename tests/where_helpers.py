@@ -162,6 +162,38 @@ class WhereOracleEngine(OracleScanEngine):
         return [(l[:capacity], d[:capacity]) for l, d in hits] if truncate else hits
 
 
+class EachOracleEngine(WhereOracleEngine):
+    """``WhereOracleEngine`` + ``search_each`` / ``count_each``: every query searched alone under its own mask."""
+
+    def search_each(self, queries, k, programs, program_of_query, want64=False, return_routes=False):
+        nq = queries.shape[0]
+        labels = np.empty((nq, k), np.int64)
+        dist = np.empty((nq, k), np.float32)
+        counts = np.empty(nq, np.int32)
+        d64 = np.empty((nq, k))
+        for i, p in enumerate(np.asarray(program_of_query).tolist()):
+            where = None if p < 0 else programs[p]
+            labels[i:i + 1], dist[i:i + 1], counts[i:i + 1], d64[i:i + 1] = self.search64(queries[i:i + 1], k, where=where)
+        out = (labels, dist, counts, d64) if want64 else (labels, dist, counts)
+        return out + (np.zeros(len(programs), np.int32),) if return_routes else out
+
+    def count_each(self, programs):
+        return np.array([self.where_count(p) for p in programs], dtype=np.int64)
+
+
+class EachRangeOracleEngine(WhereOracleEngine):
+    """``WhereOracleEngine`` + ``range_each``: every query ranged alone under its own mask; every call is counted."""
+
+    each_calls = 0
+
+    def range_each(self, queries, radius, capacity, programs, program_of_query, truncate=False, return_routes=False):
+        type(self).each_calls += 1
+        out = []
+        for i, p in enumerate(np.asarray(program_of_query).tolist()):
+            out.append(self.range(queries[i:i + 1], radius, capacity, truncate, where=None if p < 0 else programs[p])[0])
+        return (out, np.zeros(len(programs), np.int32)) if return_routes else out
+
+
 # ---------------------------------------------------------------- random data and filters
 def random_metadata(rng, n, unseen=("zydeco",)):
     out = []
