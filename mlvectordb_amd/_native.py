@@ -126,6 +126,13 @@ FACET_SIGNATURES = {
                                    C.POINTER(C.c_int64)]),
 }
 
+# include/mlvdb_order.h: the top rows by an attribute column, ranked on the device
+ORDER_MAX_ROWS = 4096
+ORDER_SIGNATURES = {
+    "mlvdb_where_ordered": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Where), C.c_int64, C.c_int64, _P, _P,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -155,7 +162,8 @@ def load() -> C.CDLL:
             f"There is no CPU fallback for the search path.")
     lib = C.CDLL(str(path))
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
-                                      **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **FACET_SIGNATURES}.items():
+                                      **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **FACET_SIGNATURES,
+                                      **ORDER_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

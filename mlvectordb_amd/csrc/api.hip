@@ -120,6 +120,9 @@ struct mlvdb_index {
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
+    // ordered queries (mlvdb_order.h): the call's state, one histogram per digit pass, the collected (key, label) pairs and the
+    // ranked window -- sized by MLVDB_ORDER_MAX_ROWS and the histograms, never by the corpus
+    DevBuf order_ws;
     // fp16 row-major shadow for the mid bounds (kernels_refine.hip): built lazily by the first range query / top_k > 64 search
     DevBuf x16, s16, rowerr16, picks, npicks;
     int64_t l2_rows = 0;      // rows [0, l2_rows) of the fp16 shadow are current (0 after compact / reset / regrowth)
@@ -1169,7 +1172,7 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     h->where_cnt.release();
     for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
                       &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel,
-                      &h->facet_tab, &h->facet_misc})
+                      &h->facet_tab, &h->facet_misc, &h->order_ws})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
@@ -3032,6 +3035,77 @@ int mlvdb_facet_bins(mlvdb_index* h, int32_t attr, const mlvdb_where* where, con
     for (int32_t i = 0; i <= n_edges; ++i) out_counts[i] = 0;
     if (h->total == 0) return MLVDB_OK;
     return facet_bins_impl(h, attr, where, edges, n_edges, out_counts, matched, absent);
+    });
+}
+
+// ---- ordered metadata queries (mlvdb_order.h)
+extern "C++" {
+namespace {
+// The whole chain is enqueued at once: the kernels hand their state to each other on the device (OrderState), and the digit
+// passes behind a finished selection return at once.  A program is evaluated once into the row mask (where_run), which every
+// pass then reads at one byte per row instead of the norms and the program's columns.
+int where_ordered_impl(mlvdb_index* h, int32_t attr, int32_t descending, const mlvdb_where* where, int64_t offset,
+                       int64_t limit, int64_t* out_labels, void* out_values, int64_t* n_out, int64_t* matched,
+                       int64_t* absent) {
+    hipStream_t s = h->stream;
+    if (where)
+        if (int rc = where_run(h, where, nullptr)) return rc;
+    // [state | histograms of the passes | keys | out labels | out values | labels]
+    constexpr size_t kStateBytes = (sizeof(OrderState) + 63) / 64 * 64;
+    constexpr size_t kHistBytes = (size_t)kOrderPasses * kOrderBins * sizeof(unsigned long long);
+    HIP_TRY(h, h->order_ws.ensure(kStateBytes + kHistBytes + (size_t)kOrderMaxRows * (3 * sizeof(int64_t) + sizeof(uint32_t))));
+    OrderState* st = h->order_ws.as<OrderState>();
+    unsigned long long* hist = reinterpret_cast<unsigned long long*>(h->order_ws.as<char>() + kStateBytes);
+    unsigned long long* keys = hist + (size_t)kOrderPasses * kOrderBins;
+    int64_t* labels_d = reinterpret_cast<int64_t*>(keys + kOrderMaxRows);
+    int64_t* values_d = labels_d + kOrderMaxRows;
+    uint32_t* clabels = reinterpret_cast<uint32_t*>(values_d + kOrderMaxRows);
+    const uint8_t* mask = where ? h->row_mask.as<uint8_t>() : nullptr;
+    const int64_t* col = h->attr_col[attr];
+    const int32_t type = h->attr_type[attr];
+    HIP_TRY(h, hipMemsetAsync(st, 0, kStateBytes + kHistBytes, s));
+    for (int32_t pass = 0; pass < kOrderPasses; ++pass) {
+        unsigned long long* hp = hist + (size_t)pass * kOrderBins;
+        HIP_TRY(h, launch_order_hist(mask, h->rn, col, type, descending, h->total, pass, hp, st, s));
+        HIP_TRY(h, launch_order_scan(hp, pass, offset, limit, st, s));
+    }
+    HIP_TRY(h, launch_order_collect(mask, h->rn, col, type, descending, h->total, st, keys, clabels, s));
+    HIP_TRY(h, launch_order_sort(keys, clabels, col, h->total, offset, st, labels_d, values_d, s));
+    OrderState host{};
+    HIP_TRY(h, hipMemcpyAsync(&host, st, sizeof host, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *matched = (int64_t)host.matched;
+    *absent = (int64_t)host.absent;
+    const int64_t candidates = *matched - *absent;
+    const int64_t n = std::max<int64_t>(0, std::min(candidates - offset, limit));
+    if (!host.done || host.overflow || host.cursor != host.n_collect || (int64_t)host.n_out != n ||
+        (n > 0 && (int64_t)host.want != offset + n))
+        return fail(h, MLVDB_ERR_INTERNAL, "where_ordered: the selection and the collected rows disagree");
+    *n_out = n;
+    if (n == 0) return MLVDB_OK;
+    HIP_TRY(h, hipMemcpyAsync(out_labels, labels_d, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_values, values_d, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_where_ordered(mlvdb_index* h, int32_t attr, int32_t descending, const mlvdb_where* where, int64_t offset,
+                        int64_t limit, int64_t* out_labels, void* out_values, int64_t* n_out, int64_t* matched,
+                        int64_t* absent) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = attr_check(h, attr))) return rc;
+    if (offset < 0 || limit < 1 || limit > MLVDB_ORDER_MAX_ROWS || offset > MLVDB_ORDER_MAX_ROWS - limit)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "offset >= 0, limit >= 1 and offset + limit <= MLVDB_ORDER_MAX_ROWS");
+    if (!out_labels || !out_values || !n_out || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (where && (rc = where_prepare(h, where))) return rc;
+    *n_out = *matched = *absent = 0;
+    if (h->total == 0) return MLVDB_OK;
+    return where_ordered_impl(h, attr, descending != 0, where, offset, limit, out_labels, out_values, n_out, matched, absent);
     });
 }
 

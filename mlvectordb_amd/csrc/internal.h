@@ -13,6 +13,7 @@
 #include "../../include/mlvdb_where_each_range.h"
 #include "../../include/mlvdb_distinct.h"
 #include "../../include/mlvdb_facet.h"
+#include "../../include/mlvdb_order.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -418,5 +419,44 @@ hipError_t launch_facet_collect(const FacetTable& t, long long* out_keys, unsign
 hipError_t launch_facet_bins(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* col,
                              int32_t type, int64_t total, const int64_t* edges, int32_t n_edges, unsigned long long* bins,
                              unsigned long long* ctr, hipStream_t s);
+
+// ---------------------------------------------------------------- ordered metadata queries (kernels_order.hip)
+// A row's composite key: its value mapped to an order-preserving uint64 (complemented for a descending call) above its
+// 32-bit label -- 96 bits, unique per row.  The N-th smallest composite is found by most-significant-digit histogram passes.
+constexpr int kOrderMaxRows = MLVDB_ORDER_MAX_ROWS;
+constexpr int kOrderDigitBits = 11;                   // 2048 bins: 8 KiB of LDS per block, 16 KiB per pass in HBM
+constexpr int kOrderBins = 1 << kOrderDigitBits;
+constexpr int kOrderPasses = 9;                       // 8 digits of 11 bits and one of 8: 96 bits
+constexpr int kOrderMaxBlocks = 1024;                 // blocks of a pass over the index (each flushes <= kOrderBins adds)
+// low bits of the composite below the digit of pass p (the last digit is the 8 bits left over)
+__host__ __device__ inline int order_shift(int pass) { return pass < 8 ? 85 - kOrderDigitBits * pass : 0; }
+// What the kernels of one call hand to each other and, at the end, to the host (zeroed by the call before its first launch)
+struct OrderState {
+    unsigned long long matched, absent;  // first pass
+    unsigned long long below;            // candidates whose composite lies below the selected bucket
+    unsigned long long want;             // N = min(offset + limit, candidates): the rank that is looked for, 1-based
+    unsigned long long key;              // the selected bucket: the digits fixed so far, in place, the bits below `low_bits`
+    uint32_t label;                      //   of key:label zero
+    uint32_t low_bits;                   // bits of the composite not fixed yet
+    uint32_t done;                       // the bucket and everything below it fit one block: no further digit pass runs
+    uint32_t n_collect;                  // ... that many rows: what the collect pass must find (0: nothing to return)
+    uint32_t cursor;                     // rows the collect pass met (may exceed kOrderMaxRows: the excess is not stored)
+    uint32_t overflow;                   // ... and then this is set
+    uint32_t passes;                     // digit passes that ran
+    uint32_t n_out;                      // rows written to the output buffers
+};
+// One digit pass: the candidates (live rows -- of `mask` when given, else with a finite norm -- with a present value) inside the
+// selected bucket counted by their digit into hist[kOrderBins]; pass 0 also counts matched / absent.  Nothing runs once
+// st->done is set.  Then the one-block scan: the digit that holds rank st->want, st updated.
+hipError_t launch_order_hist(const uint8_t* mask, const float* rn, const int64_t* col, int32_t type, int32_t descending,
+                             int64_t total, int32_t pass, unsigned long long* hist, OrderState* st, hipStream_t s);
+hipError_t launch_order_scan(const unsigned long long* hist, int32_t pass, int64_t offset, int64_t limit, OrderState* st,
+                             hipStream_t s);
+// The candidates at or below the selected bucket -> keys / labels[kOrderMaxRows] through st->cursor
+hipError_t launch_order_collect(const uint8_t* mask, const float* rn, const int64_t* col, int32_t type, int32_t descending,
+                                int64_t total, OrderState* st, unsigned long long* keys, uint32_t* labels, hipStream_t s);
+// One workgroup sorts them and writes ranks [offset, st->want) to out_labels / out_values[kOrderMaxRows] (values: col[label])
+hipError_t launch_order_sort(const unsigned long long* keys, const uint32_t* labels, const int64_t* col, int64_t total,
+                             int64_t offset, OrderState* st, int64_t* out_labels, int64_t* out_values, hipStream_t s);
 
 }  // namespace mlvdb

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "wave_peel.h"
 #include "where_common.h"
 
 namespace mlvdb {
@@ -12,35 +13,6 @@ namespace mlvdb {
 namespace {
 
 constexpr unsigned long long kFacetEmpty = 0x8000000000000000ull;  // INT64_MIN: never a present value
-
-// Wave peel: the lanes that hold the first active lane's key are counted by one add of their popcount, for at most
-// kFacetPeelRounds leading keys; a round that found its key on a single lane ends the peel (a column of many values: the
-// lanes left add one each).  A bool column is done in two rounds, six genres in six, and 64 different values cost one round.
-// Every lane of the wave must call this (ballots); add(key, n) runs on one lane per key, all of them at one call site after
-// the rounds (a lane leads at most once: its own key leaves with it).
-template <class Add>
-__device__ __forceinline__ void wave_peel_add(bool has, int64_t key, Add&& add) {
-    const int lane = threadIdx.x & 63;
-    uint32_t mine = 1;  // what this lane adds under its key, if it adds
-    bool adds = false;
-    for (int r = 0; r < kFacetPeelRounds; ++r) {
-        const unsigned long long active = __ballot(has);
-        if (!active) break;
-        const int leader = __ffsll((long long)active) - 1;
-        const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)key, leader);
-        const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)key >> 32), leader);
-        const int64_t lead = (int64_t)(((uint64_t)hi << 32) | lo);
-        const bool same = has && key == lead;
-        const int n = __popcll(__ballot(same));
-        if (lane == leader) {
-            mine = (uint32_t)n;
-            adds = true;
-        }
-        has = has && !same;
-        if (n == 1) break;
-    }
-    if (adds || has) add(key, mine);
-}
 
 // Open addressing, linear probing: the key is claimed by a 64-bit compare-and-swap, the count added behind it.
 __device__ __forceinline__ bool lds_insert(unsigned long long* keys, uint32_t* counts, int64_t key, uint32_t n) {

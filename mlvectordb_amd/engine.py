@@ -393,6 +393,24 @@ class HipScanEngine:
             C.byref(matched), C.byref(absent)), "facet_bins")
         return counts, int(matched.value), int(absent.value)
 
+    # -- ordered metadata queries (include/mlvdb_order.h) -------------------------------
+    def where_ordered(self, attr: int, limit: int, where=None, descending: bool = False, offset: int = 0):
+        """Ranks ``[offset, offset + limit)`` of the live rows (those the compiled ``where.Program`` matches, when one is
+        given) that hold a value of column ``attr``, by that value -- ascending, or descending -- and rows of equal value by
+        ascending label: (labels int64 [n_out], values int64 or float64 [n_out] by the column's type, matched, absent).
+        ``offset + limit <= _native.ORDER_MAX_ROWS``; the ranking is done on the device, only the window comes back."""
+        limit, offset = int(limit), int(offset)
+        kind = self._attr_kinds.get(int(attr), "int64")
+        size = max(0, min(limit, _native.ORDER_MAX_ROWS))
+        labels = np.empty(size, dtype=np.int64)
+        values = np.empty(size, dtype=np.float64 if kind == "float64" else np.int64)
+        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_where_ordered(
+            self._h, int(attr), 1 if descending else 0, None if w is None else C.byref(w), offset, limit,
+            labels.ctypes.data, values.ctypes.data, C.byref(n), C.byref(matched), C.byref(absent)), "where_ordered")
+        return labels[: n.value].copy(), values[: n.value].copy(), int(matched.value), int(absent.value)
+
     def search64(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None, where=None):
         """kNN; ``mask`` (optional, one byte per row, non-zero = allowed) restricts the search to those rows, ``where``
         (optional, a compiled ``where.Program``) to the rows it matches, evaluated on the device.

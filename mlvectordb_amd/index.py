@@ -648,13 +648,78 @@ class Index:
         counts = np.asarray(ns.engine.count_each(programs), dtype=np.int64)
         return [int(counts[j]) for j in of]
 
-    def query_by_metadata(self, namespace: str, where: Mapping) -> List[UUID]:
-        """UUIDs of the live rows satisfying ``where``, in insertion order (README.md:252,274: ``query_by_metadata``)."""
+    def query_by_metadata(self, namespace: str, where: Mapping, *, order_by: Optional[str] = None, descending: bool = False,
+                          limit: Optional[int] = None, offset: int = 0) -> List[UUID]:
+        """UUIDs of the live rows satisfying ``where``, in insertion order (README.md:252,274: ``query_by_metadata``).  With
+        ``order_by`` (and a ``limit``): ``top_by(namespace, order_by, limit, where, ...)["ids"]`` -- the rows that hold a value
+        of that attribute, ranked on the device."""
+        self.check_order_keywords(order_by, descending, limit, offset)
+        if order_by is not None:
+            return self.top_by(namespace, order_by, limit, where, descending=descending, offset=offset)["ids"]
         program = self._compile(namespace, where)
         ns = self._ns.get(namespace)
         if ns is None or ns.total == 0:
             return []
         return ns.ids.uuids_at(ns.engine.where_labels(program)).tolist()
+
+    # ------------------------------------------------------------------ additive: ordered metadata queries on the device
+    _MAX_ORDER_ROWS = 4096  # MLVDB_ORDER_MAX_ROWS
+
+    @staticmethod
+    def check_order_keywords(order_by, descending, limit, offset) -> None:
+        """The refusals of ``query_by_metadata``'s ordering keywords: they come with ``order_by`` (and a ``limit``) or not at all."""
+        if order_by is None:
+            if descending is not False or limit is not None or not (offset == 0 and not isinstance(offset, bool)):
+                raise ValueError("query_by_metadata: descending, limit and offset need order_by")
+        elif limit is None:
+            raise ValueError("query_by_metadata: order_by needs a limit (at most 4096 rows are ranked per call)")
+
+    def check_top_by_args(self, by, limit, descending=False, offset=0) -> str:
+        """The refusals of ``top_by`` that need no namespace -> the column kind of ``by`` ("int", "float" or "bool")."""
+        if not isinstance(by, str) or by not in self._attributes:
+            raise ValueError(f"top_by: {by!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        kind = self._attributes[by]
+        if kind == "str":
+            raise ValueError(f"top_by: attribute {by!r} is a str column; its codes are in order of first use, not in lexical "
+                             f"order, so ranking needs an int, float or bool attribute")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
+            raise ValueError(f"top_by: limit must be an int >= 1 (got {limit!r})")
+        if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
+            raise ValueError(f"top_by: offset must be an int >= 0 (got {offset!r})")
+        if int(offset) + int(limit) > self._MAX_ORDER_ROWS:
+            raise ValueError(f"top_by: offset + limit must be <= {self._MAX_ORDER_ROWS} (got {int(offset) + int(limit)})")
+        if not isinstance(descending, (bool, np.bool_)):
+            raise ValueError(f"top_by: descending must be a bool (got {descending!r})")
+        return kind
+
+    @staticmethod
+    def decode_order_values(kind: str, values) -> list:
+        """Column values as ``top_by`` returns them: ``True`` / ``False`` for a bool attribute, Python ints or floats."""
+        values = values.tolist() if isinstance(values, np.ndarray) else list(values)
+        return [bool(v) for v in values] if kind == "bool" else values
+
+    def top_by(self, namespace: str, by: str, limit: int, where: Optional[Mapping] = None, *, descending: bool = False,
+               offset: int = 0):
+        """Ranks ``[offset, offset + limit)`` of the live rows of ``namespace`` (those the dict filter ``where`` matches,
+        when one is given) that hold a value of the declared ``int`` / ``float`` / ``bool`` attribute ``by``, ranked on the
+        device (include/mlvdb_order.h) by that value -- ascending, or ``descending`` -- and rows of equal value in insertion
+        order: ``{"ids": [UUID, ...], "values": [...], "matched": live matching rows, "absent": those of them without a
+        value}``, the values decoded (``True`` / ``False``, ints, floats; ``-0.0`` and ``0.0`` tie).  ``offset + limit`` is at
+        most 4096.  An unknown or empty namespace gives no rows and zeros."""
+        kind = self.check_top_by_args(by, limit, descending, offset)
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"top_by: where must be one dict filter or None (got {type(where).__name__})")
+        program = None if where is None else self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total == 0:
+            return {"ids": [], "values": [], "matched": 0, "absent": 0}
+        where_ordered = getattr(ns.engine, "where_ordered", None)
+        if where_ordered is None:
+            raise ValueError("top_by needs an engine with where_ordered (a single-device namespace)")
+        labels, values, matched, absent = where_ordered(list(self._attributes).index(by), int(limit), where=program,
+                                                        descending=bool(descending), offset=int(offset))
+        return {"ids": ns.ids.uuids_at(labels).tolist(), "values": self.decode_order_values(kind, values), "matched": matched,
+                "absent": absent}
 
     # ------------------------------------------------------------------ additive: facet counts and histograms on the device
     _MAX_FACET_VALUES = 1 << 20  # MLVDB_FACET_MAX_VALUES

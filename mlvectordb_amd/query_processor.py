@@ -217,11 +217,39 @@ class QueryProcessor:
             return self._index.count(namespace, where)
         return sum(1 for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata))
 
-    def query_by_metadata(self, where, namespace: str = "default") -> List[UUID]:
-        """Ids of the vectors of ``namespace`` matching ``where``, in insertion order."""
+    def query_by_metadata(self, where, namespace: str = "default", *, order_by=None, descending: bool = False, limit=None,
+                          offset: int = 0) -> List[UUID]:
+        """Ids of the vectors of ``namespace`` matching ``where``, in insertion order; with ``order_by`` (and a ``limit``):
+        ``top_by(order_by, limit, where, ...)["ids"]``."""
+        if order_by is not None or descending is not False or limit is not None or offset != 0 or isinstance(offset, bool):
+            self._index.check_order_keywords(order_by, descending, limit, offset)
+            return self.top_by(order_by, limit, where, namespace, descending=descending, offset=offset)["ids"]
         if isinstance(where, Mapping):
             return self._index.query_by_metadata(namespace, where)
         return [v.id for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
+
+    # ---- additive: ordered metadata queries (Index.top_by; no reference code)
+    def top_by(self, by: str, limit: int, where=None, namespace: str = "default", *, descending: bool = False,
+               offset: int = 0):
+        """``Index.top_by`` of ``namespace``: a dict filter (or no filter) is ranked on the device; a predicate is ranked over
+        the storage's metadata on the host, as ``facets`` does -- the values ``Index.extract_attributes`` would store, rows
+        of equal value in insertion order -- with the same answer format."""
+        if where is None or isinstance(where, Mapping):
+            return self._index.top_by(namespace, by, limit, where, descending=descending, offset=offset)
+        if not callable(where):
+            raise ValueError(f"top_by: where must be a dict filter, a predicate or None (got {type(where).__name__})")
+        kind = self._index.check_top_by_args(by, limit, descending, offset)
+        picked = [v for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
+        values = self._index.extract_attributes([v.metadata for v in picked])[by]
+        if kind == "float":  # the column stores doubles: an int literal ranks as its double
+            values = [None if x is None else float(x) for x in values]
+        ranked = [(x, i) for i, x in enumerate(values) if x is not None and x == x]
+        # a stable sort keeps insertion order among equal values (-0.0 == 0.0), and reverse=True keeps it too
+        ranked.sort(key=lambda p: p[0], reverse=bool(descending))
+        window = ranked[int(offset):int(offset) + int(limit)]
+        return {"ids": [picked[i].id for _, i in window],
+                "values": self._index.decode_order_values(kind, [x for x, _ in window]),
+                "matched": len(picked), "absent": len(picked) - len(ranked)}
 
     # ---- additive: facet counts and histograms (Index.facets / Index.histogram; no reference code)
     def _host_column(self, by: str, where, namespace: str):
