@@ -133,6 +133,14 @@ ORDER_SIGNATURES = {
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
+# include/mlvdb_mmr.h: diversified kNN -- greedy maximal-marginal-relevance selection over the plain search's candidates
+MMR_MAX_FETCH = 1024
+MMR_CHUNK = 1024  # queries per round of plain search + selection inside one native call (api.hip: kMmrChunk)
+MMR_SIGNATURES = {
+    "mlvdb_search_batch_mmr": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(Where),
+                                         _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -163,7 +171,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **FACET_SIGNATURES,
-                                      **ORDER_SIGNATURES}.items():
+                                      **ORDER_SIGNATURES, **MMR_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

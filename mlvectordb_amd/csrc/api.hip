@@ -117,6 +117,9 @@ struct mlvdb_index {
     // distinct kNN (mlvdb_distinct.h): a chunk's queries, its ranked lists from the plain search, its outputs, and the
     // flagged queries' list + counter -- all sized by the chunk (<= kDistinctChunk queries), k and L, never by the corpus
     DevBuf dist_q, dist_list, dist_out, dist_sel;
+    // diversified kNN (mlvdb_mmr.h): a chunk's queries, its ranked candidate lists from the plain search and its outputs --
+    // sized by the chunk (<= kMmrChunk queries), k and fetch_k, never by the corpus
+    DevBuf mmr_q, mmr_list, mmr_out;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -1172,7 +1175,7 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     h->where_cnt.release();
     for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
                       &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel,
-                      &h->facet_tab, &h->facet_misc, &h->order_ws})
+                      &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->facet_tab, &h->facet_misc, &h->order_ws})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
@@ -2887,6 +2890,93 @@ int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq
     if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     auto call = [&]() {
         return distinct_impl(h, queries, nq, k, attr, max_groups, out_labels, out_dist, out_counts, out_dist64, out_groups);
+    };
+    if (!where) return nq == 0 ? MLVDB_OK : call();
+    rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy
+    if (rc || nq == 0) return rc;
+    if (h->total == 0) return call();
+    return with_row_mask(h, nq, call);
+    });
+}
+
+// ---- diversified kNN (mlvdb_mmr.h)
+extern "C++" {
+namespace {
+constexpr int64_t kMmrChunk = 1024;  // queries per round of plain search + selection (bounds the workspaces)
+
+// The validated call (h->rn is the masked copy when a program restricts the rows).  Per chunk of queries: the plain device
+// search for fetch_k neighbours (fp64 distances wanted) -> one launch of the select kernel -> outputs to the host.
+int mmr_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t fetch_k, double lambda, int64_t* out_labels,
+             float* out_dist, int32_t* out_counts, double* out_dist64, int32_t* out_rank, double* out_objective) {
+    hipStream_t s = h->stream;
+    if (h->total == 0 || h->total == h->deleted) {
+        for (int64_t i = 0; i < nq * k; ++i) {
+            out_labels[i] = -1;
+            out_dist[i] = __builtin_inff();
+            if (out_dist64) out_dist64[i] = __builtin_inf();
+            if (out_rank) out_rank[i] = -1;
+            if (out_objective) out_objective[i] = __builtin_inf();
+        }
+        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        return MLVDB_OK;
+    }
+    const double one_minus_lambda = 1.0 - lambda;  // formed once, here
+    for (int64_t q0 = 0; q0 < nq; q0 += kMmrChunk) {
+        const int32_t n = (int32_t)std::min<int64_t>(kMmrChunk, nq - q0);
+        const size_t nk = (size_t)n * k, nl = (size_t)n * fetch_k;
+        HIP_TRY(h, h->mmr_q.ensure((size_t)n * h->dim * sizeof(float)));
+        HIP_TRY(h, h->mmr_list.ensure(nl * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
+        HIP_TRY(h, h->mmr_out.ensure(nk * (2 * sizeof(double) + sizeof(int64_t) + sizeof(float) + sizeof(int32_t)) +
+                                     (size_t)n * sizeof(int32_t)));
+        float* dq = h->mmr_q.as<float>();
+        double* l_d64 = h->mmr_list.as<double>();  // [d64 | labels | dist | counts]
+        int64_t* l_lab = reinterpret_cast<int64_t*>(l_d64 + nl);
+        float* l_dist = reinterpret_cast<float*>(l_lab + nl);
+        int32_t* l_cnt = reinterpret_cast<int32_t*>(l_dist + nl);
+        double* o_d64 = h->mmr_out.as<double>();  // [d64 | objective | labels | dist | rank | counts]
+        double* o_obj = o_d64 + nk;
+        int64_t* o_lab = reinterpret_cast<int64_t*>(o_obj + nk);
+        float* o_dist = reinterpret_cast<float*>(o_lab + nk);
+        int32_t* o_rank = reinterpret_cast<int32_t*>(o_dist + nk);
+        int32_t* o_cnt = o_rank + nk;
+        HIP_TRY(h, hipMemcpyAsync(dq, queries + (size_t)q0 * h->dim, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
+        if (int rc = search_device_impl(h, dq, n, fetch_k, l_lab, l_dist, l_cnt, l_d64, s, false)) return rc;
+        HIP_TRY(h, launch_mmr_select(h->X, h->dim, h->ld, h->space, l_lab, l_dist, l_d64, l_cnt, n, fetch_k, k, lambda,
+                                     one_minus_lambda, o_lab, o_dist, o_cnt, o_d64, o_rank, o_obj, s));
+        const size_t at = (size_t)q0 * k;
+        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
+        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o_d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_objective) HIP_TRY(h, hipMemcpyAsync(out_objective + at, o_obj, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_rank) HIP_TRY(h, hipMemcpyAsync(out_rank + at, o_rank, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o_lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_dist + at, o_dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_mmr(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t fetch_k, double lambda,
+                           const mlvdb_where* where, int64_t* out_labels, float* out_dist, int32_t* out_counts,
+                           double* out_dist64, int32_t* out_rank, double* out_objective) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched (the program: where_run validates it before its first launch)
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "mmr: k above MLVDB_MAX_TOPK");
+    if (fetch_k < k) return fail(h, MLVDB_ERR_INVALID_ARG, "mmr: fetch_k below k");
+    if (fetch_k > kMmrMaxFetch) return fail(h, MLVDB_ERR_UNSUPPORTED, "mmr: fetch_k above MLVDB_MMR_MAX_FETCH");
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(h, MLVDB_ERR_INVALID_ARG, "mmr: lambda outside [0, 1]");
+    if (mmr_select_lds(h->ld, fetch_k) > 64 * 1024)
+        return fail(h, MLVDB_ERR_UNSUPPORTED, "mmr: the picked row and fetch_k candidates need more than 64 KiB of LDS");
+    if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    auto call = [&]() {
+        return mmr_impl(h, queries, nq, k, fetch_k, lambda, out_labels, out_dist, out_counts, out_dist64, out_rank,
+                        out_objective);
     };
     if (!where) return nq == 0 ? MLVDB_OK : call();
     rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy

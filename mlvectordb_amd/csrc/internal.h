@@ -14,6 +14,7 @@
 #include "../../include/mlvdb_distinct.h"
 #include "../../include/mlvdb_facet.h"
 #include "../../include/mlvdb_order.h"
+#include "../../include/mlvdb_mmr.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -387,6 +388,17 @@ hipError_t launch_distinct_scan(const DistinctArgs& a, const ExactPlan& p, hipSt
 hipError_t launch_distinct_merge(const DistinctEntry* partial, int32_t nq_sel, const int32_t* nq_sel_dev, const int32_t* qsel,
                                  int32_t nblk, int32_t k, int32_t k_eff, int64_t* out_labels, float* out_dist,
                                  int32_t* out_counts, double* out_d64, int64_t* out_groups, hipStream_t s);
+
+// ---------------------------------------------------------------- diversified kNN (kernels_mmr.hip)
+constexpr int kMmrMaxFetch = MLVDB_MMR_MAX_FETCH;  // longest candidate list the selection walks (the plain search's top_k)
+// LDS of one block of the select kernel: the picked row as fp64 [ld] + dq / mind / picked flag per candidate (<= 64 KiB)
+size_t mmr_select_lds(int32_t ld, int32_t fetch_k);
+// One block per query over its ranked list (l_lab / l_dist / l_d64: [nq][fetch_k], l_cnt[q] valid entries): the greedy
+// selection of mlvdb_mmr.h, outputs [nq][k] in pick order with padded tails, out_counts[q] = min(k, l_cnt[q]).
+hipError_t launch_mmr_select(const float* X, int32_t dim, int32_t ld, int32_t space, const int64_t* l_lab, const float* l_dist,
+                             const double* l_d64, const int32_t* l_cnt, int32_t nq, int32_t fetch_k, int32_t k, double lambda,
+                             double one_minus_lambda, int64_t* out_labels, float* out_dist, int32_t* out_counts,
+                             double* out_d64, int32_t* out_rank, double* out_obj, hipStream_t s);
 
 // ---------------------------------------------------------------- facet counts and histograms (kernels_facet.hip)
 constexpr int kFacetLdsSlots = 4096;  // per-block table of the value kernel: int64 key + uint32 count = 48 KiB, three blocks per CU

@@ -28,6 +28,7 @@
 
 #include "bound_common.h"
 #include "internal.h"
+#include "query_norm.h"
 #include "scan_common.h"
 
 namespace mlvdb {
@@ -1824,12 +1825,11 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
             s = __builtin_fma((double)v, (double)v, s);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    s = query_norm_wave_sum(s);
     if (lane == 0) dred[wave] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double nrm = __builtin_sqrt((dred[0] + dred[1]) + (dred[2] + dred[3]));
-        const double aux = a.space == kSpaceCosine ? 1.0 / (nrm + 1e-30) : nrm;
+        const double aux = query_aux_from_sums(dred, a.space);
         if (real) qaux[q] = aux;
         s_inv = a.space == kSpaceCosine ? aux : 1.0 / (aux + 1e-30);
     }

@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "query_norm.h"
 
 namespace mlvdb {
 
@@ -141,12 +142,11 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict
         dst[c] = v;
         s = __builtin_fma((double)v, (double)v, s);
     }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    s = query_norm_wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double nrm = __builtin_sqrt((red[0] + red[1]) + (red[2] + red[3]));
-        const double aux = space == kSpaceCosine ? 1.0 / (nrm + 1e-30) : nrm;
+        const double aux = query_aux_from_sums(red, space);  // (query_norm.h: shared with the kernels that take a row as a query)
         qaux[q] = aux;
         inv_s = space == kSpaceCosine ? aux : 1.0 / (aux + 1e-30);  // what filter_prep_kernel multiplies by
     }

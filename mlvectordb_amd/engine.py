@@ -358,6 +358,31 @@ class HipScanEngine:
             groups.ctypes.data), "search_batch_distinct")
         return (labels, dist, counts, d64, groups) if want64 else (labels, dist, counts, groups)
 
+    # -- diversified kNN (include/mlvdb_mmr.h) --------------------------------------------
+    def search_mmr(self, queries: np.ndarray, k: int, fetch_k: int, lam: float, where=None, want64: bool = False):
+        """Greedy maximal-marginal-relevance selection of ``k`` (<= 64) hits among the ``fetch_k`` (<= 1024) nearest rows
+        of each query -- those the optional compiled ``where.Program`` matches -- on the device: the first pick is the
+        nearest row, each further pick minimises ``lam * d(query, i) - (1 - lam) * min over the picks s of d(s, i)``, ties
+        to the better-ranked candidate.  Returns (labels int64 [nq, k], dist float32, counts int32, dist64 float64 or
+        ``None`` without ``want64``, rank int32 [nq, k]: the pick's position among the candidates, objective float64
+        [nq, k]), all in pick order; padding is label -1 / +inf / rank -1 / objective +inf."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        nq = queries.shape[0]
+        labels = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.int32)
+        d64 = np.empty((nq, k), dtype=np.float64) if want64 else None
+        rank = np.empty((nq, k), dtype=np.int32)
+        objective = np.empty((nq, k), dtype=np.float64)
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_search_batch_mmr(
+            self._h, queries.ctypes.data, nq, int(k), int(fetch_k), float(lam), None if w is None else C.byref(w),
+            labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
+            rank.ctypes.data, objective.ctypes.data), "search_batch_mmr")
+        return labels, dist, counts, d64, rank, objective
+
     # -- facet counts and histograms (include/mlvdb_facet.h) ---------------------------
     def facet_values(self, attr: int, max_values: int, where=None):
         """The distinct present values of int64 column ``attr`` among the live rows (those the compiled ``where.Program``

@@ -451,7 +451,8 @@ class Index:
 
     def search_many(self, queries, top_k: int, namespace: str, metric: str,
                     allowed_ids: Optional[Iterable[UUID]] = None, where: Optional[Mapping] = None,
-                    distinct: Optional[str] = None) -> BatchHits:
+                    distinct: Optional[str] = None, mmr_lambda: Optional[float] = None,
+                    fetch_k: Optional[int] = None) -> BatchHits:
         """kNN for a batch of queries in one corpus scan.
 
         ``queries`` is an ``[nq, dim]`` array or a sequence of ``VectorDTO``.  Each entry of
@@ -464,7 +465,17 @@ class Index:
         ``distinct`` (additive: the name of a declared ``int`` / ``str`` / ``bool`` attribute) returns one hit per value of
         that attribute -- the nearest row of each of the ``top_k`` (<= 64) nearest groups, rows without a value left out
         (include/mlvdb_distinct.h); an optional single dict ``where`` restricts the rows first.
+        ``mmr_lambda`` (additive: a number in [0, 1]) diversifies the answer by maximal marginal relevance on the device
+        (include/mlvdb_mmr.h): among the ``fetch_k`` nearest vectors (default ``min(1024, max(4 * top_k, 20))``, at most
+        1024) the nearest is picked first, then ``top_k`` (<= 64) in all, each minimising ``mmr_lambda * d(query, i) -
+        (1 - mmr_lambda) * min over the picks s of d(s, i)`` in the index's distance; 1 is the plain search, 0 pure
+        diversity.  Hits come back in pick order with the usual scores; an optional single dict ``where`` restricts the
+        rows first.
         """
+        if mmr_lambda is not None:
+            return self._search_many_mmr(queries, top_k, namespace, metric, allowed_ids, where, distinct, mmr_lambda, fetch_k)
+        if fetch_k is not None:
+            raise ValueError("search_many: fetch_k is the candidate count of mmr_lambda=, give both or neither")
         if distinct is not None:
             return self._search_many_distinct(queries, top_k, namespace, metric, allowed_ids, where, distinct)
         if where is not None and allowed_ids is not None:
@@ -536,6 +547,51 @@ class Index:
                              np.zeros(nq, np.int32), ns.ids)  # no string was ever stored: every row is absent
         attr = list(self._attributes).index(distinct)
         labels, dist, counts, _ = search_distinct(q, k, attr, max_groups=max_groups, where=program)
+        return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
+
+    _MAX_TOP_K_MMR = 64      # MLVDB_MAX_TOPK
+    _MAX_FETCH_K_MMR = 1024  # MLVDB_MMR_MAX_FETCH: the longest candidate list the selection walks
+
+    @classmethod
+    def _default_fetch_k(cls, top_k: int) -> int:
+        return min(cls._MAX_FETCH_K_MMR, max(4 * int(top_k), 20))
+
+    def _search_many_mmr(self, queries, top_k: int, namespace: str, metric: str, allowed_ids, where, distinct,
+                         mmr_lambda, fetch_k) -> BatchHits:
+        """``search_many`` with ``mmr_lambda=``: every refusal happens before the engine is touched."""
+        if self._devices is not None and len(self._devices) > 1:
+            raise ValueError("mmr_lambda= is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        if distinct is not None:
+            raise ValueError("mmr_lambda: distinct= cannot be combined with it, give one of the two")
+        lam = float(mmr_lambda)
+        if not 0.0 <= lam <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"mmr_lambda must lie in [0, 1] (got {mmr_lambda})")
+        if top_k > self._MAX_TOP_K_MMR:
+            raise ValueError(f"mmr_lambda: top_k must be <= {self._MAX_TOP_K_MMR} (got {top_k})")
+        if fetch_k is None:
+            fetch_k = self._default_fetch_k(max(int(top_k), 0))
+        fetch_k = int(fetch_k)
+        if fetch_k > self._MAX_FETCH_K_MMR:
+            raise ValueError(f"mmr_lambda: fetch_k must be <= {self._MAX_FETCH_K_MMR} (got {fetch_k})")
+        if fetch_k < top_k:
+            raise ValueError(f"mmr_lambda: fetch_k must be >= top_k (got fetch_k={fetch_k}, top_k={top_k})")
+        if isinstance(where, (list, tuple)):
+            raise ValueError("mmr_lambda: a per-query where list is not supported, give one dict filter")
+        if allowed_ids is not None:
+            raise ValueError("mmr_lambda: allowed_ids is not supported, give a dict where filter")
+        program = None if where is None else self._compile(namespace, where)
+        q = self._coerce_queries(queries)
+        nq = q.shape[0]
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
+            return BatchHits.empty(nq)
+        search_mmr = getattr(ns.engine, "search_mmr", None)
+        if search_mmr is None:
+            raise ValueError("mmr_lambda= needs an engine with search_mmr (a single-device namespace)")
+        active = ns.total - ns.deleted
+        k = min(int(top_k), active)  # as search_many clamps top_k (the reference clamps to the live count)
+        fetch = min(fetch_k, active)  # (>= k: fetch_k >= top_k)
+        labels, dist, counts = search_mmr(q, k, fetch, lam, where=program)[:3]
         return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
 
     def _compile_each(self, namespace: str, wheres) -> Tuple[list, np.ndarray]:
