@@ -116,6 +116,13 @@ DISTINCT_SIGNATURES = {
                                               _P, _P, _P, _P, _P]),
 }
 
+# include/mlvdb_grouped.h: the nearest rows of each of the k nearest groups
+GROUPED_MAX_SIZE = 64
+GROUPED_SIGNATURES = {
+    "mlvdb_search_batch_grouped": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(Where),
+                                             _P, _P, _P, _P, _P, _P]),
+}
+
 # include/mlvdb_facet.h: facet counts and histograms of attribute columns
 FACET_MAX_VALUES = 1 << 20
 FACET_MAX_EDGES = 4096
@@ -170,7 +177,7 @@ def load() -> C.CDLL:
             f"There is no CPU fallback for the search path.")
     lib = C.CDLL(str(path))
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
-                                      **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **FACET_SIGNATURES,
+                                      **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype

@@ -117,6 +117,10 @@ struct mlvdb_index {
     // distinct kNN (mlvdb_distinct.h): a chunk's queries, its ranked lists from the plain search, its outputs, and the
     // flagged queries' list + counter -- all sized by the chunk (<= kDistinctChunk queries), k and L, never by the corpus
     DevBuf dist_q, dist_list, dist_out, dist_sel;
+    // grouped kNN (mlvdb_grouped.h): the code table of a chunk's picked groups with its counts / cursors, the tiles, pairs and
+    // slot map, the outputs -- sized by the chunk (<= kDistinctChunk queries), k and group_size -- and the member lists: 4 B
+    // per listed row, never more than 4 B x live rows
+    DevBuf grp_tab, grp_tiles, grp_out, grp_lab;
     // diversified kNN (mlvdb_mmr.h): a chunk's queries, its ranked candidate lists from the plain search and its outputs --
     // sized by the chunk (<= kMmrChunk queries), k and fetch_k, never by the corpus
     DevBuf mmr_q, mmr_list, mmr_out;
@@ -1175,6 +1179,7 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     h->where_cnt.release();
     for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
                       &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel,
+                      &h->grp_tab, &h->grp_tiles, &h->grp_out, &h->grp_lab,
                       &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->facet_tab, &h->facet_misc, &h->order_ws})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
@@ -2780,9 +2785,90 @@ namespace {
 // ---- distinct-by-attribute kNN (mlvdb_distinct.h)
 constexpr int64_t kDistinctChunk = 1024;  // queries per round of list pass + pick + grouped scan (bounds the workspaces)
 
-// The validated call (h->rn is the masked copy when a program restricts the rows).  Per chunk of queries:
-// the plain device search for L neighbours -> the pick (final outputs of the complete queries, the others flagged) -> one
-// synchronisation for the flagged count -> the grouped exact scan + merge of the flagged queries -> outputs to the host.
+// Where a chunk's outputs lie in h->dist_out: [d64 | groups | labels | dist | counts]
+struct DistinctOut {
+    double* d64;
+    int64_t* grp;
+    int64_t* lab;
+    float* dist;
+    int32_t* cnt;
+};
+
+// L of the list pass: k <= 64 costs the filter path what k = 64 does, hence the floor; 0: no list pass
+int32_t distinct_list_len(const mlvdb_index* h, int32_t k) {
+    const int32_t os = h->tn.distinct_oversample;
+    return os > 0 ? (int32_t)std::min<int64_t>(kDistinctMaxList, std::max<int64_t>(64, (int64_t)os * k)) : 0;
+}
+
+// One chunk of n <= kDistinctChunk queries (host pointer), outputs left on the device (`o`, enqueued on h->stream, not waited
+// for): the plain device search for L neighbours -> the pick (final outputs of the complete queries, the others flagged) ->
+// one synchronisation for the flagged count -> the grouped exact scan + merge of the flagged queries.
+int distinct_chunk(mlvdb_index* h, const float* queries, int32_t n, int32_t k, int32_t k_eff, const int64_t* group, int32_t L,
+                   DistinctOut& o) {
+    hipStream_t s = h->stream;
+    const size_t nk = (size_t)n * k;
+    HIP_TRY(h, h->dist_q.ensure((size_t)n * h->dim * sizeof(float)));
+    HIP_TRY(h, h->dist_out.ensure(nk * (2 * sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
+    HIP_TRY(h, h->dist_sel.ensure((size_t)(n + 1) * sizeof(int32_t)));
+    float* dq = h->dist_q.as<float>();
+    double* o_d64 = h->dist_out.as<double>();
+    int64_t* o_grp = reinterpret_cast<int64_t*>(o_d64 + nk);
+    int64_t* o_lab = o_grp + nk;
+    float* o_dist = reinterpret_cast<float*>(o_lab + nk);
+    int32_t* o_cnt = reinterpret_cast<int32_t*>(o_dist + nk);
+    o = DistinctOut{o_d64, o_grp, o_lab, o_dist, o_cnt};
+    int32_t* nflag_d = h->dist_sel.as<int32_t>();  // [counter | flagged queries]
+    int32_t* qsel_d = nflag_d + 1;
+    HIP_TRY(h, hipMemcpyAsync(dq, queries, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
+    int32_t nsel = n;               // queries of the chunk the grouped scan serves
+    const int32_t* qsel = nullptr;  // ... all of them without a list pass
+    if (L > 0) {
+        const size_t nl = (size_t)n * L;
+        HIP_TRY(h, h->dist_list.ensure(nl * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
+        double* l_d64 = h->dist_list.as<double>();  // [d64 | labels | dist | counts]
+        int64_t* l_lab = reinterpret_cast<int64_t*>(l_d64 + nl);
+        float* l_dist = reinterpret_cast<float*>(l_lab + nl);
+        int32_t* l_cnt = reinterpret_cast<int32_t*>(l_dist + nl);
+        if (int rc = search_device_impl(h, dq, n, L, l_lab, l_dist, l_cnt, l_d64, s, false)) return rc;
+        HIP_TRY(h, hipMemsetAsync(nflag_d, 0, sizeof(int32_t), s));
+        HIP_TRY(h, launch_distinct_pick(l_lab, l_d64, l_cnt, n, L, group, k, k_eff, qsel_d, nflag_d, o_lab, o_dist, o_cnt,
+                                        o_d64, o_grp, s));
+        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
+        HIP_TRY(h, hipMemcpyAsync(&nsel, nflag_d, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        qsel = qsel_d;
+        h->host_fallbacks += nsel;
+    }
+    if (nsel > 0) {
+        HIP_TRY(h, h->qpad.ensure((size_t)n * h->ld * sizeof(float)));
+        HIP_TRY(h, h->qaux.ensure((size_t)n * sizeof(double)));
+        HIP_TRY(h, launch_query_prep(dq, n, h->dim, h->ld, h->space, h->qpad.as<float>(), h->qaux.as<double>(), nullptr, s));
+        const ExactPlan plan = plan_distinct(h->total, h->ld, nsel, k);
+        HIP_TRY(h, h->partial.ensure((size_t)nsel * plan.nblk * k * sizeof(DistinctEntry)));
+        DistinctArgs a{};
+        a.X = h->X;
+        a.rn = h->rn;
+        a.group = group;
+        a.total = h->total;
+        a.ld = h->ld;
+        a.space = h->space;
+        a.Qpad = h->qpad.as<float>();
+        a.qaux = h->qaux.as<double>();
+        a.qsel = qsel;
+        a.nq_sel = nsel;
+        a.nq_sel_dev = nullptr;
+        a.k = k;
+        a.partial = h->partial.as<DistinctEntry>();
+        if (int rc = scan_step(h, s, h->total * plan.nqtiles, [&] { return launch_distinct_scan(a, plan, s); })) return rc;
+        HIP_TRY(h, launch_distinct_merge(a.partial, nsel, nullptr, qsel, plan.nblk, k, k_eff, o_lab, o_dist, o_cnt, o_d64,
+                                         o_grp, s));
+        h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+    }
+    return MLVDB_OK;
+}
+
+// The validated call (h->rn is the masked copy when a program restricts the rows): distinct_chunk per chunk of queries, then
+// its outputs to the host.
 int distinct_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t attr, int64_t max_groups,
                   int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64, int64_t* out_groups) {
     hipStream_t s = h->stream;
@@ -2798,75 +2884,19 @@ int distinct_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, i
         return MLVDB_OK;
     }
     const int64_t* group = h->attr_col[attr];
-    const int32_t os = h->tn.distinct_oversample;
-    // k <= 64 costs the filter path what k = 64 does, hence the floor; 0: no list pass
-    const int32_t L = os > 0 ? (int32_t)std::min<int64_t>(kDistinctMaxList, std::max<int64_t>(64, (int64_t)os * k)) : 0;
+    const int32_t L = distinct_list_len(h, k);
     for (int64_t q0 = 0; q0 < nq; q0 += kDistinctChunk) {
         const int32_t n = (int32_t)std::min<int64_t>(kDistinctChunk, nq - q0);
         const size_t nk = (size_t)n * k;
-        HIP_TRY(h, h->dist_q.ensure((size_t)n * h->dim * sizeof(float)));
-        HIP_TRY(h, h->dist_out.ensure(nk * (2 * sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
-        HIP_TRY(h, h->dist_sel.ensure((size_t)(n + 1) * sizeof(int32_t)));
-        float* dq = h->dist_q.as<float>();
-        double* o_d64 = h->dist_out.as<double>();  // [d64 | groups | labels | dist | counts]
-        int64_t* o_grp = reinterpret_cast<int64_t*>(o_d64 + nk);
-        int64_t* o_lab = o_grp + nk;
-        float* o_dist = reinterpret_cast<float*>(o_lab + nk);
-        int32_t* o_cnt = reinterpret_cast<int32_t*>(o_dist + nk);
-        int32_t* nflag_d = h->dist_sel.as<int32_t>();  // [counter | flagged queries]
-        int32_t* qsel_d = nflag_d + 1;
-        HIP_TRY(h, hipMemcpyAsync(dq, queries + (size_t)q0 * h->dim, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
-        int32_t nsel = n;               // queries of the chunk the grouped scan serves
-        const int32_t* qsel = nullptr;  // ... all of them without a list pass
-        if (L > 0) {
-            const size_t nl = (size_t)n * L;
-            HIP_TRY(h, h->dist_list.ensure(nl * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
-            double* l_d64 = h->dist_list.as<double>();  // [d64 | labels | dist | counts]
-            int64_t* l_lab = reinterpret_cast<int64_t*>(l_d64 + nl);
-            float* l_dist = reinterpret_cast<float*>(l_lab + nl);
-            int32_t* l_cnt = reinterpret_cast<int32_t*>(l_dist + nl);
-            if (int rc = search_device_impl(h, dq, n, L, l_lab, l_dist, l_cnt, l_d64, s, false)) return rc;
-            HIP_TRY(h, hipMemsetAsync(nflag_d, 0, sizeof(int32_t), s));
-            HIP_TRY(h, launch_distinct_pick(l_lab, l_d64, l_cnt, n, L, group, k, k_eff, qsel_d, nflag_d, o_lab, o_dist, o_cnt,
-                                            o_d64, o_grp, s));
-            HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
-            HIP_TRY(h, hipMemcpyAsync(&nsel, nflag_d, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
-            qsel = qsel_d;
-            h->host_fallbacks += nsel;
-        }
-        if (nsel > 0) {
-            HIP_TRY(h, h->qpad.ensure((size_t)n * h->ld * sizeof(float)));
-            HIP_TRY(h, h->qaux.ensure((size_t)n * sizeof(double)));
-            HIP_TRY(h, launch_query_prep(dq, n, h->dim, h->ld, h->space, h->qpad.as<float>(), h->qaux.as<double>(), nullptr, s));
-            const ExactPlan plan = plan_distinct(h->total, h->ld, nsel, k);
-            HIP_TRY(h, h->partial.ensure((size_t)nsel * plan.nblk * k * sizeof(DistinctEntry)));
-            DistinctArgs a{};
-            a.X = h->X;
-            a.rn = h->rn;
-            a.group = group;
-            a.total = h->total;
-            a.ld = h->ld;
-            a.space = h->space;
-            a.Qpad = h->qpad.as<float>();
-            a.qaux = h->qaux.as<double>();
-            a.qsel = qsel;
-            a.nq_sel = nsel;
-            a.nq_sel_dev = nullptr;
-            a.k = k;
-            a.partial = h->partial.as<DistinctEntry>();
-            if (int rc = scan_step(h, s, h->total * plan.nqtiles, [&] { return launch_distinct_scan(a, plan, s); })) return rc;
-            HIP_TRY(h, launch_distinct_merge(a.partial, nsel, nullptr, qsel, plan.nblk, k, k_eff, o_lab, o_dist, o_cnt, o_d64,
-                                             o_grp, s));
-            h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
-        }
+        DistinctOut o{};
+        if (int rc = distinct_chunk(h, queries + (size_t)q0 * h->dim, n, k, k_eff, group, L, o)) return rc;
         const size_t at = (size_t)q0 * k;
         HIP_TRY(h, hipStreamSynchronize(s));
-        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o_d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_groups) HIP_TRY(h, hipMemcpyAsync(out_groups + at, o_grp, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o_lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_dist + at, o_dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o.d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_groups) HIP_TRY(h, hipMemcpyAsync(out_groups + at, o.grp, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_dist + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
     }
     return MLVDB_OK;
@@ -2890,6 +2920,223 @@ int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq
     if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     auto call = [&]() {
         return distinct_impl(h, queries, nq, k, attr, max_groups, out_labels, out_dist, out_counts, out_dist64, out_groups);
+    };
+    if (!where) return nq == 0 ? MLVDB_OK : call();
+    rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy
+    if (rc || nq == 0) return rc;
+    if (h->total == 0) return call();
+    return with_row_mask(h, nq, call);
+    });
+}
+
+// ---- grouped kNN (mlvdb_grouped.h)
+extern "C++" {
+namespace {
+// padding of queries [q0, q0 + n) of a grouped call, on the host
+void grouped_pad(int64_t q0, int64_t n, int32_t k, int32_t gsz, int64_t* out_labels, float* out_dist, int32_t* out_counts,
+                 int32_t* out_gcnt, double* out_dist64, int64_t* out_groups) {
+    for (int64_t i = q0 * k * gsz; i < (q0 + n) * k * gsz; ++i) {
+        out_labels[i] = -1;
+        out_dist[i] = __builtin_inff();
+        if (out_dist64) out_dist64[i] = __builtin_inf();
+    }
+    for (int64_t i = q0 * k; i < (q0 + n) * k; ++i) {
+        out_gcnt[i] = 0;
+        if (out_groups) out_groups[i] = INT64_MIN;
+    }
+    for (int64_t i = q0; i < q0 + n; ++i) out_counts[i] = 0;
+}
+
+// The member stage of one chunk of n queries: grp / cnt are the distinct stage's group codes [n, k] and counts [n] on the host,
+// h->dist_q holds the chunk's raw queries.  Member lists of the picked codes (count, prefix sum, fill), tiles, the gathered
+// kernel, the merge -- outputs left in h->grp_out [d64 | labels | dist | group counts], enqueued, not waited for.
+int grouped_members(mlvdb_index* h, int32_t n, int32_t k, int32_t gsz, int32_t qt_max, const int64_t* col, const int64_t* grp,
+                    const int32_t* cnt) {
+    hipStream_t s = h->stream;
+    const int32_t nslots = n * k;
+    // the (code, slot) pairs sorted by code, then by query: queries sharing a document share its rows' loads
+    std::vector<std::pair<int64_t, int32_t>> picked;
+    for (int32_t i = 0; i < n; ++i)
+        for (int32_t j = 0; j < cnt[i]; ++j) picked.emplace_back(grp[(size_t)i * k + j], i * k + j);
+    std::sort(picked.begin(), picked.end());
+    const int32_t npairs = (int32_t)picked.size();
+    std::vector<int32_t> first;  // first pair of every distinct code, and npairs
+    for (int32_t p = 0; p < npairs; ++p)
+        if (p == 0 || picked[p].first != picked[p - 1].first) first.push_back(p);
+    const size_t ncodes = first.size();
+    first.push_back(npairs);
+    // the open-addressing table: the smallest power of two >= 2 x the number of codes
+    uint64_t slots = 1;
+    while (slots < 2 * (uint64_t)std::max<size_t>(ncodes, 1)) slots *= 2;
+    std::vector<int64_t> keys(slots, INT64_MIN);
+    std::vector<uint32_t> slot_of(ncodes);
+    for (size_t u = 0; u < ncodes; ++u) {
+        uint64_t at = facet_hash(picked[first[u]].first) & (slots - 1);
+        while (keys[at] != INT64_MIN) at = (at + 1) & (slots - 1);
+        keys[at] = picked[first[u]].first;
+        slot_of[u] = (uint32_t)at;
+    }
+    HIP_TRY(h, h->grp_tab.ensure(slots * (sizeof(int64_t) + sizeof(uint32_t))));  // [keys | counts, then cursors]
+    long long* keys_d = h->grp_tab.as<long long>();
+    uint32_t* counts_d = reinterpret_cast<uint32_t*>(keys_d + slots);
+    std::vector<uint32_t> counts(slots, 0);
+    if (npairs > 0) {
+        HIP_TRY(h, hipMemcpyAsync(keys_d, keys.data(), slots * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemsetAsync(counts_d, 0, slots * sizeof(uint32_t), s));
+        HIP_TRY(h, launch_grouped_count(h->rn, col, h->total, keys_d, slots, counts_d, s));
+        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
+        HIP_TRY(h, hipMemcpyAsync(counts.data(), counts_d, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    // prefix sum over the slots: list begins (the fill's cursors)
+    std::vector<uint32_t> begin(slots, 0);
+    int64_t members = 0;
+    for (uint64_t t = 0; t < slots; ++t) {
+        begin[t] = (uint32_t)members;
+        members += counts[t];
+    }
+    if (members > h->total - h->deleted || members > INT32_MAX) return fail(h, MLVDB_ERR_INTERNAL, "grouped: more members than live rows");
+    if (members > 0) {
+        HIP_TRY(h, h->grp_lab.ensure((size_t)members * sizeof(int32_t)));
+        HIP_TRY(h, hipMemcpyAsync(counts_d, begin.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, launch_grouped_fill(h->rn, col, h->total, keys_d, slots, counts_d, h->grp_lab.as<int32_t>(), s));
+    }
+    // tiles: <= qt_max pairs of one group against one chunk of its list; the rows per chunk from the work of the whole chunk of
+    // queries (grouped_chunk_rows); tiles of 1 / 2 / 3-4 pairs take the QT = 1 / 2 / 4 instance
+    int64_t work = 0;
+    for (size_t u = 0; u < ncodes; ++u)
+        work += (int64_t)((first[u + 1] - first[u] + qt_max - 1) / qt_max) * counts[slot_of[u]];
+    const int64_t chunk_rows = grouped_chunk_rows(work);
+    std::vector<GroupedTile> tiles[3];  // by instance: QT 1, 2, 4
+    std::vector<GroupedPair> pairs((size_t)npairs);
+    std::vector<int32_t> pair_of_slot((size_t)nslots, -1);
+    int64_t nparts = 0;
+    for (size_t u = 0; u < ncodes; ++u) {
+        const int64_t c = counts[slot_of[u]], b = begin[slot_of[u]];
+        const int32_t nch = (int32_t)std::max<int64_t>(1, (c + chunk_rows - 1) / chunk_rows);
+        for (int32_t p0 = first[u]; p0 < first[u + 1];) {
+            const int32_t take = std::min(qt_max, first[u + 1] - p0);
+            const int cls = take == 1 ? 0 : take == 2 ? 1 : 2;
+            for (int32_t t = 0; t < take; ++t) {
+                pairs[(size_t)p0 + t] = GroupedPair{picked[(size_t)p0 + t].second / k, (int32_t)(nparts + (int64_t)t * nch), nch, 0};
+                pair_of_slot[(size_t)picked[(size_t)p0 + t].second] = p0 + t;
+            }
+            for (int32_t ch = 0; ch < nch; ++ch) {
+                const int64_t lo = std::min<int64_t>(c, ch * chunk_rows), hi = std::min<int64_t>(c, lo + chunk_rows);
+                tiles[cls].push_back(GroupedTile{(int32_t)(b + lo), (int32_t)(hi - lo), p0, take, (int32_t)(nparts + ch), nch});
+            }
+            nparts += (int64_t)take * nch;
+            p0 += take;
+        }
+    }
+    if (nparts * gsz > INT32_MAX) return fail(h, MLVDB_ERR_INTERNAL, "grouped: partial lists beyond 2^31 entries");
+    const size_t tile_bytes = (tiles[0].size() + tiles[1].size() + tiles[2].size()) * sizeof(GroupedTile);
+    const size_t pair_off = (tile_bytes + 15) / 16 * 16, slot_off = pair_off + pairs.size() * sizeof(GroupedPair);
+    HIP_TRY(h, h->grp_tiles.ensure(slot_off + pair_of_slot.size() * sizeof(int32_t) + 16));
+    char* td = h->grp_tiles.as<char>();
+    const GroupedTile* tiles_d[3];
+    size_t off = 0;
+    for (int cls = 0; cls < 3; ++cls) {
+        tiles_d[cls] = reinterpret_cast<const GroupedTile*>(td + off);
+        if (!tiles[cls].empty())
+            HIP_TRY(h, hipMemcpyAsync(td + off, tiles[cls].data(), tiles[cls].size() * sizeof(GroupedTile), hipMemcpyHostToDevice, s));
+        off += tiles[cls].size() * sizeof(GroupedTile);
+    }
+    const GroupedPair* pairs_d = reinterpret_cast<const GroupedPair*>(td + pair_off);
+    const int32_t* pos_d = reinterpret_cast<const int32_t*>(td + slot_off);
+    if (npairs > 0) HIP_TRY(h, hipMemcpyAsync(td + pair_off, pairs.data(), pairs.size() * sizeof(GroupedPair), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(td + slot_off, pair_of_slot.data(), pair_of_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    // the chunk's queries, prepared as every exact path prepares them, staged by query index
+    HIP_TRY(h, h->qpad.ensure((size_t)n * h->ld * sizeof(float)));
+    HIP_TRY(h, h->qaux.ensure((size_t)n * sizeof(double)));
+    HIP_TRY(h, launch_query_prep(h->dist_q.as<float>(), n, h->dim, h->ld, h->space, h->qpad.as<float>(), h->qaux.as<double>(),
+                                 nullptr, s));
+    HIP_TRY(h, h->partial.ensure((size_t)std::max<int64_t>(nparts, 1) * gsz * sizeof(TopEntry)));
+    static const int32_t kQt[3] = {1, 2, 4};
+    for (int cls = 0; cls < 3; ++cls)
+        HIP_TRY(h, launch_grouped_gather(h->X, h->qpad.as<float>(), h->qaux.as<double>(), h->grp_lab.as<int32_t>(), tiles_d[cls],
+                                         (int32_t)tiles[cls].size(), pairs_d, h->ld, h->space, kQt[cls], gsz,
+                                         h->partial.as<TopEntry>(), s));
+    const size_t ng = (size_t)nslots * gsz;
+    HIP_TRY(h, h->grp_out.ensure(ng * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)nslots * sizeof(int32_t)));
+    double* o_d64 = h->grp_out.as<double>();
+    int64_t* o_lab = reinterpret_cast<int64_t*>(o_d64 + ng);
+    float* o_dist = reinterpret_cast<float*>(o_lab + ng);
+    int32_t* o_gcnt = reinterpret_cast<int32_t*>(o_dist + ng);
+    HIP_TRY(h, launch_grouped_merge(h->partial.as<TopEntry>(), pairs_d, pos_d, nslots, gsz, o_lab, o_dist, o_d64, o_gcnt, s));
+    HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
+    return MLVDB_OK;
+}
+
+// The validated call (h->rn is the masked copy when a program restricts the rows).  Per chunk of queries: the distinct stage
+// with its outputs left on the device -> group codes and counts to the host -> the member stage -> outputs to the host.
+int grouped_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t gsz, int32_t qt_max, int32_t attr,
+                 int64_t max_groups, int64_t* out_labels, float* out_dist, int32_t* out_counts, int32_t* out_gcnt,
+                 double* out_dist64, int64_t* out_groups) {
+    hipStream_t s = h->stream;
+    if (h->total == 0 || h->total == h->deleted) {
+        grouped_pad(0, nq, k, gsz, out_labels, out_dist, out_counts, out_gcnt, out_dist64, out_groups);
+        return MLVDB_OK;
+    }
+    const int32_t k_eff = max_groups > 0 ? (int32_t)std::min<int64_t>(k, max_groups) : k;
+    const int64_t* col = h->attr_col[attr];
+    const int32_t L = distinct_list_len(h, k);
+    std::vector<int64_t> grp;
+    std::vector<int32_t> cnt;
+    for (int64_t q0 = 0; q0 < nq; q0 += kDistinctChunk) {
+        const int32_t n = (int32_t)std::min<int64_t>(kDistinctChunk, nq - q0);
+        const size_t nk = (size_t)n * k, ng = nk * gsz;
+        DistinctOut o{};
+        if (int rc = distinct_chunk(h, queries + (size_t)q0 * h->dim, n, k, k_eff, col, L, o)) return rc;
+        grp.resize(nk);
+        cnt.resize((size_t)n);
+        HIP_TRY(h, hipStreamSynchronize(s));
+        HIP_TRY(h, hipMemcpyAsync(grp.data(), o.grp, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(cnt.data(), o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = grouped_members(h, n, k, gsz, qt_max, col, grp.data(), cnt.data())) return rc;
+        const double* o_d64 = h->grp_out.as<double>();  // [d64 | labels | dist | group counts]
+        const int64_t* o_lab = reinterpret_cast<const int64_t*>(o_d64 + ng);
+        const float* o_dist = reinterpret_cast<const float*>(o_lab + ng);
+        const int32_t* o_gcnt = reinterpret_cast<const int32_t*>(o_dist + ng);
+        const size_t at = (size_t)q0 * k;
+        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at * gsz, o_d64, ng * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_labels + at * gsz, o_lab, ng * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_dist + at * gsz, o_dist, ng * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_gcnt + at, o_gcnt, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        if (out_groups) std::memcpy(out_groups + at, grp.data(), nk * sizeof(int64_t));
+        std::memcpy(out_counts + q0, cnt.data(), (size_t)n * sizeof(int32_t));
+    }
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_grouped(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t group_size, int32_t attr,
+                               int64_t max_groups, const mlvdb_where* where, int64_t* out_labels, float* out_dist,
+                               int32_t* out_counts, int32_t* out_group_counts, double* out_dist64, int64_t* out_groups) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched (the program: where_run validates it before its first launch)
+    if ((rc = attr_check(h, attr))) return rc;
+    if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "grouped needs an int64 column");
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (group_size < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "group_size must be >= 1");
+    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "grouped: k above MLVDB_MAX_TOPK");
+    if (group_size > kGroupedMaxSize) return fail(h, MLVDB_ERR_UNSUPPORTED, "grouped: group_size above MLVDB_GROUPED_MAX_SIZE");
+    if (max_groups < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "max_groups < 0");
+    if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts || !out_group_counts))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    int32_t qt = kGatherQT;  // pairs per tile of the gathered kernel (fewer only when the tile would not fit in LDS)
+    while (qt > 1 && where_gather_lds(qt, h->ld) > 64 * 1024) qt >>= 1;
+    if (where_gather_lds(qt, h->ld) > 64 * 1024)
+        return fail(h, MLVDB_ERR_UNSUPPORTED, "grouped: one query of this dimension needs more than 64 KiB of LDS");
+    auto call = [&]() {
+        return grouped_impl(h, queries, nq, k, group_size, qt, attr, max_groups, out_labels, out_dist, out_counts,
+                            out_group_counts, out_dist64, out_groups);
     };
     if (!where) return nq == 0 ? MLVDB_OK : call();
     rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy

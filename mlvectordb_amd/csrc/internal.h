@@ -12,6 +12,7 @@
 #include "../../include/mlvdb_where_each.h"
 #include "../../include/mlvdb_where_each_range.h"
 #include "../../include/mlvdb_distinct.h"
+#include "../../include/mlvdb_grouped.h"
 #include "../../include/mlvdb_facet.h"
 #include "../../include/mlvdb_order.h"
 #include "../../include/mlvdb_mmr.h"
@@ -388,6 +389,44 @@ hipError_t launch_distinct_scan(const DistinctArgs& a, const ExactPlan& p, hipSt
 hipError_t launch_distinct_merge(const DistinctEntry* partial, int32_t nq_sel, const int32_t* nq_sel_dev, const int32_t* qsel,
                                  int32_t nblk, int32_t k, int32_t k_eff, int64_t* out_labels, float* out_dist,
                                  int32_t* out_counts, double* out_d64, int64_t* out_groups, hipStream_t s);
+
+// ---------------------------------------------------------------- grouped kNN (kernels_grouped.hip)
+constexpr int kGroupedMaxSize = MLVDB_GROUPED_MAX_SIZE;  // rows returned per group: one WaveTopK
+constexpr int kGroupedBlocks = 2048;   // blocks the chunk rule aims at for one gathered launch chain
+constexpr int kGroupedMinChunk = 256;  // fewest rows of a list chunk that is not the whole list (a multiple of 64)
+// Rows per chunk of a member list (mirrored in tests/grouped_helpers.py): `work` = the rows all tiles of
+// the chunk of queries would gather unsplit (sum over tiles of their list's length).  The rows are cut so that about
+// kGroupedBlocks blocks share the work evenly, whatever the lists' lengths: a huge group (a bool column) spreads over the
+// machine, a group of a hundred rows stays one block.
+__host__ __device__ inline int64_t grouped_chunk_rows(int64_t work) {
+    const int64_t even = ((work + kGroupedBlocks - 1) / kGroupedBlocks + 63) / 64 * 64;
+    return even > kGroupedMinChunk ? even : kGroupedMinChunk;
+}
+// one (query, rank) pair that picked a group: the query's index in the chunk (its row of Qpad / qaux) and where the pair's
+// partial lists lie (nch lists of group_size entries from list part0 on); sorted by group
+struct GroupedPair {
+    int32_t q, part0, nch, pad;
+};
+// one block of the gathered kernel: <= QT pairs pair0.. of one group against labels[lab_begin, lab_begin + lab_count), one
+// chunk of the group's list; part0: pair0's partial list of this chunk (pair t: part0 + t * nch)
+struct GroupedTile {
+    int32_t lab_begin, lab_count, pair0, npairs, part0, nch;
+};
+// counts[slot] += live rows (finite rn) whose value of `col` is the key of `slot`; keys: `slots` (a power of two) codes placed
+// by facet_hash with linear probing, INT64_MIN = empty, at most half full
+hipError_t launch_grouped_count(const float* rn, const int64_t* col, int64_t total, const long long* keys, uint64_t slots,
+                                uint32_t* counts, hipStream_t s);
+// labels[cursor[slot]++] = row for the same rows; cursor enters as the exclusive prefix sums of the counts
+hipError_t launch_grouped_fill(const float* rn, const int64_t* col, int64_t total, const long long* keys, uint64_t slots,
+                               uint32_t* cursor, int32_t* labels, hipStream_t s);
+// the tiles (all of npairs <= qt, qt in 1, 2, 4; where_gather_lds(qt, ld) <= 64 KiB) -> partial lists of gsz entries
+hipError_t launch_grouped_gather(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
+                                 const GroupedTile* tiles, int32_t ntiles, const GroupedPair* pairs, int32_t ld, int32_t space,
+                                 int32_t qt, int32_t gsz, TopEntry* partial, hipStream_t s);
+// slot s of [0, nslots): pair pair_of_slot[s]'s partial lists folded into out_*[s * gsz ..] and out_gcnt[s]; -1: padding
+hipError_t launch_grouped_merge(const TopEntry* partial, const GroupedPair* pairs, const int32_t* pair_of_slot, int32_t nslots,
+                                int32_t gsz, int64_t* out_labels, float* out_dist, double* out_d64, int32_t* out_gcnt,
+                                hipStream_t s);
 
 // ---------------------------------------------------------------- diversified kNN (kernels_mmr.hip)
 constexpr int kMmrMaxFetch = MLVDB_MMR_MAX_FETCH;  // longest candidate list the selection walks (the plain search's top_k)

@@ -358,6 +358,33 @@ class HipScanEngine:
             groups.ctypes.data), "search_batch_distinct")
         return (labels, dist, counts, d64, groups) if want64 else (labels, dist, counts, groups)
 
+    # -- grouped kNN (include/mlvdb_grouped.h) --------------------------------------------
+    def search_grouped(self, queries: np.ndarray, k: int, group_size: int, attr: int, max_groups: int = 0, where=None,
+                       want64: bool = False):
+        """The ``group_size`` (<= 64) nearest rows of each of the ``k`` nearest groups of int64 column ``attr``: the groups
+        and their ranking are those of ``search_distinct`` with the same arguments, slot ``[i, j, 0]`` is its ``[i, j]``.
+        Returns (labels int64 [nq, k, group_size], dist float32, counts int32 [nq]: groups returned, group_counts int32
+        [nq, k]: rows returned per group, groups int64 [nq, k]) or, with ``want64``, (labels, dist, counts, group_counts,
+        dist64, groups); padding is label -1 / +inf / group count 0 / group INT64_MIN."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        nq, k, g = queries.shape[0], int(k), int(group_size)
+        shape = (nq, max(k, 0), max(g, 0))
+        labels = np.empty(shape, dtype=np.int64)
+        dist = np.empty(shape, dtype=np.float32)
+        counts = np.empty(nq, dtype=np.int32)
+        group_counts = np.empty(shape[:2], dtype=np.int32)
+        groups = np.empty(shape[:2], dtype=np.int64)
+        d64 = np.empty(shape, dtype=np.float64) if want64 else None
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_search_batch_grouped(
+            self._h, queries.ctypes.data, nq, k, g, int(attr), int(max_groups), None if w is None else C.byref(w),
+            labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, group_counts.ctypes.data,
+            None if d64 is None else d64.ctypes.data, groups.ctypes.data), "search_batch_grouped")
+        return ((labels, dist, counts, group_counts, d64, groups) if want64
+                else (labels, dist, counts, group_counts, groups))
+
     # -- diversified kNN (include/mlvdb_mmr.h) --------------------------------------------
     def search_mmr(self, queries: np.ndarray, k: int, fetch_k: int, lam: float, where=None, want64: bool = False):
         """Greedy maximal-marginal-relevance selection of ``k`` (<= 64) hits among the ``fetch_k`` (<= 1024) nearest rows

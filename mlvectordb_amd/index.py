@@ -137,6 +137,27 @@ class BatchHits(SequenceABC):
         return NotImplemented
 
 
+class GroupedBatchHits(BatchHits):
+    """What ``search_many(distinct=..., group_size=...)`` returns: ``BatchHits`` whose rows hold, per query, the groups in rank
+    order and each group's members in order, compacted (``counts`` is the total, the valid prefix as everywhere), plus what
+    splits the flat list again:
+
+    ``group_sizes``   int32 [nq, k]   members returned per group (0 at padding)
+    ``group_values``  object [nq, k]  the groups' values decoded (``str`` / ``bool`` / ``int``; ``None`` at padding)
+    """
+
+    __slots__ = ("group_sizes", "group_values")
+
+    def __init__(self, labels, scores, counts, table, group_sizes: np.ndarray, group_values: np.ndarray) -> None:
+        super().__init__(labels, scores, counts, table)
+        self.group_sizes, self.group_values = group_sizes, group_values
+
+    @classmethod
+    def empty(cls, nq: int) -> "GroupedBatchHits":
+        return cls(np.full((nq, 0), -1, dtype=np.int64), np.zeros((nq, 0)), np.zeros(nq, dtype=np.int32), None,
+                   np.zeros((nq, 0), dtype=np.int32), np.full((nq, 0), None, dtype=object))
+
+
 EngineFactory = Callable[[int, str], ScanEngine]
 
 
@@ -452,7 +473,7 @@ class Index:
     def search_many(self, queries, top_k: int, namespace: str, metric: str,
                     allowed_ids: Optional[Iterable[UUID]] = None, where: Optional[Mapping] = None,
                     distinct: Optional[str] = None, mmr_lambda: Optional[float] = None,
-                    fetch_k: Optional[int] = None) -> BatchHits:
+                    fetch_k: Optional[int] = None, group_size: Optional[int] = None) -> BatchHits:
         """kNN for a batch of queries in one corpus scan.
 
         ``queries`` is an ``[nq, dim]`` array or a sequence of ``VectorDTO``.  Each entry of
@@ -471,13 +492,18 @@ class Index:
         (1 - mmr_lambda) * min over the picks s of d(s, i)`` in the index's distance; 1 is the plain search, 0 pure
         diversity.  Hits come back in pick order with the usual scores; an optional single dict ``where`` restricts the
         rows first.
+        ``group_size`` (additive, with ``distinct``: an int in [1, 64]) returns the ``group_size`` nearest rows of each of
+        those groups instead of one (include/mlvdb_grouped.h) as a ``GroupedBatchHits``: per query the groups in rank
+        order, each group's members in order, ``group_sizes`` / ``group_values`` to split the flat list.
         """
+        if group_size is not None and distinct is None:
+            raise ValueError("search_many: group_size is the member count of distinct=, give both or neither")
         if mmr_lambda is not None:
             return self._search_many_mmr(queries, top_k, namespace, metric, allowed_ids, where, distinct, mmr_lambda, fetch_k)
         if fetch_k is not None:
             raise ValueError("search_many: fetch_k is the candidate count of mmr_lambda=, give both or neither")
         if distinct is not None:
-            return self._search_many_distinct(queries, top_k, namespace, metric, allowed_ids, where, distinct)
+            return self._search_many_distinct(queries, top_k, namespace, metric, allowed_ids, where, distinct, group_size)
         if where is not None and allowed_ids is not None:
             raise ValueError("search_many: give allowed_ids or where, not both")
         if isinstance(where, (list, tuple)):
@@ -513,9 +539,14 @@ class Index:
 
     _MAX_TOP_K_DISTINCT = 64  # MLVDB_MAX_TOPK: one selection list of a wavefront
 
+    _MAX_GROUP_SIZE = 64  # MLVDB_GROUPED_MAX_SIZE: one selection list of a wavefront
+
     def _search_many_distinct(self, queries, top_k: int, namespace: str, metric: str, allowed_ids, where,
-                              distinct: str) -> BatchHits:
+                              distinct: str, group_size: Optional[int] = None) -> BatchHits:
         """``search_many`` with ``distinct=``: every refusal happens before the engine is touched."""
+        if group_size is not None and (isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer))
+                                       or not 1 <= group_size <= self._MAX_GROUP_SIZE):
+            raise ValueError(f"group_size must be an int in [1, {self._MAX_GROUP_SIZE}] (got {group_size!r})")
         if self._devices is not None and len(self._devices) > 1:
             raise ValueError("distinct= is not supported on a row-sharded index (devices=[...] with more than one entry)")
         if distinct not in self._attributes:
@@ -534,6 +565,8 @@ class Index:
         q = self._coerce_queries(queries)
         nq = q.shape[0]
         ns = self._ns.get(namespace)
+        if group_size is not None:
+            return self._search_many_grouped(q, top_k, ns, metric, program, distinct, kind, int(group_size))
         if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
             return BatchHits.empty(nq)
         search_distinct = getattr(ns.engine, "search_distinct", None)
@@ -548,6 +581,41 @@ class Index:
         attr = list(self._attributes).index(distinct)
         labels, dist, counts, _ = search_distinct(q, k, attr, max_groups=max_groups, where=program)
         return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
+
+    def _search_many_grouped(self, q: np.ndarray, top_k: int, ns, metric: str, program, distinct: str, kind: str,
+                             g: int) -> "GroupedBatchHits":
+        """The validated ``distinct=`` call with ``group_size=``: the engine's [nq, k, g] answer compacted on the host."""
+        nq = q.shape[0]
+        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
+            return GroupedBatchHits.empty(nq)
+        search_grouped = getattr(ns.engine, "search_grouped", None)
+        if search_grouped is None:
+            raise ValueError("group_size= needs an engine with search_grouped (a single-device namespace)")
+        k = min(int(top_k), ns.total - ns.deleted)
+        max_groups = len(ns.strings.get(distinct, {})) if kind == "str" else 2 if kind == "bool" else 0
+        if kind == "str" and max_groups == 0:  # no string was ever stored: every row is absent
+            return GroupedBatchHits(np.full((nq, k * g), -1, np.int64),
+                                    self._scores(np.full((nq, k * g), np.inf, np.float32), metric), np.zeros(nq, np.int32),
+                                    ns.ids, np.zeros((nq, k), np.int32), np.full((nq, k), None, dtype=object))
+        attr = list(self._attributes).index(distinct)
+        labels, dist, ngroups, sizes, codes = search_grouped(q, k, g, attr, max_groups=max_groups, where=program)
+        # compaction: the valid slots of a query first, in their order (groups by rank, members in order), padding behind
+        valid = (np.arange(g)[None, None, :] < sizes[:, :, None]).reshape(nq, k * g)
+        order = np.argsort(~valid, axis=1, kind="stable")
+        valid = np.take_along_axis(valid, order, axis=1)
+        labels = np.where(valid, np.take_along_axis(labels.reshape(nq, k * g), order, axis=1), -1)
+        dist = np.where(valid, np.take_along_axis(dist.reshape(nq, k * g), order, axis=1), np.float32(np.inf))
+        values = np.full((nq, k), None, dtype=object)
+        have = np.arange(k)[None, :] < ngroups[:, None]
+        if kind == "str":
+            words = {code: word for word, code in ns.strings[distinct].items()}
+            values[have] = [words[c] for c in codes[have].tolist()]
+        elif kind == "bool":
+            values[have] = [bool(c) for c in codes[have].tolist()]
+        else:
+            values[have] = codes[have].tolist()
+        return GroupedBatchHits(labels, self._scores(dist, metric), sizes.sum(axis=1).astype(np.int32), ns.ids,
+                                sizes.astype(np.int32), values)
 
     _MAX_TOP_K_MMR = 64      # MLVDB_MAX_TOPK
     _MAX_FETCH_K_MMR = 1024  # MLVDB_MMR_MAX_FETCH: the longest candidate list the selection walks

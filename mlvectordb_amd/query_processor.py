@@ -67,7 +67,7 @@ class QueryProcessor:
 
     def find_similar_many(self, queries, top_k: int, namespace: str = "default",
                           metric: str = "cosine", where=None, distinct=None, mmr_lambda=None,
-                          fetch_k=None) -> List[List[dict]]:
+                          fetch_k=None, group_size=None) -> List[List[dict]]:
         """Batched ``find_similar``: ``queries`` is an [nq, dim] array or a sequence of VectorDTO.
 
         ``where`` (additive; README.md:121,130,252,274 intent, no reference code) restricts the search to the matching
@@ -80,10 +80,20 @@ class QueryProcessor:
             device in one batched call (``Index.search_many``); a predicate inside the list is a ``ValueError``.
         ``distinct`` (additive: a declared ``int`` / ``str`` / ``bool`` attribute of the index) returns one hit per value of
         that attribute: the nearest vector of each of the ``top_k`` (<= 64) nearest groups (``Index.search_many``).  With
-        it ``where`` is ``None`` or one dict filter.
+        it ``where`` is ``None`` or one dict filter.  ``group_size`` (additive, with ``distinct``: an int in [1, 64]) returns
+        the ``group_size`` nearest vectors of each of those groups instead of one: per query the groups in rank order, each
+        group's members in order, the usual dict per hit.
         ``mmr_lambda`` (additive: a number in [0, 1]; ``fetch_k``: its candidate count) diversifies the hits by maximal
         marginal relevance among the ``fetch_k`` nearest vectors, selected on the device (``Index.search_many``); hits
         come back in pick order.  With it ``where`` is ``None`` or one dict filter, and ``distinct`` is not allowed."""
+        if group_size is not None:
+            if distinct is None:
+                raise ValueError("find_similar_many: group_size is the member count of distinct=, give both or neither")
+            if where is not None and not isinstance(where, Mapping):
+                raise ValueError("distinct: where must be one dict filter (or None)")
+            hits = self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric, where=where,
+                                           distinct=distinct, mmr_lambda=mmr_lambda, fetch_k=fetch_k, group_size=group_size)
+            return self._enrich_many(hits, namespace)
         if mmr_lambda is not None or fetch_k is not None:
             if where is not None and not isinstance(where, (Mapping, list, tuple)):
                 raise ValueError("mmr_lambda: a predicate where (allowed_ids) is not supported, give a dict where filter")

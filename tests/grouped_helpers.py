@@ -1,0 +1,105 @@
+"""Shared by the grouped-kNN tests (include/mlvdb_grouped.h): the NumPy oracle, a brute-force restatement of it, an oracle
+engine with ``search_grouped``, and the member stage's host rules mirrored (the code table's size, the tiles and the rows per
+list chunk), so a test can state which tiles a call takes and how many chunks a list is cut into."""
+from __future__ import annotations
+
+import numpy as np
+
+from mlvectordb_amd.index import Index
+from oracle import exact_scan
+from tests.distinct_helpers import ABSENT, DistinctOracleEngine, distinct_knn
+
+# csrc/internal.h
+GROUPED_BLOCKS = 2048    # kGroupedBlocks
+GROUPED_MIN_CHUNK = 256  # kGroupedMinChunk
+MAX_GROUP_SIZE = 64      # MLVDB_GROUPED_MAX_SIZE
+
+
+def grouped_knn(dist: np.ndarray, groups: np.ndarray, allowed: np.ndarray, k: int, g: int):
+    """``distinct_knn`` for the groups, then the first g rows of ``lexsort((label, distance))`` within each group.
+    Returns (labels int64 [nq, k, g], dist64 [nq, k, g], counts int32 [nq], group_counts int32 [nq, k], groups int64 [nq, k]),
+    padded -1 / inf / 0 / ABSENT."""
+    nq = dist.shape[0]
+    _, _, counts, grp = distinct_knn(dist, groups, allowed, k)
+    ok = np.asarray(allowed, bool)
+    labels = np.full((nq, k, g), -1, np.int64)
+    d64 = np.full((nq, k, g), np.inf)
+    gcnt = np.zeros((nq, k), np.int32)
+    for i in range(nq):
+        for j in range(counts[i]):
+            idx = np.flatnonzero(ok & (groups == grp[i, j]))
+            keep = idx[np.lexsort((idx, dist[i, idx]))][:g]
+            gcnt[i, j] = keep.size
+            labels[i, j, :keep.size], d64[i, j, :keep.size] = keep, dist[i, keep]
+    return labels, d64, counts, gcnt, grp
+
+
+def grouped_knn_brute(dist: np.ndarray, groups: np.ndarray, allowed: np.ndarray, k: int, g: int):
+    """The same answer by the definition itself: every group's allowed rows sorted by (distance, label), the groups ranked by
+    their first row, the first g rows of the first k groups.  Per query a list of (group, [(distance, row), ...])."""
+    out = []
+    for i in range(dist.shape[0]):
+        members = {}
+        for row in range(groups.size):
+            code = int(groups[row])
+            if allowed[row] and code != ABSENT:
+                members.setdefault(code, []).append((float(dist[i, row]), row))
+        ranked = sorted((sorted(rows)[0], code) for code, rows in members.items())[:k]
+        out.append([(code, sorted(members[code])[:g]) for _, code in ranked])
+    return out
+
+
+class GroupedOracleEngine(DistinctOracleEngine):
+    """``DistinctOracleEngine`` + ``search_grouped`` as ``HipScanEngine`` declares it."""
+
+    def search_grouped(self, queries, k, group_size, attr, max_groups=0, where=None, want64=False):
+        col = self._cols[attr]
+        assert col.dtype == np.int64
+        allowed = ~self._deleted if where is None else self.match(where)
+        dist = exact_scan.exact_distances(queries, self._rows, self.space)
+        labels, d64, counts, gcnt, grp = grouped_knn(dist, col, allowed, k, group_size)
+        if max_groups:
+            assert counts.max(initial=0) <= max_groups
+        d32 = d64.astype(np.float32)
+        return (labels, d32, counts, gcnt, d64, grp) if want64 else (labels, d32, counts, gcnt, grp)
+
+
+def oracle_index(attributes, space="l2", **kw) -> Index:
+    return Index(space=space, engine_factory=GroupedOracleEngine, attributes=attributes, **kw)
+
+
+# ---------------------------------------------------------------- the member stage's host rules (api.hip: grouped_members)
+def table_slots(ncodes: int) -> int:
+    """Slots of the code table of a chunk: the smallest power of two >= 2 x the number of distinct picked codes."""
+    slots = 1
+    while slots < 2 * max(ncodes, 1):
+        slots *= 2
+    return slots
+
+
+def chunk_rows(work: int) -> int:
+    """Rows per chunk of a member list (grouped_chunk_rows): ``work`` = the sum over the tiles of their list's length; about
+    GROUPED_BLOCKS blocks share it evenly, a chunk is a multiple of 64 rows and never below GROUPED_MIN_CHUNK."""
+    even = (-(-work // GROUPED_BLOCKS) + 63) // 64 * 64
+    return max(even, GROUPED_MIN_CHUNK)
+
+
+def tile_plan(grp: np.ndarray, counts: np.ndarray, members: dict, qt_max: int = 4):
+    """The tiles of one chunk (<= 1024 queries) of a call: ``grp`` [n, k] / ``counts`` [n] are the distinct stage's answer,
+    ``members[code]`` the number of live allowed rows of a group.  Returns (rows per list chunk, [(code, pairs in the tile,
+    chunks of the list)] in launch order of the host loop): a group's pairs are cut into tiles of <= ``qt_max``."""
+    picked = {}
+    for i in range(grp.shape[0]):
+        for j in range(int(counts[i])):
+            picked[int(grp[i, j])] = picked.get(int(grp[i, j]), 0) + 1
+    work = sum(-(-n // qt_max) * members[code] for code, n in picked.items())
+    rows = chunk_rows(work)
+    tiles = []
+    for code in sorted(picked):
+        nch = max(1, -(-members[code] // rows))
+        left = picked[code]
+        while left:
+            take = min(qt_max, left)
+            tiles.append((code, take, nch))
+            left -= take
+    return rows, tiles
