@@ -626,7 +626,6 @@ __device__ __forceinline__ float l2c_delta(const FilterArgs& a, int q) {
 // shadow (k-steps of 64 int8 columns, same bytes per step; l2: the l2c body), else bf16; NQT = the query tiles the body
 // computes (int8: 8 / 4 for passes of <= 128 / <= 64 queries, else 16).
 constexpr int kAsmWaves = 8;      // waves per workgroup, two per SIMD
-constexpr int kAsmQBufs = 2;      // Q chunk buffers in LDS
 constexpr int kAsmQD = 4;         // B fragments read ahead
 template <int SPACE, int R, bool I8, int NQT>
 __global__ __launch_bounds__(kAsmWaves * 64, 2) void filter_scan_asm_kernel(const FilterArgs a, const int64_t tile_begin,

@@ -24,7 +24,9 @@ ArchVGPRs (see generate).
   * Q (query image, L2): 64-column chunks, double buffered in LDS, one s_barrier per chunk.  Early
     in chunk c every wave sends its share of chunk c+1 global -> LDS directly (buffer_load ... lds;
     the LDS address is M0 + 16*lane) and waits for it before the barrier.  vmcnt completes in
-    order, so waiting for a Q transfer also waits for every X refill issued before it.
+    order, so waiting for a Q transfer also waits for every X refill issued before it.  The int8 bodies (integer sums: any
+    chunk order gives the same bits) walk the chunks zig-zag, up in a workgroup's even tiles and down in its odd ones, and
+    stage only the chunks that are not still in LDS from the turn (q_schedule).
   * the 32 B fragments of a chunk are one software-pipelined stream: ds_read_b128 runs QD
     fragments ahead of the two MFMAs that consume a fragment.
   * admission test per query tile: 8 bounds per lane (same arithmetic as scan_epilogue), their
@@ -42,6 +44,7 @@ MT = 2                    # row panels of 16 rows per wave
 NW = 8                    # waves per workgroup
 QD = 4                    # B fragments read ahead of their MFMAs
 CHUNK_BYTES = 0x8000      # 256 queries x 64 columns x 2 B
+Q_BUFS = 2                # Q chunk buffers in LDS (kAsmQBufs: scan_asm_consts.inc)
 WG_CAP = 16384            # kWgCap: append entries per workgroup (split evenly over its waves)
 SPACES = {"l2": 0, "cosine": 1, "ip": 2}
 I8_SPACE = None
@@ -51,9 +54,34 @@ VA_BASE = 64   # v0..v63 stay with the compiler (the statement's "v" operands)
 L2C = False    # generate(): int8 l2 -- the admission test made sharp by per-row integer offsets that enter the accumulators
 #                through the first k-step's C operand, ONE query scale SQ and ONE error coefficient KE for the whole pass (the
 #                prep builds the images that way): the pre-test is cosine's -- one fma against a threshold held in a register
+ZZ = False     # generate(): the int8 bodies walk the k-chunks zig-zag -- up in a workgroup's even tiles, down in its odd ones (q_schedule)
 NQT = 16       # generate(): query tiles (of 16 queries) the body computes: 16 = a full 256-query pass; 8 / 4 (int8 bodies) for
 #                passes of <= 128 / <= 64 queries -- the MFMAs, B-fragment reads, Q staging and admission tests of the empty tiles are
 #                not issued at all, which leaves a pure stream of the shadow (see generate)
+
+
+class VmWait:
+    """A counted vmcnt wait site in Sched.lines: n operations may stay in flight (None: an earlier wait covers it).  What
+    was issued before a body depends on which body ran before it; body_lines simulates every predecessor sequence and
+    keeps, per site, the smallest count."""
+
+    def __init__(self, n):
+        self.n = n
+
+
+def merge_waits(variants):
+    """Line lists of one body under different histories -> one list; every VmWait site takes its strictest count."""
+    assert len({len(v) for v in variants}) == 1
+    out = []
+    for group in zip(*variants):
+        if isinstance(group[0], VmWait):
+            counts = [w.n for w in group if w.n is not None]
+            if counts:
+                out.append(f"s_waitcnt vmcnt({min(counts)})")
+        else:
+            assert all(g == group[0] for g in group), group
+            out.append(group[0])
+    return out
 
 
 class Sched:
@@ -92,10 +120,11 @@ class Sched:
     def need_vm(self, *tags):
         idx = max(self._last(self.vm, t) for t in tags)
         if idx < self.vm_done:
+            self.emit(VmWait(None))
             return
         n = len(self.vm) - 1 - idx
         assert n <= 63, n
-        self.emit(f"s_waitcnt vmcnt({n})")
+        self.emit(VmWait(n))
         self.vm_done = idx + 1
 
     def need_lg(self, *tags):
@@ -131,6 +160,10 @@ def ring(b, m):
 # explicit scalar registers (listed as clobbers): descriptors need sub-register arithmetic
 PRIO_STEPS = {8: (0, 2), 12: (1, 2), 16: (0, 1), 20: (1, 1), 24: (0, 0), 28: (1, 0)}   # fragment -> (wave half, priority)
 XCUR, XNEXT, RNS, RET = "s[80:83]", "s[84:87]", "s[88:91]", "s[92:93]"
+# zig-zag bodies: the direction of the tile whose k-steps the X cursors fetch / whose chunks are staged, in the two scratch
+# SGPRs of the statement: XSTEP = what a chunk's second k-step adds to the cursors (0x400 upwards, -0xC00 downwards),
+# QSTEP = +- one chunk of the query image
+XSTEP, QSTEP = "%[sacc0]", "%[sacc1]"
 
 
 def gen_pretest(s, n, part):
@@ -266,6 +299,48 @@ def gen_rowmax(s, part):
         max_tree(a, "%[e12]", "p")
 
 
+def q_schedule(nkc, bufs):
+    """Which Q chunk a tile computes at each chunk position, where it sits in LDS and what is staged meanwhile.
+
+    nkc: 128-column chunks of the image (ld8 / 128, even); bufs: chunk buffers in LDS.  Returns table[parity][p] =
+    (chunk, buffer, stage) for the workgroup's even (parity 0) / odd (1) tiles; stage = (chunk, buffer) sent L2 -> LDS during
+    position p, or None.  Integer accumulation is exact and associative, so the order of the chunks is free: even tiles
+    ascend, odd tiles descend, and the `bufs` chunks a tile ends on are the ones the next tile starts on.  Chunk c always
+    sits in buffer c % bufs (any `bufs` consecutive chunks are distinct there); a chunk is staged one position before its
+    use unless it is still resident from the turn.  The prologue stages chunks 0 .. min(nkc, bufs) - 1; with nkc <= bufs
+    nothing is ever staged again.  The buffer written at position p held the chunk used at position p - bufs + 1: never
+    the current one, and its last read lies behind at least one chunk barrier."""
+    assert nkc >= 2 and nkc % 2 == 0 and bufs in (2, 3)
+    table = []
+    for parity in (0, 1):
+        rows = []
+        for p in range(nkc):
+            c = p if parity == 0 else nkc - 1 - p
+            nxt = c + 1 if parity == 0 else c - 1                      # the chunk of position p + 1
+            turn = range(bufs) if parity == 0 else range(nkc - bufs, nkc)   # resident when the tile starts
+            stage = (nxt, nxt % bufs) if 0 <= nxt < nkc and nxt not in turn else None
+            rows.append((c, c % bufs, stage))
+        table.append(rows)
+    return table
+
+
+def body_stage_flags(bufs=None):
+    """The bodies are generic over nkc (a tile = first body, nkc/2 - 2 middle bodies, last body; or the single body of nkc = 2),
+    two chunk positions each: whether a position stages must therefore depend on the body alone -- not on nkc, not on the
+    tile's direction.  Read from q_schedule, and checked for every nkc."""
+    bufs = bufs or Q_BUFS
+    flags = {}
+    for nkc in (2, 4, 6, 8, 10, 16, 32):
+        for rows in q_schedule(nkc, bufs):
+            st = [r[2] is not None for r in rows]
+            kinds = {"single": st} if nkc == 2 else {"first": st[:2], "last": st[-2:],
+                                                     **{f"mid{i}": st[i:i + 2] for i in range(2, nkc - 2, 2)}}
+            for kind, f in kinds.items():
+                kind = kind.rstrip("0123456789")
+                assert flags.setdefault(kind, tuple(f)) == tuple(f), (nkc, kind, f, flags)
+    return flags
+
+
 def dma_pieces():
     """This wave's LDS-DMA transfers per chunk: (set name, index, byte offset inside the chunk / the LDS buffer).
     A chunk is 2 * NQT fragments of 1 KiB at n * 2048 + h * 1024 (the image keeps the 16-tile layout whatever NQT is).
@@ -279,11 +354,14 @@ def dma_pieces():
     return [("qb", 0, 0)]
 
 
-def gen_chunk(s, R, step0, zero_first, last, final):
+def gen_chunk(s, R, step0, zero_first, last, final, turn=False, stage=True):
     """One 64-column chunk = 2 k-steps = 2 * NQT fragments x MT MFMAs.  final: the tile's last chunk, whose second k-step
-    carries the admission pre-tests (int8)."""
-    s.emit("v_xor_b32 %[ldr], 0x8000, %[ldr]")
-    s.emit("s_xor_b32 %[sldw], %[sldw], 0x8000")
+    carries the admission pre-tests (int8).  Zig-zag bodies: turn = the tile's first chunk, which sits in the buffer the
+    previous tile ended on (no toggle); stage = whether this position sends a chunk to the other buffer (q_schedule)."""
+    assert ZZ or (stage and not turn)
+    if not turn:
+        s.emit("v_xor_b32 %[ldr], 0x8000, %[ldr]")
+        s.emit("s_xor_b32 %[sldw], %[sldw], 0x8000")
 
     NF = 2 * NQT   # fragments per chunk: NQT query tiles x 2 k-steps (k-step major)
 
@@ -294,6 +372,16 @@ def gen_chunk(s, R, step0, zero_first, last, final):
     def refill(h):
         step = step0 + h
         b = step % R
+        if ZZ:
+            # One cursor per panel for the whole stream: k-step R ahead of the one just computed, in EXECUTED order.  A
+            # tile walks its chunks up or down but the two k-steps inside a chunk always upwards (the fragment offsets in
+            # LDS stay what they are): + 0x400 after a chunk's first k-step, XSTEP (+ 0x400 / - 0xC00) after its second.
+            # In the tile's last body the cursor already walks the workgroup's next tile (gen_body), through XNEXT.
+            for m in range(MT):
+                s.vmem(f"buffer_load_dwordx4 {ring(b, m)}, %[lane16], {XNEXT if last else XCUR}, %[xso{m}] offen nt", ("x", b, m))
+            for m in range(MT):
+                s.emit(f"s_add_u32 %[xso{m}], %[xso{m}], " + ("0x400" if h == 0 else XSTEP))
+            return
         for m in range(MT):
             if last:   # the workgroup's next tile: k-step `step` (< R <= 4: fits the instruction offset)
                 so = "0" if m == 0 else "%[pb]"
@@ -347,7 +435,7 @@ def gen_chunk(s, R, step0, zero_first, last, final):
                     gen_pretest(s, n - 2, m)
         if f + QD < NF:
             read(f + QD)
-        if f in plan:
+        if f in plan and stage:
             setname, i, const = plan[f]
             s.emit(f"s_add_u32 m0, %[sldw], 0x{const:x}")
             s.emit(f"s_add_u32 %[st0], %[qcur], 0x{const:x}")
@@ -362,10 +450,15 @@ def gen_chunk(s, R, step0, zero_first, last, final):
         gen_pretest(s, NQT - 1, 0)
         gen_pretest(s, NQT - 1, 1)
     # advance the Q cursor (chunk c+2 -> c+3, wrapping) and publish the chunk just staged
-    s.emit("s_add_u32 %[qcur], %[qcur], 0x8000")
-    s.emit("s_cmp_eq_u32 %[qcur], %[qbytes]")
-    s.emit("s_cselect_b32 %[qcur], 0, %[qcur]")
-    s.need_vm(*[(sn, i) for sn, i, _ in dma_pieces()])   # this wave's share of the chunk staged since the last barrier
+    if ZZ:
+        if stage:   # (a position that stages nothing issues no transfer and waits for none)
+            s.emit(f"s_add_u32 %[qcur], %[qcur], {QSTEP}")   # the next chunk in the tile's direction: no wrap inside a tile
+            s.need_vm(*[(sn, i) for sn, i, _ in dma_pieces()])
+    else:
+        s.emit("s_add_u32 %[qcur], %[qcur], 0x8000")
+        s.emit("s_cmp_eq_u32 %[qcur], %[qbytes]")
+        s.emit("s_cselect_b32 %[qcur], 0, %[qcur]")
+        s.need_vm(*[(sn, i) for sn, i, _ in dma_pieces()])   # this wave's share of the chunk staged since the last barrier
     s.drain_lg()
     s.emit("s_barrier")
 
@@ -385,6 +478,16 @@ def gen_eo_loads(s):
 
 
 def gen_body(s, R, first, last):
+    if ZZ and last:
+        # From here on the X cursors fetch the workgroup's NEXT tile, which walks the other way: its first executed k-step
+        # is column step 0 (upwards) or the first of its last chunk, 2 nkc - 2 = qbytes / 0x4000 - 2 (downwards) -- all of it
+        # in the scalar offset, so one instruction serves both directions.
+        s.emit(f"s_sub_u32 {XSTEP}, 0xfffff800, {XSTEP}")     # 0x400 <-> -0xC00
+        s.emit("s_lshr_b32 %[st0], %[qbytes], 4")
+        s.emit("s_sub_u32 %[st0], %[st0], 0x800")
+        s.emit(f"s_cmp_eq_u32 {XSTEP}, 0x400")
+        s.emit("s_cselect_b32 %[xso0], 0, %[st0]")
+        s.emit("s_add_u32 %[xso1], %[pb], %[xso0]")
     if last and L2C and not first:
         # issued before the row-pair loads below: in-order completion makes the wait for those a wait for these too.  (The
         # offsets in the registers now were last read in this tile's FIRST k-step, which is not in this body.)
@@ -406,21 +509,47 @@ def gen_body(s, R, first, last):
     for ch in range(R // 2):
         if last and L2C and first and ch == 1:   # a one-body tile: its own offsets were read in chunk 0's first k-step
             gen_eo_loads(s)
+        if ZZ:
+            kind = ("single" if last else "first") if first else ("last" if last else "mid")
+            gen_chunk(s, R, 2 * ch, first and ch == 0, last, last and ch == R // 2 - 1, turn=first and ch == 0,
+                      stage=body_stage_flags()[kind][ch])
+            continue
         gen_chunk(s, R, 2 * ch, first and ch == 0, last, I8 and last and ch == R // 2 - 1)
     if last:
         s.need_vm(*([("rn", j) for j in range(4 * MT)] + ([("eo", m) for m in range(MT)] if L2C else [])))
 
 
+FIRST, MID, LAST, SINGLE = (True, False), (False, False), (False, True), (True, True)   # (first, last) of a tile's bodies
+
+
+def histories(first, last):
+    """The body sequences that can run before a body, two deep (every target of a counted wait -- ring slot, Q set, row
+    pairs -- was issued at most one body earlier).  bf16 bodies: every body issues the middle body's pattern of ring and Q
+    operations.  Zig-zag bodies do not (a position that stages nothing issues fewer), so every real predecessor sequence is
+    simulated.  A workgroup's first tile follows the prologue's vmcnt(0): its queue holds less than any history here, which
+    only makes a counted wait stricter than needed."""
+    if not ZZ:
+        return [[MID, MID]]
+    if (first, last) == SINGLE:
+        return [[SINGLE, SINGLE]]
+    if first:
+        return [[FIRST, LAST], [MID, LAST]]
+    return [[LAST, FIRST], [FIRST, MID], [MID, MID]]
+
+
 def body_lines(R, first, last, label0=0):
-    s = Sched()
-    s.recording = False
-    for _ in range(2):   # history: every predecessor issues this pattern of memory operations
-        gen_body(s, R, False, False)
-    s.recording = True
-    s.label = label0
-    s.copy = str(label0)
-    gen_body(s, R, first, last)
-    return s.lines
+    variants = []
+    for hist in histories(first, last):
+        s = Sched()
+        s.recording = False
+        for f, l in hist:
+            gen_body(s, R, f, l)
+        s.recording = True
+        s.label = label0
+        s.copy = str(label0)
+        gen_body(s, R, first, last)
+        variants.append(s.lines)
+    return merge_waits(variants)
 
 
 def gen_admission(space):
@@ -519,7 +648,7 @@ def gen_hit_stubs(copy=""):
 def lds_stage_cap():
     """Entries of a wave's staging area in LDS (12 B each, SoA): what is left of the 160 KiB per CU."""
     wgs_per_cu = (16 // MT) // NW      # two waves per SIMD
-    per_wg = (160 * 1024) // wgs_per_cu - (2 * CHUNK_BYTES + 3072)   # Q buffers + thr[256], qscale[256], ke[256]
+    per_wg = (160 * 1024) // wgs_per_cu - (Q_BUFS * CHUNK_BYTES + 3072)   # Q buffers + thr[256], qscale[256], ke[256]
     return min(WG_CAP // NW, (per_wg // NW) // 12 // 8 * 8)
 
 
@@ -666,13 +795,14 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     KE = max_q 2 |q| ke_q stands for every query's: u'_j = float(I_j + e_j) (S SQ) + (KE N_j + P0).  The per-query constants
     shrink to the threshold, kept in registers for the launch like cosine's; S SQ and KE N_j + P0 are formed once per row
     tile (gen_rowmax_l2c).  SQ, KE: scalars of the pass (filter_l2_offsets_kernel)."""
-    global I8, I8_SPACE, NQT, L2C
+    global I8, I8_SPACE, NQT, L2C, ZZ
     assert R in (2, 4) and nqt in (4, 8, 16) and (nqt == 16 or i8) and (not i8 or R == 4)
     assert l2c == (i8 and space == "l2")
     I8 = i8
     I8_SPACE = space if i8 else None
     NQT = nqt
     L2C = l2c
+    ZZ = i8
     out = []
     a = out.append
     # ---- descriptors and per-workgroup state
@@ -693,13 +823,29 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     a("s_mov_b32 %[tl], %[ntiles]")
     a("s_mov_b32 %[trow], %[row0]")
     a("s_mov_b32 %[wcnt], 0")
-    a("v_add_u32 %[ldr], 0x8000, %[lane16]")   # the first chunk moves it to buffer 0
-    # ---- prologue: Q chunk 0 -> LDS buffer 0, k-steps 0..R-1 -> the ring
-    a("s_mov_b32 %[sldw], %[wave2k]")          # buffer 0; the first chunk toggles it to buffer 1
-    for _, _, const in dma_pieces():
-        a(f"s_add_u32 m0, %[sldw], 0x{const:x}")
-        a(f"s_movk_i32 %[st0], 0x{const:x}")
-        a("buffer_load_dwordx4 %[qvoff], %[qsrd], %[st0] offen lds")
+    if ZZ:
+        # ---- prologue: Q chunks 0 and 1 -> LDS buffers 0 and 1 (what every even tile starts on: q_schedule), k-steps 0..R-1 ->
+        # the ring.  A tile's first chunk does not toggle the buffers: reads start in buffer 0, transfers go to the other one.
+        assert Q_BUFS == 2   # (the xor toggle; a third buffer needs a rotation here and in gen_chunk)
+        a("v_mov_b32 %[ldr], %[lane16]")
+        a("s_add_u32 %[sldw], %[wave2k], 0x8000")
+        for c in range(Q_BUFS):
+            for _, _, const in dma_pieces():
+                a(f"s_add_u32 m0, %[wave2k], 0x{c * CHUNK_BYTES + const:x}")
+                a(f"s_mov_b32 %[st0], 0x{c * CHUNK_BYTES + const:x}")
+                a("buffer_load_dwordx4 %[qvoff], %[qsrd], %[st0] offen lds")
+        a(f"s_mov_b32 {XSTEP}, 0x400")             # the first tile walks upwards
+        a(f"s_mov_b32 {QSTEP}, 0xffff8000")        # (.Ltile negates it)
+        a(f"s_movk_i32 %[xso0], 0x{R * 1024:x}")   # the X cursors: k-step R of the first tile; they never restart (gen_chunk)
+        a("s_add_u32 %[xso1], %[pb], %[xso0]")
+    else:
+        a("v_add_u32 %[ldr], 0x8000, %[lane16]")   # the first chunk moves it to buffer 0
+        # ---- prologue: Q chunk 0 -> LDS buffer 0, k-steps 0..R-1 -> the ring
+        a("s_mov_b32 %[sldw], %[wave2k]")          # buffer 0; the first chunk toggles it to buffer 1
+        for _, _, const in dma_pieces():
+            a(f"s_add_u32 m0, %[sldw], 0x{const:x}")
+            a(f"s_movk_i32 %[st0], 0x{const:x}")
+            a("buffer_load_dwordx4 %[qvoff], %[qsrd], %[st0] offen lds")
     for b in range(R):
         for m in range(MT):
             so = "0" if m == 0 else "%[pb]"
@@ -723,9 +869,15 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     a("s_cselect_b32 %[cnt], %[xshi], 0")
     a("s_add_u32 s84, s80, %[st0]")
     a("s_addc_u32 s85, s81, %[cnt]")
-    a("s_mov_b32 %[qcur], %[qc1]")       # first chunk staged inside this tile's loop
-    a(f"s_movk_i32 %[xso0], 0x{R * 1024:x}")
-    a("s_add_u32 %[xso1], %[pb], %[xso0]")
+    if ZZ:   # this tile's direction; the first chunk it stages (at its second position) is chunk 2, or nkc - 3 on the way down
+        a(f"s_sub_u32 {QSTEP}, 0, {QSTEP}")
+        a("s_sub_u32 %[st0], %[qbytes], 0x18000")
+        a(f"s_cmp_gt_i32 {QSTEP}, 0")
+        a("s_cselect_b32 %[qcur], 0x10000, %[st0]")
+    else:
+        a("s_mov_b32 %[qcur], %[qc1]")       # first chunk staged inside this tile's loop
+        a(f"s_movk_i32 %[xso0], 0x{R * 1024:x}")
+        a("s_add_u32 %[xso1], %[pb], %[xso0]")
     a("s_cmp_eq_u32 %[nb], 1")
     a("s_cbranch_scc1 .Lsingle_%=")
     out += body_lines(R, True, False, 0)
@@ -818,7 +970,7 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
 
     text = ["// GENERATED by tools/gen_scan_asm.py -- do not edit.",
             f"// filter scan body: space {space}, NW={NW} waves x {16 * MT} rows, ring R={R} k-steps, B fragments read {QD} ahead"
-            f", X loads non-temporal{', progress-based wave priority' if i8 else ''}, Q staged by LDS-DMA"
+            f", X loads non-temporal{', progress-based wave priority' if i8 else ''}, Q staged by LDS-DMA{', k-chunks zig-zag' if ZZ else ''}"
             f"{', int8 shadow (v_mfma_i32_16x16x64_i8)' if i8 else ''}{', accumulators in ArchVGPRs' if i8 else ''}.",
             "asm volatile("]
     for ln in out:
@@ -879,6 +1031,7 @@ def main():
     (out / "scan_asm_consts.inc").write_text(
         "// GENERATED by tools/gen_scan_asm.py -- do not edit.\n"
         f"constexpr int kAsmWgCap = {WG_CAP};\n"
+        f"constexpr int kAsmQBufs = {Q_BUFS};  // Q chunk buffers in LDS\n"
         f"constexpr int kAsmStageCap = {lds_stage_cap()};  // entries per wave staged in LDS\n")
     print("wrote", len(names), "files to", args.outdir)
 
