@@ -676,6 +676,7 @@ int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, int
     FilterArgs fa{};
     int rc = begin_pass(h, s, fa, queries_raw, q0, nq, false);
     if (rc) return rc;
+    fa.scan_q4 = k <= 64;
     // Small batches (k <= 64, int8 shadow, no row mask), up to SMALL_NQ queries (at most 8; default 2):
     //  - seed (SMALL_SEED): the exact k-th best of the prefix by a kernel made for it (one 16-row group per wave all over the
     //    chip + a one-block selection of the k-th: 8 + 10 us) instead of the dense int8 pass + exact-threshold refine (7 + 15.5 us

@@ -227,6 +227,8 @@ struct FilterArgs {
     struct RangeHit* rs;    // kNN passes: [256][kCandCap] exact (distance, label) of every rescored candidate (filter_rescore_score_kernel -> _rank_kernel)
     WgEntry* wgbuf;         // [kScanMaxGrid][kWgCap] append buffers of one scan launch, one slice per wave
     uint32_t* wgcnt;        // [kScanMaxGrid * 8] entries appended per wave (may exceed the slice: the excess was flagged as overflow)
+    int32_t scan_q4;        // host only: a k <= 64 kNN pass (run_filter_pass sets it, nobody else) -- its scans append few entries
+                            // per wave and may take the four-buffer int8 body, whose LDS staging area is small (launch_scan_space)
 };
 hipError_t launch_filter_prep(const FilterArgs& a, hipStream_t s);
 // query_prep + filter_prep + filter_prep8 (when a.X8) of one pass in one launch (+ the one-block fin): `queries` = the pass's raw

@@ -624,10 +624,11 @@ __device__ __forceinline__ float l2c_delta(const FilterArgs& a, int q) {
 }
 // The bodies (tools/gen_scan_asm.py, entries): R = the ring's k-steps (4; bf16 also 2, for odd chunk counts); I8 = the int8
 // shadow (k-steps of 64 int8 columns, same bytes per step; l2: the l2c body), else bf16; NQT = the query tiles the body
-// computes (int8: 8 / 4 for passes of <= 128 / <= 64 queries, else 16).
+// computes (int8: 8 / 4 for passes of <= 128 / <= 64 queries, else 16); QB = the Q chunk buffers in LDS (4: the int8 bodies of
+// a full pass over an image of exactly kAsmQ4Chunks chunks, whose staging areas are what four buffers leave: kAsmQ4StageCap).
 constexpr int kAsmWaves = 8;      // waves per workgroup, two per SIMD
 constexpr int kAsmQD = 4;         // B fragments read ahead
-template <int SPACE, int R, bool I8, int NQT>
+template <int SPACE, int R, bool I8, int NQT, int QB = kAsmQBufs>
 __global__ __launch_bounds__(kAsmWaves * 64, 2) void filter_scan_asm_kernel(const FilterArgs a, const int64_t tile_begin,
                                                                            const int64_t tile_end, const int xcd_mode) {
     constexpr int NW = kAsmWaves, MT = 2;
@@ -635,9 +636,10 @@ __global__ __launch_bounds__(kAsmWaves * 64, 2) void filter_scan_asm_kernel(cons
     constexpr int kThreads = NW * 64;
     constexpr int kWaveRows = 16 * MT;
     constexpr int kTileRowsV = NW * kWaveRows;
-    constexpr int kQBufs = kAsmQBufs;
-    constexpr int kStageCap = kAsmStageCap;  // entries a wave stages in LDS
-    // LDS: [2][32 KiB] Q chunks at offset 0, thr[256], qscale[256], ke[256], [NW waves] staging {u[], row[], q[]}
+    static_assert(QB == kAsmQBufs || (QB == 4 && I8 && NQT == 16 && R == 4), "tools/gen_scan_asm.py, entries()");
+    constexpr int kQBufs = QB;
+    constexpr int kStageCap = QB == 4 ? kAsmQ4StageCap : kAsmStageCap;  // entries a wave stages in LDS
+    // LDS: [kQBufs][32 KiB] Q chunks at offset 0, thr[256], qscale[256], ke[256], [NW waves] staging {u[], row[], q[]}
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* thr_l = reinterpret_cast<float*>(smem + kQBufs * kChunkVec * sizeof(uint4));
     float* sq_l = thr_l + kFilterQueries;
@@ -690,7 +692,7 @@ __global__ __launch_bounds__(kAsmWaves * 64, 2) void filter_scan_asm_kernel(cons
     }
     if (my_tiles == 0) return;
     const uint32_t lds_base = (uint32_t)reinterpret_cast<uintptr_t>(smem);
-    // The assembly toggles the Q buffers with xor 0x8000, so the dynamic LDS must start at 0, i.e. the kernel may have no
+    // The assembly toggles the Q buffers with xor 0x8000 (four buffers: wraps the read base at 128 KiB), so the dynamic LDS must start at 0, i.e. the kernel may have no
     // static LDS: launch_scan_asm checks that on the host (hipFuncGetAttributes) before the first launch.  Should it ever be
     // violated all the same, the workgroup hands its queries to the exact fallback (overflow flags) instead of trapping.
     if (lds_base != 0) {
@@ -783,7 +785,8 @@ __global__ __launch_bounds__(kAsmWaves * 64, 2) void filter_scan_asm_kernel(cons
     // launch of its own).  Every wave staged its entries {u[], row[], q[]} in its LDS area (the first kStageCap of
     // them; later ones went to its slice of a.wgbuf, same slot numbering, stores drained); s_wcnt = how many it
     // appended.  Entries are counted per query in LDS first, so the workgroup issues one device-scope atomic per query it
-    // has entries for.  The Q buffers are free by now: every wave has passed the last chunk barrier of its last tile.
+    // has entries for.  The Q buffers are free by now: every wave has passed the last chunk barrier of its last tile (or,
+    // in a body that has none there, the barrier that closes the assembly).
     {
         uint32_t* hist = reinterpret_cast<uint32_t*>(smem);          // [256]
         uint32_t* lbase = hist + kFilterQueries;                      // [256]
@@ -2655,17 +2658,19 @@ static hipError_t launch_scan_narrow(const FilterArgs& a, int64_t row_begin, int
     }
 }
 
-template <int SPACE, int R, bool I8, int NQT = 16>
+template <int SPACE, int R, bool I8, int NQT = 16, int QB = kAsmQBufs>
 static hipError_t launch_scan_asm(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
     constexpr int NW = kAsmWaves, tile_rows = NW * 32;
     const int64_t tile_begin = row_begin / tile_rows;
     const int64_t tile_end = (row_end + tile_rows - 1) / tile_rows;
     if (tile_end <= tile_begin) return hipSuccess;
-    const size_t lds = kAsmQBufs * kChunkVec * sizeof(uint4) + 3 * kFilterQueries * sizeof(float) + (size_t)NW * 12 * kAsmStageCap;
+    constexpr int stage_cap = QB == 4 ? kAsmQ4StageCap : kAsmStageCap;
+    constexpr size_t lds = QB * kChunkVec * sizeof(uint4) + 3 * kFilterQueries * sizeof(float) + (size_t)NW * 12 * stage_cap;
+    static_assert(lds <= 160 * 1024, "one workgroup per CU");
     const int64_t ntiles = tile_end - tile_begin;
     const int max_grid = 256;  // one 8-wave workgroup per CU: two waves per SIMD (<= kScanMaxGrid)
     const int grid = (int)(ntiles < max_grid ? ntiles : max_grid);
-    auto kern = filter_scan_asm_kernel<SPACE, R, I8, NQT>;
+    auto kern = filter_scan_asm_kernel<SPACE, R, I8, NQT, QB>;
     static std::atomic<uint64_t> configured{0};  // per instantiation
     static std::atomic<int> lds_base_ok{0};      // 0 = not checked yet, 1 = ok, -1 = the kernel has static LDS
     if (lds_base_ok.load(std::memory_order_acquire) == 0) {
@@ -2697,6 +2702,11 @@ static hipError_t launch_scan_space(const FilterArgs& a, int64_t row_begin, int6
         const int nqt = a.tn->scan_nqt > 0 ? a.tn->scan_nqt : (a.nq <= 64 ? 4 : (a.nq <= 128 ? 8 : 16));
         if (nqt <= 4 && a.nq <= 64) return launch_scan_asm<SPACE, 4, true, 4>(a, row_begin, row_end, s);
         if (nqt <= 8 && a.nq <= 128) return launch_scan_asm<SPACE, 4, true, 8>(a, row_begin, row_end, s);
+        // a full pass of a k <= 64 kNN call over an image of six chunks (d = 641..768): four chunk buffers, two of them
+        // written once per launch, a tile stages two chunks instead of four.  Range and big-k passes append far more per wave
+        // than the staging area four buffers leave, so they stay on two
+        if (a.scan_q4 && a.nq > 128 && a.ld8 == kAsmQ4Chunks * 2 * kFilterChunkK)
+            return launch_scan_asm<SPACE, 4, true, 16, 4>(a, row_begin, row_end, s);
         return launch_scan_asm<SPACE, 4, true, 16>(a, row_begin, row_end, s);
     }
     if (a.Xb) {  // bf16 shadow; a ring of R k-steps needs the tile's k-steps (two per chunk) to be a multiple of R

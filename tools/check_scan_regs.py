@@ -18,8 +18,8 @@ import tempfile
 from pathlib import Path
 
 LLVM = Path("/opt/rocm/lib/llvm/bin")
-# filter_scan_asm_kernel<SPACE, R, I8, NQT>: the int8 bodies (I8 = true) are the ArchVGPR bodies, one per space and query-tile
-# count (kernels_filter.hip, launch_scan_space)
+# filter_scan_asm_kernel<SPACE, R, I8, NQT, QB>: the int8 bodies (I8 = true) are the ArchVGPR bodies, one per space and query-tile
+# count, and one per space with four Q buffers (kernels_filter.hip, launch_scan_space)
 I8_BODY = re.compile(r"_ZN5mlvdb22filter_scan_asm_kernelILi(\d)ELi(\d)ELb1ELi(\d+)E")
 WANT = {".vgpr_count": 240, ".vgpr_spill_count": 0, ".private_segment_fixed_size": 0}
 
@@ -54,8 +54,8 @@ def main(argv):
         for key, want in WANT.items():
             if f.get(key) != want:
                 bad.append(f"{name}: {key} = {f.get(key)} (want {want})")
-    if checked != 9:
-        bad.append(f"{checked} int8 scan bodies found in {obj} (want 9: three spaces x 16 / 8 / 4 query tiles)")
+    if checked != 12:
+        bad.append(f"{checked} int8 scan bodies found in {obj} (want 12: three spaces x (16 / 8 / 4 query tiles + four Q buffers))")
     if bad:
         print("check_scan_regs: the default scan bodies do not have the register budget they were written for:", file=sys.stderr)
         for b in bad:

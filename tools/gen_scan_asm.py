@@ -26,7 +26,9 @@ ArchVGPRs (see generate).
     the LDS address is M0 + 16*lane) and waits for it before the barrier.  vmcnt completes in
     order, so waiting for a Q transfer also waits for every X refill issued before it.  The int8 bodies (integer sums: any
     chunk order gives the same bits) walk the chunks zig-zag, up in a workgroup's even tiles and down in its odd ones, and
-    stage only the chunks that are not still in LDS from the turn (q_schedule).
+    stage only the chunks that are not still in LDS from the turn (q_schedule).  An image of exactly six chunks (ld8 = 768)
+    also has bodies with FOUR buffers (generate(..., qbufs=4)): chunks 2 and 3 stay in LDS for the whole launch, a tile
+    stages two chunks instead of four, and the wave's append staging area shrinks to what is left.
   * the 32 B fragments of a chunk are one software-pipelined stream: ds_read_b128 runs QD
     fragments ahead of the two MFMAs that consume a fragment.
   * admission test per query tile: 8 bounds per lane (same arithmetic as scan_epilogue), their
@@ -55,6 +57,11 @@ L2C = False    # generate(): int8 l2 -- the admission test made sharp by per-row
 #                through the first k-step's C operand, ONE query scale SQ and ONE error coefficient KE for the whole pass (the
 #                prep builds the images that way): the pre-test is cosine's -- one fma against a threshold held in a register
 ZZ = False     # generate(): the int8 bodies walk the k-chunks zig-zag -- up in a workgroup's even tiles, down in its odd ones (q_schedule)
+QB = 2         # generate(): Q chunk buffers of the body being generated: 2, or 4 (int8, NQT = 16, nkc = 6 only: chunks 2 and 3 stay in
+#                buffers 2 and 3 for the whole launch, a tile stages two chunks instead of four; see generate)
+Q4_NKC = 6     # the only chunk count the four-buffer bodies are written for (ld8 = 768)
+Q4_SPARSE_BARRIERS = False   # four-buffer bodies: False = one s_barrier per chunk position; True = only the barriers the two rules
+#                of q4_barrier_flags need (measured: DESIGN 5.2)
 NQT = 16       # generate(): query tiles (of 16 queries) the body computes: 16 = a full 256-query pass; 8 / 4 (int8 bodies) for
 #                passes of <= 128 / <= 64 queries -- the MFMAs, B-fragment reads, Q staging and admission tests of the empty tiles are
 #                not issued at all, which leaves a pure stream of the shadow (see generate)
@@ -310,7 +317,7 @@ def q_schedule(nkc, bufs):
     use unless it is still resident from the turn.  The prologue stages chunks 0 .. min(nkc, bufs) - 1; with nkc <= bufs
     nothing is ever staged again.  The buffer written at position p held the chunk used at position p - bufs + 1: never
     the current one, and its last read lies behind at least one chunk barrier."""
-    assert nkc >= 2 and nkc % 2 == 0 and bufs in (2, 3)
+    assert nkc >= 2 and nkc % 2 == 0 and bufs in (2, 3, 4)
     table = []
     for parity in (0, 1):
         rows = []
@@ -330,7 +337,8 @@ def body_stage_flags(bufs=None):
     tile's direction.  Read from q_schedule, and checked for every nkc."""
     bufs = bufs or Q_BUFS
     flags = {}
-    for nkc in (2, 4, 6, 8, 10, 16, 32):
+    # (four buffers: the positions that stage depend on nkc -- the bodies exist for Q4_NKC alone, first / mid / last once each)
+    for nkc in ((Q4_NKC,) if bufs == 4 else (2, 4, 6, 8, 10, 16, 32)):
         for rows in q_schedule(nkc, bufs):
             st = [r[2] is not None for r in rows]
             kinds = {"single": st} if nkc == 2 else {"first": st[:2], "last": st[-2:],
@@ -339,6 +347,22 @@ def body_stage_flags(bufs=None):
                 kind = kind.rstrip("0123456789")
                 assert flags.setdefault(kind, tuple(f)) == tuple(f), (nkc, kind, f, flags)
     return flags
+
+
+def q4_barrier_flags(sparse=None):
+    """Four-buffer bodies: after which chunk positions of a tile the workgroup meets at an s_barrier, per body.  Two rules:
+      1. a transfer into a buffer is issued only after a barrier that every wave reaches after its last read of the chunk
+         that buffer held;
+      2. a staged chunk is first read only after a barrier that every wave reaches after its own vmcnt wait for its pieces.
+    The transfer of position p goes into the buffer that position p - 3 read (four buffers, one chunk ahead), and is first
+    read at p + 1: rule 2 asks for a barrier after every position that stages (the wait sits right before it), rule 1 for one
+    between positions p - 3 and p -- the one after position 1 serves both transfers (positions 3 and 4).  Not sparse: one
+    barrier after every position, as in the two-buffer bodies."""
+    sparse = Q4_SPARSE_BARRIERS if sparse is None else sparse
+    stage = [r[2] is not None for r in q_schedule(Q4_NKC, 4)[0]]
+    assert stage == [r[2] is not None for r in q_schedule(Q4_NKC, 4)[1]] == [False, False, False, True, True, False]
+    bar = [(not sparse) or stage[p] or p == 1 for p in range(Q4_NKC)]
+    return {"first": tuple(bar[0:2]), "mid": tuple(bar[2:4]), "last": tuple(bar[4:6])}
 
 
 def dma_pieces():
@@ -354,12 +378,21 @@ def dma_pieces():
     return [("qb", 0, 0)]
 
 
-def gen_chunk(s, R, step0, zero_first, last, final, turn=False, stage=True):
+def gen_chunk(s, R, step0, zero_first, last, final, turn=False, stage=True, barrier=True):
     """One 64-column chunk = 2 k-steps = 2 * NQT fragments x MT MFMAs.  final: the tile's last chunk, whose second k-step
     carries the admission pre-tests (int8).  Zig-zag bodies: turn = the tile's first chunk, which sits in the buffer the
     previous tile ended on (no toggle); stage = whether this position sends a chunk to the other buffer (q_schedule)."""
     assert ZZ or (stage and not turn)
-    if not turn:
+    assert barrier or QB == 4
+    if not turn and QB == 4:
+        # Chunk c sits in buffer c & 3: the read base moves one buffer in the tile's direction (QSTEP = +- 0x8000, uniform over
+        # the workgroup) and wraps at 128 KiB; lane16 < 0x8000 rides along.  Transfers only ever go to buffers 0 and 1, and
+        # alternately: the toggle at every position but a tile's first leaves sldw on buffer 0 at an upward tile's position 3
+        # (chunk 4) and on buffer 1 at a downward tile's (chunk 1) -- five toggles per tile, and the prologue starts it on buffer 1.
+        s.emit(f"v_add_u32 %[ldr], {QSTEP}, %[ldr]")
+        s.emit("v_and_b32 %[ldr], 0x1ffff, %[ldr]")
+        s.emit("s_xor_b32 %[sldw], %[sldw], 0x8000")
+    elif not turn:
         s.emit("v_xor_b32 %[ldr], 0x8000, %[ldr]")
         s.emit("s_xor_b32 %[sldw], %[sldw], 0x8000")
 
@@ -460,7 +493,8 @@ def gen_chunk(s, R, step0, zero_first, last, final, turn=False, stage=True):
         s.emit("s_cselect_b32 %[qcur], 0, %[qcur]")
         s.need_vm(*[(sn, i) for sn, i, _ in dma_pieces()])   # this wave's share of the chunk staged since the last barrier
     s.drain_lg()
-    s.emit("s_barrier")
+    if barrier:
+        s.emit("s_barrier")
 
 
 def gen_eo_loads(s):
@@ -512,7 +546,7 @@ def gen_body(s, R, first, last):
         if ZZ:
             kind = ("single" if last else "first") if first else ("last" if last else "mid")
             gen_chunk(s, R, 2 * ch, first and ch == 0, last, last and ch == R // 2 - 1, turn=first and ch == 0,
-                      stage=body_stage_flags()[kind][ch])
+                      stage=body_stage_flags(QB)[kind][ch], barrier=QB != 4 or q4_barrier_flags()[kind][ch])
             continue
         gen_chunk(s, R, 2 * ch, first and ch == 0, last, I8 and last and ch == R // 2 - 1)
     if last:
@@ -530,6 +564,8 @@ def histories(first, last):
     only makes a counted wait stricter than needed."""
     if not ZZ:
         return [[MID, MID]]
+    if QB == 4:   # a tile is first, mid, last, once each (Q4_NKC chunks): one predecessor sequence per body
+        return [{FIRST: [MID, LAST], MID: [LAST, FIRST], LAST: [FIRST, MID]}[(first, last)]]
     if (first, last) == SINGLE:
         return [[SINGLE, SINGLE]]
     if first:
@@ -645,10 +681,12 @@ def gen_hit_stubs(copy=""):
     return out
 
 
-def lds_stage_cap():
-    """Entries of a wave's staging area in LDS (12 B each, SoA): what is left of the 160 KiB per CU."""
+def lds_stage_cap(bufs=None):
+    """Entries of a wave's staging area in LDS (12 B each, SoA): what is left of the 160 KiB per CU beside `bufs` Q buffers
+    (default: the body being generated)."""
+    bufs = bufs or QB
     wgs_per_cu = (16 // MT) // NW      # two waves per SIMD
-    per_wg = (160 * 1024) // wgs_per_cu - (Q_BUFS * CHUNK_BYTES + 3072)   # Q buffers + thr[256], qscale[256], ke[256]
+    per_wg = (160 * 1024) // wgs_per_cu - (bufs * CHUNK_BYTES + 3072)   # Q buffers + thr[256], qscale[256], ke[256]
     return min(WG_CAP // NW, (per_wg // NW) // 12 // 8 * 8)
 
 
@@ -768,7 +806,7 @@ def gen_slow_fast():
     return o
 
 
-def generate(space, R, i8=False, nqt=16, l2c=False):
+def generate(space, R, i8=False, nqt=16, l2c=False, qbufs=2):
     """One body: bf16 (i8 False; R = 4, or 2 for an odd number of chunks) or int8 (R = 4; nqt query tiles; l2: l2c).
 
     i8: the 64*MT accumulator registers are ArchVGPRs, named explicitly (v[VA_BASE:...], clobbered), and the MFMA operands --
@@ -794,10 +832,26 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     quantises every query of the pass with one step, so that sq = SQ for all of them, and one error coefficient
     KE = max_q 2 |q| ke_q stands for every query's: u'_j = float(I_j + e_j) (S SQ) + (KE N_j + P0).  The per-query constants
     shrink to the threshold, kept in registers for the launch like cosine's; S SQ and KE N_j + P0 are formed once per row
-    tile (gen_rowmax_l2c).  SQ, KE: scalars of the pass (filter_l2_offsets_kernel)."""
-    global I8, I8_SPACE, NQT, L2C, ZZ
+    tile (gen_rowmax_l2c).  SQ, KE: scalars of the pass (filter_l2_offsets_kernel).
+
+    qbufs = 4 (int8, nqt = 16; an image of exactly Q4_NKC = 6 chunks, ld8 = 768): four chunk buffers at 0 / 32 / 64 / 96 KiB,
+    chunk c in buffer c & 3.  The prologue stages chunks 0..3; chunks 2 and 3 are never written again, a tile stages two
+    chunks (4 and 5 on the way up, 1 and 0 on the way down, into buffers 0 and 1) instead of four.  A tile is exactly three
+    bodies -- first, mid, last -- so there is no single body; the wave's staging area shrinks to lds_stage_cap(4) entries
+    (entries beyond it take .Lovf's global path), which is why only k <= 64 kNN passes run these bodies (launch_scan_space)."""
+    global I8, I8_SPACE, NQT, L2C, ZZ, QB
     assert R in (2, 4) and nqt in (4, 8, 16) and (nqt == 16 or i8) and (not i8 or R == 4)
     assert l2c == (i8 and space == "l2")
+    assert qbufs == 2 or (qbufs == 4 and i8 and nqt == 16)
+    QB = qbufs
+    try:
+        return _generate(space, R, i8, nqt, l2c)
+    finally:
+        QB = 2
+
+
+def _generate(space, R, i8, nqt, l2c):
+    global I8, I8_SPACE, NQT, L2C, ZZ
     I8 = i8
     I8_SPACE = space if i8 else None
     NQT = nqt
@@ -826,10 +880,12 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     if ZZ:
         # ---- prologue: Q chunks 0 and 1 -> LDS buffers 0 and 1 (what every even tile starts on: q_schedule), k-steps 0..R-1 ->
         # the ring.  A tile's first chunk does not toggle the buffers: reads start in buffer 0, transfers go to the other one.
-        assert Q_BUFS == 2   # (the xor toggle; a third buffer needs a rotation here and in gen_chunk)
+        # Four buffers: chunks 0..3 -> buffers 0..3 (M0 reaches LDS addresses >= 64 KiB: tools/probe/dma_high_probe.hip).  Later
+        # transfers go to buffers 0 and 1 only (gen_chunk).
+        assert Q_BUFS == 2 and QB in (2, 4)   # (the xor toggle of sldw; three buffers would need a rotation here and in gen_chunk)
         a("v_mov_b32 %[ldr], %[lane16]")
         a("s_add_u32 %[sldw], %[wave2k], 0x8000")
-        for c in range(Q_BUFS):
+        for c in range(QB):
             for _, _, const in dma_pieces():
                 a(f"s_add_u32 m0, %[wave2k], 0x{c * CHUNK_BYTES + const:x}")
                 a(f"s_mov_b32 %[st0], 0x{c * CHUNK_BYTES + const:x}")
@@ -870,16 +926,18 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     a("s_add_u32 s84, s80, %[st0]")
     a("s_addc_u32 s85, s81, %[cnt]")
     if ZZ:   # this tile's direction; the first chunk it stages (at its second position) is chunk 2, or nkc - 3 on the way down
+        #      (four buffers: chunk 4, or nkc - 5, at its fourth position)
         a(f"s_sub_u32 {QSTEP}, 0, {QSTEP}")
-        a("s_sub_u32 %[st0], %[qbytes], 0x18000")
+        a(f"s_sub_u32 %[st0], %[qbytes], 0x{(QB + 1) * CHUNK_BYTES:x}")
         a(f"s_cmp_gt_i32 {QSTEP}, 0")
-        a("s_cselect_b32 %[qcur], 0x10000, %[st0]")
+        a(f"s_cselect_b32 %[qcur], 0x{QB * CHUNK_BYTES:x}, %[st0]")
     else:
         a("s_mov_b32 %[qcur], %[qc1]")       # first chunk staged inside this tile's loop
         a(f"s_movk_i32 %[xso0], 0x{R * 1024:x}")
         a("s_add_u32 %[xso1], %[pb], %[xso0]")
-    a("s_cmp_eq_u32 %[nb], 1")
-    a("s_cbranch_scc1 .Lsingle_%=")
+    if QB != 4:   # (four buffers: a tile is three bodies, nb = 3)
+        a("s_cmp_eq_u32 %[nb], 1")
+        a("s_cbranch_scc1 .Lsingle_%=")
     out += body_lines(R, True, False, 0)
     a("s_sub_u32 %[cnt], %[nb], 2")
     a(".Lloop_%=:")
@@ -890,9 +948,10 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     a("s_branch .Lloop_%=")
     a(".Llast_%=:")
     out += body_lines(R, False, True, 200)
-    a("s_branch .Ladmit_%=")
-    a(".Lsingle_%=:")
-    out += body_lines(R, True, True, 300)
+    if QB != 4:
+        a("s_branch .Ladmit_%=")
+        a(".Lsingle_%=:")
+        out += body_lines(R, True, True, 300)
     a(".Ladmit_%=:")
     if i8:
         a("s_setprio 0")   # (the pre-tests ran inside the last k-step: gen_pretest; .Lback<n> live there)
@@ -913,9 +972,13 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     # filter_scan_asm_kernel (the workgroup's own scatter); the assembly only has to make sure everything it issued has
     # landed: ring / Q sets still in flight that nobody consumes, staged entries.  The entry count leaves through wcnt.
     a("s_waitcnt vmcnt(0) lgkmcnt(0)")
+    if QB == 4 and Q4_SPARSE_BARRIERS:
+        # The C++ tail reuses the Q buffers; no barrier follows a tile's last chunk position here.  Every wave of the
+        # workgroup runs the same number of tiles, so all of them arrive.
+        a("s_barrier")
     a("s_branch .Ldone_%=")
     if i8:   # one set per copy of the tile's last body (.Llast / .Lsingle): a stub returns into its copy
-        out += gen_hit_stubs("c200") + gen_hit_stubs("c300")
+        out += gen_hit_stubs("c200") + (gen_hit_stubs("c300") if QB != 4 else [])
     else:
         out += gen_hit_stubs()
     out += gen_slow_fast() if i8 else gen_slow()
@@ -971,7 +1034,8 @@ def generate(space, R, i8=False, nqt=16, l2c=False):
     text = ["// GENERATED by tools/gen_scan_asm.py -- do not edit.",
             f"// filter scan body: space {space}, NW={NW} waves x {16 * MT} rows, ring R={R} k-steps, B fragments read {QD} ahead"
             f", X loads non-temporal{', progress-based wave priority' if i8 else ''}, Q staged by LDS-DMA{', k-chunks zig-zag' if ZZ else ''}"
-            f"{', int8 shadow (v_mfma_i32_16x16x64_i8)' if i8 else ''}{', accumulators in ArchVGPRs' if i8 else ''}.",
+            f"{', int8 shadow (v_mfma_i32_16x16x64_i8)' if i8 else ''}{', accumulators in ArchVGPRs' if i8 else ''}"
+            f"{f', {QB} Q buffers ({Q4_NKC} chunks)' if QB != 2 else ''}.",
             "asm volatile("]
     for ln in out:
         text.append(f'    "{ln}\\n\\t"')
@@ -988,10 +1052,15 @@ def default_i8_body(space):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# What gets generated: (file name, dispatch condition on filter_scan_asm_kernel's template arguments <SPACE, R, I8, NQT>,
+# What gets generated: (file name, dispatch condition on filter_scan_asm_kernel's template arguments <SPACE, R, I8, NQT, QB>,
 # thunk that returns the text)
-def cond(space, r, i8, nqt):
-    return f"SPACE == {SPACES[space]} && R == {r} && {'I8' if i8 else '!I8'} && NQT == {nqt}"
+def cond(space, r, i8, nqt, qb=2):
+    return f"SPACE == {SPACES[space]} && R == {r} && {'I8' if i8 else '!I8'} && NQT == {nqt} && QB == {qb}"
+
+
+def q4_body(space):
+    """The four-buffer int8 body of a full pass in `space` (an image of Q4_NKC chunks)."""
+    return generate(space, 4, i8=True, nqt=16, l2c=space == "l2", qbufs=4)
 
 
 def entries():
@@ -1001,6 +1070,9 @@ def entries():
             name = (f"scan_asm_l2_i8_va_c_nqt{nqt}.inc" if sp == "l2" else
                     f"scan_asm_{sp}_i8_va{'' if nqt == 16 else f'_nqt{nqt}'}.inc")
             E.append((name, cond(sp, 4, True, nqt), lambda sp=sp, nqt=nqt: generate(sp, 4, True, nqt, sp == "l2")))
+    for sp in SPACES:   # the four-buffer int8 bodies: full passes over an image of Q4_NKC chunks (k <= 64 kNN passes)
+        name = "scan_asm_l2_i8_va_c_nqt16_q4.inc" if sp == "l2" else f"scan_asm_{sp}_i8_va_q4.inc"
+        E.append((name, cond(sp, 4, True, 16, 4), lambda sp=sp: q4_body(sp)))
     for sp in SPACES:   # bf16 bodies of an index that keeps a bf16 shadow: ring of 4 k-steps (2: odd chunk counts)
         for r in (4, 2):
             E.append((f"scan_asm_{sp}_nw8_r{r}_nt_dma.inc", cond(sp, r, False, 16), lambda sp=sp, r=r: generate(sp, r)))
@@ -1020,7 +1092,7 @@ def main():
     out = Path(args.outdir)
     for name, _, thunk in E:
         (out / name).write_text(thunk())
-    disp = ["// GENERATED by tools/gen_scan_asm.py -- do not edit.  Body of filter_scan_asm_kernel<SPACE, R, I8, NQT>."]
+    disp = ["// GENERATED by tools/gen_scan_asm.py -- do not edit.  Body of filter_scan_asm_kernel<SPACE, R, I8, NQT, QB>."]
     for i, (name, c, _) in enumerate(E):
         disp.append(("if" if i == 0 else "} else if") + f" constexpr ({c}) {{")
         disp.append(f'#include "{name}"')
@@ -1032,7 +1104,9 @@ def main():
         "// GENERATED by tools/gen_scan_asm.py -- do not edit.\n"
         f"constexpr int kAsmWgCap = {WG_CAP};\n"
         f"constexpr int kAsmQBufs = {Q_BUFS};  // Q chunk buffers in LDS\n"
-        f"constexpr int kAsmStageCap = {lds_stage_cap()};  // entries per wave staged in LDS\n")
+        f"constexpr int kAsmStageCap = {lds_stage_cap()};  // entries per wave staged in LDS\n"
+        f"constexpr int kAsmQ4Chunks = {Q4_NKC};  // the four-buffer bodies: the image's chunk count they are written for\n"
+        f"constexpr int kAsmQ4StageCap = {lds_stage_cap(4)};  // ... and their staging area, entries per wave\n")
     print("wrote", len(names), "files to", args.outdir)
 
 
