@@ -148,6 +148,16 @@ MMR_SIGNATURES = {
                                          _P, _P, _P, _P, _P, _P]),
 }
 
+# include/mlvdb_mutate.h: attribute values set by label, rows updated / tombstoned by filter
+SET_ASSIGN = 0
+SET_ADD = 1
+ASSIGN_DTYPE = [("attr", "<i4"), ("op", "<i4"), ("a", "<i8")]  # mlvdb_assign
+MUTATE_SIGNATURES = {
+    "mlvdb_attr_set_at": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    "mlvdb_attr_update_where": (C.c_int, [_P, C.POINTER(Where), _P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mlvdb_tombstone_where": (C.c_int, [_P, C.POINTER(Where), _P, C.c_int64, C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -178,7 +188,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
-                                      **ORDER_SIGNATURES, **MMR_SIGNATURES}.items():
+                                      **ORDER_SIGNATURES, **MMR_SIGNATURES, **MUTATE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -130,6 +130,8 @@ struct mlvdb_index {
     // ordered queries (mlvdb_order.h): the call's state, one histogram per digit pass, the collected (key, label) pairs and the
     // ranked window -- sized by MLVDB_ORDER_MAX_ROWS and the histograms, never by the corpus
     DevBuf order_ws;
+    // attribute updates (mlvdb_mutate.h): a call's assignments and counters, or the labels and values of a scatter
+    DevBuf mutate_ws;
     // fp16 row-major shadow for the mid bounds (kernels_refine.hip): built lazily by the first range query / top_k > 64 search
     DevBuf x16, s16, rowerr16, picks, npicks;
     int64_t l2_rows = 0;      // rows [0, l2_rows) of the fp16 shadow are current (0 after compact / reset / regrowth)
@@ -1181,7 +1183,7 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
                       &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel,
                       &h->grp_tab, &h->grp_tiles, &h->grp_out, &h->grp_lab,
-                      &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->facet_tab, &h->facet_misc, &h->order_ws})
+                      &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->facet_tab, &h->facet_misc, &h->order_ws, &h->mutate_ws})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
@@ -3444,6 +3446,157 @@ int mlvdb_where_ordered(mlvdb_index* h, int32_t attr, int32_t descending, const 
     *n_out = *matched = *absent = 0;
     if (h->total == 0) return MLVDB_OK;
     return where_ordered_impl(h, attr, descending != 0, where, offset, limit, out_labels, out_values, n_out, matched, absent);
+    });
+}
+
+// ---- attribute updates and filtered deletes (mlvdb_mutate.h)
+extern "C++" {
+namespace {
+int attr_set_at_impl(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const void* values, int64_t* updated) {
+    hipStream_t s = h->stream;
+    // [counter | labels | values]
+    const size_t lbytes = (size_t)n * sizeof(int64_t);
+    HIP_TRY(h, h->mutate_ws.ensure(64 + 2 * lbytes));
+    unsigned long long* cnt = h->mutate_ws.as<unsigned long long>();
+    int64_t* labels_d = reinterpret_cast<int64_t*>(h->mutate_ws.as<char>() + 64);
+    int64_t* values_d = labels_d + n;
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), s));
+    HIP_TRY(h, hipMemcpyAsync(labels_d, labels, lbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(values_d, values, lbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_attr_scatter(h->attr_col[attr], labels_d, values_d, n, h->rn, cnt, s));
+    unsigned long long wrote = 0;
+    HIP_TRY(h, hipMemcpyAsync(&wrote, cnt, sizeof wrote, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *updated = (int64_t)wrote;
+    return MLVDB_OK;
+}
+
+// The assignments of a call, checked (1..MLVDB_MAX_ATTRS of them, defined attributes, each at most once, known ops, no NaN
+// added) and resolved to their columns; *any_add: a counting pass must come first.
+int update_sets_prepare(mlvdb_index* h, const mlvdb_assign* sets, int32_t n_sets, MutateSet (&out)[MLVDB_MAX_ATTRS], bool* any_add) {
+    if (n_sets < 1 || n_sets > MLVDB_MAX_ATTRS || !sets) return fail(h, MLVDB_ERR_INVALID_ARG, "a call holds 1..MLVDB_MAX_ATTRS assignments");
+    bool seen[MLVDB_MAX_ATTRS] = {};
+    *any_add = false;
+    for (int32_t j = 0; j < n_sets; ++j) {
+        const mlvdb_assign& a = sets[j];
+        if (int rc = attr_check(h, a.attr)) return rc;
+        if (seen[a.attr]) return fail(h, MLVDB_ERR_INVALID_ARG, "an attribute is assigned twice");
+        seen[a.attr] = true;
+        if (a.op != MLVDB_SET_ASSIGN && a.op != MLVDB_SET_ADD) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown assignment op");
+        if (a.op == MLVDB_SET_ADD) {
+            *any_add = true;
+            if (h->attr_type[a.attr] == MLVDB_ATTR_FLOAT64) {
+                double d;
+                std::memcpy(&d, &a.a, sizeof d);
+                if (d != d) return fail(h, MLVDB_ERR_INVALID_ARG, "ADD of NaN");
+            }
+        }
+        out[j] = MutateSet{h->attr_col[a.attr], a.a, h->attr_type[a.attr], a.op};
+    }
+    return MLVDB_OK;
+}
+
+int attr_update_where_impl(mlvdb_index* h, const mlvdb_where* where, const MutateSet* sets, int32_t n_sets, bool any_add,
+                           int64_t* matched, int64_t* refused) {
+    hipStream_t s = h->stream;
+    const int64_t* set_d = nullptr;
+    if (int rc = where_upload(h, where, &set_d)) return rc;
+    // [matched, refused of the counting pass | the same of the storing pass | assignments]
+    HIP_TRY(h, h->mutate_ws.ensure(64 + sizeof(MutateSet) * MLVDB_MAX_ATTRS));
+    unsigned long long* cnt = h->mutate_ws.as<unsigned long long>();
+    MutateSet* sets_d = reinterpret_cast<MutateSet*>(h->mutate_ws.as<char>() + 64);
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, 64, s));
+    HIP_TRY(h, hipMemcpyAsync(sets_d, sets, sizeof(MutateSet) * (size_t)n_sets, hipMemcpyHostToDevice, s));
+    const WhereOp* prog = h->where_prog.as<WhereOp>();
+    unsigned long long host[2] = {0, 0};
+    if (any_add) {  // all or nothing: count the rows whose sums cannot be stored before anything is
+        HIP_TRY(h, launch_attr_update(prog, where->n_ops, set_d, sets_d, n_sets, h->rn, h->total, false, cnt, s));
+        HIP_TRY(h, hipMemcpyAsync(host, cnt, sizeof host, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        *matched = (int64_t)host[0];
+        *refused = (int64_t)host[1];
+        if (host[1] != 0 || host[0] == 0) return MLVDB_OK;
+    }
+    HIP_TRY(h, launch_attr_update(prog, where->n_ops, set_d, sets_d, n_sets, h->rn, h->total, true, cnt + 2, s));
+    HIP_TRY(h, hipMemcpyAsync(host, cnt + 2, sizeof host, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    if (any_add && ((int64_t)host[0] != *matched || host[1] != 0))
+        return fail(h, MLVDB_ERR_INTERNAL, "attr_update_where: the counting pass and the storing pass disagree");
+    *matched = (int64_t)host[0];
+    return MLVDB_OK;
+}
+
+int tombstone_where_impl(mlvdb_index* h, const mlvdb_where* where, int64_t* out_labels, int64_t capacity, int64_t* matches) {
+    if (int rc = where_run(h, where, matches)) return rc;  // the mask, and its count
+    const bool want_labels = capacity >= 0;
+    if (*matches == 0 || (want_labels && capacity < *matches)) return MLVDB_OK;
+    hipStream_t s = h->stream;
+    std::vector<int32_t> host;
+    if (want_labels) {  // before the norms change: the compaction map of the masked norms, as mlvdb_where_labels lists them
+        const int64_t nblocks = (h->total + 1023) / 1024;
+        HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
+        HIP_TRY(h, h->partial.ensure((size_t)nblocks * sizeof(uint32_t) + 64));
+        HIP_TRY(h, h->labels_in.ensure((size_t)*matches * sizeof(int32_t)));
+        HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, s));
+        HIP_TRY(h, launch_compact_map(h->rn_masked.as<float>(), h->total, h->partial.as<uint32_t>(),
+                                      h->where_cnt.as<unsigned long long>(), h->labels_in.as<int32_t>(), s));
+        host.resize((size_t)*matches);
+        HIP_TRY(h, hipMemcpyAsync(host.data(), h->labels_in.p, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    const bool shadow = h->rp8.p && h->i8_rows > 0;  // the int8 shadow's row constants carry the tombstones too
+    HIP_TRY(h, launch_tombstone_mask(h->row_mask.as<uint8_t>(), h->rn, shadow ? h->rp8.as<float>() : nullptr, h->i8_rows,
+                                     h->space == kSpaceL2 ? 1 : 0, h->total, s));
+    if (shadow)
+        if (int rc = forget_l2_offsets(h, 0, s)) return rc;  // (a dead row changes its lane group's P0)
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->deleted += *matches;
+    for (size_t i = 0; i < host.size(); ++i) out_labels[i] = host[i];
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_attr_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const void* values, int64_t* updated) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = attr_check(h, attr))) return rc;
+    if (!updated || n < 0 || (n > 0 && (!labels || !values))) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / values / n");
+    *updated = 0;
+    if (n == 0) return MLVDB_OK;
+    std::vector<int64_t> sorted(labels, labels + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label outside [0, total)");
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a label appears twice");
+    return attr_set_at_impl(h, attr, labels, n, values, updated);
+    });
+}
+
+int mlvdb_attr_update_where(mlvdb_index* h, const mlvdb_where* where, const mlvdb_assign* sets, int32_t n_sets,
+                            int64_t* matched, int64_t* refused) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!matched || !refused) return fail(h, MLVDB_ERR_INVALID_ARG, "null counter");
+    MutateSet resolved[MLVDB_MAX_ATTRS];
+    bool any_add = false;
+    if ((rc = update_sets_prepare(h, sets, n_sets, resolved, &any_add))) return rc;
+    if ((rc = where_prepare(h, where))) return rc;
+    *matched = *refused = 0;
+    if (h->total == 0) return MLVDB_OK;
+    return attr_update_where_impl(h, where, resolved, n_sets, any_add, matched, refused);
+    });
+}
+
+int mlvdb_tombstone_where(mlvdb_index* h, const mlvdb_where* where, int64_t* out_labels, int64_t capacity, int64_t* matches) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // labels into out_labels[capacity], or no labels at all (NULL with a negative capacity)
+    if (!matches || (out_labels ? capacity < 0 : capacity > 0)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
+    return tombstone_where_impl(h, where, out_labels, capacity, matches);
     });
 }
 

@@ -16,6 +16,7 @@
 #include "../../include/mlvdb_facet.h"
 #include "../../include/mlvdb_order.h"
 #include "../../include/mlvdb_mmr.h"
+#include "../../include/mlvdb_mutate.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -323,6 +324,26 @@ hipError_t launch_where_eval(const WhereOp* prog, int32_t n_ops, const int64_t* 
                              uint8_t* mask, unsigned long long* matches, hipStream_t s);
 hipError_t launch_attr_fill(int64_t* col, int64_t value, int64_t first, int64_t n, hipStream_t s);
 hipError_t launch_attr_gather(const int64_t* col, int64_t* ncol, const int32_t* old_of_new, int64_t live, hipStream_t s);
+
+// ---------------------------------------------------------------- attribute updates, filtered deletes (kernels_mutate.hip)
+// One assignment of a validated mlvdb_attr_update_where call as the device reads it (the column resolved on the host)
+struct MutateSet {
+    int64_t* col;
+    int64_t a;
+    int32_t type;  // MLVDB_ATTR_* of the column
+    int32_t op;    // MLVDB_SET_*
+};
+// col[labels[j]] = values[j] for the live rows among n distinct labels in [0, total) (all three on the device);
+// *updated += rows written
+hipError_t launch_attr_scatter(int64_t* col, const int64_t* labels, const int64_t* values, int64_t n, const float* rn,
+                               unsigned long long* updated, hipStream_t s);
+// counters[0] += live rows the program matches, counters[1] += those of them for which an ADD of `sets` cannot be stored;
+// store: every storable value of those rows is written (all of them, when the counting pass before found counters[1] == 0)
+hipError_t launch_attr_update(const WhereOp* prog, int32_t n_ops, const int64_t* set, const MutateSet* sets, int32_t n_sets,
+                              const float* rn, int64_t total, bool store, unsigned long long* counters, hipStream_t s);
+// rn[i] = NaN for the rows of mask, and their int8 row pairs (i < i8_rows; rp8 may be null) as tombstone_rp8_kernel does
+hipError_t launch_tombstone_mask(const uint8_t* mask, float* rn, float* rp8, int64_t i8_rows, int l2, int64_t total,
+                                 hipStream_t s);
 
 // ---------------------------------------------------------------- per-query filters (kernels_where_each.hip)
 constexpr int kWhereEachMaxPrograms = MLVDB_WHERE_EACH_MAX_PROGRAMS;

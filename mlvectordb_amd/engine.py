@@ -267,6 +267,44 @@ class HipScanEngine:
         self._check(self._lib.mlvdb_where_labels(self._h, C.byref(w), out.ctypes.data, out.size, C.byref(n)), "where_labels")
         return out[: n.value]
 
+    # -- attribute updates and filtered deletes (include/mlvdb_mutate.h) ----------------
+    def set_attr_at(self, attr: int, labels: np.ndarray, values: np.ndarray) -> int:
+        """``values[j]`` -> row ``labels[j]`` of column ``attr`` (distinct labels in [0, total); tombstoned rows are
+        skipped); returns the rows written.  The sentinels clear a value, as in ``set_attr``."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        values = np.ascontiguousarray(values).ravel()
+        if values.dtype not in (np.int64, np.float64):
+            raise RuntimeError(f"attribute values must be int64 or float64, got {values.dtype}")
+        if values.size != labels.size:
+            raise RuntimeError(f"{labels.size} labels but {values.size} values")
+        n = C.c_int64(0)
+        self._check(self._lib.mlvdb_attr_set_at(self._h, int(attr), labels.ctypes.data, labels.size, values.ctypes.data,
+                                                C.byref(n)), "attr_set_at")
+        return int(n.value)
+
+    def update_where(self, program, assigns) -> Tuple[int, int]:
+        """Apply ``assigns`` -- (attr, op, a) triples, op ``_native.SET_ASSIGN`` / ``SET_ADD``, ``a`` the int64 the column
+        takes (float64 column: the bits of the double) -- to every live row the compiled filter matches, all or nothing:
+        (matched, refused), and nothing changed when ``refused`` (rows whose sum cannot be stored) is not 0."""
+        w, keep = self._where(program)
+        sets = np.array([(int(attr), int(op), int(a)) for attr, op, a in assigns], dtype=_native.ASSIGN_DTYPE)
+        matched, refused = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.mlvdb_attr_update_where(self._h, C.byref(w), sets.ctypes.data, int(sets.size),
+                                                      C.byref(matched), C.byref(refused)), "attr_update_where")
+        return int(matched.value), int(refused.value)
+
+    def tombstone_where(self, program) -> np.ndarray:
+        """Tombstone every live row the compiled filter matches; their labels, ascending."""
+        w, keep = self._where(program)
+        total, deleted = self.counts()
+        out = np.empty(max(total - deleted, 1), dtype=np.int64)
+        n = C.c_int64(0)
+        self._check(self._lib.mlvdb_tombstone_where(self._h, C.byref(w), out.ctypes.data, out.size, C.byref(n)),
+                    "tombstone_where")
+        if n.value > out.size:  # (cannot happen: the buffer holds every live row)
+            raise RuntimeError(f"tombstone_where: {n.value} matches for {out.size} live rows")
+        return out[: n.value]
+
     # -- per-query filters (include/mlvdb_where_each.h) -------------------------------
     @staticmethod
     def _where_array(programs):

@@ -33,6 +33,7 @@ from uuid import UUID
 
 import numpy as np
 
+from . import _native
 from . import where as _where
 from .engine import FacetOverflow, HipScanEngine, ScanEngine
 from .idtable import IdTable, mint_uuid4_bytes
@@ -785,6 +786,144 @@ class Index:
         if ns is None or ns.total == 0:
             return []
         return ns.ids.uuids_at(ns.engine.where_labels(program)).tolist()
+
+    # ------------------------------------------------------------------ additive: updates and deletes on the device
+    @staticmethod
+    def _mutator(ns: _Namespace, method: str, what: str):
+        fn = getattr(ns.engine, method, None)
+        if fn is None:
+            raise ValueError(f"{what} needs an engine with {method} (a single-device namespace)")
+        return fn
+
+    def check_attribute_patches(self, n_ids: int, values) -> List[Mapping]:
+        """The refusals of ``update_attributes`` that need no namespace -> one patch per id (``values`` is one mapping for
+        every id, or a sequence with one mapping per id; the keys are declared attributes)."""
+        if isinstance(values, Mapping):
+            patches = [values] * n_ids
+            distinct = [values]
+        else:
+            patches = distinct = list(values)
+            if len(patches) != n_ids:
+                raise ValueError(f"update_attributes: {n_ids} ids but {len(patches)} value mappings")
+        for p in distinct:
+            if not isinstance(p, Mapping):
+                raise ValueError(f"update_attributes: values must be mappings, got {type(p).__name__}")
+            for name in p:
+                if name not in self._attributes:
+                    raise ValueError(f"{name!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        return patches
+
+    def _stage_patches(self, namespace: str, patches: Sequence[Mapping]):
+        """Encode per-id patches -> ({column index: (positions in the id list, encoded values)}, the namespace's string
+        dictionaries with the new strings).  Raises ``ValueError`` before anything is mutated."""
+        ns = self._ns.get(namespace)
+        strings = {name: dict(codes) for name, codes in (ns.strings if ns is not None else {}).items()}
+        out = {}
+        for i, (name, kind) in enumerate(self._attributes.items()):
+            pos = [j for j, p in enumerate(patches) if name in p]
+            if not pos:
+                continue
+            col = _where.encode_column(name, kind, [patches[j][name] for j in pos],
+                                       strings.setdefault(name, {}) if kind == "str" else {})
+            out[i] = (np.asarray(pos, dtype=np.int64), col)
+        return out, strings
+
+    def validate_attribute_update(self, n_ids: int, values, namespace: str) -> None:
+        """Raises what ``update_attributes`` would raise for these values, without touching the index."""
+        self._stage_patches(namespace, self.check_attribute_patches(n_ids, values))
+
+    def update_attributes(self, ids: Sequence[UUID], values, namespace: str) -> int:
+        """Set attribute values of the rows ``ids`` in place (no new label, no tombstone): ``values`` is one mapping applied to
+        every id, or a sequence with one mapping per id.  Keys are declared attributes, values are typed as at ingest, ``None``
+        clears a value, a key that is missing leaves that attribute alone.  Unknown or removed ids are skipped, as ``remove``
+        skips them; for an id listed twice the entries apply in order, so the last one that names a key wins.  Returns the
+        number of rows that were given a value.  New strings reach the namespace's dictionary only when every engine call
+        succeeded."""
+        ids = list(ids)
+        staged, strings = self._stage_patches(namespace, self.check_attribute_patches(len(ids), values))
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total == 0 or not ids or not staged:
+            return 0
+        set_at = self._mutator(ns, "set_attr_at", "update_attributes")
+        labels = ns.ids.lookup(ids)
+        touched = []
+        for i, (pos, col) in staged.items():
+            lab = labels[pos]
+            keep = lab >= 0
+            lab, col = lab[keep], col[keep]
+            rows, last = np.unique(lab[::-1], return_index=True)  # the last entry of each row
+            if rows.size:
+                set_at(i, rows, col[lab.size - 1 - last])
+                touched.append(rows)
+        ns.strings = strings
+        return int(np.unique(np.concatenate(touched)).size) if touched else 0
+
+    def stage_assignments(self, namespace: str, values: Mapping):
+        """The refusals of ``update_where``'s ``values`` -> ([(column, op, a), ...] as the engine takes them, the namespace's
+        string dictionaries with the new strings).  A value is a literal (typed as at ingest), ``None`` (clear) or
+        ``{"$inc": x}`` on an ``int`` (``x`` an int) or ``float`` (``x`` an int or float, not NaN) attribute."""
+        if not isinstance(values, Mapping) or not values:
+            raise ValueError("update_where: values must be a non-empty mapping of declared attributes")
+        for name in values:
+            if name not in self._attributes:
+                raise ValueError(f"{name!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        ns = self._ns.get(namespace)
+        strings = {name: dict(codes) for name, codes in (ns.strings if ns is not None else {}).items()}
+        out = []
+        for i, (name, kind) in enumerate(self._attributes.items()):
+            if name not in values:
+                continue
+            v = values[name]
+            if isinstance(v, Mapping):
+                if list(v) != ["$inc"]:
+                    raise ValueError(f"update_where: {name!r}: the only operator is $inc (got {sorted(map(str, v))})")
+                x = v["$inc"]
+                if kind == "int" and isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)):
+                    if not -(2 ** 63) < int(x) < 2 ** 63:
+                        raise ValueError(f"update_where: {name!r}: $inc {x!r} is outside int64")
+                    out.append((i, _native.SET_ADD, int(x)))
+                elif kind == "float" and isinstance(x, (int, float, np.integer, np.floating)) and \
+                        not isinstance(x, (bool, np.bool_)) and not np.isnan(float(x)):
+                    out.append((i, _native.SET_ADD, _where.float_bits(float(x))))
+                else:
+                    raise ValueError(f"update_where: {name!r} ({kind}): $inc takes an int on an int attribute, an int or a "
+                                     f"float that is not NaN on a float attribute (got {x!r})")
+                continue
+            col = _where.encode_column(name, kind, [v], strings.setdefault(name, {}) if kind == "str" else {})
+            out.append((i, _native.SET_ASSIGN, int(col.view(np.int64)[0])))
+        return out, strings
+
+    def update_where(self, namespace: str, where: Mapping, values: Mapping) -> int:
+        """Set attribute values of every live row the dict filter ``where`` matches, in one pass on the device
+        (include/mlvdb_mutate.h): ``values`` maps a declared attribute to a literal, to ``None`` (clear) or to ``{"$inc": x}``
+        (rows without a value keep none).  The filter sees the values from before the call.  Returns the matched count.  All
+        or nothing: when an increment would overflow on some row, ``ValueError`` says on how many and nothing has changed."""
+        program = self._compile(namespace, where)
+        assigns, strings = self.stage_assignments(namespace, values)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total == 0:
+            return 0
+        matched, refused = self._mutator(ns, "update_where", "update_where")(program, assigns)
+        if refused:
+            raise ValueError(f"update_where: $inc would overflow on {refused} of the {matched} matching rows; nothing was changed")
+        ns.strings = strings
+        return matched
+
+    def remove_where(self, namespace: str, where: Mapping, *, return_ids: bool = False):
+        """``remove`` of every live row the dict filter ``where`` matches, tombstoned on the device without listing them on
+        the host first.  Returns their count, or their UUIDs (insertion order) with ``return_ids=True``."""
+        program = self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total == 0:
+            return [] if return_ids else 0
+        labels = self._mutator(ns, "tombstone_where", "remove_where")(program)
+        ids = ns.ids.uuids_at(labels).tolist() if return_ids else None
+        if labels.size:
+            ns.ids.kill(labels)
+        ns.deleted += int(labels.size)
+        if ns.deleted / max(1, ns.total) >= self._rebuild_threshold:
+            ns.rebuild_required = True
+        return ids if return_ids else int(labels.size)
 
     # ------------------------------------------------------------------ additive: ordered metadata queries on the device
     _MAX_ORDER_ROWS = 4096  # MLVDB_ORDER_MAX_ROWS

@@ -32,7 +32,7 @@ class QueryProcessor:
         self._index = index
         self._rebuild_scope = rebuild_scope
 
-    # ---- writes (query_processor.py:16-24): every call mints new ids, nothing is updated in place
+    # ---- writes (query_processor.py:16-24): every call mints new ids; update_metadata / update_where change metadata in place
     def insert(self, vector: VectorDTO, namespace: str = "default") -> None:
         row = Vector(values=vector.values, metadata=vector.metadata)
         self._storage.write(row, namespace)
@@ -317,11 +317,15 @@ class QueryProcessor:
     def delete(self, ids: Sequence[UUID], namespace: str = "default") -> Sequence[UUID]:
         removed = [vid for vid in ids if self._storage.delete(vid, namespace)]
         self._index.remove(ids, namespace)
+        self._rebuild_if_required(namespace)
+        return removed
+
+    def _rebuild_if_required(self, namespace: str) -> None:
         probe = getattr(self._index, "is_rebuild_required", None)
         if probe and probe(namespace):
             compact = getattr(self._index, "compact", None)
             if compact and self._rebuild_scope != "namespace" and compact(namespace):
-                return removed  # same end state as the rebuild below, computed on the device
+                return  # same end state as the rebuild below, computed on the device
             full = self._storage.namespace_map
             if self._rebuild_scope == "namespace":
                 source = {namespace: full.get(namespace, [])}
@@ -329,6 +333,83 @@ class QueryProcessor:
                 source = dict(full)
                 source.setdefault(namespace, [])
             self._index.rebuild(self._with_values(source), metric=self._index._space)
+
+    # ---- additive: metadata updates and deletes by filter (Index.update_attributes / update_where / remove_where)
+    def _declared(self, patch: Mapping) -> dict:
+        declared = getattr(self._index, "attributes", None) or {}
+        return {k: v for k, v in patch.items() if k in declared}
+
+    def update_metadata(self, ids: Sequence[UUID], metadata, namespace: str = "default") -> List[UUID]:
+        """Overlay the stored metadata of ``ids`` with ``metadata`` -- one mapping for every id, or a sequence with one per
+        id; ``None`` deletes a key -- and set the index's declared attributes among its keys in place
+        (``Index.update_attributes``): no new id, no re-sent vector.  The index's refusals come before anything is written.
+        Returns the ids the storage holds."""
+        ids = list(ids)
+        patches = [metadata] * len(ids) if isinstance(metadata, Mapping) else list(metadata)
+        if len(patches) != len(ids) or not all(isinstance(p, Mapping) for p in patches):
+            raise ValueError(f"update_metadata: one mapping, or one mapping per id ({len(ids)} ids)")
+        declared = [self._declared(p) for p in patches]
+        indexed = any(declared) and hasattr(self._index, "update_attributes")
+        if indexed:
+            self._index.validate_attribute_update(len(ids), declared, namespace)
+        updated = [vid for vid, p in zip(ids, patches) if self._storage.update_metadata(vid, p, namespace)]
+        if indexed:
+            self._index.update_attributes(ids, declared, namespace)
+        return updated
+
+    @staticmethod
+    def _increment(value) -> bool:
+        return isinstance(value, Mapping) and list(value) == ["$inc"]
+
+    def _row_patch(self, stored: Mapping, metadata: Mapping) -> dict:
+        """``metadata`` for one stored row: every ``{"$inc": x}`` becomes the row's new value, or is left out when the row
+        holds no value to add to."""
+        out = {}
+        for key, value in metadata.items():
+            if not self._increment(value):
+                out[key] = value
+                continue
+            old = None if stored is None else stored.get(key)
+            if old is not None:
+                out[key] = old + value["$inc"]
+        return out
+
+    def update_where(self, where, metadata: Mapping, namespace: str = "default") -> int:
+        """``update_metadata`` of every vector matching ``where``; a value may be ``{"$inc": x}``, which adds to the rows
+        that hold a value and skips the others.  A dict filter updates the declared attributes in one pass on the device
+        (``Index.update_where``, all or nothing: an increment that would overflow raises before anything is written); a
+        predicate is evaluated over the storage and goes through ``update_metadata``.  Returns the matched count."""
+        if not isinstance(metadata, Mapping) or not metadata:
+            raise ValueError("update_where: metadata must be a non-empty mapping")
+        if not isinstance(where, Mapping):
+            if not callable(where):
+                raise ValueError(f"update_where: where must be a dict filter or a predicate (got {type(where).__name__})")
+            rows = [v for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
+            self.update_metadata([v.id for v in rows], [self._row_patch(v.metadata, metadata) for v in rows], namespace)
+            return len(rows)
+        declared = self._declared(metadata)
+        if declared:
+            self._index.stage_assignments(namespace, declared)  # the refusals, before anything is resolved or written
+        ids = self._index.query_by_metadata(namespace, where)
+        if declared:  # first: the only step that can still refuse (an overflowing increment), and then nothing has changed
+            self._index.update_where(namespace, where, declared)
+        stored = self._storage.read_vectors(ids, namespace)
+        for vid, row in zip(ids, stored):
+            if row is not None:
+                self._storage.update_metadata(vid, self._row_patch(row.metadata, metadata), namespace)
+        return len(ids)
+
+    def delete_where(self, where, namespace: str = "default") -> List[UUID]:
+        """``delete`` of every vector matching ``where``: a dict filter is tombstoned on the device
+        (``Index.remove_where``), a predicate is evaluated over the storage.  Returns the ids removed from the storage."""
+        if not isinstance(where, Mapping):
+            if not callable(where):
+                raise ValueError(f"delete_where: where must be a dict filter or a predicate (got {type(where).__name__})")
+            return list(self.delete([v.id for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)],
+                                    namespace))
+        ids = self._index.remove_where(namespace, where, return_ids=True)
+        removed = [vid for vid in ids if self._storage.delete(vid, namespace)]
+        self._rebuild_if_required(namespace)
         return removed
 
     def _with_values(self, source):

@@ -52,6 +52,16 @@ class InMemoryStorage:
             del self._rows[namespace]
         return True
 
+    def update_metadata(self, vector_id: UUID, patch: Mapping[str, Any], namespace: str) -> bool:
+        """The row's metadata overlaid by ``patch`` (``None`` deletes a key), as a new dict on a new row object: a dict or a
+        row another holder shares is never mutated.  False when the id is not stored."""
+        ns = self._rows.get(namespace)
+        row = None if ns is None else ns.get(vector_id)
+        if row is None:
+            return False
+        ns[vector_id] = StoredRow(row.id, row.values, patched_metadata(row.metadata, patch))
+        return True
+
     @property
     def namespace_map(self) -> Mapping[str, List[VectorProtocol]]:
         return {name: list(ns.values()) for name, ns in self._rows.items()}
@@ -67,6 +77,17 @@ class InMemoryStorage:
                 "storage_size_bytes": sum(np.asarray(v.values).nbytes for ns in self._rows.values() for v in ns.values()),
                 "namespaces": list(self._rows), "vectors_per_namespace": {n: len(r) for n, r in self._rows.items()},
                 "namespace_count": len(self._rows)}
+
+
+def patched_metadata(old: Optional[Mapping[str, Any]], patch: Mapping[str, Any]) -> Dict[str, Any]:
+    """A new dict: ``old`` overlaid by ``patch``, the keys ``patch`` maps to ``None`` dropped."""
+    new = dict(old or {})
+    for key, value in patch.items():
+        if value is None:
+            new.pop(key, None)
+        else:
+            new[key] = value
+    return new
 
 
 class StoredRow:
@@ -114,6 +135,13 @@ class _MetaColumn:
         c = int(np.searchsorted(self.starts, r, side="right")) - 1
         chunk = self.chunks[c]
         return _EMPTY if chunk is None else chunk[r - self.starts[c]]
+
+    def __setitem__(self, r: int, metadata) -> None:
+        c = int(np.searchsorted(self.starts, r, side="right")) - 1
+        if self.chunks[c] is None:  # a chunk written without metadata: materialised, every row the shared empty dict
+            self.chunks[c] = [_EMPTY] * (self.starts[c + 1] - self.starts[c])
+            self.any = True
+        self.chunks[c][r - self.starts[c]] = metadata
 
     def take(self, rows) -> List[Any]:
         """Metadata of ``rows`` (a list of row numbers, -1 = not found -> None)."""
@@ -235,6 +263,17 @@ class ArrayStorage:
         if row < 0:
             return False
         ns.ids.kill([row])
+        return True
+
+    def update_metadata(self, vector_id: UUID, patch: Mapping[str, Any], namespace: str) -> bool:
+        """As ``InMemoryStorage.update_metadata``: the row's entry becomes a new dict, whatever other rows share the old one."""
+        ns = self._ns.get(namespace)
+        if ns is None:
+            return False
+        row = int(ns.ids.lookup([vector_id])[0])
+        if row < 0:
+            return False
+        ns.metadata[row] = patched_metadata(ns.metadata[row], patch)
         return True
 
     @property
