@@ -68,6 +68,35 @@ struct PinBuf {
     }
 };
 
+// A bump carver over one block of several arrays, a DevBuf's or its copy on the host: take<T>(n) is the next n values of T.
+// It pads nothing.  Every layout carved with it lists its 8-byte fields (double, int64) before its 4-byte ones (float,
+// int32) -- descending alignment -- so every field lies aligned whatever the counts are.
+struct Carver {
+    char* at;
+    template <class T>
+    T* take(size_t n) {
+        T* first = reinterpret_cast<T*>(at);
+        at += n * sizeof(T);
+        return first;
+    }
+};
+
+// The layout most blocks have, [d64 | labels | dist | counts]: n entries and nq counts.
+struct ListBlock {
+    double* d64;
+    int64_t* lab;
+    float* dist;
+    int32_t* cnt;
+    static size_t bytes(size_t n, size_t nq) { return n * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + nq * sizeof(int32_t); }
+    ListBlock(void* block, size_t n, size_t nq) {
+        Carver c{static_cast<char*>(block)};
+        d64 = c.take<double>(n);
+        lab = c.take<int64_t>(n);
+        dist = c.take<float>(n);
+        cnt = c.take<int32_t>(nq);
+    }
+};
+
 }  // namespace
 
 struct mlvdb_index {
@@ -2228,8 +2257,38 @@ int mlvdb_range_batch_packed_where(mlvdb_index* h, const float* queries, int64_t
 
 extern "C++" {
 namespace {
+// The tail of an entry that takes an optional program, everything else checked: no program -> the call; else the program
+// into h->row_mask (where_run validates it before its first launch; the mask stays on the device: no wait, no copy) and
+// the call under that mask.
+template <class F>
+int with_where(mlvdb_index* h, const mlvdb_where* where, int64_t nq, F&& call) {
+    if (!where) return nq == 0 ? MLVDB_OK : call();
+    const int rc = where_run(h, where, nullptr);
+    if (rc || nq == 0) return rc;
+    if (h->total == 0) return call();
+    return with_row_mask(h, nq, call);
+}
+
+// Padding: n entries (label -1, distances inf; dist64 may be null) and nq zeroed counts.
+void pad_outputs(int64_t* labels, float* dist, double* dist64, int64_t n, int32_t* counts, int64_t nq) {
+    for (int64_t i = 0; i < n; ++i) {
+        labels[i] = -1;
+        dist[i] = __builtin_inff();
+        if (dist64) dist64[i] = __builtin_inf();
+    }
+    for (int64_t i = 0; i < nq; ++i) counts[i] = 0;
+}
+
 // ---- per-query filters (mlvdb_where_each.h)
-constexpr int32_t kGatherQT = 4;  // queries per tile of the gathered kernel (fewer only when the tile would not fit in LDS)
+constexpr int32_t kGatherQT = 4;  // queries per tile of the gathered kernels
+
+// ... fewer only when the tile would not fit in LDS; where even one query does not (where_gather_lds(1, ld) > 64 KiB),
+// nothing is gathered: the callers check.
+int32_t gather_qt(const mlvdb_index* h) {
+    int32_t qt = kGatherQT;
+    while (qt > 1 && where_gather_lds(qt, h->ld) > 64 * 1024) qt >>= 1;
+    return qt;
+}
 
 // The programs of a call validated (where_prepare, each against its own set table) and packed for the device: ops
 // concatenated (off[p] .. off[p + 1]), the IN ranges rebased onto one concatenated set table.
@@ -2351,72 +2410,143 @@ int search_rows(mlvdb_index* h, const float* queries, const std::vector<int32_t>
     return MLVDB_OK;
 }
 
-// The GATHER route for the programs `gp` (their queries in qof[p], matches[p] rows each): label lists, tiles, the gathered
-// kernel, exact_merge_kernel, outputs into the caller's rows.
+// The queries of a call by program: qof[p] = program p's, ascending; plain = the unfiltered ones (entry -1); any: some
+// program has a query.  Part of an entry's checks: nothing is launched before it.
+struct EachSplit {
+    std::vector<std::vector<int32_t>> qof;
+    std::vector<int32_t> plain;
+    bool any = false;
+};
+
+int where_each_split(mlvdb_index* h, const int32_t* program_of_query, int64_t nq, int32_t n_programs, EachSplit& out) {
+    out.qof.assign((size_t)n_programs, {});
+    for (int64_t i = 0; i < nq; ++i) {
+        const int32_t p = program_of_query[i];
+        if (p < -1 || p >= n_programs) return fail(h, MLVDB_ERR_INVALID_ARG, "program_of_query entry outside [-1, n_programs)");
+        (p < 0 ? out.plain : out.qof[(size_t)p]).push_back((int32_t)i);
+        out.any = out.any || p >= 0;
+    }
+    return MLVDB_OK;
+}
+
+// The route of every program (NONE: no query or no match) and the programs of the two others, ascending.  GATHER while the
+// gathered rows stay a small share of what the masked scan would read (matches x tiles x 1000 <= live x WHERE_GATHER), the
+// label lists of all gathered programs together stay below 2^31 entries, a tile fits in LDS and the caller allows it.
+struct EachRoutes {
+    std::vector<int32_t> routes, gp, sp;
+};
+
+EachRoutes where_each_routes(const mlvdb_index* h, const std::vector<std::vector<int32_t>>& qof,
+                             const std::vector<int64_t>& matches, int32_t qt, bool gather_allowed) {
+    EachRoutes r;
+    r.routes.assign(qof.size(), MLVDB_WHERE_ROUTE_NONE);
+    const bool gather_fits = gather_allowed && where_gather_lds(qt, h->ld) <= 64 * 1024;
+    const __int128 live = h->total - h->deleted;
+    int64_t nlab = 0;
+    for (size_t p = 0; p < qof.size(); ++p) {
+        const size_t nqp = qof[p].size();
+        if (nqp == 0 || matches[p] == 0) continue;
+        const __int128 tiles = (__int128)((nqp + qt - 1) / qt);
+        const bool gather = gather_fits && (__int128)matches[p] * tiles * 1000 <= live * h->tn.where_gather &&
+                            nlab + matches[p] <= INT32_MAX;
+        if (gather) nlab += matches[p];
+        r.routes[p] = gather ? MLVDB_WHERE_ROUTE_GATHER : MLVDB_WHERE_ROUTE_SCAN;
+        (gather ? r.gp : r.sp).push_back((int32_t)p);
+    }
+    return r;
+}
+
+// The SCAN route's row mask: program p's bit of h->each_bits, expanded into h->row_mask.
+int each_row_mask(mlvdb_index* h, int32_t p) {
+    HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
+    HIP_TRY(h, launch_where_each_expand(h->each_bits.as<unsigned long long>(), p, h->total, h->row_mask.as<uint8_t>(), h->stream));
+    return MLVDB_OK;
+}
+
+// What the gather stage leaves its caller: the gathered queries sorted by program (sel: their positions in the call,
+// prog_of_sel: their programs; the prepared batch h->each_qpad / each_qaux holds them in this order), the tiles (on the
+// device in h->each_tiles), the longest label list and the number of queries.  q and base are the host sides of copies the
+// stage enqueued: they live until the caller has synchronised.
+struct GatherStage {
+    std::vector<int32_t> sel, prog_of_sel;
+    std::vector<GatherTile> tiles;
+    int64_t max_m = 0;
+    int32_t ng = 0;
+    std::vector<float> q;
+    std::vector<int64_t> base;
+};
+
+// The head of the GATHER route for the programs `gp` (their queries in qof[p], matches[p] rows each), all enqueued: the
+// label lists (h->each_lab, one scatter pass over the bit words), the tiles of <= qt queries of one program -- none straddling
+// a multiple of `group` positions when group > 0 -- and the gathered queries, prepared as every exact path prepares them.
+int gather_stage(mlvdb_index* h, const float* queries, int32_t qt, size_t group, const EachSegs& sg, int32_t n_programs,
+                 const std::vector<int32_t>& gp, const std::vector<std::vector<int32_t>>& qof, const int64_t* matches,
+                 GatherStage& st) {
+    hipStream_t s = h->stream;
+    st.base.assign(kWhereEachMaxPrograms, 0);
+    unsigned long long gmask = 0;
+    int64_t nlab = 0;
+    for (int32_t p : gp) {
+        gmask |= 1ull << p;
+        st.base[p] = nlab;
+        const std::vector<int32_t>& qs = qof[p];
+        for (size_t t0 = 0; t0 < qs.size();) {
+            const size_t pos = st.sel.size() + t0;
+            GatherTile t;
+            t.lab_begin = (int32_t)nlab;
+            t.lab_count = (int32_t)matches[p];
+            t.sel0 = (int32_t)pos;
+            t.nsel = (int32_t)std::min<size_t>({(size_t)qt, qs.size() - t0, group ? group - pos % group : (size_t)qt});
+            st.tiles.push_back(t);
+            t0 += (size_t)t.nsel;
+        }
+        st.sel.insert(st.sel.end(), qs.begin(), qs.end());
+        st.prog_of_sel.insert(st.prog_of_sel.end(), qs.size(), p);
+        nlab += matches[p];
+        st.max_m = std::max(st.max_m, matches[p]);
+    }
+    st.ng = (int32_t)st.sel.size();
+    HIP_TRY(h, h->each_lab.ensure((size_t)nlab * sizeof(int32_t)));
+    int64_t* base_d = h->each_tot.as<int64_t>() + kWhereEachMaxPrograms;  // (each_tot: [totals | label bases])
+    HIP_TRY(h, hipMemcpyAsync(base_d, st.base.data(), st.base.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_where_each_scatter(h->each_bits.as<unsigned long long>(), h->total, sg.seg_rows, sg.nseg, n_programs,
+                                         h->each_seg.as<uint32_t>(), gmask, base_d, h->each_lab.as<int32_t>(), s));
+    st.q = pick_queries(queries, h->dim, st.sel);
+    HIP_TRY(h, h->each_q.ensure(st.q.size() * sizeof(float)));
+    HIP_TRY(h, h->each_qpad.ensure((size_t)st.ng * h->ld * sizeof(float)));
+    HIP_TRY(h, h->each_qaux.ensure((size_t)st.ng * sizeof(double)));
+    HIP_TRY(h, h->each_tiles.ensure(st.tiles.size() * sizeof(GatherTile)));
+    HIP_TRY(h, hipMemcpyAsync(h->each_q.p, st.q.data(), st.q.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(h->each_tiles.p, st.tiles.data(), st.tiles.size() * sizeof(GatherTile), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_query_prep(h->each_q.as<float>(), st.ng, h->dim, h->ld, h->space, h->each_qpad.as<float>(),
+                                 h->each_qaux.as<double>(), nullptr, s));
+    return MLVDB_OK;
+}
+
+// The GATHER route of a kNN call: the gather stage, the gathered kernel, exact_merge_kernel, outputs into the caller's rows.
 int gather_programs(mlvdb_index* h, const float* queries, int32_t k, int32_t qt, const EachSegs& sg, int32_t n_programs,
                     const std::vector<int32_t>& gp, const std::vector<std::vector<int32_t>>& qof, const int64_t* matches,
                     int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
     hipStream_t s = h->stream;
-    std::vector<int64_t> base(kWhereEachMaxPrograms, 0);
-    std::vector<int32_t> sel;  // the gathered queries, sorted by program (positions of the prepared batch)
-    std::vector<GatherTile> tiles;
-    unsigned long long gmask = 0;
-    int64_t nlab = 0, max_m = 0;
-    for (int32_t p : gp) {
-        gmask |= 1ull << p;
-        base[p] = nlab;
-        const std::vector<int32_t>& qs = qof[p];
-        for (size_t t0 = 0; t0 < qs.size(); t0 += qt) {
-            GatherTile t;
-            t.lab_begin = (int32_t)nlab;
-            t.lab_count = (int32_t)matches[p];
-            t.sel0 = (int32_t)sel.size() + (int32_t)t0;
-            t.nsel = (int32_t)std::min<size_t>(qt, qs.size() - t0);
-            tiles.push_back(t);
-        }
-        sel.insert(sel.end(), qs.begin(), qs.end());
-        nlab += matches[p];
-        max_m = std::max(max_m, matches[p]);
-    }
-    const int32_t ng = (int32_t)sel.size(), ntiles = (int32_t)tiles.size();
+    GatherStage st;
+    if (int rc = gather_stage(h, queries, qt, 0, sg, n_programs, gp, qof, matches, st)) return rc;
+    const int32_t ng = st.ng, ntiles = (int32_t)st.tiles.size();
     // chunks per tile: enough blocks to fill the chip (~2048), none shorter than 64 rows, at most 64 partial lists per query
-    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>({64, (2048 + ntiles - 1) / ntiles, (max_m + 63) / 64}));
-    // label lists: one scatter pass over the bit words
-    HIP_TRY(h, h->each_lab.ensure((size_t)nlab * sizeof(int32_t)));
-    HIP_TRY(h, hipMemcpyAsync(h->each_tot.as<int64_t>() + kWhereEachMaxPrograms, base.data(), base.size() * sizeof(int64_t),
-                              hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_where_each_scatter(h->each_bits.as<unsigned long long>(), h->total, sg.seg_rows, sg.nseg, n_programs,
-                                         h->each_seg.as<uint32_t>(), gmask, h->each_tot.as<int64_t>() + kWhereEachMaxPrograms,
-                                         h->each_lab.as<int32_t>(), s));
-    // the gathered queries, prepared as every exact path prepares them
-    const std::vector<float> q = pick_queries(queries, h->dim, sel);
-    HIP_TRY(h, h->each_q.ensure(q.size() * sizeof(float)));
-    HIP_TRY(h, h->each_qpad.ensure((size_t)ng * h->ld * sizeof(float)));
-    HIP_TRY(h, h->each_qaux.ensure((size_t)ng * sizeof(double)));
-    HIP_TRY(h, h->each_tiles.ensure(tiles.size() * sizeof(GatherTile)));
-    HIP_TRY(h, hipMemcpyAsync(h->each_q.p, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->each_tiles.p, tiles.data(), tiles.size() * sizeof(GatherTile), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_query_prep(h->each_q.as<float>(), ng, h->dim, h->ld, h->space, h->each_qpad.as<float>(),
-                                 h->each_qaux.as<double>(), nullptr, s));
+    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>({64, (2048 + ntiles - 1) / ntiles, (st.max_m + 63) / 64}));
     HIP_TRY(h, h->partial.ensure((size_t)ng * nchunk * k * sizeof(TopEntry)));
     HIP_TRY(h, launch_where_gather(h->X, h->each_qpad.as<float>(), h->each_qaux.as<double>(), h->each_lab.as<int32_t>(),
                                    h->each_tiles.as<GatherTile>(), ntiles, h->ld, h->space, qt, k, (int32_t)nchunk,
                                    h->partial.as<TopEntry>(), s));
     // outputs [d64 | labels | dist | counts] in the sorted order, one copy back
-    const size_t b64 = (size_t)ng * k * sizeof(double), blab = (size_t)ng * k * sizeof(int64_t);
-    const size_t bdist = (size_t)ng * k * sizeof(float), bcnt = (size_t)ng * sizeof(int32_t);
-    HIP_TRY(h, h->each_out.ensure(b64 + blab + bdist + bcnt));
-    char* dout = h->each_out.as<char>();
-    HIP_TRY(h, launch_exact_merge(h->partial.as<TopEntry>(), ng, nullptr, nullptr, (int32_t)nchunk, k,
-                                  reinterpret_cast<int64_t*>(dout + b64), reinterpret_cast<float*>(dout + b64 + blab),
-                                  reinterpret_cast<int32_t*>(dout + b64 + blab + bdist), reinterpret_cast<double*>(dout), s));
-    std::vector<char> host(b64 + blab + bdist + bcnt);
-    HIP_TRY(h, hipMemcpyAsync(host.data(), dout, host.size(), hipMemcpyDeviceToHost, s));
+    const size_t nk = (size_t)ng * k;
+    std::vector<char> host(ListBlock::bytes(nk, (size_t)ng));
+    HIP_TRY(h, h->each_out.ensure(host.size()));
+    const ListBlock o(h->each_out.p, nk, (size_t)ng), ho(host.data(), nk, (size_t)ng);
+    HIP_TRY(h, launch_exact_merge(h->partial.as<TopEntry>(), ng, nullptr, nullptr, (int32_t)nchunk, k, o.lab, o.dist, o.cnt,
+                                  o.d64, s));
+    HIP_TRY(h, hipMemcpyAsync(host.data(), h->each_out.p, host.size(), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
-    const char* ho = host.data();
-    put_rows(sel, k, reinterpret_cast<const int64_t*>(ho + b64), reinterpret_cast<const float*>(ho + b64 + blab),
-             reinterpret_cast<const int32_t*>(ho + b64 + blab + bdist), reinterpret_cast<const double*>(ho), out_labels,
-             out_dist, out_counts, out_dist64);
+    put_rows(st.sel, k, ho.lab, ho.dist, ho.cnt, ho.d64, out_labels, out_dist, out_counts, out_dist64);
     return MLVDB_OK;
 }
 }  // namespace
@@ -2449,67 +2579,36 @@ int mlvdb_search_batch_where_each(mlvdb_index* h, const float* queries, int64_t 
     if ((rc = where_each_pack(h, programs, n_programs, pk))) return rc;
     if (nq > 0 && (!queries || !program_of_query || !out_labels || !out_dist || !out_counts))
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    std::vector<std::vector<int32_t>> qof((size_t)n_programs);  // each program's queries, ascending
-    std::vector<int32_t> plain;                                  // the unfiltered ones
-    for (int64_t i = 0; i < nq; ++i) {
-        const int32_t p = program_of_query[i];
-        if (p < -1 || p >= n_programs) return fail(h, MLVDB_ERR_INVALID_ARG, "program_of_query entry outside [-1, n_programs)");
-        (p < 0 ? plain : qof[(size_t)p]).push_back((int32_t)i);
-    }
-    std::vector<int32_t> routes((size_t)n_programs, MLVDB_WHERE_ROUTE_NONE);
+    EachSplit split;
+    if ((rc = where_each_split(h, program_of_query, nq, n_programs, split))) return rc;
     std::vector<int64_t> matches((size_t)n_programs, 0);
     const EachSegs sg = each_segments(h->total);
-    bool any = false;
-    for (const auto& qs : qof) any = any || !qs.empty();
-    if (any && h->total > 0) {
+    if (split.any && h->total > 0) {
         rc = where_each_eval(h, pk, sg, matches.data());
         if (rc) return rc;
     }
-    // routes: GATHER while the gathered rows stay a small share of what the masked scan would read
-    int32_t qt = kGatherQT;
-    while (qt > 1 && where_gather_lds(qt, h->ld) > 64 * 1024) qt >>= 1;
-    const bool gather_fits = k <= MLVDB_MAX_TOPK && where_gather_lds(qt, h->ld) <= 64 * 1024;
-    const __int128 live = h->total - h->deleted;
-    std::vector<int32_t> gp, sp;
-    int64_t nlab = 0;
-    for (int32_t p = 0; p < n_programs; ++p) {
-        const size_t nqp = qof[(size_t)p].size();
-        if (nqp == 0 || matches[(size_t)p] == 0) continue;
-        const __int128 tiles = (__int128)((nqp + qt - 1) / qt);
-        const bool gather = gather_fits && (__int128)matches[(size_t)p] * tiles * 1000 <= live * h->tn.where_gather &&
-                            nlab + matches[(size_t)p] <= INT32_MAX;
-        if (gather) nlab += matches[(size_t)p];
-        routes[(size_t)p] = gather ? MLVDB_WHERE_ROUTE_GATHER : MLVDB_WHERE_ROUTE_SCAN;
-        (gather ? gp : sp).push_back(p);
-    }
-    if (out_routes)
-        for (int32_t p = 0; p < n_programs; ++p) out_routes[p] = routes[(size_t)p];
+    const int32_t qt = gather_qt(h);
+    const EachRoutes rt = where_each_routes(h, split.qof, matches, qt, k <= MLVDB_MAX_TOPK);
+    if (out_routes) std::copy(rt.routes.begin(), rt.routes.end(), out_routes);
     // NONE: padding, as a call whose program matches nothing returns it
     for (int32_t p = 0; p < n_programs; ++p) {
-        if (routes[(size_t)p] != MLVDB_WHERE_ROUTE_NONE) continue;
-        for (int32_t q : qof[(size_t)p]) {
-            for (int32_t j = 0; j < k; ++j) {
-                out_labels[(size_t)q * k + j] = -1;
-                out_dist[(size_t)q * k + j] = __builtin_inff();
-                if (out_dist64) out_dist64[(size_t)q * k + j] = __builtin_inf();
-            }
-            out_counts[q] = 0;
-        }
+        if (rt.routes[(size_t)p] != MLVDB_WHERE_ROUTE_NONE) continue;
+        for (int32_t q : split.qof[(size_t)p])
+            pad_outputs(out_labels + (size_t)q * k, out_dist + (size_t)q * k, out_dist64 ? out_dist64 + (size_t)q * k : nullptr, k,
+                        out_counts + q, 1);
     }
-    if (!gp.empty()) {
-        rc = gather_programs(h, queries, k, qt, sg, n_programs, gp, qof, matches.data(), out_labels, out_dist, out_counts,
+    if (!rt.gp.empty()) {
+        rc = gather_programs(h, queries, k, qt, sg, n_programs, rt.gp, split.qof, matches.data(), out_labels, out_dist, out_counts,
                              out_dist64);
         if (rc) return rc;
     }
     // SCAN: the program's row mask out of its bit, then exactly the masked call of mlvdb_search_batch_where
-    for (int32_t p : sp) {
-        HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
-        HIP_TRY(h, launch_where_each_expand(h->each_bits.as<unsigned long long>(), p, h->total, h->row_mask.as<uint8_t>(),
-                                            h->stream));
-        rc = search_rows(h, queries, qof[(size_t)p], k, true, out_labels, out_dist, out_counts, out_dist64);
+    for (int32_t p : rt.sp) {
+        if ((rc = each_row_mask(h, p))) return rc;
+        rc = search_rows(h, queries, split.qof[(size_t)p], k, true, out_labels, out_dist, out_counts, out_dist64);
         if (rc) return rc;
     }
-    if (!plain.empty()) return search_rows(h, queries, plain, k, false, out_labels, out_dist, out_counts, out_dist64);
+    if (!split.plain.empty()) return search_rows(h, queries, split.plain, k, false, out_labels, out_dist, out_counts, out_dist64);
     return MLVDB_OK;
     });
 }
@@ -2567,57 +2666,22 @@ int range_rows(mlvdb_index* h, const float* queries, const std::vector<int32_t>&
     return masked ? with_row_mask(h, m, call) : call();
 }
 
-// The GATHER route of a range call for the programs `gp`: label lists, tiles, then per group of 256 gathered queries (the
-// ranking kernel's workspace holds 256 hit lists) the gathered range kernel and range_rank_kernel; one synchronisation reads
-// the exact counts back.  A query with more hits than its list holds (> kCandCap) gets nothing here: it is appended to
+// The GATHER route of a range call: the gather stage, then per group of 256 gathered queries (the ranking kernel's workspace
+// holds 256 hit lists; no tile straddles two groups) the gathered range kernel and range_rank_kernel; one synchronisation
+// reads the exact counts back.  A query with more hits than its list holds (> kCandCap) gets nothing here: it is appended to
 // redo[its program] for the SCAN route.
 int gather_range_programs(mlvdb_index* h, const float* queries, float radius, int64_t cap_eff, int32_t qt, const EachSegs& sg,
                           int32_t n_programs, const std::vector<int32_t>& gp, const std::vector<std::vector<int32_t>>& qof,
                           const int64_t* matches, RangeParts& parts, std::vector<std::vector<int32_t>>& redo) {
     hipStream_t s = h->stream;
-    std::vector<int64_t> base(kWhereEachMaxPrograms, 0);
-    std::vector<int32_t> sel, prog_of_sel;  // the gathered queries, sorted by program (positions of the prepared batch)
-    std::vector<GatherTile> tiles;
-    unsigned long long gmask = 0;
-    int64_t nlab = 0, max_m = 0;
-    for (int32_t p : gp) {
-        gmask |= 1ull << p;
-        base[p] = nlab;
-        const std::vector<int32_t>& qs = qof[p];
-        for (size_t t0 = 0; t0 < qs.size();) {  // (no tile straddles two 256-query groups)
-            const size_t pos = sel.size() + t0;
-            GatherTile t;
-            t.lab_begin = (int32_t)nlab;
-            t.lab_count = (int32_t)matches[p];
-            t.sel0 = (int32_t)pos;
-            t.nsel = (int32_t)std::min<size_t>({(size_t)qt, qs.size() - t0, kFilterQueries - pos % kFilterQueries});
-            tiles.push_back(t);
-            t0 += (size_t)t.nsel;
-        }
-        sel.insert(sel.end(), qs.begin(), qs.end());
-        prog_of_sel.insert(prog_of_sel.end(), qs.size(), p);
-        nlab += matches[p];
-        max_m = std::max(max_m, matches[p]);
-    }
-    const int64_t ng = (int64_t)sel.size();
+    GatherStage st;
+    if (int rc = gather_stage(h, queries, qt, kFilterQueries, sg, n_programs, gp, qof, matches, st)) return rc;
+    const std::vector<int32_t>& sel = st.sel;
+    const std::vector<GatherTile>& tiles = st.tiles;
+    const int64_t ng = st.ng;
     const int64_t per_group = std::min<int64_t>((int64_t)tiles.size(), kFilterQueries);  // (at most: tiles of a full group)
     // chunks per tile as the gathered kNN cuts them: enough blocks to fill the chip (~2048), none shorter than 64 rows
-    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>({64, (2048 + per_group - 1) / per_group, (max_m + 63) / 64}));
-    HIP_TRY(h, h->each_lab.ensure((size_t)nlab * sizeof(int32_t)));
-    HIP_TRY(h, hipMemcpyAsync(h->each_tot.as<int64_t>() + kWhereEachMaxPrograms, base.data(), base.size() * sizeof(int64_t),
-                              hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_where_each_scatter(h->each_bits.as<unsigned long long>(), h->total, sg.seg_rows, sg.nseg, n_programs,
-                                         h->each_seg.as<uint32_t>(), gmask, h->each_tot.as<int64_t>() + kWhereEachMaxPrograms,
-                                         h->each_lab.as<int32_t>(), s));
-    const std::vector<float> q = pick_queries(queries, h->dim, sel);
-    HIP_TRY(h, h->each_q.ensure(q.size() * sizeof(float)));
-    HIP_TRY(h, h->each_qpad.ensure((size_t)ng * h->ld * sizeof(float)));
-    HIP_TRY(h, h->each_qaux.ensure((size_t)ng * sizeof(double)));
-    HIP_TRY(h, h->each_tiles.ensure(tiles.size() * sizeof(GatherTile)));
-    HIP_TRY(h, hipMemcpyAsync(h->each_q.p, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(h->each_tiles.p, tiles.data(), tiles.size() * sizeof(GatherTile), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_query_prep(h->each_q.as<float>(), (int32_t)ng, h->dim, h->ld, h->space, h->each_qpad.as<float>(),
-                                 h->each_qaux.as<double>(), nullptr, s));
+    const int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>({64, (2048 + per_group - 1) / per_group, (st.max_m + 63) / 64}));
     // the ranking kernel's workspace (what setup_filter_ws gives a range pass, without the candidate lists) and outputs
     {
         const void* before = h->fmisc.p;
@@ -2659,7 +2723,7 @@ int gather_range_programs(mlvdb_index* h, const float* queries, float radius, in
     for (int64_t i = 0; i < ng; ++i) {
         const bool flagged = counts[(size_t)i] > kCandCap;  // (the ranking kernel wrote none of its hits)
         if (flagged) {
-            redo[(size_t)prog_of_sel[(size_t)i]].push_back(sel[(size_t)i]);
+            redo[(size_t)st.prog_of_sel[(size_t)i]].push_back(sel[(size_t)i]);
             ++n_redo;
         }
         offsets[(size_t)i + 1] = offsets[(size_t)i] + (flagged ? 0 : std::min<int64_t>(counts[(size_t)i], cap_eff));
@@ -2684,8 +2748,7 @@ int mlvdb_range_batch_packed_where_each(mlvdb_index* h, const float* queries, in
     return guarded(h, [&]() -> int {
     int rc = check_handle(h);
     if (rc) return rc;
-    // everything is checked before anything is launched: the range arguments as range_batch_impl checks them, the programs
-    // as mlvdb_search_batch_where_each does
+    // everything is checked before anything is launched: the range arguments as range_batch_impl checks them
     if (!out_offsets) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
     if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
@@ -2694,14 +2757,10 @@ int mlvdb_range_batch_packed_where_each(mlvdb_index* h, const float* queries, in
     if ((rc = where_each_pack(h, programs, n_programs, pk))) return rc;
     if (nq > 0 && (!queries || !program_of_query || !out_counts || ((!out_labels || !out_dist) && total_capacity > 0)))
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    std::vector<std::vector<int32_t>> qof((size_t)n_programs);  // each program's queries, ascending
-    std::vector<int32_t> plain;                                  // the unfiltered ones
-    for (int64_t i = 0; i < nq; ++i) {
-        const int32_t p = program_of_query[i];
-        if (p < -1 || p >= n_programs) return fail(h, MLVDB_ERR_INVALID_ARG, "program_of_query entry outside [-1, n_programs)");
-        (p < 0 ? plain : qof[(size_t)p]).push_back((int32_t)i);
-    }
-    std::vector<int32_t> routes((size_t)n_programs, MLVDB_WHERE_ROUTE_NONE);
+    EachSplit split;
+    if ((rc = where_each_split(h, program_of_query, nq, n_programs, split))) return rc;
+    EachRoutes rt;
+    rt.routes.assign((size_t)n_programs, MLVDB_WHERE_ROUTE_NONE);
     RangeParts parts;
     parts.count.assign((size_t)nq, 0);
     parts.begin.assign((size_t)nq, 0);
@@ -2710,52 +2769,32 @@ int mlvdb_range_batch_packed_where_each(mlvdb_index* h, const float* queries, in
     if (nq > 0 && h->total > h->deleted) {
         std::vector<int64_t> matches((size_t)n_programs, 0);
         const EachSegs sg = each_segments(h->total);
-        bool any = false;
-        for (const auto& qs : qof) any = any || !qs.empty();
-        if (any) {
+        if (split.any) {
             rc = where_each_eval(h, pk, sg, matches.data());
             if (rc) return rc;
         }
-        // routes: the rule of mlvdb_search_batch_where_each without its bound on k
-        int32_t qt = kGatherQT;
-        while (qt > 1 && where_gather_lds(qt, h->ld) > 64 * 1024) qt >>= 1;
-        const bool gather_fits = where_gather_lds(qt, h->ld) <= 64 * 1024;
-        const __int128 live = h->total - h->deleted;
-        std::vector<int32_t> gp, sp;
-        int64_t nlab = 0;
-        for (int32_t p = 0; p < n_programs; ++p) {
-            const size_t nqp = qof[(size_t)p].size();
-            if (nqp == 0 || matches[(size_t)p] == 0) continue;
-            const __int128 tiles = (__int128)((nqp + qt - 1) / qt);
-            const bool gather = gather_fits && (__int128)matches[(size_t)p] * tiles * 1000 <= live * h->tn.where_gather &&
-                                nlab + matches[(size_t)p] <= INT32_MAX;
-            if (gather) nlab += matches[(size_t)p];
-            routes[(size_t)p] = gather ? MLVDB_WHERE_ROUTE_GATHER : MLVDB_WHERE_ROUTE_SCAN;
-            (gather ? gp : sp).push_back(p);
-        }
+        const int32_t qt = gather_qt(h);
+        rt = where_each_routes(h, split.qof, matches, qt, true);  // (a range call has no k to bound)
         // GATHER; the queries whose hits its lists could not hold join the SCAN route of their program
         std::vector<std::vector<int32_t>> redo((size_t)n_programs);
-        if (!gp.empty()) {
-            rc = gather_range_programs(h, queries, radius, cap_eff, qt, sg, n_programs, gp, qof, matches.data(), parts, redo);
+        if (!rt.gp.empty()) {
+            rc = gather_range_programs(h, queries, radius, cap_eff, qt, sg, n_programs, rt.gp, split.qof, matches.data(), parts, redo);
             if (rc) return rc;
         }
         // SCAN: the program's row mask out of its bit, then exactly the masked passes of mlvdb_range_batch_packed_where
         for (int32_t p = 0; p < n_programs; ++p) {
-            const std::vector<int32_t>& qs = routes[(size_t)p] == MLVDB_WHERE_ROUTE_SCAN ? qof[(size_t)p] : redo[(size_t)p];
+            const std::vector<int32_t>& qs = rt.routes[(size_t)p] == MLVDB_WHERE_ROUTE_SCAN ? split.qof[(size_t)p] : redo[(size_t)p];
             if (qs.empty()) continue;
-            HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
-            HIP_TRY(h, launch_where_each_expand(h->each_bits.as<unsigned long long>(), p, h->total, h->row_mask.as<uint8_t>(),
-                                                h->stream));
+            if ((rc = each_row_mask(h, p))) return rc;
             rc = range_rows(h, queries, qs, radius, cap_eff, true, parts);
             if (rc) return rc;
         }
-        if (!plain.empty()) {
-            rc = range_rows(h, queries, plain, radius, cap_eff, false, parts);
+        if (!split.plain.empty()) {
+            rc = range_rows(h, queries, split.plain, radius, cap_eff, false, parts);
             if (rc) return rc;
         }
     }
-    if (out_routes)
-        for (int32_t p = 0; p < n_programs; ++p) out_routes[p] = routes[(size_t)p];
+    if (out_routes) std::copy(rt.routes.begin(), rt.routes.end(), out_routes);
     // the packed output, once for the whole call, under the rules of range_batch_impl
     out_offsets[0] = 0;
     bool over = false, hard = false;
@@ -2814,11 +2853,12 @@ int distinct_chunk(mlvdb_index* h, const float* queries, int32_t n, int32_t k, i
     HIP_TRY(h, h->dist_out.ensure(nk * (2 * sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
     HIP_TRY(h, h->dist_sel.ensure((size_t)(n + 1) * sizeof(int32_t)));
     float* dq = h->dist_q.as<float>();
-    double* o_d64 = h->dist_out.as<double>();
-    int64_t* o_grp = reinterpret_cast<int64_t*>(o_d64 + nk);
-    int64_t* o_lab = o_grp + nk;
-    float* o_dist = reinterpret_cast<float*>(o_lab + nk);
-    int32_t* o_cnt = reinterpret_cast<int32_t*>(o_dist + nk);
+    Carver out{h->dist_out.as<char>()};
+    double* o_d64 = out.take<double>(nk);
+    int64_t* o_grp = out.take<int64_t>(nk);
+    int64_t* o_lab = out.take<int64_t>(nk);
+    float* o_dist = out.take<float>(nk);
+    int32_t* o_cnt = out.take<int32_t>((size_t)n);
     o = DistinctOut{o_d64, o_grp, o_lab, o_dist, o_cnt};
     int32_t* nflag_d = h->dist_sel.as<int32_t>();  // [counter | flagged queries]
     int32_t* qsel_d = nflag_d + 1;
@@ -2827,14 +2867,11 @@ int distinct_chunk(mlvdb_index* h, const float* queries, int32_t n, int32_t k, i
     const int32_t* qsel = nullptr;  // ... all of them without a list pass
     if (L > 0) {
         const size_t nl = (size_t)n * L;
-        HIP_TRY(h, h->dist_list.ensure(nl * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
-        double* l_d64 = h->dist_list.as<double>();  // [d64 | labels | dist | counts]
-        int64_t* l_lab = reinterpret_cast<int64_t*>(l_d64 + nl);
-        float* l_dist = reinterpret_cast<float*>(l_lab + nl);
-        int32_t* l_cnt = reinterpret_cast<int32_t*>(l_dist + nl);
-        if (int rc = search_device_impl(h, dq, n, L, l_lab, l_dist, l_cnt, l_d64, s, false)) return rc;
+        HIP_TRY(h, h->dist_list.ensure(ListBlock::bytes(nl, (size_t)n)));
+        const ListBlock l(h->dist_list.p, nl, (size_t)n);
+        if (int rc = search_device_impl(h, dq, n, L, l.lab, l.dist, l.cnt, l.d64, s, false)) return rc;
         HIP_TRY(h, hipMemsetAsync(nflag_d, 0, sizeof(int32_t), s));
-        HIP_TRY(h, launch_distinct_pick(l_lab, l_d64, l_cnt, n, L, group, k, k_eff, qsel_d, nflag_d, o_lab, o_dist, o_cnt,
+        HIP_TRY(h, launch_distinct_pick(l.lab, l.d64, l.cnt, n, L, group, k, k_eff, qsel_d, nflag_d, o_lab, o_dist, o_cnt,
                                         o_d64, o_grp, s));
         HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
         HIP_TRY(h, hipMemcpyAsync(&nsel, nflag_d, sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -2877,13 +2914,8 @@ int distinct_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, i
     hipStream_t s = h->stream;
     const int32_t k_eff = max_groups > 0 ? (int32_t)std::min<int64_t>(k, max_groups) : k;
     if (h->total == 0 || h->total == h->deleted) {
-        for (int64_t i = 0; i < nq * k; ++i) {
-            out_labels[i] = -1;
-            out_dist[i] = __builtin_inff();
-            if (out_dist64) out_dist64[i] = __builtin_inf();
-            if (out_groups) out_groups[i] = INT64_MIN;
-        }
-        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        pad_outputs(out_labels, out_dist, out_dist64, nq * k, out_counts, nq);
+        if (out_groups) std::fill(out_groups, out_groups + nq * k, INT64_MIN);
         return MLVDB_OK;
     }
     const int64_t* group = h->attr_col[attr];
@@ -2913,7 +2945,7 @@ int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq
     return guarded(h, [&]() -> int {
     int rc = check_handle(h);
     if (rc) return rc;
-    // everything is checked before anything is launched (the program: where_run validates it before its first launch)
+    // everything is checked before anything is launched (the program: with_where)
     if ((rc = attr_check(h, attr))) return rc;
     if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "distinct needs an int64 column");
     if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
@@ -2924,11 +2956,7 @@ int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq
     auto call = [&]() {
         return distinct_impl(h, queries, nq, k, attr, max_groups, out_labels, out_dist, out_counts, out_dist64, out_groups);
     };
-    if (!where) return nq == 0 ? MLVDB_OK : call();
-    rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy
-    if (rc || nq == 0) return rc;
-    if (h->total == 0) return call();
-    return with_row_mask(h, nq, call);
+    return with_where(h, where, nq, call);
     });
 }
 
@@ -2938,16 +2966,12 @@ namespace {
 // padding of queries [q0, q0 + n) of a grouped call, on the host
 void grouped_pad(int64_t q0, int64_t n, int32_t k, int32_t gsz, int64_t* out_labels, float* out_dist, int32_t* out_counts,
                  int32_t* out_gcnt, double* out_dist64, int64_t* out_groups) {
-    for (int64_t i = q0 * k * gsz; i < (q0 + n) * k * gsz; ++i) {
-        out_labels[i] = -1;
-        out_dist[i] = __builtin_inff();
-        if (out_dist64) out_dist64[i] = __builtin_inf();
-    }
+    const int64_t at = q0 * k * gsz;
+    pad_outputs(out_labels + at, out_dist + at, out_dist64 ? out_dist64 + at : nullptr, n * k * gsz, out_counts + q0, n);
     for (int64_t i = q0 * k; i < (q0 + n) * k; ++i) {
         out_gcnt[i] = 0;
         if (out_groups) out_groups[i] = INT64_MIN;
     }
-    for (int64_t i = q0; i < q0 + n; ++i) out_counts[i] = 0;
 }
 
 // The member stage of one chunk of n queries: grp / cnt are the distinct stage's group codes [n, k] and counts [n] on the host,
@@ -2980,8 +3004,9 @@ int grouped_members(mlvdb_index* h, int32_t n, int32_t k, int32_t gsz, int32_t q
         slot_of[u] = (uint32_t)at;
     }
     HIP_TRY(h, h->grp_tab.ensure(slots * (sizeof(int64_t) + sizeof(uint32_t))));  // [keys | counts, then cursors]
-    long long* keys_d = h->grp_tab.as<long long>();
-    uint32_t* counts_d = reinterpret_cast<uint32_t*>(keys_d + slots);
+    Carver tab{h->grp_tab.as<char>()};
+    long long* keys_d = tab.take<long long>(slots);
+    uint32_t* counts_d = tab.take<uint32_t>(slots);
     std::vector<uint32_t> counts(slots, 0);
     if (npairs > 0) {
         HIP_TRY(h, hipMemcpyAsync(keys_d, keys.data(), slots * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -3061,12 +3086,9 @@ int grouped_members(mlvdb_index* h, int32_t n, int32_t k, int32_t gsz, int32_t q
                                          (int32_t)tiles[cls].size(), pairs_d, h->ld, h->space, kQt[cls], gsz,
                                          h->partial.as<TopEntry>(), s));
     const size_t ng = (size_t)nslots * gsz;
-    HIP_TRY(h, h->grp_out.ensure(ng * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)nslots * sizeof(int32_t)));
-    double* o_d64 = h->grp_out.as<double>();
-    int64_t* o_lab = reinterpret_cast<int64_t*>(o_d64 + ng);
-    float* o_dist = reinterpret_cast<float*>(o_lab + ng);
-    int32_t* o_gcnt = reinterpret_cast<int32_t*>(o_dist + ng);
-    HIP_TRY(h, launch_grouped_merge(h->partial.as<TopEntry>(), pairs_d, pos_d, nslots, gsz, o_lab, o_dist, o_d64, o_gcnt, s));
+    HIP_TRY(h, h->grp_out.ensure(ListBlock::bytes(ng, (size_t)nslots)));
+    const ListBlock o(h->grp_out.p, ng, (size_t)nslots);  // (its counts: the group counts)
+    HIP_TRY(h, launch_grouped_merge(h->partial.as<TopEntry>(), pairs_d, pos_d, nslots, gsz, o.lab, o.dist, o.d64, o.cnt, s));
     HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
     return MLVDB_OK;
 }
@@ -3098,15 +3120,12 @@ int grouped_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, in
         HIP_TRY(h, hipMemcpyAsync(cnt.data(), o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
         if (int rc = grouped_members(h, n, k, gsz, qt_max, col, grp.data(), cnt.data())) return rc;
-        const double* o_d64 = h->grp_out.as<double>();  // [d64 | labels | dist | group counts]
-        const int64_t* o_lab = reinterpret_cast<const int64_t*>(o_d64 + ng);
-        const float* o_dist = reinterpret_cast<const float*>(o_lab + ng);
-        const int32_t* o_gcnt = reinterpret_cast<const int32_t*>(o_dist + ng);
+        const ListBlock m(h->grp_out.p, ng, nk);  // [d64 | labels | dist | group counts], as grouped_members left it
         const size_t at = (size_t)q0 * k;
-        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at * gsz, o_d64, ng * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_labels + at * gsz, o_lab, ng * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_dist + at * gsz, o_dist, ng * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_gcnt + at, o_gcnt, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at * gsz, m.d64, ng * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_labels + at * gsz, m.lab, ng * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_dist + at * gsz, m.dist, ng * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_gcnt + at, m.cnt, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
         if (out_groups) std::memcpy(out_groups + at, grp.data(), nk * sizeof(int64_t));
         std::memcpy(out_counts + q0, cnt.data(), (size_t)n * sizeof(int32_t));
@@ -3122,7 +3141,7 @@ int mlvdb_search_batch_grouped(mlvdb_index* h, const float* queries, int64_t nq,
     return guarded(h, [&]() -> int {
     int rc = check_handle(h);
     if (rc) return rc;
-    // everything is checked before anything is launched (the program: where_run validates it before its first launch)
+    // everything is checked before anything is launched (the program: with_where)
     if ((rc = attr_check(h, attr))) return rc;
     if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "grouped needs an int64 column");
     if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
@@ -3133,19 +3152,14 @@ int mlvdb_search_batch_grouped(mlvdb_index* h, const float* queries, int64_t nq,
     if (max_groups < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "max_groups < 0");
     if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts || !out_group_counts))
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    int32_t qt = kGatherQT;  // pairs per tile of the gathered kernel (fewer only when the tile would not fit in LDS)
-    while (qt > 1 && where_gather_lds(qt, h->ld) > 64 * 1024) qt >>= 1;
+    const int32_t qt = gather_qt(h);  // pairs per tile of the gathered kernel
     if (where_gather_lds(qt, h->ld) > 64 * 1024)
         return fail(h, MLVDB_ERR_UNSUPPORTED, "grouped: one query of this dimension needs more than 64 KiB of LDS");
     auto call = [&]() {
         return grouped_impl(h, queries, nq, k, group_size, qt, attr, max_groups, out_labels, out_dist, out_counts,
                             out_group_counts, out_dist64, out_groups);
     };
-    if (!where) return nq == 0 ? MLVDB_OK : call();
-    rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy
-    if (rc || nq == 0) return rc;
-    if (h->total == 0) return call();
-    return with_row_mask(h, nq, call);
+    return with_where(h, where, nq, call);
     });
 }
 
@@ -3160,14 +3174,9 @@ int mmr_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_
              float* out_dist, int32_t* out_counts, double* out_dist64, int32_t* out_rank, double* out_objective) {
     hipStream_t s = h->stream;
     if (h->total == 0 || h->total == h->deleted) {
-        for (int64_t i = 0; i < nq * k; ++i) {
-            out_labels[i] = -1;
-            out_dist[i] = __builtin_inff();
-            if (out_dist64) out_dist64[i] = __builtin_inf();
-            if (out_rank) out_rank[i] = -1;
-            if (out_objective) out_objective[i] = __builtin_inf();
-        }
-        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        pad_outputs(out_labels, out_dist, out_dist64, nq * k, out_counts, nq);
+        if (out_rank) std::fill(out_rank, out_rank + nq * k, -1);
+        if (out_objective) std::fill(out_objective, out_objective + nq * k, __builtin_inf());
         return MLVDB_OK;
     }
     const double one_minus_lambda = 1.0 - lambda;  // formed once, here
@@ -3175,23 +3184,21 @@ int mmr_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_
         const int32_t n = (int32_t)std::min<int64_t>(kMmrChunk, nq - q0);
         const size_t nk = (size_t)n * k, nl = (size_t)n * fetch_k;
         HIP_TRY(h, h->mmr_q.ensure((size_t)n * h->dim * sizeof(float)));
-        HIP_TRY(h, h->mmr_list.ensure(nl * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
+        HIP_TRY(h, h->mmr_list.ensure(ListBlock::bytes(nl, (size_t)n)));
         HIP_TRY(h, h->mmr_out.ensure(nk * (2 * sizeof(double) + sizeof(int64_t) + sizeof(float) + sizeof(int32_t)) +
                                      (size_t)n * sizeof(int32_t)));
         float* dq = h->mmr_q.as<float>();
-        double* l_d64 = h->mmr_list.as<double>();  // [d64 | labels | dist | counts]
-        int64_t* l_lab = reinterpret_cast<int64_t*>(l_d64 + nl);
-        float* l_dist = reinterpret_cast<float*>(l_lab + nl);
-        int32_t* l_cnt = reinterpret_cast<int32_t*>(l_dist + nl);
-        double* o_d64 = h->mmr_out.as<double>();  // [d64 | objective | labels | dist | rank | counts]
-        double* o_obj = o_d64 + nk;
-        int64_t* o_lab = reinterpret_cast<int64_t*>(o_obj + nk);
-        float* o_dist = reinterpret_cast<float*>(o_lab + nk);
-        int32_t* o_rank = reinterpret_cast<int32_t*>(o_dist + nk);
-        int32_t* o_cnt = o_rank + nk;
+        const ListBlock l(h->mmr_list.p, nl, (size_t)n);
+        Carver out{h->mmr_out.as<char>()};  // [d64 | objective | labels | dist | rank | counts]
+        double* o_d64 = out.take<double>(nk);
+        double* o_obj = out.take<double>(nk);
+        int64_t* o_lab = out.take<int64_t>(nk);
+        float* o_dist = out.take<float>(nk);
+        int32_t* o_rank = out.take<int32_t>(nk);
+        int32_t* o_cnt = out.take<int32_t>((size_t)n);
         HIP_TRY(h, hipMemcpyAsync(dq, queries + (size_t)q0 * h->dim, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
-        if (int rc = search_device_impl(h, dq, n, fetch_k, l_lab, l_dist, l_cnt, l_d64, s, false)) return rc;
-        HIP_TRY(h, launch_mmr_select(h->X, h->dim, h->ld, h->space, l_lab, l_dist, l_d64, l_cnt, n, fetch_k, k, lambda,
+        if (int rc = search_device_impl(h, dq, n, fetch_k, l.lab, l.dist, l.cnt, l.d64, s, false)) return rc;
+        HIP_TRY(h, launch_mmr_select(h->X, h->dim, h->ld, h->space, l.lab, l.dist, l.d64, l.cnt, n, fetch_k, k, lambda,
                                      one_minus_lambda, o_lab, o_dist, o_cnt, o_d64, o_rank, o_obj, s));
         const size_t at = (size_t)q0 * k;
         HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
@@ -3214,7 +3221,7 @@ int mlvdb_search_batch_mmr(mlvdb_index* h, const float* queries, int64_t nq, int
     return guarded(h, [&]() -> int {
     int rc = check_handle(h);
     if (rc) return rc;
-    // everything is checked before anything is launched (the program: where_run validates it before its first launch)
+    // everything is checked before anything is launched (the program: with_where)
     if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
     if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
     if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "mmr: k above MLVDB_MAX_TOPK");
@@ -3228,11 +3235,8 @@ int mlvdb_search_batch_mmr(mlvdb_index* h, const float* queries, int64_t nq, int
         return mmr_impl(h, queries, nq, k, fetch_k, lambda, out_labels, out_dist, out_counts, out_dist64, out_rank,
                         out_objective);
     };
-    if (!where) return nq == 0 ? MLVDB_OK : call();
-    rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy
-    if (rc || nq == 0) return rc;
-    if (h->total == 0) return call();
-    return with_row_mask(h, nq, call);
+    // the first launches: where_run(h, where, ...) for the program, then mmr_impl under with_row_mask(h, nq, ...)
+    return with_where(h, where, nq, call);
     });
 }
 

@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mlvdb_hip.h"
@@ -35,6 +36,33 @@ inline hipError_t ensure_dynamic_lds(std::atomic<uint64_t>& done, const void* ke
     e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
     return e;
+}
+
+// The same for one kernel instance (one instantiation, hence one flag per device, per kernel): a launch with `lds` above the
+// 48 KiB every kernel may use configures the instance once for `max_bytes`, the most any later launch of it may ask for --
+// the attribute holds for the rest of the process.
+template <auto Kernel>
+inline hipError_t ensure_instance_lds(size_t lds, int max_bytes) {
+    static std::atomic<uint64_t> lds_set{0};
+    return lds > 48 * 1024 ? ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(Kernel), max_bytes) : hipSuccess;
+}
+
+// f(SPACE, QT) with the space and the queries per tile (1, 2, otherwise 4) of a gathered launch as compile-time constants:
+// f is a generic lambda, `constexpr int SPACE = decltype(sp)::value` inside it.
+template <class F>
+inline hipError_t with_space_qt(int32_t space, int32_t qt, F&& f) {
+    auto with_qt = [&](auto sp) {
+        switch (qt) {
+            case 1: return f(sp, std::integral_constant<int, 1>{});
+            case 2: return f(sp, std::integral_constant<int, 2>{});
+            default: return f(sp, std::integral_constant<int, 4>{});
+        }
+    };
+    switch (space) {
+        case kSpaceL2: return with_qt(std::integral_constant<int, kSpaceL2>{});
+        case kSpaceCosine: return with_qt(std::integral_constant<int, kSpaceCosine>{});
+        default: return with_qt(std::integral_constant<int, kSpaceIp>{});
+    }
 }
 
 // ---------------------------------------------------------------- tuning state (per handle)
@@ -349,8 +377,8 @@ hipError_t launch_tombstone_mask(const uint8_t* mask, float* rn, float* rp8, int
 constexpr int kWhereEachMaxPrograms = MLVDB_WHERE_EACH_MAX_PROGRAMS;
 constexpr int kWhereEachMaxOps = MLVDB_WHERE_EACH_MAX_OPS;
 static_assert(sizeof(WhereOp) == 32, "the programs of a call are staged in 32 KiB of LDS");
-// one block row of the gathered kernel: <= QT queries of one program (positions sel0.. of the call's sorted query list)
-// and that program's label list labels[lab_begin, lab_begin + lab_count)
+// one block row of the two gathered kernels below (the walk itself: gather_walk.h): <= QT queries of one program (positions
+// sel0.. of the call's sorted query list) and that program's label list labels[lab_begin, lab_begin + lab_count)
 struct GatherTile {
     int32_t lab_begin, lab_count, sel0, nsel;
 };
@@ -368,14 +396,15 @@ hipError_t launch_where_each_scatter(const unsigned long long* bits, int64_t tot
                                      int32_t* labels, hipStream_t s);
 // mask[i] = bit p of bits[i]
 hipError_t launch_where_each_expand(const unsigned long long* bits, int32_t p, int64_t total, uint8_t* mask, hipStream_t s);
-// LDS of the gathered kernel for qt queries per tile (it must stay <= 64 KiB)
+// LDS of a gathered top-k kernel (where_gather_kernel, grouped_gather_kernel) for qt queries per tile: the query tile or the
+// block merge's lists, whichever is larger (it must stay <= 64 KiB)
 size_t where_gather_lds(int32_t qt, int32_t ld);
 // partial[(sel * nchunk + chunk) * k + j] for every query of every tile (qt in 1, 2, 4; k <= 64)
 hipError_t launch_where_gather(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
                                const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t space, int32_t qt, int32_t k,
                                int32_t nchunk, TopEntry* partial, hipStream_t s);
-// The gathered range kernel: the tiles' queries (positions q_base .. q_base + 255 of the sorted query list) against their
-// programs' label lists; every hit (fp64 distance <= radius) is counted in rhit_cnt[sel - q_base] (exact, whatever the list
+// The gathered range kernel: the tiles' queries (positions q_base .. q_base + 255 of the sorted query list; qt in 1, 2, 4)
+// against their programs' label lists; every hit (fp64 distance <= radius) is counted in rhit_cnt[sel - q_base] (exact, whatever the list
 // holds) and the first kCandCap of a query stored in rhits[(sel - q_base) * kCandCap ..] -- the input of launch_range_rank.
 hipError_t launch_where_gather_range(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
                                      const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t space, int32_t qt,
@@ -430,7 +459,7 @@ __host__ __device__ inline int64_t grouped_chunk_rows(int64_t work) {
 struct GroupedPair {
     int32_t q, part0, nch, pad;
 };
-// one block of the gathered kernel: <= QT pairs pair0.. of one group against labels[lab_begin, lab_begin + lab_count), one
+// one block of grouped_gather_kernel: <= QT pairs pair0.. of one group against labels[lab_begin, lab_begin + lab_count), one
 // chunk of the group's list; part0: pair0's partial list of this chunk (pair t: part0 + t * nch)
 struct GroupedTile {
     int32_t lab_begin, lab_count, pair0, npairs, part0, nch;

@@ -1,7 +1,7 @@
 // Grouped kNN (include/mlvdb_grouped.h): the member stage behind the distinct stage.  For the group codes a chunk of queries
 // picked, two passes over the attribute column list the live rows of every picked group (counts per code, then int32 labels
 // into one CSR array), and the gathered kernel scores each list against exactly the (query, rank) pairs that picked its
-// group -- with the arithmetic of the exact scan (scan_common.h), so a row scores bit-identically here and there.
+// group, by the gathered walk (gather_walk.h).
 //
 // The codes sit in an open-addressing table the host built (facet_hash, linear probing, at most half full, INT64_MIN =
 // empty): a row's slot is found by probing, never inserted.  The order of the rows inside a list depends on the order in
@@ -9,8 +9,8 @@
 // order (fp64 distance, label) is total.
 #include <algorithm>
 
+#include "gather_walk.h"
 #include "internal.h"
-#include "scan_common.h"
 #include "wave_peel.h"
 
 namespace mlvdb {
@@ -100,11 +100,10 @@ hipError_t launch_grouped_fill(const float* rn, const int64_t* col, int64_t tota
 }
 
 // ------------------------------------------------------------------ the gathered scoring of the member lists
-// One block per tile: <= QT of the (query, rank) pairs that picked one group against one chunk of that group's label list
-// (the shape of where_gather_kernel).  The queries are staged from Qpad / qaux by the pairs' query index -- pairs of one
-// query in different groups read the same prepared query, there is no per-pair copy.  Each wave gathers 16 rows per step
-// with the panel addressing of pair_distance_kernel and scores them with accumulate_rows / finish_distance; one WaveTopK
-// per pair with k = group_size; the block's lists are merged through LDS into the pair's partial list of this chunk,
+// One block per tile: <= QT of the (query, rank) pairs that picked one group against one chunk of that group's label list,
+// by the gathered walk (gather_walk.h).  The queries are staged from Qpad / qaux by the pairs' query index -- pairs of one
+// query in different groups read the same prepared query, there is no per-pair copy.  The sink keeps one WaveTopK per pair
+// with k = group_size; the block's lists are merged through LDS into the pair's partial list of this chunk,
 // partial[(tile.part0 + t * tile.nch) * gsz ..].  Every label is a live row of [0, total) (the fill wrote only those).
 template <int SPACE, int QT>
 __global__ __launch_bounds__(256) void grouped_gather_kernel(const float* __restrict__ X, const float* __restrict__ Qpad,
@@ -113,11 +112,9 @@ __global__ __launch_bounds__(256) void grouped_gather_kernel(const float* __rest
                                                              const GroupedTile* __restrict__ tiles,
                                                              const GroupedPair* __restrict__ pairs, int32_t ld, int32_t gsz,
                                                              TopEntry* __restrict__ partial) {
-    constexpr int NW = 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, r = lane & 15;
+    const int lane = threadIdx.x & 63;
     const GroupedTile tile = tiles[blockIdx.x];
     int qid[QT];
     double qinv[QT];
@@ -125,95 +122,30 @@ __global__ __launch_bounds__(256) void grouped_gather_kernel(const float* __rest
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         qid[t] = t < tile.npairs ? pairs[tile.pair0 + t].q : -1;
-        for (int c = threadIdx.x; c < ld; c += NW * 64)
-            qs[t * ld + c] = qid[t] >= 0 ? (double)Qpad[(int64_t)qid[t] * ld + c] : 0.0;
-        qinv[t] = qid[t] >= 0 ? qaux[qid[t]] : 0.0;
         top[t].init();
     }
-    __syncthreads();
+    gather_stage_queries<QT>(qs, Qpad, qaux, qid, ld, qinv);
     const int64_t begin = tile.lab_begin;
-    const int64_t end = begin + tile.lab_count;
-    for (int64_t j0 = begin + wave * 16; j0 < end; j0 += NW * 16) {
-        const int64_t j = j0 + r;
-        const bool have = j < end;
-        const int64_t row = have ? labels[j] : 0;  // (row 0 keeps the address valid)
-        const float* base[1] = {X + (row >> 4) * (int64_t)(kPanelRows * ld) + (row & 15) * 16 + g * 4};
-        double acc[1][QT], nx[1];
-        accumulate_rows<SPACE, QT, 1, 8>(base, qs, ld, g, acc, nx);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            const double dist = finish_distance<SPACE>(acc[0][t], nx[0], qinv[t]);
-            top[t].offer(have && lane < 16 && qid[t] >= 0, dist, (int32_t)row, gsz, lane);
-        }
-    }
-    // ---- block merge: lists of all waves through LDS (aliases the query tile)
-    __syncthreads();
-    double* ld_d = reinterpret_cast<double*>(smem);                                            // [NW][QT][64]
-    int32_t* ld_l = reinterpret_cast<int32_t*>(smem + (size_t)NW * QT * 64 * sizeof(double));  // [NW][QT][64]
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        ld_d[(wave * QT + t) * 64 + lane] = top[t].d;
-        ld_l[(wave * QT + t) * 64 + lane] = top[t].l;
-    }
-    __syncthreads();
-    for (int t = wave; t < QT; t += NW) {
-        if (qid[t] < 0) continue;  // (wave-uniform)
-        WaveTopK m;
-        m.init();
-        for (int w2 = 0; w2 < NW; ++w2) {
-            const double cd = ld_d[(w2 * QT + t) * 64 + lane];
-            const int32_t cl = ld_l[(w2 * QT + t) * 64 + lane];
-            m.offer(lane < gsz && cl != kNoLabel, cd, cl, gsz, lane);
-        }
-        if (lane < gsz) {
-            TopEntry e;
-            e.d = m.d;
-            e.l = m.l;
-            e.pad = 0;
-            partial[((int64_t)tile.part0 + (int64_t)t * tile.nch) * gsz + lane] = e;
-        }
-    }
+    gather_walk<SPACE, QT>(X, labels, begin, begin + tile.lab_count, qs, ld, qinv, [&](int t, bool have, double dist, int32_t row) {
+        top[t].offer(have && qid[t] >= 0, dist, row, gsz, lane);
+    });
+    gather_block_merge<QT>(smem, top, qid, gsz, [&](int t) { return partial + ((int64_t)tile.part0 + (int64_t)t * tile.nch) * gsz; });
 }
 
-template <int SPACE, int QT>
-static hipError_t launch_grouped_qt(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
-                                    const GroupedTile* tiles, int32_t ntiles, const GroupedPair* pairs, int32_t ld, int32_t gsz,
-                                    TopEntry* partial, hipStream_t s) {
-    // configured once per instance, for the largest tile any ld may ask for (64 KiB, launch_grouped_gather's limit): the
-    // attribute holds for the rest of the process, whatever the ld of a later call
-    static std::atomic<uint64_t> lds_set{0};
-    auto kern = grouped_gather_kernel<SPACE, QT>;
-    const size_t lds = where_gather_lds(QT, ld);
-    if (lds > 48 * 1024) {
-        hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(kern), 64 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    kern<<<(unsigned)ntiles, 256, lds, s>>>(X, Qpad, qaux, labels, tiles, pairs, ld, gsz, partial);
-    return hipGetLastError();
-}
-
-template <int SPACE>
-static hipError_t launch_grouped_space(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
-                                       const GroupedTile* tiles, int32_t ntiles, const GroupedPair* pairs, int32_t ld, int32_t qt,
-                                       int32_t gsz, TopEntry* partial, hipStream_t s) {
-    switch (qt) {
-        case 1: return launch_grouped_qt<SPACE, 1>(X, Qpad, qaux, labels, tiles, ntiles, pairs, ld, gsz, partial, s);
-        case 2: return launch_grouped_qt<SPACE, 2>(X, Qpad, qaux, labels, tiles, ntiles, pairs, ld, gsz, partial, s);
-        default: return launch_grouped_qt<SPACE, 4>(X, Qpad, qaux, labels, tiles, ntiles, pairs, ld, gsz, partial, s);
-    }
-}
-
+// (the instances are configured for the largest tile any ld may ask for, 64 KiB: the limit checked here)
 hipError_t launch_grouped_gather(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
                                  const GroupedTile* tiles, int32_t ntiles, const GroupedPair* pairs, int32_t ld, int32_t space,
                                  int32_t qt, int32_t gsz, TopEntry* partial, hipStream_t s) {
     if (ntiles <= 0) return hipSuccess;
     if (gsz < 1 || gsz > kWave || (qt != 1 && qt != 2 && qt != 4) || where_gather_lds(qt, ld) > 64 * 1024)
         return hipErrorInvalidValue;
-    switch (space) {
-        case kSpaceL2: return launch_grouped_space<kSpaceL2>(X, Qpad, qaux, labels, tiles, ntiles, pairs, ld, qt, gsz, partial, s);
-        case kSpaceCosine: return launch_grouped_space<kSpaceCosine>(X, Qpad, qaux, labels, tiles, ntiles, pairs, ld, qt, gsz, partial, s);
-        default: return launch_grouped_space<kSpaceIp>(X, Qpad, qaux, labels, tiles, ntiles, pairs, ld, qt, gsz, partial, s);
-    }
+    return with_space_qt(space, qt, [&](auto sp, auto q) {
+        constexpr int SPACE = decltype(sp)::value, QT = decltype(q)::value;
+        const size_t lds = where_gather_lds(QT, ld);
+        if (hipError_t e = ensure_instance_lds<grouped_gather_kernel<SPACE, QT>>(lds, 64 * 1024)) return e;
+        grouped_gather_kernel<SPACE, QT><<<(unsigned)ntiles, 256, lds, s>>>(X, Qpad, qaux, labels, tiles, pairs, ld, gsz, partial);
+        return hipGetLastError();
+    });
 }
 
 // The twin of exact_merge_kernel that writes to [slot, 0 .. gsz): one wave per (query, rank) slot of the chunk, four per

@@ -1,7 +1,6 @@
 // Per-query metadata filters (include/mlvdb_where_each.h): every program of a call evaluated in one pass over the attribute
 // columns into one 64-bit word per row, the ascending label lists of the programs routed to the gathered kernel, and that
-// kernel -- exact fp64 distances of just the matching rows, with the arithmetic of the exact scan (scan_common.h), so a row
-// scores bit-identically here and there -- and its range sibling (include/mlvdb_where_each_range.h), which keeps every hit
+// kernel -- exact fp64 distances of just the matching rows, by the gathered walk (gather_walk.h) -- and its range sibling (include/mlvdb_where_each_range.h), which keeps every hit
 // within the radius instead of the k nearest.  The programs reach these kernels validated (api.hip: where_prepare).
 //
 // Segments: the rows are cut into `nseg` contiguous runs of `seg_rows` rows (a multiple of 64), one wave each, in the same
@@ -9,8 +8,8 @@
 // each segment's matches in row order -- the label lists come out ascending without any sort.
 #include <algorithm>
 
+#include "gather_walk.h"
 #include "internal.h"
-#include "scan_common.h"
 #include "where_common.h"
 
 namespace mlvdb {
@@ -180,20 +179,18 @@ hipError_t launch_where_each_expand(const unsigned long long* bits, int32_t p, i
 
 // ------------------------------------------------------------------ the gathered exact top-k
 // Block (tile, chunk): the tile's <= QT queries (one program, positions sel0.. of the call's sorted query list, prepared
-// in Qpad / qaux at those positions) against chunk `blockIdx.y` of the program's label list.  Each wave gathers 16 rows
-// per step with the panel addressing of pair_distance_kernel and scores them with accumulate_rows / finish_distance; one
-// WaveTopK per query; the block's lists are merged through LDS into partial[(sel * nchunk + chunk) * k ..] (TopEntry), the
-// input of exact_merge_kernel.  Every label is a live row of [0, total) (the scatter above wrote only those).
+// in Qpad / qaux at those positions) against chunk `blockIdx.y` of the program's label list, by the gathered walk
+// (gather_walk.h).  The sink keeps one WaveTopK per query; the block's lists are merged through LDS into
+// partial[(sel * nchunk + chunk) * k ..] (TopEntry), the input of exact_merge_kernel.  Every label is a live row of
+// [0, total) (the scatter above wrote only those).
 template <int SPACE, int QT>
 __global__ __launch_bounds__(256) void where_gather_kernel(const float* __restrict__ X, const float* __restrict__ Qpad,
                                                            const double* __restrict__ qaux, const int32_t* __restrict__ labels,
                                                            const GatherTile* __restrict__ tiles, int32_t ld, int32_t k,
                                                            int32_t nchunk, TopEntry* __restrict__ partial) {
-    constexpr int NW = 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, r = lane & 15;
+    const int lane = threadIdx.x & 63;
     const GatherTile tile = tiles[blockIdx.x];
     int qid[QT];
     double qinv[QT];
@@ -201,55 +198,16 @@ __global__ __launch_bounds__(256) void where_gather_kernel(const float* __restri
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         qid[t] = t < tile.nsel ? tile.sel0 + t : -1;
-        for (int c = threadIdx.x; c < ld; c += NW * 64)
-            qs[t * ld + c] = qid[t] >= 0 ? (double)Qpad[(int64_t)qid[t] * ld + c] : 0.0;
-        qinv[t] = qid[t] >= 0 ? qaux[qid[t]] : 0.0;
         top[t].init();
     }
-    __syncthreads();
+    gather_stage_queries<QT>(qs, Qpad, qaux, qid, ld, qinv);
     const int64_t per = ((int64_t)tile.lab_count + nchunk - 1) / nchunk;
     const int64_t begin = tile.lab_begin + per * blockIdx.y;
     const int64_t end = std::min<int64_t>((int64_t)tile.lab_begin + tile.lab_count, begin + per);
-    for (int64_t j0 = begin + wave * 16; j0 < end; j0 += NW * 16) {
-        const int64_t j = j0 + r;
-        const bool have = j < end;
-        const int64_t row = have ? labels[j] : 0;  // (row 0 keeps the address valid)
-        const float* base[1] = {X + (row >> 4) * (int64_t)(kPanelRows * ld) + (row & 15) * 16 + g * 4};
-        double acc[1][QT], nx[1];
-        accumulate_rows<SPACE, QT, 1, 8>(base, qs, ld, g, acc, nx);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            const double dist = finish_distance<SPACE>(acc[0][t], nx[0], qinv[t]);
-            top[t].offer(have && lane < 16 && qid[t] >= 0, dist, (int32_t)row, k, lane);
-        }
-    }
-    // ---- block merge: lists of all waves through LDS (aliases the query tile)
-    __syncthreads();
-    double* ld_d = reinterpret_cast<double*>(smem);                                            // [NW][QT][64]
-    int32_t* ld_l = reinterpret_cast<int32_t*>(smem + (size_t)NW * QT * 64 * sizeof(double));  // [NW][QT][64]
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        ld_d[(wave * QT + t) * 64 + lane] = top[t].d;
-        ld_l[(wave * QT + t) * 64 + lane] = top[t].l;
-    }
-    __syncthreads();
-    for (int t = wave; t < QT; t += NW) {
-        if (qid[t] < 0) continue;  // (wave-uniform)
-        WaveTopK m;
-        m.init();
-        for (int w2 = 0; w2 < NW; ++w2) {
-            const double cd = ld_d[(w2 * QT + t) * 64 + lane];
-            const int32_t cl = ld_l[(w2 * QT + t) * 64 + lane];
-            m.offer(lane < k && cl != kNoLabel, cd, cl, k, lane);
-        }
-        if (lane < k) {
-            TopEntry e;
-            e.d = m.d;
-            e.l = m.l;
-            e.pad = 0;
-            partial[((int64_t)qid[t] * nchunk + blockIdx.y) * k + lane] = e;
-        }
-    }
+    gather_walk<SPACE, QT>(X, labels, begin, end, qs, ld, qinv, [&](int t, bool have, double dist, int32_t row) {
+        top[t].offer(have && qid[t] >= 0, dist, row, k, lane);
+    });
+    gather_block_merge<QT>(smem, top, qid, k, [&](int t) { return partial + ((int64_t)qid[t] * nchunk + blockIdx.y) * k; });
 }
 
 size_t where_gather_lds(int32_t qt, int32_t ld) {
@@ -258,55 +216,30 @@ size_t where_gather_lds(int32_t qt, int32_t ld) {
     return std::max(q_bytes, m_bytes);
 }
 
-template <int SPACE, int QT>
-static hipError_t launch_gather_qt(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
-                                   const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t k, int32_t nchunk,
-                                   TopEntry* partial, hipStream_t s) {
-    // configured once per instance, for the largest tile any ld may ask for (64 KiB, launch_where_gather's limit): the
-    // attribute holds for the rest of the process, whatever the ld of a later call
-    static std::atomic<uint64_t> lds_set{0};
-    auto kern = where_gather_kernel<SPACE, QT>;
-    const size_t lds = where_gather_lds(QT, ld);
-    if (lds > 48 * 1024) {
-        hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(kern), 64 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    kern<<<dim3((unsigned)ntiles, (unsigned)nchunk), 256, lds, s>>>(X, Qpad, qaux, labels, tiles, ld, k, nchunk, partial);
-    return hipGetLastError();
-}
-
-template <int SPACE>
-static hipError_t launch_gather_space(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
-                                      const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t qt, int32_t k,
-                                      int32_t nchunk, TopEntry* partial, hipStream_t s) {
-    switch (qt) {
-        case 1: return launch_gather_qt<SPACE, 1>(X, Qpad, qaux, labels, tiles, ntiles, ld, k, nchunk, partial, s);
-        case 2: return launch_gather_qt<SPACE, 2>(X, Qpad, qaux, labels, tiles, ntiles, ld, k, nchunk, partial, s);
-        default: return launch_gather_qt<SPACE, 4>(X, Qpad, qaux, labels, tiles, ntiles, ld, k, nchunk, partial, s);
-    }
-}
-
+// (the instances are configured for the largest tile any ld may ask for, 64 KiB: the limit checked here)
 hipError_t launch_where_gather(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
                                const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t space, int32_t qt, int32_t k,
                                int32_t nchunk, TopEntry* partial, hipStream_t s) {
     if (ntiles <= 0) return hipSuccess;
     if (k < 1 || k > kWave || nchunk < 1 || where_gather_lds(qt, ld) > 64 * 1024) return hipErrorInvalidValue;
-    switch (space) {
-        case kSpaceL2: return launch_gather_space<kSpaceL2>(X, Qpad, qaux, labels, tiles, ntiles, ld, qt, k, nchunk, partial, s);
-        case kSpaceCosine: return launch_gather_space<kSpaceCosine>(X, Qpad, qaux, labels, tiles, ntiles, ld, qt, k, nchunk, partial, s);
-        default: return launch_gather_space<kSpaceIp>(X, Qpad, qaux, labels, tiles, ntiles, ld, qt, k, nchunk, partial, s);
-    }
+    return with_space_qt(space, qt, [&](auto sp, auto q) {
+        constexpr int SPACE = decltype(sp)::value, QT = decltype(q)::value;
+        const size_t lds = where_gather_lds(QT, ld);
+        if (hipError_t e = ensure_instance_lds<where_gather_kernel<SPACE, QT>>(lds, 64 * 1024)) return e;
+        where_gather_kernel<SPACE, QT><<<dim3((unsigned)ntiles, (unsigned)nchunk), 256, lds, s>>>(X, Qpad, qaux, labels, tiles, ld,
+                                                                                                 k, nchunk, partial);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------ the gathered exact range
-// The block shape, the addressing and the arithmetic of where_gather_kernel; what differs is what a block keeps.  A range
-// query has no k: every (query, matching row) pair is scored and every hit (fp64 distance <= radius; the labels are live
-// matching rows already) is counted, so rhit_cnt[query] ends as the exact hit count whatever becomes of the list.  A step's
-// hits of one query claim their slots together -- one atomicAdd by lane 0 for the ballot's popcount, a hit's own slot from
-// the hits in the lanes below it -- and the first kCandCap of a query are stored {fp64 distance, label} in its hit array,
-// the input of range_rank_kernel (kernels_filter.hip), exactly as range_score_flat_kernel leaves them.  A query with more
-// hits than that is flagged by the ranking kernel and served by the masked range pass (api.hip).  Hits are a small share of
-// the scored pairs, so most steps issue no atomic at all.
+// The same walk; what differs is what a block keeps.  A range query has no k: every (query, matching row) pair is scored
+// and every hit (fp64 distance <= radius; the labels are live matching rows already) is counted, so rhit_cnt[query] ends as
+// the exact hit count whatever becomes of the list.  A step's hits of one query claim their slots together -- one atomicAdd
+// by lane 0 for the ballot's popcount, a hit's own slot from the hits in the lanes below it -- and the first kCandCap of a
+// query are stored {fp64 distance, label} in its hit array, the input of range_rank_kernel (kernels_filter.hip), exactly as
+// range_score_flat_kernel leaves them.  A query with more hits than that is flagged by the ranking kernel and served by the
+// masked range pass (api.hip).  Hits are a small share of the scored pairs, so most steps issue no atomic at all.
 // Queries: positions tile.sel0.. of the call's sorted query list; their hit arrays are indexed from q_base (the 256-query
 // group of the launch: the ranking kernel's workspace holds 256 lists).
 template <int SPACE, int QT>
@@ -316,80 +249,39 @@ __global__ __launch_bounds__(256) void where_gather_range_kernel(const float* __
                                                                  const GatherTile* __restrict__ tiles, int32_t ld,
                                                                  int32_t nchunk, double rad, int32_t q_base,
                                                                  RangeHit* __restrict__ rhits, uint32_t* __restrict__ rhit_cnt) {
-    constexpr int NW = 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, r = lane & 15;
+    const int lane = threadIdx.x & 63;
     const GatherTile tile = tiles[blockIdx.x];
-    int qloc[QT];  // the query's list of this launch's workspace, or -1
+    int qid[QT], qloc[QT];  // qloc: the query's list of this launch's workspace, or -1
     double qinv[QT];
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
-        const int qid = t < tile.nsel ? tile.sel0 + t : -1;
-        for (int c = threadIdx.x; c < ld; c += NW * 64) qs[t * ld + c] = qid >= 0 ? (double)Qpad[(int64_t)qid * ld + c] : 0.0;
-        qinv[t] = qid >= 0 ? qaux[qid] : 0.0;
-        qloc[t] = qid >= 0 ? qid - q_base : -1;
+        qid[t] = t < tile.nsel ? tile.sel0 + t : -1;
+        qloc[t] = qid[t] >= 0 ? qid[t] - q_base : -1;
     }
-    __syncthreads();
+    gather_stage_queries<QT>(qs, Qpad, qaux, qid, ld, qinv);
     const int64_t per = ((int64_t)tile.lab_count + nchunk - 1) / nchunk;
     const int64_t begin = tile.lab_begin + per * blockIdx.y;
     const int64_t end = std::min<int64_t>((int64_t)tile.lab_begin + tile.lab_count, begin + per);
     const unsigned long long below = (1ull << lane) - 1ull;
-    for (int64_t j0 = begin + wave * 16; j0 < end; j0 += NW * 16) {
-        const int64_t j = j0 + r;
-        const bool have = j < end;
-        const int64_t row = have ? labels[j] : 0;  // (row 0 keeps the address valid)
-        const float* base[1] = {X + (row >> 4) * (int64_t)(kPanelRows * ld) + (row & 15) * 16 + g * 4};
-        double acc[1][QT], nx[1];
-        accumulate_rows<SPACE, QT, 1, 8>(base, qs, ld, g, acc, nx);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            const double dist = finish_distance<SPACE>(acc[0][t], nx[0], qinv[t]);
-            const bool hit = have && lane < 16 && qloc[t] >= 0 && dist <= rad;
-            const unsigned long long bal = __ballot(hit);
-            if (bal) {  // wave-uniform
-                uint32_t first = 0;
-                if (lane == 0) first = atomicAdd(&rhit_cnt[qloc[t]], (uint32_t)__popcll(bal));
-                first = __shfl(first, 0);
-                const uint32_t slot = first + (uint32_t)__popcll(bal & below);
-                if (hit && slot < (uint32_t)kCandCap) {  // beyond: counted only
-                    RangeHit h;
-                    h.d = dist;
-                    h.l = (int32_t)row;
-                    h.pad = 0;
-                    rhits[(int64_t)qloc[t] * kCandCap + slot] = h;
-                }
+    gather_walk<SPACE, QT>(X, labels, begin, end, qs, ld, qinv, [&](int t, bool have, double dist, int32_t row) {
+        const bool hit = have && qloc[t] >= 0 && dist <= rad;
+        const unsigned long long bal = __ballot(hit);
+        if (bal) {  // wave-uniform
+            uint32_t first = 0;
+            if (lane == 0) first = atomicAdd(&rhit_cnt[qloc[t]], (uint32_t)__popcll(bal));
+            first = __shfl(first, 0);
+            const uint32_t slot = first + (uint32_t)__popcll(bal & below);
+            if (hit && slot < (uint32_t)kCandCap) {  // beyond: counted only
+                RangeHit h;
+                h.d = dist;
+                h.l = row;
+                h.pad = 0;
+                rhits[(int64_t)qloc[t] * kCandCap + slot] = h;
             }
         }
-    }
-}
-
-template <int SPACE, int QT>
-static hipError_t launch_gather_range_qt(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
-                                         const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t nchunk, float radius,
-                                         int32_t q_base, RangeHit* rhits, uint32_t* rhit_cnt, hipStream_t s) {
-    static std::atomic<uint64_t> lds_set{0};  // (as launch_gather_qt: once per instance, for the largest tile)
-    auto kern = where_gather_range_kernel<SPACE, QT>;
-    const size_t lds = (size_t)QT * ld * sizeof(double);
-    if (lds > 48 * 1024) {
-        hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(kern), 64 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    kern<<<dim3((unsigned)ntiles, (unsigned)nchunk), 256, lds, s>>>(X, Qpad, qaux, labels, tiles, ld, nchunk, (double)radius,
-                                                                    q_base, rhits, rhit_cnt);
-    return hipGetLastError();
-}
-
-template <int SPACE>
-static hipError_t launch_gather_range_space(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
-                                            const GatherTile* tiles, int32_t ntiles, int32_t ld, int32_t qt, int32_t nchunk,
-                                            float radius, int32_t q_base, RangeHit* rhits, uint32_t* rhit_cnt, hipStream_t s) {
-    switch (qt) {
-        case 1: return launch_gather_range_qt<SPACE, 1>(X, Qpad, qaux, labels, tiles, ntiles, ld, nchunk, radius, q_base, rhits, rhit_cnt, s);
-        case 2: return launch_gather_range_qt<SPACE, 2>(X, Qpad, qaux, labels, tiles, ntiles, ld, nchunk, radius, q_base, rhits, rhit_cnt, s);
-        default: return launch_gather_range_qt<SPACE, 4>(X, Qpad, qaux, labels, tiles, ntiles, ld, nchunk, radius, q_base, rhits, rhit_cnt, s);
-    }
+    });
 }
 
 hipError_t launch_where_gather_range(const float* X, const float* Qpad, const double* qaux, const int32_t* labels,
@@ -398,11 +290,14 @@ hipError_t launch_where_gather_range(const float* X, const float* Qpad, const do
                                      hipStream_t s) {
     if (ntiles <= 0) return hipSuccess;
     if (nchunk < 1 || (qt != 1 && qt != 2 && qt != 4) || where_gather_lds(qt, ld) > 64 * 1024) return hipErrorInvalidValue;
-    switch (space) {
-        case kSpaceL2: return launch_gather_range_space<kSpaceL2>(X, Qpad, qaux, labels, tiles, ntiles, ld, qt, nchunk, radius, q_base, rhits, rhit_cnt, s);
-        case kSpaceCosine: return launch_gather_range_space<kSpaceCosine>(X, Qpad, qaux, labels, tiles, ntiles, ld, qt, nchunk, radius, q_base, rhits, rhit_cnt, s);
-        default: return launch_gather_range_space<kSpaceIp>(X, Qpad, qaux, labels, tiles, ntiles, ld, qt, nchunk, radius, q_base, rhits, rhit_cnt, s);
-    }
+    return with_space_qt(space, qt, [&](auto sp, auto q) {
+        constexpr int SPACE = decltype(sp)::value, QT = decltype(q)::value;
+        const size_t lds = (size_t)QT * ld * sizeof(double);  // (no block merge: the query tile alone)
+        if (hipError_t e = ensure_instance_lds<where_gather_range_kernel<SPACE, QT>>(lds, 64 * 1024)) return e;
+        where_gather_range_kernel<SPACE, QT><<<dim3((unsigned)ntiles, (unsigned)nchunk), 256, lds, s>>>(
+            X, Qpad, qaux, labels, tiles, ld, nchunk, (double)radius, q_base, rhits, rhit_cnt);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace mlvdb

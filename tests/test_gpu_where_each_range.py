@@ -262,6 +262,38 @@ def test_list_overflow_on_the_gather_route_is_served_by_the_scan_route():
         eng.close()
 
 
+def test_more_than_256_gathered_queries_in_one_native_call():
+    """300 gathered queries: two 256-query groups of the GATHER route.  Sorted by program the second program's queries begin at
+    position 254, so its first tile is cut at 256 (no tile straddles two groups) and the group loop runs twice."""
+    n, d, space = 2000, 16, "l2"
+    eng, rows, v, tomb, rng = _engine(space, d, n, seed=256)
+    try:
+        fs = [{"v": {"$lt": 40}}, {"v": {"$gte": 100, "$lt": 150}}, {"v": {"$gte": 500, "$lt": 530}}]
+        programs, _ = W.compile_each(fs, SCHEMA)
+        masks = [_match(f, v) & ~tomb for f in fs]
+        assert all(24 <= m.sum() <= 50 for m in masks)  # a few dozen rows each
+        of = rng.permutation(np.repeat(np.arange(3, dtype=np.int32), [254, 6, 40]))
+        nq = of.size
+        qs = rng.standard_normal((nq, d), dtype=np.float32)
+        # the radius from the oracle's distances of every query to its own program's rows: a tenth of the queries have no hit
+        nearest = np.empty(nq)
+        for p, m in enumerate(masks):
+            sel = np.flatnonzero(of == p)
+            nearest[sel] = exact_scan.exact_distances(qs[sel], rows[m], space).min(axis=1)
+        radius = float(np.float32(np.quantile(nearest, 0.9)))
+        want = np.empty(nq, np.int64)
+        for p, m in enumerate(masks):
+            sel = np.flatnonzero(of == p)
+            want[sel] = [r[0].size for r in exact_scan.range_query(qs[sel], rows, radius, space, deleted=~m)]
+        assert (want == 0).any() and ((want >= 1) & (want <= 50)).mean() > 0.5 and want.max() <= 50
+        eng.set_tuning(WHERE_GATHER=ALWAYS)
+        lab, cnt, routes = _check_against_singles(eng, qs, radius, 64, programs, of, "two_groups")
+        assert routes.tolist() == [_native.ROUTE_GATHER] * 3
+        assert np.array_equal(cnt, want)
+    finally:
+        eng.close()
+
+
 def test_ties_come_out_in_ascending_label_order_on_both_routes():
     n, d, space = 12_000, 24, "cosine"
     rng = np.random.default_rng(77)
