@@ -148,6 +148,15 @@ MMR_SIGNATURES = {
                                          _P, _P, _P, _P, _P, _P]),
 }
 
+# include/mlvdb_like.h: search by stored examples -- queries built from stored rows, the examples stripped from the hits
+LIKE_MAX_FETCH = 1024
+LIKE_MAX_EXAMPLES = 64
+LIKE_CHUNK = 1024  # queries per round of synthesis + plain search + strip inside one native call (api.hip: kLikeChunk)
+LIKE_SIGNATURES = {
+    "mlvdb_search_batch_like": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Where),
+                                          _P, _P, _P, _P, _P]),
+}
+
 # include/mlvdb_mutate.h: attribute values set by label, rows updated / tombstoned by filter
 SET_ASSIGN = 0
 SET_ADD = 1
@@ -188,7 +197,7 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
-                                      **ORDER_SIGNATURES, **MMR_SIGNATURES, **MUTATE_SIGNATURES}.items():
+                                      **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MUTATE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

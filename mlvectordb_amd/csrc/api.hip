@@ -2,6 +2,7 @@
 // and the orchestration of the scan kernels.  Nothing here touches the CPU for arithmetic:
 // if no HIP device is usable every entry point fails with MLVDB_ERR_NO_DEVICE.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -153,6 +154,10 @@ struct mlvdb_index {
     // diversified kNN (mlvdb_mmr.h): a chunk's queries, its ranked candidate lists from the plain search and its outputs --
     // sized by the chunk (<= kMmrChunk queries), k and fetch_k, never by the corpus
     DevBuf mmr_q, mmr_list, mmr_out;
+    // search by stored examples (mlvdb_like.h): a chunk's synthesised queries (+ its base rows), its examples, the ranked
+    // lists of the inner search and the stripped outputs -- sized by the chunk (<= kLikeChunk queries), k and the example
+    // counts, never by the corpus
+    DevBuf like_q, like_ex, like_list, like_out;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -1212,7 +1217,8 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
                       &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel,
                       &h->grp_tab, &h->grp_tiles, &h->grp_out, &h->grp_lab,
-                      &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->facet_tab, &h->facet_misc, &h->order_ws, &h->mutate_ws})
+                      &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->like_q, &h->like_ex, &h->like_list, &h->like_out,
+                      &h->facet_tab, &h->facet_misc, &h->order_ws, &h->mutate_ws})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
@@ -3236,6 +3242,111 @@ int mlvdb_search_batch_mmr(mlvdb_index* h, const float* queries, int64_t nq, int
                         out_objective);
     };
     // the first launches: where_run(h, where, ...) for the program, then mmr_impl under with_row_mask(h, nq, ...)
+    return with_where(h, where, nq, call);
+    });
+}
+
+// ---- search by stored examples (mlvdb_like.h)
+extern "C++" {
+namespace {
+constexpr int64_t kLikeChunk = 1024;  // queries per round of synthesis + plain search + strip (bounds the workspaces)
+
+// The validated call (h->rn is the masked copy when a program restricts the rows; the examples' values are read from h->X,
+// which no mask touches).  Per chunk of queries: examples (+ base rows) to the device -> one launch of the query kernel ->
+// the plain device search for `fetch` neighbours (fp64 distances wanted) -> one launch of the strip kernel -> outputs to
+// the host.
+int like_impl(mlvdb_index* h, const int64_t* ex_labels, const double* ex_weights, const int64_t* ex_offsets, const float* base,
+              int64_t nq, int32_t k, int32_t fetch, int32_t exclude, int64_t* out_labels, float* out_dist, int32_t* out_counts,
+              double* out_dist64, float* out_queries) {
+    hipStream_t s = h->stream;
+    if (h->total == 0) {  // no row, so no example: every query is its base row
+        pad_outputs(out_labels, out_dist, out_dist64, nq * k, out_counts, nq);
+        if (out_queries && base) std::memcpy(out_queries, base, (size_t)nq * h->dim * sizeof(float));
+        return MLVDB_OK;
+    }
+    std::vector<int64_t> off((size_t)kLikeChunk + 1);  // a chunk's own offsets
+    for (int64_t q0 = 0; q0 < nq; q0 += kLikeChunk) {
+        const int32_t n = (int32_t)std::min<int64_t>(kLikeChunk, nq - q0);
+        const size_t nk = (size_t)n * k, nl = (size_t)n * fetch, nd = (size_t)n * h->dim;
+        const int64_t e0 = ex_offsets[q0];
+        const size_t ne = (size_t)(ex_offsets[q0 + n] - e0);
+        for (int32_t i = 0; i <= n; ++i) off[(size_t)i] = ex_offsets[q0 + i] - e0;  // (the last chunk's copy has completed)
+        HIP_TRY(h, h->like_q.ensure((base ? 2 : 1) * nd * sizeof(float)));
+        HIP_TRY(h, h->like_ex.ensure(ne * (sizeof(double) + sizeof(int64_t)) + ((size_t)n + 1) * sizeof(int64_t)));
+        HIP_TRY(h, h->like_list.ensure(ListBlock::bytes(nl, (size_t)n)));
+        HIP_TRY(h, h->like_out.ensure(ListBlock::bytes(nk, (size_t)n)));
+        float* dq = h->like_q.as<float>();
+        float* dbase = base ? dq + nd : nullptr;
+        Carver ex{h->like_ex.as<char>()};  // [weights | labels | offsets]
+        double* e_w = ex.take<double>(ne);
+        int64_t* e_lab = ex.take<int64_t>(ne);
+        int64_t* e_off = ex.take<int64_t>((size_t)n + 1);
+        const ListBlock l(h->like_list.p, nl, (size_t)n);
+        const ListBlock o(h->like_out.p, nk, (size_t)n);
+        if (ne > 0) {
+            HIP_TRY(h, hipMemcpyAsync(e_w, ex_weights + e0, ne * sizeof(double), hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(e_lab, ex_labels + e0, ne * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        }
+        HIP_TRY(h, hipMemcpyAsync(e_off, off.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        if (base) HIP_TRY(h, hipMemcpyAsync(dbase, base + (size_t)q0 * h->dim, nd * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, launch_like_query(h->X, h->dim, h->ld, h->space, e_lab, e_w, e_off, dbase, n, dq, s));
+        if (int rc = search_device_impl(h, dq, n, fetch, l.lab, l.dist, l.cnt, l.d64, s, false)) return rc;
+        HIP_TRY(h, launch_like_strip(l.lab, l.dist, l.d64, l.cnt, n, fetch, e_lab, e_off, exclude, k, o.lab, o.dist, o.cnt, o.d64, s));
+        const size_t at = (size_t)q0 * k;
+        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
+        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o.d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_queries) HIP_TRY(h, hipMemcpyAsync(out_queries + (size_t)q0 * h->dim, dq, nd * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_dist + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_like(mlvdb_index* h, const int64_t* example_labels, const double* example_weights,
+                            const int64_t* example_offsets, const float* base_queries, int64_t nq, int32_t k,
+                            int32_t exclude_examples, const mlvdb_where* where, int64_t* out_labels, float* out_dist,
+                            int32_t* out_counts, double* out_dist64, float* out_queries) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked on the host before anything is launched (the program: with_where)
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (k > kLikeMaxFetch) return fail(h, MLVDB_ERR_UNSUPPORTED, "like: k above MLVDB_LIKE_MAX_FETCH");
+    if (nq > 0 && (!example_offsets || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    int32_t most = 0;  // M: the most distinct example labels of one query
+    if (nq > 0) {
+        if (example_offsets[0] != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "like: example_offsets must start at 0");
+        for (int64_t i = 0; i < nq; ++i)
+            if (example_offsets[i + 1] < example_offsets[i])
+                return fail(h, MLVDB_ERR_INVALID_ARG, "like: example_offsets must ascend");
+        if (example_offsets[nq] > 0 && (!example_labels || !example_weights)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+        int64_t seen[kLikeMaxExamples];
+        for (int64_t i = 0; i < nq; ++i) {
+            const int64_t e0 = example_offsets[i], m = example_offsets[i + 1] - e0;
+            if (m > kLikeMaxExamples) return fail(h, MLVDB_ERR_UNSUPPORTED, "like: more than MLVDB_LIKE_MAX_EXAMPLES examples in a query");
+            if (m == 0 && !base_queries) return fail(h, MLVDB_ERR_INVALID_ARG, "like: a query with no example and no base row");
+            for (int64_t j = 0; j < m; ++j) {
+                const int64_t label = example_labels[e0 + j];
+                if (label < 0 || label >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "like: example label out of range");
+                if (!std::isfinite(example_weights[e0 + j])) return fail(h, MLVDB_ERR_INVALID_ARG, "like: example weight not finite");
+                seen[j] = label;
+            }
+            std::sort(seen, seen + m);
+            most = std::max(most, (int32_t)(std::unique(seen, seen + m) - seen));
+        }
+    }
+    if (k + most > kLikeMaxFetch) return fail(h, MLVDB_ERR_UNSUPPORTED, "like: k + examples above MLVDB_LIKE_MAX_FETCH");
+    const int32_t fetch = exclude_examples ? k + most : k;
+    auto call = [&]() {
+        return like_impl(h, example_labels, example_weights, example_offsets, base_queries, nq, k, fetch, exclude_examples,
+                         out_labels, out_dist, out_counts, out_dist64, out_queries);
+    };
+    // the first launches: where_run(h, where, ...) for the program, then like_impl under with_row_mask(h, nq, ...)
     return with_where(h, where, nq, call);
     });
 }

@@ -17,6 +17,7 @@
 #include "../../include/mlvdb_facet.h"
 #include "../../include/mlvdb_order.h"
 #include "../../include/mlvdb_mmr.h"
+#include "../../include/mlvdb_like.h"
 #include "../../include/mlvdb_mutate.h"
 #include "layout.h"
 #include "wave_topk.h"
@@ -490,6 +491,22 @@ hipError_t launch_mmr_select(const float* X, int32_t dim, int32_t ld, int32_t sp
                              const double* l_d64, const int32_t* l_cnt, int32_t nq, int32_t fetch_k, int32_t k, double lambda,
                              double one_minus_lambda, int64_t* out_labels, float* out_dist, int32_t* out_counts,
                              double* out_d64, int32_t* out_rank, double* out_obj, hipStream_t s);
+
+// ---------------------------------------------------------------- search by stored examples (kernels_like.hip)
+constexpr int kLikeMaxFetch = MLVDB_LIKE_MAX_FETCH;        // longest ranked list the strip walks (k + the most examples)
+constexpr int kLikeMaxExamples = MLVDB_LIKE_MAX_EXAMPLES;  // examples of one query: one per lane of the strip's wavefront
+// One block per query: out[q] ([nq, dim] dense fp32) = (float)(base[q] + sum_j t_j x_j) over the examples
+// ex_offsets[q] .. ex_offsets[q + 1] - 1 (<= kLikeMaxExamples, labels inside [0, total): the entry point checked both) in the
+// order given, by the rule of mlvdb_like.h; base may be null.
+hipError_t launch_like_query(const float* X, int32_t dim, int32_t ld, int32_t space, const int64_t* ex_labels,
+                             const double* ex_weights, const int64_t* ex_offsets, const float* base, int32_t nq, float* out,
+                             hipStream_t s);
+// One wavefront per query over its ranked list (l_lab / l_dist / l_d64: [nq][fetch], l_cnt[q] valid entries): the entries
+// whose label is no example of the query (exclude == 0: every entry), order kept, the first k to the outputs [nq][k] with
+// padded tails, out_counts[q] their number.
+hipError_t launch_like_strip(const int64_t* l_lab, const float* l_dist, const double* l_d64, const int32_t* l_cnt, int32_t nq,
+                             int32_t fetch, const int64_t* ex_labels, const int64_t* ex_offsets, int32_t exclude, int32_t k,
+                             int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64, hipStream_t s);
 
 // ---------------------------------------------------------------- facet counts and histograms (kernels_facet.hip)
 constexpr int kFacetLdsSlots = 4096;  // per-block table of the value kernel: int64 key + uint32 count = 48 KiB, three blocks per CU

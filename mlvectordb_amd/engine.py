@@ -448,6 +448,42 @@ class HipScanEngine:
             rank.ctypes.data, objective.ctypes.data), "search_batch_mmr")
         return labels, dist, counts, d64, rank, objective
 
+    # -- search by stored examples (include/mlvdb_like.h) -----------------------------------
+    def search_like(self, labels: np.ndarray, weights: np.ndarray, offsets: np.ndarray, k: int, *, base=None,
+                    exclude: bool = True, where=None, want64: bool = False, want_queries: bool = False):
+        """kNN with queries built on the device from stored rows: query ``i`` is ``base[i]`` (when given) plus
+        ``weights[j]`` times the stored row ``labels[j]`` -- the unit vector of that row on a cosine index -- over
+        ``j = offsets[i] .. offsets[i + 1] - 1`` (<= 64 per query), summed in fp64 and rounded to fp32 once.  With ``exclude``
+        the examples of a query are taken out of its hits on the device (the inner search fetches ``k`` + the most distinct
+        examples of a query, <= 1024); ``where`` (a compiled ``where.Program``) restricts the rows searched, not the
+        examples.  Returns (labels int64 [nq, k], dist float32, counts int32, dist64 float64 or ``None`` without
+        ``want64``, queries float32 [nq, dim] or ``None`` without ``want_queries``); padding is label -1 / +inf."""
+        ex_labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        ex_weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        ex_offsets = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+        if ex_offsets.size < 1 or ex_labels.size != ex_weights.size:
+            raise RuntimeError(f"search_like: {ex_labels.size} labels, {ex_weights.size} weights, {ex_offsets.size} offsets")
+        nq = ex_offsets.size - 1
+        if nq > 0 and ex_offsets[-1] > ex_labels.size:
+            raise RuntimeError(f"search_like: the offsets end at {int(ex_offsets[-1])}, there are {ex_labels.size} examples")
+        if base is not None:
+            base = np.ascontiguousarray(base, dtype=np.float32)
+            if base.shape != (nq, self.dim):
+                raise RuntimeError(f"Wrong dimensionality of the vectors: got {base.shape}, index dim {self.dim}, {nq} queries")
+        k = int(k)
+        out_labels = np.empty((nq, max(k, 0)), dtype=np.int64)
+        dist = np.empty((nq, max(k, 0)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.int32)
+        d64 = np.empty((nq, max(k, 0)), dtype=np.float64) if want64 else None
+        queries = np.empty((nq, self.dim), dtype=np.float32) if want_queries else None
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_search_batch_like(
+            self._h, ex_labels.ctypes.data, ex_weights.ctypes.data, ex_offsets.ctypes.data,
+            None if base is None else base.ctypes.data, nq, k, 1 if exclude else 0, None if w is None else C.byref(w),
+            out_labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
+            None if queries is None else queries.ctypes.data), "search_batch_like")
+        return out_labels, dist, counts, d64, queries
+
     # -- facet counts and histograms (include/mlvdb_facet.h) ---------------------------
     def facet_values(self, attr: int, max_values: int, where=None):
         """The distinct present values of int64 column ``attr`` among the live rows (those the compiled ``where.Program``

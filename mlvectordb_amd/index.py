@@ -25,6 +25,7 @@ aggregated there (``facets`` / ``histogram``).
 from __future__ import annotations
 
 import json
+import math
 import os
 from dataclasses import dataclass
 from collections.abc import Sequence as SequenceABC
@@ -662,6 +663,97 @@ class Index:
         fetch = min(fetch_k, active)  # (>= k: fetch_k >= top_k)
         labels, dist, counts = search_mmr(q, k, fetch, lam, where=program)[:3]
         return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
+
+    _MAX_LIKE_EXAMPLES = 64  # MLVDB_LIKE_MAX_EXAMPLES: one example per lane of the strip's wavefront
+    _MAX_LIKE_FETCH = 1024   # MLVDB_LIKE_MAX_FETCH: top_k + the most examples of one query
+
+    @staticmethod
+    def _like_groups(groups, what: str) -> List[list]:
+        """``positive`` / ``negative`` / ``weights`` as one list per query; a flat sequence (of UUIDs, of numbers) is one query."""
+        if isinstance(groups, (UUID, str, bytes)) or not isinstance(groups, (SequenceABC, np.ndarray)):
+            raise ValueError(f"search_like: {what} must be a sequence with one sequence per query (or one flat sequence)")
+        rows = list(groups)
+        if rows and not any(isinstance(r, (SequenceABC, np.ndarray)) and not isinstance(r, (str, bytes)) for r in rows):
+            return [rows]
+        for r in rows:
+            if isinstance(r, (UUID, str, bytes)) or not isinstance(r, (SequenceABC, np.ndarray)):
+                raise ValueError(f"search_like: {what} mixes per-query sequences with single entries")
+        return [list(r) for r in rows]
+
+    @staticmethod
+    def like_weights(n_positive: int, n_negative: int) -> Tuple[float, float]:
+        """The default "average vector" rule, in Python floats: (weight of each positive, weight of each negative) --
+        ``1/|P|`` without negatives, else ``2/|P|`` and ``-1/|N|``: ``mean(P) + (mean(P) - mean(N))``."""
+        if n_negative == 0:
+            return (1.0 / n_positive if n_positive else 0.0), 0.0
+        return (2.0 / n_positive if n_positive else 0.0), -1.0 / n_negative
+
+    def search_like(self, positive, top_k: int, namespace: str, metric: str, *, negative=None, queries=None, weights=None,
+                    exclude_examples: bool = True, where: Optional[Mapping] = None) -> BatchHits:
+        """Additive: "more like this" -- kNN around stored vectors named by id, built and searched on the device
+        (include/mlvdb_like.h): the rows never leave HBM.
+
+        ``positive`` (and the optional ``negative``) hold ``nq`` entries, each a sequence of UUIDs of stored vectors; a
+        flat sequence of UUIDs means one query.  Query ``i`` is the weighted sum of its examples -- of their unit vectors
+        in a cosine namespace -- positives first, then negatives, each summed as often as it is named: every positive
+        weighs ``1/|P|`` without negatives, ``2/|P|`` with them and every negative ``-1/|N|`` (``mean(P) + (mean(P) -
+        mean(N))``).  ``weights=`` (the shape of ``positive``) gives explicit per-example numbers instead and cannot be
+        combined with ``negative``.  ``queries=`` (``[nq, dim]`` or a sequence of ``VectorDTO``) is an optional base batch
+        the examples are added to, e.g. the embedding of a text query.  With ``exclude_examples`` (the default) a query's
+        examples never come back among its hits; at most 64 examples per query and ``top_k`` + examples <= 1024.  ``where``
+        (one dict filter) restricts the rows searched, not the examples.  Every refusal happens before the engine is
+        touched; hits and scores are otherwise those of ``search_many`` for the same query vectors."""
+        if self._devices is not None and len(self._devices) > 1:
+            raise ValueError("search_like is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        if isinstance(where, (list, tuple)):
+            raise ValueError("search_like: a per-query where list is not supported, give one dict filter")
+        if weights is not None and negative is not None:
+            raise ValueError("search_like: weights= gives every example its own number and cannot be combined with negative=")
+        pos = self._like_groups(positive, "positive")
+        nq = len(pos)
+        neg = [[] for _ in range(nq)] if negative is None else self._like_groups(negative, "negative")
+        if len(neg) != nq:
+            raise ValueError(f"search_like: {nq} positive entries, {len(neg)} negative entries")
+        if weights is not None:
+            given = self._like_groups(weights, "weights")
+            if [len(g) for g in given] != [len(p) for p in pos]:
+                raise ValueError("search_like: weights must hold one number per positive id")
+            per_example = [float(x) for g in given for x in g]
+            if not all(math.isfinite(x) for x in per_example):
+                raise ValueError("search_like: weights must be finite")
+        else:
+            per_example = []
+            for p, n in zip(pos, neg):
+                wp, wn = self.like_weights(len(p), len(n))
+                per_example += [wp] * len(p) + [wn] * len(n)
+        examples = [p + n for p, n in zip(pos, neg)]
+        for i, e in enumerate(examples):
+            if len(e) > self._MAX_LIKE_EXAMPLES:
+                raise ValueError(f"search_like: query {i} names {len(e)} examples, at most {self._MAX_LIKE_EXAMPLES} are supported")
+            if not e and queries is None:
+                raise ValueError(f"search_like: query {i} has no example and there is no queries= batch to start from")
+        most = max((len(set(e)) for e in examples), default=0)
+        if top_k + most > self._MAX_LIKE_FETCH:
+            raise ValueError(f"search_like: top_k + examples must be <= {self._MAX_LIKE_FETCH} (got {top_k} + {most})")
+        program = None if where is None else self._compile(namespace, where)
+        base = None if queries is None else self._coerce_queries(queries)
+        if base is not None and base.shape[0] != nq:
+            raise ValueError(f"search_like: {nq} positive entries, {base.shape[0]} queries")
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or (base is not None and base.shape[1] != ns.dim):
+            return BatchHits.empty(nq)
+        flat = [u for e in examples for u in e]
+        labels = ns.ids.lookup(flat) if flat else np.zeros(0, np.int64)
+        if (labels < 0).any():
+            raise ValueError(f"search_like: id {flat[int(np.argmax(labels < 0))]} is unknown or removed in namespace {namespace!r}")
+        search_like = getattr(ns.engine, "search_like", None)
+        if search_like is None:
+            raise ValueError("search_like needs an engine with search_like (a single-device namespace)")
+        offsets = np.concatenate([[0], np.cumsum([len(e) for e in examples])]).astype(np.int64)
+        k = min(int(top_k), ns.total - ns.deleted)  # as search_many clamps top_k (the reference clamps to the live count)
+        out_labels, dist, counts = search_like(labels, np.asarray(per_example, np.float64), offsets, k, base=base,
+                                               exclude=bool(exclude_examples), where=program)[:3]
+        return BatchHits(out_labels, self._scores(dist, metric), counts, ns.ids)
 
     def _compile_each(self, namespace: str, wheres) -> Tuple[list, np.ndarray]:
         for w in wheres:

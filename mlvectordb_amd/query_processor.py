@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 from collections.abc import Mapping
-from typing import Any, Dict, Iterable, List, Sequence
+from typing import Any, Dict, Iterable, List, Optional, Sequence
 from uuid import UUID
 
 from .interfaces import IndexProtocol, VectorDTO
@@ -107,6 +107,27 @@ class QueryProcessor:
                                            distinct=distinct)
             return self._enrich_many(hits, namespace)
         return self._enrich_many(self._search_many(queries, top_k, namespace, metric, where), namespace)
+
+    def find_similar_to(self, positive_ids: Sequence[UUID], top_k: int, namespace: str = "default", metric: str = "cosine", *,
+                        negative_ids: Optional[Sequence[UUID]] = None, query=None, where=None) -> List[dict]:
+        """Additive: "more like this" -- the neighbours of stored vectors named by id (``Index.search_like``): of the mean
+        of ``positive_ids``, pushed away from the mean of ``negative_ids`` when given, on top of ``query`` (a ``VectorDTO``
+        or a row of values, e.g. a text query's embedding) when given.  The named vectors never come back as hits; the
+        query is built and searched on the device.  ``where`` is ``None`` or one dict filter."""
+        queries = None if query is None else np.asarray(getattr(query, "values", query), dtype=np.float32)[None, :]
+        return self.find_similar_to_many([list(positive_ids)], top_k, namespace, metric, queries=queries, where=where,
+                                         negative_ids=None if negative_ids is None else [list(negative_ids)])[0]
+
+    def find_similar_to_many(self, positive_ids, top_k: int, namespace: str = "default", metric: str = "cosine", *,
+                             negative_ids=None, queries=None, where=None) -> List[List[dict]]:
+        """Batched ``find_similar_to``: one sequence of ids per query (``Index.search_like``)."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("find_similar_to: where must be one dict filter (or None)")
+        if not hasattr(self._index, "search_like"):
+            raise ValueError("find_similar_to needs an index with search_like")
+        hits = self._index.search_like(positive_ids, top_k, namespace, metric, negative=negative_ids, queries=queries,
+                                       where=where)
+        return self._enrich_many(hits, namespace)
 
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
         if where is None:
