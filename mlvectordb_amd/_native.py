@@ -157,6 +157,14 @@ LIKE_SIGNATURES = {
                                           _P, _P, _P, _P, _P]),
 }
 
+# include/mlvdb_maxsim.h: late-interaction search -- documents ranked by the summed best-row distance of a query's tokens
+MAXSIM_MAX_TOKENS = 128
+MAXSIM_MAX_GROUPS = FACET_MAX_VALUES
+MAXSIM_SIGNATURES = {
+    "mlvdb_search_batch_maxsim": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Where),
+                                            _P, _P, _P, _P, _P, _P]),
+}
+
 # include/mlvdb_mutate.h: attribute values set by label, rows updated / tombstoned by filter
 SET_ASSIGN = 0
 SET_ADD = 1
@@ -197,7 +205,8 @@ def load() -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
-                                      **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MUTATE_SIGNATURES}.items():
+                                      **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
+                                      **MUTATE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <memory>
 #include <mutex>
 #include <new>
 
@@ -158,6 +159,10 @@ struct mlvdb_index {
     // lists of the inner search and the stripped outputs -- sized by the chunk (<= kLikeChunk queries), k and the example
     // counts, never by the corpus
     DevBuf like_q, like_ex, like_list, like_out;
+    // late-interaction search (mlvdb_maxsim.h): the code table of the call's documents with their dense ids, the dense id of
+    // every row (4 B per row), the [token, document] keys of a chunk of queries (<= MAXSIM_WS_MB MiB, or one query's), the
+    // chunk's token offsets and its ranked outputs
+    DevBuf ms_tab, ms_rowdoc, ms_best, ms_misc, ms_out;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -1218,6 +1223,7 @@ int mlvdb_index_destroy(mlvdb_index* h) {
                       &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel,
                       &h->grp_tab, &h->grp_tiles, &h->grp_out, &h->grp_lab,
                       &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->like_q, &h->like_ex, &h->like_list, &h->like_out,
+                      &h->ms_tab, &h->ms_rowdoc, &h->ms_best, &h->ms_misc, &h->ms_out,
                       &h->facet_tab, &h->facet_misc, &h->order_ws, &h->mutate_ws})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
@@ -3490,6 +3496,196 @@ int mlvdb_facet_bins(mlvdb_index* h, int32_t attr, const mlvdb_where* where, con
     for (int32_t i = 0; i <= n_edges; ++i) out_counts[i] = 0;
     if (h->total == 0) return MLVDB_OK;
     return facet_bins_impl(h, attr, where, edges, n_edges, out_counts, matched, absent);
+    });
+}
+
+// ---- late-interaction search (mlvdb_maxsim.h)
+extern "C++" {
+namespace {
+// padding of queries [q0, q0 + n) of a late-interaction call and of their tokens' match rows, on the host
+void maxsim_pad(const int64_t* off, int64_t q0, int64_t n, int32_t k, int64_t* out_groups, float* out_score, int32_t* out_counts,
+                double* out_score64, int64_t* out_match_labels, double* out_match_dist64) {
+    for (int64_t i = q0 * k; i < (q0 + n) * k; ++i) {
+        out_groups[i] = INT64_MIN;
+        out_score[i] = __builtin_inff();
+        if (out_score64) out_score64[i] = __builtin_inf();
+    }
+    for (int64_t i = q0; i < q0 + n; ++i) out_counts[i] = 0;
+    for (int64_t i = off[q0] * k; i < off[q0 + n] * k; ++i) {
+        if (out_match_labels) out_match_labels[i] = -1;
+        if (out_match_dist64) out_match_dist64[i] = __builtin_inf();
+    }
+}
+
+// The validated call (h->rn is the masked copy when a program restricts the rows): the documents and their table, the dense
+// id of every row, then per chunk of queries the [token, document] scan, the ranking and -- when asked for -- the matches by
+// the member stage of the grouped search, its queries being the chunk's tokens and its groups each token's query's documents.
+int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t nq, int32_t k, int32_t attr, int32_t qt_max,
+                int64_t* out_groups, float* out_score, int32_t* out_counts, double* out_score64, int64_t* out_match_labels,
+                double* out_match_dist64) {
+    hipStream_t s = h->stream;
+    auto pad = [&](int64_t q0, int64_t n) {
+        maxsim_pad(off, q0, n, k, out_groups, out_score, out_counts, out_score64, out_match_labels, out_match_dist64);
+    };
+    if (h->total == 0 || h->total == h->deleted) {
+        pad(0, nq);
+        return MLVDB_OK;
+    }
+    if (int rc = begin_call(h, s)) return rc;
+    // 1. the documents: the present codes among the counted rows, ascending -- a document's dense id is its rank in that
+    // order, so a tie on the dense id is a tie on the group code
+    const int64_t* col = h->attr_col[attr];
+    std::unique_ptr<int64_t[]> codes(new int64_t[kMaxsimMaxGroups]), rows_of(new int64_t[kMaxsimMaxGroups]);
+    int64_t G = 0, matched = 0, absent = 0;
+    if (int rc = facet_values_impl(h, attr, nullptr, kMaxsimMaxGroups, codes.get(), rows_of.get(), &G, &matched, &absent))
+        return rc == MLVDB_ERR_OVERFLOW ? fail(h, rc, "maxsim: more than MLVDB_MAXSIM_MAX_GROUPS documents") : rc;
+    rows_of.reset();
+    if (G == 0) {  // every counted row's value is absent
+        pad(0, nq);
+        return end_call(h, s);
+    }
+    // the open-addressing table, as grouped_members builds it, and the dense id of every slot
+    uint64_t slots = 1;
+    while (slots < 2 * (uint64_t)G) slots *= 2;
+    {
+        std::vector<int64_t> keys(slots, INT64_MIN);
+        std::vector<int32_t> dense(slots, -1);
+        for (int64_t u = 0; u < G; ++u) {
+            uint64_t at = facet_hash(codes[u]) & (slots - 1);
+            while (keys[at] != INT64_MIN) at = (at + 1) & (slots - 1);
+            keys[at] = codes[u];
+            dense[at] = (int32_t)u;
+        }
+        HIP_TRY(h, h->ms_tab.ensure(slots * (sizeof(int64_t) + sizeof(int32_t))));  // [keys | dense ids]
+        HIP_TRY(h, h->ms_rowdoc.ensure((size_t)h->total * sizeof(int32_t)));
+        Carver tab{h->ms_tab.as<char>()};
+        long long* keys_d = tab.take<long long>(slots);
+        int32_t* dense_d = tab.take<int32_t>(slots);
+        HIP_TRY(h, hipMemcpyAsync(keys_d, keys.data(), slots * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(dense_d, dense.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        // 2. the dense id of every row: every later pass reads this instead of norm + code + probe
+        HIP_TRY(h, launch_maxsim_slot(h->rn, col, h->total, keys_d, slots, dense_d, h->ms_rowdoc.as<int32_t>(), s));
+        HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
+    }
+    const int64_t budget = (int64_t)std::max(1, h->tn.maxsim_ws_mb) << 20;
+    const bool want_matches = out_match_labels || out_match_dist64;
+    std::vector<int32_t> tok_off;
+    std::vector<int64_t> dense_out, grp;
+    std::vector<int32_t> cnt, tcnt;
+    for (int64_t q0 = 0; q0 < nq;) {
+        // the chunk: queries while their cells fit the budget and their tokens the chunk, always at least one
+        int64_t q1 = q0 + 1;
+        while (q1 < nq && (off[q1 + 1] - off[q0]) * G * (int64_t)sizeof(unsigned long long) <= budget &&
+               off[q1 + 1] - off[q0] <= kMaxsimChunkTokens)
+            ++q1;
+        const int32_t n = (int32_t)(q1 - q0), ntok = (int32_t)(off[q1] - off[q0]);
+        const size_t nk = (size_t)n * k;
+        const float* chunk_tokens = tokens + (size_t)off[q0] * h->dim;
+        tok_off.resize((size_t)n + 1);
+        for (int32_t i = 0; i <= n; ++i) tok_off[(size_t)i] = (int32_t)(off[q0 + i] - off[q0]);
+        HIP_TRY(h, h->dist_q.ensure((size_t)ntok * h->dim * sizeof(float)));
+        HIP_TRY(h, h->qpad.ensure((size_t)ntok * h->ld * sizeof(float)));
+        HIP_TRY(h, h->qaux.ensure((size_t)ntok * sizeof(double)));
+        HIP_TRY(h, h->ms_best.ensure((size_t)ntok * G * sizeof(unsigned long long)));
+        HIP_TRY(h, h->ms_misc.ensure(((size_t)n + 1) * sizeof(int32_t)));
+        HIP_TRY(h, h->ms_out.ensure(ListBlock::bytes(nk, (size_t)n)));
+        const ListBlock o(h->ms_out.p, nk, (size_t)n);  // (its labels: dense ids)
+        unsigned long long* best = h->ms_best.as<unsigned long long>();
+        HIP_TRY(h, hipMemcpyAsync(h->dist_q.p, chunk_tokens, (size_t)ntok * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(h->ms_misc.p, tok_off.data(), ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemsetAsync(best, 0xff, (size_t)ntok * G * sizeof(unsigned long long), s));
+        HIP_TRY(h, launch_query_prep(h->dist_q.as<float>(), ntok, h->dim, h->ld, h->space, h->qpad.as<float>(),
+                                     h->qaux.as<double>(), nullptr, s));
+        // 3. the scan
+        const ExactPlan plan = plan_exact(h->total, h->ld, ntok, k);
+        MaxsimArgs a{};
+        a.X = h->X;
+        a.row_doc = h->ms_rowdoc.as<int32_t>();
+        a.total = h->total;
+        a.ld = h->ld;
+        a.space = h->space;
+        a.Qpad = h->qpad.as<float>();
+        a.qaux = h->qaux.as<double>();
+        a.ntok = ntok;
+        a.ndocs = (int32_t)G;
+        a.best = best;
+        if (int rc = scan_step(h, s, h->total * plan.nqtiles, [&] { return launch_maxsim_scan(a, plan, s); })) return rc;
+        h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+        // 4. the ranking: dense ids, fp32 / fp64 scores and counts
+        const int32_t rblk = maxsim_rank_blocks((int32_t)G);
+        HIP_TRY(h, h->partial.ensure(nk * rblk * sizeof(TopEntry)));
+        HIP_TRY(h, launch_maxsim_rank(best, h->ms_misc.as<int32_t>(), n, (int32_t)G, k, rblk, h->partial.as<TopEntry>(), s));
+        HIP_TRY(h, launch_exact_merge(h->partial.as<TopEntry>(), n, nullptr, nullptr, rblk, k, o.lab, o.dist, o.cnt, o.d64, s));
+        dense_out.resize(nk);
+        cnt.resize((size_t)n);
+        const size_t at = (size_t)q0 * k;
+        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
+        HIP_TRY(h, hipMemcpyAsync(dense_out.data(), o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(cnt.data(), o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_score + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out_score64) HIP_TRY(h, hipMemcpyAsync(out_score64 + at, o.d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        for (size_t i = 0; i < nk; ++i) out_groups[at + i] = dense_out[i] >= 0 ? codes[(size_t)dense_out[i]] : INT64_MIN;
+        std::memcpy(out_counts + q0, cnt.data(), (size_t)n * sizeof(int32_t));
+        // 5. the matches: the member stage (grouped_members) over at most 1024 tokens per call, group_size 1
+        for (int32_t t0 = 0; want_matches && t0 < ntok; t0 += (int32_t)kDistinctChunk) {
+            const int32_t nt = std::min<int32_t>((int32_t)kDistinctChunk, ntok - t0);
+            const size_t ntk = (size_t)nt * k;
+            grp.assign(ntk, INT64_MIN);
+            tcnt.assign((size_t)nt, 0);
+            int32_t qi = (int32_t)(std::upper_bound(tok_off.begin(), tok_off.end(), t0) - tok_off.begin()) - 1;
+            for (int32_t t = 0; t < nt; ++t) {
+                while (tok_off[(size_t)qi + 1] <= t0 + t) ++qi;  // the query of token t0 + t
+                tcnt[(size_t)t] = cnt[(size_t)qi];
+                std::copy(out_groups + at + (size_t)qi * k, out_groups + at + ((size_t)qi + 1) * k, grp.begin() + (size_t)t * k);
+            }
+            // (h->dist_q holds the member stage's queries from row 0 on)
+            if (t0 > 0 || nt < ntok)
+                HIP_TRY(h, hipMemcpyAsync(h->dist_q.p, chunk_tokens + (size_t)t0 * h->dim, (size_t)nt * h->dim * sizeof(float),
+                                          hipMemcpyHostToDevice, s));
+            if (int rc = grouped_members(h, nt, k, 1, qt_max, col, grp.data(), tcnt.data())) return rc;
+            const ListBlock m(h->grp_out.p, ntk, ntk);  // [d64 | labels | dist | group counts], as grouped_members left it
+            const size_t mat = ((size_t)off[q0] + (size_t)t0) * k;
+            if (out_match_labels) HIP_TRY(h, hipMemcpyAsync(out_match_labels + mat, m.lab, ntk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            if (out_match_dist64) HIP_TRY(h, hipMemcpyAsync(out_match_dist64 + mat, m.d64, ntk * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_TRY(h, hipStreamSynchronize(s));
+        }
+        q0 = q1;
+    }
+    return end_call(h, s);
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_maxsim(mlvdb_index* h, const float* tokens, const int64_t* token_offsets, int64_t nq, int32_t k,
+                              int32_t attr, const mlvdb_where* where, int64_t* out_groups, float* out_score,
+                              int32_t* out_counts, double* out_score64, int64_t* out_match_labels, double* out_match_dist64) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked on the host before anything is launched (the program: with_where)
+    if ((rc = attr_check(h, attr))) return rc;
+    if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "maxsim needs an int64 column");
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "maxsim: k above MLVDB_MAX_TOPK");
+    if (nq > 0 && (!tokens || !token_offsets || !out_groups || !out_score || !out_counts))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (nq > 0 && token_offsets[0] != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "maxsim: token_offsets must start at 0");
+    for (int64_t i = 0; i < nq; ++i) {
+        if (token_offsets[i + 1] <= token_offsets[i])
+            return fail(h, MLVDB_ERR_INVALID_ARG, "maxsim: token_offsets must be strictly increasing (a query without tokens)");
+        if (token_offsets[i + 1] - token_offsets[i] > kMaxsimMaxTokens)
+            return fail(h, MLVDB_ERR_INVALID_ARG, "maxsim: more than MLVDB_MAXSIM_MAX_TOKENS tokens in a query");
+    }
+    const int32_t qt = gather_qt(h);  // pairs per tile of the member stage's gathered kernel
+    if ((out_match_labels || out_match_dist64) && where_gather_lds(qt, h->ld) > 64 * 1024)
+        return fail(h, MLVDB_ERR_UNSUPPORTED, "maxsim: the matches of one token of this dimension need more than 64 KiB of LDS");
+    auto call = [&]() {
+        return maxsim_impl(h, tokens, token_offsets, nq, k, attr, qt, out_groups, out_score, out_counts, out_score64,
+                           out_match_labels, out_match_dist64);
+    };
+    return with_where(h, where, nq, call);
     });
 }
 

@@ -18,6 +18,7 @@
 #include "../../include/mlvdb_order.h"
 #include "../../include/mlvdb_mmr.h"
 #include "../../include/mlvdb_like.h"
+#include "../../include/mlvdb_maxsim.h"
 #include "../../include/mlvdb_mutate.h"
 #include "layout.h"
 #include "wave_topk.h"
@@ -97,7 +98,8 @@ inline hipError_t with_space_qt(int32_t space, int32_t qt, F&& f) {
     X(scan_nqt, "SCAN_NQT", 0)         /* query tiles of the int8 body: 0 = by batch size, else 4 / 8 / 16 */          \
     X(l2_offset_cache, "L2_OFFSET_CACHE", 1) /* l2: keep the offsets plane across passes of the same scale (0: recompute per pass) */ \
     X(where_gather, "WHERE_GATHER", 150) /* per-query filters: gather a program's rows when matches x query tiles x 1000 <= live x this (0: never; tools/where_each_ab.py) */ \
-    X(distinct_oversample, "DISTINCT_OVERSAMPLE", 4) /* distinct kNN: the list pass ranks min(1024, max(64, this x k)) rows per query (0: no list pass, every query takes the grouped exact scan; tools/distinct_ab.py) */
+    X(distinct_oversample, "DISTINCT_OVERSAMPLE", 4) /* distinct kNN: the list pass ranks min(1024, max(64, this x k)) rows per query (0: no list pass, every query takes the grouped exact scan; tools/distinct_ab.py) */ \
+    X(maxsim_ws_mb, "MAXSIM_WS_MB", 1024) /* late interaction: MiB of the [token, document] workspace one chunk of queries may take (always at least one query; every setting returns the same bytes) */
 
 struct Tuning {
 #define X(field, name, dflt) int field = dflt;
@@ -507,6 +509,34 @@ hipError_t launch_like_query(const float* X, int32_t dim, int32_t ld, int32_t sp
 hipError_t launch_like_strip(const int64_t* l_lab, const float* l_dist, const double* l_d64, const int32_t* l_cnt, int32_t nq,
                              int32_t fetch, const int64_t* ex_labels, const int64_t* ex_offsets, int32_t exclude, int32_t k,
                              int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64, hipStream_t s);
+
+// ---------------------------------------------------------------- late-interaction search (kernels_maxsim.hip)
+constexpr int kMaxsimMaxTokens = MLVDB_MAXSIM_MAX_TOKENS;
+constexpr int kMaxsimMaxGroups = MLVDB_MAXSIM_MAX_GROUPS;
+constexpr int kMaxsimChunkTokens = 4096;  // most tokens of one chunk of queries, whatever the workspace budget allows
+struct MaxsimArgs {
+    const float* X;
+    const int32_t* row_doc;    // [total] dense id of the row's document, -1 = not counted
+    int64_t total;
+    int32_t ld;
+    int32_t space;
+    const float* Qpad;         // [ntok][ld] the chunk's tokens, prepared as queries
+    const double* qaux;        // [ntok]
+    int32_t ntok;
+    int32_t ndocs;             // G
+    unsigned long long* best;  // [ntok][G] order keys of the best distances, preset to all ones
+};
+// row_doc[i] for i < total: keys / dense = the host-built code table (group_table.h) and the dense id of every slot
+hipError_t launch_maxsim_slot(const float* rn, const int64_t* col, int64_t total, const long long* keys, uint64_t slots,
+                              const int32_t* dense, int32_t* row_doc, hipStream_t s);
+// the exact scan's geometry (p = plan_exact(total, ld, ntok, k)) with the [token, document] minimum as its sink
+hipError_t launch_maxsim_scan(const MaxsimArgs& a, const ExactPlan& p, hipStream_t s);
+// blocks per query of the rank kernel
+int32_t maxsim_rank_blocks(int32_t ndocs);
+// query q of nq <= 65535: tokens tok_off[q] .. tok_off[q + 1] of `best`; partial[(q * nblk + block) * k ..] = the block's k
+// smallest (score, dense id), the input of launch_exact_merge
+hipError_t launch_maxsim_rank(const unsigned long long* best, const int32_t* tok_off, int32_t nq, int32_t ndocs, int32_t k,
+                              int32_t nblk, TopEntry* partial, hipStream_t s);
 
 // ---------------------------------------------------------------- facet counts and histograms (kernels_facet.hip)
 constexpr int kFacetLdsSlots = 4096;  // per-block table of the value kernel: int64 key + uint32 count = 48 KiB, three blocks per CU

@@ -37,4 +37,36 @@ __device__ __forceinline__ void wave_peel_add(bool has, int64_t key, Add&& add) 
     if (adds || has) add(key, mine);
 }
 
+// The same peel for a minimum (kernels_maxsim.hip): the lanes that hold the first active lane's key fold their values into
+// one unsigned minimum, which the leading lane hands to put(key, minimum) -- one call per key instead of one per lane, by
+// the rounds and the early end of wave_peel_add.  Only lanes below WIDTH (a power of two) may have `has` set: the fold is a
+// butterfly over xor 1 .. WIDTH / 2, which stays inside those lanes.  Every lane of the wave must call this.
+template <int WIDTH, class Put>
+__device__ __forceinline__ void wave_peel_min(bool has, int32_t key, unsigned long long value, Put&& put) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long mine = value;  // what this lane puts under its key, if it puts
+    bool puts = false;
+    for (int r = 0; r < kFacetPeelRounds; ++r) {
+        const unsigned long long active = __ballot(has);
+        if (!active) break;
+        const int leader = __ffsll((long long)active) - 1;
+        const int32_t lead = __builtin_amdgcn_readlane(key, leader);
+        const bool same = has && key == lead;
+        const int n = __popcll(__ballot(same));
+        if (n > 1) {
+            unsigned long long m = same ? value : ~0ull;
+#pragma unroll
+            for (int x = 1; x < WIDTH; x <<= 1) {
+                const unsigned long long o = (unsigned long long)__shfl_xor((long long)m, x);
+                m = o < m ? o : m;
+            }
+            if (lane == leader) mine = m;
+        }
+        if (lane == leader) puts = true;
+        has = has && !same;
+        if (n == 1) break;
+    }
+    if (puts || has) put(key, mine);
+}
+
 }  // namespace mlvdb

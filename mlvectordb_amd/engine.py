@@ -100,6 +100,14 @@ class FacetOverflow(RuntimeError):
         self.max_values, self.n_values, self.matched, self.absent = max_values, n_values, matched, absent
 
 
+class MaxSimOverflow(RuntimeError):
+    """A late-interaction call met more than ``max_groups`` documents among the rows it counts (``MLVDB_ERR_OVERFLOW``)."""
+
+    def __init__(self, max_groups: int) -> None:
+        super().__init__(f"search_maxsim: more than max_groups={max_groups} documents")
+        self.max_groups = max_groups
+
+
 class HipScanEngine:
     """Exhaustive fp32 corpus scan on one MI355X, through the C ABI."""
 
@@ -483,6 +491,42 @@ class HipScanEngine:
             out_labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
             None if queries is None else queries.ctypes.data), "search_batch_like")
         return out_labels, dist, counts, d64, queries
+
+    # -- late-interaction search (include/mlvdb_maxsim.h) -----------------------------------
+    def search_maxsim(self, tokens: np.ndarray, offsets: np.ndarray, k: int, attr: int, where=None,
+                      want_matches: bool = False):
+        """Documents (the present values of int64 column ``attr``) ranked by the summed distance of each query token to the
+        document's best row: query ``i`` is the token rows ``tokens[offsets[i]:offsets[i + 1]]`` (1..128 of them), a
+        document's score the fp64 sum over them, in order, of the smallest distance to a live row of the document (one the
+        compiled ``where.Program`` matches, when given); ascending by (score, group code), ``k`` <= 64.  Returns (groups
+        int64 [nq, k], score float32, counts int32, score64 float64, match_labels int64 [total tokens, k] or ``None``,
+        match_dist64 float64 [total tokens, k] or ``None``): row ``(offsets[i] + t, j)`` of the last two is the best row of
+        query ``i``'s ``j``-th document for its token ``t`` and that pair's distance.  Padding is group INT64_MIN / +inf /
+        label -1.  More than 2**20 documents raise ``MaxSimOverflow``."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.float32)
+        if tokens.ndim != 2 or tokens.shape[1] != self.dim:
+            raise RuntimeError(f"Wrong dimensionality of the vectors: got {tokens.shape}, index dim {self.dim}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+        if offsets.size < 1 or (offsets.size > 1 and offsets[-1] > tokens.shape[0]):
+            raise RuntimeError(f"search_maxsim: {offsets.size} offsets ending at {int(offsets[-1]) if offsets.size else 0}, "
+                               f"{tokens.shape[0]} tokens")
+        nq, k = offsets.size - 1, int(k)
+        ntok = int(offsets[-1]) if nq > 0 else 0
+        groups = np.empty((nq, max(k, 0)), dtype=np.int64)
+        score = np.empty((nq, max(k, 0)), dtype=np.float32)
+        counts = np.empty(nq, dtype=np.int32)
+        score64 = np.empty((nq, max(k, 0)), dtype=np.float64)
+        match_labels = np.empty((ntok, max(k, 0)), dtype=np.int64) if want_matches else None
+        match_d64 = np.empty((ntok, max(k, 0)), dtype=np.float64) if want_matches else None
+        w, keep = self._where(where) if where is not None else (None, None)
+        rc = self._check(self._lib.mlvdb_search_batch_maxsim(
+            self._h, tokens.ctypes.data, offsets.ctypes.data, nq, k, int(attr), None if w is None else C.byref(w),
+            groups.ctypes.data, score.ctypes.data, counts.ctypes.data, score64.ctypes.data,
+            None if match_labels is None else match_labels.ctypes.data,
+            None if match_d64 is None else match_d64.ctypes.data), "search_batch_maxsim", allow=(_native.ERR_OVERFLOW,))
+        if rc == _native.ERR_OVERFLOW:
+            raise MaxSimOverflow(_native.MAXSIM_MAX_GROUPS)
+        return groups, score, counts, score64, match_labels, match_d64
 
     # -- facet counts and histograms (include/mlvdb_facet.h) ---------------------------
     def facet_values(self, attr: int, max_values: int, where=None):

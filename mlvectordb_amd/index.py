@@ -160,6 +160,73 @@ class GroupedBatchHits(BatchHits):
                    np.zeros((nq, 0), dtype=np.int32), np.full((nq, 0), None, dtype=object))
 
 
+@dataclass
+class DocumentResult:
+    value: object  # the document: the decoded value of the ``by`` attribute (``str`` / ``bool`` / ``int``)
+    score: float
+    matches: Optional[List[SearchResult]] = None  # with ``matches=True``: the document's best row per query token, in token order
+
+
+class LateBatchHits(SequenceABC):
+    """What ``search_late`` returns: a sequence of ``nq`` document lists in rank order whose ``DocumentResult`` objects are
+    only built when an entry is read.  The arrays behind it are public:
+
+    ``values``        object [nq, k]   the documents' values decoded (``None`` at padding)
+    ``scores``        float64 [nq, k]  the summed score (sum of cosines for metric "cosine", else the summed distance)
+    ``counts``        int32 [nq]       valid prefix of each row
+    ``offsets``       int64 [nq + 1]   query ``i`` owns token rows ``offsets[i] .. offsets[i + 1]`` of the two below
+    ``match_labels``  int64 [tokens, k]   with ``matches=True``: the label of the best row of the query's ``j``-th document for
+                                          the token (-1 = padding); else ``None``
+    ``match_scores``  float64 [tokens, k] that pair's score (``1 - d`` for metric "cosine"); else ``None``
+    """
+
+    __slots__ = ("values", "scores", "counts", "offsets", "match_labels", "match_scores", "_table", "_rows")
+
+    def __init__(self, values, scores, counts, offsets, table: Optional[IdTable], match_labels=None, match_scores=None) -> None:
+        self.values, self.scores, self.counts, self.offsets = values, scores, counts, offsets
+        self.match_labels, self.match_scores = match_labels, match_scores
+        self._table = table
+        self._rows: Dict[int, List[DocumentResult]] = {}
+
+    @classmethod
+    def empty(cls, lengths: Sequence[int], k: int = 0, matches: bool = False) -> "LateBatchHits":
+        nq = len(lengths)
+        offsets = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))]).astype(np.int64)
+        ntok = int(offsets[-1])
+        return cls(np.full((nq, k), None, dtype=object), np.full((nq, k), np.inf), np.zeros(nq, dtype=np.int32), offsets, None,
+                   np.full((ntok, k), -1, dtype=np.int64) if matches else None, np.full((ntok, k), np.inf) if matches else None)
+
+    def match_ids(self, i: int) -> Optional[np.ndarray]:
+        """object [T_i, counts[i]]: the UUIDs of query ``i``'s matched rows (``None`` without ``matches=True``)."""
+        if self.match_labels is None:
+            return None
+        lab = self.match_labels[int(self.offsets[i]):int(self.offsets[i + 1]), :int(self.counts[i])]
+        return self._table.uuids_at(lab) if self._table is not None else np.full(lab.shape, None, dtype=object)
+
+    def __len__(self) -> int:
+        return int(self.counts.shape[0])
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        row = self._rows.get(i)
+        if row is None:
+            n = int(self.counts[i])
+            ids = self.match_ids(i)
+            t0, t1 = int(self.offsets[i]), int(self.offsets[i + 1])
+            row = []
+            for j, (v, sc) in enumerate(zip(self.values[i, :n].tolist(), self.scores[i, :n].tolist())):
+                found = None if ids is None else [SearchResult(vector_id=u, score=float(ms)) for u, ms in
+                                                  zip(ids[:, j].tolist(), self.match_scores[t0:t1, j].tolist())]
+                row.append(DocumentResult(value=v, score=sc, matches=found))
+            self._rows[i] = row
+        return row
+
+
 EngineFactory = Callable[[int, str], ScanEngine]
 
 
@@ -607,17 +674,99 @@ class Index:
         valid = np.take_along_axis(valid, order, axis=1)
         labels = np.where(valid, np.take_along_axis(labels.reshape(nq, k * g), order, axis=1), -1)
         dist = np.where(valid, np.take_along_axis(dist.reshape(nq, k * g), order, axis=1), np.float32(np.inf))
+        values = self._decode_groups(ns, distinct, kind, codes, ngroups)
+        return GroupedBatchHits(labels, self._scores(dist, metric), sizes.sum(axis=1).astype(np.int32), ns.ids,
+                                sizes.astype(np.int32), values)
+
+    @staticmethod
+    def _decode_groups(ns, name: str, kind: str, codes: np.ndarray, ngroups: np.ndarray) -> np.ndarray:
+        """object [nq, k]: the group codes of attribute ``name`` decoded (``str`` / ``bool`` / ``int``), ``None`` at padding."""
+        nq, k = codes.shape
         values = np.full((nq, k), None, dtype=object)
         have = np.arange(k)[None, :] < ngroups[:, None]
         if kind == "str":
-            words = {code: word for word, code in ns.strings[distinct].items()}
+            words = {code: word for word, code in ns.strings[name].items()}
             values[have] = [words[c] for c in codes[have].tolist()]
         elif kind == "bool":
             values[have] = [bool(c) for c in codes[have].tolist()]
         else:
             values[have] = codes[have].tolist()
-        return GroupedBatchHits(labels, self._scores(dist, metric), sizes.sum(axis=1).astype(np.int32), ns.ids,
-                                sizes.astype(np.int32), values)
+        return values
+
+    _MAX_TOP_K_LATE = 64    # MLVDB_MAX_TOPK: one selection list of a wavefront
+    _MAX_LATE_TOKENS = 128  # MLVDB_MAXSIM_MAX_TOKENS
+
+    @staticmethod
+    def _late_queries(queries) -> List[np.ndarray]:
+        """``queries`` of ``search_late`` as one float32 ``[T_i, dim]`` array per query."""
+        if isinstance(queries, np.ndarray) and queries.ndim == 3:
+            queries = list(queries)
+        if isinstance(queries, np.ndarray) or not isinstance(queries, (SequenceABC, np.ndarray)):
+            raise ValueError("search_late: queries must be a sequence of [T_i, dim] arrays or one [nq, T, dim] array")
+        out = []
+        for i, q in enumerate(queries):
+            a = np.asarray(q, dtype=np.float32)
+            if a.ndim != 2:
+                raise ValueError(f"search_late: query {i} must be a [T, dim] array of token vectors (got shape {a.shape})")
+            out.append(np.ascontiguousarray(a))
+        return out
+
+    def search_late(self, queries, top_k: int, namespace: str, metric: str, by: str, *, where: Optional[Mapping] = None,
+                    matches: bool = False, allowed_ids: Optional[Iterable[UUID]] = None) -> LateBatchHits:
+        """Additive: late-interaction (MaxSim) search on the device (include/mlvdb_maxsim.h).  A query is a bag of token
+        vectors -- ``queries`` is a sequence of ``[T_i, dim]`` arrays (1..128 tokens each) or one ``[nq, T, dim]`` array --
+        and a document is one value of the declared ``int`` / ``str`` / ``bool`` attribute ``by`` (rows without a value are
+        in no document).  A document's distance is the sum, over the query's tokens in order, of the token's distance to
+        the document's nearest live row; the ``top_k`` (<= 64) documents with the smallest sum come back per query, exact,
+        ties to the smaller value code.  Scores, from the fp64 sum: the sum of cosines for metric "cosine" (``T_i`` minus
+        the summed distance), the summed distance itself for "l2" / "ip"; "euclidean" is refused (a root does not
+        distribute over the sum).  ``where`` (one dict filter) restricts the rows first; ``matches=True`` adds, per document
+        and token, the matched row and its score.  Every refusal happens before the engine is touched."""
+        if self._devices is not None and len(self._devices) > 1:
+            raise ValueError("search_late is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        if metric == "euclidean":
+            raise ValueError('search_late: metric "euclidean" is not supported (a root does not distribute over the sum), use "l2"')
+        if by not in self._attributes:
+            raise ValueError(f"search_late: {by!r} is not a declared attribute of this index "
+                             f"(declared: {sorted(self._attributes)})")
+        kind = self._attributes[by]
+        if kind == "float":
+            raise ValueError(f"search_late: attribute {by!r} is a float column; documents need an int, str or bool attribute")
+        if top_k > self._MAX_TOP_K_LATE:
+            raise ValueError(f"search_late: top_k must be <= {self._MAX_TOP_K_LATE} (got {top_k})")
+        if isinstance(where, (list, tuple)):
+            raise ValueError("search_late: a per-query where list is not supported, give one dict filter")
+        if allowed_ids is not None:
+            raise ValueError("search_late: allowed_ids is not supported, give a dict where filter")
+        qs = self._late_queries(queries)
+        lengths = [int(q.shape[0]) for q in qs]
+        ns = self._ns.get(namespace)
+        for i, q in enumerate(qs):
+            if not 1 <= q.shape[0] <= self._MAX_LATE_TOKENS:
+                raise ValueError(f"search_late: query {i} holds {q.shape[0]} tokens, 1 to {self._MAX_LATE_TOKENS} are supported")
+            if q.shape[1] != (ns.dim if ns is not None else qs[0].shape[1]):
+                raise ValueError(f"search_late: query {i} has token vectors of dim {q.shape[1]}, "
+                                 f"expected {ns.dim if ns is not None else qs[0].shape[1]}")
+        program = None if where is None else self._compile(namespace, where)
+        nq = len(qs)
+        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0:
+            return LateBatchHits.empty(lengths, 0, matches)
+        search_maxsim = getattr(ns.engine, "search_maxsim", None)
+        if search_maxsim is None:
+            raise ValueError("search_late needs an engine with search_maxsim (a single-device namespace)")
+        k = min(int(top_k), ns.total - ns.deleted)
+        if kind == "str" and not ns.strings.get(by):  # no string was ever stored: every row is absent
+            return LateBatchHits.empty(lengths, k, matches)
+        attr = list(self._attributes).index(by)
+        offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        codes, _, counts, s64, m_lab, m_d64 = search_maxsim(np.concatenate(qs, axis=0), offsets, k, attr, where=program,
+                                                            want_matches=bool(matches))
+        # the score rule, in fp64 from the fp64 sum: T_i - s is the sum of the tokens' cosines
+        scores = np.asarray(lengths, np.float64)[:, None] - s64 if metric == "cosine" else s64.copy()
+        scores[np.arange(k)[None, :] >= counts[:, None]] = np.inf
+        if m_d64 is not None:
+            m_d64 = np.where(m_lab >= 0, 1 - m_d64, np.inf) if metric == "cosine" else m_d64
+        return LateBatchHits(self._decode_groups(ns, by, kind, codes, counts), scores, counts, offsets, ns.ids, m_lab, m_d64)
 
     _MAX_TOP_K_MMR = 64      # MLVDB_MAX_TOPK
     _MAX_FETCH_K_MMR = 1024  # MLVDB_MMR_MAX_FETCH: the longest candidate list the selection walks

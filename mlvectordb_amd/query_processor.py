@@ -129,6 +129,26 @@ class QueryProcessor:
                                        where=where)
         return self._enrich_many(hits, namespace)
 
+    def find_documents(self, query_tokens, top_k: int, namespace: str, by: str, metric: str = "cosine", where=None,
+                       with_matches: bool = False) -> List[dict]:
+        """Additive: late-interaction (MaxSim) search for one query given as a bag of token vectors (``[T, dim]``, 1..128
+        tokens; ``Index.search_late``): the ``top_k`` (<= 64) documents -- values of the declared attribute ``by`` -- ranked by
+        the sum, over the tokens, of each token's score against the document's best vector.  One dict per document in rank
+        order: ``value``, ``score`` and, with ``with_matches``, ``matches``: per token the matched vector as
+        ``find_similar_many`` returns a hit.  ``where`` is ``None`` or one dict filter."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("find_documents: where must be one dict filter (or None)")
+        if not hasattr(self._index, "search_late"):
+            raise ValueError("find_documents needs an index with search_late")
+        docs = self._index.search_late([query_tokens], top_k, namespace, metric, by, where=where, matches=with_matches)[0]
+        out = []
+        for doc in docs:
+            entry = {"value": doc.value, "score": doc.score}
+            if with_matches:
+                entry["matches"] = self._enrich(doc.matches, namespace)
+            out.append(entry)
+        return out
+
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
         if where is None:
             return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric)

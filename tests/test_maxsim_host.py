@@ -1,0 +1,267 @@
+"""Late-interaction search (include/mlvdb_maxsim.h) without a GPU: the NumPy oracle against the definition in Python floats,
+the refusals of ``Index.search_late`` / ``QueryProcessor.find_documents`` before the engine is touched, what ``Index`` hands
+the engine, the score rule per metric, the surface over an oracle engine, and the C ABI's shape."""
+import ctypes as C
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from mlvectordb_amd import Index, InMemoryStorage, QueryProcessor, Vector, VectorDTO, _native
+from mlvectordb_amd import where as W
+from oracle import exact_scan
+from tests.distinct_helpers import ABSENT, distinct_knn
+from tests.maxsim_helpers import MaxSimOracleEngine, maxsim_brute, maxsim_oracle, offsets_of, oracle_index
+from tests.where_helpers import WhereOracleEngine
+
+ROOT = Path(__file__).resolve().parents[1]
+SCHEMA = {"doc": "int", "title": "str", "flag": "bool", "price": "float"}
+
+
+# ---------------------------------------------------------------- the oracle against the definition
+@pytest.mark.parametrize("space", ["l2", "cosine", "ip"])
+def test_the_oracle_equals_the_brute_force_restatement(space):
+    rng = np.random.default_rng(5)
+    n, d = 300, 24
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    rows[50] = rows[10]
+    groups = rng.integers(-3, 20, n).astype(np.int64)
+    groups[rng.random(n) < 0.1] = ABSENT
+    groups[50] = groups[10]  # two copies inside one document: the lower label is the match
+    allowed = rng.random(n) > 0.1
+    allowed[[10, 50]] = True
+    off = offsets_of([1, 9, 8, 3])
+    toks = rng.standard_normal((int(off[-1]), d)).astype(np.float32)
+    toks[2] = rows[10]
+    dist = exact_scan.exact_distances(toks, rows, space)
+    ndocs = np.unique(groups[allowed & (groups != ABSENT)]).size
+    for k in (1, 5, 64):
+        grp, s64, cnt, ml, md = maxsim_oracle(dist, groups, allowed, off, k)
+        brute = maxsim_brute(dist, groups, allowed, off, k)
+        assert cnt.tolist() == [min(k, ndocs)] * 4
+        for i in range(4):
+            assert len(brute[i]) == cnt[i]
+            for j, (score, code, matches) in enumerate(brute[i]):
+                assert grp[i, j] == code and s64[i, j] == score
+                for t, (dd, row) in enumerate(matches):
+                    assert ml[off[i] + t, j] == row and md[off[i] + t, j] == dd
+            assert (grp[i, cnt[i]:] == ABSENT).all() and np.isinf(s64[i, cnt[i]:]).all()
+            assert (ml[off[i]:off[i + 1], cnt[i]:] == -1).all() and np.isinf(md[off[i]:off[i + 1], cnt[i]:]).all()
+    j = maxsim_oracle(dist, groups, allowed, off, 64)[0][1].tolist().index(int(groups[10]))
+    assert maxsim_oracle(dist, groups, allowed, off, 64)[3][2, j] == 10
+    # one token per query is the distinct search
+    one = offsets_of([1] * int(off[-1]))
+    grp, s64, cnt, ml, md = maxsim_oracle(dist, groups, allowed, one, 7)
+    lab, d64, dc, dg = distinct_knn(dist, groups, allowed, 7)
+    assert np.array_equal(grp, dg) and np.array_equal(cnt, dc) and np.array_equal(ml, lab)
+    assert np.array_equal(s64, d64) and np.array_equal(md, d64)
+    # nothing counted: padding
+    grp, s64, cnt, ml, md = maxsim_oracle(dist, groups, np.zeros(n, bool), off, 3)
+    assert not cnt.any() and (grp == ABSENT).all() and (ml == -1).all() and np.isinf(s64).all() and np.isinf(md).all()
+
+
+def test_the_score_is_the_sequential_sum_not_the_pairwise_one():
+    """Three terms of which (a + b) + c and a + (b + c) differ: the oracle adds in token order from 0.0."""
+    dist = np.array([[1e16], [1.0], [1.0]])
+    grp, s64, _, _, md = maxsim_oracle(dist, np.array([4], np.int64), np.ones(1, bool), offsets_of([3]), 1)
+    assert s64[0, 0] == ((0.0 + 1e16) + 1.0) + 1.0 == 1e16 and 1e16 + (1.0 + 1.0) != 1e16 and md[:, 0].tolist() == [1e16, 1.0, 1.0]
+
+
+# ---------------------------------------------------------------- refusals, before the engine is touched
+class UntouchableEngine(WhereOracleEngine):
+    """Fails the test if a search of any kind reaches the engine."""
+
+    def search(self, *a, **kw):
+        raise AssertionError("the engine was touched")
+
+    search64 = search_maxsim = search
+
+
+def _filled(factory=MaxSimOracleEngine, n=200, d=8, seed=1, space="l2", **kw):
+    rng = np.random.default_rng(seed)
+    index = Index(space=space, engine_factory=factory, attributes=SCHEMA, **kw)
+    metas = [{"doc": int(rng.integers(0, 30)), "title": f"t{int(rng.integers(0, 12))}", "flag": bool(i % 2), "price": float(i)}
+             for i in range(n)]
+    for m in metas[::11]:
+        del m["doc"], m["title"]
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    vecs = [Vector(values=r, metadata=m) for r, m in zip(rows, metas)]
+    index.add(vecs, "ns")
+    return rng, index, vecs, rows, metas
+
+
+def test_late_refusals_are_value_errors_before_the_engine_is_touched():
+    rng, index, vecs, _, _ = _filled(UntouchableEngine)
+    q = [rng.standard_normal((3, 8)).astype(np.float32)]
+    with pytest.raises(ValueError, match='"euclidean" is not supported .* use "l2"'):
+        index.search_late(q, 5, "ns", "euclidean", "doc")
+    with pytest.raises(ValueError, match="'nope' is not a declared attribute"):
+        index.search_late(q, 5, "ns", "l2", "nope")
+    with pytest.raises(ValueError, match="'price' is a float column"):
+        index.search_late(q, 5, "ns", "l2", "price")
+    with pytest.raises(ValueError, match=r"top_k must be <= 64 \(got 65\)"):
+        index.search_late(q, 65, "ns", "l2", "doc")
+    with pytest.raises(ValueError, match="query 1 holds 0 tokens, 1 to 128"):
+        index.search_late([q[0], np.zeros((0, 8), np.float32)], 5, "ns", "l2", "doc")
+    with pytest.raises(ValueError, match="query 0 holds 129 tokens, 1 to 128"):
+        index.search_late([np.zeros((129, 8), np.float32)], 5, "ns", "l2", "doc")
+    with pytest.raises(ValueError, match="query 1 has token vectors of dim 9, expected 8"):
+        index.search_late([q[0], np.zeros((2, 9), np.float32)], 5, "ns", "l2", "doc")
+    with pytest.raises(ValueError, match=r"query 0 must be a \[T, dim\] array"):
+        index.search_late([np.zeros(8, np.float32)], 5, "ns", "l2", "doc")
+    with pytest.raises(ValueError, match="sequence of .* arrays or one"):
+        index.search_late(np.zeros((3, 8), np.float32), 5, "ns", "l2", "doc")
+    with pytest.raises(ValueError, match="per-query where list"):
+        index.search_late(q, 5, "ns", "l2", "doc", where=[{"doc": 1}])
+    with pytest.raises(ValueError, match="allowed_ids is not supported"):
+        index.search_late(q, 5, "ns", "l2", "doc", allowed_ids=[vecs[0].id])
+    with pytest.raises(ValueError, match="not a declared attribute"):
+        index.search_late(q, 5, "ns", "l2", "doc", where={"nope": 1})
+    # nothing to search: empty answers, the engine still untouched
+    assert [len(h) for h in index.search_late(q * 2, 5, "other", "l2", "doc")] == [0, 0]
+    assert [len(h) for h in index.search_late(q, 0, "ns", "l2", "doc", matches=True)] == [0]
+    index.remove([v.id for v in vecs], "ns")
+    assert [len(h) for h in index.search_late(q, 5, "ns", "l2", "doc")] == [0]
+    qp = QueryProcessor(InMemoryStorage(), index)
+    with pytest.raises(ValueError, match="where must be one dict filter"):
+        qp.find_documents(q[0], 5, "ns", "doc", where=lambda m: True)
+
+
+def test_late_on_a_row_sharded_index_or_an_engine_without_it_is_refused():
+    sharded = Index(space="l2", devices=[0, 0], engine_factory=UntouchableEngine)
+    with pytest.raises(ValueError, match="row-sharded"):
+        sharded.search_late([np.zeros((1, 8), np.float32)], 3, "ns", "l2", "doc")
+    _, index, _, _, _ = _filled(WhereOracleEngine)
+    with pytest.raises(ValueError, match="needs an engine with search_maxsim"):
+        index.search_late([np.zeros((1, 8), np.float32)], 3, "ns", "l2", "doc")
+
+
+# ---------------------------------------------------------------- Index / QueryProcessor over the oracle engine
+def test_index_hands_the_engine_offsets_a_clamped_k_the_attribute_index_and_the_program():
+    rng, index, vecs, _, _ = _filled(n=30)
+    engine = index._ns["ns"].engine
+    a, b = rng.standard_normal((3, 8)), rng.standard_normal((1, 8)).astype(np.float32)
+    index.search_late([a, b], 5, "ns", "l2", "title")
+    index.search_late(np.stack([a, a]), 64, "ns", "l2", "flag", where={"doc": {"$lt": 9}}, matches=True)
+    first, second = engine.maxsim_calls
+    assert first["offsets"].tolist() == [0, 3, 4] and first["k"] == 5 and first["attr"] == 1 and first["where"] is None
+    assert first["tokens"].dtype == np.float32 and np.array_equal(first["tokens"], np.vstack([a, b]).astype(np.float32))
+    assert not first["want_matches"]
+    assert second["offsets"].tolist() == [0, 3, 6] and second["k"] == 30 and second["attr"] == 2  # top_k clamps to the live count
+    assert second["want_matches"] and isinstance(second["where"], W.Program)
+    want = W.compile_where({"doc": {"$lt": 9}}, SCHEMA, index._ns["ns"].strings)
+    assert np.array_equal(second["where"].ops, want.ops) and np.array_equal(second["where"].set, want.set)
+
+
+@pytest.mark.parametrize("metric", ["l2", "cosine", "ip"])
+def test_the_score_rule_and_the_decoded_values(metric):
+    rng, index, vecs, rows, metas = _filled(space=metric if metric != "cosine" else "cosine")
+    lengths = [4, 1, 7]
+    off = offsets_of(lengths)
+    toks = rng.standard_normal((int(off[-1]), 8)).astype(np.float32)
+    queries = [toks[off[i]:off[i + 1]] for i in range(3)]
+    dist = exact_scan.exact_distances(toks, rows, metric)
+    for by, code_of in (("doc", lambda m: m.get("doc", ABSENT)), ("flag", lambda m: int(m["flag"])),
+                        ("title", lambda m: index._ns["ns"].strings["title"][m["title"]] if "title" in m else ABSENT)):
+        groups = np.array([code_of(m) for m in metas], np.int64)
+        grp, s64, cnt, ml, md = maxsim_oracle(dist, groups, np.ones(len(metas), bool), off, 6)
+        got = index.search_late(queries, 6, "ns", metric, by, matches=True)
+        assert np.array_equal(got.counts, cnt) and np.array_equal(got.match_labels, ml) and got.offsets.tolist() == off.tolist()
+        for i in range(3):
+            n = int(cnt[i])
+            want = (lengths[i] - s64[i, :n]) if metric == "cosine" else s64[i, :n]
+            assert got.scores[i, :n].tolist() == want.tolist() and np.isinf(got.scores[i, n:]).all()
+            docs = got[i]
+            assert len(docs) == n and [x.score for x in docs] == want.tolist()
+            values = [x.value for x in docs]
+            if by == "flag":
+                assert all(isinstance(v, bool) for v in values) and [int(v) for v in values] == grp[i, :n].tolist()
+            elif by == "title":
+                assert [index._ns["ns"].strings["title"][v] for v in values] == grp[i, :n].tolist()
+            else:
+                assert values == grp[i, :n].tolist() and all(isinstance(v, int) for v in values)
+            for j, x in enumerate(docs):
+                want_m = (1 - md[off[i]:off[i + 1], j]) if metric == "cosine" else md[off[i]:off[i + 1], j]
+                assert [m.vector_id for m in x.matches] == [vecs[r].id for r in ml[off[i]:off[i + 1], j]]
+                assert [m.score for m in x.matches] == want_m.tolist()
+        plain = index.search_late(queries, 6, "ns", metric, by)
+        assert plain.match_labels is None and all(x.matches is None for x in plain[0])
+        assert np.array_equal(plain.scores, got.scores) and np.array_equal(plain.values, got.values)
+
+
+def test_a_str_attribute_without_any_stored_string_answers_no_documents():
+    index = Index(space="l2", engine_factory=UntouchableEngine, attributes={"title": "str"})
+    index.add([Vector(values=[1.0, 2.0], metadata={})], "ns")
+    got = index.search_late([np.ones((2, 2), np.float32)], 3, "ns", "l2", "title", matches=True)
+    assert got.counts.tolist() == [0] and got[0] == [] and got.match_labels.shape == (2, 1)
+
+
+def test_query_processor_find_documents_returns_one_dict_per_document():
+    rng = np.random.default_rng(4)
+    qp = QueryProcessor(InMemoryStorage(), oracle_index({"doc": "int"}, space="cosine"))
+    dtos = [VectorDTO(values=rng.standard_normal(6).tolist(), metadata={"doc": int(i % 9), "i": i}) for i in range(120)]
+    qp.upsert_many(dtos, "ns")
+    rows = np.array([d.values for d in dtos], np.float32)
+    toks = rng.standard_normal((5, 6)).astype(np.float32)
+    dist = exact_scan.exact_distances(toks, rows, "cosine")
+    groups = np.arange(120, dtype=np.int64) % 9
+    grp, s64, cnt, ml, md = maxsim_oracle(dist, groups, np.ones(120, bool), offsets_of([5]), 4)
+    docs = qp.find_documents(toks, 4, "ns", "doc", with_matches=True)
+    assert [x["value"] for x in docs] == grp[0].tolist() and [x["score"] for x in docs] == (5 - s64[0]).tolist()
+    for j, x in enumerate(docs):
+        assert sorted(x) == ["matches", "score", "value"]
+        assert [m["metadata"]["i"] for m in x["matches"]] == ml[:, j].tolist()
+        assert [m["score"] for m in x["matches"]] == (1 - md[:, j]).tolist()
+        assert all(np.array_equal(m["values"], rows[m["metadata"]["i"]]) and m["metadata"]["doc"] == x["value"] for m in x["matches"])
+    plain = qp.find_documents(toks, 4, "ns", "doc", metric="l2")  # (the metric only changes the score rule)
+    assert [sorted(x) for x in plain] == [["score", "value"]] * 4 and [x["score"] for x in plain] == s64[0].tolist()
+    only = qp.find_documents(toks, 9, "ns", "doc", where={"doc": {"$in": [2, 5]}})
+    assert sorted(x["value"] for x in only) == [2, 5]
+    assert qp.find_documents(toks, 4, "other", "doc") == []
+
+
+# ---------------------------------------------------------------- C ABI
+def _header_text():
+    return re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "mlvdb_maxsim.h").read_text(), flags=re.S)
+
+
+def test_maxsim_header_declares_what_the_binding_binds():
+    lib = _native.load()
+    names = sorted(set(re.findall(r"\b(mlvdb_[a-z0-9_]+)\s*\(", _header_text())))
+    assert names == ["mlvdb_search_batch_maxsim"] == sorted(_native.MAXSIM_SIGNATURES)
+    assert hasattr(lib, names[0])
+    params = re.search(r"mlvdb_search_batch_maxsim\((.*?)\);", _header_text(), flags=re.S).group(1).split(",")
+    restype, argtypes = _native.MAXSIM_SIGNATURES[names[0]]
+    assert len(params) == len(argtypes) == 13 and restype is C.c_int
+    assert argtypes[3:6] == [C.c_int64, C.c_int32, C.c_int32] and "token_offsets" in params[2] and "attr" in params[5]
+    assert int(re.search(r"#define MLVDB_MAXSIM_MAX_TOKENS (\d+)", _header_text()).group(1)) == _native.MAXSIM_MAX_TOKENS == 128
+    assert re.search(r"#define MLVDB_MAXSIM_MAX_GROUPS MLVDB_FACET_MAX_VALUES", _header_text())
+    assert _native.MAXSIM_MAX_GROUPS == _native.FACET_MAX_VALUES == 1 << 20
+    assert Index._MAX_LATE_TOKENS == 128 and Index._MAX_TOP_K_LATE == _native.MAX_TOPK
+    assert lib.mlvdb_abi_version() == 7
+
+
+def test_maxsim_entry_refuses_a_null_handle_inside_the_exception_guard():
+    lib = _native.load()
+    buf = (C.c_double * 4)()
+    assert lib.mlvdb_search_batch_maxsim(C.c_void_p(), buf, buf, 1, 1, 0, None, buf, buf, buf, None, None, None) == 1
+    assert b"null index handle" in lib.mlvdb_last_global_error()
+    api = (ROOT / "mlvectordb_amd" / "csrc" / "api.hip").read_text()
+    body = api[api.index("int mlvdb_search_batch_maxsim("):]
+    assert body[body.index("{\n") + 2:].lstrip().startswith("return guarded(")
+
+
+def test_the_maxsim_kernels_and_header_are_in_the_build_and_the_workspace_key_is_known():
+    csrc = ROOT / "mlvectordb_amd" / "csrc"
+    make = (csrc / "Makefile").read_text()
+    assert re.search(r"^SRCS = .*\bkernels_maxsim\.hip\b", make, flags=re.M)
+    assert "mlvdb_maxsim.h" in make and "group_table.h" in make and "-ffp-contract=off" in make
+    kern = (csrc / "kernels_maxsim.hip").read_text()
+    for name in ("maxsim_slot_kernel", "maxsim_scan_kernel", "maxsim_rank_kernel", "accumulate_rows", "finish_distance",
+                 "wave_peel_min", "atomicMin"):
+        assert name in kern, name
+    assert "asm" not in kern
+    internal = (csrc / "internal.h").read_text()
+    assert re.search(r'X\(maxsim_ws_mb, "MAXSIM_WS_MB", 1024\)', internal)
+    assert '#include "../../include/mlvdb_maxsim.h"' in internal
