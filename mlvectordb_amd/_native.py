@@ -175,6 +175,21 @@ MUTATE_SIGNATURES = {
     "mlvdb_tombstone_where": (C.c_int, [_P, C.POINTER(Where), _P, C.c_int64, C.POINTER(C.c_int64)]),
 }
 
+# include/mlvdb_list.h: list-valued attribute columns -- a set of int64 per row, written, read back, filtered and faceted
+ATTR_INT64_LIST = 3
+LIST_ATTR_CODES = {"int64_list": ATTR_INT64_LIST}
+LIST_MAX_LEN = 255
+LIST_SIGNATURES = {
+    "mlvdb_attr_list_set": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P]),
+    "mlvdb_attr_list_set_at": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "mlvdb_attr_list_get": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "mlvdb_attr_list_update_where": (C.c_int, [_P, C.POINTER(Where), C.c_int32, _P, C.c_int32, C.c_int32,
+                                               C.POINTER(C.c_int64)]),
+    "mlvdb_attr_list_stats": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mlvdb_facet_list_values": (C.c_int, [_P, C.c_int32, C.POINTER(Where), C.c_int64, _P, _P, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -206,7 +221,7 @@ def load() -> C.CDLL:
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
-                                      **MUTATE_SIGNATURES}.items():
+                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -142,6 +142,13 @@ struct mlvdb_index {
     int64_t* attr_col[MLVDB_MAX_ATTRS] = {};  // nullptr while capacity == 0
     std::vector<WhereOp> where_ops;
     DevBuf where_prog, where_cnt;
+    // list columns (mlvdb_list.h): per attribute an append-only value pool of list_cap int64, list_used of them allocated
+    // (garbage of overwritten lists included until mlvdb_index_compact repacks it); the block sums of a scan and the CSR of
+    // a read-back
+    int64_t* list_pool[MLVDB_MAX_ATTRS] = {};
+    int64_t list_cap[MLVDB_MAX_ATTRS] = {};
+    int64_t list_used[MLVDB_MAX_ATTRS] = {};
+    DevBuf list_sums, list_out;
     // per-query filters (mlvdb_where_each.h): the call's programs, one 64-bit word per row, per-segment counts / offsets,
     // match totals, the gathered route's label lists, tiles, queries and outputs
     DevBuf each_prog, each_bits, each_seg, each_tot, each_lab, each_tiles, each_q, each_qpad, each_qaux, each_out;
@@ -256,7 +263,7 @@ const TuningField* find_tuning_field(const char* key, size_t len) {
 }
 
 // ---- attribute columns (mlvdb_where.h): the absent sentinel of a column type, and new column buffers for a capacity change
-int64_t attr_absent(int32_t type) { return type == MLVDB_ATTR_INT64 ? INT64_MIN : (int64_t)0x7ff8000000000000ll; }
+int64_t attr_absent(int32_t type) { return type == MLVDB_ATTR_FLOAT64 ? (int64_t)0x7ff8000000000000ll : INT64_MIN; }
 
 void attr_release(int64_t* (&cols)[MLVDB_MAX_ATTRS]) {
     for (int64_t*& c : cols) {
@@ -293,6 +300,74 @@ void attr_commit(mlvdb_index* h, int64_t* (&ncol)[MLVDB_MAX_ATTRS]) {
         h->attr_col[a] = ncol[a];
         ncol[a] = nullptr;
     }
+}
+
+// ---- list columns (mlvdb_list.h): the value pools
+// Room for `extra` more values behind list_used[a]: the pool regrows by doubling, its used part copied.
+int list_pool_reserve(mlvdb_index* h, int a, int64_t extra) {
+    const int64_t need = h->list_used[a] + extra;
+    if (need <= h->list_cap[a]) return MLVDB_OK;
+    const int64_t cap = std::max<int64_t>({need, 2 * h->list_cap[a], 1024});
+    int64_t* np = nullptr;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&np), (size_t)cap * sizeof(int64_t)));
+    hipError_t e = hipSuccess;
+    if (h->list_used[a] > 0)
+        e = hipMemcpyAsync(np, h->list_pool[a], (size_t)h->list_used[a] * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(np);
+        return fail(h, MLVDB_ERR_HIP, "list pool regrowth", e);
+    }
+    if (h->list_pool[a]) (void)hipFree(h->list_pool[a]);
+    h->list_pool[a] = np;
+    h->list_cap[a] = cap;
+    return MLVDB_OK;
+}
+
+// The summed list lengths of n slots (rn != nullptr: of the live rows among them) -> *sum; h->list_sums keeps the scanned
+// block sums launch_list_move reads.  Waits for the stream.
+int list_scan(mlvdb_index* h, const int64_t* slots, const float* rn, int64_t n, int64_t* sum) {
+    *sum = 0;
+    if (n <= 0) return MLVDB_OK;
+    hipStream_t s = h->stream;
+    const int64_t nblocks = (n + kListBlock - 1) / kListBlock;
+    HIP_TRY(h, h->list_sums.ensure((size_t)(nblocks + 1) * sizeof(int64_t)));
+    HIP_TRY(h, launch_list_block_sums(slots, rn, n, h->list_sums.as<int64_t>(), s));
+    HIP_TRY(h, launch_list_scan_sums(h->list_sums.as<int64_t>(), nblocks, s));
+    HIP_TRY(h, hipMemcpyAsync(sum, h->list_sums.as<int64_t>() + nblocks, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MLVDB_OK;
+}
+
+// The pool of list attribute a rebuilt from rows [0, rows) of its column (all of them live: after a compaction), every
+// list copied to a range of its own in row order and the slots rewritten: what overwritten lists left behind is gone, and
+// rows that shared a range no longer do.
+int list_repack(mlvdb_index* h, int a, int64_t rows) {
+    hipStream_t s = h->stream;
+    int64_t sum = 0;
+    if (int rc = list_scan(h, h->attr_col[a], nullptr, rows, &sum)) return rc;
+    int64_t* np = nullptr;
+    if (sum > 0) {
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&np), (size_t)sum * sizeof(int64_t)));
+    }
+    hipError_t e = launch_list_move(h->attr_col[a], rows, h->list_sums.as<int64_t>(), h->list_pool[a], np, h->attr_col[a],
+                                    nullptr, nullptr, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        if (np) (void)hipFree(np);
+        return fail(h, MLVDB_ERR_HIP, "list pool repack", e);
+    }
+    if (h->list_pool[a]) (void)hipFree(h->list_pool[a]);
+    h->list_pool[a] = np;
+    h->list_cap[a] = h->list_used[a] = sum;
+    return MLVDB_OK;
+}
+
+int list_repack_all(mlvdb_index* h, int64_t rows) {
+    for (int a = 0; a < MLVDB_MAX_ATTRS; ++a)
+        if (h->attr_type[a] == MLVDB_ATTR_INT64_LIST && h->attr_col[a])
+            if (int rc = list_repack(h, a, rows)) return rc;
+    return MLVDB_OK;
 }
 
 int reserve_rows(mlvdb_index* h, int64_t rows) {
@@ -1217,6 +1292,7 @@ int mlvdb_index_destroy(mlvdb_index* h) {
                       &h->cur_l})
         b->release();
     attr_release(h->attr_col);
+    attr_release(h->list_pool);
     h->where_prog.release();
     h->where_cnt.release();
     for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
@@ -1322,9 +1398,9 @@ int mlvdb_index_compact(mlvdb_index* h, int64_t* old_labels, int64_t capacity, i
     const int64_t want = h->total - h->deleted;
     if (capacity < want || (want > 0 && !old_labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "old_labels too small");
     if (live_out) *live_out = want;
-    if (h->deleted == 0) {  // nothing to drop: identity
+    if (h->deleted == 0) {  // nothing to drop: identity (the list pools still shed their overwritten lists)
         for (int64_t i = 0; i < want; ++i) old_labels[i] = i;
-        return MLVDB_OK;
+        return list_repack_all(h, want);
     }
     hipStream_t s = h->stream;
     const int64_t nblocks = (h->total + 1023) / 1024;
@@ -1380,7 +1456,7 @@ int mlvdb_index_compact(mlvdb_index* h, int64_t* old_labels, int64_t capacity, i
     h->deleted = 0;
     h->i8_rows = 0;
     h->l2_rows = 0;
-    return MLVDB_OK;
+    return list_repack_all(h, want);  // the slots moved with their rows: now the pools are repacked in the new row order
     });
 }
 
@@ -1407,6 +1483,7 @@ int mlvdb_index_reset(mlvdb_index* h, int32_t space) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     if (h->rowerr.p) HIP_TRY(h, hipMemsetAsync(h->rowerr.p, 0, sizeof(unsigned int), h->stream));
+    for (int64_t& used : h->list_used) used = 0;  // the list pools are empty again (their allocations stay)
     h->total = 0;
     h->deleted = 0;
     h->i8_rows = 0;
@@ -2069,6 +2146,14 @@ int attr_check(mlvdb_index* h, int32_t attr) {
     return MLVDB_OK;
 }
 
+// ... for the entries that read or write a column's values as scalars: a list column's slots (mlvdb_list.h) are neither
+// integers to rank, bin or group by, nor something a raw write may forge.
+int scalar_check(mlvdb_index* h, int32_t attr) {
+    if (h->attr_type[attr] == MLVDB_ATTR_INT64_LIST)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a list column: this entry needs a scalar column (see mlvdb_list.h)");
+    return MLVDB_OK;
+}
+
 // Host validation of a program (stack depth >= 1 throughout and exactly 1 at the end, defined attributes, ops valid for their
 // column's type, set ranges inside the table and sorted) -> h->where_ops, the form the kernel reads.  Nothing is launched for a
 // program refused here.
@@ -2099,6 +2184,8 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
                 if (int rc = attr_check(h, o.attr)) return rc;
                 d.type = h->attr_type[o.attr];
                 d.col = h->attr_col[o.attr];
+                if (d.type == MLVDB_ATTR_INT64_LIST && o.op != MLVDB_WHERE_EXISTS)
+                    return fail(h, MLVDB_ERR_INVALID_ARG, "a list column takes HAS, HAS_ANY, HAS_ALL, LEN and EXISTS only");
                 if (o.op == MLVDB_WHERE_IN) {
                     if (d.type != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "IN needs an int64 column");
                     if (o.a < 0 || o.b < 0 || o.a > w->n_set || o.b > w->n_set - o.a)
@@ -2107,6 +2194,27 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
                         if (w->set[j - 1] > w->set[j]) return fail(h, MLVDB_ERR_INVALID_ARG, "IN: set range not sorted ascending");
                 }
                 break;
+            case MLVDB_WHERE_HAS: case MLVDB_WHERE_HAS_ANY: case MLVDB_WHERE_HAS_ALL: case MLVDB_WHERE_LEN: {
+                if (int rc = attr_check(h, o.attr)) return rc;
+                d.type = h->attr_type[o.attr];
+                d.col = h->attr_col[o.attr];
+                if (d.type != MLVDB_ATTR_INT64_LIST) return fail(h, MLVDB_ERR_INVALID_ARG, "HAS, HAS_ANY, HAS_ALL and LEN need a list column");
+                if (o.op == MLVDB_WHERE_LEN) break;  // (its bounds stay in a, b: it reads the slot alone)
+                d.b = (int64_t)reinterpret_cast<intptr_t>(h->list_pool[o.attr]);  // the pool's address rides in b
+                if (o.op == MLVDB_WHERE_HAS) break;
+                const bool all = o.op == MLVDB_WHERE_HAS_ALL;
+                if (o.a < 0 || o.b < 0 || o.a > w->n_set || o.b > w->n_set - o.a)
+                    return fail(h, MLVDB_ERR_INVALID_ARG, "HAS_ANY / HAS_ALL: set range outside the set table");
+                if (o.a > INT32_MAX || o.b > INT32_MAX)
+                    return fail(h, MLVDB_ERR_INVALID_ARG, "HAS_ANY / HAS_ALL: set offset and count must be below 2^31");
+                if (all && o.b < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "HAS_ALL: an empty set range");
+                for (int64_t j = o.a + 1; j < o.a + o.b; ++j)
+                    if (all ? w->set[j - 1] >= w->set[j] : w->set[j - 1] > w->set[j])
+                        return fail(h, MLVDB_ERR_INVALID_ARG, all ? "HAS_ALL: set range not strictly ascending"
+                                                                  : "HAS_ANY: set range not sorted ascending");
+                d.a = (o.a << 32) | o.b;
+                break;
+            }
             default:
                 return fail(h, MLVDB_ERR_INVALID_ARG, "unknown where op");
         }
@@ -2155,7 +2263,8 @@ int mlvdb_attr_define(mlvdb_index* h, int32_t attr, int32_t type) {
     int rc = check_handle(h);
     if (rc) return rc;
     if (attr < 0 || attr >= MLVDB_MAX_ATTRS) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute index out of range");
-    if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown attribute type");
+    if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64 && type != MLVDB_ATTR_INT64_LIST)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "unknown attribute type");
     if (h->attr_type[attr]) {
         if (h->attr_type[attr] != type) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute already defined with another type");
         return MLVDB_OK;
@@ -2181,6 +2290,7 @@ int mlvdb_attr_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const
     int rc = check_handle(h);
     if (rc) return rc;
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = scalar_check(h, attr))) return rc;
     if (first < 0 || n < 0 || first > h->total || n > h->total - first || (n > 0 && !values))
         return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
     if (n == 0) return MLVDB_OK;
@@ -2196,6 +2306,7 @@ int mlvdb_attr_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, void*
     int rc = check_handle(h);
     if (rc) return rc;
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = scalar_check(h, attr))) return rc;
     if (first < 0 || n < 0 || first > h->total || n > h->total - first || (n > 0 && !out_values))
         return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
     if (n == 0) return MLVDB_OK;
@@ -2329,6 +2440,11 @@ int where_each_pack(mlvdb_index* h, const mlvdb_where* programs, int32_t n, Each
         const int64_t rebase = (int64_t)out.set.size();
         for (WhereOp o : h->where_ops) {
             if (o.op == MLVDB_WHERE_IN) o.a += rebase;
+            if (o.op == MLVDB_WHERE_HAS_ANY || o.op == MLVDB_WHERE_HAS_ALL) {  // (offset << 32 | count: where_prepare)
+                if ((o.a >> 32) + rebase > INT32_MAX)
+                    return fail(h, MLVDB_ERR_INVALID_ARG, "HAS_ANY / HAS_ALL: the call's set tables exceed 2^31 values");
+                o.a += rebase << 32;
+            }
             if (o.col) {
                 const auto* col = static_cast<const int64_t*>(o.col);
                 auto it = std::find(out.cols.begin(), out.cols.end(), col);
@@ -3372,8 +3488,9 @@ int facet_program(mlvdb_index* h, const mlvdb_where* where, const WhereOp** prog
     return MLVDB_OK;
 }
 
-int facet_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
-                      int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
+// (list: the column is a list column and every value of a row's list counts -- mlvdb_facet_list_values)
+int facet_values_run(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
+                     int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent, bool list) {
     hipStream_t s = h->stream;
     const WhereOp* prog;
     int32_t n_ops;
@@ -3395,7 +3512,10 @@ int facet_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, in
     HIP_TRY(h, launch_attr_fill(reinterpret_cast<int64_t*>(t.keys), INT64_MIN, 0, (int64_t)slots, s));
     HIP_TRY(h, hipMemsetAsync(t.counts, 0, slots * sizeof(unsigned long long), s));
     HIP_TRY(h, hipMemsetAsync(t.ctr, 0, kFacetCounters * sizeof(unsigned long long), s));
-    HIP_TRY(h, launch_facet_values(prog, n_ops, set_d, h->rn, h->attr_col[attr], h->total, t, s));
+    if (list)
+        HIP_TRY(h, launch_facet_list_values(prog, n_ops, set_d, h->rn, h->attr_col[attr], h->list_pool[attr], h->total, t, s));
+    else
+        HIP_TRY(h, launch_facet_values(prog, n_ops, set_d, h->rn, h->attr_col[attr], h->total, t, s));
     HIP_TRY(h, launch_facet_collect(t, packed_keys, packed_counts, s));
     unsigned long long ctr[kFacetCounters] = {};
     HIP_TRY(h, hipMemcpyAsync(ctr, t.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
@@ -3422,6 +3542,11 @@ int facet_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, in
         out_counts[i] = pairs[i].second;
     }
     return MLVDB_OK;
+}
+
+int facet_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
+                      int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
+    return facet_values_run(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent, false);
 }
 
 int facet_bins_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, const void* edges, int32_t n_edges,
@@ -3477,6 +3602,7 @@ int mlvdb_facet_bins(mlvdb_index* h, int32_t attr, const mlvdb_where* where, con
     if (rc) return rc;
     // everything is checked before anything is launched
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = scalar_check(h, attr))) return rc;
     if (n_edges < 1 || n_edges > MLVDB_FACET_MAX_EDGES)
         return fail(h, MLVDB_ERR_INVALID_ARG, "n_edges must be in 1..MLVDB_FACET_MAX_EDGES");
     if (!edges || !out_counts || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
@@ -3750,6 +3876,7 @@ int mlvdb_where_ordered(mlvdb_index* h, int32_t attr, int32_t descending, const 
     if (rc) return rc;
     // everything is checked before anything is launched
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = scalar_check(h, attr))) return rc;
     if (offset < 0 || limit < 1 || limit > MLVDB_ORDER_MAX_ROWS || offset > MLVDB_ORDER_MAX_ROWS - limit)
         return fail(h, MLVDB_ERR_INVALID_ARG, "offset >= 0, limit >= 1 and offset + limit <= MLVDB_ORDER_MAX_ROWS");
     if (!out_labels || !out_values || !n_out || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
@@ -3791,6 +3918,7 @@ int update_sets_prepare(mlvdb_index* h, const mlvdb_assign* sets, int32_t n_sets
     for (int32_t j = 0; j < n_sets; ++j) {
         const mlvdb_assign& a = sets[j];
         if (int rc = attr_check(h, a.attr)) return rc;
+        if (int rc = scalar_check(h, a.attr)) return rc;  // (ASSIGN and ADD alike)
         if (seen[a.attr]) return fail(h, MLVDB_ERR_INVALID_ARG, "an attribute is assigned twice");
         seen[a.attr] = true;
         if (a.op != MLVDB_SET_ASSIGN && a.op != MLVDB_SET_ADD) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown assignment op");
@@ -3873,6 +4001,7 @@ int mlvdb_attr_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64
     if (rc) return rc;
     // everything is checked before anything is launched
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = scalar_check(h, attr))) return rc;
     if (!updated || n < 0 || (n > 0 && (!labels || !values))) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / values / n");
     *updated = 0;
     if (n == 0) return MLVDB_OK;
@@ -3908,6 +4037,194 @@ int mlvdb_tombstone_where(mlvdb_index* h, const mlvdb_where* where, int64_t* out
     // labels into out_labels[capacity], or no labels at all (NULL with a negative capacity)
     if (!matches || (out_labels ? capacity < 0 : capacity > 0)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
     return tombstone_where_impl(h, where, out_labels, capacity, matches);
+    });
+}
+
+// ---- list columns (mlvdb_list.h)
+extern "C++" {
+namespace {
+int list_attr_check(mlvdb_index* h, int32_t attr) {
+    if (int rc = attr_check(h, attr)) return rc;
+    if (h->attr_type[attr] != MLVDB_ATTR_INT64_LIST) return fail(h, MLVDB_ERR_INVALID_ARG, "not a list column");
+    return MLVDB_OK;
+}
+
+// One list as the columns hold them: at most MLVDB_LIST_MAX_LEN values, strictly ascending, none INT64_MIN.
+int list_check(mlvdb_index* h, const int64_t* v, int64_t len) {
+    if (len < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "list offsets must not decrease");
+    if (len > MLVDB_LIST_MAX_LEN) return fail(h, MLVDB_ERR_INVALID_ARG, "a list holds at most MLVDB_LIST_MAX_LEN values");
+    if (len > 0 && !v) return fail(h, MLVDB_ERR_INVALID_ARG, "values is null");
+    for (int64_t j = 0; j < len; ++j) {
+        if (v[j] == INT64_MIN) return fail(h, MLVDB_ERR_INVALID_ARG, "INT64_MIN is not a list element");
+        if (j > 0 && v[j - 1] >= v[j]) return fail(h, MLVDB_ERR_INVALID_ARG, "a list must be strictly ascending");
+    }
+    return MLVDB_OK;
+}
+
+// The n lists of a CSR checked; nothing is written or launched.
+int list_csr_check(mlvdb_index* h, int64_t n, const int64_t* offsets, const int64_t* values, const uint8_t* present) {
+    if (!offsets || offsets[0] < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "bad list offsets");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i];
+        if (int rc = list_check(h, values ? values + offsets[i] : nullptr, len)) return rc;
+        if (present && !present[i] && len != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "an absent row with values");
+    }
+    return MLVDB_OK;
+}
+
+// The checked CSR appended to the pool of `attr` (enqueued, the pool regrown first if need be) -> the rows' slots.
+int list_append(mlvdb_index* h, int32_t attr, int64_t n, const int64_t* offsets, const int64_t* values,
+                const uint8_t* present, std::vector<int64_t>& slots) {
+    const int64_t count = offsets[n] - offsets[0];
+    if (int rc = list_pool_reserve(h, attr, count)) return rc;
+    const int64_t base = h->list_used[attr];
+    if (count > 0)
+        HIP_TRY(h, hipMemcpyAsync(h->list_pool[attr] + base, values + offsets[0], (size_t)count * sizeof(int64_t),
+                                  hipMemcpyHostToDevice, h->stream));
+    h->list_used[attr] = base + count;
+    slots.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        slots[(size_t)i] = (present && !present[i]) ? INT64_MIN
+                                                    : (((base + offsets[i] - offsets[0]) << 8) | (offsets[i + 1] - offsets[i]));
+    return MLVDB_OK;
+}
+
+int list_get_impl(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int64_t* out_offsets, int64_t* out_values,
+                  uint8_t* out_present, int64_t capacity, int64_t* needed) {
+    hipStream_t s = h->stream;
+    const int64_t* slots = h->attr_col[attr] + first;
+    if (int rc = list_scan(h, slots, nullptr, n, needed)) return rc;
+    if (capacity < *needed) return MLVDB_OK;
+    // [values | offsets | present]
+    const size_t vbytes = (size_t)*needed * sizeof(int64_t), obytes = (size_t)(n + 1) * sizeof(int64_t);
+    HIP_TRY(h, h->list_out.ensure(vbytes + obytes + (size_t)n));
+    int64_t* values_d = h->list_out.as<int64_t>();
+    int64_t* offsets_d = values_d + *needed;
+    uint8_t* present_d = reinterpret_cast<uint8_t*>(offsets_d + n + 1);
+    HIP_TRY(h, launch_list_move(slots, n, h->list_sums.as<int64_t>(), h->list_pool[attr], values_d, nullptr, offsets_d,
+                                present_d, s));
+    if (vbytes) HIP_TRY(h, hipMemcpyAsync(out_values, values_d, vbytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_offsets, offsets_d, obytes, hipMemcpyDeviceToHost, s));
+    if (out_present) HIP_TRY(h, hipMemcpyAsync(out_present, present_d, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MLVDB_OK;
+}
+
+int facet_list_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
+                           int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
+    return facet_values_run(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent, true);
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_attr_list_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const int64_t* offsets,
+                        const int64_t* values, const uint8_t* present) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = list_attr_check(h, attr))) return rc;
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (n == 0) return MLVDB_OK;
+    if ((rc = list_csr_check(h, n, offsets, values, present))) return rc;
+    std::vector<int64_t> slots;
+    if ((rc = list_append(h, attr, n, offsets, values, present, slots))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->attr_col[attr] + first, slots.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MLVDB_OK;
+    });
+}
+
+int mlvdb_attr_list_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const int64_t* offsets,
+                           const int64_t* values, const uint8_t* present, int64_t* updated) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = list_attr_check(h, attr))) return rc;
+    if (!updated || n < 0 || (n > 0 && !labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n");
+    *updated = 0;
+    if (n == 0) return MLVDB_OK;
+    std::vector<int64_t> sorted(labels, labels + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label outside [0, total)");
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a label appears twice");
+    if ((rc = list_csr_check(h, n, offsets, values, present))) return rc;
+    std::vector<int64_t> slots;
+    if ((rc = list_append(h, attr, n, offsets, values, present, slots))) return rc;
+    return attr_set_at_impl(h, attr, labels, n, slots.data(), updated);  // the slots are scattered like any int64 values
+    });
+}
+
+int mlvdb_attr_list_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int64_t* out_offsets, int64_t* out_values,
+                        uint8_t* out_present, int64_t capacity, int64_t* needed) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((rc = list_attr_check(h, attr))) return rc;
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (!needed || !out_offsets || capacity < 0 || (capacity > 0 && !out_values)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
+    *needed = 0;
+    if (n == 0) {
+        out_offsets[0] = 0;
+        return MLVDB_OK;
+    }
+    return list_get_impl(h, attr, first, n, out_offsets, out_values, out_present, capacity, needed);
+    });
+}
+
+int mlvdb_attr_list_update_where(mlvdb_index* h, const mlvdb_where* where, int32_t attr, const int64_t* values,
+                                 int32_t n_values, int32_t clear, int64_t* matched) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if (!matched) return fail(h, MLVDB_ERR_INVALID_ARG, "null counter");
+    if ((rc = list_attr_check(h, attr))) return rc;
+    if (!clear && (rc = list_check(h, values, n_values))) return rc;
+    if ((rc = where_prepare(h, where))) return rc;
+    *matched = 0;
+    if (h->total == 0) return MLVDB_OK;
+    int64_t slot = INT64_MIN;
+    if (!clear) {  // the list goes into the pool once; every matching row shares its slot
+        const int64_t offsets[2] = {0, n_values};
+        std::vector<int64_t> slots;
+        if ((rc = list_append(h, attr, 1, offsets, values, nullptr, slots))) return rc;
+        slot = slots[0];
+        if ((rc = where_prepare(h, where))) return rc;  // (the append may have moved a pool the program reads)
+    }
+    const MutateSet set{h->attr_col[attr], slot, MLVDB_ATTR_INT64, MLVDB_SET_ASSIGN};
+    int64_t refused = 0;
+    return attr_update_where_impl(h, where, &set, 1, false, matched, &refused);
+    });
+}
+
+int mlvdb_attr_list_stats(mlvdb_index* h, int32_t attr, int64_t* pool_used, int64_t* pool_live) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((rc = list_attr_check(h, attr))) return rc;
+    if (!pool_used || !pool_live) return fail(h, MLVDB_ERR_INVALID_ARG, "null counter");
+    *pool_used = h->list_used[attr];
+    return list_scan(h, h->attr_col[attr], h->rn, h->total, pool_live);
+    });
+}
+
+int mlvdb_facet_list_values(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
+                            int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = list_attr_check(h, attr))) return rc;
+    if (max_values < 1 || max_values > MLVDB_FACET_MAX_VALUES)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "max_values must be in 1..MLVDB_FACET_MAX_VALUES");
+    if (!out_values || !out_counts || !n_values || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (where && (rc = where_prepare(h, where))) return rc;
+    *n_values = *matched = *absent = 0;
+    if (h->total == 0) return MLVDB_OK;
+    return facet_list_values_impl(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent);
     });
 }
 

@@ -20,6 +20,7 @@
 #include "../../include/mlvdb_like.h"
 #include "../../include/mlvdb_maxsim.h"
 #include "../../include/mlvdb_mutate.h"
+#include "../../include/mlvdb_list.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -347,8 +348,9 @@ constexpr int kWhereMaxOps = MLVDB_WHERE_MAX_OPS;
 struct WhereOp {
     int32_t op;
     int32_t type;      // MLVDB_ATTR_* of the column (0 for TRUE / AND / OR / NOT)
-    int64_t a, b;
-    const void* col;   // the column's capacity values (int64 or float64 bits)
+    int64_t a, b;      // list ops (mlvdb_list.h): b = the pool's device address, a = the value (HAS) or set offset << 32 | count
+                       // (HAS_ANY / HAS_ALL); LEN keeps its bounds in a, b
+    const void* col;   // the column's capacity values (int64, float64 bits or list slots)
 };
 // mask[i] = row i is live and matches, for i < total; *matches += their count
 hipError_t launch_where_eval(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, int64_t total,
@@ -372,6 +374,18 @@ hipError_t launch_attr_scatter(int64_t* col, const int64_t* labels, const int64_
 // store: every storable value of those rows is written (all of them, when the counting pass before found counters[1] == 0)
 hipError_t launch_attr_update(const WhereOp* prog, int32_t n_ops, const int64_t* set, const MutateSet* sets, int32_t n_sets,
                               const float* rn, int64_t total, bool store, unsigned long long* counters, hipStream_t s);
+// ---------------------------------------------------------------- list columns (kernels_list.hip, include/mlvdb_list.h)
+constexpr int kListBlock = 256;  // rows per block of the three kernels below: one row per thread
+// sums[b] = summed list lengths of rows [b * kListBlock, ...) of the n slots (rn != nullptr: of the live ones among them)
+hipError_t launch_list_block_sums(const int64_t* slots, const float* rn, int64_t n, int64_t* sums, hipStream_t s);
+// sums[0 .. nblocks) -> their exclusive prefix sums in place, sums[nblocks] = the total
+hipError_t launch_list_scan_sums(int64_t* sums, int64_t nblocks, hipStream_t s);
+// The lists of the n slots copied back to back into out_pool in row order (offsets from the scanned block sums);
+// out_slots[i] (may be `slots` itself) = the row's slot into out_pool, out_offsets[0 .. n] its CSR offsets,
+// out_present[i] = 0 for an absent row -- each of the three may be null
+hipError_t launch_list_move(const int64_t* slots, int64_t n, const int64_t* sums, const int64_t* pool, int64_t* out_pool,
+                            int64_t* out_slots, int64_t* out_offsets, uint8_t* out_present, hipStream_t s);
+
 // rn[i] = NaN for the rows of mask, and their int8 row pairs (i < i8_rows; rp8 may be null) as tombstone_rp8_kernel does
 hipError_t launch_tombstone_mask(const uint8_t* mask, float* rn, float* rp8, int64_t i8_rows, int l2, int64_t total,
                                  hipStream_t s);
@@ -563,6 +577,9 @@ struct FacetTable {
 hipError_t launch_facet_values(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* col,
                                int64_t total, const FacetTable& t, hipStream_t s);
 // the non-empty slots of `t` packed through ctr[kFacetCursor] into out_keys / out_counts (max_values entries each), in no order
+// ... of a list column: every value of a hit row's list counts once; kFacetAbsent counts the hits with no value at all
+hipError_t launch_facet_list_values(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* col,
+                                    const int64_t* pool, int64_t total, const FacetTable& t, hipStream_t s);
 hipError_t launch_facet_collect(const FacetTable& t, long long* out_keys, unsigned long long* out_counts, hipStream_t s);
 // The same pass into bins[n_edges + 1] (zeroed by the caller): bin = number of edges <= value; `edges` on the device, int64 or
 // the bits of doubles by `type` (MLVDB_ATTR_*)

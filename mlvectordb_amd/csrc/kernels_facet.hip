@@ -106,6 +106,62 @@ hipError_t launch_facet_values(const WhereOp* prog, int32_t n_ops, const int64_t
     return hipGetLastError();
 }
 
+// The value kernel over a list column (include/mlvdb_list.h): `col` holds slots into `pool`, and a hit row counts once under
+// every value of its list.  Step j of the walk peels the j-th values of the wave's rows together; the walk is as long as the
+// wave's longest list (the bound is a ballot, so every lane runs every round the peel's ballots need).
+__global__ __launch_bounds__(256) void facet_list_values_kernel(const WhereOp* __restrict__ prog, int32_t n_ops,
+                                                                const int64_t* __restrict__ set, const float* __restrict__ rn,
+                                                                const int64_t* __restrict__ col,
+                                                                const int64_t* __restrict__ pool, int64_t total, FacetTable t) {
+    __shared__ WhereOp sp[kWhereMaxOps];
+    __shared__ unsigned long long lkeys[kFacetLdsSlots];
+    __shared__ uint32_t lcounts[kFacetLdsSlots];
+    __shared__ unsigned long long block_matched, block_absent;
+    if ((int)threadIdx.x < n_ops) sp[threadIdx.x] = prog[threadIdx.x];
+    for (int s = threadIdx.x; s < kFacetLdsSlots; s += blockDim.x) {
+        lkeys[s] = kFacetEmpty;
+        lcounts[s] = 0;
+    }
+    if (threadIdx.x == 0) block_matched = block_absent = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    unsigned long long wave_matched = 0, wave_absent = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < total; i0 += stride) {
+        int64_t slot;
+        const bool hit = facet_row(sp, n_ops, set, rn, col, i0 + threadIdx.x, total, slot);
+        const int len = slot == INT64_MIN ? 0 : (int)(slot & 0xff);  // (no hit: INT64_MIN)
+        const int64_t* lp = pool + (slot >> 8);                      // (never read when len == 0)
+        const unsigned long long bh = __ballot(hit), ba = __ballot(hit && len == 0);
+        if (lane == 0) {
+            wave_matched += __popcll(bh);
+            wave_absent += __popcll(ba);
+        }
+        for (int j = 0; __ballot(j < len); ++j) {
+            const bool has = j < len;
+            const int64_t v = has ? lp[j] : INT64_MIN;
+            wave_peel_add(has, v, [&](int64_t key, uint32_t n) {
+                if (!lds_insert(lkeys, lcounts, key, n)) global_insert(t, key, n);
+            });
+        }
+    }
+    if (lane == 0 && wave_matched) atomicAdd(&block_matched, wave_matched);
+    if (lane == 0 && wave_absent) atomicAdd(&block_absent, wave_absent);
+    __syncthreads();
+    for (int s = threadIdx.x; s < kFacetLdsSlots; s += blockDim.x)
+        if (lkeys[s] != kFacetEmpty) global_insert(t, (int64_t)lkeys[s], lcounts[s]);
+    if (threadIdx.x == 0 && block_matched) atomicAdd(&t.ctr[kFacetMatched], block_matched);
+    if (threadIdx.x == 0 && block_absent) atomicAdd(&t.ctr[kFacetAbsent], block_absent);
+}
+
+hipError_t launch_facet_list_values(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* col,
+                                    const int64_t* pool, int64_t total, const FacetTable& t, hipStream_t s) {
+    if (total == 0) return hipSuccess;
+    const int64_t blocks = std::min<int64_t>((total + 255) / 256, 256 * 16);
+    facet_list_values_kernel<<<(unsigned)blocks, 256, 0, s>>>(prog, n_ops, set, rn, col, pool, total, t);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void facet_collect_kernel(FacetTable t, long long* __restrict__ out_keys,
                                                             unsigned long long* __restrict__ out_counts) {
     for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= t.mask; s += (uint64_t)gridDim.x * blockDim.x) {

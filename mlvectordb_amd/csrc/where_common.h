@@ -48,6 +48,43 @@ __device__ __forceinline__ bool where_eval_with(const WhereOp* prog, int32_t n_o
                         bit = have && lo < o.a + o.b && set[lo] == raw;
                     }
                 }
+            } else if ((o.type & 0xff) == MLVDB_ATTR_INT64_LIST) {
+                // raw is the row's slot, (offset << 8) | len into the pool whose address the host put into o.b
+                // (include/mlvdb_list.h); an absent slot reads as len 0.  The walks below diverge per lane (<= 255 steps).
+                const bool have = raw != INT64_MIN;
+                const int len = (int)(raw & 0xff);
+                const int64_t* lp = reinterpret_cast<const int64_t*>(o.b) + (raw >> 8);
+                if (o.op == MLVDB_WHERE_EXISTS) {
+                    bit = have;
+                } else if (o.op == MLVDB_WHERE_LEN) {
+                    bit = have && len >= o.a && len <= o.b;
+                } else if (o.op == MLVDB_WHERE_HAS) {  // binary search of the row's sorted list
+                    int lo = 0, hi = len;
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (lp[mid] < o.a) lo = mid + 1; else hi = mid;
+                    }
+                    bit = lo < len && lp[lo] == o.a;
+                } else {  // HAS_ANY / HAS_ALL: every element looked up in set[s0, s0 + sn) (o.a = s0 << 32 | sn)
+                    const int64_t s0 = o.a >> 32, sn = o.a & 0xffffffffll;
+                    const bool all = o.op == MLVDB_WHERE_HAS_ALL;
+                    int found = 0;
+                    const int walk = (all && len < sn) ? 0 : len;  // a shorter list cannot hold them all
+                    for (int j = 0; j < walk; ++j) {
+                        const int64_t v = lp[j];
+                        int64_t lo = s0, hi = s0 + sn;
+                        while (lo < hi) {
+                            const int64_t mid = lo + ((hi - lo) >> 1);
+                            if (set[mid] < v) lo = mid + 1; else hi = mid;
+                        }
+                        if (lo < s0 + sn && set[lo] == v) {
+                            ++found;
+                            if (!all) break;
+                        }
+                    }
+                    // (both sides strictly ascending under HAS_ALL: every set value is found at most once)
+                    bit = all ? (have && found == sn) : found > 0;
+                }
             } else {  // float64: absent = NaN, so every ordered comparison of an absent value is false by itself
                 const double v = __longlong_as_double(raw), a = __longlong_as_double(o.a);
                 switch (o.op) {

@@ -235,8 +235,10 @@ class HipScanEngine:
 
     # -- metadata filters (include/mlvdb_where.h) ------------------------------------
     def define_attr(self, attr: int, kind: str) -> None:
-        """Column ``attr`` (0..15) of type "int64" (absent = INT64_MIN) or "float64" (absent = NaN), every row absent."""
-        self._check(self._lib.mlvdb_attr_define(self._h, int(attr), _native.ATTR_CODES[kind]), "attr_define")
+        """Column ``attr`` (0..15) of type "int64" (absent = INT64_MIN), "float64" (absent = NaN) or "int64_list" (a set of
+        int64 per row, include/mlvdb_list.h), every row absent."""
+        code = _native.LIST_ATTR_CODES[kind] if kind in _native.LIST_ATTR_CODES else _native.ATTR_CODES[kind]
+        self._check(self._lib.mlvdb_attr_define(self._h, int(attr), code), "attr_define")
         self._attr_kinds[int(attr)] = kind
 
     def set_attr(self, attr: int, first: int, values: np.ndarray) -> None:
@@ -312,6 +314,88 @@ class HipScanEngine:
         if n.value > out.size:  # (cannot happen: the buffer holds every live row)
             raise RuntimeError(f"tombstone_where: {n.value} matches for {out.size} live rows")
         return out[: n.value]
+
+    # -- list columns (include/mlvdb_list.h) -------------------------------------------
+    @staticmethod
+    def _csr(col):
+        """A ``where.ListColumn`` as the contiguous arrays the C entries take (kept alive by the caller for the call)."""
+        offsets = np.ascontiguousarray(col.offsets, dtype=np.int64)
+        values = np.ascontiguousarray(col.values, dtype=np.int64)
+        present = np.ascontiguousarray(col.present, dtype=np.uint8)
+        if offsets.size != present.size + 1:
+            raise RuntimeError(f"{present.size} rows but {offsets.size} offsets")
+        return offsets, values, present
+
+    def set_attr_list(self, attr: int, first: int, col) -> None:
+        """The lists of rows first..first+len(col)-1 of list column ``attr`` (``col``: a ``where.ListColumn``)."""
+        offsets, values, present = self._csr(col)
+        self._check(self._lib.mlvdb_attr_list_set(self._h, int(attr), int(first), present.size, offsets.ctypes.data,
+                                                  values.ctypes.data if values.size else None, present.ctypes.data),
+                    "attr_list_set")
+
+    def set_attr_list_at(self, attr: int, labels: np.ndarray, col) -> int:
+        """List i of ``col`` -> row ``labels[i]`` (distinct labels in [0, total); tombstoned rows are skipped); returns the
+        rows written."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        offsets, values, present = self._csr(col)
+        if present.size != labels.size:
+            raise RuntimeError(f"{labels.size} labels but {present.size} lists")
+        n = C.c_int64(0)
+        self._check(self._lib.mlvdb_attr_list_set_at(self._h, int(attr), labels.ctypes.data, labels.size, offsets.ctypes.data,
+                                                     values.ctypes.data if values.size else None, present.ctypes.data,
+                                                     C.byref(n)), "attr_list_set_at")
+        return int(n.value)
+
+    def get_attr_list(self, attr: int, first: int, n: int):
+        """The lists of rows first..first+n-1 as a ``where.ListColumn`` (tombstoned rows keep what they hold)."""
+        from .where import ListColumn
+
+        n = int(n)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        present = np.zeros(n, dtype=np.uint8)
+        values = np.empty(0, dtype=np.int64)
+        needed = C.c_int64(0)
+        for _ in range(2):  # the first call sizes the values, the second reads them
+            self._check(self._lib.mlvdb_attr_list_get(self._h, int(attr), int(first), n, offsets.ctypes.data,
+                                                      values.ctypes.data if values.size else None, present.ctypes.data,
+                                                      values.size, C.byref(needed)), "attr_list_get")
+            if needed.value <= values.size:
+                break
+            values = np.empty(needed.value, dtype=np.int64)
+        return ListColumn(offsets, values[: needed.value], present)
+
+    def update_where_list(self, program, attr: int, values) -> int:
+        """Every live row the compiled filter matches gets the list ``values`` (sorted unique int64), or loses its list
+        (``None``); returns the matched count."""
+        w, keep = self._where(program)
+        arr = np.zeros(0, dtype=np.int64) if values is None else np.ascontiguousarray(values, dtype=np.int64).ravel()
+        matched = C.c_int64(0)
+        self._check(self._lib.mlvdb_attr_list_update_where(self._h, C.byref(w), int(attr), arr.ctypes.data if arr.size else None,
+                                                           int(arr.size), 1 if values is None else 0, C.byref(matched)),
+                    "attr_list_update_where")
+        return int(matched.value)
+
+    def list_stats(self, attr: int) -> Tuple[int, int]:
+        """(values allocated in the attribute's pool, summed list lengths of the live rows): equal right after ``compact``."""
+        used, live = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.mlvdb_attr_list_stats(self._h, int(attr), C.byref(used), C.byref(live)), "attr_list_stats")
+        return int(used.value), int(live.value)
+
+    def facet_list_values(self, attr: int, max_values: int, where=None):
+        """``facet_values`` of a list column: counts[v] = live matching rows whose list holds values[v]; ``absent`` = the
+        matching rows with no list or an empty one (a row counts under each of its values, so the counts do not sum to
+        ``matched - absent``)."""
+        max_values = int(max_values)
+        values = np.empty(max(0, min(max_values, _native.FACET_MAX_VALUES)), dtype=np.int64)
+        counts = np.empty(values.size, dtype=np.int64)
+        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        w, keep = self._where(where) if where is not None else (None, None)
+        rc = self._check(self._lib.mlvdb_facet_list_values(
+            self._h, int(attr), None if w is None else C.byref(w), max_values, values.ctypes.data, counts.ctypes.data,
+            C.byref(n), C.byref(matched), C.byref(absent)), "facet_list_values", allow=(_native.ERR_OVERFLOW,))
+        if rc == _native.ERR_OVERFLOW:
+            raise FacetOverflow(max_values, int(n.value), int(matched.value), int(absent.value))
+        return values[: n.value].copy(), counts[: n.value].copy(), int(matched.value), int(absent.value)
 
     # -- per-query filters (include/mlvdb_where_each.h) -------------------------------
     @staticmethod

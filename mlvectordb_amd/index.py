@@ -262,8 +262,8 @@ class Index:
         for name, kind in attributes.items():
             if not isinstance(name, str) or name.startswith("$"):
                 raise ValueError(f"attribute name {name!r}: a string not starting with '$'")
-            if kind not in _where.ATTR_TYPES:
-                raise ValueError(f"attribute {name!r}: type {kind!r} is not one of {_where.ATTR_TYPES}")
+            if kind not in _where.ATTR_TYPES + _where.LIST_TYPES:
+                raise ValueError(f"attribute {name!r}: type {kind!r} is not one of {_where.ATTR_TYPES + _where.LIST_TYPES}")
         return attributes
 
     @property
@@ -317,11 +317,28 @@ class Index:
                 continue
             if len(values) != n:
                 raise ValueError(f"attribute {name!r}: {len(values)} values for {n} rows")
+            if _where.is_list(kind):
+                col = _where.encode_list_column(name, kind, values, strings.setdefault(name, {}) if kind == "str[]" else {})
+                if col.present.any():
+                    out[i] = col
+                continue
             col = _where.encode_column(name, kind, values, strings.setdefault(name, {}) if kind == "str" else {})
             present = ~np.isnan(col) if col.dtype == np.float64 else col != _where.INT64_ABSENT
             if present.any():
                 out[i] = col
         return out, strings
+
+    @staticmethod
+    def _list_engine(ns: _Namespace, method: str):
+        fn = getattr(ns.engine, method, None)
+        if fn is None:
+            raise ValueError(f"list attributes need an engine with {method} (a single-device namespace)")
+        return fn
+
+    def _check_scalar(self, what: str, name: str) -> None:
+        if _where.is_list(self._attributes[name]):
+            raise ValueError(f"{what}: attribute {name!r} is a {self._attributes[name]} column; it needs a scalar attribute "
+                             f"(a list has no one value to rank, bin or group by)")
 
     def _metadata_columns(self, metadata: Sequence[Optional[Mapping]]) -> Dict[str, list]:
         """The declared attributes' values out of per-row metadata dicts (missing key / no metadata = absent)."""
@@ -335,7 +352,10 @@ class Index:
     def _commit_attrs(ns: _Namespace, first: int, staged) -> None:
         cols, strings = staged
         for i, col in cols.items():
-            ns.engine.set_attr(i, first, col)
+            if isinstance(col, _where.ListColumn):
+                Index._list_engine(ns, "set_attr_list")(i, first, col)
+            else:
+                ns.engine.set_attr(i, first, col)
         if strings is not None:
             ns.strings = strings
 
@@ -621,6 +641,7 @@ class Index:
         if distinct not in self._attributes:
             raise ValueError(f"distinct: {distinct!r} is not a declared attribute of this index "
                              f"(declared: {sorted(self._attributes)})")
+        self._check_scalar("distinct", distinct)
         kind = self._attributes[distinct]
         if kind == "float":
             raise ValueError(f"distinct: attribute {distinct!r} is a float column; groups need an int, str or bool attribute")
@@ -729,6 +750,7 @@ class Index:
         if by not in self._attributes:
             raise ValueError(f"search_late: {by!r} is not a declared attribute of this index "
                              f"(declared: {sorted(self._attributes)})")
+        self._check_scalar("search_late", by)
         kind = self._attributes[by]
         if kind == "float":
             raise ValueError(f"search_late: attribute {by!r} is a float column; documents need an int, str or bool attribute")
@@ -1064,8 +1086,12 @@ class Index:
             pos = [j for j, p in enumerate(patches) if name in p]
             if not pos:
                 continue
-            col = _where.encode_column(name, kind, [patches[j][name] for j in pos],
-                                       strings.setdefault(name, {}) if kind == "str" else {})
+            if _where.is_list(kind):
+                col = _where.encode_list_column(name, kind, [patches[j][name] for j in pos],
+                                                strings.setdefault(name, {}) if kind == "str[]" else {})
+            else:
+                col = _where.encode_column(name, kind, [patches[j][name] for j in pos],
+                                           strings.setdefault(name, {}) if kind == "str" else {})
             out[i] = (np.asarray(pos, dtype=np.int64), col)
         return out, strings
 
@@ -1091,10 +1117,13 @@ class Index:
         for i, (pos, col) in staged.items():
             lab = labels[pos]
             keep = lab >= 0
-            lab, col = lab[keep], col[keep]
+            lab = lab[keep]
             rows, last = np.unique(lab[::-1], return_index=True)  # the last entry of each row
-            if rows.size:
-                set_at(i, rows, col[lab.size - 1 - last])
+            if rows.size and isinstance(col, _where.ListColumn):
+                self._list_engine(ns, "set_attr_list_at")(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
+                touched.append(rows)
+            elif rows.size:
+                set_at(i, rows, col[keep][lab.size - 1 - last])
                 touched.append(rows)
         ns.strings = strings
         return int(np.unique(np.concatenate(touched)).size) if touched else 0
@@ -1115,6 +1144,13 @@ class Index:
             if name not in values:
                 continue
             v = values[name]
+            if _where.is_list(kind):  # one list for every matching row, or None: (column, "list", sorted codes or None)
+                if isinstance(v, Mapping):
+                    raise ValueError(f"update_where: {name!r} is a {kind} attribute: it takes a list or None, no operator "
+                                     f"($inc adds to numbers; per-row $push / $pull are not supported)")
+                col = _where.encode_list_column(name, kind, [v], strings.setdefault(name, {}) if kind == "str[]" else {})
+                out.append((i, "list", col.row(0)))
+                continue
             if isinstance(v, Mapping):
                 if list(v) != ["$inc"]:
                     raise ValueError(f"update_where: {name!r}: the only operator is $inc (got {sorted(map(str, v))})")
@@ -1138,15 +1174,31 @@ class Index:
         """Set attribute values of every live row the dict filter ``where`` matches, in one pass on the device
         (include/mlvdb_mutate.h): ``values`` maps a declared attribute to a literal, to ``None`` (clear) or to ``{"$inc": x}``
         (rows without a value keep none).  The filter sees the values from before the call.  Returns the matched count.  All
-        or nothing: when an increment would overflow on some row, ``ValueError`` says on how many and nothing has changed."""
+        or nothing: when an increment would overflow on some row, ``ValueError`` says on how many and nothing has changed.
+        A list attribute takes a list (every matching row shares it) or ``None``.  The scalar assignments are one device pass
+        and each list attribute is one more; a call that needs several passes must not assign an attribute its own filter
+        reads (``ValueError``: split it), since a later pass would see the earlier one's values."""
         program = self._compile(namespace, where)
         assigns, strings = self.stage_assignments(namespace, values)
+        scalars = [a for a in assigns if a[1] != "list"]
+        lists = [a for a in assigns if a[1] == "list"]
+        if len(lists) + bool(scalars) > 1:
+            ops = program.ops
+            read = set(ops["attr"][~np.isin(ops["op"], (_where.TRUE, _where.AND, _where.OR, _where.NOT))].tolist())
+            clash = sorted(name for i, name in enumerate(self._attributes) if i in read and any(a[0] == i for a in assigns))
+            if clash:
+                raise ValueError(f"update_where: the filter reads {clash}, which this call assigns together with other "
+                                 f"attributes in several passes; assign them in a call of their own")
         ns = self._ns.get(namespace)
         if ns is None or ns.total == 0:
             return 0
-        matched, refused = self._mutator(ns, "update_where", "update_where")(program, assigns)
-        if refused:
-            raise ValueError(f"update_where: $inc would overflow on {refused} of the {matched} matching rows; nothing was changed")
+        matched = None
+        if scalars:  # first: the only pass that can refuse
+            matched, refused = self._mutator(ns, "update_where", "update_where")(program, scalars)
+            if refused:
+                raise ValueError(f"update_where: $inc would overflow on {refused} of the {matched} matching rows; nothing was changed")
+        for i, _, codes in lists:
+            matched = self._list_engine(ns, "update_where_list")(program, i, codes)
         ns.strings = strings
         return matched
 
@@ -1182,6 +1234,7 @@ class Index:
         """The refusals of ``top_by`` that need no namespace -> the column kind of ``by`` ("int", "float" or "bool")."""
         if not isinstance(by, str) or by not in self._attributes:
             raise ValueError(f"top_by: {by!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        self._check_scalar("top_by", by)
         kind = self._attributes[by]
         if kind == "str":
             raise ValueError(f"top_by: attribute {by!r} is a str column; its codes are in order of first use, not in lexical "
@@ -1264,7 +1317,9 @@ class Index:
         ascending; ``order="value"``: by value ascending; ``limit`` cuts after ordering.  ``max_values`` bounds the distinct
         values of an ``int`` attribute (more: ``ValueError``); a ``str`` attribute is bounded by its dictionary, a ``bool``
         by two.  ``by`` as a list of attributes returns a dict keyed by attribute (one device pass each).  An unknown or
-        empty namespace gives no values and zeros."""
+        empty namespace gives no values and zeros.  A list attribute (``str[]`` / ``int[]``) counts a row under every
+        element of its list -- the counts then do not add up to ``matched - absent`` -- and ``absent`` counts the rows with no
+        list or an empty one."""
         names = self.check_facet_args(by, order, limit, max_values)
         if where is not None and not isinstance(where, Mapping):
             raise ValueError(f"facets: where must be one dict filter or None (got {type(where).__name__})")
@@ -1275,19 +1330,19 @@ class Index:
             if ns is None or ns.total == 0:
                 out[name] = {"values": [], "matched": 0, "absent": 0}
                 continue
-            facet_values = getattr(ns.engine, "facet_values", None)
+            kind = self._attributes[name]
+            facet_values = getattr(ns.engine, "facet_list_values" if _where.is_list(kind) else "facet_values", None)
             if facet_values is None:
                 raise ValueError("facets needs an engine with facet_values (a single-device namespace)")
-            kind = self._attributes[name]
             codes = ns.strings.get(name, {})
-            bound = max(1, len(codes)) if kind == "str" else 2 if kind == "bool" else int(max_values)
+            bound = max(1, len(codes)) if kind in ("str", "str[]") else 2 if kind == "bool" else int(max_values)
             try:
                 values, counts, matched, absent = facet_values(list(self._attributes).index(name), bound, where=program)
             except FacetOverflow as e:
                 raise ValueError(f"facets: attribute {name!r} holds more than max_values={bound} distinct values among the "
                                  f"{e.matched} matching rows; raise max_values (at most {self._MAX_FACET_VALUES})") from e
             values, counts = values.tolist(), counts.tolist()
-            if kind == "str":
+            if kind in ("str", "str[]"):
                 strings = sorted(codes, key=codes.get)  # code order
                 values = [strings[v] for v in values]
             elif kind == "bool":
@@ -1300,6 +1355,7 @@ class Index:
         """The refusals of ``histogram`` -> the edges as the column's own type (int64 / float64)."""
         if not isinstance(by, str) or by not in self._attributes:
             raise ValueError(f"histogram: {by!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        self._check_scalar("histogram", by)
         kind = self._attributes[by]
         if kind not in ("int", "float"):
             raise ValueError(f"histogram: attribute {by!r} is a {kind} column; bins need an int or float attribute")
@@ -1458,13 +1514,16 @@ class Index:
     # dictionary, code order).  An index without attributes writes exactly v1.
     _FORMAT = "mlvdb-index-v1"
     _FORMAT_V2 = "mlvdb-index-v2"
+    _FORMAT_V3 = "mlvdb-index-v3"  # v2 + per list attribute the live rows' lists in CSR form (offsets.i64, values.i64)
     _CHUNK_BYTES = 256 << 20
 
     def save_index(self, path: str) -> bool:
         """Write every namespace to directory ``path`` (created if missing); streams the rows off the device in
         chunks, so host memory stays bounded."""
         os.makedirs(path, exist_ok=True)
-        meta = {"format": self._FORMAT_V2 if self._attributes else self._FORMAT, "space": self._space,
+        has_lists = any(_where.is_list(kind) for kind in self._attributes.values())
+        meta = {"format": self._FORMAT_V3 if has_lists else self._FORMAT_V2 if self._attributes else self._FORMAT,
+                "space": self._space,
                 "rebuild_threshold": self._rebuild_threshold, "namespaces": []}
         if self._attributes:
             meta["attributes"] = dict(self._attributes)
@@ -1483,6 +1542,9 @@ class Index:
             if self._attributes:
                 for j, kind in enumerate(self._attributes.values()):
                     col = self._attr_file(path, i, j, kind)
+                    if _where.is_list(kind):
+                        self._save_list(ns, j, col, dead)
+                        continue
                     dtype = np.float64 if kind == "float" else np.int64
                     (ns.engine.get_attr(j, 0, ns.total, dtype) if ns.total else np.zeros(0, dtype)).tofile(col)
                 entry["strings"] = {a: sorted(codes, key=codes.get) for a, codes in ns.strings.items()}
@@ -1492,6 +1554,32 @@ class Index:
             json.dump(meta, f, indent=1)
         os.replace(tmp, os.path.join(path, "index.json"))  # the manifest appears last and atomically
         return True
+
+    @classmethod
+    def _save_list(cls, ns: _Namespace, j: int, col_file: str, dead: np.ndarray) -> None:
+        """A list attribute of a v3 snapshot: the column file holds each row's length (INT64_MIN: no list), and next to it
+        ``.offsets.i64`` / ``.values.i64`` hold the lists of the live rows in CSR form -- what the rows hold now, not the
+        device pool with its overwritten lists; a tombstoned row is written without a list."""
+        lens = np.full(ns.total, _where.INT64_ABSENT, dtype=np.int64)
+        offsets = np.zeros(ns.total + 1, dtype=np.int64)
+        parts = []
+        chunk = 1 << 20
+        for first in range(0, ns.total, chunk):
+            n = min(chunk, ns.total - first)
+            got = cls._list_engine(ns, "get_attr_list")(j, first, n)
+            live = got.present.astype(bool)
+            live[dead[(dead >= first) & (dead < first + n)] - first] = False
+            rows = np.flatnonzero(live)
+            kept = got.take(rows)
+            n_each = np.zeros(n, dtype=np.int64)
+            n_each[rows] = kept.offsets[1:] - kept.offsets[:-1]
+            lens[first:first + n][live] = n_each[live]
+            offsets[first + 1:first + n + 1] = offsets[first] + np.cumsum(n_each)
+            parts.append(kept.values)
+        lens.tofile(col_file)
+        offsets.tofile(col_file[:-len("i64")] + "offsets.i64")
+        (np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)).astype(np.int64).tofile(
+            col_file[:-len("i64")] + "values.i64")
 
     @staticmethod
     def _attr_file(path: str, i: int, j: int, kind: str) -> str:
@@ -1505,9 +1593,9 @@ class Index:
             return False
         with open(manifest) as f:
             meta = json.load(f)
-        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2):
+        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2, self._FORMAT_V3):
             raise RuntimeError(f"unknown index format {meta.get('format')!r}")
-        v2 = meta["format"] == self._FORMAT_V2
+        v2 = meta["format"] in (self._FORMAT_V2, self._FORMAT_V3)  # (v3: v2 with list attributes)
         # v2: the snapshot's attributes replace the declared ones; v1: the declared ones stay, every value absent
         attributes = self._check_schema(meta.get("attributes", {})) if v2 else self._attributes
         if v2 and attributes and self._devices is not None and len(self._devices) > 1:
@@ -1520,6 +1608,13 @@ class Index:
             if v2 and any(os.path.getsize(self._attr_file(path, i, j, kind)) != total * 8
                           for j, kind in enumerate(attributes.values())):
                 raise RuntimeError(f"namespace {m['name']!r}: attribute file sizes do not match the manifest")
+            for j, kind in enumerate(attributes.values()):
+                if v2 and _where.is_list(kind):
+                    base = self._attr_file(path, i, j, kind)[:-len("i64")]
+                    if meta["format"] != self._FORMAT_V3 or not os.path.isfile(base + "values.i64") or \
+                            not os.path.isfile(base + "offsets.i64") or \
+                            os.path.getsize(base + "offsets.i64") != (total + 1) * 8:
+                        raise RuntimeError(f"namespace {m['name']!r}: list attribute files do not match the manifest")
         self.close()
         self._attributes = attributes
         self._space = meta["space"]
@@ -1542,7 +1637,13 @@ class Index:
             if v2:
                 for j, kind in enumerate(attributes.values()):
                     col = np.fromfile(self._attr_file(path, i, j, kind), dtype=np.float64 if kind == "float" else np.int64)
-                    if col.size:
+                    if col.size and _where.is_list(kind):
+                        base = self._attr_file(path, i, j, kind)[:-len("i64")]
+                        lists = _where.ListColumn(np.fromfile(base + "offsets.i64", dtype=np.int64),
+                                                  np.fromfile(base + "values.i64", dtype=np.int64),
+                                                  (col != _where.INT64_ABSENT).astype(np.uint8))
+                        self._list_engine(ns, "set_attr_list")(j, 0, lists)
+                    elif col.size:
                         ns.engine.set_attr(j, 0, col)
                 ns.strings = {a: {s: c for c, s in enumerate(values)} for a, values in m.get("strings", {}).items()}
             ns.total = total

@@ -319,6 +319,8 @@ class QueryProcessor:
         picked = [None if v.metadata is None else v.metadata.get(by)
                   for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
         present = [x for x in picked if x is not None and not (kind == "float" and isinstance(x, float) and x != x)]
+        if kind.endswith("[]"):  # a list attribute: a row counts once under each element; an empty list contributes nothing
+            present = [set(x) for x in present if len(x)]
         return present, len(picked)
 
     def facets(self, by, where=None, namespace: str = "default", *, limit=None, order: str = "count",
@@ -334,7 +336,8 @@ class QueryProcessor:
         for name in names:
             present, matched = self._host_column(name, where, namespace)
             counts: Dict[Any, int] = {}
-            for x in present:
+            listed = self._index.attributes[name].endswith("[]")
+            for x in (present if not listed else [e for row in present for e in row]):
                 counts[x] = counts.get(x, 0) + 1
             if self._index.attributes[name] == "int" and len(counts) > max_values:
                 raise ValueError(f"facets: attribute {name!r} holds more than max_values={max_values} distinct values")

@@ -15,6 +15,16 @@ Type rules: ``int`` / ``bool`` attributes take int and bool literals only (a flo
 take int and float literals, ``str`` attributes take strings and only ``$eq $ne $in $nin $exists`` (matched through the
 namespace's dictionary codes: a string never ingested matches nothing).  A key that is not a declared attribute, or a
 program longer than 64 ops or deeper than 32, is a ``ValueError``: there is no slow host path to fall back to.
+
+List attributes (``"str[]"`` / ``"int[]"``: a set of at most 255 tags per row, include/mlvdb_list.h) take
+
+    {"tags": "jazz"} / $eq      the list contains it        $ne      it does not (a row without a list matches)
+    {"tags": {"$in": [...]}}    any of them                 $nin     none of them (a row without a list matches)
+    {"tags": {"$all": [...]}}   all of them (not empty)     $size    3, or {"$gte": 1, "$lt": 4}: the list's length
+    $exists                     as above; an empty list ``[]`` exists, ``None`` / a missing key does not
+
+A string never ingested matches nothing, so ``$all`` with one is false as a whole.  ``$lt`` .. ``$gte`` on a list
+attribute, and ``$all`` / ``$size`` on a scalar one, are a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -26,16 +36,21 @@ from typing import Any, Dict, List, Mapping, Tuple
 import numpy as np
 
 ATTR_TYPES = ("int", "float", "str", "bool")
+LIST_TYPES = ("str[]", "int[]")  # list-valued attributes: a set of strings / ints per row
+LIST_MAX_LEN = 255               # MLVDB_LIST_MAX_LEN
 MAX_ATTRS = 16
 MAX_OPS = 64
 MAX_DEPTH = 32
 
 # op codes (MLVDB_WHERE_*)
 TRUE, EQ, NE, LT, LE, GT, GE, IN, EXISTS, AND, OR, NOT = range(12)
+HAS, HAS_ANY, HAS_ALL, LEN = range(12, 16)  # list columns only (include/mlvdb_list.h)
+_COMBINATORS = (AND, OR, NOT)
 OP_DTYPE = np.dtype([("op", "<i4"), ("attr", "<i4"), ("a", "<i8"), ("b", "<i8")])  # mlvdb_where_op
 
 _ORDERED = {"$lt": LT, "$lte": LE, "$gt": GT, "$gte": GE}
-_FIELD_OPS = ("$eq", "$ne", "$lt", "$lte", "$gt", "$gte", "$in", "$nin", "$exists")
+_FIELD_OPS = ("$eq", "$ne", "$lt", "$lte", "$gt", "$gte", "$in", "$nin", "$exists", "$all", "$size")
+_LIST_ONLY = ("$all", "$size")
 
 
 @dataclass
@@ -52,9 +67,13 @@ def float_bits(x: float) -> int:
     return struct.unpack("<q", struct.pack("<d", float(x)))[0]
 
 
+def is_list(attr_type: str) -> bool:
+    return attr_type in LIST_TYPES
+
+
 def column_kind(attr_type: str) -> str:
-    """The device column type of an attribute type: float -> float64, everything else -> int64."""
-    return "float64" if attr_type == "float" else "int64"
+    """The device column type of an attribute type: float -> float64, a list type -> int64_list, everything else -> int64."""
+    return "float64" if attr_type == "float" else "int64_list" if is_list(attr_type) else "int64"
 
 
 class _Builder:
@@ -115,6 +134,8 @@ class _Builder:
     def literal(self, key: str, value: Any) -> int:
         """A scalar literal as the int64 the column holds (int / bool / str code; float bits), or None: matches no row."""
         kind = self.schema[key]
+        if is_list(kind):  # an element of the list: typed as the scalar attribute of its element type
+            kind = kind[:-2]
         if kind in ("int", "bool"):
             if isinstance(value, (bool, np.bool_)) or (isinstance(value, (int, np.integer))):
                 v = int(value)
@@ -132,6 +153,11 @@ class _Builder:
 
     def field(self, key: str, op: str, value: Any) -> None:
         attr, kind = self.index[key], self.schema[key]
+        if op in _LIST_ONLY and not is_list(kind):
+            raise ValueError(f"{key!r} is a {kind} attribute: {op} applies to list attributes ({', '.join(LIST_TYPES)}) only")
+        if is_list(kind) and op != "$exists":
+            self.list_field(key, attr, kind, op, value)
+            return
         if op == "$exists":
             if not isinstance(value, (bool, np.bool_)):
                 raise ValueError(f"{key!r}: $exists takes True or False")
@@ -161,6 +187,64 @@ class _Builder:
             return
         self.emit({"$eq": EQ, "$ne": NE}.get(op) or _ORDERED[op], attr, v)
 
+    # -- list attributes
+    def list_set(self, key: str, values: Any, what: str) -> List[Any]:
+        if not isinstance(values, (list, tuple, set, frozenset)):
+            raise ValueError(f"{key!r}: {what} takes a list")
+        return [self.literal(key, x) for x in values]
+
+    def emit_set(self, op: int, attr: int, codes) -> None:
+        vals = np.unique(np.array(list(codes), dtype=np.int64))
+        self.emit(op, attr, self.n_set, int(vals.size))
+        self.sets.append(vals)
+        self.n_set += int(vals.size)
+
+    def list_field(self, key: str, attr: int, kind: str, op: str, value: Any) -> None:
+        if op in _ORDERED:
+            raise ValueError(f"{key!r} is a {kind} attribute: $eq, $ne, $in, $nin, $all, $size and $exists apply, {op} does not")
+        if op in ("$eq", "$ne"):
+            v = self.literal(key, value)
+            self.false() if v is None else self.emit(HAS, attr, v)  # (a value no list can hold is in none)
+            if op == "$ne":
+                self.emit(NOT)
+        elif op in ("$in", "$nin"):
+            seen = [v for v in self.list_set(key, value, op) if v is not None]
+            self.emit_set(HAS_ANY, attr, seen) if seen else self.false()
+            if op == "$nin":
+                self.emit(NOT)
+        elif op == "$all":
+            lits = self.list_set(key, value, op)
+            if not lits:
+                raise ValueError(f"{key!r}: $all takes a list that is not empty")
+            if any(v is None for v in lits) or len(set(lits)) > LIST_MAX_LEN:
+                self.false()  # one of them is in no list (or they are more than a list holds): the clause is false
+            else:
+                self.emit_set(HAS_ALL, attr, lits)
+        else:
+            self.size(key, attr, value)
+
+    def size(self, key: str, attr: int, value: Any) -> None:
+        """``$size``: an int, or a dict of ``$eq $lt $lte $gt $gte`` over ints -> one LEN lo hi."""
+        def integer(x):
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                raise ValueError(f"{key!r}: $size takes an int or a dict of $eq / $lt / $lte / $gt / $gte over ints (got {x!r})")
+            return int(x)
+        lo, hi = 0, LIST_MAX_LEN
+        if isinstance(value, Mapping):
+            if not value:
+                raise ValueError(f"{key!r}: $size: an empty operator dict")
+            for op, x in value.items():
+                if op != "$eq" and op not in _ORDERED:
+                    raise ValueError(f"{key!r}: $size: unknown operator {op!r}")
+                x = integer(x)
+                if op in ("$eq", "$gte", "$gt"):
+                    lo = max(lo, x + (op == "$gt"))
+                if op in ("$eq", "$lte", "$lt"):
+                    hi = min(hi, x - (op == "$lt"))
+        else:
+            lo = hi = integer(value)
+        self.emit(LEN, attr, lo, hi) if 0 <= lo <= hi <= LIST_MAX_LEN else self.false()
+
     def member(self, key: str, attr: int, kind: str, values: List[Any]) -> None:
         lits = [self.literal(key, x) for x in values]
         if kind == "float":  # IN reads int64 columns: a float membership is an OR of equalities
@@ -180,7 +264,7 @@ class _Builder:
             raise ValueError(f"the filter compiles to {len(self.ops)} ops; the device evaluates at most {MAX_OPS}")
         depth = deepest = 0
         for op, _, _, _ in self.ops:
-            depth += 1 if op <= EXISTS else (-1 if op in (AND, OR) else 0)
+            depth += -1 if op in (AND, OR) else 0 if op == NOT else 1
             deepest = max(deepest, depth)
         if deepest > MAX_DEPTH:
             raise ValueError(f"the filter needs a stack {deepest} deep; the device evaluates at most {MAX_DEPTH}")
@@ -260,6 +344,74 @@ def chunk_programs(programs: List[Program], program_of_query, max_programs: int 
 
 # ---------------------------------------------------------------- ingest: metadata values -> column values
 INT64_ABSENT = np.iinfo(np.int64).min
+
+
+@dataclass
+class ListColumn:
+    """A batch of a list attribute in CSR form, as ``mlvdb_attr_list_set`` takes it: row i holds
+    ``values[offsets[i]:offsets[i + 1]]`` (strictly ascending) when ``present[i]``, and no list at all otherwise."""
+
+    offsets: np.ndarray  # int64 [n + 1], offsets[0] == 0
+    values: np.ndarray   # int64
+    present: np.ndarray  # uint8 [n]
+
+    def __len__(self) -> int:
+        return int(self.present.size)
+
+    def row(self, i: int):
+        """The codes of row i as a list, or ``None``."""
+        return self.values[self.offsets[i]:self.offsets[i + 1]].tolist() if self.present[i] else None
+
+    def take(self, rows) -> "ListColumn":
+        """The rows ``rows`` (indices, in that order) as a column of their own."""
+        rows = np.asarray(rows, dtype=np.int64)
+        lens = (self.offsets[1:] - self.offsets[:-1])[rows]
+        offsets = np.zeros(rows.size + 1, dtype=np.int64)
+        np.cumsum(lens, out=offsets[1:])
+        parts = [self.values[self.offsets[r]:self.offsets[r + 1]] for r in rows.tolist()]
+        values = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+        return ListColumn(offsets, np.ascontiguousarray(values, dtype=np.int64), self.present[rows].copy())
+
+
+def encode_list_column(name: str, kind: str, values, codes: Dict[str, int]) -> ListColumn:
+    """One list attribute's values of a batch -> ``ListColumn``.  A value is a list, tuple or set of str (``"str[]"``) or
+    int (``"int[]"``): ``None`` = absent, ``[]`` = an empty list (present), duplicates collapse, the codes are sorted.
+    More than 255 distinct elements, an element of the wrong type or a bare scalar raise ``ValueError`` naming the
+    attribute.  New strings get codes in ``codes`` (a copy of the caller's, kept only if the whole batch is accepted)."""
+    n = len(values)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    present = np.zeros(n, dtype=np.uint8)
+    parts: List[List[int]] = []
+    for i, v in enumerate(values):
+        row: List[int] = []
+        if v is not None:
+            if not isinstance(v, (list, tuple, set, frozenset)):
+                raise ValueError(f"attribute {name!r} ({kind}): row {i} holds {v!r}, not a list, tuple or set")
+            seen = set()
+            for x in v:
+                if kind == "str[]":
+                    if not isinstance(x, str):
+                        raise ValueError(f"attribute {name!r} ({kind}): row {i} holds the element {x!r}")
+                    code = codes.get(x)
+                    if code is None:
+                        code = codes[x] = len(codes)
+                else:
+                    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+                        raise ValueError(f"attribute {name!r} ({kind}): row {i} holds the element {x!r}")
+                    code = int(x)
+                    if not -(2 ** 63) < code < 2 ** 63:
+                        raise ValueError(f"attribute {name!r} ({kind}): row {i} holds {x!r}, outside int64 "
+                                         f"(INT64_MIN marks absent)")
+                seen.add(code)
+            if len(seen) > LIST_MAX_LEN:
+                raise ValueError(f"attribute {name!r} ({kind}): row {i} holds {len(seen)} distinct elements; a list holds "
+                                 f"at most {LIST_MAX_LEN}")
+            row = sorted(seen)
+            present[i] = 1
+        parts.append(row)
+        offsets[i + 1] = offsets[i] + len(row)
+    flat = np.array([c for row in parts for c in row], dtype=np.int64)
+    return ListColumn(offsets, flat, present)
 
 
 def encode_column(name: str, kind: str, values, codes: Dict[str, int]) -> np.ndarray:
