@@ -190,6 +190,19 @@ LIST_SIGNATURES = {
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
+# include/mlvdb_sparse.h: sparse vector columns -- (term, weight) pairs per row in the list column's storage, and their
+# exact top-k inner product with a batch of sparse queries
+ATTR_SPARSE = 4
+LIST_ATTR_CODES["sparse"] = ATTR_SPARSE
+SPARSE_MAX_NNZ = 255
+SPARSE_MAX_QUERY_TERMS = 1024
+SPARSE_SIGNATURES = {
+    "mlvdb_sparse_set": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "mlvdb_sparse_set_at": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "mlvdb_sparse_get": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "mlvdb_search_batch_sparse": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(Where), _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -221,7 +234,7 @@ def load() -> C.CDLL:
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
-                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES}.items():
+                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -149,6 +149,8 @@ struct mlvdb_index {
     int64_t list_cap[MLVDB_MAX_ATTRS] = {};
     int64_t list_used[MLVDB_MAX_ATTRS] = {};
     DevBuf list_sums, list_out;
+    // sparse vector columns (mlvdb_sparse.h): a pass's tiles, term unions and weights; its answers
+    DevBuf sparse_in, sparse_out;
     // per-query filters (mlvdb_where_each.h): the call's programs, one 64-bit word per row, per-segment counts / offsets,
     // match totals, the gathered route's label lists, tiles, queries and outputs
     DevBuf each_prog, each_bits, each_seg, each_tot, each_lab, each_tiles, each_q, each_qpad, each_qaux, each_out;
@@ -264,6 +266,8 @@ const TuningField* find_tuning_field(const char* key, size_t len) {
 
 // ---- attribute columns (mlvdb_where.h): the absent sentinel of a column type, and new column buffers for a capacity change
 int64_t attr_absent(int32_t type) { return type == MLVDB_ATTR_FLOAT64 ? (int64_t)0x7ff8000000000000ll : INT64_MIN; }
+// "has a slot and a pool": list columns (mlvdb_list.h) and sparse vector columns (mlvdb_sparse.h), which share the storage
+bool pooled(int32_t type) { return type == MLVDB_ATTR_INT64_LIST || type == MLVDB_ATTR_SPARSE; }
 
 void attr_release(int64_t* (&cols)[MLVDB_MAX_ATTRS]) {
     for (int64_t*& c : cols) {
@@ -365,7 +369,7 @@ int list_repack(mlvdb_index* h, int a, int64_t rows) {
 
 int list_repack_all(mlvdb_index* h, int64_t rows) {
     for (int a = 0; a < MLVDB_MAX_ATTRS; ++a)
-        if (h->attr_type[a] == MLVDB_ATTR_INT64_LIST && h->attr_col[a])
+        if (pooled(h->attr_type[a]) && h->attr_col[a])
             if (int rc = list_repack(h, a, rows)) return rc;
     return MLVDB_OK;
 }
@@ -1300,7 +1304,8 @@ int mlvdb_index_destroy(mlvdb_index* h) {
                       &h->grp_tab, &h->grp_tiles, &h->grp_out, &h->grp_lab,
                       &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->like_q, &h->like_ex, &h->like_list, &h->like_out,
                       &h->ms_tab, &h->ms_rowdoc, &h->ms_best, &h->ms_misc, &h->ms_out,
-                      &h->facet_tab, &h->facet_misc, &h->order_ws, &h->mutate_ws})
+                      &h->facet_tab, &h->facet_misc, &h->order_ws, &h->mutate_ws, &h->list_sums, &h->list_out,
+                      &h->sparse_in, &h->sparse_out})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
@@ -2147,10 +2152,12 @@ int attr_check(mlvdb_index* h, int32_t attr) {
 }
 
 // ... for the entries that read or write a column's values as scalars: a list column's slots (mlvdb_list.h) are neither
-// integers to rank, bin or group by, nor something a raw write may forge.
+// integers to rank, bin or group by, nor something a raw write may forge; a sparse column's (mlvdb_sparse.h) are the same.
 int scalar_check(mlvdb_index* h, int32_t attr) {
     if (h->attr_type[attr] == MLVDB_ATTR_INT64_LIST)
         return fail(h, MLVDB_ERR_INVALID_ARG, "a list column: this entry needs a scalar column (see mlvdb_list.h)");
+    if (h->attr_type[attr] == MLVDB_ATTR_SPARSE)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse column: this entry needs a scalar column (see mlvdb_sparse.h)");
     return MLVDB_OK;
 }
 
@@ -2186,6 +2193,10 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
                 d.col = h->attr_col[o.attr];
                 if (d.type == MLVDB_ATTR_INT64_LIST && o.op != MLVDB_WHERE_EXISTS)
                     return fail(h, MLVDB_ERR_INVALID_ARG, "a list column takes HAS, HAS_ANY, HAS_ALL, LEN and EXISTS only");
+                if (d.type == MLVDB_ATTR_SPARSE) {
+                    if (o.op != MLVDB_WHERE_EXISTS) return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse column takes EXISTS and LEN only");
+                    d.type = MLVDB_ATTR_INT64_LIST;  // the same slot: the evaluators see a list column
+                }
                 if (o.op == MLVDB_WHERE_IN) {
                     if (d.type != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "IN needs an int64 column");
                     if (o.a < 0 || o.b < 0 || o.a > w->n_set || o.b > w->n_set - o.a)
@@ -2198,6 +2209,10 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
                 if (int rc = attr_check(h, o.attr)) return rc;
                 d.type = h->attr_type[o.attr];
                 d.col = h->attr_col[o.attr];
+                if (d.type == MLVDB_ATTR_SPARSE) {
+                    if (o.op != MLVDB_WHERE_LEN) return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse column takes EXISTS and LEN only");
+                    d.type = MLVDB_ATTR_INT64_LIST;  // the same slot: the evaluators see a list column
+                }
                 if (d.type != MLVDB_ATTR_INT64_LIST) return fail(h, MLVDB_ERR_INVALID_ARG, "HAS, HAS_ANY, HAS_ALL and LEN need a list column");
                 if (o.op == MLVDB_WHERE_LEN) break;  // (its bounds stay in a, b: it reads the slot alone)
                 d.b = (int64_t)reinterpret_cast<intptr_t>(h->list_pool[o.attr]);  // the pool's address rides in b
@@ -2263,7 +2278,7 @@ int mlvdb_attr_define(mlvdb_index* h, int32_t attr, int32_t type) {
     int rc = check_handle(h);
     if (rc) return rc;
     if (attr < 0 || attr >= MLVDB_MAX_ATTRS) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute index out of range");
-    if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64 && type != MLVDB_ATTR_INT64_LIST)
+    if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64 && !pooled(type))
         return fail(h, MLVDB_ERR_INVALID_ARG, "unknown attribute type");
     if (h->attr_type[attr]) {
         if (h->attr_type[attr] != type) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute already defined with another type");
@@ -4110,6 +4125,34 @@ int list_get_impl(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int64_
     return MLVDB_OK;
 }
 
+// The checked CSR written to rows [first, first + n) of a pooled column.
+int list_set_impl(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const int64_t* offsets, const int64_t* values,
+                  const uint8_t* present) {
+    std::vector<int64_t> slots;
+    if (int rc = list_append(h, attr, n, offsets, values, present, slots)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->attr_col[attr] + first, slots.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return MLVDB_OK;
+}
+
+// n >= 1 labels of a by-label write: inside [0, total), none twice.
+int labels_check(mlvdb_index* h, const int64_t* labels, int64_t n) {
+    std::vector<int64_t> sorted(labels, labels + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label outside [0, total)");
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a label appears twice");
+    return MLVDB_OK;
+}
+
+// The checked CSR written to the rows of the checked labels.
+int list_set_at_impl(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const int64_t* offsets,
+                     const int64_t* values, const uint8_t* present, int64_t* updated) {
+    std::vector<int64_t> slots;
+    if (int rc = list_append(h, attr, n, offsets, values, present, slots)) return rc;
+    return attr_set_at_impl(h, attr, labels, n, slots.data(), updated);  // the slots are scattered like any int64 values
+}
+
 int facet_list_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
                            int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
     return facet_values_run(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent, true);
@@ -4127,11 +4170,7 @@ int mlvdb_attr_list_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, 
     if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
     if (n == 0) return MLVDB_OK;
     if ((rc = list_csr_check(h, n, offsets, values, present))) return rc;
-    std::vector<int64_t> slots;
-    if ((rc = list_append(h, attr, n, offsets, values, present, slots))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->attr_col[attr] + first, slots.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return MLVDB_OK;
+    return list_set_impl(h, attr, first, n, offsets, values, present);
     });
 }
 
@@ -4145,15 +4184,9 @@ int mlvdb_attr_list_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, 
     if (!updated || n < 0 || (n > 0 && !labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n");
     *updated = 0;
     if (n == 0) return MLVDB_OK;
-    std::vector<int64_t> sorted(labels, labels + n);
-    std::sort(sorted.begin(), sorted.end());
-    if (sorted.front() < 0 || sorted.back() >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label outside [0, total)");
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-        return fail(h, MLVDB_ERR_INVALID_ARG, "a label appears twice");
+    if ((rc = labels_check(h, labels, n))) return rc;
     if ((rc = list_csr_check(h, n, offsets, values, present))) return rc;
-    std::vector<int64_t> slots;
-    if ((rc = list_append(h, attr, n, offsets, values, present, slots))) return rc;
-    return attr_set_at_impl(h, attr, labels, n, slots.data(), updated);  // the slots are scattered like any int64 values
+    return list_set_at_impl(h, attr, labels, n, offsets, values, present, updated);
     });
 }
 
@@ -4204,7 +4237,8 @@ int mlvdb_attr_list_stats(mlvdb_index* h, int32_t attr, int64_t* pool_used, int6
     return guarded(h, [&]() -> int {
     int rc = check_handle(h);
     if (rc) return rc;
-    if ((rc = list_attr_check(h, attr))) return rc;
+    if ((rc = attr_check(h, attr))) return rc;
+    if (!pooled(h->attr_type[attr])) return fail(h, MLVDB_ERR_INVALID_ARG, "not a list or sparse column");
     if (!pool_used || !pool_live) return fail(h, MLVDB_ERR_INVALID_ARG, "null counter");
     *pool_used = h->list_used[attr];
     return list_scan(h, h->attr_col[attr], h->rn, h->total, pool_live);
@@ -4225,6 +4259,224 @@ int mlvdb_facet_list_values(mlvdb_index* h, int32_t attr, const mlvdb_where* whe
     *n_values = *matched = *absent = 0;
     if (h->total == 0) return MLVDB_OK;
     return facet_list_values_impl(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent);
+    });
+}
+
+// ---- sparse vector columns (mlvdb_sparse.h)
+extern "C++" {
+namespace {
+int sparse_attr_check(mlvdb_index* h, int32_t attr) {
+    if (int rc = attr_check(h, attr)) return rc;
+    if (h->attr_type[attr] != MLVDB_ATTR_SPARSE) return fail(h, MLVDB_ERR_INVALID_ARG, "not a sparse column");
+    return MLVDB_OK;
+}
+
+// One sparse vector: at most max_len entries, terms in [0, 2^31) strictly ascending, weights finite.
+int sparse_vector_check(mlvdb_index* h, const int32_t* terms, const float* weights, int64_t len, int64_t max_len) {
+    if (len < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "sparse offsets must not decrease");
+    if (len > max_len) return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse vector with too many entries");
+    if (len > 0 && (!terms || !weights)) return fail(h, MLVDB_ERR_INVALID_ARG, "terms / weights is null");
+    for (int64_t j = 0; j < len; ++j) {
+        if (terms[j] < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse term must be in [0, 2^31)");
+        if (j > 0 && terms[j - 1] >= terms[j]) return fail(h, MLVDB_ERR_INVALID_ARG, "sparse terms must be strictly ascending");
+        if (!std::isfinite(weights[j])) return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse weight must be finite");
+    }
+    return MLVDB_OK;
+}
+
+// The n row vectors of a CSR checked and packed into pool elements ((int64)term << 32 | bits(weight)) -> packed, indexed
+// like terms from offsets[0] on; nothing is written or launched.
+int sparse_csr_pack(mlvdb_index* h, int64_t n, const int64_t* offsets, const int32_t* terms, const float* weights,
+                    const uint8_t* present, std::vector<int64_t>& packed, std::vector<int64_t>& rebased) {
+    if (!offsets || offsets[0] < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "bad sparse offsets");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i];
+        const bool have = len > 0 && terms && weights;
+        if (int rc = sparse_vector_check(h, have ? terms + offsets[i] : nullptr, have ? weights + offsets[i] : nullptr, len,
+                                         MLVDB_SPARSE_MAX_NNZ))
+            return rc;
+        if (present && !present[i] && len != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "an absent row with entries");
+    }
+    const int64_t base = offsets[0], count = offsets[n] - base;
+    packed.resize((size_t)count);
+    for (int64_t j = 0; j < count; ++j) {
+        uint32_t bits;
+        std::memcpy(&bits, &weights[base + j], sizeof bits);
+        packed[(size_t)j] = ((int64_t)terms[base + j] << 32) | (int64_t)bits;
+    }
+    rebased.resize((size_t)n + 1);
+    for (int64_t i = 0; i <= n; ++i) rebased[(size_t)i] = offsets[i] - base;
+    return MLVDB_OK;
+}
+
+// One pass of at most kSparseChunk queries [q0, q1): tiles, unions and weights up, scan, merge, answers down.
+int sparse_pass(mlvdb_index* h, int32_t attr, const int64_t* off, const int32_t* terms, const float* weights, int64_t q0,
+                int64_t q1, int32_t k, const uint8_t* mask, int64_t* out_labels, float* out_score, int32_t* out_counts,
+                double* out_score64) {
+    hipStream_t s = h->stream;
+    const int32_t n = (int32_t)(q1 - q0);
+    // greedy tiles: consecutive queries while they are <= kSparseQT and their term union holds <= kSparseMaxUnion terms
+    std::vector<SparseTile> tiles;
+    std::vector<int32_t> U, cur, merged;
+    std::vector<float> W;
+    auto close_tile = [&](int32_t tq0, int32_t tq1) {
+        const int32_t u0 = (int32_t)U.size();
+        tiles.push_back(SparseTile{tq0, tq1 - tq0, u0, (int32_t)cur.size()});
+        U.insert(U.end(), cur.begin(), cur.end());
+        W.resize((size_t)U.size() * kSparseQT, 0.0f);
+        for (int32_t q = tq0; q < tq1; ++q)
+            for (int64_t j = off[q0 + q]; j < off[q0 + q + 1]; ++j) {
+                const size_t u = (size_t)(std::lower_bound(cur.begin(), cur.end(), terms[j]) - cur.begin());
+                W[((size_t)u0 + u) * kSparseQT + (size_t)(q - tq0)] = weights[j];
+            }
+    };
+    int32_t tq0 = 0;
+    for (int32_t q = 0; q < n; ++q) {
+        const int32_t* qt = terms + off[q0 + q];
+        const size_t qn = (size_t)(off[q0 + q + 1] - off[q0 + q]);
+        merged.resize(cur.size() + qn);
+        merged.resize((size_t)(std::set_union(cur.begin(), cur.end(), qt, qt + qn, merged.begin()) - merged.begin()));
+        if (q > tq0 && (q - tq0 == kSparseQT || merged.size() > (size_t)kSparseMaxUnion)) {
+            close_tile(tq0, q);
+            tq0 = q;
+            merged.assign(qt, qt + qn);
+        }
+        cur.swap(merged);
+    }
+    close_tile(tq0, n);
+    const int32_t ntiles = (int32_t)tiles.size();
+    const size_t nk = (size_t)n * k;
+    const int32_t nblk = sparse_scan_blocks(h->total, n, k);
+    // [tiles | U | W], all 4-byte fields
+    const size_t tbytes = tiles.size() * sizeof(SparseTile), ubytes = U.size() * sizeof(int32_t), wbytes = W.size() * sizeof(float);
+    HIP_TRY(h, h->sparse_in.ensure(tbytes + ubytes + wbytes + 16));
+    HIP_TRY(h, h->sparse_out.ensure(ListBlock::bytes(nk, (size_t)n)));
+    HIP_TRY(h, h->partial.ensure(nk * (size_t)nblk * sizeof(TopEntry)));
+    char* in = h->sparse_in.as<char>();
+    HIP_TRY(h, hipMemcpyAsync(in, tiles.data(), tbytes, hipMemcpyHostToDevice, s));
+    if (ubytes) HIP_TRY(h, hipMemcpyAsync(in + tbytes, U.data(), ubytes, hipMemcpyHostToDevice, s));
+    if (wbytes) HIP_TRY(h, hipMemcpyAsync(in + tbytes + ubytes, W.data(), wbytes, hipMemcpyHostToDevice, s));
+    const ListBlock o(h->sparse_out.p, nk, (size_t)n);
+    HIP_TRY(h, launch_sparse_scan(h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total,
+                                  reinterpret_cast<const SparseTile*>(in), ntiles, reinterpret_cast<const int32_t*>(in + tbytes),
+                                  reinterpret_cast<const float*>(in + tbytes + ubytes), k, nblk, h->partial.as<TopEntry>(), s));
+    HIP_TRY(h, launch_sparse_merge(h->partial.as<TopEntry>(), n, nblk, k, o.lab, o.dist, o.cnt, o.d64, s));
+    const size_t at = (size_t)q0 * k;
+    HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
+    HIP_TRY(h, hipMemcpyAsync(out_labels + at, o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_score + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (out_score64) HIP_TRY(h, hipMemcpyAsync(out_score64 + at, o.d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_sparse_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const int64_t* offsets, const int32_t* terms,
+                     const float* weights, const uint8_t* present) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = sparse_attr_check(h, attr))) return rc;
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (n == 0) return MLVDB_OK;
+    std::vector<int64_t> packed, rebased;
+    if ((rc = sparse_csr_pack(h, n, offsets, terms, weights, present, packed, rebased))) return rc;
+    return list_set_impl(h, attr, first, n, rebased.data(), packed.data(), present);
+    });
+}
+
+int mlvdb_sparse_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const int64_t* offsets,
+                        const int32_t* terms, const float* weights, const uint8_t* present, int64_t* updated) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = sparse_attr_check(h, attr))) return rc;
+    if (!updated || n < 0 || (n > 0 && !labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n");
+    *updated = 0;
+    if (n == 0) return MLVDB_OK;
+    if ((rc = labels_check(h, labels, n))) return rc;
+    std::vector<int64_t> packed, rebased;
+    if ((rc = sparse_csr_pack(h, n, offsets, terms, weights, present, packed, rebased))) return rc;
+    return list_set_at_impl(h, attr, labels, n, rebased.data(), packed.data(), present, updated);
+    });
+}
+
+int mlvdb_sparse_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int64_t* out_offsets, int32_t* out_terms,
+                     float* out_weights, uint8_t* out_present, int64_t capacity, int64_t* needed) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((rc = sparse_attr_check(h, attr))) return rc;
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (!needed || !out_offsets || capacity < 0 || (capacity > 0 && (!out_terms || !out_weights)))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
+    *needed = 0;
+    if (n == 0) {
+        out_offsets[0] = 0;
+        return MLVDB_OK;
+    }
+    // the list read-back into a buffer of exactly the size its first launches report, then unpacked
+    if ((rc = list_scan(h, h->attr_col[attr] + first, nullptr, n, needed))) return rc;
+    if (capacity < *needed) return MLVDB_OK;
+    std::vector<int64_t> packed((size_t)*needed);
+    if ((rc = list_get_impl(h, attr, first, n, out_offsets, packed.data(), out_present, *needed, needed))) return rc;
+    for (size_t j = 0; j < packed.size(); ++j) {
+        out_terms[j] = (int32_t)(packed[j] >> 32);
+        const uint32_t bits = (uint32_t)(packed[j] & 0xffffffffll);
+        std::memcpy(&out_weights[j], &bits, sizeof bits);
+    }
+    return MLVDB_OK;
+    });
+}
+
+int mlvdb_search_batch_sparse(mlvdb_index* h, int32_t attr, const int64_t* q_offsets, const int32_t* q_terms,
+                              const float* q_weights, int64_t nq, int32_t k, const mlvdb_where* where, int64_t* out_labels,
+                              float* out_score, int32_t* out_counts, double* out_score64) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked on the host before anything is launched
+    if ((rc = sparse_attr_check(h, attr))) return rc;
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "sparse search: k above MLVDB_MAX_TOPK");
+    if (nq > 0 && (!q_offsets || !out_labels || !out_score || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (nq > 0 && q_offsets[0] != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "sparse search: q_offsets must start at 0");
+    for (int64_t i = 0; i < nq; ++i) {
+        const int64_t len = q_offsets[i + 1] - q_offsets[i];
+        const bool have = len > 0 && q_terms && q_weights;
+        if ((rc = sparse_vector_check(h, have ? q_terms + q_offsets[i] : nullptr, have ? q_weights + q_offsets[i] : nullptr, len,
+                                      MLVDB_SPARSE_MAX_QUERY_TERMS)))
+            return rc;
+    }
+    if (h->total > INT32_MAX) return fail(h, MLVDB_ERR_UNSUPPORTED, "sparse search: more than 2^31 - 1 rows");
+    if (where && (rc = where_prepare(h, where))) return rc;
+    if (nq == 0) return MLVDB_OK;
+    if (h->total == 0) {
+        for (int64_t i = 0; i < nq * k; ++i) {
+            out_labels[i] = -1;
+            out_score[i] = -__builtin_inff();
+            if (out_score64) out_score64[i] = -__builtin_inf();
+        }
+        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        return MLVDB_OK;
+    }
+    const uint8_t* mask = nullptr;
+    if (where) {  // the program into h->row_mask (live matching rows), which every pass reads at one byte per row
+        if ((rc = where_run(h, where, nullptr))) return rc;
+        mask = h->row_mask.as<uint8_t>();
+    }
+    for (int64_t q0 = 0; q0 < nq; q0 += kSparseChunk) {
+        const int64_t q1 = std::min<int64_t>(nq, q0 + kSparseChunk);
+        if ((rc = sparse_pass(h, attr, q_offsets, q_terms, q_weights, q0, q1, k, mask, out_labels, out_score, out_counts,
+                              out_score64)))
+            return rc;
+    }
+    return MLVDB_OK;
     });
 }
 

@@ -21,6 +21,7 @@
 #include "../../include/mlvdb_maxsim.h"
 #include "../../include/mlvdb_mutate.h"
 #include "../../include/mlvdb_list.h"
+#include "../../include/mlvdb_sparse.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -385,6 +386,25 @@ hipError_t launch_list_scan_sums(int64_t* sums, int64_t nblocks, hipStream_t s);
 // out_present[i] = 0 for an absent row -- each of the three may be null
 hipError_t launch_list_move(const int64_t* slots, int64_t n, const int64_t* sums, const int64_t* pool, int64_t* out_pool,
                             int64_t* out_slots, int64_t* out_offsets, uint8_t* out_present, hipStream_t s);
+
+// ---------------------------------------------------------------- sparse vector columns (kernels_sparse.hip, include/mlvdb_sparse.h)
+constexpr int kSparseQT = 8;            // queries per tile
+constexpr int kSparseMaxUnion = 1024;   // terms in a tile's union (= MLVDB_SPARSE_MAX_QUERY_TERMS: a query alone always fits)
+constexpr int kSparseMaxBlocks = 1024;  // blocks per tile: beyond 16 * kSparseMaxBlocks rows the blocks stride
+constexpr int kSparseChunk = 256;       // queries per pass
+// queries [q0, q0 + nq) of the pass; their sorted term union U[u0, u0 + nu) and weights W[(u0 + u) * kSparseQT + i]
+struct SparseTile {
+    int32_t q0, nq, u0, nu;
+};
+int32_t sparse_scan_blocks(int64_t total, int64_t nq, int32_t k);
+// partial[(q * nblk + block) * k ..] = the block's k best (-score, row) of query q over the live rows with a present slot
+// (mask != nullptr: whose mask byte is set too)
+hipError_t launch_sparse_scan(const int64_t* slots, const int64_t* pool, const float* rn, const uint8_t* mask, int64_t total,
+                              const SparseTile* tiles, int32_t ntiles, const int32_t* U, const float* W, int32_t k,
+                              int32_t nblk, TopEntry* partial, hipStream_t s);
+// ... folded: labels (-1), scores (float and double, -inf) and counts of nq queries
+hipError_t launch_sparse_merge(const TopEntry* partial, int32_t nq, int32_t nblk, int32_t k, int64_t* out_labels,
+                               float* out_score, int32_t* out_counts, double* out_s64, hipStream_t s);
 
 // rn[i] = NaN for the rows of mask, and their int8 row pairs (i < i8_rows; rp8 may be null) as tombstone_rp8_kernel does
 hipError_t launch_tombstone_mask(const uint8_t* mask, float* rn, float* rp8, int64_t i8_rows, int l2, int64_t total,

@@ -235,8 +235,8 @@ class HipScanEngine:
 
     # -- metadata filters (include/mlvdb_where.h) ------------------------------------
     def define_attr(self, attr: int, kind: str) -> None:
-        """Column ``attr`` (0..15) of type "int64" (absent = INT64_MIN), "float64" (absent = NaN) or "int64_list" (a set of
-        int64 per row, include/mlvdb_list.h), every row absent."""
+        """Column ``attr`` (0..15) of type "int64" (absent = INT64_MIN), "float64" (absent = NaN), "int64_list" (a set of
+        int64 per row, include/mlvdb_list.h) or "sparse" (a sparse vector per row, include/mlvdb_sparse.h), every row absent."""
         code = _native.LIST_ATTR_CODES[kind] if kind in _native.LIST_ATTR_CODES else _native.ATTR_CODES[kind]
         self._check(self._lib.mlvdb_attr_define(self._h, int(attr), code), "attr_define")
         self._attr_kinds[int(attr)] = kind
@@ -396,6 +396,86 @@ class HipScanEngine:
         if rc == _native.ERR_OVERFLOW:
             raise FacetOverflow(max_values, int(n.value), int(matched.value), int(absent.value))
         return values[: n.value].copy(), counts[: n.value].copy(), int(matched.value), int(absent.value)
+
+    # -- sparse vector columns (include/mlvdb_sparse.h) ----------------------------------
+    @staticmethod
+    def _sparse_csr(col):
+        """A ``where.SparseColumn`` as the contiguous arrays the C entries take (kept alive by the caller for the call)."""
+        offsets = np.ascontiguousarray(col.offsets, dtype=np.int64)
+        terms = np.ascontiguousarray(col.terms, dtype=np.int32)
+        weights = np.ascontiguousarray(col.weights, dtype=np.float32)
+        present = np.ascontiguousarray(col.present, dtype=np.uint8)
+        if offsets.size != present.size + 1 or terms.size != weights.size:
+            raise RuntimeError(f"{present.size} rows but {offsets.size} offsets, {terms.size} terms and {weights.size} weights")
+        return offsets, terms, weights, present
+
+    def set_attr_sparse(self, attr: int, first: int, col) -> None:
+        """The vectors of rows first..first+len(col)-1 of sparse column ``attr`` (``col``: a ``where.SparseColumn``)."""
+        offsets, terms, weights, present = self._sparse_csr(col)
+        self._check(self._lib.mlvdb_sparse_set(self._h, int(attr), int(first), present.size, offsets.ctypes.data,
+                                               terms.ctypes.data if terms.size else None,
+                                               weights.ctypes.data if weights.size else None, present.ctypes.data),
+                    "sparse_set")
+
+    def set_attr_sparse_at(self, attr: int, labels: np.ndarray, col) -> int:
+        """Vector i of ``col`` -> row ``labels[i]`` (distinct labels in [0, total); tombstoned rows are skipped); returns the
+        rows written."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        offsets, terms, weights, present = self._sparse_csr(col)
+        if present.size != labels.size:
+            raise RuntimeError(f"{labels.size} labels but {present.size} vectors")
+        n = C.c_int64(0)
+        self._check(self._lib.mlvdb_sparse_set_at(self._h, int(attr), labels.ctypes.data, labels.size, offsets.ctypes.data,
+                                                  terms.ctypes.data if terms.size else None,
+                                                  weights.ctypes.data if weights.size else None, present.ctypes.data,
+                                                  C.byref(n)), "sparse_set_at")
+        return int(n.value)
+
+    def get_attr_sparse(self, attr: int, first: int, n: int):
+        """The vectors of rows first..first+n-1 as a ``where.SparseColumn`` (tombstoned rows keep what they hold)."""
+        from .where import SparseColumn
+
+        n = int(n)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        present = np.zeros(n, dtype=np.uint8)
+        terms = np.empty(0, dtype=np.int32)
+        weights = np.empty(0, dtype=np.float32)
+        needed = C.c_int64(0)
+        for _ in range(2):  # the first call sizes the entries, the second reads them
+            self._check(self._lib.mlvdb_sparse_get(self._h, int(attr), int(first), n, offsets.ctypes.data,
+                                                   terms.ctypes.data if terms.size else None,
+                                                   weights.ctypes.data if weights.size else None, present.ctypes.data,
+                                                   terms.size, C.byref(needed)), "sparse_get")
+            if needed.value <= terms.size:
+                break
+            terms = np.empty(needed.value, dtype=np.int32)
+            weights = np.empty(needed.value, dtype=np.float32)
+        return SparseColumn(offsets, terms[: needed.value], weights[: needed.value], present)
+
+    def search_batch_sparse(self, attr: int, queries, k: int, where=None):
+        """Exact lexical kNN (``mlvdb_search_batch_sparse``): ``queries`` is a ``where.SparseColumn`` (its ``present`` is
+        ignored: every query is one, an empty one ranks by label), ``where`` a compiled filter or ``None``.  Returns
+        (labels int64 [nq, k] padded -1, scores float32 [nq, k] padded -inf, counts int32 [nq], scores float64 [nq, k]):
+        the rows with a vector ranked by (inner product descending, label ascending)."""
+        offsets = np.ascontiguousarray(queries.offsets, dtype=np.int64)
+        terms = np.ascontiguousarray(queries.terms, dtype=np.int32)
+        weights = np.ascontiguousarray(queries.weights, dtype=np.float32)
+        nq, k = offsets.size - 1, int(k)
+        if nq < 0 or terms.size != weights.size:
+            raise RuntimeError(f"{offsets.size} offsets, {terms.size} terms and {weights.size} weights")
+        shape = (nq, max(k, 0))
+        labels = np.empty(shape, dtype=np.int64)
+        score = np.empty(shape, dtype=np.float32)
+        score64 = np.empty(shape, dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.int32)
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_search_batch_sparse(self._h, int(attr), offsets.ctypes.data,
+                                                        terms.ctypes.data if terms.size else None,
+                                                        weights.ctypes.data if weights.size else None, nq, k,
+                                                        None if w is None else C.byref(w), labels.ctypes.data,
+                                                        score.ctypes.data, counts.ctypes.data, score64.ctypes.data),
+                    "search_batch_sparse")
+        return labels, score, counts, score64
 
     # -- per-query filters (include/mlvdb_where_each.h) -------------------------------
     @staticmethod

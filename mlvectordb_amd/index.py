@@ -262,8 +262,9 @@ class Index:
         for name, kind in attributes.items():
             if not isinstance(name, str) or name.startswith("$"):
                 raise ValueError(f"attribute name {name!r}: a string not starting with '$'")
-            if kind not in _where.ATTR_TYPES + _where.LIST_TYPES:
-                raise ValueError(f"attribute {name!r}: type {kind!r} is not one of {_where.ATTR_TYPES + _where.LIST_TYPES}")
+            if kind not in _where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES:
+                raise ValueError(f"attribute {name!r}: type {kind!r} is not one of "
+                                 f"{_where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES}")
         return attributes
 
     @property
@@ -322,6 +323,11 @@ class Index:
                 if col.present.any():
                     out[i] = col
                 continue
+            if _where.is_sparse(kind):
+                col = _where.encode_sparse_column(name, values)
+                if col.present.any():
+                    out[i] = col
+                continue
             col = _where.encode_column(name, kind, values, strings.setdefault(name, {}) if kind == "str" else {})
             present = ~np.isnan(col) if col.dtype == np.float64 else col != _where.INT64_ABSENT
             if present.any():
@@ -335,7 +341,20 @@ class Index:
             raise ValueError(f"list attributes need an engine with {method} (a single-device namespace)")
         return fn
 
+    @staticmethod
+    def _sparse_engine(ns: _Namespace, method: str):
+        fn = getattr(ns.engine, method, None)
+        if fn is None:
+            raise ValueError(f"sparse attributes need an engine with {method} (a single-device namespace)")
+        return fn
+
+    def _check_sparse(self, what: str, name: str) -> None:
+        if _where.is_sparse(self._attributes[name]):
+            raise ValueError(f"{what}: attribute {name!r} is a sparse column; it needs a scalar attribute "
+                             f"(a sparse vector is searched with search_sparse)")
+
     def _check_scalar(self, what: str, name: str) -> None:
+        self._check_sparse(what, name)
         if _where.is_list(self._attributes[name]):
             raise ValueError(f"{what}: attribute {name!r} is a {self._attributes[name]} column; it needs a scalar attribute "
                              f"(a list has no one value to rank, bin or group by)")
@@ -354,6 +373,8 @@ class Index:
         for i, col in cols.items():
             if isinstance(col, _where.ListColumn):
                 Index._list_engine(ns, "set_attr_list")(i, first, col)
+            elif isinstance(col, _where.SparseColumn):
+                Index._sparse_engine(ns, "set_attr_sparse")(i, first, col)
             else:
                 ns.engine.set_attr(i, first, col)
         if strings is not None:
@@ -790,6 +811,47 @@ class Index:
             m_d64 = np.where(m_lab >= 0, 1 - m_d64, np.inf) if metric == "cosine" else m_d64
         return LateBatchHits(self._decode_groups(ns, by, kind, codes, counts), scores, counts, offsets, ns.ids, m_lab, m_d64)
 
+    _MAX_TOP_K_SPARSE = 64  # MLVDB_MAX_TOPK: one selection list of a wavefront
+
+    def search_sparse(self, queries, top_k: int, namespace: str, by: str, *, where: Optional[Mapping] = None) -> BatchHits:
+        """Additive: exact lexical kNN over the declared ``sparse`` attribute ``by`` on the device
+        (include/mlvdb_sparse.h).  ``queries`` is a sequence of sparse vectors -- each a mapping ``{term: weight}`` or a pair
+        ``(indices, values)``, at most 1024 nonzeros, typed as at ingest -- and every live row that holds a vector (an empty
+        one included) is a candidate; ``where`` (one dict filter) restricts the rows first.  Per query the ``top_k`` rows
+        with the largest inner product come back, ties to the earlier row; ``scores`` is the fp64 dot product.  ``top_k`` is
+        clamped to the live row count and to 64.  Every refusal happens before the engine is touched."""
+        if self._devices is not None and len(self._devices) > 1:
+            raise ValueError("search_sparse is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        if not isinstance(by, str) or by not in self._attributes:
+            raise ValueError(f"search_sparse: {by!r} is not a declared attribute of this index "
+                             f"(declared: {sorted(self._attributes)})")
+        if not _where.is_sparse(self._attributes[by]):
+            raise ValueError(f"search_sparse: attribute {by!r} is a {self._attributes[by]} column; it needs a sparse attribute")
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"search_sparse: where must be one dict filter or None (got {type(where).__name__})")
+        if isinstance(queries, Mapping) or isinstance(queries, (str, bytes)):
+            raise ValueError("search_sparse: queries is a sequence of sparse vectors (got one mapping: wrap it in a list)")
+        queries = list(queries)
+        offsets = np.zeros(len(queries) + 1, dtype=np.int64)
+        terms: List[int] = []
+        weights: List[float] = []
+        for i, q in enumerate(queries):
+            t, w = _where.encode_sparse_vector(q, f"search_sparse: query {i}", _where.SPARSE_MAX_QUERY_TERMS)
+            terms.extend(t)
+            weights.extend(w)
+            offsets[i + 1] = len(terms)
+        program = None if where is None else self._compile(namespace, where)
+        nq = len(queries)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0:
+            return BatchHits.empty(nq)
+        search = self._sparse_engine(ns, "search_batch_sparse")
+        k = min(int(top_k), ns.total - ns.deleted, self._MAX_TOP_K_SPARSE)
+        col = _where.SparseColumn(offsets, np.array(terms, dtype=np.int32), np.array(weights, dtype=np.float32),
+                                  np.ones(nq, dtype=np.uint8))
+        labels, _, counts, s64 = search(list(self._attributes).index(by), col, k, where=program)
+        return BatchHits(labels, s64, counts, ns.ids)
+
     _MAX_TOP_K_MMR = 64      # MLVDB_MAX_TOPK
     _MAX_FETCH_K_MMR = 1024  # MLVDB_MMR_MAX_FETCH: the longest candidate list the selection walks
 
@@ -1089,6 +1151,8 @@ class Index:
             if _where.is_list(kind):
                 col = _where.encode_list_column(name, kind, [patches[j][name] for j in pos],
                                                 strings.setdefault(name, {}) if kind == "str[]" else {})
+            elif _where.is_sparse(kind):
+                col = _where.encode_sparse_column(name, [patches[j][name] for j in pos])
             else:
                 col = _where.encode_column(name, kind, [patches[j][name] for j in pos],
                                            strings.setdefault(name, {}) if kind == "str" else {})
@@ -1122,6 +1186,9 @@ class Index:
             if rows.size and isinstance(col, _where.ListColumn):
                 self._list_engine(ns, "set_attr_list_at")(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
                 touched.append(rows)
+            elif rows.size and isinstance(col, _where.SparseColumn):
+                self._sparse_engine(ns, "set_attr_sparse_at")(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
+                touched.append(rows)
             elif rows.size:
                 set_at(i, rows, col[keep][lab.size - 1 - last])
                 touched.append(rows)
@@ -1144,6 +1211,9 @@ class Index:
             if name not in values:
                 continue
             v = values[name]
+            if _where.is_sparse(kind):
+                raise ValueError(f"update_where: {name!r} is a sparse attribute: one vector for every matching row is not "
+                                 f"supported, use update_attributes with ids")
             if _where.is_list(kind):  # one list for every matching row, or None: (column, "list", sorted codes or None)
                 if isinstance(v, Mapping):
                     raise ValueError(f"update_where: {name!r} is a {kind} attribute: it takes a list or None, no operator "
@@ -1289,6 +1359,7 @@ class Index:
             if name not in self._attributes:
                 raise ValueError(f"facets: {name!r} is not a declared attribute of this index "
                                  f"(declared: {sorted(self._attributes)})")
+            self._check_sparse("facets", name)
             if self._attributes[name] == "float":
                 raise ValueError(f"facets: attribute {name!r} is a float column; value facets need an int, str or bool "
                                  f"attribute (histogram() bins floats)")
@@ -1515,6 +1586,9 @@ class Index:
     _FORMAT = "mlvdb-index-v1"
     _FORMAT_V2 = "mlvdb-index-v2"
     _FORMAT_V3 = "mlvdb-index-v3"  # v2 + per list attribute the live rows' lists in CSR form (offsets.i64, values.i64)
+    # v3 + per sparse attribute the live rows' vectors in CSR form (offsets.i64, terms.i32, weights.f32); written only by
+    # an index that declares a sparse attribute
+    _FORMAT_V4 = "mlvdb-index-v4"
     _CHUNK_BYTES = 256 << 20
 
     def save_index(self, path: str) -> bool:
@@ -1522,8 +1596,10 @@ class Index:
         chunks, so host memory stays bounded."""
         os.makedirs(path, exist_ok=True)
         has_lists = any(_where.is_list(kind) for kind in self._attributes.values())
-        meta = {"format": self._FORMAT_V3 if has_lists else self._FORMAT_V2 if self._attributes else self._FORMAT,
-                "space": self._space,
+        has_sparse = any(_where.is_sparse(kind) for kind in self._attributes.values())
+        fmt = self._FORMAT_V4 if has_sparse else self._FORMAT_V3 if has_lists else self._FORMAT_V2 if self._attributes else \
+            self._FORMAT
+        meta = {"format": fmt, "space": self._space,
                 "rebuild_threshold": self._rebuild_threshold, "namespaces": []}
         if self._attributes:
             meta["attributes"] = dict(self._attributes)
@@ -1544,6 +1620,9 @@ class Index:
                     col = self._attr_file(path, i, j, kind)
                     if _where.is_list(kind):
                         self._save_list(ns, j, col, dead)
+                        continue
+                    if _where.is_sparse(kind):
+                        self._save_sparse(ns, j, col, dead)
                         continue
                     dtype = np.float64 if kind == "float" else np.int64
                     (ns.engine.get_attr(j, 0, ns.total, dtype) if ns.total else np.zeros(0, dtype)).tofile(col)
@@ -1581,6 +1660,34 @@ class Index:
         (np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)).astype(np.int64).tofile(
             col_file[:-len("i64")] + "values.i64")
 
+    @classmethod
+    def _save_sparse(cls, ns: _Namespace, j: int, col_file: str, dead: np.ndarray) -> None:
+        """A sparse attribute of a v4 snapshot: the column file holds each row's number of nonzeros (INT64_MIN: no vector),
+        and next to it ``.offsets.i64`` / ``.terms.i32`` / ``.weights.f32`` hold the vectors of the live rows in CSR form;
+        a tombstoned row is written without a vector."""
+        lens = np.full(ns.total, _where.INT64_ABSENT, dtype=np.int64)
+        offsets = np.zeros(ns.total + 1, dtype=np.int64)
+        terms, weights = [], []
+        chunk = 1 << 20
+        for first in range(0, ns.total, chunk):
+            n = min(chunk, ns.total - first)
+            got = cls._sparse_engine(ns, "get_attr_sparse")(j, first, n)
+            live = got.present.astype(bool)
+            live[dead[(dead >= first) & (dead < first + n)] - first] = False
+            rows = np.flatnonzero(live)
+            kept = got.take(rows)
+            n_each = np.zeros(n, dtype=np.int64)
+            n_each[rows] = kept.offsets[1:] - kept.offsets[:-1]
+            lens[first:first + n][live] = n_each[live]
+            offsets[first + 1:first + n + 1] = offsets[first] + np.cumsum(n_each)
+            terms.append(kept.terms)
+            weights.append(kept.weights)
+        base = col_file[:-len("i64")]
+        lens.tofile(col_file)
+        offsets.tofile(base + "offsets.i64")
+        (np.concatenate(terms) if terms else np.zeros(0, np.int32)).astype(np.int32).tofile(base + "terms.i32")
+        (np.concatenate(weights) if weights else np.zeros(0, np.float32)).astype(np.float32).tofile(base + "weights.f32")
+
     @staticmethod
     def _attr_file(path: str, i: int, j: int, kind: str) -> str:
         return os.path.join(path, f"ns{i}.attr{j}.{'f64' if kind == 'float' else 'i64'}")
@@ -1593,9 +1700,10 @@ class Index:
             return False
         with open(manifest) as f:
             meta = json.load(f)
-        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2, self._FORMAT_V3):
+        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4):
             raise RuntimeError(f"unknown index format {meta.get('format')!r}")
-        v2 = meta["format"] in (self._FORMAT_V2, self._FORMAT_V3)  # (v3: v2 with list attributes)
+        # (v3: v2 with list attributes, v4: v3 with sparse attributes)
+        v2 = meta["format"] in (self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4)
         # v2: the snapshot's attributes replace the declared ones; v1: the declared ones stay, every value absent
         attributes = self._check_schema(meta.get("attributes", {})) if v2 else self._attributes
         if v2 and attributes and self._devices is not None and len(self._devices) > 1:
@@ -1611,10 +1719,17 @@ class Index:
             for j, kind in enumerate(attributes.values()):
                 if v2 and _where.is_list(kind):
                     base = self._attr_file(path, i, j, kind)[:-len("i64")]
-                    if meta["format"] != self._FORMAT_V3 or not os.path.isfile(base + "values.i64") or \
+                    if meta["format"] not in (self._FORMAT_V3, self._FORMAT_V4) or not os.path.isfile(base + "values.i64") or \
                             not os.path.isfile(base + "offsets.i64") or \
                             os.path.getsize(base + "offsets.i64") != (total + 1) * 8:
                         raise RuntimeError(f"namespace {m['name']!r}: list attribute files do not match the manifest")
+                if v2 and _where.is_sparse(kind):
+                    base = self._attr_file(path, i, j, kind)[:-len("i64")]
+                    if meta["format"] != self._FORMAT_V4 or not os.path.isfile(base + "terms.i32") or \
+                            not os.path.isfile(base + "weights.f32") or not os.path.isfile(base + "offsets.i64") or \
+                            os.path.getsize(base + "offsets.i64") != (total + 1) * 8 or \
+                            os.path.getsize(base + "terms.i32") != os.path.getsize(base + "weights.f32"):
+                        raise RuntimeError(f"namespace {m['name']!r}: sparse attribute files do not match the manifest")
         self.close()
         self._attributes = attributes
         self._space = meta["space"]
@@ -1643,6 +1758,13 @@ class Index:
                                                   np.fromfile(base + "values.i64", dtype=np.int64),
                                                   (col != _where.INT64_ABSENT).astype(np.uint8))
                         self._list_engine(ns, "set_attr_list")(j, 0, lists)
+                    elif col.size and _where.is_sparse(kind):
+                        base = self._attr_file(path, i, j, kind)[:-len("i64")]
+                        vectors = _where.SparseColumn(np.fromfile(base + "offsets.i64", dtype=np.int64),
+                                                      np.fromfile(base + "terms.i32", dtype=np.int32),
+                                                      np.fromfile(base + "weights.f32", dtype=np.float32),
+                                                      (col != _where.INT64_ABSENT).astype(np.uint8))
+                        self._sparse_engine(ns, "set_attr_sparse")(j, 0, vectors)
                     elif col.size:
                         ns.engine.set_attr(j, 0, col)
                 ns.strings = {a: {s: c for c, s in enumerate(values)} for a, values in m.get("strings", {}).items()}

@@ -149,6 +149,21 @@ class QueryProcessor:
             out.append(entry)
         return out
 
+    def find_similar_sparse(self, query, top_k: int, namespace: str = "default", by: str = "", where=None) -> List[dict]:
+        """Additive: lexical search for one sparse query -- a mapping ``{term: weight}`` or a pair ``(indices, values)`` --
+        over the declared ``sparse`` attribute ``by`` (``Index.search_sparse``): the ``top_k`` (<= 64) vectors with the
+        largest inner product, as ``find_similar_many`` returns a hit (``score``: the dot product)."""
+        return self.find_similar_sparse_many([query], top_k, namespace, by, where=where)[0]
+
+    def find_similar_sparse_many(self, queries, top_k: int, namespace: str = "default", by: str = "",
+                                 where=None) -> List[List[dict]]:
+        """Batched ``find_similar_sparse``: one sparse vector per query, one scan.  ``where`` is ``None`` or one dict filter."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("find_similar_sparse: where must be one dict filter (or None)")
+        if not hasattr(self._index, "search_sparse"):
+            raise ValueError("find_similar_sparse needs an index with search_sparse")
+        return self._enrich_many(self._index.search_sparse(queries, top_k, namespace, by, where=where), namespace)
+
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
         if where is None:
             return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric)

@@ -25,6 +25,9 @@ List attributes (``"str[]"`` / ``"int[]"``: a set of at most 255 tags per row, i
 
 A string never ingested matches nothing, so ``$all`` with one is false as a whole.  ``$lt`` .. ``$gte`` on a list
 attribute, and ``$all`` / ``$size`` on a scalar one, are a ``ValueError``.
+
+A sparse attribute (``"sparse"``: at most 255 (term, weight) pairs per row, include/mlvdb_sparse.h) takes ``$exists`` and
+``$size`` (the number of its nonzeros) only; an empty vector ``{}`` exists.  Everything else on it is a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -38,6 +41,9 @@ import numpy as np
 ATTR_TYPES = ("int", "float", "str", "bool")
 LIST_TYPES = ("str[]", "int[]")  # list-valued attributes: a set of strings / ints per row
 LIST_MAX_LEN = 255               # MLVDB_LIST_MAX_LEN
+SPARSE_TYPES = ("sparse",)       # sparse vectors: (term, weight) pairs per row, searched by Index.search_sparse
+SPARSE_MAX_NNZ = 255             # MLVDB_SPARSE_MAX_NNZ
+SPARSE_MAX_QUERY_TERMS = 1024    # MLVDB_SPARSE_MAX_QUERY_TERMS
 MAX_ATTRS = 16
 MAX_OPS = 64
 MAX_DEPTH = 32
@@ -71,9 +77,20 @@ def is_list(attr_type: str) -> bool:
     return attr_type in LIST_TYPES
 
 
+def is_sparse(attr_type: str) -> bool:
+    return attr_type in SPARSE_TYPES
+
+
+def is_pooled(attr_type: str) -> bool:
+    """A list or a sparse attribute: the column holds slots into a pool, not values."""
+    return is_list(attr_type) or is_sparse(attr_type)
+
+
 def column_kind(attr_type: str) -> str:
-    """The device column type of an attribute type: float -> float64, a list type -> int64_list, everything else -> int64."""
-    return "float64" if attr_type == "float" else "int64_list" if is_list(attr_type) else "int64"
+    """The device column type of an attribute type: float -> float64, a list type -> int64_list, sparse -> sparse,
+    everything else -> int64."""
+    return "float64" if attr_type == "float" else "int64_list" if is_list(attr_type) else \
+        "sparse" if is_sparse(attr_type) else "int64"
 
 
 class _Builder:
@@ -153,7 +170,14 @@ class _Builder:
 
     def field(self, key: str, op: str, value: Any) -> None:
         attr, kind = self.index[key], self.schema[key]
-        if op in _LIST_ONLY and not is_list(kind):
+        if is_sparse(kind):
+            if op == "$size":
+                self.size(key, attr, value)
+                return
+            if op != "$exists":
+                raise ValueError(f"{key!r} is a sparse attribute: only $exists and $size apply (it is searched with "
+                                 f"search_sparse, not filtered by value)")
+        if op in _LIST_ONLY and not is_pooled(kind):
             raise ValueError(f"{key!r} is a {kind} attribute: {op} applies to list attributes ({', '.join(LIST_TYPES)}) only")
         if is_list(kind) and op != "$exists":
             self.list_field(key, attr, kind, op, value)
@@ -412,6 +436,96 @@ def encode_list_column(name: str, kind: str, values, codes: Dict[str, int]) -> L
         offsets[i + 1] = offsets[i] + len(row)
     flat = np.array([c for row in parts for c in row], dtype=np.int64)
     return ListColumn(offsets, flat, present)
+
+
+@dataclass
+class SparseColumn:
+    """A batch of a sparse attribute in CSR form, as ``mlvdb_sparse_set`` takes it: row i holds the pairs
+    ``(terms[j], weights[j])`` for j in ``offsets[i]:offsets[i + 1]`` (terms strictly ascending) when ``present[i]``, and
+    no vector at all otherwise."""
+
+    offsets: np.ndarray  # int64 [n + 1], offsets[0] == 0
+    terms: np.ndarray    # int32
+    weights: np.ndarray  # float32
+    present: np.ndarray  # uint8 [n]
+
+    def __len__(self) -> int:
+        return int(self.present.size)
+
+    def row(self, i: int):
+        """Row i as a dict term -> weight, or ``None``."""
+        if not self.present[i]:
+            return None
+        lo, hi = int(self.offsets[i]), int(self.offsets[i + 1])
+        return dict(zip(self.terms[lo:hi].tolist(), self.weights[lo:hi].tolist()))
+
+    def take(self, rows) -> "SparseColumn":
+        """The rows ``rows`` (indices, in that order) as a column of their own."""
+        rows = np.asarray(rows, dtype=np.int64)
+        lens = (self.offsets[1:] - self.offsets[:-1])[rows]
+        offsets = np.zeros(rows.size + 1, dtype=np.int64)
+        np.cumsum(lens, out=offsets[1:])
+        pick = [np.arange(self.offsets[r], self.offsets[r + 1]) for r in rows.tolist()]
+        pick = np.concatenate(pick).astype(np.int64) if pick else np.zeros(0, dtype=np.int64)
+        return SparseColumn(offsets, np.ascontiguousarray(self.terms[pick], dtype=np.int32),
+                            np.ascontiguousarray(self.weights[pick], dtype=np.float32), self.present[rows].copy())
+
+
+def encode_sparse_vector(value, what: str, max_nnz: int = SPARSE_MAX_NNZ) -> Tuple[List[int], List[float]]:
+    """One sparse vector -- a mapping ``{term: weight}`` or a pair ``(indices, values)`` -- as (terms ascending, weights):
+    explicit zero weights are dropped.  ``ValueError`` (starting with ``what``) for a duplicate term, a term that is not an
+    integer in [0, 2^31), a weight that is not a finite float32, or more than ``max_nnz`` nonzeros."""
+    if isinstance(value, Mapping):
+        pairs = list(value.items())
+    else:
+        try:
+            indices, values = value
+            indices = indices.tolist() if isinstance(indices, np.ndarray) else list(indices)
+            values = values.tolist() if isinstance(values, np.ndarray) else list(values)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: {value!r} is not a mapping term -> weight or a pair (indices, values)") from None
+        if len(indices) != len(values):
+            raise ValueError(f"{what}: {len(indices)} indices but {len(values)} values")
+        pairs = list(zip(indices, values))
+    seen: Dict[int, float] = {}
+    for t, w in pairs:
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)):
+            raise ValueError(f"{what}: term {t!r} is not an integer")
+        t = int(t)
+        if not 0 <= t < 2 ** 31:
+            raise ValueError(f"{what}: term {t} is outside [0, 2^31)")
+        if t in seen:
+            raise ValueError(f"{what}: term {t} appears twice")
+        if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{what}: the weight {w!r} of term {t} is not a number")
+        with np.errstate(over="ignore"):
+            w32 = float(np.float32(w))
+        if not math.isfinite(w32):
+            raise ValueError(f"{what}: the weight {w!r} of term {t} is not a finite float32")
+        seen[t] = w32
+    kept = sorted((t, w) for t, w in seen.items() if w != 0.0)
+    if len(kept) > max_nnz:
+        raise ValueError(f"{what}: {len(kept)} nonzeros; a sparse vector holds at most {max_nnz}")
+    return [t for t, _ in kept], [w for _, w in kept]
+
+
+def encode_sparse_column(name: str, values, max_nnz: int = SPARSE_MAX_NNZ) -> SparseColumn:
+    """One sparse attribute's values of a batch -> ``SparseColumn``.  A value is a mapping ``{term: weight}`` or a pair
+    ``(indices, values)``; ``None`` = absent, ``{}`` = an empty vector (present).  See ``encode_sparse_vector`` for what is
+    dropped, sorted and refused; the whole batch is checked before anything is returned."""
+    n = len(values)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    present = np.zeros(n, dtype=np.uint8)
+    terms: List[int] = []
+    weights: List[float] = []
+    for i, v in enumerate(values):
+        if v is not None:
+            t, w = encode_sparse_vector(v, f"attribute {name!r} (sparse): row {i}", max_nnz)
+            terms.extend(t)
+            weights.extend(w)
+            present[i] = 1
+        offsets[i + 1] = len(terms)
+    return SparseColumn(offsets, np.array(terms, dtype=np.int32), np.array(weights, dtype=np.float32), present)
 
 
 def encode_column(name: str, kind: str, values, codes: Dict[str, int]) -> np.ndarray:
