@@ -8,6 +8,7 @@ import numpy as np
 from mlvectordb_amd.index import Index
 from oracle import exact_scan
 from tests.distinct_helpers import ABSENT, DistinctOracleEngine, distinct_knn
+from tests.helpers import SCORE_ATOL
 
 # csrc/internal.h
 GROUPED_BLOCKS = 2048    # kGroupedBlocks
@@ -62,6 +63,35 @@ class GroupedOracleEngine(DistinctOracleEngine):
             assert counts.max(initial=0) <= max_groups
         d32 = d64.astype(np.float32)
         return (labels, d32, counts, gcnt, d64, grp) if want64 else (labels, d32, counts, gcnt, grp)
+
+
+def check_grouped(eng, qs, k, g, got, want, tag):
+    """``got``: what ``eng.search_grouped(qs, k, g, attr, want64=True)`` returned, against the oracle's (labels, d64, counts,
+    group counts, groups) for this k and g: everything but the distances exactly, the fp64 distances within SCORE_ATOL, the
+    fp32 ones the rounded fp64, both bit-equal to ``pair_distances`` of the same handle."""
+    from tests.conftest import dump_mismatch
+
+    lab, dist, cnt, gcnt, d64, grp = got
+    wl, wd, wc, wgc, wg = want
+    ok = np.array_equal(lab, wl) and np.array_equal(cnt, wc) and np.array_equal(gcnt, wgc) and np.array_equal(grp, wg)
+    if not ok:
+        dump_mismatch(f"grouped_{tag}", lab=lab, wl=wl, cnt=cnt, wc=wc, gcnt=gcnt, wgc=wgc, grp=grp, wg=wg, d64=d64, wd=wd)
+        bad = np.flatnonzero((lab != wl).any(axis=(1, 2)) | (cnt != wc) | (gcnt != wgc).any(axis=1) | (grp != wg).any(axis=1))
+        raise AssertionError(f"{tag}: {bad.size} queries differ, first {bad[0]}: got {lab[bad[0]].tolist()} ({cnt[bad[0]]}, "
+                             f"{gcnt[bad[0]].tolist()}) want {wl[bad[0]].tolist()} ({wc[bad[0]]}, {wgc[bad[0]].tolist()})")
+    fin = np.isfinite(wd)
+    assert np.array_equal(np.isfinite(d64), fin) and np.array_equal(np.isfinite(dist), fin), f"{tag}: padding differs"
+    if fin.any():
+        err = float(np.abs(d64[fin] - wd[fin]).max())
+        print(f"{tag}: max |d64 - oracle| = {err:.3e}")
+        assert err <= SCORE_ATOL, f"{tag}: distance error {err}"
+    # the fp32 output is the fp64 distance rounded once (an absolute bound cannot be asked of fp32 itself beyond 128)
+    assert np.array_equal(dist.view(np.int32), d64.astype(np.float32).view(np.int32)), f"{tag}: fp32 is not the rounded fp64"
+    nq = qs.shape[0]
+    p64, p32 = eng.pair_distances(qs, lab.reshape(nq, k * g))
+    assert np.array_equal(p64.view(np.int64), d64.reshape(nq, k * g).view(np.int64)), f"{tag}: fp64 differs from pair_distances"
+    assert np.array_equal(p32.view(np.int32), dist.reshape(nq, k * g).view(np.int32)), f"{tag}: fp32 differs from pair_distances"
+    return lab, cnt, gcnt, grp
 
 
 def oracle_index(attributes, space="l2", **kw) -> Index:

@@ -36,6 +36,13 @@ def like_queries(rows, labels, weights, offsets, space: str, base=None):
     return out, scale
 
 
+def cosine_query_bound(want, scale):
+    """What a component of a device-built cosine query may differ from ``like_queries``' by: one float32 spacing (the norm
+    is summed in another order, so the fp64 sum can land on the other side of a rounding boundary) + 1e-12 of the summed
+    |terms|."""
+    return np.spacing(np.abs(want)).astype(np.float64) + 1e-12 * scale
+
+
 def example_sets(labels, offsets):
     labels = np.asarray(labels, dtype=np.int64)
     return [set(labels[int(a):int(b)].tolist()) for a, b in zip(offsets[:-1], offsets[1:])]

@@ -8,14 +8,19 @@ from mlvectordb_amd.index import Index
 from oracle import exact_scan
 from tests.where_helpers import WhereOracleEngine
 
+D64_BOUND = 1e-10  # what a device fp64 distance may differ from the oracle's by where the oracle's picks are asked for
+GAP_MIN = 1e-9  # an fp64 sum of <= 208 exact products errs by <= 208 * 2^-53 * sum|terms| ~ 5e-11 at these shapes; an objective
+                # inherits at most one such error from each of its two distances: 1e-9 leaves a tenfold margin
 
-def mmr_select(dq, P, k: int, lam: float):
+
+def mmr_select(dq, P, k: int, lam: float, step_gaps=None):
     """The greedy of mlvdb_mmr.h over one candidate list.  ``dq`` [m]: float64 distances to the query in rank order.
     ``P``: the float64 matrix P[s][i] = D(s, i), or a callable ``P(s)`` giving row s (only the picked rows are ever asked
     for).  The first pick is position 0; each further pick is the unpicked position minimising
     ``lam * dq[i] - (1.0 - lam) * mind[i]`` -- two rounded products, one rounded subtraction -- the first minimum in
     position order (a stable argmin).  Returns (picks int32 [min(k, m)], objectives float64, the smallest gap between the
-    best and the runner-up objective over all steps that had a runner-up; inf when none had)."""
+    best and the runner-up objective over all steps that had a runner-up; inf when none had).  ``step_gaps``: a list that
+    receives that gap of every step that had a runner-up."""
     dq = np.asarray(dq, dtype=np.float64)
     m = dq.size
     n = min(int(k), m)
@@ -37,7 +42,10 @@ def mmr_select(dq, P, k: int, lam: float):
             j = int(np.argmin(oc))  # the first minimum: the lower position
             s, o = int(cand[j]), oc[j]
             if cand.size > 1:
-                gap = min(gap, float(np.partition(oc, 1)[1] - o))
+                step = float(np.partition(oc, 1)[1] - o)
+                gap = min(gap, step)
+                if step_gaps is not None:
+                    step_gaps.append(step)
         picks[t], objs[t] = s, o
         free[s] = False
         if t + 1 < n:

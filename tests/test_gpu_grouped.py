@@ -11,10 +11,9 @@ import pytest
 from mlvectordb_amd import Index, InMemoryStorage, QueryProcessor, VectorDTO
 from mlvectordb_amd.engine import HipScanEngine
 from oracle import exact_scan
-from tests.conftest import dump_mismatch
 from tests.distinct_helpers import ABSENT
 from tests.facet_helpers import colliding_keys, facet_hash
-from tests.grouped_helpers import grouped_knn, oracle_index, table_slots, tile_plan
+from tests.grouped_helpers import check_grouped, grouped_knn, oracle_index, table_slots, tile_plan
 from tests.helpers import SCORE_ATOL
 from tests.where_helpers import SCHEMA, py_match, random_filter, random_metadata
 
@@ -44,27 +43,7 @@ def _route(eng, oversample):
 
 def _check(eng, qs, k, g, want, tag, **kw):
     """One call against the oracle's (labels, d64, counts, group counts, groups) for this k and g."""
-    lab, dist, cnt, gcnt, d64, grp = eng.search_grouped(qs, k, g, 0, want64=True, **kw)
-    wl, wd, wc, wgc, wg = want
-    ok = np.array_equal(lab, wl) and np.array_equal(cnt, wc) and np.array_equal(gcnt, wgc) and np.array_equal(grp, wg)
-    if not ok:
-        dump_mismatch(f"grouped_{tag}", lab=lab, wl=wl, cnt=cnt, wc=wc, gcnt=gcnt, wgc=wgc, grp=grp, wg=wg, d64=d64, wd=wd)
-        bad = np.flatnonzero((lab != wl).any(axis=(1, 2)) | (cnt != wc) | (gcnt != wgc).any(axis=1) | (grp != wg).any(axis=1))
-        raise AssertionError(f"{tag}: {bad.size} queries differ, first {bad[0]}: got {lab[bad[0]].tolist()} ({cnt[bad[0]]}, "
-                             f"{gcnt[bad[0]].tolist()}) want {wl[bad[0]].tolist()} ({wc[bad[0]]}, {wgc[bad[0]].tolist()})")
-    fin = np.isfinite(wd)
-    assert np.array_equal(np.isfinite(d64), fin) and np.array_equal(np.isfinite(dist), fin), f"{tag}: padding differs"
-    if fin.any():
-        err = float(np.abs(d64[fin] - wd[fin]).max())
-        print(f"{tag}: max |d64 - oracle| = {err:.3e}")
-        assert err <= SCORE_ATOL, f"{tag}: distance error {err}"
-    # the fp32 output is the fp64 distance rounded once (an absolute bound cannot be asked of fp32 itself beyond 128)
-    assert np.array_equal(dist.view(np.int32), d64.astype(np.float32).view(np.int32)), f"{tag}: fp32 is not the rounded fp64"
-    nq = qs.shape[0]
-    p64, p32 = eng.pair_distances(qs, lab.reshape(nq, k * g))
-    assert np.array_equal(p64.view(np.int64), d64.reshape(nq, k * g).view(np.int64)), f"{tag}: fp64 differs from pair_distances"
-    assert np.array_equal(p32.view(np.int32), dist.reshape(nq, k * g).view(np.int32)), f"{tag}: fp32 differs from pair_distances"
-    return lab, cnt, gcnt, grp
+    return check_grouped(eng, qs, k, g, eng.search_grouped(qs, k, g, 0, want64=True, **kw), want, tag)
 
 
 def _cut(full, nq, k, g):

@@ -45,3 +45,20 @@ def test_history_through_three_logical_shards_equals_one_model(key):
     """``MultiDeviceEngine`` over three ``HipScanEngine`` shards on device 0, the ops of tests/test_host_fuzz.py."""
     seed, space, d, _ = key
     _replay(key, lambda: MultiDeviceEngine(d, space, [0, 0, 0]))
+
+
+@pytest.mark.parametrize("key", H.WIDE, ids=lambda key: H.history_tag(*key))
+def test_wide_history_equals_the_model_at_every_step(key):
+    """The entry families added since the first histories -- ordered, diversified, grouped, by-example and late-interaction
+    queries, updates and filtered deletes, list and sparse columns -- on one handle: pools that regrow, are repacked and
+    reset, the inner searches on the filter route across mutations, masked calls before unmasked ones."""
+    seed, space, d, _ = key
+    _replay(key, lambda: HipScanEngine(d, space, device=0))
+
+
+@pytest.mark.parametrize("key", H.WIDE_LARGE, ids=lambda key: H.history_tag(*key))
+def test_wide_large_history_moves_the_inner_searches_between_the_routes(key):
+    """Past 32,768 rows `auto` itself takes the filter route inside search_mmr / search_like / search_grouped and the tag-filtered
+    search_each at nq = 12 and 40; a ``tombstone_where`` of about a third of the rows and a compaction bring it back; growth again."""
+    seed, space, d, _ = key
+    _replay(key, lambda: HipScanEngine(d, space, device=0))

@@ -18,7 +18,7 @@ from mlvectordb_amd.engine import HipScanEngine
 from oracle import exact_scan
 from tests.conftest import dump_mismatch
 from tests.helpers import SCORE_ATOL
-from tests.like_helpers import example_sets, like_queries, like_strip, most_examples
+from tests.like_helpers import cosine_query_bound, example_sets, like_queries, like_strip, most_examples
 from tests.where_helpers import SCHEMA, py_match, random_filter, random_metadata
 
 pytestmark = pytest.mark.gpu
@@ -101,7 +101,7 @@ def test_the_synthesised_queries_equal_the_numpy_rule(space, d):
                                          f"want {want[tuple(bad[0])]!r}")
             else:
                 err = np.abs(got.astype(np.float64) - want.astype(np.float64))
-                bound = np.spacing(np.abs(want)).astype(np.float64) + 1e-12 * scale
+                bound = cosine_query_bound(want, scale)
                 print(f"{space} d={d}: worst error / bound {float((err / bound).max()):.3f}")
                 assert (err <= bound).all(), float((err / bound).max())
             if b is None:

@@ -14,11 +14,10 @@ import pytest
 from mlvectordb_amd import Index, InMemoryStorage, QueryProcessor, VectorDTO
 from mlvectordb_amd.engine import HipScanEngine
 from oracle import exact_scan
-from tests.conftest import dump_mismatch
 from tests.distinct_helpers import ABSENT
 from tests.facet_helpers import colliding_keys, facet_hash
 from tests.helpers import SCORE_ATOL, make_case
-from tests.maxsim_helpers import maxsim_oracle, offsets_of, oracle_index
+from tests.maxsim_helpers import check_maxsim, maxsim_oracle, offsets_of, oracle_index
 from tests.where_helpers import SCHEMA, py_match, random_filter, random_metadata
 
 pytestmark = pytest.mark.gpu
@@ -36,39 +35,9 @@ def _engine(space, rows, groups, tomb=None):
     return eng
 
 
-def _seq_sum(md, off, k):
-    """[nq, k]: (((0.0 + d0) + d1) + ...) over each query's token rows of ``md`` [tokens, k]."""
-    out = np.empty((off.size - 1, k))
-    for i in range(off.size - 1):
-        acc = np.zeros(k)
-        for t in range(int(off[i]), int(off[i + 1])):
-            acc = acc + md[t]
-        out[i] = acc
-    return out
-
-
 def _check(eng, toks, off, k, want, tag, **kw):
     """One call against the oracle's (groups, score64, counts, match labels, match dist64) for this k; the bit contracts."""
-    grp, s32, cnt, s64, ml, md = eng.search_maxsim(toks, off, k, 0, want_matches=True, **kw)
-    wg, ws, wc, wml, wmd = want
-    if not (np.array_equal(grp, wg) and np.array_equal(cnt, wc) and np.array_equal(ml, wml)):
-        dump_mismatch(f"maxsim_{tag}", grp=grp, wg=wg, cnt=cnt, wc=wc, ml=ml, wml=wml, s64=s64, ws=ws, md=md, wmd=wmd)
-        bad = np.flatnonzero((grp != wg).any(axis=1) | (cnt != wc))
-        i = int(bad[0]) if bad.size else -1
-        raise AssertionError(f"{tag}: {bad.size} queries differ in groups / counts (first {i}: got {grp[i].tolist()} "
-                             f"({cnt[i]}) want {wg[i].tolist()} ({wc[i]})); match labels equal: {np.array_equal(ml, wml)}")
-    fin = np.isfinite(ws)
-    assert np.array_equal(np.isfinite(s64), fin) and np.array_equal(np.isfinite(s32), fin), f"{tag}: padding differs"
-    assert np.array_equal(np.isfinite(md), np.isfinite(wmd)), f"{tag}: match padding differs"
-    if fin.any():
-        err = float((np.abs(s64[fin] - ws[fin]) / np.maximum(1.0, np.abs(ws[fin]))).max())
-        print(f"{tag}: max |score64 - oracle| / max(1, |s|) = {err:.3e}")
-        assert err <= SCORE_ATOL, f"{tag}: score error {err}"
-    assert np.array_equal(s32.view(np.int32), s64.astype(np.float32).view(np.int32)), f"{tag}: fp32 is not the rounded fp64"
-    p64, _ = eng.pair_distances(toks, ml)
-    assert np.array_equal(p64.view(np.int64), md.view(np.int64)), f"{tag}: match distances differ from pair_distances"
-    assert np.array_equal(_seq_sum(md, off, k).view(np.int64), s64.view(np.int64)), f"{tag}: score64 is not the sequential sum"
-    return grp, cnt, s64, ml, md
+    return check_maxsim(eng, toks, off, k, eng.search_maxsim(toks, off, k, 0, want_matches=True, **kw), want, tag)
 
 
 def _documents(rng, n, lo, hi):

@@ -17,7 +17,7 @@ from mlvectordb_amd.engine import HipScanEngine
 from oracle import exact_scan
 from tests.conftest import dump_mismatch
 from tests.helpers import SCORE_ATOL
-from tests.mmr_helpers import mmr_from_candidates, mmr_select
+from tests.mmr_helpers import D64_BOUND, GAP_MIN, mmr_from_candidates, mmr_select
 from tests.where_helpers import SCHEMA, py_match, random_filter, random_metadata
 
 pytestmark = pytest.mark.gpu
@@ -95,8 +95,6 @@ def test_search_mmr_equals_the_greedy_replayed_on_the_devices_own_bits(space, d)
 
 
 # ---------------------------------------------------------------- 2. against the NumPy oracle
-GAP_MIN = 1e-9  # an fp64 sum of <= 208 exact products errs by <= 208 * 2^-53 * sum|terms| ~ 5e-11 at these shapes; an objective
-                # inherits at most one such error from each of its two distances: 1e-9 leaves a tenfold margin
 ORACLE_LAMBDAS = (0.0, 0.3, 0.7)
 
 
@@ -150,7 +148,7 @@ def test_search_mmr_equals_the_numpy_oracle_where_no_step_is_a_near_tie(space, d
                                      f"want {wrank[bad[0]]}")
             err = float(np.abs(d64 - wd64).max())
             print(f"{space} d={d} lambda={lam}: max |d64 - oracle| = {err:.3e}")
-            assert err <= 1e-10, err  # the premise of GAP_MIN's derivation
+            assert err <= D64_BOUND, err  # the premise of GAP_MIN's derivation
             assert err <= SCORE_ATOL
             # (the fp32 output is the fp64 distance rounded once; an absolute 1e-5 cannot be asked of fp32 itself beyond 128)
             assert np.array_equal(_bits(dist), _bits(d64.astype(np.float32)))

@@ -1,6 +1,8 @@
-"""The seeded call histories of tests/history_helpers.py without a GPU: they are deterministic, the model agrees with the oracle
-engines it is composed from, the committed seed set meets every coverage condition (printed with the seed and step that meets
-it), the driver reports three seeded stale-state defects, and near-tie redraws stay under 1 % of the drawn queries."""
+"""The seeded call histories of tests/history_helpers.py without a GPU: they are deterministic, the first ones are pinned by the
+sha256 of their op lists, the models agree with the oracle engines they are composed from, the committed seed sets meet every
+coverage condition (a to j for the first histories, k to w for the wide ones; each printed with the seed and step that meets
+it), the driver reports three plus five seeded stale-state defects, and near-tie redraws stay under 1 % of the drawn queries."""
+import hashlib
 import json
 
 import numpy as np
@@ -134,6 +136,34 @@ WANTED = (["a", "d", "h", "i", "j", "c_search_mask", "c_search_where", "c_search
           + ["e_" + w for w in H.REFUSALS] + [f"g_{m}>{q}" for m, q in H.PAIRS])
 
 
+# ---------------------------------------------------------------- the first histories are pinned
+# sha256(json.dumps(ops)) of every history of HISTORIES as generated before the wide scale existed: new ops and program kinds
+# live in scales of their own, so that these seeds keep drawing what they drew.
+PINNED = {
+    "small_l2_d20_seed0": "626dbe9888705c21eedbe3f9b8be9739267a6497a35301372648ec86d5e3ef06",
+    "small_l2_d20_seed1": "b3aba4a086d5f19f003c218810a007fceec1028fac0b06d74828b13b83c69c1b",
+    "small_cosine_d64_seed2": "14400f45c4b8484234286a4ce4e986959d9a77a98e6d1b12231c94e46690a3a0",
+    "small_cosine_d64_seed3": "0a211e6d419f59c49595e7e6813546171d0d956efcdc778e3309010c11593d57",
+    "small_ip_d128_seed4": "d422f1da0dbc62f45de75d71dedefbd65a99d668a6a0d1ca661fc7f66242cfac",
+    "small_ip_d128_seed5": "f0dc7388bbae902c17d2526827535108eeeffed53cdac4be3c9edb11cd7f5e63",
+    "small_l2_d256_seed6": "97a17951ed51e5b5c9547dcaeffe90a707027c6d2b55f88856bb52b0eb40c5cb",
+    "small_l2_d256_seed7": "8cd3a0b5df189f2d42e89487d3564318f4548e89f76284a43efa571d51672b3a",
+    "small_cosine_d100_seed8": "5c804b324151158e185b0886b052d25ba7c3057f396a007c878b749091ae12f0",
+    "small_cosine_d100_seed9": "c6cc02820740349a6decc2ce9aa6e91d474b67db96002bcc90e5fae6d36bea32",
+    "large_l2_d64_seed100": "5f0eeca469b09fa431a96bba515a3bf72f1bdaa22b544a4b97711a9a2d1dca2b",
+    "large_cosine_d64_seed101": "1591b3011333674f2bb4309d74f5bd7248e3a9a230393ec45a91434551817f55",
+    "large_ip_d64_seed102": "3c823f4c4ad7cee5cfa35d1477927ba794b1c672cb3b5062ed3296e2280d523f",
+    "multi_cosine_d48_seed200": "fae4c7f1d6cda9416b7ab8a917bfa337bf41709adcba36b725a2bf25a982d2d7",
+}
+
+
+def test_the_first_histories_generate_byte_identical_op_lists():
+    assert {H.history_tag(*key) for key in H.HISTORIES} == set(PINNED)
+    for key in H.HISTORIES:
+        ops, _ = H.make_history(*key)
+        assert hashlib.sha256(json.dumps(ops).encode()).hexdigest() == PINNED[H.history_tag(*key)], H.history_tag(*key)
+
+
 # ---------------------------------------------------------------- determinism
 def test_make_history_is_deterministic_and_json_serialisable():
     key = H.SMALL[0]
@@ -206,6 +236,101 @@ def test_history_model_agrees_with_the_individual_oracle_engines():
                     lambda: model.facet_bins(2, np.array([5, 3])), lambda: model.where_count(H.program_of({"ops": [[W.EQ, 9, 1, 0]], "set": []}))):
         with pytest.raises(RuntimeError):
             refused()
+    _the_wide_model_agrees_with_the_oracle_engines_of_the_newer_entries(rows, qs)
+
+
+def _the_wide_model_agrees_with_the_oracle_engines_of_the_newer_entries(rows, qs):
+    """The same state -- two appends, every column valued, tombstones -- in ``WideHistoryModel`` and in each oracle engine it
+    is composed from; one call per new entry, list programs inside the kNN entries included."""
+    from mlvectordb_amd import _native
+    from tests.grouped_helpers import GroupedOracleEngine
+    from tests.like_helpers import LikeOracleEngine
+    from tests.maxsim_helpers import MaxSimOracleEngine, offsets_of
+    from tests.mmr_helpers import MmrOracleEngine
+    from tests.order_helpers import OrderOracleEngine
+    from tests.sparse_helpers import SparseOracleEngine, random_corpus, sparse_csr
+
+    n, d = rows.shape
+    lists = H.csr(H.wide_lists(np.random.default_rng(4), n))
+    vectors = sparse_csr(random_corpus(np.random.default_rng(5), n, H.SPARSE_VOCAB, True))
+    engines = [cls(d, "l2") for cls in (H.WideHistoryModel, SparseOracleEngine, OrderOracleEngine, GroupedOracleEngine,
+                                        MmrOracleEngine, LikeOracleEngine, MaxSimOracleEngine)]
+    for e in engines:
+        pooled = isinstance(e, SparseOracleEngine)
+        for attr, kind in ((0, "int64"), (1, "float64"), (2, "int64")) + (((4, "int64_list"), (5, "sparse")) if pooled else ()):
+            e.define_attr(attr, kind)
+        e.append(rows[:250])
+        e.append(rows[250:])
+        for attr in range(3):
+            e.set_attr(attr, 0, H.column_values(attr, n, np.random.default_rng(attr), n))
+        if pooled:
+            e.set_attr_list(4, 0, lists)
+            e.set_attr_sparse(5, 0, vectors)
+        e.tombstone(np.arange(0, n, 7))
+    model, sparse, order, grouped, mmr, like, maxsim = engines
+    half = H.program_of({"ops": HALF, "set": []})
+    tagged = H.program_of({"ops": [[W.HAS, 4, 3, 0], [W.LT, 2, 8, 0], [W.AND, 0, 0, 0]], "set": []})
+    same = lambda a, b: len(a) == len(b) and all((x is None and y is None) or np.array_equal(x, y) for x, y in zip(a, b))  # noqa: E731
+    column = lambda c: tuple(vars(c).values())  # noqa: E731
+    assert same(model.where_ordered(1, 20, half, True, 3)[:2], order.where_ordered(1, 20, half, True, 3)[:2])
+    assert model.where_ordered(0, 5, half)[2:] == order.where_ordered(0, 5, half)[2:]
+    assert same(model.search_grouped(qs, 4, 3, 0, where=half, want64=True), grouped.search_grouped(qs, 4, 3, 0, where=half, want64=True))
+    assert same(model.search_mmr(qs, 5, 40, 0.3, where=half, want64=True), mmr.search_mmr(qs, 5, 40, 0.3, where=half, want64=True))
+    ex = (np.array([3, 9, 14, 200]), np.array([1.0, 0.5, 1.0, -0.25]), np.array([0, 2, 4]))  # (14 is tombstoned)
+    assert same(model.search_like(*ex, 6, where=half, want64=True, want_queries=True),
+                like.search_like(*ex, 6, where=half, want64=True, want_queries=True))
+    toks, off = np.concatenate([qs, qs[:3]]), offsets_of([3, 1, 4])
+    assert same(model.search_maxsim(toks, off, 5, 0, half, True), maxsim.search_maxsim(toks, off, 5, 0, half, True))
+    # the entries of the pooled columns, and list programs inside the kNN entries, against the sparse / tags / mutate engine
+    sq = H._sparse_queries(np.random.default_rng(6), 4)
+    for e in (model, sparse):
+        assert e.set_attr_at(2, np.array([5, 14, 30]), np.array([1, 2, 3])) == 2
+        assert e.update_where(tagged, [(0, _native.SET_ADD, 1), (2, _native.SET_ASSIGN, 4)])[1] == 0
+        assert e.update_where(half, [(0, _native.SET_ADD, 2 ** 63 - 1)])[1] > 0
+        assert e.set_attr_list_at(4, np.array([8, 14, 2]), H.csr([[1, 2], [3], None])) == 2
+        assert e.set_attr_sparse_at(5, np.array([9, 14]), sparse_csr([{3: 0.5}, {4: 1.0}])) == 1
+        assert e.update_where_list(tagged, 4, np.array([2, 6])) > 0
+    assert np.array_equal(model.tombstone_where(tagged), sparse.tombstone_where(tagged))
+    for attr in range(3):
+        assert np.array_equal(model.get_attr(attr, 0, n, np.float64), sparse._cols[attr].astype(np.float64), equal_nan=True)
+    assert same(column(model.get_attr_list(4, 0, n)), column(sparse.get_attr_list(4, 0, n)))
+    assert same(column(model.get_attr_sparse(5, 0, n)), column(sparse.get_attr_sparse(5, 0, n)))
+    assert model.list_stats(4) == sparse.list_stats(4) and model.list_stats(5) == sparse.list_stats(5)
+    got, want = model.facet_list_values(4, 4096, half), sparse.facet_list_values(4, 4096, half)
+    assert same(got[:2], want[:2]) and got[2:] == want[2:]
+    has = H.program_of({"ops": [[W.HAS_ANY, 4, 0, 2, ]], "set": [2, 6]})
+    assert same(model.search_batch_sparse(5, sq, 7, has), sparse.search_batch_sparse(5, sq, 7, has))
+    assert same(model.search_grouped(qs, 4, 3, 0, where=has, want64=True)[:4], grouped_with(sparse, qs, 4, 3, has))
+    assert np.array_equal(model.compact(), sparse.compact()) and model.list_stats(4) == sparse.list_stats(4)
+    assert same(model.search_batch_sparse(5, sq, 7, has), sparse.search_batch_sparse(5, sq, 7, has))
+    # what the model adds: pools mirrored, a reset that empties the lists and keeps their definitions, the refusals
+    used, cap, live = model.pools()[4]
+    assert used == cap == live == model.list_stats(4)[1] > 0
+    model.reset()
+    assert model.pools()[4] == (0, cap, 0) and model.append(rows[:5]) == 0
+    assert not model.get_attr_list(4, 0, 5).present.any() and not model.get_attr_sparse(5, 0, 5).present.any()
+    tok129 = np.zeros((129, d), np.float32)
+    for status, refused in ((1, lambda: model.search_mmr(qs, 10, 9, 0.5)), (1, lambda: model.search_grouped(qs, 3, 0, 0)),
+                            (6, lambda: model.search_grouped(qs, 3, 65, 0)), (1, lambda: model.search_like([5], [1.0], [0, 1], 3)),
+                            (1, lambda: model.search_maxsim(tok129[:3], offsets_of([2, 0, 1]), 3, 0)),
+                            (1, lambda: model.search_maxsim(tok129, offsets_of([129]), 3, 0)),
+                            (1, lambda: model.where_ordered(2, 4091, None, False, 6)),
+                            (1, lambda: model.set_attr_at(2, np.array([0, 0]), np.array([1, 2]))),
+                            (1, lambda: model.set_attr(4, 0, np.array([1]))), (1, lambda: model.set_attr_list(5, 0, H.csr([[1]]))),
+                            (1, lambda: model.search_batch_sparse(4, sq, 5))):
+        with pytest.raises(RuntimeError) as err:
+            refused()
+        assert H._status_of(err.value) == status
+
+
+def grouped_with(engine, qs, k, g, where):
+    """``search_grouped`` of tests/grouped_helpers.py over the state of another oracle engine (one that evaluates list programs)."""
+    from oracle import exact_scan
+    from tests.grouped_helpers import grouped_knn
+
+    dist = exact_scan.exact_distances(qs, engine._rows, engine.space)
+    labels, d64, counts, gcnt, _ = grouped_knn(dist, engine._cols[0], engine.match(where), k, g)
+    return labels, d64.astype(np.float32), counts, gcnt
 
 
 def test_the_shard_history_passes_through_logical_shards_of_oracle_engines():
@@ -348,10 +473,475 @@ def test_the_driver_reports_a_seeded_stale_state_defect(defect, tmp_path, monkey
     assert reported >= 2, f"{defect.__name__}: reported in {reported} of 4 histories"
 
 
+# ================================================================ the wide histories (conditions k to w)
+LIST_OPS = (W.HAS, W.HAS_ANY, W.HAS_ALL, W.LEN)
+GROUP_READERS = ("search_grouped", "search_maxsim", "search_distinct", "where_ordered")
+
+
+def programs_of(op):
+    return ([op["program"]] if op.get("program") else []) + op.get("programs", [])
+
+
+def list_leaf(op, attr):
+    return any(o[0] in LIST_OPS and o[1] == attr for p in programs_of(op) for o in p["ops"])
+
+
+def pooled_leaf(op):
+    """A list op, or EXISTS on a list or sparse column, in one of the op's programs."""
+    return any(o[0] in LIST_OPS or (o[0] == W.EXISTS and o[1] in H.POOLED) for p in programs_of(op) for o in p["ops"])
+
+
+PROGRAM_TAKING = ("search_where", "search_each", "range_where", "range_each", "search_distinct", "facet_values", "facet_bins",
+                  "where_count", "where_labels", "count_each", "update_where", "tombstone_where", "update_where_list",
+                  "where_ordered", "search_mmr", "search_grouped", "search_like", "search_maxsim", "facet_list_values",
+                  "search_batch_sparse")
+
+
+def write_floor(op):
+    """The lowest row a write to a pooled column may touch."""
+    if "first" in op:
+        return op["first"]
+    if "labels" in op:
+        return min(op["labels"])
+    return op.get("lo", 0)
+
+
+def wide_trace(ops, expected, space):
+    """The handle's state BEFORE each step of a wide history, from the ops and what the model counted (rows, tombstones,
+    used / capacity / live values of every pool)."""
+    st = dict(strategy="auto", total=0, deleted=0, space=space, cap=0, regrowths=0, valued=set(), pools={})
+    out = []
+    for op, exp in zip(ops, expected):
+        out.append({**st, "valued": set(st["valued"])})
+        kind = op["op"]
+        if kind == "set_strategy":
+            st["strategy"] = op["strategy"]
+        elif kind == "append":
+            cap = H.capacity_after(st["cap"], st["total"] + op["n"])
+            if cap != st["cap"] and st["cap"] and {H.LIST_A, H.SPARSE_A} <= st["valued"]:
+                st["regrowths"] += 1
+            st["cap"] = cap
+        elif kind == "compact":  # (the slot columns are rebuilt: what regrew before is gone)
+            st["cap"] = H.capacity_after_compact(st["cap"], st["total"] - st["deleted"], st["deleted"])
+            st["regrowths"] = 0
+        elif kind in ("set_attr_list", "set_attr_sparse") and op["n"]:
+            st["valued"] = st["valued"] | {op["attr"]}
+        elif kind == "reset":
+            st.update(regrowths=0, valued=set())
+            st["space"] = op["space"] or st["space"]
+        if "counts" in exp:
+            st["total"], st["deleted"] = exp["counts"]
+        st["pools"] = exp["pools"]
+    return out
+
+
+def run_of(ops, i, kinds):
+    seen = []
+    while i < len(ops) and ops[i]["op"] in kinds:
+        seen.append(i)
+        i += 1
+    return seen, i
+
+
+def wide_conditions(ops, expected, space):
+    """{condition: step} for every condition k to w this wide history meets."""
+    st = wide_trace(ops, expected, space)
+    kinds = [op["op"] for op in ops]
+    n = len(ops)
+    met = {}
+    grow = {a: 0 for a in H.POOLED}
+    floor = {a: np.inf for a in H.POOLED}
+    late = dict(defined=False, written=set())
+
+    def put(name, step):
+        met.setdefault(name, step)
+
+    def nq_of(op):
+        return len(op["groups"]) if op["op"] == "search_like" else op["nq"]
+
+    for i, op in enumerate(ops):
+        k = kinds[i]
+        nxt = kinds[i + 1] if i + 1 < n else None
+        s = st[i]
+        pooled_name = lambda a: "sparse" if H.POOLED[a] == "sparse" else "list"  # noqa: E731
+        # (k)
+        if k in H.WIDE_MUTATIONS and nxt in H.WIDE_QUERIES and (k in H.NEW_MUTATIONS or nxt in H.NEW_QUERIES):
+            put(f"k_{k}>{nxt}", i)
+        # (l)
+        if k == "compact" and i + 2 < n:
+            for a, (used, _, live) in s["pools"].items():
+                tag_query = (ops[i + 1]["op"] == "search_batch_sparse" and ops[i + 1]["attr"] == a) or list_leaf(ops[i + 1], a)
+                if used > live > 0 and tag_query and kinds[i + 2] == "list_stats" and ops[i + 2]["attr"] == a:
+                    assert expected[i + 2]["want"][0] == expected[i + 2]["want"][1] > 0  # the repack: used == live
+                    put(f"l_{pooled_name(a)}_{'dead' if s['deleted'] else 'clean'}", i)
+        # (m)
+        if k in ("compact", "reset"):
+            grow, floor = {a: 0 for a in H.POOLED}, {a: np.inf for a in H.POOLED}
+        if k in H.NEW_MUTATIONS and op.get("attr") in s["pools"] and k != "set_attr_at":
+            a = op["attr"]
+            used, cap, live = s["pools"][a]
+            if expected[i]["pools"][a][1] != cap:
+                assert expected[i]["pools"][a][1] == H.pool_capacity_after(cap, expected[i]["pools"][a][0])
+                if used > 0 and live > 0:
+                    grow[a] += 1
+            if grow[a]:
+                floor[a] = min(floor[a], write_floor(op))
+        if k in ("get_attr_list", "get_attr_sparse") and op["first"] == 0 and 0 < op["n"] <= floor[op["attr"]] and grow[op["attr"]] >= 2:
+            put(f"m_{pooled_name(op['attr'])}", i)
+        # (n)
+        if s["regrowths"] >= 2:
+            if k in ("get_attr_list", "facet_list_values", "search_batch_sparse") and \
+                    op["attr"] == (H.SPARSE_A if k == "search_batch_sparse" else H.LIST_A):
+                put("n_" + k, i)
+            if list_leaf(op, H.LIST_A):
+                put("n_tag_program", i)
+        # (o) and (w): a reset or an emptying compaction, what is asked then, a refill, what is asked again
+        emptied_by_compact = (k == "compact" and s["total"] > 0 and expected[i]["counts"] == (0, 0) and i > 0
+                              and kinds[i - 1] == "tombstone_where" and ops[i - 1]["program"]["ops"] == [[W.TRUE, 0, 0, 0]])
+        if k == "reset" and s["total"] > 0 and nxt == "append":
+            first, j = run_of(ops, i + 2, H.WIDE_QUERIES)
+            sets, j2 = run_of(ops, j, H.WIDE_MUTATIONS)
+            again, _ = run_of(ops, j2, H.WIDE_QUERIES)
+            absent = True
+            for x in first:
+                want = expected[x]["want"]
+                if kinds[x] == "list_stats":
+                    absent &= tuple(want) == (0, 0)
+                elif kinds[x] in ("get_attr_list", "get_attr_sparse"):
+                    absent &= ops[x]["n"] > 0 and not want.present.any()
+                elif kinds[x] == "search_batch_sparse":
+                    absent &= not want[2].any()
+                elif kinds[x] == "facet_list_values":
+                    absent &= want[0].size == 0 and want[2] == want[3] > 0
+                elif kinds[x] == "where_count" and list_leaf(ops[x], H.LIST_A):
+                    absent &= want == 0
+            if (absent and set(H.LIST_READERS) <= {kinds[x] for x in first} and {"set_attr_list", "set_attr_sparse"} <= {kinds[x] for x in sets}
+                    and set(H.LIST_READERS) <= {kinds[x] for x in again}):
+                put("o_reset" if op["space"] is None else "o_reset_other", i)
+        if emptied_by_compact or (k == "reset" and s["total"] > 0):
+            first, j = run_of(ops, i + 1, H.WIDE_QUERIES)
+            if j < n and kinds[j] == "append":
+                _, j2 = run_of(ops, j, H.WIDE_MUTATIONS)
+                again, _ = run_of(ops, j2, H.WIDE_QUERIES)
+                padding = all(not np.asarray(expected[x]["want"][2]).any() for x in first if kinds[x] in H.MASKABLE)
+                if padding and set(H.NEW_QUERIES) <= {kinds[x] for x in first} and set(H.NEW_QUERIES) <= {kinds[x] for x in again}:
+                    put("w_" + k, i)
+        # (p)
+        if k in H.INNER_SEARCHES and s["strategy"] == "filter":
+            between, j = run_of(ops, i + 1, [m for m in H.WIDE_MUTATIONS if m not in ("set_strategy", "set_tuning")])
+            if between and j < n and kinds[j] == k:
+                for x in between:
+                    if kinds[x] in ("tombstone_where", "tombstone", "append", "compact"):
+                        put(f"p_{k}_{kinds[x]}", i)
+            if s["space"] == "l2" and i + 3 < n and nxt in H.INNER_SEARCHES and nq_of(ops[i + 1]) != nq_of(op) \
+                    and kinds[i + 2] == "tombstone_where" and kinds[i + 3] in SEARCHES:
+                put("p_l2", i)
+        # (q)
+        if k in H.MASKABLE and op.get("program") is not None:
+            if nxt == "search64":
+                put(f"q_{k}_plain", i)
+            if nxt == k and ops[i + 1].get("program") is None:
+                put(f"q_{k}_own", i)
+        # (r)
+        if k == "define_attr" and op["attr"] == H.LATE_LIST and s["total"] > 0 and not late["defined"]:
+            late["defined"] = True
+            put("r_defined", i)
+        elif late["defined"]:
+            if k in H.NEW_MUTATIONS and op.get("attr") in (H.LATE_LIST, H.LATE_SPARSE) and k != "set_attr_at":
+                late["written"].add(op["attr"])
+            phase = {0: "absent", 2: "set"}.get(len(late["written"]))
+            if phase:
+                if list_leaf(op, H.LATE_LIST):
+                    put(f"r_{phase}_has", i)
+                if k in ("facet_list_values", "get_attr_list") and op["attr"] == H.LATE_LIST:
+                    put(f"r_{phase}_{k}", i)
+                if k in ("get_attr_sparse", "search_batch_sparse") and op["attr"] == H.LATE_SPARSE:
+                    put(f"r_{phase}_{k}", i)
+        # (s)
+        if nxt in GROUP_READERS:
+            written = [a for a, _, _ in op["assigns"]] if k == "update_where" else [op["attr"]] if k == "set_attr_at" else []
+            if ops[i + 1]["attr"] in written and ops[i + 1]["attr"] != 1:
+                put(f"s_{k}>{nxt}", i)
+            if k == "update_where" and nxt == "where_ordered" and ops[i + 1]["attr"] == 1 and [1, 1] in [x[:2] for x in op["assigns"]]:
+                put("s_float_add", i)
+        # (t)
+        if k == "update_where" and expected[i]["want"][1] > 0 and nxt == "get_attr" and ops[i + 1]["attr"] in [x[0] for x in op["assigns"]]:
+            put("t", i)
+        # (u)
+        if k == "tombstone" and op["mode"] == "labels" and op["labels"] and kinds[i + 1:i + 7] == \
+                ["search_like", "get_rows_at", "compact", "search_like", "get_rows_at", "refuse"] and i + 7 < n:
+            dead, new_total = set(op["labels"]), expected[i + 3]["counts"][0]
+            stale = ops[i + 6]
+            if (any(set(g) & dead for g in ops[i + 1]["groups"]) and set(ops[i + 2]["labels"]) <= dead
+                    and stale["which"] == "like_label" and new_total <= stale["label"] < st[i + 3]["total"]
+                    and expected[i + 6]["want"] == ("refused", 1) and kinds[i + 7] in H.WIDE_QUERIES):
+                put("u", i)
+        # (v)
+        if k == "refuse" and op["which"] in H.WIDE_REFUSALS and expected[i]["want"][0] == "refused" and nxt in H.WIDE_QUERIES:
+            put("v_" + op["which"], i)
+    for name, parts in (("n", ["n_get_attr_list", "n_tag_program", "n_facet_list_values", "n_search_batch_sparse"]),
+                        ("r", ["r_defined"] + [f"r_{p}_{x}" for p in ("absent", "set") for x in
+                                               ("has", "facet_list_values", "get_attr_list", "get_attr_sparse", "search_batch_sparse")])):
+        if all(x in met for x in parts):
+            met[name] = met[parts[0]]
+    return met
+
+
+WIDE_WANTED = ([f"k_{m}>{q}" for m, q in H.WIDE_PAIRS]
+               + [f"l_{c}_{v}" for c in ("list", "sparse") for v in ("clean", "dead")] + ["m_list", "m_sparse", "n", "o_reset", "o_reset_other"]
+               + [f"p_{i}_{x}" for i in H.INNER_SEARCHES for x in ("tombstone_where", "tombstone", "append", "compact")] + ["p_l2"]
+               + [f"q_{k}_{x}" for k in H.MASKABLE for x in ("plain", "own")] + ["r"]
+               + [f"s_{w}>{r}" for w in ("update_where", "set_attr_at") for r in GROUP_READERS] + ["s_float_add", "t", "u"]
+               + ["v_" + w for w in H.WIDE_REFUSALS] + ["w_compact", "w_reset"])
+
+
+def test_the_wide_histories_meet_every_coverage_condition():
+    where, tagged = {}, {}
+    for key in H.WIDE:
+        ops, expected = H.make_history(*key)
+        for name, step in wide_conditions(ops, expected, key[1]).items():
+            where.setdefault(name, (key[0], step))
+        assert max(e["counts"][0] for e in expected if "counts" in e) <= H.MAX_ROWS_WIDE, key
+        for step, op in enumerate(ops):  # the kinds that take a program, and those of them that got a list or sparse leaf
+            if programs_of(op):
+                tagged.setdefault(op["op"], None)
+                if tagged[op["op"]] is None and pooled_leaf(op):
+                    tagged[op["op"]] = (key[0], step)
+        print(f"history {H.history_tag(*key)}: {len(ops)} steps")
+    for name in WIDE_WANTED:
+        if name in where:
+            print(f"condition {name}: seed {where[name][0]}, step {where[name][1]}")
+    missing = [name for name in WIDE_WANTED if name not in where]
+    assert not missing, f"coverage conditions never met: {missing}"
+    assert len(H.WIDE_PAIRS) == 16 * 29 - 8 * 19 and len(H.WIDE) == 12
+    # the new program kinds go into every program-taking op, old kinds included
+    for kind, at in sorted(tagged.items()):
+        print(f"a list or sparse leaf in {kind}: " + ("never" if at is None else f"seed {at[0]}, step {at[1]}"))
+    assert set(PROGRAM_TAKING) <= set(tagged) and not [kind for kind, at in tagged.items() if at is None], tagged
+    # the large ones move the inner search between the routes by `auto` alone: exact, filter, exact after the compaction, filter
+    for key in H.WIDE_LARGE:
+        ops, expected = H.make_history(*key)
+        st = wide_trace(ops, expected, key[1])
+        assert all(s["strategy"] == "auto" for s in st)
+        for kind in ("search_mmr", "search_like", "search_grouped"):
+            routes = [s["total"] >= H.FILTER_MIN_ROWS for op, s in zip(ops, st) if op["op"] == kind and
+                      (len(op["groups"]) if kind == "search_like" else op["nq"]) >= 12]
+            assert True in routes and False in routes[routes.index(True):] and routes[-1] is True, (key, kind, routes)
+        each = [(op["nq"], s["total"] >= H.FILTER_MIN_ROWS, any(list_leaf({"programs": op["programs"]}, H.LIST_A) for _ in [0]))
+                for op, s in zip(ops, st) if op["op"] == "search_each"]
+        assert {(12, True, True), (40, True, True)} <= set(each), each
+        kinds = {op["op"] for op in ops}
+        assert {"search_mmr", "search_like", "search_grouped", "search_maxsim", "search_each", "tombstone_where", "compact"} <= kinds
+        assert sum(op["op"] in H.WIDE_QUERIES for op in ops) <= 20
+        i = [op["op"] for op in ops].index("tombstone_where")
+        died = expected[i]["counts"][1] / expected[i]["counts"][0]
+        assert 0.25 < died < 0.42, died
+        print(f"history {H.history_tag(*key)}: {len(ops)} steps, tombstone_where of {died:.0%} of the rows at step {i}")
+
+
+def test_pool_capacity_after_mirrors_list_pool_reserve():
+    assert H.pool_capacity_after(0, 0) == 0 and H.pool_capacity_after(0, 1) == 1024 and H.pool_capacity_after(1024, 1024) == 1024
+    assert H.pool_capacity_after(1024, 1025) == 2048 and H.pool_capacity_after(2048, 9000) == 9000
+    assert H.pool_capacity_after(700, 701) == 1400  # after a repack the capacity is the live sum, whatever it is
+    m = H.WideHistoryModel(4, "l2")
+    m.define_attr(4, "int64_list")
+    m.append(np.zeros((600, 4), np.float32))
+    lists = H.csr([[1, 2, 3]] * 600)
+    m.set_attr_list(4, 0, lists)
+    assert m.pools()[4] == (1800, 1800, 1800)
+    m.set_attr_list(4, 0, lists)
+    assert m.pools()[4] == (3600, 3600, 1800)
+    m.compact()
+    assert m.pools()[4] == (1800, 1800, 1800)
+    m.reset()
+    assert m.pools()[4] == (0, 1800, 0)
+
+
+# ---------------------------------------------------------------- sensitivity of the wide histories: five seeded defects
+def _differs(a, b):
+    return any((x is None) != (y is None) or (x is not None and np.asarray(x).tobytes() != np.asarray(y).tobytes()) for x, y in zip(a, b))
+
+
+def reads_pooled(op):
+    return op["op"] in H.LIST_READERS + ("get_attr_list",) or any(
+        o[1] in H.POOLED and o[0] not in (W.AND, W.OR, W.NOT, W.TRUE) for p in programs_of(op) for o in p["ops"])
+
+
+class KeepsListsInOldRowOrder(H.WideHistoryModel):
+    """Lists and sparse vectors stay in pre-compaction row order while the scalar columns move."""
+    fired = None
+    seen_by = staticmethod(reads_pooled)
+    at_once = False
+
+    def compact(self):
+        lists = {a: list(rows) for a, rows in self._lists.items()}
+        lengths = {a: self._cols[a].copy() for a in self._lists}
+        old = super().compact()
+        for a in lists:
+            if self.fired is None and lists[a][:old.size] != self._lists[a]:
+                self.fired = self.step
+            self._lists[a], self._cols[a] = lists[a][:old.size], lengths[a][:old.size]
+        return old
+
+
+class ListsSurviveReset(H.WideHistoryModel):
+    """``reset`` leaves the lists where they were: freshly appended rows inherit them."""
+    fired = None
+    seen_by = staticmethod(reads_pooled)
+    at_once = False
+    _left = None
+
+    def reset(self, space=None):
+        self._left = {a: list(rows) for a, rows in self._lists.items()}
+        super().reset(space)
+
+    def append(self, rows):
+        first = super().append(rows)
+        for a, left in (self._left or {}).items():
+            for row in range(first, min(self._rows.shape[0], len(left))):
+                if left[row] is not None:
+                    self._put(a, row, left[row])
+                    if self.fired is None:
+                        self.fired = self.step
+        self._left = None
+        return first
+
+
+class InnerSearchMissesFilteredDeletes(H.WideHistoryModel):
+    """``search_mmr`` and ``search_like`` do not see the rows ``tombstone_where`` deleted (until a compaction drops them)."""
+    fired = None
+    seen_by = staticmethod(lambda op: op["op"] in ("search_mmr", "search_like"))
+    at_once = True
+    _ghosts = None
+
+    def tombstone_where(self, program):
+        labels = super().tombstone_where(program)
+        self._ghosts = labels if self._ghosts is None else np.union1d(self._ghosts, labels)
+        return labels
+
+    def compact(self):
+        self._ghosts = None
+        return super().compact()
+
+    def reset(self, space=None):
+        self._ghosts = None
+        super().reset(space)
+
+    def _haunted(self, name, *a, **kw):
+        right = getattr(super(), name)(*a, **kw)
+        if self._ghosts is None or not self._ghosts.size:
+            return right
+        keep = self._deleted.copy()
+        self._deleted[self._ghosts] = False
+        try:
+            wrong = getattr(super(), name)(*a, **kw)
+        finally:
+            self._deleted = keep
+        if self.fired is None and _differs(right, wrong):
+            self.fired = self.step
+        return wrong
+
+    def search_mmr(self, *a, **kw):
+        return self._haunted("search_mmr", *a, **kw)
+
+    def search_like(self, *a, **kw):
+        return self._haunted("search_like", *a, **kw)
+
+
+class AppliesARefusedUpdate(H.WideHistoryModel):
+    """``update_where`` writes what it can although ``refused > 0``."""
+    fired = None
+    seen_by = staticmethod(lambda op: op["op"] == "get_attr")
+    at_once = False
+
+    def update_where(self, program, assigns):
+        hit = self.match(program)
+        matched, refused = super().update_where(program, assigns)
+        if refused:
+            for attr, op, a in assigns:
+                col = self._cols[attr]
+                if op == H._native.SET_ASSIGN:
+                    col.view(np.int64)[hit] = a
+                elif col.dtype == np.int64:
+                    rows = hit & (col != W.INT64_ABSENT)
+                    with np.errstate(over="ignore"):
+                        col[rows] = col[rows] + np.int64(a)
+            if self.fired is None:
+                self.fired = self.step
+        return matched, refused
+
+
+class MaxsimReadsTheOldDocumentColumn(H.WideHistoryModel):
+    """``search_maxsim`` is answered from the document column as it was before the last ``update_where``."""
+    fired = None
+    seen_by = staticmethod(lambda op: op["op"] == "search_maxsim")
+    at_once = True
+    _before = None
+
+    def update_where(self, program, assigns):
+        self._before = {a: col.copy() for a, col in self._cols.items()}
+        return super().update_where(program, assigns)
+
+    def search_maxsim(self, tokens, offsets, k, attr, where=None, want_matches=False):
+        right = super().search_maxsim(tokens, offsets, k, attr, where, want_matches)
+        old = (self._before or {}).get(attr)
+        if old is None or old.size != self._cols[attr].size:
+            return right
+        keep = self._cols[attr]
+        self._cols[attr] = old
+        try:
+            wrong = super().search_maxsim(tokens, offsets, k, attr, where, want_matches)
+        finally:
+            self._cols[attr] = keep
+        if self.fired is None and _differs(right, wrong):
+            self.fired = self.step
+        return wrong
+
+
+@pytest.mark.parametrize("defect", [KeepsListsInOldRowOrder, ListsSurviveReset, InnerSearchMissesFilteredDeletes,
+                                    AppliesARefusedUpdate, MaxsimReadsTheOldDocumentColumn])
+def test_the_driver_reports_a_seeded_defect_in_the_wide_histories(defect, tmp_path, monkeypatch):
+    from tests import conftest
+
+    monkeypatch.setattr(conftest, "OUT_DIR", tmp_path)
+    reported, real_call = 0, H.call
+    for key in H.WIDE[:4]:
+        ops, expected = H.make_history(*key)
+        engine = defect(key[2], key[1])
+        stepped = []
+
+        def counted(e, op, a, engine=engine, stepped=stepped):
+            if e is engine:
+                engine.step = len(stepped)
+                stepped.append(op["op"])
+            return real_call(e, op, a)
+
+        monkeypatch.setattr(H, "call", counted)
+        tag = H.history_tag(*key)
+        try:
+            H.run_history(engine, ops, expected, tag)
+        except AssertionError as err:
+            failed = len(stepped) - 1
+            assert f"history {tag}: step {failed}, op " in str(err) and f"seed{key[0]}" in str(err)
+            assert engine.fired is not None and defect.seen_by(ops[failed]), (engine.fired, failed, ops[failed])
+            if defect.at_once:  # `fired` is the first call whose answer the defect changes: that call is the one reported
+                assert failed == engine.fired, (failed, engine.fired)
+            else:               # the state breaks in a mutation; the first later call that reads it differently reports it
+                assert failed > engine.fired and ops[engine.fired]["op"] in H.WIDE_MUTATIONS, (failed, engine.fired)
+            dumped = json.loads((tmp_path / f"history_{tag}.json").read_text())
+            assert dumped["failed_step"] == failed and dumped["ops"] == ops[:failed + 1]
+            print(f"{defect.__name__}: {tag} fired at step {engine.fired}, reported at step {failed} ({ops[failed]['op']})")
+            reported += 1
+        else:
+            assert engine.fired is None or not defect.at_once, f"{tag}: fired at step {engine.fired}, never reported"
+        monkeypatch.setattr(H, "call", real_call)
+    assert reported >= 2, f"{defect.__name__}: reported in {reported} of 4 histories"
+
+
 # ---------------------------------------------------------------- redraws
 def test_near_tie_redraws_stay_under_one_percent():
     drawn = redrawn = 0
-    for key in H.HISTORIES:
+    for key in H.HISTORIES + H.WIDE + H.WIDE_LARGE:
         a, b = H.redraw_counts(*key)
         drawn, redrawn = drawn + a, redrawn + b
     print(f"{redrawn} of {drawn} drawn queries were redrawn")
