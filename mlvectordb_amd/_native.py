@@ -203,6 +203,16 @@ SPARSE_SIGNATURES = {
     "mlvdb_search_batch_sparse": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(Where), _P, _P, _P, _P]),
 }
 
+# include/mlvdb_hybrid.h: hybrid search -- a dense and a sparse kNN answer fused into one ranked list on the device
+FUSE_CODES = {"rrf": 0, "linear": 1, "relative": 2}
+HYBRID_MAX_FETCH_DENSE = 1024
+HYBRID_CHUNK = 256  # queries per round of the two legs + union + completion + fusion inside one native call (api.hip: kHybridChunk)
+HYBRID_SIGNATURES = {
+    "mlvdb_search_batch_hybrid": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_double, C.c_double, C.c_double, C.POINTER(Where),
+                                            _P, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -234,7 +244,7 @@ def load() -> C.CDLL:
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
-                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES}.items():
+                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **HYBRID_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -151,6 +151,9 @@ struct mlvdb_index {
     DevBuf list_sums, list_out;
     // sparse vector columns (mlvdb_sparse.h): a pass's tiles, term unions and weights; its answers
     DevBuf sparse_in, sparse_out;
+    // hybrid search (mlvdb_hybrid.h): a chunk's dense and sparse queries, its two ranked lists, the union with the completed
+    // components, and its outputs -- sized by the chunk (<= kHybridChunk queries), k and the fetch sizes, never by the corpus
+    DevBuf hyb_q, hyb_list, hyb_union, hyb_out;
     // per-query filters (mlvdb_where_each.h): the call's programs, one 64-bit word per row, per-segment counts / offsets,
     // match totals, the gathered route's label lists, tiles, queries and outputs
     DevBuf each_prog, each_bits, each_seg, each_tot, each_lab, each_tiles, each_q, each_qpad, each_qaux, each_out;
@@ -1305,7 +1308,7 @@ int mlvdb_index_destroy(mlvdb_index* h) {
                       &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->like_q, &h->like_ex, &h->like_list, &h->like_out,
                       &h->ms_tab, &h->ms_rowdoc, &h->ms_best, &h->ms_misc, &h->ms_out,
                       &h->facet_tab, &h->facet_misc, &h->order_ws, &h->mutate_ws, &h->list_sums, &h->list_out,
-                      &h->sparse_in, &h->sparse_out})
+                      &h->sparse_in, &h->sparse_out, &h->hyb_q, &h->hyb_list, &h->hyb_union, &h->hyb_out})
         b->release();
     if (h->host_flags) (void)hipHostFree(h->host_flags);
     h->pin_in.release();
@@ -4309,10 +4312,10 @@ int sparse_csr_pack(mlvdb_index* h, int64_t n, const int64_t* offsets, const int
     return MLVDB_OK;
 }
 
-// One pass of at most kSparseChunk queries [q0, q1): tiles, unions and weights up, scan, merge, answers down.
-int sparse_pass(mlvdb_index* h, int32_t attr, const int64_t* off, const int32_t* terms, const float* weights, int64_t q0,
-                int64_t q1, int32_t k, const uint8_t* mask, int64_t* out_labels, float* out_score, int32_t* out_counts,
-                double* out_score64) {
+// The device part of one pass of at most kSparseChunk queries [q0, q1): tiles, unions and weights up, scan, merge; the ranked
+// answers stay on the device in `o` ((q1 - q0) * k entries, q1 - q0 counts).  Returns with the stream drained.
+int sparse_pass_device(mlvdb_index* h, int32_t attr, const int64_t* off, const int32_t* terms, const float* weights, int64_t q0,
+                       int64_t q1, int32_t k, const uint8_t* mask, const ListBlock& o) {
     hipStream_t s = h->stream;
     const int32_t n = (int32_t)(q1 - q0);
     // greedy tiles: consecutive queries while they are <= kSparseQT and their term union holds <= kSparseMaxUnion terms
@@ -4350,19 +4353,30 @@ int sparse_pass(mlvdb_index* h, int32_t attr, const int64_t* off, const int32_t*
     // [tiles | U | W], all 4-byte fields
     const size_t tbytes = tiles.size() * sizeof(SparseTile), ubytes = U.size() * sizeof(int32_t), wbytes = W.size() * sizeof(float);
     HIP_TRY(h, h->sparse_in.ensure(tbytes + ubytes + wbytes + 16));
-    HIP_TRY(h, h->sparse_out.ensure(ListBlock::bytes(nk, (size_t)n)));
     HIP_TRY(h, h->partial.ensure(nk * (size_t)nblk * sizeof(TopEntry)));
     char* in = h->sparse_in.as<char>();
     HIP_TRY(h, hipMemcpyAsync(in, tiles.data(), tbytes, hipMemcpyHostToDevice, s));
     if (ubytes) HIP_TRY(h, hipMemcpyAsync(in + tbytes, U.data(), ubytes, hipMemcpyHostToDevice, s));
     if (wbytes) HIP_TRY(h, hipMemcpyAsync(in + tbytes + ubytes, W.data(), wbytes, hipMemcpyHostToDevice, s));
-    const ListBlock o(h->sparse_out.p, nk, (size_t)n);
     HIP_TRY(h, launch_sparse_scan(h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total,
                                   reinterpret_cast<const SparseTile*>(in), ntiles, reinterpret_cast<const int32_t*>(in + tbytes),
                                   reinterpret_cast<const float*>(in + tbytes + ubytes), k, nblk, h->partial.as<TopEntry>(), s));
     HIP_TRY(h, launch_sparse_merge(h->partial.as<TopEntry>(), n, nblk, k, o.lab, o.dist, o.cnt, o.d64, s));
-    const size_t at = (size_t)q0 * k;
     HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
+    return MLVDB_OK;
+}
+
+// One pass: its device part into h->sparse_out, answers down.
+int sparse_pass(mlvdb_index* h, int32_t attr, const int64_t* off, const int32_t* terms, const float* weights, int64_t q0,
+                int64_t q1, int32_t k, const uint8_t* mask, int64_t* out_labels, float* out_score, int32_t* out_counts,
+                double* out_score64) {
+    hipStream_t s = h->stream;
+    const int32_t n = (int32_t)(q1 - q0);
+    const size_t nk = (size_t)n * k;
+    HIP_TRY(h, h->sparse_out.ensure(ListBlock::bytes(nk, (size_t)n)));
+    const ListBlock o(h->sparse_out.p, nk, (size_t)n);
+    if (int rc = sparse_pass_device(h, attr, off, terms, weights, q0, q1, k, mask, o)) return rc;
+    const size_t at = (size_t)q0 * k;
     HIP_TRY(h, hipMemcpyAsync(out_labels + at, o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(out_score + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -4477,6 +4491,153 @@ int mlvdb_search_batch_sparse(mlvdb_index* h, int32_t attr, const int64_t* q_off
             return rc;
     }
     return MLVDB_OK;
+    });
+}
+
+// ---- hybrid search (mlvdb_hybrid.h)
+extern "C++" {
+namespace {
+constexpr int64_t kHybridChunk = kSparseChunk;  // queries per round: one sparse pass, one plain search, three or five launches
+
+// The validated call (h->rn is the masked copy and `mask` h->row_mask when a program restricts the rows).  Per chunk of
+// queries: dense and sparse queries up -> the plain device search for fetch_dense neighbours and the sparse pass for
+// fetch_sparse, both lists left on the device -> union -> the completion (launch_pair_distances on the members without a
+// distance, the gathered scorer on those without a score; skipped when `complete` is false) -> fuse and select -> outputs down.
+int hybrid_impl(mlvdb_index* h, const float* queries, int32_t attr, const int64_t* off, const int32_t* terms,
+                const float* weights, int64_t nq, int32_t k, int32_t fd, int32_t fs, int32_t method, double w_dense,
+                double w_sparse, double rrf_c, const uint8_t* mask, int64_t* out_labels, double* out_fused, int32_t* out_counts,
+                double* out_dist64, double* out_sparse64, int32_t* out_rank_dense, int32_t* out_rank_sparse) {
+    hipStream_t s = h->stream;
+    if (h->total == 0 || h->total == h->deleted) {
+        std::fill(out_labels, out_labels + nq * k, (int64_t)-1);
+        std::fill(out_fused, out_fused + nq * k, -__builtin_inf());
+        std::fill(out_counts, out_counts + nq, 0);
+        if (out_dist64) std::fill(out_dist64, out_dist64 + nq * k, __builtin_inf());
+        if (out_sparse64) std::fill(out_sparse64, out_sparse64 + nq * k, -__builtin_inf());
+        if (out_rank_dense) std::fill(out_rank_dense, out_rank_dense + nq * k, -1);
+        if (out_rank_sparse) std::fill(out_rank_sparse, out_rank_sparse + nq * k, -1);
+        return MLVDB_OK;
+    }
+    const bool complete = method != MLVDB_FUSE_RRF || out_dist64 || out_sparse64;
+    const int32_t m = fd + fs;
+    std::vector<int64_t> roff;
+    for (int64_t q0 = 0; q0 < nq; q0 += kHybridChunk) {
+        const int32_t n = (int32_t)std::min<int64_t>(kHybridChunk, nq - q0);
+        const size_t nk = (size_t)n * k, nm = (size_t)n * m, nt = (size_t)(off[q0 + n] - off[q0]);
+        const size_t dbytes = (ListBlock::bytes((size_t)n * fd, (size_t)n) + 7) & ~(size_t)7;
+        HIP_TRY(h, h->hyb_q.ensure(((size_t)n + 1) * sizeof(int64_t) + (size_t)n * sizeof(double) +
+                                   (size_t)n * (h->dim + h->ld) * sizeof(float) + nt * (sizeof(int32_t) + sizeof(float)) + 16));
+        HIP_TRY(h, h->hyb_list.ensure(dbytes + ListBlock::bytes((size_t)n * fs, (size_t)n)));
+        HIP_TRY(h, h->hyb_union.ensure(nm * (2 * sizeof(double) + 3 * sizeof(int64_t) + 2 * sizeof(int32_t)) +
+                                       (size_t)n * sizeof(int32_t)));
+        HIP_TRY(h, h->hyb_out.ensure(nk * (3 * sizeof(double) + sizeof(int64_t) + 2 * sizeof(int32_t)) + (size_t)n * sizeof(int32_t)));
+        Carver in{h->hyb_q.as<char>()};  // [offsets | qaux | queries | padded queries | terms | weights]
+        int64_t* d_off = in.take<int64_t>((size_t)n + 1);
+        double* d_aux = in.take<double>((size_t)n);
+        float* dq = in.take<float>((size_t)n * h->dim);
+        float* d_pad = in.take<float>((size_t)n * h->ld);
+        int32_t* d_terms = in.take<int32_t>(nt);
+        float* d_weights = in.take<float>(nt);
+        const ListBlock ld(h->hyb_list.p, (size_t)n * fd, (size_t)n);
+        const ListBlock ls(h->hyb_list.as<char>() + dbytes, (size_t)n * fs, (size_t)n);
+        Carver un{h->hyb_union.as<char>()};  // [comp_d | comp_s | labels | need_d | need_s | rank_D | rank_S | counts]
+        double* comp_d = un.take<double>(nm);
+        double* comp_s = un.take<double>(nm);
+        int64_t* u_lab = un.take<int64_t>(nm);
+        int64_t* need_d = un.take<int64_t>(nm);
+        int64_t* need_s = un.take<int64_t>(nm);
+        int32_t* u_rd = un.take<int32_t>(nm);
+        int32_t* u_rs = un.take<int32_t>(nm);
+        int32_t* u_cnt = un.take<int32_t>((size_t)n);
+        Carver out{h->hyb_out.as<char>()};  // [fused | d64 | s64 | labels | rank_D | rank_S | counts]
+        double* o_fused = out.take<double>(nk);
+        double* o_d64 = out.take<double>(nk);
+        double* o_s64 = out.take<double>(nk);
+        int64_t* o_lab = out.take<int64_t>(nk);
+        int32_t* o_rd = out.take<int32_t>(nk);
+        int32_t* o_rs = out.take<int32_t>(nk);
+        int32_t* o_cnt = out.take<int32_t>((size_t)n);
+        roff.resize((size_t)n + 1);
+        for (int32_t i = 0; i <= n; ++i) roff[(size_t)i] = off[q0 + i] - off[q0];
+        // (the host arrays of these copies are consumed when sparse_pass_device returns: it drains the stream)
+        HIP_TRY(h, hipMemcpyAsync(dq, queries + (size_t)q0 * h->dim, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(d_off, roff.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        if (nt) {
+            HIP_TRY(h, hipMemcpyAsync(d_terms, terms + off[q0], nt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(d_weights, weights + off[q0], nt * sizeof(float), hipMemcpyHostToDevice, s));
+        }
+        if (int rc = search_device_impl(h, dq, n, fd, ld.lab, ld.dist, ld.cnt, ld.d64, s, false)) return rc;
+        if (int rc = sparse_pass_device(h, attr, off, terms, weights, q0, q0 + n, fs, mask, ls)) return rc;
+        HIP_TRY(h, launch_hybrid_union(ld.lab, ld.cnt, fd, ls.lab, ls.cnt, fs, n, u_lab, u_rd, u_rs, need_d, need_s, u_cnt, s));
+        if (complete) {
+            HIP_TRY(h, launch_query_prep(dq, n, h->dim, h->ld, h->space, d_pad, d_aux, nullptr, s));
+            HIP_TRY(h, launch_pair_distances(h->X, d_pad, d_aux, need_d, n, m, h->ld, h->space, comp_d, nullptr, s));
+            HIP_TRY(h, launch_sparse_pair_score(h->attr_col[attr], h->list_pool[attr], h->total, d_off, d_terms, d_weights, need_s,
+                                                u_cnt, n, m, comp_s, s));
+        }
+        HIP_TRY(h, launch_hybrid_fuse(u_lab, u_rd, u_rs, u_cnt, n, m, ld.d64, fd, ls.d64, fs, complete ? comp_d : nullptr,
+                                      complete ? comp_s : nullptr, method, w_dense, w_sparse, rrf_c, k, o_lab, o_fused, o_cnt,
+                                      out_dist64 ? o_d64 : nullptr, out_sparse64 ? o_s64 : nullptr,
+                                      out_rank_dense ? o_rd : nullptr, out_rank_sparse ? o_rs : nullptr, s));
+        const size_t at = (size_t)q0 * k;
+        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
+        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o_lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_fused + at, o_fused, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o_d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_sparse64) HIP_TRY(h, hipMemcpyAsync(out_sparse64 + at, o_s64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (out_rank_dense) HIP_TRY(h, hipMemcpyAsync(out_rank_dense + at, o_rd, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (out_rank_sparse) HIP_TRY(h, hipMemcpyAsync(out_rank_sparse + at, o_rs, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_hybrid(mlvdb_index* h, const float* queries, int32_t attr, const int64_t* q_offsets,
+                              const int32_t* q_terms, const float* q_weights, int64_t nq, int32_t k, int32_t fetch_dense,
+                              int32_t fetch_sparse, int32_t method, double w_dense, double w_sparse, double rrf_c,
+                              const mlvdb_where* where, int64_t* out_labels, double* out_fused, int32_t* out_counts,
+                              double* out_dist64, double* out_sparse64, int32_t* out_rank_dense, int32_t* out_rank_sparse) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked on the host before anything is launched (the program: with_where)
+    if ((rc = sparse_attr_check(h, attr))) return rc;
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "hybrid: k above MLVDB_MAX_TOPK");
+    if (fetch_dense < 1 || fetch_sparse < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: fetch_dense / fetch_sparse must be >= 1");
+    if (fetch_dense > kHybridMaxFetchDense) return fail(h, MLVDB_ERR_UNSUPPORTED, "hybrid: fetch_dense above MLVDB_HYBRID_MAX_FETCH_DENSE");
+    if (fetch_sparse > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "hybrid: fetch_sparse above MLVDB_MAX_TOPK");
+    if (k > fetch_dense + fetch_sparse) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: k above fetch_dense + fetch_sparse");
+    if (method != MLVDB_FUSE_RRF && method != MLVDB_FUSE_LINEAR && method != MLVDB_FUSE_RELATIVE)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: unknown fusion method");
+    if (!(std::isfinite(w_dense) && w_dense >= 0.0 && std::isfinite(w_sparse) && w_sparse >= 0.0))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: a weight must be finite and >= 0");
+    if (!(std::isfinite(rrf_c) && rrf_c >= 0.0)) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: the RRF constant must be finite and >= 0");
+    if (nq > 0 && (!queries || !q_offsets || !out_labels || !out_fused || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (nq > 0 && q_offsets[0] != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: q_offsets must start at 0");
+    for (int64_t i = 0; i < nq; ++i) {
+        const int64_t len = q_offsets[i + 1] - q_offsets[i];
+        const bool have = len > 0 && q_terms && q_weights;
+        if ((rc = sparse_vector_check(h, have ? q_terms + q_offsets[i] : nullptr, have ? q_weights + q_offsets[i] : nullptr, len,
+                                      MLVDB_SPARSE_MAX_QUERY_TERMS)))
+            return rc;
+    }
+    for (int64_t i = 0; i < nq * h->dim; ++i)
+        if (queries[i] != queries[i]) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: a NaN in the dense queries");
+    if (h->total > INT32_MAX) return fail(h, MLVDB_ERR_UNSUPPORTED, "hybrid: more than 2^31 - 1 rows");
+    auto call = [&]() {
+        // (under a program h->row_mask holds the one evaluation both legs read: the dense leg through the masked norms)
+        const uint8_t* mask = where && h->total > 0 ? h->row_mask.as<uint8_t>() : nullptr;
+        return hybrid_impl(h, queries, attr, q_offsets, q_terms, q_weights, nq, k, fetch_dense, fetch_sparse, method, w_dense,
+                           w_sparse, rrf_c, mask, out_labels, out_fused, out_counts, out_dist64, out_sparse64, out_rank_dense,
+                           out_rank_sparse);
+    };
+    // the first launches: where_run(h, where, ...) for the program, then hybrid_impl under with_row_mask(h, nq, ...)
+    return with_where(h, where, nq, call);
     });
 }
 

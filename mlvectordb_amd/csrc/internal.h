@@ -22,6 +22,7 @@
 #include "../../include/mlvdb_mutate.h"
 #include "../../include/mlvdb_list.h"
 #include "../../include/mlvdb_sparse.h"
+#include "../../include/mlvdb_hybrid.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -405,6 +406,30 @@ hipError_t launch_sparse_scan(const int64_t* slots, const int64_t* pool, const f
 // ... folded: labels (-1), scores (float and double, -inf) and counts of nq queries
 hipError_t launch_sparse_merge(const TopEntry* partial, int32_t nq, int32_t nblk, int32_t k, int64_t* out_labels,
                                float* out_score, int32_t* out_counts, double* out_s64, hipStream_t s);
+
+// ---------------------------------------------------------------- hybrid search (kernels_hybrid.hip, include/mlvdb_hybrid.h)
+constexpr int kHybridMaxFetchDense = MLVDB_HYBRID_MAX_FETCH_DENSE;
+constexpr int kHybridMaxUnion = kHybridMaxFetchDense + kWave;  // |C| <= fetch_dense + fetch_sparse
+// One block per query over its ranked lists (d_lab: [nq][fd], s_lab: [nq][fs], d_cnt / s_cnt valid entries): the union in
+// [nq][fd + fs] arrays -- D's entries in order, then S's that D lacks, in order; u_rd / u_rs the member's position in D / S
+// (-1: not in it); need_d / need_s the member's label where it lacks a distance / a score, -1 elsewhere; the tails all -1
+hipError_t launch_hybrid_union(const int64_t* d_lab, const int32_t* d_cnt, int32_t fd, const int64_t* s_lab,
+                               const int32_t* s_cnt, int32_t fs, int32_t nq, int64_t* u_lab, int32_t* u_rd, int32_t* u_rs,
+                               int64_t* need_d, int64_t* need_s, int32_t* u_cnt, hipStream_t s);
+// The gathered scorer: out[q][p] = the sparse score of (query q, row labels[q][p]) for p < min(cnt[q], m), the bits
+// launch_sparse_scan gives the pair; +0.0 for a label < 0 and for a row without a vector.  The queries are a CSR on the
+// device (q_off[0 .. nq], <= kSparseMaxUnion terms each); labels < total.
+hipError_t launch_sparse_pair_score(const int64_t* slots, const int64_t* pool, int64_t total, const int64_t* q_off,
+                                    const int32_t* q_terms, const float* q_weights, const int64_t* labels, const int32_t* cnt,
+                                    int32_t nq, int32_t m, double* out, hipStream_t s);
+// One block per query: the members' components (the lists' own d_d64 / s_d64 where u_rd / u_rs >= 0, else comp_d / comp_s;
+// both null: an RRF call that reports no component), the fused score of `method` and the top k by (fused descending, label
+// ascending) to the outputs [nq][k] with padded tails; out_d64 / out_s64 / out_rd / out_rs may be null
+hipError_t launch_hybrid_fuse(const int64_t* u_lab, const int32_t* u_rd, const int32_t* u_rs, const int32_t* u_cnt, int32_t nq,
+                              int32_t m, const double* d_d64, int32_t fd, const double* s_d64, int32_t fs, const double* comp_d,
+                              const double* comp_s, int32_t method, double w_dense, double w_sparse, double rrf_c, int32_t k,
+                              int64_t* out_labels, double* out_fused, int32_t* out_counts, double* out_d64, double* out_s64,
+                              int32_t* out_rd, int32_t* out_rs, hipStream_t s);
 
 // rn[i] = NaN for the rows of mask, and their int8 row pairs (i < i8_rows; rp8 may be null) as tombstone_rp8_kernel does
 hipError_t launch_tombstone_mask(const uint8_t* mask, float* rn, float* rp8, int64_t i8_rows, int l2, int64_t total,

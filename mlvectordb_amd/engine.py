@@ -477,6 +477,45 @@ class HipScanEngine:
                     "search_batch_sparse")
         return labels, score, counts, score64
 
+    # -- hybrid search (include/mlvdb_hybrid.h) -------------------------------------------
+    def search_hybrid(self, queries: np.ndarray, attr: int, sparse_queries, k: int, fetch_dense: int, fetch_sparse: int,
+                      method: str = "rrf", weights=(1.0, 1.0), rrf_k: float = 60.0, where=None, components: bool = False):
+        """Dense and sparse kNN fused on the device (``mlvdb_search_batch_hybrid``): ``queries`` [nq, dim], ``sparse_queries``
+        a ``where.SparseColumn`` of ``nq`` vectors over sparse column ``attr`` (an empty one gets the sparse search's
+        label-ordered zero-score list: a caller without a sparse query wants ``search``), ``method`` one of "rrf", "linear",
+        "relative", ``weights`` = (w_dense, w_sparse), ``where`` a compiled filter or ``None`` (it restricts both legs).
+        Returns (labels int64 [nq, k] padded -1, fused float64 [nq, k] padded -inf, counts int32 [nq]) and, with
+        ``components``, (dist64, sparse64, rank_dense, rank_sparse) behind them: each hit's completed components and its
+        position in the two candidate lists (-1: not in that list)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        if method not in _native.FUSE_CODES:
+            raise RuntimeError(f"unknown fusion method {method!r} (one of {sorted(_native.FUSE_CODES)})")
+        offsets = np.ascontiguousarray(sparse_queries.offsets, dtype=np.int64)
+        terms = np.ascontiguousarray(sparse_queries.terms, dtype=np.int32)
+        wts = np.ascontiguousarray(sparse_queries.weights, dtype=np.float32)
+        nq, k = queries.shape[0], int(k)
+        if offsets.size != nq + 1 or terms.size != wts.size:
+            raise RuntimeError(f"{nq} dense queries but {offsets.size} offsets, {terms.size} terms and {wts.size} weights")
+        shape = (nq, max(k, 0))
+        labels = np.empty(shape, dtype=np.int64)
+        fused = np.empty(shape, dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.int32)
+        d64 = np.empty(shape, dtype=np.float64) if components else None
+        s64 = np.empty(shape, dtype=np.float64) if components else None
+        rd = np.empty(shape, dtype=np.int32) if components else None
+        rs = np.empty(shape, dtype=np.int32) if components else None
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_search_batch_hybrid(
+            self._h, queries.ctypes.data, int(attr), offsets.ctypes.data, terms.ctypes.data if terms.size else None,
+            wts.ctypes.data if wts.size else None, nq, k, int(fetch_dense), int(fetch_sparse), _native.FUSE_CODES[method],
+            float(weights[0]), float(weights[1]), float(rrf_k), None if w is None else C.byref(w), labels.ctypes.data,
+            fused.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
+            None if s64 is None else s64.ctypes.data, None if rd is None else rd.ctypes.data,
+            None if rs is None else rs.ctypes.data), "search_batch_hybrid")
+        return (labels, fused, counts, d64, s64, rd, rs) if components else (labels, fused, counts)
+
     # -- per-query filters (include/mlvdb_where_each.h) -------------------------------
     @staticmethod
     def _where_array(programs):

@@ -160,6 +160,28 @@ class GroupedBatchHits(BatchHits):
                    np.zeros((nq, 0), dtype=np.int32), np.full((nq, 0), None, dtype=object))
 
 
+class HybridBatchHits(BatchHits):
+    """What ``search_hybrid(components=True)`` returns: ``BatchHits`` whose ``scores`` is the fused score, plus what it was
+    fused from:
+
+    ``dense``        float64 [nq, k]  the hit's distance to the dense query (+inf at padding)
+    ``sparse``       float64 [nq, k]  its sparse score (-inf at padding)
+    ``rank_dense``   int32 [nq, k]    its position among the dense candidates, -1: only the sparse leg found it
+    ``rank_sparse``  int32 [nq, k]    its position among the sparse candidates, -1: only the dense leg found it
+    """
+
+    __slots__ = ("dense", "sparse", "rank_dense", "rank_sparse")
+
+    def __init__(self, labels, scores, counts, table, dense, sparse, rank_dense, rank_sparse) -> None:
+        super().__init__(labels, scores, counts, table)
+        self.dense, self.sparse, self.rank_dense, self.rank_sparse = dense, sparse, rank_dense, rank_sparse
+
+    @classmethod
+    def empty(cls, nq: int) -> "HybridBatchHits":
+        return cls(np.full((nq, 0), -1, dtype=np.int64), np.zeros((nq, 0)), np.zeros(nq, dtype=np.int32), None,
+                   np.zeros((nq, 0)), np.zeros((nq, 0)), np.zeros((nq, 0), dtype=np.int32), np.zeros((nq, 0), dtype=np.int32))
+
+
 @dataclass
 class DocumentResult:
     value: object  # the document: the decoded value of the ``by`` attribute (``str`` / ``bool`` / ``int``)
@@ -851,6 +873,101 @@ class Index:
                                   np.ones(nq, dtype=np.uint8))
         labels, _, counts, s64 = search(list(self._attributes).index(by), col, k, where=program)
         return BatchHits(labels, s64, counts, ns.ids)
+
+    _FUSIONS = ("rrf", "linear", "relative")  # MLVDB_FUSE_*
+    _MAX_FETCH_K_HYBRID = 1024                # MLVDB_HYBRID_MAX_FETCH_DENSE
+
+    @classmethod
+    def _default_fetch_k_sparse(cls, top_k: int) -> int:
+        return min(cls._MAX_TOP_K_SPARSE, max(int(top_k), 20))
+
+    def search_hybrid(self, queries, sparse_queries, top_k: int, namespace: str, metric: str, by: str, *,
+                      fusion: str = "rrf", weights=(1.0, 1.0), rrf_k: float = 60.0, fetch_k: Optional[int] = None,
+                      fetch_k_sparse: Optional[int] = None, where: Optional[Mapping] = None,
+                      components: bool = False) -> BatchHits:
+        """Additive: hybrid retrieval in one device call (include/mlvdb_hybrid.h).  Query ``i`` is the dense vector
+        ``queries[i]`` and the sparse vector ``sparse_queries[i]`` (typed as for ``search_sparse``) over the declared
+        ``sparse`` attribute ``by``.  The ``fetch_k`` nearest rows (default ``min(1024, max(4 * top_k, 20))``, at most 1024)
+        and the ``fetch_k_sparse`` best lexical matches (default ``min(64, max(top_k, 20))``, at most 64) are joined, every
+        row of the union gets both its distance and its sparse score, and the ``top_k`` (<= 64) rows with the largest fused
+        score come back, ties to the earlier row.  ``fusion``:
+
+        ``"rrf"``       ``w_dense / (rrf_k + rank_dense + 1) + w_sparse / (rrf_k + rank_sparse + 1)``, a term being 0 for a
+                        row its list does not hold (ranks are 0-based)
+        ``"linear"``    ``w_sparse * sparse_score - w_dense * distance``
+        ``"relative"``  ``w_dense * nd + w_sparse * ns``, the components min-max normalised over the union (the nearest row
+                        has ``nd`` 1, the best match ``ns`` 1)
+
+        with ``weights = (w_dense, w_sparse)``, finite and >= 0, and the distance the index's own (whatever ``metric``).
+        ``where`` (one dict filter) is evaluated once and restricts both legs.  ``scores`` is the fused score;
+        ``components=True`` returns a ``HybridBatchHits`` that adds ``dense`` (the distance), ``sparse`` (the score),
+        ``rank_dense`` and ``rank_sparse`` (-1: the hit is not in that list).  An empty sparse query is no special case: its
+        sparse list is the first ``fetch_k_sparse`` rows by label with score 0 -- a caller without a sparse query wants
+        ``search_many``.  The fetch sizes are clamped to the live row count.  Every refusal happens before the engine is
+        touched."""
+        if self._devices is not None and len(self._devices) > 1:
+            raise ValueError("search_hybrid is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        if not isinstance(by, str) or by not in self._attributes:
+            raise ValueError(f"search_hybrid: {by!r} is not a declared attribute of this index "
+                             f"(declared: {sorted(self._attributes)})")
+        if not _where.is_sparse(self._attributes[by]):
+            raise ValueError(f"search_hybrid: attribute {by!r} is a {self._attributes[by]} column; it needs a sparse attribute")
+        if fusion not in self._FUSIONS:
+            raise ValueError(f"search_hybrid: fusion must be one of {self._FUSIONS} (got {fusion!r})")
+        try:
+            w_dense, w_sparse = (float(w) for w in weights)
+            c = float(rrf_k)
+        except (TypeError, ValueError):
+            raise ValueError(f"search_hybrid: weights is a pair of numbers and rrf_k a number (got {weights!r}, {rrf_k!r})") from None
+        if not (np.isfinite(w_dense) and w_dense >= 0 and np.isfinite(w_sparse) and w_sparse >= 0):
+            raise ValueError(f"search_hybrid: weights must be finite and >= 0 (got {weights!r})")
+        if not (np.isfinite(c) and c >= 0):
+            raise ValueError(f"search_hybrid: rrf_k must be finite and >= 0 (got {rrf_k!r})")
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"search_hybrid: where must be one dict filter or None (got {type(where).__name__})")
+        if top_k > self._MAX_TOP_K_SPARSE:
+            raise ValueError(f"search_hybrid: top_k must be <= {self._MAX_TOP_K_SPARSE} (got {top_k})")
+        fetch_k = self._default_fetch_k(max(int(top_k), 0)) if fetch_k is None else int(fetch_k)
+        fetch_k_sparse = self._default_fetch_k_sparse(max(int(top_k), 0)) if fetch_k_sparse is None else int(fetch_k_sparse)
+        if not 1 <= fetch_k <= self._MAX_FETCH_K_HYBRID:
+            raise ValueError(f"search_hybrid: fetch_k must lie in [1, {self._MAX_FETCH_K_HYBRID}] (got {fetch_k})")
+        if not 1 <= fetch_k_sparse <= self._MAX_TOP_K_SPARSE:
+            raise ValueError(f"search_hybrid: fetch_k_sparse must lie in [1, {self._MAX_TOP_K_SPARSE}] (got {fetch_k_sparse})")
+        if top_k > fetch_k + fetch_k_sparse:
+            raise ValueError(f"search_hybrid: top_k must be <= fetch_k + fetch_k_sparse (got {top_k} > {fetch_k} + {fetch_k_sparse})")
+        if isinstance(sparse_queries, Mapping) or isinstance(sparse_queries, (str, bytes)):
+            raise ValueError("search_hybrid: sparse_queries is a sequence of sparse vectors (got one mapping: wrap it in a list)")
+        sparse_queries = list(sparse_queries)
+        q = self._coerce_queries(queries)
+        nq = q.shape[0]
+        if len(sparse_queries) != nq:
+            raise ValueError(f"search_hybrid: {nq} dense queries but {len(sparse_queries)} sparse queries")
+        if not np.isfinite(q).all():
+            raise ValueError("search_hybrid: a dense query holds a non-finite value (NaN / inf)")
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        terms: List[int] = []
+        wts: List[float] = []
+        for i, sq in enumerate(sparse_queries):
+            t, w = _where.encode_sparse_vector(sq, f"search_hybrid: sparse query {i}", _where.SPARSE_MAX_QUERY_TERMS)
+            terms.extend(t)
+            wts.extend(w)
+            offsets[i + 1] = len(terms)
+        program = None if where is None else self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
+            return HybridBatchHits.empty(nq) if components else BatchHits.empty(nq)
+        search = getattr(ns.engine, "search_hybrid", None)
+        if search is None:
+            raise ValueError("search_hybrid needs an engine with search_hybrid (a single-device namespace)")
+        active = ns.total - ns.deleted
+        k = min(int(top_k), active)
+        col = _where.SparseColumn(offsets, np.array(terms, dtype=np.int32), np.array(wts, dtype=np.float32),
+                                  np.ones(nq, dtype=np.uint8))
+        out = search(q, list(self._attributes).index(by), col, k, min(fetch_k, active), min(fetch_k_sparse, active),
+                     method=fusion, weights=(w_dense, w_sparse), rrf_k=c, where=program, components=components)
+        if not components:
+            return BatchHits(out[0], out[1], out[2], ns.ids)
+        return HybridBatchHits(out[0], out[1], out[2], ns.ids, *out[3:7])
 
     _MAX_TOP_K_MMR = 64      # MLVDB_MAX_TOPK
     _MAX_FETCH_K_MMR = 1024  # MLVDB_MMR_MAX_FETCH: the longest candidate list the selection walks

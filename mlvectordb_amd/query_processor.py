@@ -164,6 +164,31 @@ class QueryProcessor:
             raise ValueError("find_similar_sparse needs an index with search_sparse")
         return self._enrich_many(self._index.search_sparse(queries, top_k, namespace, by, where=where), namespace)
 
+    def find_similar_hybrid(self, query, sparse_query, top_k: int, namespace: str = "default", metric: str = "cosine",
+                            by: str = "", **options) -> List[dict]:
+        """Additive: hybrid retrieval for one query -- a dense vector and a sparse one (a mapping ``{term: weight}`` or a
+        pair ``(indices, values)``) over the declared ``sparse`` attribute ``by`` -- fused on the device
+        (``Index.search_hybrid``, whose keywords ``fusion``, ``weights``, ``rrf_k``, ``fetch_k``, ``fetch_k_sparse`` and
+        ``where`` pass through): the ``top_k`` (<= 64) vectors with the largest fused score, as ``find_similar_many``
+        returns a hit (``score``: the fused score)."""
+        values = getattr(query, "values", query)
+        return self.find_similar_hybrid_many(np.asarray(values, dtype=np.float32)[None, :], [sparse_query], top_k, namespace,
+                                             metric, by, **options)[0]
+
+    def find_similar_hybrid_many(self, queries, sparse_queries, top_k: int, namespace: str = "default",
+                                 metric: str = "cosine", by: str = "", *, fusion: str = "rrf", weights=(1.0, 1.0),
+                                 rrf_k: float = 60.0, fetch_k: Optional[int] = None, fetch_k_sparse: Optional[int] = None,
+                                 where=None) -> List[List[dict]]:
+        """Batched ``find_similar_hybrid``: one dense and one sparse vector per query, one device call.  ``where`` is
+        ``None`` or one dict filter; it restricts both legs."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("find_similar_hybrid: where must be one dict filter (or None)")
+        if not hasattr(self._index, "search_hybrid"):
+            raise ValueError("find_similar_hybrid needs an index with search_hybrid")
+        hits = self._index.search_hybrid(queries, sparse_queries, top_k, namespace, metric, by, fusion=fusion, weights=weights,
+                                         rrf_k=rrf_k, fetch_k=fetch_k, fetch_k_sparse=fetch_k_sparse, where=where)
+        return self._enrich_many(hits, namespace)
+
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
         if where is None:
             return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric)
