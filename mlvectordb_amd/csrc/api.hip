@@ -125,7 +125,9 @@ struct mlvdb_index {
     DevBuf stage, qpad, qaux, partial, qsel, seed_lab, seed_dist, seed_cnt, seed_d64;
     DevBuf cand_range, rhits, rhit_cnt;  // range passes: larger candidate lists, exact hits, hit counts
     DevBuf row_mask, rn_masked;  // filtered search
-    DevBuf qerr, rowerr;         // rounding errors of the bf16 images: per query / maximum over the rows (device scalar)
+    DevBuf qerr, rowerr;         // rounding errors of the bf16 images: per query / maximum over the rows (device scalars: kRowErrWords)
+    unsigned int row_stats[kRowErrWords] = {};  // where an append reads rowerr back to
+    float norm_max = 0.f, norm_min = __builtin_inff();  // largest / smallest norm of a non-zero row ever appended (magnitudes_in_window)
     // experimental int8 shadow (MLVDB_I8=1, cosine, ld % 256 == 0): built lazily at search time, rebuilt after any mutation
     DevBuf x8, rp8, rowerr8, qimg8, sq8;
     DevBuf l2tag;  // l2: which pass scale the offsets plane behind rp8 ([0..3]) / rp8_masked ([4..7]) was computed for: filter_l2_offsets_kernel
@@ -377,10 +379,38 @@ int list_repack_all(mlvdb_index* h, int64_t rows) {
     return MLVDB_OK;
 }
 
+// The device scalars row_norms_kernel maintains (internal.h: kRowErrWords) and their host copies, as of an index without rows.
+int clear_row_stats(mlvdb_index* h, bool keep_row_error = false) {
+    static const unsigned int empty[kRowErrWords] = {0u, 0u, 0x7f800000u, 0u};  // {no error, largest norm 0, smallest +inf, -}
+    const int first = keep_row_error ? 1 : 0;  // (compaction: the bf16 error of the rows that left stays, an upper bound)
+    HIP_TRY(h, hipMemcpyAsync(h->rowerr.as<unsigned int>() + first, empty + first, (kRowErrWords - first) * sizeof(unsigned int),
+                              hipMemcpyHostToDevice, h->stream));
+    h->norm_max = 0.f;
+    h->norm_min = __builtin_inff();
+    return MLVDB_OK;
+}
+
+// After rows were appended (their row_norms_kernel is on h->stream): the norm range of the index, for use_filter.  The
+// caller synchronises the stream.
+int fetch_row_stats(mlvdb_index* h) {
+    HIP_TRY(h, hipMemcpyAsync(h->row_stats, h->rowerr.p, sizeof h->row_stats, hipMemcpyDeviceToHost, h->stream));
+    return MLVDB_OK;
+}
+void commit_row_stats(mlvdb_index* h) {
+    std::memcpy(&h->norm_max, &h->row_stats[1], sizeof(float));
+    std::memcpy(&h->norm_min, &h->row_stats[2], sizeof(float));
+}
+
+// Do the norms of the index's non-zero rows lie inside the magnitude window of the filter path (internal.h, DESIGN
+// "Magnitudes")?  Tombstones do not narrow the range again; compaction (from the live rows' norms) and mlvdb_index_reset do.
+bool magnitudes_in_window(const mlvdb_index* h) {
+    return h->norm_max <= norm_window_hi(h->space) && h->norm_min >= norm_window_lo(h->space);  // (no non-zero row: 0 and +inf)
+}
+
 int reserve_rows(mlvdb_index* h, int64_t rows) {
-    if (!h->rowerr.p) {  // largest relative bf16 rounding error of any row appended so far (0 = no rows)
-        HIP_TRY(h, h->rowerr.ensure(sizeof(unsigned int)));
-        HIP_TRY(h, hipMemsetAsync(h->rowerr.p, 0, sizeof(unsigned int), h->stream));
+    if (!h->rowerr.p) {  // largest relative bf16 rounding error of any row appended so far (0 = no rows), and their norm range
+        HIP_TRY(h, h->rowerr.ensure(kRowErrWords * sizeof(unsigned int)));
+        if (int rc = clear_row_stats(h)) return rc;
     }
     if (rows <= h->capacity) return MLVDB_OK;
     int64_t want = rows;
@@ -1157,6 +1187,9 @@ int filter_ready(mlvdb_index* h, hipStream_t s, int64_t nq, bool* ready) {
 
 bool use_filter(const mlvdb_index* h, int64_t nq, bool ready) {
     if (h->strategy == MLVDB_STRATEGY_EXACT || !ready) return false;
+    // rows beyond the magnitude window: no shadow holds them and the fp32 bounds overflow -- the exact scans (fp64) serve the
+    // index whatever strategy is set, a forced MLVDB_STRATEGY_FILTER included
+    if (!magnitudes_in_window(h)) return false;
     if (h->strategy == MLVDB_STRATEGY_FILTER) return true;
     const bool shadowed = h->Xb != nullptr || h->i8_only;
     // dim < 64: the padded int8 shadow (256 B per row) is wider than the fp32 rows (4 ld B), and the exact scan of such short
@@ -1340,7 +1373,9 @@ int mlvdb_index_append_device(mlvdb_index* h, const float* rows_device, int64_t 
     HIP_TRY(h, launch_scatter_rows(rows_device, h->X, h->total, n, h->dim, h->ld, h->stream));
     HIP_TRY(h, launch_row_norms(h->X, h->rn, h->total, n, h->ld, h->rowerr.as<unsigned int>(), h->stream));
     if (h->Xb) HIP_TRY(h, launch_shadow_rows(h->X, h->Xb, h->total, n, h->ld, h->stream));
+    if (int rc2 = fetch_row_stats(h)) return rc2;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    commit_row_stats(h);
     h->total += n;
     return MLVDB_OK;
     });
@@ -1365,7 +1400,9 @@ int mlvdb_index_append(mlvdb_index* h, const float* rows, int64_t n, int64_t* fi
         HIP_TRY(h, launch_scatter_rows(h->stage.as<float>(), h->X, h->total + done, m, h->dim, h->ld, h->stream));
         HIP_TRY(h, launch_row_norms(h->X, h->rn, h->total + done, m, h->ld, h->rowerr.as<unsigned int>(), h->stream));
         if (h->Xb) HIP_TRY(h, launch_shadow_rows(h->X, h->Xb, h->total + done, m, h->ld, h->stream));
+        if (int rc2 = fetch_row_stats(h)) return rc2;
         HIP_TRY(h, hipStreamSynchronize(h->stream));
+        commit_row_stats(h);
     }
     h->total += n;
     return MLVDB_OK;
@@ -1439,6 +1476,14 @@ int mlvdb_index_compact(mlvdb_index* h, int64_t* old_labels, int64_t capacity, i
     HIP_TRY(h, hipMemsetAsync(nrn, 0xFF, (size_t)cap * sizeof(float), s));  // NaN = not a row
     if (nXb) HIP_TRY(h, hipMemsetAsync(nXb, 0, (size_t)cap * h->ld * 2, s));
     HIP_TRY(h, launch_compact_rows(h->X, nX, h->Xb, nXb, h->rn, nrn, old_of_new, want, h->ld, s));
+    // the norm range starts over from the rows that stay: a tombstoned row outside the magnitude window leaves with them
+    // (read back at the synchronisation below, committed with the new buffers)
+    const float old_max = h->norm_max, old_min = h->norm_min;
+    if (int rc2 = clear_row_stats(h, true)) return rc2;
+    h->norm_max = old_max;  // (the index still holds the old rows until the swap)
+    h->norm_min = old_min;
+    HIP_TRY(h, launch_norm_range(nrn, want, h->rowerr.as<unsigned int>(), s));
+    if (int rc2 = fetch_row_stats(h)) return rc2;
     int64_t* ncol[MLVDB_MAX_ATTRS];
     if (int rc2 = attr_alloc(h, cap, want, old_of_new, ncol)) {  // the attribute columns move with their rows
         (void)hipStreamSynchronize(s);
@@ -1451,6 +1496,7 @@ int mlvdb_index_compact(mlvdb_index* h, int64_t* old_labels, int64_t capacity, i
     if (want > 0)
         HIP_TRY(h, hipMemcpyAsync(host_map.data(), old_of_new, (size_t)want * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
+    commit_row_stats(h);
     attr_commit(h, ncol);
     for (int64_t i = 0; i < want; ++i) old_labels[i] = host_map[(size_t)i];
     (void)hipFree(h->X);
@@ -1490,7 +1536,8 @@ int mlvdb_index_reset(mlvdb_index* h, int32_t space) {
             if (h->attr_col[a]) HIP_TRY(h, launch_attr_fill(h->attr_col[a], attr_absent(h->attr_type[a]), 0, h->capacity, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    if (h->rowerr.p) HIP_TRY(h, hipMemsetAsync(h->rowerr.p, 0, sizeof(unsigned int), h->stream));
+    if (h->rowerr.p)
+        if (int rc2 = clear_row_stats(h)) return rc2;
     for (int64_t& used : h->list_used) used = 0;  // the list pools are empty again (their allocations stay)
     h->total = 0;
     h->deleted = 0;

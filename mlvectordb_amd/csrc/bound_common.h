@@ -16,6 +16,10 @@ __device__ __forceinline__ float float_below(double v) {
 // round a double up to a float that is >= it
 __device__ __forceinline__ float float_above(double v) { return -float_below(-v); }
 
+// the next float above a non-negative f (an error term "rounded up by one bit"); FLT_MAX becomes +inf, and +inf and NaN
+// stay what they are -- one more than the bits of +inf would be a NaN, which every comparison then answers with "no"
+__device__ __forceinline__ float float_bump(float f) { return f <= 3.4028234663852886e38f ? __uint_as_float(__float_as_uint(f) + 1u) : f; }
+
 __device__ __forceinline__ uint32_t float_order_key(float f) {  // monotone float -> uint (larger float, larger key)
     const uint32_t b = __float_as_uint(f);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);

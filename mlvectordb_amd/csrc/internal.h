@@ -117,9 +117,12 @@ hipError_t launch_scatter_rows(const float* stage, float* X, int64_t first_row, 
 // Xb (bf16 shadow, layout_offset_b) for the same rows, from the fp32 panels
 hipError_t launch_shadow_rows(const float* X, void* Xb, int64_t first_row, int64_t n, int32_t ld, hipStream_t s);
 // rn[row] = (float)|x_row| for the same rows (fp64 sum of squares); *rel_err_max = max(*rel_err_max, |x - bf16(x)| / |x|)
-// as float bits (rounded up)
+// as float bits (rounded up); rel_err_max[1] / [2] = the largest / smallest norm of a non-zero row so far, as float bits
+// (+inf for a row whose norm is no float): the index's side of the magnitude window below
 hipError_t launch_row_norms(const float* X, float* rn, int64_t first_row, int64_t n, int32_t ld, unsigned int* rel_err_max,
                             hipStream_t s);
+// stats[1] / [2] (as launch_row_norms keeps them) from the stored norms of rows [0, n): max / min over the live non-zero rows
+hipError_t launch_norm_range(const float* rn, int64_t n, unsigned int* stats, hipStream_t s);
 // panels -> row-major [n, dim]
 hipError_t launch_gather_rows(const float* X, float* out, int64_t first_row, int64_t n, int32_t dim, int32_t ld,
                               hipStream_t s);
@@ -188,6 +191,20 @@ hipError_t launch_pair_distances(const float* X, const float* Qpad, const double
                                  int32_t m, int32_t ld, int32_t space, double* out64, float* out32, hipStream_t s);
 
 // ---------------------------------------------------------------- filter path (kernels_filter.hip)
+// The magnitude window of the filter path (DESIGN "Magnitudes").  Its bounds, thresholds and shadows are fp32, and a threshold
+// beyond +-1e30 counts as a sentinel; the window is where that arithmetic neither overflows nor loses a normal float:
+//   cosine  2^-100 .. 2^120  scores lie in [-1, 1]; above, a norm or a bf16 component nears +inf; below, |x| + 1e-30 is all
+//                            regulariser and the shadows' scales turn subnormal
+//   ip      2^-63 .. 2^90    scores reach |x| (in units of |q|)
+//   l2      2^-63 .. 2^48    scores reach |q|^2 + 2 |q| |x| + |x|^2: 4 x 2^96 = 3.2e29; a squared norm of 2^-126 is still normal
+// An index holding a non-zero row whose norm lies outside the window is served by the exact scans (use_filter, api.hip); a
+// non-zero query outside it is flagged for the exact fallback by the pass's prep kernel (query_leaves_window,
+// kernels_filter.hip).  Zero rows and zero queries are inside.
+__host__ __device__ constexpr float norm_window_lo(int space) { return space == kSpaceCosine ? 0x1p-100f : 0x1p-63f; }
+__host__ __device__ constexpr float norm_window_hi(int space) {
+    return space == kSpaceCosine ? 0x1p120f : (space == kSpaceIp ? 0x1p90f : 0x1p48f);
+}
+constexpr int kRowErrWords = 4;       // the index's device scalars behind FilterArgs::row_err: {bf16 error, largest norm, smallest norm, -}
 constexpr int kFilterQueries = 256;   // queries per filter pass
 constexpr int kFilterChunkK = 64;     // columns per Q chunk staged in LDS
 constexpr int kCandCap = 8192;        // candidate slots per query (kNN passes; also the most range hits sorted in LDS)
@@ -231,7 +248,7 @@ struct FilterArgs {
     const float* Qpad;      // [nq][ld] raw queries of this pass (q0..q0+nq)
     const double* qaux;
     const float* qerr;      // [nq] rounding error of the bf16 query image, |q^ - q^_b| (rounded up)
-    const float* row_err;   // device scalar: max over rows of |x - bf16(x)| / |x| (rounded up)
+    const float* row_err;   // device scalars: [0] max over rows of |x - bf16(x)| / |x| (rounded up), [1] the largest row norm
     int32_t nq;             // <= kFilterQueries
     // workspace (per pass)
     void* qimg;             // bf16 image, filter_qimg_bytes

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void filter_prep_kernel(const FilterArgs a) {
         // per-query error term of the bound (see the header): E1q, plus the slack of the epilogue arithmetic
         const double e1q = (q < a.nq ? (double)a.qerr[q] : 0.0) + 1.00390625 * (double)*a.row_err + (double)a.ld * 2.384185791015625e-07;
         float ke = (float)(e1q * 1.000001) + (a.space == kSpaceCosine ? 2.0f : 1.0f) * kSlack;
-        a.ke[q] = __uint_as_float(__float_as_uint(ke) + 1u);
+        a.ke[q] = float_bump(ke);
         a.thr[q] = q < a.nq ? -3.0e38f : 3.4e38f;  // padded queries never admit anything
         a.cnt[q] = 0;
         a.overflow[q] = 0;
@@ -1543,7 +1543,7 @@ __global__ __launch_bounds__(256) void shadow8_rows_kernel(const float* X, const
         float rel = 0.f;  // (every lane of the row holds the reduced sums)
         if (n2 > 0.0) {
             rel = (float)(__builtin_sqrt(err2 / n2) * 1.000001);
-            rel = __uint_as_float(__float_as_uint(rel) + 1u);
+            rel = float_bump(rel);
         }
         if (nrm[p] == nrm[p]) bg = __builtin_fmaxf(bg, rel);
         if (g == 0) {
@@ -1801,6 +1801,20 @@ __global__ __launch_bounds__(256) void filter_prep8_fin_kernel(const FilterArgs 
     prep8_fin_query(a, q, sqmin, eqmax);
 }
 
+// Does a query of norm qn leave the magnitude window of the filter path (internal.h: norm_window_lo / _hi; DESIGN "Magnitudes")?
+//  - its norm: beyond the window the fp32 query scale, thresholds and bounds of the pass overflow or lose their meaning;
+//  - cosine / ip: the distance is 1 - s, and once every |s| the index can give (xmax: its largest row norm) is below 2^-24 the
+//    subtraction keeps fewer than 29 bits of s: rows the filter tells apart by s tie in the fp64 distance and fall to their
+//    labels, which only a scan of every row sees.
+// The zero query is inside (every score is 0).
+__device__ __forceinline__ bool query_leaves_window(double qn, double xmax, int space) {
+    if (!(qn > 0.0)) return false;
+    if (qn < (double)norm_window_lo(space) || qn > (double)norm_window_hi(space)) return true;
+    if (space == kSpaceL2) return false;
+    const double top = space == kSpaceIp ? qn * xmax : (qn / (qn + 1e-30)) * (xmax / (xmax + 1e-30));
+    return top < 5.9604644775390625e-08;  // 2^-24
+}
+
 // ------------------------------------------------------------------ one launch for everything a pass needs of its queries
 // query_prep_kernel (padded copy, norm, bf16 rounding error) + filter_prep_kernel (bf16 image, per-query state) +
 // filter_prep8_kernel (int8 image, scale, error) as ONE kernel, block q = query q of the pass: three launches and their
@@ -1812,6 +1826,7 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
     __shared__ double dred[4];
     __shared__ float fred[4];
     __shared__ double s_inv;
+    __shared__ bool s_flag;
     const int q = blockIdx.x;
     const bool real = q < a.nq;
     const int ld = a.ld;
@@ -1834,8 +1849,13 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
         const double aux = query_aux_from_sums(dred, a.space);
         if (real) qaux[q] = aux;
         s_inv = a.space == kSpaceCosine ? aux : 1.0 / (aux + 1e-30);
+        // a query outside the magnitude window starts the pass flagged, like one whose list overflowed: the exact scan serves
+        // it from Qpad / qaux.  To the pass it is the zero query (image, scales, error terms): nothing of it reaches what the
+        // queries of a pass share (a.sqmin, a.rmaxq and the common l2 step), and none of its own constants overflows.
+        s_flag = real && query_leaves_window(__builtin_sqrt((dred[0] + dred[1]) + (dred[2] + dred[3])), (double)a.row_err[1], a.space);
     }
     __syncthreads();
+    const bool live = real && !s_flag;
     const double inv = s_inv;
     const float invf = (float)inv;
     // 2. bf16 image in B-fragment order (filter_prep_kernel) and its measured rounding error (query_prep_kernel)
@@ -1845,7 +1865,7 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
     double e2 = 0.0;
     float amax = 0.f;
     for (int c = threadIdx.x; c < ld; c += 256) {
-        const float x = real ? dst[c] : 0.f;  // (this thread wrote dst[c] itself)
+        const float x = live ? dst[c] : 0.f;  // (this thread wrote dst[c] itself)
         const float v = x * invf;
         const __bf16 b = (__bf16)v;
         int kc = c >> 6, ks, g, j;
@@ -1874,24 +1894,24 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
     __syncthreads();
     if (threadIdx.x == 0) {
         float e = (float)(__builtin_sqrt((dred[0] + dred[1]) + (dred[2] + dred[3])) * 1.000001);
-        e = __uint_as_float(__float_as_uint(e) + 1u);  // never below the true error
+        e = float_bump(e);  // never below the true error
         if (real) qerr[q] = e;
         // per-query state of the pass (filter_prep_kernel, block 0)
-        const double nrm = real ? (a.space == kSpaceCosine ? 0.0 : qaux[q]) : 0.0;
+        const double nrm = live ? (a.space == kSpaceCosine ? 0.0 : qaux[q]) : 0.0;
         a.qscale[q] = a.space == kSpaceL2 ? (float)(2.0 * nrm) : 1.0f;
         const double e1q = (real ? (double)e : 0.0) + 1.00390625 * (double)*a.row_err + (double)ld * 2.384185791015625e-07;
         const float ke = (float)(e1q * 1.000001) + (a.space == kSpaceCosine ? 2.0f : 1.0f) * kSlack;
-        a.ke[q] = __uint_as_float(__float_as_uint(ke) + 1u);
+        a.ke[q] = float_bump(ke);
         a.thr[q] = real ? -3.0e38f : 3.4e38f;  // padded queries never admit anything
         a.cnt[q] = 0;
-        a.overflow[q] = 0;
+        a.overflow[q] = s_flag ? 1u : 0u;
     }
     if (!want_i8) return;
     amax = __builtin_fmaxf(__builtin_fmaxf(fred[0], fred[1]), __builtin_fmaxf(fred[2], fred[3]));
     if (a.l2c) {
         // l2 with one quantisation step for the whole pass (round 4: filter_prep8_l2c_kernel builds the images once the pass's
         // largest raw component is known): here only this query's largest |q_i| = max |q^_i| x |q|, rounded up
-        if (threadIdx.x == 0) a.rmaxq[q] = real ? float_above((double)amax * (qaux[q] + 1e-30) * 1.000001) : 0.f;
+        if (threadIdx.x == 0) a.rmaxq[q] = live ? float_above((double)amax * (qaux[q] + 1e-30) * 1.000001) : 0.f;
         return;
     }
     // 3. int8 image, scale and error (filter_prep8_kernel); a.sqmin[] was left initialised by the previous pass's fin kernel
@@ -1900,7 +1920,7 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
     int8_t* img8 = reinterpret_cast<int8_t*>(a.qimg8);
     double err2 = 0.0;
     for (int c = threadIdx.x; c < a.ld8; c += 256) {  // (columns ld..ld8 of the image: zeros, like the shadow's)
-        const float v = real && c < ld ? dst[c] * invf : 0.f;
+        const float v = live && c < ld ? dst[c] * invf : 0.f;
         float t = __builtin_rintf(v * isq);
         t = __builtin_fminf(127.f, __builtin_fmaxf(-127.f, t));
         const double e = (double)v - (double)sq * (double)t;
@@ -1977,7 +1997,8 @@ __global__ __launch_bounds__(256) void filter_prep8_l2c_kernel(const FilterArgs 
         if (g >= qmax && g <= qmax * 1.5f) qmax = g;  // (anything odd in the float functions: keep the exact maximum)
     }
     const float SQ = qmax > 0.f ? float_above((double)qmax * (2.0 / 127.0) * 1.000001) : 1.0f;
-    const double nrm = real ? a.qaux[q] : 0.0;  // l2: qaux = |q|
+    const bool live = real && a.overflow[q] == 0u;  // (flagged by the fused kernel: the zero query to this pass)
+    const double nrm = live ? a.qaux[q] : 0.0;  // l2: qaux = |q|
     const float invf = (float)(1.0 / (nrm + 1e-30));  // as filter_prep_kernel forms q^ = q / (|q| + 1e-30)
     const float sq = nrm > 0.0 ? (float)((double)SQ / (2.0 * nrm)) : 1.0f;
     const float isq = 1.0f / sq;
@@ -1985,7 +2006,7 @@ __global__ __launch_bounds__(256) void filter_prep8_l2c_kernel(const FilterArgs 
     const int n16 = q >> 4, c16 = q & 15;
     double err2 = 0.0;
     for (int c = threadIdx.x; c < a.ld8; c += 256) {  // (columns ld..ld8 of the image: zeros, like the shadow's)
-        const float v = real && c < ld ? a.Qpad[(int64_t)q * ld + c] * invf : 0.f;
+        const float v = live && c < ld ? a.Qpad[(int64_t)q * ld + c] * invf : 0.f;
         float t = __builtin_rintf(v * isq);
         t = __builtin_fminf(127.f, __builtin_fmaxf(-127.f, t));
         const double e = (double)v - (double)sq * (double)t;

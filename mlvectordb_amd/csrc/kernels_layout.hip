@@ -3,6 +3,7 @@
 // src/mlvectordb/implementations/index.py:65,80,158 (the index copies and owns the rows).
 #include <algorithm>
 
+#include "bound_common.h"
 #include "internal.h"
 #include "query_norm.h"
 
@@ -73,7 +74,9 @@ __global__ __launch_bounds__(256) void gather_rows_at_kernel(const float* __rest
 // One wave per panel; lane 16*g + r sums the squares of row r over its column slices.
 // Also maintains *rel_err_max = max over rows of |x - bf16(x)| / |x| (RNE, the conversion the filter scan and the
 // shadow use): the row half of the filter's rounding bound (kernels_filter.hip).  Non-negative floats order like
-// their bit patterns, so the maximum is an atomicMax on the bits.
+// their bit patterns, so the maximum is an atomicMax on the bits.  rel_err_max[1] / [2]: the largest / smallest norm of a
+// non-zero row, the same way (a norm beyond FLT_MAX is +inf and stays the maximum): what use_filter (api.hip) holds against
+// the magnitude window of the filter path.
 __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict__ X, float* __restrict__ rn,
                                                         int64_t first_row, int64_t n, int32_t ld,
                                                         unsigned int* __restrict__ rel_err_max) {
@@ -102,12 +105,29 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const float* __restrict_
         err += __shfl_xor(err, 32);
         const int64_t row = panel * kPanelRows + (lane & 15);
         if (lane < 16 && row >= first_row && row < first_row + n) {
-            rn[row] = (float)__builtin_sqrt(s);
-            if (s > 0.0 && err > 0.0) {
+            const float nrm = (float)__builtin_sqrt(s);
+            rn[row] = nrm;
+            if (s > 0.0) {  // (the norm of a non-zero row is at least 2^-149: never 0 as a float)
+                atomicMax(rel_err_max + 1, __float_as_uint(nrm));
+                atomicMin(rel_err_max + 2, __float_as_uint(nrm));
+            }
+            if (s > 0.0 && err > 0.0) {  // (a component bf16 rounds to inf: err = rel = +inf, an honest "no bound")
                 float rel = (float)(__builtin_sqrt(err / s) * 1.000001);
-                rel = __uint_as_float(__float_as_uint(rel) + 1u);  // (float) may have rounded down
+                rel = float_bump(rel);  // (float) may have rounded down
                 atomicMax(rel_err_max, __float_as_uint(rel));
             }
+        }
+    }
+}
+
+// The norm range of the live rows [0, n) from their stored norms (NaN: tombstoned, 0: a zero row), into stats[1] / stats[2] as
+// row_norms_kernel keeps them: what compaction starts the range over with.
+__global__ __launch_bounds__(256) void norm_range_kernel(const float* __restrict__ rn, int64_t n, unsigned int* __restrict__ stats) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = rn[i];
+        if (v > 0.f) {  // (false for NaN)
+            atomicMax(stats + 1, __float_as_uint(v));
+            atomicMin(stats + 2, __float_as_uint(v));
         }
     }
 }
@@ -165,7 +185,7 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict
     __syncthreads();
     if (threadIdx.x == 0) {
         float e = (float)(__builtin_sqrt((red[0] + red[1]) + (red[2] + red[3])) * 1.000001);
-        qerr[q] = __uint_as_float(__float_as_uint(e) + 1u);  // (float) may have rounded down; never below the true error
+        qerr[q] = float_bump(e);  // (float) may have rounded down; never below the true error
     }
 }
 
@@ -200,6 +220,12 @@ hipError_t launch_gather_rows_at(const float* X, float* out, const int64_t* labe
                                  hipStream_t s) {
     if (n <= 0) return hipSuccess;
     gather_rows_at_kernel<<<(unsigned)n, 256, 0, s>>>(X, out, labels, dim, ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_norm_range(const float* rn, int64_t n, unsigned int* stats, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    norm_range_kernel<<<grid_for(n, 256), 256, 0, s>>>(rn, n, stats);
     return hipGetLastError();
 }
 

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void shadow16_rows_kernel(const float* __restr
         s16[row] = sx;
         if (n2 > 0.0) {
             float rel = (float)(__builtin_sqrt(err2 / n2) * 1.000001);
-            rel = __uint_as_float(__float_as_uint(rel) + 1u);  // never below the true relative error
+            rel = float_bump(rel);  // never below the true relative error
             atomicMax(row_err16, __float_as_uint(rel));        // non-negative floats order like their bits
         }
     }
