@@ -111,27 +111,50 @@ def _seq_sum(md, off, k):
     return out
 
 
-def check_maxsim(eng, toks, off, k, got, want, tag):
+def check_maxsim(eng, toks, off, k, got, want, tag, magnitudes=None):
     """``got``: what ``eng.search_maxsim(toks, off, k, attr, want_matches=True)`` returned, against the oracle's (groups,
-    score64, counts, match labels, match dist64) for this k; the bit contracts."""
+    score64, counts, match labels, match dist64) for this k; the bit contracts.
+
+    ``magnitudes`` (tests/test_gpu_magnitudes_families.py: inputs anywhere in the float32 range) = (rows, space, excluded
+    queries): padding is then told by group INT64_MIN / label -1 alone -- a real document's fp32 score may be +-inf -- every
+    match distance is held to magnitude_helpers.family_fp64_bar (the score is their sequential sum, bit for bit, below), and
+    the ids of the ``excluded`` queries are not compared; the bit contracts hold for every query either way."""
     from tests.conftest import dump_mismatch
 
     grp, s32, cnt, s64, ml, md = got
     wg, ws, wc, wml, wmd = want
-    if not (np.array_equal(grp, wg) and np.array_equal(cnt, wc) and np.array_equal(ml, wml)):
-        dump_mismatch(f"maxsim_{tag}", grp=grp, wg=wg, cnt=cnt, wc=wc, ml=ml, wml=wml, s64=s64, ws=ws, md=md, wmd=wmd)
-        bad = np.flatnonzero((grp != wg).any(axis=1) | (cnt != wc))
-        i = int(bad[0]) if bad.size else -1
-        raise AssertionError(f"{tag}: {bad.size} queries differ in groups / counts (first {i}: got {grp[i].tolist()} "
-                             f"({cnt[i]}) want {wg[i].tolist()} ({wc[i]})); match labels equal: {np.array_equal(ml, wml)}")
-    fin = np.isfinite(ws)
-    assert np.array_equal(np.isfinite(s64), fin) and np.array_equal(np.isfinite(s32), fin), f"{tag}: padding differs"
-    assert np.array_equal(np.isfinite(md), np.isfinite(wmd)), f"{tag}: match padding differs"
-    if fin.any():
-        err = float((np.abs(s64[fin] - ws[fin]) / np.maximum(1.0, np.abs(ws[fin]))).max())
-        print(f"{tag}: max |score64 - oracle| / max(1, |s|) = {err:.3e}")
-        assert err <= SCORE_ATOL, f"{tag}: score error {err}"
-    assert np.array_equal(s32.view(np.int32), s64.astype(np.float32).view(np.int32)), f"{tag}: fp32 is not the rounded fp64"
+    off = np.asarray(off, dtype=np.int64)
+    tok_query = np.repeat(np.arange(off.size - 1), np.diff(off))
+    bad = np.union1d(np.flatnonzero((grp != wg).any(axis=1) | (cnt != wc)), tok_query[(ml != wml).any(axis=1)])
+    if magnitudes is not None:
+        bad = np.setdiff1d(bad, np.asarray(magnitudes[2], dtype=np.int64))
+    if bad.size:
+        dump_mismatch(f"maxsim_{tag}".replace("/", "_"), grp=grp, wg=wg, cnt=cnt, wc=wc, ml=ml, wml=wml, s64=s64, ws=ws, md=md,
+                      wmd=wmd)
+        i = int(bad[0])
+        raise AssertionError(f"{tag}: {bad.size} queries differ in groups / counts / match labels (first {i}: got "
+                             f"{grp[i].tolist()} ({cnt[i]}) want {wg[i].tolist()} ({wc[i]})); match labels equal: "
+                             f"{np.array_equal(ml, wml)}")
+    if magnitudes is None:
+        fin = np.isfinite(ws)
+        assert np.array_equal(np.isfinite(s64), fin) and np.array_equal(np.isfinite(s32), fin), f"{tag}: padding differs"
+        assert np.array_equal(np.isfinite(md), np.isfinite(wmd)), f"{tag}: match padding differs"
+        if fin.any():
+            err = float((np.abs(s64[fin] - ws[fin]) / np.maximum(1.0, np.abs(ws[fin]))).max())
+            print(f"{tag}: max |score64 - oracle| / max(1, |s|) = {err:.3e}")
+            assert err <= SCORE_ATOL, f"{tag}: score error {err}"
+    else:
+        from tests.magnitude_helpers import assert_family_fp64
+
+        pad = grp == ABSENT
+        assert np.array_equal(pad, np.arange(k)[None, :] >= cnt[:, None]), f"{tag}: the padded groups are not the tail"
+        assert np.isposinf(s64[pad]).all() and np.isposinf(s32[pad]).all(), f"{tag}: padding scores are not +inf"
+        assert np.isfinite(s64[~pad]).all(), f"{tag}: an fp64 score of finite inputs is not finite"
+        assert np.array_equal(ml < 0, pad[tok_query]), f"{tag}: match padding differs from the groups'"
+        assert_family_fp64(md, None, toks, magnitudes[0], ml, magnitudes[1], tag)
+    with np.errstate(over="ignore"):
+        rounded = s64.astype(np.float32)
+    assert np.array_equal(s32.view(np.int32), rounded.view(np.int32)), f"{tag}: fp32 is not the rounded fp64"
     p64, _ = eng.pair_distances(toks, ml)
     assert np.array_equal(p64.view(np.int64), md.view(np.int64)), f"{tag}: match distances differ from pair_distances"
     assert np.array_equal(_seq_sum(md, off, k).view(np.int64), s64.view(np.int64)), f"{tag}: score64 is not the sequential sum"

@@ -8,62 +8,16 @@ strategy_used / bound_dtype / fallback_queries goes to the file MLVDB_ROUTE_LOG 
 forced-filter call on an index inside the filter path's magnitude window must still report the filter route (record).  A
 call the library serves by its exact scan or fallback passes as long as the answer is the oracle's.
 """
-import json
-import os
-
 import numpy as np
 import pytest
 
-from mlvectordb_amd.engine import HipScanEngine
 from tests import magnitude_helpers as mh
 from tests.helpers import assert_range_matches
 
 pytestmark = pytest.mark.gpu
 
 STRATEGIES = ("exact", "filter")
-
-
-def open_engine(rows, space, strategy, deleted=None):
-    eng = HipScanEngine(rows.shape[1], space, device=0, strategy=strategy)
-    try:
-        for part in np.array_split(rows, [rows.shape[0] * 5 // 8 + 3]):  # two pieces, the first ends inside a panel
-            eng.append(part)
-        if deleted is not None and deleted.any():
-            assert eng.tombstone(np.nonzero(deleted)[0]) == int(deleted.sum())
-        eng.last_stats()
-    except Exception:
-        eng.close()
-        raise
-    return eng
-
-
-def record(eng, tag: str, rows, strategy: str, qs=None) -> dict:
-    """The route of the call just made, kept in the route log.  A forced-filter call on an index inside the filter path's
-    magnitude window (magnitude_helpers.inside_filter_window) must report the filter route: the code before the magnitude
-    fixes reported it for every such call of this file, and nothing about those indexes calls for the exact scan.  (The
-    window is the fix's own: the issue asked for the assertion wherever the filter route was reported before, and three
-    families that were answered correctly on it -- uniform l2 at 2**-100, ip at 2**100 and 2**124 where right, cosine at 2**124
-    with d = 64 and 100 -- lie outside the window, run the exact scan now and carry no route assertion.)  Outside the window the
-    route is free.  Inside it the exact fallback is held too (``qs``: the call's queries): none for a batch of queries the
-    filter serves, at least the queries magnitude_helpers.queries_leaving_window names otherwise -- so the filter route
-    cannot quietly become the exact scan."""
-    st = eng.last_stats()
-    path = os.environ.get("MLVDB_ROUTE_LOG")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps({"tag": tag, "strategy_used": st["strategy_used"], "bound_dtype": st["bound_dtype"],
-                                "fallback_queries": st["fallback_queries"]}) + "\n")
-    if strategy == "filter" and mh.inside_filter_window(rows, eng.space):
-        assert st["strategy_used"] == 2, f"{tag}: the forced filter strategy was served by route {st['strategy_used']}"
-        if qs is not None:
-            leaving = int(mh.queries_leaving_window(qs, rows, eng.space).sum())
-            if leaving == 0:
-                assert st["fallback_queries"] == 0, f"{tag}: {st['fallback_queries']} queries fell back to the exact scan"
-            else:  # (a range call may run twice: the statistics accumulate)
-                assert st["fallback_queries"] >= leaving, f"{tag}: {st['fallback_queries']} fallbacks, {leaving} queries leave the window"
-    if strategy == "exact":
-        assert st["strategy_used"] == 1, f"{tag}: the forced exact strategy was served by route {st['strategy_used']}"
-    return st
+open_engine, record = mh.open_engine, mh.record  # (shared with tests/test_gpu_magnitudes_families.py)
 
 
 # ---------------------------------------------------------------- 1. uniform scale
