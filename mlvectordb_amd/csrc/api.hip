@@ -7,10 +7,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
 
+#include "device_memory.h"
 #include "internal.h"
 
 using namespace mlvdb;
@@ -19,88 +21,16 @@ namespace {
 
 thread_local std::string g_error;
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t need) {
-        if (need <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        size_t want = need + need / 4;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            want = need;
-            e = hipMalloc(&p, want);
-        }
-        if (e == hipSuccess) bytes = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <class T>
-    T* as() const {
-        return static_cast<T*>(p);
-    }
-};
-
-// Pinned host staging (grow only): a hipMemcpyAsync from / to pageable memory goes through the runtime's own staging with
-// a synchronisation per copy -- four small D2H copies and one 786 KB H2D copy cost a 256-query wave 0.33 ms on top of its
-// 2.0 ms of kernels (round 2: p50_ms_per_wave_host_io 2.349 vs 2.016 device-resident).
-struct PinBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t need) {
-        if (need <= bytes) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-        const size_t want = need + need / 4;
-        hipError_t e = hipHostMalloc(&p, want, 0);
-        if (e == hipSuccess) bytes = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-};
-
-// A bump carver over one block of several arrays, a DevBuf's or its copy on the host: take<T>(n) is the next n values of T.
-// It pads nothing.  Every layout carved with it lists its 8-byte fields (double, int64) before its 4-byte ones (float,
-// int32) -- descending alignment -- so every field lies aligned whatever the counts are.
-struct Carver {
-    char* at;
-    template <class T>
-    T* take(size_t n) {
-        T* first = reinterpret_cast<T*>(at);
-        at += n * sizeof(T);
-        return first;
-    }
-};
-
-// The layout most blocks have, [d64 | labels | dist | counts]: n entries and nq counts.
-struct ListBlock {
-    double* d64;
-    int64_t* lab;
-    float* dist;
-    int32_t* cnt;
-    static size_t bytes(size_t n, size_t nq) { return n * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + nq * sizeof(int32_t); }
-    ListBlock(void* block, size_t n, size_t nq) {
-        Carver c{static_cast<char*>(block)};
-        d64 = c.take<double>(n);
-        lab = c.take<int64_t>(n);
-        dist = c.take<float>(n);
-        cnt = c.take<int32_t>(nq);
-    }
-};
-
 }  // namespace
 
+// The blocks sized by the row capacity: they are allocated, regrown and compacted together (reserve_rows, mlvdb_index_compact).
+struct RowStore {
+    DevBuf X, rn, Xb, col[MLVDB_MAX_ATTRS];
+};
+
+// Every device or pinned block of an index is a DevBuf / PinBuf member (device_memory.h) and goes with the handle.  The raw
+// X / Xb / rn / attr_col[] / list_pool[] / host_flags pointers are views of such members for the kernels' arguments, set
+// where the owner is committed; with_row_mask points rn at the masked copy for the length of a call.
 struct mlvdb_index {
     int device = 0;
     int32_t dim = 0, ld = 0, space = 0;
@@ -115,6 +45,7 @@ struct mlvdb_index {
                           // int8 one serves every pass (1.25x instead of 1.75x the corpus in HBM); only an index whose rows
                           // quantise too badly for int8 bounds (l2 / ip, rmax8 > 0.03) converts the fp32 rows in registers
     float* rn = nullptr;  // row norms, NaN = tombstoned / not a row
+    RowStore rows;        // owns X, Xb, rn and attr_col[]
     int64_t capacity = 0, total = 0, deleted = 0;
     hipStream_t stream = nullptr;
     hipStream_t aux_stream = nullptr;  // mlvdb_index_get_rows_at: a hit-enrichment gather must not queue behind the next scan
@@ -148,6 +79,7 @@ struct mlvdb_index {
     // (garbage of overwritten lists included until mlvdb_index_compact repacks it); the block sums of a scan and the CSR of
     // a read-back
     int64_t* list_pool[MLVDB_MAX_ATTRS] = {};
+    DevBuf pool[MLVDB_MAX_ATTRS];  // owns list_pool[]
     int64_t list_cap[MLVDB_MAX_ATTRS] = {};
     int64_t list_used[MLVDB_MAX_ATTRS] = {};
     DevBuf list_sums, list_out;
@@ -196,6 +128,7 @@ struct mlvdb_index {
     bool flags_in_out = false;       // search_host: the deferred overflow flags travel behind the outputs (flags_out, device)
     uint32_t* flags_out = nullptr;
     uint32_t* host_flags = nullptr;  // pinned, kFilterQueries words
+    PinBuf flags_pin;                // owns host_flags
     bool deferred = false;           // search_host: the pass left its overflow flags in host_flags instead of launching the
     FilterArgs deferred_fa{};        //   exact fallback; its arguments, for the (rare) fallback after the sync
     int64_t host_fallbacks = 0;      // fallback queries decided on the host (added to the device-side count in the stats)
@@ -209,6 +142,16 @@ struct mlvdb_index {
     bool stats_pending = false;
     hipStream_t counters_stream = nullptr;  // stream of the last call that wrote the device counters
     bool counters_pending = false;
+    ~mlvdb_index() {  // (mlvdb_index_destroy has set the device and drained it; the memory members free themselves afterwards)
+        for (auto& p : scan_events) {
+            (void)hipEventDestroy(p.first);
+            (void)hipEventDestroy(p.second);
+        }
+        for (auto& ev : total_events)
+            if (ev) (void)hipEventDestroy(ev);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (aux_stream) (void)hipStreamDestroy(aux_stream);
+    }
 };
 
 namespace {
@@ -233,6 +176,27 @@ int fail(mlvdb_index* h, int code, const char* what, hipError_t e = hipSuccess) 
         if (e__ != hipSuccess)                                                              \
             return fail(h, e__ == hipErrorOutOfMemory ? MLVDB_ERR_OUT_OF_MEMORY : MLVDB_ERR_HIP, #call, e__); \
     } while (0)
+
+// One output array of a chunk: n values at dev -> out + at; a null `out` means the caller does not want that array.
+struct Down {
+    void* host;
+    const void* dev;
+    size_t bytes;
+    template <class T>
+    Down(T* out, size_t at, const T* dev, size_t n) : host(out ? out + at : nullptr), dev(dev), bytes(n * sizeof(T)) {}
+};
+
+// A chunk's outputs to the host: wait, copy each wanted array down, wait.
+int copy_down(mlvdb_index* h, hipStream_t s, std::initializer_list<Down> outs) {
+    // The first wait is measured, not caution: a D2H copy enqueued behind the kernels would park at the head of the copy
+    // queue until they end, and the copies of the index's other stream wait with it (search_host).  On a drained stream
+    // it does no device work.
+    HIP_TRY(h, hipStreamSynchronize(s));
+    for (const Down& o : outs)
+        if (o.host) HIP_TRY(h, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return MLVDB_OK;
+}
 
 // ---- tuning state: name table, the one environment read, KEY=VAL parsing
 struct TuningField {
@@ -274,41 +238,40 @@ int64_t attr_absent(int32_t type) { return type == MLVDB_ATTR_FLOAT64 ? (int64_t
 // "has a slot and a pool": list columns (mlvdb_list.h) and sparse vector columns (mlvdb_sparse.h), which share the storage
 bool pooled(int32_t type) { return type == MLVDB_ATTR_INT64_LIST || type == MLVDB_ATTR_SPARSE; }
 
-void attr_release(int64_t* (&cols)[MLVDB_MAX_ATTRS]) {
-    for (int64_t*& c : cols) {
-        if (c) (void)hipFree(c);
-        c = nullptr;
-    }
-}
-
-// ncol[a] = a fresh column of `cap` values for every defined attribute: rows [0, keep) copied from the current column
+// nb.col[a] = a fresh column of `cap` values for every defined attribute: rows [0, keep) copied from the current column
 // (old_of_new == nullptr: regrowth) or gathered through old_of_new (compaction), the rest absent.  Enqueued on h->stream;
-// the caller swaps them in (attr_commit) after the stream has drained, and releases them if anything else fails first.
-int attr_alloc(mlvdb_index* h, int64_t cap, int64_t keep, const int32_t* old_of_new, int64_t* (&ncol)[MLVDB_MAX_ATTRS]) {
-    for (int64_t*& c : ncol) c = nullptr;
+// the caller commits them with the rows (commit_rows) after the stream has drained.
+int attr_alloc(mlvdb_index* h, int64_t cap, int64_t keep, const int32_t* old_of_new, RowStore& nb) {
     for (int a = 0; a < MLVDB_MAX_ATTRS; ++a) {
         if (!h->attr_type[a] || cap == 0) continue;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&ncol[a]), (size_t)cap * sizeof(int64_t));
+        hipError_t e = nb.col[a].exact((size_t)cap * sizeof(int64_t));
+        int64_t* ncol = nb.col[a].as<int64_t>();
         const bool copy = keep > 0 && h->attr_col[a];
-        if (e == hipSuccess) e = launch_attr_fill(ncol[a], attr_absent(h->attr_type[a]), copy ? keep : 0, cap - (copy ? keep : 0), h->stream);
+        if (e == hipSuccess) e = launch_attr_fill(ncol, attr_absent(h->attr_type[a]), copy ? keep : 0, cap - (copy ? keep : 0), h->stream);
         if (e == hipSuccess && copy)
-            e = old_of_new ? launch_attr_gather(h->attr_col[a], ncol[a], old_of_new, keep, h->stream)
-                           : hipMemcpyAsync(ncol[a], h->attr_col[a], (size_t)keep * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream);
-        if (e != hipSuccess) {
-            attr_release(ncol);
+            e = old_of_new ? launch_attr_gather(h->attr_col[a], ncol, old_of_new, keep, h->stream)
+                           : hipMemcpyAsync(ncol, h->attr_col[a], (size_t)keep * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream);
+        if (e != hipSuccess)
             return fail(h, e == hipErrorOutOfMemory ? MLVDB_ERR_OUT_OF_MEMORY : MLVDB_ERR_HIP, "attribute columns", e);
-        }
     }
     return MLVDB_OK;
 }
 
-void attr_commit(mlvdb_index* h, int64_t* (&ncol)[MLVDB_MAX_ATTRS]) {
-    for (int a = 0; a < MLVDB_MAX_ATTRS; ++a) {
-        if (!h->attr_type[a]) continue;
-        if (h->attr_col[a]) (void)hipFree(h->attr_col[a]);
-        h->attr_col[a] = ncol[a];
-        ncol[a] = nullptr;
-    }
+// The new blocks of a capacity change become the index's (h->stream has drained): the old ones are freed, the views follow.
+void commit_rows(mlvdb_index* h, RowStore& nb, int64_t cap) {
+    h->rows = std::move(nb);
+    h->X = h->rows.X.as<float>();
+    h->rn = h->rows.rn.as<float>();
+    h->Xb = h->rows.Xb.p;
+    for (int a = 0; a < MLVDB_MAX_ATTRS; ++a) h->attr_col[a] = h->rows.col[a].as<int64_t>();
+    h->capacity = cap;
+}
+
+// ... and the new value pool of list attribute a (list_pool_reserve, list_repack).
+void commit_pool(mlvdb_index* h, int a, DevBuf& np, int64_t cap) {
+    h->pool[a] = std::move(np);
+    h->list_pool[a] = h->pool[a].as<int64_t>();
+    h->list_cap[a] = cap;
 }
 
 // ---- list columns (mlvdb_list.h): the value pools
@@ -317,19 +280,14 @@ int list_pool_reserve(mlvdb_index* h, int a, int64_t extra) {
     const int64_t need = h->list_used[a] + extra;
     if (need <= h->list_cap[a]) return MLVDB_OK;
     const int64_t cap = std::max<int64_t>({need, 2 * h->list_cap[a], 1024});
-    int64_t* np = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&np), (size_t)cap * sizeof(int64_t)));
+    Staged<DevBuf> np(h->stream);
+    HIP_TRY(h, np.exact((size_t)cap * sizeof(int64_t)));
     hipError_t e = hipSuccess;
     if (h->list_used[a] > 0)
-        e = hipMemcpyAsync(np, h->list_pool[a], (size_t)h->list_used[a] * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream);
+        e = hipMemcpyAsync(np.p, h->list_pool[a], (size_t)h->list_used[a] * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(np);
-        return fail(h, MLVDB_ERR_HIP, "list pool regrowth", e);
-    }
-    if (h->list_pool[a]) (void)hipFree(h->list_pool[a]);
-    h->list_pool[a] = np;
-    h->list_cap[a] = cap;
+    if (e != hipSuccess) return fail(h, MLVDB_ERR_HIP, "list pool regrowth", e);
+    commit_pool(h, a, np, cap);
     return MLVDB_OK;
 }
 
@@ -355,20 +313,14 @@ int list_repack(mlvdb_index* h, int a, int64_t rows) {
     hipStream_t s = h->stream;
     int64_t sum = 0;
     if (int rc = list_scan(h, h->attr_col[a], nullptr, rows, &sum)) return rc;
-    int64_t* np = nullptr;
-    if (sum > 0) {
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&np), (size_t)sum * sizeof(int64_t)));
-    }
-    hipError_t e = launch_list_move(h->attr_col[a], rows, h->list_sums.as<int64_t>(), h->list_pool[a], np, h->attr_col[a],
-                                    nullptr, nullptr, s);
+    Staged<DevBuf> np(s);
+    if (sum > 0) HIP_TRY(h, np.exact((size_t)sum * sizeof(int64_t)));
+    hipError_t e = launch_list_move(h->attr_col[a], rows, h->list_sums.as<int64_t>(), h->list_pool[a], np.as<int64_t>(),
+                                    h->attr_col[a], nullptr, nullptr, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        if (np) (void)hipFree(np);
-        return fail(h, MLVDB_ERR_HIP, "list pool repack", e);
-    }
-    if (h->list_pool[a]) (void)hipFree(h->list_pool[a]);
-    h->list_pool[a] = np;
-    h->list_cap[a] = h->list_used[a] = sum;
+    if (e != hipSuccess) return fail(h, MLVDB_ERR_HIP, "list pool repack", e);
+    commit_pool(h, a, np, sum);
+    h->list_used[a] = sum;
     return MLVDB_OK;
 }
 
@@ -416,24 +368,15 @@ int reserve_rows(mlvdb_index* h, int64_t rows) {
     int64_t want = rows;
     if (h->capacity > 0 && want < h->capacity + h->capacity / 2) want = h->capacity + h->capacity / 2;
     const int64_t cap = round_up_rows(want);
-    float* nX = nullptr;
-    float* nrn = nullptr;
-    void* nXb = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&nX), (size_t)cap * h->ld * sizeof(float)));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nrn), (size_t)cap * sizeof(float));
-    if (e == hipSuccess && h->shadow) e = hipMalloc(&nXb, (size_t)cap * h->ld * 2);
-    if (e != hipSuccess) {
-        (void)hipFree(nX);
-        if (nrn) (void)hipFree(nrn);
-        return fail(h, MLVDB_ERR_OUT_OF_MEMORY, "hipMalloc(row norms / bf16 shadow)", e);
-    }
-    int64_t* ncol[MLVDB_MAX_ATTRS];
-    if (int rc = attr_alloc(h, cap, h->total, nullptr, ncol)) {  // the attribute columns grow with the rows
-        (void)hipFree(nX);
-        (void)hipFree(nrn);
-        if (nXb) (void)hipFree(nXb);
-        return rc;
-    }
+    Staged<RowStore> nb(h->stream);
+    HIP_TRY(h, nb.X.exact((size_t)cap * h->ld * sizeof(float)));
+    hipError_t e = nb.rn.exact((size_t)cap * sizeof(float));
+    if (e == hipSuccess && h->shadow) e = nb.Xb.exact((size_t)cap * h->ld * 2);
+    if (e != hipSuccess) return fail(h, MLVDB_ERR_OUT_OF_MEMORY, "allocating the row norms / bf16 shadow", e);
+    float* nX = nb.X.as<float>();
+    float* nrn = nb.rn.as<float>();
+    void* nXb = nb.Xb.p;
+    if (int rc = attr_alloc(h, cap, h->total, nullptr, nb)) return rc;  // the attribute columns grow with the rows
     const size_t used_floats = (size_t)((h->total + 15) / 16) * 16 * h->ld;
     HIP_TRY(h, hipMemsetAsync(nX + used_floats, 0, ((size_t)cap * h->ld - used_floats) * sizeof(float), h->stream));
     HIP_TRY(h, hipMemsetAsync(nrn, 0xFF, (size_t)cap * sizeof(float), h->stream));  // 0xFFFFFFFF = NaN
@@ -448,14 +391,7 @@ int reserve_rows(mlvdb_index* h, int64_t rows) {
         HIP_TRY(h, hipMemcpyAsync(nrn, h->rn, (size_t)h->total * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    attr_commit(h, ncol);
-    if (h->X) (void)hipFree(h->X);
-    if (h->rn) (void)hipFree(h->rn);
-    if (h->Xb) (void)hipFree(h->Xb);
-    h->X = nX;
-    h->rn = nrn;
-    h->Xb = nXb;
-    h->capacity = cap;
+    commit_rows(h, nb, cap);
     return MLVDB_OK;
 }
 
@@ -591,8 +527,8 @@ int setup_filter_ws(mlvdb_index* h, FilterArgs& fa, int32_t q0, int32_t nq, bool
         HIP_TRY(h, h->wgbuf.ensure((size_t)kScanMaxGrid * kWgCap * sizeof(WgEntry)));
         HIP_TRY(h, h->wgcnt.ensure((size_t)kScanMaxGrid * 8 * sizeof(uint32_t)));
     }
-    if (!h->host_flags)
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->host_flags), kFilterQueries * sizeof(uint32_t), 0));
+    HIP_TRY(h, h->flags_pin.ensure(kFilterQueries * sizeof(uint32_t)));
+    h->host_flags = static_cast<uint32_t*>(h->flags_pin.p);
     fa.tn = &h->tn;
     fa.X = h->X;
     fa.Xb = h->Xb;
@@ -1301,14 +1237,14 @@ int mlvdb_index_create(int device, int32_t dim, int32_t space, int64_t capacity_
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = h->counters.ensure(64);
     if (e != hipSuccess) {
-        mlvdb_index_destroy(h);
-        return fail(nullptr, MLVDB_ERR_HIP, "hipMalloc(counters)", e);
+        delete h;
+        return fail(nullptr, MLVDB_ERR_HIP, "allocating the counters", e);
     }
     if (capacity_hint > 0) {
         rc = reserve_rows(h, capacity_hint);
         if (rc) {
             g_error = h->err;
-            mlvdb_index_destroy(h);
+            delete h;
             return rc;
         }
     }
@@ -1323,38 +1259,6 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)hipDeviceSynchronize();
-    if (h->X) (void)hipFree(h->X);
-    if (h->rn) (void)hipFree(h->rn);
-    if (h->Xb) (void)hipFree(h->Xb);
-    for (DevBuf* b : {&h->stage, &h->qpad, &h->qaux, &h->partial, &h->qsel, &h->seed_lab, &h->seed_dist, &h->seed_cnt,
-                      &h->seed_d64, &h->qimg, &h->fmisc, &h->cand, &h->rescr, &h->wgbuf, &h->wgcnt, &h->row_mask, &h->rn_masked, &h->qerr, &h->rowerr, &h->io_q, &h->io_lab, &h->io_dist, &h->io_cnt, &h->io_d64, &h->gather_out, &h->gather_lab, &h->cand_range, &h->rhits, &h->rhit_cnt, &h->rp8_masked, &h->x16, &h->s16, &h->rowerr16, &h->picks, &h->npicks, &h->x8, &h->rp8, &h->rowerr8, &h->qimg8, &h->sq8,
-                      &h->counters, &h->labels_in, &h->page_lab, &h->page_dist, &h->page_cnt, &h->page_d64, &h->cur_d,
-                      &h->cur_l})
-        b->release();
-    attr_release(h->attr_col);
-    attr_release(h->list_pool);
-    h->where_prog.release();
-    h->where_cnt.release();
-    for (DevBuf* b : {&h->each_prog, &h->each_bits, &h->each_seg, &h->each_tot, &h->each_lab, &h->each_tiles, &h->each_q,
-                      &h->each_qpad, &h->each_qaux, &h->each_out, &h->dist_q, &h->dist_list, &h->dist_out, &h->dist_sel,
-                      &h->grp_tab, &h->grp_tiles, &h->grp_out, &h->grp_lab,
-                      &h->mmr_q, &h->mmr_list, &h->mmr_out, &h->like_q, &h->like_ex, &h->like_list, &h->like_out,
-                      &h->ms_tab, &h->ms_rowdoc, &h->ms_best, &h->ms_misc, &h->ms_out,
-                      &h->facet_tab, &h->facet_misc, &h->order_ws, &h->mutate_ws, &h->list_sums, &h->list_out,
-                      &h->sparse_in, &h->sparse_out, &h->hyb_q, &h->hyb_list, &h->hyb_union, &h->hyb_out})
-        b->release();
-    if (h->host_flags) (void)hipHostFree(h->host_flags);
-    h->pin_in.release();
-    h->pin_out.release();
-    h->io_out.release();
-    for (auto& p : h->scan_events) {
-        (void)hipEventDestroy(p.first);
-        (void)hipEventDestroy(p.second);
-    }
-    for (auto& ev : h->total_events)
-        if (ev) (void)hipEventDestroy(ev);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
     delete h;
     return MLVDB_OK;
     });
@@ -1461,17 +1365,15 @@ int mlvdb_index_compact(mlvdb_index* h, int64_t* old_labels, int64_t capacity, i
     if ((int64_t)live != want) return fail(h, MLVDB_ERR_INTERNAL, "live-row count disagrees with the tombstone accounting");
     // new buffers sized for the live rows (zero / NaN filled), gather, swap
     const int64_t cap = round_up_rows(std::max<int64_t>(want, 1));
-    float* nX = nullptr;
-    float* nrn = nullptr;
-    void* nXb = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nX), (size_t)cap * h->ld * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&nrn), (size_t)cap * sizeof(float));
-    if (e == hipSuccess && h->Xb) e = hipMalloc(&nXb, (size_t)cap * h->ld * 2);
-    if (e != hipSuccess) {
-        if (nX) (void)hipFree(nX);
-        if (nrn) (void)hipFree(nrn);
-        return fail(h, MLVDB_ERR_OUT_OF_MEMORY, "hipMalloc(compaction buffers)", e);
-    }
+    std::vector<int32_t> host_map((size_t)want);  // (before nb: an abandoned call drains the stream's copy into it first)
+    Staged<RowStore> nb(s);
+    hipError_t e = nb.X.exact((size_t)cap * h->ld * sizeof(float));
+    if (e == hipSuccess) e = nb.rn.exact((size_t)cap * sizeof(float));
+    if (e == hipSuccess && h->Xb) e = nb.Xb.exact((size_t)cap * h->ld * 2);
+    if (e != hipSuccess) return fail(h, MLVDB_ERR_OUT_OF_MEMORY, "allocating the compaction buffers", e);
+    float* nX = nb.X.as<float>();
+    float* nrn = nb.rn.as<float>();
+    void* nXb = nb.Xb.p;
     HIP_TRY(h, hipMemsetAsync(nX, 0, (size_t)cap * h->ld * sizeof(float), s));
     HIP_TRY(h, hipMemsetAsync(nrn, 0xFF, (size_t)cap * sizeof(float), s));  // NaN = not a row
     if (nXb) HIP_TRY(h, hipMemsetAsync(nXb, 0, (size_t)cap * h->ld * 2, s));
@@ -1484,28 +1386,13 @@ int mlvdb_index_compact(mlvdb_index* h, int64_t* old_labels, int64_t capacity, i
     h->norm_min = old_min;
     HIP_TRY(h, launch_norm_range(nrn, want, h->rowerr.as<unsigned int>(), s));
     if (int rc2 = fetch_row_stats(h)) return rc2;
-    int64_t* ncol[MLVDB_MAX_ATTRS];
-    if (int rc2 = attr_alloc(h, cap, want, old_of_new, ncol)) {  // the attribute columns move with their rows
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(nX);
-        (void)hipFree(nrn);
-        if (nXb) (void)hipFree(nXb);
-        return rc2;
-    }
-    std::vector<int32_t> host_map((size_t)want);
+    if (int rc2 = attr_alloc(h, cap, want, old_of_new, nb)) return rc2;  // the attribute columns move with their rows
     if (want > 0)
         HIP_TRY(h, hipMemcpyAsync(host_map.data(), old_of_new, (size_t)want * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     commit_row_stats(h);
-    attr_commit(h, ncol);
     for (int64_t i = 0; i < want; ++i) old_labels[i] = host_map[(size_t)i];
-    (void)hipFree(h->X);
-    (void)hipFree(h->rn);
-    if (h->Xb) (void)hipFree(h->Xb);
-    h->X = nX;
-    h->rn = nrn;
-    h->Xb = nXb;
-    h->capacity = cap;
+    commit_rows(h, nb, cap);
     h->total = want;
     h->deleted = 0;
     h->i8_rows = 0;
@@ -2335,15 +2222,13 @@ int mlvdb_attr_define(mlvdb_index* h, int32_t attr, int32_t type) {
         return MLVDB_OK;
     }
     if (h->capacity > 0) {
-        int64_t* col = nullptr;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&col), (size_t)h->capacity * sizeof(int64_t)));
-        hipError_t e = launch_attr_fill(col, attr_absent(type), 0, h->capacity, h->stream);
+        Staged<DevBuf> col(h->stream);
+        HIP_TRY(h, col.exact((size_t)h->capacity * sizeof(int64_t)));
+        hipError_t e = launch_attr_fill(col.as<int64_t>(), attr_absent(type), 0, h->capacity, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(col);
-            return fail(h, MLVDB_ERR_HIP, "attribute column fill", e);
-        }
-        h->attr_col[attr] = col;
+        if (e != hipSuccess) return fail(h, MLVDB_ERR_HIP, "attribute column fill", e);
+        h->rows.col[attr] = std::move(col);
+        h->attr_col[attr] = h->rows.col[attr].as<int64_t>();
     }
     h->attr_type[attr] = type;
     return MLVDB_OK;
@@ -3066,9 +2951,7 @@ int distinct_chunk(mlvdb_index* h, const float* queries, int32_t n, int32_t k, i
         HIP_TRY(h, hipMemsetAsync(nflag_d, 0, sizeof(int32_t), s));
         HIP_TRY(h, launch_distinct_pick(l.lab, l.d64, l.cnt, n, L, group, k, k_eff, qsel_d, nflag_d, o_lab, o_dist, o_cnt,
                                         o_d64, o_grp, s));
-        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
-        HIP_TRY(h, hipMemcpyAsync(&nsel, nflag_d, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{&nsel, 0, nflag_d, 1}})) return rc;
         qsel = qsel_d;
         h->host_fallbacks += nsel;
     }
@@ -3119,13 +3002,9 @@ int distinct_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, i
         DistinctOut o{};
         if (int rc = distinct_chunk(h, queries + (size_t)q0 * h->dim, n, k, k_eff, group, L, o)) return rc;
         const size_t at = (size_t)q0 * k;
-        HIP_TRY(h, hipStreamSynchronize(s));
-        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o.d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_groups) HIP_TRY(h, hipMemcpyAsync(out_groups + at, o.grp, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_dist + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{out_dist64, at, o.d64, nk}, {out_groups, at, o.grp, nk}, {out_labels, at, o.lab, nk},
+                                      {out_dist, at, o.dist, nk}, {out_counts, (size_t)q0, o.cnt, (size_t)n}}))
+            return rc;
     }
     return MLVDB_OK;
 }
@@ -3205,9 +3084,7 @@ int grouped_members(mlvdb_index* h, int32_t n, int32_t k, int32_t gsz, int32_t q
         HIP_TRY(h, hipMemcpyAsync(keys_d, keys.data(), slots * sizeof(int64_t), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMemsetAsync(counts_d, 0, slots * sizeof(uint32_t), s));
         HIP_TRY(h, launch_grouped_count(h->rn, col, h->total, keys_d, slots, counts_d, s));
-        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
-        HIP_TRY(h, hipMemcpyAsync(counts.data(), counts_d, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{counts.data(), 0, counts_d, slots}})) return rc;
     }
     // prefix sum over the slots: list begins (the fill's cursors)
     std::vector<uint32_t> begin(slots, 0);
@@ -3308,18 +3185,13 @@ int grouped_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, in
         if (int rc = distinct_chunk(h, queries + (size_t)q0 * h->dim, n, k, k_eff, col, L, o)) return rc;
         grp.resize(nk);
         cnt.resize((size_t)n);
-        HIP_TRY(h, hipStreamSynchronize(s));
-        HIP_TRY(h, hipMemcpyAsync(grp.data(), o.grp, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(cnt.data(), o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{grp.data(), 0, o.grp, nk}, {cnt.data(), 0, o.cnt, (size_t)n}})) return rc;
         if (int rc = grouped_members(h, n, k, gsz, qt_max, col, grp.data(), cnt.data())) return rc;
         const ListBlock m(h->grp_out.p, ng, nk);  // [d64 | labels | dist | group counts], as grouped_members left it
         const size_t at = (size_t)q0 * k;
-        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at * gsz, m.d64, ng * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_labels + at * gsz, m.lab, ng * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_dist + at * gsz, m.dist, ng * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_gcnt + at, m.cnt, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{out_dist64, at * gsz, m.d64, ng}, {out_labels, at * gsz, m.lab, ng},
+                                      {out_dist, at * gsz, m.dist, ng}, {out_gcnt, at, m.cnt, nk}}))
+            return rc;
         if (out_groups) std::memcpy(out_groups + at, grp.data(), nk * sizeof(int64_t));
         std::memcpy(out_counts + q0, cnt.data(), (size_t)n * sizeof(int32_t));
     }
@@ -3394,14 +3266,10 @@ int mmr_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_
         HIP_TRY(h, launch_mmr_select(h->X, h->dim, h->ld, h->space, l.lab, l.dist, l.d64, l.cnt, n, fetch_k, k, lambda,
                                      one_minus_lambda, o_lab, o_dist, o_cnt, o_d64, o_rank, o_obj, s));
         const size_t at = (size_t)q0 * k;
-        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
-        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o_d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_objective) HIP_TRY(h, hipMemcpyAsync(out_objective + at, o_obj, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_rank) HIP_TRY(h, hipMemcpyAsync(out_rank + at, o_rank, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o_lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_dist + at, o_dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{out_dist64, at, o_d64, nk}, {out_objective, at, o_obj, nk}, {out_rank, at, o_rank, nk},
+                                      {out_labels, at, o_lab, nk}, {out_dist, at, o_dist, nk},
+                                      {out_counts, (size_t)q0, o_cnt, (size_t)n}}))
+            return rc;
     }
     return MLVDB_OK;
 }
@@ -3480,13 +3348,10 @@ int like_impl(mlvdb_index* h, const int64_t* ex_labels, const double* ex_weights
         if (int rc = search_device_impl(h, dq, n, fetch, l.lab, l.dist, l.cnt, l.d64, s, false)) return rc;
         HIP_TRY(h, launch_like_strip(l.lab, l.dist, l.d64, l.cnt, n, fetch, e_lab, e_off, exclude, k, o.lab, o.dist, o.cnt, o.d64, s));
         const size_t at = (size_t)q0 * k;
-        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
-        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o.d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_queries) HIP_TRY(h, hipMemcpyAsync(out_queries + (size_t)q0 * h->dim, dq, nd * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_dist + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{out_dist64, at, o.d64, nk}, {out_queries, (size_t)q0 * h->dim, dq, nd},
+                                      {out_labels, at, o.lab, nk}, {out_dist, at, o.dist, nk},
+                                      {out_counts, (size_t)q0, o.cnt, (size_t)n}}))
+            return rc;
     }
     return MLVDB_OK;
 }
@@ -3810,12 +3675,9 @@ int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t
         dense_out.resize(nk);
         cnt.resize((size_t)n);
         const size_t at = (size_t)q0 * k;
-        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
-        HIP_TRY(h, hipMemcpyAsync(dense_out.data(), o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(cnt.data(), o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_score + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (out_score64) HIP_TRY(h, hipMemcpyAsync(out_score64 + at, o.d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{dense_out.data(), 0, o.lab, nk}, {cnt.data(), 0, o.cnt, (size_t)n},
+                                      {out_score, at, o.dist, nk}, {out_score64, at, o.d64, nk}}))
+            return rc;
         for (size_t i = 0; i < nk; ++i) out_groups[at + i] = dense_out[i] >= 0 ? codes[(size_t)dense_out[i]] : INT64_MIN;
         std::memcpy(out_counts + q0, cnt.data(), (size_t)n * sizeof(int32_t));
         // 5. the matches: the member stage (grouped_members) over at most 1024 tokens per call, group_size 1
@@ -3837,9 +3699,7 @@ int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t
             if (int rc = grouped_members(h, nt, k, 1, qt_max, col, grp.data(), tcnt.data())) return rc;
             const ListBlock m(h->grp_out.p, ntk, ntk);  // [d64 | labels | dist | group counts], as grouped_members left it
             const size_t mat = ((size_t)off[q0] + (size_t)t0) * k;
-            if (out_match_labels) HIP_TRY(h, hipMemcpyAsync(out_match_labels + mat, m.lab, ntk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            if (out_match_dist64) HIP_TRY(h, hipMemcpyAsync(out_match_dist64 + mat, m.d64, ntk * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipStreamSynchronize(s));
+            if (int rc = copy_down(h, s, {{out_match_labels, mat, m.lab, ntk}, {out_match_dist64, mat, m.d64, ntk}})) return rc;
         }
         q0 = q1;
     }
@@ -4424,12 +4284,8 @@ int sparse_pass(mlvdb_index* h, int32_t attr, const int64_t* off, const int32_t*
     const ListBlock o(h->sparse_out.p, nk, (size_t)n);
     if (int rc = sparse_pass_device(h, attr, off, terms, weights, q0, q1, k, mask, o)) return rc;
     const size_t at = (size_t)q0 * k;
-    HIP_TRY(h, hipMemcpyAsync(out_labels + at, o.lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(out_score + at, o.dist, nk * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o.cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (out_score64) HIP_TRY(h, hipMemcpyAsync(out_score64 + at, o.d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return MLVDB_OK;
+    return copy_down(h, s, {{out_labels, at, o.lab, nk}, {out_score, at, o.dist, nk}, {out_counts, (size_t)q0, o.cnt, (size_t)n},
+                            {out_score64, at, o.d64, nk}});
 }
 }  // namespace
 }  // extern "C++"
@@ -4627,15 +4483,11 @@ int hybrid_impl(mlvdb_index* h, const float* queries, int32_t attr, const int64_
                                       out_dist64 ? o_d64 : nullptr, out_sparse64 ? o_s64 : nullptr,
                                       out_rank_dense ? o_rd : nullptr, out_rank_sparse ? o_rs : nullptr, s));
         const size_t at = (size_t)q0 * k;
-        HIP_TRY(h, hipStreamSynchronize(s));  // (a D2H copy enqueued behind the kernels would park in the copy queue)
-        HIP_TRY(h, hipMemcpyAsync(out_labels + at, o_lab, nk * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_fused + at, o_fused, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(out_counts + q0, o_cnt, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (out_dist64) HIP_TRY(h, hipMemcpyAsync(out_dist64 + at, o_d64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_sparse64) HIP_TRY(h, hipMemcpyAsync(out_sparse64 + at, o_s64, nk * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (out_rank_dense) HIP_TRY(h, hipMemcpyAsync(out_rank_dense + at, o_rd, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (out_rank_sparse) HIP_TRY(h, hipMemcpyAsync(out_rank_sparse + at, o_rs, nk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
+        if (int rc = copy_down(h, s, {{out_labels, at, o_lab, nk}, {out_fused, at, o_fused, nk},
+                                      {out_counts, (size_t)q0, o_cnt, (size_t)n}, {out_dist64, at, o_d64, nk},
+                                      {out_sparse64, at, o_s64, nk}, {out_rank_dense, at, o_rd, nk},
+                                      {out_rank_sparse, at, o_rs, nk}}))
+            return rc;
     }
     return MLVDB_OK;
 }

@@ -147,3 +147,16 @@ def test_the_search_path_never_reads_the_environment():
     text = (csrc / "api.hip").read_text()
     body = text[text.index("Tuning tuning_from_env()"):text.index("const TuningField* find_tuning_field")]
     assert body.count("getenv(") == sum(uses.values())
+
+
+def test_device_memory_is_allocated_and_freed_by_its_owners_only():
+    """Nobody frees by hand: the four allocator calls occur in device_memory.h alone (DevBuf / PinBuf), the handle's blocks go
+    with `delete h`, and no list of buffer names exists that a new family could forget to extend."""
+    csrc = ROOT / "mlvectordb_amd" / "csrc"
+    calls = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\(")
+    users = {p.name for p in list(csrc.glob("*.hip")) + list(csrc.glob("*.h")) if calls.search(p.read_text())}
+    assert users == {"device_memory.h"}, users
+    text = (csrc / "api.hip").read_text()
+    destroy = re.search(r"^int mlvdb_index_destroy\([^)]*\) \{\n(.*?)^\}", text, flags=re.S | re.M).group(1)
+    assert "release(" not in destroy and "hipFree" not in destroy and "delete h;" in destroy
+    assert "attr_release" not in text

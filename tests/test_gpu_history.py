@@ -56,6 +56,25 @@ def test_wide_history_equals_the_model_at_every_step(key):
     _replay(key, lambda: HipScanEngine(d, space, device=0))
 
 
+def test_an_index_outlives_a_destroyed_neighbour_that_used_every_workspace():
+    """Engine B is opened first; engine A replays the first wide history -- every family's workspace, regrown rows, columns and
+    pools -- and is closed, which frees all of it; then B replays the second one and equals the model at every step.  Answers
+    only: the card is shared, so its free memory is not ours to assert on."""
+    key_a, key_b = H.WIDE[0], H.WIDE[1]
+    ops_a, expected_a = H.make_history(*key_a)
+    ops_b, expected_b = H.make_history(*key_b)
+    b = HipScanEngine(key_b[2], key_b[1], device=0)
+    try:
+        a = HipScanEngine(key_a[2], key_a[1], device=0)
+        try:
+            assert H.run_history(a, ops_a, expected_a, "neighbour_" + H.history_tag(*key_a))["steps"] == len(ops_a)
+        finally:
+            a.close()
+        assert H.run_history(b, ops_b, expected_b, "survivor_" + H.history_tag(*key_b))["steps"] == len(ops_b)
+    finally:
+        b.close()
+
+
 @pytest.mark.parametrize("key", H.WIDE_LARGE, ids=lambda key: H.history_tag(*key))
 def test_wide_large_history_moves_the_inner_searches_between_the_routes(key):
     """Past 32,768 rows `auto` itself takes the filter route inside search_mmr / search_like / search_grouped and the tag-filtered

@@ -234,7 +234,10 @@ def test_the_source_shows_every_validation_before_the_first_launch():
     text = (ROOT / "mlvectordb_amd" / "csrc" / "api.hip").read_text()
     impl = re.search(r"^int mmr_impl\(.*?^\}", text, flags=re.S | re.M).group(0)
     assert "hipLaunchKernelGGL" not in body and "<<<" not in body
-    assert impl.index("search_device_impl(") < impl.index("launch_mmr_select(") < impl.index("hipMemcpyDeviceToHost")
+    assert impl.index("search_device_impl(") < impl.index("launch_mmr_select(") < impl.index("copy_down(")
+    down = re.search(r"^int copy_down\(.*?^\}", text, flags=re.S | re.M).group(0)  # wait, copy each output down, wait
+    assert down.index("hipStreamSynchronize") < down.index("hipMemcpyDeviceToHost")
+    assert down.rindex("hipMemcpyDeviceToHost") < down.rindex("hipStreamSynchronize")
     assert "const double one_minus_lambda = 1.0 - lambda;" in impl  # formed once, on the host
 
 
