@@ -3,8 +3,9 @@
 * configs[1] shape (1M x 768): filter == exact fp64 scan, properties, and a 1M-row comparison with the NumPy
   oracle itself (32 queries).
 * configs[2] (10M x 768 cosine, batch 256, the headline): every one of the 256 queries, int8 body, three scan
-  rounds (the third only exists beyond 1,572,864 rows), ids and fp32 distances equal to the exact fp64 scan
-  (itself pinned against the oracle at small sizes in test_gpu_parity.py and at 1M rows here) AND, for 8 of the queries, to
+  rounds (the third only exists beyond 1,572,864 rows at the default round sizes; test_gpu_knn_limits.py runs all three on
+  6,200 rows), ids and fp32 distances equal to the exact fp64 scan (itself pinned against the oracle at small sizes, at the
+  limits of its kernels, in test_gpu_knn_limits.py, on seeded shapes in test_gpu_parity.py, and at 1M rows here) AND, for 8 of the queries, to
   the NumPy fp64 oracle over the whole 10M rows (chunk-wise scan + merge); planted near-copies; a 1024-query (four-pass) wave;
   again after tombstoning 10 % of the rows with default_rng(99).
 * configs[3] (10M x 768 squared-l2): kNN the same way, and the range query at the mean 10th-neighbour radius
