@@ -213,6 +213,16 @@ HYBRID_SIGNATURES = {
                                             _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# include/mlvdb_geo.h: geo attribute columns -- a location per row, radius / box filters, nearest by distance
+ATTR_GEO = 5
+ATTR_CODES["geo"] = ATTR_GEO
+WHERE_GEO_BOX = 16
+WHERE_GEO_RADIUS = 17
+GEO_SIGNATURES = {
+    "mlvdb_geo_nearest": (C.c_int, [_P, C.c_int32, C.c_int64, C.POINTER(Where), C.c_int64, C.c_int64, _P, _P, _P,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -244,7 +254,8 @@ def load() -> C.CDLL:
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
-                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **HYBRID_SIGNATURES}.items():
+                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **HYBRID_SIGNATURES,
+                                      **GEO_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -13,6 +13,7 @@
 #include <new>
 
 #include "device_memory.h"
+#include "geo_common.h"
 #include "internal.h"
 
 using namespace mlvdb;
@@ -2098,6 +2099,24 @@ int scalar_check(mlvdb_index* h, int32_t attr) {
     return MLVDB_OK;
 }
 
+// ... for the entries that rank, bin or group by a column's values: a geo column's packed points (mlvdb_geo.h) are stored as
+// int64 but are no integers to order or count by.
+int value_check(mlvdb_index* h, int32_t attr) {
+    if (h->attr_type[attr] == MLVDB_ATTR_GEO)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a geo column: this entry needs an int64 or float64 value column (see mlvdb_geo.h)");
+    return MLVDB_OK;
+}
+
+// Values about to be written to a column: on a geo column every non-absent one must be a point inside the ranges.
+int geo_values_check(mlvdb_index* h, int32_t attr, const void* values, int64_t n) {
+    if (h->attr_type[attr] != MLVDB_ATTR_GEO) return MLVDB_OK;
+    const int64_t* v = static_cast<const int64_t*>(values);
+    for (int64_t i = 0; i < n; ++i)
+        if (v[i] != INT64_MIN && !geo_valid(v[i]))
+            return fail(h, MLVDB_ERR_INVALID_ARG, "a geo value outside lat_e7 in [-9e8, 9e8], lon_e7 in [-18e8, 18e8]");
+    return MLVDB_OK;
+}
+
 // Host validation of a program (stack depth >= 1 throughout and exactly 1 at the end, defined attributes, ops valid for their
 // column's type, set ranges inside the table and sorted) -> h->where_ops, the form the kernel reads.  Nothing is launched for a
 // program refused here.
@@ -2130,6 +2149,8 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
                 d.col = h->attr_col[o.attr];
                 if (d.type == MLVDB_ATTR_INT64_LIST && o.op != MLVDB_WHERE_EXISTS)
                     return fail(h, MLVDB_ERR_INVALID_ARG, "a list column takes HAS, HAS_ANY, HAS_ALL, LEN and EXISTS only");
+                if (d.type == MLVDB_ATTR_GEO && o.op != MLVDB_WHERE_EXISTS)
+                    return fail(h, MLVDB_ERR_INVALID_ARG, "a geo column takes GEO_RADIUS, GEO_BOX and EXISTS only");
                 if (d.type == MLVDB_ATTR_SPARSE) {
                     if (o.op != MLVDB_WHERE_EXISTS) return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse column takes EXISTS and LEN only");
                     d.type = MLVDB_ATTR_INT64_LIST;  // the same slot: the evaluators see a list column
@@ -2165,6 +2186,25 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
                         return fail(h, MLVDB_ERR_INVALID_ARG, all ? "HAS_ALL: set range not strictly ascending"
                                                                   : "HAS_ANY: set range not sorted ascending");
                 d.a = (o.a << 32) | o.b;
+                break;
+            }
+            case MLVDB_WHERE_GEO_BOX: case MLVDB_WHERE_GEO_RADIUS: {
+                if (int rc = attr_check(h, o.attr)) return rc;
+                d.type = h->attr_type[o.attr];
+                d.col = h->attr_col[o.attr];
+                if (d.type != MLVDB_ATTR_GEO) return fail(h, MLVDB_ERR_INVALID_ARG, "GEO_RADIUS and GEO_BOX need a geo column");
+                if (!geo_valid(o.a))
+                    return fail(h, MLVDB_ERR_INVALID_ARG, "GEO_RADIUS / GEO_BOX: a is not a point (lat_e7, lon_e7 out of range)");
+                if (o.op == MLVDB_WHERE_GEO_BOX) {
+                    if (!geo_valid(o.b)) return fail(h, MLVDB_ERR_INVALID_ARG, "GEO_BOX: b is not a point (lat_e7, lon_e7 out of range)");
+                    if (geo_lat(o.a) > geo_lat(o.b))
+                        return fail(h, MLVDB_ERR_INVALID_ARG, "GEO_BOX: the south-west corner lies north of the north-east one");
+                } else {
+                    double thr;
+                    std::memcpy(&thr, &o.b, sizeof thr);
+                    if (!(thr >= 0.0 && thr <= 1.0))  // (NaN fails both)
+                        return fail(h, MLVDB_ERR_INVALID_ARG, "GEO_RADIUS: the threshold sin^2(r / 2R) must be in [0, 1]");
+                }
                 break;
             }
             default:
@@ -2215,7 +2255,7 @@ int mlvdb_attr_define(mlvdb_index* h, int32_t attr, int32_t type) {
     int rc = check_handle(h);
     if (rc) return rc;
     if (attr < 0 || attr >= MLVDB_MAX_ATTRS) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute index out of range");
-    if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64 && !pooled(type))
+    if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64 && type != MLVDB_ATTR_GEO && !pooled(type))
         return fail(h, MLVDB_ERR_INVALID_ARG, "unknown attribute type");
     if (h->attr_type[attr]) {
         if (h->attr_type[attr] != type) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute already defined with another type");
@@ -2244,6 +2284,7 @@ int mlvdb_attr_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const
     if (first < 0 || n < 0 || first > h->total || n > h->total - first || (n > 0 && !values))
         return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
     if (n == 0) return MLVDB_OK;
+    if ((rc = geo_values_check(h, attr, values, n))) return rc;
     // (the sentinels are values like any other here: INT64_MIN / NaN written to a row make it absent)
     HIP_TRY(h, hipMemcpyAsync(h->attr_col[attr] + first, values, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -3019,6 +3060,7 @@ int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq
     if (rc) return rc;
     // everything is checked before anything is launched (the program: with_where)
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = value_check(h, attr))) return rc;
     if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "distinct needs an int64 column");
     if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
     if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
@@ -3208,6 +3250,7 @@ int mlvdb_search_batch_grouped(mlvdb_index* h, const float* queries, int64_t nq,
     if (rc) return rc;
     // everything is checked before anything is launched (the program: with_where)
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = value_check(h, attr))) return rc;
     if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "grouped needs an int64 column");
     if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
     if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
@@ -3514,6 +3557,7 @@ int mlvdb_facet_values(mlvdb_index* h, int32_t attr, const mlvdb_where* where, i
     if (rc) return rc;
     // everything is checked before anything is launched
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = value_check(h, attr))) return rc;
     if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "value facets need an int64 column");
     if (max_values < 1 || max_values > MLVDB_FACET_MAX_VALUES)
         return fail(h, MLVDB_ERR_INVALID_ARG, "max_values must be in 1..MLVDB_FACET_MAX_VALUES");
@@ -3533,6 +3577,7 @@ int mlvdb_facet_bins(mlvdb_index* h, int32_t attr, const mlvdb_where* where, con
     // everything is checked before anything is launched
     if ((rc = attr_check(h, attr))) return rc;
     if ((rc = scalar_check(h, attr))) return rc;
+    if ((rc = value_check(h, attr))) return rc;
     if (n_edges < 1 || n_edges > MLVDB_FACET_MAX_EDGES)
         return fail(h, MLVDB_ERR_INVALID_ARG, "n_edges must be in 1..MLVDB_FACET_MAX_EDGES");
     if (!edges || !out_counts || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
@@ -3716,6 +3761,7 @@ int mlvdb_search_batch_maxsim(mlvdb_index* h, const float* tokens, const int64_t
     if (rc) return rc;
     // everything is checked on the host before anything is launched (the program: with_where)
     if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = value_check(h, attr))) return rc;
     if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "maxsim needs an int64 column");
     if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
     if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
@@ -3746,33 +3792,35 @@ namespace {
 // The whole chain is enqueued at once: the kernels hand their state to each other on the device (OrderState), and the digit
 // passes behind a finished selection return at once.  A program is evaluated once into the row mask (where_run), which every
 // pass then reads at one byte per row instead of the norms and the program's columns.
-int where_ordered_impl(mlvdb_index* h, int32_t attr, int32_t descending, const mlvdb_where* where, int64_t offset,
-                       int64_t limit, int64_t* out_labels, void* out_values, int64_t* n_out, int64_t* matched,
-                       int64_t* absent) {
+// A geo column (mlvdb_geo_nearest): the key is hav from `centre`, and the rows' distances come back in out_dist.
+int where_ordered_impl(mlvdb_index* h, int32_t attr, int32_t descending, int64_t centre, const mlvdb_where* where,
+                       int64_t offset, int64_t limit, int64_t* out_labels, void* out_values, double* out_dist, int64_t* n_out,
+                       int64_t* matched, int64_t* absent) {
     hipStream_t s = h->stream;
     if (where)
         if (int rc = where_run(h, where, nullptr)) return rc;
-    // [state | histograms of the passes | keys | out labels | out values | labels]
+    // [state | histograms of the passes | keys | out labels | out values | out distances | labels]
     constexpr size_t kStateBytes = (sizeof(OrderState) + 63) / 64 * 64;
     constexpr size_t kHistBytes = (size_t)kOrderPasses * kOrderBins * sizeof(unsigned long long);
-    HIP_TRY(h, h->order_ws.ensure(kStateBytes + kHistBytes + (size_t)kOrderMaxRows * (3 * sizeof(int64_t) + sizeof(uint32_t))));
+    HIP_TRY(h, h->order_ws.ensure(kStateBytes + kHistBytes + (size_t)kOrderMaxRows * (4 * sizeof(int64_t) + sizeof(uint32_t))));
     OrderState* st = h->order_ws.as<OrderState>();
     unsigned long long* hist = reinterpret_cast<unsigned long long*>(h->order_ws.as<char>() + kStateBytes);
     unsigned long long* keys = hist + (size_t)kOrderPasses * kOrderBins;
     int64_t* labels_d = reinterpret_cast<int64_t*>(keys + kOrderMaxRows);
     int64_t* values_d = labels_d + kOrderMaxRows;
-    uint32_t* clabels = reinterpret_cast<uint32_t*>(values_d + kOrderMaxRows);
+    double* dist_d = reinterpret_cast<double*>(values_d + kOrderMaxRows);
+    uint32_t* clabels = reinterpret_cast<uint32_t*>(dist_d + kOrderMaxRows);
     const uint8_t* mask = where ? h->row_mask.as<uint8_t>() : nullptr;
     const int64_t* col = h->attr_col[attr];
     const int32_t type = h->attr_type[attr];
     HIP_TRY(h, hipMemsetAsync(st, 0, kStateBytes + kHistBytes, s));
     for (int32_t pass = 0; pass < kOrderPasses; ++pass) {
         unsigned long long* hp = hist + (size_t)pass * kOrderBins;
-        HIP_TRY(h, launch_order_hist(mask, h->rn, col, type, descending, h->total, pass, hp, st, s));
+        HIP_TRY(h, launch_order_hist(mask, h->rn, col, type, descending, centre, h->total, pass, hp, st, s));
         HIP_TRY(h, launch_order_scan(hp, pass, offset, limit, st, s));
     }
-    HIP_TRY(h, launch_order_collect(mask, h->rn, col, type, descending, h->total, st, keys, clabels, s));
-    HIP_TRY(h, launch_order_sort(keys, clabels, col, h->total, offset, st, labels_d, values_d, s));
+    HIP_TRY(h, launch_order_collect(mask, h->rn, col, type, descending, centre, h->total, st, keys, clabels, s));
+    HIP_TRY(h, launch_order_sort(keys, clabels, col, type, centre, h->total, offset, st, labels_d, values_d, dist_d, s));
     OrderState host{};
     HIP_TRY(h, hipMemcpyAsync(&host, st, sizeof host, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
@@ -3787,6 +3835,7 @@ int where_ordered_impl(mlvdb_index* h, int32_t attr, int32_t descending, const m
     if (n == 0) return MLVDB_OK;
     HIP_TRY(h, hipMemcpyAsync(out_labels, labels_d, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(out_values, values_d, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (out_dist) HIP_TRY(h, hipMemcpyAsync(out_dist, dist_d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     return MLVDB_OK;
 }
@@ -3802,13 +3851,37 @@ int mlvdb_where_ordered(mlvdb_index* h, int32_t attr, int32_t descending, const 
     // everything is checked before anything is launched
     if ((rc = attr_check(h, attr))) return rc;
     if ((rc = scalar_check(h, attr))) return rc;
+    if ((rc = value_check(h, attr))) return rc;
     if (offset < 0 || limit < 1 || limit > MLVDB_ORDER_MAX_ROWS || offset > MLVDB_ORDER_MAX_ROWS - limit)
         return fail(h, MLVDB_ERR_INVALID_ARG, "offset >= 0, limit >= 1 and offset + limit <= MLVDB_ORDER_MAX_ROWS");
     if (!out_labels || !out_values || !n_out || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     if (where && (rc = where_prepare(h, where))) return rc;
     *n_out = *matched = *absent = 0;
     if (h->total == 0) return MLVDB_OK;
-    return where_ordered_impl(h, attr, descending != 0, where, offset, limit, out_labels, out_values, n_out, matched, absent);
+    return where_ordered_impl(h, attr, descending != 0, 0, where, offset, limit, out_labels, out_values, nullptr, n_out, matched,
+                              absent);
+    });
+}
+
+// ---- nearest by distance on a geo column (mlvdb_geo.h): the ordered chain with hav from the centre as the key
+int mlvdb_geo_nearest(mlvdb_index* h, int32_t attr, int64_t center, const mlvdb_where* where, int64_t offset, int64_t limit,
+                      int64_t* out_labels, int64_t* out_points, double* out_dist_m, int64_t* n_out, int64_t* matched,
+                      int64_t* absent) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = attr_check(h, attr))) return rc;
+    if (h->attr_type[attr] != MLVDB_ATTR_GEO) return fail(h, MLVDB_ERR_INVALID_ARG, "geo_nearest needs a geo column");
+    if (!geo_valid(center)) return fail(h, MLVDB_ERR_INVALID_ARG, "geo_nearest: center is not a point (lat_e7, lon_e7 out of range)");
+    if (offset < 0 || limit < 1 || limit > MLVDB_ORDER_MAX_ROWS || offset > MLVDB_ORDER_MAX_ROWS - limit)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "offset >= 0, limit >= 1 and offset + limit <= MLVDB_ORDER_MAX_ROWS");
+    if (!out_labels || !out_points || !out_dist_m || !n_out || !matched || !absent)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (where && (rc = where_prepare(h, where))) return rc;
+    *n_out = *matched = *absent = 0;
+    if (h->total == 0) return MLVDB_OK;
+    return where_ordered_impl(h, attr, 0, center, where, offset, limit, out_labels, out_points, out_dist_m, n_out, matched, absent);
     });
 }
 
@@ -3847,6 +3920,10 @@ int update_sets_prepare(mlvdb_index* h, const mlvdb_assign* sets, int32_t n_sets
         if (seen[a.attr]) return fail(h, MLVDB_ERR_INVALID_ARG, "an attribute is assigned twice");
         seen[a.attr] = true;
         if (a.op != MLVDB_SET_ASSIGN && a.op != MLVDB_SET_ADD) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown assignment op");
+        if (h->attr_type[a.attr] == MLVDB_ATTR_GEO) {
+            if (a.op == MLVDB_SET_ADD) return fail(h, MLVDB_ERR_INVALID_ARG, "ADD on a geo column (ASSIGN a point, or INT64_MIN to clear)");
+            if (int rc = geo_values_check(h, a.attr, &a.a, 1)) return rc;
+        }
         if (a.op == MLVDB_SET_ADD) {
             *any_add = true;
             if (h->attr_type[a.attr] == MLVDB_ATTR_FLOAT64) {
@@ -3935,6 +4012,7 @@ int mlvdb_attr_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64
     if (sorted.front() < 0 || sorted.back() >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label outside [0, total)");
     if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
         return fail(h, MLVDB_ERR_INVALID_ARG, "a label appears twice");
+    if ((rc = geo_values_check(h, attr, values, n))) return rc;
     return attr_set_at_impl(h, attr, labels, n, values, updated);
     });
 }

@@ -23,6 +23,7 @@
 #include "../../include/mlvdb_list.h"
 #include "../../include/mlvdb_sparse.h"
 #include "../../include/mlvdb_hybrid.h"
+#include "../../include/mlvdb_geo.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -677,15 +678,20 @@ struct OrderState {
 // One digit pass: the candidates (live rows -- of `mask` when given, else with a finite norm -- with a present value) inside the
 // selected bucket counted by their digit into hist[kOrderBins]; pass 0 also counts matched / absent.  Nothing runs once
 // st->done is set.  Then the one-block scan: the digit that holds rank st->want, st updated.
+// type == MLVDB_ATTR_GEO (mlvdb_geo_nearest): the key is hav of the row's point from the packed point `centre`, ascending
 hipError_t launch_order_hist(const uint8_t* mask, const float* rn, const int64_t* col, int32_t type, int32_t descending,
-                             int64_t total, int32_t pass, unsigned long long* hist, OrderState* st, hipStream_t s);
+                             int64_t centre, int64_t total, int32_t pass, unsigned long long* hist, OrderState* st,
+                             hipStream_t s);
 hipError_t launch_order_scan(const unsigned long long* hist, int32_t pass, int64_t offset, int64_t limit, OrderState* st,
                              hipStream_t s);
 // The candidates at or below the selected bucket -> keys / labels[kOrderMaxRows] through st->cursor
 hipError_t launch_order_collect(const uint8_t* mask, const float* rn, const int64_t* col, int32_t type, int32_t descending,
-                                int64_t total, OrderState* st, unsigned long long* keys, uint32_t* labels, hipStream_t s);
+                                int64_t centre, int64_t total, OrderState* st, unsigned long long* keys, uint32_t* labels,
+                                hipStream_t s);
 // One workgroup sorts them and writes ranks [offset, st->want) to out_labels / out_values[kOrderMaxRows] (values: col[label])
-hipError_t launch_order_sort(const unsigned long long* keys, const uint32_t* labels, const int64_t* col, int64_t total,
-                             int64_t offset, OrderState* st, int64_t* out_labels, int64_t* out_values, hipStream_t s);
+// and, of a geo call, their distances in metres to out_dist[kOrderMaxRows] (otherwise not touched)
+hipError_t launch_order_sort(const unsigned long long* keys, const uint32_t* labels, const int64_t* col, int32_t type,
+                             int64_t centre, int64_t total, int64_t offset, OrderState* st, int64_t* out_labels,
+                             int64_t* out_values, double* out_dist, hipStream_t s);
 
 }  // namespace mlvdb

@@ -1,4 +1,6 @@
 // Ordered metadata queries (include/mlvdb_order.h): the rows of ranks [offset, offset + limit) by an attribute column.
+// mlvdb_geo_nearest (include/mlvdb_geo.h) is the same chain with another key source (kGeo): hav of the row's point from the
+// call's centre, as geo_common.h defines it, in place of the value.
 // Every candidate has a unique 96-bit composite key (order-preserving image of its value : label), so the N-th smallest
 // composite, N = min(offset + limit, candidates), bounds exactly N rows and ties need no second mechanism.  It is found by
 // most-significant-digit histogram passes (order_hist_kernel + the one-block order_scan_kernel per digit); the passes end as
@@ -9,6 +11,7 @@
 // uniform over the block so that every ballot sees whole waves), over at most kOrderMaxBlocks blocks.
 #include <algorithm>
 
+#include "geo_common.h"
 #include "internal.h"
 #include "wave_peel.h"
 
@@ -30,13 +33,31 @@ __device__ __forceinline__ unsigned long long order_key(int64_t raw, bool f64, b
     return descending ? ~u : u;
 }
 
-// row i: a candidate -> its key; hit = live and matching (whatever its value)
+// The centre of a geo call as every thread holds it (uniform): its halves and its cosine, computed once per thread.
+struct GeoCentre {
+    int32_t lat, lon;
+    double cos_lat;
+};
+template <bool kGeo>
+__device__ __forceinline__ GeoCentre geo_centre(int64_t centre) {
+    if constexpr (kGeo) return GeoCentre{geo_lat(centre), geo_lon(centre), geo_cos_lat(geo_lat(centre))};
+    return GeoCentre{0, 0, 0.0};
+}
+
+// row i: a candidate -> its key; hit = live and matching (whatever its value).  kGeo: the key is hav from `c` (ascending: the
+// bits of a double >= 0), and f64 / descending are not read.
+template <bool kGeo>
 __device__ __forceinline__ bool order_row(const uint8_t* __restrict__ mask, const float* __restrict__ rn,
-                                          const int64_t* __restrict__ col, bool f64, bool descending, int64_t i, int64_t total,
-                                          bool& hit, unsigned long long& key) {
+                                          const int64_t* __restrict__ col, bool f64, bool descending, const GeoCentre& c,
+                                          int64_t i, int64_t total, bool& hit, unsigned long long& key) {
     const bool in = i < total;
     hit = in && (mask ? mask[i] != 0 : rn[i] == rn[i]);  // (the mask of a program holds live rows only)
     const int64_t raw = hit ? col[i] : 0;
+    if constexpr (kGeo) {
+        const bool has = hit && raw != INT64_MIN;
+        key = has ? order_key(__double_as_longlong(geo_hav(raw, c.lat, c.lon, c.cos_lat)), true, false) : 0;
+        return has;
+    }
     const double dv = __longlong_as_double(raw);
     const bool has = hit && (f64 ? dv == dv : raw != INT64_MIN);
     key = order_key(raw, f64, descending);
@@ -66,10 +87,11 @@ __device__ __forceinline__ int order_side(unsigned long long key, uint32_t label
 
 }  // namespace
 
+template <bool kGeo>
 __global__ __launch_bounds__(256) void order_hist_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ rn,
                                                          const int64_t* __restrict__ col, int32_t f64, int32_t descending,
-                                                         int64_t total, int32_t pass, unsigned long long* __restrict__ hist,
-                                                         OrderState* __restrict__ st) {
+                                                         int64_t centre, int64_t total, int32_t pass,
+                                                         unsigned long long* __restrict__ hist, OrderState* __restrict__ st) {
     __shared__ uint32_t lh[kOrderBins];
     __shared__ unsigned long long block_matched, block_absent;
     if (st->done) return;  // (uniform: written by an earlier launch)
@@ -79,13 +101,14 @@ __global__ __launch_bounds__(256) void order_hist_kernel(const uint8_t* __restri
     if (threadIdx.x == 0) block_matched = block_absent = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
+    const GeoCentre c = geo_centre<kGeo>(centre);
     unsigned long long wave_matched = 0, wave_absent = 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < total; i0 += stride) {
         const int64_t i = i0 + threadIdx.x;
         bool hit;
         unsigned long long key;
-        const bool has = order_row(mask, rn, col, f64 != 0, descending != 0, i, total, hit, key);
+        const bool has = order_row<kGeo>(mask, rn, col, f64 != 0, descending != 0, c, i, total, hit, key);
         if (pass == 0) {
             const unsigned long long bh = __ballot(hit), ba = __ballot(hit && !has);
             if (lane == 0) {
@@ -108,11 +131,15 @@ __global__ __launch_bounds__(256) void order_hist_kernel(const uint8_t* __restri
 }
 
 hipError_t launch_order_hist(const uint8_t* mask, const float* rn, const int64_t* col, int32_t type, int32_t descending,
-                             int64_t total, int32_t pass, unsigned long long* hist, OrderState* st, hipStream_t s) {
+                             int64_t centre, int64_t total, int32_t pass, unsigned long long* hist, OrderState* st,
+                             hipStream_t s) {
     if (total == 0) return hipSuccess;
     const int64_t blocks = std::min<int64_t>((total + 255) / 256, kOrderMaxBlocks);
-    order_hist_kernel<<<(unsigned)blocks, 256, 0, s>>>(mask, rn, col, type == MLVDB_ATTR_FLOAT64, descending, total, pass, hist,
-                                                       st);
+    if (type == MLVDB_ATTR_GEO)
+        order_hist_kernel<true><<<(unsigned)blocks, 256, 0, s>>>(mask, rn, col, 0, 0, centre, total, pass, hist, st);
+    else
+        order_hist_kernel<false><<<(unsigned)blocks, 256, 0, s>>>(mask, rn, col, type == MLVDB_ATTR_FLOAT64, descending, 0, total,
+                                                                  pass, hist, st);
     return hipGetLastError();
 }
 
@@ -193,19 +220,21 @@ hipError_t launch_order_scan(const unsigned long long* hist, int32_t pass, int64
     return hipGetLastError();
 }
 
+template <bool kGeo>
 __global__ __launch_bounds__(256) void order_collect_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ rn,
                                                             const int64_t* __restrict__ col, int32_t f64, int32_t descending,
-                                                            int64_t total, OrderState* __restrict__ st,
+                                                            int64_t centre, int64_t total, OrderState* __restrict__ st,
                                                             unsigned long long* __restrict__ keys,
                                                             uint32_t* __restrict__ labels) {
     if (st->n_collect == 0) return;
     const unsigned long long bkey = st->key;
     const uint32_t blabel = st->label, low_bits = st->low_bits;
+    const GeoCentre c = geo_centre<kGeo>(centre);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         bool hit;
         unsigned long long key;
-        if (!order_row(mask, rn, col, f64 != 0, descending != 0, i, total, hit, key)) continue;
+        if (!order_row<kGeo>(mask, rn, col, f64 != 0, descending != 0, c, i, total, hit, key)) continue;
         if (order_side(key, (uint32_t)i, bkey, blabel, low_bits) > 0) continue;
         const uint32_t at = atomicAdd(&st->cursor, 1u);
         if (at < (uint32_t)kOrderMaxRows) {
@@ -218,20 +247,26 @@ __global__ __launch_bounds__(256) void order_collect_kernel(const uint8_t* __res
 }
 
 hipError_t launch_order_collect(const uint8_t* mask, const float* rn, const int64_t* col, int32_t type, int32_t descending,
-                                int64_t total, OrderState* st, unsigned long long* keys, uint32_t* labels, hipStream_t s) {
+                                int64_t centre, int64_t total, OrderState* st, unsigned long long* keys, uint32_t* labels,
+                                hipStream_t s) {
     if (total == 0) return hipSuccess;
     const int64_t blocks = std::min<int64_t>((total + 255) / 256, kOrderMaxBlocks);
-    order_collect_kernel<<<(unsigned)blocks, 256, 0, s>>>(mask, rn, col, type == MLVDB_ATTR_FLOAT64, descending, total, st, keys,
-                                                          labels);
+    if (type == MLVDB_ATTR_GEO)
+        order_collect_kernel<true><<<(unsigned)blocks, 256, 0, s>>>(mask, rn, col, 0, 0, centre, total, st, keys, labels);
+    else
+        order_collect_kernel<false><<<(unsigned)blocks, 256, 0, s>>>(mask, rn, col, type == MLVDB_ATTR_FLOAT64, descending, 0,
+                                                                     total, st, keys, labels);
     return hipGetLastError();
 }
 
 // Bitonic sort of the collected (key, label) pairs in LDS (48 KiB), padded to a power of two with pairs above every real one
-// (a real label is below 2^31), then ranks [offset, want) out.
+// (a real label is below 2^31), then ranks [offset, want) out.  kGeo: also the rows' distances in metres, from the same hav.
+template <bool kGeo>
 __global__ __launch_bounds__(1024) void order_sort_kernel(const unsigned long long* __restrict__ keys,
                                                           const uint32_t* __restrict__ labels, const int64_t* __restrict__ col,
-                                                          int64_t total, int64_t offset, OrderState* __restrict__ st,
-                                                          int64_t* __restrict__ out_labels, int64_t* __restrict__ out_values) {
+                                                          int64_t centre, int64_t total, int64_t offset,
+                                                          OrderState* __restrict__ st, int64_t* __restrict__ out_labels,
+                                                          int64_t* __restrict__ out_values, double* __restrict__ out_dist) {
     __shared__ unsigned long long sk[kOrderMaxRows];
     __shared__ uint32_t sl[kOrderMaxRows];
     const uint32_t n = st->cursor < (uint32_t)kOrderMaxRows ? st->cursor : (uint32_t)kOrderMaxRows;
@@ -261,18 +296,25 @@ __global__ __launch_bounds__(1024) void order_sort_kernel(const unsigned long lo
         }
     }
     const unsigned long long want = st->want < n ? st->want : n;
+    const GeoCentre c = geo_centre<kGeo>(centre);
     for (unsigned long long r = (unsigned long long)offset + threadIdx.x; r < want; r += blockDim.x) {
         const uint32_t label = sl[r];
         if ((int64_t)label >= total) continue;  // (never: a collected label is a row)
         out_labels[r - offset] = (int64_t)label;
-        out_values[r - offset] = col[label];  // the stored bits, not the key's image of them
+        const int64_t raw = col[label];
+        out_values[r - offset] = raw;  // the stored bits, not the key's image of them
+        if constexpr (kGeo) out_dist[r - offset] = geo_dist_m(geo_hav(raw, c.lat, c.lon, c.cos_lat));
     }
     if (threadIdx.x == 0) st->n_out = want > (unsigned long long)offset ? (uint32_t)(want - offset) : 0;
 }
 
-hipError_t launch_order_sort(const unsigned long long* keys, const uint32_t* labels, const int64_t* col, int64_t total,
-                             int64_t offset, OrderState* st, int64_t* out_labels, int64_t* out_values, hipStream_t s) {
-    order_sort_kernel<<<1, 1024, 0, s>>>(keys, labels, col, total, offset, st, out_labels, out_values);
+hipError_t launch_order_sort(const unsigned long long* keys, const uint32_t* labels, const int64_t* col, int32_t type,
+                             int64_t centre, int64_t total, int64_t offset, OrderState* st, int64_t* out_labels,
+                             int64_t* out_values, double* out_dist, hipStream_t s) {
+    if (type == MLVDB_ATTR_GEO)
+        order_sort_kernel<true><<<1, 1024, 0, s>>>(keys, labels, col, centre, total, offset, st, out_labels, out_values, out_dist);
+    else
+        order_sort_kernel<false><<<1, 1024, 0, s>>>(keys, labels, col, 0, total, offset, st, out_labels, out_values, nullptr);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "geo_common.h"
 #include "internal.h"
 
 namespace mlvdb {
@@ -84,6 +85,19 @@ __device__ __forceinline__ bool where_eval_with(const WhereOp* prog, int32_t n_o
                     }
                     // (both sides strictly ascending under HAS_ALL: every set value is found at most once)
                     bit = all ? (have && found == sn) : found > 0;
+                }
+            } else if ((o.type & 0xff) == MLVDB_ATTR_GEO) {
+                // raw is a packed point (include/mlvdb_geo.h); an absent row fails both ops, and computes nothing
+                const bool have = raw != INT64_MIN;
+                if (o.op == MLVDB_WHERE_EXISTS) {
+                    bit = have;
+                } else if (o.op == MLVDB_WHERE_GEO_BOX) {  // a = south-west, b = north-east; inclusive, in integers
+                    const int32_t lat = geo_lat(raw), lon = geo_lon(raw), w = geo_lon(o.a), e = geo_lon(o.b);
+                    const bool in_lon = w <= e ? (lon >= w && lon <= e) : (lon >= w || lon <= e);  // (else: across the antimeridian)
+                    bit = have && lat >= geo_lat(o.a) && lat <= geo_lat(o.b) && in_lon;
+                } else {  // GEO_RADIUS: a = the centre, b = the bits of sin^2(r / 2R)
+                    const int32_t lat_c = geo_lat(o.a);
+                    bit = have && geo_hav(raw, lat_c, geo_lon(o.a), geo_cos_lat(lat_c)) <= __longlong_as_double(o.b);
                 }
             } else {  // float64: absent = NaN, so every ordered comparison of an absent value is false by itself
                 const double v = __longlong_as_double(raw), a = __longlong_as_double(o.a);

@@ -236,7 +236,8 @@ class HipScanEngine:
     # -- metadata filters (include/mlvdb_where.h) ------------------------------------
     def define_attr(self, attr: int, kind: str) -> None:
         """Column ``attr`` (0..15) of type "int64" (absent = INT64_MIN), "float64" (absent = NaN), "int64_list" (a set of
-        int64 per row, include/mlvdb_list.h) or "sparse" (a sparse vector per row, include/mlvdb_sparse.h), every row absent."""
+        int64 per row, include/mlvdb_list.h), "sparse" (a sparse vector per row, include/mlvdb_sparse.h) or "geo" (a packed
+        location per row, stored as int64 with INT64_MIN absent, include/mlvdb_geo.h), every row absent."""
         code = _native.LIST_ATTR_CODES[kind] if kind in _native.LIST_ATTR_CODES else _native.ATTR_CODES[kind]
         self._check(self._lib.mlvdb_attr_define(self._h, int(attr), code), "attr_define")
         self._attr_kinds[int(attr)] = kind
@@ -783,6 +784,24 @@ class HipScanEngine:
             self._h, int(attr), 1 if descending else 0, None if w is None else C.byref(w), offset, limit,
             labels.ctypes.data, values.ctypes.data, C.byref(n), C.byref(matched), C.byref(absent)), "where_ordered")
         return labels[: n.value].copy(), values[: n.value].copy(), int(matched.value), int(absent.value)
+
+    # -- nearest by distance on a geo column (include/mlvdb_geo.h) ----------------------
+    def geo_nearest(self, attr: int, center: int, limit: int, where=None, offset: int = 0):
+        """Ranks ``[offset, offset + limit)`` of the live rows (those the compiled ``where.Program`` matches, when one is
+        given) that hold a point in geo column ``attr``, by great-circle distance from the packed point ``center`` and rows
+        at equal distance by ascending label: (labels int64 [n_out], points int64 [n_out] as stored, metres float64 [n_out],
+        matched, absent).  ``offset + limit <= _native.ORDER_MAX_ROWS``; a maximum distance is a ``$geo_radius`` in ``where``."""
+        limit, offset = int(limit), int(offset)
+        size = max(0, min(limit, _native.ORDER_MAX_ROWS))
+        labels = np.empty(size, dtype=np.int64)
+        points = np.empty(size, dtype=np.int64)
+        dist = np.empty(size, dtype=np.float64)
+        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        w, keep = self._where(where) if where is not None else (None, None)
+        self._check(self._lib.mlvdb_geo_nearest(
+            self._h, int(attr), int(center), None if w is None else C.byref(w), offset, limit, labels.ctypes.data,
+            points.ctypes.data, dist.ctypes.data, C.byref(n), C.byref(matched), C.byref(absent)), "geo_nearest")
+        return labels[: n.value].copy(), points[: n.value].copy(), dist[: n.value].copy(), int(matched.value), int(absent.value)
 
     def search64(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None, where=None):
         """kNN; ``mask`` (optional, one byte per row, non-zero = allowed) restricts the search to those rows, ``where``

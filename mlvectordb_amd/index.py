@@ -284,9 +284,9 @@ class Index:
         for name, kind in attributes.items():
             if not isinstance(name, str) or name.startswith("$"):
                 raise ValueError(f"attribute name {name!r}: a string not starting with '$'")
-            if kind not in _where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES:
+            if kind not in _where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES + _where.GEO_TYPES:
                 raise ValueError(f"attribute {name!r}: type {kind!r} is not one of "
-                                 f"{_where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES}")
+                                 f"{_where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES + _where.GEO_TYPES}")
         return attributes
 
     @property
@@ -374,6 +374,9 @@ class Index:
         if _where.is_sparse(self._attributes[name]):
             raise ValueError(f"{what}: attribute {name!r} is a sparse column; it needs a scalar attribute "
                              f"(a sparse vector is searched with search_sparse)")
+        if _where.is_geo(self._attributes[name]):
+            raise ValueError(f"{what}: attribute {name!r} is a geo column; it needs a scalar attribute (a location is "
+                             f"filtered with $geo_radius / $geo_box and ranked with nearest)")
 
     def _check_scalar(self, what: str, name: str) -> None:
         self._check_sparse(what, name)
@@ -1331,6 +1334,8 @@ class Index:
             if _where.is_sparse(kind):
                 raise ValueError(f"update_where: {name!r} is a sparse attribute: one vector for every matching row is not "
                                  f"supported, use update_attributes with ids")
+            if _where.is_geo(kind) and isinstance(v, Mapping) and "$inc" in v:
+                raise ValueError(f"update_where: {name!r} is a geo attribute: it takes a point or None, $inc adds to numbers")
             if _where.is_list(kind):  # one list for every matching row, or None: (column, "list", sorted codes or None)
                 if isinstance(v, Mapping):
                     raise ValueError(f"update_where: {name!r} is a {kind} attribute: it takes a list or None, no operator "
@@ -1338,7 +1343,7 @@ class Index:
                 col = _where.encode_list_column(name, kind, [v], strings.setdefault(name, {}) if kind == "str[]" else {})
                 out.append((i, "list", col.row(0)))
                 continue
-            if isinstance(v, Mapping):
+            if isinstance(v, Mapping) and not _where.is_geo(kind):  # (a geo literal may be {"lat": .., "lon": ..})
                 if list(v) != ["$inc"]:
                     raise ValueError(f"update_where: {name!r}: the only operator is $inc (got {sorted(map(str, v))})")
                 x = v["$inc"]
@@ -1464,6 +1469,43 @@ class Index:
                                                         descending=bool(descending), offset=int(offset))
         return {"ids": ns.ids.uuids_at(labels).tolist(), "values": self.decode_order_values(kind, values), "matched": matched,
                 "absent": absent}
+
+    # ------------------------------------------------------------------ additive: nearest by distance on a geo attribute
+    def check_nearest_args(self, by, point, limit, offset=0) -> int:
+        """The refusals of ``nearest`` that need no namespace -> the packed centre."""
+        if not isinstance(by, str) or by not in self._attributes:
+            raise ValueError(f"nearest: {by!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        if not _where.is_geo(self._attributes[by]):
+            raise ValueError(f"nearest: attribute {by!r} is a {self._attributes[by]} column; it needs a geo attribute")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
+            raise ValueError(f"nearest: limit must be an int >= 1 (got {limit!r})")
+        if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
+            raise ValueError(f"nearest: offset must be an int >= 0 (got {offset!r})")
+        if int(offset) + int(limit) > self._MAX_ORDER_ROWS:
+            raise ValueError(f"nearest: offset + limit must be <= {self._MAX_ORDER_ROWS} (got {int(offset) + int(limit)})")
+        return _where.geo_pack(point, "nearest: point")
+
+    def nearest(self, namespace: str, by: str, point, limit: int, where: Optional[Mapping] = None, *, offset: int = 0):
+        """Ranks ``[offset, offset + limit)`` of the live rows of ``namespace`` (those the dict filter ``where`` matches,
+        when one is given) that hold a location in the declared ``geo`` attribute ``by``, ranked on the device
+        (include/mlvdb_geo.h) by great-circle distance from ``point`` and rows at equal distance in insertion order:
+        ``{"ids": [UUID, ...], "points": [(lat, lon), ...], "distances": [metres, ...], "matched": live matching rows,
+        "absent": those of them without a location}``.  ``point`` is quantised as stored points are; a maximum distance is a
+        ``$geo_radius`` in ``where``.  ``offset + limit`` is at most 4096.  An unknown or empty namespace gives no rows."""
+        center = self.check_nearest_args(by, point, limit, offset)
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"nearest: where must be one dict filter or None (got {type(where).__name__})")
+        program = None if where is None else self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        if ns is None or ns.total == 0:
+            return {"ids": [], "points": [], "distances": [], "matched": 0, "absent": 0}
+        geo_nearest = getattr(ns.engine, "geo_nearest", None)
+        if geo_nearest is None:
+            raise ValueError("nearest needs an engine with geo_nearest (a single-device namespace)")
+        labels, points, dist, matched, absent = geo_nearest(list(self._attributes).index(by), center, int(limit),
+                                                            where=program, offset=int(offset))
+        return {"ids": ns.ids.uuids_at(labels).tolist(), "points": [_where.geo_degrees(p) for p in points.tolist()],
+                "distances": dist.tolist(), "matched": matched, "absent": absent}
 
     # ------------------------------------------------------------------ additive: facet counts and histograms on the device
     _MAX_FACET_VALUES = 1 << 20  # MLVDB_FACET_MAX_VALUES
@@ -1706,6 +1748,9 @@ class Index:
     # v3 + per sparse attribute the live rows' vectors in CSR form (offsets.i64, terms.i32, weights.f32); written only by
     # an index that declares a sparse attribute
     _FORMAT_V4 = "mlvdb-index-v4"
+    # the layout the index would otherwise write (v2, v3 or v4) with a "geo" attribute in the schema, whose column file is
+    # the raw int64 column (packed points, INT64_MIN = absent); written only by an index that declares a geo attribute
+    _FORMAT_V5 = "mlvdb-index-v5"
     _CHUNK_BYTES = 256 << 20
 
     def save_index(self, path: str) -> bool:
@@ -1714,7 +1759,8 @@ class Index:
         os.makedirs(path, exist_ok=True)
         has_lists = any(_where.is_list(kind) for kind in self._attributes.values())
         has_sparse = any(_where.is_sparse(kind) for kind in self._attributes.values())
-        fmt = self._FORMAT_V4 if has_sparse else self._FORMAT_V3 if has_lists else self._FORMAT_V2 if self._attributes else \
+        has_geo = any(_where.is_geo(kind) for kind in self._attributes.values())
+        fmt = self._FORMAT_V5 if has_geo else self._FORMAT_V4 if has_sparse else self._FORMAT_V3 if has_lists else self._FORMAT_V2 if self._attributes else \
             self._FORMAT
         meta = {"format": fmt, "space": self._space,
                 "rebuild_threshold": self._rebuild_threshold, "namespaces": []}
@@ -1817,10 +1863,12 @@ class Index:
             return False
         with open(manifest) as f:
             meta = json.load(f)
-        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4):
+        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5):
             raise RuntimeError(f"unknown index format {meta.get('format')!r}")
-        # (v3: v2 with list attributes, v4: v3 with sparse attributes)
-        v2 = meta["format"] in (self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4)
+        # (v3: v2 with list attributes, v4: v3 with sparse attributes, v5: any of them with geo attributes)
+        v2 = meta["format"] in (self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5)
+        if v2 and meta["format"] != self._FORMAT_V5 and any(_where.is_geo(k) for k in meta.get("attributes", {}).values()):
+            raise RuntimeError(f"a geo attribute in a {meta['format']} snapshot: only {self._FORMAT_V5} holds them")
         # v2: the snapshot's attributes replace the declared ones; v1: the declared ones stay, every value absent
         attributes = self._check_schema(meta.get("attributes", {})) if v2 else self._attributes
         if v2 and attributes and self._devices is not None and len(self._devices) > 1:
@@ -1836,13 +1884,13 @@ class Index:
             for j, kind in enumerate(attributes.values()):
                 if v2 and _where.is_list(kind):
                     base = self._attr_file(path, i, j, kind)[:-len("i64")]
-                    if meta["format"] not in (self._FORMAT_V3, self._FORMAT_V4) or not os.path.isfile(base + "values.i64") or \
+                    if meta["format"] not in (self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5) or not os.path.isfile(base + "values.i64") or \
                             not os.path.isfile(base + "offsets.i64") or \
                             os.path.getsize(base + "offsets.i64") != (total + 1) * 8:
                         raise RuntimeError(f"namespace {m['name']!r}: list attribute files do not match the manifest")
                 if v2 and _where.is_sparse(kind):
                     base = self._attr_file(path, i, j, kind)[:-len("i64")]
-                    if meta["format"] != self._FORMAT_V4 or not os.path.isfile(base + "terms.i32") or \
+                    if meta["format"] not in (self._FORMAT_V4, self._FORMAT_V5) or not os.path.isfile(base + "terms.i32") or \
                             not os.path.isfile(base + "weights.f32") or not os.path.isfile(base + "offsets.i64") or \
                             os.path.getsize(base + "offsets.i64") != (total + 1) * 8 or \
                             os.path.getsize(base + "terms.i32") != os.path.getsize(base + "weights.f32"):

@@ -352,6 +352,23 @@ class QueryProcessor:
                 "values": self._index.decode_order_values(kind, [x for x, _ in window]),
                 "matched": len(picked), "absent": len(picked) - len(ranked)}
 
+    # ---- additive: nearest by distance on a geo attribute (Index.nearest; no reference code)
+    def find_nearby(self, point, limit: int, namespace: str, by: str, where=None, offset: int = 0) -> List[dict]:
+        """The stored vectors of ``namespace`` nearest to ``point`` -- ``(lat, lon)`` or ``{"lat": .., "lon": ..}`` -- by the
+        declared geo attribute ``by``, ranked on the device (``Index.nearest``; ``where``: a dict filter or ``None``, a
+        maximum distance is a ``$geo_radius`` in it): ``[{"id", "values", "metadata", "distance": metres, "point": (lat,
+        lon) as the index holds it}, ...]``, nearest first."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"find_nearby: where must be a dict filter or None (got {type(where).__name__})")
+        got = self._index.nearest(namespace, by, point, limit, where, offset=offset)
+        stored = {v.id: v for v in self._storage.read_vectors(got["ids"], namespace) if v}
+        out = []
+        for vid, p, d in zip(got["ids"], got["points"], got["distances"]):
+            v = stored.get(vid)
+            if v:
+                out.append({"id": v.id, "values": v.values, "metadata": v.metadata, "distance": d, "point": p})
+        return self._fill_values(out, namespace)
+
     # ---- additive: facet counts and histograms (Index.facets / Index.histogram; no reference code)
     def _host_column(self, by: str, where, namespace: str):
         """(values of attribute ``by`` of the stored vectors ``where`` accepts -- ``None`` / NaN = absent --, their number)."""

@@ -28,6 +28,16 @@ attribute, and ``$all`` / ``$size`` on a scalar one, are a ``ValueError``.
 
 A sparse attribute (``"sparse"``: at most 255 (term, weight) pairs per row, include/mlvdb_sparse.h) takes ``$exists`` and
 ``$size`` (the number of its nonzeros) only; an empty vector ``{}`` exists.  Everything else on it is a ``ValueError``.
+
+A geo attribute (``"geo"``: one location per row, include/mlvdb_geo.h) holds a point ``(lat, lon)`` or
+``{"lat": .., "lon": ..}`` in degrees, quantised to 1e-7 degree, and takes
+
+    {"loc": {"$geo_radius": {"center": point, "radius": metres}}}    great-circle distance <= radius (R = 6371008.8 m)
+    {"loc": {"$geo_box": {"sw": point, "ne": point}}}                inclusive; sw.lon > ne.lon: across the antimeridian
+    $exists
+
+only; centres and corners are quantised exactly as stored points are.  Everything else on it, and both geo operators on
+another attribute, are a ``ValueError``.
 """
 from __future__ import annotations
 
@@ -44,6 +54,10 @@ LIST_MAX_LEN = 255               # MLVDB_LIST_MAX_LEN
 SPARSE_TYPES = ("sparse",)       # sparse vectors: (term, weight) pairs per row, searched by Index.search_sparse
 SPARSE_MAX_NNZ = 255             # MLVDB_SPARSE_MAX_NNZ
 SPARSE_MAX_QUERY_TERMS = 1024    # MLVDB_SPARSE_MAX_QUERY_TERMS
+GEO_TYPES = ("geo",)             # one location per row: (lat_e7 << 32) | uint32(lon_e7) in an int64 column
+GEO_LAT_MAX_E7 = 900_000_000     # MLVDB_GEO_LAT_MAX_E7
+GEO_LON_MAX_E7 = 1_800_000_000   # MLVDB_GEO_LON_MAX_E7
+GEO_EARTH_RADIUS_M = 6371008.8   # MLVDB_GEO_EARTH_RADIUS_M
 MAX_ATTRS = 16
 MAX_OPS = 64
 MAX_DEPTH = 32
@@ -51,12 +65,15 @@ MAX_DEPTH = 32
 # op codes (MLVDB_WHERE_*)
 TRUE, EQ, NE, LT, LE, GT, GE, IN, EXISTS, AND, OR, NOT = range(12)
 HAS, HAS_ANY, HAS_ALL, LEN = range(12, 16)  # list columns only (include/mlvdb_list.h)
+GEO_BOX, GEO_RADIUS = 16, 17  # geo columns only (include/mlvdb_geo.h)
 _COMBINATORS = (AND, OR, NOT)
 OP_DTYPE = np.dtype([("op", "<i4"), ("attr", "<i4"), ("a", "<i8"), ("b", "<i8")])  # mlvdb_where_op
 
 _ORDERED = {"$lt": LT, "$lte": LE, "$gt": GT, "$gte": GE}
-_FIELD_OPS = ("$eq", "$ne", "$lt", "$lte", "$gt", "$gte", "$in", "$nin", "$exists", "$all", "$size")
+_FIELD_OPS = ("$eq", "$ne", "$lt", "$lte", "$gt", "$gte", "$in", "$nin", "$exists", "$all", "$size", "$geo_radius",
+              "$geo_box")
 _LIST_ONLY = ("$all", "$size")
+_GEO_ONLY = ("$geo_radius", "$geo_box")
 
 
 @dataclass
@@ -81,6 +98,55 @@ def is_sparse(attr_type: str) -> bool:
     return attr_type in SPARSE_TYPES
 
 
+def is_geo(attr_type: str) -> bool:
+    return attr_type in GEO_TYPES
+
+
+def geo_pack(point: Any, what: str = "a point") -> int:
+    """A point -- ``(lat, lon)`` or ``{"lat": .., "lon": ..}``, finite degrees with lat in [-90, 90] and lon in
+    [-180, 180] -- as the int64 a geo column holds: ``(lat_e7 << 32) | uint32(lon_e7)``, each ``np.rint(x * 1e7)``.
+    ``ValueError`` (starting with ``what``) for anything else."""
+    if isinstance(point, Mapping):
+        if set(point) != {"lat", "lon"}:
+            raise ValueError(f"{what}: a point dict holds exactly 'lat' and 'lon', got {sorted(map(str, point))}")
+        pair = (point["lat"], point["lon"])
+    elif isinstance(point, (tuple, list)) and len(point) == 2:
+        pair = tuple(point)
+    else:
+        raise ValueError(f"{what}: {point!r} is not a point, (lat, lon) or {{'lat': .., 'lon': ..}}")
+    for x in pair:
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{what}: the coordinate {x!r} is not a number")
+    lat, lon = float(pair[0]), float(pair[1])
+    if not (math.isfinite(lat) and math.isfinite(lon) and -90.0 <= lat <= 90.0 and -180.0 <= lon <= 180.0):
+        raise ValueError(f"{what}: ({lat}, {lon}) is outside lat in [-90, 90], lon in [-180, 180]")
+    return (int(np.rint(lat * 1e7)) << 32) | (int(np.rint(lon * 1e7)) & 0xFFFFFFFF)
+
+
+def geo_unpack(value: int) -> Tuple[int, int]:
+    """A stored geo value -> ``(lat_e7, lon_e7)``."""
+    value = int(value)
+    lon = value & 0xFFFFFFFF
+    return value >> 32, lon - (1 << 32) if lon >= 1 << 31 else lon
+
+
+def geo_degrees(value: int) -> Tuple[float, float]:
+    """A stored geo value -> ``(lat, lon)`` in degrees."""
+    lat, lon = geo_unpack(value)
+    return lat / 1e7, lon / 1e7
+
+
+def geo_radius_threshold(radius: Any, what: str = "$geo_radius") -> float:
+    """``sin^2(r / 2R)`` clamped to 1 for a radius in metres (finite, >= 0): what GEO_RADIUS compares hav against."""
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{what}: the radius {radius!r} is not a number of metres")
+    r = float(radius)
+    if not math.isfinite(r) or r < 0.0:
+        raise ValueError(f"{what}: the radius must be finite and >= 0 metres, got {r}")
+    half = r / (2.0 * GEO_EARTH_RADIUS_M)
+    return 1.0 if half >= math.pi / 2 else min(1.0, math.sin(half) ** 2)
+
+
 def is_pooled(attr_type: str) -> bool:
     """A list or a sparse attribute: the column holds slots into a pool, not values."""
     return is_list(attr_type) or is_sparse(attr_type)
@@ -88,9 +154,9 @@ def is_pooled(attr_type: str) -> bool:
 
 def column_kind(attr_type: str) -> str:
     """The device column type of an attribute type: float -> float64, a list type -> int64_list, sparse -> sparse,
-    everything else -> int64."""
+    geo -> geo, everything else -> int64."""
     return "float64" if attr_type == "float" else "int64_list" if is_list(attr_type) else \
-        "sparse" if is_sparse(attr_type) else "int64"
+        "sparse" if is_sparse(attr_type) else "geo" if is_geo(attr_type) else "int64"
 
 
 class _Builder:
@@ -170,6 +236,13 @@ class _Builder:
 
     def field(self, key: str, op: str, value: Any) -> None:
         attr, kind = self.index[key], self.schema[key]
+        if is_geo(kind) != (op in _GEO_ONLY) and op != "$exists":
+            if is_geo(kind):
+                raise ValueError(f"{key!r} is a geo attribute: only $geo_radius, $geo_box and $exists apply, {op} does not")
+            raise ValueError(f"{key!r} is a {kind} attribute: {op} applies to geo attributes only")
+        if op in _GEO_ONLY:
+            self.geo_field(key, attr, op, value)
+            return
         if is_sparse(kind):
             if op == "$size":
                 self.size(key, attr, value)
@@ -210,6 +283,21 @@ class _Builder:
             self.false() if op != "$ne" else self.emit(TRUE)
             return
         self.emit({"$eq": EQ, "$ne": NE}.get(op) or _ORDERED[op], attr, v)
+
+    # -- geo attributes
+    def geo_field(self, key: str, attr: int, op: str, value: Any) -> None:
+        names = ("center", "radius") if op == "$geo_radius" else ("sw", "ne")
+        if not isinstance(value, Mapping) or set(value) != set(names):
+            raise ValueError(f"{key!r}: {op} takes a dict with exactly {names[0]!r} and {names[1]!r}")
+        a = geo_pack(value[names[0]], f"{key!r}: {op} {names[0]}")
+        if op == "$geo_radius":
+            self.emit(GEO_RADIUS, attr, a, float_bits(geo_radius_threshold(value["radius"], f"{key!r}: $geo_radius")))
+            return
+        b = geo_pack(value["ne"], f"{key!r}: {op} ne")
+        if geo_unpack(a)[0] > geo_unpack(b)[0]:
+            raise ValueError(f"{key!r}: $geo_box: sw lies north of ne (a box that crosses the antimeridian has sw.lon > ne.lon; "
+                             f"its latitudes stay ordered)")
+        self.emit(GEO_BOX, attr, a, b)
 
     # -- list attributes
     def list_set(self, key: str, values: Any, what: str) -> List[Any]:
@@ -531,7 +619,14 @@ def encode_sparse_column(name: str, values, max_nnz: int = SPARSE_MAX_NNZ) -> Sp
 def encode_column(name: str, kind: str, values, codes: Dict[str, int]) -> np.ndarray:
     """One attribute's values of a batch (``None`` = absent) as the device column (int64 with INT64_MIN absent, float64
     with NaN absent).  New strings get codes in ``codes`` (the caller passes a copy and keeps it only if the whole batch
-    is accepted).  A value of the wrong type raises ``ValueError`` naming the attribute."""
+    is accepted).  A value of the wrong type raises ``ValueError`` naming the attribute.  A geo attribute's values are
+    points (``geo_pack``), packed into int64."""
+    if is_geo(kind):
+        out = np.full(len(values), INT64_ABSENT, dtype=np.int64)
+        for i, v in enumerate(values.tolist() if isinstance(values, np.ndarray) else values):
+            if v is not None:
+                out[i] = geo_pack(v, f"attribute {name!r} (geo): row {i}")
+        return out
     if isinstance(values, np.ndarray) and values.dtype != object:
         return _encode_array(name, kind, values, codes)
     n = len(values)
