@@ -223,6 +223,12 @@ GEO_SIGNATURES = {
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
+# include/mlvdb_stats.h: min, max, sum and count of an attribute column per group of a second one
+STATS_SIGNATURES = {
+    "mlvdb_attr_stats": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Where), C.c_int64, _P, _P, _P, _P, _P, _P, _P,
+                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -255,7 +261,7 @@ def load() -> C.CDLL:
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
                                       **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **HYBRID_SIGNATURES,
-                                      **GEO_SIGNATURES}.items():
+                                      **GEO_SIGNATURES, **STATS_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -2,6 +2,7 @@
 // and the orchestration of the scan kernels.  Nothing here touches the CPU for arithmetic:
 // if no HIP device is usable every entry point fails with MLVDB_ERR_NO_DEVICE.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -113,6 +114,9 @@ struct mlvdb_index {
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
+    // attribute statistics (mlvdb_stats.h): the global group table, its packed copy and the counters, sized by the call's
+    // max_groups, never by the corpus
+    DevBuf stats_tab;
     // ordered queries (mlvdb_order.h): the call's state, one histogram per digit pass, the collected (key, label) pairs and the
     // ranked window -- sized by MLVDB_ORDER_MAX_ROWS and the histograms, never by the corpus
     DevBuf order_ws;
@@ -3597,6 +3601,112 @@ int mlvdb_facet_bins(mlvdb_index* h, int32_t attr, const mlvdb_where* where, con
     for (int32_t i = 0; i <= n_edges; ++i) out_counts[i] = 0;
     if (h->total == 0) return MLVDB_OK;
     return facet_bins_impl(h, attr, where, edges, n_edges, out_counts, matched, absent);
+    });
+}
+
+// ---- attribute statistics (mlvdb_stats.h)
+extern "C++" {
+namespace {
+int attr_stats_impl(mlvdb_index* h, int32_t attr, int32_t by, const mlvdb_where* where, int64_t max_groups, int64_t* out_keys,
+                    int64_t* out_rows, int64_t* out_count, void* out_min, void* out_max, int64_t* out_sum_hi,
+                    uint64_t* out_sum_lo, int64_t* n_groups, int64_t* matched, int64_t* by_absent) {
+    hipStream_t s = h->stream;
+    const WhereOp* prog;
+    int32_t n_ops;
+    const int64_t* set_d;
+    if (int rc = facet_program(h, where, &prog, &n_ops, &set_d)) return rc;
+    const bool f64 = h->attr_type[attr] == MLVDB_ATTR_FLOAT64;
+    uint64_t slots = 64;  // a power of two >= 2 max_groups: the table is at most half full when the call succeeds
+    while (slots < 2 * (uint64_t)max_groups) slots *= 2;
+    // [keys | min | rows | count | max | sum hi | sum lo | counters | packed groups]
+    const size_t words = 7 * slots + kFacetCounters + (size_t)max_groups * kStatsRecord;
+    HIP_TRY(h, h->stats_tab.ensure(words * sizeof(unsigned long long)));
+    StatsTable t{};
+    t.keys = h->stats_tab.as<unsigned long long>();
+    t.mn = t.keys + slots;
+    t.rows = t.mn + slots;
+    t.count = t.rows + slots;
+    t.mx = t.count + slots;
+    t.hi = t.mx + slots;
+    t.lo = t.hi + slots;
+    t.ctr = t.lo + slots;
+    t.mask = slots - 1;
+    t.max_groups = (unsigned long long)max_groups;
+    unsigned long long* packed = t.ctr + kFacetCounters;
+    HIP_TRY(h, launch_attr_fill(reinterpret_cast<int64_t*>(t.keys), INT64_MIN, 0, (int64_t)slots, s));
+    HIP_TRY(h, hipMemsetAsync(t.mn, 0xFF, slots * sizeof(unsigned long long), s));
+    HIP_TRY(h, hipMemsetAsync(t.rows, 0, (5 * slots + kFacetCounters) * sizeof(unsigned long long), s));
+    const int64_t* by_col = by < 0 ? nullptr : h->attr_col[by];
+    HIP_TRY(h, launch_stats_pass1(prog, n_ops, set_d, h->rn, by_col, h->attr_col[attr], f64, h->total, t, s));
+    if (f64) HIP_TRY(h, launch_stats_pass2(prog, n_ops, set_d, h->rn, by_col, h->attr_col[attr], h->total, t, s));
+    HIP_TRY(h, launch_stats_collect(t, packed, s));
+    unsigned long long ctr[kFacetCounters] = {};
+    HIP_TRY(h, hipMemcpyAsync(ctr, t.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *matched = (int64_t)ctr[kFacetMatched];
+    *by_absent = (int64_t)ctr[kFacetAbsent];
+    *n_groups = (int64_t)ctr[kFacetDistinct];
+    if (ctr[kFacetOverflow] || ctr[kFacetDistinct] > (unsigned long long)max_groups) {
+        *n_groups = std::max<int64_t>(*n_groups, max_groups + 1);
+        return fail(h, MLVDB_ERR_OVERFLOW, "attr_stats: more than max_groups distinct values of by");
+    }
+    const size_t n = (size_t)ctr[kFacetDistinct];
+    if (ctr[kFacetCursor] != ctr[kFacetDistinct]) return fail(h, MLVDB_ERR_INTERNAL, "attr_stats: table and counter disagree");
+    if (n == 0) {  // nothing matched: no group, or the one empty group of an ungrouped call (written by the caller)
+        if (by < 0) *n_groups = 1;
+        return MLVDB_OK;
+    }
+    // one copy-down for all outputs: n records of kStatsRecord words
+    std::vector<std::array<unsigned long long, kStatsRecord>> recs(n);
+    HIP_TRY(h, hipMemcpyAsync(recs.data(), packed, n * sizeof recs[0], hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    std::sort(recs.begin(), recs.end(),  // (the keys are distinct: the order is total)
+              [](const auto& a, const auto& b) { return (int64_t)a[0] < (int64_t)b[0]; });
+    for (size_t i = 0; i < n; ++i) {
+        const auto& r = recs[i];
+        out_keys[i] = (int64_t)r[0];
+        out_rows[i] = (int64_t)r[1];
+        out_count[i] = (int64_t)r[2];
+        // the images back to the column's own type (count == 0: unspecified)
+        static_cast<uint64_t*>(out_min)[i] = f64 ? stats_bits_f64(r[3]) : stats_image_i64((int64_t)r[3]);
+        static_cast<uint64_t*>(out_max)[i] = f64 ? stats_bits_f64(r[4]) : stats_image_i64((int64_t)r[4]);
+        out_sum_hi[i] = (int64_t)r[5];
+        out_sum_lo[i] = r[6];
+    }
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_attr_stats(mlvdb_index* h, int32_t attr, int32_t by, const mlvdb_where* where, int64_t max_groups, int64_t* out_keys,
+                     int64_t* out_rows, int64_t* out_count, void* out_min, void* out_max, int64_t* out_sum_hi,
+                     uint64_t* out_sum_lo, int64_t* n_groups, int64_t* matched, int64_t* by_absent) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = attr_check(h, attr))) return rc;
+    if ((rc = scalar_check(h, attr))) return rc;
+    if ((rc = value_check(h, attr))) return rc;
+    if (by != -1) {
+        if ((rc = attr_check(h, by))) return rc;
+        if ((rc = value_check(h, by))) return rc;
+        if (h->attr_type[by] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "attr_stats: by needs an int64 column");
+    }
+    if (max_groups < 1 || max_groups > MLVDB_FACET_MAX_VALUES)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "max_groups must be in 1..MLVDB_FACET_MAX_VALUES");
+    if (!out_keys || !out_rows || !out_count || !out_min || !out_max || !out_sum_hi || !out_sum_lo || !n_groups || !matched ||
+        !by_absent)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (where && (rc = where_prepare(h, where))) return rc;
+    *n_groups = by < 0 ? 1 : 0;
+    *matched = *by_absent = 0;
+    out_keys[0] = out_rows[0] = out_count[0] = out_sum_hi[0] = 0;  // the one group of an ungrouped call when nothing matches
+    out_sum_lo[0] = 0;
+    static_cast<int64_t*>(out_min)[0] = static_cast<int64_t*>(out_max)[0] = 0;
+    if (h->total == 0) return MLVDB_OK;
+    return attr_stats_impl(h, attr, by, where, max_groups, out_keys, out_rows, out_count, out_min, out_max, out_sum_hi,
+                           out_sum_lo, n_groups, matched, by_absent);
     });
 }
 

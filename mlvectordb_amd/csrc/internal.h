@@ -15,6 +15,7 @@
 #include "../../include/mlvdb_distinct.h"
 #include "../../include/mlvdb_grouped.h"
 #include "../../include/mlvdb_facet.h"
+#include "../../include/mlvdb_stats.h"
 #include "../../include/mlvdb_order.h"
 #include "../../include/mlvdb_mmr.h"
 #include "../../include/mlvdb_like.h"
@@ -649,6 +650,48 @@ hipError_t launch_facet_collect(const FacetTable& t, long long* out_keys, unsign
 hipError_t launch_facet_bins(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* col,
                              int32_t type, int64_t total, const int64_t* edges, int32_t n_edges, unsigned long long* bins,
                              unsigned long long* ctr, hipStream_t s);
+
+// ---------------------------------------------------------------- attribute statistics (kernels_stats.hip)
+// per-block table: 48 B per slot of an int64 column (48 KiB, three blocks per CU), 32 B of a float64 one
+constexpr int kStatsLdsSlots = 1024;
+constexpr int kStatsLdsSlotsOne = 64;  // ... of an ungrouped call: one key
+constexpr int kStatsRecord = 8;       // words of a packed group: key, rows, count, min, max, sum hi, sum lo, 0
+// Order-preserving uint64 images: integer order of the images = integer order of int64 values / IEEE totalOrder of doubles
+// (-0.0 below +0.0).  Image 0 is INT64_MIN / a NaN: never a present value.
+__host__ __device__ inline uint64_t stats_image_i64(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }
+__host__ __device__ inline uint64_t stats_image_f64(uint64_t bits) { return bits ^ ((bits >> 63) ? ~0ull : 0x8000000000000000ull); }
+__host__ __device__ inline uint64_t stats_bits_f64(uint64_t image) {  // the image back to the double's bits
+    return image ^ ((image >> 63) ? 0x8000000000000000ull : ~0ull);
+}
+// E = floor(log2 m) of the group's largest finite magnitude m from the bits of its min and max (include/mlvdb_stats.h);
+// false when the group's fixed-point sum is 0 by definition: it holds an infinity, or m == 0
+__host__ __device__ inline bool stats_exponent(uint64_t min_bits, uint64_t max_bits, int* E) {
+    const uint64_t a = min_bits & 0x7FFFFFFFFFFFFFFFull, b = max_bits & 0x7FFFFFFFFFFFFFFFull, m = a > b ? a : b;
+    if (m >= 0x7FF0000000000000ull || m == 0) return false;
+    int top = 51;  // a subnormal: the place of its leading bit
+    while (!(m >> 52) && !((m >> top) & 1)) --top;
+    *E = (m >> 52) ? (int)(m >> 52) - 1023 : top - 1074;
+    return true;
+}
+// The global table of one call: `mask + 1` slots (a power of two >= 2 max_groups), keys INT64_MIN = empty, placed by
+// facet_hash with linear probing; min / max as images (min starts at ~0, max at 0), sum hi:lo a 128-bit two's complement
+struct StatsTable {
+    unsigned long long *keys, *mn, *rows, *count, *mx, *hi, *lo;
+    uint64_t mask;
+    unsigned long long max_groups;
+    unsigned long long* ctr;  // [kFacetCounters], the words of a facet call
+};
+// Pass 1 over rn, the program's columns, `by` (int64; nullptr: one group under key 0) and `col` (int64, or float64 by
+// `f64`): every live matching row with a value of `by` counted under it in `t` -- rows, count, min, max and, of an int64
+// column, the sum; ctr[matched / absent (no value of by) / distinct / overflow] updated.  n_ops == 0: no program.
+hipError_t launch_stats_pass1(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* by,
+                              const int64_t* col, bool f64, int64_t total, const StatsTable& t, hipStream_t s);
+// Pass 2 of a float64 column over the final table of pass 1: the fixed-point terms of every group's sum added to hi:lo.
+// Does nothing when pass 1 overflowed.
+hipError_t launch_stats_pass2(const WhereOp* prog, int32_t n_ops, const int64_t* set, const float* rn, const int64_t* by,
+                              const int64_t* col, int64_t total, const StatsTable& t, hipStream_t s);
+// the non-empty slots of `t` packed through ctr[kFacetCursor] into out[max_groups][kStatsRecord], in no order
+hipError_t launch_stats_collect(const StatsTable& t, unsigned long long* out, hipStream_t s);
 
 // ---------------------------------------------------------------- ordered metadata queries (kernels_order.hip)
 // A row's composite key: its value mapped to an order-preserving uint64 (complemented for a descending call) above its

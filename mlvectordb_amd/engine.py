@@ -100,6 +100,15 @@ class FacetOverflow(RuntimeError):
         self.max_values, self.n_values, self.matched, self.absent = max_values, n_values, matched, absent
 
 
+class StatsOverflow(RuntimeError):
+    """An ``attr_stats`` call met more than ``max_groups`` distinct values of ``by`` (``MLVDB_ERR_OVERFLOW``).  ``matched`` and
+    ``by_absent`` are still exact; ``n_groups`` is some number above ``max_groups``."""
+
+    def __init__(self, max_groups: int, n_groups: int, matched: int, by_absent: int) -> None:
+        super().__init__(f"attr_stats: more than max_groups={max_groups} distinct values of by")
+        self.max_groups, self.n_groups, self.matched, self.by_absent = max_groups, n_groups, matched, by_absent
+
+
 class MaxSimOverflow(RuntimeError):
     """A late-interaction call met more than ``max_groups`` documents among the rows it counts (``MLVDB_ERR_OVERFLOW``)."""
 
@@ -766,6 +775,30 @@ class HipScanEngine:
             self._h, int(attr), None if w is None else C.byref(w), edges.ctypes.data, int(edges.size), counts.ctypes.data,
             C.byref(matched), C.byref(absent)), "facet_bins")
         return counts, int(matched.value), int(absent.value)
+
+    # -- attribute statistics (include/mlvdb_stats.h) ------------------------------------
+    def attr_stats(self, attr: int, by: Optional[int] = None, max_groups: int = 1, where=None):
+        """Rows, count, min, max and sum of scalar column ``attr`` among the live rows (those the compiled ``where.Program``
+        matches, when one is given), per distinct present value of int64 column ``by`` or, with ``by=None``, as one group
+        under key 0: (keys int64 ascending, rows int64, count int64, min, max -- int64 or float64 by the column's type,
+        unspecified where count is 0 --, sum_hi int64, sum_lo uint64, matched, by_absent) with ``rows.sum() + by_absent ==
+        matched``.  ``sum_hi:sum_lo`` is a signed 128-bit integer: the exact sum of an int64 column, the fixed-point sum
+        of a float64 one (``stats.int128`` / ``stats.float_sum``).  More than ``max_groups`` groups raise ``StatsOverflow``."""
+        max_groups = int(max_groups)
+        size = max(1, min(max_groups, _native.FACET_MAX_VALUES))
+        kind = self._attr_kinds.get(int(attr), "int64")
+        keys, rows, count, hi = (np.zeros(size, dtype=np.int64) for _ in range(4))
+        lo = np.zeros(size, dtype=np.uint64)
+        mn, mx = (np.zeros(size, dtype=np.float64 if kind == "float64" else np.int64) for _ in range(2))
+        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        w, keep = self._where(where) if where is not None else (None, None)
+        rc = self._check(self._lib.mlvdb_attr_stats(
+            self._h, int(attr), -1 if by is None else int(by), None if w is None else C.byref(w), max_groups,
+            keys.ctypes.data, rows.ctypes.data, count.ctypes.data, mn.ctypes.data, mx.ctypes.data, hi.ctypes.data,
+            lo.ctypes.data, C.byref(n), C.byref(matched), C.byref(absent)), "attr_stats", allow=(_native.ERR_OVERFLOW,))
+        if rc == _native.ERR_OVERFLOW:
+            raise StatsOverflow(max_groups, int(n.value), int(matched.value), int(absent.value))
+        return tuple(a[: n.value].copy() for a in (keys, rows, count, mn, mx, hi, lo)) + (int(matched.value), int(absent.value))
 
     # -- ordered metadata queries (include/mlvdb_order.h) -------------------------------
     def where_ordered(self, attr: int, limit: int, where=None, descending: bool = False, offset: int = 0):

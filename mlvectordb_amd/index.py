@@ -35,8 +35,9 @@ from uuid import UUID
 import numpy as np
 
 from . import _native
+from . import stats as _stats
 from . import where as _where
-from .engine import FacetOverflow, HipScanEngine, ScanEngine
+from .engine import FacetOverflow, HipScanEngine, ScanEngine, StatsOverflow
 from .idtable import IdTable, mint_uuid4_bytes
 from .interfaces import VectorDTO, VectorProtocol
 
@@ -1626,6 +1627,88 @@ class Index:
             raise ValueError("histogram needs an engine with facet_bins (a single-device namespace)")
         counts, matched, absent = facet_bins(list(self._attributes).index(by), e, where=program)
         return {"counts": counts, "matched": matched, "absent": absent}
+
+    # ------------------------------------------------------------------ additive: attribute statistics on the device
+    def check_stats_args(self, attr, by: Optional[str] = None, max_groups: int = 65536) -> List[str]:
+        """The refusals of ``stats`` that need no namespace -> the attributes to summarise (``attr`` as a list)."""
+        if self._devices is not None and len(self._devices) > 1:
+            raise ValueError("stats is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        names = list(attr) if isinstance(attr, (list, tuple)) else [attr]
+        for name in names + ([] if by is None else [by]):
+            if not isinstance(name, str) or name not in self._attributes:
+                raise ValueError(f"stats: {name!r} is not a declared attribute of this index "
+                                 f"(declared: {sorted(self._attributes)})")
+            self._check_scalar("stats", name)
+        for name in names:
+            if self._attributes[name] not in ("int", "float", "bool"):
+                raise ValueError(f"stats: attribute {name!r} is a {self._attributes[name]} column; min, max and sum need an "
+                                 f"int, float or bool attribute")
+        if by is not None and self._attributes[by] == "float":
+            raise ValueError(f"stats: by={by!r} is a float column; groups need an int, str or bool attribute")
+        if isinstance(max_groups, bool) or not isinstance(max_groups, (int, np.integer)) or \
+                not 1 <= max_groups <= self._MAX_FACET_VALUES:
+            raise ValueError(f"stats: max_groups must be in 1..{self._MAX_FACET_VALUES} (got {max_groups!r})")
+        return names
+
+    def stats(self, namespace: str, attr, where: Optional[Mapping] = None, by: Optional[str] = None,
+              max_groups: int = 65536):
+        """Count, min, max, sum and mean of a declared ``int`` / ``float`` / ``bool`` attribute over the live rows of
+        ``namespace`` (those the dict filter ``where`` matches, when one is given), aggregated on the device
+        (include/mlvdb_stats.h).  Ungrouped: ``{"matched": live matching rows, "count": those with a value, "absent": those
+        without, "min", "max", "sum", "mean"}``.  ``by=`` a declared ``int`` / ``str`` / ``bool`` attribute: ``{"groups":
+        [(value, {"rows", "count", "min", "max", "sum", "mean"}), ...], "matched", "by_absent"}``, the groups ascending by
+        decoded value, ``rows`` the group's matching rows and ``by_absent`` the matching rows without a value of ``by``.
+        An ``int`` sum is an exact Python int, a ``bool`` counts as 0 / 1 (``mean`` = the share of true), a ``float`` sum
+        is the fixed-point sum of the header -- the same bits whatever the order of the rows, the correctly rounded sum
+        when the values lie within a factor 2**9 of the largest; ``mean`` is ``sum / count``.  No value at all: ``min``,
+        ``max`` and ``mean`` are ``None``, ``sum`` is 0.  ``max_groups`` bounds the groups of an ``int`` ``by`` (more:
+        ``ValueError``); a ``str`` one is bounded by its dictionary, a ``bool`` by two.  ``attr`` as a list of attributes
+        returns a dict keyed by attribute (one device call each)."""
+        names = self.check_stats_args(attr, by, max_groups)
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"stats: where must be one dict filter or None (got {type(where).__name__})")
+        program = None if where is None else self._compile(namespace, where)
+        ns = self._ns.get(namespace)
+        out = {}
+        for name in names:
+            kind = self._attributes[name]
+            if ns is None or ns.total == 0:
+                out[name] = self.shape_stats(kind, by, [], [], 0, 0) if by is not None else \
+                    self.shape_stats(kind, None, [None], [(0, 0, None, None, 0)], 0, 0)
+                continue
+            attr_stats = getattr(ns.engine, "attr_stats", None)
+            if attr_stats is None:
+                raise ValueError("stats needs an engine with attr_stats (a single-device namespace)")
+            columns = list(self._attributes)
+            by_kind = None if by is None else self._attributes[by]
+            codes = {} if by is None else ns.strings.get(by, {})
+            bound = 1 if by is None else max(1, len(codes)) if by_kind == "str" else 2 if by_kind == "bool" else int(max_groups)
+            try:
+                keys, rows, count, lo, hi, sum_hi, sum_lo, matched, by_absent = attr_stats(
+                    columns.index(name), None if by is None else columns.index(by), bound, where=program)
+            except StatsOverflow as e:
+                raise ValueError(f"stats: by={by!r} holds more than max_groups={bound} distinct values among the {e.matched} "
+                                 f"matching rows; raise max_groups (at most {self._MAX_FACET_VALUES})") from e
+            values = keys.tolist()
+            if by_kind == "str":
+                strings = sorted(codes, key=codes.get)  # code order
+                values = [strings[v] for v in values]
+            elif by_kind == "bool":
+                values = [bool(v) for v in values]
+            groups = [(r, c, a, b, _stats.int128(h, l)) for r, c, a, b, h, l in
+                      zip(rows.tolist(), count.tolist(), lo.tolist(), hi.tolist(), sum_hi.tolist(), sum_lo.tolist())]
+            out[name] = self.shape_stats(kind, by, values, groups, matched, by_absent)
+        return out if isinstance(attr, (list, tuple)) else out[names[0]]
+
+    @staticmethod
+    def shape_stats(kind: str, by: Optional[str], values: list, groups: List[tuple], matched: int, by_absent: int) -> dict:
+        """The answer of ``stats`` from decoded group values and (rows, count, min, max, exact or fixed-point sum) per
+        group; ungrouped (``by is None``): the one group."""
+        if by is None:
+            rows, count, lo, hi, total = groups[0]
+            return {"matched": matched, "absent": matched - count, **_stats.summary(kind, count, lo, hi, total)}
+        pairs = [(v, {"rows": g[0], **_stats.summary(kind, *g[1:])}) for v, g in zip(values, groups)]
+        return {"groups": sorted(pairs, key=lambda p: p[0]), "matched": matched, "by_absent": by_absent}
 
     def range_search_many(self, queries, radius: float, namespace: str, metric: str,
                           max_results: int = 1024, where=None) -> List[List[SearchResult]]:

@@ -20,6 +20,7 @@ from collections.abc import Mapping
 from typing import Any, Dict, Iterable, List, Optional, Sequence
 from uuid import UUID
 
+from . import stats as _stats
 from .interfaces import IndexProtocol, VectorDTO
 from .vector import Vector
 
@@ -413,6 +414,42 @@ class QueryProcessor:
         bins = np.searchsorted(e, np.asarray(present, dtype=e.dtype), side="right")
         return {"counts": np.bincount(bins, minlength=e.size + 1).astype(np.int64), "matched": matched,
                 "absent": matched - len(present)}
+
+    # ---- additive: attribute statistics (Index.stats; no reference code)
+    def stats(self, attr, where=None, namespace: str = "default", by: Optional[str] = None, max_groups: int = 65536):
+        """``Index.stats`` of ``namespace``: a dict filter (or no filter) is aggregated on the device; a predicate is
+        computed over the storage's metadata on the host, as ``facets`` does, by the same rules -- exact integer sums, the
+        fixed-point sum of floats (stats.py) -- so both paths return equal values."""
+        if where is None or isinstance(where, Mapping):
+            return self._index.stats(namespace, attr, where, by=by, max_groups=max_groups)
+        if not callable(where):
+            raise ValueError(f"stats: where must be a dict filter, a predicate or None (got {type(where).__name__})")
+        names = self._index.check_stats_args(attr, by, max_groups)
+        kinds = self._index.attributes
+        picked = [v.metadata or {} for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
+        out = {}
+        for name in names:
+            kind = kinds[name]
+            members: Dict[Any, list] = {} if by is not None else {None: []}
+            by_absent = 0
+            for m in picked:
+                g = None if by is None else m.get(by)
+                if by is not None and g is None:
+                    by_absent += 1
+                    continue
+                x = m.get(name)
+                members.setdefault(g, []).append(None if x is None else float(x) if kind == "float" else int(x))
+            if by is not None and kinds[by] == "int" and len(members) > max_groups:
+                raise ValueError(f"stats: by={by!r} holds more than max_groups={max_groups} distinct values")
+            groups = []
+            for xs in members.values():
+                present = [x for x in xs if x is not None and x == x]
+                if kind == "float":
+                    groups.append((len(xs),) + _stats.float_group(present))
+                else:
+                    groups.append((len(xs), len(present), min(present, default=None), max(present, default=None), sum(present)))
+            out[name] = self._index.shape_stats(kind, by, list(members), groups, len(picked), by_absent)
+        return out if isinstance(attr, (list, tuple)) else out[names[0]]
 
     # ---- delete -> lazy rebuild (query_processor.py:51-62)
     def delete(self, ids: Sequence[UUID], namespace: str = "default") -> Sequence[UUID]:
