@@ -117,6 +117,16 @@ class MaxSimOverflow(RuntimeError):
         self.max_groups = max_groups
 
 
+def _opt(a):
+    """The data pointer of an optional array: ``None`` stays ``None`` (NULL: the entry skips that output or input)."""
+    return None if a is None else a.ctypes.data
+
+
+def _nonempty(a):
+    """The data pointer of an array that may be empty: NULL then (NumPy's pointer of an empty array points nowhere)."""
+    return a.ctypes.data if a.size else None
+
+
 class HipScanEngine:
     """Exhaustive fp32 corpus scan on one MI355X, through the C ABI."""
 
@@ -150,6 +160,31 @@ class HipScanEngine:
     @property
     def handle(self) -> C.c_void_p:
         return self._h
+
+    def _queries(self, queries) -> np.ndarray:
+        """``queries`` as the contiguous float32 [nq, dim] array the entries read (itself when it already is one)."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        return queries
+
+    @staticmethod
+    def _knn_outputs(shape, want64: bool):
+        """The outputs of a kNN-shaped entry: labels int64 and distances float32 of ``shape`` = (nq, k, ...), counts int32
+        [nq] (zeros), float64 distances of ``shape`` with ``want64`` (else ``None``)."""
+        return (np.empty(shape, dtype=np.int64), np.empty(shape, dtype=np.float32), np.zeros(shape[0], dtype=np.int32),
+                np.empty(shape, dtype=np.float64) if want64 else None)
+
+    @staticmethod
+    def _tally():
+        """The ``n, matched, absent`` out-parameters of the aggregating entries."""
+        return C.c_int64(0), C.c_int64(0), C.c_int64(0)
+
+    @staticmethod
+    def _first(n, arrays, *totals) -> tuple:
+        """What an aggregating entry returns: the first ``n`` of each output buffer (copies: the buffers are sized for the
+        most the call may return), then the totals as ints."""
+        return tuple(a[: n.value].copy() for a in arrays) + tuple(int(t.value) for t in totals)
 
     def set_strategy(self, strategy: str) -> None:
         self._check(self._lib.mlvdb_index_set_strategy(self._h, _native.STRATEGY_CODES[strategy]), "set_strategy")
@@ -230,9 +265,7 @@ class HipScanEngine:
     def pair_distances(self, queries: np.ndarray, labels: np.ndarray):
         """Exact distances of the pairs (queries[q], row labels[q, j]) in this index's space, by the kernels' own fp64
         summation (``mlvdb_pair_distances``): (float64 [nq, m], float32 [nq, m]); label -1 gives +inf."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         labels = np.ascontiguousarray(labels, dtype=np.int64)
         if labels.ndim != 2 or labels.shape[0] != queries.shape[0]:
             raise RuntimeError(f"labels must be [nq, m]; got {labels.shape} for {queries.shape[0]} queries")
@@ -268,8 +301,17 @@ class HipScanEngine:
         """(mlvdb_where, the arrays it points into: kept alive by the caller for the call)."""
         ops = np.ascontiguousarray(program.ops)
         table = np.ascontiguousarray(program.set, dtype=np.int64)
-        w = _native.Where(ops.ctypes.data, int(ops.size), table.ctypes.data if table.size else None, int(table.size))
+        w = _native.Where(ops.ctypes.data, int(ops.size), _nonempty(table), int(table.size))
         return w, (ops, table)
+
+    @classmethod
+    def _where_arg(cls, program):
+        """An optional compiled filter as (the ``const mlvdb_where*`` argument: ``None`` without one, what the caller keeps
+        alive for the call)."""
+        if program is None:
+            return None, None
+        w, keep = cls._where(program)
+        return C.byref(w), (w, keep)
 
     def where_count(self, program) -> int:
         """Live rows the compiled filter (``where.Program``) matches, counted on the device."""
@@ -340,8 +382,7 @@ class HipScanEngine:
         """The lists of rows first..first+len(col)-1 of list column ``attr`` (``col``: a ``where.ListColumn``)."""
         offsets, values, present = self._csr(col)
         self._check(self._lib.mlvdb_attr_list_set(self._h, int(attr), int(first), present.size, offsets.ctypes.data,
-                                                  values.ctypes.data if values.size else None, present.ctypes.data),
-                    "attr_list_set")
+                                                  _nonempty(values), present.ctypes.data), "attr_list_set")
 
     def set_attr_list_at(self, attr: int, labels: np.ndarray, col) -> int:
         """List i of ``col`` -> row ``labels[i]`` (distinct labels in [0, total); tombstoned rows are skipped); returns the
@@ -352,8 +393,7 @@ class HipScanEngine:
             raise RuntimeError(f"{labels.size} labels but {present.size} lists")
         n = C.c_int64(0)
         self._check(self._lib.mlvdb_attr_list_set_at(self._h, int(attr), labels.ctypes.data, labels.size, offsets.ctypes.data,
-                                                     values.ctypes.data if values.size else None, present.ctypes.data,
-                                                     C.byref(n)), "attr_list_set_at")
+                                                     _nonempty(values), present.ctypes.data, C.byref(n)), "attr_list_set_at")
         return int(n.value)
 
     def get_attr_list(self, attr: int, first: int, n: int):
@@ -366,9 +406,8 @@ class HipScanEngine:
         values = np.empty(0, dtype=np.int64)
         needed = C.c_int64(0)
         for _ in range(2):  # the first call sizes the values, the second reads them
-            self._check(self._lib.mlvdb_attr_list_get(self._h, int(attr), int(first), n, offsets.ctypes.data,
-                                                      values.ctypes.data if values.size else None, present.ctypes.data,
-                                                      values.size, C.byref(needed)), "attr_list_get")
+            self._check(self._lib.mlvdb_attr_list_get(self._h, int(attr), int(first), n, offsets.ctypes.data, _nonempty(values),
+                                                      present.ctypes.data, values.size, C.byref(needed)), "attr_list_get")
             if needed.value <= values.size:
                 break
             values = np.empty(needed.value, dtype=np.int64)
@@ -380,8 +419,8 @@ class HipScanEngine:
         w, keep = self._where(program)
         arr = np.zeros(0, dtype=np.int64) if values is None else np.ascontiguousarray(values, dtype=np.int64).ravel()
         matched = C.c_int64(0)
-        self._check(self._lib.mlvdb_attr_list_update_where(self._h, C.byref(w), int(attr), arr.ctypes.data if arr.size else None,
-                                                           int(arr.size), 1 if values is None else 0, C.byref(matched)),
+        self._check(self._lib.mlvdb_attr_list_update_where(self._h, C.byref(w), int(attr), _nonempty(arr), int(arr.size),
+                                                           1 if values is None else 0, C.byref(matched)),
                     "attr_list_update_where")
         return int(matched.value)
 
@@ -395,37 +434,30 @@ class HipScanEngine:
         """``facet_values`` of a list column: counts[v] = live matching rows whose list holds values[v]; ``absent`` = the
         matching rows with no list or an empty one (a row counts under each of its values, so the counts do not sum to
         ``matched - absent``)."""
-        max_values = int(max_values)
-        values = np.empty(max(0, min(max_values, _native.FACET_MAX_VALUES)), dtype=np.int64)
-        counts = np.empty(values.size, dtype=np.int64)
-        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        w, keep = self._where(where) if where is not None else (None, None)
-        rc = self._check(self._lib.mlvdb_facet_list_values(
-            self._h, int(attr), None if w is None else C.byref(w), max_values, values.ctypes.data, counts.ctypes.data,
-            C.byref(n), C.byref(matched), C.byref(absent)), "facet_list_values", allow=(_native.ERR_OVERFLOW,))
-        if rc == _native.ERR_OVERFLOW:
-            raise FacetOverflow(max_values, int(n.value), int(matched.value), int(absent.value))
-        return values[: n.value].copy(), counts[: n.value].copy(), int(matched.value), int(absent.value)
+        return self._facet("facet_list_values", attr, max_values, where)
 
     # -- sparse vector columns (include/mlvdb_sparse.h) ----------------------------------
     @staticmethod
     def _sparse_csr(col):
         """A ``where.SparseColumn`` as the contiguous arrays the C entries take (kept alive by the caller for the call)."""
-        offsets = np.ascontiguousarray(col.offsets, dtype=np.int64)
-        terms = np.ascontiguousarray(col.terms, dtype=np.int32)
-        weights = np.ascontiguousarray(col.weights, dtype=np.float32)
+        offsets, terms, weights = HipScanEngine._sparse_arrays(col)
         present = np.ascontiguousarray(col.present, dtype=np.uint8)
         if offsets.size != present.size + 1 or terms.size != weights.size:
             raise RuntimeError(f"{present.size} rows but {offsets.size} offsets, {terms.size} terms and {weights.size} weights")
         return offsets, terms, weights, present
 
+    @staticmethod
+    def _sparse_arrays(col):
+        """``_sparse_csr`` without ``present`` and without its size check: the form of a batch of sparse queries, whose
+        entries check the sizes against their own query count."""
+        return (np.ascontiguousarray(col.offsets, dtype=np.int64), np.ascontiguousarray(col.terms, dtype=np.int32),
+                np.ascontiguousarray(col.weights, dtype=np.float32))
+
     def set_attr_sparse(self, attr: int, first: int, col) -> None:
         """The vectors of rows first..first+len(col)-1 of sparse column ``attr`` (``col``: a ``where.SparseColumn``)."""
         offsets, terms, weights, present = self._sparse_csr(col)
         self._check(self._lib.mlvdb_sparse_set(self._h, int(attr), int(first), present.size, offsets.ctypes.data,
-                                               terms.ctypes.data if terms.size else None,
-                                               weights.ctypes.data if weights.size else None, present.ctypes.data),
-                    "sparse_set")
+                                               _nonempty(terms), _nonempty(weights), present.ctypes.data), "sparse_set")
 
     def set_attr_sparse_at(self, attr: int, labels: np.ndarray, col) -> int:
         """Vector i of ``col`` -> row ``labels[i]`` (distinct labels in [0, total); tombstoned rows are skipped); returns the
@@ -436,9 +468,8 @@ class HipScanEngine:
             raise RuntimeError(f"{labels.size} labels but {present.size} vectors")
         n = C.c_int64(0)
         self._check(self._lib.mlvdb_sparse_set_at(self._h, int(attr), labels.ctypes.data, labels.size, offsets.ctypes.data,
-                                                  terms.ctypes.data if terms.size else None,
-                                                  weights.ctypes.data if weights.size else None, present.ctypes.data,
-                                                  C.byref(n)), "sparse_set_at")
+                                                  _nonempty(terms), _nonempty(weights), present.ctypes.data, C.byref(n)),
+                    "sparse_set_at")
         return int(n.value)
 
     def get_attr_sparse(self, attr: int, first: int, n: int):
@@ -452,10 +483,9 @@ class HipScanEngine:
         weights = np.empty(0, dtype=np.float32)
         needed = C.c_int64(0)
         for _ in range(2):  # the first call sizes the entries, the second reads them
-            self._check(self._lib.mlvdb_sparse_get(self._h, int(attr), int(first), n, offsets.ctypes.data,
-                                                   terms.ctypes.data if terms.size else None,
-                                                   weights.ctypes.data if weights.size else None, present.ctypes.data,
-                                                   terms.size, C.byref(needed)), "sparse_get")
+            self._check(self._lib.mlvdb_sparse_get(self._h, int(attr), int(first), n, offsets.ctypes.data, _nonempty(terms),
+                                                   _nonempty(weights), present.ctypes.data, terms.size, C.byref(needed)),
+                        "sparse_get")
             if needed.value <= terms.size:
                 break
             terms = np.empty(needed.value, dtype=np.int32)
@@ -467,24 +497,15 @@ class HipScanEngine:
         ignored: every query is one, an empty one ranks by label), ``where`` a compiled filter or ``None``.  Returns
         (labels int64 [nq, k] padded -1, scores float32 [nq, k] padded -inf, counts int32 [nq], scores float64 [nq, k]):
         the rows with a vector ranked by (inner product descending, label ascending)."""
-        offsets = np.ascontiguousarray(queries.offsets, dtype=np.int64)
-        terms = np.ascontiguousarray(queries.terms, dtype=np.int32)
-        weights = np.ascontiguousarray(queries.weights, dtype=np.float32)
+        offsets, terms, weights = self._sparse_arrays(queries)
         nq, k = offsets.size - 1, int(k)
         if nq < 0 or terms.size != weights.size:
             raise RuntimeError(f"{offsets.size} offsets, {terms.size} terms and {weights.size} weights")
-        shape = (nq, max(k, 0))
-        labels = np.empty(shape, dtype=np.int64)
-        score = np.empty(shape, dtype=np.float32)
-        score64 = np.empty(shape, dtype=np.float64)
-        counts = np.zeros(nq, dtype=np.int32)
-        w, keep = self._where(where) if where is not None else (None, None)
-        self._check(self._lib.mlvdb_search_batch_sparse(self._h, int(attr), offsets.ctypes.data,
-                                                        terms.ctypes.data if terms.size else None,
-                                                        weights.ctypes.data if weights.size else None, nq, k,
-                                                        None if w is None else C.byref(w), labels.ctypes.data,
-                                                        score.ctypes.data, counts.ctypes.data, score64.ctypes.data),
-                    "search_batch_sparse")
+        labels, score, counts, score64 = self._knn_outputs((nq, max(k, 0)), True)
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_search_batch_sparse(
+            self._h, int(attr), offsets.ctypes.data, _nonempty(terms), _nonempty(weights), nq, k, w, labels.ctypes.data,
+            score.ctypes.data, counts.ctypes.data, score64.ctypes.data), "search_batch_sparse")
         return labels, score, counts, score64
 
     # -- hybrid search (include/mlvdb_hybrid.h) -------------------------------------------
@@ -497,14 +518,10 @@ class HipScanEngine:
         Returns (labels int64 [nq, k] padded -1, fused float64 [nq, k] padded -inf, counts int32 [nq]) and, with
         ``components``, (dist64, sparse64, rank_dense, rank_sparse) behind them: each hit's completed components and its
         position in the two candidate lists (-1: not in that list)."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         if method not in _native.FUSE_CODES:
             raise RuntimeError(f"unknown fusion method {method!r} (one of {sorted(_native.FUSE_CODES)})")
-        offsets = np.ascontiguousarray(sparse_queries.offsets, dtype=np.int64)
-        terms = np.ascontiguousarray(sparse_queries.terms, dtype=np.int32)
-        wts = np.ascontiguousarray(sparse_queries.weights, dtype=np.float32)
+        offsets, terms, wts = self._sparse_arrays(sparse_queries)
         nq, k = queries.shape[0], int(k)
         if offsets.size != nq + 1 or terms.size != wts.size:
             raise RuntimeError(f"{nq} dense queries but {offsets.size} offsets, {terms.size} terms and {wts.size} weights")
@@ -516,14 +533,12 @@ class HipScanEngine:
         s64 = np.empty(shape, dtype=np.float64) if components else None
         rd = np.empty(shape, dtype=np.int32) if components else None
         rs = np.empty(shape, dtype=np.int32) if components else None
-        w, keep = self._where(where) if where is not None else (None, None)
+        w, keep = self._where_arg(where)
         self._check(self._lib.mlvdb_search_batch_hybrid(
-            self._h, queries.ctypes.data, int(attr), offsets.ctypes.data, terms.ctypes.data if terms.size else None,
-            wts.ctypes.data if wts.size else None, nq, k, int(fetch_dense), int(fetch_sparse), _native.FUSE_CODES[method],
-            float(weights[0]), float(weights[1]), float(rrf_k), None if w is None else C.byref(w), labels.ctypes.data,
-            fused.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
-            None if s64 is None else s64.ctypes.data, None if rd is None else rd.ctypes.data,
-            None if rs is None else rs.ctypes.data), "search_batch_hybrid")
+            self._h, queries.ctypes.data, int(attr), offsets.ctypes.data, _nonempty(terms), _nonempty(wts), nq, k,
+            int(fetch_dense), int(fetch_sparse), _native.FUSE_CODES[method], float(weights[0]), float(weights[1]),
+            float(rrf_k), w, labels.ctypes.data, fused.ctypes.data, counts.ctypes.data, _opt(d64), _opt(s64), _opt(rd),
+            _opt(rs)), "search_batch_hybrid")
         return (labels, fused, counts, d64, s64, rd, rs) if components else (labels, fused, counts)
 
     # -- per-query filters (include/mlvdb_where_each.h) -------------------------------
@@ -560,31 +575,23 @@ class HipScanEngine:
         One native call per chunk of at most 64 programs / 1024 ops (``where.chunk_programs``)."""
         from .where import chunk_programs
 
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         of = np.ascontiguousarray(program_of_query, dtype=np.int32)
         nq = queries.shape[0]
         if of.shape != (nq,):
             raise RuntimeError(f"program_of_query: {of.shape}, expected ({nq},)")
-        labels = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.int32)
-        d64 = np.empty((nq, k), dtype=np.float64) if want64 else None
+        labels, dist, counts, d64 = self._knn_outputs((nq, k), want64)
         routes = np.zeros(len(programs), dtype=np.int32)
         start = 0
         for idx, chunk, local in chunk_programs(list(programs), of):
             n = idx.size
             q = np.ascontiguousarray(queries[idx])
-            lab = np.empty((n, k), dtype=np.int64)
-            dst = np.empty((n, k), dtype=np.float32)
-            cnt = np.empty(n, dtype=np.int32)
-            l64 = np.empty((n, k), dtype=np.float64) if want64 else None
+            lab, dst, cnt, l64 = self._knn_outputs((n, k), want64)
             rts = np.zeros(max(len(chunk), 1), dtype=np.int32)
             arr, keep = self._where_array(chunk)
             self._check(self._lib.mlvdb_search_batch_where_each(
                 self._h, q.ctypes.data, n, int(k), arr, len(chunk), local.ctypes.data, lab.ctypes.data, dst.ctypes.data,
-                cnt.ctypes.data, None if l64 is None else l64.ctypes.data, rts.ctypes.data), "search_batch_where_each")
+                cnt.ctypes.data, _opt(l64), rts.ctypes.data), "search_batch_where_each")
             labels[idx], dist[idx], counts[idx] = lab, dst, cnt
             if want64:
                 d64[idx] = l64
@@ -601,20 +608,14 @@ class HipScanEngine:
         values (0 = unknown), which only lets a query stop early; ``where`` (optional, a compiled ``where.Program``)
         restricts the rows first.  Returns (labels int64 [nq, k], dist float32, counts int32, groups int64 [nq, k]) or,
         with ``want64``, (labels, dist, counts, dist64, groups); padding is label -1 / +inf / group INT64_MIN."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         nq = queries.shape[0]
-        labels = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.int32)
+        labels, dist, counts, d64 = self._knn_outputs((nq, k), want64)
         groups = np.empty((nq, k), dtype=np.int64)
-        d64 = np.empty((nq, k), dtype=np.float64) if want64 else None
-        w, keep = self._where(where) if where is not None else (None, None)
+        w, keep = self._where_arg(where)
         self._check(self._lib.mlvdb_search_batch_distinct(
-            self._h, queries.ctypes.data, nq, int(k), int(attr), int(max_groups), None if w is None else C.byref(w),
-            labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
-            groups.ctypes.data), "search_batch_distinct")
+            self._h, queries.ctypes.data, nq, int(k), int(attr), int(max_groups), w, labels.ctypes.data, dist.ctypes.data,
+            counts.ctypes.data, _opt(d64), groups.ctypes.data), "search_batch_distinct")
         return (labels, dist, counts, d64, groups) if want64 else (labels, dist, counts, groups)
 
     # -- grouped kNN (include/mlvdb_grouped.h) --------------------------------------------
@@ -625,22 +626,16 @@ class HipScanEngine:
         Returns (labels int64 [nq, k, group_size], dist float32, counts int32 [nq]: groups returned, group_counts int32
         [nq, k]: rows returned per group, groups int64 [nq, k]) or, with ``want64``, (labels, dist, counts, group_counts,
         dist64, groups); padding is label -1 / +inf / group count 0 / group INT64_MIN."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         nq, k, g = queries.shape[0], int(k), int(group_size)
         shape = (nq, max(k, 0), max(g, 0))
-        labels = np.empty(shape, dtype=np.int64)
-        dist = np.empty(shape, dtype=np.float32)
-        counts = np.empty(nq, dtype=np.int32)
+        labels, dist, counts, d64 = self._knn_outputs(shape, want64)
         group_counts = np.empty(shape[:2], dtype=np.int32)
         groups = np.empty(shape[:2], dtype=np.int64)
-        d64 = np.empty(shape, dtype=np.float64) if want64 else None
-        w, keep = self._where(where) if where is not None else (None, None)
+        w, keep = self._where_arg(where)
         self._check(self._lib.mlvdb_search_batch_grouped(
-            self._h, queries.ctypes.data, nq, k, g, int(attr), int(max_groups), None if w is None else C.byref(w),
-            labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, group_counts.ctypes.data,
-            None if d64 is None else d64.ctypes.data, groups.ctypes.data), "search_batch_grouped")
+            self._h, queries.ctypes.data, nq, k, g, int(attr), int(max_groups), w, labels.ctypes.data, dist.ctypes.data,
+            counts.ctypes.data, group_counts.ctypes.data, _opt(d64), groups.ctypes.data), "search_batch_grouped")
         return ((labels, dist, counts, group_counts, d64, groups) if want64
                 else (labels, dist, counts, group_counts, groups))
 
@@ -652,21 +647,15 @@ class HipScanEngine:
         to the better-ranked candidate.  Returns (labels int64 [nq, k], dist float32, counts int32, dist64 float64 or
         ``None`` without ``want64``, rank int32 [nq, k]: the pick's position among the candidates, objective float64
         [nq, k]), all in pick order; padding is label -1 / +inf / rank -1 / objective +inf."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         nq = queries.shape[0]
-        labels = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.int32)
-        d64 = np.empty((nq, k), dtype=np.float64) if want64 else None
+        labels, dist, counts, d64 = self._knn_outputs((nq, k), want64)
         rank = np.empty((nq, k), dtype=np.int32)
         objective = np.empty((nq, k), dtype=np.float64)
-        w, keep = self._where(where) if where is not None else (None, None)
+        w, keep = self._where_arg(where)
         self._check(self._lib.mlvdb_search_batch_mmr(
-            self._h, queries.ctypes.data, nq, int(k), int(fetch_k), float(lam), None if w is None else C.byref(w),
-            labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
-            rank.ctypes.data, objective.ctypes.data), "search_batch_mmr")
+            self._h, queries.ctypes.data, nq, int(k), int(fetch_k), float(lam), w, labels.ctypes.data, dist.ctypes.data,
+            counts.ctypes.data, _opt(d64), rank.ctypes.data, objective.ctypes.data), "search_batch_mmr")
         return labels, dist, counts, d64, rank, objective
 
     # -- search by stored examples (include/mlvdb_like.h) -----------------------------------
@@ -692,17 +681,13 @@ class HipScanEngine:
             if base.shape != (nq, self.dim):
                 raise RuntimeError(f"Wrong dimensionality of the vectors: got {base.shape}, index dim {self.dim}, {nq} queries")
         k = int(k)
-        out_labels = np.empty((nq, max(k, 0)), dtype=np.int64)
-        dist = np.empty((nq, max(k, 0)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.int32)
-        d64 = np.empty((nq, max(k, 0)), dtype=np.float64) if want64 else None
+        out_labels, dist, counts, d64 = self._knn_outputs((nq, max(k, 0)), want64)
         queries = np.empty((nq, self.dim), dtype=np.float32) if want_queries else None
-        w, keep = self._where(where) if where is not None else (None, None)
+        w, keep = self._where_arg(where)
         self._check(self._lib.mlvdb_search_batch_like(
-            self._h, ex_labels.ctypes.data, ex_weights.ctypes.data, ex_offsets.ctypes.data,
-            None if base is None else base.ctypes.data, nq, k, 1 if exclude else 0, None if w is None else C.byref(w),
-            out_labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, None if d64 is None else d64.ctypes.data,
-            None if queries is None else queries.ctypes.data), "search_batch_like")
+            self._h, ex_labels.ctypes.data, ex_weights.ctypes.data, ex_offsets.ctypes.data, _opt(base), nq, k,
+            1 if exclude else 0, w, out_labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, _opt(d64), _opt(queries)),
+            "search_batch_like")
         return out_labels, dist, counts, d64, queries
 
     # -- late-interaction search (include/mlvdb_maxsim.h) -----------------------------------
@@ -716,27 +701,21 @@ class HipScanEngine:
         match_dist64 float64 [total tokens, k] or ``None``): row ``(offsets[i] + t, j)`` of the last two is the best row of
         query ``i``'s ``j``-th document for its token ``t`` and that pair's distance.  Padding is group INT64_MIN / +inf /
         label -1.  More than 2**20 documents raise ``MaxSimOverflow``."""
-        tokens = np.ascontiguousarray(tokens, dtype=np.float32)
-        if tokens.ndim != 2 or tokens.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {tokens.shape}, index dim {self.dim}")
+        tokens = self._queries(tokens)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
         if offsets.size < 1 or (offsets.size > 1 and offsets[-1] > tokens.shape[0]):
             raise RuntimeError(f"search_maxsim: {offsets.size} offsets ending at {int(offsets[-1]) if offsets.size else 0}, "
                                f"{tokens.shape[0]} tokens")
         nq, k = offsets.size - 1, int(k)
         ntok = int(offsets[-1]) if nq > 0 else 0
-        groups = np.empty((nq, max(k, 0)), dtype=np.int64)
-        score = np.empty((nq, max(k, 0)), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.int32)
-        score64 = np.empty((nq, max(k, 0)), dtype=np.float64)
+        groups, score, counts, score64 = self._knn_outputs((nq, max(k, 0)), True)
         match_labels = np.empty((ntok, max(k, 0)), dtype=np.int64) if want_matches else None
         match_d64 = np.empty((ntok, max(k, 0)), dtype=np.float64) if want_matches else None
-        w, keep = self._where(where) if where is not None else (None, None)
+        w, keep = self._where_arg(where)
         rc = self._check(self._lib.mlvdb_search_batch_maxsim(
-            self._h, tokens.ctypes.data, offsets.ctypes.data, nq, k, int(attr), None if w is None else C.byref(w),
-            groups.ctypes.data, score.ctypes.data, counts.ctypes.data, score64.ctypes.data,
-            None if match_labels is None else match_labels.ctypes.data,
-            None if match_d64 is None else match_d64.ctypes.data), "search_batch_maxsim", allow=(_native.ERR_OVERFLOW,))
+            self._h, tokens.ctypes.data, offsets.ctypes.data, nq, k, int(attr), w, groups.ctypes.data, score.ctypes.data,
+            counts.ctypes.data, score64.ctypes.data, _opt(match_labels), _opt(match_d64)), "search_batch_maxsim",
+            allow=(_native.ERR_OVERFLOW,))
         if rc == _native.ERR_OVERFLOW:
             raise MaxSimOverflow(_native.MAXSIM_MAX_GROUPS)
         return groups, score, counts, score64, match_labels, match_d64
@@ -746,17 +725,21 @@ class HipScanEngine:
         """The distinct present values of int64 column ``attr`` among the live rows (those the compiled ``where.Program``
         matches, when one is given) and how many rows hold each: (values int64 ascending, counts int64, matched, absent)
         with ``counts.sum() + absent == matched``.  More than ``max_values`` distinct values raise ``FacetOverflow``."""
+        return self._facet("facet_values", attr, max_values, where)
+
+    def _facet(self, entry: str, attr: int, max_values: int, where):
+        """``mlvdb_facet_values`` or ``mlvdb_facet_list_values``: the two take and return the same."""
         max_values = int(max_values)
         values = np.empty(max(0, min(max_values, _native.FACET_MAX_VALUES)), dtype=np.int64)
         counts = np.empty(values.size, dtype=np.int64)
-        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        w, keep = self._where(where) if where is not None else (None, None)
-        rc = self._check(self._lib.mlvdb_facet_values(
-            self._h, int(attr), None if w is None else C.byref(w), max_values, values.ctypes.data, counts.ctypes.data,
-            C.byref(n), C.byref(matched), C.byref(absent)), "facet_values", allow=(_native.ERR_OVERFLOW,))
+        n, matched, absent = self._tally()
+        w, keep = self._where_arg(where)
+        rc = self._check(getattr(self._lib, "mlvdb_" + entry)(
+            self._h, int(attr), w, max_values, values.ctypes.data, counts.ctypes.data, C.byref(n), C.byref(matched),
+            C.byref(absent)), entry, allow=(_native.ERR_OVERFLOW,))
         if rc == _native.ERR_OVERFLOW:
             raise FacetOverflow(max_values, int(n.value), int(matched.value), int(absent.value))
-        return values[: n.value].copy(), counts[: n.value].copy(), int(matched.value), int(absent.value)
+        return self._first(n, (values, counts), matched, absent)
 
     def facet_bins(self, attr: int, edges: np.ndarray, where=None):
         """Histogram of column ``attr`` over the strictly ascending ``edges`` (an int64 array for an int64 column, float64
@@ -770,10 +753,9 @@ class HipScanEngine:
             raise RuntimeError(f"attribute {attr} is an {kind} column, the edges are {edges.dtype.name}")
         counts = np.zeros(edges.size + 1, dtype=np.int64)
         matched, absent = C.c_int64(0), C.c_int64(0)
-        w, keep = self._where(where) if where is not None else (None, None)
-        self._check(self._lib.mlvdb_facet_bins(
-            self._h, int(attr), None if w is None else C.byref(w), edges.ctypes.data, int(edges.size), counts.ctypes.data,
-            C.byref(matched), C.byref(absent)), "facet_bins")
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_facet_bins(self._h, int(attr), w, edges.ctypes.data, int(edges.size), counts.ctypes.data,
+                                               C.byref(matched), C.byref(absent)), "facet_bins")
         return counts, int(matched.value), int(absent.value)
 
     # -- attribute statistics (include/mlvdb_stats.h) ------------------------------------
@@ -790,15 +772,15 @@ class HipScanEngine:
         keys, rows, count, hi = (np.zeros(size, dtype=np.int64) for _ in range(4))
         lo = np.zeros(size, dtype=np.uint64)
         mn, mx = (np.zeros(size, dtype=np.float64 if kind == "float64" else np.int64) for _ in range(2))
-        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        w, keep = self._where(where) if where is not None else (None, None)
+        n, matched, absent = self._tally()
+        w, keep = self._where_arg(where)
         rc = self._check(self._lib.mlvdb_attr_stats(
-            self._h, int(attr), -1 if by is None else int(by), None if w is None else C.byref(w), max_groups,
-            keys.ctypes.data, rows.ctypes.data, count.ctypes.data, mn.ctypes.data, mx.ctypes.data, hi.ctypes.data,
-            lo.ctypes.data, C.byref(n), C.byref(matched), C.byref(absent)), "attr_stats", allow=(_native.ERR_OVERFLOW,))
+            self._h, int(attr), -1 if by is None else int(by), w, max_groups, keys.ctypes.data, rows.ctypes.data,
+            count.ctypes.data, mn.ctypes.data, mx.ctypes.data, hi.ctypes.data, lo.ctypes.data, C.byref(n), C.byref(matched),
+            C.byref(absent)), "attr_stats", allow=(_native.ERR_OVERFLOW,))
         if rc == _native.ERR_OVERFLOW:
             raise StatsOverflow(max_groups, int(n.value), int(matched.value), int(absent.value))
-        return tuple(a[: n.value].copy() for a in (keys, rows, count, mn, mx, hi, lo)) + (int(matched.value), int(absent.value))
+        return self._first(n, (keys, rows, count, mn, mx, hi, lo), matched, absent)
 
     # -- ordered metadata queries (include/mlvdb_order.h) -------------------------------
     def where_ordered(self, attr: int, limit: int, where=None, descending: bool = False, offset: int = 0):
@@ -811,12 +793,12 @@ class HipScanEngine:
         size = max(0, min(limit, _native.ORDER_MAX_ROWS))
         labels = np.empty(size, dtype=np.int64)
         values = np.empty(size, dtype=np.float64 if kind == "float64" else np.int64)
-        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        w, keep = self._where(where) if where is not None else (None, None)
+        n, matched, absent = self._tally()
+        w, keep = self._where_arg(where)
         self._check(self._lib.mlvdb_where_ordered(
-            self._h, int(attr), 1 if descending else 0, None if w is None else C.byref(w), offset, limit,
-            labels.ctypes.data, values.ctypes.data, C.byref(n), C.byref(matched), C.byref(absent)), "where_ordered")
-        return labels[: n.value].copy(), values[: n.value].copy(), int(matched.value), int(absent.value)
+            self._h, int(attr), 1 if descending else 0, w, offset, limit, labels.ctypes.data, values.ctypes.data, C.byref(n),
+            C.byref(matched), C.byref(absent)), "where_ordered")
+        return self._first(n, (labels, values), matched, absent)
 
     # -- nearest by distance on a geo column (include/mlvdb_geo.h) ----------------------
     def geo_nearest(self, attr: int, center: int, limit: int, where=None, offset: int = 0):
@@ -829,12 +811,12 @@ class HipScanEngine:
         labels = np.empty(size, dtype=np.int64)
         points = np.empty(size, dtype=np.int64)
         dist = np.empty(size, dtype=np.float64)
-        n, matched, absent = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        w, keep = self._where(where) if where is not None else (None, None)
+        n, matched, absent = self._tally()
+        w, keep = self._where_arg(where)
         self._check(self._lib.mlvdb_geo_nearest(
-            self._h, int(attr), int(center), None if w is None else C.byref(w), offset, limit, labels.ctypes.data,
-            points.ctypes.data, dist.ctypes.data, C.byref(n), C.byref(matched), C.byref(absent)), "geo_nearest")
-        return labels[: n.value].copy(), points[: n.value].copy(), dist[: n.value].copy(), int(matched.value), int(absent.value)
+            self._h, int(attr), int(center), w, offset, limit, labels.ctypes.data, points.ctypes.data, dist.ctypes.data,
+            C.byref(n), C.byref(matched), C.byref(absent)), "geo_nearest")
+        return self._first(n, (labels, points, dist), matched, absent)
 
     def search64(self, queries: np.ndarray, k: int, mask: np.ndarray | None = None, where=None):
         """kNN; ``mask`` (optional, one byte per row, non-zero = allowed) restricts the search to those rows, ``where``
@@ -848,30 +830,23 @@ class HipScanEngine:
         return self._search(queries, k, mask, False, where)
 
     def _search(self, queries: np.ndarray, k: int, mask, want64: bool, where=None):
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         nq = queries.shape[0]
-        labels = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
-        counts = np.empty(nq, dtype=np.int32)
-        d64 = np.empty((nq, k), dtype=np.float64) if want64 else None
+        labels, dist, counts, d64 = self._knn_outputs((nq, k), want64)
         if where is not None:
             if mask is not None:
                 raise RuntimeError("search: give a row mask or a where program, not both")
             w, keep = self._where(where)
             self._check(self._lib.mlvdb_search_batch_where(self._h, queries.ctypes.data, nq, int(k), C.byref(w),
-                                                           labels.ctypes.data, dist.ctypes.data, counts.ctypes.data,
-                                                           None if d64 is None else d64.ctypes.data), "search_batch_where")
+                                                           labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, _opt(d64)),
+                        "search_batch_where")
             return (labels, dist, counts, d64) if want64 else (labels, dist, counts)
         if mask is not None:
             mask = np.ascontiguousarray(mask, dtype=np.uint8)
             if mask.shape != (self.counts()[0],):
                 raise RuntimeError(f"row mask has shape {mask.shape}, the index holds {self.counts()[0]} rows")
-        self._check(self._lib.mlvdb_search_batch_ex(self._h, queries.ctypes.data, nq, int(k),
-                                                    None if mask is None else mask.ctypes.data, labels.ctypes.data,
-                                                    dist.ctypes.data, counts.ctypes.data,
-                                                    None if d64 is None else d64.ctypes.data), "search_batch")
+        self._check(self._lib.mlvdb_search_batch_ex(self._h, queries.ctypes.data, nq, int(k), _opt(mask), labels.ctypes.data,
+                                                    dist.ctypes.data, counts.ctypes.data, _opt(d64)), "search_batch")
         return (labels, dist, counts, d64) if want64 else (labels, dist, counts)
 
     def search_device(self, q_ptr: int, nq: int, k: int, labels_ptr: int, dist_ptr: int, counts_ptr: int,
@@ -896,11 +871,9 @@ class HipScanEngine:
         hold the hits and nothing else (a first call with room for 256 hits per query on average; when the hits need
         more, the call is repeated with the size the first one reported).  ``where`` (optional, a compiled ``where.Program``)
         restricts the hits to the rows it matches (``mlvdb_range_batch_packed_where``)."""
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         nq = queries.shape[0]
-        w, keep = self._where(where) if where is not None else (None, None)
+        w, keep = self._where_arg(where)
 
         def call(capacity, total, labels, dist, offsets, counts):
             if w is None:
@@ -908,8 +881,8 @@ class HipScanEngine:
                                                           labels.ctypes.data, dist.ctypes.data, offsets.ctypes.data,
                                                           counts.ctypes.data)
             return self._lib.mlvdb_range_batch_packed_where(self._h, queries.ctypes.data, nq, float(radius), capacity, total,
-                                                            C.byref(w), labels.ctypes.data, dist.ctypes.data,
-                                                            offsets.ctypes.data, counts.ctypes.data)
+                                                            w, labels.ctypes.data, dist.ctypes.data, offsets.ctypes.data,
+                                                            counts.ctypes.data)
 
         return RangeHits(*self._range_packed(call, nq, capacity, truncate))
 
@@ -945,9 +918,7 @@ class HipScanEngine:
         stitched in query order."""
         from .where import chunk_programs
 
-        queries = np.ascontiguousarray(queries, dtype=np.float32)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise RuntimeError(f"Wrong dimensionality of the vectors: got {queries.shape}, index dim {self.dim}")
+        queries = self._queries(queries)
         of = np.ascontiguousarray(program_of_query, dtype=np.int32)
         nq = queries.shape[0]
         if of.shape != (nq,):

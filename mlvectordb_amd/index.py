@@ -274,8 +274,8 @@ class Index:
         # attributes={"genre": "str", "year": "int", ...}: per-row metadata columns in HBM, filtered on the device (where.py);
         # attribute i (declaration order) is the engine's column i
         self._attributes: Dict[str, str] = self._check_schema(attributes or {})
-        if self._attributes and self._devices is not None and len(self._devices) > 1:
-            raise ValueError("attributes= is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        if self._attributes:
+            self._refuse_sharded("attributes=")
 
     @staticmethod
     def _check_schema(attributes: Mapping[str, str]) -> Dict[str, str]:
@@ -330,8 +330,7 @@ class Index:
                 raise ValueError(f"this index declares no attributes (got {sorted(columns)})")
             return {}, None
         for name in columns:
-            if name not in self._attributes:
-                raise ValueError(f"{name!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+            self._declared(name)
         ns = self._ns.get(namespace)
         strings = {name: dict(codes) for name, codes in (ns.strings if ns is not None else {}).items()}
         out = {}
@@ -357,19 +356,98 @@ class Index:
                 out[i] = col
         return out, strings
 
+    # ------------------------------------------------------------------ what the entry families share
+    # Each refusal takes ``what``, the words its message starts with; the entries call them in the order they refuse in.
+    def _refuse_sharded(self, what: str) -> None:
+        if self._devices is not None and len(self._devices) > 1:
+            raise ValueError(f"{what} is not supported on a row-sharded index (devices=[...] with more than one entry)")
+
+    def _declared(self, name, what: str = "") -> str:
+        """The type of the declared attribute ``name``."""
+        if not isinstance(name, str) or name not in self._attributes:
+            raise ValueError(f"{what}{name!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        return self._attributes[name]
+
+    def _column(self, name: str) -> int:
+        """The engine's column of the declared attribute ``name``."""
+        return list(self._attributes).index(name)
+
     @staticmethod
-    def _list_engine(ns: _Namespace, method: str):
+    def _engine_entry(ns: _Namespace, method: str, subject: str, named: Optional[str] = None):
+        """The engine's ``method``; ``subject`` is who asks ("top_by needs", "list attributes need")."""
         fn = getattr(ns.engine, method, None)
         if fn is None:
-            raise ValueError(f"list attributes need an engine with {method} (a single-device namespace)")
+            raise ValueError(f"{subject} an engine with {named or method} (a single-device namespace)")
         return fn
 
     @staticmethod
-    def _sparse_engine(ns: _Namespace, method: str):
-        fn = getattr(ns.engine, method, None)
-        if fn is None:
-            raise ValueError(f"sparse attributes need an engine with {method} (a single-device namespace)")
-        return fn
+    def _one_filter(what: str, where) -> None:
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"{what}: where must be one dict filter or None (got {type(where).__name__})")
+
+    @staticmethod
+    def _no_where_list(what: str, where, allowed_ids=None) -> None:
+        """The older families' form of ``_one_filter``: they name what they refuse and leave other types to ``_compile``."""
+        if isinstance(where, (list, tuple)):
+            raise ValueError(f"{what}: a per-query where list is not supported, give one dict filter")
+        if allowed_ids is not None:
+            raise ValueError(f"{what}: allowed_ids is not supported, give a dict where filter")
+
+    def _program(self, namespace: str, where) -> Optional["_where.Program"]:
+        return None if where is None else self._compile(namespace, where)
+
+    @staticmethod
+    def _nothing_to_search(ns: Optional[_Namespace], top_k=1, nq: int = 1, dim: Optional[int] = None) -> bool:
+        """The empty answer is due: no live row, no neighbour asked for, no query, or queries of another dimensionality."""
+        return ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or (dim is not None and dim != ns.dim)
+
+    @staticmethod
+    def _no_rows(ns: Optional[_Namespace]) -> bool:
+        """Nothing for a metadata query to read (tombstoned rows still count: the engine holds their columns)."""
+        return ns is None or ns.total == 0
+
+    @staticmethod
+    def _int_in(value, lo: int, hi: Optional[int] = None) -> bool:
+        """``value`` is an int, not a bool, in [lo, hi]."""
+        return (not isinstance(value, bool) and isinstance(value, (int, np.integer)) and lo <= value
+                and (hi is None or value <= hi))
+
+    def _check_window(self, what: str, limit, offset) -> None:
+        if not self._int_in(limit, 1):
+            raise ValueError(f"{what}: limit must be an int >= 1 (got {limit!r})")
+        if not self._int_in(offset, 0):
+            raise ValueError(f"{what}: offset must be an int >= 0 (got {offset!r})")
+        if int(offset) + int(limit) > self._MAX_ORDER_ROWS:
+            raise ValueError(f"{what}: offset + limit must be <= {self._MAX_ORDER_ROWS} (got {int(offset) + int(limit)})")
+
+    @staticmethod
+    def _group_bound(ns: _Namespace, name: str, kind: str, other: int) -> int:
+        """What the host knows about the number of values of attribute ``name``: the dictionary's size, two booleans,
+        ``other`` for integers."""
+        return len(ns.strings.get(name, {})) if kind in ("str", "str[]") else 2 if kind == "bool" else other
+
+    @staticmethod
+    def _decode_codes(ns: _Namespace, name: str, kind: str, codes: list) -> list:
+        """Column values of attribute ``name`` decoded: the strings of its dictionary, ``True`` / ``False``, ints."""
+        if kind in ("str", "str[]"):
+            known = ns.strings.get(name, {})
+            strings = sorted(known, key=known.get)  # code order
+            return [strings[c] for c in codes]
+        return [bool(c) for c in codes] if kind == "bool" else codes
+
+    @staticmethod
+    def _sparse_queries(queries: list, what: str) -> "_where.SparseColumn":
+        """Sparse query vectors as one column; query ``i`` is refused as ``{what} i``."""
+        offsets = np.zeros(len(queries) + 1, dtype=np.int64)
+        terms: List[int] = []
+        weights: List[float] = []
+        for i, q in enumerate(queries):
+            t, w = _where.encode_sparse_vector(q, f"{what} {i}", _where.SPARSE_MAX_QUERY_TERMS)
+            terms.extend(t)
+            weights.extend(w)
+            offsets[i + 1] = len(terms)
+        return _where.SparseColumn(offsets, np.array(terms, dtype=np.int32), np.array(weights, dtype=np.float32),
+                                   np.ones(len(queries), dtype=np.uint8))
 
     def _check_sparse(self, what: str, name: str) -> None:
         if _where.is_sparse(self._attributes[name]):
@@ -398,9 +476,9 @@ class Index:
         cols, strings = staged
         for i, col in cols.items():
             if isinstance(col, _where.ListColumn):
-                Index._list_engine(ns, "set_attr_list")(i, first, col)
+                Index._engine_entry(ns, "set_attr_list", "list attributes need")(i, first, col)
             elif isinstance(col, _where.SparseColumn):
-                Index._sparse_engine(ns, "set_attr_sparse")(i, first, col)
+                Index._engine_entry(ns, "set_attr_sparse", "sparse attributes need")(i, first, col)
             else:
                 ns.engine.set_attr(i, first, col)
         if strings is not None:
@@ -644,17 +722,13 @@ class Index:
             raise ValueError("search_many: give allowed_ids or where, not both")
         if isinstance(where, (list, tuple)):
             return self._search_many_each(queries, top_k, namespace, metric, where)
-        program = None if where is None else self._compile(namespace, where)
+        program = self._program(namespace, where)
         q = self._coerce_queries(queries)
         nq = q.shape[0]
         ns = self._ns.get(namespace)
-        if ns is None:
-            return BatchHits.empty(nq)
+        if self._nothing_to_search(ns, top_k, nq, q.shape[1]):
+            return BatchHits.empty(nq)  # (another dimensionality: the reference swallows the RuntimeError, index.py:110-119)
         active = ns.total - ns.deleted
-        if active <= 0 or top_k <= 0 or nq == 0:
-            return BatchHits.empty(nq)
-        if q.shape[1] != ns.dim:
-            return BatchHits.empty(nq)  # reference: RuntimeError swallowed at index.py:110-119
         mask = None
         if allowed_ids is not None:
             picked = ns.ids.lookup(allowed_ids)
@@ -680,62 +754,48 @@ class Index:
     def _search_many_distinct(self, queries, top_k: int, namespace: str, metric: str, allowed_ids, where,
                               distinct: str, group_size: Optional[int] = None) -> BatchHits:
         """``search_many`` with ``distinct=``: every refusal happens before the engine is touched."""
-        if group_size is not None and (isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer))
-                                       or not 1 <= group_size <= self._MAX_GROUP_SIZE):
+        if group_size is not None and not self._int_in(group_size, 1, self._MAX_GROUP_SIZE):
             raise ValueError(f"group_size must be an int in [1, {self._MAX_GROUP_SIZE}] (got {group_size!r})")
-        if self._devices is not None and len(self._devices) > 1:
-            raise ValueError("distinct= is not supported on a row-sharded index (devices=[...] with more than one entry)")
-        if distinct not in self._attributes:
-            raise ValueError(f"distinct: {distinct!r} is not a declared attribute of this index "
-                             f"(declared: {sorted(self._attributes)})")
+        self._refuse_sharded("distinct=")
+        kind = self._declared(distinct, "distinct: ")
         self._check_scalar("distinct", distinct)
-        kind = self._attributes[distinct]
         if kind == "float":
             raise ValueError(f"distinct: attribute {distinct!r} is a float column; groups need an int, str or bool attribute")
         if top_k > self._MAX_TOP_K_DISTINCT:
             raise ValueError(f"distinct: top_k must be <= {self._MAX_TOP_K_DISTINCT} (got {top_k})")
-        if isinstance(where, (list, tuple)):
-            raise ValueError("distinct: a per-query where list is not supported, give one dict filter")
-        if allowed_ids is not None:
-            raise ValueError("distinct: allowed_ids is not supported, give a dict where filter")
-        program = None if where is None else self._compile(namespace, where)
+        self._no_where_list("distinct", where, allowed_ids)
+        program = self._program(namespace, where)
         q = self._coerce_queries(queries)
         nq = q.shape[0]
         ns = self._ns.get(namespace)
         if group_size is not None:
             return self._search_many_grouped(q, top_k, ns, metric, program, distinct, kind, int(group_size))
-        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
+        if self._nothing_to_search(ns, top_k, nq, q.shape[1]):
             return BatchHits.empty(nq)
-        search_distinct = getattr(ns.engine, "search_distinct", None)
-        if search_distinct is None:
-            raise ValueError("distinct= needs an engine with search_distinct (a single-device namespace)")
+        search_distinct = self._engine_entry(ns, "search_distinct", "distinct= needs")
         k = min(int(top_k), ns.total - ns.deleted)
-        # what the host knows about the number of groups: the dictionary's size, two booleans, nothing for integers
-        max_groups = len(ns.strings.get(distinct, {})) if kind == "str" else 2 if kind == "bool" else 0
+        max_groups = self._group_bound(ns, distinct, kind, 0)  # (nothing is known about integers)
         if kind == "str" and max_groups == 0:
             return BatchHits(np.full((nq, k), -1, np.int64), self._scores(np.full((nq, k), np.inf, np.float32), metric),
                              np.zeros(nq, np.int32), ns.ids)  # no string was ever stored: every row is absent
-        attr = list(self._attributes).index(distinct)
-        labels, dist, counts, _ = search_distinct(q, k, attr, max_groups=max_groups, where=program)
+        labels, dist, counts, _ = search_distinct(q, k, self._column(distinct), max_groups=max_groups, where=program)
         return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
 
     def _search_many_grouped(self, q: np.ndarray, top_k: int, ns, metric: str, program, distinct: str, kind: str,
                              g: int) -> "GroupedBatchHits":
         """The validated ``distinct=`` call with ``group_size=``: the engine's [nq, k, g] answer compacted on the host."""
         nq = q.shape[0]
-        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
+        if self._nothing_to_search(ns, top_k, nq, q.shape[1]):
             return GroupedBatchHits.empty(nq)
-        search_grouped = getattr(ns.engine, "search_grouped", None)
-        if search_grouped is None:
-            raise ValueError("group_size= needs an engine with search_grouped (a single-device namespace)")
+        search_grouped = self._engine_entry(ns, "search_grouped", "group_size= needs")
         k = min(int(top_k), ns.total - ns.deleted)
-        max_groups = len(ns.strings.get(distinct, {})) if kind == "str" else 2 if kind == "bool" else 0
+        max_groups = self._group_bound(ns, distinct, kind, 0)
         if kind == "str" and max_groups == 0:  # no string was ever stored: every row is absent
             return GroupedBatchHits(np.full((nq, k * g), -1, np.int64),
                                     self._scores(np.full((nq, k * g), np.inf, np.float32), metric), np.zeros(nq, np.int32),
                                     ns.ids, np.zeros((nq, k), np.int32), np.full((nq, k), None, dtype=object))
-        attr = list(self._attributes).index(distinct)
-        labels, dist, ngroups, sizes, codes = search_grouped(q, k, g, attr, max_groups=max_groups, where=program)
+        labels, dist, ngroups, sizes, codes = search_grouped(q, k, g, self._column(distinct), max_groups=max_groups,
+                                                             where=program)
         # compaction: the valid slots of a query first, in their order (groups by rank, members in order), padding behind
         valid = (np.arange(g)[None, None, :] < sizes[:, :, None]).reshape(nq, k * g)
         order = np.argsort(~valid, axis=1, kind="stable")
@@ -752,13 +812,7 @@ class Index:
         nq, k = codes.shape
         values = np.full((nq, k), None, dtype=object)
         have = np.arange(k)[None, :] < ngroups[:, None]
-        if kind == "str":
-            words = {code: word for word, code in ns.strings[name].items()}
-            values[have] = [words[c] for c in codes[have].tolist()]
-        elif kind == "bool":
-            values[have] = [bool(c) for c in codes[have].tolist()]
-        else:
-            values[have] = codes[have].tolist()
+        values[have] = Index._decode_codes(ns, name, kind, codes[have].tolist())
         return values
 
     _MAX_TOP_K_LATE = 64    # MLVDB_MAX_TOPK: one selection list of a wavefront
@@ -790,23 +844,16 @@ class Index:
         the summed distance), the summed distance itself for "l2" / "ip"; "euclidean" is refused (a root does not
         distribute over the sum).  ``where`` (one dict filter) restricts the rows first; ``matches=True`` adds, per document
         and token, the matched row and its score.  Every refusal happens before the engine is touched."""
-        if self._devices is not None and len(self._devices) > 1:
-            raise ValueError("search_late is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        self._refuse_sharded("search_late")
         if metric == "euclidean":
             raise ValueError('search_late: metric "euclidean" is not supported (a root does not distribute over the sum), use "l2"')
-        if by not in self._attributes:
-            raise ValueError(f"search_late: {by!r} is not a declared attribute of this index "
-                             f"(declared: {sorted(self._attributes)})")
+        kind = self._declared(by, "search_late: ")
         self._check_scalar("search_late", by)
-        kind = self._attributes[by]
         if kind == "float":
             raise ValueError(f"search_late: attribute {by!r} is a float column; documents need an int, str or bool attribute")
         if top_k > self._MAX_TOP_K_LATE:
             raise ValueError(f"search_late: top_k must be <= {self._MAX_TOP_K_LATE} (got {top_k})")
-        if isinstance(where, (list, tuple)):
-            raise ValueError("search_late: a per-query where list is not supported, give one dict filter")
-        if allowed_ids is not None:
-            raise ValueError("search_late: allowed_ids is not supported, give a dict where filter")
+        self._no_where_list("search_late", where, allowed_ids)
         qs = self._late_queries(queries)
         lengths = [int(q.shape[0]) for q in qs]
         ns = self._ns.get(namespace)
@@ -816,20 +863,16 @@ class Index:
             if q.shape[1] != (ns.dim if ns is not None else qs[0].shape[1]):
                 raise ValueError(f"search_late: query {i} has token vectors of dim {q.shape[1]}, "
                                  f"expected {ns.dim if ns is not None else qs[0].shape[1]}")
-        program = None if where is None else self._compile(namespace, where)
-        nq = len(qs)
-        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0:
+        program = self._program(namespace, where)
+        if self._nothing_to_search(ns, top_k, len(qs)):
             return LateBatchHits.empty(lengths, 0, matches)
-        search_maxsim = getattr(ns.engine, "search_maxsim", None)
-        if search_maxsim is None:
-            raise ValueError("search_late needs an engine with search_maxsim (a single-device namespace)")
+        search_maxsim = self._engine_entry(ns, "search_maxsim", "search_late needs")
         k = min(int(top_k), ns.total - ns.deleted)
         if kind == "str" and not ns.strings.get(by):  # no string was ever stored: every row is absent
             return LateBatchHits.empty(lengths, k, matches)
-        attr = list(self._attributes).index(by)
         offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-        codes, _, counts, s64, m_lab, m_d64 = search_maxsim(np.concatenate(qs, axis=0), offsets, k, attr, where=program,
-                                                            want_matches=bool(matches))
+        codes, _, counts, s64, m_lab, m_d64 = search_maxsim(np.concatenate(qs, axis=0), offsets, k, self._column(by),
+                                                            where=program, want_matches=bool(matches))
         # the score rule, in fp64 from the fp64 sum: T_i - s is the sum of the tokens' cosines
         scores = np.asarray(lengths, np.float64)[:, None] - s64 if metric == "cosine" else s64.copy()
         scores[np.arange(k)[None, :] >= counts[:, None]] = np.inf
@@ -846,36 +889,21 @@ class Index:
         one included) is a candidate; ``where`` (one dict filter) restricts the rows first.  Per query the ``top_k`` rows
         with the largest inner product come back, ties to the earlier row; ``scores`` is the fp64 dot product.  ``top_k`` is
         clamped to the live row count and to 64.  Every refusal happens before the engine is touched."""
-        if self._devices is not None and len(self._devices) > 1:
-            raise ValueError("search_sparse is not supported on a row-sharded index (devices=[...] with more than one entry)")
-        if not isinstance(by, str) or by not in self._attributes:
-            raise ValueError(f"search_sparse: {by!r} is not a declared attribute of this index "
-                             f"(declared: {sorted(self._attributes)})")
-        if not _where.is_sparse(self._attributes[by]):
+        self._refuse_sharded("search_sparse")
+        if not _where.is_sparse(self._declared(by, "search_sparse: ")):
             raise ValueError(f"search_sparse: attribute {by!r} is a {self._attributes[by]} column; it needs a sparse attribute")
-        if where is not None and not isinstance(where, Mapping):
-            raise ValueError(f"search_sparse: where must be one dict filter or None (got {type(where).__name__})")
+        self._one_filter("search_sparse", where)
         if isinstance(queries, Mapping) or isinstance(queries, (str, bytes)):
             raise ValueError("search_sparse: queries is a sequence of sparse vectors (got one mapping: wrap it in a list)")
-        queries = list(queries)
-        offsets = np.zeros(len(queries) + 1, dtype=np.int64)
-        terms: List[int] = []
-        weights: List[float] = []
-        for i, q in enumerate(queries):
-            t, w = _where.encode_sparse_vector(q, f"search_sparse: query {i}", _where.SPARSE_MAX_QUERY_TERMS)
-            terms.extend(t)
-            weights.extend(w)
-            offsets[i + 1] = len(terms)
-        program = None if where is None else self._compile(namespace, where)
-        nq = len(queries)
+        col = self._sparse_queries(list(queries), "search_sparse: query")
+        program = self._program(namespace, where)
+        nq = col.present.size
         ns = self._ns.get(namespace)
-        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0:
+        if self._nothing_to_search(ns, top_k, nq):
             return BatchHits.empty(nq)
-        search = self._sparse_engine(ns, "search_batch_sparse")
+        search = self._engine_entry(ns, "search_batch_sparse", "sparse attributes need")
         k = min(int(top_k), ns.total - ns.deleted, self._MAX_TOP_K_SPARSE)
-        col = _where.SparseColumn(offsets, np.array(terms, dtype=np.int32), np.array(weights, dtype=np.float32),
-                                  np.ones(nq, dtype=np.uint8))
-        labels, _, counts, s64 = search(list(self._attributes).index(by), col, k, where=program)
+        labels, _, counts, s64 = search(self._column(by), col, k, where=program)
         return BatchHits(labels, s64, counts, ns.ids)
 
     _FUSIONS = ("rrf", "linear", "relative")  # MLVDB_FUSE_*
@@ -909,12 +937,8 @@ class Index:
         sparse list is the first ``fetch_k_sparse`` rows by label with score 0 -- a caller without a sparse query wants
         ``search_many``.  The fetch sizes are clamped to the live row count.  Every refusal happens before the engine is
         touched."""
-        if self._devices is not None and len(self._devices) > 1:
-            raise ValueError("search_hybrid is not supported on a row-sharded index (devices=[...] with more than one entry)")
-        if not isinstance(by, str) or by not in self._attributes:
-            raise ValueError(f"search_hybrid: {by!r} is not a declared attribute of this index "
-                             f"(declared: {sorted(self._attributes)})")
-        if not _where.is_sparse(self._attributes[by]):
+        self._refuse_sharded("search_hybrid")
+        if not _where.is_sparse(self._declared(by, "search_hybrid: ")):
             raise ValueError(f"search_hybrid: attribute {by!r} is a {self._attributes[by]} column; it needs a sparse attribute")
         if fusion not in self._FUSIONS:
             raise ValueError(f"search_hybrid: fusion must be one of {self._FUSIONS} (got {fusion!r})")
@@ -927,8 +951,7 @@ class Index:
             raise ValueError(f"search_hybrid: weights must be finite and >= 0 (got {weights!r})")
         if not (np.isfinite(c) and c >= 0):
             raise ValueError(f"search_hybrid: rrf_k must be finite and >= 0 (got {rrf_k!r})")
-        if where is not None and not isinstance(where, Mapping):
-            raise ValueError(f"search_hybrid: where must be one dict filter or None (got {type(where).__name__})")
+        self._one_filter("search_hybrid", where)
         if top_k > self._MAX_TOP_K_SPARSE:
             raise ValueError(f"search_hybrid: top_k must be <= {self._MAX_TOP_K_SPARSE} (got {top_k})")
         fetch_k = self._default_fetch_k(max(int(top_k), 0)) if fetch_k is None else int(fetch_k)
@@ -948,26 +971,15 @@ class Index:
             raise ValueError(f"search_hybrid: {nq} dense queries but {len(sparse_queries)} sparse queries")
         if not np.isfinite(q).all():
             raise ValueError("search_hybrid: a dense query holds a non-finite value (NaN / inf)")
-        offsets = np.zeros(nq + 1, dtype=np.int64)
-        terms: List[int] = []
-        wts: List[float] = []
-        for i, sq in enumerate(sparse_queries):
-            t, w = _where.encode_sparse_vector(sq, f"search_hybrid: sparse query {i}", _where.SPARSE_MAX_QUERY_TERMS)
-            terms.extend(t)
-            wts.extend(w)
-            offsets[i + 1] = len(terms)
-        program = None if where is None else self._compile(namespace, where)
+        col = self._sparse_queries(sparse_queries, "search_hybrid: sparse query")
+        program = self._program(namespace, where)
         ns = self._ns.get(namespace)
-        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
+        if self._nothing_to_search(ns, top_k, nq, q.shape[1]):
             return HybridBatchHits.empty(nq) if components else BatchHits.empty(nq)
-        search = getattr(ns.engine, "search_hybrid", None)
-        if search is None:
-            raise ValueError("search_hybrid needs an engine with search_hybrid (a single-device namespace)")
+        search = self._engine_entry(ns, "search_hybrid", "search_hybrid needs")
         active = ns.total - ns.deleted
         k = min(int(top_k), active)
-        col = _where.SparseColumn(offsets, np.array(terms, dtype=np.int32), np.array(wts, dtype=np.float32),
-                                  np.ones(nq, dtype=np.uint8))
-        out = search(q, list(self._attributes).index(by), col, k, min(fetch_k, active), min(fetch_k_sparse, active),
+        out = search(q, self._column(by), col, k, min(fetch_k, active), min(fetch_k_sparse, active),
                      method=fusion, weights=(w_dense, w_sparse), rrf_k=c, where=program, components=components)
         if not components:
             return BatchHits(out[0], out[1], out[2], ns.ids)
@@ -983,8 +995,7 @@ class Index:
     def _search_many_mmr(self, queries, top_k: int, namespace: str, metric: str, allowed_ids, where, distinct,
                          mmr_lambda, fetch_k) -> BatchHits:
         """``search_many`` with ``mmr_lambda=``: every refusal happens before the engine is touched."""
-        if self._devices is not None and len(self._devices) > 1:
-            raise ValueError("mmr_lambda= is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        self._refuse_sharded("mmr_lambda=")
         if distinct is not None:
             raise ValueError("mmr_lambda: distinct= cannot be combined with it, give one of the two")
         lam = float(mmr_lambda)
@@ -999,19 +1010,14 @@ class Index:
             raise ValueError(f"mmr_lambda: fetch_k must be <= {self._MAX_FETCH_K_MMR} (got {fetch_k})")
         if fetch_k < top_k:
             raise ValueError(f"mmr_lambda: fetch_k must be >= top_k (got fetch_k={fetch_k}, top_k={top_k})")
-        if isinstance(where, (list, tuple)):
-            raise ValueError("mmr_lambda: a per-query where list is not supported, give one dict filter")
-        if allowed_ids is not None:
-            raise ValueError("mmr_lambda: allowed_ids is not supported, give a dict where filter")
-        program = None if where is None else self._compile(namespace, where)
+        self._no_where_list("mmr_lambda", where, allowed_ids)
+        program = self._program(namespace, where)
         q = self._coerce_queries(queries)
         nq = q.shape[0]
         ns = self._ns.get(namespace)
-        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or q.shape[1] != ns.dim:
+        if self._nothing_to_search(ns, top_k, nq, q.shape[1]):
             return BatchHits.empty(nq)
-        search_mmr = getattr(ns.engine, "search_mmr", None)
-        if search_mmr is None:
-            raise ValueError("mmr_lambda= needs an engine with search_mmr (a single-device namespace)")
+        search_mmr = self._engine_entry(ns, "search_mmr", "mmr_lambda= needs")
         active = ns.total - ns.deleted
         k = min(int(top_k), active)  # as search_many clamps top_k (the reference clamps to the live count)
         fetch = min(fetch_k, active)  # (>= k: fetch_k >= top_k)
@@ -1057,10 +1063,8 @@ class Index:
         examples never come back among its hits; at most 64 examples per query and ``top_k`` + examples <= 1024.  ``where``
         (one dict filter) restricts the rows searched, not the examples.  Every refusal happens before the engine is
         touched; hits and scores are otherwise those of ``search_many`` for the same query vectors."""
-        if self._devices is not None and len(self._devices) > 1:
-            raise ValueError("search_like is not supported on a row-sharded index (devices=[...] with more than one entry)")
-        if isinstance(where, (list, tuple)):
-            raise ValueError("search_like: a per-query where list is not supported, give one dict filter")
+        self._refuse_sharded("search_like")
+        self._no_where_list("search_like", where)
         if weights is not None and negative is not None:
             raise ValueError("search_like: weights= gives every example its own number and cannot be combined with negative=")
         pos = self._like_groups(positive, "positive")
@@ -1089,20 +1093,18 @@ class Index:
         most = max((len(set(e)) for e in examples), default=0)
         if top_k + most > self._MAX_LIKE_FETCH:
             raise ValueError(f"search_like: top_k + examples must be <= {self._MAX_LIKE_FETCH} (got {top_k} + {most})")
-        program = None if where is None else self._compile(namespace, where)
+        program = self._program(namespace, where)
         base = None if queries is None else self._coerce_queries(queries)
         if base is not None and base.shape[0] != nq:
             raise ValueError(f"search_like: {nq} positive entries, {base.shape[0]} queries")
         ns = self._ns.get(namespace)
-        if ns is None or ns.total - ns.deleted <= 0 or top_k <= 0 or nq == 0 or (base is not None and base.shape[1] != ns.dim):
+        if self._nothing_to_search(ns, top_k, nq, None if base is None else base.shape[1]):
             return BatchHits.empty(nq)
         flat = [u for e in examples for u in e]
         labels = ns.ids.lookup(flat) if flat else np.zeros(0, np.int64)
         if (labels < 0).any():
             raise ValueError(f"search_like: id {flat[int(np.argmax(labels < 0))]} is unknown or removed in namespace {namespace!r}")
-        search_like = getattr(ns.engine, "search_like", None)
-        if search_like is None:
-            raise ValueError("search_like needs an engine with search_like (a single-device namespace)")
+        search_like = self._engine_entry(ns, "search_like", "search_like needs")
         offsets = np.concatenate([[0], np.cumsum([len(e) for e in examples])]).astype(np.int64)
         k = min(int(top_k), ns.total - ns.deleted)  # as search_many clamps top_k (the reference clamps to the live count)
         out_labels, dist, counts = search_like(labels, np.asarray(per_example, np.float64), offsets, k, base=base,
@@ -1124,21 +1126,13 @@ class Index:
             raise ValueError(f"search_many: {len(wheres)} per-query filters for {nq} queries")
         programs, of = self._compile_each(namespace, wheres)
         ns = self._ns.get(namespace)
-        if ns is None:
+        if self._nothing_to_search(ns, top_k, nq, q.shape[1]):
             return BatchHits.empty(nq)
-        active = ns.total - ns.deleted
-        if active <= 0 or top_k <= 0 or nq == 0:
-            return BatchHits.empty(nq)
-        if q.shape[1] != ns.dim:
-            return BatchHits.empty(nq)
-        k = min(int(top_k), active, self._MAX_TOP_K)  # as a single-dict call clamps it
+        k = min(int(top_k), ns.total - ns.deleted, self._MAX_TOP_K)  # as a single-dict call clamps it
         if not programs:
             labels, dist, counts = self._search_engine(ns, q, k)
         else:
-            search_each = getattr(ns.engine, "search_each", None)
-            if search_each is None:
-                raise ValueError("per-query filters need an engine with search_each (a single-device namespace)")
-            labels, dist, counts = search_each(q, k, programs, of)
+            labels, dist, counts = self._engine_entry(ns, "search_each", "per-query filters need")(q, k, programs, of)
         return BatchHits(labels, self._scores(dist, metric), counts, ns.ids)
 
     def search_stream(self, batches, top_k: int, namespace: str, metric: str):
@@ -1148,12 +1142,11 @@ class Index:
         (``MultiDeviceEngine.search_stream``); on a single engine a worker thread runs the next ``search_many`` (the ctypes
         call holds no GIL) while the caller consumes the current one.  The namespace must not be mutated meanwhile."""
         ns = self._ns.get(namespace)
-        active = 0 if ns is None else ns.total - ns.deleted
-        if ns is None or active <= 0 or top_k <= 0:
+        if self._nothing_to_search(ns, top_k):
             for q in batches:
                 yield BatchHits.empty(self._coerce_queries(q).shape[0])
             return
-        k = min(int(top_k), active, self._MAX_TOP_K)
+        k = min(int(top_k), ns.total - ns.deleted, self._MAX_TOP_K)
         stream = getattr(ns.engine, "search_stream", None)
         if stream is not None:
             ok = []  # per batch: the query count if it could not be scanned (wrong dimensionality), else None
@@ -1205,7 +1198,7 @@ class Index:
         namespace."""
         program = self._compile(namespace, where)
         ns = self._ns.get(namespace)
-        return 0 if ns is None or ns.total == 0 else ns.engine.where_count(program)
+        return 0 if self._no_rows(ns) else ns.engine.where_count(program)
 
     def count_many(self, namespace: str, wheres: Sequence[Mapping]) -> List[int]:
         """``count`` of each dict filter of ``wheres``, all evaluated in one pass over the columns per native call."""
@@ -1214,7 +1207,7 @@ class Index:
             raise ValueError("count_many: every entry must be a dict filter")
         programs, of = self._compile_each(namespace, wheres)
         ns = self._ns.get(namespace)
-        if ns is None or ns.total == 0 or not programs:
+        if self._no_rows(ns) or not programs:
             return [0] * len(wheres)
         counts = np.asarray(ns.engine.count_each(programs), dtype=np.int64)
         return [int(counts[j]) for j in of]
@@ -1229,18 +1222,11 @@ class Index:
             return self.top_by(namespace, order_by, limit, where, descending=descending, offset=offset)["ids"]
         program = self._compile(namespace, where)
         ns = self._ns.get(namespace)
-        if ns is None or ns.total == 0:
+        if self._no_rows(ns):
             return []
         return ns.ids.uuids_at(ns.engine.where_labels(program)).tolist()
 
     # ------------------------------------------------------------------ additive: updates and deletes on the device
-    @staticmethod
-    def _mutator(ns: _Namespace, method: str, what: str):
-        fn = getattr(ns.engine, method, None)
-        if fn is None:
-            raise ValueError(f"{what} needs an engine with {method} (a single-device namespace)")
-        return fn
-
     def check_attribute_patches(self, n_ids: int, values) -> List[Mapping]:
         """The refusals of ``update_attributes`` that need no namespace -> one patch per id (``values`` is one mapping for
         every id, or a sequence with one mapping per id; the keys are declared attributes)."""
@@ -1255,8 +1241,7 @@ class Index:
             if not isinstance(p, Mapping):
                 raise ValueError(f"update_attributes: values must be mappings, got {type(p).__name__}")
             for name in p:
-                if name not in self._attributes:
-                    raise ValueError(f"{name!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+                self._declared(name)
         return patches
 
     def _stage_patches(self, namespace: str, patches: Sequence[Mapping]):
@@ -1294,9 +1279,9 @@ class Index:
         ids = list(ids)
         staged, strings = self._stage_patches(namespace, self.check_attribute_patches(len(ids), values))
         ns = self._ns.get(namespace)
-        if ns is None or ns.total == 0 or not ids or not staged:
+        if self._no_rows(ns) or not ids or not staged:
             return 0
-        set_at = self._mutator(ns, "set_attr_at", "update_attributes")
+        set_at = self._engine_entry(ns, "set_attr_at", "update_attributes needs")
         labels = ns.ids.lookup(ids)
         touched = []
         for i, (pos, col) in staged.items():
@@ -1304,15 +1289,17 @@ class Index:
             keep = lab >= 0
             lab = lab[keep]
             rows, last = np.unique(lab[::-1], return_index=True)  # the last entry of each row
-            if rows.size and isinstance(col, _where.ListColumn):
-                self._list_engine(ns, "set_attr_list_at")(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
-                touched.append(rows)
-            elif rows.size and isinstance(col, _where.SparseColumn):
-                self._sparse_engine(ns, "set_attr_sparse_at")(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
-                touched.append(rows)
-            elif rows.size:
+            if not rows.size:
+                continue
+            if isinstance(col, _where.ListColumn):
+                set_list_at = self._engine_entry(ns, "set_attr_list_at", "list attributes need")
+                set_list_at(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
+            elif isinstance(col, _where.SparseColumn):
+                set_sparse_at = self._engine_entry(ns, "set_attr_sparse_at", "sparse attributes need")
+                set_sparse_at(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
+            else:
                 set_at(i, rows, col[keep][lab.size - 1 - last])
-                touched.append(rows)
+            touched.append(rows)
         ns.strings = strings
         return int(np.unique(np.concatenate(touched)).size) if touched else 0
 
@@ -1323,8 +1310,7 @@ class Index:
         if not isinstance(values, Mapping) or not values:
             raise ValueError("update_where: values must be a non-empty mapping of declared attributes")
         for name in values:
-            if name not in self._attributes:
-                raise ValueError(f"{name!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+            self._declared(name)
         ns = self._ns.get(namespace)
         strings = {name: dict(codes) for name, codes in (ns.strings if ns is not None else {}).items()}
         out = []
@@ -1383,15 +1369,15 @@ class Index:
                 raise ValueError(f"update_where: the filter reads {clash}, which this call assigns together with other "
                                  f"attributes in several passes; assign them in a call of their own")
         ns = self._ns.get(namespace)
-        if ns is None or ns.total == 0:
+        if self._no_rows(ns):
             return 0
         matched = None
         if scalars:  # first: the only pass that can refuse
-            matched, refused = self._mutator(ns, "update_where", "update_where")(program, scalars)
+            matched, refused = self._engine_entry(ns, "update_where", "update_where needs")(program, scalars)
             if refused:
                 raise ValueError(f"update_where: $inc would overflow on {refused} of the {matched} matching rows; nothing was changed")
         for i, _, codes in lists:
-            matched = self._list_engine(ns, "update_where_list")(program, i, codes)
+            matched = self._engine_entry(ns, "update_where_list", "list attributes need")(program, i, codes)
         ns.strings = strings
         return matched
 
@@ -1400,9 +1386,9 @@ class Index:
         the host first.  Returns their count, or their UUIDs (insertion order) with ``return_ids=True``."""
         program = self._compile(namespace, where)
         ns = self._ns.get(namespace)
-        if ns is None or ns.total == 0:
+        if self._no_rows(ns):
             return [] if return_ids else 0
-        labels = self._mutator(ns, "tombstone_where", "remove_where")(program)
+        labels = self._engine_entry(ns, "tombstone_where", "remove_where needs")(program)
         ids = ns.ids.uuids_at(labels).tolist() if return_ids else None
         if labels.size:
             ns.ids.kill(labels)
@@ -1425,19 +1411,12 @@ class Index:
 
     def check_top_by_args(self, by, limit, descending=False, offset=0) -> str:
         """The refusals of ``top_by`` that need no namespace -> the column kind of ``by`` ("int", "float" or "bool")."""
-        if not isinstance(by, str) or by not in self._attributes:
-            raise ValueError(f"top_by: {by!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        kind = self._declared(by, "top_by: ")
         self._check_scalar("top_by", by)
-        kind = self._attributes[by]
         if kind == "str":
             raise ValueError(f"top_by: attribute {by!r} is a str column; its codes are in order of first use, not in lexical "
                              f"order, so ranking needs an int, float or bool attribute")
-        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
-            raise ValueError(f"top_by: limit must be an int >= 1 (got {limit!r})")
-        if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
-            raise ValueError(f"top_by: offset must be an int >= 0 (got {offset!r})")
-        if int(offset) + int(limit) > self._MAX_ORDER_ROWS:
-            raise ValueError(f"top_by: offset + limit must be <= {self._MAX_ORDER_ROWS} (got {int(offset) + int(limit)})")
+        self._check_window("top_by", limit, offset)
         if not isinstance(descending, (bool, np.bool_)):
             raise ValueError(f"top_by: descending must be a bool (got {descending!r})")
         return kind
@@ -1457,16 +1436,13 @@ class Index:
         value}``, the values decoded (``True`` / ``False``, ints, floats; ``-0.0`` and ``0.0`` tie).  ``offset + limit`` is at
         most 4096.  An unknown or empty namespace gives no rows and zeros."""
         kind = self.check_top_by_args(by, limit, descending, offset)
-        if where is not None and not isinstance(where, Mapping):
-            raise ValueError(f"top_by: where must be one dict filter or None (got {type(where).__name__})")
-        program = None if where is None else self._compile(namespace, where)
+        self._one_filter("top_by", where)
+        program = self._program(namespace, where)
         ns = self._ns.get(namespace)
-        if ns is None or ns.total == 0:
+        if self._no_rows(ns):
             return {"ids": [], "values": [], "matched": 0, "absent": 0}
-        where_ordered = getattr(ns.engine, "where_ordered", None)
-        if where_ordered is None:
-            raise ValueError("top_by needs an engine with where_ordered (a single-device namespace)")
-        labels, values, matched, absent = where_ordered(list(self._attributes).index(by), int(limit), where=program,
+        where_ordered = self._engine_entry(ns, "where_ordered", "top_by needs")
+        labels, values, matched, absent = where_ordered(self._column(by), int(limit), where=program,
                                                         descending=bool(descending), offset=int(offset))
         return {"ids": ns.ids.uuids_at(labels).tolist(), "values": self.decode_order_values(kind, values), "matched": matched,
                 "absent": absent}
@@ -1474,16 +1450,9 @@ class Index:
     # ------------------------------------------------------------------ additive: nearest by distance on a geo attribute
     def check_nearest_args(self, by, point, limit, offset=0) -> int:
         """The refusals of ``nearest`` that need no namespace -> the packed centre."""
-        if not isinstance(by, str) or by not in self._attributes:
-            raise ValueError(f"nearest: {by!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
-        if not _where.is_geo(self._attributes[by]):
+        if not _where.is_geo(self._declared(by, "nearest: ")):
             raise ValueError(f"nearest: attribute {by!r} is a {self._attributes[by]} column; it needs a geo attribute")
-        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
-            raise ValueError(f"nearest: limit must be an int >= 1 (got {limit!r})")
-        if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
-            raise ValueError(f"nearest: offset must be an int >= 0 (got {offset!r})")
-        if int(offset) + int(limit) > self._MAX_ORDER_ROWS:
-            raise ValueError(f"nearest: offset + limit must be <= {self._MAX_ORDER_ROWS} (got {int(offset) + int(limit)})")
+        self._check_window("nearest", limit, offset)
         return _where.geo_pack(point, "nearest: point")
 
     def nearest(self, namespace: str, by: str, point, limit: int, where: Optional[Mapping] = None, *, offset: int = 0):
@@ -1494,17 +1463,14 @@ class Index:
         "absent": those of them without a location}``.  ``point`` is quantised as stored points are; a maximum distance is a
         ``$geo_radius`` in ``where``.  ``offset + limit`` is at most 4096.  An unknown or empty namespace gives no rows."""
         center = self.check_nearest_args(by, point, limit, offset)
-        if where is not None and not isinstance(where, Mapping):
-            raise ValueError(f"nearest: where must be one dict filter or None (got {type(where).__name__})")
-        program = None if where is None else self._compile(namespace, where)
+        self._one_filter("nearest", where)
+        program = self._program(namespace, where)
         ns = self._ns.get(namespace)
-        if ns is None or ns.total == 0:
+        if self._no_rows(ns):
             return {"ids": [], "points": [], "distances": [], "matched": 0, "absent": 0}
-        geo_nearest = getattr(ns.engine, "geo_nearest", None)
-        if geo_nearest is None:
-            raise ValueError("nearest needs an engine with geo_nearest (a single-device namespace)")
-        labels, points, dist, matched, absent = geo_nearest(list(self._attributes).index(by), center, int(limit),
-                                                            where=program, offset=int(offset))
+        geo_nearest = self._engine_entry(ns, "geo_nearest", "nearest needs")
+        labels, points, dist, matched, absent = geo_nearest(self._column(by), center, int(limit), where=program,
+                                                            offset=int(offset))
         return {"ids": ns.ids.uuids_at(labels).tolist(), "points": [_where.geo_degrees(p) for p in points.tolist()],
                 "distances": dist.tolist(), "matched": matched, "absent": absent}
 
@@ -1516,19 +1482,16 @@ class Index:
         """The refusals of ``facets`` that need no namespace -> the attributes to facet (``by`` as a list)."""
         names = list(by) if isinstance(by, (list, tuple)) else [by]
         for name in names:
-            if name not in self._attributes:
-                raise ValueError(f"facets: {name!r} is not a declared attribute of this index "
-                                 f"(declared: {sorted(self._attributes)})")
+            kind = self._declared(name, "facets: ")
             self._check_sparse("facets", name)
-            if self._attributes[name] == "float":
+            if kind == "float":
                 raise ValueError(f"facets: attribute {name!r} is a float column; value facets need an int, str or bool "
                                  f"attribute (histogram() bins floats)")
         if order not in ("count", "value"):
             raise ValueError(f'facets: order must be "count" or "value" (got {order!r})')
-        if limit is not None and (isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1):
+        if limit is not None and not self._int_in(limit, 1):
             raise ValueError(f"facets: limit must be None or an int >= 1 (got {limit!r})")
-        if isinstance(max_values, bool) or not isinstance(max_values, (int, np.integer)) or \
-                not 1 <= max_values <= self._MAX_FACET_VALUES:
+        if not self._int_in(max_values, 1, self._MAX_FACET_VALUES):
             raise ValueError(f"facets: max_values must be in 1..{self._MAX_FACET_VALUES} (got {max_values!r})")
         return names
 
@@ -1552,42 +1515,32 @@ class Index:
         element of its list -- the counts then do not add up to ``matched - absent`` -- and ``absent`` counts the rows with no
         list or an empty one."""
         names = self.check_facet_args(by, order, limit, max_values)
-        if where is not None and not isinstance(where, Mapping):
-            raise ValueError(f"facets: where must be one dict filter or None (got {type(where).__name__})")
-        program = None if where is None else self._compile(namespace, where)
+        self._one_filter("facets", where)
+        program = self._program(namespace, where)
         ns = self._ns.get(namespace)
         out = {}
         for name in names:
-            if ns is None or ns.total == 0:
+            if self._no_rows(ns):
                 out[name] = {"values": [], "matched": 0, "absent": 0}
                 continue
             kind = self._attributes[name]
-            facet_values = getattr(ns.engine, "facet_list_values" if _where.is_list(kind) else "facet_values", None)
-            if facet_values is None:
-                raise ValueError("facets needs an engine with facet_values (a single-device namespace)")
-            codes = ns.strings.get(name, {})
-            bound = max(1, len(codes)) if kind in ("str", "str[]") else 2 if kind == "bool" else int(max_values)
+            facet_values = self._engine_entry(ns, "facet_list_values" if _where.is_list(kind) else "facet_values", "facets needs",
+                                              named="facet_values")
+            bound = max(1, self._group_bound(ns, name, kind, int(max_values)))
             try:
-                values, counts, matched, absent = facet_values(list(self._attributes).index(name), bound, where=program)
+                values, counts, matched, absent = facet_values(self._column(name), bound, where=program)
             except FacetOverflow as e:
                 raise ValueError(f"facets: attribute {name!r} holds more than max_values={bound} distinct values among the "
                                  f"{e.matched} matching rows; raise max_values (at most {self._MAX_FACET_VALUES})") from e
-            values, counts = values.tolist(), counts.tolist()
-            if kind in ("str", "str[]"):
-                strings = sorted(codes, key=codes.get)  # code order
-                values = [strings[v] for v in values]
-            elif kind == "bool":
-                values = [bool(v) for v in values]
-            out[name] = {"values": self.order_facets(list(zip(values, counts)), order, limit), "matched": matched,
+            values = self._decode_codes(ns, name, kind, values.tolist())
+            out[name] = {"values": self.order_facets(list(zip(values, counts.tolist())), order, limit), "matched": matched,
                          "absent": absent}
         return out if isinstance(by, (list, tuple)) else out[names[0]]
 
     def check_histogram_args(self, by: str, edges) -> np.ndarray:
         """The refusals of ``histogram`` -> the edges as the column's own type (int64 / float64)."""
-        if not isinstance(by, str) or by not in self._attributes:
-            raise ValueError(f"histogram: {by!r} is not a declared attribute of this index (declared: {sorted(self._attributes)})")
+        kind = self._declared(by, "histogram: ")
         self._check_scalar("histogram", by)
-        kind = self._attributes[by]
         if kind not in ("int", "float"):
             raise ValueError(f"histogram: attribute {by!r} is a {kind} column; bins need an int or float attribute")
         edges = edges.tolist() if isinstance(edges, np.ndarray) else list(edges)
@@ -1616,28 +1569,21 @@ class Index:
         side="right")``: slot 0 below the first edge, the last slot at or above the last).  ``edges``: 1..4096 strictly
         ascending literals, ints for an ``int`` attribute, ints or floats (not NaN) for a ``float`` one."""
         e = self.check_histogram_args(by, edges)
-        if where is not None and not isinstance(where, Mapping):
-            raise ValueError(f"histogram: where must be one dict filter or None (got {type(where).__name__})")
-        program = None if where is None else self._compile(namespace, where)
+        self._one_filter("histogram", where)
+        program = self._program(namespace, where)
         ns = self._ns.get(namespace)
-        if ns is None or ns.total == 0:
+        if self._no_rows(ns):
             return {"counts": np.zeros(e.size + 1, dtype=np.int64), "matched": 0, "absent": 0}
-        facet_bins = getattr(ns.engine, "facet_bins", None)
-        if facet_bins is None:
-            raise ValueError("histogram needs an engine with facet_bins (a single-device namespace)")
-        counts, matched, absent = facet_bins(list(self._attributes).index(by), e, where=program)
+        counts, matched, absent = self._engine_entry(ns, "facet_bins", "histogram needs")(self._column(by), e, where=program)
         return {"counts": counts, "matched": matched, "absent": absent}
 
     # ------------------------------------------------------------------ additive: attribute statistics on the device
     def check_stats_args(self, attr, by: Optional[str] = None, max_groups: int = 65536) -> List[str]:
         """The refusals of ``stats`` that need no namespace -> the attributes to summarise (``attr`` as a list)."""
-        if self._devices is not None and len(self._devices) > 1:
-            raise ValueError("stats is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        self._refuse_sharded("stats")
         names = list(attr) if isinstance(attr, (list, tuple)) else [attr]
         for name in names + ([] if by is None else [by]):
-            if not isinstance(name, str) or name not in self._attributes:
-                raise ValueError(f"stats: {name!r} is not a declared attribute of this index "
-                                 f"(declared: {sorted(self._attributes)})")
+            self._declared(name, "stats: ")
             self._check_scalar("stats", name)
         for name in names:
             if self._attributes[name] not in ("int", "float", "bool"):
@@ -1645,8 +1591,7 @@ class Index:
                                  f"int, float or bool attribute")
         if by is not None and self._attributes[by] == "float":
             raise ValueError(f"stats: by={by!r} is a float column; groups need an int, str or bool attribute")
-        if isinstance(max_groups, bool) or not isinstance(max_groups, (int, np.integer)) or \
-                not 1 <= max_groups <= self._MAX_FACET_VALUES:
+        if not self._int_in(max_groups, 1, self._MAX_FACET_VALUES):
             raise ValueError(f"stats: max_groups must be in 1..{self._MAX_FACET_VALUES} (got {max_groups!r})")
         return names
 
@@ -1665,36 +1610,26 @@ class Index:
         ``ValueError``); a ``str`` one is bounded by its dictionary, a ``bool`` by two.  ``attr`` as a list of attributes
         returns a dict keyed by attribute (one device call each)."""
         names = self.check_stats_args(attr, by, max_groups)
-        if where is not None and not isinstance(where, Mapping):
-            raise ValueError(f"stats: where must be one dict filter or None (got {type(where).__name__})")
-        program = None if where is None else self._compile(namespace, where)
+        self._one_filter("stats", where)
+        program = self._program(namespace, where)
         ns = self._ns.get(namespace)
         out = {}
         for name in names:
             kind = self._attributes[name]
-            if ns is None or ns.total == 0:
+            if self._no_rows(ns):
                 out[name] = self.shape_stats(kind, by, [], [], 0, 0) if by is not None else \
                     self.shape_stats(kind, None, [None], [(0, 0, None, None, 0)], 0, 0)
                 continue
-            attr_stats = getattr(ns.engine, "attr_stats", None)
-            if attr_stats is None:
-                raise ValueError("stats needs an engine with attr_stats (a single-device namespace)")
-            columns = list(self._attributes)
+            attr_stats = self._engine_entry(ns, "attr_stats", "stats needs")
             by_kind = None if by is None else self._attributes[by]
-            codes = {} if by is None else ns.strings.get(by, {})
-            bound = 1 if by is None else max(1, len(codes)) if by_kind == "str" else 2 if by_kind == "bool" else int(max_groups)
+            bound = 1 if by is None else max(1, self._group_bound(ns, by, by_kind, int(max_groups)))
             try:
                 keys, rows, count, lo, hi, sum_hi, sum_lo, matched, by_absent = attr_stats(
-                    columns.index(name), None if by is None else columns.index(by), bound, where=program)
+                    self._column(name), None if by is None else self._column(by), bound, where=program)
             except StatsOverflow as e:
                 raise ValueError(f"stats: by={by!r} holds more than max_groups={bound} distinct values among the {e.matched} "
                                  f"matching rows; raise max_groups (at most {self._MAX_FACET_VALUES})") from e
-            values = keys.tolist()
-            if by_kind == "str":
-                strings = sorted(codes, key=codes.get)  # code order
-                values = [strings[v] for v in values]
-            elif by_kind == "bool":
-                values = [bool(v) for v in values]
+            values = self._decode_codes(ns, by, by_kind, keys.tolist())
             groups = [(r, c, a, b, _stats.int128(h, l)) for r, c, a, b, h, l in
                       zip(rows.tolist(), count.tolist(), lo.tolist(), hi.tolist(), sum_hi.tolist(), sum_lo.tolist())]
             out[name] = self.shape_stats(kind, by, values, groups, matched, by_absent)
@@ -1732,15 +1667,13 @@ class Index:
         elif where is not None:
             program = self._compile(namespace, where)
         ns = self._ns.get(namespace)
-        if ns is None or ns.total - ns.deleted <= 0 or nq == 0 or q.shape[1] != ns.dim:
+        if self._nothing_to_search(ns, nq=nq, dim=q.shape[1]):
             return [[] for _ in range(nq)]
         native_radius = float(radius) ** 2 if metric == "euclidean" else float(radius)
         cap = self._MAX_TOP_K if max_results is None else max(1, int(max_results))
         if programs:
-            range_each = getattr(ns.engine, "range_each", None)
-            if range_each is None:
-                raise ValueError("per-query filters need an engine with range_each (a single-device namespace)")
-            per_query = range_each(q, native_radius, cap, programs, of, truncate=True)
+            per_query = self._engine_entry(ns, "range_each", "per-query filters need")(q, native_radius, cap, programs, of,
+                                                                                       truncate=True)
         elif program is None:
             per_query = ns.engine.range(q, native_radius, cap, truncate=True)
         else:
@@ -1891,7 +1824,7 @@ class Index:
         chunk = 1 << 20
         for first in range(0, ns.total, chunk):
             n = min(chunk, ns.total - first)
-            got = cls._list_engine(ns, "get_attr_list")(j, first, n)
+            got = cls._engine_entry(ns, "get_attr_list", "list attributes need")(j, first, n)
             live = got.present.astype(bool)
             live[dead[(dead >= first) & (dead < first + n)] - first] = False
             rows = np.flatnonzero(live)
@@ -1917,7 +1850,7 @@ class Index:
         chunk = 1 << 20
         for first in range(0, ns.total, chunk):
             n = min(chunk, ns.total - first)
-            got = cls._sparse_engine(ns, "get_attr_sparse")(j, first, n)
+            got = cls._engine_entry(ns, "get_attr_sparse", "sparse attributes need")(j, first, n)
             live = got.present.astype(bool)
             live[dead[(dead >= first) & (dead < first + n)] - first] = False
             rows = np.flatnonzero(live)
@@ -1954,8 +1887,8 @@ class Index:
             raise RuntimeError(f"a geo attribute in a {meta['format']} snapshot: only {self._FORMAT_V5} holds them")
         # v2: the snapshot's attributes replace the declared ones; v1: the declared ones stay, every value absent
         attributes = self._check_schema(meta.get("attributes", {})) if v2 else self._attributes
-        if v2 and attributes and self._devices is not None and len(self._devices) > 1:
-            raise ValueError("attributes= is not supported on a row-sharded index (devices=[...] with more than one entry)")
+        if v2 and attributes:
+            self._refuse_sharded("attributes=")
         for i, m in enumerate(meta["namespaces"]):  # validate sizes before touching anything
             total, dim = int(m["total"]), int(m["dim"])
             if os.path.getsize(os.path.join(path, f"ns{i}.rows.f32")) != total * dim * 4 or \
@@ -2005,14 +1938,14 @@ class Index:
                         lists = _where.ListColumn(np.fromfile(base + "offsets.i64", dtype=np.int64),
                                                   np.fromfile(base + "values.i64", dtype=np.int64),
                                                   (col != _where.INT64_ABSENT).astype(np.uint8))
-                        self._list_engine(ns, "set_attr_list")(j, 0, lists)
+                        self._engine_entry(ns, "set_attr_list", "list attributes need")(j, 0, lists)
                     elif col.size and _where.is_sparse(kind):
                         base = self._attr_file(path, i, j, kind)[:-len("i64")]
                         vectors = _where.SparseColumn(np.fromfile(base + "offsets.i64", dtype=np.int64),
                                                       np.fromfile(base + "terms.i32", dtype=np.int32),
                                                       np.fromfile(base + "weights.f32", dtype=np.float32),
                                                       (col != _where.INT64_ABSENT).astype(np.uint8))
-                        self._sparse_engine(ns, "set_attr_sparse")(j, 0, vectors)
+                        self._engine_entry(ns, "set_attr_sparse", "sparse attributes need")(j, 0, vectors)
                     elif col.size:
                         ns.engine.set_attr(j, 0, col)
                 ns.strings = {a: {s: c for c, s in enumerate(values)} for a, values in m.get("strings", {}).items()}
