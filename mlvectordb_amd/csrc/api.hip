@@ -553,7 +553,7 @@ int setup_filter_ws(mlvdb_index* h, FilterArgs& fa, int32_t q0, int32_t nq, bool
     fa.cnt = h->fmisc.as<uint32_t>() + 2 * kFilterQueries;
     fa.overflow = h->fmisc.as<uint32_t>() + 3 * kFilterQueries;
     fa.ke = h->fmisc.as<float>() + 4 * kFilterQueries;
-    fa.keb = h->fmisc.as<float>() + 5 * kFilterQueries;
+    // (words 5 x 256 .. 6 x 256 are free)
     fa.ke8 = h->fmisc.as<float>() + 6 * kFilterQueries;  // 257 floats
     fa.sqmin = h->fmisc.as<uint32_t>() + 7 * kFilterQueries + 128;  // [0..1] smallest scale / largest error (cosine); [2..3] l2c QMAX by parity
     fa.l2c_out = h->fmisc.as<float>() + 7 * kFilterQueries + 132;
@@ -658,18 +658,28 @@ int update_i8_shadow(mlvdb_index* h, hipStream_t s) {
     return MLVDB_OK;
 }
 
-int attach_i8(mlvdb_index* h, hipStream_t s, FilterArgs& fa) {
+// Can the int8 shadow serve this call?  The index keeps one, it is current -- brought up to date here; under a row mask the
+// masked copy of the row pairs must have been built instead (without it: the bf16 / fp32 bodies) -- and its bounds are usable:
+// one scale per row means a row with an outlier component quantises badly.  Cosine bounds carry every row's own error; l2 / ip
+// still use the index-wide maximum, which would then admit everything: beyond 0.03 (typical data sits at 0.008-0.015) they
+// keep to the bf16 shadow, whose error is relative per component (i8_bounds_usable).
+int i8_ready(mlvdb_index* h, hipStream_t s, bool* ready) {
+    *ready = false;
     if (!i8_eligible(h)) return MLVDB_OK;
     if (h->mask_active) {
-        if (!h->mask_pairs_ready) return MLVDB_OK;  // the masked copy of the row pairs was not built: bf16 / fp32 bodies
+        if (!h->mask_pairs_ready) return MLVDB_OK;
     } else {
         int rc = update_i8_shadow(h, s);
         if (rc) return rc;
     }
-    // One scale per row: a row with an outlier component quantises badly.  Cosine bounds carry every row's own error;
-    // l2 / ip still use the index-wide maximum, which would then admit everything: beyond 0.03 (typical data sits at
-    // 0.008-0.015) they keep to the bf16 shadow, whose error is relative per component.
-    if (!i8_bounds_usable(h)) return MLVDB_OK;
+    *ready = i8_bounds_usable(h);
+    return MLVDB_OK;
+}
+
+int attach_i8(mlvdb_index* h, hipStream_t s, FilterArgs& fa) {
+    bool ready = false;
+    int rc = i8_ready(h, s, &ready);
+    if (rc || !ready) return rc;
     HIP_TRY(h, h->qimg8.ensure((size_t)kFilterQueries * h->ld8));
     HIP_TRY(h, h->sq8.ensure(kFilterQueries * sizeof(float)));
     fa.X8 = h->x8.p;
@@ -679,7 +689,7 @@ int attach_i8(mlvdb_index* h, hipStream_t s, FilterArgs& fa) {
     if (fa.rp8_cap > 0) {
         fa.l2c = 1;
         if (!h->l2tag.p) {
-            int rc = forget_l2_offsets(h, 0, s);  // (allocates, zeroed)
+            rc = forget_l2_offsets(h, 0, s);  // (allocates, zeroed)
             if (rc) return rc;
         }
         fa.l2tag = h->tn.l2_offset_cache != 0 ? h->l2tag.as<uint32_t>() + (h->mask_active ? 4 : 0) : nullptr;
@@ -699,6 +709,7 @@ int begin_pass(mlvdb_index* h, hipStream_t s, FilterArgs& fa, const float* queri
     if (rc) return rc;
     rc = attach_i8(h, s, fa);
     if (rc) return rc;
+    HIP_TRY(h, filter_set_body(fa));  // the pass's one body choice: the prep, the scans and the stats below read fa.body
     if (h->sqmin_fresh) {  // what the fused prep's atomicMin / atomicMax start from; afterwards every fin kernel restores it
         HIP_TRY(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(fa.sqmin), 0x7f7f7f7f, 1, s));
         HIP_TRY(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(fa.sqmin + 1), 0, 1, s));
@@ -706,13 +717,13 @@ int begin_pass(mlvdb_index* h, hipStream_t s, FilterArgs& fa, const float* queri
     }
     HIP_TRY(h, launch_filter_prep_fused(fa, queries_raw + (size_t)q0 * h->dim, h->dim, h->qpad.as<float>() + (size_t)q0 * h->ld,
                                         h->qaux.as<double>() + q0, h->qerr.as<float>() + q0, s));
-    if (fa.X8 && fa.rp8_cap > 0) {
+    if (fa.body == kBodyI8 && fa.rp8_cap > 0) {
         // l2: this pass's integer offsets (they depend on its largest query scale and on which rows are live): 29 us for 10M rows
         // (it stays in the pass's stream: DESIGN "tried and dropped")
         const int64_t rows = std::min<int64_t>(h->capacity, (h->total + kFilterTile - 1) / kFilterTile * kFilterTile);
         HIP_TRY(h, launch_filter_l2_offsets(fa, rows, s));
     }
-    h->stats.bound_dtype = fa.X8 ? 2 : 1;
+    h->stats.bound_dtype = fa.body == kBodyI8 ? 2 : 1;
     return MLVDB_OK;
 }
 
@@ -779,7 +790,7 @@ int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, int
     //    launch_filter_finish_small).  One block per query: at 4-8 queries the rescoring kernel's spread over the whole chip
     //    wins again -- 0.261 vs 0.247 ms at 4; neither step gains there (profiles/r03/small_batch_fused_finish_and_prefix_seed_1m.txt).
     const int small_nq = std::max(0, std::min(8, h->tn.small_nq));
-    const bool small = fa.X8 && nq <= small_nq && k <= 64;
+    const bool small = fa.body == kBodyI8 && nq <= small_nq && k <= 64;
     const bool small_finish = small && filter_refine_can_fuse(fa) && h->tn.small_finish != 0;
     // One query on a small corpus (SMALL_BATCH; two queries: 0.214-0.220 vs 0.211-0.219 ms -- no gain) goes ONE round: the exact
     // k-th best of an 11,520-row prefix puts the threshold at quantile k / 11,520; one scan launch over every row then appends
@@ -802,7 +813,7 @@ int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, int
     // l2 index with a few badly quantising rows: the dense int8 pass would bound every seed row with the index-wide error,
     // and those inflated bounds then crowd the refines' picks -- the threshold stalls at the seed's quantile.  Such a pass takes
     // its thresholds from the EXACT k-th best score among the seed rows (exact fp64 scan of that prefix + merge + one tiny kernel)
-    const bool seed_exact = fa.X8 && h->space == kSpaceL2 && h->i8_err > 0.03f;
+    const bool seed_exact = fa.body == kBodyI8 && h->space == kSpaceL2 && h->i8_err > 0.03f;
     if (one_round || (small && !h->mask_active && !seed_exact && h->tn.small_seed != 0)) {
         HIP_TRY(h, h->seed_d64.ensure(((size_t)kFilterQueries * 64 + (size_t)8 * kSeedRows) * sizeof(double)));
         double* d64 = h->seed_d64.as<double>();
@@ -848,11 +859,7 @@ int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, int
             ranked = true;
             break;
         }
-        // int8 bounds are loose: thresholds from exact scores of the k best bounds; the same kernel prunes the lists
-        // (the update kernel's bound-derived threshold could only be lower) unless the query does not fit beside them
-        const bool fuse = fa.X8 && filter_refine_can_fuse(fa);
-        if (fa.X8) HIP_TRY(h, launch_filter_refine_thr(fa, k, -1, fuse, s));
-        if (!fuse) HIP_TRY(h, launch_filter_update(fa, k, s));
+        HIP_TRY(h, launch_filter_refine_update(fa, k, -1, s));
     }
     return finish_filter_pass(h, s, fa, q0, nq, k, out_labels, out_dist, out_counts, out_d64, defer_fallback, ranked);
 }
@@ -1104,7 +1111,7 @@ bool i8_bounds_usable(const mlvdb_index* h) {
 
 // Is a filter body available for this index right now?  ld % 64 == 0: always (bf16 shadow, int8 shadow, or the fp32 rows
 // converted in registers).  Any other ld has only the int8 body: the (zero-padded) int8 shadow is brought up to date here
-// and its bounds must be usable (attach_i8's criterion: l2 / ip rows that quantise too badly go to the exact scan).
+// and its bounds must be usable (i8_ready, the test attach_i8 makes: l2 / ip rows that quantise too badly go to the exact scan).
 bool use_filter(const mlvdb_index* h, int64_t nq, bool ready);
 
 int filter_ready(mlvdb_index* h, hipStream_t s, int64_t nq, bool* ready) {
@@ -1115,15 +1122,7 @@ int filter_ready(mlvdb_index* h, hipStream_t s, int64_t nq, bool* ready) {
         *ready = true;
         return MLVDB_OK;
     }
-    if (!i8_eligible(h)) return MLVDB_OK;
-    if (h->mask_active) {
-        *ready = h->mask_pairs_ready && i8_bounds_usable(h);
-        return MLVDB_OK;
-    }
-    int rc = update_i8_shadow(h, s);
-    if (rc) return rc;
-    *ready = i8_bounds_usable(h);
-    return MLVDB_OK;
+    return i8_ready(h, s, ready);
 }
 
 bool use_filter(const mlvdb_index* h, int64_t nq, bool ready) {
@@ -1790,7 +1789,7 @@ static int range_ranked(mlvdb_index* h, hipStream_t s, const float* queries, int
         } else {
             rc = setup_filter_ws(h, fa, (int32_t)q0, n, true);
             if (rc) return rc;
-            HIP_TRY(h, launch_filter_prep(fa, s));  // per-query state only (no image: the exact range scan reads Qpad)
+            HIP_TRY(h, launch_filter_state(fa, s));  // per-query state only (no image: the exact range scan reads Qpad)
             h->stats.bound_dtype = 0;
         }
         rc = scan_step(h, s, h->total, [&]() -> hipError_t {

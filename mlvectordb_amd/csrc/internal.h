@@ -54,22 +54,26 @@ inline hipError_t ensure_instance_lds(size_t lds, int max_bytes) {
     return lds > 48 * 1024 ? ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(Kernel), max_bytes) : hipSuccess;
 }
 
-// f(SPACE, QT) with the space and the queries per tile (1, 2, otherwise 4) of a gathered launch as compile-time constants:
-// f is a generic lambda, `constexpr int SPACE = decltype(sp)::value` inside it.
+// f(SPACE) with the space as a compile-time constant: f is a generic lambda, `constexpr int SPACE = decltype(sp)::value` inside it.
+template <class F>
+inline hipError_t with_space(int32_t space, F&& f) {
+    switch (space) {
+        case kSpaceL2: return f(std::integral_constant<int, kSpaceL2>{});
+        case kSpaceCosine: return f(std::integral_constant<int, kSpaceCosine>{});
+        default: return f(std::integral_constant<int, kSpaceIp>{});
+    }
+}
+
+// f(SPACE, QT): the same with the queries per tile (1, 2, otherwise 4) of a gathered launch as a second constant.
 template <class F>
 inline hipError_t with_space_qt(int32_t space, int32_t qt, F&& f) {
-    auto with_qt = [&](auto sp) {
+    return with_space(space, [&](auto sp) {
         switch (qt) {
             case 1: return f(sp, std::integral_constant<int, 1>{});
             case 2: return f(sp, std::integral_constant<int, 2>{});
             default: return f(sp, std::integral_constant<int, 4>{});
         }
-    };
-    switch (space) {
-        case kSpaceL2: return with_qt(std::integral_constant<int, kSpaceL2>{});
-        case kSpaceCosine: return with_qt(std::integral_constant<int, kSpaceCosine>{});
-        default: return with_qt(std::integral_constant<int, kSpaceIp>{});
-    }
+    });
 }
 
 // ---------------------------------------------------------------- tuning state (per handle)
@@ -89,7 +93,6 @@ inline hipError_t with_space_qt(int32_t space, int32_t qt, F&& f) {
     X(small_finish, "SMALL_FINISH", 1) /* 1-2 queries: fused last refine + rescoring + ranking */                       \
     X(small_nq, "SMALL_NQ", 2)                                                                                          \
     X(seed_rows, "SEED_ROWS", 5)       /* dense seeding pass, units of 768 rows */                                      \
-    X(seed_i8, "SEED_I8", 1)                                                                                            \
     X(round1, "ROUND1", 85)            /* ends of the first / second scan round, units of 768 rows */                   \
     X(round2, "ROUND2", 2048)                                                                                           \
     X(refine_picks, "REFINE_PICKS", 0) /* 0 = 1.5 k, at least 16 */                                                     \
@@ -238,8 +241,13 @@ struct WgEntry {
 bool filter_supported(int32_t ld);
 size_t filter_qimg_bytes(int32_t ld);   // bf16 query image for one pass of kFilterQueries
 
+// The body that serves every scan of a pass -- what its kernels stream, hence which query image the prep writes and in which
+// k-order: the fp32 rows converted in registers, the bf16 shadow, or the int8 shadow.  Decided once per pass (filter_set_body).
+enum ScanBody : int32_t { kBodyFp32 = 0, kBodyBf16 = 1, kBodyI8 = 2 };
+
 struct FilterArgs {
     const Tuning* tn;       // host only: the handle's tuning state (never dereferenced on the device)
+    ScanBody body;          // set by filter_set_body; the prep and the scan launchers read it instead of X8 / Xb
     const float* X;
     const void* Xb;         // bf16 shadow of X (layout_offset_b) or nullptr: the scan then converts fp32 in registers
     const float* rn;
@@ -276,7 +284,6 @@ struct FilterArgs {
     void* qimg8;            // int8 query image
     float* sq8;             // [256] scale of the query image
     float* ke8;             // [257] cosine: the query's own int8 error term (row errors are per row); [256] = K = (1 + max eq8)/min sq8
-    float* keb;             // [256] the bf16 error term: what the (bf16) seeding pass adds, while `ke` covers both kinds of entry
     unsigned int* sqmin;    // two device scalars: bits of the smallest sq8 / of the largest query error of the pass's queries
     struct RangeHit* rs;    // kNN passes: [256][kCandCap] exact (distance, label) of every rescored candidate (filter_rescore_score_kernel -> _rank_kernel)
     WgEntry* wgbuf;         // [kScanMaxGrid][kWgCap] append buffers of one scan launch, one slice per wave
@@ -284,9 +291,15 @@ struct FilterArgs {
     int32_t scan_q4;        // host only: a k <= 64 kNN pass (run_filter_pass sets it, nobody else) -- its scans append few entries
                             // per wave and may take the four-buffer int8 body, whose LDS staging area is small (launch_scan_space)
 };
-hipError_t launch_filter_prep(const FilterArgs& a, hipStream_t s);
-// query_prep + filter_prep + filter_prep8 (when a.X8) of one pass in one launch (+ the one-block fin): `queries` = the pass's raw
-// [a.nq][dim] rows on the device; writes Qpad / qaux / qerr (= a.Qpad / a.qaux / a.qerr) and everything launch_filter_prep(8) does.
+// a.body from the shadows the pass was given (X8 attached: int8; else Xb: bf16; else fp32).  The one place that refuses a pass
+// without a body: only the int8 one takes an ld that is no multiple of 64 (hipErrorInvalidValue).
+hipError_t filter_set_body(FilterArgs& a);
+// The per-query state alone (scale, bf16 error term, threshold, empty list) from a.qaux / a.qerr as launch_query_prep left
+// them: one block, no image -- the exact range scan reads Qpad.
+hipError_t launch_filter_state(const FilterArgs& a, hipStream_t s);
+// Everything a pass needs of its queries in one launch (+ the one-block fin or the l2 image kernel of an int8 pass):
+// `queries` = the pass's raw [a.nq][dim] rows on the device; writes Qpad / qaux / qerr (= a.Qpad / a.qaux / a.qerr), the
+// per-query state and the query image of a.body.
 // a.sqmin[] must hold {0x7f7f7f7f, 0} on entry (set when the workspace is allocated, restored by every fin kernel).
 hipError_t launch_filter_prep_fused(const FilterArgs& a, const float* queries, int32_t dim, float* Qpad, double* qaux, float* qerr,
                                     hipStream_t s);
@@ -294,17 +307,19 @@ hipError_t launch_filter_prep_fused(const FilterArgs& a, const float* queries, i
 // thr[q] from the k-th smallest of d64[q][0..m) (m <= 3 kSeedRows; fewer than k finite values: thr stays as it is)
 hipError_t launch_filter_prefix_thr(const FilterArgs& a, const double* d64, int32_t m, int32_t k, hipStream_t s);
 hipError_t launch_filter_seed_thr(const FilterArgs& a, const double* seed_d64, int32_t k, hipStream_t s);
-// int8 shadow: (re)build the panels covering rows [row_begin, row_end) (also rp8 and the index-wide error), the query image of a
-// pass (after launch_filter_prep: overrides ke with the int8 error term), exact thresholds from the k best bounds
+// int8 shadow: (re)build the panels covering rows [row_begin, row_end) (also rp8 and the index-wide error)
 hipError_t launch_shadow8_rows(const float* X, const float* rn, void* X8, float* rp8, float* row_err8, int64_t row_begin,
                                int64_t row_end, int32_t ld, int32_t ld8, int32_t space, hipStream_t s);
-hipError_t launch_filter_prep8(const FilterArgs& a, hipStream_t s);
 // l2, once per pass (after the prep kernels): the integer offsets e_j of rows [0, rows) that fold the row term -|x|^2 of the l2
 // score into the scan's accumulators (tools/gen_scan_asm.py, l2e): needs a.rp8_cap > 0
 hipError_t launch_filter_l2_offsets(const FilterArgs& a, int64_t rows, hipStream_t s);
 bool filter_refine_can_fuse(const FilterArgs& a);
 bool filter_narrow_ok(const FilterArgs& a);  // the pass's scans run on the narrow kernel (bf16 shadow, <= 64 queries, image resident in LDS)
-hipError_t launch_filter_refine_thr(const FilterArgs& a, int32_t k, int32_t forced_cnt, bool fuse, hipStream_t s);
+// What follows every scan launch of a k <= 64 pass: lists -> thresholds, entries below them dropped (cnt[q] = survivors).  An
+// int8 pass, whose bounds are loose, first takes its thresholds from the exact scores of the best bounds; that kernel prunes
+// too where the lists fit in LDS beside the query (filter_refine_can_fuse), and the update kernel is then not launched.
+// forced_cnt >= 0: every list holds that many entries (after the dense pass); -1: cnt[q]
+hipError_t launch_filter_refine_update(const FilterArgs& a, int32_t k, int32_t forced_cnt, hipStream_t s);
 // batches of <= 8 queries: the last refine + exact rescoring + ranking + output in one launch (needs filter_refine_can_fuse)
 hipError_t launch_filter_finish_small(const FilterArgs& a, int32_t k, int32_t q0, int64_t* out_labels, float* out_dist,
                                       int32_t* out_counts, double* out_d64, unsigned long long* rescored, int32_t* qsel,
@@ -313,7 +328,6 @@ hipError_t launch_filter_scan(const FilterArgs& a, int64_t row_begin, int64_t ro
 // dense seeding pass over rows [0,row_end), row_end <= kSeedRows: all bounds -> candidate lists -> thresholds (update)
 constexpr int kSeedRows = 3840;  // a multiple of every scan tile (128, 192) and <= kCandCap
 hipError_t launch_filter_seed_scan(const FilterArgs& a, int64_t row_end, int32_t k, hipStream_t s);
-hipError_t launch_filter_update(const FilterArgs& a, int32_t k, hipStream_t s);
 // rescored[0] += rescored pairs; qsel != nullptr: also compacts the overflowed queries of the pass, qsel[0..*nflag) = their
 // indices, rescored[1] += *nflag (the device-decided exact fallback that follows reads them)
 hipError_t launch_filter_rescore(const FilterArgs& a, int32_t k, int32_t q0, int64_t* out_labels, float* out_dist,

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void exact_merge_kernel(const TopEntry* __rest
 }
 
 // Range-query candidate generator: same scan, but every live row with dist <= radius is
-// appended to its query's candidate list (rescored and sorted by range_rescore_kernel).  QT queries per block, their fp64
+// appended to its query's candidate list (rescored and sorted by launch_range_rescore's kernels).  QT queries per block, their fp64
 // image [QT][ld] in LDS: launch_exact_range_scan picks 4 / 2 / 1 by the row width.
 template <int SPACE, int QT>
 __global__ __launch_bounds__(512) void exact_range_kernel(const FilterArgs a, const double radius, const int nblk,

@@ -64,50 +64,53 @@ bool filter_supported(int32_t ld) { return ld >= kFilterChunkK && (ld % kFilterC
 size_t filter_qimg_bytes(int32_t ld) { return (size_t)kFilterQueries * ld * 2; }
 
 
-// ------------------------------------------------------------------ query image
-// Qimg[kc][n][ks][lane][j] = bf16(q^[16n + (lane&15)][64kc + 16(2ks + (j>>2)) + 4(lane>>4) + (j&3)])
-// i.e. exactly the B-operand fragments of v_mfma_f32_16x16x32_bf16 for the k-order in which
-// the scan kernel receives its A fragments from the panel layout (layout.h).
-__global__ __launch_bounds__(256) void filter_prep_kernel(const FilterArgs a) {
-    const int nkc = a.ld / kFilterChunkK;
-    __bf16* img = reinterpret_cast<__bf16*>(a.qimg);
-    const int64_t total = (int64_t)nkc * kChunkVec * 8;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (int64_t)gridDim.x * blockDim.x) {
-        const int j = idx & 7;
-        const int lane = (idx >> 3) & 63;
-        const int ks = (idx >> 9) & 1;
-        const int n = (idx >> 10) & 15;
-        const int kc = (int)(idx >> 14);
-        const int q = 16 * n + (lane & 15);
-        // k order of the A fragments: fp32 panels give lane g the columns {4g..4g+3} of two 16-col groups,
-        // the bf16 shadow gives it 8 consecutive columns
-        const int col = a.Xb ? 64 * kc + 32 * ks + 8 * (lane >> 4) + j
-                             : 64 * kc + 16 * (2 * ks + (j >> 2)) + 4 * (lane >> 4) + (j & 3);
-        float v = 0.f;
-        if (q < a.nq) {
-            const double aux = a.qaux[q];
-            const double inv = a.space == kSpaceCosine ? aux : 1.0 / (aux + 1e-30);
-            v = a.Qpad[(int64_t)q * a.ld + col] * (float)inv;
-        }
-        img[idx] = (__bf16)v;
+hipError_t filter_set_body(FilterArgs& a) {
+    a.body = a.X8 ? kBodyI8 : (a.Xb ? kBodyBf16 : kBodyFp32);
+    return a.body == kBodyI8 || filter_supported(a.ld) ? hipSuccess : hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------ query images
+// bf16: Qimg[kc][n][ks][lane][j] = bf16(q^[16n + (lane&15)][column]), i.e. exactly the B-operand fragments of
+// v_mfma_f32_16x16x32_bf16 for the k-order in which the scan kernel receives its A fragments.  The bf16 shadow gives lane
+// group g = lane>>4 eight consecutive columns, 64kc + 32ks + 8g + j; the fp32 panels (layout.h) give it the columns
+// {4g..4g+3} of two 16-column groups, 64kc + 16(2ks + (j>>2)) + 4g + (j&3).  Index of (query slot q, column c):
+__device__ __forceinline__ int64_t qimg_index(const int q, const int c, const bool shadow_order) {
+    int ks, g, j;
+    if (shadow_order) {
+        ks = (c >> 5) & 1; g = (c >> 3) & 3; j = c & 7;
+    } else {
+        const int t = (c >> 4) & 3;
+        ks = t >> 1; g = (c >> 2) & 3; j = (t & 1) * 4 + (c & 3);
     }
-    if (blockIdx.x == 0) {
-        const int q = threadIdx.x;  // 256 threads = kFilterQueries
-        const double nrm = q < a.nq ? (a.space == kSpaceCosine ? 0.0 : a.qaux[q]) : 0.0;
-        a.qscale[q] = a.space == kSpaceL2 ? (float)(2.0 * nrm) : 1.0f;
-        // per-query error term of the bound (see the header): E1q, plus the slack of the epilogue arithmetic
-        const double e1q = (q < a.nq ? (double)a.qerr[q] : 0.0) + 1.00390625 * (double)*a.row_err + (double)a.ld * 2.384185791015625e-07;
-        float ke = (float)(e1q * 1.000001) + (a.space == kSpaceCosine ? 2.0f : 1.0f) * kSlack;
-        a.ke[q] = float_bump(ke);
-        a.thr[q] = q < a.nq ? -3.0e38f : 3.4e38f;  // padded queries never admit anything
-        a.cnt[q] = 0;
-        a.overflow[q] = 0;
-        if (q == 0 && a.sqmin) {  // what filter_prep8_kernel's atomicMin / atomicMax start from (it runs after this kernel)
-            a.sqmin[0] = 0x7f7f7f7fu;  // 3.39e38: above every query scale
-            a.sqmin[1] = 0u;           // largest query error so far
-        }
-    }
+    return ((((int64_t)(c >> 6) * 16 + (q >> 4)) * 2 + ks) * 64 + ((q & 15) + 16 * g)) * 8 + j;
+}
+// int8: Qimg8[kc][n][ks][lane][j] = q8[16n + (lane&15)][128kc + 64ks + 16(lane>>4) + j]
+__device__ __forceinline__ int64_t qimg8_index(const int q, const int c) {
+    const int kc = c >> 7, ks = (c >> 6) & 1, g = (c >> 4) & 3, j = c & 15;
+    return ((((int64_t)kc * 16 + (q >> 4)) * 2 + ks) * 64 + ((q & 15) + 16 * g)) * 16 + j;
+}
+
+// The state every pass starts from, for query slot q (one thread per slot): score scale, the bf16 error term of the bound (see
+// the header: E1q, plus the slack of the epilogue arithmetic), threshold, empty list.  aux / qerr: the query's qaux and the
+// measured rounding error of its bf16 image (padded slots: 0); flagged: the query left the magnitude window -- to the pass it
+// is the zero query, and it starts flagged for the exact fallback like one whose list overflowed.
+__device__ __forceinline__ void prep_query_state(const FilterArgs& a, const int q, const bool real, const bool flagged,
+                                                 const double aux, const float qerr) {
+    const double nrm = real && !flagged && a.space != kSpaceCosine ? aux : 0.0;
+    a.qscale[q] = a.space == kSpaceL2 ? (float)(2.0 * nrm) : 1.0f;
+    const double e1q = (real ? (double)qerr : 0.0) + 1.00390625 * (double)*a.row_err + (double)a.ld * 2.384185791015625e-07;
+    const float ke = (float)(e1q * 1.000001) + (a.space == kSpaceCosine ? 2.0f : 1.0f) * kSlack;
+    a.ke[q] = float_bump(ke);
+    a.thr[q] = real ? -3.0e38f : 3.4e38f;  // padded queries never admit anything
+    a.cnt[q] = 0;
+    a.overflow[q] = flagged ? 1u : 0u;
+}
+
+// The state alone, from what launch_query_prep left in a.qaux / a.qerr (the exact branch of a range call: no window flag)
+__global__ __launch_bounds__(kFilterQueries) void filter_state_kernel(const FilterArgs a) {
+    const int q = threadIdx.x;
+    const bool real = q < a.nq;
+    prep_query_state(a, q, real, false, real ? a.qaux[q] : 0.0, real ? a.qerr[q] : 0.f);
 }
 
 // thr[q] from the exact distance of the k-th nearest seed row
@@ -159,7 +162,7 @@ __device__ __forceinline__ void scan_epilogue(const FilterArgs& a, const f32x4 (
                                               const float* thr_l, const float* sq_l, const float* ke_l, float* dump,
                                               const int c16, const int qbase = 0) {
     // qbase: first query of the 16*NQT this call covers (thr_l / sq_l / ke_l are already offset by it; the lists are not)
-    // ke = the query's error term (filter_prep_kernel).  Per-row constants:
+    // ke = the query's error term (prep_query_state).  Per-row constants:
     //   cosine  u = a*p0 + ke             (p0 = 1/(|x|+1e-30))
     //   ip      u = a + ke*p0             (p0 = |x|)
     //   l2      u = sq*(a + ke*p0) + p1   (p1 = -|x|^2 (1-slack))
@@ -504,7 +507,7 @@ __global__ __launch_bounds__(NW * 64) void filter_scan_narrow_kernel(const Filte
         sq_l[threadIdx.x] = sqv;
         ke_l[threadIdx.x] = kev;
     }
-    // query image (filter_prep_kernel's [kc][n][ks][lane] order) -> LDS [2kc+ks][n < NQT][lane]
+    // query image (qimg_index's / qimg8_index's [kc][n][ks][lane] order) -> LDS [2kc+ks][n < NQT][lane]
     {
         const uint4* qimg = reinterpret_cast<const uint4*>(I8 ? a.qimg8 : a.qimg);
         for (int v = threadIdx.x; v < nsteps * NQT * 64; v += NW * 64) {
@@ -1430,9 +1433,8 @@ __global__ __launch_bounds__(kRankThreads) void range_rank_kernel(const FilterAr
 }
 
 // ------------------------------------------------------------------ launchers
-hipError_t launch_filter_prep(const FilterArgs& a, hipStream_t s) {
-    const int nkc = a.ld / kFilterChunkK;
-    filter_prep_kernel<<<nkc > 0 ? nkc * 16 : 1, 256, 0, s>>>(a);  // nkc == 0: only the per-query state
+hipError_t launch_filter_state(const FilterArgs& a, hipStream_t s) {
+    filter_state_kernel<<<1, kFilterQueries, 0, s>>>(a);
     return hipGetLastError();
 }
 
@@ -1715,62 +1717,14 @@ hipError_t launch_shadow8_rows(const float* X, const float* rn, void* X8, float*
     return hipGetLastError();
 }
 
-// Query image: Qimg8[kc][n][ks][lane][j] = q8[16n + (lane&15)][128kc + 64ks + 16(lane>>4) + j], one block per query
-// slot; also sq8, and ke = the int8 error term (overrides filter_prep_kernel's, so that every kernel of the pass --
-// the bf16 seeding pass included -- uses the same, larger eps).
-__global__ __launch_bounds__(256) void filter_prep8_kernel(const FilterArgs a) {
-    __shared__ float red[4];
-    __shared__ double dred[4];
-    const int q = blockIdx.x;
-    const int ld = a.ld;
-    int8_t* img = reinterpret_cast<int8_t*>(a.qimg8);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float inv = 0.f;
-    if (q < a.nq) inv = a.space == kSpaceCosine ? (float)a.qaux[q] : (float)(1.0 / (a.qaux[q] + 1e-30));  // as filter_prep_kernel
-    float amax = 0.f;
-    for (int c = threadIdx.x; c < ld; c += 256) {
-        const float v = q < a.nq ? a.Qpad[(int64_t)q * ld + c] * inv : 0.f;
-        amax = __builtin_fmaxf(amax, __builtin_fabsf(v));
-    }
-    for (int off = 32; off > 0; off >>= 1) amax = __builtin_fmaxf(amax, __shfl_xor(amax, off));
-    if (lane == 0) red[wave] = amax;
-    __syncthreads();
-    amax = __builtin_fmaxf(__builtin_fmaxf(red[0], red[1]), __builtin_fmaxf(red[2], red[3]));
-    const float sq = amax > 0.f ? amax / 127.0f : 1.0f;
-    const float isq = 1.0f / sq;
-    double err2 = 0.0;
-    for (int c = threadIdx.x; c < a.ld8; c += 256) {  // (columns ld..ld8 of the image: zeros, like the shadow's)
-        const float v = q < a.nq && c < ld ? a.Qpad[(int64_t)q * ld + c] * inv : 0.f;
-        float t = __builtin_rintf(v * isq);
-        t = __builtin_fminf(127.f, __builtin_fmaxf(-127.f, t));
-        const double e = (double)v - (double)sq * (double)t;
-        err2 += e * e;
-        const int kc = c >> 7, ks = (c >> 6) & 1, g = (c >> 4) & 3, j = c & 15;
-        const int n = q >> 4, l = (q & 15) + 16 * g;
-        img[((((int64_t)kc * 16 + n) * 2 + ks) * 64 + l) * 16 + j] = (int8_t)t;
-    }
-    for (int off = 32; off > 0; off >>= 1) err2 += __shfl_xor(err2, off);
-    if (lane == 0) dred[wave] = err2;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double eq8 = __builtin_sqrt(dred[0] + dred[1] + dred[2] + dred[3]) * 1.000001 + 1e-12;
-        a.sq8[q] = sq;
-        a.ke8[q] = q < a.nq ? float_above(eq8) : 0.f;  // finished by filter_prep8_fin_kernel
-        if (q < a.nq) {
-            atomicMin(a.sqmin, __float_as_uint(sq));                    // positive floats order like their bits
-            atomicMax(a.sqmin + 1, __float_as_uint(float_above(eq8)));  // the largest query error of the pass
-        }
-    }
-}
-
 // Second phase (one block): the error terms that need the smallest query scale of the pass.
 //   cosine  rows carry their own error b: the scan tests  w + b K >= (thr - ke8)/sq8  with K = (1 + max eq8)/min sq8,
 //           i.e. the bound u = sq8 w + ke8 + (1 + max eq8) b sq8/min sq8 >= <q^,x>/|x|;  ke8 = eq8 + roundings + slack
 //           (|q8 image| <= 1 + eq8: a query with one dominant component quantises its small ones badly, eq8 ~ 0.1)
 //   l2, ip  index-wide row error: ke = eq8 + (1 + eq8) rmax8 + roundings + slack (x |x|)
-//   keb     the bf16 term (filter_prep_kernel's ke): what the bf16 seeding pass adds to its bounds
-//   ke      covers both kinds of entry (the update kernel's lower bounds u - 2 eps): the larger of the two, with the
-//           int8 row term at its index-wide maximum
+//   ke      what the update kernel's lower bounds u - 2 eps use: the larger of the int8 term, its row term at the index-wide
+//           maximum, and the bf16 term (prep_query_state) -- no pass mixes the two kinds of entry any more, but the value
+//           sets the candidate counts and stays as it is
 // (device function: also called by filter_prep_fused_kernel for one-query passes; needs a.ke8[q] = eq8 and a.ke[q] = the bf16 term)
 __device__ __forceinline__ void prep8_fin_query(const FilterArgs& a, const int q, const float sqmin, const float eqmax_f) {
     const double eqmax = (double)eqmax_f;
@@ -1779,24 +1733,22 @@ __device__ __forceinline__ void prep8_fin_query(const FilterArgs& a, const int q
     const double rnd = 4.0 * 5.9604644775390625e-08;  // float(I) * rp8 (+ b K) * sq8: roundings of a value <= ~1
     const double slack = (a.space == kSpaceCosine ? 2.0 : 1.0) * (double)kSlack;
     const double e8 = eq8 + (1.0 + (a.space == kSpaceCosine ? eqmax : eq8)) * 1.000001 * (double)*a.row_err8 * ratio + rnd;
-    const double eb = (double)a.ke[q];  // bf16 term incl. its slack (filter_prep_kernel)
-    a.keb[q] = a.ke[q];
+    const double eb = (double)a.ke[q];  // bf16 term incl. its slack (prep_query_state)
     const double big = (e8 * 1.000001 + slack) > eb ? (e8 * 1.000001 + slack) : eb;
     a.ke[q] = float_above(big);
     a.ke8[q] = float_above((eq8 + rnd) * 1.000001 + slack);
     if (q == 0) a.ke8[kFilterQueries] = float_above((1.0 + eqmax) / (double)sqmin * 1.000001);
 }
 
-__global__ __launch_bounds__(256) void filter_prep8_fin_kernel(const FilterArgs a, const int reset) {
+__global__ __launch_bounds__(256) void filter_prep8_fin_kernel(const FilterArgs a) {
     const int q = threadIdx.x;
     const float sqmin = __uint_as_float(a.sqmin[0]);
     const float eqmax = __uint_as_float(a.sqmin[1]);
-    if (reset) {  // fused prep: nobody re-initialises the two scalars before the next pass's atomics -- this kernel does, once
-        __syncthreads();  // every thread of this (only) block has read them
-        if (q == 0) {
-            a.sqmin[0] = 0x7f7f7f7fu;
-            a.sqmin[1] = 0u;
-        }
+    // nobody else re-initialises the two scalars before the next pass's atomics -- this kernel does, once
+    __syncthreads();  // every thread of this (only) block has read them
+    if (q == 0) {
+        a.sqmin[0] = 0x7f7f7f7fu;  // 3.39e38: above every query scale
+        a.sqmin[1] = 0u;           // largest query error so far
     }
     prep8_fin_query(a, q, sqmin, eqmax);
 }
@@ -1815,14 +1767,37 @@ __device__ __forceinline__ bool query_leaves_window(double qn, double xmax, int 
     return top < 5.9604644775390625e-08;  // 2^-24
 }
 
+// One block quantises query slot q into the int8 image: component c is src[c] * invf in steps of sq, clamped to +-127 (src ==
+// nullptr: the zero query; columns ld..ld8 of the image: zeros, like the shadow's).  Returns to every thread the block's
+// eq8 = |q^ - sq q8|, measured and rounded up.  dred: four doubles of LDS nobody else is using.
+__device__ __forceinline__ double quantise_query8(const FilterArgs& a, const float* src, const float invf, const float sq,
+                                                  const int q, double* dred) {
+    const float isq = 1.0f / sq;
+    int8_t* img8 = reinterpret_cast<int8_t*>(a.qimg8);
+    double err2 = 0.0;
+    for (int c = threadIdx.x; c < a.ld8; c += 256) {
+        const float v = src && c < a.ld ? src[c] * invf : 0.f;
+        float t = __builtin_rintf(v * isq);
+        t = __builtin_fminf(127.f, __builtin_fmaxf(-127.f, t));
+        const double e = (double)v - (double)sq * (double)t;
+        err2 += e * e;
+        img8[qimg8_index(q, c)] = (int8_t)t;
+    }
+    for (int off = 32; off > 0; off >>= 1) err2 += __shfl_xor(err2, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) dred[threadIdx.x >> 6] = err2;
+    __syncthreads();
+    return __builtin_sqrt(dred[0] + dred[1] + dred[2] + dred[3]) * 1.000001 + 1e-12;
+}
+
 // ------------------------------------------------------------------ one launch for everything a pass needs of its queries
-// query_prep_kernel (padded copy, norm, bf16 rounding error) + filter_prep_kernel (bf16 image, per-query state) +
-// filter_prep8_kernel (int8 image, scale, error) as ONE kernel, block q = query q of the pass: three launches and their
-// two kernel boundaries less per pass (round 3; ~14 us of a 256-query wave, ~20 us of a batch-1 call).  Same arithmetic,
-// value for value, as the three kernels it replaces (they still serve the range path and the exact scans).
+// Block q = query q of the pass: (1) the zero-padded copy, the norm and the window flag; (2) the rounding error of the bf16
+// image -- and the image itself in the k-order of a bf16 / fp32 body -- then the per-query state; (3) in an int8 pass the
+// int8 image, its scale and error (l2: only the query's largest component; filter_prep8_l2c_kernel builds the images).
+// Steps 1 and 2 compute, value for value, what launch_query_prep gives the exact scans.
 __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs a, const float* __restrict__ queries, const int32_t dim,
                                                                 float* __restrict__ Qpad, double* __restrict__ qaux,
-                                                                float* __restrict__ qerr, const int want_i8) {
+                                                                float* __restrict__ qerr) {
     __shared__ double dred[4];
     __shared__ float fred[4];
     __shared__ double s_inv;
@@ -1832,7 +1807,7 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
     const int ld = a.ld;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* dst = Qpad + (int64_t)q * ld;
-    // 1. zero-padded copy and norm (query_prep_kernel)
+    // 1. zero-padded copy and norm
     double s = 0.0;
     if (real) {
         const float* src = queries + (int64_t)q * dim;
@@ -1858,24 +1833,15 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
     const bool live = real && !s_flag;
     const double inv = s_inv;
     const float invf = (float)inv;
-    // 2. bf16 image in B-fragment order (filter_prep_kernel) and its measured rounding error (query_prep_kernel)
+    // 2. the measured rounding error of the bf16 image (an int8 pass needs it too: ke reads it) and, for the body that reads
+    // it, the image in B-fragment order
     __bf16* img = reinterpret_cast<__bf16*>(a.qimg);
-    const bool want_bf16 = ld % kFilterChunkK == 0;  // (another ld has no bf16 / fp32 filter body: only the int8 image is used)
-    const int n16 = q >> 4, c16 = q & 15;
     double e2 = 0.0;
     float amax = 0.f;
     for (int c = threadIdx.x; c < ld; c += 256) {
         const float x = live ? dst[c] : 0.f;  // (this thread wrote dst[c] itself)
         const float v = x * invf;
-        const __bf16 b = (__bf16)v;
-        int kc = c >> 6, ks, g, j;
-        if (a.Xb) {  // shadow k order: 8 consecutive columns per lane group
-            ks = (c >> 5) & 1; g = (c >> 3) & 3; j = c & 7;
-        } else {     // fp32 panels: columns {4g..4g+3} of two 16-column groups
-            const int t = (c >> 4) & 3;
-            ks = t >> 1; g = (c >> 2) & 3; j = (t & 1) * 4 + (c & 3);
-        }
-        if (want_bf16) img[((((int64_t)kc * 16 + n16) * 2 + ks) * 64 + (c16 + 16 * g)) * 8 + j] = b;
+        if (a.body != kBodyI8) img[qimg_index(q, c, a.body == kBodyBf16)] = (__bf16)v;
         if (c < dim) {
             const double e = (double)x * inv - (double)(float)(__bf16)(x * invf);
             e2 = __builtin_fma(e, e, e2);
@@ -1896,49 +1862,25 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
         float e = (float)(__builtin_sqrt((dred[0] + dred[1]) + (dred[2] + dred[3])) * 1.000001);
         e = float_bump(e);  // never below the true error
         if (real) qerr[q] = e;
-        // per-query state of the pass (filter_prep_kernel, block 0)
-        const double nrm = live ? (a.space == kSpaceCosine ? 0.0 : qaux[q]) : 0.0;
-        a.qscale[q] = a.space == kSpaceL2 ? (float)(2.0 * nrm) : 1.0f;
-        const double e1q = (real ? (double)e : 0.0) + 1.00390625 * (double)*a.row_err + (double)ld * 2.384185791015625e-07;
-        const float ke = (float)(e1q * 1.000001) + (a.space == kSpaceCosine ? 2.0f : 1.0f) * kSlack;
-        a.ke[q] = float_bump(ke);
-        a.thr[q] = real ? -3.0e38f : 3.4e38f;  // padded queries never admit anything
-        a.cnt[q] = 0;
-        a.overflow[q] = s_flag ? 1u : 0u;
+        prep_query_state(a, q, real, s_flag, real ? qaux[q] : 0.0, e);
     }
-    if (!want_i8) return;
+    if (a.body != kBodyI8) return;
     amax = __builtin_fmaxf(__builtin_fmaxf(fred[0], fred[1]), __builtin_fmaxf(fred[2], fred[3]));
     if (a.l2c) {
-        // l2 with one quantisation step for the whole pass (round 4: filter_prep8_l2c_kernel builds the images once the pass's
-        // largest raw component is known): here only this query's largest |q_i| = max |q^_i| x |q|, rounded up
+        // l2 with one quantisation step for the whole pass (filter_prep8_l2c_kernel builds the images once the pass's largest
+        // raw component is known): here only this query's largest |q_i| = max |q^_i| x |q|, rounded up
         if (threadIdx.x == 0) a.rmaxq[q] = live ? float_above((double)amax * (qaux[q] + 1e-30) * 1.000001) : 0.f;
         return;
     }
-    // 3. int8 image, scale and error (filter_prep8_kernel); a.sqmin[] was left initialised by the previous pass's fin kernel
+    // 3. int8 image, scale and error; a.sqmin[] was left initialised by the previous pass's fin kernel
     const float sq = amax > 0.f ? amax / 127.0f : 1.0f;
-    const float isq = 1.0f / sq;
-    int8_t* img8 = reinterpret_cast<int8_t*>(a.qimg8);
-    double err2 = 0.0;
-    for (int c = threadIdx.x; c < a.ld8; c += 256) {  // (columns ld..ld8 of the image: zeros, like the shadow's)
-        const float v = live && c < ld ? dst[c] * invf : 0.f;
-        float t = __builtin_rintf(v * isq);
-        t = __builtin_fminf(127.f, __builtin_fmaxf(-127.f, t));
-        const double e = (double)v - (double)sq * (double)t;
-        err2 += e * e;
-        const int kc = c >> 7, ks = (c >> 6) & 1, g = (c >> 4) & 3, j = c & 15;
-        img8[((((int64_t)kc * 16 + n16) * 2 + ks) * 64 + (c16 + 16 * g)) * 16 + j] = (int8_t)t;
-    }
-    for (int off = 32; off > 0; off >>= 1) err2 += __shfl_xor(err2, off);
-    __syncthreads();
-    if (lane == 0) dred[wave] = err2;
-    __syncthreads();
+    const double eq8 = quantise_query8(a, live ? dst : nullptr, invf, sq, q, dred);
     if (threadIdx.x == 0) {
-        const double eq8 = __builtin_sqrt(dred[0] + dred[1] + dred[2] + dred[3]) * 1.000001 + 1e-12;
         a.sq8[q] = sq;
         a.ke8[q] = real ? float_above(eq8) : 0.f;  // finished by filter_prep8_fin_kernel
         if (real && a.nq > 1) {
-            atomicMin(a.sqmin, __float_as_uint(sq));
-            atomicMax(a.sqmin + 1, __float_as_uint(float_above(eq8)));
+            atomicMin(a.sqmin, __float_as_uint(sq));                    // positive floats order like their bits
+            atomicMax(a.sqmin + 1, __float_as_uint(float_above(eq8)));  // the largest query error of the pass
         }
         if (real && a.nq == 1) {
             // a one-query pass (BASELINE configs[1]): the smallest scale / largest error "of the pass" are this query's own,
@@ -1946,7 +1888,7 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
             prep8_fin_query(a, 0, sq, float_above(eq8));
         }
     }
-    if (want_i8 && a.nq == 1 && q > 0 && threadIdx.x == 0) prep8_fin_query(a, q, 1.0f, 0.0f);  // padded slots (never admitted)
+    if (a.nq == 1 && q > 0 && threadIdx.x == 0) prep8_fin_query(a, q, 1.0f, 0.0f);  // padded slots (never admitted)
 }
 
 // l2, common query scale (a.l2c = 2 + parity of the pass; round 4).  The l2 score in the scan's units is
@@ -1961,8 +1903,6 @@ __global__ __launch_bounds__(256) void filter_prep_fused_kernel(const FilterArgs
 __global__ __launch_bounds__(256) void filter_prep8_l2c_kernel(const FilterArgs a) {
     __shared__ double dred[4];
     const int q = blockIdx.x;
-    const int ld = a.ld;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool real = q < a.nq;
     // The pass's common step follows the largest raw component of its TYPICAL queries: every block finds, from the 256 per-query
     // maxima the fused kernel left in a.sq8, the median m of the real queries' and takes QMAX = the largest maximum <= 4 m.  One
@@ -1999,26 +1939,10 @@ __global__ __launch_bounds__(256) void filter_prep8_l2c_kernel(const FilterArgs 
     const float SQ = qmax > 0.f ? float_above((double)qmax * (2.0 / 127.0) * 1.000001) : 1.0f;
     const bool live = real && a.overflow[q] == 0u;  // (flagged by the fused kernel: the zero query to this pass)
     const double nrm = live ? a.qaux[q] : 0.0;  // l2: qaux = |q|
-    const float invf = (float)(1.0 / (nrm + 1e-30));  // as filter_prep_kernel forms q^ = q / (|q| + 1e-30)
+    const float invf = (float)(1.0 / (nrm + 1e-30));  // as the fused kernel forms q^ = q / (|q| + 1e-30)
     const float sq = nrm > 0.0 ? (float)((double)SQ / (2.0 * nrm)) : 1.0f;
-    const float isq = 1.0f / sq;
-    int8_t* img8 = reinterpret_cast<int8_t*>(a.qimg8);
-    const int n16 = q >> 4, c16 = q & 15;
-    double err2 = 0.0;
-    for (int c = threadIdx.x; c < a.ld8; c += 256) {  // (columns ld..ld8 of the image: zeros, like the shadow's)
-        const float v = live && c < ld ? a.Qpad[(int64_t)q * ld + c] * invf : 0.f;
-        float t = __builtin_rintf(v * isq);
-        t = __builtin_fminf(127.f, __builtin_fmaxf(-127.f, t));
-        const double e = (double)v - (double)sq * (double)t;
-        err2 += e * e;
-        const int kc = c >> 7, ks = (c >> 6) & 1, g = (c >> 4) & 3, j = c & 15;
-        img8[((((int64_t)kc * 16 + n16) * 2 + ks) * 64 + (c16 + 16 * g)) * 16 + j] = (int8_t)t;
-    }
-    for (int off = 32; off > 0; off >>= 1) err2 += __shfl_xor(err2, off);
-    if (lane == 0) dred[wave] = err2;
-    __syncthreads();
+    const double eq8 = quantise_query8(a, live ? a.Qpad + (int64_t)q * a.ld : nullptr, invf, sq, q, dred);
     if (threadIdx.x == 0) {
-        const double eq8 = __builtin_sqrt(dred[0] + dred[1] + dred[2] + dred[3]) * 1.000001 + 1e-12;
         a.sq8[q] = sq;
         a.ke8[q] = real ? float_above(eq8) : 0.f;
         prep8_fin_query(a, q, 1.0f, 0.0f);  // (l2: the query's own error only; a.ke[q] = the bf16 term the fused kernel left)
@@ -2027,18 +1951,9 @@ __global__ __launch_bounds__(256) void filter_prep8_l2c_kernel(const FilterArgs 
 
 hipError_t launch_filter_prep_fused(const FilterArgs& a, const float* queries, int32_t dim, float* Qpad, double* qaux, float* qerr,
                                     hipStream_t s) {
-    const int want_i8 = a.X8 != nullptr;
-    if (!want_i8 && !filter_supported(a.ld)) return hipErrorInvalidValue;
-    filter_prep_fused_kernel<<<kFilterQueries, 256, 0, s>>>(a, queries, dim, Qpad, qaux, qerr, want_i8);
-    if (want_i8 && a.l2c) filter_prep8_l2c_kernel<<<kFilterQueries, 256, 0, s>>>(a);
-    else if (want_i8 && a.nq > 1) filter_prep8_fin_kernel<<<1, kFilterQueries, 0, s>>>(a, 1);  // (one query: done inside the kernel above)
-    return hipGetLastError();
-}
-
-hipError_t launch_filter_prep8(const FilterArgs& a, hipStream_t s) {
-    // a.sqmin[0..1] were initialised by filter_prep_kernel (always launched first: launch_filter_prep)
-    filter_prep8_kernel<<<kFilterQueries, 256, 0, s>>>(a);
-    filter_prep8_fin_kernel<<<1, kFilterQueries, 0, s>>>(a, 1);
+    filter_prep_fused_kernel<<<kFilterQueries, 256, 0, s>>>(a, queries, dim, Qpad, qaux, qerr);
+    if (a.body == kBodyI8 && a.l2c) filter_prep8_l2c_kernel<<<kFilterQueries, 256, 0, s>>>(a);
+    else if (a.body == kBodyI8 && a.nq > 1) filter_prep8_fin_kernel<<<1, kFilterQueries, 0, s>>>(a);  // (one query: done inside the kernel above)
     return hipGetLastError();
 }
 
@@ -2560,27 +2475,31 @@ __global__ __launch_bounds__(256) void filter_refine_thr_kernel(const FilterArgs
     }
 }
 
-// fuse: also do the threshold update's pruning (then filter_update_kernel is not needed for the round); possible while
+// The refine kernel can also do the threshold update's pruning (then filter_update_kernel is not needed for the round) while
 // the lists' LDS copy fits beside the query (ld <= 2048)
 bool filter_refine_can_fuse(const FilterArgs& a) { return a.ld <= 2048; }
 
-hipError_t launch_filter_refine_thr(const FilterArgs& a, int32_t k, int32_t forced_cnt, bool fuse, hipStream_t s) {
-    const size_t lds = (size_t)a.ld * sizeof(double) + 65 * sizeof(double) + 64 * 4 + 256 * 4 + 24 * 4 + (size_t)kCandCap * 4 +
-                       (fuse ? (size_t)kCandCap * sizeof(CandEntry) : 0);
-    auto kern = a.space == kSpaceL2 ? filter_refine_thr_kernel<kSpaceL2>
-                : a.space == kSpaceCosine ? filter_refine_thr_kernel<kSpaceCosine> : filter_refine_thr_kernel<kSpaceIp>;
-    static std::atomic<uint64_t> configured[3];
-    if (hipError_t e = ensure_dynamic_lds(configured[a.space], reinterpret_cast<const void*>(kern), 160 * 1024); e != hipSuccess)
-        return e;
-    // rows scored exactly per query and round: 1.5 k (at least 16, at most 64); MLVDB_REFINE_PICKS overrides (tuning; = k
-    // gives "the smallest exact score of the k largest bounds").  10M x 768, k = 10, per wave: 10 picks 1.962 ms, 16 1.935,
-    // 30 1.953, 48 1.976 (profiles/r02/scan_ab_refine_picks_10m.txt): more picks are more page walks per round
+// rows scored exactly per query and round: 1.5 k (at least 16, at most 64); MLVDB_REFINE_PICKS overrides (tuning; = k
+// gives "the smallest exact score of the k largest bounds").  10M x 768, k = 10, per wave: 10 picks 1.962 ms, 16 1.935,
+// 30 1.953, 48 1.976 (profiles/r02/scan_ab_refine_picks_10m.txt): more picks are more page walks per round
+static int refine_picks(const FilterArgs& a, int32_t k) {
     const int pv = a.tn ? a.tn->refine_picks : 0;
     int picks = pv > 0 ? pv : k + k / 2;
     if (pv <= 0 && picks < 16) picks = 16;
-    picks = picks < k ? k : (picks > 64 ? 64 : picks);
-    kern<<<a.nq, 256, lds, s>>>(a, k, forced_cnt, fuse, picks, FinishOut{});
-    return hipGetLastError();
+    return picks < k ? k : (picks > 64 ? 64 : picks);
+}
+
+// one launch of the refine kernel: the query as fp64, its selection scratch and keys, and (lists: pruning too) the list's copy
+template <bool FINISH>
+static hipError_t launch_refine(const FilterArgs& a, int32_t k, int32_t forced_cnt, bool lists, const FinishOut& fo, hipStream_t s) {
+    const size_t lds = (size_t)a.ld * sizeof(double) + 65 * sizeof(double) + 64 * 4 + 256 * 4 + 24 * 4 + (size_t)kCandCap * 4 +
+                       (lists ? (size_t)kCandCap * sizeof(CandEntry) : 0);
+    return with_space(a.space, [&](auto sp) {
+        constexpr auto kern = filter_refine_thr_kernel<decltype(sp)::value, FINISH>;
+        if (hipError_t e = ensure_instance_lds<kern>(lds, 160 * 1024); e != hipSuccess) return e;
+        kern<<<a.nq, 256, lds, s>>>(a, k, forced_cnt, lists, refine_picks(a, k), fo);
+        return hipGetLastError();
+    });
 }
 
 // The last refine of a pass of <= 8 queries + rescoring + ranking in one launch (filter_refine_can_fuse(a) must hold, k <= 64).
@@ -2588,20 +2507,7 @@ hipError_t launch_filter_finish_small(const FilterArgs& a, int32_t k, int32_t q0
                                       int32_t* out_counts, double* out_d64, unsigned long long* rescored, int32_t* qsel,
                                       int32_t* nflag, hipStream_t s) {
     if (!filter_refine_can_fuse(a) || k < 1 || k > 64) return hipErrorInvalidValue;
-    const size_t lds = (size_t)a.ld * sizeof(double) + 65 * sizeof(double) + 64 * 4 + 256 * 4 + 24 * 4 + (size_t)kCandCap * 4 +
-                       (size_t)kCandCap * sizeof(CandEntry);
-    auto kern = a.space == kSpaceL2 ? filter_refine_thr_kernel<kSpaceL2, true>
-                : a.space == kSpaceCosine ? filter_refine_thr_kernel<kSpaceCosine, true> : filter_refine_thr_kernel<kSpaceIp, true>;
-    static std::atomic<uint64_t> configured[3];
-    if (hipError_t e = ensure_dynamic_lds(configured[a.space], reinterpret_cast<const void*>(kern), 160 * 1024); e != hipSuccess)
-        return e;
-    const int pv = a.tn ? a.tn->refine_picks : 0;
-    int picks = pv > 0 ? pv : k + k / 2;
-    if (pv <= 0 && picks < 16) picks = 16;
-    picks = picks < k ? k : (picks > 64 ? 64 : picks);
-    FinishOut fo{q0, out_labels, out_dist, out_counts, out_d64, rescored, qsel, nflag};
-    kern<<<a.nq, 256, lds, s>>>(a, k, -1, true, picks, fo);
-    return hipGetLastError();
+    return launch_refine<true>(a, k, -1, true, FinishOut{q0, out_labels, out_dist, out_counts, out_d64, rescored, qsel, nflag}, s);
 }
 
 template <int SPACE, bool XB, bool DENSE = false>
@@ -2634,7 +2540,7 @@ static size_t narrow_lds(int32_t ld, int nqt, int nw, bool i8 = false) {
 bool filter_narrow_ok(const FilterArgs& a) {
     // a pass with an int8 shadow scans on the assembly body generated for 4 query tiles, at any batch size: this kernel streams
     // the bf16 shadow (its int8 form serves only the dense seeding pass: launch_filter_dense_scan)
-    if (!a.Xb || a.X8 || a.nq > kNarrowMaxQueries) return false;
+    if (a.body != kBodyBf16 || a.nq > kNarrowMaxQueries) return false;
     if (a.tn->scan_narrow == 0) return false;
     return narrow_lds(a.ld, narrow_nqt(a.nq), 8) <= kNarrowLdsMax;
 }
@@ -2707,133 +2613,108 @@ static hipError_t launch_scan_asm(const FilterArgs& a, int64_t row_begin, int64_
     return hipGetLastError();
 }
 
-// Picks the scan kernel for a launch: the narrow kernel for small batches it takes; the int8 body wherever the pass has an
-// int8 shadow; the bf16 body for an index that keeps a bf16 shadow; the compiler-scheduled kernel for an index without
-// shadow (fp32 rows converted in registers).  The handle's tuning state picks among them -- nothing here reads the
-// environment.
+// Picks the scan kernel for a launch from the pass's body: the narrow kernel for the small bf16 batches it takes, else the
+// hand-written bodies (tools/gen_scan_asm.py: one 8-wave workgroup per CU -- 256-row tiles, the query image staged once per
+// CU by LDS-DMA -- non-temporal X loads, ring of 4 k-steps: measured fastest, profiles/r01/scan_ab_*.txt) for the two
+// shadows, and the compiler-scheduled kernel for the fp32 rows converted in registers.  The handle's tuning state picks
+// among an int8 pass's tile counts -- nothing here reads the environment.
 template <int SPACE>
 static hipError_t launch_scan_space(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
     if (filter_narrow_ok(a)) return launch_scan_narrow<SPACE, false>(a, row_begin, row_end, s);  // appends to the lists itself
-    // hand-written bodies (tools/gen_scan_asm.py): one 8-wave workgroup per CU (256-row tiles: the query image is staged
-    // once per CU, by LDS-DMA), non-temporal X loads, ring of 4 k-steps -- measured fastest (profiles/r01/scan_ab_*.txt)
-    if (a.X8 && a.ld8 > 0) {  // int8 shadow (the caller attached it): ld8/128 chunks, an even number
-        // passes of <= 64 / <= 128 queries: the same body computing 4 / 8 of the 16 query tiles (round 4; SCAN_NQT=16 pads).
-        // l2: the folded admission test with per-row integer offsets (the pass computed them: api.hip prep_pass) is the only
-        // int8 body -- api.hip attaches the int8 shadow to an l2 pass only with rp8_cap and l2c set
+    if (a.body == kBodyI8) {  // ld8/128 chunks, an even number
+        // passes of <= 64 / <= 128 queries: the same body computing 4 / 8 of the 16 query tiles (SCAN_NQT=16 pads).
+        // l2: the folded admission test with per-row integer offsets (the pass computed them: api.hip begin_pass) is the
+        // only int8 body -- api.hip attaches the int8 shadow to an l2 pass only with rp8_cap and l2c set
         const int nqt = a.tn->scan_nqt > 0 ? a.tn->scan_nqt : (a.nq <= 64 ? 4 : (a.nq <= 128 ? 8 : 16));
         if (nqt <= 4 && a.nq <= 64) return launch_scan_asm<SPACE, 4, true, 4>(a, row_begin, row_end, s);
         if (nqt <= 8 && a.nq <= 128) return launch_scan_asm<SPACE, 4, true, 8>(a, row_begin, row_end, s);
         // a full pass of a k <= 64 kNN call over an image of six chunks (d = 641..768): four chunk buffers, two of them
-        // written once per launch, a tile stages two chunks instead of four.  Range and big-k passes append far more per wave
-        // than the staging area four buffers leave, so they stay on two
+        // written once per launch, a tile stages two chunks instead of four.  Range and big-k passes append far more per
+        // wave than the staging area four buffers leave, so they stay on two
         if (a.scan_q4 && a.nq > 128 && a.ld8 == kAsmQ4Chunks * 2 * kFilterChunkK)
             return launch_scan_asm<SPACE, 4, true, 16, 4>(a, row_begin, row_end, s);
         return launch_scan_asm<SPACE, 4, true, 16>(a, row_begin, row_end, s);
     }
-    if (a.Xb) {  // bf16 shadow; a ring of R k-steps needs the tile's k-steps (two per chunk) to be a multiple of R
+    if (a.body == kBodyBf16) {  // a ring of R k-steps needs the tile's k-steps (two per chunk) to be a multiple of R
         if ((a.ld / kFilterChunkK) % 2 == 0) return launch_scan_asm<SPACE, 4, false>(a, row_begin, row_end, s);
         return launch_scan_asm<SPACE, 2, false>(a, row_begin, row_end, s);
     }
-    // no shadow (or an int8-only index without usable int8 bounds): fp32 rows converted in registers
     return launch_scan_one<SPACE, false>(a, row_begin, row_end, s);
 }
 
-// Seeding pass over rows [0, row_end): every bound goes into the candidate lists (slot = row),
-// row_end <= kCandCap; then the update kernel (told that every list holds row_end rounded up to
-// the tile entries) turns the lists into thresholds and drops what is below them.
-static hipError_t launch_update(const FilterArgs& a, int32_t k, int32_t forced_cnt, hipStream_t s);
+hipError_t launch_filter_scan(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
+    return with_space(a.space, [&](auto sp) { return launch_scan_space<decltype(sp)::value>(a, row_begin, row_end, s); });
+}
 
+// The dense pass over rows [0, rows): every bound goes into the candidate lists (slot = row).
 hipError_t launch_filter_dense_scan(const FilterArgs& a, int64_t rows, hipStream_t s) {
-    const bool xb = a.Xb != nullptr;
-    if (filter_narrow_ok(a)) {
-        return a.space == kSpaceL2       ? launch_scan_narrow<kSpaceL2, true>(a, 0, rows, s)
-               : a.space == kSpaceCosine ? launch_scan_narrow<kSpaceCosine, true>(a, 0, rows, s)
-                                         : launch_scan_narrow<kSpaceIp, true>(a, 0, rows, s);
-    }
-    if (a.X8 && a.tn->seed_i8) {
-        // Round 3: the dense pass of a 256-query batch on the int8 shadow too -- the narrow kernel (64 queries' image in LDS)
-        // once per group of 64 queries (grid.y): 30 row tiles x 4 groups = 120 workgroups instead of the 30 of the bf16
-        // kernel below, half the MFMAs, and no pass of the default path reads the bf16 shadow any more (so an index need
-        // not keep one: 1.25x instead of 1.75x the corpus in HBM).  Every bound goes into the lists either way; the refine
-        // that follows takes the threshold from exact scores.
+    return with_space(a.space, [&](auto sp) {
+        constexpr int SPACE = decltype(sp)::value;
+        if (filter_narrow_ok(a)) return launch_scan_narrow<SPACE, true>(a, 0, rows, s);
+        if (a.body == kBodyBf16) return launch_scan_one<SPACE, true, true>(a, 0, rows, s);
+        if (a.body == kBodyFp32) return launch_scan_one<SPACE, false, true>(a, 0, rows, s);
+        // int8: the narrow kernel (64 queries' image in LDS) once per group of 64 queries (grid.y): 30 row tiles x 4 groups =
+        // 120 workgroups instead of the 30 of the 256-query kernel, half the MFMAs, and no pass of the default path reads a
+        // bf16 shadow (so an index need not keep one: 1.25x instead of 1.75x the corpus in HBM).  Every bound goes into the
+        // lists; the refine that follows takes the threshold from exact scores.
         // queries per group: as many as the image leaves room for in LDS (64 up to ld8 = 2304, 32 up to 4736, else 16)
         const int nqt = narrow_lds(a.ld8, 4, 4, true) <= kNarrowLdsMax ? 4 : (narrow_lds(a.ld8, 2, 4, true) <= kNarrowLdsMax ? 2 : 1);
         const int groups = (a.nq + 16 * nqt - 1) / (16 * nqt);
-#define MLVDB_SEED_I8(SP)                                                                                              \
-    (nqt == 4 ? launch_scan_narrow_n<SP, 4, true, 4, 4, true>(a, 0, rows, s, groups)                                  \
-              : nqt == 2 ? launch_scan_narrow_n<SP, 2, true, 4, 4, true>(a, 0, rows, s, groups)                       \
-                         : launch_scan_narrow_n<SP, 1, true, 4, 4, true>(a, 0, rows, s, groups))
-        return a.space == kSpaceL2 ? MLVDB_SEED_I8(kSpaceL2) : a.space == kSpaceCosine ? MLVDB_SEED_I8(kSpaceCosine) : MLVDB_SEED_I8(kSpaceIp);
-#undef MLVDB_SEED_I8
-    }
-    FilterArgs b = a;
-    if (a.X8) b.ke = a.keb;  // bf16 bounds get the bf16 error term; `a.ke` (update, below) covers int8 entries too
-    switch (a.space) {
-        case kSpaceL2:
-            return xb ? launch_scan_one<kSpaceL2, true, true>(b, 0, rows, s) : launch_scan_one<kSpaceL2, false, true>(b, 0, rows, s);
-        case kSpaceCosine:
-            return xb ? launch_scan_one<kSpaceCosine, true, true>(b, 0, rows, s)
-                      : launch_scan_one<kSpaceCosine, false, true>(b, 0, rows, s);
-        default:
-            return xb ? launch_scan_one<kSpaceIp, true, true>(b, 0, rows, s) : launch_scan_one<kSpaceIp, false, true>(b, 0, rows, s);
-    }
+        switch (nqt) {
+            case 4: return launch_scan_narrow_n<SPACE, 4, true, 4, 4, true>(a, 0, rows, s, groups);
+            case 2: return launch_scan_narrow_n<SPACE, 2, true, 4, 4, true>(a, 0, rows, s, groups);
+            default: return launch_scan_narrow_n<SPACE, 1, true, 4, 4, true>(a, 0, rows, s, groups);
+        }
+    });
 }
-
-hipError_t launch_filter_seed_scan(const FilterArgs& a, int64_t row_end, int32_t k, hipStream_t s) {
-    const int64_t rows = (row_end + kSeedTileRows - 1) / kSeedTileRows * kSeedTileRows;
-    hipError_t e = launch_filter_dense_scan(a, rows, s);
-    if (e != hipSuccess) return e;
-    if (a.X8) {  // int8 bounds are loose: the threshold comes from exact scores of the best bounds (the same kernel prunes)
-        const bool fuse = filter_refine_can_fuse(a);
-        if ((e = launch_filter_refine_thr(a, k, (int32_t)rows, fuse, s)) != hipSuccess || fuse) return e;
-    }
-    return launch_update(a, k, (int32_t)rows, s);  // lists -> thresholds; cnt[q] = survivors
-}
-
-hipError_t launch_filter_scan(const FilterArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
-    switch (a.space) {
-        case kSpaceL2: return launch_scan_space<kSpaceL2>(a, row_begin, row_end, s);
-        case kSpaceCosine: return launch_scan_space<kSpaceCosine>(a, row_begin, row_end, s);
-        default: return launch_scan_space<kSpaceIp>(a, row_begin, row_end, s);
-    }
-}
-
 
 static hipError_t launch_update(const FilterArgs& a, int32_t k, int32_t forced_cnt, hipStream_t s) {
     const size_t lds = (size_t)kCandCap * (sizeof(CandEntry) + sizeof(uint32_t)) + 256 * 4 + 64;  // hist + s_scan[16]
-    static std::atomic<uint64_t> configured{0};
-    if (hipError_t e = ensure_dynamic_lds(configured, reinterpret_cast<const void*>(filter_update_kernel), (int)lds); e != hipSuccess)
-        return e;
+    if (hipError_t e = ensure_instance_lds<filter_update_kernel>(lds, (int)lds); e != hipSuccess) return e;
     filter_update_kernel<<<a.nq, kUpdThreads, lds, s>>>(a, k, forced_cnt);
     return hipGetLastError();
 }
 
-hipError_t launch_filter_update(const FilterArgs& a, int32_t k, hipStream_t s) { return launch_update(a, k, -1, s); }
+hipError_t launch_filter_refine_update(const FilterArgs& a, int32_t k, int32_t forced_cnt, hipStream_t s) {
+    if (a.body == kBodyI8) {
+        const bool fuse = filter_refine_can_fuse(a);
+        if (hipError_t e = launch_refine<false>(a, k, forced_cnt, fuse, FinishOut{}, s); e != hipSuccess || fuse) return e;
+    }
+    return launch_update(a, k, forced_cnt, s);
+}
+
+// Seeding pass over rows [0, row_end), row_end <= kCandCap: the dense pass, then the lists (told that each holds row_end
+// rounded up to the tile entries) turned into thresholds.
+hipError_t launch_filter_seed_scan(const FilterArgs& a, int64_t row_end, int32_t k, hipStream_t s) {
+    const int64_t rows = (row_end + kSeedTileRows - 1) / kSeedTileRows * kSeedTileRows;
+    if (hipError_t e = launch_filter_dense_scan(a, rows, s); e != hipSuccess) return e;
+    return launch_filter_refine_update(a, k, (int32_t)rows, s);
+}
+
+// waves per block and LDS of the two exact scoring kernels: every wave keeps its current query in LDS as fp64; at least
+// 96 KiB per block, so that the dispatcher cannot put two on one CU
+struct ScoreShape {
+    int waves;
+    size_t lds;
+};
+constexpr int kScoreLdsMax = 144 * 1024;
+static ScoreShape score_shape(int32_t ld) {
+    int waves = kRescoreWaves;
+    while (waves > 1 && (size_t)waves * ld * sizeof(double) > (size_t)kScoreLdsMax) waves >>= 1;
+    return {waves, std::max((size_t)waves * ld * sizeof(double), (size_t)96 * 1024)};
+}
 
 hipError_t launch_filter_rescore(const FilterArgs& a, int32_t k, int32_t q0, int64_t* out_labels, float* out_dist,
                                  int32_t* out_counts, double* out_d64, unsigned long long* rescored, int32_t* qsel,
                                  int32_t* nflag, hipStream_t s) {
-    // every wave keeps its current query in LDS as fp64; at least 96 KiB per block, so that the dispatcher cannot put two on one CU
-    int waves = kRescoreWaves;
-    while (waves > 1 && (size_t)waves * a.ld * sizeof(double) > 144 * 1024) waves >>= 1;
-    const size_t lds = std::max((size_t)waves * a.ld * sizeof(double), (size_t)96 * 1024);
-    hipError_t e = hipSuccess;
-#define MLVDB_LAUNCH_RESCORE(SP)                                                                                     \
-    do {                                                                                                             \
-        auto kern = filter_rescore_score_kernel<SP>;                                                                 \
-        if (lds > 48 * 1024)                                                                                         \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)lds);                                                                       \
-        if (e == hipSuccess) kern<<<kRescoreGrid, waves * 64, lds, s>>>(a);                                          \
-    } while (0)
-    switch (a.space) {
-        case kSpaceL2: MLVDB_LAUNCH_RESCORE(kSpaceL2); break;
-        case kSpaceCosine: MLVDB_LAUNCH_RESCORE(kSpaceCosine); break;
-        default: MLVDB_LAUNCH_RESCORE(kSpaceIp); break;
-    }
-#undef MLVDB_LAUNCH_RESCORE
+    const ScoreShape sh = score_shape(a.ld);
+    hipError_t e = with_space(a.space, [&](auto sp) {
+        constexpr auto kern = filter_rescore_score_kernel<decltype(sp)::value>;
+        if (hipError_t ce = ensure_instance_lds<kern>(sh.lds, kScoreLdsMax); ce != hipSuccess) return ce;
+        kern<<<kRescoreGrid, sh.waves * 64, sh.lds, s>>>(a);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
-    if ((e = hipGetLastError()) != hipSuccess) return e;
     filter_rescore_rank_kernel<<<a.nq, kRankWaves * 64, 0, s>>>(a, k, q0, out_labels, out_dist, out_counts, out_d64, rescored, qsel,
                                                                 nflag);
     return hipGetLastError();
@@ -2843,9 +2724,7 @@ hipError_t launch_filter_rescore(const FilterArgs& a, int32_t k, int32_t q0, int
 static hipError_t launch_rank(const FilterArgs& a, int32_t q0, int64_t capacity, int64_t* out_labels, float* out_dist,
                               int64_t* out_counts, const KnnOut& knn, hipStream_t s) {
     const size_t lds_sort = (size_t)kCandCap * (sizeof(double) + sizeof(int32_t));  // the ranking kernel's {d[], l[]} (kCandCap % 64 == 0)
-    static std::atomic<uint64_t> rank_configured{0};
-    hipError_t e = ensure_dynamic_lds(rank_configured, reinterpret_cast<const void*>(range_rank_kernel), (int)lds_sort);
-    if (e != hipSuccess) return e;
+    if (hipError_t e = ensure_instance_lds<range_rank_kernel>(lds_sort, (int)lds_sort); e != hipSuccess) return e;
     range_rank_kernel<<<kRankGrid, kRankThreads, lds_sort, s>>>(a, q0, capacity, out_labels, out_dist, out_counts, knn);
     return hipGetLastError();
 }
@@ -2861,15 +2740,14 @@ static hipError_t launch_score_rank(const FilterArgs& a, float radius, int32_t q
                                     float* out_dist, int64_t* out_counts, const KnnOut& knn, hipStream_t s) {
     hipError_t e = hipMemsetAsync(a.rhit_cnt, 0, kFilterQueries * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    int waves = kRescoreWaves;
-    while (waves > 1 && (size_t)waves * a.ld * sizeof(double) > 144 * 1024) waves >>= 1;
-    const size_t lds_score = std::max((size_t)waves * a.ld * sizeof(double), (size_t)96 * 1024);
-    auto kern = a.space == kSpaceL2 ? range_score_flat_kernel<kSpaceL2>
-                : a.space == kSpaceCosine ? range_score_flat_kernel<kSpaceCosine> : range_score_flat_kernel<kSpaceIp>;
-    static std::atomic<uint64_t> score_configured[3];
-    if ((e = ensure_dynamic_lds(score_configured[a.space], reinterpret_cast<const void*>(kern), 144 * 1024)) != hipSuccess) return e;
-    kern<<<kRescoreGrid, waves * 64, lds_score, s>>>(a, radius);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const ScoreShape sh = score_shape(a.ld);
+    e = with_space(a.space, [&](auto sp) {
+        constexpr auto kern = range_score_flat_kernel<decltype(sp)::value>;
+        if (hipError_t ce = ensure_instance_lds<kern>(sh.lds, kScoreLdsMax); ce != hipSuccess) return ce;
+        kern<<<kRescoreGrid, sh.waves * 64, sh.lds, s>>>(a, radius);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
     return launch_rank(a, q0, capacity, out_labels, out_dist, out_counts, knn, s);
 }
 

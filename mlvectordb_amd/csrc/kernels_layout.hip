@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void tombstone_kernel(float* __restrict__ rn, 
 
 // One block per query: zero-padded copy + fp64 norm.
 // qerr[q] (optional) = |q^ - q^_b| rounded up, where q^ = q / (|q| + 1e-30) and q^_b is the bf16 query image exactly
-// as filter_prep_kernel computes it (fp32 product with the fp32 inverse norm, then RNE to bf16): the query half of
+// as filter_prep_fused_kernel computes it (fp32 product with the fp32 inverse norm, then RNE to bf16): the query half of
 // the filter's rounding bound.
 __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict__ queries, int32_t dim, int32_t ld,
                                                          int32_t space, float* __restrict__ Qpad,
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void query_prep_kernel(const float* __restrict
     if (threadIdx.x == 0) {
         const double aux = query_aux_from_sums(red, space);  // (query_norm.h: shared with the kernels that take a row as a query)
         qaux[q] = aux;
-        inv_s = space == kSpaceCosine ? aux : 1.0 / (aux + 1e-30);  // what filter_prep_kernel multiplies by
+        inv_s = space == kSpaceCosine ? aux : 1.0 / (aux + 1e-30);  // what filter_prep_fused_kernel multiplies by
     }
     if (!qerr) return;
     __syncthreads();

@@ -699,7 +699,6 @@ SCAN_VARIANTS = [  # (tuning variables, the shapes the variant runs)
     ({"MLVDB_I8": "0", "MLVDB_SHADOW": "bf16"},              # bf16 body: one 8-wave workgroup per CU, Q by LDS-DMA (rings of 4 and of 2 k-steps)
      [("ip", 64), ("ip", 768)]),
     ({"MLVDB_SHADOW": "bf16"}, [("ip", 64), ("ip", 768)]),   # both shadows kept (round 2's default): int8 scans, bf16 seeding / narrow passes off
-    ({"MLVDB_SEED_I8": "0"}, [("l2", 192), ("l2", 1536)]),   # int8-only index, seeding pass by the compiler kernel on the fp32 rows
     ({"MLVDB_I8_PAD": "0"},                                  # round 3: int8 shadow only where dim % 256 == 0
      [("cosine", 128), ("cosine", 768), ("l2", 256)]),
 ]
@@ -751,7 +750,7 @@ def test_passes_of_9_to_128_queries_compute_only_their_query_tiles(space, nq):
 
 
 RETIRED_TUNING_KEYS = ["RANGE_FLAT", "RANGE_I8", "NARROW_I8_MAX", "NARROW_WGS", "NARROW_BALANCE", "EVENT_FENCE", "SEED_EXACT",
-                       "PINNED_IO", "PREFIX_PF", "PREFIX_WAVES", "EXACT_NT", "EXACT_NBLK", "SCAN_L2E"]
+                       "PINNED_IO", "PREFIX_PF", "PREFIX_WAVES", "EXACT_NT", "EXACT_NBLK", "SCAN_L2E", "SEED_I8"]
 
 
 @pytest.mark.parametrize("key", RETIRED_TUNING_KEYS)

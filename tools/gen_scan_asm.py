@@ -595,7 +595,7 @@ def gen_admission(space):
     a = s.emit
     a("s_nop 15")   # XDL write -> v_accvgpr_read of the accumulators
     a("s_nop 7")
-    # ke = the query's error term from LDS (filter_prep_kernel).  Per-row constants (scan_epilogue):
+    # ke = the query's error term from LDS (prep_query_state).  Per-row constants (scan_epilogue):
     # cosine p0 = 1/(|x|+1e-30), u = a*p0 + ke; ip p0 = |x|, u = a + ke*p0; l2 p0 = |x|, p1 = -|x|^2 (1-slack),
     # u = sq*(a + ke*p0) + p1
     NR = 4 * MT
