@@ -11,6 +11,7 @@
  * (a third type, MLVDB_ATTR_INT64_LIST = 3, a set of int64 per row with ops of its own, lives in mlvdb_list.h)
  * (and a fourth, MLVDB_ATTR_SPARSE = 4, a sparse vector per row in the same storage, in mlvdb_sparse.h)
  * (and a fifth, MLVDB_ATTR_GEO = 5, a location per row stored as an int64 with ops of its own, in mlvdb_geo.h)
+ * (and a sixth, MLVDB_ATTR_BITS = 6, a bit code per row in the list column's storage, in mlvdb_bits.h)
  * so mlvdb_attr_set stores either as "absent" (which is how a caller clears a value); a caller whose data may hold
  * INT64_MIN as a real value must refuse it at ingest (the Python Index does).
  *

@@ -203,6 +203,22 @@ SPARSE_SIGNATURES = {
     "mlvdb_search_batch_sparse": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.POINTER(Where), _P, _P, _P, _P]),
 }
 
+# include/mlvdb_bits.h: binary vector columns -- one fixed-width bit code per row in the list column's storage, and their
+# exact top-k Hamming / Jaccard distance to a batch of codes
+ATTR_BITS = 6
+LIST_ATTR_CODES["bits"] = ATTR_BITS
+BITS_MAX_WORDS = 255
+BITS_HAMMING = 0
+BITS_JACCARD = 1
+BITS_METRIC_CODES = {"hamming": BITS_HAMMING, "jaccard": BITS_JACCARD}
+BITS_SIGNATURES = {
+    "mlvdb_bits_set": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
+    "mlvdb_bits_set_at": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, _P, _P, C.POINTER(C.c_int64)]),
+    "mlvdb_bits_get": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "mlvdb_search_batch_bits": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Where),
+                                          _P, _P, _P, _P]),
+}
+
 # include/mlvdb_hybrid.h: hybrid search -- a dense and a sparse kNN answer fused into one ranked list on the device
 FUSE_CODES = {"rrf": 0, "linear": 1, "relative": 2}
 HYBRID_MAX_FETCH_DENSE = 1024
@@ -260,7 +276,8 @@ def load() -> C.CDLL:
     for name, (restype, argtypes) in {**SIGNATURES, **WHERE_SIGNATURES, **WHERE_EACH_SIGNATURES,
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
-                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **HYBRID_SIGNATURES,
+                                      **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **BITS_SIGNATURES,
+                                      **HYBRID_SIGNATURES,
                                       **GEO_SIGNATURES, **STATS_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype

@@ -87,6 +87,8 @@ struct mlvdb_index {
     DevBuf list_sums, list_out;
     // sparse vector columns (mlvdb_sparse.h): a pass's tiles, term unions and weights; its answers
     DevBuf sparse_in, sparse_out;
+    // binary vector columns (mlvdb_bits.h): a pass's queries and their popcounts; its answers
+    DevBuf bits_in, bits_out;
     // hybrid search (mlvdb_hybrid.h): a chunk's dense and sparse queries, its two ranked lists, the union with the completed
     // components, and its outputs -- sized by the chunk (<= kHybridChunk queries), k and the fetch sizes, never by the corpus
     DevBuf hyb_q, hyb_list, hyb_union, hyb_out;
@@ -240,8 +242,9 @@ const TuningField* find_tuning_field(const char* key, size_t len) {
 
 // ---- attribute columns (mlvdb_where.h): the absent sentinel of a column type, and new column buffers for a capacity change
 int64_t attr_absent(int32_t type) { return type == MLVDB_ATTR_FLOAT64 ? (int64_t)0x7ff8000000000000ll : INT64_MIN; }
-// "has a slot and a pool": list columns (mlvdb_list.h) and sparse vector columns (mlvdb_sparse.h), which share the storage
-bool pooled(int32_t type) { return type == MLVDB_ATTR_INT64_LIST || type == MLVDB_ATTR_SPARSE; }
+// "has a slot and a pool": list columns (mlvdb_list.h), sparse vector columns (mlvdb_sparse.h) and binary vector columns
+// (mlvdb_bits.h), which share the storage
+bool pooled(int32_t type) { return type == MLVDB_ATTR_INT64_LIST || type == MLVDB_ATTR_SPARSE || type == MLVDB_ATTR_BITS; }
 
 // nb.col[a] = a fresh column of `cap` values for every defined attribute: rows [0, keep) copied from the current column
 // (old_of_new == nullptr: regrowth) or gathered through old_of_new (compaction), the rest absent.  Enqueued on h->stream;
@@ -2099,6 +2102,8 @@ int scalar_check(mlvdb_index* h, int32_t attr) {
         return fail(h, MLVDB_ERR_INVALID_ARG, "a list column: this entry needs a scalar column (see mlvdb_list.h)");
     if (h->attr_type[attr] == MLVDB_ATTR_SPARSE)
         return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse column: this entry needs a scalar column (see mlvdb_sparse.h)");
+    if (h->attr_type[attr] == MLVDB_ATTR_BITS)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a bits column: this entry needs a scalar column (see mlvdb_bits.h)");
     return MLVDB_OK;
 }
 
@@ -2158,6 +2163,10 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
                     if (o.op != MLVDB_WHERE_EXISTS) return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse column takes EXISTS and LEN only");
                     d.type = MLVDB_ATTR_INT64_LIST;  // the same slot: the evaluators see a list column
                 }
+                if (d.type == MLVDB_ATTR_BITS) {
+                    if (o.op != MLVDB_WHERE_EXISTS) return fail(h, MLVDB_ERR_INVALID_ARG, "a bits column takes EXISTS only");
+                    d.type = MLVDB_ATTR_INT64_LIST;  // the same slot: the evaluators see a list column
+                }
                 if (o.op == MLVDB_WHERE_IN) {
                     if (d.type != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "IN needs an int64 column");
                     if (o.a < 0 || o.b < 0 || o.a > w->n_set || o.b > w->n_set - o.a)
@@ -2174,6 +2183,7 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
                     if (o.op != MLVDB_WHERE_LEN) return fail(h, MLVDB_ERR_INVALID_ARG, "a sparse column takes EXISTS and LEN only");
                     d.type = MLVDB_ATTR_INT64_LIST;  // the same slot: the evaluators see a list column
                 }
+                if (d.type == MLVDB_ATTR_BITS) return fail(h, MLVDB_ERR_INVALID_ARG, "a bits column takes EXISTS only");
                 if (d.type != MLVDB_ATTR_INT64_LIST) return fail(h, MLVDB_ERR_INVALID_ARG, "HAS, HAS_ANY, HAS_ALL and LEN need a list column");
                 if (o.op == MLVDB_WHERE_LEN) break;  // (its bounds stay in a, b: it reads the slot alone)
                 d.b = (int64_t)reinterpret_cast<intptr_t>(h->list_pool[o.attr]);  // the pool's address rides in b
@@ -4335,7 +4345,7 @@ int mlvdb_attr_list_stats(mlvdb_index* h, int32_t attr, int64_t* pool_used, int6
     int rc = check_handle(h);
     if (rc) return rc;
     if ((rc = attr_check(h, attr))) return rc;
-    if (!pooled(h->attr_type[attr])) return fail(h, MLVDB_ERR_INVALID_ARG, "not a list or sparse column");
+    if (!pooled(h->attr_type[attr])) return fail(h, MLVDB_ERR_INVALID_ARG, "not a list, sparse or bits column");
     if (!pool_used || !pool_live) return fail(h, MLVDB_ERR_INVALID_ARG, "null counter");
     *pool_used = h->list_used[attr];
     return list_scan(h, h->attr_col[attr], h->rn, h->total, pool_live);
@@ -4578,6 +4588,164 @@ int mlvdb_search_batch_sparse(mlvdb_index* h, int32_t attr, const int64_t* q_off
         const int64_t q1 = std::min<int64_t>(nq, q0 + kSparseChunk);
         if ((rc = sparse_pass(h, attr, q_offsets, q_terms, q_weights, q0, q1, k, mask, out_labels, out_score, out_counts,
                               out_score64)))
+            return rc;
+    }
+    return MLVDB_OK;
+    });
+}
+
+// ---- binary vector columns (mlvdb_bits.h)
+extern "C++" {
+namespace {
+int bits_attr_check(mlvdb_index* h, int32_t attr) {
+    if (int rc = attr_check(h, attr)) return rc;
+    if (h->attr_type[attr] != MLVDB_ATTR_BITS) return fail(h, MLVDB_ERR_INVALID_ARG, "not a bits column");
+    return MLVDB_OK;
+}
+
+int bits_words_check(mlvdb_index* h, int32_t words) {
+    if (words < 1 || words > MLVDB_BITS_MAX_WORDS) return fail(h, MLVDB_ERR_INVALID_ARG, "words must be in 1..MLVDB_BITS_MAX_WORDS");
+    return MLVDB_OK;
+}
+
+// n codes of `words` words as the CSR the pool's entries take: row i owns [offsets[i], offsets[i + 1]), an absent row an
+// empty range, the present rows' words back to back in `packed`; nothing is written or launched.
+void bits_csr_pack(int64_t n, int32_t words, const uint64_t* codes, const uint8_t* present, std::vector<int64_t>& packed,
+                   std::vector<int64_t>& offsets) {
+    offsets.resize((size_t)n + 1);
+    offsets[0] = 0;
+    for (int64_t i = 0; i < n; ++i) offsets[(size_t)i + 1] = offsets[(size_t)i] + ((present && !present[i]) ? 0 : words);
+    packed.resize((size_t)offsets[(size_t)n]);
+    for (int64_t i = 0; i < n; ++i)
+        if (offsets[(size_t)i + 1] > offsets[(size_t)i])
+            std::memcpy(packed.data() + offsets[(size_t)i], codes + i * words, (size_t)words * sizeof(uint64_t));
+}
+
+// One pass of at most kBitsChunk queries [q0, q1): queries and popcounts up, scan, merge, answers down.
+int bits_pass(mlvdb_index* h, int32_t attr, const uint64_t* queries, int64_t q0, int64_t q1, int32_t words, int32_t metric,
+              int32_t k, const uint8_t* mask, int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
+    hipStream_t s = h->stream;
+    const int32_t n = (int32_t)(q1 - q0);
+    const size_t nk = (size_t)n * k;
+    const uint64_t* q = queries + q0 * words;
+    std::vector<int32_t> qpop((size_t)n, 0);
+    for (int32_t i = 0; i < n; ++i)
+        for (int32_t w = 0; w < words; ++w) qpop[(size_t)i] += __builtin_popcountll(q[(size_t)i * words + w]);
+    const int32_t nblk = bits_scan_blocks(h->total, n, k, words);
+    // [queries | popcounts]
+    const size_t qbytes = (size_t)n * words * sizeof(uint64_t), pbytes = (size_t)n * sizeof(int32_t);
+    HIP_TRY(h, h->bits_in.ensure(qbytes + pbytes));
+    HIP_TRY(h, h->partial.ensure(nk * (size_t)nblk * sizeof(TopEntry)));
+    HIP_TRY(h, h->bits_out.ensure(ListBlock::bytes(nk, (size_t)n)));
+    const ListBlock o(h->bits_out.p, nk, (size_t)n);
+    char* in = h->bits_in.as<char>();
+    HIP_TRY(h, hipMemcpyAsync(in, q, qbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(in + qbytes, qpop.data(), pbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_bits_scan(h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total, reinterpret_cast<const uint64_t*>(in),
+                                reinterpret_cast<const int32_t*>(in + qbytes), n, words, metric, k, nblk,
+                                h->partial.as<TopEntry>(), s));
+    HIP_TRY(h, launch_exact_merge(h->partial.as<TopEntry>(), n, nullptr, nullptr, nblk, k, o.lab, o.dist, o.cnt, o.d64, s));
+    const size_t at = (size_t)q0 * k;
+    // (copy_down drains the stream: qpop is consumed by then)
+    return copy_down(h, s, {{out_labels, at, o.lab, nk}, {out_dist, at, o.dist, nk}, {out_counts, (size_t)q0, o.cnt, (size_t)n},
+                            {out_dist64, at, o.d64, nk}});
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_bits_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int32_t words, const uint64_t* codes,
+                   const uint8_t* present) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = bits_attr_check(h, attr))) return rc;
+    if ((rc = bits_words_check(h, words))) return rc;
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (n == 0) return MLVDB_OK;
+    if (!codes) return fail(h, MLVDB_ERR_INVALID_ARG, "codes is null");
+    std::vector<int64_t> packed, offsets;
+    bits_csr_pack(n, words, codes, present, packed, offsets);
+    return list_set_impl(h, attr, first, n, offsets.data(), packed.data(), present);
+    });
+}
+
+int mlvdb_bits_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, int32_t words, const uint64_t* codes,
+                      const uint8_t* present, int64_t* updated) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked before anything is launched
+    if ((rc = bits_attr_check(h, attr))) return rc;
+    if ((rc = bits_words_check(h, words))) return rc;
+    if (!updated || n < 0 || (n > 0 && !labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n");
+    *updated = 0;
+    if (n == 0) return MLVDB_OK;
+    if (!codes) return fail(h, MLVDB_ERR_INVALID_ARG, "codes is null");
+    if ((rc = labels_check(h, labels, n))) return rc;
+    std::vector<int64_t> packed, offsets;
+    bits_csr_pack(n, words, codes, present, packed, offsets);
+    return list_set_at_impl(h, attr, labels, n, offsets.data(), packed.data(), present, updated);
+    });
+}
+
+int mlvdb_bits_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int32_t* out_words, uint64_t* out_codes,
+                   int64_t capacity, int64_t* needed) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((rc = bits_attr_check(h, attr))) return rc;
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (!needed || capacity < 0 || (n > 0 && !out_words) || (capacity > 0 && !out_codes))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
+    *needed = 0;
+    if (n == 0) return MLVDB_OK;
+    // the list read-back: a row's width is the length of its range, 0 for an absent row (a present code has >= 1 word)
+    if ((rc = list_scan(h, h->attr_col[attr] + first, nullptr, n, needed))) return rc;
+    if (capacity < *needed) return MLVDB_OK;
+    std::vector<int64_t> offsets((size_t)n + 1);
+    static_assert(sizeof(uint64_t) == sizeof(int64_t), "the codes are read back as the pool's elements");
+    if ((rc = list_get_impl(h, attr, first, n, offsets.data(), reinterpret_cast<int64_t*>(out_codes), nullptr, *needed, needed)))
+        return rc;
+    for (int64_t i = 0; i < n; ++i) out_words[i] = (int32_t)(offsets[(size_t)i + 1] - offsets[(size_t)i]);
+    return MLVDB_OK;
+    });
+}
+
+int mlvdb_search_batch_bits(mlvdb_index* h, int32_t attr, const uint64_t* queries, int64_t nq, int32_t words, int32_t metric,
+                            int32_t k, const mlvdb_where* where, int64_t* out_labels, float* out_dist, int32_t* out_counts,
+                            double* out_dist64) {
+    return guarded(h, [&]() -> int {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    // everything is checked on the host before anything is launched
+    if ((rc = bits_attr_check(h, attr))) return rc;
+    if ((rc = bits_words_check(h, words))) return rc;
+    if (metric != MLVDB_BITS_HAMMING && metric != MLVDB_BITS_JACCARD) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown bits metric");
+    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "bits search: k above MLVDB_MAX_TOPK");
+    if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (h->total > INT32_MAX) return fail(h, MLVDB_ERR_UNSUPPORTED, "bits search: more than 2^31 - 1 rows");
+    if (where && (rc = where_prepare(h, where))) return rc;
+    if (nq == 0) return MLVDB_OK;
+    if (h->total == 0) {
+        for (int64_t i = 0; i < nq * k; ++i) {
+            out_labels[i] = -1;
+            out_dist[i] = __builtin_inff();
+            if (out_dist64) out_dist64[i] = __builtin_inf();
+        }
+        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        return MLVDB_OK;
+    }
+    const uint8_t* mask = nullptr;
+    if (where) {  // the program into h->row_mask (live matching rows), which every pass reads at one byte per row
+        if ((rc = where_run(h, where, nullptr))) return rc;
+        mask = h->row_mask.as<uint8_t>();
+    }
+    for (int64_t q0 = 0; q0 < nq; q0 += kBitsChunk) {
+        const int64_t q1 = std::min<int64_t>(nq, q0 + kBitsChunk);
+        if ((rc = bits_pass(h, attr, queries, q0, q1, words, metric, k, mask, out_labels, out_dist, out_counts, out_dist64)))
             return rc;
     }
     return MLVDB_OK;

@@ -23,6 +23,7 @@
 #include "../../include/mlvdb_mutate.h"
 #include "../../include/mlvdb_list.h"
 #include "../../include/mlvdb_sparse.h"
+#include "../../include/mlvdb_bits.h"
 #include "../../include/mlvdb_hybrid.h"
 #include "../../include/mlvdb_geo.h"
 #include "layout.h"
@@ -463,6 +464,18 @@ hipError_t launch_hybrid_fuse(const int64_t* u_lab, const int32_t* u_rd, const i
                               const double* comp_s, int32_t method, double w_dense, double w_sparse, double rrf_c, int32_t k,
                               int64_t* out_labels, double* out_fused, int32_t* out_counts, double* out_d64, double* out_s64,
                               int32_t* out_rd, int32_t* out_rs, hipStream_t s);
+
+// ---------------------------------------------------------------- binary vector columns (kernels_bits.hip, include/mlvdb_bits.h)
+constexpr int kBitsQT = 16;           // queries per tile
+constexpr int kBitsMaxBlocks = 512;   // blocks over all tiles of a pass (two per CU): the rows of a tile are strided over its share
+constexpr int kBitsChunk = 256;       // queries per pass
+int32_t bits_scan_blocks(int64_t total, int64_t nq, int32_t k, int32_t words);
+// partial[(q * nblk + block) * k ..] = the block's k best (distance, row) of query q (queries[q * words ..], qpop[q] its
+// popcount) over the live rows whose slot holds exactly `words` words (mask != nullptr:
+// whose mask byte is set too); launch_exact_merge folds them
+hipError_t launch_bits_scan(const int64_t* slots, const int64_t* pool, const float* rn, const uint8_t* mask, int64_t total,
+                            const uint64_t* queries, const int32_t* qpop, int32_t nq, int32_t words, int32_t metric, int32_t k,
+                            int32_t nblk, TopEntry* partial, hipStream_t s);
 
 // rn[i] = NaN for the rows of mask, and their int8 row pairs (i < i8_rows; rp8 may be null) as tombstone_rp8_kernel does
 hipError_t launch_tombstone_mask(const uint8_t* mask, float* rn, float* rp8, int64_t i8_rows, int l2, int64_t total,

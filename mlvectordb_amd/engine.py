@@ -278,7 +278,8 @@ class HipScanEngine:
     # -- metadata filters (include/mlvdb_where.h) ------------------------------------
     def define_attr(self, attr: int, kind: str) -> None:
         """Column ``attr`` (0..15) of type "int64" (absent = INT64_MIN), "float64" (absent = NaN), "int64_list" (a set of
-        int64 per row, include/mlvdb_list.h), "sparse" (a sparse vector per row, include/mlvdb_sparse.h) or "geo" (a packed
+        int64 per row, include/mlvdb_list.h), "sparse" (a sparse vector per row, include/mlvdb_sparse.h), "bits" (a bit code
+        per row, include/mlvdb_bits.h) or "geo" (a packed
         location per row, stored as int64 with INT64_MIN absent, include/mlvdb_geo.h), every row absent."""
         code = _native.LIST_ATTR_CODES[kind] if kind in _native.LIST_ATTR_CODES else _native.ATTR_CODES[kind]
         self._check(self._lib.mlvdb_attr_define(self._h, int(attr), code), "attr_define")
@@ -507,6 +508,67 @@ class HipScanEngine:
             self._h, int(attr), offsets.ctypes.data, _nonempty(terms), _nonempty(weights), nq, k, w, labels.ctypes.data,
             score.ctypes.data, counts.ctypes.data, score64.ctypes.data), "search_batch_sparse")
         return labels, score, counts, score64
+
+    # -- binary vector columns (include/mlvdb_bits.h) -------------------------------------
+    @staticmethod
+    def _bits_codes(col):
+        """A ``where.BitsColumn`` as the contiguous arrays the C entries take (kept alive by the caller for the call)."""
+        words = np.ascontiguousarray(col.words, dtype=np.uint64)
+        present = np.ascontiguousarray(col.present, dtype=np.uint8)
+        if words.ndim != 2 or words.shape[0] != present.size:
+            raise RuntimeError(f"{present.size} rows but codes of shape {words.shape}")
+        return words, present
+
+    def bits_set(self, attr: int, first: int, col) -> None:
+        """The codes of rows first..first+len(col)-1 of bits column ``attr`` (``col``: a ``where.BitsColumn``)."""
+        words, present = self._bits_codes(col)
+        self._check(self._lib.mlvdb_bits_set(self._h, int(attr), int(first), present.size, words.shape[1], _nonempty(words),
+                                             present.ctypes.data), "bits_set")
+
+    def bits_set_at(self, attr: int, labels: np.ndarray, col) -> int:
+        """Code i of ``col`` -> row ``labels[i]`` (distinct labels in [0, total); tombstoned rows are skipped); returns the
+        rows written."""
+        labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        words, present = self._bits_codes(col)
+        if present.size != labels.size:
+            raise RuntimeError(f"{labels.size} labels but {present.size} codes")
+        n = C.c_int64(0)
+        self._check(self._lib.mlvdb_bits_set_at(self._h, int(attr), labels.ctypes.data, labels.size, words.shape[1],
+                                                _nonempty(words), present.ctypes.data, C.byref(n)), "bits_set_at")
+        return int(n.value)
+
+    def bits_get(self, attr: int, first: int, n: int):
+        """The codes of rows first..first+n-1: (widths int32 [n] in words, 0 = absent; the present rows' words uint64, back to
+        back in row order).  Tombstoned rows keep what they hold."""
+        n = int(n)
+        widths = np.zeros(n, dtype=np.int32)
+        codes = np.empty(0, dtype=np.uint64)
+        needed = C.c_int64(0)
+        for _ in range(2):  # the first call sizes the codes, the second reads them
+            self._check(self._lib.mlvdb_bits_get(self._h, int(attr), int(first), n, _nonempty(widths), _nonempty(codes),
+                                                 codes.size, C.byref(needed)), "bits_get")
+            if needed.value <= codes.size:
+                break
+            codes = np.empty(needed.value, dtype=np.uint64)
+        return widths, codes[: needed.value]
+
+    def search_bits(self, attr: int, queries: np.ndarray, k: int, metric: str = "hamming", where=None):
+        """Exact kNN over bit codes (``mlvdb_search_batch_bits``): ``queries`` uint64 [nq, words], ``metric`` "hamming" or
+        "jaccard", ``where`` a compiled filter or ``None``.  Returns (labels int64 [nq, k] padded -1, distances float32
+        [nq, k] padded +inf, counts int32 [nq], distances float64 [nq, k]): the live rows with a code of ``words`` words
+        ranked by (distance ascending, label ascending)."""
+        queries = np.ascontiguousarray(queries, dtype=np.uint64)
+        if queries.ndim != 2:
+            raise RuntimeError(f"queries must be [nq, words]; got shape {queries.shape}")
+        if metric not in _native.BITS_METRIC_CODES:
+            raise RuntimeError(f"unknown bits metric {metric!r} (one of {sorted(_native.BITS_METRIC_CODES)})")
+        nq, k = queries.shape[0], int(k)
+        labels, dist, counts, dist64 = self._knn_outputs((nq, max(k, 0)), True)
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_search_batch_bits(
+            self._h, int(attr), _nonempty(queries), nq, queries.shape[1], _native.BITS_METRIC_CODES[metric], k, w,
+            labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, dist64.ctypes.data), "search_batch_bits")
+        return labels, dist, counts, dist64
 
     # -- hybrid search (include/mlvdb_hybrid.h) -------------------------------------------
     def search_hybrid(self, queries: np.ndarray, attr: int, sparse_queries, k: int, fetch_dense: int, fetch_sparse: int,

@@ -285,9 +285,10 @@ class Index:
         for name, kind in attributes.items():
             if not isinstance(name, str) or name.startswith("$"):
                 raise ValueError(f"attribute name {name!r}: a string not starting with '$'")
-            if kind not in _where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES + _where.GEO_TYPES:
-                raise ValueError(f"attribute {name!r}: type {kind!r} is not one of "
-                                 f"{_where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES + _where.GEO_TYPES}")
+            known = _where.ATTR_TYPES + _where.LIST_TYPES + _where.SPARSE_TYPES + _where.GEO_TYPES
+            if kind not in known and not _where.is_bits(kind):
+                raise ValueError(f"attribute {name!r}: type {kind!r} is not one of {known + _where.BITS_TYPES} "
+                                 f"(N a multiple of 64 in [64, {64 * _where.BITS_MAX_WORDS}])")
         return attributes
 
     @property
@@ -347,6 +348,11 @@ class Index:
                 continue
             if _where.is_sparse(kind):
                 col = _where.encode_sparse_column(name, values)
+                if col.present.any():
+                    out[i] = col
+                continue
+            if _where.is_bits(kind):
+                col = _where.encode_bits_column(name, kind, values)
                 if col.present.any():
                     out[i] = col
                 continue
@@ -456,6 +462,9 @@ class Index:
         if _where.is_geo(self._attributes[name]):
             raise ValueError(f"{what}: attribute {name!r} is a geo column; it needs a scalar attribute (a location is "
                              f"filtered with $geo_radius / $geo_box and ranked with nearest)")
+        if _where.is_bits(self._attributes[name]):
+            raise ValueError(f"{what}: attribute {name!r} is a {self._attributes[name]} column; it needs a scalar attribute "
+                             f"(a bit code is searched with search_bits)")
 
     def _check_scalar(self, what: str, name: str) -> None:
         self._check_sparse(what, name)
@@ -479,6 +488,8 @@ class Index:
                 Index._engine_entry(ns, "set_attr_list", "list attributes need")(i, first, col)
             elif isinstance(col, _where.SparseColumn):
                 Index._engine_entry(ns, "set_attr_sparse", "sparse attributes need")(i, first, col)
+            elif isinstance(col, _where.BitsColumn):
+                Index._engine_entry(ns, "bits_set", "bits attributes need")(i, first, col)
             else:
                 ns.engine.set_attr(i, first, col)
         if strings is not None:
@@ -906,6 +917,48 @@ class Index:
         labels, _, counts, s64 = search(self._column(by), col, k, where=program)
         return BatchHits(labels, s64, counts, ns.ids)
 
+    _BITS_METRICS = ("hamming", "jaccard")  # MLVDB_BITS_*
+
+    @staticmethod
+    def _bits_queries(queries, nbits: int, entry: str) -> np.ndarray:
+        """Bit-code queries as uint64 [nq, nbits / 64]; query ``i`` is refused as ``{entry}: query i``."""
+        if isinstance(queries, (str, bytes, bytearray, memoryview, Mapping)) or \
+                (isinstance(queries, np.ndarray) and queries.ndim != 2):
+            raise ValueError(f"{entry}: queries is a sequence of bit codes or a 2-d array with one code per row "
+                             f"(got one code: wrap it in a list)")
+        rows = list(queries)
+        out = np.zeros((len(rows), nbits // 64), dtype=np.uint64)
+        for i, q in enumerate(rows):
+            out[i] = _where.encode_bits_code(q, nbits, f"{entry}: query {i}")
+        return out
+
+    def search_bits(self, queries, top_k: int, namespace: str, by: str, *, metric: str = "hamming",
+                    where: Optional[Mapping] = None) -> BatchHits:
+        """Additive: exact kNN over the declared ``bits<N>`` attribute ``by`` on the device (include/mlvdb_bits.h).
+        ``queries`` is a sequence of ``N``-bit codes -- each ``bytes`` of ``N / 8`` bytes, a ``uint8`` array of ``N / 8``
+        entries or a bool / 0-1 array of ``N`` entries, typed as at ingest -- or a ``uint8`` array ``[nq, N / 8]``; every live
+        row that holds a code is a candidate, and ``where`` (one dict filter) restricts the rows first.  ``metric`` is
+        ``"hamming"`` (the number of differing bits) or ``"jaccard"`` (``1 - |q & x| / |q | x|``, 0 for two all-zero codes).
+        Per query the ``top_k`` rows with the smallest distance come back, ties to the earlier row; ``scores`` is the fp64
+        distance.  ``top_k`` is clamped to the live row count and to 64.  Every refusal happens before the engine is
+        touched."""
+        self._refuse_sharded("search_bits")
+        if not _where.is_bits(self._declared(by, "search_bits: ")):
+            raise ValueError(f"search_bits: attribute {by!r} is a {self._attributes[by]} column; it needs a bits attribute")
+        if metric not in self._BITS_METRICS:
+            raise ValueError(f"search_bits: metric must be one of {self._BITS_METRICS} (got {metric!r})")
+        self._one_filter("search_bits", where)
+        q = self._bits_queries(queries, _where.bits_width(self._attributes[by]), "search_bits")
+        program = self._program(namespace, where)
+        nq = q.shape[0]
+        ns = self._ns.get(namespace)
+        if self._nothing_to_search(ns, top_k, nq):
+            return BatchHits.empty(nq)
+        search = self._engine_entry(ns, "search_bits", "bits attributes need")
+        k = min(int(top_k), ns.total - ns.deleted, self._MAX_TOP_K_SPARSE)
+        labels, _, counts, d64 = search(self._column(by), q, k, metric=metric, where=program)
+        return BatchHits(labels, d64, counts, ns.ids)
+
     _FUSIONS = ("rrf", "linear", "relative")  # MLVDB_FUSE_*
     _MAX_FETCH_K_HYBRID = 1024                # MLVDB_HYBRID_MAX_FETCH_DENSE
 
@@ -1259,6 +1312,8 @@ class Index:
                                                 strings.setdefault(name, {}) if kind == "str[]" else {})
             elif _where.is_sparse(kind):
                 col = _where.encode_sparse_column(name, [patches[j][name] for j in pos])
+            elif _where.is_bits(kind):
+                col = _where.encode_bits_column(name, kind, [patches[j][name] for j in pos])
             else:
                 col = _where.encode_column(name, kind, [patches[j][name] for j in pos],
                                            strings.setdefault(name, {}) if kind == "str" else {})
@@ -1297,6 +1352,9 @@ class Index:
             elif isinstance(col, _where.SparseColumn):
                 set_sparse_at = self._engine_entry(ns, "set_attr_sparse_at", "sparse attributes need")
                 set_sparse_at(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
+            elif isinstance(col, _where.BitsColumn):
+                set_bits_at = self._engine_entry(ns, "bits_set_at", "bits attributes need")
+                set_bits_at(i, rows, col.take(np.flatnonzero(keep)[lab.size - 1 - last]))
             else:
                 set_at(i, rows, col[keep][lab.size - 1 - last])
             touched.append(rows)
@@ -1320,6 +1378,9 @@ class Index:
             v = values[name]
             if _where.is_sparse(kind):
                 raise ValueError(f"update_where: {name!r} is a sparse attribute: one vector for every matching row is not "
+                                 f"supported, use update_attributes with ids")
+            if _where.is_bits(kind):
+                raise ValueError(f"update_where: {name!r} is a {kind} attribute: one code for every matching row is not "
                                  f"supported, use update_attributes with ids")
             if _where.is_geo(kind) and isinstance(v, Mapping) and "$inc" in v:
                 raise ValueError(f"update_where: {name!r} is a geo attribute: it takes a point or None, $inc adds to numbers")
@@ -1767,6 +1828,9 @@ class Index:
     # the layout the index would otherwise write (v2, v3 or v4) with a "geo" attribute in the schema, whose column file is
     # the raw int64 column (packed points, INT64_MIN = absent); written only by an index that declares a geo attribute
     _FORMAT_V5 = "mlvdb-index-v5"
+    # v5's layout with a "bits<N>" attribute in the schema, whose column file holds 1 / 0 (INT64_MIN) presence and whose
+    # .bits.u64 holds the present live rows' codes, dense, in row order; written only by an index that declares one
+    _FORMAT_V6 = "mlvdb-index-v6"
     _CHUNK_BYTES = 256 << 20
 
     def save_index(self, path: str) -> bool:
@@ -1776,7 +1840,8 @@ class Index:
         has_lists = any(_where.is_list(kind) for kind in self._attributes.values())
         has_sparse = any(_where.is_sparse(kind) for kind in self._attributes.values())
         has_geo = any(_where.is_geo(kind) for kind in self._attributes.values())
-        fmt = self._FORMAT_V5 if has_geo else self._FORMAT_V4 if has_sparse else self._FORMAT_V3 if has_lists else self._FORMAT_V2 if self._attributes else \
+        has_bits = any(_where.is_bits(kind) for kind in self._attributes.values())
+        fmt = self._FORMAT_V6 if has_bits else self._FORMAT_V5 if has_geo else self._FORMAT_V4 if has_sparse else self._FORMAT_V3 if has_lists else self._FORMAT_V2 if self._attributes else \
             self._FORMAT
         meta = {"format": fmt, "space": self._space,
                 "rebuild_threshold": self._rebuild_threshold, "namespaces": []}
@@ -1802,6 +1867,9 @@ class Index:
                         continue
                     if _where.is_sparse(kind):
                         self._save_sparse(ns, j, col, dead)
+                        continue
+                    if _where.is_bits(kind):
+                        self._save_bits(ns, j, col, dead, _where.bits_width(kind) // 64)
                         continue
                     dtype = np.float64 if kind == "float" else np.int64
                     (ns.engine.get_attr(j, 0, ns.total, dtype) if ns.total else np.zeros(0, dtype)).tofile(col)
@@ -1867,6 +1935,28 @@ class Index:
         (np.concatenate(terms) if terms else np.zeros(0, np.int32)).astype(np.int32).tofile(base + "terms.i32")
         (np.concatenate(weights) if weights else np.zeros(0, np.float32)).astype(np.float32).tofile(base + "weights.f32")
 
+    @classmethod
+    def _save_bits(cls, ns: _Namespace, j: int, col_file: str, dead: np.ndarray, words: int) -> None:
+        """A bits attribute of a v6 snapshot: the column file holds 1 for a live row with a code (INT64_MIN: none), and next
+        to it ``.bits.u64`` holds those rows' codes, ``words`` words each, in row order; a tombstoned row is written without a
+        code, and so is a row whose code has another width (only the raw C entries can write one)."""
+        has = np.full(ns.total, _where.INT64_ABSENT, dtype=np.int64)
+        parts = []
+        chunk = 1 << 20
+        for first in range(0, ns.total, chunk):
+            n = min(chunk, ns.total - first)
+            widths, codes = cls._engine_entry(ns, "bits_get", "bits attributes need")(j, first, n)
+            starts = np.concatenate([[0], np.cumsum(widths, dtype=np.int64)])[:-1]
+            live = widths == words
+            live[dead[(dead >= first) & (dead < first + n)] - first] = False
+            rows = np.flatnonzero(live)
+            has[first + rows] = 1
+            parts.append(codes[(starts[rows][:, None] + np.arange(words)[None, :]).ravel()] if rows.size
+                         else np.zeros(0, dtype=np.uint64))
+        has.tofile(col_file)
+        (np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)).astype("<u8").tofile(
+            col_file[:-len("i64")] + "bits.u64")
+
     @staticmethod
     def _attr_file(path: str, i: int, j: int, kind: str) -> str:
         return os.path.join(path, f"ns{i}.attr{j}.{'f64' if kind == 'float' else 'i64'}")
@@ -1879,12 +1969,17 @@ class Index:
             return False
         with open(manifest) as f:
             meta = json.load(f)
-        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5):
+        if meta.get("format") not in (self._FORMAT, self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5,
+                                      self._FORMAT_V6):
             raise RuntimeError(f"unknown index format {meta.get('format')!r}")
-        # (v3: v2 with list attributes, v4: v3 with sparse attributes, v5: any of them with geo attributes)
-        v2 = meta["format"] in (self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5)
-        if v2 and meta["format"] != self._FORMAT_V5 and any(_where.is_geo(k) for k in meta.get("attributes", {}).values()):
-            raise RuntimeError(f"a geo attribute in a {meta['format']} snapshot: only {self._FORMAT_V5} holds them")
+        # (v3: v2 with list attributes, v4: v3 with sparse attributes, v5: any of them with geo attributes, v6: any of them
+        # with bits attributes)
+        v2 = meta["format"] in (self._FORMAT_V2, self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5, self._FORMAT_V6)
+        v5 = meta["format"] in (self._FORMAT_V5, self._FORMAT_V6)
+        if v2 and not v5 and any(_where.is_geo(k) for k in meta.get("attributes", {}).values()):
+            raise RuntimeError(f"a geo attribute in a {meta['format']} snapshot: only {self._FORMAT_V5} and later hold them")
+        if v2 and meta["format"] != self._FORMAT_V6 and any(_where.is_bits(k) for k in meta.get("attributes", {}).values()):
+            raise RuntimeError(f"a bits attribute in a {meta['format']} snapshot: only {self._FORMAT_V6} holds them")
         # v2: the snapshot's attributes replace the declared ones; v1: the declared ones stay, every value absent
         attributes = self._check_schema(meta.get("attributes", {})) if v2 else self._attributes
         if v2 and attributes:
@@ -1900,17 +1995,25 @@ class Index:
             for j, kind in enumerate(attributes.values()):
                 if v2 and _where.is_list(kind):
                     base = self._attr_file(path, i, j, kind)[:-len("i64")]
-                    if meta["format"] not in (self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5) or not os.path.isfile(base + "values.i64") or \
+                    if meta["format"] not in (self._FORMAT_V3, self._FORMAT_V4, self._FORMAT_V5, self._FORMAT_V6) or \
+                            not os.path.isfile(base + "values.i64") or \
                             not os.path.isfile(base + "offsets.i64") or \
                             os.path.getsize(base + "offsets.i64") != (total + 1) * 8:
                         raise RuntimeError(f"namespace {m['name']!r}: list attribute files do not match the manifest")
                 if v2 and _where.is_sparse(kind):
                     base = self._attr_file(path, i, j, kind)[:-len("i64")]
-                    if meta["format"] not in (self._FORMAT_V4, self._FORMAT_V5) or not os.path.isfile(base + "terms.i32") or \
+                    if meta["format"] not in (self._FORMAT_V4, self._FORMAT_V5, self._FORMAT_V6) or \
+                            not os.path.isfile(base + "terms.i32") or \
                             not os.path.isfile(base + "weights.f32") or not os.path.isfile(base + "offsets.i64") or \
                             os.path.getsize(base + "offsets.i64") != (total + 1) * 8 or \
                             os.path.getsize(base + "terms.i32") != os.path.getsize(base + "weights.f32"):
                         raise RuntimeError(f"namespace {m['name']!r}: sparse attribute files do not match the manifest")
+                if v2 and _where.is_bits(kind):
+                    base = self._attr_file(path, i, j, kind)[:-len("i64")]
+                    held = int((np.fromfile(base + "i64", dtype=np.int64) != _where.INT64_ABSENT).sum())
+                    if not os.path.isfile(base + "bits.u64") or \
+                            os.path.getsize(base + "bits.u64") != held * (_where.bits_width(kind) // 8):
+                        raise RuntimeError(f"namespace {m['name']!r}: bits attribute files do not match the manifest")
         self.close()
         self._attributes = attributes
         self._space = meta["space"]
@@ -1946,6 +2049,13 @@ class Index:
                                                       np.fromfile(base + "weights.f32", dtype=np.float32),
                                                       (col != _where.INT64_ABSENT).astype(np.uint8))
                         self._engine_entry(ns, "set_attr_sparse", "sparse attributes need")(j, 0, vectors)
+                    elif col.size and _where.is_bits(kind):
+                        present = (col != _where.INT64_ABSENT).astype(np.uint8)
+                        words = _where.bits_width(kind) // 64
+                        dense = np.fromfile(self._attr_file(path, i, j, kind)[:-len("i64")] + "bits.u64", dtype="<u8")
+                        codes = np.zeros((total, words), dtype=np.uint64)
+                        codes[present.astype(bool)] = dense.reshape(-1, words)
+                        self._engine_entry(ns, "bits_set", "bits attributes need")(j, 0, _where.BitsColumn(codes, present))
                     elif col.size:
                         ns.engine.set_attr(j, 0, col)
                 ns.strings = {a: {s: c for c, s in enumerate(values)} for a, values in m.get("strings", {}).items()}

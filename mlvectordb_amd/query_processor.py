@@ -165,6 +165,22 @@ class QueryProcessor:
             raise ValueError("find_similar_sparse needs an index with search_sparse")
         return self._enrich_many(self._index.search_sparse(queries, top_k, namespace, by, where=where), namespace)
 
+    def find_similar_bits(self, query, top_k: int, namespace: str = "default", by: str = "", metric: str = "hamming",
+                          where=None) -> List[dict]:
+        """Additive: search for one bit code -- ``bytes``, a ``uint8`` array of ``N / 8`` entries or a bool / 0-1 array of
+        ``N`` entries -- over the declared ``bits<N>`` attribute ``by`` (``Index.search_bits``): the ``top_k`` (<= 64) vectors
+        with the smallest Hamming or Jaccard distance, as ``find_similar_many`` returns a hit (``score``: the distance)."""
+        return self.find_similar_bits_many([query], top_k, namespace, by, metric=metric, where=where)[0]
+
+    def find_similar_bits_many(self, queries, top_k: int, namespace: str = "default", by: str = "", metric: str = "hamming",
+                               where=None) -> List[List[dict]]:
+        """Batched ``find_similar_bits``: one code per query, one scan.  ``where`` is ``None`` or one dict filter."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("find_similar_bits: where must be one dict filter (or None)")
+        if not hasattr(self._index, "search_bits"):
+            raise ValueError("find_similar_bits needs an index with search_bits")
+        return self._enrich_many(self._index.search_bits(queries, top_k, namespace, by, metric=metric, where=where), namespace)
+
     def find_similar_hybrid(self, query, sparse_query, top_k: int, namespace: str = "default", metric: str = "cosine",
                             by: str = "", **options) -> List[dict]:
         """Additive: hybrid retrieval for one query -- a dense vector and a sparse one (a mapping ``{term: weight}`` or a

@@ -29,6 +29,9 @@ attribute, and ``$all`` / ``$size`` on a scalar one, are a ``ValueError``.
 A sparse attribute (``"sparse"``: at most 255 (term, weight) pairs per row, include/mlvdb_sparse.h) takes ``$exists`` and
 ``$size`` (the number of its nonzeros) only; an empty vector ``{}`` exists.  Everything else on it is a ``ValueError``.
 
+A bits attribute (``"bits<N>"``, e.g. ``"bits256"``: one ``N``-bit code per row, ``N`` a multiple of 64 in [64, 16320],
+include/mlvdb_bits.h) takes ``$exists`` only: it is searched with ``Index.search_bits``, not filtered by value.
+
 A geo attribute (``"geo"``: one location per row, include/mlvdb_geo.h) holds a point ``(lat, lon)`` or
 ``{"lat": .., "lon": ..}`` in degrees, quantised to 1e-7 degree, and takes
 
@@ -42,6 +45,7 @@ another attribute, are a ``ValueError``.
 from __future__ import annotations
 
 import math
+import re
 import struct
 from dataclasses import dataclass
 from typing import Any, Dict, List, Mapping, Tuple
@@ -54,6 +58,9 @@ LIST_MAX_LEN = 255               # MLVDB_LIST_MAX_LEN
 SPARSE_TYPES = ("sparse",)       # sparse vectors: (term, weight) pairs per row, searched by Index.search_sparse
 SPARSE_MAX_NNZ = 255             # MLVDB_SPARSE_MAX_NNZ
 SPARSE_MAX_QUERY_TERMS = 1024    # MLVDB_SPARSE_MAX_QUERY_TERMS
+BITS_TYPES = ("bits<N>",)        # bit codes: "bits64" .. "bits16320", N a multiple of 64, searched by Index.search_bits
+BITS_MAX_WORDS = 255             # MLVDB_BITS_MAX_WORDS
+_BITS_TYPE = re.compile(r"bits([1-9][0-9]*)\Z")
 GEO_TYPES = ("geo",)             # one location per row: (lat_e7 << 32) | uint32(lon_e7) in an int64 column
 GEO_LAT_MAX_E7 = 900_000_000     # MLVDB_GEO_LAT_MAX_E7
 GEO_LON_MAX_E7 = 1_800_000_000   # MLVDB_GEO_LON_MAX_E7
@@ -102,6 +109,19 @@ def is_geo(attr_type: str) -> bool:
     return attr_type in GEO_TYPES
 
 
+def is_bits(attr_type: str) -> bool:
+    """``"bits<N>"`` with ``N`` a multiple of 64 in [64, 64 * BITS_MAX_WORDS]."""
+    m = _BITS_TYPE.match(attr_type) if isinstance(attr_type, str) else None
+    return m is not None and int(m.group(1)) % 64 == 0 and int(m.group(1)) <= 64 * BITS_MAX_WORDS
+
+
+def bits_width(attr_type: str) -> int:
+    """The ``N`` of a ``"bits<N>"`` attribute type."""
+    if not is_bits(attr_type):
+        raise ValueError(f"{attr_type!r} is not a bits type: 'bits<N>' with N a multiple of 64 in [64, {64 * BITS_MAX_WORDS}]")
+    return int(attr_type[4:])
+
+
 def geo_pack(point: Any, what: str = "a point") -> int:
     """A point -- ``(lat, lon)`` or ``{"lat": .., "lon": ..}``, finite degrees with lat in [-90, 90] and lon in
     [-180, 180] -- as the int64 a geo column holds: ``(lat_e7 << 32) | uint32(lon_e7)``, each ``np.rint(x * 1e7)``.
@@ -148,15 +168,15 @@ def geo_radius_threshold(radius: Any, what: str = "$geo_radius") -> float:
 
 
 def is_pooled(attr_type: str) -> bool:
-    """A list or a sparse attribute: the column holds slots into a pool, not values."""
-    return is_list(attr_type) or is_sparse(attr_type)
+    """A list, a sparse or a bits attribute: the column holds slots into a pool, not values."""
+    return is_list(attr_type) or is_sparse(attr_type) or is_bits(attr_type)
 
 
 def column_kind(attr_type: str) -> str:
     """The device column type of an attribute type: float -> float64, a list type -> int64_list, sparse -> sparse,
-    geo -> geo, everything else -> int64."""
+    bits<N> -> bits, geo -> geo, everything else -> int64."""
     return "float64" if attr_type == "float" else "int64_list" if is_list(attr_type) else \
-        "sparse" if is_sparse(attr_type) else "geo" if is_geo(attr_type) else "int64"
+        "sparse" if is_sparse(attr_type) else "bits" if is_bits(attr_type) else "geo" if is_geo(attr_type) else "int64"
 
 
 class _Builder:
@@ -250,6 +270,9 @@ class _Builder:
             if op != "$exists":
                 raise ValueError(f"{key!r} is a sparse attribute: only $exists and $size apply (it is searched with "
                                  f"search_sparse, not filtered by value)")
+        if is_bits(kind) and op != "$exists":
+            raise ValueError(f"{key!r} is a {kind} attribute: only $exists applies (it is searched with search_bits, not "
+                             f"filtered by value)")
         if op in _LIST_ONLY and not is_pooled(kind):
             raise ValueError(f"{key!r} is a {kind} attribute: {op} applies to list attributes ({', '.join(LIST_TYPES)}) only")
         if is_list(kind) and op != "$exists":
@@ -614,6 +637,72 @@ def encode_sparse_column(name: str, values, max_nnz: int = SPARSE_MAX_NNZ) -> Sp
             present[i] = 1
         offsets[i + 1] = len(terms)
     return SparseColumn(offsets, np.array(terms, dtype=np.int32), np.array(weights, dtype=np.float32), present)
+
+
+@dataclass
+class BitsColumn:
+    """A batch of a bits attribute, as ``mlvdb_bits_set`` takes it: row i holds the code ``words[i]`` (word w = bits
+    64w .. 64w + 63) when ``present[i]``, and no code at all otherwise (its words are then zero and ignored)."""
+
+    words: np.ndarray    # uint64 [n, N / 64]
+    present: np.ndarray  # uint8 [n]
+
+    def __len__(self) -> int:
+        return int(self.present.size)
+
+    def row(self, i: int):
+        """Row i's code as ``N / 8`` bytes (little-endian words), or ``None``."""
+        return self.words[i].astype("<u8").tobytes() if self.present[i] else None
+
+    def take(self, rows) -> "BitsColumn":
+        """The rows ``rows`` (indices, in that order) as a column of their own."""
+        rows = np.asarray(rows, dtype=np.int64)
+        return BitsColumn(np.ascontiguousarray(self.words[rows]), self.present[rows].copy())
+
+
+def encode_bits_code(value, nbits: int, what: str) -> np.ndarray:
+    """One ``nbits``-bit code as ``nbits / 64`` uint64 words (word w = bits 64w .. 64w + 63).  ``value`` is ``bytes`` of
+    ``nbits / 8`` bytes read as little-endian 64-bit words, a ``uint8`` array of ``nbits / 8`` entries read the same way, or
+    a bool / 0-1 array (or list) of ``nbits`` entries, entry b being bit b.  ``ValueError`` (starting with ``what``) for
+    anything else: a wrong length, a wrong dtype, an entry that is neither 0 nor 1."""
+    if isinstance(value, (bytes, bytearray, memoryview)):
+        raw = bytes(value)
+        if len(raw) != nbits // 8:
+            raise ValueError(f"{what}: {len(raw)} bytes; a {nbits}-bit code is {nbits // 8} bytes")
+        return np.frombuffer(raw, dtype="<u8").astype(np.uint64)
+    if isinstance(value, (str, Mapping)) or value is None:
+        raise ValueError(f"{what}: {value!r} is not a bit code (bytes, a uint8 array of {nbits // 8} entries or a bool / 0-1 "
+                         f"array of {nbits} entries)")
+    try:
+        arr = np.asarray(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {value!r} is not a bit code") from None
+    if arr.ndim != 1 or arr.dtype.kind not in "bui":
+        raise ValueError(f"{what}: an array of shape {arr.shape} and dtype {arr.dtype}; a bit code is a 1-d uint8 array of "
+                         f"{nbits // 8} entries or a 1-d bool / 0-1 array of {nbits} entries")
+    if arr.dtype == np.uint8 and arr.size == nbits // 8:
+        return np.frombuffer(np.ascontiguousarray(arr).tobytes(), dtype="<u8").astype(np.uint64)
+    if arr.size != nbits:
+        raise ValueError(f"{what}: {arr.size} entries; a {nbits}-bit code is {nbits} bits (or {nbits // 8} uint8 bytes)")
+    if arr.dtype.kind != "b" and ((arr != 0) & (arr != 1)).any():
+        raise ValueError(f"{what}: a bit array holds 0 and 1 only")
+    packed = np.packbits(arr.astype(bool), bitorder="little")
+    return np.frombuffer(packed.tobytes(), dtype="<u8").astype(np.uint64)
+
+
+def encode_bits_column(name: str, kind: str, values) -> BitsColumn:
+    """One bits attribute's values of a batch -> ``BitsColumn``.  ``None`` = absent; see ``encode_bits_code`` for the forms a
+    code comes in and what is refused; the whole batch is checked before anything is returned."""
+    nbits = bits_width(kind)
+    n = len(values)
+    words = np.zeros((n, nbits // 64), dtype=np.uint64)
+    present = np.zeros(n, dtype=np.uint8)
+    for i in range(n):
+        v = values[i]
+        if v is not None:
+            words[i] = encode_bits_code(v, nbits, f"attribute {name!r} ({kind}): row {i}")
+            present[i] = 1
+    return BitsColumn(words, present)
 
 
 def encode_column(name: str, kind: str, values, codes: Dict[str, int]) -> np.ndarray:
