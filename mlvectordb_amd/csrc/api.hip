@@ -464,15 +464,15 @@ int scan_step(mlvdb_index* h, hipStream_t s, int64_t rows, Launch&& launch) {
     return MLVDB_OK;
 }
 
-// ---- exact scan of rows [row_begin,row_end) for a set of queries of the prepared batch.
+// ---- exact scan of rows [0,row_end) for a set of queries of the prepared batch.
 // Qpad/qaux point at query 0 of the set's index space; qsel (device) lists the members or is null.
 int run_exact(mlvdb_index* h, hipStream_t s, const float* Qpad, const double* qaux, int32_t nq_sel,
-              const int32_t* qsel, int64_t row_begin, int64_t row_end, int32_t k, int64_t* out_labels,
+              const int32_t* qsel, int64_t row_end, int32_t k, int64_t* out_labels,
               float* out_dist, int32_t* out_counts, double* out_d64, bool is_main_scan,
               const int32_t* nq_sel_dev = nullptr, const double* cursor_d = nullptr,
               const int32_t* cursor_l = nullptr) {
     if (nq_sel <= 0) return MLVDB_OK;
-    ExactPlan plan = plan_exact(row_end - row_begin, h->ld, nq_sel, k);
+    ExactPlan plan = plan_exact(row_end, h->ld, nq_sel, k);
     if (nq_sel_dev) {
         // device-decided fallback: usually zero or a few queries are selected, so spread each query
         // tile over many blocks; blocks of unselected tiles exit at once
@@ -483,7 +483,6 @@ int run_exact(mlvdb_index* h, hipStream_t s, const float* Qpad, const double* qa
     ExactArgs a{};
     a.X = h->X;
     a.rn = h->rn;
-    a.row_begin = row_begin;
     a.row_end = row_end;
     a.ld = h->ld;
     a.space = h->space;
@@ -497,7 +496,7 @@ int run_exact(mlvdb_index* h, hipStream_t s, const float* Qpad, const double* qa
     a.cursor_l = cursor_l;
     a.partial = h->partial.as<TopEntry>();
     if (is_main_scan) {
-        int rc = scan_step(h, s, (row_end - row_begin) * plan.nqtiles, [&] { return launch_exact_scan(a, plan, s); });
+        int rc = scan_step(h, s, row_end * plan.nqtiles, [&] { return launch_exact_scan(a, plan, s); });
         if (rc) return rc;
     } else {
         HIP_TRY(h, launch_exact_scan(a, plan, s));
@@ -758,7 +757,7 @@ int finish_filter_pass(mlvdb_index* h, hipStream_t s, FilterArgs& fa, int32_t q0
         h->deferred = true;
         return MLVDB_OK;
     }
-    return run_exact(h, s, fa.Qpad, fa.qaux, nq, h->qsel.as<int32_t>(), 0, h->total, k, out_labels + (size_t)q0 * k,
+    return run_exact(h, s, fa.Qpad, fa.qaux, nq, h->qsel.as<int32_t>(), h->total, k, out_labels + (size_t)q0 * k,
                      out_dist + (size_t)q0 * k, out_counts + q0, out_d64 ? out_d64 + (size_t)q0 * k : nullptr, false, nflag);
 }
 
@@ -828,7 +827,7 @@ int run_filter_pass(mlvdb_index* h, hipStream_t s, const float* queries_raw, int
         HIP_TRY(h, h->seed_dist.ensure((size_t)kFilterQueries * k * sizeof(float)));
         HIP_TRY(h, h->seed_cnt.ensure(kFilterQueries * sizeof(int32_t)));
         HIP_TRY(h, h->seed_d64.ensure((size_t)kFilterQueries * k * sizeof(double)));
-        rc = run_exact(h, s, fa.Qpad, fa.qaux, nq, nullptr, 0, n_seed, k, h->seed_lab.as<int64_t>(),
+        rc = run_exact(h, s, fa.Qpad, fa.qaux, nq, nullptr, n_seed, k, h->seed_lab.as<int64_t>(),
                        h->seed_dist.as<float>(), h->seed_cnt.as<int32_t>(), h->seed_d64.as<double>(), false);
         if (rc) return rc;
         HIP_TRY(h, launch_filter_seed_thr(fa, h->seed_d64.as<double>(), k, s));
@@ -1042,7 +1041,7 @@ int run_paged_exact(mlvdb_index* h, hipStream_t s, const float* Qpad, const doub
     HIP_TRY(h, hipGetLastError());
     for (int32_t offset = 0; offset < k; offset += page) {
         const int32_t kp = std::min(page, k - offset);
-        int rc = run_exact(h, s, Qpad, qaux, nsel, qsel, 0, h->total, kp, h->page_lab.as<int64_t>(),
+        int rc = run_exact(h, s, Qpad, qaux, nsel, qsel, h->total, kp, h->page_lab.as<int64_t>(),
                            h->page_dist.as<float>(), h->page_cnt.as<int32_t>(), h->page_d64.as<double>(), true, nullptr,
                            h->cur_d.as<double>(), h->cur_l.as<int32_t>());
         if (rc) return rc;
@@ -1571,7 +1570,7 @@ static int search_device_impl(mlvdb_index* h, const float* queries_device, int64
             if (rc) return rc;
         }
     } else if (route == kRouteExact) {
-        rc = run_exact(h, s, h->qpad.as<float>(), h->qaux.as<double>(), (int32_t)nq, nullptr, 0, h->total, k,
+        rc = run_exact(h, s, h->qpad.as<float>(), h->qaux.as<double>(), (int32_t)nq, nullptr, h->total, k,
                        out_labels_device, out_dist_device, out_counts_device, out_dist64_device, true);
         if (rc) return rc;
     }
@@ -1647,7 +1646,7 @@ int search_host(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int
                 const FilterArgs& fa = h->deferred_fa;
                 HIP_TRY(h, hipMemcpyAsync(h->qsel.p, sel, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
                 HIP_TRY(h, hipStreamSynchronize(h->stream));  // `sel` is on this stack frame
-                rc = run_exact(h, h->stream, fa.Qpad, fa.qaux, n, h->qsel.as<int32_t>(), 0, h->total, k, d_lab, d_dist, d_cnt, d_d64,
+                rc = run_exact(h, h->stream, fa.Qpad, fa.qaux, n, h->qsel.as<int32_t>(), h->total, k, d_lab, d_dist, d_cnt, d_d64,
                                false);
                 if (rc) return rc;
                 continue;  // copy the corrected outputs

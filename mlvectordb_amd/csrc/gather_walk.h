@@ -12,15 +12,16 @@ namespace mlvdb {
 constexpr int kGatherWaves = 4;  // waves per block (256 threads), 16 labels each per step
 
 // qs[t][0 .. ld) = query qid[t] of Qpad as fp64 (zeros for an empty slot), qinv[t] = its qaux; then the block's barrier.
+// For a block of NW waves: the streamed scans (panel_walk.h) stage their tiles with it too.
 // (qinv is read behind all the copies: read between them, it costs where_gather_kernel<cosine, 2> ten VGPRs and with them
 // one of its four waves per SIMD.)
-template <int QT>
+template <int QT, int NW = kGatherWaves>
 __device__ __forceinline__ void gather_stage_queries(double* qs, const float* __restrict__ Qpad,
                                                      const double* __restrict__ qaux, const int (&qid)[QT], int ld,
                                                      double (&qinv)[QT]) {
 #pragma unroll
     for (int t = 0; t < QT; ++t)
-        for (int c = threadIdx.x; c < ld; c += kGatherWaves * 64)
+        for (int c = threadIdx.x; c < ld; c += NW * 64)
             qs[t * ld + c] = qid[t] >= 0 ? (double)Qpad[(int64_t)qid[t] * ld + c] : 0.0;
 #pragma unroll
     for (int t = 0; t < QT; ++t) qinv[t] = qid[t] >= 0 ? qaux[qid[t]] : 0.0;
@@ -51,10 +52,9 @@ __device__ __forceinline__ void gather_walk(const float* __restrict__ X, const i
 
 // The lists of all waves through LDS (smem: [waves][QT][64] distances, then as many labels; it aliases the query tile,
 // hence the barrier first) into one list of k entries per filled slot: out(t)[0 .. k), the slot's partial list.
-template <int QT, class Out>
+template <int QT, int NW = kGatherWaves, class Out>
 __device__ __forceinline__ void gather_block_merge(char* smem, const WaveTopK (&top)[QT], const int (&qid)[QT], int k,
                                                    Out&& out) {
-    constexpr int NW = kGatherWaves;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads();
     double* ld_d = reinterpret_cast<double*>(smem);                                            // [NW][QT][64]

@@ -77,6 +77,38 @@ inline hipError_t with_space_qt(int32_t space, int32_t qt, F&& f) {
     });
 }
 
+// The tiles of the exact scan and of the scans that keep its geometry (distinct, maxsim): queries per tile, panels of 16
+// rows per wave step, waves per block.  plan_exact picks the tile and sizes the grid by it; with_exact_tile instantiates it.
+struct ExactTile {
+    int qt, pw, nw;
+};
+constexpr ExactTile kExactTiles[4] = {{1, 2, 16}, {2, 2, 16}, {4, 4, 8}, {8, 2, 8}};
+constexpr int exact_tile_index(int qt) { return qt == 1 ? 0 : qt == 2 ? 1 : qt == 4 ? 2 : 3; }
+
+// f(SPACE, QT, PW, NW): the space and the tile of `qt` queries as compile-time constants.
+template <class F>
+inline hipError_t with_exact_tile(int32_t space, int32_t qt, F&& f) {
+    return with_space(space, [&](auto sp) {
+        auto tile = [&](auto i) {
+            constexpr ExactTile t = kExactTiles[decltype(i)::value];
+            return f(sp, std::integral_constant<int, t.qt>{}, std::integral_constant<int, t.pw>{},
+                     std::integral_constant<int, t.nw>{});
+        };
+        switch (exact_tile_index(qt)) {
+            case 0: return tile(std::integral_constant<int, 0>{});
+            case 1: return tile(std::integral_constant<int, 1>{});
+            case 2: return tile(std::integral_constant<int, 2>{});
+            default: return tile(std::integral_constant<int, 3>{});
+        }
+    });
+}
+
+// The most dynamic LDS a kernel that stages fp64 query images by plan_exact's rule may ask for: an image of one query is
+// ld x 8 B <= 64 KiB (ld <= 8192: mlvdb_index_create refuses a wider row), a tile of more queries is halved until its
+// image fits 64 KiB, and the block merges' lists stay below that (at most 8 x 8 x 64 x 12 B = 48 KiB for the exact scan,
+// 16 x 2 x 64 x 20 B = 40 KiB for the distinct scan).
+constexpr int kQueryImageMaxLds = 64 * 1024;
+
 // ---------------------------------------------------------------- tuning state (per handle)
 // Every knob the kernels' launchers and the pass orchestration consult.  Filled ONCE, by mlvdb_index_create, from the
 // MLVDB_* environment variables of that moment (tuning_from_env, api.hip: the library's only getenv loop), and changed
@@ -168,8 +200,7 @@ ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k);
 struct ExactArgs {
     const float* X;
     const float* rn;
-    int64_t row_begin;   // first row scanned (multiple of 16)
-    int64_t row_end;     // one past the last row scanned (<= total)
+    int64_t row_end;     // rows [0, row_end) are scanned (<= total)
     int32_t ld;
     int32_t space;
     const float* Qpad;   // [nq][ld]

@@ -10,7 +10,7 @@
 #include <algorithm>
 
 #include "internal.h"
-#include "scan_common.h"
+#include "panel_walk.h"
 #include "wave_topk_distinct.h"
 
 namespace mlvdb {
@@ -75,9 +75,6 @@ __global__ __launch_bounds__(NW * 64) void distinct_scan_kernel(const DistinctAr
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int g = lane >> 4;
-    const int r = lane & 15;
-    const int ld = a.ld;
     const int nq_sel = a.nq_sel_dev ? min(*a.nq_sel_dev, a.nq_sel) : a.nq_sel;
     if ((int)blockIdx.y * QT >= nq_sel) return;  // block-uniform: nothing selected for this query tile
 
@@ -87,21 +84,16 @@ __global__ __launch_bounds__(NW * 64) void distinct_scan_kernel(const DistinctAr
         const int sel = blockIdx.y * QT + t;
         qid[t] = sel < nq_sel ? (a.qsel ? a.qsel[sel] : sel) : -1;
     }
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        for (int c = threadIdx.x; c < ld; c += NW * 64)
-            qs[t * ld + c] = qid[t] >= 0 ? (double)a.Qpad[(int64_t)qid[t] * ld + c] : 0.0;
-    }
-    __syncthreads();
-
     double qinv[QT];
+    gather_stage_queries<QT, NW>(qs, a.Qpad, a.qaux, qid, a.ld, qinv);
+
     WaveTopKDistinct top[QT];
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        qinv[t] = qid[t] >= 0 ? a.qaux[qid[t]] : 0.0;
-        top[t].init();
-    }
+    for (int t = 0; t < QT; ++t) top[t].init();
 
+    // panel_walk's loop, written out: through the shared function the eight-query l2 and ip instances come out at 224 and
+    // 221 VGPRs instead of 166 and lose their third wave per SIMD (profiles/r16), whatever shape the sink is given.
+    const int ld = a.ld, g = lane >> 4, r = lane & 15;
     const int64_t panel_end = (a.total + 15) >> 4;
     const int64_t ntasks = (panel_end + PW - 1) / PW;
     for (int64_t task = (int64_t)blockIdx.x * NW + wave; task < ntasks; task += (int64_t)nblk * NW) {
@@ -119,12 +111,8 @@ __global__ __launch_bounds__(NW * 64) void distinct_scan_kernel(const DistinctAr
 #pragma unroll
         for (int p = 0; p < PW; ++p) {
             const int64_t row = panel[p] * kPanelRows + r;
-            bool live = lane < 16 && panel[p] < panel_end && row < a.total;
+            bool live = panel_row_live(a.rn, row, lane < 16 && panel[p] < panel_end && row < a.total);
             int64_t grp = kNoGroup;
-            if (live) {
-                const float nrm = a.rn[row];
-                live = nrm == nrm;  // NaN marks a tombstoned (or masked-out) row
-            }
             if (live) {
                 grp = a.group[row];
                 live = grp != kNoGroup;  // an absent value belongs to no group
@@ -248,35 +236,15 @@ ExactPlan plan_distinct(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k) {
     return p;
 }
 
-template <int SPACE, int QT, int PW, int NW>
-static hipError_t launch_one(const DistinctArgs& a, const ExactPlan& p, hipStream_t s) {
-    auto kern = distinct_scan_kernel<SPACE, QT, PW, NW>;
-    if (p.lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)p.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    kern<<<dim3(p.nblk, p.nqtiles), p.threads, p.lds_bytes, s>>>(a, p.nblk);
-    return hipGetLastError();
-}
-
-template <int SPACE>
-static hipError_t launch_space(const DistinctArgs& a, const ExactPlan& p, hipStream_t s) {
-    switch (p.qt) {  // plan_exact's pairs of (queries per tile, panels per wave step, waves)
-        case 1: return launch_one<SPACE, 1, 2, 16>(a, p, s);
-        case 2: return launch_one<SPACE, 2, 2, 16>(a, p, s);
-        case 4: return launch_one<SPACE, 4, 4, 8>(a, p, s);
-        default: return launch_one<SPACE, 8, 2, 8>(a, p, s);
-    }
-}
-
 hipError_t launch_distinct_scan(const DistinctArgs& a, const ExactPlan& p, hipStream_t s) {
     if (a.nq_sel <= 0) return hipSuccess;
-    switch (a.space) {
-        case kSpaceL2: return launch_space<kSpaceL2>(a, p, s);
-        case kSpaceCosine: return launch_space<kSpaceCosine>(a, p, s);
-        default: return launch_space<kSpaceIp>(a, p, s);
-    }
+    return with_exact_tile(a.space, p.qt, [&](auto sp, auto qt, auto pw, auto nw) {
+        constexpr auto kern = distinct_scan_kernel<decltype(sp)::value, decltype(qt)::value, decltype(pw)::value, decltype(nw)::value>;
+        // plan_distinct: the query image or the merge lists, neither above kQueryImageMaxLds
+        if (hipError_t e = ensure_instance_lds<kern>(p.lds_bytes, kQueryImageMaxLds); e != hipSuccess) return e;
+        kern<<<dim3(p.nblk, p.nqtiles), p.threads, p.lds_bytes, s>>>(a, p.nblk);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_distinct_merge(const DistinctEntry* partial, int32_t nq_sel, const int32_t* nq_sel_dev, const int32_t* qsel,

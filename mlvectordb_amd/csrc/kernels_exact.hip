@@ -10,7 +10,7 @@
 #include <cstdlib>
 
 #include "internal.h"
-#include "scan_common.h"
+#include "panel_walk.h"
 
 namespace mlvdb {
 
@@ -19,10 +19,6 @@ __global__ __launch_bounds__(NW * 64) void exact_scan_kernel(const ExactArgs a, 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
     const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int g = lane >> 4;
-    const int r = lane & 15;
-    const int ld = a.ld;
     const int nq_sel = a.nq_sel_dev ? min(*a.nq_sel_dev, a.nq_sel) : a.nq_sel;
     if ((int)blockIdx.y * QT >= nq_sel) return;  // block-uniform: nothing selected for this query tile
 
@@ -32,132 +28,29 @@ __global__ __launch_bounds__(NW * 64) void exact_scan_kernel(const ExactArgs a, 
         const int sel = blockIdx.y * QT + t;
         qid[t] = sel < nq_sel ? (a.qsel ? a.qsel[sel] : sel) : -1;
     }
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        for (int c = threadIdx.x; c < ld; c += NW * 64)
-            qs[t * ld + c] = qid[t] >= 0 ? (double)a.Qpad[(int64_t)qid[t] * ld + c] : 0.0;
-    }
-    __syncthreads();
-
     double qinv[QT];
+    gather_stage_queries<QT, NW>(qs, a.Qpad, a.qaux, qid, a.ld, qinv);
+
     double cur_d[QT];
     int32_t cur_l[QT];
     WaveTopK top[QT];
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
-        qinv[t] = qid[t] >= 0 ? a.qaux[qid[t]] : 0.0;
         const bool has_cur = a.cursor_d != nullptr && qid[t] >= 0;
         cur_d[t] = has_cur ? a.cursor_d[qid[t]] : -__builtin_inf();
         cur_l[t] = has_cur ? a.cursor_l[qid[t]] : -1;
         top[t].init();
     }
-
-    const int64_t panel_begin = a.row_begin >> 4;
-    const int64_t panel_end = (a.row_end + 15) >> 4;
-    const int64_t ntasks = (panel_end - panel_begin + PW - 1) / PW;
-    for (int64_t task = (int64_t)blockIdx.x * NW + wave; task < ntasks; task += (int64_t)nblk * NW) {
-        const float* base[PW];
-        int64_t panel[PW];
-#pragma unroll
-        for (int p = 0; p < PW; ++p) {
-            panel[p] = panel_begin + task * PW + p;
-            const int64_t pp = panel[p] < panel_end ? panel[p] : panel_begin;  // keep the address valid
-            base[p] = a.X + pp * (int64_t)(kPanelRows * ld) + lane_group_offset(lane);
-        }
-        double acc[PW][QT];
-        double nx[PW];
-        accumulate_rows<SPACE, QT, PW, (QT == 8 ? 4 : 0), /*NT=*/true>(base, qs, ld, g, acc, nx);  // every row is read once per launch
-#pragma unroll
-        for (int p = 0; p < PW; ++p) {
-            const int64_t row = panel[p] * kPanelRows + r;
-            bool live = lane < 16 && panel[p] < panel_end && row >= a.row_begin && row < a.row_end;
-            if (live) {
-                const float nrm = a.rn[row];
-                live = nrm == nrm;  // NaN marks a tombstoned row
-            }
-#pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                const double dist = finish_distance<SPACE>(acc[p][t], nx[p], qinv[t]);
-                const bool want = live && qid[t] >= 0 && entry_less(cur_d[t], cur_l[t], dist, (int32_t)row);
-                top[t].offer(want, dist, (int32_t)row, a.k, lane);
-            }
-        }
-    }
-
-    // ---- block merge: lists of all waves through LDS (aliases the query tile)
-    __syncthreads();
-    double* ld_d = reinterpret_cast<double*>(smem);                                  // [NW][QT][64]
-    int32_t* ld_l = reinterpret_cast<int32_t*>(smem + (size_t)NW * QT * 64 * sizeof(double));  // [NW][QT][64]
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        ld_d[(wave * QT + t) * 64 + lane] = top[t].d;
-        ld_l[(wave * QT + t) * 64 + lane] = top[t].l;
-    }
-    __syncthreads();
-    for (int t = wave; t < QT; t += NW) {
-        WaveTopK m;
-        m.init();
-        for (int w2 = 0; w2 < NW; ++w2) {
-            const double cd = ld_d[(w2 * QT + t) * 64 + lane];
-            const int32_t cl = ld_l[(w2 * QT + t) * 64 + lane];
-            m.offer(lane < a.k && cl != kNoLabel, cd, cl, a.k, lane);
-        }
-        const int sel = blockIdx.y * QT + t;
-        if (sel < nq_sel && lane < a.k) {
-            TopEntry e;
-            e.d = m.d;
-            e.l = m.l;
-            e.pad = 0;
-            a.partial[((int64_t)sel * nblk + blockIdx.x) * a.k + lane] = e;
-        }
-    }
-}
-
-// One block (4 waves) per selected query: each wave folds a quarter of the partial entries,
-// wave 0 folds the four lists and writes the final answer.
-__global__ __launch_bounds__(256) void exact_merge_kernel(const TopEntry* __restrict__ partial,
-                                                          const int32_t* nq_sel_dev, const int32_t* qsel,
-                                                          int32_t nblk, int32_t k, int64_t* out_labels,
-                                                          float* out_dist, int32_t* out_counts, double* out_d64) {
-    __shared__ double sd[4][64];
-    __shared__ int32_t sl[4][64];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int sel = blockIdx.x;
-    if (nq_sel_dev && sel >= *nq_sel_dev) return;
-    const int q = qsel ? qsel[sel] : sel;
-    const TopEntry* src = partial + (int64_t)sel * nblk * k;
-    const int64_t n = (int64_t)nblk * k;
-    WaveTopK m;
-    m.init();
-    for (int64_t i0 = (int64_t)wave * 64; i0 < n; i0 += 256) {
-        const int64_t i = i0 + lane;
-        TopEntry e;
-        e.d = __builtin_inf();
-        e.l = kNoLabel;
-        if (i < n) e = src[i];
-        m.offer(e.l != kNoLabel, e.d, e.l, k, lane);
-    }
-    sd[wave][lane] = m.d;
-    sl[wave][lane] = m.l;
-    __syncthreads();
-    if (wave != 0) return;
-    WaveTopK f;
-    f.init();
-#pragma unroll
-    for (int w2 = 0; w2 < 4; ++w2) {
-        const double cd = sd[w2][lane];
-        const int32_t cl = sl[w2][lane];
-        f.offer(lane < k && cl != kNoLabel, cd, cl, k, lane);
-    }
-    const bool valid = lane < k && f.l != kNoLabel;
-    if (lane < k) {
-        out_labels[(int64_t)q * k + lane] = valid ? (int64_t)f.l : -1;
-        out_dist[(int64_t)q * k + lane] = valid ? (float)f.d : __builtin_inff();
-        if (out_d64) out_d64[(int64_t)q * k + lane] = valid ? f.d : __builtin_inf();
-    }
-    const int cnt = __popcll(__ballot(valid));
-    if (lane == 0) out_counts[q] = cnt;
+    // every row is read once per launch, hence the non-temporal loads
+    panel_walk<SPACE, QT, PW, NW, (QT == 8 ? 4 : 0), /*NT=*/true>(
+        a.X, a.ld, a.row_end, nblk, qs, qinv, [&](int64_t row, bool in) { return panel_row_live(a.rn, row, in); },
+        [&](int t, bool live, double dist, int32_t row) {
+            const bool want = live && qid[t] >= 0 && entry_less(cur_d[t], cur_l[t], dist, row);
+            top[t].offer(want, dist, row, a.k, lane);
+        });
+    gather_block_merge<QT, NW>(smem, top, qid, a.k, [&](int t) {
+        return a.partial + ((int64_t)(blockIdx.y * QT + t) * nblk + blockIdx.x) * a.k;
+    });
 }
 
 // Range-query candidate generator: same scan, but every live row with dist <= radius is
@@ -169,61 +62,29 @@ __global__ __launch_bounds__(512) void exact_range_kernel(const FilterArgs a, co
     constexpr int PW = 2, NW = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int g = lane >> 4;
-    const int r = lane & 15;
-    const int ld = a.ld;
     int qid[QT];
-    double qinv[QT];
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         const int sel = blockIdx.y * QT + t;
         qid[t] = sel < nsel ? (qsel ? qsel[sel] : sel) : -1;
-        for (int c = threadIdx.x; c < ld; c += NW * 64)
-            qs[t * ld + c] = qid[t] >= 0 ? (double)a.Qpad[(int64_t)qid[t] * ld + c] : 0.0;
-        qinv[t] = qid[t] >= 0 ? a.qaux[qid[t]] : 0.0;
     }
-    __syncthreads();
-    const int64_t panel_end = (a.total + 15) >> 4;
-    const int64_t ntasks = (panel_end + PW - 1) / PW;
-    for (int64_t task = (int64_t)blockIdx.x * NW + wave; task < ntasks; task += (int64_t)nblk * NW) {
-        const float* base[PW];
-        int64_t panel[PW];
-#pragma unroll
-        for (int p = 0; p < PW; ++p) {
-            panel[p] = task * PW + p;
-            const int64_t pp = panel[p] < panel_end ? panel[p] : 0;
-            base[p] = a.X + pp * (int64_t)(kPanelRows * ld) + lane_group_offset(lane);
-        }
-        double acc[PW][QT];
-        double nx[PW];
-        accumulate_rows<SPACE, QT, PW>(base, qs, ld, g, acc, nx);
-#pragma unroll
-        for (int p = 0; p < PW; ++p) {
-            const int64_t row = panel[p] * kPanelRows + r;
-            bool live = lane < 16 && panel[p] < panel_end && row < a.total;
-            if (live) {
-                const float nrm = a.rn[row];
-                live = nrm == nrm;
-            }
-#pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                const double dist = finish_distance<SPACE>(acc[p][t], nx[p], qinv[t]);
-                if (live && qid[t] >= 0 && dist <= radius) {
-                    const uint32_t slot = atomicAdd(&a.cnt[qid[t]], 1u);
-                    if (slot < (uint32_t)a.cand_cap) {
-                        CandEntry e;
-                        e.u = 0.f;
-                        e.row = (int32_t)row;
-                        a.cand[(int64_t)qid[t] * a.cand_cap + slot] = e;
-                    } else {
-                        a.overflow[qid[t]] = 1u;
-                    }
+    double qinv[QT];
+    gather_stage_queries<QT, NW>(qs, a.Qpad, a.qaux, qid, a.ld, qinv);
+    panel_walk<SPACE, QT, PW, NW, 0, /*NT=*/false>(
+        a.X, a.ld, a.total, nblk, qs, qinv, [&](int64_t row, bool in) { return panel_row_live(a.rn, row, in); },
+        [&](int t, bool live, double dist, int32_t row) {
+            if (live && qid[t] >= 0 && dist <= radius) {
+                const uint32_t slot = atomicAdd(&a.cnt[qid[t]], 1u);
+                if (slot < (uint32_t)a.cand_cap) {
+                    CandEntry e;
+                    e.u = 0.f;
+                    e.row = row;
+                    a.cand[(int64_t)qid[t] * a.cand_cap + slot] = e;
+                } else {
+                    a.overflow[qid[t]] = 1u;
                 }
             }
-        }
-    }
+        });
 }
 
 hipError_t launch_exact_range_scan(const FilterArgs& a, float radius, const int32_t* qsel, int32_t nsel, hipStream_t s) {
@@ -240,23 +101,13 @@ hipError_t launch_exact_range_scan(const FilterArgs& a, float radius, const int3
     if (nblk > cap) nblk = cap;
     if (nblk < 1) nblk = 1;
     const size_t lds = (size_t)qt * a.ld * sizeof(double);
-    hipError_t e = hipSuccess;
-#define MLVDB_LAUNCH_ER(SP)                                                                                      \
-    do {                                                                                                         \
-        auto kern = qt == 4 ? exact_range_kernel<SP, 4> : qt == 2 ? exact_range_kernel<SP, 2> : exact_range_kernel<SP, 1>; \
-        if (lds > 48 * 1024)                                                                                     \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)lds);                                                                   \
-        if (e == hipSuccess) kern<<<dim3((unsigned)nblk, nqtiles), 512, lds, s>>>(a, (double)radius, (int)nblk, qsel, nsel); \
-    } while (0)
-    switch (a.space) {
-        case kSpaceL2: MLVDB_LAUNCH_ER(kSpaceL2); break;
-        case kSpaceCosine: MLVDB_LAUNCH_ER(kSpaceCosine); break;
-        default: MLVDB_LAUNCH_ER(kSpaceIp); break;
-    }
-#undef MLVDB_LAUNCH_ER
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
+    return with_space_qt(a.space, qt, [&](auto sp, auto qtc) {
+        constexpr auto kern = exact_range_kernel<decltype(sp)::value, decltype(qtc)::value>;
+        // the halving above keeps the image within kQueryImageMaxLds
+        if (hipError_t e = ensure_instance_lds<kern>(lds, kQueryImageMaxLds); e != hipSuccess) return e;
+        kern<<<dim3((unsigned)nblk, nqtiles), 512, lds, s>>>(a, (double)radius, (int)nblk, qsel, nsel);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------------------ host side
@@ -339,21 +190,16 @@ hipError_t launch_prefix_exact(const float* X, const float* rn, const float* Qpa
     const bool pf24 = (ld / 16) % 24 == 0;
     const int nw = 4;  // waves per block, 16 rows each
     const dim3 grid((unsigned)nq, (unsigned)(((int64_t)m + 16 * nw - 1) / (16 * nw)));
-    hipError_t e = hipSuccess;
-#define MLVDB_LAUNCH_PREFIX(SP)                                                                                        \
-    do {                                                                                                               \
-        auto kern = pf24 ? prefix_exact_kernel<SP, 24> : prefix_exact_kernel<SP, 8>;                                   \
-        if (lds > 48 * 1024)                                                                                           \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess) kern<<<grid, nw * 64, lds, s>>>(X, rn, Qpad, qaux, m, ld, d64);                               \
-    } while (0)
-    switch (space) {
-        case kSpaceL2: MLVDB_LAUNCH_PREFIX(kSpaceL2); break;
-        case kSpaceCosine: MLVDB_LAUNCH_PREFIX(kSpaceCosine); break;
-        default: MLVDB_LAUNCH_PREFIX(kSpaceIp); break;
-    }
-#undef MLVDB_LAUNCH_PREFIX
-    return e != hipSuccess ? e : hipGetLastError();
+    return with_space(space, [&](auto sp) {
+        auto launch = [&](auto pf) {
+            constexpr auto kern = prefix_exact_kernel<decltype(sp)::value, decltype(pf)::value>;
+            // one query's image: within kQueryImageMaxLds
+            if (hipError_t e = ensure_instance_lds<kern>(lds, kQueryImageMaxLds); e != hipSuccess) return e;
+            kern<<<grid, nw * 64, lds, s>>>(X, rn, Qpad, qaux, m, ld, d64);
+            return hipGetLastError();
+        };
+        return pf24 ? launch(std::integral_constant<int, 24>{}) : launch(std::integral_constant<int, 8>{});
+    });
 }
 
 hipError_t launch_pair_distances(const float* X, const float* Qpad, const double* qaux, const int64_t* labels, int32_t nq,
@@ -361,21 +207,13 @@ hipError_t launch_pair_distances(const float* X, const float* Qpad, const double
     if (nq <= 0 || m <= 0) return hipSuccess;
     const size_t lds = (size_t)ld * sizeof(double);
     const dim3 grid((unsigned)nq, (unsigned)std::min<int64_t>(64, ((int64_t)m + 63) / 64));
-    hipError_t e = hipSuccess;
-#define MLVDB_LAUNCH_PAIRS(SP)                                                                                         \
-    do {                                                                                                               \
-        auto kern = pair_distance_kernel<SP>;                                                                          \
-        if (lds > 48 * 1024)                                                                                           \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e == hipSuccess) kern<<<grid, 256, lds, s>>>(X, Qpad, qaux, labels, m, ld, out64, out32);                   \
-    } while (0)
-    switch (space) {
-        case kSpaceL2: MLVDB_LAUNCH_PAIRS(kSpaceL2); break;
-        case kSpaceCosine: MLVDB_LAUNCH_PAIRS(kSpaceCosine); break;
-        default: MLVDB_LAUNCH_PAIRS(kSpaceIp); break;
-    }
-#undef MLVDB_LAUNCH_PAIRS
-    return e != hipSuccess ? e : hipGetLastError();
+    return with_space(space, [&](auto sp) {
+        constexpr auto kern = pair_distance_kernel<decltype(sp)::value>;
+        // one query's image: within kQueryImageMaxLds
+        if (hipError_t e = ensure_instance_lds<kern>(lds, kQueryImageMaxLds); e != hipSuccess) return e;
+        kern<<<grid, 256, lds, s>>>(X, Qpad, qaux, labels, m, ld, out64, out32);
+        return hipGetLastError();
+    });
 }
 
 ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k) {
@@ -383,8 +221,7 @@ ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k) {
     int qt = nq_sel >= 8 ? 8 : nq_sel >= 4 ? 4 : nq_sel >= 2 ? 2 : 1;
     while (qt > 1 && (size_t)qt * ld * sizeof(double) > 64 * 1024) qt >>= 1;
     p.qt = qt;
-    const int nw = qt <= 2 ? 16 : 8;
-    const int pw = qt == 4 ? 4 : 2;
+    const int nw = kExactTiles[exact_tile_index(qt)].nw, pw = kExactTiles[exact_tile_index(qt)].pw;
     p.threads = nw * 64;
     p.nqtiles = (nq_sel + qt - 1) / qt;
     const int64_t npanels = (nrows + 15) / 16;
@@ -404,43 +241,23 @@ ExactPlan plan_exact(int64_t nrows, int32_t ld, int32_t nq_sel, int32_t k) {
     return p;
 }
 
-template <int SPACE, int QT, int PW, int NW>
-static hipError_t launch_one(const ExactArgs& a, const ExactPlan& p, hipStream_t s) {
-    auto kern = exact_scan_kernel<SPACE, QT, PW, NW>;
-    if (p.lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    kern<<<dim3(p.nblk, p.nqtiles), p.threads, p.lds_bytes, s>>>(a, p.nblk);
-    return hipGetLastError();
-}
-
-template <int SPACE>
-static hipError_t launch_space(const ExactArgs& a, const ExactPlan& p, hipStream_t s) {
-    switch (p.qt) {
-        case 1: return launch_one<SPACE, 1, 2, 16>(a, p, s);
-        case 2: return launch_one<SPACE, 2, 2, 16>(a, p, s);
-        case 4: return launch_one<SPACE, 4, 4, 8>(a, p, s);
-        default: return launch_one<SPACE, 8, 2, 8>(a, p, s);
-    }
-}
-
 hipError_t launch_exact_scan(const ExactArgs& a, const ExactPlan& p, hipStream_t s) {
     if (a.nq_sel <= 0) return hipSuccess;
-    switch (a.space) {
-        case kSpaceL2: return launch_space<kSpaceL2>(a, p, s);
-        case kSpaceCosine: return launch_space<kSpaceCosine>(a, p, s);
-        default: return launch_space<kSpaceIp>(a, p, s);
-    }
+    return with_exact_tile(a.space, p.qt, [&](auto sp, auto qt, auto pw, auto nw) {
+        constexpr auto kern = exact_scan_kernel<decltype(sp)::value, decltype(qt)::value, decltype(pw)::value, decltype(nw)::value>;
+        // plan_exact: the query image or the merge lists, neither above kQueryImageMaxLds
+        if (hipError_t e = ensure_instance_lds<kern>(p.lds_bytes, kQueryImageMaxLds); e != hipSuccess) return e;
+        kern<<<dim3(p.nblk, p.nqtiles), p.threads, p.lds_bytes, s>>>(a, p.nblk);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_exact_merge(const TopEntry* partial, int32_t nq_sel, const int32_t* nq_sel_dev, const int32_t* qsel,
                               int32_t nblk, int32_t k, int64_t* out_labels, float* out_dist, int32_t* out_counts,
                               double* out_d64, hipStream_t s) {
     if (nq_sel <= 0) return hipSuccess;
-    exact_merge_kernel<<<nq_sel, 256, 0, s>>>(partial, nq_sel_dev, qsel, nblk, k, out_labels, out_dist, out_counts,
-                                              out_d64);
+    exact_merge_kernel<false><<<nq_sel, 256, 0, s>>>(partial, nq_sel_dev, qsel, nblk, k, out_labels, out_dist, out_counts,
+                                                     out_d64);
     return hipGetLastError();
 }
 

@@ -9,7 +9,7 @@
 
 #include "group_table.h"
 #include "internal.h"
-#include "scan_common.h"
+#include "panel_walk.h"
 #include "wave_peel.h"
 
 namespace mlvdb {
@@ -62,11 +62,6 @@ template <int SPACE, int QT, int PW, int NW>
 __global__ __launch_bounds__(NW * 64) void maxsim_scan_kernel(const MaxsimArgs a, const int nblk) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* qs = reinterpret_cast<double*>(smem);  // [QT][ld]
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int g = lane >> 4;
-    const int r = lane & 15;
-    const int ld = a.ld;
 
     int qid[QT];
 #pragma unroll
@@ -74,80 +69,33 @@ __global__ __launch_bounds__(NW * 64) void maxsim_scan_kernel(const MaxsimArgs a
         const int tok = blockIdx.y * QT + t;
         qid[t] = tok < a.ntok ? tok : -1;
     }
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        for (int c = threadIdx.x; c < ld; c += NW * 64)
-            qs[t * ld + c] = qid[t] >= 0 ? (double)a.Qpad[(int64_t)qid[t] * ld + c] : 0.0;
-    }
-    __syncthreads();
-
     double qinv[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) qinv[t] = qid[t] >= 0 ? a.qaux[qid[t]] : 0.0;
-
-    const int64_t panel_end = (a.total + 15) >> 4;
-    const int64_t ntasks = (panel_end + PW - 1) / PW;
-    for (int64_t task = (int64_t)blockIdx.x * NW + wave; task < ntasks; task += (int64_t)nblk * NW) {
-        const float* base[PW];
-        int64_t panel[PW];
-#pragma unroll
-        for (int p = 0; p < PW; ++p) {
-            panel[p] = task * PW + p;
-            const int64_t pp = panel[p] < panel_end ? panel[p] : 0;  // keep the address valid
-            base[p] = a.X + pp * (int64_t)(kPanelRows * ld) + lane_group_offset(lane);
-        }
-        double acc[PW][QT];
-        double nx[PW];
-        accumulate_rows<SPACE, QT, PW, (QT == 8 ? 4 : 0), /*NT=*/true>(base, qs, ld, g, acc, nx);  // every row is read once per launch
-#pragma unroll
-        for (int p = 0; p < PW; ++p) {
-            const int64_t row = panel[p] * kPanelRows + r;
-            const bool in = lane < 16 && panel[p] < panel_end && row < a.total;
-            const int32_t doc = in ? a.row_doc[row] : -1;  // -1: tombstoned, masked out or in no document
-#pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                const double dist = finish_distance<SPACE>(acc[p][t], nx[p], qinv[t]);
-                const bool want = doc >= 0 && qid[t] >= 0 && dist == dist;  // (a NaN is never a best distance)
-                unsigned long long* const cells = a.best + (int64_t)(qid[t] >= 0 ? qid[t] : 0) * a.ndocs;
-                wave_peel_min<16>(want, doc, maxsim_key(dist), [&](int32_t d, unsigned long long key) {
-                    unsigned long long* const cell = cells + d;
-                    if (__hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(cell, key);
-                });
-            }
-        }
-    }
-}
-
-template <int SPACE, int QT, int PW, int NW>
-static hipError_t launch_one(const MaxsimArgs& a, const ExactPlan& p, hipStream_t s) {
-    auto kern = maxsim_scan_kernel<SPACE, QT, PW, NW>;
-    const size_t lds = (size_t)QT * a.ld * sizeof(double);  // the query tile alone: there is no block merge
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    kern<<<dim3(p.nblk, p.nqtiles), p.threads, lds, s>>>(a, p.nblk);
-    return hipGetLastError();
-}
-
-template <int SPACE>
-static hipError_t launch_space(const MaxsimArgs& a, const ExactPlan& p, hipStream_t s) {
-    switch (p.qt) {  // plan_exact's pairs of (tokens per tile, panels per wave step, waves)
-        case 1: return launch_one<SPACE, 1, 2, 16>(a, p, s);
-        case 2: return launch_one<SPACE, 2, 2, 16>(a, p, s);
-        case 4: return launch_one<SPACE, 4, 4, 8>(a, p, s);
-        default: return launch_one<SPACE, 8, 2, 8>(a, p, s);
-    }
+    gather_stage_queries<QT, NW>(qs, a.Qpad, a.qaux, qid, a.ld, qinv);
+    // the exact scan's instance of the walk; every row is read once per launch
+    panel_walk<SPACE, QT, PW, NW, (QT == 8 ? 4 : 0), /*NT=*/true>(
+        a.X, a.ld, a.total, nblk, qs, qinv,
+        [&](int64_t row, bool in) { return in ? a.row_doc[row] : -1; },  // -1: tombstoned, masked out or in no document
+        [&](int t, int32_t doc, double dist, int32_t) {
+            const bool want = doc >= 0 && qid[t] >= 0 && dist == dist;  // (a NaN is never a best distance)
+            unsigned long long* const cells = a.best + (int64_t)(qid[t] >= 0 ? qid[t] : 0) * a.ndocs;
+            wave_peel_min<16>(want, doc, maxsim_key(dist), [&](int32_t d, unsigned long long key) {
+                unsigned long long* const cell = cells + d;
+                if (__hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(cell, key);
+            });
+        });
 }
 
 hipError_t launch_maxsim_scan(const MaxsimArgs& a, const ExactPlan& p, hipStream_t s) {
     if (a.ntok <= 0 || a.total <= 0) return hipSuccess;
     if (p.nqtiles > 65535) return hipErrorInvalidValue;
-    switch (a.space) {
-        case kSpaceL2: return launch_space<kSpaceL2>(a, p, s);
-        case kSpaceCosine: return launch_space<kSpaceCosine>(a, p, s);
-        default: return launch_space<kSpaceIp>(a, p, s);
-    }
+    const size_t lds = (size_t)p.qt * a.ld * sizeof(double);  // the query tile alone: there is no block merge
+    return with_exact_tile(a.space, p.qt, [&](auto sp, auto qt, auto pw, auto nw) {
+        constexpr auto kern = maxsim_scan_kernel<decltype(sp)::value, decltype(qt)::value, decltype(pw)::value, decltype(nw)::value>;
+        // plan_exact's halving keeps the image within kQueryImageMaxLds
+        if (hipError_t e = ensure_instance_lds<kern>(lds, kQueryImageMaxLds); e != hipSuccess) return e;
+        kern<<<dim3(p.nblk, p.nqtiles), p.threads, lds, s>>>(a, p.nblk);
+        return hipGetLastError();
+    });
 }
 
 // Grid (blocks per query, queries of the chunk), 4 waves.  A lane takes documents g, adjacent lanes adjacent g (the reads of

@@ -161,23 +161,13 @@ hipError_t launch_mmr_select(const float* X, int32_t dim, int32_t ld, int32_t sp
     if (nq <= 0) return hipSuccess;
     const size_t lds = mmr_select_lds(ld, fetch_k);
     if (lds > 64 * 1024) return hipErrorInvalidValue;  // (the entry point refuses such a call before anything is launched)
-    hipError_t e = hipSuccess;
-#define MLVDB_LAUNCH_MMR(SP)                                                                                           \
-    do {                                                                                                               \
-        static std::atomic<uint64_t> done{0};                                                                          \
-        auto kern = mmr_select_kernel<SP>;                                                                             \
-        if (lds > 48 * 1024) e = ensure_dynamic_lds(done, reinterpret_cast<const void*>(kern), 64 * 1024);            \
-        if (e == hipSuccess)                                                                                           \
-            kern<<<nq, 256, lds, s>>>(X, dim, ld, l_lab, l_dist, l_d64, l_cnt, fetch_k, k, lambda, one_minus_lambda,   \
-                                      out_labels, out_dist, out_counts, out_d64, out_rank, out_obj);                   \
-    } while (0)
-    switch (space) {
-        case kSpaceL2: MLVDB_LAUNCH_MMR(kSpaceL2); break;
-        case kSpaceCosine: MLVDB_LAUNCH_MMR(kSpaceCosine); break;
-        default: MLVDB_LAUNCH_MMR(kSpaceIp); break;
-    }
-#undef MLVDB_LAUNCH_MMR
-    return e != hipSuccess ? e : hipGetLastError();
+    return with_space(space, [&](auto sp) {
+        constexpr auto kern = mmr_select_kernel<decltype(sp)::value>;
+        if (hipError_t e = ensure_instance_lds<kern>(lds, 64 * 1024); e != hipSuccess) return e;
+        kern<<<nq, 256, lds, s>>>(X, dim, ld, l_lab, l_dist, l_d64, l_cnt, fetch_k, k, lambda, one_minus_lambda, out_labels,
+                                  out_dist, out_counts, out_d64, out_rank, out_obj);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace mlvdb

@@ -235,21 +235,12 @@ hipError_t launch_mid_score(const FilterArgs& a, const MidArgs& m, hipStream_t s
     int waves = kMidWaves;
     while (waves > 1 && (size_t)waves * m.ld16 * sizeof(double) > 144 * 1024) waves >>= 1;
     const size_t lds = std::max((size_t)waves * m.ld16 * sizeof(double), (size_t)96 * 1024);
-    hipError_t e = hipSuccess;
-#define MLVDB_LAUNCH_MID(SP)                                                                                         \
-    do {                                                                                                             \
-        auto kern = mid_score_flat_kernel<SP>;                                                                       \
-        static std::atomic<uint64_t> configured{0};                                                                  \
-        e = ensure_dynamic_lds(configured, reinterpret_cast<const void*>(kern), 156 * 1024);                         \
-        if (e == hipSuccess) kern<<<kMidGrid, waves * 64, lds, s>>>(a, m);                                            \
-    } while (0)
-    switch (a.space) {
-        case kSpaceL2: MLVDB_LAUNCH_MID(kSpaceL2); break;
-        case kSpaceCosine: MLVDB_LAUNCH_MID(kSpaceCosine); break;
-        default: MLVDB_LAUNCH_MID(kSpaceIp); break;
-    }
-#undef MLVDB_LAUNCH_MID
-    return e != hipSuccess ? e : hipGetLastError();
+    return with_space(a.space, [&](auto sp) {
+        constexpr auto kern = mid_score_flat_kernel<decltype(sp)::value>;
+        if (hipError_t e = ensure_instance_lds<kern>(lds, 156 * 1024); e != hipSuccess) return e;  // (lds >= 96 KiB: always set)
+        kern<<<kMidGrid, waves * 64, lds, s>>>(a, m);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------ block-wide k-th largest key
@@ -476,12 +467,10 @@ __global__ __launch_bounds__(kSelThreads) void bigk_thr_prune_kernel(const Filte
 }
 
 hipError_t launch_bigk_thr_prune(const FilterArgs& a, const MidArgs& m, int32_t k, int32_t forced_cnt, hipStream_t s) {
-    switch (a.space) {
-        case kSpaceL2: bigk_thr_prune_kernel<kSpaceL2><<<a.nq, kSelThreads, 0, s>>>(a, m, k, forced_cnt); break;
-        case kSpaceCosine: bigk_thr_prune_kernel<kSpaceCosine><<<a.nq, kSelThreads, 0, s>>>(a, m, k, forced_cnt); break;
-        default: bigk_thr_prune_kernel<kSpaceIp><<<a.nq, kSelThreads, 0, s>>>(a, m, k, forced_cnt); break;
-    }
-    return hipGetLastError();
+    return with_space(a.space, [&](auto sp) {
+        bigk_thr_prune_kernel<decltype(sp)::value><<<a.nq, kSelThreads, 0, s>>>(a, m, k, forced_cnt);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace mlvdb

@@ -12,6 +12,7 @@
 // the row's own element order alone, and a term another query of the tile brought into U adds fma(w, 0, acc), which leaves
 // acc as it is (acc is never -0: it starts at +0 and x + (-0) == x).
 #include "internal.h"
+#include "panel_walk.h"  // exact_merge_kernel
 #include "sparse_dpp.h"  // the bitmap's size and the 16-lane fold, shared with the gathered scorer (kernels_hybrid.hip)
 
 namespace mlvdb {
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(256) void sparse_scan_kernel(const int64_t* __restr
         }
     }
 
-    // the block's four lists of each query -> partial[((q0 + i) * gridDim.x + block) * k ..], the input of sparse_merge_kernel
+    // the block's four lists of each query -> partial[((q0 + i) * gridDim.x + block) * k ..], the input of exact_merge_kernel<true>
 #pragma unroll
     for (int i = 0; i < QT; ++i) {
         if (i >= tile.nq) break;  // (uniform)
@@ -142,50 +143,6 @@ __global__ __launch_bounds__(256) void sparse_scan_kernel(const int64_t* __restr
     }
 }
 
-// exact_merge_kernel for scores: the partial entries hold (-score, row); the outputs are the scores again (a zero comes out
-// as +0.0), padded with -inf.  One block (4 waves) per query.
-__global__ __launch_bounds__(256) void sparse_merge_kernel(const TopEntry* __restrict__ partial, int32_t nblk, int32_t k,
-                                                           int64_t* __restrict__ out_labels, float* __restrict__ out_score,
-                                                           int32_t* __restrict__ out_counts, double* __restrict__ out_s64) {
-    __shared__ double sd[4][64];
-    __shared__ int32_t sl[4][64];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int q = blockIdx.x;
-    const TopEntry* src = partial + (int64_t)q * nblk * k;
-    const int64_t n = (int64_t)nblk * k;
-    WaveTopK m;
-    m.init();
-    for (int64_t i0 = (int64_t)wave * 64; i0 < n; i0 += 256) {
-        const int64_t i = i0 + lane;
-        TopEntry e;
-        e.d = __builtin_inf();
-        e.l = kNoLabel;
-        if (i < n) e = src[i];
-        m.offer(e.l != kNoLabel, e.d, e.l, k, lane);
-    }
-    sd[wave][lane] = m.d;
-    sl[wave][lane] = m.l;
-    __syncthreads();
-    if (wave != 0) return;
-    WaveTopK f;
-    f.init();
-#pragma unroll
-    for (int w2 = 0; w2 < 4; ++w2) {
-        const double cd = sd[w2][lane];
-        const int32_t cl = sl[w2][lane];
-        f.offer(lane < k && cl != kNoLabel, cd, cl, k, lane);
-    }
-    const bool valid = lane < k && f.l != kNoLabel;
-    if (lane < k) {
-        out_labels[(int64_t)q * k + lane] = valid ? (int64_t)f.l : -1;
-        out_score[(int64_t)q * k + lane] = valid ? (float)(-f.d) : -__builtin_inff();
-        out_s64[(int64_t)q * k + lane] = valid ? -f.d : -__builtin_inf();
-    }
-    const int cnt = __popcll(__ballot(valid));
-    if (lane == 0) out_counts[q] = cnt;
-}
-
 int32_t sparse_scan_blocks(int64_t total, int64_t nq, int32_t k) {
     // <= 64 MiB of partial entries, <= 1024 blocks per tile (four per CU), one block per 16 rows at the most
     const int64_t by_mem = (int64_t)(64u << 20) / (std::max<int64_t>(nq, 1) * k * (int64_t)sizeof(TopEntry));
@@ -206,7 +163,9 @@ hipError_t launch_sparse_scan(const int64_t* slots, const int64_t* pool, const f
 hipError_t launch_sparse_merge(const TopEntry* partial, int32_t nq, int32_t nblk, int32_t k, int64_t* out_labels,
                                float* out_score, int32_t* out_counts, double* out_s64, hipStream_t s) {
     if (nq <= 0) return hipSuccess;
-    sparse_merge_kernel<<<(unsigned)nq, 256, 0, s>>>(partial, nblk, k, out_labels, out_score, out_counts, out_s64);
+    // the exact scan's merge with the signs turned back (panel_walk.h); every query of the pass is selected
+    exact_merge_kernel<true><<<(unsigned)nq, 256, 0, s>>>(partial, nullptr, nullptr, nblk, k, out_labels, out_score, out_counts,
+                                                          out_s64);
     return hipGetLastError();
 }
 

@@ -70,7 +70,7 @@ def oracle_index(attributes, space="l2", **kw) -> Index:
 # ---------------------------------------------------------------- launch geometry of the grouped exact scan
 def scan_geometry(n: int, dim: int, nq_sel: int):
     """(queries per tile, panels per wave step, waves per block, blocks along the corpus) the grouped scan takes for ``n`` rows
-    and ``nq_sel`` selected queries: plan_exact's rule (kernels_exact.hip), which plan_distinct keeps."""
+    and ``nq_sel`` selected queries: plan_exact's rule (kernels_exact.hip) over internal.h's kExactTiles, which plan_distinct keeps."""
     ld = (dim + 15) // 16 * 16
     qt = 8 if nq_sel >= 8 else 4 if nq_sel >= 4 else 2 if nq_sel >= 2 else 1
     while qt > 1 and qt * ld * 8 > 64 * 1024:

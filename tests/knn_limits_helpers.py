@@ -27,7 +27,7 @@ def layout_ld(d: int) -> int:
 
 
 def plan_exact(nrows: int, ld: int, nq: int) -> ExactPlan:
-    """kernels_exact.hip: plan_exact + launch_space -- the query tile (halved while its fp64 image is above 64 KiB), the waves
+    """kernels_exact.hip: plan_exact over internal.h's kExactTiles (with_exact_tile instantiates them) -- the query tile (halved while its fp64 image is above 64 KiB), the waves
     per block and panels per wave of that tile, the blocks per query tile and the dynamic LDS of the launch."""
     qt = 8 if nq >= 8 else 4 if nq >= 4 else 2 if nq >= 2 else 1
     while qt > 1 and qt * ld * 8 > 64 * 1024:

@@ -116,6 +116,40 @@ def test_both_routes_equal_the_oracle_at_every_size(space, d, oversample):
             eng.close()
 
 
+# ---------------------------------------------------------------- a2. the tail of the grouped scan's walk
+# distinct_scan_kernel walks the rows as the exact scan does (plan_exact's tiles): totals at and around one wave step and one
+# block step of every tile (16 x PW x NW = 512 rows for 1, 2 and 4 queries, 256 for 8), as tests/test_gpu_knn_limits.py has them.
+TAIL_COUNTS = [1, 15, 17, 255, 257, 511, 513]
+
+
+@pytest.mark.parametrize("space", ["l2", "cosine", "ip"])
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+def test_grouped_scan_tail_with_the_last_row_tombstoned(n, space):
+    """The list pass off: every query takes the grouped scan.  The last row is a copy of query 0 in a group of its own and
+    tombstoned (where there is more than one row); batches of 1, 2, 3, 4 and 8 queries.  No two live fp64 distances of a
+    query lie within 1e-9 (relative) of each other."""
+    d, k = 20, 3
+    rng = np.random.default_rng(9900 + n)
+    rows = rng.standard_normal((n, d), dtype=np.float32)
+    qs = rng.standard_normal((8, d), dtype=np.float32)
+    groups = (np.arange(n) % 7).astype(np.int64)
+    tomb = np.zeros(n, dtype=bool)
+    if n > 1:
+        rows[n - 1], groups[n - 1], tomb[n - 1] = qs[0], 1000, True
+    dm = exact_scan.exact_distances(qs, rows, space)
+    srt = np.sort(dm[:, ~tomb], axis=1)
+    assert (np.diff(srt, axis=1) > 1e-9 * np.abs(srt[:, 1:])).all(), "precondition: an accidental near-tie -- choose another seed"
+    assert n == 1 or (dm[0, n - 1] < srt[0, 0]), "precondition: the tombstoned row would lead query 0"
+    full = distinct_knn(dm, groups, ~tomb, k)
+    assert n == 1 or not (full[3] == 1000).any(), "precondition: the oracle leaves the tombstoned row's group out"
+    eng = _route(_engine(space, rows, groups, tomb), 0)
+    try:
+        for nq in (1, 2, 3, 4, 8):
+            _check(eng, qs[:nq], k, tuple(a[:nq] for a in full), f"tail_{space}_n{n}_q{nq}")
+    finally:
+        eng.close()
+
+
 # ---------------------------------------------------------------- b. shapes of the group column
 @pytest.mark.parametrize("oversample", ROUTES)
 @pytest.mark.parametrize("n", [3000, 40_000])

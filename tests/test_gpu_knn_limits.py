@@ -129,7 +129,7 @@ ROW_COUNTS = [1, 15, 16, 17, 31, 32, 33, 255, 256, 257, 511, 512, 513, 1100]
 @pytest.mark.parametrize("n", ROW_COUNTS)
 def test_exact_row_counts_around_panels_tasks_and_blocks(n, space):
     """Rows 0 and n - 1 are bit-identical and nearest to query 0: from 255 rows on they belong to different waves, at 1,100 to
-    different blocks.  Batches of 2, 4 and 9 queries: every (PW, NW) pair that launch_space uses."""
+    different blocks.  Batches of 2, 4 and 9 queries: every (PW, NW) pair of kExactTiles."""
     d, k = 24, 5
     rng = np.random.default_rng(7100 + n)
     rows = rng.standard_normal((n, d), dtype=np.float32)
@@ -155,6 +155,40 @@ def test_exact_row_counts_around_panels_tasks_and_blocks(n, space):
             got, st = search(eng, qs[:nq], k)
             assert st["strategy_used"] == 1, st
             assert_knn_matches(got, tuple(w[:nq] for w in want), f"exact-rows/{space}/n{n}/nq{nq}")
+    finally:
+        eng.close()
+
+
+# The tail of the streamed walk (panel_walk.h): totals at and around one wave step (16 x PW rows) and one block step of each
+# tile (16 x PW x NW rows, above), the last row tombstoned -- a case the counts above leave out: their last row is live.
+TAIL_COUNTS = [1, 15, 17, 255, 257, 511, 513]
+
+
+@pytest.mark.parametrize("space", SPACES)
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+def test_exact_walk_tail_with_the_last_row_tombstoned(n, space):
+    """The last row is the nearest of query 0 and tombstoned (where there is more than one row): a walk that scored it as live,
+    or one that stopped a panel short, returns other ids.  Batches of 1, 2, 3, 4 and 8 queries: every tile, and the half-filled
+    tile of 4."""
+    d, k = 20, 3
+    rng = np.random.default_rng(7900 + n)
+    rows = rng.standard_normal((n, d), dtype=np.float32)
+    qs = rng.standard_normal((8, d), dtype=np.float32)
+    deleted = np.zeros(n, dtype=bool)
+    if n > 1:
+        H.plant(rows, qs, space, [(0, n - 1)], rng)
+        H.assert_rank0(qs, rows, space, [(0, n - 1)])
+        deleted[n - 1] = True
+    H.assert_cuts(qs, rows, space, [1, 2, k], deleted, f"tail n{n}")
+    want = H.oracle_knn(qs, rows, k, space, deleted)
+    assert (want[2] == min(k, n - int(deleted.sum()))).all()
+    assert n == 1 or not (want[0] == n - 1).any(), "precondition: the oracle leaves the tombstoned row out"
+    eng = open_engine(rows, space, "exact", deleted)
+    try:
+        for nq in (1, 2, 3, 4, 8):
+            got, st = search(eng, qs[:nq], k)
+            assert st["strategy_used"] == 1, st
+            assert_knn_matches(got, tuple(w[:nq] for w in want), f"exact-tail/{space}/n{n}/nq{nq}")
     finally:
         eng.close()
 

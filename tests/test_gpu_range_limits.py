@@ -296,6 +296,45 @@ def test_pass_and_query_tile_edges(nq, space, strategy):
     assert np.array_equal(got.offsets, np.concatenate([[0], np.cumsum(sizes)]))
 
 
+# ---------------------------------------------------------------- 4b. the tail of the exact range scan's walk
+# exact_range_kernel streams 16 x 2 rows per wave step and 16 x 2 x 8 = 256 per block step (panel_walk.h); the exact kNN
+# tiles' block steps are 256 and 512 rows, and tests/test_gpu_knn_limits.py holds them to the same totals.
+TAIL_COUNTS = [1, 15, 17, 255, 257, 511, 513]
+
+
+@pytest.mark.parametrize("space", ["l2", "cosine", "ip"])
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+def test_exact_range_walk_tail_with_the_last_row_tombstoned(n, space):
+    """The last row is a copy of query 0, well inside the radius, and tombstoned (where there is more than one row); the radius
+    is the median distance, so about half the rows of every total are hits.  Batches of 1, 2, 3, 4 and 8 queries: full and
+    half-filled tiles of four.  No fp64 distance lies within 1e-9 (relative) of the radius or of the next one of its query."""
+    d = 20
+    rng = np.random.default_rng(8800 + n)
+    rows = rng.standard_normal((n, d), dtype=np.float32)
+    qs = rng.standard_normal((8, d), dtype=np.float32)
+    deleted = np.zeros(n, dtype=bool)
+    if n > 1:
+        rows[n - 1] = qs[0]
+        deleted[n - 1] = True
+    dm = exact_scan.exact_distances(qs, rows, space)
+    radius = float(np.float32(np.median(dm[:, ~deleted])))
+    assert n == 1 or dm[0, n - 1] < radius, "precondition: the tombstoned row would be a hit"
+    assert (np.abs(dm - radius) > 1e-9 * np.maximum(np.abs(dm), abs(radius))).all(), "precondition: a distance on the radius"
+    srt = np.sort(dm[:, ~deleted], axis=1)
+    assert (np.diff(srt, axis=1) > 1e-9 * np.abs(srt[:, 1:])).all(), "precondition: an accidental near-tie -- choose another seed"
+    want = exact_scan.range_query(qs, rows, radius, space, deleted=deleted)
+    assert n == 1 or sizes_of(want).sum() >= 2, "precondition: hits"
+    eng = open_engine(rows, space, "exact", deleted)
+    try:
+        for nq in (1, 2, 3, 4, 8):
+            got = eng.range(qs[:nq], radius, 64)
+            assert eng.last_stats()["strategy_used"] == 1
+            assert_range_matches(got, want[:nq], f"tail/exact/{space}/n{n}/nq{nq}")
+            assert np.array_equal(got.offsets, np.concatenate([[0], np.cumsum(sizes_of(want[:nq]))]))
+    finally:
+        eng.close()
+
+
 # ---------------------------------------------------------------- 5. wide rows
 def wide_case(seed, n, d, nq, space):
     rng = np.random.default_rng(seed)

@@ -258,10 +258,14 @@ def test_the_maxsim_kernels_and_header_are_in_the_build_and_the_workspace_key_is
     assert re.search(r"^SRCS = .*\bkernels_maxsim\.hip\b", make, flags=re.M)
     assert "mlvdb_maxsim.h" in make and "group_table.h" in make and "-ffp-contract=off" in make
     kern = (csrc / "kernels_maxsim.hip").read_text()
-    for name in ("maxsim_slot_kernel", "maxsim_scan_kernel", "maxsim_rank_kernel", "accumulate_rows", "finish_distance",
-                 "wave_peel_min", "atomicMin"):
+    assert '#include "panel_walk.h"' in kern  # the scan's walk (the exact scan's arithmetic) lives there
+    walk = (csrc / "panel_walk.h").read_text()
+    for name in ("maxsim_slot_kernel", "maxsim_scan_kernel", "maxsim_rank_kernel", "wave_peel_min", "atomicMin"):
         assert name in kern, name
-    assert "asm" not in kern
+    for name in ("accumulate_rows", "finish_distance"):
+        assert name in kern or name in walk, name
+    assert "panel_walk<" in kern and "accumulate_rows<" in walk and "finish_distance<" in walk
+    assert "asm" not in kern and "asm" not in walk
     internal = (csrc / "internal.h").read_text()
     assert re.search(r'X\(maxsim_ws_mb, "MAXSIM_WS_MB", 1024\)', internal)
     assert '#include "../../include/mlvdb_maxsim.h"' in internal
