@@ -205,6 +205,30 @@ int copy_down(mlvdb_index* h, hipStream_t s, std::initializer_list<Down> outs) {
     return MLVDB_OK;
 }
 
+// A workspace of several fields, stated once: `fields` is a list of c.take<T>(n) calls assigning the field pointers.  It runs
+// over no block to measure, `buf` grows to exactly that many bytes, and it runs again over the block.  The size and the
+// layout cannot disagree, and a field that would not lie aligned is an error before any pointer exists.
+template <class Fields>
+int carve(mlvdb_index* h, DevBuf& buf, Fields&& fields) {
+    Carver measure;
+    fields(measure);
+    if (measure.misaligned) return fail(h, MLVDB_ERR_INTERNAL, "workspace layout: a field does not lie aligned");
+    HIP_TRY(h, buf.ensure(measure.at));
+    Carver c{buf.as<char>()};
+    fields(c);
+    return MLVDB_OK;
+}
+
+#define CARVE(h, buf, ...) do { if (int rc__ = carve(h, buf, __VA_ARGS__)) return rc__; } while (0)
+
+// ... the layout most blocks have (ListBlock): n entries and nq counts.
+int carve_list(mlvdb_index* h, DevBuf& buf, size_t n, size_t nq, ListBlock& l) {
+    return carve(h, buf, [&](Carver& c) { l.take(c, n, nq); });
+}
+
+// Bytes from the field `from` up to the field `to` of one carved block: the length of a memset that clears adjacent fields.
+size_t span_bytes(const void* from, const void* to) { return (size_t)((const char*)to - (const char*)from); }
+
 // ---- tuning state: name table, the one environment read, KEY=VAL parsing
 struct TuningField {
     const char* name;
@@ -1170,6 +1194,76 @@ int guarded(mlvdb_index* h, F&& body) noexcept {
     }
 }
 
+// ... and the entry that works on its handle's device: the guard, then check_handle, then the body.  (The entries that
+// only read or set host state of the handle check it themselves and never call hipSetDevice.)
+constexpr struct OnDevice {} kOnDevice;
+template <class F>
+int guarded(mlvdb_index* h, OnDevice, F&& body) noexcept {
+    return guarded(h, [&]() -> int {
+        if (int rc = check_handle(h)) return rc;
+        return body();
+    });
+}
+
+// ---- the refusals several entries share, each with its one status and text.  Which refusal wins when a call has two
+// faults is behaviour: an entry calls these in its own order, between its own checks, and none of them checks two things.
+int check_nq(mlvdb_index* h, int64_t nq) {
+    return nq < 0 || nq > (1 << 24) ? fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range") : MLVDB_OK;
+}
+int check_k_min(mlvdb_index* h, int32_t k) { return k < 1 ? fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1") : MLVDB_OK; }
+// k <= MLVDB_MAX_TOPK / the 2^31 - 1 rows the pooled-column kernels index, refused under the family's prefix ("distinct: ", ...)
+int check_k_max(mlvdb_index* h, int32_t k, const char* prefix) {
+    return k > MLVDB_MAX_TOPK ? fail(h, MLVDB_ERR_UNSUPPORTED, (std::string(prefix) + "k above MLVDB_MAX_TOPK").c_str()) : MLVDB_OK;
+}
+int check_row_limit(mlvdb_index* h, const char* prefix) {
+    return h->total > INT32_MAX ? fail(h, MLVDB_ERR_UNSUPPORTED, (std::string(prefix) + "more than 2^31 - 1 rows").c_str()) : MLVDB_OK;
+}
+int check_k_max_paged(mlvdb_index* h, int32_t k) {
+    return k > MLVDB_MAX_TOPK_PAGED ? fail(h, MLVDB_ERR_UNSUPPORTED, "k above MLVDB_MAX_TOPK_PAGED") : MLVDB_OK;
+}
+
+// rows [first, first + n) lie inside the index, and a non-empty range has its buffer
+int check_row_range(mlvdb_index* h, int64_t first, int64_t n, bool have_buffer = true) {
+    if (first < 0 || n < 0 || first > h->total || n > h->total - first || (n > 0 && !have_buffer))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    return MLVDB_OK;
+}
+
+// n >= 1 labels of a by-label write: inside [0, total), none twice.
+int labels_check(mlvdb_index* h, const int64_t* labels, int64_t n) {
+    std::vector<int64_t> sorted(labels, labels + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label outside [0, total)");
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a label appears twice");
+    return MLVDB_OK;
+}
+
+// The head of a by-label write: the arguments (have_buffers: the entry's other arrays of n values), *updated zeroed, nothing
+// to do for no label, the labels themselves; then `write`, the entry's remaining checks and its work.
+template <class F>
+int with_labels(mlvdb_index* h, const int64_t* labels, int64_t n, int64_t* updated, bool have_buffers, const char* what, F&& write) {
+    if (!updated || n < 0 || (n > 0 && (!labels || !have_buffers))) return fail(h, MLVDB_ERR_INVALID_ARG, what);
+    *updated = 0;
+    if (n == 0) return MLVDB_OK;
+    if (int rc = labels_check(h, labels, n)) return rc;
+    return write();
+}
+
+// Null-tolerant padding of one output array, and of the outputs most searches share: n entries (label -1, distances
+// sign x inf -- +1 for distances, -1 for scores; dist64 may be null) and nq zeroed counts.
+template <class T, class V>
+void pad(T* out, int64_t n, V value) {
+    if (out) std::fill(out, out + n, (T)value);
+}
+
+void pad_outputs(int64_t* labels, float* dist, double* dist64, int64_t n, int32_t* counts, int64_t nq, float sign = 1.0f) {
+    pad(labels, n, -1);
+    pad(dist, n, sign * __builtin_inff());
+    pad(dist64, n, sign * __builtin_inf());
+    pad(counts, nq, 0);
+}
+
 }  // namespace
 
 // ============================================================================== C ABI
@@ -1271,15 +1365,12 @@ int mlvdb_index_destroy(mlvdb_index* h) {
 }
 
 int mlvdb_index_append_device(mlvdb_index* h, const float* rows_device, int64_t n, int64_t* first_label) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (n < 0 || (n > 0 && !rows_device)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad rows / n");
     if (h->total + n > 0x7fffff00ll) return fail(h, MLVDB_ERR_UNSUPPORTED, "more than 2^31 rows per index");
     if (first_label) *first_label = h->total;
     if (n == 0) return MLVDB_OK;
-    rc = reserve_rows(h, h->total + n);
-    if (rc) return rc;
+    if (int rc = reserve_rows(h, h->total + n)) return rc;
     HIP_TRY(h, launch_scatter_rows(rows_device, h->X, h->total, n, h->dim, h->ld, h->stream));
     HIP_TRY(h, launch_row_norms(h->X, h->rn, h->total, n, h->ld, h->rowerr.as<unsigned int>(), h->stream));
     if (h->Xb) HIP_TRY(h, launch_shadow_rows(h->X, h->Xb, h->total, n, h->ld, h->stream));
@@ -1292,15 +1383,12 @@ int mlvdb_index_append_device(mlvdb_index* h, const float* rows_device, int64_t 
 }
 
 int mlvdb_index_append(mlvdb_index* h, const float* rows, int64_t n, int64_t* first_label) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (n < 0 || (n > 0 && !rows)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad rows / n");
     if (h->total + n > 0x7fffff00ll) return fail(h, MLVDB_ERR_UNSUPPORTED, "more than 2^31 rows per index");
     if (first_label) *first_label = h->total;
     if (n == 0) return MLVDB_OK;
-    rc = reserve_rows(h, h->total + n);
-    if (rc) return rc;
+    if (int rc = reserve_rows(h, h->total + n)) return rc;
     const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(256u << 20) / ((int64_t)h->dim * 4));
     for (int64_t done = 0; done < n; done += chunk_rows) {
         const int64_t m = std::min(chunk_rows, n - done);
@@ -1320,9 +1408,7 @@ int mlvdb_index_append(mlvdb_index* h, const float* rows, int64_t n, int64_t* fi
 }
 
 int mlvdb_index_tombstone(mlvdb_index* h, const int64_t* labels, int64_t n, int64_t* newly_deleted) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (n < 0 || (n > 0 && !labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n");
     if (newly_deleted) *newly_deleted = 0;
     if (n == 0 || h->total == 0) return MLVDB_OK;
@@ -1347,9 +1433,7 @@ int mlvdb_index_tombstone(mlvdb_index* h, const int64_t* labels, int64_t n, int6
 }
 
 int mlvdb_index_compact(mlvdb_index* h, int64_t* old_labels, int64_t capacity, int64_t* live_out) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     const int64_t want = h->total - h->deleted;
     if (capacity < want || (want > 0 && !old_labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "old_labels too small");
     if (live_out) *live_out = want;
@@ -1417,9 +1501,7 @@ int mlvdb_index_counts(const mlvdb_index* h, int64_t* total, int64_t* deleted) {
 }
 
 int mlvdb_index_reset(mlvdb_index* h, int32_t space) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (space > 2) return fail(h, MLVDB_ERR_INVALID_ARG, "space must be < 0 (keep) or a MLVDB_SPACE_* value");
     if (h->capacity > 0) {
         HIP_TRY(h, hipMemsetAsync(h->X, 0, (size_t)h->capacity * h->ld * sizeof(float), h->stream));
@@ -1442,9 +1524,7 @@ int mlvdb_index_reset(mlvdb_index* h, int32_t space) {
 }
 
 int mlvdb_index_get_rows(mlvdb_index* h, int64_t first, int64_t n, float* out_rows) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (first < 0 || n < 0 || first + n > h->total || (n > 0 && !out_rows))
         return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
     const int64_t chunk_rows = std::max<int64_t>(1, (int64_t)(256u << 20) / ((int64_t)h->dim * 4));
@@ -1461,9 +1541,7 @@ int mlvdb_index_get_rows(mlvdb_index* h, int64_t first, int64_t n, float* out_ro
 }
 
 int mlvdb_index_get_rows_at(mlvdb_index* h, const int64_t* labels, int64_t n, float* out_rows) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (n < 0 || (n > 0 && (!labels || !out_rows))) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n / out_rows");
     for (int64_t i = 0; i < n; ++i)
         if (labels[i] < 0 || labels[i] >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label out of range");
@@ -1505,9 +1583,9 @@ static int search_device_impl(mlvdb_index* h, const float* queries_device, int64
     int rc = check_handle(h);
     if (rc) return rc;
     h->deferred = false;
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
-    if (k > MLVDB_MAX_TOPK_PAGED) return fail(h, MLVDB_ERR_UNSUPPORTED, "k above MLVDB_MAX_TOPK_PAGED");
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max_paged(h, k)) return rc;
     if (nq == 0) return MLVDB_OK;
     if (!queries_device || !out_labels_device || !out_dist_device || !out_counts_device)
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
@@ -1580,9 +1658,9 @@ static int search_device_impl(mlvdb_index* h, const float* queries_device, int64
 namespace {
 int search_host(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int64_t* out_labels, float* out_dist,
                 int32_t* out_counts, double* out_dist64) {
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
-    if (k > MLVDB_MAX_TOPK_PAGED) return fail(h, MLVDB_ERR_UNSUPPORTED, "k above MLVDB_MAX_TOPK_PAGED");
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max_paged(h, k)) return rc;
     if (nq == 0) return MLVDB_OK;
     if (!queries || !out_labels || !out_dist || !out_counts) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     // queries: user memory -> pinned staging -> device (one DMA); outputs: ONE device buffer [d64 | labels | dist | counts]
@@ -1700,9 +1778,7 @@ int with_row_mask(mlvdb_index* h, int64_t nq, F&& call) {
 
 int mlvdb_search_batch_ex(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const uint8_t* row_mask,
                           int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (!row_mask || h->total == 0) return search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64);
     HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
     HIP_TRY(h, hipMemcpyAsync(h->row_mask.p, row_mask, (size_t)h->total, hipMemcpyHostToDevice, h->stream));
@@ -1872,7 +1948,7 @@ static int range_batch_impl(mlvdb_index* h, const float* queries, int64_t nq, fl
     int rc = check_handle(h);
     if (rc) return rc;
     if (packed && !out_offsets) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (int rc = check_nq(h, nq)) return rc;
     if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
     if (out_offsets && total_capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "total_capacity must be >= 0");
     if (nq == 0) {
@@ -1968,9 +2044,7 @@ int mlvdb_range_batch_packed(mlvdb_index* h, const float* queries, int64_t nq, f
 
 int mlvdb_pair_distances(mlvdb_index* h, const float* queries, int64_t nq, const int64_t* labels, int64_t m,
                          double* out_dist64, float* out_dist) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (nq < 0 || nq > (1 << 24) || m < 0 || m > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq / m out of range");
     if (nq == 0 || m == 0) return MLVDB_OK;
     if (!queries || !labels || !out_dist64) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
@@ -2049,9 +2123,7 @@ int mlvdb_index_set_profiling(mlvdb_index* h, int32_t enabled) {
 }
 
 int mlvdb_index_last_stats(mlvdb_index* h, mlvdb_stats* out) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (!out) return fail(h, MLVDB_ERR_INVALID_ARG, "out is null");
     if (h->counters_pending) {
         unsigned long long c[2] = {0, 0};
@@ -2112,6 +2184,19 @@ int value_check(mlvdb_index* h, int32_t attr) {
     if (h->attr_type[attr] == MLVDB_ATTR_GEO)
         return fail(h, MLVDB_ERR_INVALID_ARG, "a geo column: this entry needs an int64 or float64 value column (see mlvdb_geo.h)");
     return MLVDB_OK;
+}
+
+// ... and for those that need a defined column of one type (`what` says so in the entry's words): a pooled one, or an int64
+// one to group or count by.
+int typed_attr_check(mlvdb_index* h, int32_t attr, int32_t type, const char* what) {
+    if (int rc = attr_check(h, attr)) return rc;
+    return h->attr_type[attr] != type ? fail(h, MLVDB_ERR_INVALID_ARG, what) : MLVDB_OK;
+}
+
+int int64_attr_check(mlvdb_index* h, int32_t attr, const char* what) {
+    if (int rc = attr_check(h, attr)) return rc;
+    if (int rc = value_check(h, attr)) return rc;
+    return h->attr_type[attr] != MLVDB_ATTR_INT64 ? fail(h, MLVDB_ERR_INVALID_ARG, what) : MLVDB_OK;
 }
 
 // Values about to be written to a column: on a geo column every non-absent one must be a point inside the ranges.
@@ -2231,11 +2316,17 @@ int where_prepare(mlvdb_index* h, const mlvdb_where* w) {
 // The validated program (h->where_ops) and its set table -> h->where_prog on the device, enqueued on h->stream.
 int where_upload(mlvdb_index* h, const mlvdb_where* w, const int64_t** set_d) {
     hipStream_t s = h->stream;
-    const size_t pbytes = h->where_ops.size() * sizeof(WhereOp), sbytes = (size_t)w->n_set * sizeof(int64_t);
-    HIP_TRY(h, h->where_prog.ensure(pbytes + sbytes + sizeof(int64_t)));
-    HIP_TRY(h, hipMemcpyAsync(h->where_prog.p, h->where_ops.data(), pbytes, hipMemcpyHostToDevice, s));
-    *set_d = reinterpret_cast<const int64_t*>(h->where_prog.as<char>() + pbytes);
-    if (sbytes) HIP_TRY(h, hipMemcpyAsync(h->where_prog.as<char>() + pbytes, w->set, sbytes, hipMemcpyHostToDevice, s));
+    const size_t nops = h->where_ops.size(), nset = (size_t)w->n_set;
+    WhereOp* ops_d = nullptr;
+    int64_t* sets_d = nullptr;
+    CARVE(h, h->where_prog, [&](Carver& c) {
+        ops_d = c.take<WhereOp>(nops);
+        sets_d = c.take<int64_t>(nset);
+        c.take<char>(sizeof(int64_t));  // slack behind the set table
+    });
+    HIP_TRY(h, hipMemcpyAsync(ops_d, h->where_ops.data(), nops * sizeof(WhereOp), hipMemcpyHostToDevice, s));
+    *set_d = sets_d;
+    if (nset) HIP_TRY(h, hipMemcpyAsync(sets_d, w->set, nset * sizeof(int64_t), hipMemcpyHostToDevice, s));
     return MLVDB_OK;
 }
 
@@ -2260,12 +2351,34 @@ int where_run(mlvdb_index* h, const mlvdb_where* w, int64_t* matches) {
     }
     return MLVDB_OK;
 }
+
+// The `matches` rows of h->row_mask as labels in ascending order -> h->labels_in (enqueued): the compaction map of the masked
+// norms (NaN = tombstoned or no match).
+int mask_labels(mlvdb_index* h, int64_t matches) {
+    hipStream_t s = h->stream;
+    const int64_t nblocks = (h->total + 1023) / 1024;
+    HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
+    HIP_TRY(h, h->partial.ensure((size_t)nblocks * sizeof(uint32_t) + 64));
+    HIP_TRY(h, h->labels_in.ensure((size_t)matches * sizeof(int32_t)));
+    HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, s));
+    HIP_TRY(h, launch_compact_map(h->rn_masked.as<float>(), h->total, h->partial.as<uint32_t>(),
+                                  h->where_cnt.as<unsigned long long>(), h->labels_in.as<int32_t>(), s));
+    return MLVDB_OK;
+}
+
+// An optional program evaluated into h->row_mask for the kernels that read it at one byte per row (no wait, no copy):
+// *mask is that mask, or nullptr without a program.  Requires h->total > 0.
+int where_mask(mlvdb_index* h, const mlvdb_where* where, const uint8_t** mask) {
+    *mask = nullptr;
+    if (!where) return MLVDB_OK;
+    if (int rc = where_run(h, where, nullptr)) return rc;
+    *mask = h->row_mask.as<uint8_t>();
+    return MLVDB_OK;
+}
 }  // namespace
 
 int mlvdb_attr_define(mlvdb_index* h, int32_t attr, int32_t type) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (attr < 0 || attr >= MLVDB_MAX_ATTRS) return fail(h, MLVDB_ERR_INVALID_ARG, "attribute index out of range");
     if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64 && type != MLVDB_ATTR_GEO && !pooled(type))
         return fail(h, MLVDB_ERR_INVALID_ARG, "unknown attribute type");
@@ -2288,15 +2401,12 @@ int mlvdb_attr_define(mlvdb_index* h, int32_t attr, int32_t type) {
 }
 
 int mlvdb_attr_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const void* values) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = scalar_check(h, attr))) return rc;
-    if (first < 0 || n < 0 || first > h->total || n > h->total - first || (n > 0 && !values))
-        return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = attr_check(h, attr)) return rc;
+    if (int rc = scalar_check(h, attr)) return rc;
+    if (int rc = check_row_range(h, first, n, values != nullptr)) return rc;
     if (n == 0) return MLVDB_OK;
-    if ((rc = geo_values_check(h, attr, values, n))) return rc;
+    if (int rc = geo_values_check(h, attr, values, n)) return rc;
     // (the sentinels are values like any other here: INT64_MIN / NaN written to a row make it absent)
     HIP_TRY(h, hipMemcpyAsync(h->attr_col[attr] + first, values, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2305,13 +2415,10 @@ int mlvdb_attr_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const
 }
 
 int mlvdb_attr_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, void* out_values) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = scalar_check(h, attr))) return rc;
-    if (first < 0 || n < 0 || first > h->total || n > h->total - first || (n > 0 && !out_values))
-        return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = attr_check(h, attr)) return rc;
+    if (int rc = scalar_check(h, attr)) return rc;
+    if (int rc = check_row_range(h, first, n, out_values != nullptr)) return rc;
     if (n == 0) return MLVDB_OK;
     HIP_TRY(h, hipMemcpyAsync(out_values, h->attr_col[attr] + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2320,30 +2427,19 @@ int mlvdb_attr_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, void*
 }
 
 int mlvdb_where_count(mlvdb_index* h, const mlvdb_where* where, int64_t* matches) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (!matches) return fail(h, MLVDB_ERR_INVALID_ARG, "matches is null");
     return where_run(h, where, matches);
     });
 }
 
 int mlvdb_where_labels(mlvdb_index* h, const mlvdb_where* where, int64_t* out_labels, int64_t capacity, int64_t* matches) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (!matches || capacity < 0 || (capacity > 0 && !out_labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
-    rc = where_run(h, where, matches);
+    const int rc = where_run(h, where, matches);
     if (rc || *matches == 0 || capacity == 0) return rc;
-    // the matching rows' labels in ascending order: the compaction map of the masked norms (NaN = tombstoned or no match)
     hipStream_t s = h->stream;
-    const int64_t nblocks = (h->total + 1023) / 1024;
-    HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
-    HIP_TRY(h, h->partial.ensure((size_t)nblocks * sizeof(uint32_t) + 64));
-    HIP_TRY(h, h->labels_in.ensure((size_t)*matches * sizeof(int32_t)));
-    HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, s));
-    HIP_TRY(h, launch_compact_map(h->rn_masked.as<float>(), h->total, h->partial.as<uint32_t>(),
-                                  h->where_cnt.as<unsigned long long>(), h->labels_in.as<int32_t>(), s));
+    if (int rc2 = mask_labels(h, *matches)) return rc2;
     const int64_t n = std::min(capacity, *matches);
     std::vector<int32_t> host((size_t)n);
     HIP_TRY(h, hipMemcpyAsync(host.data(), h->labels_in.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -2355,11 +2451,8 @@ int mlvdb_where_labels(mlvdb_index* h, const mlvdb_where* where, int64_t* out_la
 
 int mlvdb_search_batch_where(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const mlvdb_where* where,
                              int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_dist64) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    rc = where_run(h, where, nullptr);  // the mask stays on the device: no wait, no copy
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = where_run(h, where, nullptr)) return rc;  // the mask stays on the device: no wait, no copy
     if (h->total == 0) return search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64);
     return with_row_mask(h, nq, [&]() { return search_host(h, queries, nq, k, out_labels, out_dist, out_counts, out_dist64); });
     });
@@ -2368,11 +2461,8 @@ int mlvdb_search_batch_where(mlvdb_index* h, const float* queries, int64_t nq, i
 int mlvdb_range_batch_packed_where(mlvdb_index* h, const float* queries, int64_t nq, float radius, int64_t capacity,
                                    int64_t total_capacity, const mlvdb_where* where, int64_t* out_labels, float* out_dist,
                                    int64_t* out_offsets, int64_t* out_counts) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    rc = where_run(h, where, nullptr);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = where_run(h, where, nullptr)) return rc;
     auto call = [&]() {
         return range_batch_impl(h, queries, nq, radius, capacity, out_labels, out_dist, out_counts, out_offsets, total_capacity, true);
     };
@@ -2393,16 +2483,6 @@ int with_where(mlvdb_index* h, const mlvdb_where* where, int64_t nq, F&& call) {
     if (rc || nq == 0) return rc;
     if (h->total == 0) return call();
     return with_row_mask(h, nq, call);
-}
-
-// Padding: n entries (label -1, distances inf; dist64 may be null) and nq zeroed counts.
-void pad_outputs(int64_t* labels, float* dist, double* dist64, int64_t n, int32_t* counts, int64_t nq) {
-    for (int64_t i = 0; i < n; ++i) {
-        labels[i] = -1;
-        dist[i] = __builtin_inff();
-        if (dist64) dist64[i] = __builtin_inf();
-    }
-    for (int64_t i = 0; i < nq; ++i) counts[i] = 0;
 }
 
 // ---- per-query filters (mlvdb_where_each.h)
@@ -2477,29 +2557,44 @@ EachSegs each_segments(int64_t total) {
     return sg;
 }
 
+// h->each_tot: the programs' match totals and the bases of their label lists (the gather stage's), one of each per program
+struct EachTotals {
+    int64_t *total = nullptr, *base = nullptr;
+    void take(Carver& c) {
+        total = c.take<int64_t>(kWhereEachMaxPrograms);
+        base = c.take<int64_t>(kWhereEachMaxPrograms);
+    }
+};
+
 // Every program on every row in one pass: h->each_bits, the per-segment counts (exclusive offsets afterwards) and
 // matches[p] on the host (the call's one synchronisation).  Requires h->total > 0 and at least one program.
 int where_each_eval(mlvdb_index* h, const EachPrograms& pk, const EachSegs& sg, int64_t* matches) {
     hipStream_t s = h->stream;
     const int32_t n = (int32_t)pk.off.size() - 1;
-    const size_t obytes = pk.ops.size() * sizeof(WhereOp), fbytes = pk.off.size() * sizeof(int32_t);
-    const size_t sbytes = pk.set.size() * sizeof(int64_t), cbytes = pk.cols.size() * sizeof(void*);
-    const size_t foff = obytes, soff = (foff + fbytes + 15) / 16 * 16, coff = soff + sbytes;
-    HIP_TRY(h, h->each_prog.ensure(coff + cbytes + 16));
+    WhereOp* ops_d = nullptr;
+    int32_t* off_d = nullptr;
+    int64_t* set_d = nullptr;
+    const int64_t** cols_d = nullptr;
+    CARVE(h, h->each_prog, [&](Carver& c) {
+        ops_d = c.take<WhereOp>(pk.ops.size());
+        off_d = c.take<int32_t>(pk.off.size());
+        c.pad_to(16);
+        set_d = c.take<int64_t>(pk.set.size());
+        cols_d = c.take<const int64_t*>(pk.cols.size());
+        c.take<char>(16);  // slack
+    });
     HIP_TRY(h, h->each_bits.ensure((size_t)h->total * sizeof(unsigned long long)));
     HIP_TRY(h, h->each_seg.ensure((size_t)n * sg.nseg * sizeof(uint32_t)));
-    HIP_TRY(h, h->each_tot.ensure((size_t)(2 * kWhereEachMaxPrograms) * sizeof(int64_t)));  // [totals | label bases]
-    char* dp = h->each_prog.as<char>();
-    HIP_TRY(h, hipMemcpyAsync(dp, pk.ops.data(), obytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dp + foff, pk.off.data(), fbytes, hipMemcpyHostToDevice, s));
-    if (sbytes) HIP_TRY(h, hipMemcpyAsync(dp + soff, pk.set.data(), sbytes, hipMemcpyHostToDevice, s));
-    if (cbytes) HIP_TRY(h, hipMemcpyAsync(dp + coff, pk.cols.data(), cbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_where_each_eval(reinterpret_cast<const WhereOp*>(dp), reinterpret_cast<const int32_t*>(dp + foff), n,
-                                      (int32_t)pk.ops.size(), reinterpret_cast<const int64_t*>(dp + soff),
-                                      reinterpret_cast<const int64_t* const*>(dp + coff), (int32_t)pk.cols.size(), h->rn, h->total,
+    EachTotals tot;
+    if (int rc = carve(h, h->each_tot, [&](Carver& c) { tot.take(c); })) return rc;
+    HIP_TRY(h, hipMemcpyAsync(ops_d, pk.ops.data(), pk.ops.size() * sizeof(WhereOp), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(off_d, pk.off.data(), pk.off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (!pk.set.empty()) HIP_TRY(h, hipMemcpyAsync(set_d, pk.set.data(), pk.set.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (!pk.cols.empty()) HIP_TRY(h, hipMemcpyAsync(cols_d, pk.cols.data(), pk.cols.size() * sizeof(void*), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_where_each_eval(ops_d, off_d, n, (int32_t)pk.ops.size(), set_d, cols_d, (int32_t)pk.cols.size(), h->rn, h->total,
                                       sg.seg_rows, sg.nseg, h->each_bits.as<unsigned long long>(), h->each_seg.as<uint32_t>(), s));
-    HIP_TRY(h, launch_where_each_scan(h->each_seg.as<uint32_t>(), n, sg.nseg, h->each_tot.as<int64_t>(), s));
-    HIP_TRY(h, hipMemcpyAsync(matches, h->each_tot.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, launch_where_each_scan(h->each_seg.as<uint32_t>(), n, sg.nseg, tot.total, s));
+    HIP_TRY(h, hipMemcpyAsync(matches, tot.total, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
     return MLVDB_OK;
 }
@@ -2638,7 +2733,10 @@ int gather_stage(mlvdb_index* h, const float* queries, int32_t qt, size_t group,
     }
     st.ng = (int32_t)st.sel.size();
     HIP_TRY(h, h->each_lab.ensure((size_t)nlab * sizeof(int32_t)));
-    int64_t* base_d = h->each_tot.as<int64_t>() + kWhereEachMaxPrograms;  // (each_tot: [totals | label bases])
+    EachTotals tot;  // (where_each_eval sized the block: this only finds the bases in it)
+    Carver in_tot{h->each_tot.as<char>()};
+    tot.take(in_tot);
+    int64_t* base_d = tot.base;
     HIP_TRY(h, hipMemcpyAsync(base_d, st.base.data(), st.base.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(h, launch_where_each_scatter(h->each_bits.as<unsigned long long>(), h->total, sg.seg_rows, sg.nseg, n_programs,
                                          h->each_seg.as<uint32_t>(), gmask, base_d, h->each_lab.as<int32_t>(), s));
@@ -2670,9 +2768,11 @@ int gather_programs(mlvdb_index* h, const float* queries, int32_t k, int32_t qt,
                                    h->partial.as<TopEntry>(), s));
     // outputs [d64 | labels | dist | counts] in the sorted order, one copy back
     const size_t nk = (size_t)ng * k;
-    std::vector<char> host(ListBlock::bytes(nk, (size_t)ng));
-    HIP_TRY(h, h->each_out.ensure(host.size()));
-    const ListBlock o(h->each_out.p, nk, (size_t)ng), ho(host.data(), nk, (size_t)ng);
+    ListBlock o, ho;
+    if (int rc = carve_list(h, h->each_out, nk, (size_t)ng, o)) return rc;
+    std::vector<char> host(span_bytes(o.d64, o.cnt + ng));
+    Carver hc{host.data()};
+    ho.take(hc, nk, (size_t)ng);
     HIP_TRY(h, launch_exact_merge(h->partial.as<TopEntry>(), ng, nullptr, nullptr, (int32_t)nchunk, k, o.lab, o.dist, o.cnt,
                                   o.d64, s));
     HIP_TRY(h, hipMemcpyAsync(host.data(), h->each_out.p, host.size(), hipMemcpyDeviceToHost, s));
@@ -2684,11 +2784,9 @@ int gather_programs(mlvdb_index* h, const float* queries, int32_t k, int32_t qt,
 }  // extern "C++"
 
 int mlvdb_where_count_each(mlvdb_index* h, const mlvdb_where* programs, int32_t n_programs, int64_t* out_matches) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     EachPrograms pk;
-    if ((rc = where_each_pack(h, programs, n_programs, pk))) return rc;
+    if (int rc = where_each_pack(h, programs, n_programs, pk)) return rc;
     if (n_programs > 0 && !out_matches) return fail(h, MLVDB_ERR_INVALID_ARG, "out_matches is null");
     for (int32_t p = 0; p < n_programs; ++p) out_matches[p] = 0;
     if (n_programs == 0 || h->total == 0) return MLVDB_OK;
@@ -2699,24 +2797,21 @@ int mlvdb_where_count_each(mlvdb_index* h, const mlvdb_where* programs, int32_t 
 int mlvdb_search_batch_where_each(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const mlvdb_where* programs,
                                   int32_t n_programs, const int32_t* program_of_query, int64_t* out_labels, float* out_dist,
                                   int32_t* out_counts, double* out_dist64, int32_t* out_routes) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
-    if (k > MLVDB_MAX_TOPK_PAGED) return fail(h, MLVDB_ERR_UNSUPPORTED, "k above MLVDB_MAX_TOPK_PAGED");
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max_paged(h, k)) return rc;
     EachPrograms pk;
-    if ((rc = where_each_pack(h, programs, n_programs, pk))) return rc;
+    if (int rc = where_each_pack(h, programs, n_programs, pk)) return rc;
     if (nq > 0 && (!queries || !program_of_query || !out_labels || !out_dist || !out_counts))
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     EachSplit split;
-    if ((rc = where_each_split(h, program_of_query, nq, n_programs, split))) return rc;
+    if (int rc = where_each_split(h, program_of_query, nq, n_programs, split)) return rc;
     std::vector<int64_t> matches((size_t)n_programs, 0);
     const EachSegs sg = each_segments(h->total);
     if (split.any && h->total > 0) {
-        rc = where_each_eval(h, pk, sg, matches.data());
-        if (rc) return rc;
+        if (int rc = where_each_eval(h, pk, sg, matches.data())) return rc;
     }
     const int32_t qt = gather_qt(h);
     const EachRoutes rt = where_each_routes(h, split.qof, matches, qt, k <= MLVDB_MAX_TOPK);
@@ -2729,15 +2824,15 @@ int mlvdb_search_batch_where_each(mlvdb_index* h, const float* queries, int64_t 
                         out_counts + q, 1);
     }
     if (!rt.gp.empty()) {
-        rc = gather_programs(h, queries, k, qt, sg, n_programs, rt.gp, split.qof, matches.data(), out_labels, out_dist, out_counts,
-                             out_dist64);
-        if (rc) return rc;
+        if (int rc = gather_programs(h, queries, k, qt, sg, n_programs, rt.gp, split.qof, matches.data(), out_labels, out_dist,
+                                     out_counts, out_dist64))
+            return rc;
     }
     // SCAN: the program's row mask out of its bit, then exactly the masked call of mlvdb_search_batch_where
     for (int32_t p : rt.sp) {
-        if ((rc = each_row_mask(h, p))) return rc;
-        rc = search_rows(h, queries, split.qof[(size_t)p], k, true, out_labels, out_dist, out_counts, out_dist64);
-        if (rc) return rc;
+        if (int rc = each_row_mask(h, p)) return rc;
+        if (int rc = search_rows(h, queries, split.qof[(size_t)p], k, true, out_labels, out_dist, out_counts, out_dist64))
+            return rc;
     }
     if (!split.plain.empty()) return search_rows(h, queries, split.plain, k, false, out_labels, out_dist, out_counts, out_dist64);
     return MLVDB_OK;
@@ -2783,13 +2878,11 @@ int range_rows(mlvdb_index* h, const float* queries, const std::vector<int32_t>&
         int rc = begin_call(h, s);
         if (rc) return rc;
         std::vector<int64_t> counts, offsets;
-        rc = range_ranked(h, s, q.data(), m, radius, cap_eff, counts, offsets);
-        if (rc) return rc;
+        if (int rc = range_ranked(h, s, q.data(), m, radius, cap_eff, counts, offsets)) return rc;
         const int64_t* pl = nullptr;
         const float* pd = nullptr;
         if (offsets[(size_t)m] > 0) {
-            rc = pack_range_hits(h, s, m, cap_eff, offsets, nullptr, nullptr, &pl, &pd);
-            if (rc) return rc;
+            if (int rc = pack_range_hits(h, s, m, cap_eff, offsets, nullptr, nullptr, &pl, &pd)) return rc;
         }
         take_hits(parts, sel, counts, offsets, pl, pd);
         return end_call(h, s);
@@ -2876,20 +2969,18 @@ int mlvdb_range_batch_packed_where_each(mlvdb_index* h, const float* queries, in
                                         int64_t total_capacity, const mlvdb_where* programs, int32_t n_programs,
                                         const int32_t* program_of_query, int64_t* out_labels, float* out_dist,
                                         int64_t* out_offsets, int64_t* out_counts, int32_t* out_routes) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched: the range arguments as range_batch_impl checks them
     if (!out_offsets) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
+    if (int rc = check_nq(h, nq)) return rc;
     if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
     if (total_capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "total_capacity must be >= 0");
     EachPrograms pk;
-    if ((rc = where_each_pack(h, programs, n_programs, pk))) return rc;
+    if (int rc = where_each_pack(h, programs, n_programs, pk)) return rc;
     if (nq > 0 && (!queries || !program_of_query || !out_counts || ((!out_labels || !out_dist) && total_capacity > 0)))
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     EachSplit split;
-    if ((rc = where_each_split(h, program_of_query, nq, n_programs, split))) return rc;
+    if (int rc = where_each_split(h, program_of_query, nq, n_programs, split)) return rc;
     EachRoutes rt;
     rt.routes.assign((size_t)n_programs, MLVDB_WHERE_ROUTE_NONE);
     RangeParts parts;
@@ -2901,28 +2992,26 @@ int mlvdb_range_batch_packed_where_each(mlvdb_index* h, const float* queries, in
         std::vector<int64_t> matches((size_t)n_programs, 0);
         const EachSegs sg = each_segments(h->total);
         if (split.any) {
-            rc = where_each_eval(h, pk, sg, matches.data());
-            if (rc) return rc;
+            if (int rc = where_each_eval(h, pk, sg, matches.data())) return rc;
         }
         const int32_t qt = gather_qt(h);
         rt = where_each_routes(h, split.qof, matches, qt, true);  // (a range call has no k to bound)
         // GATHER; the queries whose hits its lists could not hold join the SCAN route of their program
         std::vector<std::vector<int32_t>> redo((size_t)n_programs);
         if (!rt.gp.empty()) {
-            rc = gather_range_programs(h, queries, radius, cap_eff, qt, sg, n_programs, rt.gp, split.qof, matches.data(), parts, redo);
-            if (rc) return rc;
+            if (int rc = gather_range_programs(h, queries, radius, cap_eff, qt, sg, n_programs, rt.gp, split.qof, matches.data(), parts,
+                                               redo))
+                return rc;
         }
         // SCAN: the program's row mask out of its bit, then exactly the masked passes of mlvdb_range_batch_packed_where
         for (int32_t p = 0; p < n_programs; ++p) {
             const std::vector<int32_t>& qs = rt.routes[(size_t)p] == MLVDB_WHERE_ROUTE_SCAN ? split.qof[(size_t)p] : redo[(size_t)p];
             if (qs.empty()) continue;
-            if ((rc = each_row_mask(h, p))) return rc;
-            rc = range_rows(h, queries, qs, radius, cap_eff, true, parts);
-            if (rc) return rc;
+            if (int rc = each_row_mask(h, p)) return rc;
+            if (int rc = range_rows(h, queries, qs, radius, cap_eff, true, parts)) return rc;
         }
         if (!split.plain.empty()) {
-            rc = range_rows(h, queries, split.plain, radius, cap_eff, false, parts);
-            if (rc) return rc;
+            if (int rc = range_rows(h, queries, split.plain, radius, cap_eff, false, parts)) return rc;
         }
     }
     if (out_routes) std::copy(rt.routes.begin(), rt.routes.end(), out_routes);
@@ -2958,13 +3047,20 @@ namespace {
 // ---- distinct-by-attribute kNN (mlvdb_distinct.h)
 constexpr int64_t kDistinctChunk = 1024;  // queries per round of list pass + pick + grouped scan (bounds the workspaces)
 
-// Where a chunk's outputs lie in h->dist_out: [d64 | groups | labels | dist | counts]
+// Where a chunk's outputs lie in h->dist_out: n queries of k entries each
 struct DistinctOut {
-    double* d64;
-    int64_t* grp;
-    int64_t* lab;
-    float* dist;
-    int32_t* cnt;
+    double* d64 = nullptr;
+    int64_t* grp = nullptr;
+    int64_t* lab = nullptr;
+    float* dist = nullptr;
+    int32_t* cnt = nullptr;
+    void take(Carver& c, size_t nk, size_t n) {
+        d64 = c.take<double>(nk);
+        grp = c.take<int64_t>(nk);
+        lab = c.take<int64_t>(nk);
+        dist = c.take<float>(nk);
+        cnt = c.take<int32_t>(n);
+    }
 };
 
 // L of the list pass: k <= 64 costs the filter path what k = 64 does, hence the floor; 0: no list pass
@@ -2981,29 +3077,24 @@ int distinct_chunk(mlvdb_index* h, const float* queries, int32_t n, int32_t k, i
     hipStream_t s = h->stream;
     const size_t nk = (size_t)n * k;
     HIP_TRY(h, h->dist_q.ensure((size_t)n * h->dim * sizeof(float)));
-    HIP_TRY(h, h->dist_out.ensure(nk * (2 * sizeof(double) + sizeof(int64_t) + sizeof(float)) + (size_t)n * sizeof(int32_t)));
-    HIP_TRY(h, h->dist_sel.ensure((size_t)(n + 1) * sizeof(int32_t)));
+    if (int rc = carve(h, h->dist_out, [&](Carver& c) { o.take(c, nk, (size_t)n); })) return rc;
+    int32_t *nflag_d = nullptr, *qsel_d = nullptr;  // the flagged queries and their counter
+    CARVE(h, h->dist_sel, [&](Carver& c) {
+        nflag_d = c.take<int32_t>(1);
+        qsel_d = c.take<int32_t>((size_t)n);
+    });
     float* dq = h->dist_q.as<float>();
-    Carver out{h->dist_out.as<char>()};
-    double* o_d64 = out.take<double>(nk);
-    int64_t* o_grp = out.take<int64_t>(nk);
-    int64_t* o_lab = out.take<int64_t>(nk);
-    float* o_dist = out.take<float>(nk);
-    int32_t* o_cnt = out.take<int32_t>((size_t)n);
-    o = DistinctOut{o_d64, o_grp, o_lab, o_dist, o_cnt};
-    int32_t* nflag_d = h->dist_sel.as<int32_t>();  // [counter | flagged queries]
-    int32_t* qsel_d = nflag_d + 1;
     HIP_TRY(h, hipMemcpyAsync(dq, queries, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
     int32_t nsel = n;               // queries of the chunk the grouped scan serves
     const int32_t* qsel = nullptr;  // ... all of them without a list pass
     if (L > 0) {
         const size_t nl = (size_t)n * L;
-        HIP_TRY(h, h->dist_list.ensure(ListBlock::bytes(nl, (size_t)n)));
-        const ListBlock l(h->dist_list.p, nl, (size_t)n);
+        ListBlock l;
+        if (int rc = carve_list(h, h->dist_list, nl, (size_t)n, l)) return rc;
         if (int rc = search_device_impl(h, dq, n, L, l.lab, l.dist, l.cnt, l.d64, s, false)) return rc;
         HIP_TRY(h, hipMemsetAsync(nflag_d, 0, sizeof(int32_t), s));
-        HIP_TRY(h, launch_distinct_pick(l.lab, l.d64, l.cnt, n, L, group, k, k_eff, qsel_d, nflag_d, o_lab, o_dist, o_cnt,
-                                        o_d64, o_grp, s));
+        HIP_TRY(h, launch_distinct_pick(l.lab, l.d64, l.cnt, n, L, group, k, k_eff, qsel_d, nflag_d, o.lab, o.dist, o.cnt,
+                                        o.d64, o.grp, s));
         if (int rc = copy_down(h, s, {{&nsel, 0, nflag_d, 1}})) return rc;
         qsel = qsel_d;
         h->host_fallbacks += nsel;
@@ -3029,8 +3120,8 @@ int distinct_chunk(mlvdb_index* h, const float* queries, int32_t n, int32_t k, i
         a.k = k;
         a.partial = h->partial.as<DistinctEntry>();
         if (int rc = scan_step(h, s, h->total * plan.nqtiles, [&] { return launch_distinct_scan(a, plan, s); })) return rc;
-        HIP_TRY(h, launch_distinct_merge(a.partial, nsel, nullptr, qsel, plan.nblk, k, k_eff, o_lab, o_dist, o_cnt, o_d64,
-                                         o_grp, s));
+        HIP_TRY(h, launch_distinct_merge(a.partial, nsel, nullptr, qsel, plan.nblk, k, k_eff, o.lab, o.dist, o.cnt, o.d64,
+                                         o.grp, s));
         h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
     }
     return MLVDB_OK;
@@ -3044,7 +3135,7 @@ int distinct_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, i
     const int32_t k_eff = max_groups > 0 ? (int32_t)std::min<int64_t>(k, max_groups) : k;
     if (h->total == 0 || h->total == h->deleted) {
         pad_outputs(out_labels, out_dist, out_dist64, nq * k, out_counts, nq);
-        if (out_groups) std::fill(out_groups, out_groups + nq * k, INT64_MIN);
+        pad(out_groups, nq * k, INT64_MIN);
         return MLVDB_OK;
     }
     const int64_t* group = h->attr_col[attr];
@@ -3067,16 +3158,12 @@ int distinct_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, i
 int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t attr, int64_t max_groups,
                                 const mlvdb_where* where, int64_t* out_labels, float* out_dist, int32_t* out_counts,
                                 double* out_dist64, int64_t* out_groups) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched (the program: with_where)
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = value_check(h, attr))) return rc;
-    if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "distinct needs an int64 column");
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
-    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "distinct: k above MLVDB_MAX_TOPK");
+    if (int rc = int64_attr_check(h, attr, "distinct needs an int64 column")) return rc;
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max(h, k, "distinct: ")) return rc;
     if (max_groups < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "max_groups < 0");
     if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     auto call = [&]() {
@@ -3089,22 +3176,19 @@ int mlvdb_search_batch_distinct(mlvdb_index* h, const float* queries, int64_t nq
 // ---- grouped kNN (mlvdb_grouped.h)
 extern "C++" {
 namespace {
-// padding of queries [q0, q0 + n) of a grouped call, on the host
-void grouped_pad(int64_t q0, int64_t n, int32_t k, int32_t gsz, int64_t* out_labels, float* out_dist, int32_t* out_counts,
+// padding of the nq queries of a grouped call, on the host
+void grouped_pad(int64_t nq, int32_t k, int32_t gsz, int64_t* out_labels, float* out_dist, int32_t* out_counts,
                  int32_t* out_gcnt, double* out_dist64, int64_t* out_groups) {
-    const int64_t at = q0 * k * gsz;
-    pad_outputs(out_labels + at, out_dist + at, out_dist64 ? out_dist64 + at : nullptr, n * k * gsz, out_counts + q0, n);
-    for (int64_t i = q0 * k; i < (q0 + n) * k; ++i) {
-        out_gcnt[i] = 0;
-        if (out_groups) out_groups[i] = INT64_MIN;
-    }
+    pad_outputs(out_labels, out_dist, out_dist64, nq * k * gsz, out_counts, nq);
+    pad(out_gcnt, nq * k, 0);
+    pad(out_groups, nq * k, INT64_MIN);
 }
 
 // The member stage of one chunk of n queries: grp / cnt are the distinct stage's group codes [n, k] and counts [n] on the host,
 // h->dist_q holds the chunk's raw queries.  Member lists of the picked codes (count, prefix sum, fill), tiles, the gathered
-// kernel, the merge -- outputs left in h->grp_out [d64 | labels | dist | group counts], enqueued, not waited for.
+// kernel, the merge -- outputs left in h->grp_out (`o`: n * k * gsz entries, n * k group counts), complete on return.
 int grouped_members(mlvdb_index* h, int32_t n, int32_t k, int32_t gsz, int32_t qt_max, const int64_t* col, const int64_t* grp,
-                    const int32_t* cnt) {
+                    const int32_t* cnt, ListBlock& o) {
     hipStream_t s = h->stream;
     const int32_t nslots = n * k;
     // the (code, slot) pairs sorted by code, then by query: queries sharing a document share its rows' loads
@@ -3129,10 +3213,12 @@ int grouped_members(mlvdb_index* h, int32_t n, int32_t k, int32_t gsz, int32_t q
         keys[at] = picked[first[u]].first;
         slot_of[u] = (uint32_t)at;
     }
-    HIP_TRY(h, h->grp_tab.ensure(slots * (sizeof(int64_t) + sizeof(uint32_t))));  // [keys | counts, then cursors]
-    Carver tab{h->grp_tab.as<char>()};
-    long long* keys_d = tab.take<long long>(slots);
-    uint32_t* counts_d = tab.take<uint32_t>(slots);
+    long long* keys_d = nullptr;
+    uint32_t* counts_d = nullptr;  // counts, then the fill's cursors
+    CARVE(h, h->grp_tab, [&](Carver& c) {
+        keys_d = c.take<long long>(slots);
+        counts_d = c.take<uint32_t>(slots);
+    });
     std::vector<uint32_t> counts(slots, 0);
     if (npairs > 0) {
         HIP_TRY(h, hipMemcpyAsync(keys_d, keys.data(), slots * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -3182,22 +3268,21 @@ int grouped_members(mlvdb_index* h, int32_t n, int32_t k, int32_t gsz, int32_t q
         }
     }
     if (nparts * gsz > INT32_MAX) return fail(h, MLVDB_ERR_INTERNAL, "grouped: partial lists beyond 2^31 entries");
-    const size_t tile_bytes = (tiles[0].size() + tiles[1].size() + tiles[2].size()) * sizeof(GroupedTile);
-    const size_t pair_off = (tile_bytes + 15) / 16 * 16, slot_off = pair_off + pairs.size() * sizeof(GroupedPair);
-    HIP_TRY(h, h->grp_tiles.ensure(slot_off + pair_of_slot.size() * sizeof(int32_t) + 16));
-    char* td = h->grp_tiles.as<char>();
-    const GroupedTile* tiles_d[3];
-    size_t off = 0;
-    for (int cls = 0; cls < 3; ++cls) {
-        tiles_d[cls] = reinterpret_cast<const GroupedTile*>(td + off);
+    GroupedTile* tiles_d[3] = {};
+    GroupedPair* pairs_d = nullptr;
+    int32_t* pos_d = nullptr;
+    CARVE(h, h->grp_tiles, [&](Carver& c) {
+        for (int cls = 0; cls < 3; ++cls) tiles_d[cls] = c.take<GroupedTile>(tiles[cls].size());
+        c.pad_to(16);
+        pairs_d = c.take<GroupedPair>(pairs.size());
+        pos_d = c.take<int32_t>(pair_of_slot.size());
+        c.take<char>(16);  // slack
+    });
+    for (int cls = 0; cls < 3; ++cls)
         if (!tiles[cls].empty())
-            HIP_TRY(h, hipMemcpyAsync(td + off, tiles[cls].data(), tiles[cls].size() * sizeof(GroupedTile), hipMemcpyHostToDevice, s));
-        off += tiles[cls].size() * sizeof(GroupedTile);
-    }
-    const GroupedPair* pairs_d = reinterpret_cast<const GroupedPair*>(td + pair_off);
-    const int32_t* pos_d = reinterpret_cast<const int32_t*>(td + slot_off);
-    if (npairs > 0) HIP_TRY(h, hipMemcpyAsync(td + pair_off, pairs.data(), pairs.size() * sizeof(GroupedPair), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(td + slot_off, pair_of_slot.data(), pair_of_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(tiles_d[cls], tiles[cls].data(), tiles[cls].size() * sizeof(GroupedTile), hipMemcpyHostToDevice, s));
+    if (npairs > 0) HIP_TRY(h, hipMemcpyAsync(pairs_d, pairs.data(), pairs.size() * sizeof(GroupedPair), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(pos_d, pair_of_slot.data(), pair_of_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     // the chunk's queries, prepared as every exact path prepares them, staged by query index
     HIP_TRY(h, h->qpad.ensure((size_t)n * h->ld * sizeof(float)));
     HIP_TRY(h, h->qaux.ensure((size_t)n * sizeof(double)));
@@ -3209,9 +3294,7 @@ int grouped_members(mlvdb_index* h, int32_t n, int32_t k, int32_t gsz, int32_t q
         HIP_TRY(h, launch_grouped_gather(h->X, h->qpad.as<float>(), h->qaux.as<double>(), h->grp_lab.as<int32_t>(), tiles_d[cls],
                                          (int32_t)tiles[cls].size(), pairs_d, h->ld, h->space, kQt[cls], gsz,
                                          h->partial.as<TopEntry>(), s));
-    const size_t ng = (size_t)nslots * gsz;
-    HIP_TRY(h, h->grp_out.ensure(ListBlock::bytes(ng, (size_t)nslots)));
-    const ListBlock o(h->grp_out.p, ng, (size_t)nslots);  // (its counts: the group counts)
+    if (int rc = carve_list(h, h->grp_out, (size_t)nslots * gsz, (size_t)nslots, o)) return rc;  // (its counts: the group counts)
     HIP_TRY(h, launch_grouped_merge(h->partial.as<TopEntry>(), pairs_d, pos_d, nslots, gsz, o.lab, o.dist, o.d64, o.cnt, s));
     HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
     return MLVDB_OK;
@@ -3224,7 +3307,7 @@ int grouped_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, in
                  double* out_dist64, int64_t* out_groups) {
     hipStream_t s = h->stream;
     if (h->total == 0 || h->total == h->deleted) {
-        grouped_pad(0, nq, k, gsz, out_labels, out_dist, out_counts, out_gcnt, out_dist64, out_groups);
+        grouped_pad(nq, k, gsz, out_labels, out_dist, out_counts, out_gcnt, out_dist64, out_groups);
         return MLVDB_OK;
     }
     const int32_t k_eff = max_groups > 0 ? (int32_t)std::min<int64_t>(k, max_groups) : k;
@@ -3240,8 +3323,8 @@ int grouped_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, in
         grp.resize(nk);
         cnt.resize((size_t)n);
         if (int rc = copy_down(h, s, {{grp.data(), 0, o.grp, nk}, {cnt.data(), 0, o.cnt, (size_t)n}})) return rc;
-        if (int rc = grouped_members(h, n, k, gsz, qt_max, col, grp.data(), cnt.data())) return rc;
-        const ListBlock m(h->grp_out.p, ng, nk);  // [d64 | labels | dist | group counts], as grouped_members left it
+        ListBlock m;
+        if (int rc = grouped_members(h, n, k, gsz, qt_max, col, grp.data(), cnt.data(), m)) return rc;
         const size_t at = (size_t)q0 * k;
         if (int rc = copy_down(h, s, {{out_dist64, at * gsz, m.d64, ng}, {out_labels, at * gsz, m.lab, ng},
                                       {out_dist, at * gsz, m.dist, ng}, {out_gcnt, at, m.cnt, nk}}))
@@ -3257,17 +3340,13 @@ int grouped_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, in
 int mlvdb_search_batch_grouped(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_t group_size, int32_t attr,
                                int64_t max_groups, const mlvdb_where* where, int64_t* out_labels, float* out_dist,
                                int32_t* out_counts, int32_t* out_group_counts, double* out_dist64, int64_t* out_groups) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched (the program: with_where)
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = value_check(h, attr))) return rc;
-    if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "grouped needs an int64 column");
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (int rc = int64_attr_check(h, attr, "grouped needs an int64 column")) return rc;
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
     if (group_size < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "group_size must be >= 1");
-    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "grouped: k above MLVDB_MAX_TOPK");
+    if (int rc = check_k_max(h, k, "grouped: ")) return rc;
     if (group_size > kGroupedMaxSize) return fail(h, MLVDB_ERR_UNSUPPORTED, "grouped: group_size above MLVDB_GROUPED_MAX_SIZE");
     if (max_groups < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "max_groups < 0");
     if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts || !out_group_counts))
@@ -3295,8 +3374,8 @@ int mmr_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_
     hipStream_t s = h->stream;
     if (h->total == 0 || h->total == h->deleted) {
         pad_outputs(out_labels, out_dist, out_dist64, nq * k, out_counts, nq);
-        if (out_rank) std::fill(out_rank, out_rank + nq * k, -1);
-        if (out_objective) std::fill(out_objective, out_objective + nq * k, __builtin_inf());
+        pad(out_rank, nq * k, -1);
+        pad(out_objective, nq * k, __builtin_inf());
         return MLVDB_OK;
     }
     const double one_minus_lambda = 1.0 - lambda;  // formed once, here
@@ -3304,18 +3383,21 @@ int mmr_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, int32_
         const int32_t n = (int32_t)std::min<int64_t>(kMmrChunk, nq - q0);
         const size_t nk = (size_t)n * k, nl = (size_t)n * fetch_k;
         HIP_TRY(h, h->mmr_q.ensure((size_t)n * h->dim * sizeof(float)));
-        HIP_TRY(h, h->mmr_list.ensure(ListBlock::bytes(nl, (size_t)n)));
-        HIP_TRY(h, h->mmr_out.ensure(nk * (2 * sizeof(double) + sizeof(int64_t) + sizeof(float) + sizeof(int32_t)) +
-                                     (size_t)n * sizeof(int32_t)));
+        ListBlock l;
+        if (int rc = carve_list(h, h->mmr_list, nl, (size_t)n, l)) return rc;
+        double *o_d64 = nullptr, *o_obj = nullptr;
+        int64_t* o_lab = nullptr;
+        float* o_dist = nullptr;
+        int32_t *o_rank = nullptr, *o_cnt = nullptr;
+        CARVE(h, h->mmr_out, [&](Carver& c) {
+            o_d64 = c.take<double>(nk);
+            o_obj = c.take<double>(nk);
+            o_lab = c.take<int64_t>(nk);
+            o_dist = c.take<float>(nk);
+            o_rank = c.take<int32_t>(nk);
+            o_cnt = c.take<int32_t>((size_t)n);
+        });
         float* dq = h->mmr_q.as<float>();
-        const ListBlock l(h->mmr_list.p, nl, (size_t)n);
-        Carver out{h->mmr_out.as<char>()};  // [d64 | objective | labels | dist | rank | counts]
-        double* o_d64 = out.take<double>(nk);
-        double* o_obj = out.take<double>(nk);
-        int64_t* o_lab = out.take<int64_t>(nk);
-        float* o_dist = out.take<float>(nk);
-        int32_t* o_rank = out.take<int32_t>(nk);
-        int32_t* o_cnt = out.take<int32_t>((size_t)n);
         HIP_TRY(h, hipMemcpyAsync(dq, queries + (size_t)q0 * h->dim, (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
         if (int rc = search_device_impl(h, dq, n, fetch_k, l.lab, l.dist, l.cnt, l.d64, s, false)) return rc;
         HIP_TRY(h, launch_mmr_select(h->X, h->dim, h->ld, h->space, l.lab, l.dist, l.d64, l.cnt, n, fetch_k, k, lambda,
@@ -3381,18 +3463,21 @@ int like_impl(mlvdb_index* h, const int64_t* ex_labels, const double* ex_weights
         const int64_t e0 = ex_offsets[q0];
         const size_t ne = (size_t)(ex_offsets[q0 + n] - e0);
         for (int32_t i = 0; i <= n; ++i) off[(size_t)i] = ex_offsets[q0 + i] - e0;  // (the last chunk's copy has completed)
-        HIP_TRY(h, h->like_q.ensure((base ? 2 : 1) * nd * sizeof(float)));
-        HIP_TRY(h, h->like_ex.ensure(ne * (sizeof(double) + sizeof(int64_t)) + ((size_t)n + 1) * sizeof(int64_t)));
-        HIP_TRY(h, h->like_list.ensure(ListBlock::bytes(nl, (size_t)n)));
-        HIP_TRY(h, h->like_out.ensure(ListBlock::bytes(nk, (size_t)n)));
-        float* dq = h->like_q.as<float>();
-        float* dbase = base ? dq + nd : nullptr;
-        Carver ex{h->like_ex.as<char>()};  // [weights | labels | offsets]
-        double* e_w = ex.take<double>(ne);
-        int64_t* e_lab = ex.take<int64_t>(ne);
-        int64_t* e_off = ex.take<int64_t>((size_t)n + 1);
-        const ListBlock l(h->like_list.p, nl, (size_t)n);
-        const ListBlock o(h->like_out.p, nk, (size_t)n);
+        float *dq = nullptr, *dbase = nullptr;
+        CARVE(h, h->like_q, [&](Carver& c) {
+            dq = c.take<float>(nd);
+            if (base) dbase = c.take<float>(nd);
+        });
+        double* e_w = nullptr;
+        int64_t *e_lab = nullptr, *e_off = nullptr;
+        CARVE(h, h->like_ex, [&](Carver& c) {
+            e_w = c.take<double>(ne);
+            e_lab = c.take<int64_t>(ne);
+            e_off = c.take<int64_t>((size_t)n + 1);
+        });
+        ListBlock l, o;
+        if (int rc = carve_list(h, h->like_list, nl, (size_t)n, l)) return rc;
+        if (int rc = carve_list(h, h->like_out, nk, (size_t)n, o)) return rc;
         if (ne > 0) {
             HIP_TRY(h, hipMemcpyAsync(e_w, ex_weights + e0, ne * sizeof(double), hipMemcpyHostToDevice, s));
             HIP_TRY(h, hipMemcpyAsync(e_lab, ex_labels + e0, ne * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -3417,12 +3502,10 @@ int mlvdb_search_batch_like(mlvdb_index* h, const int64_t* example_labels, const
                             const int64_t* example_offsets, const float* base_queries, int64_t nq, int32_t k,
                             int32_t exclude_examples, const mlvdb_where* where, int64_t* out_labels, float* out_dist,
                             int32_t* out_counts, double* out_dist64, float* out_queries) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked on the host before anything is launched (the program: with_where)
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
     if (k > kLikeMaxFetch) return fail(h, MLVDB_ERR_UNSUPPORTED, "like: k above MLVDB_LIKE_MAX_FETCH");
     if (nq > 0 && (!example_offsets || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     int32_t most = 0;  // M: the most distinct example labels of one query
@@ -3462,14 +3545,17 @@ int mlvdb_search_batch_like(mlvdb_index* h, const int64_t* example_labels, const
 extern "C++" {
 namespace {
 // The program of a facet call on the device (where == nullptr: no program, n_ops 0); validated by the caller.
-int facet_program(mlvdb_index* h, const mlvdb_where* where, const WhereOp** prog, int32_t* n_ops, const int64_t** set_d) {
-    *prog = nullptr;
-    *n_ops = 0;
-    *set_d = nullptr;
+struct DevProgram {
+    const WhereOp* ops = nullptr;
+    int32_t n_ops = 0;
+    const int64_t* set = nullptr;
+};
+
+int facet_program(mlvdb_index* h, const mlvdb_where* where, DevProgram& pg) {
     if (!where) return MLVDB_OK;
-    if (int rc = where_upload(h, where, set_d)) return rc;
-    *prog = h->where_prog.as<WhereOp>();
-    *n_ops = where->n_ops;
+    if (int rc = where_upload(h, where, &pg.set)) return rc;
+    pg.ops = h->where_prog.as<WhereOp>();
+    pg.n_ops = where->n_ops;
     return MLVDB_OK;
 }
 
@@ -3477,30 +3563,30 @@ int facet_program(mlvdb_index* h, const mlvdb_where* where, const WhereOp** prog
 int facet_values_run(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
                      int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent, bool list) {
     hipStream_t s = h->stream;
-    const WhereOp* prog;
-    int32_t n_ops;
-    const int64_t* set_d;
-    if (int rc = facet_program(h, where, &prog, &n_ops, &set_d)) return rc;
+    DevProgram pg;
+    if (int rc = facet_program(h, where, pg)) return rc;
     uint64_t slots = 64;  // a power of two >= 2 max_values: the table is at most half full when the call succeeds
     while (slots < 2 * (uint64_t)max_values) slots *= 2;
-    // [keys | counts | packed keys | packed counts]
-    HIP_TRY(h, h->facet_tab.ensure((2 * slots + 2 * (size_t)max_values) * sizeof(int64_t)));
-    HIP_TRY(h, h->facet_misc.ensure(kFacetCounters * sizeof(unsigned long long)));
     FacetTable t{};
-    t.keys = h->facet_tab.as<unsigned long long>();
-    t.counts = t.keys + slots;
+    long long* packed_keys = nullptr;
+    unsigned long long* packed_counts = nullptr;
+    CARVE(h, h->facet_tab, [&](Carver& c) {
+        t.keys = c.take<unsigned long long>(slots);
+        t.counts = c.take<unsigned long long>(slots);
+        packed_keys = c.take<long long>((size_t)max_values);
+        packed_counts = c.take<unsigned long long>((size_t)max_values);
+    });
+    HIP_TRY(h, h->facet_misc.ensure(kFacetCounters * sizeof(unsigned long long)));
     t.mask = slots - 1;
     t.max_values = (unsigned long long)max_values;
     t.ctr = h->facet_misc.as<unsigned long long>();
-    long long* packed_keys = reinterpret_cast<long long*>(t.counts + slots);
-    unsigned long long* packed_counts = t.counts + slots + max_values;
     HIP_TRY(h, launch_attr_fill(reinterpret_cast<int64_t*>(t.keys), INT64_MIN, 0, (int64_t)slots, s));
     HIP_TRY(h, hipMemsetAsync(t.counts, 0, slots * sizeof(unsigned long long), s));
     HIP_TRY(h, hipMemsetAsync(t.ctr, 0, kFacetCounters * sizeof(unsigned long long), s));
     if (list)
-        HIP_TRY(h, launch_facet_list_values(prog, n_ops, set_d, h->rn, h->attr_col[attr], h->list_pool[attr], h->total, t, s));
+        HIP_TRY(h, launch_facet_list_values(pg.ops, pg.n_ops, pg.set, h->rn, h->attr_col[attr], h->list_pool[attr], h->total, t, s));
     else
-        HIP_TRY(h, launch_facet_values(prog, n_ops, set_d, h->rn, h->attr_col[attr], h->total, t, s));
+        HIP_TRY(h, launch_facet_values(pg.ops, pg.n_ops, pg.set, h->rn, h->attr_col[attr], h->total, t, s));
     HIP_TRY(h, launch_facet_collect(t, packed_keys, packed_counts, s));
     unsigned long long ctr[kFacetCounters] = {};
     HIP_TRY(h, hipMemcpyAsync(ctr, t.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
@@ -3529,27 +3615,22 @@ int facet_values_run(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int
     return MLVDB_OK;
 }
 
-int facet_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
-                      int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
-    return facet_values_run(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent, false);
-}
-
 int facet_bins_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, const void* edges, int32_t n_edges,
                     int64_t* out_counts, int64_t* matched, int64_t* absent) {
     hipStream_t s = h->stream;
-    const WhereOp* prog;
-    int32_t n_ops;
-    const int64_t* set_d;
-    if (int rc = facet_program(h, where, &prog, &n_ops, &set_d)) return rc;
-    // [counters | bins | edges]
+    DevProgram pg;
+    if (int rc = facet_program(h, where, pg)) return rc;
     const size_t nbins = (size_t)n_edges + 1;
-    HIP_TRY(h, h->facet_misc.ensure((kFacetCounters + nbins + (size_t)n_edges) * sizeof(int64_t)));
-    unsigned long long* ctr_d = h->facet_misc.as<unsigned long long>();
-    unsigned long long* bins_d = ctr_d + kFacetCounters;
-    int64_t* edges_d = reinterpret_cast<int64_t*>(bins_d + nbins);
-    HIP_TRY(h, hipMemsetAsync(ctr_d, 0, (kFacetCounters + nbins) * sizeof(unsigned long long), s));
+    unsigned long long *ctr_d = nullptr, *bins_d = nullptr;  // adjacent: cleared, and read back, as one run
+    int64_t* edges_d = nullptr;
+    CARVE(h, h->facet_misc, [&](Carver& c) {
+        ctr_d = c.take<unsigned long long>(kFacetCounters);
+        bins_d = c.take<unsigned long long>(nbins);
+        edges_d = c.take<int64_t>((size_t)n_edges);
+    });
+    HIP_TRY(h, hipMemsetAsync(ctr_d, 0, span_bytes(ctr_d, edges_d), s));
     HIP_TRY(h, hipMemcpyAsync(edges_d, edges, (size_t)n_edges * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_facet_bins(prog, n_ops, set_d, h->rn, h->attr_col[attr], h->attr_type[attr], h->total, edges_d, n_edges,
+    HIP_TRY(h, launch_facet_bins(pg.ops, pg.n_ops, pg.set, h->rn, h->attr_col[attr], h->attr_type[attr], h->total, edges_d, n_edges,
                                  bins_d, ctr_d, s));
     std::vector<int64_t> host(kFacetCounters + nbins);
     HIP_TRY(h, hipMemcpyAsync(host.data(), ctr_d, host.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -3564,32 +3645,26 @@ int facet_bins_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, cons
 
 int mlvdb_facet_values(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
                        int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = value_check(h, attr))) return rc;
-    if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "value facets need an int64 column");
+    if (int rc = int64_attr_check(h, attr, "value facets need an int64 column")) return rc;
     if (max_values < 1 || max_values > MLVDB_FACET_MAX_VALUES)
         return fail(h, MLVDB_ERR_INVALID_ARG, "max_values must be in 1..MLVDB_FACET_MAX_VALUES");
     if (!out_values || !out_counts || !n_values || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (where && (rc = where_prepare(h, where))) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
     *n_values = *matched = *absent = 0;
     if (h->total == 0) return MLVDB_OK;
-    return facet_values_impl(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent);
+    return facet_values_run(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent, false);
     });
 }
 
 int mlvdb_facet_bins(mlvdb_index* h, int32_t attr, const mlvdb_where* where, const void* edges, int32_t n_edges,
                      int64_t* out_counts, int64_t* matched, int64_t* absent) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = scalar_check(h, attr))) return rc;
-    if ((rc = value_check(h, attr))) return rc;
+    if (int rc = attr_check(h, attr)) return rc;
+    if (int rc = scalar_check(h, attr)) return rc;
+    if (int rc = value_check(h, attr)) return rc;
     if (n_edges < 1 || n_edges > MLVDB_FACET_MAX_EDGES)
         return fail(h, MLVDB_ERR_INVALID_ARG, "n_edges must be in 1..MLVDB_FACET_MAX_EDGES");
     if (!edges || !out_counts || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
@@ -3604,7 +3679,7 @@ int mlvdb_facet_bins(mlvdb_index* h, int32_t attr, const mlvdb_where* where, con
         for (int32_t i = 1; i < n_edges; ++i)  // (a NaN edge fails the comparison too)
             if (!(e[i - 1] < e[i])) return fail(h, MLVDB_ERR_INVALID_ARG, "edges must be strictly ascending and not NaN");
     }
-    if (where && (rc = where_prepare(h, where))) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
     *matched = *absent = 0;
     for (int32_t i = 0; i <= n_edges; ++i) out_counts[i] = 0;
     if (h->total == 0) return MLVDB_OK;
@@ -3619,34 +3694,33 @@ int attr_stats_impl(mlvdb_index* h, int32_t attr, int32_t by, const mlvdb_where*
                     int64_t* out_rows, int64_t* out_count, void* out_min, void* out_max, int64_t* out_sum_hi,
                     uint64_t* out_sum_lo, int64_t* n_groups, int64_t* matched, int64_t* by_absent) {
     hipStream_t s = h->stream;
-    const WhereOp* prog;
-    int32_t n_ops;
-    const int64_t* set_d;
-    if (int rc = facet_program(h, where, &prog, &n_ops, &set_d)) return rc;
+    DevProgram pg;
+    if (int rc = facet_program(h, where, pg)) return rc;
     const bool f64 = h->attr_type[attr] == MLVDB_ATTR_FLOAT64;
     uint64_t slots = 64;  // a power of two >= 2 max_groups: the table is at most half full when the call succeeds
     while (slots < 2 * (uint64_t)max_groups) slots *= 2;
-    // [keys | min | rows | count | max | sum hi | sum lo | counters | packed groups]
-    const size_t words = 7 * slots + kFacetCounters + (size_t)max_groups * kStatsRecord;
-    HIP_TRY(h, h->stats_tab.ensure(words * sizeof(unsigned long long)));
     StatsTable t{};
-    t.keys = h->stats_tab.as<unsigned long long>();
-    t.mn = t.keys + slots;
-    t.rows = t.mn + slots;
-    t.count = t.rows + slots;
-    t.mx = t.count + slots;
-    t.hi = t.mx + slots;
-    t.lo = t.hi + slots;
-    t.ctr = t.lo + slots;
+    unsigned long long* packed = nullptr;  // the packed groups, kStatsRecord words each
+    CARVE(h, h->stats_tab, [&](Carver& c) {
+        using u64 = unsigned long long;
+        t.keys = c.take<u64>(slots);
+        t.mn = c.take<u64>(slots);
+        t.rows = c.take<u64>(slots);  // rows .. counters are adjacent: cleared as one run
+        t.count = c.take<u64>(slots);
+        t.mx = c.take<u64>(slots);
+        t.hi = c.take<u64>(slots);
+        t.lo = c.take<u64>(slots);
+        t.ctr = c.take<u64>(kFacetCounters);
+        packed = c.take<u64>((size_t)max_groups * kStatsRecord);
+    });
     t.mask = slots - 1;
     t.max_groups = (unsigned long long)max_groups;
-    unsigned long long* packed = t.ctr + kFacetCounters;
     HIP_TRY(h, launch_attr_fill(reinterpret_cast<int64_t*>(t.keys), INT64_MIN, 0, (int64_t)slots, s));
-    HIP_TRY(h, hipMemsetAsync(t.mn, 0xFF, slots * sizeof(unsigned long long), s));
-    HIP_TRY(h, hipMemsetAsync(t.rows, 0, (5 * slots + kFacetCounters) * sizeof(unsigned long long), s));
+    HIP_TRY(h, hipMemsetAsync(t.mn, 0xFF, span_bytes(t.mn, t.rows), s));
+    HIP_TRY(h, hipMemsetAsync(t.rows, 0, span_bytes(t.rows, packed), s));
     const int64_t* by_col = by < 0 ? nullptr : h->attr_col[by];
-    HIP_TRY(h, launch_stats_pass1(prog, n_ops, set_d, h->rn, by_col, h->attr_col[attr], f64, h->total, t, s));
-    if (f64) HIP_TRY(h, launch_stats_pass2(prog, n_ops, set_d, h->rn, by_col, h->attr_col[attr], h->total, t, s));
+    HIP_TRY(h, launch_stats_pass1(pg.ops, pg.n_ops, pg.set, h->rn, by_col, h->attr_col[attr], f64, h->total, t, s));
+    if (f64) HIP_TRY(h, launch_stats_pass2(pg.ops, pg.n_ops, pg.set, h->rn, by_col, h->attr_col[attr], h->total, t, s));
     HIP_TRY(h, launch_stats_collect(t, packed, s));
     unsigned long long ctr[kFacetCounters] = {};
     HIP_TRY(h, hipMemcpyAsync(ctr, t.ctr, sizeof ctr, hipMemcpyDeviceToHost, s));
@@ -3689,24 +3763,20 @@ int attr_stats_impl(mlvdb_index* h, int32_t attr, int32_t by, const mlvdb_where*
 int mlvdb_attr_stats(mlvdb_index* h, int32_t attr, int32_t by, const mlvdb_where* where, int64_t max_groups, int64_t* out_keys,
                      int64_t* out_rows, int64_t* out_count, void* out_min, void* out_max, int64_t* out_sum_hi,
                      uint64_t* out_sum_lo, int64_t* n_groups, int64_t* matched, int64_t* by_absent) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = scalar_check(h, attr))) return rc;
-    if ((rc = value_check(h, attr))) return rc;
+    if (int rc = attr_check(h, attr)) return rc;
+    if (int rc = scalar_check(h, attr)) return rc;
+    if (int rc = value_check(h, attr)) return rc;
     if (by != -1) {
-        if ((rc = attr_check(h, by))) return rc;
-        if ((rc = value_check(h, by))) return rc;
-        if (h->attr_type[by] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "attr_stats: by needs an int64 column");
+        if (int rc = int64_attr_check(h, by, "attr_stats: by needs an int64 column")) return rc;
     }
     if (max_groups < 1 || max_groups > MLVDB_FACET_MAX_VALUES)
         return fail(h, MLVDB_ERR_INVALID_ARG, "max_groups must be in 1..MLVDB_FACET_MAX_VALUES");
     if (!out_keys || !out_rows || !out_count || !out_min || !out_max || !out_sum_hi || !out_sum_lo || !n_groups || !matched ||
         !by_absent)
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (where && (rc = where_prepare(h, where))) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
     *n_groups = by < 0 ? 1 : 0;
     *matched = *by_absent = 0;
     out_keys[0] = out_rows[0] = out_count[0] = out_sum_hi[0] = 0;  // the one group of an ungrouped call when nothing matches
@@ -3721,19 +3791,15 @@ int mlvdb_attr_stats(mlvdb_index* h, int32_t attr, int32_t by, const mlvdb_where
 // ---- late-interaction search (mlvdb_maxsim.h)
 extern "C++" {
 namespace {
-// padding of queries [q0, q0 + n) of a late-interaction call and of their tokens' match rows, on the host
-void maxsim_pad(const int64_t* off, int64_t q0, int64_t n, int32_t k, int64_t* out_groups, float* out_score, int32_t* out_counts,
+// padding of the nq queries of a late-interaction call and of their ntok tokens' match rows, on the host
+void maxsim_pad(int64_t nq, int64_t ntok, int32_t k, int64_t* out_groups, float* out_score, int32_t* out_counts,
                 double* out_score64, int64_t* out_match_labels, double* out_match_dist64) {
-    for (int64_t i = q0 * k; i < (q0 + n) * k; ++i) {
-        out_groups[i] = INT64_MIN;
-        out_score[i] = __builtin_inff();
-        if (out_score64) out_score64[i] = __builtin_inf();
-    }
-    for (int64_t i = q0; i < q0 + n; ++i) out_counts[i] = 0;
-    for (int64_t i = off[q0] * k; i < off[q0 + n] * k; ++i) {
-        if (out_match_labels) out_match_labels[i] = -1;
-        if (out_match_dist64) out_match_dist64[i] = __builtin_inf();
-    }
+    pad(out_groups, nq * k, INT64_MIN);
+    pad(out_score, nq * k, __builtin_inff());
+    pad(out_score64, nq * k, __builtin_inf());
+    pad(out_counts, nq, 0);
+    pad(out_match_labels, ntok * k, -1);
+    pad(out_match_dist64, ntok * k, __builtin_inf());
 }
 
 // The validated call (h->rn is the masked copy when a program restricts the rows): the documents and their table, the dense
@@ -3743,11 +3809,11 @@ int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t
                 int64_t* out_groups, float* out_score, int32_t* out_counts, double* out_score64, int64_t* out_match_labels,
                 double* out_match_dist64) {
     hipStream_t s = h->stream;
-    auto pad = [&](int64_t q0, int64_t n) {
-        maxsim_pad(off, q0, n, k, out_groups, out_score, out_counts, out_score64, out_match_labels, out_match_dist64);
+    auto pad_all = [&] {  // (off[0] == 0: off[nq] tokens in all)
+        maxsim_pad(nq, off[nq], k, out_groups, out_score, out_counts, out_score64, out_match_labels, out_match_dist64);
     };
     if (h->total == 0 || h->total == h->deleted) {
-        pad(0, nq);
+        pad_all();
         return MLVDB_OK;
     }
     if (int rc = begin_call(h, s)) return rc;
@@ -3756,11 +3822,11 @@ int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t
     const int64_t* col = h->attr_col[attr];
     std::unique_ptr<int64_t[]> codes(new int64_t[kMaxsimMaxGroups]), rows_of(new int64_t[kMaxsimMaxGroups]);
     int64_t G = 0, matched = 0, absent = 0;
-    if (int rc = facet_values_impl(h, attr, nullptr, kMaxsimMaxGroups, codes.get(), rows_of.get(), &G, &matched, &absent))
+    if (int rc = facet_values_run(h, attr, nullptr, kMaxsimMaxGroups, codes.get(), rows_of.get(), &G, &matched, &absent, false))
         return rc == MLVDB_ERR_OVERFLOW ? fail(h, rc, "maxsim: more than MLVDB_MAXSIM_MAX_GROUPS documents") : rc;
     rows_of.reset();
     if (G == 0) {  // every counted row's value is absent
-        pad(0, nq);
+        pad_all();
         return end_call(h, s);
     }
     // the open-addressing table, as grouped_members builds it, and the dense id of every slot
@@ -3775,11 +3841,13 @@ int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t
             keys[at] = codes[u];
             dense[at] = (int32_t)u;
         }
-        HIP_TRY(h, h->ms_tab.ensure(slots * (sizeof(int64_t) + sizeof(int32_t))));  // [keys | dense ids]
+        long long* keys_d = nullptr;
+        int32_t* dense_d = nullptr;
+        CARVE(h, h->ms_tab, [&](Carver& c) {
+            keys_d = c.take<long long>(slots);
+            dense_d = c.take<int32_t>(slots);
+        });
         HIP_TRY(h, h->ms_rowdoc.ensure((size_t)h->total * sizeof(int32_t)));
-        Carver tab{h->ms_tab.as<char>()};
-        long long* keys_d = tab.take<long long>(slots);
-        int32_t* dense_d = tab.take<int32_t>(slots);
         HIP_TRY(h, hipMemcpyAsync(keys_d, keys.data(), slots * sizeof(int64_t), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(dense_d, dense.data(), slots * sizeof(int32_t), hipMemcpyHostToDevice, s));
         // 2. the dense id of every row: every later pass reads this instead of norm + code + probe
@@ -3807,8 +3875,8 @@ int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t
         HIP_TRY(h, h->qaux.ensure((size_t)ntok * sizeof(double)));
         HIP_TRY(h, h->ms_best.ensure((size_t)ntok * G * sizeof(unsigned long long)));
         HIP_TRY(h, h->ms_misc.ensure(((size_t)n + 1) * sizeof(int32_t)));
-        HIP_TRY(h, h->ms_out.ensure(ListBlock::bytes(nk, (size_t)n)));
-        const ListBlock o(h->ms_out.p, nk, (size_t)n);  // (its labels: dense ids)
+        ListBlock o;  // (its labels: dense ids)
+        if (int rc = carve_list(h, h->ms_out, nk, (size_t)n, o)) return rc;
         unsigned long long* best = h->ms_best.as<unsigned long long>();
         HIP_TRY(h, hipMemcpyAsync(h->dist_q.p, chunk_tokens, (size_t)ntok * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMemcpyAsync(h->ms_misc.p, tok_off.data(), ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -3859,8 +3927,8 @@ int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t
             if (t0 > 0 || nt < ntok)
                 HIP_TRY(h, hipMemcpyAsync(h->dist_q.p, chunk_tokens + (size_t)t0 * h->dim, (size_t)nt * h->dim * sizeof(float),
                                           hipMemcpyHostToDevice, s));
-            if (int rc = grouped_members(h, nt, k, 1, qt_max, col, grp.data(), tcnt.data())) return rc;
-            const ListBlock m(h->grp_out.p, ntk, ntk);  // [d64 | labels | dist | group counts], as grouped_members left it
+            ListBlock m;
+            if (int rc = grouped_members(h, nt, k, 1, qt_max, col, grp.data(), tcnt.data(), m)) return rc;
             const size_t mat = ((size_t)off[q0] + (size_t)t0) * k;
             if (int rc = copy_down(h, s, {{out_match_labels, mat, m.lab, ntk}, {out_match_dist64, mat, m.d64, ntk}})) return rc;
         }
@@ -3874,16 +3942,12 @@ int maxsim_impl(mlvdb_index* h, const float* tokens, const int64_t* off, int64_t
 int mlvdb_search_batch_maxsim(mlvdb_index* h, const float* tokens, const int64_t* token_offsets, int64_t nq, int32_t k,
                               int32_t attr, const mlvdb_where* where, int64_t* out_groups, float* out_score,
                               int32_t* out_counts, double* out_score64, int64_t* out_match_labels, double* out_match_dist64) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked on the host before anything is launched (the program: with_where)
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = value_check(h, attr))) return rc;
-    if (h->attr_type[attr] != MLVDB_ATTR_INT64) return fail(h, MLVDB_ERR_INVALID_ARG, "maxsim needs an int64 column");
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
-    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "maxsim: k above MLVDB_MAX_TOPK");
+    if (int rc = int64_attr_check(h, attr, "maxsim needs an int64 column")) return rc;
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max(h, k, "maxsim: ")) return rc;
     if (nq > 0 && (!tokens || !token_offsets || !out_groups || !out_score || !out_counts))
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     if (nq > 0 && token_offsets[0] != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "maxsim: token_offsets must start at 0");
@@ -3915,23 +3979,26 @@ int where_ordered_impl(mlvdb_index* h, int32_t attr, int32_t descending, int64_t
                        int64_t offset, int64_t limit, int64_t* out_labels, void* out_values, double* out_dist, int64_t* n_out,
                        int64_t* matched, int64_t* absent) {
     hipStream_t s = h->stream;
-    if (where)
-        if (int rc = where_run(h, where, nullptr)) return rc;
-    // [state | histograms of the passes | keys | out labels | out values | out distances | labels]
-    constexpr size_t kStateBytes = (sizeof(OrderState) + 63) / 64 * 64;
-    constexpr size_t kHistBytes = (size_t)kOrderPasses * kOrderBins * sizeof(unsigned long long);
-    HIP_TRY(h, h->order_ws.ensure(kStateBytes + kHistBytes + (size_t)kOrderMaxRows * (4 * sizeof(int64_t) + sizeof(uint32_t))));
-    OrderState* st = h->order_ws.as<OrderState>();
-    unsigned long long* hist = reinterpret_cast<unsigned long long*>(h->order_ws.as<char>() + kStateBytes);
-    unsigned long long* keys = hist + (size_t)kOrderPasses * kOrderBins;
-    int64_t* labels_d = reinterpret_cast<int64_t*>(keys + kOrderMaxRows);
-    int64_t* values_d = labels_d + kOrderMaxRows;
-    double* dist_d = reinterpret_cast<double*>(values_d + kOrderMaxRows);
-    uint32_t* clabels = reinterpret_cast<uint32_t*>(dist_d + kOrderMaxRows);
-    const uint8_t* mask = where ? h->row_mask.as<uint8_t>() : nullptr;
+    const uint8_t* mask = nullptr;
+    if (int rc = where_mask(h, where, &mask)) return rc;
+    OrderState* st = nullptr;
+    unsigned long long *hist = nullptr, *keys = nullptr;  // one histogram per digit pass; the collected keys
+    int64_t *labels_d = nullptr, *values_d = nullptr;     // the ranked window
+    double* dist_d = nullptr;
+    uint32_t* clabels = nullptr;                           // the collected keys' labels
+    CARVE(h, h->order_ws, [&](Carver& c) {
+        st = c.take<OrderState>(1);  // the state and the histograms are adjacent: cleared as one run
+        c.pad_to(64);
+        hist = c.take<unsigned long long>((size_t)kOrderPasses * kOrderBins);
+        keys = c.take<unsigned long long>(kOrderMaxRows);
+        labels_d = c.take<int64_t>(kOrderMaxRows);
+        values_d = c.take<int64_t>(kOrderMaxRows);
+        dist_d = c.take<double>(kOrderMaxRows);
+        clabels = c.take<uint32_t>(kOrderMaxRows);
+    });
     const int64_t* col = h->attr_col[attr];
     const int32_t type = h->attr_type[attr];
-    HIP_TRY(h, hipMemsetAsync(st, 0, kStateBytes + kHistBytes, s));
+    HIP_TRY(h, hipMemsetAsync(st, 0, span_bytes(st, keys), s));
     for (int32_t pass = 0; pass < kOrderPasses; ++pass) {
         unsigned long long* hp = hist + (size_t)pass * kOrderBins;
         HIP_TRY(h, launch_order_hist(mask, h->rn, col, type, descending, centre, h->total, pass, hp, st, s));
@@ -3963,17 +4030,15 @@ int where_ordered_impl(mlvdb_index* h, int32_t attr, int32_t descending, int64_t
 int mlvdb_where_ordered(mlvdb_index* h, int32_t attr, int32_t descending, const mlvdb_where* where, int64_t offset,
                         int64_t limit, int64_t* out_labels, void* out_values, int64_t* n_out, int64_t* matched,
                         int64_t* absent) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = scalar_check(h, attr))) return rc;
-    if ((rc = value_check(h, attr))) return rc;
+    if (int rc = attr_check(h, attr)) return rc;
+    if (int rc = scalar_check(h, attr)) return rc;
+    if (int rc = value_check(h, attr)) return rc;
     if (offset < 0 || limit < 1 || limit > MLVDB_ORDER_MAX_ROWS || offset > MLVDB_ORDER_MAX_ROWS - limit)
         return fail(h, MLVDB_ERR_INVALID_ARG, "offset >= 0, limit >= 1 and offset + limit <= MLVDB_ORDER_MAX_ROWS");
     if (!out_labels || !out_values || !n_out || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (where && (rc = where_prepare(h, where))) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
     *n_out = *matched = *absent = 0;
     if (h->total == 0) return MLVDB_OK;
     return where_ordered_impl(h, attr, descending != 0, 0, where, offset, limit, out_labels, out_values, nullptr, n_out, matched,
@@ -3985,18 +4050,16 @@ int mlvdb_where_ordered(mlvdb_index* h, int32_t attr, int32_t descending, const 
 int mlvdb_geo_nearest(mlvdb_index* h, int32_t attr, int64_t center, const mlvdb_where* where, int64_t offset, int64_t limit,
                       int64_t* out_labels, int64_t* out_points, double* out_dist_m, int64_t* n_out, int64_t* matched,
                       int64_t* absent) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = attr_check(h, attr))) return rc;
+    if (int rc = attr_check(h, attr)) return rc;
     if (h->attr_type[attr] != MLVDB_ATTR_GEO) return fail(h, MLVDB_ERR_INVALID_ARG, "geo_nearest needs a geo column");
     if (!geo_valid(center)) return fail(h, MLVDB_ERR_INVALID_ARG, "geo_nearest: center is not a point (lat_e7, lon_e7 out of range)");
     if (offset < 0 || limit < 1 || limit > MLVDB_ORDER_MAX_ROWS || offset > MLVDB_ORDER_MAX_ROWS - limit)
         return fail(h, MLVDB_ERR_INVALID_ARG, "offset >= 0, limit >= 1 and offset + limit <= MLVDB_ORDER_MAX_ROWS");
     if (!out_labels || !out_points || !out_dist_m || !n_out || !matched || !absent)
         return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (where && (rc = where_prepare(h, where))) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
     *n_out = *matched = *absent = 0;
     if (h->total == 0) return MLVDB_OK;
     return where_ordered_impl(h, attr, 0, center, where, offset, limit, out_labels, out_points, out_dist_m, n_out, matched, absent);
@@ -4008,12 +4071,15 @@ extern "C++" {
 namespace {
 int attr_set_at_impl(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const void* values, int64_t* updated) {
     hipStream_t s = h->stream;
-    // [counter | labels | values]
     const size_t lbytes = (size_t)n * sizeof(int64_t);
-    HIP_TRY(h, h->mutate_ws.ensure(64 + 2 * lbytes));
-    unsigned long long* cnt = h->mutate_ws.as<unsigned long long>();
-    int64_t* labels_d = reinterpret_cast<int64_t*>(h->mutate_ws.as<char>() + 64);
-    int64_t* values_d = labels_d + n;
+    unsigned long long* cnt = nullptr;
+    int64_t *labels_d = nullptr, *values_d = nullptr;
+    CARVE(h, h->mutate_ws, [&](Carver& c) {
+        cnt = c.take<unsigned long long>(1);
+        c.pad_to(64);
+        labels_d = c.take<int64_t>((size_t)n);
+        values_d = c.take<int64_t>((size_t)n);
+    });
     HIP_TRY(h, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), s));
     HIP_TRY(h, hipMemcpyAsync(labels_d, labels, lbytes, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(values_d, values, lbytes, hipMemcpyHostToDevice, s));
@@ -4060,11 +4126,14 @@ int attr_update_where_impl(mlvdb_index* h, const mlvdb_where* where, const Mutat
     hipStream_t s = h->stream;
     const int64_t* set_d = nullptr;
     if (int rc = where_upload(h, where, &set_d)) return rc;
-    // [matched, refused of the counting pass | the same of the storing pass | assignments]
-    HIP_TRY(h, h->mutate_ws.ensure(64 + sizeof(MutateSet) * MLVDB_MAX_ATTRS));
-    unsigned long long* cnt = h->mutate_ws.as<unsigned long long>();
-    MutateSet* sets_d = reinterpret_cast<MutateSet*>(h->mutate_ws.as<char>() + 64);
-    HIP_TRY(h, hipMemsetAsync(cnt, 0, 64, s));
+    unsigned long long* cnt = nullptr;  // matched, refused of the counting pass; the same of the storing pass
+    MutateSet* sets_d = nullptr;
+    CARVE(h, h->mutate_ws, [&](Carver& c) {
+        cnt = c.take<unsigned long long>(4);
+        c.pad_to(64);
+        sets_d = c.take<MutateSet>(MLVDB_MAX_ATTRS);
+    });
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, span_bytes(cnt, sets_d), s));
     HIP_TRY(h, hipMemcpyAsync(sets_d, sets, sizeof(MutateSet) * (size_t)n_sets, hipMemcpyHostToDevice, s));
     const WhereOp* prog = h->where_prog.as<WhereOp>();
     unsigned long long host[2] = {0, 0};
@@ -4092,13 +4161,7 @@ int tombstone_where_impl(mlvdb_index* h, const mlvdb_where* where, int64_t* out_
     hipStream_t s = h->stream;
     std::vector<int32_t> host;
     if (want_labels) {  // before the norms change: the compaction map of the masked norms, as mlvdb_where_labels lists them
-        const int64_t nblocks = (h->total + 1023) / 1024;
-        HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
-        HIP_TRY(h, h->partial.ensure((size_t)nblocks * sizeof(uint32_t) + 64));
-        HIP_TRY(h, h->labels_in.ensure((size_t)*matches * sizeof(int32_t)));
-        HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, s));
-        HIP_TRY(h, launch_compact_map(h->rn_masked.as<float>(), h->total, h->partial.as<uint32_t>(),
-                                      h->where_cnt.as<unsigned long long>(), h->labels_in.as<int32_t>(), s));
+        if (int rc = mask_labels(h, *matches)) return rc;
         host.resize((size_t)*matches);
         HIP_TRY(h, hipMemcpyAsync(host.data(), h->labels_in.p, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
@@ -4116,35 +4179,25 @@ int tombstone_where_impl(mlvdb_index* h, const mlvdb_where* where, int64_t* out_
 }  // extern "C++"
 
 int mlvdb_attr_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const void* values, int64_t* updated) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = attr_check(h, attr))) return rc;
-    if ((rc = scalar_check(h, attr))) return rc;
-    if (!updated || n < 0 || (n > 0 && (!labels || !values))) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / values / n");
-    *updated = 0;
-    if (n == 0) return MLVDB_OK;
-    std::vector<int64_t> sorted(labels, labels + n);
-    std::sort(sorted.begin(), sorted.end());
-    if (sorted.front() < 0 || sorted.back() >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label outside [0, total)");
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-        return fail(h, MLVDB_ERR_INVALID_ARG, "a label appears twice");
-    if ((rc = geo_values_check(h, attr, values, n))) return rc;
-    return attr_set_at_impl(h, attr, labels, n, values, updated);
+    if (int rc = attr_check(h, attr)) return rc;
+    if (int rc = scalar_check(h, attr)) return rc;
+    return with_labels(h, labels, n, updated, values != nullptr, "bad labels / values / n", [&]() -> int {
+        if (int rc = geo_values_check(h, attr, values, n)) return rc;
+        return attr_set_at_impl(h, attr, labels, n, values, updated);
+    });
     });
 }
 
 int mlvdb_attr_update_where(mlvdb_index* h, const mlvdb_where* where, const mlvdb_assign* sets, int32_t n_sets,
                             int64_t* matched, int64_t* refused) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     if (!matched || !refused) return fail(h, MLVDB_ERR_INVALID_ARG, "null counter");
     MutateSet resolved[MLVDB_MAX_ATTRS];
     bool any_add = false;
-    if ((rc = update_sets_prepare(h, sets, n_sets, resolved, &any_add))) return rc;
-    if ((rc = where_prepare(h, where))) return rc;
+    if (int rc = update_sets_prepare(h, sets, n_sets, resolved, &any_add)) return rc;
+    if (int rc = where_prepare(h, where)) return rc;
     *matched = *refused = 0;
     if (h->total == 0) return MLVDB_OK;
     return attr_update_where_impl(h, where, resolved, n_sets, any_add, matched, refused);
@@ -4152,9 +4205,7 @@ int mlvdb_attr_update_where(mlvdb_index* h, const mlvdb_where* where, const mlvd
 }
 
 int mlvdb_tombstone_where(mlvdb_index* h, const mlvdb_where* where, int64_t* out_labels, int64_t capacity, int64_t* matches) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // labels into out_labels[capacity], or no labels at all (NULL with a negative capacity)
     if (!matches || (out_labels ? capacity < 0 : capacity > 0)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
     return tombstone_where_impl(h, where, out_labels, capacity, matches);
@@ -4164,11 +4215,7 @@ int mlvdb_tombstone_where(mlvdb_index* h, const mlvdb_where* where, int64_t* out
 // ---- list columns (mlvdb_list.h)
 extern "C++" {
 namespace {
-int list_attr_check(mlvdb_index* h, int32_t attr) {
-    if (int rc = attr_check(h, attr)) return rc;
-    if (h->attr_type[attr] != MLVDB_ATTR_INT64_LIST) return fail(h, MLVDB_ERR_INVALID_ARG, "not a list column");
-    return MLVDB_OK;
-}
+int list_attr_check(mlvdb_index* h, int32_t attr) { return typed_attr_check(h, attr, MLVDB_ATTR_INT64_LIST, "not a list column"); }
 
 // One list as the columns hold them: at most MLVDB_LIST_MAX_LEN values, strictly ascending, none INT64_MIN.
 int list_check(mlvdb_index* h, const int64_t* v, int64_t len) {
@@ -4216,12 +4263,14 @@ int list_get_impl(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int64_
     const int64_t* slots = h->attr_col[attr] + first;
     if (int rc = list_scan(h, slots, nullptr, n, needed)) return rc;
     if (capacity < *needed) return MLVDB_OK;
-    // [values | offsets | present]
     const size_t vbytes = (size_t)*needed * sizeof(int64_t), obytes = (size_t)(n + 1) * sizeof(int64_t);
-    HIP_TRY(h, h->list_out.ensure(vbytes + obytes + (size_t)n));
-    int64_t* values_d = h->list_out.as<int64_t>();
-    int64_t* offsets_d = values_d + *needed;
-    uint8_t* present_d = reinterpret_cast<uint8_t*>(offsets_d + n + 1);
+    int64_t *values_d = nullptr, *offsets_d = nullptr;
+    uint8_t* present_d = nullptr;
+    CARVE(h, h->list_out, [&](Carver& c) {
+        values_d = c.take<int64_t>((size_t)*needed);
+        offsets_d = c.take<int64_t>((size_t)n + 1);
+        present_d = c.take<uint8_t>((size_t)n);
+    });
     HIP_TRY(h, launch_list_move(slots, n, h->list_sums.as<int64_t>(), h->list_pool[attr], values_d, nullptr, offsets_d,
                                 present_d, s));
     if (vbytes) HIP_TRY(h, hipMemcpyAsync(out_values, values_d, vbytes, hipMemcpyDeviceToHost, s));
@@ -4241,16 +4290,6 @@ int list_set_impl(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const 
     return MLVDB_OK;
 }
 
-// n >= 1 labels of a by-label write: inside [0, total), none twice.
-int labels_check(mlvdb_index* h, const int64_t* labels, int64_t n) {
-    std::vector<int64_t> sorted(labels, labels + n);
-    std::sort(sorted.begin(), sorted.end());
-    if (sorted.front() < 0 || sorted.back() >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "label outside [0, total)");
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-        return fail(h, MLVDB_ERR_INVALID_ARG, "a label appears twice");
-    return MLVDB_OK;
-}
-
 // The checked CSR written to the rows of the checked labels.
 int list_set_at_impl(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const int64_t* offsets,
                      const int64_t* values, const uint8_t* present, int64_t* updated) {
@@ -4259,50 +4298,38 @@ int list_set_at_impl(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_
     return attr_set_at_impl(h, attr, labels, n, slots.data(), updated);  // the slots are scattered like any int64 values
 }
 
-int facet_list_values_impl(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
-                           int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
-    return facet_values_run(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent, true);
-}
 }  // namespace
 }  // extern "C++"
 
 int mlvdb_attr_list_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const int64_t* offsets,
                         const int64_t* values, const uint8_t* present) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = list_attr_check(h, attr))) return rc;
-    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (int rc = list_attr_check(h, attr)) return rc;
+    if (int rc = check_row_range(h, first, n)) return rc;
     if (n == 0) return MLVDB_OK;
-    if ((rc = list_csr_check(h, n, offsets, values, present))) return rc;
+    if (int rc = list_csr_check(h, n, offsets, values, present)) return rc;
     return list_set_impl(h, attr, first, n, offsets, values, present);
     });
 }
 
 int mlvdb_attr_list_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const int64_t* offsets,
                            const int64_t* values, const uint8_t* present, int64_t* updated) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = list_attr_check(h, attr))) return rc;
-    if (!updated || n < 0 || (n > 0 && !labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n");
-    *updated = 0;
-    if (n == 0) return MLVDB_OK;
-    if ((rc = labels_check(h, labels, n))) return rc;
-    if ((rc = list_csr_check(h, n, offsets, values, present))) return rc;
-    return list_set_at_impl(h, attr, labels, n, offsets, values, present, updated);
+    if (int rc = list_attr_check(h, attr)) return rc;
+    return with_labels(h, labels, n, updated, true, "bad labels / n", [&]() -> int {
+        if (int rc = list_csr_check(h, n, offsets, values, present)) return rc;
+        return list_set_at_impl(h, attr, labels, n, offsets, values, present, updated);
+    });
     });
 }
 
 int mlvdb_attr_list_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int64_t* out_offsets, int64_t* out_values,
                         uint8_t* out_present, int64_t capacity, int64_t* needed) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if ((rc = list_attr_check(h, attr))) return rc;
-    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = list_attr_check(h, attr)) return rc;
+    if (int rc = check_row_range(h, first, n)) return rc;
     if (!needed || !out_offsets || capacity < 0 || (capacity > 0 && !out_values)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
     *needed = 0;
     if (n == 0) {
@@ -4315,23 +4342,21 @@ int mlvdb_attr_list_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, 
 
 int mlvdb_attr_list_update_where(mlvdb_index* h, const mlvdb_where* where, int32_t attr, const int64_t* values,
                                  int32_t n_values, int32_t clear, int64_t* matched) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
     if (!matched) return fail(h, MLVDB_ERR_INVALID_ARG, "null counter");
-    if ((rc = list_attr_check(h, attr))) return rc;
-    if (!clear && (rc = list_check(h, values, n_values))) return rc;
-    if ((rc = where_prepare(h, where))) return rc;
+    if (int rc = list_attr_check(h, attr)) return rc;
+    if (int rc = clear ? MLVDB_OK : list_check(h, values, n_values)) return rc;
+    if (int rc = where_prepare(h, where)) return rc;
     *matched = 0;
     if (h->total == 0) return MLVDB_OK;
     int64_t slot = INT64_MIN;
     if (!clear) {  // the list goes into the pool once; every matching row shares its slot
         const int64_t offsets[2] = {0, n_values};
         std::vector<int64_t> slots;
-        if ((rc = list_append(h, attr, 1, offsets, values, nullptr, slots))) return rc;
+        if (int rc = list_append(h, attr, 1, offsets, values, nullptr, slots)) return rc;
         slot = slots[0];
-        if ((rc = where_prepare(h, where))) return rc;  // (the append may have moved a pool the program reads)
+        if (int rc = where_prepare(h, where)) return rc;  // (the append may have moved a pool the program reads)
     }
     const MutateSet set{h->attr_col[attr], slot, MLVDB_ATTR_INT64, MLVDB_SET_ASSIGN};
     int64_t refused = 0;
@@ -4340,10 +4365,8 @@ int mlvdb_attr_list_update_where(mlvdb_index* h, const mlvdb_where* where, int32
 }
 
 int mlvdb_attr_list_stats(mlvdb_index* h, int32_t attr, int64_t* pool_used, int64_t* pool_live) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if ((rc = attr_check(h, attr))) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = attr_check(h, attr)) return rc;
     if (!pooled(h->attr_type[attr])) return fail(h, MLVDB_ERR_INVALID_ARG, "not a list, sparse or bits column");
     if (!pool_used || !pool_live) return fail(h, MLVDB_ERR_INVALID_ARG, "null counter");
     *pool_used = h->list_used[attr];
@@ -4353,29 +4376,23 @@ int mlvdb_attr_list_stats(mlvdb_index* h, int32_t attr, int64_t* pool_used, int6
 
 int mlvdb_facet_list_values(mlvdb_index* h, int32_t attr, const mlvdb_where* where, int64_t max_values, int64_t* out_values,
                             int64_t* out_counts, int64_t* n_values, int64_t* matched, int64_t* absent) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = list_attr_check(h, attr))) return rc;
+    if (int rc = list_attr_check(h, attr)) return rc;
     if (max_values < 1 || max_values > MLVDB_FACET_MAX_VALUES)
         return fail(h, MLVDB_ERR_INVALID_ARG, "max_values must be in 1..MLVDB_FACET_MAX_VALUES");
     if (!out_values || !out_counts || !n_values || !matched || !absent) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (where && (rc = where_prepare(h, where))) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
     *n_values = *matched = *absent = 0;
     if (h->total == 0) return MLVDB_OK;
-    return facet_list_values_impl(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent);
+    return facet_values_run(h, attr, where, max_values, out_values, out_counts, n_values, matched, absent, true);
     });
 }
 
 // ---- sparse vector columns (mlvdb_sparse.h)
 extern "C++" {
 namespace {
-int sparse_attr_check(mlvdb_index* h, int32_t attr) {
-    if (int rc = attr_check(h, attr)) return rc;
-    if (h->attr_type[attr] != MLVDB_ATTR_SPARSE) return fail(h, MLVDB_ERR_INVALID_ARG, "not a sparse column");
-    return MLVDB_OK;
-}
+int sparse_attr_check(mlvdb_index* h, int32_t attr) { return typed_attr_check(h, attr, MLVDB_ATTR_SPARSE, "not a sparse column"); }
 
 // One sparse vector: at most max_len entries, terms in [0, 2^31) strictly ascending, weights finite.
 int sparse_vector_check(mlvdb_index* h, const int32_t* terms, const float* weights, int64_t len, int64_t max_len) {
@@ -4412,6 +4429,19 @@ int sparse_csr_pack(mlvdb_index* h, int64_t n, const int64_t* offsets, const int
     }
     rebased.resize((size_t)n + 1);
     for (int64_t i = 0; i <= n; ++i) rebased[(size_t)i] = offsets[i] - base;
+    return MLVDB_OK;
+}
+
+// The CSR of a call's sparse queries (q_offsets[0] == 0 checked by the caller): every query a sparse vector of at most
+// MLVDB_SPARSE_MAX_QUERY_TERMS entries.
+int sparse_queries_check(mlvdb_index* h, int64_t nq, const int64_t* q_offsets, const int32_t* q_terms, const float* q_weights) {
+    for (int64_t i = 0; i < nq; ++i) {
+        const int64_t len = q_offsets[i + 1] - q_offsets[i];
+        const bool have = len > 0 && q_terms && q_weights;
+        if (int rc = sparse_vector_check(h, have ? q_terms + q_offsets[i] : nullptr, have ? q_weights + q_offsets[i] : nullptr, len,
+                                         MLVDB_SPARSE_MAX_QUERY_TERMS))
+            return rc;
+    }
     return MLVDB_OK;
 }
 
@@ -4453,17 +4483,21 @@ int sparse_pass_device(mlvdb_index* h, int32_t attr, const int64_t* off, const i
     const int32_t ntiles = (int32_t)tiles.size();
     const size_t nk = (size_t)n * k;
     const int32_t nblk = sparse_scan_blocks(h->total, n, k);
-    // [tiles | U | W], all 4-byte fields
-    const size_t tbytes = tiles.size() * sizeof(SparseTile), ubytes = U.size() * sizeof(int32_t), wbytes = W.size() * sizeof(float);
-    HIP_TRY(h, h->sparse_in.ensure(tbytes + ubytes + wbytes + 16));
+    SparseTile* tiles_d = nullptr;
+    int32_t* U_d = nullptr;
+    float* W_d = nullptr;
+    CARVE(h, h->sparse_in, [&](Carver& c) {
+        tiles_d = c.take<SparseTile>(tiles.size());
+        U_d = c.take<int32_t>(U.size());
+        W_d = c.take<float>(W.size());
+        c.take<char>(16);  // slack
+    });
     HIP_TRY(h, h->partial.ensure(nk * (size_t)nblk * sizeof(TopEntry)));
-    char* in = h->sparse_in.as<char>();
-    HIP_TRY(h, hipMemcpyAsync(in, tiles.data(), tbytes, hipMemcpyHostToDevice, s));
-    if (ubytes) HIP_TRY(h, hipMemcpyAsync(in + tbytes, U.data(), ubytes, hipMemcpyHostToDevice, s));
-    if (wbytes) HIP_TRY(h, hipMemcpyAsync(in + tbytes + ubytes, W.data(), wbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_sparse_scan(h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total,
-                                  reinterpret_cast<const SparseTile*>(in), ntiles, reinterpret_cast<const int32_t*>(in + tbytes),
-                                  reinterpret_cast<const float*>(in + tbytes + ubytes), k, nblk, h->partial.as<TopEntry>(), s));
+    HIP_TRY(h, hipMemcpyAsync(tiles_d, tiles.data(), tiles.size() * sizeof(SparseTile), hipMemcpyHostToDevice, s));
+    if (!U.empty()) HIP_TRY(h, hipMemcpyAsync(U_d, U.data(), U.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (!W.empty()) HIP_TRY(h, hipMemcpyAsync(W_d, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_sparse_scan(h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total, tiles_d, ntiles, U_d, W_d, k, nblk,
+                                  h->partial.as<TopEntry>(), s));
     HIP_TRY(h, launch_sparse_merge(h->partial.as<TopEntry>(), n, nblk, k, o.lab, o.dist, o.cnt, o.d64, s));
     HIP_TRY(h, hipStreamSynchronize(s));  // (the host vectors above are consumed by now)
     return MLVDB_OK;
@@ -4476,8 +4510,8 @@ int sparse_pass(mlvdb_index* h, int32_t attr, const int64_t* off, const int32_t*
     hipStream_t s = h->stream;
     const int32_t n = (int32_t)(q1 - q0);
     const size_t nk = (size_t)n * k;
-    HIP_TRY(h, h->sparse_out.ensure(ListBlock::bytes(nk, (size_t)n)));
-    const ListBlock o(h->sparse_out.p, nk, (size_t)n);
+    ListBlock o;
+    if (int rc = carve_list(h, h->sparse_out, nk, (size_t)n, o)) return rc;
     if (int rc = sparse_pass_device(h, attr, off, terms, weights, q0, q1, k, mask, o)) return rc;
     const size_t at = (size_t)q0 * k;
     return copy_down(h, s, {{out_labels, at, o.lab, nk}, {out_score, at, o.dist, nk}, {out_counts, (size_t)q0, o.cnt, (size_t)n},
@@ -4488,43 +4522,35 @@ int sparse_pass(mlvdb_index* h, int32_t attr, const int64_t* off, const int32_t*
 
 int mlvdb_sparse_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, const int64_t* offsets, const int32_t* terms,
                      const float* weights, const uint8_t* present) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = sparse_attr_check(h, attr))) return rc;
-    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (int rc = sparse_attr_check(h, attr)) return rc;
+    if (int rc = check_row_range(h, first, n)) return rc;
     if (n == 0) return MLVDB_OK;
     std::vector<int64_t> packed, rebased;
-    if ((rc = sparse_csr_pack(h, n, offsets, terms, weights, present, packed, rebased))) return rc;
+    if (int rc = sparse_csr_pack(h, n, offsets, terms, weights, present, packed, rebased)) return rc;
     return list_set_impl(h, attr, first, n, rebased.data(), packed.data(), present);
     });
 }
 
 int mlvdb_sparse_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, const int64_t* offsets,
                         const int32_t* terms, const float* weights, const uint8_t* present, int64_t* updated) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = sparse_attr_check(h, attr))) return rc;
-    if (!updated || n < 0 || (n > 0 && !labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n");
-    *updated = 0;
-    if (n == 0) return MLVDB_OK;
-    if ((rc = labels_check(h, labels, n))) return rc;
-    std::vector<int64_t> packed, rebased;
-    if ((rc = sparse_csr_pack(h, n, offsets, terms, weights, present, packed, rebased))) return rc;
-    return list_set_at_impl(h, attr, labels, n, rebased.data(), packed.data(), present, updated);
+    if (int rc = sparse_attr_check(h, attr)) return rc;
+    return with_labels(h, labels, n, updated, true, "bad labels / n", [&]() -> int {
+        std::vector<int64_t> packed, rebased;
+        if (int rc = sparse_csr_pack(h, n, offsets, terms, weights, present, packed, rebased)) return rc;
+        return list_set_at_impl(h, attr, labels, n, rebased.data(), packed.data(), present, updated);
+    });
     });
 }
 
 int mlvdb_sparse_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int64_t* out_offsets, int32_t* out_terms,
                      float* out_weights, uint8_t* out_present, int64_t capacity, int64_t* needed) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if ((rc = sparse_attr_check(h, attr))) return rc;
-    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = sparse_attr_check(h, attr)) return rc;
+    if (int rc = check_row_range(h, first, n)) return rc;
     if (!needed || !out_offsets || capacity < 0 || (capacity > 0 && (!out_terms || !out_weights)))
         return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
     *needed = 0;
@@ -4533,10 +4559,10 @@ int mlvdb_sparse_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int
         return MLVDB_OK;
     }
     // the list read-back into a buffer of exactly the size its first launches report, then unpacked
-    if ((rc = list_scan(h, h->attr_col[attr] + first, nullptr, n, needed))) return rc;
+    if (int rc = list_scan(h, h->attr_col[attr] + first, nullptr, n, needed)) return rc;
     if (capacity < *needed) return MLVDB_OK;
     std::vector<int64_t> packed((size_t)*needed);
-    if ((rc = list_get_impl(h, attr, first, n, out_offsets, packed.data(), out_present, *needed, needed))) return rc;
+    if (int rc = list_get_impl(h, attr, first, n, out_offsets, packed.data(), out_present, *needed, needed)) return rc;
     for (size_t j = 0; j < packed.size(); ++j) {
         out_terms[j] = (int32_t)(packed[j] >> 32);
         const uint32_t bits = (uint32_t)(packed[j] & 0xffffffffll);
@@ -4549,44 +4575,28 @@ int mlvdb_sparse_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int
 int mlvdb_search_batch_sparse(mlvdb_index* h, int32_t attr, const int64_t* q_offsets, const int32_t* q_terms,
                               const float* q_weights, int64_t nq, int32_t k, const mlvdb_where* where, int64_t* out_labels,
                               float* out_score, int32_t* out_counts, double* out_score64) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked on the host before anything is launched
-    if ((rc = sparse_attr_check(h, attr))) return rc;
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
-    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "sparse search: k above MLVDB_MAX_TOPK");
+    if (int rc = sparse_attr_check(h, attr)) return rc;
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max(h, k, "sparse search: ")) return rc;
     if (nq > 0 && (!q_offsets || !out_labels || !out_score || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     if (nq > 0 && q_offsets[0] != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "sparse search: q_offsets must start at 0");
-    for (int64_t i = 0; i < nq; ++i) {
-        const int64_t len = q_offsets[i + 1] - q_offsets[i];
-        const bool have = len > 0 && q_terms && q_weights;
-        if ((rc = sparse_vector_check(h, have ? q_terms + q_offsets[i] : nullptr, have ? q_weights + q_offsets[i] : nullptr, len,
-                                      MLVDB_SPARSE_MAX_QUERY_TERMS)))
-            return rc;
-    }
-    if (h->total > INT32_MAX) return fail(h, MLVDB_ERR_UNSUPPORTED, "sparse search: more than 2^31 - 1 rows");
-    if (where && (rc = where_prepare(h, where))) return rc;
+    if (int rc = sparse_queries_check(h, nq, q_offsets, q_terms, q_weights)) return rc;
+    if (int rc = check_row_limit(h, "sparse search: ")) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
     if (nq == 0) return MLVDB_OK;
     if (h->total == 0) {
-        for (int64_t i = 0; i < nq * k; ++i) {
-            out_labels[i] = -1;
-            out_score[i] = -__builtin_inff();
-            if (out_score64) out_score64[i] = -__builtin_inf();
-        }
-        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        pad_outputs(out_labels, out_score, out_score64, nq * k, out_counts, nq, -1.0f);  // scores: -inf
         return MLVDB_OK;
     }
-    const uint8_t* mask = nullptr;
-    if (where) {  // the program into h->row_mask (live matching rows), which every pass reads at one byte per row
-        if ((rc = where_run(h, where, nullptr))) return rc;
-        mask = h->row_mask.as<uint8_t>();
-    }
+    const uint8_t* mask = nullptr;  // the program's live matching rows, which every pass reads at one byte per row
+    if (int rc = where_mask(h, where, &mask)) return rc;
     for (int64_t q0 = 0; q0 < nq; q0 += kSparseChunk) {
         const int64_t q1 = std::min<int64_t>(nq, q0 + kSparseChunk);
-        if ((rc = sparse_pass(h, attr, q_offsets, q_terms, q_weights, q0, q1, k, mask, out_labels, out_score, out_counts,
-                              out_score64)))
+        if (int rc = sparse_pass(h, attr, q_offsets, q_terms, q_weights, q0, q1, k, mask, out_labels, out_score, out_counts,
+                              out_score64))
             return rc;
     }
     return MLVDB_OK;
@@ -4596,11 +4606,7 @@ int mlvdb_search_batch_sparse(mlvdb_index* h, int32_t attr, const int64_t* q_off
 // ---- binary vector columns (mlvdb_bits.h)
 extern "C++" {
 namespace {
-int bits_attr_check(mlvdb_index* h, int32_t attr) {
-    if (int rc = attr_check(h, attr)) return rc;
-    if (h->attr_type[attr] != MLVDB_ATTR_BITS) return fail(h, MLVDB_ERR_INVALID_ARG, "not a bits column");
-    return MLVDB_OK;
-}
+int bits_attr_check(mlvdb_index* h, int32_t attr) { return typed_attr_check(h, attr, MLVDB_ATTR_BITS, "not a bits column"); }
 
 int bits_words_check(mlvdb_index* h, int32_t words) {
     if (words < 1 || words > MLVDB_BITS_MAX_WORDS) return fail(h, MLVDB_ERR_INVALID_ARG, "words must be in 1..MLVDB_BITS_MAX_WORDS");
@@ -4631,17 +4637,18 @@ int bits_pass(mlvdb_index* h, int32_t attr, const uint64_t* queries, int64_t q0,
     for (int32_t i = 0; i < n; ++i)
         for (int32_t w = 0; w < words; ++w) qpop[(size_t)i] += __builtin_popcountll(q[(size_t)i * words + w]);
     const int32_t nblk = bits_scan_blocks(h->total, n, k, words);
-    // [queries | popcounts]
-    const size_t qbytes = (size_t)n * words * sizeof(uint64_t), pbytes = (size_t)n * sizeof(int32_t);
-    HIP_TRY(h, h->bits_in.ensure(qbytes + pbytes));
+    uint64_t* q_d = nullptr;
+    int32_t* qpop_d = nullptr;
+    CARVE(h, h->bits_in, [&](Carver& c) {
+        q_d = c.take<uint64_t>((size_t)n * words);
+        qpop_d = c.take<int32_t>((size_t)n);
+    });
     HIP_TRY(h, h->partial.ensure(nk * (size_t)nblk * sizeof(TopEntry)));
-    HIP_TRY(h, h->bits_out.ensure(ListBlock::bytes(nk, (size_t)n)));
-    const ListBlock o(h->bits_out.p, nk, (size_t)n);
-    char* in = h->bits_in.as<char>();
-    HIP_TRY(h, hipMemcpyAsync(in, q, qbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(in + qbytes, qpop.data(), pbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, launch_bits_scan(h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total, reinterpret_cast<const uint64_t*>(in),
-                                reinterpret_cast<const int32_t*>(in + qbytes), n, words, metric, k, nblk,
+    ListBlock o;
+    if (int rc = carve_list(h, h->bits_out, nk, (size_t)n, o)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(q_d, q, (size_t)n * words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(qpop_d, qpop.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_bits_scan(h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total, q_d, qpop_d, n, words, metric, k, nblk,
                                 h->partial.as<TopEntry>(), s));
     HIP_TRY(h, launch_exact_merge(h->partial.as<TopEntry>(), n, nullptr, nullptr, nblk, k, o.lab, o.dist, o.cnt, o.d64, s));
     const size_t at = (size_t)q0 * k;
@@ -4654,13 +4661,11 @@ int bits_pass(mlvdb_index* h, int32_t attr, const uint64_t* queries, int64_t q0,
 
 int mlvdb_bits_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int32_t words, const uint64_t* codes,
                    const uint8_t* present) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = bits_attr_check(h, attr))) return rc;
-    if ((rc = bits_words_check(h, words))) return rc;
-    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    if (int rc = bits_attr_check(h, attr)) return rc;
+    if (int rc = bits_words_check(h, words)) return rc;
+    if (int rc = check_row_range(h, first, n)) return rc;
     if (n == 0) return MLVDB_OK;
     if (!codes) return fail(h, MLVDB_ERR_INVALID_ARG, "codes is null");
     std::vector<int64_t> packed, offsets;
@@ -4671,17 +4676,15 @@ int mlvdb_bits_set(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int32
 
 int mlvdb_bits_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64_t n, int32_t words, const uint64_t* codes,
                       const uint8_t* present, int64_t* updated) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked before anything is launched
-    if ((rc = bits_attr_check(h, attr))) return rc;
-    if ((rc = bits_words_check(h, words))) return rc;
+    if (int rc = bits_attr_check(h, attr)) return rc;
+    if (int rc = bits_words_check(h, words)) return rc;
     if (!updated || n < 0 || (n > 0 && !labels)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad labels / n");
     *updated = 0;
     if (n == 0) return MLVDB_OK;
     if (!codes) return fail(h, MLVDB_ERR_INVALID_ARG, "codes is null");
-    if ((rc = labels_check(h, labels, n))) return rc;
+    if (int rc = labels_check(h, labels, n)) return rc;
     std::vector<int64_t> packed, offsets;
     bits_csr_pack(n, words, codes, present, packed, offsets);
     return list_set_at_impl(h, attr, labels, n, offsets.data(), packed.data(), present, updated);
@@ -4690,21 +4693,19 @@ int mlvdb_bits_set_at(mlvdb_index* h, int32_t attr, const int64_t* labels, int64
 
 int mlvdb_bits_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int32_t* out_words, uint64_t* out_codes,
                    int64_t capacity, int64_t* needed) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if ((rc = bits_attr_check(h, attr))) return rc;
-    if (first < 0 || n < 0 || first > h->total || n > h->total - first) return fail(h, MLVDB_ERR_INVALID_ARG, "row range out of bounds");
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = bits_attr_check(h, attr)) return rc;
+    if (int rc = check_row_range(h, first, n)) return rc;
     if (!needed || capacity < 0 || (n > 0 && !out_words) || (capacity > 0 && !out_codes))
         return fail(h, MLVDB_ERR_INVALID_ARG, "bad output buffers");
     *needed = 0;
     if (n == 0) return MLVDB_OK;
     // the list read-back: a row's width is the length of its range, 0 for an absent row (a present code has >= 1 word)
-    if ((rc = list_scan(h, h->attr_col[attr] + first, nullptr, n, needed))) return rc;
+    if (int rc = list_scan(h, h->attr_col[attr] + first, nullptr, n, needed)) return rc;
     if (capacity < *needed) return MLVDB_OK;
     std::vector<int64_t> offsets((size_t)n + 1);
     static_assert(sizeof(uint64_t) == sizeof(int64_t), "the codes are read back as the pool's elements");
-    if ((rc = list_get_impl(h, attr, first, n, offsets.data(), reinterpret_cast<int64_t*>(out_codes), nullptr, *needed, needed)))
+    if (int rc = list_get_impl(h, attr, first, n, offsets.data(), reinterpret_cast<int64_t*>(out_codes), nullptr, *needed, needed))
         return rc;
     for (int64_t i = 0; i < n; ++i) out_words[i] = (int32_t)(offsets[(size_t)i + 1] - offsets[(size_t)i]);
     return MLVDB_OK;
@@ -4714,37 +4715,27 @@ int mlvdb_bits_get(mlvdb_index* h, int32_t attr, int64_t first, int64_t n, int32
 int mlvdb_search_batch_bits(mlvdb_index* h, int32_t attr, const uint64_t* queries, int64_t nq, int32_t words, int32_t metric,
                             int32_t k, const mlvdb_where* where, int64_t* out_labels, float* out_dist, int32_t* out_counts,
                             double* out_dist64) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked on the host before anything is launched
-    if ((rc = bits_attr_check(h, attr))) return rc;
-    if ((rc = bits_words_check(h, words))) return rc;
+    if (int rc = bits_attr_check(h, attr)) return rc;
+    if (int rc = bits_words_check(h, words)) return rc;
     if (metric != MLVDB_BITS_HAMMING && metric != MLVDB_BITS_JACCARD) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown bits metric");
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
-    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "bits search: k above MLVDB_MAX_TOPK");
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max(h, k, "bits search: ")) return rc;
     if (nq > 0 && (!queries || !out_labels || !out_dist || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
-    if (h->total > INT32_MAX) return fail(h, MLVDB_ERR_UNSUPPORTED, "bits search: more than 2^31 - 1 rows");
-    if (where && (rc = where_prepare(h, where))) return rc;
+    if (int rc = check_row_limit(h, "bits search: ")) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
     if (nq == 0) return MLVDB_OK;
     if (h->total == 0) {
-        for (int64_t i = 0; i < nq * k; ++i) {
-            out_labels[i] = -1;
-            out_dist[i] = __builtin_inff();
-            if (out_dist64) out_dist64[i] = __builtin_inf();
-        }
-        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        pad_outputs(out_labels, out_dist, out_dist64, nq * k, out_counts, nq);
         return MLVDB_OK;
     }
-    const uint8_t* mask = nullptr;
-    if (where) {  // the program into h->row_mask (live matching rows), which every pass reads at one byte per row
-        if ((rc = where_run(h, where, nullptr))) return rc;
-        mask = h->row_mask.as<uint8_t>();
-    }
+    const uint8_t* mask = nullptr;  // the program's live matching rows, which every pass reads at one byte per row
+    if (int rc = where_mask(h, where, &mask)) return rc;
     for (int64_t q0 = 0; q0 < nq; q0 += kBitsChunk) {
         const int64_t q1 = std::min<int64_t>(nq, q0 + kBitsChunk);
-        if ((rc = bits_pass(h, attr, queries, q0, q1, words, metric, k, mask, out_labels, out_dist, out_counts, out_dist64)))
+        if (int rc = bits_pass(h, attr, queries, q0, q1, words, metric, k, mask, out_labels, out_dist, out_counts, out_dist64))
             return rc;
     }
     return MLVDB_OK;
@@ -4766,13 +4757,13 @@ int hybrid_impl(mlvdb_index* h, const float* queries, int32_t attr, const int64_
                 double* out_dist64, double* out_sparse64, int32_t* out_rank_dense, int32_t* out_rank_sparse) {
     hipStream_t s = h->stream;
     if (h->total == 0 || h->total == h->deleted) {
-        std::fill(out_labels, out_labels + nq * k, (int64_t)-1);
-        std::fill(out_fused, out_fused + nq * k, -__builtin_inf());
-        std::fill(out_counts, out_counts + nq, 0);
-        if (out_dist64) std::fill(out_dist64, out_dist64 + nq * k, __builtin_inf());
-        if (out_sparse64) std::fill(out_sparse64, out_sparse64 + nq * k, -__builtin_inf());
-        if (out_rank_dense) std::fill(out_rank_dense, out_rank_dense + nq * k, -1);
-        if (out_rank_sparse) std::fill(out_rank_sparse, out_rank_sparse + nq * k, -1);
+        pad(out_labels, nq * k, -1);
+        pad(out_fused, nq * k, -__builtin_inf());
+        pad(out_counts, nq, 0);
+        pad(out_dist64, nq * k, __builtin_inf());
+        pad(out_sparse64, nq * k, -__builtin_inf());
+        pad(out_rank_dense, nq * k, -1);
+        pad(out_rank_sparse, nq * k, -1);
         return MLVDB_OK;
     }
     const bool complete = method != MLVDB_FUSE_RRF || out_dist64 || out_sparse64;
@@ -4781,39 +4772,50 @@ int hybrid_impl(mlvdb_index* h, const float* queries, int32_t attr, const int64_
     for (int64_t q0 = 0; q0 < nq; q0 += kHybridChunk) {
         const int32_t n = (int32_t)std::min<int64_t>(kHybridChunk, nq - q0);
         const size_t nk = (size_t)n * k, nm = (size_t)n * m, nt = (size_t)(off[q0 + n] - off[q0]);
-        const size_t dbytes = (ListBlock::bytes((size_t)n * fd, (size_t)n) + 7) & ~(size_t)7;
-        HIP_TRY(h, h->hyb_q.ensure(((size_t)n + 1) * sizeof(int64_t) + (size_t)n * sizeof(double) +
-                                   (size_t)n * (h->dim + h->ld) * sizeof(float) + nt * (sizeof(int32_t) + sizeof(float)) + 16));
-        HIP_TRY(h, h->hyb_list.ensure(dbytes + ListBlock::bytes((size_t)n * fs, (size_t)n)));
-        HIP_TRY(h, h->hyb_union.ensure(nm * (2 * sizeof(double) + 3 * sizeof(int64_t) + 2 * sizeof(int32_t)) +
-                                       (size_t)n * sizeof(int32_t)));
-        HIP_TRY(h, h->hyb_out.ensure(nk * (3 * sizeof(double) + sizeof(int64_t) + 2 * sizeof(int32_t)) + (size_t)n * sizeof(int32_t)));
-        Carver in{h->hyb_q.as<char>()};  // [offsets | qaux | queries | padded queries | terms | weights]
-        int64_t* d_off = in.take<int64_t>((size_t)n + 1);
-        double* d_aux = in.take<double>((size_t)n);
-        float* dq = in.take<float>((size_t)n * h->dim);
-        float* d_pad = in.take<float>((size_t)n * h->ld);
-        int32_t* d_terms = in.take<int32_t>(nt);
-        float* d_weights = in.take<float>(nt);
-        const ListBlock ld(h->hyb_list.p, (size_t)n * fd, (size_t)n);
-        const ListBlock ls(h->hyb_list.as<char>() + dbytes, (size_t)n * fs, (size_t)n);
-        Carver un{h->hyb_union.as<char>()};  // [comp_d | comp_s | labels | need_d | need_s | rank_D | rank_S | counts]
-        double* comp_d = un.take<double>(nm);
-        double* comp_s = un.take<double>(nm);
-        int64_t* u_lab = un.take<int64_t>(nm);
-        int64_t* need_d = un.take<int64_t>(nm);
-        int64_t* need_s = un.take<int64_t>(nm);
-        int32_t* u_rd = un.take<int32_t>(nm);
-        int32_t* u_rs = un.take<int32_t>(nm);
-        int32_t* u_cnt = un.take<int32_t>((size_t)n);
-        Carver out{h->hyb_out.as<char>()};  // [fused | d64 | s64 | labels | rank_D | rank_S | counts]
-        double* o_fused = out.take<double>(nk);
-        double* o_d64 = out.take<double>(nk);
-        double* o_s64 = out.take<double>(nk);
-        int64_t* o_lab = out.take<int64_t>(nk);
-        int32_t* o_rd = out.take<int32_t>(nk);
-        int32_t* o_rs = out.take<int32_t>(nk);
-        int32_t* o_cnt = out.take<int32_t>((size_t)n);
+        int64_t* d_off = nullptr;  // the chunk's sparse queries (offsets, terms, weights) and its dense ones, raw and prepared
+        double* d_aux = nullptr;
+        float *dq = nullptr, *d_pad = nullptr, *d_weights = nullptr;
+        int32_t* d_terms = nullptr;
+        CARVE(h, h->hyb_q, [&](Carver& c) {
+            d_off = c.take<int64_t>((size_t)n + 1);
+            d_aux = c.take<double>((size_t)n);
+            dq = c.take<float>((size_t)n * h->dim);
+            d_pad = c.take<float>((size_t)n * h->ld);
+            d_terms = c.take<int32_t>(nt);
+            d_weights = c.take<float>(nt);
+            c.take<char>(16);  // slack
+        });
+        ListBlock ld, ls;  // the two legs' ranked lists
+        CARVE(h, h->hyb_list, [&](Carver& c) {
+            ld.take(c, (size_t)n * fd, (size_t)n);
+            c.pad_to(8);
+            ls.take(c, (size_t)n * fs, (size_t)n);
+        });
+        double *comp_d = nullptr, *comp_s = nullptr;  // the union: completed components, labels, members to complete, ranks
+        int64_t *u_lab = nullptr, *need_d = nullptr, *need_s = nullptr;
+        int32_t *u_rd = nullptr, *u_rs = nullptr, *u_cnt = nullptr;
+        CARVE(h, h->hyb_union, [&](Carver& c) {
+            comp_d = c.take<double>(nm);
+            comp_s = c.take<double>(nm);
+            u_lab = c.take<int64_t>(nm);
+            need_d = c.take<int64_t>(nm);
+            need_s = c.take<int64_t>(nm);
+            u_rd = c.take<int32_t>(nm);
+            u_rs = c.take<int32_t>(nm);
+            u_cnt = c.take<int32_t>((size_t)n);
+        });
+        double *o_fused = nullptr, *o_d64 = nullptr, *o_s64 = nullptr;
+        int64_t* o_lab = nullptr;
+        int32_t *o_rd = nullptr, *o_rs = nullptr, *o_cnt = nullptr;
+        CARVE(h, h->hyb_out, [&](Carver& c) {
+            o_fused = c.take<double>(nk);
+            o_d64 = c.take<double>(nk);
+            o_s64 = c.take<double>(nk);
+            o_lab = c.take<int64_t>(nk);
+            o_rd = c.take<int32_t>(nk);
+            o_rs = c.take<int32_t>(nk);
+            o_cnt = c.take<int32_t>((size_t)n);
+        });
         roff.resize((size_t)n + 1);
         for (int32_t i = 0; i <= n; ++i) roff[(size_t)i] = off[q0 + i] - off[q0];
         // (the host arrays of these copies are consumed when sparse_pass_device returns: it drains the stream)
@@ -4853,14 +4855,12 @@ int mlvdb_search_batch_hybrid(mlvdb_index* h, const float* queries, int32_t attr
                               int32_t fetch_sparse, int32_t method, double w_dense, double w_sparse, double rrf_c,
                               const mlvdb_where* where, int64_t* out_labels, double* out_fused, int32_t* out_counts,
                               double* out_dist64, double* out_sparse64, int32_t* out_rank_dense, int32_t* out_rank_sparse) {
-    return guarded(h, [&]() -> int {
-    int rc = check_handle(h);
-    if (rc) return rc;
+    return guarded(h, kOnDevice, [&]() -> int {
     // everything is checked on the host before anything is launched (the program: with_where)
-    if ((rc = sparse_attr_check(h, attr))) return rc;
-    if (nq < 0 || nq > (1 << 24)) return fail(h, MLVDB_ERR_INVALID_ARG, "nq out of range");
-    if (k < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "k must be >= 1");
-    if (k > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "hybrid: k above MLVDB_MAX_TOPK");
+    if (int rc = sparse_attr_check(h, attr)) return rc;
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max(h, k, "hybrid: ")) return rc;
     if (fetch_dense < 1 || fetch_sparse < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: fetch_dense / fetch_sparse must be >= 1");
     if (fetch_dense > kHybridMaxFetchDense) return fail(h, MLVDB_ERR_UNSUPPORTED, "hybrid: fetch_dense above MLVDB_HYBRID_MAX_FETCH_DENSE");
     if (fetch_sparse > MLVDB_MAX_TOPK) return fail(h, MLVDB_ERR_UNSUPPORTED, "hybrid: fetch_sparse above MLVDB_MAX_TOPK");
@@ -4872,16 +4872,10 @@ int mlvdb_search_batch_hybrid(mlvdb_index* h, const float* queries, int32_t attr
     if (!(std::isfinite(rrf_c) && rrf_c >= 0.0)) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: the RRF constant must be finite and >= 0");
     if (nq > 0 && (!queries || !q_offsets || !out_labels || !out_fused || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     if (nq > 0 && q_offsets[0] != 0) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: q_offsets must start at 0");
-    for (int64_t i = 0; i < nq; ++i) {
-        const int64_t len = q_offsets[i + 1] - q_offsets[i];
-        const bool have = len > 0 && q_terms && q_weights;
-        if ((rc = sparse_vector_check(h, have ? q_terms + q_offsets[i] : nullptr, have ? q_weights + q_offsets[i] : nullptr, len,
-                                      MLVDB_SPARSE_MAX_QUERY_TERMS)))
-            return rc;
-    }
+    if (int rc = sparse_queries_check(h, nq, q_offsets, q_terms, q_weights)) return rc;
     for (int64_t i = 0; i < nq * h->dim; ++i)
         if (queries[i] != queries[i]) return fail(h, MLVDB_ERR_INVALID_ARG, "hybrid: a NaN in the dense queries");
-    if (h->total > INT32_MAX) return fail(h, MLVDB_ERR_UNSUPPORTED, "hybrid: more than 2^31 - 1 rows");
+    if (int rc = check_row_limit(h, "hybrid: ")) return rc;
     auto call = [&]() {
         // (under a program h->row_mask holds the one evaluation both legs read: the dense leg through the masked norms)
         const uint8_t* mask = where && h->total > 0 ? h->row_mask.as<uint8_t>() : nullptr;

@@ -102,28 +102,32 @@ struct Staged : Blocks {
     ~Staged() { (void)hipStreamSynchronize(stream); }
 };
 
-// A bump carver over one block of several arrays, a DevBuf's or its copy on the host: take<T>(n) is the next n values of T.
-// It pads nothing.  Every layout carved with it lists its 8-byte fields (double, int64) before its 4-byte ones (float,
-// int32) -- descending alignment -- so every field lies aligned whatever the counts are.
+// One block of several arrays, a DevBuf's or its copy on the host, stated once as a list of take<T>(n) calls: the next n
+// values of T.  The list runs twice -- over no block (base == nullptr) it only measures, `at` being the bytes the block
+// needs; over the block it hands out the fields.  A block's size is therefore never a formula of its own.  Nothing is
+// rounded silently: a field whose offset is no multiple of its alignment sets `misaligned`, which the caller reports before
+// any pointer is used; slack and alignment steps are written into the list (take<char>(16), pad_to(64)).
 struct Carver {
-    char* at;
+    char* base = nullptr;
+    size_t at = 0;
+    bool misaligned = false;
     template <class T>
     T* take(size_t n) {
-        T* first = reinterpret_cast<T*>(at);
+        misaligned |= at % alignof(T) != 0;
+        T* first = base ? reinterpret_cast<T*>(base + at) : nullptr;
         at += n * sizeof(T);
         return first;
     }
+    void pad_to(size_t align) { at = (at + align - 1) / align * align; }
 };
 
 // The layout most blocks have, [d64 | labels | dist | counts]: n entries and nq counts.
 struct ListBlock {
-    double* d64;
-    int64_t* lab;
-    float* dist;
-    int32_t* cnt;
-    static size_t bytes(size_t n, size_t nq) { return n * (sizeof(double) + sizeof(int64_t) + sizeof(float)) + nq * sizeof(int32_t); }
-    ListBlock(void* block, size_t n, size_t nq) {
-        Carver c{static_cast<char*>(block)};
+    double* d64 = nullptr;
+    int64_t* lab = nullptr;
+    float* dist = nullptr;
+    int32_t* cnt = nullptr;
+    void take(Carver& c, size_t n, size_t nq) {
         d64 = c.take<double>(n);
         lab = c.take<int64_t>(n);
         dist = c.take<float>(n);

@@ -155,6 +155,34 @@ int main() {
         CHECK(live == 2 && kept.a.bytes == 32 && one.p == nullptr);
     }
     CHECK(live == 0);
+    {  // a field list measures over no block (no pointer, no arithmetic on null) and carves over one: same offsets, same size
+        mlvdb::ListBlock a, b;
+        auto fields = [](mlvdb::Carver& c, mlvdb::ListBlock& l, mlvdb::ListBlock& m) {
+            l.take(c, 5, 3);  // 5 * (8 + 8 + 4) + 3 * 4 = 112 bytes
+            c.take<char>(3);
+            c.pad_to(8);      // 115 -> 120: the next block's doubles lie aligned
+            m.take(c, 2, 1);  // 2 * 20 + 4 = 44
+        };
+        mlvdb::Carver measure;
+        fields(measure, a, b);
+        CHECK(measure.at == 164 && !measure.misaligned);
+        CHECK(a.d64 == nullptr && a.lab == nullptr && a.dist == nullptr && a.cnt == nullptr && b.d64 == nullptr);
+        alignas(8) static char block[164];
+        mlvdb::Carver carve{block};
+        fields(carve, a, b);
+        CHECK(carve.at == measure.at && !carve.misaligned);
+        CHECK((char*)a.d64 == block && (char*)a.lab == block + 40 && (char*)a.dist == block + 80 && (char*)a.cnt == block + 100);
+        CHECK((char*)b.d64 == block + 120 && (char*)(b.cnt + 1) == block + 164);
+        b.cnt[0] = 7;  // the last field's last value is inside the block (ASan)
+        mlvdb::Carver odd;  // an 8-byte field behind an odd count of 4-byte ones: flagged, not rounded
+        odd.take<float>(3);
+        odd.take<double>(1);
+        CHECK(odd.misaligned && odd.at == 20);
+        mlvdb::Carver bytes;  // ... and a byte field needs no alignment
+        bytes.take<int64_t>(2);
+        bytes.take<unsigned char>(5);
+        CHECK(!bytes.misaligned && bytes.at == 21);
+    }
     if (failures) return 1;
     std::puts("device_memory ok");
     return 0;
