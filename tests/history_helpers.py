@@ -6,7 +6,8 @@ steps, running the model as it goes, and returns the ops with the model's answer
 one by one and compares every answer at once.  The ``wide`` and ``wide_large`` scales (``WideHistoryModel``, ``_WideGenerator``)
 do the same over the entry families added since -- ordered, diversified, grouped, by-example and late-interaction queries,
 updates and filtered deletes, list and sparse columns -- with op tuples, a program pool and schedules of their own, so that the
-first histories keep generating the op lists they always did.  Nothing here needs a GPU."""
+first histories keep generating the op lists they always did.  The ``recent`` scales (bits, geo, statistics, hybrid) live in
+tests/history_recent_helpers.py; ``call``, ``compare`` and ``_history`` dispatch there.  Nothing here needs a GPU."""
 from __future__ import annotations
 
 import functools
@@ -300,7 +301,16 @@ def call(e, op: dict, a: dict):
         return _refusal(e, op, a)
     if kind in _WIDE_CALLS:
         return _WIDE_CALLS[kind](e, op, a)
+    if kind in _recent().CALLS:
+        return _recent().CALLS[kind](e, op, a)
     raise ValueError(f"unknown op {kind!r}")
+
+
+def _recent():
+    """tests/history_recent_helpers.py: the ops of the third wave (it imports this module: looked up when first needed)."""
+    from tests import history_recent_helpers
+
+    return history_recent_helpers
 
 
 def _status_of(err):
@@ -411,6 +421,8 @@ def compare(e, op, a, got, want, tag, stats):
         assert tuple(got) == tuple(want), f"{tag}: counts {got}, the model {want}"
     elif kind == "refuse":
         assert tuple(got) == tuple(want), f"{tag}: {got}, the model {want}"
+    elif kind in _recent().CALLS:
+        _recent().compare(e, op, a, got, want, tag, stats)
     else:
         assert got is None and want is None, f"{tag}: returned {got!r}"
 
@@ -1834,7 +1846,10 @@ class _WideGenerator(_Generator):
 
 @functools.lru_cache(maxsize=None)
 def _history(seed, space, d, scale):
-    g = (_WideGenerator if scale in WIDE_SCALES else _Generator)(seed, space, d, scale)
+    if scale in _recent().RECENT_SCALES:
+        g = _recent()._RecentGenerator(seed, space, d, scale)
+    else:
+        g = (_WideGenerator if scale in WIDE_SCALES else _Generator)(seed, space, d, scale)
     getattr(g, scale)()
     return g
 

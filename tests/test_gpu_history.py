@@ -1,5 +1,6 @@
 """Seeded call histories on ONE ``HipScanEngine`` handle from creation to close, against the NumPy model of the whole engine
-(tests/history_helpers.py; the coverage the committed seed set reaches is asserted without a GPU in tests/test_history_host.py).
+(tests/history_helpers.py, tests/history_recent_helpers.py; the coverage the committed seed sets reach is asserted without a
+GPU in tests/test_history_host.py).
 Every answer is compared at once: labels, counts, groups, facet and bin counts exactly, distances by the suite's bars.  A
 mismatch leaves history_<tag>.json (the ops up to the failing step) in the mismatch directory of tests/conftest.py and the
 arrays beside it, names seed, step and op, and starts nothing more on the device but ``close()``."""
@@ -8,6 +9,7 @@ import pytest
 from mlvectordb_amd.engine import HipScanEngine
 from mlvectordb_amd.multi_device import MultiDeviceEngine
 from tests import history_helpers as H
+from tests import history_recent_helpers as R
 
 pytestmark = pytest.mark.gpu
 
@@ -80,4 +82,44 @@ def test_wide_large_history_moves_the_inner_searches_between_the_routes(key):
     """Past 32,768 rows `auto` itself takes the filter route inside search_mmr / search_like / search_grouped and the tag-filtered
     search_each at nq = 12 and 40; a ``tombstone_where`` of about a third of the rows and a compaction bring it back; growth again."""
     seed, space, d, _ = key
+    _replay(key, lambda: HipScanEngine(d, space, device=0))
+
+
+@pytest.mark.parametrize("key", R.RECENT, ids=lambda key: H.history_tag(*key))
+def test_recent_history_equals_the_model_at_every_step(key):
+    """Binary vectors, geo columns, attribute statistics and hybrid search on one handle with every mutation of the wide wave
+    (tests/history_recent_helpers.py): the bits pool regrown, repacked and reset, rows rewritten at another width, hybrid on
+    the filter route and at paged depths across compactions, ``geo_nearest`` and ``where_ordered`` in one workspace,
+    ``attr_stats`` at a small ``max_groups`` after a large one, masked calls before unmasked ones."""
+    seed, space, d, _ = key
+    print(f"history {H.history_tag(*key)}: distance bar {R.geo_bar(*key):.3e}")
+    _replay(key, lambda: HipScanEngine(d, space, device=0))
+
+
+def test_an_index_outlives_a_destroyed_neighbour_that_used_the_recent_workspaces():
+    """Engine B is opened first; engine A replays the first recent history -- the hybrid, bits, statistics and ordering
+    workspaces among the rest -- and is closed, which frees all of it; then B replays the second one and equals the model at
+    every step."""
+    key_a, key_b = R.RECENT[0], R.RECENT[1]
+    ops_a, expected_a = H.make_history(*key_a)
+    ops_b, expected_b = H.make_history(*key_b)
+    b = HipScanEngine(key_b[2], key_b[1], device=0)
+    try:
+        a = HipScanEngine(key_a[2], key_a[1], device=0)
+        try:
+            assert H.run_history(a, ops_a, expected_a, "neighbour_" + H.history_tag(*key_a))["steps"] == len(ops_a)
+        finally:
+            a.close()
+        assert H.run_history(b, ops_b, expected_b, "survivor_" + H.history_tag(*key_b))["steps"] == len(ops_b)
+    finally:
+        b.close()
+
+
+@pytest.mark.parametrize("key", R.RECENT_LARGE, ids=lambda key: H.history_tag(*key))
+def test_recent_large_history_moves_the_dense_leg_of_hybrid_between_the_routes(key):
+    """Past 32,768 rows `auto` itself takes the filter route inside ``search_hybrid`` at nq = 12 and 40 with fetch_dense <= 64;
+    fetch_dense = 65 and 1024 on each side; a ``tombstone_where`` of about a third of the rows through a geo box and a
+    compaction bring it back; growth again."""
+    seed, space, d, _ = key
+    print(f"history {H.history_tag(*key)}: distance bar {R.geo_bar(*key):.3e}")
     _replay(key, lambda: HipScanEngine(d, space, device=0))

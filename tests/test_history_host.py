@@ -1,7 +1,8 @@
 """The seeded call histories of tests/history_helpers.py without a GPU: they are deterministic, the first ones are pinned by the
 sha256 of their op lists, the models agree with the oracle engines they are composed from, the committed seed sets meet every
-coverage condition (a to j for the first histories, k to w for the wide ones; each printed with the seed and step that meets
-it), the driver reports three plus five seeded stale-state defects, and near-tie redraws stay under 1 % of the drawn queries."""
+coverage condition (a to j for the first histories, k to w for the wide ones, ``RECENT_WANTED`` for the recent ones of
+tests/history_recent_helpers.py; each printed with the seed and step that meets it), the driver reports three plus five plus
+six seeded stale-state defects, and near-tie and guard redraws stay under 1 % of the drawn queries."""
 import hashlib
 import json
 
@@ -938,11 +939,628 @@ def test_the_driver_reports_a_seeded_defect_in_the_wide_histories(defect, tmp_pa
     assert reported >= 2, f"{defect.__name__}: reported in {reported} of 4 histories"
 
 
+
+
+# ================================================================ the recent histories: bits, geo, stats and hybrid on one handle
+from mlvectordb_amd import _native  # noqa: E402
+from mlvectordb_amd.engine import StatsOverflow  # noqa: E402
+from tests import geo_helpers as GH  # noqa: E402
+from tests import history_recent_helpers as R  # noqa: E402
+
+GEO_OPS = (W.GEO_BOX, W.GEO_RADIUS)
+
+
+def leaf_on(op, attr, kinds):
+    return any(o[0] in kinds and o[1] == attr for p in R.programs_of(op) for o in p["ops"])
+
+
+def test_the_recent_model_agrees_with_the_oracle_engines_it_is_composed_from():
+    """The same state -- two appends, every column valued, tombstones -- in ``RecentHistoryModel`` and in the bits, hybrid,
+    statistics and geo oracle engines; one call per new entry with a program, then what the model adds: the bits pool
+    mirrored, one ``match`` for list, geo and bits leaves together, the refusals with the status the headers name."""
+    from tests.bits_helpers import BitsOracleEngine
+    from tests.hybrid_helpers import HybridOracleEngine
+    from tests.sparse_helpers import random_corpus, sparse_csr
+    from tests.stats_helpers import StatsOracleEngine
+
+    rng = np.random.default_rng(11)
+    d, n = 12, 400
+    rows = rng.standard_normal((n, d), dtype=np.float32)
+    qs = rng.standard_normal((5, d), dtype=np.float32)
+    centre = R.CENTRES[0]
+    points = R.geo_values(np.random.default_rng(12), n, centre)
+    codes = R.bits_column(np.random.default_rng(13), n, R.WORDS, 0.1)
+    short = R.bits_column(np.random.default_rng(14), 50, R.WORDS_FEW, 0.0)
+    short_at = np.arange(0, 100, 2, dtype=np.int64)
+    lists = H.csr(H.wide_lists(np.random.default_rng(4), n))
+    vectors = sparse_csr(random_corpus(np.random.default_rng(5), n, H.SPARSE_VOCAB, True))
+    engines = [cls(d, "l2") for cls in (R.RecentHistoryModel, BitsOracleEngine, HybridOracleEngine, StatsOracleEngine,
+                                        GH.oracle_engine_class())]
+    model, bits, hybrid, stats, geo = engines
+    for e in engines:
+        pooled, is_bits, is_geo = isinstance(e, HybridOracleEngine), isinstance(e, BitsOracleEngine), e in (model, geo)
+        columns = ((0, "int64"), (1, "float64"), (2, "int64")) + (((4, "int64_list"), (5, "sparse")) if pooled else ()) \
+            + (((R.GEO_A, "geo"),) if is_geo else ()) + (((R.BITS_A, "bits"),) if is_bits else ())
+        for attr, kind in columns:
+            e.define_attr(attr, kind)
+        e.append(rows[:250])
+        e.append(rows[250:])
+        for attr in range(3):
+            e.set_attr(attr, 0, H.column_values(attr, n, np.random.default_rng(attr), n))
+        if pooled:
+            e.set_attr_list(4, 0, lists)
+            e.set_attr_sparse(5, 0, vectors)
+        if is_geo:
+            e.set_attr(R.GEO_A, 0, points)
+        if is_bits:
+            e.bits_set(R.BITS_A, 0, codes)
+        e.tombstone(np.arange(0, n, 7))
+        if is_bits:
+            assert e.bits_set_at(R.BITS_A, short_at, short) == 50 - 8  # (eight of the labels are tombstoned)
+    half = H.program_of({"ops": HALF, "set": []})
+    same = lambda a, b: len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))  # noqa: E731
+    # bits
+    coded = H.program_of({"ops": [[W.EXISTS, R.BITS_A, 0, 0], [W.LT, 2, 8, 0], [W.AND, 0, 0, 0]], "set": []})
+    for words in (R.WORDS, R.WORDS_FEW):
+        bq = R.bits_codes(np.random.default_rng(15), 4, words)
+        for metric in ("hamming", "jaccard"):
+            got, want = model.search_bits(R.BITS_A, bq, 9, metric, coded), bits.search_bits(R.BITS_A, bq, 9, metric, coded)
+            assert same(got, want) and got[2].min() > 0
+    assert same(model.bits_get(R.BITS_A, 0, n), bits.bits_get(R.BITS_A, 0, n))
+    assert model.list_stats(R.BITS_A) == bits.list_stats(R.BITS_A)
+    # hybrid: the entry's seven outputs, and behind them the whole union
+    sq = H._sparse_queries(np.random.default_rng(6), 5)
+    for method in ("rrf", "linear", "relative"):
+        got = model.search_hybrid(qs, 5, sq, 10, 40, 20, method=method, weights=(0.75, 1.3), rrf_k=7.5, where=half)
+        want = hybrid.search_hybrid(qs, 5, sq, 10, 40, 20, method=method, weights=(0.75, 1.3), rrf_k=7.5, where=half, components=True)
+        assert same(got[:7], want)
+        union = hybrid.search_hybrid(qs, 5, sq, 60, 40, 20, method=method, weights=(0.75, 1.3), rrf_k=7.5, where=half, components=True)
+        assert same(got[7], union) and (union[2] > 40).all()
+    # statistics
+    for attr, by in ((1, 0), (0, None), (2, 2)):
+        assert same(model.attr_stats(attr, by, 4096, half), stats.attr_stats(attr, by, 4096, half))
+    for e in (model, stats):
+        with pytest.raises(StatsOverflow) as err:
+            e.attr_stats(1, 2, 3, half)
+        assert (err.value.matched, err.value.by_absent) == (model.where_count(half), 0) and err.value.n_groups > 3
+    # geo: a radius leaf AND-ed with a scalar one, a box, nearest under a program
+    c = int(GH.quantise([centre[0]], [centre[1]])[0])
+    near = GH.radius_program(R.GEO_A, c, 3.0e4)
+    both = W.Program(np.concatenate([near.ops, half.ops, np.array([(W.AND, 0, 0, 0)], W.OP_DTYPE)]), near.set)
+    box = GH.box_program(R.GEO_A, *GH.quantise([centre[0] - 5, centre[0] + 5], [179.5, -179.5]))
+    for program in (near, both, box, GH.negate(near)):
+        assert np.array_equal(model.match(program), geo.match(program)) and model.match(program).any()
+    got, want = model.geo_nearest(R.GEO_A, c, 20, both, 3), geo.geo_nearest(R.GEO_A, c, 20, both, 3)
+    assert same(got[:2], want[:2]) and np.array_equal(got[2].astype(np.float64), want[2]) and got[3:] == want[3:]
+    assert got[2].dtype == GH.LD and got[0].size == 20
+    # what the model adds: list, geo and bits leaves in one program
+    mixed = H.program_of({"ops": [[W.HAS, 4, 3, 0], [W.EXISTS, R.BITS_A, 0, 0], [W.AND, 0, 0, 0]] + [list(map(int, o)) for o in near.ops.tolist()]
+                          + [[W.OR, 0, 0, 0]], "set": []})
+    want = (hybrid.match(H.program_of({"ops": [[W.HAS, 4, 3, 0]], "set": []}))
+            & bits.match(H.program_of({"ops": [[W.EXISTS, R.BITS_A, 0, 0]], "set": []}))) | geo.match(near)
+    assert np.array_equal(model.match(mixed), want) and 0 < want.sum() < model.counts()[0] - model.counts()[1]
+    # ... the bits pool mirrored as a list's, through the repack and the reset
+    used, cap, live = model.pools()[R.BITS_A]
+    assert used == R.WORDS * int(codes.present.sum()) + R.WORDS_FEW * 50 and cap == H.pool_capacity_after(R.WORDS * int(codes.present.sum()), used)
+    assert 0 < live < used
+    assert np.array_equal(model.compact(), bits.compact()) and model.list_stats(R.BITS_A) == bits.list_stats(R.BITS_A)
+    assert model.pools()[R.BITS_A] == (live, live, live)
+    assert same(model.bits_get(R.BITS_A, 0, 300), bits.bits_get(R.BITS_A, 0, 300))
+    model.reset()
+    assert model.pools()[R.BITS_A] == (0, live, 0) and model.append(rows[:5]) == 0
+    assert not model.bits_get(R.BITS_A, 0, 5)[0].any() and (model.get_attr(R.GEO_A, 0, 5) == GH.ABSENT).all()
+    # ... and the refusals, with the status codes the headers name, none of which changes the state
+    before = (model.get_attr(R.GEO_A, 0, 5).copy(), model.pools())
+    a = {"qs": qs[:3], "sq": H._sparse_queries(np.random.default_rng(7), 3), "bq": R.bits_codes(rng, 2, R.WORDS)}
+    for which in R.RECENT_REFUSALS:
+        op = {"op": "refuse_recent", "which": which, "seed": 1, "centre": c}
+        if which.startswith("bits_words") or which == "bits_at_repeat":
+            a["col"] = R.materialise(model, op)["col"]
+        assert R.CALLS["refuse_recent"](model, op, a) == ("refused", 6 if which in R.UNSUPPORTED_REFUSALS else 1), which
+    assert np.array_equal(model.get_attr(R.GEO_A, 0, 5), before[0]) and model.pools() == before[1]
+
+
+def recent_trace(ops, expected, space):
+    """The handle's state BEFORE each step of a recent history.  ``shadow`` counts what resets the derived row shadows (a
+    compaction that drops rows, a reset, an append that regrows the capacity); ``regrowths`` the capacity regrowths while the
+    sparse, geo and bits columns hold values."""
+    st = dict(strategy="auto", total=0, deleted=0, space=space, cap=0, regrowths=0, valued=set(), pools={}, shadow=0)
+    out = []
+    for op, exp in zip(ops, expected):
+        out.append({**st, "valued": set(st["valued"])})
+        kind = op["op"]
+        if kind == "set_strategy":
+            st["strategy"] = op["strategy"]
+        elif kind == "append":
+            cap = H.capacity_after(st["cap"], st["total"] + op["n"])
+            if cap != st["cap"] and st["cap"]:
+                st["shadow"] += 1
+                if {H.SPARSE_A, R.GEO_A, R.BITS_A} <= st["valued"]:
+                    st["regrowths"] += 1
+            st["cap"] = cap
+        elif kind == "compact":
+            st["cap"] = H.capacity_after_compact(st["cap"], st["total"] - st["deleted"], st["deleted"])
+            st["regrowths"] = 0
+            st["shadow"] += bool(st["deleted"])
+        elif kind in ("set_attr_sparse", "bits_set", "set_attr") and op["n"] and op["attr"] in (H.SPARSE_A, R.GEO_A, R.BITS_A):
+            st["valued"] = st["valued"] | {op["attr"]}
+        elif kind == "reset":
+            st.update(regrowths=0, valued=set(), shadow=st["shadow"] + 1)
+            st["space"] = op["space"] or st["space"]
+        if "counts" in exp:
+            st["total"], st["deleted"] = exp["counts"]
+        st["pools"] = exp["pools"]
+    return out
+
+
+def answers_nothing(op, want):
+    """A new query on an index without rows: padding or zeros."""
+    kind = op["op"]
+    if kind in ("search_bits", "search_hybrid"):
+        return not np.asarray(want[2]).any() and (want[0] == -1).all()
+    if kind == "bits_get":
+        return want[0].size == 0 and want[1].size == 0
+    if kind == "attr_stats":
+        return tuple(want[7:]) == (0, 0) and not want[1].any()
+    return want[0].size == 0 and tuple(want[3:]) == (0, 0)  # geo_nearest
+
+
+def recent_conditions(ops, expected, space):
+    """{condition: step} for every condition of RECENT_WANTED this recent history meets."""
+    st = recent_trace(ops, expected, space)
+    kinds = [op["op"] for op in ops]
+    n = len(ops)
+    met = {}
+    grow, floor = 0, np.inf
+    late = dict(defined=False, written=set())
+    mutations = [m for m in R.RECENT_MUTATIONS if m not in ("set_strategy", "set_tuning")]
+    full = lambda o: o["offset"] + o["limit"] == R.ORDER_MAX_ROWS  # noqa: E731
+    one = lambda o: o["limit"] == 1  # noqa: E731
+
+    def put(name, step):
+        met.setdefault(name, step)
+
+    for i, op in enumerate(ops):
+        k = kinds[i]
+        nxt = kinds[i + 1] if i + 1 < n else None
+        after = ops[i + 1] if i + 1 < n else {}
+        s = st[i]
+        # pairs: either side is new
+        if k in R.RECENT_MUTATIONS and nxt in R.RECENT_QUERIES and (k in R.BITS_MUTATIONS or nxt in R.RECENT_NEW_QUERIES):
+            put(f"k_{k}>{nxt}", i)
+        # the bits pool: a compaction with garbage, then search_bits and list_stats
+        if k == "compact" and i + 2 < n and R.BITS_A in s["pools"]:
+            used, _, live = s["pools"][R.BITS_A]
+            if used > live > 0 and nxt == "search_bits" and after["attr"] == R.BITS_A and kinds[i + 2] == "list_stats" \
+                    and ops[i + 2]["attr"] == R.BITS_A:
+                assert expected[i + 2]["want"][0] == expected[i + 2]["want"][1] > 0  # the repack: used == live
+                put(f"l_bits_{'dead' if s['deleted'] else 'clean'}", i)
+        # ... its capacity grows twice while it holds live codes, then rows written before the first growth are read
+        if k in ("compact", "reset"):
+            grow, floor = 0, np.inf
+        if k in R.BITS_MUTATIONS and op["attr"] == R.BITS_A:
+            used, cap, live = s["pools"][R.BITS_A]
+            if expected[i]["pools"][R.BITS_A][1] != cap:
+                assert expected[i]["pools"][R.BITS_A][1] == H.pool_capacity_after(cap, expected[i]["pools"][R.BITS_A][0])
+                if used > 0 and live > 0:
+                    grow += 1
+            if grow:
+                floor = min(floor, write_floor(op))
+        if k == "bits_get" and op["attr"] == R.BITS_A and op["first"] == 0 and 0 < op["n"] <= floor and grow >= 2:
+            put("m_bits", i)
+        # width: rows of 5 words rewritten with 2 words (or made absent), then a 5-word and a 2-word search
+        if k == "bits_set_at" and op["attr"] == R.BITS_A and op["words"] == R.WORDS_FEW and op["p_absent"] in (0.0, 1.0) \
+                and set(expected[i]["widths_before"]) == {R.WORDS} and kinds[i + 1:i + 3] == ["search_bits", "search_bits"] \
+                and [ops[i + 1]["words"], ops[i + 2]["words"]] == [R.WORDS, R.WORDS_FEW]:
+            put("width_2" if op["p_absent"] == 0.0 else "width_absent", i)
+        # two regrowths of the rows with values present, then the readers
+        if s["regrowths"] >= 2:
+            if k in ("bits_get", "search_bits", "geo_nearest", "search_hybrid"):
+                put("n_" + k, i)
+            if leaf_on(op, R.GEO_A, GEO_OPS):
+                put("n_geo_program", i)
+            if k == "attr_stats" and op["by"] is not None:
+                put("n_attr_stats_by", i)
+        # emptied: the five new queries answer padding or zeros, a refill, the five again
+        emptied_by_compact = (k == "compact" and s["total"] > 0 and expected[i]["counts"] == (0, 0) and i > 0
+                              and kinds[i - 1] == "tombstone_where" and ops[i - 1]["program"]["ops"] == [[W.TRUE, 0, 0, 0]])
+        if emptied_by_compact or (k == "reset" and s["total"] > 0):
+            first, j = run_of(ops, i + 1, R.RECENT_QUERIES)
+            if j < n and kinds[j] == "append":  # rows, the five, the values of every column, the five again
+                bare, j2 = run_of(ops, j + 1, R.RECENT_QUERIES)
+                values, j3 = run_of(ops, j2, R.RECENT_MUTATIONS)
+                again, _ = run_of(ops, j3, R.RECENT_QUERIES)
+                new = [x for x in first if kinds[x] in R.RECENT_NEW_QUERIES]
+                written = {(kinds[x], ops[x].get("attr")) for x in values}
+                if all(answers_nothing(ops[x], expected[x]["want"]) for x in new) and set(R.RECENT_NEW_QUERIES) <= {kinds[x] for x in new} \
+                        and set(R.RECENT_NEW_QUERIES) <= {kinds[x] for x in bare} and set(R.RECENT_NEW_QUERIES) <= {kinds[x] for x in again} \
+                        and {("bits_set", R.BITS_A), ("set_attr", R.GEO_A), ("set_attr_sparse", H.SPARSE_A)} <= written:
+                    put("w_compact" if k == "compact" else "w_reset" if op["space"] is None else "w_reset_other", i)
+        # hybrid on the filter route across mutations
+        if k == "search_hybrid" and s["strategy"] == "filter":
+            between, j = run_of(ops, i + 1, mutations)
+            if between and j < n and kinds[j] == "search_hybrid" and st[j]["strategy"] == "filter":
+                small = op["fd"] <= 64 and ops[j]["fd"] <= 64
+                big = op["fd"] > 64 and ops[j]["fd"] > 64
+                for x in between:
+                    if small and kinds[x] in ("tombstone_where", "tombstone", "append", "compact"):
+                        put(f"p_hybrid_small_{kinds[x]}", i)
+                    if big and st[j]["shadow"] > s["shadow"]:  # the fp16 shadow was dropped in between
+                        if kinds[x] == "compact" and st[x]["deleted"]:
+                            put("p_hybrid_big_compact", i)
+                        if kinds[x] == "append" and st[x + 1]["cap"] != st[x]["cap"] and st[x]["cap"]:
+                            put("p_hybrid_big_regrowth", i)
+            if s["space"] == "l2" and i + 3 < n and nxt == "search_hybrid" and after["nq"] != op["nq"] \
+                    and kinds[i + 2] == "tombstone_where" and kinds[i + 3] in SEARCHES:
+                put("p_l2_hybrid", i)
+        # the mask is handed back
+        if k in ("search_hybrid", "search_bits") and op.get("program") is not None:
+            if nxt == "search64":
+                put(f"q_{k}_plain", i)
+            if nxt == k and after.get("program") is None:
+                put(f"q_{k}_own", i)
+        # one workspace, two windows
+        if {k, nxt} == {"where_ordered", "geo_nearest"} and ((full(op) and one(after)) or (one(op) and full(after))):
+            put("ws_ordered>nearest" if k == "where_ordered" else "ws_nearest>ordered", i)
+        # the grow-only table of the statistics
+        if k == "attr_stats" and op["by"] is not None and kinds[i + 1:i + 4] == ["attr_stats"] * 3 and not isinstance(expected[i]["want"][0], str):
+            groups = int(expected[i]["want"][0].size)
+            a, b, c = ops[i + 1:i + 4]
+            wa, wb, wc = (expected[x]["want"] for x in (i + 1, i + 2, i + 3))
+            if op["max_groups"] > 8 * groups and all(o["by"] == op["by"] and o.get("program") is None for o in (op, a, b, c)) \
+                    and a["max_groups"] == groups and not isinstance(wa[0], str) and wa[0].size == groups \
+                    and b["max_groups"] == groups - 1 and tuple(wb) == ("overflow", True) + tuple(wa[7:]) \
+                    and not isinstance(wc[0], str):
+                put("g_chain", i)
+        if k == "attr_stats" and nxt == "facet_values" and after["attr"] == op["by"]:
+            put("g_stats>facet", i)
+        if k == "facet_values" and nxt == "attr_stats" and after["by"] == op["attr"]:
+            put("g_facet>stats", i)
+        # writers, then at once the readers of what they wrote
+        if k == "update_where":
+            if [R.GEO_A, _native.SET_ASSIGN] in [x[:2] for x in op["assigns"]]:
+                if nxt == "geo_nearest" and after["attr"] == R.GEO_A:
+                    put("s_geo_assign>geo_nearest", i)
+                if leaf_on(after, R.GEO_A, (W.GEO_RADIUS,)):
+                    put("s_geo_assign>radius", i)
+            if [1, _native.SET_ADD] in [x[:2] for x in op["assigns"]] and nxt == "attr_stats" and after["attr"] == 1:
+                put("s_float_add>attr_stats", i)
+        if k == "set_attr_at" and nxt == "attr_stats" and after["by"] == op["attr"]:
+            put("s_by>attr_stats", i)
+        if k == "set_attr_sparse_at" and nxt == "search_hybrid" and after["attr"] == op["attr"]:
+            put("s_sparse_at>search_hybrid", i)
+        if k == "bits_set_at" and 0 < expected[i]["dead"] and expected[i]["want"] < len(expected[i]["widths_before"]) \
+                and nxt == "search_bits" and after["attr"] == op["attr"]:
+            put("s_bits_at_dead>search_bits", i)
+        if k == "tombstone_where" and leaf_on(op, R.GEO_A, (W.GEO_RADIUS,)) and nxt in ("attr_stats", "geo_nearest", "search_bits"):
+            put(f"s_tombstone_radius>{nxt}", i)
+        # the late columns: all absent, then written
+        if k == "define_attr" and op["attr"] == R.LATE_GEO and s["total"] > 0 and not late["defined"]:
+            late["defined"] = True
+            put("r_defined", i)
+        elif late["defined"]:
+            if (k in ("set_attr", "set_attr_at", "bits_set", "bits_set_at") and op["attr"] in (R.LATE_GEO, R.LATE_BITS)) or \
+                    (k == "update_where" and R.LATE_GEO in [x[0] for x in op["assigns"]]):
+                late["written"].add(R.LATE_GEO if k in ("set_attr", "set_attr_at", "update_where") else R.LATE_BITS)
+            phase = {0: "absent", 2: "set"}.get(len(late["written"]))
+            if phase:
+                if k == "geo_nearest" and op["attr"] == R.LATE_GEO:
+                    put(f"r_{phase}_geo_nearest", i)
+                if leaf_on(op, R.LATE_GEO, GEO_OPS):
+                    put(f"r_{phase}_geo_leaf", i)
+                if k in ("search_bits", "bits_get") and op["attr"] == R.LATE_BITS:
+                    put(f"r_{phase}_{k}", i)
+        # refusals with the status the header names, the pools as they were, each followed at once by a query
+        if k == "refuse_recent" and nxt in R.RECENT_QUERIES and expected[i]["pools"] == s["pools"] and \
+                expected[i]["want"] == ("refused", 6 if op["which"] in R.UNSUPPORTED_REFUSALS else 1):
+            put("v_" + op["which"], i)
+    for name, parts in (("n", ["n_bits_get", "n_search_bits", "n_geo_nearest", "n_geo_program", "n_attr_stats_by", "n_search_hybrid"]),
+                        ("r", ["r_defined"] + [f"r_{p}_{x}" for p in ("absent", "set") for x in
+                                               ("geo_nearest", "geo_leaf", "search_bits", "bits_get")])):
+        if all(x in met for x in parts):
+            met[name] = met[parts[0]]
+    return met
+
+
+RECENT_WANTED = ([f"k_{m}>{q}" for m, q in R.RECENT_PAIRS] + ["l_bits_clean", "l_bits_dead", "m_bits", "width_2", "width_absent", "n",
+                                                               "w_reset", "w_reset_other", "w_compact"]
+                 + [f"p_hybrid_small_{x}" for x in ("tombstone_where", "tombstone", "append", "compact")]
+                 + ["p_hybrid_big_compact", "p_hybrid_big_regrowth", "p_l2_hybrid"]
+                 + [f"q_{k}_{x}" for k in ("search_hybrid", "search_bits") for x in ("plain", "own")]
+                 + ["ws_ordered>nearest", "ws_nearest>ordered", "g_chain", "g_stats>facet", "g_facet>stats"]
+                 + ["s_geo_assign>geo_nearest", "s_geo_assign>radius", "s_by>attr_stats", "s_float_add>attr_stats",
+                    "s_sparse_at>search_hybrid", "s_bits_at_dead>search_bits"]
+                 + [f"s_tombstone_radius>{q}" for q in ("attr_stats", "geo_nearest", "search_bits")] + ["r"]
+                 + ["v_" + w for w in R.RECENT_REFUSALS])
+
+
+def test_the_recent_histories_meet_every_coverage_condition():
+    where, tagged = {}, {}
+    for key in R.RECENT:
+        ops, expected = H.make_history(*key)
+        for name, step in recent_conditions(ops, expected, key[1]).items():
+            where.setdefault(name, (key[0], step))
+        assert max(e["counts"][0] for e in expected if "counts" in e) <= H.MAX_ROWS_WIDE, key
+        for step, op in enumerate(ops):  # the kinds that take a program, and those of them that got a geo leaf or EXISTS on bits
+            if R.programs_of(op):
+                tagged.setdefault(op["op"], None)
+                if tagged[op["op"]] is None and any(R.has_recent_leaf(p) for p in R.programs_of(op)):
+                    tagged[op["op"]] = (key[0], step)
+        print(f"history {H.history_tag(*key)}: {len(ops)} steps, distance bar {R.geo_bar(*key):.3e}")
+    for name in RECENT_WANTED:
+        if name in where:
+            print(f"condition {name}: seed {where[name][0]}, step {where[name][1]}")
+    missing = [name for name in RECENT_WANTED if name not in where]
+    assert not missing, f"coverage conditions never met: {missing}"
+    assert len(R.RECENT_PAIRS) == 18 * 34 - 16 * 29 and len(R.RECENT) == 12 and len(set(RECENT_WANTED)) == len(RECENT_WANTED)
+    # the new program kinds go into every program-taking op, old kinds included; and every one of the six kinds is drawn
+    for kind, at in sorted(tagged.items()):
+        print(f"a geo leaf or EXISTS on the bits column in {kind}: " + ("never" if at is None else f"seed {at[0]}, step {at[1]}"))
+    assert set(R.PROGRAM_TAKING) <= set(tagged) and not [kind for kind, at in tagged.items() if at is None], tagged
+    shapes = set()
+    for key in R.RECENT:
+        for op in H.make_history(*key)[0]:
+            for p in R.programs_of(op):
+                codes = [o[0] for o in p["ops"]]
+                box = [o for o in p["ops"] if o[0] == W.GEO_BOX]
+                shapes |= {"radius"} if codes == [W.GEO_RADIUS] else {"not_radius"} if codes == [W.GEO_RADIUS, W.NOT] else set()
+                shapes |= {"geo_and_scalar"} if codes == [W.GEO_RADIUS, W.LT, W.AND] else set()
+                shapes |= {"bits_exists"} if [o[:2] for o in p["ops"]] == [[W.EXISTS, R.BITS_A]] else set()
+                for o in box:
+                    (_, w), (_, e) = GH.unpack(np.int64(o[2])), GH.unpack(np.int64(o[3]))
+                    shapes.add("box" if w <= e else "box_anti")
+    assert shapes == set(R.RECENT_PROGRAMS), shapes
+    # the large ones move hybrid's dense leg between the routes by `auto` alone, with the paged depths on each side
+    for key in R.RECENT_LARGE:
+        ops, expected = H.make_history(*key)
+        st = recent_trace(ops, expected, key[1])
+        assert all(s["strategy"] == "auto" for s in st)
+        hybrid = [(op, s["total"] >= H.FILTER_MIN_ROWS) for op, s in zip(ops, st) if op["op"] == "search_hybrid"]
+        routes = [above for op, above in hybrid if op["nq"] >= 12 and op["fd"] <= 64]
+        assert routes[0] is False and True in routes and False in routes[routes.index(True):] and routes[-1] is True, (key, routes)
+        assert {(12, True), (40, True)} <= {(op["nq"], above) for op, above in hybrid if op["fd"] <= 64}
+        for fd in (65, 1024):
+            assert {above for op, above in hybrid if op["fd"] == fd} == {True, False}, (key, fd)
+        new = [(op["op"], s["total"] >= H.FILTER_MIN_ROWS) for op, s in zip(ops, st) if op["op"] in R.RECENT_NEW_QUERIES]
+        assert len(new) <= 20 and {(q, True) for q in R.RECENT_NEW_QUERIES} <= set(new), new
+        i = [op["op"] for op in ops].index("tombstone_where")
+        assert [o[0] for o in ops[i]["program"]["ops"]] == [W.GEO_BOX] and "compact" in [op["op"] for op in ops[i:]]
+        died = expected[i]["counts"][1] / expected[i]["counts"][0]
+        assert 0.25 < died < 0.42, died
+        assert max(e["counts"][0] for e in expected if "counts" in e) > H.FILTER_MIN_ROWS
+        print(f"history {H.history_tag(*key)}: {len(ops)} steps, tombstone_where through a geo box of {died:.0%} of the rows at "
+              f"step {i}, distance bar {R.geo_bar(*key):.3e}")
+
+
+def test_the_recent_op_lists_are_deterministic_and_json_serialisable():
+    key = R.RECENT[1]
+    ops, expected = H.make_history(*key)
+    again = H._history.__wrapped__(*key)  # (generated anew; the cache keeps what the other tests share)
+    ops2, expected2 = again.ops, again.expected
+    assert ops2 is not ops and json.dumps(ops) == json.dumps(ops2) and json.loads(json.dumps(ops)) == ops
+    for a, b in zip(expected, expected2):
+        assert a["args"].keys() == b["args"].keys()
+        for name, x in a["args"].items():
+            if isinstance(x, np.ndarray):
+                assert x.tobytes() == b["args"][name].tobytes(), name
+    other, _ = H.make_history(key[0] + 1, *key[1:])
+    assert json.dumps(other) != json.dumps(ops)
+
+
+# ---------------------------------------------------------------- sensitivity of the recent histories: six seeded defects
+def reads_bits(op):
+    return op["op"] in ("search_bits", "bits_get") or (op["op"] == "list_stats" and op["attr"] in R.BITS_COLUMNS) or any(
+        leaf_on(op, a, (W.EXISTS,)) for a in R.BITS_COLUMNS)
+
+
+class KeepsCodesInOldRowOrder(R.RecentHistoryModel):
+    """Bit codes stay in pre-compaction row order while the scalar columns move."""
+    fired = None
+    seen_by = staticmethod(reads_bits)
+    at_once = False
+
+    def compact(self):
+        codes = {a: list(self._lists[a]) for a in self._bits}
+        lengths = {a: self._cols[a].copy() for a in self._bits}
+        old = super().compact()
+        for a in codes:
+            if self.fired is None and codes[a][:old.size] != self._lists[a]:
+                self.fired = self.step
+            self._lists[a], self._cols[a] = codes[a][:old.size], lengths[a][:old.size]
+        return old
+
+
+class CodesSurviveReset(R.RecentHistoryModel):
+    """``reset`` leaves the codes where they were: freshly appended rows inherit them."""
+    fired = None
+    seen_by = staticmethod(reads_bits)
+    at_once = False
+    _left = None
+
+    def reset(self, space=None):
+        self._left = {a: list(self._lists[a]) for a in self._bits}
+        super().reset(space)
+
+    def append(self, rows):
+        first = super().append(rows)
+        for a, left in (self._left or {}).items():
+            for row in range(first, min(self._rows.shape[0], len(left))):
+                if left[row] is not None:
+                    self._put(a, row, left[row])
+                    if self.fired is None:
+                        self.fired = self.step
+        self._left = None
+        return first
+
+
+class SearchBitsTakesOtherWidths(R.RecentHistoryModel):
+    """``search_bits`` takes the rows of another width as candidates (their first words, zero-extended)."""
+    fired = None
+    seen_by = staticmethod(lambda op: op["op"] == "search_bits")
+    at_once = True
+
+    def search_bits(self, attr, queries, k, metric="hamming", where=None):
+        from tests.bits_helpers import distances, rank
+
+        right = super().search_bits(attr, queries, k, metric, where)
+        words = queries.shape[1]
+        cand = self.candidates(attr, where)
+        idx = np.flatnonzero(cand)
+        codes = np.zeros((idx.size, words), np.uint64)
+        for j, i in enumerate(idx.tolist()):
+            code = self._lists[attr][i][:words]
+            codes[j, :len(code)] = code
+        dist = distances(queries, codes, metric) if idx.size else np.zeros((queries.shape[0], 0))
+        labels, d64, counts = rank(dist, cand, k)
+        wrong = (labels, d64.astype(np.float32), counts, d64)
+        if self.fired is None and _differs(right, wrong):
+            self.fired = self.step
+        return wrong
+
+
+class StatsCountsFilteredDeletes(R.RecentHistoryModel):
+    """``attr_stats`` counts the rows ``tombstone_where`` deleted, until a compaction drops them."""
+    fired = None
+    seen_by = staticmethod(lambda op: op["op"] == "attr_stats")
+    at_once = True
+    _ghosts = None
+
+    def tombstone_where(self, program):
+        labels = super().tombstone_where(program)
+        self._ghosts = labels if self._ghosts is None else np.union1d(self._ghosts, labels)
+        return labels
+
+    def compact(self):
+        self._ghosts = None
+        return super().compact()
+
+    def reset(self, space=None):
+        self._ghosts = None
+        super().reset(space)
+
+    def _outcome(self, *a):
+        try:
+            return super().attr_stats(*a), None
+        except StatsOverflow as err:
+            return (np.array([err.matched, err.by_absent]),), err
+
+    def attr_stats(self, attr, by=None, max_groups=1, where=None):
+        right, err = self._outcome(attr, by, max_groups, where)
+        if self._ghosts is not None and self._ghosts.size:
+            keep = self._deleted.copy()
+            self._deleted[self._ghosts] = False
+            try:
+                wrong, wrong_err = self._outcome(attr, by, max_groups, where)
+            finally:
+                self._deleted = keep
+            if self.fired is None and (len(right) != len(wrong) or _differs(right, wrong)):
+                self.fired = self.step
+            right, err = wrong, wrong_err
+        if err is not None:
+            raise err
+        return right
+
+
+class NearestReadsTheOldGeoColumn(R.RecentHistoryModel):
+    """``geo_nearest`` is answered from the geo column as it was before the last ``update_where``."""
+    fired = None
+    seen_by = staticmethod(lambda op: op["op"] == "geo_nearest")
+    at_once = True
+    _before = None
+
+    def update_where(self, program, assigns):
+        self._before = {a: self._cols[a].copy() for a in R.GEO_COLUMNS if a in self._cols}
+        return super().update_where(program, assigns)
+
+    def geo_nearest(self, attr, center, limit, where=None, offset=0):
+        right = super().geo_nearest(attr, center, limit, where, offset)
+        old = (self._before or {}).get(attr)
+        if old is None or old.size != self._cols[attr].size:
+            return right
+        keep = self._cols[attr]
+        self._cols[attr] = old
+        try:
+            wrong = super().geo_nearest(attr, center, limit, where, offset)
+        except AssertionError:  # (the rank guard was checked for the column as it is, not as it was)
+            return right
+        finally:
+            self._cols[attr] = keep
+        differs = any(not np.array_equal(x, y) for x, y in zip(right[:3], wrong[:3])) or right[3:] != wrong[3:]
+        if self.fired is None and differs:  # (by value: a long double's bytes hold padding)
+            self.fired = self.step
+        return wrong
+
+
+class SparseLegIgnoresTheProgram(R.RecentHistoryModel):
+    """Hybrid's sparse leg ignores the program: only the dense leg is masked."""
+    fired = None
+    seen_by = staticmethod(lambda op: op["op"] == "search_hybrid")
+    at_once = True
+    _unmasked = False
+
+    def candidates(self, attr, where=None, words=None):
+        return super().candidates(attr, None if self._unmasked else where, words)
+
+    def search_hybrid(self, *a, **kw):
+        right = super().search_hybrid(*a, **kw)
+        self._unmasked = True
+        try:
+            wrong = super().search_hybrid(*a, **kw)
+        finally:
+            self._unmasked = False
+        if self.fired is None and _differs(right[:7], wrong[:7]):
+            self.fired = self.step
+        return wrong
+
+
+@pytest.mark.parametrize("defect", [KeepsCodesInOldRowOrder, CodesSurviveReset, SearchBitsTakesOtherWidths,
+                                    StatsCountsFilteredDeletes, NearestReadsTheOldGeoColumn, SparseLegIgnoresTheProgram])
+def test_the_driver_reports_a_seeded_defect_in_the_recent_histories(defect, tmp_path, monkeypatch):
+    from tests import conftest
+
+    monkeypatch.setattr(conftest, "OUT_DIR", tmp_path)
+    reported, real_call = 0, H.call
+    for key in R.RECENT[:4]:
+        ops, expected = H.make_history(*key)
+        engine = defect(key[2], key[1])
+        stepped = []
+
+        def counted(e, op, a, engine=engine, stepped=stepped):
+            if e is engine:
+                engine.step = len(stepped)
+                stepped.append(op["op"])
+            return real_call(e, op, a)
+
+        monkeypatch.setattr(H, "call", counted)
+        tag = H.history_tag(*key)
+        try:
+            H.run_history(engine, ops, expected, tag)
+        except AssertionError as err:
+            failed = len(stepped) - 1
+            assert f"history {tag}: step {failed}, op " in str(err) and f"seed{key[0]}" in str(err)
+            assert engine.fired is not None and defect.seen_by(ops[failed]), (engine.fired, failed, ops[failed])
+            if defect.at_once:  # `fired` is the first call whose answer the defect changes: that call is the one reported
+                assert failed == engine.fired, (failed, engine.fired)
+            else:               # the state breaks in a mutation; the first later call that reads it differently reports it
+                assert failed > engine.fired and ops[engine.fired]["op"] in R.RECENT_MUTATIONS, (failed, engine.fired)
+            dumped = json.loads((tmp_path / f"history_{tag}.json").read_text())
+            assert dumped["failed_step"] == failed and dumped["ops"] == ops[:failed + 1]
+            print(f"{defect.__name__}: {tag} fired at step {engine.fired}, reported at step {failed} ({ops[failed]['op']})")
+            reported += 1
+        else:
+            assert engine.fired is None or not defect.at_once, f"{tag}: fired at step {engine.fired}, never reported"
+        monkeypatch.setattr(H, "call", real_call)
+    assert reported >= 2, f"{defect.__name__}: reported in {reported} of 4 histories"
+
+
 # ---------------------------------------------------------------- redraws
 def test_near_tie_redraws_stay_under_one_percent():
+    """Near-ties of the kNN kinds, and in the recent histories the draws that tripped a guard of tests/geo_helpers.py."""
     drawn = redrawn = 0
-    for key in H.HISTORIES + H.WIDE + H.WIDE_LARGE:
+    for key in H.HISTORIES + H.WIDE + H.WIDE_LARGE + R.RECENT + R.RECENT_LARGE:
         a, b = H.redraw_counts(*key)
+        if key[3] in R.RECENT_SCALES:
+            print(f"history {H.history_tag(*key)}: {b} of {a} drawn queries were redrawn")
         drawn, redrawn = drawn + a, redrawn + b
     print(f"{redrawn} of {drawn} drawn queries were redrawn")
     assert drawn > 300 and redrawn <= 0.01 * drawn
