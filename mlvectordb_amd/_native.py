@@ -245,6 +245,24 @@ STATS_SIGNATURES = {
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
+# include/mlvdb_score.h: scored kNN -- rows ranked by a formula of the distance and the attribute columns
+SCORE_MAX_OPS = 32
+SCORE_MAX_DEPTH = 8
+SCORE_MAX_CONDS = 8
+SCORE_CONST, SCORE_DIST, SCORE_ATTR, SCORE_MATCH = 0, 1, 2, 3
+SCORE_ADD, SCORE_SUB, SCORE_MUL, SCORE_DIV, SCORE_MIN, SCORE_MAX = 4, 5, 6, 7, 8, 9
+SCORE_NEG, SCORE_ABS = 10, 11
+
+
+class Score(C.Structure):
+    _fields_ = [("ops", C.c_void_p), ("n_ops", C.c_int32), ("conds", C.POINTER(Where)), ("n_conds", C.c_int32)]
+
+
+SCORE_SIGNATURES = {
+    "mlvdb_search_batch_scored": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.POINTER(Score), C.POINTER(Where),
+                                            _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -278,7 +296,7 @@ def load() -> C.CDLL:
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
                                       **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **BITS_SIGNATURES,
                                       **HYBRID_SIGNATURES,
-                                      **GEO_SIGNATURES, **STATS_SIGNATURES}.items():
+                                      **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -113,6 +113,9 @@ struct mlvdb_index {
     // every row (4 B per row), the [token, document] keys of a chunk of queries (<= MAXSIM_WS_MB MiB, or one query's), the
     // chunk's token offsets and its ranked outputs
     DevBuf ms_tab, ms_rowdoc, ms_best, ms_misc, ms_out;
+    // scored kNN (mlvdb_score.h): the call's programs with the conds' set table, a chunk's queries and its outputs -- sized
+    // by the chunk (<= kDistinctChunk queries) and k, never by the corpus
+    DevBuf score_prog, score_q, score_out;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -4884,6 +4887,169 @@ int mlvdb_search_batch_hybrid(mlvdb_index* h, const float* queries, int32_t attr
                            out_rank_sparse);
     };
     // the first launches: where_run(h, where, ...) for the program, then hybrid_impl under with_row_mask(h, nq, ...)
+    return with_where(h, where, nq, call);
+    });
+}
+
+// ---- scored kNN (mlvdb_score.h)
+extern "C++" {
+namespace {
+// Host validation of a score program and its conds (the stack's depth throughout and at the end, the columns ATTR reads, the
+// MATCH indices; each cond by where_prepare) -> `out`, the block the scan stages, and the conds' concatenated set table.
+// Nothing is launched for a program refused here.
+int score_prepare(mlvdb_index* h, const mlvdb_score* sc, ScoreProgram& out, std::vector<int64_t>& set) {
+    if (!sc) return fail(h, MLVDB_ERR_INVALID_ARG, "score is null");
+    if (sc->n_ops < 1 || sc->n_ops > MLVDB_SCORE_MAX_OPS || !sc->ops)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "a score program holds 1..MLVDB_SCORE_MAX_OPS ops");
+    if (sc->n_conds < 0 || sc->n_conds > MLVDB_SCORE_MAX_CONDS || (sc->n_conds > 0 && !sc->conds))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "score: n_conds outside 0..MLVDB_SCORE_MAX_CONDS");
+    int64_t cond_ops = 0;
+    for (int32_t c = 0; c < sc->n_conds; ++c) cond_ops += sc->conds[c].n_ops > 0 ? sc->conds[c].n_ops : 0;
+    if (cond_ops > MLVDB_WHERE_MAX_OPS) return fail(h, MLVDB_ERR_INVALID_ARG, "score: more than MLVDB_WHERE_MAX_OPS ops over all conds");
+    std::memset(&out, 0, sizeof out);
+    int depth = 0;
+    for (int32_t i = 0; i < sc->n_ops; ++i) {
+        const mlvdb_score_op& o = sc->ops[i];
+        ScoreOp& d = out.ops[i];
+        d = ScoreOp{o.op, 0, o.a};
+        switch (o.op) {
+            case MLVDB_SCORE_ADD: case MLVDB_SCORE_SUB: case MLVDB_SCORE_MUL: case MLVDB_SCORE_DIV:
+            case MLVDB_SCORE_MIN: case MLVDB_SCORE_MAX:
+                if (depth < 2) return fail(h, MLVDB_ERR_INVALID_ARG, "score: a binary op needs two operands on the stack");
+                --depth;
+                continue;
+            case MLVDB_SCORE_NEG: case MLVDB_SCORE_ABS:
+                if (depth < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "score: NEG / ABS needs an operand on the stack");
+                continue;
+            case MLVDB_SCORE_CONST: case MLVDB_SCORE_DIST:
+                break;
+            case MLVDB_SCORE_ATTR: {
+                if (int rc = attr_check(h, o.attr)) return rc;
+                const int32_t type = h->attr_type[o.attr];
+                if (type != MLVDB_ATTR_INT64 && type != MLVDB_ATTR_FLOAT64)
+                    return fail(h, MLVDB_ERR_INVALID_ARG, "score: ATTR needs an int64 or float64 column (list, sparse, geo and bits columns hold no number)");
+                int32_t j = 0;  // the (column, default) pair's operand
+                while (j < out.n_operands && !(out.operands[j].col == h->attr_col[o.attr] && out.operands[j].dflt == o.a)) ++j;
+                if (j == out.n_operands) out.operands[out.n_operands++] = ScoreOperand{h->attr_col[o.attr], o.a, type, 0};
+                d.slot = j;
+                break;
+            }
+            case MLVDB_SCORE_MATCH:
+                if (o.a < 0 || o.a >= sc->n_conds) return fail(h, MLVDB_ERR_INVALID_ARG, "score: MATCH index outside conds");
+                d.slot = (int32_t)o.a;
+                break;
+            default:
+                return fail(h, MLVDB_ERR_INVALID_ARG, "unknown score op");
+        }
+        if (++depth > MLVDB_SCORE_MAX_DEPTH) return fail(h, MLVDB_ERR_INVALID_ARG, "score program deeper than MLVDB_SCORE_MAX_DEPTH");
+    }
+    if (depth != 1) return fail(h, MLVDB_ERR_INVALID_ARG, "a score program must leave exactly one value on the stack");
+    out.n_ops = sc->n_ops;
+    out.n_conds = sc->n_conds;
+    EachPrograms ep;
+    if (int rc = where_each_pack(h, sc->conds, sc->n_conds, ep)) return rc;
+    std::copy(ep.ops.begin(), ep.ops.end(), out.cond_ops);
+    std::copy(ep.off.begin(), ep.off.end(), out.cond_off);
+    set = std::move(ep.set);
+    return MLVDB_OK;
+}
+
+// Where a chunk's outputs lie in h->score_out: n queries of k entries each (dist: the merge's fp32 image of the scores, unused)
+struct ScoredOut {
+    double* score = nullptr;
+    double* d64 = nullptr;
+    int64_t* lab = nullptr;
+    float* dist = nullptr;
+    int32_t* cnt = nullptr;
+    void take(Carver& c, size_t nk, size_t n) {
+        score = c.take<double>(nk);
+        d64 = c.take<double>(nk);
+        lab = c.take<int64_t>(nk);
+        dist = c.take<float>(nk);
+        cnt = c.take<int32_t>(n);
+    }
+};
+
+// The validated call (h->rn is the masked copy when a program restricts the rows): the programs to the device, then per chunk
+// of queries the scored scan, the merge, the distances of the returned pairs and the outputs to the host.
+int scored_impl(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const ScoreProgram& prog,
+                const std::vector<int64_t>& set, int64_t* out_labels, double* out_score, int32_t* out_counts,
+                double* out_dist64) {
+    hipStream_t s = h->stream;
+    if (h->total == 0 || h->total == h->deleted) {
+        pad(out_labels, nq * k, -1);
+        pad(out_score, nq * k, __builtin_inf());
+        pad(out_dist64, nq * k, __builtin_inf());
+        pad(out_counts, nq, 0);
+        return MLVDB_OK;
+    }
+    if (int rc = begin_call(h, s)) return rc;
+    ScoreProgram* prog_d = nullptr;
+    int64_t* set_d = nullptr;
+    CARVE(h, h->score_prog, [&](Carver& c) {
+        prog_d = c.take<ScoreProgram>(1);
+        set_d = c.take<int64_t>(set.size());
+        c.take<char>(sizeof(int64_t));  // slack behind the set table
+    });
+    HIP_TRY(h, hipMemcpyAsync(prog_d, &prog, sizeof prog, hipMemcpyHostToDevice, s));
+    if (!set.empty()) HIP_TRY(h, hipMemcpyAsync(set_d, set.data(), set.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    for (int64_t q0 = 0; q0 < nq; q0 += kDistinctChunk) {
+        const int32_t n = (int32_t)std::min<int64_t>(kDistinctChunk, nq - q0);
+        const size_t nk = (size_t)n * k;
+        HIP_TRY(h, h->score_q.ensure((size_t)n * h->dim * sizeof(float)));
+        HIP_TRY(h, h->qpad.ensure((size_t)n * h->ld * sizeof(float)));
+        HIP_TRY(h, h->qaux.ensure((size_t)n * sizeof(double)));
+        ScoredOut o{};
+        if (int rc = carve(h, h->score_out, [&](Carver& c) { o.take(c, nk, (size_t)n); })) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->score_q.p, queries + (size_t)q0 * h->dim, (size_t)n * h->dim * sizeof(float),
+                                  hipMemcpyHostToDevice, s));
+        HIP_TRY(h, launch_query_prep(h->score_q.as<float>(), n, h->dim, h->ld, h->space, h->qpad.as<float>(),
+                                     h->qaux.as<double>(), nullptr, s));
+        const ExactPlan plan = plan_scored(h->total, h->ld, n, k);
+        HIP_TRY(h, h->partial.ensure(nk * plan.nblk * sizeof(TopEntry)));
+        ScoredArgs a{};
+        a.X = h->X;
+        a.rn = h->rn;
+        a.total = h->total;
+        a.ld = h->ld;
+        a.space = h->space;
+        a.Qpad = h->qpad.as<float>();
+        a.qaux = h->qaux.as<double>();
+        a.nq = n;
+        a.k = k;
+        a.prog = prog_d;
+        a.set = set_d;
+        a.partial = h->partial.as<TopEntry>();
+        if (int rc = scan_step(h, s, h->total * plan.nqtiles, [&] { return launch_scored_scan(a, plan, s); })) return rc;
+        h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+        HIP_TRY(h, launch_exact_merge(a.partial, n, nullptr, nullptr, plan.nblk, k, o.lab, o.dist, o.cnt, o.score, s));
+        // the bits DIST had for every hit: the same accumulate_rows on the returned pairs (a padded label gives +inf)
+        if (out_dist64)
+            HIP_TRY(h, launch_pair_distances(h->X, a.Qpad, a.qaux, o.lab, n, k, h->ld, h->space, o.d64, nullptr, s));
+        const size_t at = (size_t)q0 * k;
+        if (int rc = copy_down(h, s, {{out_score, at, o.score, nk}, {out_dist64, at, o.d64, nk}, {out_labels, at, o.lab, nk},
+                                      {out_counts, (size_t)q0, o.cnt, (size_t)n}}))
+            return rc;
+    }
+    return end_call(h, s);
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_scored(mlvdb_index* h, const float* queries, int64_t nq, int32_t k, const mlvdb_score* score,
+                              const mlvdb_where* where, int64_t* out_labels, double* out_score, int32_t* out_counts,
+                              double* out_dist64) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything is checked on the host before anything is launched (the outer program: with_where)
+    ScoreProgram prog;
+    std::vector<int64_t> set;
+    if (int rc = score_prepare(h, score, prog, set)) return rc;
+    if (int rc = check_nq(h, nq)) return rc;
+    if (int rc = check_k_min(h, k)) return rc;
+    if (int rc = check_k_max(h, k, "scored: ")) return rc;
+    if (nq > 0 && (!queries || !out_labels || !out_score || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (int rc = check_row_limit(h, "scored: ")) return rc;
+    auto call = [&]() { return scored_impl(h, queries, nq, k, prog, set, out_labels, out_score, out_counts, out_dist64); };
     return with_where(h, where, nq, call);
     });
 }

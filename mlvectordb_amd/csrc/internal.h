@@ -26,6 +26,7 @@
 #include "../../include/mlvdb_bits.h"
 #include "../../include/mlvdb_hybrid.h"
 #include "../../include/mlvdb_geo.h"
+#include "../../include/mlvdb_score.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -580,6 +581,52 @@ hipError_t launch_distinct_scan(const DistinctArgs& a, const ExactPlan& p, hipSt
 hipError_t launch_distinct_merge(const DistinctEntry* partial, int32_t nq_sel, const int32_t* nq_sel_dev, const int32_t* qsel,
                                  int32_t nblk, int32_t k, int32_t k_eff, int64_t* out_labels, float* out_dist,
                                  int32_t* out_counts, double* out_d64, int64_t* out_groups, hipStream_t s);
+
+// ---------------------------------------------------------------- scored kNN (kernels_score.hip, include/mlvdb_score.h)
+constexpr int kScoreMaxOps = MLVDB_SCORE_MAX_OPS;
+constexpr int kScoreMaxConds = MLVDB_SCORE_MAX_CONDS;
+constexpr int kScoreMaxOperands = MLVDB_SCORE_MAX_OPS / 2;  // n pushes need n - 1 binary ops: at most 16 pushes in 32 ops
+// One op of a validated score program as the device reads it
+struct ScoreOp {
+    int32_t op;
+    int32_t slot;  // ATTR: the operand's index in ScoreProgram::operands; MATCH: the cond's index
+    int64_t a;     // CONST: the double's bits
+};
+// One distinct (column, default) pair the ATTR ops of a program push, the column resolved on the host
+struct ScoreOperand {
+    const int64_t* col;
+    int64_t dflt;  // the bits of the double an absent value pushes
+    int32_t type;  // MLVDB_ATTR_INT64 or MLVDB_ATTR_FLOAT64
+    int32_t pad;
+};
+// A validated call's programs, one fixed block: uploaded as it stands and staged in LDS once per block of the scan.  The
+// cond programs are concatenated (cond c: cond_ops[cond_off[c] .. cond_off[c + 1])), their set ranges rebased onto one
+// concatenated set table that stays in HBM (ScoredArgs::set), as the per-query filters pack theirs.
+struct ScoreProgram {
+    ScoreOp ops[kScoreMaxOps];
+    ScoreOperand operands[kScoreMaxOperands];
+    int32_t cond_off[kScoreMaxConds + 1];
+    int32_t n_ops, n_operands, n_conds;
+    WhereOp cond_ops[kWhereMaxOps];
+};
+static_assert(sizeof(ScoreProgram) % 16 == 0, "staged in LDS behind the query tile, 16-byte words");
+struct ScoredArgs {
+    const float* X;
+    const float* rn;
+    int64_t total;
+    int32_t ld;
+    int32_t space;
+    const float* Qpad;   // [nq][ld]
+    const double* qaux;  // [nq]
+    int32_t nq;
+    int32_t k;
+    const ScoreProgram* prog;
+    const int64_t* set;  // the conds' concatenated set table (may be null without one)
+    TopEntry* partial;   // [nq][nblk][k]: (score, row), the input of launch_exact_merge
+};
+// the exact scan's geometry; the LDS also holds the programs and, per wave, a panel's operand values
+ExactPlan plan_scored(int64_t nrows, int32_t ld, int32_t nq, int32_t k);
+hipError_t launch_scored_scan(const ScoredArgs& a, const ExactPlan& p, hipStream_t s);
 
 // ---------------------------------------------------------------- grouped kNN (kernels_grouped.hip)
 constexpr int kGroupedMaxSize = MLVDB_GROUPED_MAX_SIZE;  // rows returned per group: one WaveTopK

@@ -680,6 +680,26 @@ class HipScanEngine:
             counts.ctypes.data, _opt(d64), groups.ctypes.data), "search_batch_distinct")
         return (labels, dist, counts, d64, groups) if want64 else (labels, dist, counts, groups)
 
+    # -- scored kNN (include/mlvdb_score.h) -----------------------------------------------
+    def search_scored(self, queries: np.ndarray, k: int, program, where=None, want64: bool = False):
+        """The ``k`` (<= 64) rows with the smallest score per query, the score being the compiled ``score.ScoreProgram``
+        evaluated on the device for every live row -- of those the optional compiled ``where.Program`` matches -- in fp64:
+        the exact top k by (score, label), rows whose score is NaN dropped.  Returns (labels int64 [nq, k], scores float64
+        [nq, k], counts int32) or, with ``want64``, (labels, scores, counts, dist64: the rows' fp64 distances); padding is
+        label -1 / +inf, and ``counts`` tells it from a real +inf score."""
+        queries = self._queries(queries)
+        nq = queries.shape[0]
+        labels, _, counts, d64 = self._knn_outputs((nq, k), want64)
+        scores = np.empty((nq, k), dtype=np.float64)
+        ops = np.ascontiguousarray(program.ops)
+        conds, keep_conds = self._where_array(program.conds)
+        sc = _native.Score(ops.ctypes.data, int(ops.size), conds, len(program.conds))
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_search_batch_scored(
+            self._h, queries.ctypes.data, nq, int(k), C.byref(sc), w, labels.ctypes.data, scores.ctypes.data,
+            counts.ctypes.data, _opt(d64)), "search_batch_scored")
+        return (labels, scores, counts, d64) if want64 else (labels, scores, counts)
+
     # -- grouped kNN (include/mlvdb_grouped.h) --------------------------------------------
     def search_grouped(self, queries: np.ndarray, k: int, group_size: int, attr: int, max_groups: int = 0, where=None,
                        want64: bool = False):

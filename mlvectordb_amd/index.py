@@ -35,6 +35,7 @@ from uuid import UUID
 import numpy as np
 
 from . import _native
+from . import score as _score
 from . import stats as _stats
 from . import where as _where
 from .engine import FacetOverflow, HipScanEngine, ScanEngine, StatsOverflow
@@ -138,6 +139,25 @@ class BatchHits(SequenceABC):
         if isinstance(other, (list, BatchHits)):
             return len(self) == len(other) and all(a == b for a, b in zip(self, other))
         return NotImplemented
+
+
+class ScoredBatchHits(BatchHits):
+    """What ``search_scored`` returns: ``BatchHits`` whose ``scores`` are the fp64 values of the score formula (lower is
+    better, as computed), plus
+
+    ``distances``  float64 [nq, k]  the hits' raw fp64 distances in the index's space (+inf at padding)
+    """
+
+    __slots__ = ("distances",)
+
+    def __init__(self, labels, scores, counts, table, distances: np.ndarray) -> None:
+        super().__init__(labels, scores, counts, table)
+        self.distances = distances
+
+    @classmethod
+    def empty(cls, nq: int) -> "ScoredBatchHits":
+        return cls(np.full((nq, 0), -1, dtype=np.int64), np.zeros((nq, 0)), np.zeros(nq, dtype=np.int32), None,
+                   np.zeros((nq, 0)))
 
 
 class GroupedBatchHits(BatchHits):
@@ -890,6 +910,41 @@ class Index:
         if m_d64 is not None:
             m_d64 = np.where(m_lab >= 0, 1 - m_d64, np.inf) if metric == "cosine" else m_d64
         return LateBatchHits(self._decode_groups(ns, by, kind, codes, counts), scores, counts, offsets, ns.ids, m_lab, m_d64)
+
+    _MAX_TOP_K_SCORED = 64  # MLVDB_MAX_TOPK: one selection list of a wavefront
+
+    def search_scored(self, queries, top_k: int, namespace: str, metric: str, score, *, where: Optional[Mapping] = None,
+                      allowed_ids: Optional[Iterable[UUID]] = None) -> "ScoredBatchHits":
+        """Additive: scored kNN on the device (include/mlvdb_score.h) -- the ``top_k`` rows with the smallest value of the
+        formula ``score`` (score.py: an expression over ``"$distance"``, ``{"$attr": ..}``, ``{"$match": {..}}`` and
+        ``$add $sub $mul $div $min $max $neg $abs``), evaluated in fp64 for every live row -- of those ``where`` (one dict
+        filter) matches -- so the answer is exact, with no candidate window.  Rows whose score is NaN (an absent attribute
+        without a ``$default``, ``0/0``) are dropped; ties go to the earlier row.  ``scores`` are the formula's values,
+        lower is better, returned as computed; ``distances`` the hits' raw fp64 distances.  ``$distance`` is the index's
+        distance -- the squared distance for "l2", ``1 - cosine`` for "cosine" -- so metric "euclidean" is refused: use
+        "l2".  ``top_k`` is clamped to the live row count and to 64.  Recipes:
+
+            bonus               {"$sub": ["$distance", {"$mul": [0.2, {"$match": {"tier": "gold"}}]}]}
+            popularity          {"$div": ["$distance", {"$add": [1, {"$attr": "likes", "$default": 0}]}]}
+            linear age penalty  {"$add": ["$distance", {"$mul": [0.3, {"$min": [1, {"$div": [{"$abs": {"$sub": [
+                                    {"$attr": "year"}, 2024]}}, 10]}]}]}]}
+
+        Every refusal happens before the engine is touched."""
+        self._refuse_sharded("search_scored")
+        if metric == "euclidean":
+            raise ValueError('search_scored: metric "euclidean" is not supported ($distance is the squared distance), use "l2"')
+        self._no_where_list("search_scored", where, allowed_ids)
+        ns = self._ns.get(namespace)
+        program = _score.compile_score(score, self._attributes, ns.strings if ns is not None else {})
+        where_program = self._program(namespace, where)
+        q = self._coerce_queries(queries)
+        nq = q.shape[0]
+        if self._nothing_to_search(ns, top_k, nq, q.shape[1]):
+            return ScoredBatchHits.empty(nq)
+        search = self._engine_entry(ns, "search_scored", "search_scored needs")
+        k = min(int(top_k), ns.total - ns.deleted, self._MAX_TOP_K_SCORED)
+        labels, scores, counts, d64 = search(q, k, program, where=where_program, want64=True)
+        return ScoredBatchHits(labels, scores, counts, ns.ids, d64)
 
     _MAX_TOP_K_SPARSE = 64  # MLVDB_MAX_TOPK: one selection list of a wavefront
 

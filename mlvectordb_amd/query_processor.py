@@ -206,6 +206,31 @@ class QueryProcessor:
                                          rrf_k=rrf_k, fetch_k=fetch_k, fetch_k_sparse=fetch_k_sparse, where=where)
         return self._enrich_many(hits, namespace)
 
+    def find_similar_scored(self, query, top_k: int, score, namespace: str = "default", metric: str = "cosine",
+                            where=None) -> List[dict]:
+        """Additive: "function score" search for one query (``Index.search_scored``): the ``top_k`` (<= 64) vectors with the
+        smallest value of the formula ``score`` over the distance and the declared attributes (score.py), exact over all
+        matching vectors, as ``find_similar_many`` returns a hit (``score``: the formula's value, lower is better).  Recipes:
+
+            bonus               {"$sub": ["$distance", {"$mul": [0.2, {"$match": {"tier": "gold"}}]}]}
+            popularity          {"$div": ["$distance", {"$add": [1, {"$attr": "likes", "$default": 0}]}]}
+            linear age penalty  {"$add": ["$distance", {"$mul": [0.3, {"$min": [1, {"$div": [{"$abs": {"$sub": [
+                                    {"$attr": "year"}, 2024]}}, 10]}]}]}]}
+        """
+        values = getattr(query, "values", query)
+        return self.find_similar_scored_many(np.asarray(values, dtype=np.float32)[None, :], top_k, score, namespace, metric,
+                                             where=where)[0]
+
+    def find_similar_scored_many(self, queries, top_k: int, score, namespace: str = "default", metric: str = "cosine",
+                                 where=None) -> List[List[dict]]:
+        """Batched ``find_similar_scored``: one formula for all queries, one scan.  ``where`` is ``None`` or one dict filter
+        (a predicate has no device form and is refused)."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("find_similar_scored: where must be one dict filter (or None)")
+        if not hasattr(self._index, "search_scored"):
+            raise ValueError("find_similar_scored needs an index with search_scored")
+        return self._enrich_many(self._index.search_scored(queries, top_k, namespace, metric, score, where=where), namespace)
+
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
         if where is None:
             return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric)
