@@ -263,6 +263,16 @@ SCORE_SIGNATURES = {
                                             _P, _P, _P, _P]),
 }
 
+# include/mlvdb_examples.h: recommend / discover -- rows ranked against a set of examples, each judged on its own
+EXAMPLES_MAX = 64
+EXAMPLES_BEST, EXAMPLES_DISCOVER, EXAMPLES_CONTEXT = 0, 1, 2
+EXAMPLE_POS, EXAMPLE_NEG, EXAMPLE_TARGET = 0, 1, 2
+
+EXAMPLES_SIGNATURES = {
+    "mlvdb_search_batch_examples": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32,
+                                              C.POINTER(Where), _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -296,7 +306,8 @@ def load() -> C.CDLL:
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
                                       **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **BITS_SIGNATURES,
                                       **HYBRID_SIGNATURES,
-                                      **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES}.items():
+                                      **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES,
+                                      **EXAMPLES_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

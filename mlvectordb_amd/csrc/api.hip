@@ -116,6 +116,10 @@ struct mlvdb_index {
     // scored kNN (mlvdb_score.h): the call's programs with the conds' set table, a chunk's queries and its outputs -- sized
     // by the chunk (<= kDistinctChunk queries) and k, never by the corpus
     DevBuf score_prog, score_q, score_out;
+    // recommend / discover (mlvdb_examples.h): a chunk's examples, tiles and exclusion table, its staged example rows, its
+    // outputs -- sized by the chunk (<= kExamplesChunk queries) and k -- and the per-(query, row) state of its bags of more
+    // than one tile: 16 B (24 B with one-example tiles) per row and such query, at most EXAMPLES_WS_MB MiB (or one query's)
+    DevBuf ex_in, ex_q, ex_out, ex_state;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -5050,6 +5054,181 @@ int mlvdb_search_batch_scored(mlvdb_index* h, const float* queries, int64_t nq, 
     if (nq > 0 && (!queries || !out_labels || !out_score || !out_counts)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
     if (int rc = check_row_limit(h, "scored: ")) return rc;
     auto call = [&]() { return scored_impl(h, queries, nq, k, prog, set, out_labels, out_score, out_counts, out_dist64); };
+    return with_where(h, where, nq, call);
+    });
+}
+
+
+// ---- recommend / discover (mlvdb_examples.h)
+extern "C++" {
+namespace {
+// The validated call (h->rn is the masked copy when a program restricts the rows; the examples' values are read from h->X,
+// which no mask touches).  Per chunk of queries: the bags cut into tiles (examples_cut), examples, tiles and exclusion labels
+// to the device -> the staging kernel and the query prep -> launch t of the scan walks tile t of every query that has one,
+// the state workspace carrying a bag from one launch to the next -> the merge -> outputs to the host.
+int examples_impl(mlvdb_index* h, int32_t mode, const int64_t* labels, const float* vectors, const int32_t* roles,
+                  const int64_t* off, int64_t nq, int32_t k, int32_t exclude, int64_t* out_labels, int32_t* out_tier,
+                  double* out_value, int32_t* out_counts) {
+    hipStream_t s = h->stream;
+    if (h->total == 0 || h->total == h->deleted) {
+        pad(out_labels, nq * k, -1);
+        pad(out_tier, nq * k, INT32_MAX);
+        pad(out_value, nq * k, __builtin_inf());
+        pad(out_counts, nq, 0);
+        return MLVDB_OK;
+    }
+    if (int rc = begin_call(h, s)) return rc;
+    int32_t most = 0;
+    for (int64_t i = 0; i < nq; ++i) most = std::max(most, (int32_t)(off[i + 1] - off[i]));
+    const int32_t qt = examples_tile_width(h->ld, most);  // one width for the call: the answer does not depend on it
+    const int64_t budget = (int64_t)std::max(1, h->tn.examples_ws_mb) << 20;
+    // (tiles of one example carry a pair's POS distance beside the state)
+    const int64_t per_query = h->total * (int64_t)(sizeof(ExamplesState) + (qt == 1 ? sizeof(double) : 0));
+    std::vector<ExamplesTile> cut, tiles;  // the chunk's tiles query by query / launch by launch
+    std::vector<int32_t> first_tile, launch_at, excl, raw, nblk_of;
+    std::vector<float> raw_rows;
+    std::vector<ExactPlan> plans;
+    for (int64_t q0 = 0; q0 < nq;) {
+        // the chunk: queries while they and their examples fit the chunk and the state of their bags the budget, always at
+        // least one
+        cut.clear();
+        excl.clear();
+        first_tile.assign(1, 0);
+        int32_t slots = 0;
+        int64_t q1 = q0;
+        for (; q1 < nq; ++q1) {
+            if (q1 > q0 && (q1 - q0 >= kExamplesChunk || off[q1 + 1] - off[q0] > kExamplesChunkExamples)) break;
+            const size_t cut_before = cut.size(), excl_before = excl.size();
+            for (int64_t j = off[q1]; exclude && j < off[q1 + 1]; ++j)  // the query's distinct stored labels
+                if (labels[j] >= 0 && std::find(excl.begin() + excl_before, excl.end(), (int32_t)labels[j]) == excl.end())
+                    excl.push_back((int32_t)labels[j]);
+            const int nt = examples_cut(mode, roles + off[q1], (int32_t)(off[q1 + 1] - off[q1]), qt, (int32_t)(off[q1] - off[q0]),
+                                        (int32_t)(q1 - q0), (int32_t)excl_before, (int32_t)(excl.size() - excl_before), cut);
+            if (nt > 1) {
+                if (q1 > q0 && (slots + 1) * per_query > budget) {
+                    cut.resize(cut_before);
+                    excl.resize(excl_before);
+                    break;
+                }
+                for (size_t i = cut_before; i < cut.size(); ++i) cut[i].state = slots;
+                ++slots;
+            }
+            first_tile.push_back((int32_t)cut.size());
+        }
+        const int32_t n = (int32_t)(q1 - q0);
+        const int64_t e0 = off[q0];
+        const size_t ne = (size_t)(off[q1] - e0), nk = (size_t)n * k;
+        // launch t: tile t of every query that has one
+        int32_t launches = 0;
+        for (int32_t i = 0; i < n; ++i) launches = std::max(launches, first_tile[(size_t)i + 1] - first_tile[(size_t)i]);
+        tiles.clear();
+        launch_at.assign(1, 0);
+        for (int32_t t = 0; t < launches; ++t) {
+            for (int32_t i = 0; i < n; ++i)
+                if (first_tile[(size_t)i] + t < first_tile[(size_t)i + 1]) tiles.push_back(cut[(size_t)(first_tile[(size_t)i] + t)]);
+            launch_at.push_back((int32_t)tiles.size());
+        }
+        plans.clear();
+        int32_t stride = 1;
+        for (int32_t t = 0; t < launches; ++t) {
+            plans.push_back(plan_examples(h->total, h->ld, qt, launch_at[(size_t)t + 1] - launch_at[(size_t)t]));
+            stride = std::max(stride, plans.back().nblk);
+        }
+        nblk_of.resize((size_t)n);
+        for (int32_t i = 0; i < n; ++i) nblk_of[(size_t)i] = plans[(size_t)(first_tile[(size_t)i + 1] - first_tile[(size_t)i] - 1)].nblk;
+        // the raw examples' rows, packed
+        raw.assign(ne, -1);
+        raw_rows.clear();
+        for (size_t j = 0; j < ne; ++j)
+            if (labels[e0 + (int64_t)j] < 0) {
+                raw[j] = (int32_t)(raw_rows.size() / (size_t)h->dim);
+                raw_rows.insert(raw_rows.end(), vectors + (size_t)(e0 + (int64_t)j) * h->dim, vectors + (size_t)(e0 + (int64_t)j + 1) * h->dim);
+            }
+        int64_t* lab_d = nullptr;
+        ExamplesTile* tiles_d = nullptr;
+        float* rows_d = nullptr;
+        int32_t *raw_d = nullptr, *excl_d = nullptr, *nblk_d = nullptr;
+        CARVE(h, h->ex_in, [&](Carver& c) {
+            lab_d = c.take<int64_t>(ne);
+            tiles_d = c.take<ExamplesTile>(tiles.size());
+            rows_d = c.take<float>(raw_rows.size());
+            raw_d = c.take<int32_t>(ne);
+            excl_d = c.take<int32_t>(excl.size() + 1);
+            nblk_d = c.take<int32_t>((size_t)n);
+        });
+        double* o_val = nullptr;
+        int64_t* o_lab = nullptr;
+        int32_t *o_tier = nullptr, *o_cnt = nullptr;
+        CARVE(h, h->ex_out, [&](Carver& c) {
+            o_val = c.take<double>(nk);
+            o_lab = c.take<int64_t>(nk);
+            o_tier = c.take<int32_t>(nk);
+            o_cnt = c.take<int32_t>((size_t)n);
+        });
+        HIP_TRY(h, h->ex_q.ensure(ne * h->dim * sizeof(float)));
+        HIP_TRY(h, h->qpad.ensure(ne * h->ld * sizeof(float)));
+        HIP_TRY(h, h->qaux.ensure(ne * sizeof(double)));
+        HIP_TRY(h, h->ex_state.ensure((size_t)slots * (size_t)per_query));
+        HIP_TRY(h, h->partial.ensure(nk * (size_t)stride * sizeof(TopEntry)));
+        HIP_TRY(h, hipMemcpyAsync(lab_d, labels + e0, ne * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(tiles_d, tiles.data(), tiles.size() * sizeof(ExamplesTile), hipMemcpyHostToDevice, s));
+        if (!raw_rows.empty())
+            HIP_TRY(h, hipMemcpyAsync(rows_d, raw_rows.data(), raw_rows.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(raw_d, raw.data(), ne * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (!excl.empty()) HIP_TRY(h, hipMemcpyAsync(excl_d, excl.data(), excl.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(nblk_d, nblk_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, launch_examples_stage(h->X, h->dim, h->ld, lab_d, raw_d, rows_d, (int32_t)ne, h->ex_q.as<float>(), s));
+        HIP_TRY(h, launch_query_prep(h->ex_q.as<float>(), (int32_t)ne, h->dim, h->ld, h->space, h->qpad.as<float>(),
+                                     h->qaux.as<double>(), nullptr, s));
+        ExamplesArgs a{};
+        a.X = h->X;
+        a.rn = h->rn;
+        a.total = h->total;
+        a.ld = h->ld;
+        a.space = h->space;
+        a.Qpad = h->qpad.as<float>();
+        a.qaux = h->qaux.as<double>();
+        a.k = k;
+        a.excl = excl_d;
+        a.state = h->ex_state.as<ExamplesState>();
+        a.held = reinterpret_cast<double*>(a.state + (size_t)slots * (size_t)h->total);
+        a.partial = h->partial.as<TopEntry>();
+        a.partial_stride = stride;
+        for (int32_t t = 0; t < launches; ++t) {
+            a.tiles = tiles_d + launch_at[(size_t)t];
+            a.ntiles = launch_at[(size_t)t + 1] - launch_at[(size_t)t];
+            const ExactPlan& plan = plans[(size_t)t];
+            if (int rc = scan_step(h, s, h->total * a.ntiles, [&] { return launch_examples_scan(a, plan, s); })) return rc;
+        }
+        h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+        HIP_TRY(h, launch_examples_merge(a.partial, n, nblk_d, stride, k, o_lab, o_tier, o_val, o_cnt, s));
+        const size_t at = (size_t)q0 * k;
+        // (the wait inside also ends the reads of this chunk's host vectors)
+        if (int rc = copy_down(h, s, {{out_value, at, o_val, nk}, {out_labels, at, o_lab, nk}, {out_tier, at, o_tier, nk},
+                                      {out_counts, (size_t)q0, o_cnt, (size_t)n}}))
+            return rc;
+        q0 = q1;
+    }
+    return end_call(h, s);
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_search_batch_examples(mlvdb_index* h, int32_t mode, const int64_t* example_labels, const float* example_vectors,
+                                const int32_t* example_roles, const int64_t* example_offsets, int64_t nq, int32_t k,
+                                int32_t exclude_examples, const mlvdb_where* where, int64_t* out_labels, int32_t* out_tier,
+                                double* out_value, int32_t* out_counts) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything is checked on the host before anything is launched (the program: with_where)
+    const ExamplesRefusal r = examples_check(mode, example_labels, example_vectors, example_roles, example_offsets, nq, k,
+                                             MLVDB_MAX_TOPK, h->total, h->dim, out_labels,
+                                             out_tier, out_value, out_counts);
+    if (r.code != MLVDB_OK) return fail(h, r.code, r.what);
+    if (int rc = check_row_limit(h, "examples: ")) return rc;
+    auto call = [&]() {
+        return examples_impl(h, mode, example_labels, example_vectors, example_roles, example_offsets, nq, k, exclude_examples,
+                             out_labels, out_tier, out_value, out_counts);
+    };
     return with_where(h, where, nq, call);
     });
 }

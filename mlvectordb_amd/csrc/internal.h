@@ -27,9 +27,11 @@
 #include "../../include/mlvdb_hybrid.h"
 #include "../../include/mlvdb_geo.h"
 #include "../../include/mlvdb_score.h"
+#include "../../include/mlvdb_examples.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
+#include "examples_plan.h"
 
 namespace mlvdb {
 
@@ -141,7 +143,8 @@ constexpr int kQueryImageMaxLds = 64 * 1024;
     X(l2_offset_cache, "L2_OFFSET_CACHE", 1) /* l2: keep the offsets plane across passes of the same scale (0: recompute per pass) */ \
     X(where_gather, "WHERE_GATHER", 150) /* per-query filters: gather a program's rows when matches x query tiles x 1000 <= live x this (0: never; tools/where_each_ab.py) */ \
     X(distinct_oversample, "DISTINCT_OVERSAMPLE", 4) /* distinct kNN: the list pass ranks min(1024, max(64, this x k)) rows per query (0: no list pass, every query takes the grouped exact scan; tools/distinct_ab.py) */ \
-    X(maxsim_ws_mb, "MAXSIM_WS_MB", 1024) /* late interaction: MiB of the [token, document] workspace one chunk of queries may take (always at least one query; every setting returns the same bytes) */
+    X(maxsim_ws_mb, "MAXSIM_WS_MB", 1024) /* late interaction: MiB of the [token, document] workspace one chunk of queries may take (always at least one query; every setting returns the same bytes) */ \
+    X(examples_ws_mb, "EXAMPLES_WS_MB", 1024) /* recommend / discover: MiB of the per-(query, row) state one chunk of queries may take for its bags of more than one tile (always at least one query; every setting returns the same bytes) */
 
 struct Tuning {
 #define X(field, name, dflt) int field = dflt;
@@ -692,6 +695,44 @@ hipError_t launch_like_query(const float* X, int32_t dim, int32_t ld, int32_t sp
 hipError_t launch_like_strip(const int64_t* l_lab, const float* l_dist, const double* l_d64, const int32_t* l_cnt, int32_t nq,
                              int32_t fetch, const int64_t* ex_labels, const int64_t* ex_offsets, int32_t exclude, int32_t k,
                              int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64, hipStream_t s);
+
+// ---------------------------------------------------------------- recommend / discover (kernels_examples.hip, include/mlvdb_examples.h)
+constexpr int64_t kExamplesChunk = 1024;           // queries of one chunk
+constexpr int64_t kExamplesChunkExamples = 16384;  // ... and their examples (always at least one query)
+// The per-(query, row) state a bag of several tiles carries from one launch to the next: BEST (p, n), DISCOVER (d_target,
+// pairs missed so far -- a small integer, exact), CONTEXT (s, unused)
+struct __attribute__((aligned(16))) ExamplesState {
+    double a, b;
+};
+struct ExamplesArgs {
+    const float* X;
+    const float* rn;
+    int64_t total;
+    int32_t ld;
+    int32_t space;
+    const float* Qpad;          // [examples of the chunk][ld]
+    const double* qaux;         // [examples of the chunk]
+    const ExamplesTile* tiles;  // the tiles of THIS launch, one per block row
+    int32_t ntiles;
+    int32_t k;
+    const int32_t* excl;   // the chunk's exclusion table (ExamplesTile::excl_off)
+    ExamplesState* state;  // [state slots][total]
+    double* held;          // [state slots][total]: tiles of one example only -- the POS distance of the pair a tile boundary splits
+    TopEntry* partial;     // [queries of the chunk][partial_stride][k]: (value, row, tier); a query's last tile writes its lists
+    int32_t partial_stride;
+};
+// raw[j] >= 0: row raw[j] of `vectors` ([., dim], uploaded); else the stored row labels[j] -> out[j][0 .. dim)
+hipError_t launch_examples_stage(const float* X, int32_t dim, int32_t ld, const int64_t* labels, const int32_t* raw,
+                                 const float* vectors, int32_t n, float* out, hipStream_t s);
+// plan_exact's geometry for tiles of qt examples, ntiles block rows
+ExactPlan plan_examples(int64_t nrows, int32_t ld, int32_t qt, int32_t ntiles);
+// the tile width for bags of at most `most` examples: the smallest of 1, 2, 4, 8 that holds them (8 beyond), halved like
+// plan_exact's until the fp64 image fits
+int32_t examples_tile_width(int32_t ld, int32_t most);
+hipError_t launch_examples_scan(const ExamplesArgs& a, const ExactPlan& p, hipStream_t s);
+// nblk_of[q]: the blocks that wrote query q's partial lists
+hipError_t launch_examples_merge(const TopEntry* partial, int32_t nq, const int32_t* nblk_of, int32_t stride, int32_t k,
+                                 int64_t* out_labels, int32_t* out_tier, double* out_value, int32_t* out_counts, hipStream_t s);
 
 // ---------------------------------------------------------------- late-interaction search (kernels_maxsim.hip)
 constexpr int kMaxsimMaxTokens = MLVDB_MAXSIM_MAX_TOKENS;

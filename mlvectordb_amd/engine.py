@@ -772,6 +772,42 @@ class HipScanEngine:
             "search_batch_like")
         return out_labels, dist, counts, d64, queries
 
+    # -- recommend / discover (include/mlvdb_examples.h) ------------------------------------
+    def search_examples(self, mode: int, labels: np.ndarray, vectors, roles: np.ndarray, offsets: np.ndarray, k: int, *,
+                        exclude: bool = True, where=None):
+        """The ``k`` (<= 64) best rows per query against its bag of examples, each example judged on its own: query ``i``
+        owns the examples ``offsets[i] .. offsets[i + 1] - 1`` (1..64); example ``j`` is the stored row ``labels[j]`` (read
+        on the device) or, with ``labels[j] == -1``, row ``j`` of ``vectors`` (float32 ``[examples, dim]``, ``None`` without
+        one); ``roles[j]`` is ``_native.EXAMPLE_POS / NEG / TARGET`` as ``mode`` (``_native.EXAMPLES_BEST / DISCOVER /
+        CONTEXT``) allows.  Rows are ranked by (tier, value, label) as the header defines them; with ``exclude`` a query's
+        stored examples never come back; ``where`` (a compiled ``where.Program``) restricts the rows, not the examples.
+        Returns (labels int64 [nq, k] padded -1, tiers int32 padded INT32_MAX, values float64 padded +inf, counts int32)."""
+        ex_labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        ex_roles = np.ascontiguousarray(roles, dtype=np.int32).ravel()
+        ex_offsets = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+        if ex_offsets.size < 1 or ex_labels.size != ex_roles.size:
+            raise RuntimeError(f"search_examples: {ex_labels.size} labels, {ex_roles.size} roles, {ex_offsets.size} offsets")
+        nq = ex_offsets.size - 1
+        if nq > 0 and ex_offsets[-1] > ex_labels.size:
+            raise RuntimeError(f"search_examples: the offsets end at {int(ex_offsets[-1])}, there are {ex_labels.size} examples")
+        if vectors is not None:
+            vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+            if vectors.shape != (ex_labels.size, self.dim):
+                raise RuntimeError(f"Wrong dimensionality of the vectors: got {vectors.shape}, index dim {self.dim}, "
+                                   f"{ex_labels.size} examples")
+        k = int(k)
+        shape = (nq, max(k, 0))
+        out_labels = np.empty(shape, dtype=np.int64)
+        tiers = np.empty(shape, dtype=np.int32)
+        values = np.empty(shape, dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.int32)
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_search_batch_examples(
+            self._h, int(mode), _nonempty(ex_labels), _opt(vectors), _nonempty(ex_roles), ex_offsets.ctypes.data, nq, k,
+            1 if exclude else 0, w, out_labels.ctypes.data, tiers.ctypes.data, values.ctypes.data, counts.ctypes.data),
+            "search_batch_examples")
+        return out_labels, tiers, values, counts
+
     # -- late-interaction search (include/mlvdb_maxsim.h) -----------------------------------
     def search_maxsim(self, tokens: np.ndarray, offsets: np.ndarray, k: int, attr: int, where=None,
                       want_matches: bool = False):

@@ -160,6 +160,27 @@ class ScoredBatchHits(BatchHits):
                    np.zeros((nq, 0)))
 
 
+class TieredBatchHits(BatchHits):
+    """What ``search_examples`` / ``search_discover`` return: ``BatchHits`` ranked by (tier, value), plus
+
+    ``tiers``   int32 [nq, k]    the hits' tiers (INT32_MAX at padding), lower first
+    ``values``  float64 [nq, k]  the hits' values inside their tier, as computed (+inf at padding), lower first
+
+    ``scores`` is ``values``: a distance of the index's space (or a sum of such differences), never ``1 - d``.
+    """
+
+    __slots__ = ("tiers", "values")
+
+    def __init__(self, labels, tiers: np.ndarray, values: np.ndarray, counts, table) -> None:
+        super().__init__(labels, values, counts, table)
+        self.tiers, self.values = tiers, values
+
+    @classmethod
+    def empty(cls, nq: int) -> "TieredBatchHits":
+        return cls(np.full((nq, 0), -1, dtype=np.int64), np.zeros((nq, 0), dtype=np.int32), np.zeros((nq, 0)),
+                   np.zeros(nq, dtype=np.int32), None)
+
+
 class GroupedBatchHits(BatchHits):
     """What ``search_many(distinct=..., group_size=...)`` returns: ``BatchHits`` whose rows hold, per query, the groups in rank
     order and each group's members in order, compacted (``counts`` is the total, the valid prefix as everywhere), plus what
@@ -1218,6 +1239,147 @@ class Index:
         out_labels, dist, counts = search_like(labels, np.asarray(per_example, np.float64), offsets, k, base=base,
                                                exclude=bool(exclude_examples), where=program)[:3]
         return BatchHits(out_labels, self._scores(dist, metric), counts, ns.ids)
+
+    _MAX_EXAMPLES = 64        # MLVDB_EXAMPLES_MAX
+    _MAX_TOP_K_EXAMPLES = 64  # MLVDB_MAX_TOPK: one selection list of a wavefront
+
+    @staticmethod
+    def _is_example_vector(e) -> bool:
+        """``e`` is one vector: a ``VectorDTO``-like object, a 1-D array, or a sequence of plain numbers."""
+        if hasattr(e, "values") and not isinstance(e, (dict, np.ndarray)):
+            return True
+        if isinstance(e, np.ndarray):
+            return e.ndim == 1
+        return (isinstance(e, SequenceABC) and not isinstance(e, (str, bytes)) and len(e) > 0
+                and all(isinstance(x, (int, float, np.number)) and not isinstance(x, bool) for x in e))
+
+    def _example_bags(self, what: str, bags, name: str) -> List[list]:
+        """``positive`` / ``negative`` / ``context`` as one list per query; a flat sequence of ids is one query."""
+        if isinstance(bags, (UUID, str, bytes)) or not isinstance(bags, (SequenceABC, np.ndarray)):
+            raise ValueError(f"{what}: {name} must hold one sequence of examples per query")
+        rows = list(bags)
+        if rows and all(isinstance(r, UUID) for r in rows):
+            return [rows]
+        for i, r in enumerate(rows):
+            if isinstance(r, (UUID, str, bytes)) or not isinstance(r, (SequenceABC, np.ndarray)):
+                raise ValueError(f"{what}: {name} mixes per-query sequences with single entries")
+            if self._is_example_vector(r):
+                raise ValueError(f"{what}: {name}[{i}] is one vector where the examples of query {i} are expected; "
+                                 "wrap it in a list")
+        return [list(r) for r in rows]
+
+    def _search_bags(self, what: str, mode: int, bags, top_k: int, namespace: str, metric: str, where, allowed_ids,
+                     exclude_examples: bool) -> "TieredBatchHits":
+        """The tail the two entries share.  ``bags``: per query a list of (example, role); every refusal before the engine."""
+        if metric == "euclidean":
+            raise ValueError(f'{what}: metric "euclidean" is not supported (tiers and sums are defined on the squared '
+                             'distance), use "l2"')
+        self._no_where_list(what, where, allowed_ids)
+        if callable(where):
+            raise ValueError(f"{what}: where must be one dict filter (a predicate has no device form)")
+        for i, bag in enumerate(bags):
+            if len(bag) > self._MAX_EXAMPLES:
+                raise ValueError(f"{what}: query {i} holds {len(bag)} examples, at most {self._MAX_EXAMPLES} are supported")
+        program = self._program(namespace, where)
+        ns = self._ns.get(namespace)
+        nq = len(bags)
+        flat = [e for bag in bags for e, _ in bag]
+        stored = [i for i, e in enumerate(flat) if not self._is_example_vector(e)]
+        for i in stored:
+            if not isinstance(flat[i], UUID):
+                raise ValueError(f"{what}: example {i} is neither the UUID of a stored vector nor a vector (a 1-D array, a "
+                                 f"sequence of numbers or a VectorDTO): {flat[i]!r}")
+        labels = np.full(len(flat), -1, np.int64)
+        if stored:
+            ids = [flat[i] for i in stored]
+            found = ns.ids.lookup(ids) if ns is not None else np.full(len(ids), -1, np.int64)
+            if (found < 0).any():
+                raise ValueError(f"{what}: id {ids[int(np.argmax(found < 0))]} is unknown or removed in namespace {namespace!r}")
+            labels[stored] = found
+        vectors = None
+        if len(stored) < len(flat):
+            dim = ns.dim if ns is not None else None
+            for i, e in enumerate(flat):
+                if labels[i] >= 0:
+                    continue
+                v = np.asarray(getattr(e, "values", e), dtype=np.float32)
+                if v.ndim != 1 or (dim is not None and v.size != dim) or not np.isfinite(v).all():
+                    raise ValueError(f"{what}: example {i} is no finite vector of the namespace's dimensionality")
+                if vectors is None:
+                    dim = v.size
+                    vectors = np.zeros((len(flat), dim), np.float32)
+                vectors[i] = v
+        if self._nothing_to_search(ns, top_k, nq):
+            return TieredBatchHits.empty(nq)
+        search = self._engine_entry(ns, "search_examples", f"{what} needs")
+        roles = np.asarray([r for bag in bags for _, r in bag], np.int32)
+        offsets = np.concatenate([[0], np.cumsum([len(bag) for bag in bags])]).astype(np.int64)
+        k = min(int(top_k), ns.total - ns.deleted, self._MAX_TOP_K_EXAMPLES)
+        out_labels, tiers, values, counts = search(mode, labels, vectors, roles, offsets, k, exclude=bool(exclude_examples),
+                                                   where=program)
+        return TieredBatchHits(out_labels, tiers, values, counts, ns.ids)
+
+    def search_examples(self, positive, top_k: int, namespace: str, metric: str, *, negative=None,
+                        where: Optional[Mapping] = None, exclude_examples: bool = True,
+                        allowed_ids: Optional[Iterable[UUID]] = None) -> "TieredBatchHits":
+        """Additive: "recommend", best score (include/mlvdb_examples.h) -- every row judged against each example on its own
+        instead of against their average (``search_like``).  ``positive`` (and the optional ``negative``) hold one sequence
+        per query; an example is the UUID of a stored vector (read on the device, never sent) or a vector (an array, a
+        sequence of numbers, a ``VectorDTO``); a flat sequence of UUIDs means one query.  Rows nearer to some liked example
+        than to any disliked one come first (tier 0), ranked by the distance to their nearest liked example; the others
+        follow (tier 1), the farthest from its nearest disliked example first (value: minus that distance).  The answer is
+        the exact top ``top_k`` (clamped to the live count and to 64) over all live rows -- of those ``where`` (one dict
+        filter) matches; with ``exclude_examples`` a query's stored examples never come back.  Values are distances of the
+        index's space -- the squared distance for "l2", ``1 - cosine`` for "cosine" -- so metric "euclidean" is refused.
+        At most 64 examples per query, at least one.  Every refusal happens before the engine is touched."""
+        what = "search_examples"
+        self._refuse_sharded(what)
+        pos = self._example_bags(what, positive, "positive")
+        neg = [[] for _ in pos] if negative is None else self._example_bags(what, negative, "negative")
+        if len(neg) != len(pos):
+            raise ValueError(f"{what}: {len(pos)} positive entries, {len(neg)} negative entries")
+        bags = [[(e, _native.EXAMPLE_POS) for e in p] + [(e, _native.EXAMPLE_NEG) for e in n] for p, n in zip(pos, neg)]
+        for i, bag in enumerate(bags):
+            if not bag:
+                raise ValueError(f"{what}: query {i} has no example")
+        return self._search_bags(what, _native.EXAMPLES_BEST, bags, top_k, namespace, metric, where, allowed_ids,
+                                 exclude_examples)
+
+    def search_discover(self, top_k: int, namespace: str, metric: str, *, target=None, context,
+                        where: Optional[Mapping] = None, exclude_examples: bool = True,
+                        allowed_ids: Optional[Iterable[UUID]] = None) -> "TieredBatchHits":
+        """Additive: "discover" / "context" search (include/mlvdb_examples.h).  ``context`` holds per query a sequence of
+        (positive, negative) pairs of examples (ids or vectors, as in ``search_examples``); each pair cuts the space into
+        the half nearer to its positive.  With ``target`` (one example per query) the rows are ranked by the number of
+        pairs they miss (tier), then by their distance to the target (value): the target is searched inside as many of
+        the half-spaces as possible, and without pairs this is the plain exact search.  ``target=None`` selects context
+        mode (at least one pair per query): tier 0 for every row, value the sum over the pairs of how much nearer the row
+        is to the negative than to the positive, 0.0 inside every half-space.  Limits and refusals as ``search_examples``:
+        at most 64 examples per query, the target included."""
+        what = "search_discover"
+        self._refuse_sharded(what)
+        if isinstance(context, (UUID, str, bytes)) or not isinstance(context, (SequenceABC, np.ndarray)):
+            raise ValueError(f"{what}: context must hold one sequence of (positive, negative) pairs per query")
+        per_query = [list(c) for c in context]
+        if target is None:
+            targets = [None] * len(per_query)
+        else:
+            # one example (an id, or one vector in any of its forms) is the target of one query; else one per query
+            targets = [target] if isinstance(target, UUID) or self._is_example_vector(target) else list(target)
+            if len(targets) != len(per_query):
+                raise ValueError(f"{what}: {len(targets)} targets, {len(per_query)} context entries")
+        bags = []
+        for i, (t, pairs) in enumerate(zip(targets, per_query)):
+            bag = [] if target is None else [(t, _native.EXAMPLE_TARGET)]
+            for pair in pairs:
+                if isinstance(pair, (UUID, str, bytes)) or not isinstance(pair, (SequenceABC, np.ndarray)) or len(pair) != 2:
+                    raise ValueError(f"{what}: query {i}: every context entry must be a (positive, negative) pair")
+                bag += [(pair[0], _native.EXAMPLE_POS), (pair[1], _native.EXAMPLE_NEG)]
+            if target is None and not pairs:
+                raise ValueError(f"{what}: query {i} has neither a target nor a context pair")
+            bags.append(bag)
+        mode = _native.EXAMPLES_CONTEXT if target is None else _native.EXAMPLES_DISCOVER
+        return self._search_bags(what, mode, bags, top_k, namespace, metric, where, allowed_ids, exclude_examples)
 
     def _compile_each(self, namespace: str, wheres) -> Tuple[list, np.ndarray]:
         for w in wheres:

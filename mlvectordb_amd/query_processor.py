@@ -231,6 +231,55 @@ class QueryProcessor:
             raise ValueError("find_similar_scored needs an index with search_scored")
         return self._enrich_many(self._index.search_scored(queries, top_k, namespace, metric, score, where=where), namespace)
 
+    def recommend(self, positive, top_k: int, namespace: str = "default", metric: str = "cosine", negative=None,
+                  where=None, exclude_examples: bool = True) -> List[dict]:
+        """Additive: "recommend", best score, for one query (``Index.search_examples``): ``positive`` / ``negative`` are
+        sequences of examples -- ids of stored vectors or vectors -- each judged on its own; hits as ``find_similar_many``
+        returns them (``score``: the value inside the tier, a distance, lower is better) plus ``tier``."""
+        return self.recommend_many([list(positive)], top_k, namespace, metric,
+                                   negative=None if negative is None else [list(negative)], where=where,
+                                   exclude_examples=exclude_examples)[0]
+
+    def recommend_many(self, positive, top_k: int, namespace: str = "default", metric: str = "cosine", negative=None,
+                       where=None, exclude_examples: bool = True) -> List[List[dict]]:
+        """Batched ``recommend``: one sequence of examples per query, one chain of scans.  ``where`` is ``None`` or one dict
+        filter (a predicate has no device form and is refused)."""
+        self._examples_entry("recommend", "search_examples", where)
+        hits = self._index.search_examples(positive, top_k, namespace, metric, negative=negative, where=where,
+                                           exclude_examples=exclude_examples)
+        return self._with_tiers(hits, namespace)
+
+    def discover(self, top_k: int, namespace: str = "default", metric: str = "cosine", target=None, context=(),
+                 where=None, exclude_examples: bool = True) -> List[dict]:
+        """Additive: "discover" (with ``target``) / "context" (without) search for one query (``Index.search_discover``):
+        ``context`` is a sequence of (positive, negative) pairs of examples; hits as ``recommend`` returns them."""
+        return self.discover_many(top_k, namespace, metric, target=None if target is None else [target],
+                                  context=[list(context)], where=where, exclude_examples=exclude_examples)[0]
+
+    def discover_many(self, top_k: int, namespace: str = "default", metric: str = "cosine", target=None, context=(),
+                      where=None, exclude_examples: bool = True) -> List[List[dict]]:
+        """Batched ``discover``: one target (or none at all) and one sequence of pairs per query."""
+        self._examples_entry("discover", "search_discover", where)
+        hits = self._index.search_discover(top_k, namespace, metric, target=target, context=context, where=where,
+                                           exclude_examples=exclude_examples)
+        return self._with_tiers(hits, namespace)
+
+    def _examples_entry(self, what: str, method: str, where) -> None:
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"{what}: where must be one dict filter (or None)")
+        if not hasattr(self._index, method):
+            raise ValueError(f"{what} needs an index with {method}")
+
+    def _with_tiers(self, hits, namespace: str) -> List[List[dict]]:
+        """``_enrich_many`` plus each hit's ``tier``."""
+        out = self._enrich_many(hits, namespace)
+        by_id = [dict(zip(ids[:n].tolist(), tiers[:n].tolist()))
+                 for ids, tiers, n in zip(hits.ids(), hits.tiers, hits.counts.tolist())]
+        for rows, tier_of in zip(out, by_id):
+            for row in rows:
+                row["tier"] = tier_of[row["id"]]
+        return out
+
     def _search_many(self, queries, top_k: int, namespace: str, metric: str, where):
         if where is None:
             return self._index.search_many(queries, top_k=top_k, namespace=namespace, metric=metric)
