@@ -273,6 +273,15 @@ EXAMPLES_SIGNATURES = {
                                               C.POINTER(Where), _P, _P, _P, _P]),
 }
 
+# include/mlvdb_join.h: similarity join -- the stored rows within a radius of given stored rows, the queries gathered on the device
+JOIN_OTHERS, JOIN_LATER = 0, 1
+JOIN_WAVE = 256  # left rows per pass of the range chain inside one native call (internal.h: kJoinWave)
+JOIN_MAX_CAPACITY = MAX_TOPK_PAGED - JOIN_WAVE
+JOIN_SIGNATURES = {
+    "mlvdb_join_within": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_float, C.c_int64, C.c_int64, C.POINTER(Where),
+                                    _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -307,7 +316,7 @@ def load() -> C.CDLL:
                                       **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **BITS_SIGNATURES,
                                       **HYBRID_SIGNATURES,
                                       **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES,
-                                      **EXAMPLES_SIGNATURES}.items():
+                                      **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

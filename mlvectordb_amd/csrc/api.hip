@@ -120,6 +120,10 @@ struct mlvdb_index {
     // outputs -- sized by the chunk (<= kExamplesChunk queries) and k -- and the per-(query, row) state of its bags of more
     // than one tile: 16 B (24 B with one-example tiles) per row and such query, at most EXAMPLES_WS_MB MiB (or one query's)
     DevBuf ex_in, ex_q, ex_out, ex_state;
+    // similarity join (mlvdb_join.h): the call's left labels (pack_range_hits reuses labels_in), a wave's labels, self
+    // distances, results and dense outputs -- sized by the wave (<= kJoinWave rows) and `capacity` -- and the packed hits of
+    // the call so far: 12 B per returned hit, grown as they come, never beyond total_capacity
+    DevBuf join_left, join_ws, join_lab, join_dist;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -1842,8 +1846,11 @@ static int pack_range_hits(mlvdb_index* h, hipStream_t s, int64_t nq, int64_t ca
 // The range passes of a call (between its begin_call and end_call; the index holds live rows, nq >= 1): the ranked hits of
 // query i -- its nearest min(count, cap_eff) -- are left on the device in rows i of h->io_lab / h->io_dist (cap_eff slots each),
 // counts[i] is its exact hit count and offsets ([nq + 1]) the packed layout of the returned hits.
+// queries == nullptr: the caller has left them on the device, dense in h->io_q (at least nq * dim floats, written on `s`).
+// row_begin: the caller knows that no row below it can be a hit (the join has masked them out): the filter scan starts at
+// that row's tile; every other kernel of the chain sees all rows.
 static int range_ranked(mlvdb_index* h, hipStream_t s, const float* queries, int64_t nq, float radius, int64_t cap_eff,
-                        std::vector<int64_t>& counts, std::vector<int64_t>& offsets) {
+                        std::vector<int64_t>& counts, std::vector<int64_t>& offsets, int64_t row_begin = 0) {
     int rc = MLVDB_OK;
     HIP_TRY(h, h->io_q.ensure((size_t)nq * h->dim * sizeof(float)));
     HIP_TRY(h, h->qpad.ensure((size_t)nq * h->ld * sizeof(float)));
@@ -1852,8 +1859,10 @@ static int range_ranked(mlvdb_index* h, hipStream_t s, const float* queries, int
     HIP_TRY(h, h->io_dist.ensure((size_t)nq * cap_eff * sizeof(float)));
     HIP_TRY(h, h->io_cnt.ensure((size_t)nq * sizeof(int64_t)));
     HIP_TRY(h, h->pin_in.ensure(std::max((size_t)nq * h->dim * sizeof(float), ((size_t)nq + 1) * sizeof(int64_t))));
-    std::memcpy(h->pin_in.p, queries, (size_t)nq * h->dim * sizeof(float));  // pinned staging: one DMA (search_host)
-    HIP_TRY(h, hipMemcpyAsync(h->io_q.p, h->pin_in.p, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
+    if (queries) {
+        std::memcpy(h->pin_in.p, queries, (size_t)nq * h->dim * sizeof(float));  // pinned staging: one DMA (search_host)
+        HIP_TRY(h, hipMemcpyAsync(h->io_q.p, h->pin_in.p, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(h, h->qerr.ensure((size_t)nq * sizeof(float)));
     bool ready = false;
     rc = filter_ready(h, s, nq, &ready);
@@ -1877,10 +1886,10 @@ static int range_ranked(mlvdb_index* h, hipStream_t s, const float* queries, int
             HIP_TRY(h, launch_filter_state(fa, s));  // per-query state only (no image: the exact range scan reads Qpad)
             h->stats.bound_dtype = 0;
         }
-        rc = scan_step(h, s, h->total, [&]() -> hipError_t {
+        rc = scan_step(h, s, filt ? h->total - row_begin : h->total, [&]() -> hipError_t {
             if (!filt) return launch_exact_range_scan(fa, radius, nullptr, 0, s);
             const hipError_t e = launch_filter_range_thr(fa, radius, s);
-            return e != hipSuccess ? e : launch_filter_scan(fa, 0, h->total, s);
+            return e != hipSuccess ? e : launch_filter_scan(fa, row_begin, h->total, s);
         });
         if (rc) return rc;
         int32_t n_flagged = 0;
@@ -3545,6 +3554,193 @@ int mlvdb_search_batch_like(mlvdb_index* h, const int64_t* example_labels, const
     };
     // the first launches: where_run(h, where, ...) for the program, then like_impl under with_row_mask(h, nq, ...)
     return with_where(h, where, nq, call);
+    });
+}
+
+// ---- similarity join (mlvdb_join.h)
+extern "C++" {
+namespace {
+// Room for `need` packed hits behind the `used` the call already holds (join_lab / join_dist grow by doubling, bounded by the
+// caller's total_capacity; what they hold moves along).
+int join_reserve(mlvdb_index* h, hipStream_t s, int64_t used, int64_t need, int64_t total_capacity) {
+    const int64_t have = (int64_t)(h->join_lab.bytes / sizeof(int64_t));
+    if (need <= have && (size_t)need * sizeof(float) <= h->join_dist.bytes) return MLVDB_OK;
+    const int64_t cap = std::min<int64_t>(total_capacity, std::max<int64_t>({need, 2 * have, 65536}));
+    Staged<DevBuf> nl(s), nd(s);
+    HIP_TRY(h, nl.exact((size_t)cap * sizeof(int64_t)));
+    HIP_TRY(h, nd.exact((size_t)cap * sizeof(float)));
+    if (used > 0) {
+        HIP_TRY(h, hipMemcpyAsync(nl.p, h->join_lab.p, (size_t)used * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(nd.p, h->join_dist.p, (size_t)used * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(h, hipStreamSynchronize(s));
+    h->join_lab = std::move(nl);
+    h->join_dist = std::move(nd);
+    return MLVDB_OK;
+}
+
+// The validated call, under with_row_mask: h->rn is the masked copy of the norms (`where`, or every live row), and
+// h->rp8_masked that of the row pairs when the int8 shadow serves the call.  Per wave of <= kJoinWave left rows: their values
+// gathered into h->io_q -> LATER: the rows below the wave's first label leave the masked copies -> the range passes at
+// capacity + kJoinWave, the filter scan starting at that label's tile -> strip -> counts to the host -> pack.  A row whose
+// truncated list cannot give its count (LATER, not the head of its wave) heads the next wave: a wave always resolves its
+// first row, so the call ends.
+int join_impl(mlvdb_index* h, const int64_t* left, int64_t n_left, int32_t mode, float radius, int64_t capacity,
+              int64_t total_capacity, int64_t* out_labels, float* out_dist, int64_t* out_offsets, int64_t* out_counts) {
+    hipStream_t s = h->stream;
+    int rc = begin_call(h, s);
+    if (rc) return rc;
+    const int64_t cap_eff = capacity + kJoinWave;  // the wave's own rows may stand in the way of the nearest `capacity`
+    const bool later = mode == MLVDB_JOIN_LATER;
+    const bool want_hits = total_capacity > 0;
+    HIP_TRY(h, h->join_left.ensure((size_t)n_left * sizeof(int64_t)));
+    HIP_TRY(h, hipMemcpyAsync(h->join_left.p, left, (size_t)n_left * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, h->io_q.ensure((size_t)kJoinWave * h->dim * sizeof(float)));  // (range_ranked asks for no more: no regrowth there)
+    int64_t *w_lab = nullptr, *w_count = nullptr, *d_lab = nullptr;
+    double* w_self = nullptr;
+    int32_t *w_kept = nullptr, *w_flag = nullptr;
+    float* d_dist = nullptr;
+    CARVE(h, h->join_ws, [&](Carver& c) {
+        w_lab = c.take<int64_t>(kJoinWave);
+        w_count = c.take<int64_t>(kJoinWave);
+        w_self = c.take<double>(kJoinWave);
+        d_lab = c.take<int64_t>((size_t)kJoinWave * capacity);
+        d_dist = c.take<float>((size_t)kJoinWave * capacity);
+        w_kept = c.take<int32_t>(kJoinWave);
+        w_flag = c.take<int32_t>(kJoinWave);
+    });
+    std::vector<int64_t> kept_of((size_t)n_left, 0), start_of((size_t)n_left, 0);
+    std::vector<int64_t> redo, wave, wave_labels, counts, offsets;
+    int64_t h_count[kJoinWave];
+    int32_t h_kept[kJoinWave], h_flag[kJoinWave];
+    int64_t next = 0, hidden = 0, used = 0;  // left rows taken; LATER: labels [0, hidden) are masked out; packed hits so far
+    bool in_order = true, fits = true, over = false;
+    while (next < n_left || !redo.empty()) {
+        const int64_t* labels_d = nullptr;
+        wave.clear();
+        if (!redo.empty()) {  // rows of the last wave again, the first flagged one at the head
+            wave.swap(redo);
+            wave_labels.resize(wave.size());
+            for (size_t j = 0; j < wave.size(); ++j) wave_labels[j] = left[wave[j]];
+            HIP_TRY(h, hipMemcpyAsync(w_lab, wave_labels.data(), wave.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            labels_d = w_lab;
+            in_order = false;
+        } else {
+            const int64_t n = std::min<int64_t>(kJoinWave, n_left - next);
+            for (int64_t j = 0; j < n; ++j) wave.push_back(next + j);
+            labels_d = h->join_left.as<int64_t>() + next;
+            next += n;
+        }
+        const int32_t n = (int32_t)wave.size();
+        const int64_t a_lo = left[wave[0]];
+        HIP_TRY(h, launch_join_gather_queries(h->X, labels_d, n, h->dim, h->ld, h->io_q.as<float>(), s));
+        if (later && a_lo > hidden) {
+            HIP_TRY(h, launch_join_mask_advance(h->rn, h->mask_pairs_ready ? h->rp8_masked.as<float>() : nullptr,
+                                                h->space == kSpaceL2 ? 1 : 0, hidden, a_lo, s));
+            // (the l2 offsets plane behind the masked pairs was computed from the pairs of the last wave)
+            if (h->mask_pairs_ready)
+                if (int rc2 = forget_l2_offsets(h, 1, s)) return rc2;
+            hidden = a_lo;
+        }
+        rc = range_ranked(h, s, nullptr, n, radius, cap_eff, counts, offsets, later ? a_lo : 0);
+        if (rc) return rc;
+        bool truncated = false;
+        for (int32_t j = 0; j < n; ++j) truncated |= counts[(size_t)j] > cap_eff;
+        if (truncated)  // the distance of each row to itself, with the bits the range passes gave it (their Qpad / qaux)
+            HIP_TRY(h, launch_pair_distances(h->X, h->qpad.as<float>(), h->qaux.as<double>(), labels_d, n, 1, h->ld, h->space,
+                                             w_self, nullptr, s));
+        HIP_TRY(h, launch_join_strip(h->io_lab.as<int64_t>(), h->io_dist.as<float>(), h->io_cnt.as<int64_t>(), cap_eff, labels_d,
+                                     n, mode, truncated ? w_self : nullptr, radius, h->rn, capacity, d_lab, d_dist, w_count,
+                                     w_kept, w_flag, s));
+        rc = copy_down(h, s, {{h_count, 0, w_count, (size_t)n}, {h_kept, 0, w_kept, (size_t)n}, {h_flag, 0, w_flag, (size_t)n}});
+        if (rc) return rc;
+        const int64_t base = used;
+        for (int32_t j = 0; j < n; ++j) {
+            const size_t i = (size_t)wave[(size_t)j];
+            if (h_flag[j]) {
+                redo.push_back(wave[(size_t)j]);
+                continue;
+            }
+            out_counts[i] = h_count[j];
+            over |= h_count[j] > capacity;
+            kept_of[i] = h_kept[j];
+            start_of[i] = used;
+            used += h_kept[j];
+        }
+        fits = fits && used <= total_capacity;
+        if (want_hits && fits && used > base) {
+            rc = join_reserve(h, s, base, used, total_capacity);
+            if (rc) return rc;
+            HIP_TRY(h, launch_join_pack(d_lab, d_dist, w_kept, w_flag, n, capacity, base, h->join_lab.as<int64_t>(),
+                                        h->join_dist.as<float>(), s));
+        }
+    }
+    out_offsets[0] = 0;
+    for (int64_t i = 0; i < n_left; ++i) out_offsets[i + 1] = out_offsets[i] + kept_of[(size_t)i];
+    if (fits && used > 0) {
+        if (in_order) {  // the packed array is the answer
+            rc = copy_down(h, s, {{out_labels, 0, h->join_lab.as<int64_t>(), (size_t)used},
+                                  {out_dist, 0, h->join_dist.as<float>(), (size_t)used}});
+            if (rc) return rc;
+        } else {  // some rows were resolved after later ones: their hits move to their places on the host
+            std::vector<int64_t> p_lab((size_t)used);
+            std::vector<float> p_dist((size_t)used);
+            rc = copy_down(h, s, {{p_lab.data(), 0, h->join_lab.as<int64_t>(), (size_t)used},
+                                  {p_dist.data(), 0, h->join_dist.as<float>(), (size_t)used}});
+            if (rc) return rc;
+            for (int64_t i = 0; i < n_left; ++i) {
+                const size_t m = (size_t)kept_of[(size_t)i];
+                if (!m) continue;
+                std::memcpy(out_labels + out_offsets[i], p_lab.data() + start_of[(size_t)i], m * sizeof(int64_t));
+                std::memcpy(out_dist + out_offsets[i], p_dist.data() + start_of[(size_t)i], m * sizeof(float));
+            }
+        }
+    }
+    rc = end_call(h, s);
+    if (rc) return rc;
+    if (!fits)
+        return fail(h, MLVDB_ERR_OVERFLOW, "join: more hits in all than total_capacity; out_counts / out_offsets hold the exact "
+                                           "counts and the layout the hits need, out_labels / out_dist nothing");
+    if (over) return fail(h, MLVDB_ERR_OVERFLOW, "join: some row has more partners than `capacity`; out_counts holds the exact counts");
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_join_within(mlvdb_index* h, const int64_t* left_labels, int64_t n_left, int32_t mode, float radius,
+                      int64_t capacity, int64_t total_capacity, const mlvdb_where* where, int64_t* out_labels,
+                      float* out_dist, int64_t* out_offsets, int64_t* out_counts) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything is checked on the host before anything is launched (the program: where_run validates it first)
+    if (int rc = check_nq(h, n_left)) return rc;
+    if (mode != MLVDB_JOIN_OTHERS && mode != MLVDB_JOIN_LATER) return fail(h, MLVDB_ERR_INVALID_ARG, "join: unknown mode");
+    if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
+    if (total_capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "total_capacity must be >= 0");
+    if (capacity > MLVDB_JOIN_MAX_CAPACITY) return fail(h, MLVDB_ERR_UNSUPPORTED, "join: capacity above MLVDB_JOIN_MAX_CAPACITY");
+    if (!out_offsets || (n_left > 0 && (!left_labels || !out_counts)) || (total_capacity > 0 && (!out_labels || !out_dist)))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    for (int64_t i = 0; i < n_left; ++i) {
+        if (left_labels[i] < 0 || left_labels[i] >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "join: left label out of range");
+        if (i > 0 && left_labels[i] <= left_labels[i - 1])
+            return fail(h, MLVDB_ERR_INVALID_ARG, "join: left labels must ascend strictly");
+    }
+    if (where)
+        if (int rc = where_prepare(h, where)) return rc;
+    if (n_left == 0 || h->total == h->deleted) {  // no left row, or no live row to be a partner
+        for (int64_t i = 0; i < n_left; ++i) out_counts[i] = 0;
+        for (int64_t i = 0; i <= n_left; ++i) out_offsets[i] = 0;
+        return MLVDB_OK;
+    }
+    if (where) {
+        if (int rc = where_run(h, where, nullptr)) return rc;
+    } else {  // the call always runs under a row mask: all ones
+        HIP_TRY(h, h->row_mask.ensure((size_t)h->total));
+        HIP_TRY(h, hipMemsetAsync(h->row_mask.p, 1, (size_t)h->total, h->stream));
+    }
+    return with_row_mask(h, std::min<int64_t>(n_left, kJoinWave), [&]() {
+        return join_impl(h, left_labels, n_left, mode, radius, capacity, total_capacity, out_labels, out_dist, out_offsets,
+                         out_counts);
+    });
     });
 }
 

@@ -28,6 +28,7 @@
 #include "../../include/mlvdb_geo.h"
 #include "../../include/mlvdb_score.h"
 #include "../../include/mlvdb_examples.h"
+#include "../../include/mlvdb_join.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -695,6 +696,28 @@ hipError_t launch_like_query(const float* X, int32_t dim, int32_t ld, int32_t sp
 hipError_t launch_like_strip(const int64_t* l_lab, const float* l_dist, const double* l_d64, const int32_t* l_cnt, int32_t nq,
                              int32_t fetch, const int64_t* ex_labels, const int64_t* ex_offsets, int32_t exclude, int32_t k,
                              int64_t* out_labels, float* out_dist, int32_t* out_counts, double* out_d64, hipStream_t s);
+
+// ---------------------------------------------------------------- similarity join (kernels_join.hip, include/mlvdb_join.h)
+constexpr int kJoinWave = 256;  // left rows of one wave: one pass of the range chain (kFilterQueries)
+// One block per left row: out ([n, dim] dense fp32) = the stored values of rows labels[0 .. n) (inside [0, total): the entry
+// point checked it).
+hipError_t launch_join_gather_queries(const float* X, const int64_t* labels, int32_t n, int32_t dim, int32_t ld, float* out,
+                                      hipStream_t s);
+// rn[lo .. hi) = NaN and, with rp8 (the masked row pairs; may be null), their pairs "not a row" (l2: the x slot stays).
+hipError_t launch_join_mask_advance(float* rn, float* rp8, int l2, int64_t lo, int64_t hi, hipStream_t s);
+// One block per left row over its ranked list (l_lab / l_dist: [n][cap_eff], l_cnt[i] the exact inner count): the entries with
+// label == left[i] (OTHERS) or <= left[i] (LATER) dropped, the first `capacity` survivors to out_labels / out_dist
+// ([n][capacity]), out_kept[i] their number, out_count[i] the exact number of partners, out_flag[i] = 1 where a truncated
+// list cannot give it (the row wants a wave of its own).  self64 (may be null when no list is truncated): the distance of
+// each row to itself; rn: the call's masked norms.
+hipError_t launch_join_strip(const int64_t* l_lab, const float* l_dist, const int64_t* l_cnt, int64_t cap_eff,
+                             const int64_t* left, int32_t n, int32_t mode, const double* self64, float radius, const float* rn,
+                             int64_t capacity, int64_t* out_labels, float* out_dist, int64_t* out_count, int32_t* out_kept,
+                             int32_t* out_flag, hipStream_t s);
+// One block per left row (n <= kJoinWave): its kept entries to p_lab / p_dist at base + the kept counts of the unflagged rows
+// before it.
+hipError_t launch_join_pack(const int64_t* d_lab, const float* d_dist, const int32_t* kept, const int32_t* flag, int32_t n,
+                            int64_t capacity, int64_t base, int64_t* p_lab, float* p_dist, hipStream_t s);
 
 // ---------------------------------------------------------------- recommend / discover (kernels_examples.hip, include/mlvdb_examples.h)
 constexpr int64_t kExamplesChunk = 1024;           // queries of one chunk

@@ -109,6 +109,15 @@ class StatsOverflow(RuntimeError):
         self.max_groups, self.n_groups, self.matched, self.by_absent = max_groups, n_groups, matched, by_absent
 
 
+class JoinOverflow(RuntimeError):
+    """A self-join met a row with more than ``max_per_row`` partners, so its pair list is truncated and does not determine
+    the connected components (``duplicate_groups``).  ``most`` is the largest exact partner count."""
+
+    def __init__(self, max_per_row: int, most: int) -> None:
+        super().__init__(f"duplicate_groups: a row has {most} partners within the radius, more than max_per_row={max_per_row}")
+        self.max_per_row, self.most = max_per_row, most
+
+
 class MaxSimOverflow(RuntimeError):
     """A late-interaction call met more than ``max_groups`` documents among the rows it counts (``MLVDB_ERR_OVERFLOW``)."""
 
@@ -772,6 +781,28 @@ class HipScanEngine:
             "search_batch_like")
         return out_labels, dist, counts, d64, queries
 
+    # -- similarity join (include/mlvdb_join.h) ---------------------------------------------
+    def join_within(self, labels: np.ndarray, mode: int, radius: float, capacity: int, where=None, truncate: bool = False):
+        """The stored rows within ``radius`` of the stored rows ``labels`` (strictly ascending; tombstoned ones allowed), the
+        queries gathered on the device: per left row what ``range(get_rows_at(labels), radius, ..., where=where)`` returns
+        for it, bit for bit, without the row itself (``_native.JOIN_OTHERS``) or without every label <= its own
+        (``_native.JOIN_LATER``: every unordered pair once).  Returns (``RangeHits``, exact counts int64 [n]); ``capacity``
+        and ``truncate`` as in ``range``, the most per row being ``_native.JOIN_MAX_CAPACITY``.  The first call leaves room
+        for 16 partners per row on average (near-duplicates are few); when the hits need more, the call is repeated with
+        the sizes the first one reported."""
+        left = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        n = int(left.size)
+        w, keep = self._where_arg(where)
+
+        def call(capacity, total, out_labels, dist, offsets, counts):
+            return self._lib.mlvdb_join_within(self._h, _nonempty(left), n, int(mode), float(radius), capacity, total, w,
+                                               out_labels.ctypes.data, dist.ctypes.data, offsets.ctypes.data,
+                                               _nonempty(counts))
+
+        out_labels, dist, offsets, counts = self._range_packed_counts(call, n, capacity, truncate, _native.JOIN_MAX_CAPACITY,
+                                                                      16, "join_within")
+        return RangeHits(out_labels, dist, offsets), counts
+
     # -- recommend / discover (include/mlvdb_examples.h) ------------------------------------
     def search_examples(self, mode: int, labels: np.ndarray, vectors, roles: np.ndarray, offsets: np.ndarray, k: int, *,
                         exclude: bool = True, where=None):
@@ -1008,23 +1039,28 @@ class HipScanEngine:
         """The protocol of the packed range entries: a first guess of ``total_capacity`` (room for 256 hits per query on
         average) and one repeat with the sizes the first call reported.  ``call(capacity, total, labels, dist, offsets,
         counts)`` -> status.  Returns (labels, dist, offsets)."""
-        capacity = max(1, min(int(capacity), _native.MAX_TOPK_PAGED))
-        total = min(nq * capacity, max(65_536, 256 * nq))
+        return self._range_packed_counts(call, nq, capacity, truncate)[:3]
+
+    def _range_packed_counts(self, call, nq: int, capacity: int, truncate: bool, cap_max: int = _native.MAX_TOPK_PAGED,
+                             per_query: int = 256, what: str = "range_batch_packed"):
+        """``_range_packed`` with the exact counts behind its answer: (labels, dist, offsets, counts).  ``cap_max``: the most
+        hits per query the entry ranks; ``per_query``: the hits per query the first guess leaves room for on average."""
+        capacity = max(1, min(int(capacity), cap_max))
+        total = min(nq * capacity, max(65_536, per_query * nq))
         while True:
             labels = np.empty(total, dtype=np.int64)
             dist = np.empty(total, dtype=np.float32)
             offsets = np.zeros(nq + 1, dtype=np.int64)
             counts = np.zeros(nq, dtype=np.int64)
-            rc = self._check(call(capacity, total, labels, dist, offsets, counts), "range_batch_packed",
-                             allow=(_native.ERR_OVERFLOW,))
+            rc = self._check(call(capacity, total, labels, dist, offsets, counts), what, allow=(_native.ERR_OVERFLOW,))
             if rc == _native.OK:
                 break
-            need_cap = capacity if truncate else min(max(int(counts.max(initial=0)), capacity), _native.MAX_TOPK_PAGED)
+            need_cap = capacity if truncate else min(max(int(counts.max(initial=0)), capacity), cap_max)
             need_total = int(np.minimum(counts, need_cap).sum())
             if need_cap == capacity and need_total <= total:
                 break  # per-query truncation was asked for (or the engine's limit reached): the outputs hold the nearest
             capacity, total = need_cap, max(need_total, 1)
-        return labels, dist, offsets
+        return labels, dist, offsets, counts
 
     def range_each(self, queries: np.ndarray, radius: float, capacity: int, programs, program_of_query,
                    truncate: bool = False, return_routes: bool = False):

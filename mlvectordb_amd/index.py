@@ -35,10 +35,11 @@ from uuid import UUID
 import numpy as np
 
 from . import _native
+from . import join as _join
 from . import score as _score
 from . import stats as _stats
 from . import where as _where
-from .engine import FacetOverflow, HipScanEngine, ScanEngine, StatsOverflow
+from .engine import FacetOverflow, HipScanEngine, JoinOverflow, ScanEngine, StatsOverflow
 from .idtable import IdTable, mint_uuid4_bytes
 from .interfaces import VectorDTO, VectorProtocol
 
@@ -1962,6 +1963,100 @@ class Index:
             scores = self._scores(dist, metric).tolist()
             out.append([SearchResult(vector_id=u, score=s) for u, s in zip(uids, scores) if u is not None])
         return out
+
+    # ------------------------------------------------------------------ additive: similarity join
+    _MAX_JOIN_PER_ROW = _native.JOIN_MAX_CAPACITY  # MLVDB_JOIN_MAX_CAPACITY: the most partners one row returns
+
+    def check_join_args(self, what: str, metric, radius, where=None, ids=None, max_per_row=1024, order: str = "left") -> float:
+        """The refusals of ``join_within`` / ``duplicate_groups`` that need no namespace, in their order; returns the radius
+        in the space's own distance (squared for ``metric="euclidean"``)."""
+        self._refuse_sharded(what)
+        if callable(where) and not isinstance(where, Mapping):
+            raise ValueError(f"{what}: where must be one dict filter (a predicate has no device form)")
+        self._one_filter(what, where)
+        if metric not in _join.METRICS:
+            raise ValueError(f"{what}: metric must be one of {_join.METRICS} (got {metric!r})")
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or math.isnan(radius):
+            raise ValueError(f"{what}: radius must be a number (got {radius!r})")
+        if radius < 0 and metric != "ip":  # (an ip distance is 1 - <a, b>: similar rows lie below zero)
+            raise ValueError(f"{what}: radius must be >= 0 for metric {metric!r} (got {radius!r})")
+        if not self._int_in(max_per_row, 1, self._MAX_JOIN_PER_ROW):
+            raise ValueError(f"{what}: max_per_row must be an int in [1, {self._MAX_JOIN_PER_ROW}] (got {max_per_row!r})")
+        if order not in _join.ORDERS:
+            raise ValueError(f"{what}: order must be one of {_join.ORDERS} (got {order!r})")
+        if ids is not None:
+            ids = list(ids)
+            if len(set(ids)) != len(ids):
+                raise ValueError(f"{what}: ids must not repeat")
+        return float(radius) ** 2 if metric == "euclidean" else float(radius)
+
+    def join_within(self, namespace: str, metric: str, radius: float, *, where: Optional[Mapping] = None,
+                    ids: Optional[Sequence[UUID]] = None, max_per_row: int = 1024, order: str = "left") -> "_join.PairHits":
+        """Additive: which stored rows lie within ``radius`` of each other, answered on the device from the rows in HBM
+        (include/mlvdb_join.h) -- near-duplicate detection, record linkage, the neighbourhood graph of a cluster view.
+
+        ``ids=None`` is the self-join: the left rows are the live rows ``where`` matches (all live rows without one), and
+        every unordered pair of them within ``radius`` appears once, the earlier-inserted row on the left.  ``ids=[...]``
+        asks "what is stored near these stored vectors": per id, every other live row ``where`` matches within ``radius``
+        (the ids themselves need not match it), answered in the caller's order; repeated ids are refused.  ``radius`` and
+        the scores follow ``range_search_many`` (squared for l2, plain for ``metric="euclidean"``).  At most
+        ``max_per_row`` partners per left row come back, the nearest; ``counts`` holds the exact numbers and ``complete``
+        says whether any was cut.  ``order="left"``: grouped by left row, nearest first; ``"distance"``: nearest pair
+        first over the whole answer (ties by left, then right insertion order).  Every refusal happens before the engine
+        is touched.  Returns a ``PairHits``."""
+        native_radius = self.check_join_args("join_within", metric, radius, where, ids, max_per_row, order)
+        program = self._program(namespace, where)
+        ns = self._ns.get(namespace)
+        asked = None if ids is None else list(ids)
+        labels = None
+        if asked is not None and ns is not None:
+            labels = ns.ids.lookup(asked) if asked else np.zeros(0, np.int64)
+            if (labels < 0).any():
+                raise ValueError(f"join_within: id {asked[int(np.argmax(labels < 0))]} is unknown or removed in namespace "
+                                 f"{namespace!r}")
+        elif asked:
+            raise ValueError(f"join_within: id {asked[0]} is unknown or removed in namespace {namespace!r}")
+        if self._nothing_to_search(ns):
+            return _join.PairHits.empty()
+        join = self._engine_entry(ns, "join_within", "join_within needs")
+        if labels is None:  # the self-join: every unordered pair once
+            left = ns.engine.where_labels(program if program is not None else self._compile(namespace, {}))
+            back = np.arange(left.size)
+            mode = _native.JOIN_LATER
+        else:
+            back = np.argsort(labels, kind="stable")  # the engine takes ascending labels; the answer keeps the caller's order
+            left = labels[back]
+            mode = _native.JOIN_OTHERS
+        hits, counts = join(left, mode, native_radius, int(max_per_row), where=program, truncate=True)
+        if labels is not None:
+            inverse = np.empty_like(back)
+            inverse[back] = np.arange(back.size)
+            pick = _join.gather_segments(hits.offsets, inverse)
+            lens = np.diff(hits.offsets)[inverse]
+            right, dist, counts, left = hits.labels[pick], hits.dist[pick], counts[inverse], labels
+        else:
+            lens = np.diff(hits.offsets)
+            right, dist = hits.labels[:int(hits.offsets[-1])], hits.dist[:int(hits.offsets[-1])]
+        left_of_pair = np.repeat(left, lens)
+        if order == "distance":
+            by = np.lexsort((right, left_of_pair, dist))
+            left_of_pair, right, dist = left_of_pair[by], right[by], dist[by]
+        return _join.PairHits(ns.ids.uuids_at(left_of_pair), ns.ids.uuids_at(right), self._scores(dist, metric), counts,
+                              bool((counts <= int(max_per_row)).all()), left_of_pair, right, dist, ns.ids.uuids_at(left))
+
+    def duplicate_groups(self, namespace: str, metric: str, radius: float, *, where: Optional[Mapping] = None,
+                         max_per_row: int = 1024) -> List[List[UUID]]:
+        """Additive: the groups of near-duplicates -- the connected components (two rows or more) of the self-join's pairs
+        (``join_within`` with ``ids=None``), each in insertion order, the groups ordered by their first member.  Raises
+        ``JoinOverflow`` when a row has more than ``max_per_row`` partners: a truncated pair list does not determine the
+        components."""
+        self.check_join_args("duplicate_groups", metric, radius, where, None, max_per_row)
+        pairs = self.join_within(namespace, metric, radius, where=where, max_per_row=max_per_row)
+        if not pairs.complete:
+            raise JoinOverflow(int(max_per_row), int(pairs.counts.max()))
+        ns = self._ns.get(namespace)
+        return [ns.ids.uuids_at(np.asarray(g, dtype=np.int64)).tolist()
+                for g in _join.connected_groups(pairs.left_labels, pairs.right_labels)]
 
     # ------------------------------------------------------------------ helpers
     @staticmethod

@@ -402,6 +402,61 @@ class QueryProcessor:
                 out = [hits[:max(1, int(max_results))] for hits in out]
         return [self._fill_values(hits, namespace) for hits in out]
 
+    # ---- additive: similarity join (Index.join_within / duplicate_groups)
+    def _stored(self, ids, namespace: str) -> dict:
+        """id -> {"id", "values", "metadata"} of the stored vectors among ``ids`` (values from the index where the storage
+        keeps none)."""
+        ids = list(dict.fromkeys(ids))
+        rows = [{"id": v.id, "values": v.values, "metadata": v.metadata} for v in self._storage.read_vectors(ids, namespace) if v]
+        return {r["id"]: r for r in self._fill_values(rows, namespace)}
+
+    def _join_pairs(self, what: str, radius: float, namespace: str, metric: str, where, max_per_row: int, order: str = "left"):
+        """The self-join's pairs for ``where`` = None, a dict filter (on the device) or a predicate (the host path: the
+        matching stored vectors are the left rows of a by-ids join, whose pairs are kept when the partner matches too and
+        was inserted later)."""
+        if where is None or isinstance(where, Mapping):
+            return self._index.join_within(namespace, metric, radius, where=where, max_per_row=max_per_row, order=order)
+        if not callable(where):
+            raise ValueError(f"{what}: where must be a dict filter, a predicate or None (got {type(where).__name__})")
+        allowed = [v.id for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
+        hits = self._index.join_within(namespace, metric, radius, ids=allowed, max_per_row=max_per_row, order=order)
+        inside = set(allowed)
+        keep = np.array([r in inside for r in hits.right_ids.tolist()], dtype=bool) & (hits.right_labels > hits.left_labels)
+        for name in ("left_ids", "right_ids", "scores", "left_labels", "right_labels", "distances"):
+            setattr(hits, name, getattr(hits, name)[keep])
+        return hits
+
+    def find_near_pairs(self, radius: float, namespace: str = "default", metric: str = "cosine", where=None,
+                        max_per_row: int = 1024, order: str = "left") -> dict:
+        """Additive: every unordered pair of stored vectors within ``radius`` of each other (``Index.join_within``, the
+        self-join), enriched like ``find_in_radius``: {"pairs": [{"left": {id, values, metadata}, "right": {...}, "score"},
+        ...], "complete": no vector had more than ``max_per_row`` partners}.  The earlier-inserted vector is on the left.
+        ``where``: a dict filter is evaluated on the device; a predicate picks the vectors by their stored metadata."""
+        hits = self._join_pairs("find_near_pairs", radius, namespace, metric, where, max_per_row, order)
+        stored = self._stored(hits.left_ids.tolist() + hits.right_ids.tolist(), namespace)
+        pairs = [{"left": stored[a], "right": stored[b], "score": s} for a, b, s in hits.pairs() if a in stored and b in stored]
+        return {"pairs": pairs, "complete": hits.complete}
+
+    def find_duplicates(self, radius: float, namespace: str = "default", metric: str = "cosine", where=None,
+                        max_per_row: int = 1024) -> List[List[dict]]:
+        """Additive: the groups of near-duplicates (``Index.duplicate_groups``: the connected components of the pairs within
+        ``radius``), every member enriched with values and metadata; groups and members in insertion order.  Raises
+        ``engine.JoinOverflow`` when a vector has more than ``max_per_row`` partners.  ``where`` as in ``find_near_pairs``."""
+        if where is None or isinstance(where, Mapping):
+            groups = self._index.duplicate_groups(namespace, metric, radius, where=where, max_per_row=max_per_row)
+        else:
+            from .engine import JoinOverflow
+            from .join import connected_groups
+
+            hits = self._join_pairs("find_duplicates", radius, namespace, metric, where, max_per_row)
+            if not hits.complete:
+                raise JoinOverflow(int(max_per_row), int(hits.counts.max()))
+            id_of = dict(zip(hits.left_labels.tolist(), hits.left_ids.tolist()))
+            id_of.update(zip(hits.right_labels.tolist(), hits.right_ids.tolist()))
+            groups = [[id_of[x] for x in g] for g in connected_groups(hits.left_labels, hits.right_labels)]
+        stored = self._stored([u for g in groups for u in g], namespace)
+        return [[stored[u] for u in g if u in stored] for g in groups]
+
     # ---- additive: metadata queries (README.md:252,274: StorageEngine.query_by_metadata; no reference code)
     def count_where(self, where, namespace: str = "default") -> int:
         """Live vectors of ``namespace`` matching ``where`` (dict filter: counted on the device; predicate: over storage)."""
