@@ -282,6 +282,16 @@ JOIN_SIGNATURES = {
                                     _P, _P, _P, _P]),
 }
 
+# include/mlvdb_cluster.h: nearest-centroid assignment and k-means over the stored rows, the cluster id into an int64 column
+CLUSTER_MAX = 1024
+CLUSTER_SEGMENT = 256
+CLUSTER_MAX_ITERATIONS = 1000
+CLUSTER_SIGNATURES = {
+    "mlvdb_assign_nearest": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(Where), C.c_int32, _P, _P, C.POINTER(C.c_int64)]),
+    "mlvdb_kmeans": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(Where), C.c_int32, _P, _P, _P,
+                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -316,7 +326,7 @@ def load() -> C.CDLL:
                                       **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **BITS_SIGNATURES,
                                       **HYBRID_SIGNATURES,
                                       **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES,
-                                      **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES}.items():
+                                      **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES, **CLUSTER_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

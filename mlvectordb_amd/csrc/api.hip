@@ -124,6 +124,9 @@ struct mlvdb_index {
     // distances, results and dense outputs -- sized by the wave (<= kJoinWave rows) and `capacity` -- and the packed hits of
     // the call so far: 12 B per returned hit, grown as they come, never beyond total_capacity
     DevBuf join_left, join_ws, join_lab, join_dist;
+    // clustering (mlvdb_cluster.h): the call's centroid labels and raw rows, the dense centroids, the per-row workspace (20 B per
+    // row, 28 B for cosine k-means, and the listing's histograms), the segment table and the segment sums of one iteration
+    DevBuf cl_in, cl_cent, cl_ws, cl_segs, cl_part;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -5426,6 +5429,180 @@ int mlvdb_search_batch_examples(mlvdb_index* h, int32_t mode, const int64_t* exa
                              out_labels, out_tier, out_value, out_counts);
     };
     return with_where(h, where, nq, call);
+    });
+}
+
+
+// ---- clustering (mlvdb_cluster.h)
+extern "C++" {
+namespace {
+// The validated call (rn: the index's norms, or their masked copy when a program restricts the rows -- evaluated once, before
+// anything is written; the centroids' stored rows are read from h->X, which no mask touches).  The centroids staged dense (examples_stage_kernel)
+// -> per iteration: the query prep, one scan launch per tile in ascending order, the ordered member lists, ONE wait for the
+// moved counter, the candidates and the member counts, the segment table up, the blocked sums and the finish -> the column,
+// the outputs.  kmeans == false: one assignment, its counts and costs, no mean.
+int cluster_impl(mlvdb_index* h, const float* rn, const int64_t* labels, const float* vectors, int32_t m, bool kmeans, int32_t max_iterations,
+                 int32_t assign_attr, float* out_centroids, int64_t* out_rows, double* out_cost, int32_t* iterations,
+                 int32_t* converged, int64_t* matched) {
+    hipStream_t s = h->stream;
+    const size_t md = (size_t)m * h->dim;
+    // (an assignment that meets no candidate repeats itself: the second iteration is the first that can say "converged")
+    const int32_t idle_iterations = std::min(2, max_iterations);
+    if (h->total == 0) {  // (no stored label is valid here: every centroid is raw)
+        if (out_centroids) std::copy(vectors, vectors + md, out_centroids);
+        pad(out_rows, m, 0);
+        pad(out_cost, m, 0.0);
+        *matched = 0;
+        if (iterations) *iterations = idle_iterations;
+        if (converged) *converged = max_iterations >= 2;
+        return MLVDB_OK;
+    }
+    if (int rc = begin_call(h, s)) return rc;
+    const int32_t qt = cluster_tile_width(h->ld, m);
+    const ExactPlan plan = plan_assign(h->total, h->ld, qt);
+    if (plan.qt != qt) return fail(h, MLVDB_ERR_INTERNAL, "cluster: the scan's tile is not the width the centroids were cut by");
+    const bool weights = kmeans && h->space == kSpaceCosine;
+    const int64_t nblocks = cluster_list_blocks(h->total);
+    const size_t total = (size_t)h->total;
+    // the raw centroids' rows, packed
+    std::vector<int32_t> raw((size_t)m, -1);
+    std::vector<int64_t> lab((size_t)m, -1);
+    std::vector<float> raw_rows;
+    for (int32_t j = 0; j < m; ++j) {
+        if (labels) lab[(size_t)j] = labels[j];
+        if (lab[(size_t)j] >= 0) continue;
+        raw[(size_t)j] = (int32_t)(raw_rows.size() / (size_t)h->dim);
+        raw_rows.insert(raw_rows.end(), vectors + (size_t)j * h->dim, vectors + (size_t)(j + 1) * h->dim);
+    }
+    int64_t* lab_d = nullptr;
+    float* rows_d = nullptr;
+    int32_t* raw_d = nullptr;
+    CARVE(h, h->cl_in, [&](Carver& c) {
+        lab_d = c.take<int64_t>((size_t)m);
+        rows_d = c.take<float>(raw_rows.size());
+        raw_d = c.take<int32_t>((size_t)m);
+    });
+    double *best_d = nullptr, *w_d = nullptr, *cost_d = nullptr;
+    unsigned long long* ctr_d = nullptr;  // [moved, candidates], the member counts right behind them: one copy down
+    int64_t *counts_d = nullptr, *base_d = nullptr;
+    int32_t *sidx_d = nullptr, *assign_d = nullptr, *members_d = nullptr, *hist_d = nullptr, *first_d = nullptr;
+    CARVE(h, h->cl_ws, [&](Carver& c) {
+        best_d = c.take<double>(total);
+        w_d = c.take<double>(weights ? total : 0);
+        cost_d = c.take<double>((size_t)m);
+        ctr_d = c.take<unsigned long long>(2);
+        counts_d = c.take<int64_t>((size_t)m);
+        base_d = c.take<int64_t>((size_t)m);
+        sidx_d = c.take<int32_t>(total);
+        assign_d = c.take<int32_t>(total);
+        members_d = c.take<int32_t>(total);
+        hist_d = c.take<int32_t>((size_t)nblocks * (size_t)m);
+        first_d = c.take<int32_t>((size_t)m + 1);
+    });
+    HIP_TRY(h, h->cl_cent.ensure(md * sizeof(float)));
+    HIP_TRY(h, h->qpad.ensure((size_t)m * h->ld * sizeof(float)));
+    HIP_TRY(h, h->qaux.ensure((size_t)m * sizeof(double)));
+    float* const cent_d = h->cl_cent.as<float>();
+    HIP_TRY(h, hipMemcpyAsync(lab_d, lab.data(), (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(raw_d, raw.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (!raw_rows.empty())
+        HIP_TRY(h, hipMemcpyAsync(rows_d, raw_rows.data(), raw_rows.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_examples_stage(h->X, h->dim, h->ld, lab_d, raw_d, rows_d, m, cent_d, s));
+    HIP_TRY(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(assign_d), kClusterNoCandidate, total, s));
+    if (weights) HIP_TRY(h, launch_cluster_weights(h->X, h->ld, h->total, w_d, s));
+
+    AssignArgs a{};
+    a.X = h->X;
+    a.rn = rn;
+    a.total = h->total;
+    a.ld = h->ld;
+    a.space = h->space;
+    a.Qpad = h->qpad.as<float>();
+    a.qaux = h->qaux.as<double>();
+    a.m = m;
+    a.best = best_d;
+    a.sidx = sidx_d;
+    a.assign = assign_d;
+    a.moved = ctr_d;
+    std::vector<int64_t> head((size_t)m + 2);  // moved, candidates, counts[m]
+    std::vector<ClusterSegment> segs;
+    std::vector<int32_t> seg_first;
+    const int32_t last_iteration = kmeans ? max_iterations : 1;
+    int32_t t = 1;
+    bool done = false;
+    for (;; ++t) {
+        HIP_TRY(h, launch_query_prep(cent_d, m, h->dim, h->ld, h->space, h->qpad.as<float>(), h->qaux.as<double>(), nullptr, s));
+        HIP_TRY(h, hipMemsetAsync(ctr_d, 0, 2 * sizeof(unsigned long long), s));
+        for (a.first = 0; a.first < m; a.first += plan.qt)
+            if (int rc = scan_step(h, s, h->total, [&] { return launch_assign_scan(a, plan, s); })) return rc;
+        HIP_TRY(h, launch_cluster_list(assign_d, h->total, m, hist_d, counts_d, base_d, members_d, ctr_d + 1, s));
+        // the iteration's one wait (it also ends the reads of the host vectors uploaded so far)
+        HIP_TRY(h, hipMemcpyAsync(head.data(), ctr_d, head.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        done = kmeans && t >= 2 && head[0] == 0;
+        cluster_segments(head.data() + 2, m, segs, seg_first);
+        HIP_TRY(h, h->cl_segs.ensure(segs.size() * sizeof(ClusterSegment)));
+        HIP_TRY(h, h->cl_part.ensure(segs.size() * ((size_t)h->ld + 1) * sizeof(double)));
+        if (!segs.empty())
+            HIP_TRY(h, hipMemcpyAsync(h->cl_segs.p, segs.data(), segs.size() * sizeof(ClusterSegment), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(first_d, seg_first.data(), seg_first.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, launch_cluster_sums(h->X, h->dim, h->ld, h->space == kSpaceCosine, h->cl_segs.as<ClusterSegment>(),
+                                       (int32_t)segs.size(), first_d, members_d, w_d, best_d, counts_d, m, kmeans,
+                                       h->cl_part.as<double>(), cent_d, cost_d, s));
+        if (done || t == last_iteration) break;
+    }
+    h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+    if (assign_attr >= 0) HIP_TRY(h, launch_cluster_write(assign_d, h->total, h->attr_col[assign_attr], s));
+    // (the wait inside also ends the reads of the last segment table)
+    if (int rc = copy_down(h, s, {{out_centroids, 0, cent_d, md}, {out_cost, 0, cost_d, (size_t)m}})) return rc;
+    std::copy(head.begin() + 2, head.end(), out_rows);
+    *matched = head[1];
+    if (iterations) *iterations = t;
+    if (converged) *converged = done ? 1 : 0;
+    return end_call(h, s);
+}
+
+int cluster_entry(mlvdb_index* h, const int64_t* labels, const float* vectors, int32_t m, bool kmeans, int32_t max_iterations,
+                  const mlvdb_where* where, int32_t assign_attr, float* out_centroids, int64_t* out_rows, double* out_cost,
+                  int32_t* iterations, int32_t* converged, int64_t* matched) {
+    // everything is checked on the host before anything is launched (the program: with_where)
+    const int32_t attr_type = assign_attr >= 0 && assign_attr < MLVDB_MAX_ATTRS ? h->attr_type[assign_attr] : 0;
+    const ClusterRefusal r = cluster_check(labels, vectors, m, h->total, h->dim, h->space, assign_attr, attr_type, out_rows,
+                                           out_cost, matched, kmeans, max_iterations, out_centroids && iterations && converged);
+    if (r.code != MLVDB_OK) return fail(h, r.code, r.what);
+    if (int rc = check_row_limit(h, "cluster: ")) return rc;
+    // The candidates: the index's norms, or a masked copy of them (NaN = no candidate) made once, before anything is written.
+    // The copy is handed to the scan as an argument: the handle's own pointers stay as they are (nothing to restore on any
+    // way out), and the int8 shadow, which this family never reads, is neither refreshed nor masked.
+    const float* rn = h->rn;
+    if (where) {
+        if (int rc = where_run(h, where, nullptr)) return rc;
+        if (h->total > 0) {
+            HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
+            HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, h->stream));
+            rn = h->rn_masked.as<float>();
+        }
+    }
+    return cluster_impl(h, rn, labels, vectors, m, kmeans, max_iterations, assign_attr, out_centroids, out_rows, out_cost,
+                        iterations, converged, matched);
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_assign_nearest(mlvdb_index* h, const int64_t* centroid_labels, const float* centroid_vectors, int32_t m,
+                         const mlvdb_where* where, int32_t assign_attr, int64_t* out_rows, double* out_cost, int64_t* matched) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    return cluster_entry(h, centroid_labels, centroid_vectors, m, false, 1, where, assign_attr, nullptr, out_rows, out_cost,
+                         nullptr, nullptr, matched);
+    });
+}
+
+int mlvdb_kmeans(mlvdb_index* h, const int64_t* centroid_labels, const float* centroid_vectors, int32_t m,
+                 int32_t max_iterations, const mlvdb_where* where, int32_t assign_attr, float* out_centroids,
+                 int64_t* out_rows, double* out_cost, int32_t* iterations, int32_t* converged, int64_t* matched) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    return cluster_entry(h, centroid_labels, centroid_vectors, m, true, max_iterations, where, assign_attr, out_centroids,
+                         out_rows, out_cost, iterations, converged, matched);
     });
 }
 

@@ -29,10 +29,12 @@
 #include "../../include/mlvdb_score.h"
 #include "../../include/mlvdb_examples.h"
 #include "../../include/mlvdb_join.h"
+#include "../../include/mlvdb_cluster.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
 #include "examples_plan.h"
+#include "cluster_plan.h"
 
 namespace mlvdb {
 
@@ -905,5 +907,42 @@ hipError_t launch_order_collect(const uint8_t* mask, const float* rn, const int6
 hipError_t launch_order_sort(const unsigned long long* keys, const uint32_t* labels, const int64_t* col, int32_t type,
                              int64_t centre, int64_t total, int64_t offset, OrderState* st, int64_t* out_labels,
                              int64_t* out_values, double* out_dist, hipStream_t s);
+
+// ---------------------------------------------------------------- clustering (kernels_cluster.hip, include/mlvdb_cluster.h)
+constexpr int32_t kClusterNoCandidate = -2;  // assignment of a row that is no candidate (-1: an unassigned candidate)
+enum : uint32_t { kClusterFirst = 1, kClusterLast = 2 };
+// One launch of the assignment scan: the tile of centroids [first, min(m, first + qt)) of the prepared batch.
+struct AssignArgs {
+    const float* X;
+    const float* rn;
+    int64_t total;
+    int32_t ld;
+    int32_t space;
+    const float* Qpad;   // [m][ld]
+    const double* qaux;  // [m]
+    int32_t m, first;
+    uint32_t flags;      // (launch_assign_scan sets them from `first`)
+    double* best;        // [total]: the best distance so far / of the assignment
+    int32_t* sidx;       // [total]: its centroid, between the tiles
+    int32_t* assign;     // [total]: the previous assignment in, this one out (kClusterNoCandidate: not written)
+    unsigned long long* moved;  // += the candidates whose centroid changed
+};
+// plan_exact's geometry for one tile of qt centroids
+ExactPlan plan_assign(int64_t nrows, int32_t ld, int32_t qt);
+hipError_t launch_assign_scan(const AssignArgs& a, const ExactPlan& p, hipStream_t s);
+// w[row] = 1 / (sqrt(nx) + 1e-30) for rows [0, total), nx in accumulate_rows' order
+hipError_t launch_cluster_weights(const float* X, int32_t ld, int64_t total, double* w, hipStream_t s);
+// The members of every cluster in ascending label order: members[base[c] .. base[c] + counts[c]); hist holds
+// cluster_list_blocks(total) x m words; *matched += the candidates (assign != kClusterNoCandidate)
+hipError_t launch_cluster_list(const int32_t* assign, int64_t total, int32_t m, int32_t* hist, int64_t* counts, int64_t* base,
+                               int32_t* members, unsigned long long* matched, hipStream_t s);
+// The blocked sums over the segment table (cluster_segments; partial: [nsegs][ld + 1]): cost[c], and with `means` the new
+// centroid rows cent[c][0 .. dim) of the clusters that have members
+hipError_t launch_cluster_sums(const float* X, int32_t dim, int32_t ld, bool cosine, const ClusterSegment* segs, int32_t nsegs,
+                               const int32_t* seg_first, const int32_t* members, const double* w, const double* best,
+                               const int64_t* counts, int32_t m, bool means, double* partial, float* cent, double* cost,
+                               hipStream_t s);
+// column[row] = assign[row] (INT64_MIN for -1) for every candidate row
+hipError_t launch_cluster_write(const int32_t* assign, int64_t total, int64_t* column, hipStream_t s);
 
 }  // namespace mlvdb

@@ -839,6 +839,54 @@ class HipScanEngine:
             "search_batch_examples")
         return out_labels, tiers, values, counts
 
+    # -- clustering (include/mlvdb_cluster.h) ------------------------------------------------
+    def _centroids(self, labels, vectors, what: str):
+        """The centroid arguments of the two entries: (labels int64 [m] or ``None``, vectors float32 [m, dim] or ``None``,
+        m).  Centroid ``j`` is the stored row ``labels[j]`` or, with ``labels[j] == -1`` (or no labels at all), row ``j`` of
+        ``vectors``."""
+        if labels is None and vectors is None:
+            raise RuntimeError(f"{what}: neither centroid labels nor centroid vectors")
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        if vectors is not None:
+            vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+            if vectors.ndim != 2 or vectors.shape[1] != self.dim or (labels is not None and vectors.shape[0] != labels.size):
+                raise RuntimeError(f"Wrong dimensionality of the vectors: got {vectors.shape}, index dim {self.dim}"
+                                   + ("" if labels is None else f", {labels.size} centroids"))
+        return labels, vectors, int(labels.size if labels is not None else vectors.shape[0])
+
+    def assign_nearest(self, labels, vectors=None, *, where=None, assign_attr: int = -1):
+        """Every candidate row (live, matching ``where``) to its nearest centroid: the lowest ``j`` with the smallest
+        ``pair_distances`` value, bit for bit; a row every distance of which is NaN or +inf stays unassigned.  With
+        ``assign_attr`` >= 0 that int64 column receives ``j`` (absent for an unassigned row); no other row is touched, and
+        the filter is evaluated before anything is written.  Returns (sizes int64 [m], costs float64 [m] -- the members'
+        best distances in the header's blocked order --, candidates)."""
+        labels, vectors, m = self._centroids(labels, vectors, "assign_nearest")
+        sizes = np.zeros(max(m, 1), dtype=np.int64)
+        costs = np.zeros(max(m, 1), dtype=np.float64)
+        matched = C.c_int64(0)
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_assign_nearest(self._h, _opt(labels), _opt(vectors), m, w, int(assign_attr),
+                                                   sizes.ctypes.data, costs.ctypes.data, C.byref(matched)), "assign_nearest")
+        return sizes[:m], costs[:m], int(matched.value)
+
+    def kmeans(self, labels, vectors=None, *, max_iterations: int = 25, where=None, assign_attr: int = -1):
+        """Lloyd's algorithm over the candidate rows from the given centroids (l2 and cosine): per iteration the assignment
+        of ``assign_nearest`` and, per cluster, the mean of its members in the order ``include/mlvdb_cluster.h`` states
+        (cosine: of the normalised members); a cluster without members keeps its centroid.  Stops after the first iteration
+        >= 2 that moves no row, or at ``max_iterations``.  Returns (centroids float32 [m, dim], sizes int64 [m], costs
+        float64 [m], iterations, converged, candidates); ``assign_attr`` holds the last assignment."""
+        labels, vectors, m = self._centroids(labels, vectors, "kmeans")
+        centroids = np.zeros((max(m, 1), self.dim), dtype=np.float32)
+        sizes = np.zeros(max(m, 1), dtype=np.int64)
+        costs = np.zeros(max(m, 1), dtype=np.float64)
+        iterations, converged, matched = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_kmeans(self._h, _opt(labels), _opt(vectors), m, int(max_iterations), w, int(assign_attr),
+                                           centroids.ctypes.data, sizes.ctypes.data, costs.ctypes.data, C.byref(iterations),
+                                           C.byref(converged), C.byref(matched)), "kmeans")
+        return centroids[:m], sizes[:m], costs[:m], int(iterations.value), bool(converged.value), int(matched.value)
+
     # -- late-interaction search (include/mlvdb_maxsim.h) -----------------------------------
     def search_maxsim(self, tokens: np.ndarray, offsets: np.ndarray, k: int, attr: int, where=None,
                       want_matches: bool = False):

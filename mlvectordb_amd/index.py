@@ -35,6 +35,7 @@ from uuid import UUID
 import numpy as np
 
 from . import _native
+from . import cluster as _cluster
 from . import join as _join
 from . import score as _score
 from . import stats as _stats
@@ -2057,6 +2058,138 @@ class Index:
         ns = self._ns.get(namespace)
         return [ns.ids.uuids_at(np.asarray(g, dtype=np.int64)).tolist()
                 for g in _join.connected_groups(pairs.left_labels, pairs.right_labels)]
+
+    # ------------------------------------------------------------------ additive: clustering
+    _MAX_CLUSTERS = _native.CLUSTER_MAX  # MLVDB_CLUSTER_MAX
+    _MAX_CLUSTER_ITERATIONS = _native.CLUSTER_MAX_ITERATIONS
+
+    def _check_cluster_args(self, what: str, metric, metrics, where, assign_to) -> int:
+        """The refusals the two clustering entries share that need no namespace, in their order; returns the engine's
+        column of ``assign_to`` (-1 without one)."""
+        self._refuse_sharded(what)
+        if callable(where) and not isinstance(where, Mapping):
+            raise ValueError(f"{what}: where must be one dict filter (a predicate has no device form)")
+        self._one_filter(what, where)
+        if metric not in metrics:
+            raise ValueError(f"{what}: metric must be one of {metrics} (got {metric!r})"
+                             + (": no mean minimises the inner product; assign_clusters serves it" if metric == "ip" else ""))
+        if assign_to is None:
+            return -1
+        if self._declared(assign_to, f"{what}: assign_to ") != "int":
+            raise ValueError(f"{what}: assign_to {assign_to!r} is a {self._attributes[assign_to]} attribute; a cluster id "
+                             f"needs an int attribute")
+        return self._column(assign_to)
+
+    def _cluster_namespace(self, what: str, namespace: str, metric: str) -> Optional[_Namespace]:
+        ns = self._ns.get(namespace)
+        space = getattr(ns.engine, "space", metric) if ns is not None else metric
+        if space != metric:
+            raise ValueError(f"{what}: namespace {namespace!r} is indexed in space {space!r}, not {metric!r}")
+        return ns
+
+    def _centroid_array(self, what: str, centroids, ns: Optional[_Namespace]) -> np.ndarray:
+        try:
+            c = np.ascontiguousarray(centroids, dtype=np.float32)
+        except (TypeError, ValueError):
+            c = None
+        if c is None or c.ndim != 2 or (ns is not None and c.shape[1] != ns.dim) or not np.isfinite(c).all():
+            raise ValueError(f"{what}: the centroids must be a finite [k, dim] array of the namespace's dimensionality")
+        if not 1 <= c.shape[0] <= self._MAX_CLUSTERS:
+            raise ValueError(f"{what}: between 1 and {self._MAX_CLUSTERS} centroids are supported (got {c.shape[0]})")
+        return c
+
+    def cluster(self, namespace: str, metric: str, k: int, *, where: Optional[Mapping] = None, init="random", seed: int = 0,
+                max_iterations: int = 25, assign_to: Optional[str] = None) -> "_cluster.ClusterResult":
+        """Additive: k-means over the stored rows, on the device from the rows in HBM (include/mlvdb_cluster.h) -- "which
+        themes does this corpus hold", and a cluster id per row to filter, facet and diversify by.
+
+        The candidates are the live rows ``where`` (one dict filter) matches.  Lloyd's algorithm runs from ``init``:
+        ``"random"`` draws ``k`` distinct candidates with ``np.random.default_rng(seed)`` (passed as labels: no vector
+        crosses the bus); a sequence of ``k`` UUIDs names stored vectors; a ``[k, dim]`` array gives the centroids
+        themselves.  Every iteration assigns each candidate to its nearest centroid (the lowest one on a tie) and moves
+        every centroid to the mean of its members -- of its normalised members for "cosine"; a cluster without members
+        keeps its centroid.  It stops after the first iteration >= 2 that moves no row, or after ``max_iterations``.
+        ``assign_to`` names a declared ``int`` attribute that receives the cluster id of every candidate (no other row is
+        touched; the filter is evaluated before anything is written, so it may read ``assign_to`` itself).  Metric "ip" is
+        refused: no mean minimises it.  The answer depends on the stored rows and the arguments only.  Every refusal
+        happens before the engine is touched.  Returns a ``ClusterResult``."""
+        what = "cluster"
+        column = self._check_cluster_args(what, metric, _cluster.METRICS, where, assign_to)
+        if not self._int_in(k, 1, self._MAX_CLUSTERS):
+            raise ValueError(f"{what}: k must be an int in [1, {self._MAX_CLUSTERS}] (got {k!r})")
+        if not self._int_in(max_iterations, 1, self._MAX_CLUSTER_ITERATIONS):
+            raise ValueError(f"{what}: max_iterations must be an int in [1, {self._MAX_CLUSTER_ITERATIONS}] (got {max_iterations!r})")
+        k = int(k)
+        program = self._program(namespace, where)
+        ns = self._cluster_namespace(what, namespace, metric)
+        labels = vectors = None
+        if isinstance(init, str):
+            if init != "random":
+                raise ValueError(f'{what}: init must be "random", a sequence of ids or a [k, dim] array (got {init!r})')
+            if not self._int_in(seed, 0):
+                raise ValueError(f"{what}: seed must be an int >= 0 (got {seed!r})")
+            live = 0 if ns is None else ns.total - ns.deleted
+            pool = None
+            if live >= k and program is not None:  # (only a filter can leave fewer candidates than live rows)
+                pool = ns.engine.where_labels(program)
+                live = int(pool.size)
+            if live < k:
+                raise ValueError(f"{what}: k = {k} centroids but only {live} candidate rows in namespace {namespace!r}")
+            if pool is None:
+                pool = ns.engine.where_labels(self._compile(namespace, {}))
+            labels = np.sort(np.random.default_rng(int(seed)).choice(pool, k, replace=False)).astype(np.int64)
+        elif isinstance(init, (bytes, UUID)) or not isinstance(init, (SequenceABC, np.ndarray)):
+            raise ValueError(f'{what}: init must be "random", a sequence of ids or a [k, dim] array (got {init!r})')
+        elif len(init) > 0 and all(isinstance(e, UUID) for e in init):
+            ids = list(init)
+            if len(ids) != k:
+                raise ValueError(f"{what}: k = {k} but init names {len(ids)} ids")
+            labels = ns.ids.lookup(ids) if ns is not None else np.full(len(ids), -1, np.int64)
+            if (labels < 0).any():
+                raise ValueError(f"{what}: id {ids[int(np.argmax(labels < 0))]} is unknown or removed in namespace {namespace!r}")
+        else:
+            vectors = self._centroid_array(what, init, ns)
+            if vectors.shape[0] != k:
+                raise ValueError(f"{what}: k = {k} but init holds {vectors.shape[0]} centroids")
+        if self._no_rows(ns):
+            return _cluster.ClusterResult.of(vectors, np.zeros(k, np.int64), np.zeros(k), min(2, int(max_iterations)),
+                                             max_iterations >= 2)
+        kmeans = self._engine_entry(ns, "kmeans", f"{what} needs")
+        centroids, sizes, costs, iterations, converged, _ = kmeans(labels, vectors, max_iterations=int(max_iterations),
+                                                                    where=program, assign_attr=column)
+        return _cluster.ClusterResult.of(centroids, sizes, costs, iterations, converged)
+
+    def assign_clusters(self, namespace: str, metric: str, centroids, assign_to: Optional[str] = None,
+                        where: Optional[Mapping] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Additive: every live row ``where`` matches to the nearest of the given ``[k, dim]`` centroids (the lowest one on
+        a tie), on the device -- "assign the rows I just appended to the centroids I already have".  ``assign_to`` (a
+        declared ``int`` attribute) receives the cluster ids as in ``cluster``.  Works for "l2", "cosine" and "ip".
+        Returns (sizes int64 [k], costs float64 [k]) as ``ClusterResult`` holds them."""
+        what = "assign_clusters"
+        column = self._check_cluster_args(what, metric, _cluster.ASSIGN_METRICS, where, assign_to)
+        program = self._program(namespace, where)
+        ns = self._cluster_namespace(what, namespace, metric)
+        vectors = self._centroid_array(what, centroids, ns)
+        if self._no_rows(ns):
+            return np.zeros(vectors.shape[0], np.int64), np.zeros(vectors.shape[0])
+        assign = self._engine_entry(ns, "assign_nearest", f"{what} needs")
+        sizes, costs, _ = assign(None, vectors, where=program, assign_attr=column)
+        return sizes, costs
+
+    def _int_attribute_of(self, namespace: str, name: str, ids: Sequence[UUID]) -> List[Optional[int]]:
+        """The value of the declared ``int`` attribute ``name`` of every stored vector in ``ids`` (``None``: no value, or an
+        unknown or removed id).  For ``QueryProcessor``'s clustering entries, which copy a freshly written cluster column
+        into the stored metadata of (usually) every row: the whole column comes down in one read, 8 B per row."""
+        if self._declared(name) != "int":
+            raise ValueError(f"_int_attribute_of: {name!r} is a {self._attributes[name]} attribute")
+        ids = list(ids)
+        ns = self._ns.get(namespace)
+        if self._no_rows(ns) or not ids:
+            return [None] * len(ids)
+        labels = ns.ids.lookup(ids)
+        column = ns.engine.get_attr(self._column(name), 0, ns.total)
+        values = np.where(labels >= 0, column[np.maximum(labels, 0)], _where.INT64_ABSENT)
+        return [None if v == _where.INT64_ABSENT else int(v) for v in values.tolist()]
 
     # ------------------------------------------------------------------ helpers
     @staticmethod

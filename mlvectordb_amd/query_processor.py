@@ -457,6 +457,41 @@ class QueryProcessor:
         stored = self._stored([u for g in groups for u in g], namespace)
         return [[stored[u] for u in g if u in stored] for g in groups]
 
+    # ---- additive: clustering (Index.cluster / Index.assign_clusters)
+    def cluster_vectors(self, k: int, namespace: str = "default", metric: str = "cosine", where=None, init="random",
+                        seed: int = 0, max_iterations: int = 25, assign_to: Optional[str] = None):
+        """Additive: k-means over the stored vectors of ``namespace`` (``Index.cluster``: on the device, from the rows in
+        HBM).  With ``assign_to`` (a declared ``int`` attribute) every clustered vector's id goes into the index's column
+        AND into the stored metadata under that key, as ``update_where`` keeps the two in step.  Returns the
+        ``ClusterResult``."""
+        return self._clustered("cluster_vectors", "cluster", namespace, where, assign_to,
+                               lambda: self._index.cluster(namespace, metric, k, where=where, init=init, seed=seed,
+                                                           max_iterations=max_iterations, assign_to=assign_to))
+
+    def assign_clusters(self, centroids, namespace: str = "default", metric: str = "cosine", assign_to: Optional[str] = None,
+                        where=None):
+        """Additive: every stored vector matching ``where`` to the nearest of ``centroids`` (``Index.assign_clusters``), the
+        cluster ids into ``assign_to`` in the index and in the stored metadata.  Returns (sizes, costs)."""
+        return self._clustered("assign_clusters", "assign_clusters", namespace, where, assign_to,
+                               lambda: self._index.assign_clusters(namespace, metric, centroids, assign_to=assign_to, where=where))
+
+    def _clustered(self, what: str, method: str, namespace: str, where, assign_to, call):
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError(f"{what}: where must be one dict filter (or None)")
+        if not hasattr(self._index, method):
+            raise ValueError(f"{what} needs an index with {method}")
+        if assign_to is None:
+            return call()
+        if assign_to not in (getattr(self._index, "attributes", None) or {}):
+            return call()  # (the index refuses it, in its own words)
+        # the candidates are the filter's matches BEFORE the call: it may read assign_to itself
+        ids = self._index.query_by_metadata(namespace, where if where is not None else {})
+        result = call()
+        values = self._index._int_attribute_of(namespace, assign_to, ids)
+        for vid, value in zip(ids, values):
+            self._storage.update_metadata(vid, {assign_to: value}, namespace)
+        return result
+
     # ---- additive: metadata queries (README.md:252,274: StorageEngine.query_by_metadata; no reference code)
     def count_where(self, where, namespace: str = "default") -> int:
         """Live vectors of ``namespace`` matching ``where`` (dict filter: counted on the device; predicate: over storage)."""
