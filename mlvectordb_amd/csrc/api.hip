@@ -4948,6 +4948,156 @@ int mlvdb_search_batch_bits(mlvdb_index* h, int32_t attr, const uint64_t* querie
     });
 }
 
+// ---- range search over bit codes (mlvdb_bits_range.h)
+extern "C++" {
+namespace {
+constexpr int64_t kBitsRangeOffs = kBitsChunk + 1;  // a pass's exclusive offsets: one per query and the pass's total
+
+// The call's state on the device, carved from h->bits_out: per pass its offsets and over-capacity flag, per query its
+// count and its cursor.  12 B per query.
+struct BitsRangeState {
+    int64_t* off = nullptr;
+    int32_t *cnt = nullptr, *cursor = nullptr, *over = nullptr;
+};
+
+// The queries [q0, q0 + n) of a pass and their popcounts up, into h->bits_in.
+int bits_range_upload(mlvdb_index* h, const uint64_t* queries, const int32_t* qpop, int64_t q0, int32_t n, int32_t words,
+                      uint64_t*& q_d, int32_t*& qpop_d) {
+    CARVE(h, h->bits_in, [&](Carver& c) {
+        q_d = c.take<uint64_t>((size_t)n * words);
+        qpop_d = c.take<int32_t>((size_t)n);
+    });
+    HIP_TRY(h, hipMemcpyAsync(q_d, queries + q0 * words, (size_t)n * words * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(qpop_d, qpop + q0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    return MLVDB_OK;
+}
+
+// Phase B of one pass whose segments hold `entries` hits in all (`longest` in the longest): collect the keys, sort every
+// segment, and the labels and distances down into the caller's packed arrays at `at`, the pass's first entry.
+int bits_range_pass(mlvdb_index* h, int32_t attr, const uint64_t* q_d, const int32_t* qpop_d, int32_t n, int32_t words,
+                    int32_t metric, double radius, const uint8_t* mask, int32_t nblk, const int64_t* off_d, int32_t* cursor_d,
+                    int64_t entries, int32_t longest, int64_t at, int64_t* out_labels, float* out_dist, double* out_dist64) {
+    hipStream_t s = h->stream;
+    uint64_t* keys = nullptr;
+    ListBlock o;
+    CARVE(h, h->partial, [&](Carver& c) {
+        keys = c.take<uint64_t>((size_t)entries);
+        o.take(c, (size_t)entries, 0);
+    });
+    HIP_TRY(h, launch_bits_range_walk(true, h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total, q_d, qpop_d, n, words,
+                                      metric, radius, nblk, nullptr, off_d, cursor_d, keys, s));
+    HIP_TRY(h, launch_bits_range_sort(h->attr_col[attr], h->list_pool[attr], q_d, qpop_d, n, words, metric, longest, off_d, keys,
+                                      o.lab, o.dist, o.d64, s));
+    return copy_down(h, s, {{out_labels, (size_t)at, o.lab, (size_t)entries}, {out_dist, (size_t)at, o.dist, (size_t)entries},
+                            {out_dist64, (size_t)at, o.d64, (size_t)entries}});
+}
+
+// The validated call on a non-empty index.  Phase A: per pass of kBitsChunk queries the counting walk and the plan; all
+// counts, offsets and flags down in one copy.  Phase B (when the caller's arrays take the segments): bits_range_pass.
+int bits_range_impl(mlvdb_index* h, int32_t attr, const uint64_t* queries, int64_t nq, int32_t words, int32_t metric,
+                    double radius, int64_t capacity, int64_t total_capacity, const uint8_t* mask, int64_t* out_labels,
+                    float* out_dist, double* out_dist64, int64_t* out_offsets, int64_t* out_counts) {
+    hipStream_t s = h->stream;
+    const int64_t npass = (nq + kBitsChunk - 1) / kBitsChunk;
+    std::vector<int32_t> qpop((size_t)nq, 0);
+    for (int64_t i = 0; i < nq; ++i)
+        for (int32_t w = 0; w < words; ++w) qpop[(size_t)i] += __builtin_popcountll(queries[i * words + w]);
+    int cus = 0;
+    HIP_TRY(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    BitsRangeState st;
+    CARVE(h, h->bits_out, [&](Carver& c) {
+        st.off = c.take<int64_t>((size_t)(npass * kBitsRangeOffs));
+        st.cnt = c.take<int32_t>((size_t)nq);
+        st.cursor = c.take<int32_t>((size_t)nq);
+        st.over = c.take<int32_t>((size_t)npass);
+    });
+    HIP_TRY(h, hipMemsetAsync(st.cnt, 0, span_bytes(st.cnt, st.over + npass), s));
+    uint64_t* q_d = nullptr;
+    int32_t* qpop_d = nullptr;
+    auto pass_blocks = [&](int64_t n) { return bits_range_blocks(h->total, n, words, cus); };
+    for (int64_t p = 0; p < npass; ++p) {
+        const int64_t q0 = p * kBitsChunk;
+        const int32_t n = (int32_t)std::min<int64_t>(kBitsChunk, nq - q0);
+        if (int rc = bits_range_upload(h, queries, qpop.data(), q0, n, words, q_d, qpop_d)) return rc;
+        HIP_TRY(h, launch_bits_range_walk(false, h->attr_col[attr], h->list_pool[attr], h->rn, mask, h->total, q_d, qpop_d, n,
+                                          words, metric, radius, pass_blocks(n), st.cnt + q0, nullptr, nullptr, nullptr, s));
+        HIP_TRY(h, launch_bits_range_plan(st.cnt + q0, n, (int32_t)capacity, st.off + p * kBitsRangeOffs, st.over + p, s));
+    }
+    std::vector<int32_t> cnt((size_t)nq), over((size_t)npass);
+    std::vector<int64_t> off((size_t)(npass * kBitsRangeOffs));
+    if (int rc = copy_down(h, s, {{cnt.data(), 0, st.cnt, cnt.size()}, {over.data(), 0, st.over, over.size()},
+                                  {off.data(), 0, st.off, off.size()}}))
+        return rc;
+    // the call's layout from the passes': a pass's segments follow the earlier passes'
+    int64_t need = 0;
+    bool any_over = false;
+    for (int64_t p = 0; p < npass; ++p) {
+        const int64_t q0 = p * kBitsChunk, n = std::min<int64_t>(kBitsChunk, nq - q0);
+        const int64_t* o = off.data() + p * kBitsRangeOffs;
+        for (int64_t i = 0; i < n; ++i) {
+            out_counts[q0 + i] = cnt[(size_t)(q0 + i)];
+            out_offsets[q0 + i] = need + o[i];
+        }
+        need += o[n];
+        any_over |= over[(size_t)p] != 0;
+    }
+    out_offsets[nq] = need;
+    if (need > total_capacity)
+        return fail(h, MLVDB_ERR_OVERFLOW, "bits range: more hits in all than total_capacity; out_counts / out_offsets hold the "
+                                           "exact counts and the layout the hits need, out_labels / out_dist nothing");
+    for (int64_t p = 0; p < npass && need > 0; ++p) {
+        const int64_t q0 = p * kBitsChunk;
+        const int32_t n = (int32_t)std::min<int64_t>(kBitsChunk, nq - q0);
+        const int64_t* o = off.data() + p * kBitsRangeOffs;
+        if (o[n] == 0) continue;
+        int64_t longest = 0;
+        for (int32_t i = 0; i < n; ++i) longest = std::max(longest, o[i + 1] - o[i]);
+        // (a one-pass call still has its queries in h->bits_in)
+        if (npass > 1)
+            if (int rc = bits_range_upload(h, queries, qpop.data(), q0, n, words, q_d, qpop_d)) return rc;
+        if (int rc = bits_range_pass(h, attr, q_d, qpop_d, n, words, metric, radius, mask, pass_blocks(n),
+                                     st.off + p * kBitsRangeOffs, st.cursor + q0, o[n], (int32_t)longest, out_offsets[q0],
+                                     out_labels, out_dist, out_dist64))
+            return rc;
+    }
+    if (any_over)
+        return fail(h, MLVDB_ERR_OVERFLOW, "bits range: some query has more hits than `capacity`: its segment is empty and "
+                                           "out_counts holds its exact count");
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_range_batch_bits(mlvdb_index* h, int32_t attr, const uint64_t* queries, int64_t nq, int32_t words, int32_t metric,
+                           double radius, int64_t capacity, int64_t total_capacity, const mlvdb_where* where,
+                           int64_t* out_labels, float* out_dist, double* out_dist64, int64_t* out_offsets,
+                           int64_t* out_counts) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything is checked on the host before anything is launched
+    if (int rc = bits_attr_check(h, attr)) return rc;
+    if (int rc = bits_words_check(h, words)) return rc;
+    if (metric != MLVDB_BITS_HAMMING && metric != MLVDB_BITS_JACCARD) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown bits metric");
+    if (int rc = check_nq(h, nq)) return rc;
+    if (radius != radius) return fail(h, MLVDB_ERR_INVALID_ARG, "radius is NaN");
+    if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
+    if (capacity > MLVDB_BITS_RANGE_MAX_HITS) return fail(h, MLVDB_ERR_UNSUPPORTED, "bits range: capacity above MLVDB_BITS_RANGE_MAX_HITS");
+    if (total_capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "total_capacity must be >= 0");
+    if (!out_offsets || (nq > 0 && (!queries || !out_counts)) || (total_capacity > 0 && (!out_labels || !out_dist)))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (int rc = check_row_limit(h, "bits range: ")) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
+    if (nq == 0 || h->total == 0) {
+        for (int64_t i = 0; i < nq; ++i) out_counts[i] = 0;
+        for (int64_t i = 0; i <= nq; ++i) out_offsets[i] = 0;
+        return MLVDB_OK;
+    }
+    const uint8_t* mask = nullptr;  // the program's live matching rows, which every walk reads at one byte per row
+    if (int rc = where_mask(h, where, &mask)) return rc;
+    return bits_range_impl(h, attr, queries, nq, words, metric, radius, capacity, total_capacity, mask, out_labels, out_dist,
+                           out_dist64, out_offsets, out_counts);
+    });
+}
+
 // ---- hybrid search (mlvdb_hybrid.h)
 extern "C++" {
 namespace {

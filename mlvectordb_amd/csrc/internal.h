@@ -24,6 +24,7 @@
 #include "../../include/mlvdb_list.h"
 #include "../../include/mlvdb_sparse.h"
 #include "../../include/mlvdb_bits.h"
+#include "../../include/mlvdb_bits_range.h"
 #include "../../include/mlvdb_hybrid.h"
 #include "../../include/mlvdb_geo.h"
 #include "../../include/mlvdb_score.h"
@@ -514,6 +515,27 @@ int32_t bits_scan_blocks(int64_t total, int64_t nq, int32_t k, int32_t words);
 hipError_t launch_bits_scan(const int64_t* slots, const int64_t* pool, const float* rn, const uint8_t* mask, int64_t total,
                             const uint64_t* queries, const int32_t* qpop, int32_t nq, int32_t words, int32_t metric, int32_t k,
                             int32_t nblk, TopEntry* partial, hipStream_t s);
+
+// ---------------------------------------------------------------- range search over bit codes (kernels_bits_range.hip, include/mlvdb_bits_range.h)
+constexpr int kBitsRangeQT = 32;           // queries per tile: 128 VGPRs of query words up to 32 words, 63.75 KiB of LDS above
+constexpr int kBitsRangeBlocksPerCU = 2;   // resident blocks per compute unit the grid is sized for (the resource table)
+int bits_lanes(int32_t words);             // (kernels_bits.hip) lanes per row: the smallest power of two >= words / 2, at most 16
+int32_t bits_range_blocks(int64_t total, int64_t nq, int32_t words, int32_t cus);
+// One walk over the rows for the nq <= kBitsChunk queries of a pass (queries[q * words ..], qpop[q] its popcount), with the
+// candidates of launch_bits_scan.  fill = false: cnt[q] += the rows with d <= radius (cnt cleared by the caller).
+// fill = true: the key (distance << 32 | row) of every such row -> keys[off[q] + cursor[q]++] for the queries with
+// off[q + 1] > off[q] (cursor cleared by the caller, off from launch_bits_range_plan over the counts of the same rows).
+hipError_t launch_bits_range_walk(bool fill, const int64_t* slots, const int64_t* pool, const float* rn, const uint8_t* mask,
+                                  int64_t total, const uint64_t* queries, const int32_t* qpop, int32_t nq, int32_t words,
+                                  int32_t metric, double radius, int32_t nblk, int32_t* cnt, const int64_t* off, int32_t* cursor,
+                                  uint64_t* keys, hipStream_t s);
+// off[0 .. n] = the exclusive scan of (cnt[q] <= capacity ? cnt[q] : 0); *over = some cnt[q] > capacity
+hipError_t launch_bits_range_plan(const int32_t* cnt, int32_t n, int32_t capacity, int64_t* off, int32_t* over, hipStream_t s);
+// Every segment keys[off[q], off[q + 1]) sorted; out_lab / out_dist / out_d64[off[q] + r] = the row of its r-th key and that
+// row's distance, computed again from its code.  longest = the longest segment (the launch's LDS).
+hipError_t launch_bits_range_sort(const int64_t* slots, const int64_t* pool, const uint64_t* queries, const int32_t* qpop,
+                                  int32_t n, int32_t words, int32_t metric, int32_t longest, const int64_t* off,
+                                  const uint64_t* keys, int64_t* out_lab, float* out_dist, double* out_d64, hipStream_t s);
 
 // rn[i] = NaN for the rows of mask, and their int8 row pairs (i < i8_rows; rp8 may be null) as tombstone_rp8_kernel does
 hipError_t launch_tombstone_mask(const uint8_t* mask, float* rn, float* rp8, int64_t i8_rows, int l2, int64_t total,

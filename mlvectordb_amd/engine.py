@@ -579,6 +579,41 @@ class HipScanEngine:
             labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, dist64.ctypes.data), "search_batch_bits")
         return labels, dist, counts, dist64
 
+    def range_bits(self, attr: int, queries: np.ndarray, radius: float, metric: str = "hamming",
+                   capacity: int = _native.BITS_RANGE_MAX_HITS, where=None, count_only: bool = False):
+        """Range search over bit codes (``mlvdb_range_batch_bits``): per query the candidates of ``search_bits`` whose
+        distance is ``<= radius``, ranked by (distance ascending, label ascending).  Returns (hits, distances float64
+        [total], counts int64 [nq]): ``hits`` is what ``range`` returns (``RangeHits``) and the float64 distances lie packed
+        like its ``dist``.  ``counts`` is exact for any radius; a query with more than ``capacity`` (<= 16384) hits has an
+        empty segment.  ``count_only=True`` -> the counts alone.  Two native calls: the first counts, the second is made
+        with the exact total."""
+        queries = np.ascontiguousarray(queries, dtype=np.uint64)
+        if queries.ndim != 2:
+            raise RuntimeError(f"queries must be [nq, words]; got shape {queries.shape}")
+        if metric not in _native.BITS_METRIC_CODES:
+            raise RuntimeError(f"unknown bits metric {metric!r} (one of {sorted(_native.BITS_METRIC_CODES)})")
+        nq = queries.shape[0]
+        w, keep = self._where_arg(where)
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        counts = np.zeros(nq, dtype=np.int64)
+
+        def call(total, labels, dist, dist64):
+            return self._check(self._lib.mlvdb_range_batch_bits(
+                self._h, int(attr), _nonempty(queries), nq, queries.shape[1], _native.BITS_METRIC_CODES[metric], float(radius),
+                int(capacity), total, w, _opt(labels), _opt(dist), _opt(dist64), offsets.ctypes.data, _nonempty(counts)),
+                "range_batch_bits", allow=(_native.ERR_OVERFLOW,))
+
+        call(0, None, None, None)
+        if count_only:
+            return counts
+        total = int(offsets[nq])
+        labels = np.empty(total, dtype=np.int64)
+        dist = np.empty(total, dtype=np.float32)
+        dist64 = np.empty(total, dtype=np.float64)
+        if total:
+            call(total, labels, dist, dist64)
+        return RangeHits(labels, dist, offsets), dist64, counts
+
     # -- hybrid search (include/mlvdb_hybrid.h) -------------------------------------------
     def search_hybrid(self, queries: np.ndarray, attr: int, sparse_queries, k: int, fetch_dense: int, fetch_sparse: int,
                       method: str = "rrf", weights=(1.0, 1.0), rrf_k: float = 60.0, where=None, components: bool = False):

@@ -1037,6 +1037,61 @@ class Index:
         labels, _, counts, d64 = search(self._column(by), q, k, metric=metric, where=program)
         return BatchHits(labels, d64, counts, ns.ids)
 
+    _MAX_HITS_BITS = _native.BITS_RANGE_MAX_HITS  # MLVDB_BITS_RANGE_MAX_HITS
+
+    def _range_bits_args(self, what: str, queries, radius, namespace: str, by: str, metric: str, where):
+        """The refusals ``range_search_bits`` and ``count_within_bits`` share, in their order; returns (the queries as uint64
+        words, the compiled filter, the namespace or ``None``)."""
+        self._refuse_sharded(what)
+        if not _where.is_bits(self._declared(by, f"{what}: ")):
+            raise ValueError(f"{what}: attribute {by!r} is a {self._attributes[by]} column; it needs a bits attribute")
+        if metric not in self._BITS_METRICS:
+            raise ValueError(f"{what}: metric must be one of {self._BITS_METRICS} (got {metric!r})")
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)) or math.isnan(radius):
+            raise ValueError(f"{what}: radius must be a number (got {radius!r})")
+        self._one_filter(what, where)
+        q = self._bits_queries(queries, _where.bits_width(self._attributes[by]), what)
+        return q, self._program(namespace, where), self._ns.get(namespace)
+
+    def range_search_bits(self, queries, radius: float, namespace: str, by: str, *, metric: str = "hamming",
+                          where: Optional[Mapping] = None, max_hits: int = 16384) -> List[List[SearchResult]]:
+        """Additive: every live row whose code in the declared ``bits<N>`` attribute ``by`` lies within ``radius`` of each
+        query, on the device (include/mlvdb_bits_range.h) -- "everything within Hamming distance 6 of this hash", "every
+        fingerprint with Tanimoto >= 0.85" (``metric="jaccard"``, ``radius=0.15``).  Queries, metrics and ``where`` as in
+        ``search_bits``; a row is a hit iff its fp64 distance is ``<= radius`` (a negative radius finds nothing).  Per query
+        the hits come back nearest first, ties to the earlier row, in the shape ``range_search_many`` returns, the score
+        being the fp64 distance.  A query with more than ``max_hits`` (<= 16384) hits raises ``OverflowError`` naming the
+        first such query and its exact count: ``count_within_bits`` answers for any radius.  Every refusal happens before
+        the engine is touched."""
+        what = "range_search_bits"
+        if not self._int_in(max_hits, 1, self._MAX_HITS_BITS):
+            raise ValueError(f"{what}: max_hits must be an int in [1, {self._MAX_HITS_BITS}] (got {max_hits!r})")
+        q, program, ns = self._range_bits_args(what, queries, radius, namespace, by, metric, where)
+        if self._nothing_to_search(ns, nq=q.shape[0]):
+            return [[] for _ in range(q.shape[0])]
+        hits, d64, counts = self._engine_entry(ns, "range_bits", "bits attributes need")(
+            self._column(by), q, float(radius), metric, int(max_hits), where=program)
+        over = np.flatnonzero(counts > max_hits)
+        if over.size:
+            raise OverflowError(f"{what}: query {int(over[0])} has {int(counts[over[0]])} hits, more than max_hits={max_hits} "
+                                f"(count_within_bits gives the counts; a smaller radius or a filter the hits)")
+        out: List[List[SearchResult]] = []
+        for i, (labels, _) in enumerate(hits):
+            uids = ns.ids.uuids_at(labels).tolist()
+            scores = d64[hits.offsets[i]:hits.offsets[i + 1]].tolist()
+            out.append([SearchResult(vector_id=u, score=s) for u, s in zip(uids, scores) if u is not None])
+        return out
+
+    def count_within_bits(self, queries, radius: float, namespace: str, by: str, *, metric: str = "hamming",
+                          where: Optional[Mapping] = None) -> np.ndarray:
+        """Additive: per query the exact number of hits ``range_search_bits`` has to return, as an ``int64`` array -- for
+        any radius, also where the hits themselves would exceed ``max_hits``."""
+        q, program, ns = self._range_bits_args("count_within_bits", queries, radius, namespace, by, metric, where)
+        if self._nothing_to_search(ns, nq=q.shape[0]):
+            return np.zeros(q.shape[0], dtype=np.int64)
+        return self._engine_entry(ns, "range_bits", "bits attributes need")(
+            self._column(by), q, float(radius), metric, where=program, count_only=True)
+
     _FUSIONS = ("rrf", "linear", "relative")  # MLVDB_FUSE_*
     _MAX_FETCH_K_HYBRID = 1024                # MLVDB_HYBRID_MAX_FETCH_DENSE
 

@@ -181,6 +181,23 @@ class QueryProcessor:
             raise ValueError("find_similar_bits needs an index with search_bits")
         return self._enrich_many(self._index.search_bits(queries, top_k, namespace, by, metric=metric, where=where), namespace)
 
+    def find_in_radius_bits(self, query, radius: float, namespace: str = "default", by: str = "", metric: str = "hamming",
+                            max_hits: int = 16384, where=None) -> List[dict]:
+        """Additive: every vector whose code in the declared ``bits<N>`` attribute ``by`` lies within ``radius`` (Hamming or
+        Jaccard) of one bit code (``Index.range_search_bits``), nearest first, as ``find_in_radius`` returns its hits
+        (``score``: the distance)."""
+        return self.find_in_radius_bits_many([query], radius, namespace, by, metric=metric, max_hits=max_hits, where=where)[0]
+
+    def find_in_radius_bits_many(self, queries, radius: float, namespace: str = "default", by: str = "",
+                                 metric: str = "hamming", max_hits: int = 16384, where=None) -> List[List[dict]]:
+        """Batched ``find_in_radius_bits``: one code per query, one call.  ``where`` is ``None`` or one dict filter."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("find_in_radius_bits: where must be one dict filter (or None)")
+        if not hasattr(self._index, "range_search_bits"):
+            raise ValueError("find_in_radius_bits needs an index with range_search_bits")
+        per_query = self._index.range_search_bits(queries, radius, namespace, by, metric=metric, where=where, max_hits=max_hits)
+        return [self._fill_values(self._enrich(hits, namespace), namespace) for hits in per_query]
+
     def find_similar_hybrid(self, query, sparse_query, top_k: int, namespace: str = "default", metric: str = "cosine",
                             by: str = "", **options) -> List[dict]:
         """Additive: hybrid retrieval for one query -- a dense vector and a sparse one (a mapping ``{term: weight}`` or a
