@@ -226,6 +226,12 @@ BITS_RANGE_SIGNATURES = {
                                          C.POINTER(Where), _P, _P, _P, _P, _P]),
 }
 
+# include/mlvdb_bits_join.h: similarity join over bit codes -- the rows within a radius of the codes of given stored rows
+BITS_JOIN_SIGNATURES = {
+    "mlvdb_join_within_bits": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int64,
+                                         C.c_int64, C.POINTER(Where), _P, _P, _P, _P, _P]),
+}
+
 # include/mlvdb_hybrid.h: hybrid search -- a dense and a sparse kNN answer fused into one ranked list on the device
 FUSE_CODES = {"rrf": 0, "linear": 1, "relative": 2}
 HYBRID_MAX_FETCH_DENSE = 1024
@@ -331,7 +337,7 @@ def load() -> C.CDLL:
                                       **WHERE_EACH_RANGE_SIGNATURES, **DISTINCT_SIGNATURES, **GROUPED_SIGNATURES, **FACET_SIGNATURES,
                                       **ORDER_SIGNATURES, **MMR_SIGNATURES, **LIKE_SIGNATURES, **MAXSIM_SIGNATURES,
                                       **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **BITS_SIGNATURES,
-                                      **BITS_RANGE_SIGNATURES, **HYBRID_SIGNATURES,
+                                      **BITS_RANGE_SIGNATURES, **BITS_JOIN_SIGNATURES, **HYBRID_SIGNATURES,
                                       **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES,
                                       **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES, **CLUSTER_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete

@@ -5098,6 +5098,172 @@ int mlvdb_range_batch_bits(mlvdb_index* h, int32_t attr, const uint64_t* queries
     });
 }
 
+// ---- similarity join over bit codes (mlvdb_bits_join.h)
+extern "C++" {
+namespace {
+// The validated call on a non-empty index with n_left >= 1.  The popcount of every candidate row once (4 B per row), then
+// per wave of left rows (bits_join_wave_rows: its dense codes stay within BITS_JOIN_WS_MB MiB) -- phase A: gather, counting
+// walk, plan; the counts, offsets and flags of all waves down in one copy; phase B (when the caller's arrays take the
+// segments): gather again unless the call is one wave, fill walk, sort, the wave's hits down at its place.  h->bits_out
+// holds the call's state (28 B per left row, 4 B per row), h->bits_in the wave's codes, h->partial a wave's keys and hits.
+int bits_join_impl(mlvdb_index* h, int32_t attr, const int64_t* left, int64_t n_left, int32_t mode, int32_t words,
+                   int32_t metric, double radius, int64_t capacity, int64_t total_capacity, const uint8_t* mask,
+                   int64_t* out_labels, float* out_dist, double* out_dist64, int64_t* out_offsets, int64_t* out_counts) {
+    hipStream_t s = h->stream;
+    const int64_t wave_rows = bits_join_wave_rows(words, h->tn.bits_join_ws_mb);
+    const int64_t nwave = (n_left + wave_rows - 1) / wave_rows;
+    const int64_t nrt = (h->total + kBitsJoinTile - 1) / kBitsJoinTile;
+    int cus = 0;
+    HIP_TRY(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    // The right tiles every left tile walks, as one exclusive scan per wave: all of them, or (LATER) those that hold a row
+    // above the tile's first label -- a self-join walks the triangle, not the square.
+    std::vector<int64_t> tb, tb_at((size_t)nwave);
+    for (int64_t v = 0; v < nwave; ++v) {
+        const int64_t l0 = v * wave_rows, n = std::min(wave_rows, n_left - l0);
+        tb_at[(size_t)v] = (int64_t)tb.size();
+        int64_t run = 0;
+        for (int64_t i = 0; i < n; i += kBitsJoinTile) {
+            tb.push_back(run);
+            run += nrt - (mode == MLVDB_JOIN_LATER ? std::min(nrt, (left[l0 + i] + 1) / kBitsJoinTile) : 0);
+        }
+        tb.push_back(run);
+    }
+    int64_t *labels_d = nullptr, *tb_d = nullptr, *off_d = nullptr;
+    int32_t *rpop = nullptr, *cnt_d = nullptr, *cursor = nullptr, *over_d = nullptr, *lpop = nullptr;
+    uint64_t* lq = nullptr;
+    CARVE(h, h->bits_out, [&](Carver& c) {
+        labels_d = c.take<int64_t>((size_t)n_left);
+        tb_d = c.take<int64_t>(tb.size());
+        off_d = c.take<int64_t>((size_t)(n_left + nwave));  // per wave its rows' offsets and its total
+        rpop = c.take<int32_t>((size_t)h->total);
+        cnt_d = c.take<int32_t>((size_t)n_left);
+        cursor = c.take<int32_t>((size_t)n_left);
+        over_d = c.take<int32_t>((size_t)nwave);
+    });
+    CARVE(h, h->bits_in, [&](Carver& c) {
+        lq = c.take<uint64_t>((size_t)std::min(wave_rows, n_left) * words);
+        lpop = c.take<int32_t>((size_t)std::min(wave_rows, n_left));
+    });
+    HIP_TRY(h, hipMemcpyAsync(labels_d, left, (size_t)n_left * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(tb_d, tb.data(), tb.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(cnt_d, 0, span_bytes(cnt_d, over_d + nwave), s));
+    const int64_t* slots = h->attr_col[attr];
+    const int64_t* pool = h->list_pool[attr];
+    HIP_TRY(h, launch_bits_join_gather(slots, pool, h->rn, mask, nullptr, h->total, words, nullptr, rpop, s));
+    struct Wave {
+        int64_t l0, items, *off;
+        int32_t n;
+        const int64_t* tiles;
+    };
+    auto wave = [&](int64_t v) {
+        const int64_t l0 = v * wave_rows, n = std::min(wave_rows, n_left - l0);
+        const int64_t at = tb_at[(size_t)v], nlt = (n + kBitsJoinTile - 1) / kBitsJoinTile;
+        return Wave{l0, tb[(size_t)(at + nlt)], off_d + l0 + v, (int32_t)n, tb_d + at};
+    };
+    // a left label is a left row iff it is live and holds a code of `words` words: `where` restricts the partners alone
+    auto gather = [&](const Wave& w) {
+        return launch_bits_join_gather(slots, pool, h->rn, nullptr, labels_d + w.l0, w.n, words, lq, lpop, s);
+    };
+    auto walk = [&](const Wave& w, bool fill, uint64_t* keys) {
+        return launch_bits_join_walk(fill, slots, pool, rpop, h->total, labels_d + w.l0, lq, lpop, w.n, w.tiles, w.items, words,
+                                     metric, mode, radius, bits_join_blocks(w.items, cus), cnt_d + w.l0, w.off, cursor + w.l0,
+                                     keys, s);
+    };
+    for (int64_t v = 0; v < nwave; ++v) {
+        const Wave w = wave(v);
+        HIP_TRY(h, gather(w));
+        HIP_TRY(h, walk(w, false, nullptr));
+        HIP_TRY(h, launch_bits_join_plan(cnt_d + w.l0, w.n, (int32_t)capacity, w.off, over_d + v, s));
+    }
+    std::vector<int32_t> cnt((size_t)n_left), over((size_t)nwave);
+    std::vector<int64_t> off((size_t)(n_left + nwave));
+    if (int rc = copy_down(h, s, {{cnt.data(), 0, cnt_d, cnt.size()}, {over.data(), 0, over_d, over.size()},
+                                  {off.data(), 0, off_d, off.size()}}))
+        return rc;
+    // the call's layout from the waves': a wave's segments follow the earlier waves'
+    int64_t need = 0;
+    bool any_over = false;
+    for (int64_t v = 0; v < nwave; ++v) {
+        const Wave w = wave(v);
+        const int64_t* o = off.data() + w.l0 + v;
+        for (int64_t i = 0; i < w.n; ++i) {
+            out_counts[w.l0 + i] = cnt[(size_t)(w.l0 + i)];
+            out_offsets[w.l0 + i] = need + o[i];
+        }
+        need += o[w.n];
+        any_over |= over[(size_t)v] != 0;
+    }
+    out_offsets[n_left] = need;
+    if (need > total_capacity)
+        return fail(h, MLVDB_ERR_OVERFLOW, "bits join: more partners in all than total_capacity; out_counts / out_offsets hold the "
+                                           "exact counts and the layout the hits need, out_labels / out_dist nothing");
+    for (int64_t v = 0; v < nwave && need > 0; ++v) {
+        const Wave w = wave(v);
+        const int64_t* o = off.data() + w.l0 + v;
+        const int64_t entries = o[w.n];
+        if (entries == 0) continue;
+        int64_t longest = 0;
+        for (int32_t i = 0; i < w.n; ++i) longest = std::max(longest, o[i + 1] - o[i]);
+        if (nwave > 1) HIP_TRY(h, gather(w));  // (a one-wave call still has its codes in h->bits_in)
+        uint64_t* keys = nullptr;
+        ListBlock b;
+        CARVE(h, h->partial, [&](Carver& c) {
+            keys = c.take<uint64_t>((size_t)entries);
+            b.take(c, (size_t)entries, 0);
+        });
+        HIP_TRY(h, walk(w, true, keys));
+        // the wave's dense codes are the sort's queries: it computes every reported distance again from the two codes
+        HIP_TRY(h, launch_bits_range_sort(slots, pool, lq, lpop, w.n, words, metric, (int32_t)longest, w.off, keys, b.lab, b.dist,
+                                          b.d64, s));
+        const size_t at = (size_t)out_offsets[w.l0];
+        if (int rc = copy_down(h, s, {{out_labels, at, b.lab, (size_t)entries}, {out_dist, at, b.dist, (size_t)entries},
+                                      {out_dist64, at, b.d64, (size_t)entries}}))
+            return rc;
+    }
+    if (any_over)
+        return fail(h, MLVDB_ERR_OVERFLOW, "bits join: some row has more partners than `capacity`: its segment is empty and "
+                                           "out_counts holds its exact count");
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_join_within_bits(mlvdb_index* h, int32_t attr, const int64_t* left_labels, int64_t n_left, int32_t mode,
+                           int32_t words, int32_t metric, double radius, int64_t capacity, int64_t total_capacity,
+                           const mlvdb_where* where, int64_t* out_labels, float* out_dist, double* out_dist64,
+                           int64_t* out_offsets, int64_t* out_counts) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything is checked on the host before anything is launched
+    if (int rc = bits_attr_check(h, attr)) return rc;
+    if (int rc = bits_words_check(h, words)) return rc;
+    if (metric != MLVDB_BITS_HAMMING && metric != MLVDB_BITS_JACCARD) return fail(h, MLVDB_ERR_INVALID_ARG, "unknown bits metric");
+    if (mode != MLVDB_JOIN_OTHERS && mode != MLVDB_JOIN_LATER) return fail(h, MLVDB_ERR_INVALID_ARG, "bits join: unknown mode");
+    if (int rc = check_nq(h, n_left)) return rc;
+    if (radius != radius) return fail(h, MLVDB_ERR_INVALID_ARG, "radius is NaN");
+    if (capacity < 1) return fail(h, MLVDB_ERR_INVALID_ARG, "capacity must be >= 1");
+    if (capacity > MLVDB_BITS_RANGE_MAX_HITS) return fail(h, MLVDB_ERR_UNSUPPORTED, "bits join: capacity above MLVDB_BITS_RANGE_MAX_HITS");
+    if (total_capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "total_capacity must be >= 0");
+    if (!out_offsets || (n_left > 0 && (!left_labels || !out_counts)) || (total_capacity > 0 && (!out_labels || !out_dist)))
+        return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    for (int64_t i = 0; i < n_left; ++i) {
+        if (left_labels[i] < 0 || left_labels[i] >= h->total) return fail(h, MLVDB_ERR_INVALID_ARG, "bits join: left label out of range");
+        if (i > 0 && left_labels[i] <= left_labels[i - 1])
+            return fail(h, MLVDB_ERR_INVALID_ARG, "bits join: left labels must ascend strictly");
+    }
+    if (int rc = check_row_limit(h, "bits join: ")) return rc;
+    if (int rc = where ? where_prepare(h, where) : MLVDB_OK) return rc;
+    if (n_left == 0 || h->total == 0) {
+        for (int64_t i = 0; i < n_left; ++i) out_counts[i] = 0;
+        for (int64_t i = 0; i <= n_left; ++i) out_offsets[i] = 0;
+        return MLVDB_OK;
+    }
+    const uint8_t* mask = nullptr;  // the program's live matching rows: the partners
+    if (int rc = where_mask(h, where, &mask)) return rc;
+    return bits_join_impl(h, attr, left_labels, n_left, mode, words, metric, radius, capacity, total_capacity, mask, out_labels,
+                          out_dist, out_dist64, out_offsets, out_counts);
+    });
+}
+
 // ---- hybrid search (mlvdb_hybrid.h)
 extern "C++" {
 namespace {

@@ -25,6 +25,7 @@
 #include "../../include/mlvdb_sparse.h"
 #include "../../include/mlvdb_bits.h"
 #include "../../include/mlvdb_bits_range.h"
+#include "../../include/mlvdb_bits_join.h"
 #include "../../include/mlvdb_hybrid.h"
 #include "../../include/mlvdb_geo.h"
 #include "../../include/mlvdb_score.h"
@@ -148,7 +149,8 @@ constexpr int kQueryImageMaxLds = 64 * 1024;
     X(where_gather, "WHERE_GATHER", 150) /* per-query filters: gather a program's rows when matches x query tiles x 1000 <= live x this (0: never; tools/where_each_ab.py) */ \
     X(distinct_oversample, "DISTINCT_OVERSAMPLE", 4) /* distinct kNN: the list pass ranks min(1024, max(64, this x k)) rows per query (0: no list pass, every query takes the grouped exact scan; tools/distinct_ab.py) */ \
     X(maxsim_ws_mb, "MAXSIM_WS_MB", 1024) /* late interaction: MiB of the [token, document] workspace one chunk of queries may take (always at least one query; every setting returns the same bytes) */ \
-    X(examples_ws_mb, "EXAMPLES_WS_MB", 1024) /* recommend / discover: MiB of the per-(query, row) state one chunk of queries may take for its bags of more than one tile (always at least one query; every setting returns the same bytes) */
+    X(examples_ws_mb, "EXAMPLES_WS_MB", 1024) /* recommend / discover: MiB of the per-(query, row) state one chunk of queries may take for its bags of more than one tile (always at least one query; every setting returns the same bytes) */ \
+    X(bits_join_ws_mb, "BITS_JOIN_WS_MB", 32) /* bits join: MiB the dense copy of one wave of left codes may take (always at least one tile of 128 rows; every setting returns the same bytes) */
 
 struct Tuning {
 #define X(field, name, dflt) int field = dflt;
@@ -532,10 +534,38 @@ hipError_t launch_bits_range_walk(bool fill, const int64_t* slots, const int64_t
 // off[0 .. n] = the exclusive scan of (cnt[q] <= capacity ? cnt[q] : 0); *over = some cnt[q] > capacity
 hipError_t launch_bits_range_plan(const int32_t* cnt, int32_t n, int32_t capacity, int64_t* off, int32_t* over, hipStream_t s);
 // Every segment keys[off[q], off[q + 1]) sorted; out_lab / out_dist / out_d64[off[q] + r] = the row of its r-th key and that
-// row's distance, computed again from its code.  longest = the longest segment (the launch's LDS).
+// row's distance, computed again from its code.  longest = the longest segment (the launch's LDS).  n <= kBitsSortMaxSegments:
+// a pass of the range search, or a left wave of the bits join (one workgroup per segment, an empty one returns at once).
+constexpr int kBitsSortMaxSegments = 1 << 20;
 hipError_t launch_bits_range_sort(const int64_t* slots, const int64_t* pool, const uint64_t* queries, const int32_t* qpop,
                                   int32_t n, int32_t words, int32_t metric, int32_t longest, const int64_t* off,
                                   const uint64_t* keys, int64_t* out_lab, float* out_dist, double* out_d64, hipStream_t s);
+
+// ---------------------------------------------------------------- similarity join over bit codes (kernels_bits_join.hip, include/mlvdb_bits_join.h)
+constexpr int kBitsJoinTile = 128;            // left rows x right rows of a tile: 8 x 8 pairs per thread of 256
+constexpr int kBitsJoinKC = 8;                // words per staged chunk
+constexpr int kBitsJoinBlocksPerCU = 3;      // resident blocks per compute unit (the resource table)
+// The left rows a wave holds: a multiple of the tile whose dense codes stay within budget_mb MiB (Tuning::bits_join_ws_mb),
+// at least one tile and at most the sort's segment limit.
+int64_t bits_join_wave_rows(int32_t words, int32_t budget_mb);
+// Blocks of one walk: a resident set (kBitsJoinBlocksPerCU per compute unit), no more than the walk has tiles.
+int32_t bits_join_blocks(int64_t items, int32_t cus);
+// pop[i] = the popcount of the code of row (labels ? labels[i] : i) if that row is live (rn), set in `mask` (may be null) and
+// holds exactly `words` words, else -1; dense (may be null) [n][words] = the code, zeros for a -1 row.  labels < total.
+hipError_t launch_bits_join_gather(const int64_t* slots, const int64_t* pool, const float* rn, const uint8_t* mask,
+                                   const int64_t* labels, int64_t n, int32_t words, uint64_t* dense, int32_t* pop, hipStream_t s);
+// One walk of the tiles (left tile, right tile) of a wave of n left rows against all rows.  labels [n] ascending, lq / lpop
+// the wave's dense codes and popcounts (launch_bits_join_gather), rpop [total] the rows' popcounts (-1: no candidate);
+// tile_begin [ceil(n / 128) + 1] = the exclusive scan of the right tiles each left tile walks (all of them, or those from
+// the tile of label + 1 on in the LATER mode), made by the caller.  fill = false: cnt[i] += the partners of left row i (cnt
+// cleared by the caller); fill = true: the key of every partner -> keys[off[i] + cursor[i]++] where off[i + 1] > off[i].
+hipError_t launch_bits_join_walk(bool fill, const int64_t* slots, const int64_t* pool, const int32_t* rpop, int64_t total,
+                                 const int64_t* labels, const uint64_t* lq, const int32_t* lpop, int32_t n,
+                                 const int64_t* tile_begin, int64_t items, int32_t words, int32_t metric, int32_t mode,
+                                 double radius, int32_t nblk, int32_t* cnt, const int64_t* off, int32_t* cursor,
+                                 uint64_t* keys, hipStream_t s);
+// off[0 .. n] = the exclusive scan of (cnt[i] <= capacity ? cnt[i] : 0) over a wave; *over = some cnt[i] > capacity
+hipError_t launch_bits_join_plan(const int32_t* cnt, int32_t n, int32_t capacity, int64_t* off, int32_t* over, hipStream_t s);
 
 // rn[i] = NaN for the rows of mask, and their int8 row pairs (i < i8_rows; rp8 may be null) as tombstone_rp8_kernel does
 hipError_t launch_tombstone_mask(const uint8_t* mask, float* rn, float* rp8, int64_t i8_rows, int l2, int64_t total,

@@ -13,6 +13,7 @@
 // bits_range_plan_kernel turns a pass's counts into segment lengths (0 above `capacity`), their exclusive scan and the
 // over-capacity flag.  bits_range_sort_kernel is one workgroup per non-empty segment: keys into LDS, bitonic sort, labels
 // out, and every hit's distance computed again from the row's code and the query -- the key orders, it reports nothing.
+#include "bits_range_key.h"
 #include "internal.h"
 
 namespace mlvdb {
@@ -33,14 +34,6 @@ __device__ __forceinline__ void load_pair(bool have, const uint64_t* src, int w,
     } else if (have && w < words) {
         xa = src[w];
     }
-}
-
-// (distance, row) as one integer that orders like the pair.  Hamming distances are integers; two distinct Jaccard quotients
-// of denominators <= 32,640 differ by more than 2^-31 (>= 3.75e-9), the scaling by 2^31 is exact, and equal
-// quotients give equal keys, so floor(d * 2^31) is strictly monotone on the distances that occur.  Rows stay below 2^31.
-__device__ __forceinline__ uint64_t range_key(int32_t metric, int32_t ham, double d, int64_t row) {
-    const uint64_t hi = metric == MLVDB_BITS_JACCARD ? (uint64_t)(d * 2147483648.0) : (uint64_t)ham;
-    return hi << 32 | (uint64_t)row;
 }
 }  // namespace
 
@@ -344,7 +337,8 @@ hipError_t launch_bits_range_plan(const int32_t* cnt, int32_t n, int32_t capacit
 hipError_t launch_bits_range_sort(const int64_t* slots, const int64_t* pool, const uint64_t* queries, const int32_t* qpop,
                                   int32_t n, int32_t words, int32_t metric, int32_t longest, const int64_t* off,
                                   const uint64_t* keys, int64_t* out_lab, float* out_dist, double* out_d64, hipStream_t s) {
-    if (n < 1 || n > kBitsChunk || longest < 1 || longest > MLVDB_BITS_RANGE_MAX_HITS || words < 1 || words > MLVDB_BITS_MAX_WORDS)
+    if (n < 1 || n > kBitsSortMaxSegments || longest < 1 || longest > MLVDB_BITS_RANGE_MAX_HITS || words < 1 ||
+        words > MLVDB_BITS_MAX_WORDS)
         return hipErrorInvalidValue;
     size_t np = 1;
     while (np < (size_t)longest) np <<= 1;

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 from collections.abc import Sequence
-from typing import List, Protocol, Tuple
+from typing import List, Optional, Protocol, Tuple
 
 import numpy as np
 
@@ -613,6 +613,44 @@ class HipScanEngine:
         if total:
             call(total, labels, dist, dist64)
         return RangeHits(labels, dist, offsets), dist64, counts
+
+    def join_within_bits(self, attr: int, labels: np.ndarray, mode: int, radius: float,
+                         capacity: int = _native.BITS_RANGE_MAX_HITS, metric: str = "hamming", where=None,
+                         words: Optional[int] = None):
+        """Similarity join over bit codes (``mlvdb_join_within_bits``): per stored row of ``labels`` (strictly ascending) what
+        ``range_bits`` returns for that row's stored code, without the row itself (``_native.JOIN_OTHERS``) or without every
+        label <= its own (``_native.JOIN_LATER``: every unordered pair once); the codes never leave the device.  A label
+        that is not a live row holding a code has no partners; ``where`` restricts the partners alone.  Returns (hits,
+        distances float64 [total], counts int64 [n]) shaped like ``range_bits``'s: ``counts`` is exact, a row with more than
+        ``capacity`` (<= 16384) partners has an empty segment.  ``words`` is the width of the codes in 64-bit words
+        (``None``: the width of the first of the leading 64 left rows that holds a code).  Two native calls: the first
+        counts, the second is made with the exact total."""
+        left =np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        if metric not in _native.BITS_METRIC_CODES:
+            raise RuntimeError(f"unknown bits metric {metric!r} (one of {sorted(_native.BITS_METRIC_CODES)})")
+        n = int(left.size)
+        if words is None:  # the width of the first left row that holds a code (a column of one width, as Index declares it)
+            widths = np.concatenate([self.bits_get(attr, int(a), 1)[0] for a in left.tolist()[:64]] + [np.zeros(1, np.int32)])
+            words = int(widths[np.argmax(widths > 0)]) or 1
+        words = int(words)
+        w, keep = self._where_arg(where)
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        counts = np.zeros(n, dtype=np.int64)
+
+        def call(total, out_labels, dist, dist64):
+            return self._check(self._lib.mlvdb_join_within_bits(
+                self._h, int(attr), _nonempty(left), n, int(mode), words, _native.BITS_METRIC_CODES[metric], float(radius),
+                int(capacity), total, w, _opt(out_labels), _opt(dist), _opt(dist64), offsets.ctypes.data, _nonempty(counts)),
+                "join_within_bits", allow=(_native.ERR_OVERFLOW,))
+
+        call(0, None, None, None)
+        total = int(offsets[n])
+        out_labels = np.empty(total, dtype=np.int64)
+        dist = np.empty(total, dtype=np.float32)
+        dist64 = np.empty(total, dtype=np.float64)
+        if total:
+            call(total, out_labels, dist, dist64)
+        return RangeHits(out_labels, dist, offsets), dist64, counts
 
     # -- hybrid search (include/mlvdb_hybrid.h) -------------------------------------------
     def search_hybrid(self, queries: np.ndarray, attr: int, sparse_queries, k: int, fetch_dense: int, fetch_sparse: int,

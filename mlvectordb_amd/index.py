@@ -2063,42 +2063,107 @@ class Index:
         native_radius = self.check_join_args("join_within", metric, radius, where, ids, max_per_row, order)
         program = self._program(namespace, where)
         ns = self._ns.get(namespace)
-        asked = None if ids is None else list(ids)
-        labels = None
-        if asked is not None and ns is not None:
-            labels = ns.ids.lookup(asked) if asked else np.zeros(0, np.int64)
-            if (labels < 0).any():
-                raise ValueError(f"join_within: id {asked[int(np.argmax(labels < 0))]} is unknown or removed in namespace "
-                                 f"{namespace!r}")
-        elif asked:
-            raise ValueError(f"join_within: id {asked[0]} is unknown or removed in namespace {namespace!r}")
+        labels = self._join_ids("join_within", namespace, ns, ids)
         if self._nothing_to_search(ns):
             return _join.PairHits.empty()
         join = self._engine_entry(ns, "join_within", "join_within needs")
         if labels is None:  # the self-join: every unordered pair once
             left = ns.engine.where_labels(program if program is not None else self._compile(namespace, {}))
-            back = np.arange(left.size)
             mode = _native.JOIN_LATER
         else:
-            back = np.argsort(labels, kind="stable")  # the engine takes ascending labels; the answer keeps the caller's order
-            left = labels[back]
+            left = np.sort(labels)  # the engine takes ascending labels; the answer keeps the caller's order
             mode = _native.JOIN_OTHERS
         hits, counts = join(left, mode, native_radius, int(max_per_row), where=program, truncate=True)
+        return self._pair_hits(ns, hits, hits.dist, counts, left, labels, order, max_per_row,
+                               lambda dist: self._scores(dist, metric))
+
+    @staticmethod
+    def _join_ids(what: str, namespace: str, ns: Optional[_Namespace], ids) -> Optional[np.ndarray]:
+        """The labels of a by-ids join in the caller's order (``None``: the self-join); an unknown or removed id is refused."""
+        asked = None if ids is None else list(ids)
+        if asked is not None and ns is not None:
+            labels = ns.ids.lookup(asked) if asked else np.zeros(0, np.int64)
+            if (labels < 0).any():
+                raise ValueError(f"{what}: id {asked[int(np.argmax(labels < 0))]} is unknown or removed in namespace "
+                                 f"{namespace!r}")
+            return labels
+        if asked:
+            raise ValueError(f"{what}: id {asked[0]} is unknown or removed in namespace {namespace!r}")
+        return None
+
+    @staticmethod
+    def _pair_hits(ns: _Namespace, hits, values, counts, left, labels, order: str, max_per_row, scores) -> "_join.PairHits":
+        """The engine's packed answer for the ascending ``left`` rows (``values`` packed like ``hits.dist``) as ``PairHits``:
+        regrouped into the caller's order ``labels`` for a by-ids join, by distance when ``order`` asks; ``scores`` makes
+        the reported scores of the pairs' values."""
+        total = int(hits.offsets[-1])
         if labels is not None:
-            inverse = np.empty_like(back)
-            inverse[back] = np.arange(back.size)
+            inverse = np.searchsorted(left, labels)
             pick = _join.gather_segments(hits.offsets, inverse)
             lens = np.diff(hits.offsets)[inverse]
-            right, dist, counts, left = hits.labels[pick], hits.dist[pick], counts[inverse], labels
+            right, dist, values, counts, left = hits.labels[pick], hits.dist[pick], values[pick], counts[inverse], labels
         else:
             lens = np.diff(hits.offsets)
-            right, dist = hits.labels[:int(hits.offsets[-1])], hits.dist[:int(hits.offsets[-1])]
+            right, dist, values = hits.labels[:total], hits.dist[:total], values[:total]
         left_of_pair = np.repeat(left, lens)
         if order == "distance":
-            by = np.lexsort((right, left_of_pair, dist))
-            left_of_pair, right, dist = left_of_pair[by], right[by], dist[by]
-        return _join.PairHits(ns.ids.uuids_at(left_of_pair), ns.ids.uuids_at(right), self._scores(dist, metric), counts,
+            by = np.lexsort((right, left_of_pair, values))
+            left_of_pair, right, dist, values = left_of_pair[by], right[by], dist[by], values[by]
+        return _join.PairHits(ns.ids.uuids_at(left_of_pair), ns.ids.uuids_at(right), scores(values), counts,
                               bool((counts <= int(max_per_row)).all()), left_of_pair, right, dist, ns.ids.uuids_at(left))
+
+    def join_within_bits(self, namespace: str, by: str, radius: float, *, metric: str = "hamming",
+                         where: Optional[Mapping] = None, ids: Optional[Sequence[UUID]] = None, max_per_row: int = 1024,
+                         order: str = "left") -> "_join.PairHits":
+        """Additive: which stored rows hold codes within ``radius`` of each other in the declared ``bits<N>`` attribute
+        ``by``, answered on the device from the codes in HBM (include/mlvdb_bits_join.h) -- deduplication by perceptual
+        hash, SimHash / MinHash signature or fingerprint.  The shape and the rules are ``join_within``'s: ``ids=None`` is
+        the self-join over the live rows ``where`` matches that hold a code, every unordered pair once with the
+        earlier-inserted row on the left; ``ids=[...]`` asks per id for every other live matching row within ``radius``, in
+        the caller's order (an id whose row holds no code has no partners).  Metrics, radius and ``where`` as in
+        ``range_search_bits``; ``scores`` is the fp64 distance.  At most ``max_per_row`` (<= 16384) partners per left row
+        come back: a row with more has its exact count in ``counts``, NO pair in the answer, and ``complete`` is false.
+        Every refusal happens before the engine is touched.  Returns a ``PairHits``."""
+        what = "join_within_bits"
+        _, program, ns = self._range_bits_args(what, [], radius, namespace, by, metric, where)
+        if not self._int_in(max_per_row, 1, self._MAX_HITS_BITS):
+            raise ValueError(f"{what}: max_per_row must be an int in [1, {self._MAX_HITS_BITS}] (got {max_per_row!r})")
+        if order not in _join.ORDERS:
+            raise ValueError(f"{what}: order must be one of {_join.ORDERS} (got {order!r})")
+        if ids is not None:
+            ids = list(ids)
+            if len(set(ids)) != len(ids):
+                raise ValueError(f"{what}: ids must not repeat")
+        labels = self._join_ids(what, namespace, ns, ids)
+        if self._nothing_to_search(ns):
+            return _join.PairHits.empty()
+        join = self._engine_entry(ns, "join_within_bits", "join_within_bits needs")
+        column = self._column(by)
+        if labels is None:  # the self-join over the matching rows that hold a code: every unordered pair once
+            ops = [(_where.EXISTS, column, 0, 0)] + ([] if program is None else [(_where.AND, 0, 0, 0)])
+            ops = np.array(ops, dtype=_where.OP_DTYPE)
+            left = ns.engine.where_labels(_where.Program(ops, np.zeros(0, np.int64)) if program is None else
+                                          _where.Program(np.concatenate([program.ops, ops]), program.set))
+            mode = _native.JOIN_LATER
+        else:
+            left = np.sort(labels)
+            mode = _native.JOIN_OTHERS
+        hits, d64, counts = join(column, left, mode, float(radius), int(max_per_row), metric, where=program,
+                                 words=_where.bits_width(self._attributes[by]) // 64)
+        return self._pair_hits(ns, hits, d64, counts, left, labels, order, max_per_row, lambda d: d)
+
+    def duplicate_groups_bits(self, namespace: str, by: str, radius: float, *, metric: str = "hamming",
+                              where: Optional[Mapping] = None, max_per_row: int = 1024) -> List[List[UUID]]:
+        """Additive: the groups of rows whose codes in ``by`` are near-duplicates -- the connected components (two rows or
+        more) of ``join_within_bits``'s self-join, each in insertion order, the groups ordered by their first member.  Raises
+        ``JoinOverflow`` when a row has more than ``max_per_row`` partners: a cut pair list does not determine the
+        components."""
+        pairs = self.join_within_bits(namespace, by, radius, metric=metric, where=where, max_per_row=max_per_row)
+        if not pairs.complete:
+            raise JoinOverflow(int(max_per_row), int(pairs.counts.max()))
+        ns = self._ns.get(namespace)
+        return [ns.ids.uuids_at(np.asarray(g, dtype=np.int64)).tolist()
+                for g in _join.connected_groups(pairs.left_labels, pairs.right_labels)]
 
     def duplicate_groups(self, namespace: str, metric: str, radius: float, *, where: Optional[Mapping] = None,
                          max_per_row: int = 1024) -> List[List[UUID]]:

@@ -427,16 +427,22 @@ class QueryProcessor:
         rows = [{"id": v.id, "values": v.values, "metadata": v.metadata} for v in self._storage.read_vectors(ids, namespace) if v]
         return {r["id"]: r for r in self._fill_values(rows, namespace)}
 
-    def _join_pairs(self, what: str, radius: float, namespace: str, metric: str, where, max_per_row: int, order: str = "left"):
+    def _join_pairs(self, what: str, radius: float, namespace: str, metric: str, where, max_per_row: int, order: str = "left",
+                    by: Optional[str] = None):
         """The self-join's pairs for ``where`` = None, a dict filter (on the device) or a predicate (the host path: the
         matching stored vectors are the left rows of a by-ids join, whose pairs are kept when the partner matches too and
-        was inserted later)."""
+        was inserted later).  ``by``: the join over the codes of that bits attribute instead of the vectors."""
+        def join(**kw):
+            if by is None:
+                return self._index.join_within(namespace, metric, radius, max_per_row=max_per_row, order=order, **kw)
+            return self._index.join_within_bits(namespace, by, radius, metric=metric, max_per_row=max_per_row, order=order, **kw)
+
         if where is None or isinstance(where, Mapping):
-            return self._index.join_within(namespace, metric, radius, where=where, max_per_row=max_per_row, order=order)
+            return join(where=where)
         if not callable(where):
             raise ValueError(f"{what}: where must be a dict filter, a predicate or None (got {type(where).__name__})")
         allowed = [v.id for v in self._storage.namespace_map.get(namespace, []) if where(v.metadata)]
-        hits = self._index.join_within(namespace, metric, radius, ids=allowed, max_per_row=max_per_row, order=order)
+        hits = join(ids=allowed)
         inside = set(allowed)
         keep = np.array([r in inside for r in hits.right_ids.tolist()], dtype=bool) & (hits.right_labels > hits.left_labels)
         for name in ("left_ids", "right_ids", "scores", "left_labels", "right_labels", "distances"):
@@ -454,18 +460,35 @@ class QueryProcessor:
         pairs = [{"left": stored[a], "right": stored[b], "score": s} for a, b, s in hits.pairs() if a in stored and b in stored]
         return {"pairs": pairs, "complete": hits.complete}
 
+    def find_near_pairs_bits(self, by: str, radius: float, namespace: str = "default", metric: str = "hamming", where=None,
+                             max_per_row: int = 1024, order: str = "left") -> dict:
+        """Additive: ``find_near_pairs`` over the codes of the bits attribute ``by`` (``Index.join_within_bits``): every
+        unordered pair of stored vectors whose codes lie within ``radius`` (``metric`` "hamming" or "jaccard"), enriched."""
+        hits = self._join_pairs("find_near_pairs_bits", radius, namespace, metric, where, max_per_row, order, by=by)
+        stored = self._stored(hits.left_ids.tolist() + hits.right_ids.tolist(), namespace)
+        pairs = [{"left": stored[a], "right": stored[b], "score": s} for a, b, s in hits.pairs() if a in stored and b in stored]
+        return {"pairs": pairs, "complete": hits.complete}
+
+    def find_duplicates_bits(self, by: str, radius: float, namespace: str = "default", metric: str = "hamming", where=None,
+                             max_per_row: int = 1024) -> List[List[dict]]:
+        """Additive: ``find_duplicates`` over the codes of the bits attribute ``by`` (``Index.duplicate_groups_bits``)."""
+        return self.find_duplicates(radius, namespace, metric, where, max_per_row, by=by)
+
     def find_duplicates(self, radius: float, namespace: str = "default", metric: str = "cosine", where=None,
-                        max_per_row: int = 1024) -> List[List[dict]]:
+                        max_per_row: int = 1024, by: Optional[str] = None) -> List[List[dict]]:
         """Additive: the groups of near-duplicates (``Index.duplicate_groups``: the connected components of the pairs within
         ``radius``), every member enriched with values and metadata; groups and members in insertion order.  Raises
-        ``engine.JoinOverflow`` when a vector has more than ``max_per_row`` partners.  ``where`` as in ``find_near_pairs``."""
-        if where is None or isinstance(where, Mapping):
+        ``engine.JoinOverflow`` when a vector has more than ``max_per_row`` partners.  ``where`` as in ``find_near_pairs``;
+        ``by``: what ``find_duplicates_bits`` passes."""
+        if (where is None or isinstance(where, Mapping)) and by is not None:
+            groups = self._index.duplicate_groups_bits(namespace, by, radius, metric=metric, where=where, max_per_row=max_per_row)
+        elif where is None or isinstance(where, Mapping):
             groups = self._index.duplicate_groups(namespace, metric, radius, where=where, max_per_row=max_per_row)
         else:
             from .engine import JoinOverflow
             from .join import connected_groups
 
-            hits = self._join_pairs("find_duplicates", radius, namespace, metric, where, max_per_row)
+            hits = self._join_pairs("find_duplicates", radius, namespace, metric, where, max_per_row, by=by)
             if not hits.complete:
                 raise JoinOverflow(int(max_per_row), int(hits.counts.max()))
             id_of = dict(zip(hits.left_labels.tolist(), hits.left_ids.tolist()))
