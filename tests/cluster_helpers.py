@@ -53,6 +53,8 @@ def row_weights(rows):
     of a float32 is exact in float64."""
     rows = np.asarray(rows, dtype=np.float32)
     n, d = rows.shape
+    if n == 0:  # (an empty index: nothing to weigh, and reshape(0, -1) is ambiguous)
+        return np.zeros(0)
     ld = (d + 15) // 16 * 16
     x = np.zeros((n, ld))
     x[:, :d] = rows

@@ -7,7 +7,8 @@ one by one and compares every answer at once.  The ``wide`` and ``wide_large`` s
 do the same over the entry families added since -- ordered, diversified, grouped, by-example and late-interaction queries,
 updates and filtered deletes, list and sparse columns -- with op tuples, a program pool and schedules of their own, so that the
 first histories keep generating the op lists they always did.  The ``recent`` scales (bits, geo, statistics, hybrid) live in
-tests/history_recent_helpers.py; ``call``, ``compare`` and ``_history`` dispatch there.  Nothing here needs a GPU."""
+tests/history_recent_helpers.py, the ``latest`` ones (scored kNN, recommend / discover, the two joins, bit-code range search,
+clustering) in tests/history_latest_helpers.py; ``call``, ``compare`` and ``_history`` dispatch there.  Nothing here needs a GPU."""
 from __future__ import annotations
 
 import functools
@@ -303,6 +304,8 @@ def call(e, op: dict, a: dict):
         return _WIDE_CALLS[kind](e, op, a)
     if kind in _recent().CALLS:
         return _recent().CALLS[kind](e, op, a)
+    if kind in _latest().CALLS:
+        return _latest().CALLS[kind](e, op, a)
     raise ValueError(f"unknown op {kind!r}")
 
 
@@ -311,6 +314,13 @@ def _recent():
     from tests import history_recent_helpers
 
     return history_recent_helpers
+
+
+def _latest():
+    """tests/history_latest_helpers.py: the ops of the fourth wave, looked up when first needed as well."""
+    from tests import history_latest_helpers
+
+    return history_latest_helpers
 
 
 def _status_of(err):
@@ -423,6 +433,8 @@ def compare(e, op, a, got, want, tag, stats):
         assert tuple(got) == tuple(want), f"{tag}: {got}, the model {want}"
     elif kind in _recent().CALLS:
         _recent().compare(e, op, a, got, want, tag, stats)
+    elif kind in _latest().CALLS:
+        _latest().compare(e, op, a, got, want, tag, stats)
     else:
         assert got is None and want is None, f"{tag}: returned {got!r}"
 
@@ -1848,6 +1860,8 @@ class _WideGenerator(_Generator):
 def _history(seed, space, d, scale):
     if scale in _recent().RECENT_SCALES:
         g = _recent()._RecentGenerator(seed, space, d, scale)
+    elif scale in _latest().LATEST_SCALES:
+        g = _latest()._LatestGenerator(seed, space, d, scale)
     else:
         g = (_WideGenerator if scale in WIDE_SCALES else _Generator)(seed, space, d, scale)
     getattr(g, scale)()

@@ -543,7 +543,7 @@ class _RecentGenerator(H._WideGenerator):
     def emit(self, op):
         for p in programs_of(op):  # the radius guard holds for the state the program is evaluated on
             assert self._radius_ok(p), f"radius guard tripped at emission: {op}"
-        args = materialise(self.model, op)
+        args = self._materialise(op)
         exp = {"args": args}
         kind = op["op"]
         if kind == "bits_set_at":  # what the host conditions read: the widths the rows held, and how many of them are dead
@@ -563,6 +563,9 @@ class _RecentGenerator(H._WideGenerator):
         self.ops.append(op)
         self.expected.append(exp)
         return exp["want"]
+
+    def _materialise(self, op):
+        return materialise(self.model, op)
 
     def finish(self):
         """The bar of every returned distance: 16 x the fp64 deviation over the history's own points and centres."""

@@ -1,5 +1,5 @@
 """Seeded call histories on ONE ``HipScanEngine`` handle from creation to close, against the NumPy model of the whole engine
-(tests/history_helpers.py, tests/history_recent_helpers.py; the coverage the committed seed sets reach is asserted without a
+(tests/history_helpers.py, tests/history_recent_helpers.py, tests/history_latest_helpers.py; the coverage the committed seed sets reach is asserted without a
 GPU in tests/test_history_host.py).
 Every answer is compared at once: labels, counts, groups, facet and bin counts exactly, distances by the suite's bars.  A
 mismatch leaves history_<tag>.json (the ops up to the failing step) in the mismatch directory of tests/conftest.py and the
@@ -9,6 +9,7 @@ import pytest
 from mlvectordb_amd.engine import HipScanEngine
 from mlvectordb_amd.multi_device import MultiDeviceEngine
 from tests import history_helpers as H
+from tests import history_latest_helpers as L
 from tests import history_recent_helpers as R
 
 pytestmark = pytest.mark.gpu
@@ -122,4 +123,43 @@ def test_recent_large_history_moves_the_dense_leg_of_hybrid_between_the_routes(k
     compaction bring it back; growth again."""
     seed, space, d, _ = key
     print(f"history {H.history_tag(*key)}: distance bar {R.geo_bar(*key):.3e}")
+    _replay(key, lambda: HipScanEngine(d, space, device=0))
+
+
+@pytest.mark.parametrize("key", L.LATEST, ids=lambda key: H.history_tag(*key))
+def test_latest_history_equals_the_model_at_every_step(key):
+    """Scored kNN, recommend / discover, the dense and the bit-code join, bit-code range search and clustering on one handle
+    with every mutation of the recent wave (tests/history_latest_helpers.py): clustering writes a column that filters, facets,
+    statistics, distinct, grouped, ordered and scored calls read at once; its workspace regrown, shrunk and reshaped between
+    l2 and cosine; joins around plain range search, across compactions and with tombstoned and renumbered labels; the bits
+    pool regrown, repacked, reset and rewritten at another width under ``range_bits`` and ``join_within_bits``."""
+    seed, space, d, _ = key
+    _replay(key, lambda: HipScanEngine(d, space, device=0))
+
+
+def test_an_index_outlives_a_destroyed_neighbour_that_used_the_latest_workspaces():
+    """Engine B is opened first; engine A replays the first latest history -- the clustering, join, by-example and score
+    workspaces among the rest -- and is closed, which frees all of it; then B replays the second one and equals the model at
+    every step."""
+    key_a, key_b = L.LATEST[0], L.LATEST[1]
+    ops_a, expected_a = H.make_history(*key_a)
+    ops_b, expected_b = H.make_history(*key_b)
+    b = HipScanEngine(key_b[2], key_b[1], device=0)
+    try:
+        a = HipScanEngine(key_a[2], key_a[1], device=0)
+        try:
+            assert H.run_history(a, ops_a, expected_a, "neighbour_" + H.history_tag(*key_a))["steps"] == len(ops_a)
+        finally:
+            a.close()
+        assert H.run_history(b, ops_b, expected_b, "survivor_" + H.history_tag(*key_b))["steps"] == len(ops_b)
+    finally:
+        b.close()
+
+
+@pytest.mark.parametrize("key", L.LATEST_LARGE, ids=lambda key: H.history_tag(*key))
+def test_latest_large_history_moves_the_join_between_the_routes_and_clusters_across_listing_blocks(key):
+    """Past 32,768 rows `auto` itself takes the filter route inside ``join_within`` at 12 and 40 left rows; clustering lists
+    rows over several 4,096-row blocks, clusters of more than one 256-member segment, 17 and 65 centroids; a
+    ``tombstone_where`` of about a third of the rows through a geo box and a compaction bring the corpus back; growth again."""
+    seed, space, d, _ = key
     _replay(key, lambda: HipScanEngine(d, space, device=0))

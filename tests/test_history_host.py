@@ -1,8 +1,8 @@
 """The seeded call histories of tests/history_helpers.py without a GPU: they are deterministic, the first ones are pinned by the
 sha256 of their op lists, the models agree with the oracle engines they are composed from, the committed seed sets meet every
 coverage condition (a to j for the first histories, k to w for the wide ones, ``RECENT_WANTED`` for the recent ones of
-tests/history_recent_helpers.py; each printed with the seed and step that meets it), the driver reports three plus five plus
-six seeded stale-state defects, and near-tie and guard redraws stay under 1 % of the drawn queries."""
+tests/history_recent_helpers.py, ``LATEST_WANTED`` for the latest ones of tests/history_latest_helpers.py; each printed with the
+seed and step that meets it), the driver reports three plus five plus six plus six seeded stale-state defects, and near-tie and guard redraws stay under 1 % of the drawn queries."""
 import hashlib
 import json
 
@@ -11,6 +11,8 @@ import pytest
 
 from mlvectordb_amd import where as W
 from tests import history_helpers as H
+from tests import history_latest_helpers as L
+from tests.cluster_helpers import ClusterOracleEngine
 from tests.distinct_helpers import DistinctOracleEngine
 from tests.facet_helpers import FacetOracleEngine
 from tests.where_helpers import EachOracleEngine, EachRangeOracleEngine
@@ -155,12 +157,44 @@ PINNED = {
     "large_cosine_d64_seed101": "1591b3011333674f2bb4309d74f5bd7248e3a9a230393ec45a91434551817f55",
     "large_ip_d64_seed102": "3c823f4c4ad7cee5cfa35d1477927ba794b1c672cb3b5062ed3296e2280d523f",
     "multi_cosine_d48_seed200": "fae4c7f1d6cda9416b7ab8a917bfa337bf41709adcba36b725a2bf25a982d2d7",
+    # every wide and recent history as generated before the latest scales existed
+    "wide_l2_d20_seed300": "d58bed72d8f47c2087aa32d4767abe7d475517beeb50a457482e7bf99950afd1",
+    "wide_l2_d20_seed301": "069bb382f7514aab84fafe57c995ed4b39e8421a0e5b85853b90fb0e3963751d",
+    "wide_cosine_d64_seed302": "91741b0f48ca2fba586daff5bf8efb0f7e1462ab56488bb27c3cb2236fa63d8f",
+    "wide_cosine_d64_seed303": "0501b2c401d21552da6f117eb21459091b598df963252563e55f0af5638f07e2",
+    "wide_ip_d128_seed304": "2626221ed199f885ddb4bcee0050ea6a165220b5b0421ba584664dd300439760",
+    "wide_ip_d128_seed305": "488377f95578a437b0bf7c3d8d5026f7e40c816b6426e6749f20bc1bb72bcfbf",
+    "wide_l2_d256_seed306": "f0df09dccad4c8ea05fdf0bf245d0a738ac26d9e0fabd9b7a42c240306edb487",
+    "wide_l2_d256_seed307": "6f81b73c05a571b037a70a5153db95f61b204aa4e4a611d4d8e93aa74765ed1c",
+    "wide_cosine_d100_seed308": "fe4ecc55558f001c6c4f300dc7d312adcca0bb35953459b0499bfb422d0175fa",
+    "wide_cosine_d100_seed309": "651d0a37b863567e94c0f75d68c451ec6c065aa770327347ac0b11be5cfb05d4",
+    "wide_ip_d48_seed310": "4efdfd76f52238ba6e37c10279b58e9b2416446a67251338cad1db220f5f2685",
+    "wide_ip_d48_seed311": "163d453eabc04eea9e2c558f320f85308399645951b85254cde964b97726ee7e",
+    "wide_large_l2_d64_seed400": "e416f78bc78777403add1ce6b282d451bf6a615e902e0e3eef47f484e464115f",
+    "wide_large_cosine_d64_seed401": "8c5d05f182f37298329d39b2ae6d57807ca7b0aa500e87ce9814978fa4a31172",
+    "wide_large_ip_d64_seed402": "4acbdc6a9b1af0e5bd6cf4e4ba1ef7f96300be7eb946bda614a57bace5569f6b",
+    "recent_l2_d20_seed500": "8713d78a1b0fbce0addd3d6fe3b68d6e086330a576bf8635caa15cc5e5c576b2",
+    "recent_l2_d20_seed501": "febeb07efc2cbf6c5dcafa8626bbebe3e928fc94f66ccbd00c0335011f30f3be",
+    "recent_cosine_d64_seed502": "ad19480144671038dfa590d2706ba1f3d967fe6b7940b8a21cd275ace4f3fc6d",
+    "recent_cosine_d64_seed503": "ac50f63d9664a235e686f27c8f9df545ae7784e7b692f3477d5b4a90fd2dc9b1",
+    "recent_ip_d128_seed504": "fcd2674d660db62026c4888b72f8e32fa66f61e7bce5c7e2a64214e33bf254e6",
+    "recent_ip_d128_seed505": "0acbc608c95574d361c62f47dc146e7866b22e9f443ebb496efe57971e257b59",
+    "recent_l2_d256_seed506": "0a3b72ebd9454a61a34fb877f1a40fc5113cea636b9c0bbd0945442172d63aed",
+    "recent_l2_d256_seed507": "b893b0860bbeb23c936b33ee2d1abeb2f918e7f30abc6afd3ebe90d2f563b3bf",
+    "recent_cosine_d100_seed508": "d95f1480801ed5be5d042b2a996263ababc06139dfa086a0d3e3cbc7e1363bca",
+    "recent_cosine_d100_seed509": "dd331a01d140be19e8037ab2fda59fa0f56872bac69013ade3d728cdfd20d42a",
+    "recent_ip_d48_seed510": "70b1658dd4755ac56d2a48383e4fd5ea352d12d2c00f9ac2a35f46bcfdffddb4",
+    "recent_ip_d48_seed511": "366119f426d5cc8b756a42733b2f90243d01173224d078b654edf452c1606d2d",
+    "recent_large_l2_d64_seed600": "1364cfad2753179fc3ea7b75e9062d814316dc4c864a26d43d29e493021de1bb",
+    "recent_large_cosine_d64_seed601": "251b321d9e46f2f60438514c0a309756367b9d44f06094ba95ec6f81688866bc",
+    "recent_large_ip_d64_seed602": "d1970ff93371b09a1e8dd962c9f4e95d5288b17bbfa1e00f5e65a51ec48abdec",
 }
 
 
 def test_the_first_histories_generate_byte_identical_op_lists():
-    assert {H.history_tag(*key) for key in H.HISTORIES} == set(PINNED)
-    for key in H.HISTORIES:
+    keys = H.HISTORIES + H.WIDE + H.WIDE_LARGE + R.RECENT + R.RECENT_LARGE
+    assert {H.history_tag(*key) for key in keys} == set(PINNED)
+    for key in keys:
         ops, _ = H.make_history(*key)
         assert hashlib.sha256(json.dumps(ops).encode()).hexdigest() == PINNED[H.history_tag(*key)], H.history_tag(*key)
 
@@ -1516,11 +1550,16 @@ class SparseLegIgnoresTheProgram(R.RecentHistoryModel):
 @pytest.mark.parametrize("defect", [KeepsCodesInOldRowOrder, CodesSurviveReset, SearchBitsTakesOtherWidths,
                                     StatsCountsFilteredDeletes, NearestReadsTheOldGeoColumn, SparseLegIgnoresTheProgram])
 def test_the_driver_reports_a_seeded_defect_in_the_recent_histories(defect, tmp_path, monkeypatch):
+    _the_driver_reports(defect, R.RECENT[:4], R.RECENT_MUTATIONS, tmp_path, monkeypatch)
+
+
+def _the_driver_reports(defect, keys, mutations, tmp_path, monkeypatch):
+    """The defective model replays the first four histories of a wave as the engine; the driver reports it in two at least."""
     from tests import conftest
 
     monkeypatch.setattr(conftest, "OUT_DIR", tmp_path)
     reported, real_call = 0, H.call
-    for key in R.RECENT[:4]:
+    for key in keys:
         ops, expected = H.make_history(*key)
         engine = defect(key[2], key[1])
         stepped = []
@@ -1542,7 +1581,7 @@ def test_the_driver_reports_a_seeded_defect_in_the_recent_histories(defect, tmp_
             if defect.at_once:  # `fired` is the first call whose answer the defect changes: that call is the one reported
                 assert failed == engine.fired, (failed, engine.fired)
             else:               # the state breaks in a mutation; the first later call that reads it differently reports it
-                assert failed > engine.fired and ops[engine.fired]["op"] in R.RECENT_MUTATIONS, (failed, engine.fired)
+                assert failed > engine.fired and ops[engine.fired]["op"] in mutations, (failed, engine.fired)
             dumped = json.loads((tmp_path / f"history_{tag}.json").read_text())
             assert dumped["failed_step"] == failed and dumped["ops"] == ops[:failed + 1]
             print(f"{defect.__name__}: {tag} fired at step {engine.fired}, reported at step {failed} ({ops[failed]['op']})")
@@ -1557,10 +1596,556 @@ def test_the_driver_reports_a_seeded_defect_in_the_recent_histories(defect, tmp_
 def test_near_tie_redraws_stay_under_one_percent():
     """Near-ties of the kNN kinds, and in the recent histories the draws that tripped a guard of tests/geo_helpers.py."""
     drawn = redrawn = 0
-    for key in H.HISTORIES + H.WIDE + H.WIDE_LARGE + R.RECENT + R.RECENT_LARGE:
+    for key in H.HISTORIES + H.WIDE + H.WIDE_LARGE + R.RECENT + R.RECENT_LARGE + L.LATEST + L.LATEST_LARGE:
         a, b = H.redraw_counts(*key)
-        if key[3] in R.RECENT_SCALES:
+        if key[3] in R.RECENT_SCALES + L.LATEST_SCALES:
             print(f"history {H.history_tag(*key)}: {b} of {a} drawn queries were redrawn")
         drawn, redrawn = drawn + a, redrawn + b
     print(f"{redrawn} of {drawn} drawn queries were redrawn")
     assert drawn > 300 and redrawn <= 0.01 * drawn
+
+
+# ================================================================ the fourth wave: tests/history_latest_helpers.py
+def test_the_latest_op_lists_are_deterministic_and_json_serialisable():
+    key = L.LATEST[1]
+    ops, expected = H.make_history(*key)
+    again = H._history.__wrapped__(*key)
+    ops2, expected2 = again.ops, again.expected
+    assert ops2 is not ops and json.dumps(ops) == json.dumps(ops2) and json.loads(json.dumps(ops)) == ops
+    for a, b in zip(expected, expected2):
+        assert a["args"].keys() == b["args"].keys()
+        for name, x in a["args"].items():
+            if isinstance(x, np.ndarray):
+                assert x.tobytes() == b["args"][name].tobytes(), name
+    other, _ = H.make_history(key[0] + 1, *key[1:])
+    assert json.dumps(other) != json.dumps(ops)
+
+
+def _hits_equal(a, b):
+    return all(np.array_equal(getattr(a, f), getattr(b, f)) for f in ("labels", "dist", "offsets"))
+
+
+def test_the_latest_model_agrees_with_the_oracle_engines_it_is_composed_from():
+    """The same state -- two appends, every column valued, tombstones -- in ``LatestHistoryModel`` and in the scored, examples,
+    join, cluster and bits-range oracle engines, and the bits join against the rule of tests/test_gpu_bits_join.py; one call per
+    new entry with a program; then what the model adds: conds with list leaves, and the refusals with the headers' statuses,
+    none of which changes the state."""
+    from tests.bits_range_helpers import BitsRangeOracleEngine, range_bits
+    from tests.examples_helpers import ExamplesOracleEngine, random_bags
+    from tests.join_helpers import JoinOracleEngine
+    from tests.scored_helpers import ScoredOracleEngine
+    from tests.test_gpu_bits_join import partners
+
+    rng = np.random.default_rng(21)
+    d, n = 12, 400
+    rows = rng.standard_normal((n, d), dtype=np.float32)
+    qs = rng.standard_normal((5, d), dtype=np.float32)
+    codes = R.bits_column(np.random.default_rng(13), n, R.WORDS, 0.1)
+    lists = H.csr(H.wide_lists(np.random.default_rng(4), n))
+    half = H.program_of({"ops": HALF, "set": []})
+    for space in ("l2", "cosine", "ip"):
+        engines = [cls(d, space) for cls in (L.LatestHistoryModel, ScoredOracleEngine, ExamplesOracleEngine, JoinOracleEngine,
+                                             ClusterOracleEngine, BitsRangeOracleEngine)]
+        model, scored, examples, join, cluster, bits = engines
+        for e in engines:
+            for attr, kind in ((0, "int64"), (1, "float64"), (2, "int64"), (L.CLUSTER_A, "int64")):
+                e.define_attr(attr, kind)
+            if e is model:
+                e.define_attr(H.LIST_A, "int64_list")
+            if e in (model, bits):
+                e.define_attr(R.BITS_A, "bits")
+            e.append(rows[:250])
+            e.append(rows[250:])
+            for attr in range(3):
+                e.set_attr(attr, 0, H.column_values(attr, n, np.random.default_rng(attr), n))
+            if e is model:
+                e.set_attr_list(H.LIST_A, 0, lists)
+            if e in (model, bits):
+                e.bits_set(R.BITS_A, 0, codes)
+            e.tombstone(np.arange(0, n, 7))
+        same = lambda a, b: len(a) == len(b) and all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))  # noqa: E731
+        # scored: a program with a cond, an operand with a default, hostile floats
+        for which in ("dist_attr", "dist_float", "min_abs"):
+            g = L._LatestGenerator(700, "l2", 20, "latest")
+            prog = L.score_of(g.score(which))
+            assert same(model.search_scored(qs, 9, prog, half, want64=True), scored.search_scored(qs, 9, prog, half, want64=True))
+        cond = L.score_of({"ops": [[L.S.DIST, 0, 0], [L.S.MATCH, 0, 0], [L.S.SUB, 0, 0]], "conds": [{"ops": HALF, "set": []}]})
+        assert same(model.search_scored(qs, 9, cond, None, want64=True), scored.search_scored(qs, 9, cond, None, want64=True))
+        listy = L.score_of({"ops": [[L.S.DIST, 0, 0], [L.S.MATCH, 0, 0], [L.S.SUB, 0, 0]], "conds": [{"ops": [[W.HAS, H.LIST_A, 3, 0]], "set": []}]})
+        got = model.search_scored(qs, 9, listy, None, want64=True)  # (what the model adds: the scalar evaluator knows no list leaf)
+        assert (got[2] == 9).all() and not same(got, model.search_scored(qs, 9, cond, None, want64=True))
+        # examples, every mode, stored (tombstoned among them) and raw, exclude on and off
+        for mode in L.MODES:
+            bags = random_bags(np.random.default_rng(mode), mode, [1, 3, 9, 17], n, d)
+            for exclude in (True, False):
+                assert same(model.search_examples(mode, *bags, 10, exclude=exclude, where=half),
+                            examples.search_examples(mode, *bags, 10, exclude=exclude, where=half))
+        # the dense join
+        left = np.sort(rng.choice(n, 12, replace=False))
+        radius = float(np.sort(H.exact_scan.exact_distances(rows[left[:1]], rows, space)[0])[6])
+        for mode in L.JOIN_MODES:
+            for cap, truncate in ((64, False), (2, True)):
+                g, w = model.join_within(left, mode, radius, cap, half, truncate), join.join_within(left, mode, radius, cap, half, truncate)
+                assert _hits_equal(g[0], w[0]) and np.array_equal(g[1], w[1]) and g[1].sum() > 0
+        # clustering: as a query, and writing the column
+        cl, cv = rng.choice(n, 5).astype(np.int64), rng.standard_normal((5, d)).astype(np.float32)
+        cl[2] = -1
+        assert same(model.assign_nearest(cl, cv, where=half, assign_attr=L.CLUSTER_A), cluster.assign_nearest(cl, cv, where=half, assign_attr=L.CLUSTER_A))
+        assert np.array_equal(model.get_attr(L.CLUSTER_A, 0, n), cluster.get_attr(L.CLUSTER_A, 0, n))
+        if space != "ip":
+            assert same(model.kmeans(cl, cv, max_iterations=3, assign_attr=L.CLUSTER_A), cluster.kmeans(cl, cv, max_iterations=3, assign_attr=L.CLUSTER_A))
+            assert np.array_equal(model.get_attr(L.CLUSTER_A, 0, n), cluster.get_attr(L.CLUSTER_A, 0, n))
+        # bit codes: the range search, and the join against range_bits + partners
+        bq = R.bits_codes(np.random.default_rng(15), 4, R.WORDS)
+        coded = H.program_of({"ops": HALF, "set": []})
+        for metric, radius in (("hamming", 150.0), ("jaccard", 0.62)):
+            for cap in (L.MAX_HITS, 3):
+                g, w = model.range_bits(R.BITS_A, bq, radius, metric, cap, coded), bits.range_bits(R.BITS_A, bq, radius, metric, cap, coded)
+                assert _hits_equal(g[0], w[0]) and np.array_equal(g[1], w[1]) and np.array_equal(g[2], w[2])
+                assert np.array_equal(model.range_bits(R.BITS_A, bq, radius, metric, cap, coded, count_only=True), w[2])
+                bl = np.arange(0, 60, dtype=np.int64)
+                cand = np.flatnonzero(bits.candidates(R.BITS_A, None, R.WORDS))
+                stored = np.array([bits.bits_rows(R.BITS_A)[i] for i in cand.tolist()], dtype=np.uint64).reshape(cand.size, R.WORDS)
+                lab, d64, off, _ = range_bits(bits, R.BITS_A, stored, 64.0 * R.WORDS if metric == "hamming" else 1.0, metric, L.MAX_HITS, coded)
+                ref = {a: (lab[off[i]:off[i + 1]], d64[off[i]:off[i + 1]]) for i, a in enumerate(cand.tolist())}
+                for mode in L.JOIN_MODES:
+                    wl, wd, wo, wc = partners(ref, bl, mode, radius, cap)
+                    hits, g64, gc = model.join_within_bits(R.BITS_A, bl, mode, radius, cap, metric, coded, R.WORDS)
+                    assert np.array_equal(hits.labels, wl) and np.array_equal(g64, wd) and np.array_equal(hits.offsets, wo) and np.array_equal(gc, wc)
+                    assert gc.sum() > 0
+        # the refusals, with the status codes the headers name, none of which changes the state
+        before = (model.get_attr(L.CLUSTER_A, 0, n).copy(), model.pools(), model.counts())
+        for which, status in L.LATEST_REFUSALS.items():
+            if which == "kmeans_ip" and space != "ip":
+                continue
+            op = {"op": "refuse_latest", "which": which, "seed": 1, "total": n}
+            assert L.CALLS["refuse_latest"](model, op, L.materialise(model, op)) == ("refused", status), which
+        assert np.array_equal(model.get_attr(L.CLUSTER_A, 0, n), before[0]) and (model.pools(), model.counts()) == before[1:]
+
+
+CLUSTER_READERS = ("filter", "facet_values", "attr_stats", "search_distinct", "search_grouped", "where_ordered", "search_scored", "cluster")
+CLUSTER_KINDS = ("assign_nearest", "kmeans") + L.WRITERS
+EMPTY_HOWS = ("reset", "reset_other", "compact")
+ACROSS = ("tombstone", "tombstone_where", "append", "compact", "regrowth")
+
+
+def reads_cluster_column(op):
+    """Which reader of the cluster column an op is, or None."""
+    kind = op["op"]
+    if kind in CLUSTER_KINDS:
+        return "cluster" if leaf_on(op, L.CLUSTER_A, (W.EQ, W.EXISTS)) else None
+    if kind == "where_count" and leaf_on(op, L.CLUSTER_A, (W.EQ,)):
+        return "filter"
+    if kind == "attr_stats":
+        return kind if op["by"] == L.CLUSTER_A else None
+    if kind == "search_scored":
+        return kind if any(o[0] == L.S.ATTR and o[1] == L.CLUSTER_A for o in op["score"]["ops"]) else None
+    return kind if kind in CLUSTER_READERS and op.get("attr") == L.CLUSTER_A else None
+
+
+def latest_answers_nothing(op, want):
+    kind = op["op"]
+    if kind in ("search_scored", "search_examples"):
+        return not np.asarray(want[2 if kind == "search_scored" else 3]).any() and (want[0] == -1).all()
+    if kind in ("join_within",):
+        return want[0].labels.size == 0 and not want[1].any()
+    if kind in ("range_bits", "join_within_bits"):
+        return not np.asarray(want if op.get("count_only") else want[2]).any()
+    if kind == "assign_nearest":
+        return not want[0].any() and want[2] == 0
+    return not want[1].any() and want[5] == 0  # kmeans
+
+
+def latest_conditions(ops, expected, space):
+    """{condition: step} for every condition of LATEST_WANTED this latest history meets."""
+    st = recent_trace(ops, expected, space)
+    kinds = [op["op"] for op in ops]
+    n = len(ops)
+    met = {}
+    grown = shrunk = False           # since the last clustering call: a row regrowth / a compaction that dropped rows
+    shape = None                     # the shape cl_ws was last used in: 20 B per row (l2-shaped) or 28 B (cosine k-means)
+    dead_since_compact = renumbered = False
+    emptied, empty_seen = None, set()
+    bits = dict(garbage=False, grown=0, width=None, reset=False, late_defined=False, late_written=False)
+
+    def put(name, step):
+        met.setdefault(name, step)
+
+    for i, op in enumerate(ops):
+        k, s, exp = kinds[i], st[i], expected[i]
+        nxt = kinds[i + 1] if i + 1 < n else None
+        after = ops[i + 1] if i + 1 < n else {}
+        prev = kinds[i - 1] if i else None
+        a = exp["args"]
+        if k in L.LATEST_MUTATIONS and nxt in L.LATEST_QUERIES and (k in L.WRITERS or nxt in L.LATEST_NEW_QUERIES):
+            put(f"k_{k}>{nxt}", i)
+        # clustering as a writer directly before each reader of its column
+        if k in L.WRITERS and op["assign_attr"] == L.CLUSTER_A and nxt is not None and reads_cluster_column(after):
+            put(f"w_{reads_cluster_column(after)}", i)
+        if k in CLUSTER_KINDS and op["assign_attr"] >= 0 and s["total"]:
+            live, col = a["live"], a["column_after"]
+            if s["deleted"] and op["program"] is not None and not live.all():
+                put("c_untouched", i)
+            # (no candidate can stay unassigned here: the engine takes finite rows and centroids only, and the fp64 distance of
+            # two finite float32 vectors is finite in every space (DESIGN.md 4, the magnitude contract), so a centroid always wins)
+            assert not (col[live] == W.INT64_ABSENT).any(), (i, op)
+            if op["assign_attr"] == L.LATE_CLUSTER:
+                put("c_late_column", i)
+        if k in CLUSTER_KINDS:
+            now = 28 if k.startswith("kmeans") and s["space"] == "cosine" else 20
+            if shape is not None and shape != now and prev in ("append", "reset"):
+                put("ws_cosine_after_l2" if now == 28 else "ws_l2_after_cosine", i)
+            shape = now
+            if grown:
+                put("c_after_regrowth", i)
+            if shrunk:
+                put("c_after_shrink", i)
+            grown = shrunk = False
+            if k.startswith("kmeans") and op.get("far") and exp["want"][1][-1] == 0:
+                c0 = L.centroid_vectors(a["rows"], a["labels"], a["vectors"])
+                assert np.array_equal(exp["want"][0][-1], c0[-1])
+                put("c_empty_cluster_keeps_centroid", i)
+        if k == "append" and H.capacity_after(s["cap"], s["total"] + op["n"]) != s["cap"] and s["cap"]:
+            grown = True
+        if k == "compact" and s["deleted"]:
+            shrunk, renumbered, dead_since_compact = True, True, False
+        if k in ("tombstone", "tombstone_where"):
+            dead_since_compact = True
+        if k == "reset":
+            renumbered = False
+        # the dense join around plain range search
+        if k == "join_within":
+            if nxt == "range":
+                put("j_before_range", i)
+            if prev == "range":
+                put("j_after_range", i)
+            if prev == "range_each":
+                put("j_after_range_each", i)
+            cut = (exp["want"][1] > op["capacity"]).any() and op["truncate"]
+            if cut and nxt == "join_within" and not (expected[i + 1]["want"][1] > after["capacity"]).any() and after["n_left"] == op["n_left"]:
+                put("j_cut_then_complete", i)
+            if a["labels"].size and a["dead_mask"][a["labels"]].any():
+                put("j_dead_left", i)
+            if renumbered:
+                put("j_renumbered", i)
+        if k == "search_examples":
+            stored = a["labels"][a["labels"] >= 0]
+            if stored.size and a["dead_mask"][stored].any():
+                put("x_dead_example", i)
+            if renumbered and stored.size:
+                put("x_renumbered", i)
+            if stored.size != np.unique(stored).size:
+                put("x_repeated_label", i)
+            if (a["labels"] < 0).any() and stored.size:
+                put("x_raw_and_stored", i)
+            put(f"x_mode{op['mode']}_exclude{int(op['exclude'])}", i)
+            if max(op["sizes"]) > 16:
+                put("x_bag_over_a_tile", i)
+        for entry, short in (("join_within", "j"), ("search_examples", "x")):
+            for x in ("tombstone", "tombstone_where", "append", "compact"):
+                if k == x and nxt == entry:
+                    put(f"{short}_after_{x}", i)
+                if k == entry and nxt == x:
+                    put(f"{short}_before_{x}", i)
+            if k == entry and grown:
+                put(f"{short}_after_regrowth", i)
+        if k in ("join_within", "join_within_bits"):
+            put(f"{k}_mode{op['mode']}", i)
+            if (exp["want"][-1] > op["capacity"]).any():
+                put(f"{k}_over_capacity", i)
+        if k == "join_within":
+            put(f"j_truncate{int(op['truncate'])}", i)
+        if k == "range_bits":
+            put(f"b_{op['metric']}", i)
+            if op["count_only"]:
+                put("b_count_only", i)
+        # the bits pool under the two new readers
+        if k == "compact" and R.BITS_A in s["pools"]:
+            used, _, live = s["pools"][R.BITS_A]
+            bits["garbage"] = used > live > 0
+        if k == "bits_set_at" and op["attr"] == R.BITS_A:
+            cap_before, cap_after = s["pools"][R.BITS_A][1], exp["pools"][R.BITS_A][1]
+            bits["grown"] = bits["grown"] + 1 if cap_after != cap_before and s["pools"][R.BITS_A][0] > 0 else bits["grown"]
+            if "labels" in op and set(exp["widths_before"]) == {R.WORDS} and op["words"] == R.WORDS_FEW:
+                bits["width"] = "absent" if op["p_absent"] == 1.0 else "other"
+        if k == "reset":
+            bits.update(reset=True, grown=0, garbage=False, width=None)
+        if k in ("bits_set", "bits_set_at") and op["attr"] == R.BITS_A:
+            bits["reset"] = False
+        if k == "define_attr" and op["attr"] == R.LATE_BITS:
+            bits["late_defined"] = True
+        if k in ("bits_set", "bits_set_at") and op["attr"] == R.LATE_BITS:
+            bits["late_written"] = True
+        if k in ("range_bits", "join_within_bits"):
+            if op["attr"] == R.LATE_BITS:
+                put(f"{k}_late_{'written' if bits['late_written'] else 'absent'}", i)
+            else:
+                if bits["garbage"]:
+                    put(f"{k}_after_garbage", i)
+                if bits["grown"] >= 2:
+                    put(f"{k}_after_doubling", i)
+                if bits["width"]:
+                    put(f"{k}_width_{bits['width']}", i)
+                if bits["reset"] and s["total"]:
+                    put(f"{k}_after_reset_before_any_code", i)
+            if k == "join_within_bits" and prev not in ("compact",):
+                bits["garbage"] = False
+        if k == "compact":
+            bits["grown"] = 0
+        # emptied: every new entry answers padding or zeros
+        if k in ("reset", "compact") and exp.get("counts", (1,))[0] == 0:
+            emptied = ("reset_other" if op.get("space") else "reset") if k == "reset" else "compact"
+            empty_seen = set()
+        elif k in L.LATEST_NEW_QUERIES and emptied and s["total"] == 0:
+            assert latest_answers_nothing(op, exp["want"]), (i, op)
+            empty_seen.add(k)
+            if empty_seen >= set(L.LATEST_NEW_QUERIES) - ({"kmeans"} if s["space"] == "ip" else set()):
+                put(f"e_{emptied}", i)
+        elif s["total"]:
+            emptied = None
+        # a program, then the same call without one / a plain search: the mask is handed back
+        if k in L.NEW_TAKING and op.get("program") is not None:
+            if nxt == k and after.get("program") is None:
+                put(f"q_{k}_own", i)
+            if nxt == "search64":
+                put(f"q_{k}_plain", i)
+        # score_prog keeps the conds' set table: a program with a table, then one without conds
+        if k == "search_scored" and any(c["set"] for c in op["score"]["conds"]) and nxt == k and not after["score"]["conds"]:
+            put("s_table_then_none", i)
+        if k == "refuse_latest" and nxt in L.LATEST_QUERIES:
+            assert exp["want"] == ("refused", L.LATEST_REFUSALS[op["which"]]), (i, op, exp["want"])
+            put("v_" + op["which"], i)
+    return met
+
+
+LATEST_WANTED = ([f"k_{m}>{q}" for m, q in L.LATEST_PAIRS] + ["w_" + r for r in CLUSTER_READERS]
+                 + ["c_untouched", "c_late_column", "ws_cosine_after_l2", "ws_l2_after_cosine", "c_after_regrowth",
+                    "c_after_shrink", "c_empty_cluster_keeps_centroid", "j_before_range", "j_after_range", "j_after_range_each",
+                    "j_cut_then_complete", "j_dead_left", "j_renumbered", "x_dead_example", "x_renumbered", "x_repeated_label",
+                    "x_raw_and_stored", "x_bag_over_a_tile", "j_after_regrowth", "x_after_regrowth", "j_truncate0", "j_truncate1",
+                    "b_hamming", "b_jaccard", "b_count_only", "s_table_then_none"]
+                 + [f"x_mode{m}_exclude{e}" for m in L.MODES for e in (0, 1)]
+                 + [f"{s}_{w}_{x}" for s in "jx" for w in ("before", "after") for x in ("tombstone", "tombstone_where", "append", "compact")]
+                 + [f"{k}_mode{m}" for k in ("join_within", "join_within_bits") for m in L.JOIN_MODES]
+                 + [f"{k}_over_capacity" for k in ("join_within", "join_within_bits")]
+                 + [f"{k}_{x}" for k in ("range_bits", "join_within_bits")
+                    for x in ("after_garbage", "after_doubling", "width_other", "width_absent", "after_reset_before_any_code", "late_absent",
+                              "late_written")]
+                 + ["e_" + h for h in EMPTY_HOWS] + [f"q_{k}_{x}" for k in L.NEW_TAKING for x in ("own", "plain")]
+                 + ["v_" + w for w in L.LATEST_REFUSALS])
+
+
+def test_the_latest_histories_meet_every_coverage_condition():
+    where, drawn = {}, {}
+    for key in L.LATEST:
+        ops, expected = H.make_history(*key)
+        for name, step in latest_conditions(ops, expected, key[1]).items():
+            where.setdefault(name, (key[0], step))
+        assert max(e["counts"][0] for e in expected if "counts" in e) <= H.MAX_ROWS_WIDE, key
+        for step, op in enumerate(ops):
+            if op["op"] in L.NEW_TAKING and op.get("program_kind"):
+                drawn.setdefault((op["op"], op["program_kind"]), (key[0], step))
+        print(f"history {H.history_tag(*key)}: {len(ops)} steps")
+    for name in LATEST_WANTED:
+        if name in where:
+            print(f"condition {name}: seed {where[name][0]}, step {where[name][1]}")
+    missing = [name for name in LATEST_WANTED if name not in where]
+    assert not missing, f"coverage conditions never met: {missing}"
+    assert len(L.LATEST_PAIRS) == 20 * 41 - 18 * 34 and len(L.LATEST) == 12 and len(set(LATEST_WANTED)) == len(LATEST_WANTED)
+    # every new entry takes a program, and every program kind of the pool -- the wide, the recent and the two new ones -- is
+    # drawn for every one of them
+    kinds = L._LatestGenerator.PROGRAMS
+    assert len(kinds) == 23 and set(L.NEW_TAKING) <= set(L.PROGRAM_TAKING)
+    never = [(entry, kind) for entry in L.NEW_TAKING for kind in kinds if (entry, kind) not in drawn]
+    assert not never, f"program kinds never drawn: {never}"
+    # the large ones: `auto` alone moves the join between the routes; the shapes of the listing the small scale cannot reach
+    for key in L.LATEST_LARGE:
+        ops, expected = H.make_history(*key)
+        st = recent_trace(ops, expected, key[1])
+        assert all(s["strategy"] == "auto" for s in st)
+        joins = [(op["n_left"], s["total"] >= H.FILTER_MIN_ROWS) for op, s in zip(ops, st) if op["op"] == "join_within"]
+        routes = [above for n_left, above in joins if n_left >= 12]
+        assert routes[0] is False and True in routes and False in routes[routes.index(True):] and routes[-1] is True, (key, routes)
+        assert {(12, True), (40, True), (12, False), (40, False)} <= set(joins)
+        assert (L.N.JOIN_WAVE + 1, True) in joins  # more left rows than one wave of the join's range chain takes
+        cl = [(op, exp, s) for op, exp, s in zip(ops, expected, st) if op["op"] in CLUSTER_KINDS]
+        sizes = [exp["want"][0 if op["op"].startswith("assign") else 1] for op, exp, s in cl]
+        assert max(s["total"] for _, _, s in cl) > 2 * 4096 and max(int(x.max()) for x in sizes) > 256   # blocks, segments
+        assert {17, 65} <= {op["m"] for op, _, _ in cl}                                                    # centroid tiles
+        new = {(op["op"], s["total"] >= H.FILTER_MIN_ROWS) for op, s in zip(ops, st) if op["op"] in L.LATEST_NEW_QUERIES + L.WRITERS}
+        assert {(q, True) for q in L.LATEST_NEW_QUERIES if q != "kmeans"} <= new, new
+        assert max(e["counts"][0] for e in expected if "counts" in e) > H.FILTER_MIN_ROWS
+        i = [op["op"] for op in ops].index("tombstone_where")
+        died = expected[i]["counts"][1] / expected[i]["counts"][0]
+        assert 0.25 < died < 0.42 and "compact" in [op["op"] for op in ops[i:]], died
+        print(f"history {H.history_tag(*key)}: {len(ops)} steps, {died:.0%} of the rows die at step {i}")
+
+
+# ---------------------------------------------------------------- sensitivity of the latest histories: six seeded defects
+def _flat(answer):
+    out = {}
+    H._evidence(answer, "x", out)
+    return {name: x.tobytes() for name, x in out.items()}
+
+
+class _Defective(L.LatestHistoryModel):
+    fired = None
+    at_once = True
+
+    def _fires_if(self, right, wrong):
+        if self.fired is None and _flat(right) != _flat(wrong):
+            self.fired = self.step
+        return wrong
+
+
+class ClusterWritesTombstonedRows(_Defective):
+    """Clustering writes its column for the tombstoned rows too (cluster 0)."""
+    seen_by = staticmethod(lambda op: op["op"] in CLUSTER_KINDS and op["assign_attr"] >= 0)
+
+    def _write(self, attr, assign):
+        super()._write(attr, assign)
+        if attr >= 0 and self._deleted.any():
+            if self.fired is None and (self._cols[attr][self._deleted] != 0).any():
+                self.fired = self.step
+            self._cols[attr][self._deleted] = 0
+
+
+class CountsReadTheColumnBeforeClustering(_Defective):
+    """``where_count`` / ``where_labels`` read the cluster column as it was before the last clustering call wrote it."""
+    seen_by = staticmethod(lambda op: op["op"] in ("where_count", "where_labels"))
+    _before = None
+
+    def _write(self, attr, assign):
+        if attr >= 0:
+            self._before = (attr, self._cols[attr].copy())
+        super()._write(attr, assign)
+
+    def compact(self):
+        self._before = None
+        return super().compact()
+
+    def reset(self, space=None):
+        self._before = None
+        super().reset(space)
+
+    def _stale(self, entry, program):
+        right = entry(program)
+        if self._before is None or self._before[1].size != self._rows.shape[0]:
+            return right
+        attr, old = self._before
+        keep = self._cols[attr]
+        self._cols[attr] = old
+        try:
+            wrong = entry(program)
+        finally:
+            self._cols[attr] = keep
+        return self._fires_if((right,), (wrong,))[0]
+
+    def where_count(self, program):
+        return self._stale(super().where_count, program)
+
+    def where_labels(self, program):
+        return self._stale(super().where_labels, program)
+
+
+class JoinReadsRowsInOldOrder(_Defective):
+    """``join_within`` reads the vectors in pre-compaction row order while the labels and columns have moved."""
+    seen_by = staticmethod(lambda op: op["op"] == "join_within")
+    _old = None
+
+    def compact(self):
+        rows = self._rows.copy()
+        old = super().compact()
+        self._old = rows[:old.size]
+        return old
+
+    def reset(self, space=None):
+        self._old = None
+        super().reset(space)
+
+    def join_within(self, *a, **kw):
+        right = super().join_within(*a, **kw)
+        if self._old is None:
+            return right
+        keep = self._rows
+        self._rows = np.concatenate([self._old, keep[self._old.shape[0]:]])
+        try:
+            wrong = super().join_within(*a, **kw)
+        finally:
+            self._rows = keep
+        return self._fires_if(right, wrong)
+
+
+class ExamplesKeepARenumberedExample(_Defective):
+    """``search_examples`` excludes by the labels from before the last compaction: a call with a renumbered example excludes none."""
+    seen_by = staticmethod(lambda op: op["op"] == "search_examples")
+    _moved = None
+
+    def compact(self):
+        old = super().compact()
+        self._moved = old != np.arange(old.size)
+        return old
+
+    def reset(self, space=None):
+        self._moved = None
+        super().reset(space)
+
+    def search_examples(self, mode, labels, vectors, roles, offsets, k, *, exclude=True, where=None):
+        right = super().search_examples(mode, labels, vectors, roles, offsets, k, exclude=exclude, where=where)
+        stored = np.asarray(labels, np.int64)
+        if not exclude or self._moved is None or not self._moved[stored[(stored >= 0) & (stored < self._moved.size)]].any():
+            return right
+        return self._fires_if(right, super().search_examples(mode, labels, vectors, roles, offsets, k, exclude=False, where=where))
+
+
+class RangeBitsTakesOtherWidths(_Defective):
+    """``range_bits`` takes the rows of another width as candidates (their first words, zero-extended)."""
+    seen_by = staticmethod(lambda op: op["op"] == "range_bits")
+
+    def range_bits(self, attr, queries, *a, **kw):
+        right = super().range_bits(attr, queries, *a, **kw)
+        words, rows = np.asarray(queries).shape[1], self._lists[attr]
+        keep = {i: r for i, r in enumerate(rows) if r is not None and len(r) != words}
+        for i, r in keep.items():
+            rows[i] = (tuple(r) + (0,) * words)[:words]
+        try:
+            wrong = super().range_bits(attr, queries, *a, **kw)
+        finally:
+            for i, r in keep.items():
+                rows[i] = r
+        if isinstance(wrong, tuple):
+            return self._fires_if(right, wrong)
+        return self._fires_if((right,), (wrong,))[0]  # (count_only: one array)
+
+
+class BitsJoinReadsCodesThatSurviveReset(_Defective):
+    """``join_within_bits`` still finds the codes ``reset`` should have emptied, in the rows that hold none yet."""
+    seen_by = staticmethod(lambda op: op["op"] == "join_within_bits")
+    _left = None
+
+    def reset(self, space=None):
+        self._left = {a: list(self._lists[a]) for a in self._bits}
+        super().reset(space)
+
+    def compact(self):
+        self._left = None
+        return super().compact()
+
+    def join_within_bits(self, attr, *a, **kw):
+        right = super().join_within_bits(attr, *a, **kw)
+        left, rows = (self._left or {}).get(attr) or [], self._lists[attr]
+        ghosts = [i for i in range(min(len(rows), len(left))) if rows[i] is None and left[i] is not None]
+        for i in ghosts:
+            rows[i] = left[i]
+        try:
+            wrong = super().join_within_bits(attr, *a, **kw)
+        finally:
+            for i in ghosts:
+                rows[i] = None
+        return self._fires_if(right, wrong)
+
+
+@pytest.mark.parametrize("defect", [ClusterWritesTombstonedRows, CountsReadTheColumnBeforeClustering, JoinReadsRowsInOldOrder,
+                                    ExamplesKeepARenumberedExample, RangeBitsTakesOtherWidths, BitsJoinReadsCodesThatSurviveReset])
+def test_the_driver_reports_a_seeded_defect_in_the_latest_histories(defect, tmp_path, monkeypatch):
+    _the_driver_reports(defect, L.LATEST[:4], L.LATEST_MUTATIONS, tmp_path, monkeypatch)
