@@ -305,6 +305,13 @@ CLUSTER_SIGNATURES = {
                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
 }
 
+# include/mlvdb_seed.h: greedy k-means++ seeding of the stored rows, the picks in order with their potentials
+SEED_MAX_TRIALS = 8
+SEED_BLOCK = 256
+SEED_SIGNATURES = {
+    "mlvdb_kmeans_seed": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(Where), _P, _P, C.POINTER(C.c_int64)]),
+}
+
 _lib = None
 
 
@@ -339,7 +346,8 @@ def load() -> C.CDLL:
                                       **MUTATE_SIGNATURES, **LIST_SIGNATURES, **SPARSE_SIGNATURES, **BITS_SIGNATURES,
                                       **BITS_RANGE_SIGNATURES, **BITS_JOIN_SIGNATURES, **HYBRID_SIGNATURES,
                                       **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES,
-                                      **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES, **CLUSTER_SIGNATURES}.items():
+                                      **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES, **CLUSTER_SIGNATURES,
+                                      **SEED_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

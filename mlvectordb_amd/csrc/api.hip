@@ -127,6 +127,9 @@ struct mlvdb_index {
     // clustering (mlvdb_cluster.h): the call's centroid labels and raw rows, the dense centroids, the per-row workspace (20 B per
     // row, 28 B for cosine k-means, and the listing's histograms), the segment table and the segment sums of one iteration
     DevBuf cl_in, cl_cent, cl_ws, cl_segs, cl_part;
+    // k-means++ seeding (mlvdb_seed.h): best and one plane per trial (8 B per row each) with the stored levels of their sum
+    // trees and of T1's, and the call's small state: the trial labels and rows, u, the outputs
+    DevBuf seed_ws, seed_io;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -5752,6 +5755,22 @@ int mlvdb_search_batch_examples(mlvdb_index* h, int32_t mode, const int64_t* exa
 // ---- clustering (mlvdb_cluster.h)
 extern "C++" {
 namespace {
+// The candidates of a clustering or seeding call: *rn = the index's norms, or a masked copy of them (NaN = no candidate) made
+// once, before anything is written.  The copy is handed to the scan as an argument: the handle's own pointers stay as they
+// are (nothing to restore on any way out), and the int8 shadow, which this family never reads, is neither refreshed nor
+// masked.
+int cluster_candidates(mlvdb_index* h, const mlvdb_where* where, const float** rn) {
+    *rn = h->rn;
+    if (!where) return MLVDB_OK;
+    if (int rc = where_run(h, where, nullptr)) return rc;
+    if (h->total > 0) {
+        HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
+        HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, h->stream));
+        *rn = h->rn_masked.as<float>();
+    }
+    return MLVDB_OK;
+}
+
 // The validated call (rn: the index's norms, or their masked copy when a program restricts the rows -- evaluated once, before
 // anything is written; the centroids' stored rows are read from h->X, which no mask touches).  The centroids staged dense (examples_stage_kernel)
 // -> per iteration: the query prep, one scan launch per tile in ascending order, the ordered member lists, ONE wait for the
@@ -5887,20 +5906,81 @@ int cluster_entry(mlvdb_index* h, const int64_t* labels, const float* vectors, i
                                            out_cost, matched, kmeans, max_iterations, out_centroids && iterations && converged);
     if (r.code != MLVDB_OK) return fail(h, r.code, r.what);
     if (int rc = check_row_limit(h, "cluster: ")) return rc;
-    // The candidates: the index's norms, or a masked copy of them (NaN = no candidate) made once, before anything is written.
-    // The copy is handed to the scan as an argument: the handle's own pointers stay as they are (nothing to restore on any
-    // way out), and the int8 shadow, which this family never reads, is neither refreshed nor masked.
-    const float* rn = h->rn;
-    if (where) {
-        if (int rc = where_run(h, where, nullptr)) return rc;
-        if (h->total > 0) {
-            HIP_TRY(h, h->rn_masked.ensure((size_t)h->capacity * sizeof(float)));
-            HIP_TRY(h, launch_mask_norms(h->rn, h->row_mask.as<uint8_t>(), h->rn_masked.as<float>(), h->total, h->capacity, h->stream));
-            rn = h->rn_masked.as<float>();
-        }
-    }
+    const float* rn = nullptr;
+    if (int rc = cluster_candidates(h, where, &rn)) return rc;
     return cluster_impl(h, rn, labels, vectors, m, kmeans, max_iterations, assign_attr, out_centroids, out_rows, out_cost,
                         iterations, converged, matched);
+}
+
+// mlvdb_kmeans_seed, validated (rn as in cluster_impl; h->total > 0).  T1's stored levels -> the one wait: the candidates
+// -> c_0 drawn -> per step: the trial rows staged dense, the query prep, one scan launch per tile of trials, the trees of the
+// planes, the pick (outputs, the next step's draws), the commit -> the outputs.
+int seed_impl(mlvdb_index* h, const float* rn, int32_t m, int32_t trials, const double* u, int64_t* out_labels,
+              double* out_potential, int64_t* matched) {
+    hipStream_t s = h->stream;
+    if (int rc = begin_call(h, s)) return rc;
+    const SeedGeometry g = seed_geometry(h->total);
+    const size_t nu = (size_t)m * trials;
+    double *planes_d = nullptr, *best_d = nullptr, *heap_d = nullptr, *heap1_d = nullptr, *u_d = nullptr, *pot_d = nullptr;
+    int64_t* lab_d = nullptr;
+    SeedState* st_d = nullptr;
+    float* rows_d = nullptr;
+    CARVE(h, h->seed_ws, [&](Carver& c) {
+        planes_d = c.take<double>((size_t)trials * g.stride);  // (first: a lane's four leaves are read as two 16-byte words)
+        best_d = c.take<double>((size_t)h->total);
+        heap_d = c.take<double>((size_t)trials * g.heap);
+        heap1_d = c.take<double>((size_t)g.heap);
+    });
+    CARVE(h, h->seed_io, [&](Carver& c) {
+        u_d = c.take<double>(nu);
+        pot_d = c.take<double>((size_t)m);
+        lab_d = c.take<int64_t>((size_t)m);
+        st_d = c.take<SeedState>(1);
+        rows_d = c.take<float>((size_t)trials * h->dim);
+    });
+    HIP_TRY(h, h->qpad.ensure((size_t)trials * h->ld * sizeof(float)));
+    HIP_TRY(h, h->qaux.ensure((size_t)trials * sizeof(double)));
+    // the candidates: the root of T1, an exact integer
+    HIP_TRY(h, launch_seed_tree(nullptr, rn, h->total, g, 1, heap1_d, s));
+    double count = 0.0;
+    if (int rc = copy_down(h, s, {{&count, 0, heap1_d + 1, 1}})) return rc;
+    *matched = (int64_t)count;
+    if (*matched < m) return fail(h, MLVDB_ERR_INVALID_ARG, "seed: fewer candidates than m");
+
+    SeedState st0{};
+    std::fill(st0.raw, st0.raw + kSeedMaxTrials, -1);
+    HIP_TRY(h, hipMemcpyAsync(st_d, &st0, sizeof st0, hipMemcpyHostToDevice, s));  // (st0 and u are read until copy_down's wait)
+    HIP_TRY(h, hipMemcpyAsync(u_d, u, nu * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_seed_pick(nullptr, nullptr, heap1_d, rn, h->total, g, 0, u_d, 1, 0, st_d, lab_d, pot_d, s));
+    SeedScanArgs a{};
+    a.X = h->X;
+    a.rn = rn;
+    a.total = h->total;
+    a.ld = h->ld;
+    a.space = h->space;
+    a.Qpad = h->qpad.as<float>();
+    a.qaux = h->qaux.as<double>();
+    a.planes = planes_d;
+    a.stride = g.stride;
+    for (int32_t j = 0; j < m; ++j) {
+        a.nslots = j == 0 ? 1 : trials;
+        a.best = j == 0 ? nullptr : best_d;
+        const int32_t qt = cluster_tile_width(h->ld, a.nslots);
+        const ExactPlan plan = plan_assign(h->total, h->ld, qt);
+        if (plan.qt != qt) return fail(h, MLVDB_ERR_INTERNAL, "seed: the scan's tile is not the width the trials were cut by");
+        HIP_TRY(h, launch_examples_stage(h->X, h->dim, h->ld, st_d->trial, st_d->raw, nullptr, a.nslots, rows_d, s));
+        HIP_TRY(h, launch_query_prep(rows_d, a.nslots, h->dim, h->ld, h->space, h->qpad.as<float>(), h->qaux.as<double>(), nullptr, s));
+        for (a.first = 0; a.first < a.nslots; a.first += plan.qt)
+            if (int rc = scan_step(h, s, h->total, [&] { return launch_seed_scan(a, plan, s); })) return rc;
+        HIP_TRY(h, launch_seed_tree(planes_d, rn, h->total, g, a.nslots, heap_d, s));
+        const bool more = j + 1 < m;
+        HIP_TRY(h, launch_seed_pick(heap_d, planes_d, heap1_d, rn, h->total, g, a.nslots, u_d + (size_t)(more ? j + 1 : 0) * trials,
+                                    more ? trials : 0, j, st_d, lab_d, pot_d, s));
+        if (more) HIP_TRY(h, launch_seed_commit(planes_d, g.stride, h->total, st_d, best_d, s));
+    }
+    h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+    if (int rc = copy_down(h, s, {{out_labels, 0, lab_d, (size_t)m}, {out_potential, 0, pot_d, (size_t)m}})) return rc;
+    return end_call(h, s);
 }
 }  // namespace
 }  // extern "C++"
@@ -5919,6 +5999,23 @@ int mlvdb_kmeans(mlvdb_index* h, const int64_t* centroid_labels, const float* ce
     return guarded(h, kOnDevice, [&]() -> int {
     return cluster_entry(h, centroid_labels, centroid_vectors, m, true, max_iterations, where, assign_attr, out_centroids,
                          out_rows, out_cost, iterations, converged, matched);
+    });
+}
+
+int mlvdb_kmeans_seed(mlvdb_index* h, int32_t m, int32_t trials, const double* u, const mlvdb_where* where,
+                      int64_t* out_labels, double* out_potential, int64_t* matched) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything is checked on the host before anything is launched (the program: where_run)
+    const ClusterRefusal r = seed_check(m, trials, u, h->space, out_labels, out_potential, matched);
+    if (r.code != MLVDB_OK) return fail(h, r.code, r.what);
+    if (int rc = check_row_limit(h, "seed: ")) return rc;
+    const float* rn = nullptr;
+    if (int rc = cluster_candidates(h, where, &rn)) return rc;
+    if (h->total == 0) {
+        *matched = 0;
+        return fail(h, MLVDB_ERR_INVALID_ARG, "seed: fewer candidates than m");
+    }
+    return seed_impl(h, rn, m, trials, u, out_labels, out_potential, matched);
     });
 }
 

@@ -1,6 +1,7 @@
 // Clustering (include/mlvdb_cluster.h), the host side that needs no device: the argument check of the two entries, the cut
 // of the m centroids into the tiles the assignment scan walks, the segment table of the blocked sums from the per-cluster
-// member counts, and the sizes of the workspace.  Plain C++ -- api.hip includes it, and so does the stand-alone program that
+// member counts, and the sizes of the workspace; below them the same for k-means++ seeding (include/mlvdb_seed.h): its
+// argument check and the geometry of its sum trees.  Plain C++ -- api.hip includes it, and so does the stand-alone program that
 // runs it under the sanitizers (tests/cpp/cluster_plan_main.cpp).
 #pragma once
 #include <stdint.h>
@@ -10,6 +11,7 @@
 
 #include "../../include/mlvdb_cluster.h"
 #include "../../include/mlvdb_hip.h"
+#include "../../include/mlvdb_seed.h"
 
 namespace mlvdb {
 
@@ -23,6 +25,10 @@ struct ClusterRefusal {
     const char* what;
 };
 
+// What mlvdb_kmeans and mlvdb_kmeans_seed (seed_check below) refuse alike, stated once.
+inline bool cluster_count_ok(int32_t m) { return m >= 1 && m <= kClusterMax; }
+constexpr ClusterRefusal kClusterNoIp = {MLVDB_ERR_UNSUPPORTED, "cluster: k-means needs l2 or cosine (no mean minimises ip)"};
+
 // Everything the two entries refuse that depends on their arguments alone (the program is where_run's).  attr_type: the
 // type of column assign_attr as the handle knows it, 0 for an undefined one (unused with assign_attr == -1).
 // kmeans: mlvdb_kmeans' extra arguments are checked too (out_centroids, iterations, converged as `kmeans_out`).
@@ -30,13 +36,13 @@ inline ClusterRefusal cluster_check(const int64_t* labels, const float* vectors,
                                     int32_t space, int32_t assign_attr, int32_t attr_type, const void* out_rows,
                                     const void* out_cost, const void* matched, bool kmeans, int32_t max_iterations,
                                     bool kmeans_out) {
-    if (m < 1 || m > kClusterMax) return {MLVDB_ERR_INVALID_ARG, "cluster: m outside 1..MLVDB_CLUSTER_MAX"};
+    if (!cluster_count_ok(m)) return {MLVDB_ERR_INVALID_ARG, "cluster: m outside 1..MLVDB_CLUSTER_MAX"};
     if (!out_rows || !out_cost || !matched || (kmeans && !kmeans_out)) return {MLVDB_ERR_INVALID_ARG, "null buffer"};
     if (kmeans) {
         if (max_iterations < 1) return {MLVDB_ERR_INVALID_ARG, "cluster: max_iterations must be >= 1"};
         if (max_iterations > MLVDB_CLUSTER_MAX_ITERATIONS)
             return {MLVDB_ERR_UNSUPPORTED, "cluster: max_iterations above MLVDB_CLUSTER_MAX_ITERATIONS"};
-        if (space == MLVDB_SPACE_IP) return {MLVDB_ERR_UNSUPPORTED, "cluster: k-means needs l2 or cosine (no mean minimises ip)"};
+        if (space == MLVDB_SPACE_IP) return kClusterNoIp;
     }
     if (assign_attr != -1) {
         if (assign_attr < 0 || assign_attr >= MLVDB_MAX_ATTRS) return {MLVDB_ERR_INVALID_ARG, "attribute index out of range"};
@@ -110,5 +116,44 @@ inline size_t cluster_workspace_bytes(int64_t total, int64_t candidates, int32_t
     b += (size_t)m * ((size_t)dim + ld) * sizeof(float);
     return b;
 }
+
+// ---- k-means++ seeding (include/mlvdb_seed.h)
+constexpr int kSeedMaxTrials = MLVDB_SEED_MAX_TRIALS;
+constexpr int kSeedBlock = MLVDB_SEED_BLOCK;  // labels of one block: its levels 1 .. 8 are rebuilt where needed, never stored
+constexpr int kSeedFan = 256;                 // nodes one workgroup of the upper-tree kernel lifts: 8 levels per launch
+
+// Everything mlvdb_kmeans_seed refuses that depends on its arguments alone (the program is where_run's; the candidate
+// count is known later).
+inline ClusterRefusal seed_check(int32_t m, int32_t trials, const double* u, int32_t space, const void* out_labels,
+                                 const void* out_potential, const void* matched) {
+    if (!cluster_count_ok(m)) return {MLVDB_ERR_INVALID_ARG, "seed: m outside 1..MLVDB_CLUSTER_MAX"};
+    if (trials < 1 || trials > kSeedMaxTrials) return {MLVDB_ERR_INVALID_ARG, "seed: trials outside 1..MLVDB_SEED_MAX_TRIALS"};
+    if (!u || !out_labels || !out_potential || !matched) return {MLVDB_ERR_INVALID_ARG, "null buffer"};
+    if (space == MLVDB_SPACE_IP) return kClusterNoIp;
+    for (int64_t i = 0; i < (int64_t)m * trials; ++i)
+        if (!(u[i] >= 0.0 && u[i] < 1.0)) return {MLVDB_ERR_INVALID_ARG, "seed: a u outside [0, 1)"};  // (a NaN fails both)
+    return {MLVDB_OK, ""};
+}
+
+// The geometry of the sum trees over `total` labels.  A tree's levels 8 .. log2 P lie in one heap of 2 blocks doubles: node
+// 1 is the root, the children of node i are 2 i and 2 i + 1, the sums of the blocks are nodes blocks .. 2 blocks - 1.
+struct SeedGeometry {
+    int64_t P;       // leaves: the smallest power of two >= max(total, kSeedBlock)
+    int64_t blocks;  // P / kSeedBlock, a power of two
+    int64_t stride;  // doubles from one plane to the next: total rounded up to 4, so a lane's four leaves are 32 B aligned
+    int64_t heap;    // doubles of one tree's stored levels
+};
+inline SeedGeometry seed_geometry(int64_t total) {
+    SeedGeometry g;
+    g.P = kSeedBlock;
+    while (g.P < total) g.P <<= 1;
+    g.blocks = g.P / kSeedBlock;
+    g.stride = (total + 3) / 4 * 4;
+    g.heap = 2 * g.blocks;
+    return g;
+}
+
+// (The workspace -- (trials + 1) (stride + heap) doubles and the call's small state, the formula of include/mlvdb_seed.h --
+// is laid out once, by the entry's CARVE lists.)
 
 }  // namespace mlvdb

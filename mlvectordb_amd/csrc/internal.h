@@ -32,6 +32,7 @@
 #include "../../include/mlvdb_examples.h"
 #include "../../include/mlvdb_join.h"
 #include "../../include/mlvdb_cluster.h"
+#include "../../include/mlvdb_seed.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -996,5 +997,41 @@ hipError_t launch_cluster_sums(const float* X, int32_t dim, int32_t ld, bool cos
                                hipStream_t s);
 // column[row] = assign[row] (INT64_MIN for -1) for every candidate row
 hipError_t launch_cluster_write(const int32_t* assign, int64_t total, int64_t* column, hipStream_t s);
+
+// ---------------------------------------------------------------- k-means++ seeding (kernels_seed.hip, include/mlvdb_seed.h)
+// The device-side state of one call: what a step's pick leaves for the launches behind it.
+struct SeedState {
+    int64_t trial[kSeedMaxTrials];  // the labels the next scan gathers its queries from (examples_stage_kernel reads them)
+    int32_t raw[kSeedMaxTrials];    // -1 each: every trial is a stored row
+    int32_t winner;                 // the plane the last pick chose: what the commit copies into `best`
+};
+// One launch of the seeding scan: trial slots [first, min(nslots, first + qt)) of the prepared batch against every row.
+struct SeedScanArgs {
+    const float* X;
+    const float* rn;     // NaN: no candidate
+    int64_t total;
+    int32_t ld;
+    int32_t space;
+    const float* Qpad;   // [nslots][ld]
+    const double* qaux;  // [nslots]
+    int32_t nslots, first;
+    const double* best;  // [total]; nullptr: +inf (step 0)
+    double* planes;      // [nslots][stride]: plane t receives p_t(x), +0.0 for a row that is no candidate
+    int64_t stride;
+};
+hipError_t launch_seed_scan(const SeedScanArgs& a, const ExactPlan& p, hipStream_t s);
+// Levels 8 .. log2 P of `nplanes` trees into their heaps (heap + p g.heap): the leaves of tree p are planes + p g.stride, or,
+// with planes == nullptr, 1.0 for every row whose rn is no NaN (T1; nplanes == 1)
+hipError_t launch_seed_tree(const double* planes, const float* rn, int64_t total, const SeedGeometry& g, int32_t nplanes,
+                            double* heap, hipStream_t s);
+// One workgroup.  nslots >= 1: the winner of the step's trees (heap, planes) by the header's rule -> out_labels[step],
+// out_potential[step], st->winner.  ndraw >= 1: st->trial[t] = draw(winner's tree, or T1's -- heap1, rn -- when its root is
+// not > 0, u[t]) for t < ndraw.  nslots == 0: the draws come from T1 (step 0's c_0).
+hipError_t launch_seed_pick(const double* heap, const double* planes, const double* heap1, const float* rn, int64_t total,
+                            const SeedGeometry& g, int32_t nslots, const double* u, int32_t ndraw, int32_t step,
+                            SeedState* st, int64_t* out_labels, double* out_potential, hipStream_t s);
+// best[x] = planes[st->winner][x] for x < total
+hipError_t launch_seed_commit(const double* planes, int64_t stride, int64_t total, const SeedState* st, double* best,
+                              hipStream_t s);
 
 }  // namespace mlvdb

@@ -960,6 +960,23 @@ class HipScanEngine:
                                            C.byref(converged), C.byref(matched)), "kmeans")
         return centroids[:m], sizes[:m], costs[:m], int(iterations.value), bool(converged.value), int(matched.value)
 
+    # -- k-means++ seeding (include/mlvdb_seed.h) --------------------------------------------
+    def kmeans_seed(self, m: int, u, *, where=None):
+        """Greedy k-means++ over the candidate rows (l2 and cosine): ``m`` picks, ``u`` float64 [m, trials] in [0, 1) the
+        random numbers of their draws -- row 0 uses ``u[0, 0]`` alone --, every step keeping the trial that leaves the
+        smallest potential, sums and draws in the order ``include/mlvdb_seed.h`` states.  Returns (labels int64 [m] in pick
+        order, potentials float64 [m], candidates)."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.ndim != 2 or u.shape[0] != int(m):
+            raise RuntimeError(f"kmeans_seed: u must be [m, trials] (got {u.shape}, m = {m})")
+        labels = np.full(max(int(m), 1), -1, dtype=np.int64)
+        potentials = np.zeros(max(int(m), 1), dtype=np.float64)
+        matched = C.c_int64(0)
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_kmeans_seed(self._h, int(m), int(u.shape[1]), _nonempty(u), w, labels.ctypes.data,
+                                                potentials.ctypes.data, C.byref(matched)), "kmeans_seed")
+        return labels[:int(m)], potentials[:int(m)], int(matched.value)
+
     # -- late-interaction search (include/mlvdb_maxsim.h) -----------------------------------
     def search_maxsim(self, tokens: np.ndarray, offsets: np.ndarray, k: int, attr: int, where=None,
                       want_matches: bool = False):

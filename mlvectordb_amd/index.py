@@ -2218,15 +2218,64 @@ class Index:
             raise ValueError(f"{what}: between 1 and {self._MAX_CLUSTERS} centroids are supported (got {c.shape[0]})")
         return c
 
+    _MAX_SEED_TRIALS = _native.SEED_MAX_TRIALS  # MLVDB_SEED_MAX_TRIALS
+
+    def _seed_trials(self, what: str, k: int, seed, trials) -> int:
+        """The refusals of a k-means++ start that need no namespace; returns the trials per step (``None``: the greedy
+        k-means++ default ``2 + floor(ln k)``, at most ``MLVDB_SEED_MAX_TRIALS``)."""
+        if not self._int_in(seed, 0):
+            raise ValueError(f"{what}: seed must be an int >= 0 (got {seed!r})")
+        if trials is None:
+            return min(self._MAX_SEED_TRIALS, 2 + int(math.floor(math.log(k))))
+        if not self._int_in(trials, 1, self._MAX_SEED_TRIALS):
+            raise ValueError(f"{what}: trials must be an int in [1, {self._MAX_SEED_TRIALS}] or None (got {trials!r})")
+        return int(trials)
+
+    def _seed_labels(self, what: str, ns: Optional[_Namespace], namespace: str, program, k: int, seed: int,
+                     trials: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(labels int64 [k] in pick order, potentials float64 [k]) of the device's greedy k-means++ over the candidates,
+        its random numbers ``np.random.default_rng(seed).random((k, 8))[:, :trials]``."""
+        live = 0 if ns is None else ns.total - ns.deleted
+        if live >= k:
+            seeder = self._engine_entry(ns, "kmeans_seed", f"{what} needs")
+            if program is not None:  # (only a filter can leave fewer candidates than live rows)
+                live = int(ns.engine.where_count(program))
+        if live < k:
+            raise ValueError(f"{what}: k = {k} centroids but only {live} candidate rows in namespace {namespace!r}")
+        u = np.random.default_rng(int(seed)).random((k, self._MAX_SEED_TRIALS))[:, :trials]
+        labels, potentials, _ = seeder(k, u, where=program)
+        return labels, potentials
+
+    def cluster_seeds(self, namespace: str, metric: str, k: int, *, where: Optional[Mapping] = None, seed: int = 0,
+                      trials: Optional[int] = None) -> Tuple[List[UUID], np.ndarray]:
+        """Additive: ``k`` stored vectors picked by greedy k-means++ on the device (include/mlvdb_seed.h) -- the start
+        ``cluster(init="k-means++")`` uses, on its own.  The first is drawn uniformly from the candidates (the live rows
+        ``where`` matches), every later one with probability proportional to its distance from the nearest pick so far --
+        the squared distance for "l2", ``1 - cos`` for "cosine" --, the best of ``trials`` draws per step (``None``:
+        ``min(8, 2 + floor(ln k))``).  Returns (ids in pick order, potentials float64 [k]: the candidates' summed distance
+        to their nearest pick after each step).  The answer depends on the stored rows and the arguments only.  Every
+        refusal is a ``ValueError``; fewer candidates than ``k`` is one."""
+        what = "cluster_seeds"
+        self._check_cluster_args(what, metric, _cluster.METRICS, where, None)
+        if not self._int_in(k, 1, self._MAX_CLUSTERS):
+            raise ValueError(f"{what}: k must be an int in [1, {self._MAX_CLUSTERS}] (got {k!r})")
+        trials = self._seed_trials(what, int(k), seed, trials)
+        program = self._program(namespace, where)
+        ns = self._cluster_namespace(what, namespace, metric)
+        labels, potentials = self._seed_labels(what, ns, namespace, program, int(k), seed, trials)
+        return ns.ids.uuids_at(labels).tolist(), potentials
+
     def cluster(self, namespace: str, metric: str, k: int, *, where: Optional[Mapping] = None, init="random", seed: int = 0,
-                max_iterations: int = 25, assign_to: Optional[str] = None) -> "_cluster.ClusterResult":
+                max_iterations: int = 25, assign_to: Optional[str] = None,
+                trials: Optional[int] = None) -> "_cluster.ClusterResult":
         """Additive: k-means over the stored rows, on the device from the rows in HBM (include/mlvdb_cluster.h) -- "which
         themes does this corpus hold", and a cluster id per row to filter, facet and diversify by.
 
         The candidates are the live rows ``where`` (one dict filter) matches.  Lloyd's algorithm runs from ``init``:
         ``"random"`` draws ``k`` distinct candidates with ``np.random.default_rng(seed)`` (passed as labels: no vector
-        crosses the bus); a sequence of ``k`` UUIDs names stored vectors; a ``[k, dim]`` array gives the centroids
-        themselves.  Every iteration assigns each candidate to its nearest centroid (the lowest one on a tie) and moves
+        crosses the bus); ``"k-means++"`` picks them by greedy k-means++ on the device (``cluster_seeds`` with the same
+        ``seed`` and ``trials``; passed as labels in pick order); a sequence of ``k`` UUIDs names stored vectors; a
+        ``[k, dim]`` array gives the centroids themselves.  Every iteration assigns each candidate to its nearest centroid (the lowest one on a tie) and moves
         every centroid to the mean of its members -- of its normalised members for "cosine"; a cluster without members
         keeps its centroid.  It stops after the first iteration >= 2 that moves no row, or after ``max_iterations``.
         ``assign_to`` names a declared ``int`` attribute that receives the cluster id of every candidate (no other row is
@@ -2243,9 +2292,12 @@ class Index:
         program = self._program(namespace, where)
         ns = self._cluster_namespace(what, namespace, metric)
         labels = vectors = None
-        if isinstance(init, str):
+        if isinstance(init, str) and init == "k-means++":
+            labels, _ = self._seed_labels(what, ns, namespace, program, k, seed, self._seed_trials(what, k, seed, trials))
+        elif isinstance(init, str):
             if init != "random":
-                raise ValueError(f'{what}: init must be "random", a sequence of ids or a [k, dim] array (got {init!r})')
+                raise ValueError(f'{what}: init must be "random", "k-means++", a sequence of ids or a [k, dim] array '
+                                 f"(got {init!r})")
             if not self._int_in(seed, 0):
                 raise ValueError(f"{what}: seed must be an int >= 0 (got {seed!r})")
             live = 0 if ns is None else ns.total - ns.deleted

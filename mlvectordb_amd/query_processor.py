@@ -499,14 +499,16 @@ class QueryProcessor:
 
     # ---- additive: clustering (Index.cluster / Index.assign_clusters)
     def cluster_vectors(self, k: int, namespace: str = "default", metric: str = "cosine", where=None, init="random",
-                        seed: int = 0, max_iterations: int = 25, assign_to: Optional[str] = None):
+                        seed: int = 0, max_iterations: int = 25, assign_to: Optional[str] = None,
+                        trials: Optional[int] = None):
         """Additive: k-means over the stored vectors of ``namespace`` (``Index.cluster``: on the device, from the rows in
         HBM).  With ``assign_to`` (a declared ``int`` attribute) every clustered vector's id goes into the index's column
         AND into the stored metadata under that key, as ``update_where`` keeps the two in step.  Returns the
         ``ClusterResult``."""
         return self._clustered("cluster_vectors", "cluster", namespace, where, assign_to,
                                lambda: self._index.cluster(namespace, metric, k, where=where, init=init, seed=seed,
-                                                           max_iterations=max_iterations, assign_to=assign_to))
+                                                           max_iterations=max_iterations, assign_to=assign_to,
+                                                           trials=trials))
 
     def assign_clusters(self, centroids, namespace: str = "default", metric: str = "cosine", assign_to: Optional[str] = None,
                         where=None):
