@@ -312,6 +312,12 @@ SEED_SIGNATURES = {
     "mlvdb_kmeans_seed": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(Where), _P, _P, C.POINTER(C.c_int64)]),
 }
 
+# include/mlvdb_project.h: bit codes computed from the stored rows (SimHash planes or thresholded signs) into a bits column
+PROJECT_SIGNATURES = {
+    "mlvdb_bits_project": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.POINTER(Where), C.POINTER(C.c_int64)]),
+    "mlvdb_bits_project_vectors": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, _P]),
+}
+
 _lib = None
 
 
@@ -347,7 +353,7 @@ def load() -> C.CDLL:
                                       **BITS_RANGE_SIGNATURES, **BITS_JOIN_SIGNATURES, **HYBRID_SIGNATURES,
                                       **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES,
                                       **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES, **CLUSTER_SIGNATURES,
-                                      **SEED_SIGNATURES}.items():
+                                      **SEED_SIGNATURES, **PROJECT_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

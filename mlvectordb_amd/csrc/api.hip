@@ -130,6 +130,8 @@ struct mlvdb_index {
     // k-means++ seeding (mlvdb_seed.h): best and one plane per trial (8 B per row each) with the stored levels of their sum
     // trees and of T1's, and the call's small state: the trial labels and rows, u, the outputs
     DevBuf seed_ws, seed_io;
+    // bit codes from rows (mlvdb_project.h): the call's padded planes and thresholds; for given vectors also these and their codes
+    DevBuf project_ws;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -6020,3 +6022,111 @@ int mlvdb_kmeans_seed(mlvdb_index* h, int32_t m, int32_t trials, const double* u
 }
 
 }  // extern "C"
+
+// ---- bit codes from the stored rows (mlvdb_project.h)
+extern "C++" {
+namespace {
+// What both entries refuse about the function itself; *words = nbits / 64.
+int project_check(mlvdb_index* h, const float* planes, int32_t nbits, const double* thresholds, int32_t* words) {
+    if (nbits < 64 || nbits % 64 != 0 || nbits / 64 > MLVDB_BITS_MAX_WORDS)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "project: nbits must be a multiple of 64 in [64, 64 * MLVDB_BITS_MAX_WORDS]");
+    if (!planes && nbits != (h->dim + 63) / 64 * 64)
+        return fail(h, MLVDB_ERR_INVALID_ARG, "project: sign mode needs nbits = dim rounded up to 64");
+    if (planes)
+        for (size_t i = 0, n = (size_t)nbits * h->dim; i < n; ++i)
+            if (!std::isfinite(planes[i])) return fail(h, MLVDB_ERR_INVALID_ARG, "project: a plane value is not finite");
+    if (thresholds)
+        for (int32_t j = 0; j < nbits; ++j)
+            if (thresholds[j] != thresholds[j]) return fail(h, MLVDB_ERR_INVALID_ARG, "project: a threshold is NaN");
+    *words = nbits / 64;
+    return MLVDB_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_bits_project(mlvdb_index* h, int32_t attr, const float* planes, int32_t nbits, const double* thresholds,
+                       const mlvdb_where* where, int64_t* matched) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything is checked on the host before anything is launched (the program: where_mask)
+    if (int rc = bits_attr_check(h, attr)) return rc;
+    int32_t words = 0;
+    if (int rc = project_check(h, planes, nbits, thresholds, &words)) return rc;
+    if (!matched) return fail(h, MLVDB_ERR_INVALID_ARG, "project: matched is null");
+    if (int rc = check_row_limit(h, "project: ")) return rc;
+    *matched = 0;
+    if (h->total == 0) return where ? where_prepare(h, where) : MLVDB_OK;
+    hipStream_t s = h->stream;
+    const uint8_t* mask = nullptr;  // the program's live matching rows, evaluated before anything is written
+    if (int rc = where_mask(h, where, &mask)) return rc;
+    if (int rc = begin_call(h, s)) return rc;
+    // the planes padded to ld, the thresholds
+    std::vector<float> ppad(planes ? (size_t)nbits * h->ld : 0, 0.f);
+    for (int32_t j = 0; planes && j < nbits; ++j)
+        std::copy(planes + (size_t)j * h->dim, planes + (size_t)(j + 1) * h->dim, ppad.begin() + (size_t)j * h->ld);
+    std::vector<double> thr((size_t)nbits, 0.0);
+    if (thresholds) std::copy(thresholds, thresholds + nbits, thr.begin());
+    double* thr_d = nullptr;
+    float* ppad_d = nullptr;
+    CARVE(h, h->project_ws, [&](Carver& c) {
+        thr_d = c.take<double>(thr.size());
+        ppad_d = c.take<float>(ppad.size());
+    });
+    if (int rc = list_pool_reserve(h, attr, h->total * words)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(thr_d, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    if (planes) HIP_TRY(h, hipMemcpyAsync(ppad_d, ppad.data(), ppad.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    ProjectArgs a{};
+    a.X = h->X;
+    a.rn = h->rn;
+    a.mask = mask;
+    a.total = h->total;
+    a.ld = h->ld;
+    a.dim = h->dim;
+    a.thr = thr_d;
+    a.words = words;
+    a.pool = h->list_pool[attr];
+    a.base = h->list_used[attr];
+    a.slots = h->attr_col[attr];
+    if (int rc = scan_step(h, s, h->total, [&] { return planes ? launch_project_planes(a, ppad_d, s) : launch_project_sign(a, s); }))
+        return rc;
+    h->list_used[attr] += h->total * words;
+    h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+    // the call's one wait: the candidate count (it also ends the reads of the host vectors)
+    unsigned long long n = (unsigned long long)(h->total - h->deleted);
+    if (where) {
+        if (int rc = copy_down(h, s, {{&n, 0, h->where_cnt.as<unsigned long long>(), 1}})) return rc;
+    } else {
+        HIP_TRY(h, hipStreamSynchronize(s));
+    }
+    *matched = (int64_t)n;
+    return end_call(h, s);
+    });
+}
+
+int mlvdb_bits_project_vectors(mlvdb_index* h, const float* vectors, int64_t n, const float* planes, int32_t nbits,
+                               const double* thresholds, uint64_t* out_codes) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    int32_t words = 0;
+    if (int rc = project_check(h, planes, nbits, thresholds, &words)) return rc;
+    if (int rc = check_nq(h, n)) return rc;
+    if (n > 0 && (!vectors || !out_codes)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (n == 0) return MLVDB_OK;
+    hipStream_t s = h->stream;
+    std::vector<double> thr((size_t)nbits, 0.0);
+    if (thresholds) std::copy(thresholds, thresholds + nbits, thr.begin());
+    const size_t np = planes ? (size_t)nbits * h->dim : 0, nv = (size_t)n * h->dim, nout = (size_t)n * words;
+    double* thr_d = nullptr;
+    uint64_t* out_d = nullptr;
+    float *planes_d = nullptr, *vec_d = nullptr;
+    CARVE(h, h->project_ws, [&](Carver& c) {
+        thr_d = c.take<double>(thr.size());
+        out_d = c.take<uint64_t>(nout);
+        planes_d = c.take<float>(np);
+        vec_d = c.take<float>(nv);
+    });
+    HIP_TRY(h, hipMemcpyAsync(thr_d, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    if (planes) HIP_TRY(h, hipMemcpyAsync(planes_d, planes, np * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(vec_d, vectors, nv * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, launch_project_vectors(vec_d, n, h->dim, planes ? planes_d : nullptr, thr_d, words, out_d, s));
+    return copy_down(h, s, {{out_codes, 0, out_d, nout}});
+    });
+}

@@ -33,6 +33,7 @@
 #include "../../include/mlvdb_join.h"
 #include "../../include/mlvdb_cluster.h"
 #include "../../include/mlvdb_seed.h"
+#include "../../include/mlvdb_project.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -1033,5 +1034,29 @@ hipError_t launch_seed_pick(const double* heap, const double* planes, const doub
 // best[x] = planes[st->winner][x] for x < total
 hipError_t launch_seed_commit(const double* planes, int64_t stride, int64_t total, const SeedState* st, double* best,
                               hipStream_t s);
+
+// ---------------------------------------------------------------- bit codes from the stored rows (kernels_project.hip, include/mlvdb_project.h)
+constexpr int kProjectPlaneTile = 64;  // planes per workgroup: one code word
+constexpr int kProjectRowBlock = 128;  // rows per workgroup: 8 panels (kTileRows is a multiple)
+// One call's write into a bits column: row r < total gets pool[base + r * words, + words) -- its code when it is a candidate
+// (rn[r] no NaN, mask == nullptr or mask[r] != 0), zeros otherwise -- and a candidate's slot becomes (that offset << 8) | words.
+struct ProjectArgs {
+    const float* X;
+    const float* rn;
+    const uint8_t* mask;
+    int64_t total;
+    int32_t ld, dim;
+    const double* thr;  // [64 * words]
+    int32_t words;
+    int64_t* pool;
+    int64_t base;
+    int64_t* slots;
+};
+// planes mode: Ppad [64 * words][ld] fp32, zero beyond dim.  grid (words, ceil(total / kProjectRowBlock))
+hipError_t launch_project_planes(const ProjectArgs& a, const float* Ppad, hipStream_t s);
+hipError_t launch_project_sign(const ProjectArgs& a, hipStream_t s);
+// n given vectors [n][dim] row-major -> out [n][words]; planes [64 * words][dim] row-major, or nullptr: sign mode
+hipError_t launch_project_vectors(const float* vectors, int64_t n, int32_t dim, const float* planes, const double* thr,
+                                  int32_t words, uint64_t* out, hipStream_t s);
 
 }  // namespace mlvdb

@@ -579,6 +579,39 @@ class HipScanEngine:
             labels.ctypes.data, dist.ctypes.data, counts.ctypes.data, dist64.ctypes.data), "search_batch_bits")
         return labels, dist, counts, dist64
 
+    # -- bit codes from the stored rows (include/mlvdb_project.h) ---------------------------
+    def _project_args(self, planes, nbits: int, thresholds):
+        """(planes float32 [nbits, dim] or ``None`` for sign mode, thresholds float64 [nbits] or ``None``), contiguous."""
+        if planes is not None:
+            planes = np.ascontiguousarray(planes, dtype=np.float32)
+            if planes.shape != (int(nbits), self.dim):
+                raise RuntimeError(f"planes must be [{nbits}, {self.dim}]; got shape {planes.shape}")
+        if thresholds is not None:
+            thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
+            if thresholds.shape != (int(nbits),):
+                raise RuntimeError(f"thresholds must be [{nbits}]; got shape {thresholds.shape}")
+        return planes, thresholds
+
+    def bits_project(self, attr: int, planes, nbits: int, thresholds=None, where=None) -> int:
+        """Every candidate row's code in bits column ``attr`` becomes bit j = ``proj(planes[j], row) > thresholds[j]``
+        (``planes=None``: sign mode, bit c = ``row[c] > thresholds[c]``), computed and written on the device in the order
+        ``include/mlvdb_project.h`` states.  Returns the candidates: the live rows ``where`` matches."""
+        planes, thresholds = self._project_args(planes, nbits, thresholds)
+        matched = C.c_int64(0)
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_bits_project(self._h, int(attr), _opt(planes), int(nbits), _opt(thresholds), w,
+                                                 C.byref(matched)), "bits_project")
+        return int(matched.value)
+
+    def bits_project_vectors(self, vectors: np.ndarray, planes, nbits: int, thresholds=None) -> np.ndarray:
+        """The same function of the given vectors float32 [n, dim], on the device: codes uint64 [n, nbits / 64]."""
+        vectors = self._queries(vectors)
+        planes, thresholds = self._project_args(planes, nbits, thresholds)
+        out = np.zeros((vectors.shape[0], max(int(nbits) // 64, 0)), dtype=np.uint64)
+        self._check(self._lib.mlvdb_bits_project_vectors(self._h, _nonempty(vectors), vectors.shape[0], _opt(planes), int(nbits),
+                                                         _opt(thresholds), _nonempty(out)), "bits_project_vectors")
+        return out
+
     def range_bits(self, attr: int, queries: np.ndarray, radius: float, metric: str = "hamming",
                    capacity: int = _native.BITS_RANGE_MAX_HITS, where=None, count_only: bool = False):
         """Range search over bit codes (``mlvdb_range_batch_bits``): per query the candidates of ``search_bits`` whose

@@ -2165,6 +2165,92 @@ class Index:
         return [ns.ids.uuids_at(np.asarray(g, dtype=np.int64)).tolist()
                 for g in _join.connected_groups(pairs.left_labels, pairs.right_labels)]
 
+    def _binarize_args(self, what: str, to, planes, seed, thresholds, dim: Optional[int]):
+        """The refusals ``binarize`` and ``binarize_queries`` share, in their order; returns (nbits, the planes float32
+        [nbits, dim] or ``None`` for sign mode, the thresholds float64 [nbits] or ``None``).  ``dim`` is the rows' -- ``None``
+        when nothing is stored yet, and then only what needs no dimensionality is checked."""
+        self._refuse_sharded(what)
+        if not _where.is_bits(self._declared(to, f"{what}: ")):
+            raise ValueError(f"{what}: attribute {to!r} is a {self._attributes[to]} column; it needs a bits attribute")
+        nbits = _where.bits_width(self._attributes[to])
+        if thresholds is not None:
+            try:
+                thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
+            except (TypeError, ValueError):
+                thresholds = np.empty(0)
+            if thresholds.shape != (nbits,) or np.isnan(thresholds).any():
+                raise ValueError(f"{what}: thresholds must be {nbits} numbers, none of them NaN")
+        if isinstance(planes, str):
+            if planes != "sign":
+                raise ValueError(f"{what}: planes must be an [N, dim] array, \"sign\" or None (got {planes!r})")
+            if dim is not None and nbits != (dim + 63) // 64 * 64:
+                raise ValueError(f"{what}: \"sign\" writes one bit per component: {to!r} must be bits{(dim + 63) // 64 * 64} "
+                                 f"for dim {dim}, not bits{nbits}")
+            return nbits, None, thresholds
+        if planes is None:
+            if not self._int_in(seed, 0):
+                raise ValueError(f"{what}: seed must be an int >= 0 (got {seed!r})")
+            if dim is not None:
+                planes = np.random.default_rng(int(seed)).standard_normal((nbits, dim)).astype(np.float32)
+            return nbits, planes, thresholds
+        try:
+            planes = np.ascontiguousarray(planes, dtype=np.float32)
+        except (TypeError, ValueError):
+            planes = np.empty(0, dtype=np.float32)
+        if planes.ndim != 2 or planes.shape[0] != nbits or (dim is not None and planes.shape[1] != dim) \
+                or not np.isfinite(planes).all():
+            raise ValueError(f"{what}: planes must be a finite [{nbits}, dim] array of the namespace's dimensionality")
+        return nbits, planes, thresholds
+
+    def binarize(self, namespace: str, to: str, *, planes=None, seed: int = 0, thresholds=None,
+                 where: Optional[Mapping] = None) -> int:
+        """Additive: the declared ``bits<N>`` attribute ``to`` of every live row ``where`` matches (``None``: every live row)
+        becomes a code computed from the row on the device (include/mlvdb_project.h); no row and no code crosses the bus.
+        ``planes`` is an ``[N, dim]`` array -- bit j is ``planes[j] . row > thresholds[j]`` (SimHash, a rotation followed by
+        a threshold) --, ``None`` for N Gaussian planes ``np.random.default_rng(seed).standard_normal((N, dim))`` as float32,
+        or ``"sign"``: bit c is ``row[c] > thresholds[c]``, and N must be dim rounded up to 64.  ``thresholds`` defaults to
+        zeros.  The filter is evaluated before anything is written, so ``{to: {"$exists": False}}`` binarises what was
+        appended since.  Returns the rows written; the stored metadata is not touched (``QueryProcessor.binarize_vectors``
+        keeps it in step).  Every refusal is a ``ValueError`` before the engine is touched."""
+        what = "binarize"
+        ns = self._ns.get(namespace)
+        nbits, planes, thresholds = self._binarize_args(what, to, planes, seed, thresholds, None if ns is None else ns.dim)
+        if callable(where) and not isinstance(where, Mapping):
+            raise ValueError(f"{what}: where must be one dict filter (a predicate has no device form)")
+        self._one_filter(what, where)
+        program = self._program(namespace, where)
+        if self._nothing_to_search(ns):
+            return 0
+        project = self._engine_entry(ns, "bits_project", f"{what} needs")
+        return int(project(self._column(to), planes, nbits, thresholds, where=program))
+
+    def binarize_queries(self, queries, to: str, *, planes=None, seed: int = 0, thresholds=None) -> np.ndarray:
+        """Additive: the codes ``binarize`` gives rows with these values, computed by the same device function: ``queries``
+        float32 ``[nq, dim]`` -> ``uint8 [nq, N / 8]``, what ``search_bits`` and its siblings take.  The arguments are
+        ``binarize``'s and must be the ones the column was written with."""
+        what = "binarize_queries"
+        q = self._coerce_queries(queries)
+        nbits, planes, thresholds = self._binarize_args(what, to, planes, seed, thresholds, q.shape[1])
+        ns = next((n for n in self._ns.values() if n.dim == q.shape[1]), None)
+        if ns is None:
+            raise ValueError(f"{what}: no namespace of dimensionality {q.shape[1]} holds an engine to compute on")
+        project = self._engine_entry(ns, "bits_project_vectors", f"{what} needs")
+        return project(q, planes, nbits, thresholds).astype("<u8").view(np.uint8).reshape(q.shape[0], nbits // 8)
+
+    def _bits_attribute_of(self, namespace: str, name: str, ids: Sequence[UUID]) -> List[Optional[bytes]]:
+        """The code of the declared bits attribute ``name`` of every stored vector in ``ids``, as the bytes the metadata
+        holds (``None``: no code, or an unknown or removed id).  For ``QueryProcessor.binarize_vectors``: the column comes
+        down in one read."""
+        ids = list(ids)
+        ns = self._ns.get(namespace)
+        if self._no_rows(ns) or not ids:
+            return [None] * len(ids)
+        labels = ns.ids.lookup(ids)
+        widths, codes = ns.engine.bits_get(self._column(name), 0, ns.total)
+        starts = np.concatenate(([0], np.cumsum(widths)))
+        return [None if l < 0 or widths[l] == 0 else codes[starts[l]:starts[l + 1]].astype("<u8").tobytes()
+                for l in labels.tolist()]
+
     def duplicate_groups(self, namespace: str, metric: str, radius: float, *, where: Optional[Mapping] = None,
                          max_per_row: int = 1024) -> List[List[UUID]]:
         """Additive: the groups of near-duplicates -- the connected components (two rows or more) of the self-join's pairs

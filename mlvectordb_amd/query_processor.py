@@ -534,6 +534,24 @@ class QueryProcessor:
             self._storage.update_metadata(vid, {assign_to: value}, namespace)
         return result
 
+    def binarize_vectors(self, to: str, namespace: str = "default", *, planes=None, seed: int = 0, thresholds=None,
+                         where=None) -> int:
+        """Additive: ``Index.binarize`` -- the bits attribute ``to`` of every stored vector matching ``where`` computed from
+        its row on the device -- with the stored metadata kept in step: the written codes are read back for the rows the call
+        changed and go into the metadata under ``to``.  Returns the rows written."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("binarize_vectors: where must be one dict filter (or None)")
+        if not hasattr(self._index, "binarize"):
+            raise ValueError("binarize_vectors needs an index with binarize")
+        if to not in (getattr(self._index, "attributes", None) or {}):
+            return self._index.binarize(namespace, to, planes=planes, seed=seed, thresholds=thresholds, where=where)  # (refused there)
+        # the candidates are the filter's matches BEFORE the call: it may read `to` itself
+        ids = self._index.query_by_metadata(namespace, where if where is not None else {})
+        written = self._index.binarize(namespace, to, planes=planes, seed=seed, thresholds=thresholds, where=where)
+        for vid, code in zip(ids, self._index._bits_attribute_of(namespace, to, ids)):
+            self._storage.update_metadata(vid, {to: code}, namespace)
+        return written
+
     # ---- additive: metadata queries (README.md:252,274: StorageEngine.query_by_metadata; no reference code)
     def count_where(self, where, namespace: str = "default") -> int:
         """Live vectors of ``namespace`` matching ``where`` (dict filter: counted on the device; predicate: over storage)."""
