@@ -318,6 +318,13 @@ PROJECT_SIGNATURES = {
     "mlvdb_bits_project_vectors": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, _P]),
 }
 
+# include/mlvdb_moments.h: the count, the column sums and the fp64 Gram matrix of the stored rows
+MOMENTS_SIGNATURES = {
+    "mlvdb_row_moments": (C.c_int, [_P, C.POINTER(Where), C.POINTER(C.c_int64), _P, _P]),
+}
+MOMENTS_SLAB = 4096      # MLVDB_MOMENTS_SLAB
+MOMENTS_MAX_DIM = 4096   # MLVDB_MOMENTS_MAX_DIM
+
 _lib = None
 
 
@@ -353,7 +360,8 @@ def load() -> C.CDLL:
                                       **BITS_RANGE_SIGNATURES, **BITS_JOIN_SIGNATURES, **HYBRID_SIGNATURES,
                                       **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES,
                                       **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES, **CLUSTER_SIGNATURES,
-                                      **SEED_SIGNATURES, **PROJECT_SIGNATURES}.items():
+                                      **SEED_SIGNATURES, **PROJECT_SIGNATURES,
+                                      **MOMENTS_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

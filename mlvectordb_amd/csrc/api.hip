@@ -132,6 +132,9 @@ struct mlvdb_index {
     DevBuf seed_ws, seed_io;
     // bit codes from rows (mlvdb_project.h): the call's padded planes and thresholds; for given vectors also these and their codes
     DevBuf project_ws;
+    // row moments (mlvdb_moments.h): one batch's slab partials (bounded by kMomentsPartialBytes, never sized by the corpus), and
+    // the result on the device: dim sums, dim * dim Gram entries
+    DevBuf moments_ws, moments_out;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -6128,5 +6131,61 @@ int mlvdb_bits_project_vectors(mlvdb_index* h, const float* vectors, int64_t n, 
     HIP_TRY(h, hipMemcpyAsync(vec_d, vectors, nv * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(h, launch_project_vectors(vec_d, n, h->dim, planes ? planes_d : nullptr, thr_d, words, out_d, s));
     return copy_down(h, s, {{out_codes, 0, out_d, nout}});
+    });
+}
+
+// ---- row moments (mlvdb_moments.h)
+int mlvdb_row_moments(mlvdb_index* h, const mlvdb_where* where, int64_t* out_count, double* out_sums, double* out_gram) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything is checked on the host before anything is launched (the program: where_mask)
+    if (!out_count || !out_sums || !out_gram) return fail(h, MLVDB_ERR_INVALID_ARG, "moments: null output");
+    if (h->dim > MLVDB_MOMENTS_MAX_DIM) return fail(h, MLVDB_ERR_UNSUPPORTED, "moments: dim above MLVDB_MOMENTS_MAX_DIM");
+    const size_t dim = (size_t)h->dim;
+    if (h->total == 0) {
+        if (where)
+            if (int rc = where_prepare(h, where)) return rc;
+        *out_count = 0;
+        std::fill(out_sums, out_sums + dim, 0.0);
+        std::fill(out_gram, out_gram + dim * dim, 0.0);
+        return MLVDB_OK;
+    }
+    hipStream_t s = h->stream;
+    const uint8_t* mask = nullptr;
+    if (int rc = where_mask(h, where, &mask)) return rc;
+    if (int rc = begin_call(h, s)) return rc;
+    MomentsArgs a{};
+    a.X = h->X;
+    a.rn = h->rn;
+    a.mask = mask;
+    a.total = h->total;
+    a.ld = h->ld;
+    a.dim = h->dim;
+    a.tiles = moments_tiles(h->ld);
+    a.npairs = moments_pairs(a.tiles);
+    const int64_t slabs = (h->total + kMomentsSlab - 1) / kMomentsSlab;
+    const int64_t batch = std::min<int64_t>(slabs, moments_batch(a.npairs));
+    CARVE(h, h->moments_ws, [&](Carver& c) {
+        a.part = c.take<double>((size_t)batch * a.npairs * kMomentsTile * kMomentsTile);
+        a.part_sums = c.take<double>((size_t)batch * a.tiles * kMomentsTile);
+    });
+    CARVE(h, h->moments_out, [&](Carver& c) {
+        a.sums = c.take<double>(dim);
+        a.gram = c.take<double>(dim * dim);
+    });
+    // batch after batch on the one stream: the tiles of its slabs, then their fold into the result in ascending slab order
+    for (a.slab0 = 0; a.slab0 < slabs; a.slab0 += batch) {
+        a.nslabs = (int32_t)std::min<int64_t>(batch, slabs - a.slab0);
+        const int64_t rows = std::min<int64_t>(h->total - a.slab0 * kMomentsSlab, (int64_t)a.nslabs * kMomentsSlab);
+        if (int rc = scan_step(h, s, rows, [&] { return launch_moments_tiles(a, s); })) return rc;
+        HIP_TRY(h, launch_moments_fold(a, a.slab0 == 0, s));
+    }
+    h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+    // the call's one wait: the count, the sums and the matrix come down together
+    unsigned long long n = (unsigned long long)(h->total - h->deleted);
+    const unsigned long long* n_d = where ? h->where_cnt.as<unsigned long long>() : nullptr;
+    if (int rc = copy_down(h, s, {{n_d ? &n : nullptr, 0, n_d, 1}, {out_sums, 0, a.sums, dim}, {out_gram, 0, a.gram, dim * dim}}))
+        return rc;
+    *out_count = (int64_t)n;
+    return end_call(h, s);
     });
 }

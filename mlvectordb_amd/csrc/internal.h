@@ -34,6 +34,7 @@
 #include "../../include/mlvdb_cluster.h"
 #include "../../include/mlvdb_seed.h"
 #include "../../include/mlvdb_project.h"
+#include "../../include/mlvdb_moments.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -1058,5 +1059,39 @@ hipError_t launch_project_sign(const ProjectArgs& a, hipStream_t s);
 // n given vectors [n][dim] row-major -> out [n][words]; planes [64 * words][dim] row-major, or nullptr: sign mode
 hipError_t launch_project_vectors(const float* vectors, int64_t n, int32_t dim, const float* planes, const double* thr,
                                   int32_t words, uint64_t* out, hipStream_t s);
+
+// ---------------------------------------------------------------- row moments (kernels_moments.hip, include/mlvdb_moments.h)
+constexpr int kMomentsTile = 128;                     // columns per strip: a workgroup owns a kMomentsTile x kMomentsTile tile
+constexpr int kMomentsSlab = MLVDB_MOMENTS_SLAB;      // rows per workgroup: one accumulator per entry runs over them
+constexpr size_t kMomentsPartialBytes = 128u << 20;   // bound of the slab partials of one batch, whatever the row count
+// One batch of slabs [slab0, slab0 + nslabs): the tile kernel leaves a tile per (slab, pair) in `part` and, from the diagonal
+// pairs, the slab's column sums in `part_sums`; the fold adds them into gram / sums in ascending slab order.  A candidate is
+// a row < total with rn[row] no NaN and (mask == nullptr or mask[row] != 0).  tiles = ceil(ld / kMomentsTile), the pairs
+// (I, J), I <= J, are numbered row by row of the upper triangle.
+struct MomentsArgs {
+    const float* X;
+    const float* rn;
+    const uint8_t* mask;
+    int64_t total;
+    int32_t ld, dim;
+    int32_t tiles, npairs;
+    int64_t slab0;
+    int32_t nslabs;
+    double* part;       // [nslabs][npairs][kMomentsTile][kMomentsTile]
+    double* part_sums;  // [nslabs][tiles * kMomentsTile]
+    double* gram;       // [dim][dim]
+    double* sums;       // [dim]
+};
+inline int32_t moments_tiles(int32_t ld) { return (ld + kMomentsTile - 1) / kMomentsTile; }
+inline int32_t moments_pairs(int32_t tiles) { return tiles * (tiles + 1) / 2; }
+// slabs per batch: as many as the bound holds, one at the least (MLVDB_MOMENTS_MAX_DIM keeps one slab inside the bound)
+inline int32_t moments_batch(int32_t npairs) {
+    const size_t per_slab = (size_t)npairs * kMomentsTile * kMomentsTile * sizeof(double);
+    return per_slab >= kMomentsPartialBytes ? 1 : (int32_t)(kMomentsPartialBytes / per_slab);
+}
+// grid (npairs * nslabs): the pair runs fastest, so the tiles of one slab run together
+hipError_t launch_moments_tiles(const MomentsArgs& a, hipStream_t s);
+// one thread per entry; `first`: the batch starts the fold from +0.0 instead of from what gram / sums hold
+hipError_t launch_moments_fold(const MomentsArgs& a, bool first, hipStream_t s);
 
 }  // namespace mlvdb

@@ -612,6 +612,16 @@ class HipScanEngine:
                                                          _opt(thresholds), _nonempty(out)), "bits_project_vectors")
         return out
 
+    # -- row moments (include/mlvdb_moments.h) ----------------------------------------------
+    def row_moments(self, program=None):
+        """(count, sums float64 [dim], gram float64 [dim, dim]) of the live rows the compiled filter matches (``None``: every
+        live row): the column sums and ``X.T @ X`` in fp64, on the device, in the order ``include/mlvdb_moments.h`` states."""
+        count = C.c_int64(0)
+        sums, gram = np.empty(self.dim, dtype=np.float64), np.empty((self.dim, self.dim), dtype=np.float64)
+        w, keep = self._where_arg(program)
+        self._check(self._lib.mlvdb_row_moments(self._h, w, C.byref(count), sums.ctypes.data, gram.ctypes.data), "row_moments")
+        return int(count.value), sums, gram
+
     def range_bits(self, attr: int, queries: np.ndarray, radius: float, metric: str = "hamming",
                    capacity: int = _native.BITS_RANGE_MAX_HITS, where=None, count_only: bool = False):
         """Range search over bit codes (``mlvdb_range_batch_bits``): per query the candidates of ``search_bits`` whose

@@ -37,6 +37,7 @@ import numpy as np
 from . import _native
 from . import cluster as _cluster
 from . import join as _join
+from . import moments as _moments
 from . import score as _score
 from . import stats as _stats
 from . import where as _where
@@ -2236,6 +2237,41 @@ class Index:
             raise ValueError(f"{what}: no namespace of dimensionality {q.shape[1]} holds an engine to compute on")
         project = self._engine_entry(ns, "bits_project_vectors", f"{what} needs")
         return project(q, planes, nbits, thresholds).astype("<u8").view(np.uint8).reshape(q.shape[0], nbits // 8)
+
+    def moments(self, namespace: str, where: Optional[Mapping] = None) -> Tuple[int, np.ndarray, np.ndarray]:
+        """Additive: (count, sums float64 [dim], gram float64 [dim, dim]) of the live rows ``where`` (one dict filter; ``None``:
+        every live row) matches -- the column sums and ``X.T @ X`` of the stored fp32 rows in fp64, computed on the device in
+        the order include/mlvdb_moments.h states; no row crosses the bus.  Means, variances, the covariance, whitening and
+        ``pca`` follow from them on the host.  Every refusal is a ``ValueError`` before the engine is touched."""
+        return self._moments("moments", namespace, where)
+
+    def _moments(self, what: str, namespace: str, where):
+        self._refuse_sharded(what)
+        if callable(where) and not isinstance(where, Mapping):
+            raise ValueError(f"{what}: where must be one dict filter (a predicate has no device form)")
+        self._one_filter(what, where)
+        program = self._program(namespace, where)
+        ns = self._ns.get(namespace)
+        if ns is None:
+            raise ValueError(f"{what}: namespace {namespace!r} holds no rows")
+        return self._engine_entry(ns, "row_moments", f"{what} needs")(program)
+
+    def pca(self, namespace: str, n_components: int, where: Optional[Mapping] = None,
+            center: bool = True) -> "_moments.PcaResult":
+        """Additive: the ``n_components`` principal axes of the live rows ``where`` matches, from ``moments`` (on the device)
+        and one ``dim x dim`` eigen-decomposition on the host (``moments.pca_from_moments``).  With the result ``p``,
+        ``binarize(namespace, to, planes=p.components[:N], thresholds=p.thresholds[:N])`` writes centred PCA-sign codes
+        with no row crossing the bus, ``binarize_queries`` with the same arguments gives queries theirs, and
+        ``p.transform(vectors)`` maps vectors onto the axes on the host.  ``n_components`` outside 1..dim, fewer than two
+        candidates when centred (one otherwise), an unknown namespace, a ``where`` that is no dict filter or a row-sharded
+        index is a ``ValueError``."""
+        what = "pca"
+        self._refuse_sharded(what)
+        ns = self._ns.get(namespace)
+        if ns is not None and not self._int_in(n_components, 1, ns.dim):
+            raise ValueError(f"{what}: n_components must be an int in [1, {ns.dim}] (got {n_components!r})")
+        count, sums, gram = self._moments(what, namespace, where)
+        return _moments.pca_from_moments(count, sums, gram, n_components, center=bool(center))
 
     def _bits_attribute_of(self, namespace: str, name: str, ids: Sequence[UUID]) -> List[Optional[bytes]]:
         """The code of the declared bits attribute ``name`` of every stored vector in ``ids``, as the bytes the metadata

@@ -552,6 +552,15 @@ class QueryProcessor:
             self._storage.update_metadata(vid, {to: code}, namespace)
         return written
 
+    def fit_pca(self, n_components: int, namespace: str = "default", *, where=None, center: bool = True):
+        """Additive: ``Index.pca`` -- the principal axes of the stored vectors matching ``where``, from moments taken on the
+        device.  A dict ``where`` goes to the device; a predicate has no device form and is refused."""
+        if where is not None and not isinstance(where, Mapping):
+            raise ValueError("fit_pca: where must be one dict filter (or None)")
+        if not hasattr(self._index, "pca"):
+            raise ValueError("fit_pca needs an index with pca")
+        return self._index.pca(namespace, n_components, where=where, center=center)
+
     # ---- additive: metadata queries (README.md:252,274: StorageEngine.query_by_metadata; no reference code)
     def count_where(self, where, namespace: str = "default") -> int:
         """Live vectors of ``namespace`` matching ``where`` (dict filter: counted on the device; predicate: over storage)."""
