@@ -325,6 +325,14 @@ MOMENTS_SIGNATURES = {
 MOMENTS_SLAB = 4096      # MLVDB_MOMENTS_SLAB
 MOMENTS_MAX_DIM = 4096   # MLVDB_MOMENTS_MAX_DIM
 
+# include/mlvdb_transform.h: linear maps of the stored rows, appended to another index or copied down
+TRANSFORM_MAX_OUT = 4096  # MLVDB_TRANSFORM_MAX_OUT
+TRANSFORM_SIGNATURES = {
+    "mlvdb_rows_transform": (C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(Where), _P, C.c_int64, _P, _P,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mlvdb_rows_transform_vectors": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, _P]),
+}
+
 _lib = None
 
 
@@ -361,7 +369,7 @@ def load() -> C.CDLL:
                                       **GEO_SIGNATURES, **STATS_SIGNATURES, **SCORE_SIGNATURES,
                                       **EXAMPLES_SIGNATURES, **JOIN_SIGNATURES, **CLUSTER_SIGNATURES,
                                       **SEED_SIGNATURES, **PROJECT_SIGNATURES,
-                                      **MOMENTS_SIGNATURES}.items():
+                                      **MOMENTS_SIGNATURES, **TRANSFORM_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = restype
         fn.argtypes = argtypes

@@ -135,6 +135,9 @@ struct mlvdb_index {
     // row moments (mlvdb_moments.h): one batch's slab partials (bounded by kMomentsPartialBytes, never sized by the corpus), and
     // the result on the device: dim sums, dim * dim Gram entries
     DevBuf moments_ws, moments_out;
+    // linear maps of rows (mlvdb_transform.h): the call's padded matrix, shift and flag word; for given vectors also these and
+    // their images.  (The images of the stored rows live in a buffer of the call itself.)
+    DevBuf transform_ws;
     // facets (mlvdb_facet.h): the global value table + its packed copy, sized by the call's max_values; counters, bin edges and
     // bin counts -- never sized by the corpus
     DevBuf facet_tab, facet_misc;
@@ -1386,8 +1389,11 @@ int mlvdb_index_destroy(mlvdb_index* h) {
     });
 }
 
-int mlvdb_index_append_device(mlvdb_index* h, const float* rows_device, int64_t n, int64_t* first_label) {
-    return guarded(h, kOnDevice, [&]() -> int {
+extern "C++" {
+namespace {
+// n dense rows [n][dim] that are resident on h's device -> its labels *first_label ..: scatter, norms, shadow, row statistics.
+// (mlvdb_index_append_device, and the sink of mlvdb_rows_transform.)
+int append_device_rows(mlvdb_index* h, const float* rows_device, int64_t n, int64_t* first_label) {
     if (n < 0 || (n > 0 && !rows_device)) return fail(h, MLVDB_ERR_INVALID_ARG, "bad rows / n");
     if (h->total + n > 0x7fffff00ll) return fail(h, MLVDB_ERR_UNSUPPORTED, "more than 2^31 rows per index");
     if (first_label) *first_label = h->total;
@@ -1401,7 +1407,12 @@ int mlvdb_index_append_device(mlvdb_index* h, const float* rows_device, int64_t 
     commit_row_stats(h);
     h->total += n;
     return MLVDB_OK;
-    });
+}
+}  // namespace
+}  // extern "C++"
+
+int mlvdb_index_append_device(mlvdb_index* h, const float* rows_device, int64_t n, int64_t* first_label) {
+    return guarded(h, kOnDevice, [&]() -> int { return append_device_rows(h, rows_device, n, first_label); });
 }
 
 int mlvdb_index_append(mlvdb_index* h, const float* rows, int64_t n, int64_t* first_label) {
@@ -6187,5 +6198,143 @@ int mlvdb_row_moments(mlvdb_index* h, const mlvdb_where* where, int64_t* out_cou
         return rc;
     *out_count = (int64_t)n;
     return end_call(h, s);
+    });
+}
+
+// ---- linear maps of the stored rows (mlvdb_transform.h)
+namespace {
+// What both entries refuse about the function itself.
+int transform_check(mlvdb_index* h, const float* matrix, int32_t out_dim, const double* shift) {
+    if (out_dim < 1 || out_dim > MLVDB_TRANSFORM_MAX_OUT)
+        return fail(h, MLVDB_ERR_UNSUPPORTED, "transform: out_dim must be in 1 .. MLVDB_TRANSFORM_MAX_OUT");
+    if (!matrix) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: matrix is null");
+    for (size_t i = 0, n = (size_t)out_dim * h->dim; i < n; ++i)
+        if (!std::isfinite(matrix[i])) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: a matrix value is not finite");
+    for (int32_t j = 0; shift && j < out_dim; ++j)
+        if (!std::isfinite(shift[j])) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: a shift value is not finite");
+    return MLVDB_OK;
+}
+
+const char* const kTransformNotFinite = "transform: a transformed value is not finite";
+}  // namespace
+
+int mlvdb_rows_transform(mlvdb_index* h, const float* matrix, int32_t out_dim, const double* shift, const mlvdb_where* where,
+                         mlvdb_index* dst, int64_t capacity, float* out_rows, int64_t* out_labels, int64_t* matched,
+                         int64_t* first_label) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    // everything the host can know is checked before anything is launched (the program: where_run)
+    if (int rc = transform_check(h, matrix, out_dim, shift)) return rc;
+    if (!matched) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: matched is null");
+    if (!dst && !out_rows) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: neither dst nor out_rows is given");
+    if (capacity < 0) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: capacity < 0");
+    if (dst == h) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: dst is the source index");
+    if (dst && dst->device != h->device) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: dst lives on another device");
+    if (dst && dst->dim != out_dim) return fail(h, MLVDB_ERR_INVALID_ARG, "transform: dst's dim is not out_dim");
+    if (int rc = check_row_limit(h, "transform: ")) return rc;
+    hipStream_t s = h->stream;
+    // the candidates as ascending labels (nullptr: the identity -- no filter, no tombstone)
+    int64_t m = h->total - h->deleted;
+    const int32_t* labels = nullptr;
+    if (where) {
+        if (int rc = where_run(h, where, &m)) return rc;
+        if (m > 0) {
+            if (int rc = mask_labels(h, m)) return rc;
+            labels = h->labels_in.as<int32_t>();
+        }
+    } else if (h->deleted > 0 && m > 0) {
+        HIP_TRY(h, h->partial.ensure((size_t)((h->total + 1023) / 1024) * sizeof(uint32_t) + 64));
+        HIP_TRY(h, h->labels_in.ensure((size_t)m * sizeof(int32_t)));
+        HIP_TRY(h, launch_compact_map(h->rn, h->total, h->partial.as<uint32_t>(), h->counters.as<unsigned long long>(),
+                                      h->labels_in.as<int32_t>(), s));
+        labels = h->labels_in.as<int32_t>();
+    }
+    *matched = m;
+    if ((out_rows || out_labels) && m > capacity) return fail(h, MLVDB_ERR_OVERFLOW, "transform: more candidates than capacity");
+    if (dst && dst->total + m > 0x7fffff00ll) return fail(h, MLVDB_ERR_UNSUPPORTED, "more than 2^31 rows per index");
+    if (m == 0) {
+        if (dst && first_label) *first_label = dst->total;
+        return MLVDB_OK;
+    }
+    if (int rc = begin_call(h, s)) return rc;
+    // the matrix padded to ld and to whole column tiles, the shift
+    const size_t cols = (size_t)((out_dim + kTransformColTile - 1) / kTransformColTile) * kTransformColTile;
+    std::vector<float> mpad(cols * h->ld, 0.f);
+    for (int32_t j = 0; j < out_dim; ++j)
+        std::copy(matrix + (size_t)j * h->dim, matrix + (size_t)(j + 1) * h->dim, mpad.begin() + (size_t)j * h->ld);
+    std::vector<double> sh(cols, 0.0);
+    if (shift) std::copy(shift, shift + out_dim, sh.begin());
+    TransformArgs a{};
+    double* sh_d = nullptr;
+    float* mpad_d = nullptr;
+    CARVE(h, h->transform_ws, [&](Carver& c) {
+        sh_d = c.take<double>(sh.size());
+        mpad_d = c.take<float>(mpad.size());
+        a.flag = c.take<uint32_t>(1);
+    });
+    // the whole result stays here until the flag has been read: one append at the end, all or nothing
+    Staged<DevBuf> res(s);
+    if (hipError_t e = res.exact((size_t)m * out_dim * sizeof(float)); e != hipSuccess)
+        return fail(h, MLVDB_ERR_OUT_OF_MEMORY, "transform: allocating the result", e);
+    HIP_TRY(h, hipMemcpyAsync(sh_d, sh.data(), sh.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(mpad_d, mpad.data(), mpad.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(a.flag, 0, sizeof(uint32_t), s));
+    a.X = h->X;
+    a.labels = labels;
+    a.matched = m;
+    a.ld = h->ld;
+    a.out_dim = out_dim;
+    a.Mpad = mpad_d;
+    a.shift = sh_d;
+    a.out = res.as<float>();
+    if (int rc = scan_step(h, s, m, [&] { return launch_transform_tiles(a, s); })) return rc;
+    h->stats.strategy_used = MLVDB_STRATEGY_EXACT;
+    uint32_t flag = 0;
+    if (int rc = copy_down(h, s, {{&flag, 0, a.flag, 1}})) return rc;
+    if (flag) return fail(h, MLVDB_ERR_INVALID_ARG, kTransformNotFinite);
+    if (dst) {
+        if (int rc = append_device_rows(dst, res.as<float>(), m, first_label)) {
+            h->err = "transform: appending to dst: " + dst->err;
+            return rc;
+        }
+    }
+    std::vector<int32_t> lab32(out_labels && labels ? (size_t)m : 0);
+    if (int rc = copy_down(h, s, {{out_rows, 0, res.as<float>(), (size_t)m * out_dim},
+                                  {lab32.empty() ? nullptr : lab32.data(), 0, labels, (size_t)m}}))
+        return rc;
+    for (int64_t i = 0; out_labels && i < m; ++i) out_labels[i] = labels ? lab32[(size_t)i] : i;
+    return end_call(h, s);
+    });
+}
+
+int mlvdb_rows_transform_vectors(mlvdb_index* h, const float* vectors, int64_t n, const float* matrix, int32_t out_dim,
+                                 const double* shift, float* out) {
+    return guarded(h, kOnDevice, [&]() -> int {
+    if (int rc = transform_check(h, matrix, out_dim, shift)) return rc;
+    if (int rc = check_nq(h, n)) return rc;
+    if (n > 0 && (!vectors || !out)) return fail(h, MLVDB_ERR_INVALID_ARG, "null buffer");
+    if (n == 0) return MLVDB_OK;
+    hipStream_t s = h->stream;
+    std::vector<double> sh((size_t)out_dim, 0.0);
+    if (shift) std::copy(shift, shift + out_dim, sh.begin());
+    const size_t nm = (size_t)out_dim * h->dim, nv = (size_t)n * h->dim, nout = (size_t)n * out_dim;
+    double* sh_d = nullptr;
+    float *matrix_d = nullptr, *vec_d = nullptr, *out_d = nullptr;
+    uint32_t* flag_d = nullptr;
+    CARVE(h, h->transform_ws, [&](Carver& c) {
+        sh_d = c.take<double>(sh.size());
+        matrix_d = c.take<float>(nm);
+        vec_d = c.take<float>(nv);
+        out_d = c.take<float>(nout);
+        flag_d = c.take<uint32_t>(1);
+    });
+    HIP_TRY(h, hipMemcpyAsync(sh_d, sh.data(), sh.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(matrix_d, matrix, nm * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(vec_d, vectors, nv * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(flag_d, 0, sizeof(uint32_t), s));
+    HIP_TRY(h, launch_transform_vectors(vec_d, n, h->dim, matrix_d, sh_d, out_dim, out_d, flag_d, s));
+    uint32_t flag = 0;
+    if (int rc = copy_down(h, s, {{&flag, 0, flag_d, 1}})) return rc;
+    if (flag) return fail(h, MLVDB_ERR_INVALID_ARG, kTransformNotFinite);
+    return copy_down(h, s, {{out, 0, out_d, nout}});
     });
 }

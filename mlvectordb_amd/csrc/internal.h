@@ -35,6 +35,7 @@
 #include "../../include/mlvdb_seed.h"
 #include "../../include/mlvdb_project.h"
 #include "../../include/mlvdb_moments.h"
+#include "../../include/mlvdb_transform.h"
 #include "layout.h"
 #include "wave_topk.h"
 #include "wave_topk_distinct.h"
@@ -1093,5 +1094,27 @@ inline int32_t moments_batch(int32_t npairs) {
 hipError_t launch_moments_tiles(const MomentsArgs& a, hipStream_t s);
 // one thread per entry; `first`: the batch starts the fold from +0.0 instead of from what gram / sums hold
 hipError_t launch_moments_fold(const MomentsArgs& a, bool first, hipStream_t s);
+
+// ---------------------------------------------------------------- linear maps of the stored rows (kernels_transform.hip, include/mlvdb_transform.h)
+constexpr int kTransformColTile = 64;    // output columns per workgroup
+constexpr int kTransformRowBlock = 128;  // candidates per workgroup
+// out [matched][out_dim] = (float)(proj(Mpad[j], row labels[i]) - shift[j]), dense in candidate order.  labels: `matched`
+// ascending row labels, or nullptr for the identity (no filter, no tombstone).  Mpad [tiles * 64][ld] fp32 and shift
+// [tiles * 64] are zero beyond dim / out_dim, tiles = ceil(out_dim / 64).  *flag becomes 1 when a value of a candidate is not
+// finite in fp32 (a plain store: every writer stores the same word); the caller clears it first.
+struct TransformArgs {
+    const float* X;
+    const int32_t* labels;
+    int64_t matched;
+    int32_t ld, out_dim;
+    const float* Mpad;
+    const double* shift;
+    float* out;
+    uint32_t* flag;
+};
+hipError_t launch_transform_tiles(const TransformArgs& a, hipStream_t s);
+// n given vectors [n][dim] row-major -> out [n][out_dim]; matrix [out_dim][dim] row-major, shift [out_dim]
+hipError_t launch_transform_vectors(const float* vectors, int64_t n, int32_t dim, const float* matrix, const double* shift,
+                                    int32_t out_dim, float* out, uint32_t* flag, hipStream_t s);
 
 }  // namespace mlvdb

@@ -622,6 +622,45 @@ class HipScanEngine:
         self._check(self._lib.mlvdb_row_moments(self._h, w, C.byref(count), sums.ctypes.data, gram.ctypes.data), "row_moments")
         return int(count.value), sums, gram
 
+    # -- linear maps of the stored rows (include/mlvdb_transform.h) ----------------------------
+    def _transform_args(self, matrix, shift):
+        matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+        if matrix.ndim != 2 or matrix.shape[1] != self.dim:
+            raise RuntimeError(f"matrix must be [out_dim, {self.dim}]; got shape {matrix.shape}")
+        if shift is not None:
+            shift = np.ascontiguousarray(shift, dtype=np.float64)
+            if shift.shape != (matrix.shape[0],):
+                raise RuntimeError(f"shift must be [{matrix.shape[0]}]; got shape {shift.shape}")
+        return matrix, shift
+
+    def rows_transform(self, matrix, shift=None, where=None, dst: "HipScanEngine | None" = None, want_rows: bool = True):
+        """``(float)(proj(matrix[j], row) - shift[j])`` of every candidate row (the live rows ``where`` matches, ascending
+        label), computed on the device in the order ``include/mlvdb_transform.h`` states.  ``dst``: the images are appended
+        to that engine (same device, dim = out_dim) without crossing the bus.  Returns (labels int64 [matched], rows float32
+        [matched, out_dim] or ``None`` without ``want_rows``, the first label in ``dst`` or -1)."""
+        matrix, shift = self._transform_args(matrix, shift)
+        total, deleted = self.counts()
+        cap = max(total - deleted, 1)
+        labels = np.empty(cap, dtype=np.int64)
+        rows = np.empty((cap, matrix.shape[0]), dtype=np.float32) if want_rows else None
+        matched, first = C.c_int64(0), C.c_int64(-1)
+        w, keep = self._where_arg(where)
+        self._check(self._lib.mlvdb_rows_transform(self._h, matrix.ctypes.data, matrix.shape[0], _opt(shift), w,
+                                                   None if dst is None else dst._h, cap, _opt(rows), labels.ctypes.data,
+                                                   C.byref(matched), C.byref(first)), "rows_transform")
+        n = int(matched.value)
+        return labels[:n], None if rows is None else rows[:n], int(first.value)
+
+    def rows_transform_vectors(self, vectors: np.ndarray, matrix, shift=None) -> np.ndarray:
+        """The same function of the given vectors float32 [n, dim], on the device: float32 [n, out_dim]."""
+        vectors = self._queries(vectors)
+        matrix, shift = self._transform_args(matrix, shift)
+        out = np.zeros((vectors.shape[0], matrix.shape[0]), dtype=np.float32)
+        self._check(self._lib.mlvdb_rows_transform_vectors(self._h, _nonempty(vectors), vectors.shape[0], matrix.ctypes.data,
+                                                           matrix.shape[0], _opt(shift), _nonempty(out)),
+                    "rows_transform_vectors")
+        return out
+
     def range_bits(self, attr: int, queries: np.ndarray, radius: float, metric: str = "hamming",
                    capacity: int = _native.BITS_RANGE_MAX_HITS, where=None, count_only: bool = False):
         """Range search over bit codes (``mlvdb_range_batch_bits``): per query the candidates of ``search_bits`` whose

@@ -42,7 +42,7 @@ from . import score as _score
 from . import stats as _stats
 from . import where as _where
 from .engine import FacetOverflow, HipScanEngine, JoinOverflow, ScanEngine, StatsOverflow
-from .idtable import IdTable, mint_uuid4_bytes
+from .idtable import IdTable, mint_uuid4_bytes, uuids_to_bytes
 from .interfaces import VectorDTO, VectorProtocol
 
 _SPACE_ALIASES = {"l2": "l2", "cosine": "cosine", "ip": "ip", "euclidean": "l2"}
@@ -2262,7 +2262,9 @@ class Index:
         and one ``dim x dim`` eigen-decomposition on the host (``moments.pca_from_moments``).  With the result ``p``,
         ``binarize(namespace, to, planes=p.components[:N], thresholds=p.thresholds[:N])`` writes centred PCA-sign codes
         with no row crossing the bus, ``binarize_queries`` with the same arguments gives queries theirs, and
-        ``p.transform(vectors)`` maps vectors onto the axes on the host.  ``n_components`` outside 1..dim, fewer than two
+        ``p.transform(vectors)`` maps vectors onto the axes on the host;
+        ``transform(namespace, p.components, shift=p.thresholds, to="ns_pca")`` writes the reduced rows into a searchable
+        namespace on the device.  ``n_components`` outside 1..dim, fewer than two
         candidates when centred (one otherwise), an unknown namespace, a ``where`` that is no dict filter or a row-sharded
         index is a ``ValueError``."""
         what = "pca"
@@ -2272,6 +2274,93 @@ class Index:
             raise ValueError(f"{what}: n_components must be an int in [1, {ns.dim}] (got {n_components!r})")
         count, sums, gram = self._moments(what, namespace, where)
         return _moments.pca_from_moments(count, sums, gram, n_components, center=bool(center))
+
+    def _transform_args(self, what: str, matrix, shift, dim: int):
+        """The refusals ``transform`` and ``transform_queries`` share -> (matrix float32 [out_dim, dim], shift float64
+        [out_dim] or ``None``)."""
+        self._refuse_sharded(what)
+        try:
+            matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+        except (TypeError, ValueError):
+            matrix = np.empty(0, dtype=np.float32)
+        if matrix.ndim != 2 or matrix.shape[1] != dim or not 1 <= matrix.shape[0] <= _native.TRANSFORM_MAX_OUT \
+                or not np.isfinite(matrix).all():
+            raise ValueError(f"{what}: matrix must be a finite [out_dim, {dim}] array with out_dim in "
+                             f"[1, {_native.TRANSFORM_MAX_OUT}]")
+        if shift is not None:
+            try:
+                shift = np.ascontiguousarray(shift, dtype=np.float64)
+            except (TypeError, ValueError):
+                shift = np.empty(0)
+            if shift.shape != (matrix.shape[0],) or not np.isfinite(shift).all():
+                raise ValueError(f"{what}: shift must be {matrix.shape[0]} finite numbers")
+        return matrix, shift
+
+    def transform(self, namespace: str, matrix, *, shift=None, where: Optional[Mapping] = None, to: Optional[str] = None):
+        """Additive: the linear map ``matrix @ row - shift`` of every live row ``where`` matches (``None``: every live row),
+        computed on the device in the order include/mlvdb_transform.h states.  ``to=None`` returns ``(ids, float32 [count,
+        out_dim])`` in insertion order -- a 2-D map of the corpus.  ``to="name"`` appends the images to namespace ``to``
+        under the *same ids* without a row crossing the bus and returns their number: ``to`` is created with ``dim =
+        out_dim`` and the index's space when it does not exist, must differ from ``namespace``, must have dim ``out_dim`` and
+        must hold none of the candidates' ids; the attribute columns of the new rows stay absent.  With ``p = pca(...)``,
+        ``transform(ns, p.components, shift=p.thresholds, to="ns_pca")`` is the reduced copy and ``transform_queries`` maps
+        the queries.  A row-sharded index, a ``where`` that is no dict filter, a matrix of another shape or with non-finite
+        values, a shift of another length, an unknown namespace or an id conflict is a ``ValueError`` before the engine
+        computes anything; a transformed value that is not finite in fp32 is the engine's ``RuntimeError`` and leaves both
+        namespaces as they were."""
+        what = "transform"
+        self._refuse_sharded(what)
+        ns = self._ns.get(namespace)
+        if ns is None:
+            raise ValueError(f"{what}: namespace {namespace!r} holds no rows")
+        matrix, shift = self._transform_args(what, matrix, shift, ns.dim)
+        if callable(where) and not isinstance(where, Mapping):
+            raise ValueError(f"{what}: where must be one dict filter (a predicate has no device form)")
+        self._one_filter(what, where)
+        program = self._program(namespace, where)
+        out_dim = matrix.shape[0]
+        dst = None
+        if to is not None:
+            if not isinstance(to, str) or to == namespace:
+                raise ValueError(f"{what}: to must name another namespace than {namespace!r} (got {to!r})")
+            dst = self._ns.get(to)
+            if dst is not None and dst.dim != out_dim:
+                raise ValueError(f"{what}: namespace {to!r} has dim {dst.dim}, the matrix maps to {out_dim}")
+            if dst is not None and dst.total > 0:
+                if where is None:
+                    raw = ns.ids.raw[:ns.total][ns.ids.live[:ns.total]]
+                else:
+                    raw = uuids_to_bytes(self.query_by_metadata(namespace, where))
+                if (dst.ids.lookup_raw(raw) >= 0).any():
+                    raise ValueError(f"{what}: namespace {to!r} already holds ids of the rows to transform")
+        run = self._engine_entry(ns, "rows_transform", f"{what} needs")
+        if to is None:
+            labels, rows, _ = run(matrix, shift, where=program)
+            return ns.ids.uuids_at(labels), rows
+        created = dst is None
+        dst = self._get_or_create(to, out_dim, self._space)
+        try:
+            labels, _, first = run(matrix, shift, where=program, dst=dst.engine, want_rows=False)
+        except Exception:
+            if created:
+                self._ns.pop(to).engine.close()
+            raise
+        if first != dst.total or dst.ids.append_raw(ns.ids.raw[labels], ns.ids.handles[labels]) != first:
+            raise RuntimeError(f"engine label base {first} != host row count {dst.total}")
+        dst.total += int(labels.size)
+        return int(labels.size)
+
+    def transform_queries(self, queries, matrix, *, shift=None) -> np.ndarray:
+        """Additive: the images ``transform`` gives rows with these values, computed by the same device function:
+        ``queries`` float32 ``[nq, dim]`` -> float32 ``[nq, out_dim]``, the queries of the namespace ``transform(..., to=)``
+        filled.  A stored row, given as a query, finds its own image at distance 0."""
+        what = "transform_queries"
+        q = self._coerce_queries(queries)
+        matrix, shift = self._transform_args(what, matrix, shift, q.shape[1])
+        ns = next((n for n in self._ns.values() if n.dim == q.shape[1]), None)
+        if ns is None:
+            raise ValueError(f"{what}: no namespace of dimensionality {q.shape[1]} holds an engine to compute on")
+        return self._engine_entry(ns, "rows_transform_vectors", f"{what} needs")(q, matrix, shift)
 
     def _bits_attribute_of(self, namespace: str, name: str, ids: Sequence[UUID]) -> List[Optional[bytes]]:
         """The code of the declared bits attribute ``name`` of every stored vector in ``ids``, as the bytes the metadata
